@@ -9,21 +9,30 @@ One step = one pass of the hot path over one synthetic frame: K0 light view tran
 over the per-tile lists (BASELINE.json configs[2]: 4K, 65 536 point+spot lights, synthetic G-buffer/surface tiles), with
 every input already resident in HBM.  With N > 1 the step is ONE frame cut into N cost-balanced tile-row bands, one band per
 rank (BASELINE.json's multi-GPU metric, SURVEY.md 8e: strong scaling; cull + shade need no collective), and
-`value` = W*H*K / max-over-ranks(time); after the timed steps the band lists are exchanged once through the SHIPPED exchange --
+`value` = W*H*K / max-over-ranks(time); with --full, after the timed steps the band lists are exchanged once through the SHIPPED exchange --
 sailor_hip_exchange_light_lists_rows (exchange.hip: three ncclAllGather on an ncclComm_t of the job's ranks + one stitch kernel), the
 call HipGraphicsDriver::ExchangeLightLists makes -- and the stitched global buffers are summarised by a checksum, so the distributed
-path is exercised end to end (`--exchange-every-step` puts the exchange inside the timed region).  The same invocation also measures
+path is exercised end to end (`--exchange-every-step` puts the exchange inside the timed region).  The same invocation with --full also measures
 the other way of using N GPUs -- every rank renders whole frames of its own -- and reports it as `alternate_frame_rendering`, together
 with `speedup_vs_one_gpu_whole_frame` = that whole-frame step time / the split step time.  `--frame-per-gpu` swaps the roles.
 
 Lights: static (the prepared views derived once, outside the timed region) or dynamic (every light dirty every frame: the
-preparation of all N lights inside every step).  C5 ("1 M dynamic lights") is quoted dynamic, the others static; the line always
-carries both step times (`value_dynamic_lights` / `ms_per_step_dynamic`, resp. `..._static`) and `lights.mode` says which is `value`.
+preparation of all N lights inside every step).  C5 ("1 M dynamic lights") is quoted dynamic, the others static; `lights.mode` says which
+is `value`, and a --full line carries both step times (`value_dynamic_lights` / `ms_per_step_dynamic`, resp. `..._static`).
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (k2_shade): algorithmic bytes per launch
-/ its launch duration read DIRECTLY: one HIP event pair around every launch, each launch between its real neighbours
-(kernel_in_frame_ms).  `cpu_baseline` = the CPU oracle (a port: the reference cannot be built here) timed on a bounded
-sample of the same workload on this box's host cores.
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: set-up, spin-up and W warm-up steps, the K timed steps, the
+line (`metric`, `value`, `unit`, `ms_per_step`, `higher_is_better`, `dtype`, the configuration and the launch form).  Everything else this
+file measures or checks runs only with `--full`: the per-step distribution, the other light mode, the serial (one frame in flight) step,
+the per-kernel figures and the roofline, the box's copy probe, the list statistics, the exchange and the other multi-GPU mode of N > 1
+runs, the split readings of other configurations, K4 across the ranks, and the CPU baseline with the side blocks (ECS sweep, mesh cull,
+linearize, ambient, blur, IBL pre-filter, shadow passes).  `roofline` is for the dominant kernel (k2_shade): algorithmic bytes per launch
+ / its launch duration read DIRECTLY: one HIP event pair around every launch, each launch between its real neighbours
+(kernel_in_frame_ms).  `cpu_baseline` = the CPU oracle (a port: the reference cannot be built here) timed on a bounded sample of the same
+workload on this box's host cores.
+
+`--dump-outputs DIR`: after the timed steps, what the last of them computed, as a caller of the path receives it -- the frame's radiance
+and its per-tile light lists (dump_outputs) -- as .npy files; the inputs are the seeded synthetic frame, the same in every run of the same
+arguments, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -49,7 +58,7 @@ if ROOT not in sys.path:
 from sailor_amd import _lib, host, synth  # noqa: E402
 from sailor_amd.forward_plus import PreparedLights, EcsSweep, ForwardPlus, HipContext, upload_lights  # noqa: E402
 
-HBM_PEAK_GBS = 8000.0       # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+HBM_PEAK_GBS = 8000.0       # the MI355X micro-architecture guide: HBM3E 8.0 TB/s spec
 HBM_COPY_GBS = 6290.0       # same table: 6.29 TB/s measured float4 copy
 FP32_VALU_TFLOPS = 157.3
 
@@ -71,7 +80,7 @@ def parse(argv=None):
     ap.add_argument("--plain-lights", action="store_true", help="no prepared lights: cull and shade read the 112-byte light records (rounds 1-2)")
     ap.add_argument("--dynamic-lights", action="store_true", default=None,
                     help="every light is dirty every frame (LightingECS::Tick re-uploads it, ECS/LightingECS.cpp:152-191): sailor_hip_prepare_lights over all N lights inside "
-                         "every step, in front of the cull.  The default for C5 (\"1 M dynamic lights\"); the other configurations report it beside `value` as value_dynamic_lights")
+                         "every step, in front of the cull.  The default for C5 (\"1 M dynamic lights\"); with --full the other configurations report it beside `value` as value_dynamic_lights")
     ap.add_argument("--static-lights", dest="dynamic_lights", action="store_false", help="the lights' prepared views are derived once, outside the timed region (the default except for C5)")
     ap.add_argument("--separate-prepare", action="store_true", help="dynamic lights: sailor_hip_prepare_lights as a launch of its own in front of every cull (round 3) instead of "
                                                                     "folded into the cull's per-light pass (SAILOR_CULL_PREPARE_LIGHTS)")
@@ -94,15 +103,22 @@ def parse(argv=None):
     ap.add_argument("--no-afr", action="store_true", help="N > 1: skip the supplementary measurement (the other of the two multi-GPU modes)")
     ap.add_argument("--simulate-split", type=int, default=0, help="G: time each band of a cost-balanced G-way split one after the other on this GPU and print the predicted speed-up; diagnostic")
     ap.add_argument("--simulate-band", default=None, help="R/G: time only band R of a G-way split in this single process (no collectives); diagnostic")
-    ap.add_argument("--force-dist", action="store_true", help="initialise the RCCL process group and run the list exchange even with one rank")
+    ap.add_argument("--force-dist", action="store_true", help="initialise the RCCL process group even with one rank (and, with --full, run the list exchange)")
     ap.add_argument("--split-configs", default=None,
-                    help="N > 1: comma-separated configurations whose split frame gets a bounded reading (~20 steps each) appended to the line as `split_configs`; "
+                    help="N > 1 with --full: comma-separated configurations whose split frame gets a bounded reading (~20 steps each) appended to the line as `split_configs`; "
                          "default: C4,C5 -- the two BASELINE.json names for eight GPUs -- when the headline is C3, none otherwise; '' = none")
     ap.add_argument("--split-config-steps", type=int, default=24)
     ap.add_argument("--rebalance", type=int, default=2,
                     help="N > 1 (and --simulate-split): rounds of re-cutting the cost-balanced bands on MEASURED band times (a renderer has the previous frame's); 0 = the "
                          "list-volume model alone")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, every further reading and check of this file (see the module docstring); a plain run times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (radiance, light grid, culled lights) as DIR/<name>.npy (dump_outputs)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 class HipDevice:
@@ -307,9 +323,14 @@ def exchange_stats(dev, do_exchange, stream, dist=None, device=None, n=EXCHANGE_
     return gg, gi, out
 
 
+TIMING_SLOTS = 4096          # dispatch-packet event pairs one context can arm at once (sailor_hip_context_time_launches refuses more)
+MAX_READING_LAUNCHES = 500   # a per-kernel reading takes at most this many launches (or batch calls), however large --steps is
+
+
 def event_ms(fn, steps):
-    """average duration of fn() in ms, HIP events on the current (= launch) stream, one pair per call."""
+    """average duration of fn() in ms, HIP events on the current (= launch) stream, one pair per call (at most MAX_READING_LAUNCHES calls)."""
     dev = _dev()
+    steps = min(int(steps), MAX_READING_LAUNCHES)
     pairs = []
     for _ in range(steps):
         a, b = dev.event(), dev.event()
@@ -326,8 +347,10 @@ def kernel_in_frame_ms(ctx, before, kernel, launches, kernels_per_call=1, which=
     figure rocprofv3's kernel trace reports -- while the launch sits between its real neighbours: before(); kernel(); before(); ... on the launch
     stream, eagerly, nothing drained around it.  Nothing is subtracted and no two medians are combined.  (Events recorded in front of and behind a
     launch drain the stream on both sides -- isolated_* -- and fifty launches of the kernel alone back to back run into each other's write-back --
-    back_to_back_launch_ms.)  kernels_per_call / which: kernel() launches several kernels and the `which`-th is the one wanted."""
+    back_to_back_launch_ms.)  kernels_per_call / which: kernel() launches several kernels and the `which`-th is the one wanted.  At most
+    MAX_READING_LAUNCHES launches, and no more than the context's TIMING_SLOTS hold."""
     dev = _dev()
+    launches = min(int(launches), MAX_READING_LAUNCHES, TIMING_SLOTS // kernels_per_call)
     for i in range(launches):
         before()
         ctx.time_launches(i * kernels_per_call, kernels_per_call)
@@ -340,8 +363,10 @@ def kernel_in_frame_ms(ctx, before, kernel, launches, kernels_per_call=1, which=
 
 def chain_kernels_ms(ctx, chain, behind, launches, count):
     """the durations of the `count` kernels one chain() call launches (the cull chain), each by the event pair on its own dispatch packet, between
-    their real neighbours (behind() = the rest of the frame): median over `launches` frames per kernel, in launch order"""
+    their real neighbours (behind() = the rest of the frame): median over `launches` frames per kernel, in launch order (at most
+    MAX_READING_LAUNCHES frames, and no more than the context's TIMING_SLOTS hold)"""
     dev = _dev()
+    launches = min(int(launches), MAX_READING_LAUNCHES, TIMING_SLOTS // max(count, 1))
     for i in range(launches):
         ctx.time_launches(i * count, count)
         chain()
@@ -357,7 +382,8 @@ BATCH_LAUNCHES = 50  # ... of at least this many back-to-back launches each, wha
 
 def event_batch_stats(fn, steps, graph_stream=None, batches=BATCHES):
     """Duration of fn() in ms from HIP event pairs around batches of back-to-back calls on the launch stream: what a launch costs inside a running
-    pipeline (the next launch ramps up while the previous one drains).  `batches` batches of max(steps, BATCH_LAUNCHES) calls each; the figure is
+    pipeline (the next launch ramps up while the previous one drains).  `batches` batches of max(steps, BATCH_LAUNCHES) calls each (at most
+    MAX_READING_LAUNCHES); the figure is
     the MEDIAN batch (min / max kept alongside), so a short --steps or one disturbed batch does not move it.  An event pair around every single launch
     (event_ms) drains the GPU on both sides of the kernel and reads 10-15 % longer for a 0.2 ms kernel.  With graph_stream the calls of a batch are
     captured into one hipGraph first and the pair brackets its replay: eager launches of one kernel back to back leave the command processor's
@@ -365,7 +391,7 @@ def event_batch_stats(fn, steps, graph_stream=None, batches=BATCHES):
     includes besides the kernels' own durations (rocprofv3's kernel trace reports those): the gap between consecutive launches and the end-of-kernel
     write-back -- see `launch_gap_ms` in the JSON line."""
     dev = _dev()
-    n = max(int(steps), BATCH_LAUNCHES)
+    n = min(max(int(steps), BATCH_LAUNCHES), max(MAX_READING_LAUNCHES, BATCH_LAUNCHES))
     times = []
     if graph_stream is not None:
         try:
@@ -1200,7 +1226,8 @@ def main(argv=None, device_factory=None):
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=device)
         else:
             dist.init_process_group(dev.dist_backend, rank=rank, world_size=world)
-        dev.make_comm(rank, world)   # the ncclComm_t of the shipped exchange (exchange.hip), beside torch's own
+        if args.full or args.exchange_every_step:   # (a plain run has no exchange)
+            dev.make_comm(rank, world)   # the ncclComm_t of the shipped exchange (exchange.hip), beside torch's own
 
     frame = BenchFrame(args.config)
     cam, W, H = frame.cam, frame.cam.width, frame.cam.height
@@ -1368,8 +1395,9 @@ def main(argv=None, device_factory=None):
         dev.synchronize()
 
     def build_runner(dyn):
-        """-> (run, finish, per_run, launch): run() = `per_run` steps (the main pipeline graph, or one step of the other forms), finish() = the
-        pipeline's shorter graph for the rest of K, launch = how the steps are launched (for the JSON line)"""
+        """-> (run, finish, per_run, launch, last): run() = `per_run` steps (the main pipeline graph, or one step of the other forms), finish() = the
+        pipeline's shorter graph for the rest of K, launch = how the steps are launched (for the JSON line), last = the list set whose lists and
+        radiance the last of K timed steps leaves (every replay of a pipeline graph starts shading at set 0)"""
         def step():
             cull_of(fp, None, dyn, defer_pack)
             if pack_mode == "deferred":
@@ -1389,18 +1417,19 @@ def main(argv=None, device_factory=None):
                 per = unroll if unroll else tail
                 how = (f"hipGraph replay ({per} steps of the frame pipeline per graph" + (f", {tail} in the last" if unroll and tail else "") +
                        f"), 2 frames in flight over {args.list_sets} list sets" + (", k1_pack behind the event the shade waits for" if pack_mode == "deferred" else (", no k1_pack (no consumer of the canonical buffers)" if pack_mode == "never" else "")))
-                return main_graph.replay, (rest.replay if rest is not None else (lambda: None)), per, how
+                last = fps[((tail if rest is not None else per) - 1) % len(fps)]
+                return main_graph.replay, (rest.replay if rest is not None else (lambda: None)), per, how, last
             except Exception as e:
                 print(f"[bench] two-frames-in-flight capture failed ({type(e).__name__}: {e}); falling back to one frame in flight", file=sys.stderr)
                 dev.synchronize()
         if not args.no_graph and not args.exchange_every_step:
             try:
                 step(); dev.synchronize()
-                return dev.capture(side, step).replay, (lambda: None), 1, "hipGraph replay"
+                return dev.capture(side, step).replay, (lambda: None), 1, "hipGraph replay", fp
             except Exception as e:  # capture unsupported: stay eager, say so in the JSON line
                 print(f"[bench] hipGraph capture failed ({type(e).__name__}: {e}); launching eagerly", file=sys.stderr)
                 dev.synchronize()
-        return step, (lambda: None), 1, "eager"
+        return step, (lambda: None), 1, "eager", fp
 
     def time_steps(run, finish, per):
         """W warm-up steps, then EXACTLY K timed steps between barrier + synchronize on both sides; the MAX over ranks, in seconds"""
@@ -1427,10 +1456,46 @@ def main(argv=None, device_factory=None):
             el = float(t.item())
         return el
 
-    run, finish, per_run, launch = build_runner(dynamic)
+    run, finish, per_run, launch, last_set = build_runner(dynamic)
     elapsed = time_steps(run, finish, per_run)
     ms_per_step = elapsed / args.steps * 1e3
     frames_per_step = world if (weak and world > 1) else 1
+    value = frames_per_step * W * H * args.steps / elapsed / 1e6
+    if args.dump_outputs:
+        if pack_mode == "never":
+            last_set.pack()   # (no frame wrote the canonical lists: written from the per-tile lists the last shade read)
+        dump_outputs(args.dump_outputs, last_set, rank, world)
+
+    def headline():
+        """the line of a plain run: what the K timed steps measured, and on what"""
+        mode = (("dynamic: every light dirty every frame -- the prepared views of all %d lights re-derived inside every step, " % N) +
+                ("by sailor_hip_prepare_lights in front of the cull" if args.separate_prepare else "folded into the cull's per-light pass (SAILOR_CULL_PREPARE_LIGHTS)")) if dynamic else \
+               ("static: the lights' prepared views derived ONCE, outside the timed region (LightingECS::Tick uploads dirty runs only; the synthetic set does not move)" if prep is not None
+                else "plain: no prepared views, cull and shade read the 112-byte records")
+        return {
+            "metric": "lit Mpixels/s (K0+K1 tile light cull + K2 PBR shade over per-tile lists)", "value": value, "unit": "Mpixels/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "spinup_ms": args.spinup_ms, "ms_per_step": ms_per_step, "higher_is_better": True,
+            "scaling": "weak" if weak else "strong", "launch": launch, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"{args.config}: {W}x{H}, {N} point+spot lights" + (" (all dirty every frame)" if dynamic else "") + f", 16x16 tiles ({fp.Tx}x{fp.Ty}), cull + PBR shade"
+                                   + (" + 4-cascade CSM" if csm is not None else ""),
+                       "width": W, "height": H, "lights": N, "parallelism": (f"dp{world}: a whole frame per GPU" if weak else f"tile-row bands x{world}"), "partition": partition, "rebalance": rebalance_info,
+                       "generator": {"seed": synth.SEED, "radius_scale": frame.cfg["lights"].radius_scale}},
+            "lights": {"mode": mode},
+        }
+
+    def finish_line(line):
+        if dist is not None:
+            dist.barrier()
+            dev.close()
+            dist.destroy_process_group()
+        if rank == 0:
+            emit(line)
+        return line
+
+    if not args.full:
+        return finish_line(json.dumps(headline()) if rank == 0 else None)
+
+    # ---- --full from here on ----
     # per-step distribution (SURVEY.md 8d: median, p10 / p90): a second pass of K steps with one HIP event per step on the launch stream --
     # outside the timed region above, which stays free of event records
     n_runs = max(args.steps // per_run, 1)
@@ -1445,12 +1510,11 @@ def main(argv=None, device_factory=None):
                   "how": ("HIP events between consecutive steps on the launch stream" if per_run == 1 else
                           f"HIP events between consecutive replays of the {per_run}-step pipeline graph on the launch stream, divided by {per_run}") +
                          ", a separate pass of K steps (this rank)"}
-    value = frames_per_step * W * H * args.steps / elapsed / 1e6
 
     # ---- the other light mode, same launch form, same K steps: static lights beside a dynamic headline and the other way round ----
     other_mode = None
     if prep is not None and not args.single_mode:
-        run2, finish2, per2, _ = build_runner(not dynamic)
+        run2, finish2, per2, _, _ = build_runner(not dynamic)
         el2 = time_steps(run2, finish2, per2)
         other_mode = {"ms_per_step": el2 / args.steps * 1e3, "value": frames_per_step * W * H * args.steps / el2 / 1e6}
         prep.prepare(0, N)   # (the views as the per-kernel measurements below expect them)
@@ -1738,21 +1802,11 @@ def main(argv=None, device_factory=None):
 
     line = None
     if rank == 0:
-        mode = (("dynamic: every light dirty every frame -- the prepared views of all %d lights re-derived inside every step, " % N) +
-                ("by sailor_hip_prepare_lights in front of the cull" if args.separate_prepare else "folded into the cull's per-light pass (SAILOR_CULL_PREPARE_LIGHTS)")) if dynamic else \
-               ("static: the lights' prepared views derived ONCE, outside the timed region (LightingECS::Tick uploads dirty runs only; the synthetic set does not move)" if prep is not None
-                else "plain: no prepared views, cull and shade read the 112-byte records")
-        out = {
-            "metric": "lit Mpixels/s (K0+K1 tile light cull + K2 PBR shade over per-tile lists)", "value": value, "unit": "Mpixels/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "spinup_ms": args.spinup_ms, "ms_per_step": ms_per_step, "higher_is_better": True,
-            "scaling": "weak" if weak else "strong", "launch": launch, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{args.config}: {W}x{H}, {N} point+spot lights" + (" (all dirty every frame)" if dynamic else "") + f", 16x16 tiles ({fp.Tx}x{fp.Ty}), cull + PBR shade"
-                                   + (" + 4-cascade CSM" if csm is not None else ""),
-                       "width": W, "height": H, "lights": N, "parallelism": (f"dp{world}: a whole frame per GPU" if weak else f"tile-row bands x{world}"), "partition": partition, "rebalance": rebalance_info,
-                       "mean_list_length": sum_nt / max(fp.band_tiles, 1), "sum_num_rank0_band": sum_nt, "distinct_lights_rank0_band": distinct,
-                       "generator": {"seed": synth.SEED, "radius_scale": frame.cfg["lights"].radius_scale}},
-            "lights": {"mode": mode, "prepare_lights_ms": prepare_ms,
-                       "prepare_lights_how": "sailor_hip_prepare_lights(0, N) back to back, median of event-bracketed batches (what one frame's re-upload of every light adds)"},
+        out = headline()
+        out["config"].update({"mean_list_length": sum_nt / max(fp.band_tiles, 1), "sum_num_rank0_band": sum_nt, "distinct_lights_rank0_band": distinct})
+        out["lights"].update({"prepare_lights_ms": prepare_ms,
+                              "prepare_lights_how": "sailor_hip_prepare_lights(0, N) back to back, median of event-bracketed batches (what one frame's re-upload of every light adds)"})
+        out.update({
             "step_ms": step_stats,
             "value_serial": frames_per_step * W * H / (serial_max * 1e-3) / 1e6 if not (weak and world > 1) else None,
             "serial_step_ms": {"median": serial["median"], "min": serial["min"], "max": serial["max"], "max_over_ranks": serial_max,
@@ -1768,7 +1822,7 @@ def main(argv=None, device_factory=None):
                              "(sailor_hip_light_cull_pack), its kernel time reported here; deferred / inline: inside every step"},
             "roofline": roofline,
             "box": box,
-        }
+        })
         if other_mode is not None:
             tag = "static_lights" if dynamic else "dynamic_lights"
             out["value_" + tag] = other_mode["value"]
@@ -1799,13 +1853,39 @@ def main(argv=None, device_factory=None):
             out["ibl_prefilter"] = ibl_prefilter_block(ctx, 3)
             out["shadow_passes"] = shadow_pass_block(ctx, 1 << 20, 4096, 5)
         line = json.dumps(out)
-    if dist is not None:
-        dist.barrier()
-        dev.close()
-        dist.destroy_process_group()
-    if rank == 0:
-        emit(line)
-    return line
+    return finish_line(line)
+
+
+DUMP_BYTES = 60 << 20   # --dump-outputs: at most this many bytes of data in all, shared by the ranks of an N > 1 run (under 64 MB with the files' headers)
+DUMP_SEED = synth.SEED  # ... and the seed of the sample taken of an output larger than its share
+
+
+def dump_outputs(out_dir: str, fp, rank: int = 0, world: int = 1):
+    """--dump-outputs: what the timed path computed in its last step, as a caller of the path receives it, from `fp` (the list set that step shaded):
+      radiance.npy       float32 [band rows, W, 4]: the shade's output;
+      light_grid.npy     float64 [tiles, 2]: lightsGrid, (offset, count) per tile of the band (band-local offsets);
+      culled_lights.npy  float64 [1 + total]: culledLights, the total followed by the light indices, tile after tile.
+    The lists come from the cull whose per-tile lists that step's shade read (k1_pack writes them bit for bit).  An output larger than its share
+    of DUMP_BYTES (radiance 3/8, light_grid 1/8, culled_lights 1/2; divided by the ranks) is written as a fixed, seeded sample of its rows (pixels,
+    tiles, entries) -- sorted row numbers drawn with DUMP_SEED, the same in every run -- and <name>_index.npy holds those row numbers (float64).
+    N > 1: every rank writes its own band, as rank<r>_<name>.npy."""
+    g, idx = fp.lists_to_host()
+    rad = fp.radiance.cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BYTES // max(world, 1)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    outputs = (("radiance", rad, rad.reshape(-1, 4), np.float32, 3 * budget // 8),   # (the rows of a sample: pixels, tiles, entries)
+               ("light_grid", g, g, np.float64, budget // 8),
+               ("culled_lights", idx, idx, np.float64, budget // 2))
+    for name, whole, rows, dtype, share in outputs:
+        path = os.path.join(out_dir, prefix + name)
+        if whole.size * np.dtype(dtype).itemsize <= share:
+            np.save(path + ".npy", whole.astype(dtype))
+            continue
+        n = share // (rows[0].size * np.dtype(dtype).itemsize + 8)
+        sel = np.sort(np.random.default_rng(DUMP_SEED).choice(len(rows), n, replace=False))
+        np.save(path + ".npy", rows[sel].astype(dtype))
+        np.save(path + "_index.npy", sel.astype(np.float64))
 
 
 _JSON_FD = None   # set when this process is run as a rank: the descriptor stdout had at start-up

@@ -8,7 +8,7 @@ mkdir -p "$out"
 for round in 1 2; do
   for side in A B; do
     val=$a; [ $side = B ] && val=$b
-    env "$var=$val" python bench.py --no-cpu-baseline "$@" > "$out/${side}_$round.json" 2> "$out/${side}_$round.err"
+    env "$var=$val" python bench.py --full --no-cpu-baseline "$@" > "$out/${side}_$round.json" 2> "$out/${side}_$round.err"
   done
 done
 python - "$out" "$var" "$a" "$b" <<'PY' | tee "$out/summary.txt"

@@ -60,8 +60,8 @@ class _Context:
     def synchronize(self):
         pass
 
-    def time_launches(self, first_slot, count):
-        pass
+    def time_launches(self, first_slot, count):   # (the library arms at most 4096 slots: sailor_hip_context_time_launches)
+        assert first_slot >= 0 and count >= 0 and first_slot + count <= 4096, (first_slot, count)
 
     def timed_launch_ms(self, slot):
         return 0.01
@@ -225,7 +225,7 @@ class _Device:
         pass
 
 
-def _worker(rank, world, port, extra, out_dir):
+def _worker(rank, world, port, extra, out_dir, full=True):
     sys.path.insert(0, str(ROOT))
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world))
     import bench
@@ -235,7 +235,8 @@ def _worker(rank, world, port, extra, out_dir):
     def factory(local_rank):
         made.append(_Device(local_rank))
         return made[-1]
-    line = bench.main(["--gpus", str(world), "--config", "tiny", "--steps", "3", "--warmup", "1", "--spinup-ms", "0", "--no-cpu-baseline"] + list(extra), device_factory=factory)
+    line = bench.main(["--gpus", str(world), "--config", "tiny", "--steps", "3", "--warmup", "1", "--spinup-ms", "0", "--no-cpu-baseline"] + (["--full"] if full else []) + list(extra),
+                      device_factory=factory)
     assert (line is not None) == (rank == 0), "rank 0 alone assembles the JSON line"
     with open(Path(out_dir) / f"rank{rank}.json", "w") as f:
         json.dump({"line": json.loads(line) if line else None, "exchanges": made[0].exchanges}, f)
@@ -315,6 +316,84 @@ def test_two_ranks_run_the_whole_of_bench_main(extra, tmp_path):
             assert abs(v["speedup_vs_one_gpu_whole_frame"] - v["whole_frame_per_gpu_ms_per_step"] / v["split_ms_per_step"]) < 1e-9
     else:
         assert "split_configs" not in d
+
+
+FULL_ONLY = ("step_ms", "value_serial", "serial_step_ms", "roofline", "box", "pack", "cull_ms", "shade_ms", "exchange", "alternate_frame_rendering",
+             "split_frame", "split_configs", "ecs_sweep", "cpu_baseline", "value_dynamic_lights", "value_static_lights", "value_exchange_every_step")
+
+
+@pytest.mark.parametrize("world", [1, 2])
+def test_a_plain_run_times_the_steps_and_prints_the_headline_alone(world, tmp_path):
+    """Without --full, bench.main() sets up, warms up, times exactly K steps and prints the headline: no further reading, no exchange, and the
+    outputs of the last timed step under --dump-outputs -- the whole frame's lists and radiance, rank by rank for N > 1, as the oracle has them."""
+    out_dir = tmp_path / "out"
+    mp.spawn(_worker, args=(world, _free_port(), ("--dump-outputs", str(out_dir)), str(tmp_path), False), nprocs=world, join=True)
+    res = [json.load(open(tmp_path / f"rank{r}.json")) for r in range(world)]
+    d = res[0]["line"]
+    for key in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype", "n_gpus", "steps", "warmup", "scaling", "launch", "config"):
+        assert key in d, key
+    assert d["n_gpus"] == world and d["steps"] == 3 and d["unit"] == "Mpixels/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["value"] - 128 * 96 * 3 / (d["ms_per_step"] * 3e-3) / 1e6) < 1e-6 * d["value"]
+    assert d["lights"]["mode"].startswith("static") and d["config"]["workload"].startswith("tiny: 128x96, 512 ")
+    assert [k for k in FULL_ONLY if k in d] == []
+    assert all(r["exchanges"] == 0 for r in res), "a plain run exchanges nothing"
+    from oracle import oracle
+    import bench
+    f = bench.BenchFrame("tiny")
+    g, idx = _oracle_whole_frame()
+    rad = oracle.shade(f.cam.frame, 128, 96, f.surface_rows(0, 96), f.lights, g, idx, None)
+    idx = idx[: 1 + int(idx[0])]
+    names = ["radiance", "light_grid", "culled_lights"]
+    if world == 1:
+        assert sorted(p.name for p in out_dir.iterdir()) == sorted(n + ".npy" for n in names)
+        got = {n: np.load(out_dir / f"{n}.npy") for n in names}
+        assert got["radiance"].dtype == np.float32 and got["light_grid"].dtype == got["culled_lights"].dtype == np.float64
+        np.testing.assert_array_equal(got["radiance"], rad)
+        np.testing.assert_array_equal(got["light_grid"], g.astype(np.float64))
+        np.testing.assert_array_equal(got["culled_lights"], idx.astype(np.float64))
+    else:
+        assert sorted(p.name for p in out_dir.iterdir()) == sorted(f"rank{r}_{n}.npy" for r in range(world) for n in names)
+        from sailor_amd import host
+        bounds = json.loads(d["config"]["partition"].split("tile rows ")[1].split(" (")[0])
+        for r in range(world):
+            band = host.band_from_tile_rows(128, 96, bounds[r], bounds[r + 1])
+            got = {n: np.load(out_dir / f"rank{r}_{n}.npy") for n in names}
+            np.testing.assert_array_equal(got["radiance"], rad[band.fbRowBegin:band.fbRowBegin + band.fbRowCount])
+            bg, bi, _ = oracle.light_cull(f.cam.frame, 128, 96, f.lights, f.depth, tile_rows=(bounds[r], bounds[r + 1]))   # (a band's own cull: band-local offsets)
+            np.testing.assert_array_equal(got["light_grid"], bg.astype(np.float64))
+            np.testing.assert_array_equal(got["culled_lights"], bi[: 1 + int(bi[0])].astype(np.float64))
+
+
+def test_dump_outputs_samples_what_exceeds_its_share(monkeypatch, tmp_path):
+    """An output larger than its share of bench.DUMP_BYTES is written as a seeded sample of its rows beside their row numbers: the same rows in
+    every run, the whole within the budget, float32 / float64 only."""
+    sys.path.insert(0, str(ROOT))
+    import bench
+    rng = np.random.default_rng(1)
+    rad = rng.random((96, 128, 4), dtype=np.float32)
+    grid = rng.integers(0, 1 << 20, (48, 2)).astype(np.uint32)
+    culled = rng.integers(0, 1 << 16, 5000).astype(np.uint32)
+
+    class _Fp:
+        radiance = torch.from_numpy(rad)
+
+        def lists_to_host(self):
+            return grid.copy(), culled.copy()
+    monkeypatch.setattr(bench, "DUMP_BYTES", 64 << 10)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), _Fp())
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["culled_lights.npy", "culled_lights_index.npy", "light_grid.npy", "radiance.npy", "radiance_index.npy"]
+    assert sum(np.load(tmp_path / "a" / n).nbytes for n in files) <= 64 << 10
+    for n in files:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    sel = np.load(tmp_path / "a" / "radiance_index.npy").astype(np.int64)
+    assert len(sel) > 0 and np.all(np.diff(sel) > 0)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "radiance.npy"), rad.reshape(-1, 4)[sel])
+    sel = np.load(tmp_path / "a" / "culled_lights_index.npy").astype(np.int64)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "culled_lights.npy"), culled[sel].astype(np.float64))
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "light_grid.npy"), grid.astype(np.float64))
 
 
 def test_a_bare_gpus_n_starts_its_ranks_as_child_processes(monkeypatch):

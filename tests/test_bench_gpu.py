@@ -1,5 +1,6 @@
-"""bench.py's output contract on a real device: one JSON line with the driver's keys, the `roofline` and `cpu_baseline` objects, and -- with a one-rank
-RCCL process group -- both multi-GPU modes (the split frame + list exchange as `value`, a frame per GPU next to it; `--frame-per-gpu` swaps them)."""
+"""bench.py's output contract on a real device: a plain run's headline line and its --dump-outputs; with --full, one JSON line with the driver's
+keys, the `roofline` and `cpu_baseline` objects, and -- with a one-rank RCCL process group -- both multi-GPU modes (the split frame + list
+exchange as `value`, a frame per GPU next to it; `--frame-per-gpu` swaps them)."""
 import json
 import os
 import subprocess
@@ -25,7 +26,7 @@ def _run(cmd, env=None):
 
 
 def test_default_line_carries_the_contract():
-    d = _run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--spinup-ms", "50", "--cpu-sample-tile-rows", "4"])
+    d = _run([sys.executable, "bench.py", "--full", "--steps", "5", "--warmup", "2", "--spinup-ms", "50", "--cpu-sample-tile-rows", "4"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
         assert key in d, key
     assert d["unit"] == "Mpixels/s" and d["n_gpus"] == 1 and d["steps"] == 5 and d["warmup"] == 2 and d["higher_is_better"] is True
@@ -69,10 +70,32 @@ def test_default_line_carries_the_contract():
     assert set(sim) == {"2", "4", "8"} and all(v["slice_ms_max"] > 0 for v in sim.values()) and d["ecs_sweep"]["split"]["default"] == "replicated"
 
 
+def test_a_plain_run_prints_the_headline_and_dumps_the_last_steps_outputs(tmp_path):
+    """Without --full: the headline alone (no further reading), and --dump-outputs writes what the last timed step computed -- the frame's lists bit
+    for bit and its radiance within 1e-4 relative of the oracle, as smoke() holds them."""
+    import numpy as np
+
+    from oracle import oracle
+    from sailor_amd import synth
+    d = _run([sys.executable, "bench.py", "--config", "tiny", "--steps", "7", "--warmup", "2", "--spinup-ms", "50", "--dump-outputs", str(tmp_path)])
+    assert d["steps"] == 7 and d["unit"] == "Mpixels/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["ms_per_step"] > 0
+    assert abs(d["value"] - 128 * 96 / (d["ms_per_step"] * 1e-3) / 1e6) < 1e-6 * d["value"]
+    assert [k for k in ("step_ms", "roofline", "box", "serial_step_ms", "value_dynamic_lights", "cpu_baseline", "ecs_sweep") if k in d] == []
+    f = synth.make_frame("tiny")
+    og, oi, _ = oracle.light_cull(f.cam.frame, 128, 96, f.lights, f.depth)
+    orad = oracle.shade(f.cam.frame, 128, 96, f.surface, f.lights, og, oi, None)
+    np.testing.assert_array_equal(np.load(tmp_path / "light_grid.npy"), og.astype(np.float64))
+    np.testing.assert_array_equal(np.load(tmp_path / "culled_lights.npy"), oi[: 1 + int(oi[0])].astype(np.float64))
+    rad = np.load(tmp_path / "radiance.npy")
+    assert rad.dtype == np.float32 and rad.shape == (96, 128, 4)
+    err = np.abs(rad.astype(np.float64) - orad)
+    assert (err <= 1e-4 * np.abs(orad)).all(), f"radiance differs from the oracle: max abs err {err.max()}"
+
+
 @pytest.mark.parametrize("split_primary", [True, False])
 def test_one_rank_process_group_runs_both_multi_gpu_modes(split_primary):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29541", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, "bench.py", "--gpus", "1", "--force-dist", "--steps", "5", "--warmup", "2", "--spinup-ms", "50", "--no-cpu-baseline"]
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--force-dist", "--full", "--steps", "5", "--warmup", "2", "--spinup-ms", "50", "--no-cpu-baseline"]
     d = _run(cmd + ([] if split_primary else ["--frame-per-gpu"]), env)
     assert d["scaling"] == ("strong" if split_primary else "weak")  # the default headline is the split frame (BASELINE.json's metric)
     other = d["alternate_frame_rendering"] if split_primary else d["split_frame"]
@@ -96,7 +119,7 @@ def test_ranks_sharing_the_gpu_run_the_split_frame_for_real(ranks):
     SAILOR_BENCH_SHARE_GPU=1 every rank takes device 0 over a `gloo` group.  The figures mean nothing (the ranks time-share the device); the path is the
     real one -- calibration cull, cost-balanced re-split, band kernels inside the pipeline graph, every collective of main(), the list exchange -- and the
     exchanged global lists must be the ones a single rank holds for the whole frame."""
-    common = ["--steps", "6", "--warmup", "2", "--spinup-ms", "50", "--no-cpu-baseline"]
+    common = ["--full", "--steps", "6", "--warmup", "2", "--spinup-ms", "50", "--no-cpu-baseline"]
     env1 = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29543", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     one = _run([sys.executable, "bench.py", "--gpus", "1", "--force-dist", "--no-afr"] + common, env1)
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
@@ -129,10 +152,22 @@ def test_ranks_sharing_the_gpu_run_the_split_frame_for_real(ranks):
 
 @pytest.mark.parametrize("sets, steps", [(3, 12), (2, 8)])
 def test_step_counts_the_list_sets_divide_run_one_pipeline_graph(sets, steps):
-    d = _run([sys.executable, "bench.py", "--steps", str(steps), "--warmup", "2", "--spinup-ms", "50", "--no-cpu-baseline", "--list-sets", str(sets)])
+    d = _run([sys.executable, "bench.py", "--full", "--steps", str(steps), "--warmup", "2", "--spinup-ms", "50", "--no-cpu-baseline", "--list-sets", str(sets)])
     assert f"{steps} steps of the frame pipeline per graph)" in d["launch"] and f"{sets} list sets" in d["launch"] and d["steps"] == steps
     assert abs(d["value"] - 3840 * 2160 / (d["ms_per_step"] * 1e-3) / 1e6) < 1e-6 * d["value"]
     assert d["step_ms"]["p10"] <= d["step_ms"]["median"] <= d["step_ms"]["p90"]
+
+
+def test_full_line_with_more_steps_than_the_context_has_timing_slots():
+    """--full with a K whose per-kernel readings would need more dispatch-packet event pairs than a context holds (4096: 4 x 1100 for the cull
+    chain): every reading is bounded (bench.MAX_READING_LAUNCHES), whatever K is, and the line still carries the per-kernel figures."""
+    import bench
+    d = _run([sys.executable, "bench.py", "--full", "--config", "tiny", "--steps", "1100", "--warmup", "2", "--spinup-ms", "50", "--no-cpu-baseline"])
+    assert d["steps"] == 1100 and abs(d["value"] - 128 * 96 / (d["ms_per_step"] * 1e-3) / 1e6) < 1e-6 * d["value"]
+    r = d["roofline"]
+    assert r["avg_launch_ms_stats"]["launches"] == bench.MAX_READING_LAUNCHES and r["avg_launch_ms"] > 0
+    assert len(r["cull"]["kernels_ms"]) >= 2 and all(v > 0 for v in r["cull"]["kernels_ms"].values())
+    assert d["step_ms"]["p10"] <= d["step_ms"]["median"] <= d["step_ms"]["p90"] and d["ms_per_step_dynamic"] > 0
 
 
 @pytest.mark.parametrize("sets, deferred", [(2, False), (3, False), (3, True), (2, True)])
