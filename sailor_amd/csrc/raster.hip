@@ -19,13 +19,6 @@
 #ifndef RASTER_SMALL_BOX
 #define RASTER_SMALL_BOX 64 // pixels a lane fills on its own
 #endif
-// (RASTER_PRETEST builds only) how the depth test reads the stored depth in front of its atomic: a plain load (this XCD's L2: possibly stale, never too high) or --
-// RASTER_PRETEST_COHERENT -- a relaxed device-scope atomic load (the memory side: current, dearer)
-#ifdef RASTER_PRETEST_COHERENT
-#define RASTER_PRETEST_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#else
-#define RASTER_PRETEST_LOAD(p) (*(p))
-#endif
 #if defined(RASTER_STATS) || defined(RASTER_WAVE_TIME)
 __device__ unsigned long long gStats[16]; // [8..]: per-wave durations on the 100 MHz clock -- sum, max, waves, waves above 100 us, above 1 ms
 #ifdef RASTER_STATS
@@ -147,17 +140,11 @@ __device__ __forceinline__ bool raster_top_left(long long ax, long long ay, long
     return (dy == 0 && dx > 0) || dy < 0;
 }
 
-// The depth test of one fragment: atomicMax over float bits (depths are > 0).  (Round 6, measured and left off -- RASTER_PRETEST: the stored depth read first, the
-// atomic only for a fragment that beats it.  The buffer only rises, so a stale value is merely too low and the test is safe; but the load is a round trip in front of
-// every block of a wave that fills its blocks one after the other, and the caster draws are bound by exactly that chain, not by the atomics' throughput: the four
-// cascades of the million-box scene 26.8 -> 34.3 ms with it, plain or device-coherent load alike -- profiles/r06/raster_variants.txt.)
+// The depth test of one fragment: atomicMax over float bits (depths are > 0).  (Round 6: reading the stored depth before the atomic measured slower, the
+// caster draws being bound by that round trip: DESIGN.md §4 raster.)
 __device__ __forceinline__ void raster_depth_test(unsigned int* __restrict__ p, const float z)
 {
-    const unsigned int zb = __float_as_uint(z); // positive floats order like their bits
-#ifdef RASTER_PRETEST
-    if (zb > RASTER_PRETEST_LOAD(p))
-#endif
-        atomicMax(p, zb);
+    atomicMax(p, __float_as_uint(z)); // positive floats order like their bits
 }
 
 __device__ __forceinline__ long long bcast64(long long v, int src)
@@ -247,9 +234,6 @@ __device__ __forceinline__ void raster_superblock(const RasterTri& b, const Rast
     }
     unsigned long long live = __ballot(alive);
     if (lane == 0) { STAT(2, 64); STAT(3, __popcll(live)); }
-#ifdef RASTER_PROBE_NOFILL
-    live = 0ull; // (timing probe: everything but the texel-level fill -- WRONG results)
-#endif
     // ---- the surviving blocks, one lane per texel ----
     while (live) {
         const int s2 = __builtin_ctzll(live);
@@ -487,9 +471,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         }
         // the large ones: the whole wave on one triangle at a time
         unsigned long long todo = __ballot(t.valid && !small);
-#ifdef RASTER_PROBE_NOLARGE
-        todo = 0ull; // (timing probe: what the launch costs without its large triangles -- WRONG results)
-#endif
         while (todo) {
             const int src = __builtin_ctzll(todo);
             todo &= todo - 1ull;

@@ -28,13 +28,6 @@ cd $GRAFT_REPO_ROOT
 python3 scripts/make_traffic_json.py $OUT/fetch $OUT/write $OUT/traffic.json C3 > /dev/null
 python3 scripts/make_traffic_json.py $OUT/fetch4 $OUT/write4 $OUT/traffic_C4.json C4 > /dev/null
 python3 scripts/make_traffic_json.py $OUT/fetch5 $OUT/write5 $OUT/traffic_C5.json C5 > /dev/null
-# (round 6) C5's wide list builder in round 5's form (one row of four groups per block), for the traffic and time beside the 4 x 4-patch form above
-cd /tmp
-SAILOR_CULL_WIDE16=0 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch5w -- python3 $B --config C5 --steps 3 --warmup 1 $EAGER > /dev/null 2>&1
-SAILOR_CULL_WIDE16=0 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write5w -- python3 $B --config C5 --steps 3 --warmup 1 $EAGER > /dev/null 2>&1
-cd $GRAFT_REPO_ROOT
-python3 scripts/make_traffic_json.py $OUT/fetch5w $OUT/write5w $OUT/traffic_C5_wide16_off.json C5 > /dev/null
-for rep in 1 2; do for v in 1 0; do SAILOR_CULL_WIDE16=$v python3 bench.py --full --config C5 --no-cpu-baseline --steps 20 > $OUT/bench_C5_wide16_${v}_$rep.json 2> /dev/null; done; done
 python3 scripts/r06_raster_probe.py 5 > $OUT/shadow_passes.json 2> /dev/null
 python3 scripts/pmc_summary.py $OUT/sq k2_shade_pt > $OUT/pmc_shade.txt
 python3 scripts/pmc_summary.py $OUT/sq tile_cull > $OUT/pmc_tile_cull.txt

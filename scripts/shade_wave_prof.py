@@ -32,13 +32,12 @@ buf = np.zeros((65536, 12), dtype=np.uint64)
 fn = lib.sailor_hip_debug_read_shade_wave_prof
 fn.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
 assert fn(buf.ctypes.data, buf.nbytes) == 0
-import os
-WPB = 2 if os.environ.get("SAILOR_SHADE_HALF") == "1" else 4   # waves per block: the two-wave form (round 6) has two blocks per tile, half tiles side by side in x
-Tx = fp.Tx; tpp = (Tx + 79) // 80; gx = 8 * tpp * (4 // WPB)
+WPB = 4   # waves per block
+Tx = fp.Tx; tpp = (Tx + 79) // 80; gx = 8 * tpp
 nrows = band.tileRowEnd - band.tileRowBegin
 nb = min(gx * 10 * nrows, 65536)
 lin = np.arange(nb); bx, by, bz = lin % gx, (lin // gx) % 10, lin // (gx * 10)
-btx = (((bx - bz) & 7) + 8 * by) * tpp + (bx >> (3 if WPB == 4 else 4))
+btx = (((bx - bz) & 7) + 8 * by) * tpp + (bx >> 3)
 real = btx < Tx
 p = buf[:nb][real].astype(np.int64)
 t0 = p[:, 0:WPB].min()
