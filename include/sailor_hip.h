@@ -527,6 +527,39 @@ SAILOR_HIP_API int sailor_hip_ecs_sweep_range(SailorHipContext* ctx, uint32_t nu
                                               const SailorAABB* dLocalAabb, const float* planes,
                                               float* dWorld, SailorAABB* dWorldAabb, uint64_t* dVisibility,
                                               uint32_t entityBegin, uint32_t entityEnd);
+/* Row E4 as the reference runs it: RHISceneView::TraceScene (RHI/SceneView.cpp:56, the camera snapshot at :170, the cascade mesh lists at
+ * ECS/LightingECS.cpp:296) walks a TOctree whose elements are the world boxes TRUNCATED to integers -- StaticMeshRendererECS.cpp:81,96,132 pass
+ * GetCenter() / GetExtents() (Math/Bounds.cpp:455-463) to TOctree::Update(const glm::ivec3&, const glm::ivec3&, ...) -- and draws only what the
+ * root (ivec3(0), RHI/SceneView.h:91-92) STRICTLY contains (Containers/Octree.h:44-53: -h < p - e and h > p + e per axis, h = rootSize / 2 as an
+ * integer), traced with Frustum::OverlapsAABB on AABB((vec3)p, (vec3)e) (Octree.h:239-274) once the root's own box passes (:239-247).
+ * sailor_hip_ecs_sweep and sailor_hip_csm_caster_masks test the float boxes flat (SAILOR_TRACE_FLAT_FLOAT_BOXES); SAILOR_TRACE_OCTREE_INT_BOXES
+ * gives the reference's set without building a tree: per entity, inserted = the root strictly contains the integer box, visible =
+ * inserted, the root's box passes and the integer box passes.  That is the walk's answer, bit for bit, whenever every truncated extent is >= 0 --
+ * always so for the sweep's own world boxes (AABB::Apply yields min <= max).  The inserted bits are the reference's for every defined box.
+ * Two stated divergences:
+ *   - Undefined inputs: glm::ivec3(float) is undefined behaviour for NaN, +-Inf and magnitudes >= 2^31.  Here an entity with such a centre or
+ *     extent component is neither inserted nor visible (the reference's result depends on its compiler and CPU).
+ *   - Negative extents (a caller's box with min > max by two units or more): TNode::Contains is then an overlap test, where the element rests
+ *     depends on the other elements, and the walk may prune a node the frustum misses while the element's own box is in view.  Here such an
+ *     entity is visible by the rule above: a superset of the walk's answer, independent of the other entities. */
+#define SAILOR_TRACE_FLAT_FLOAT_BOXES 0u  /* what sailor_hip_ecs_sweep does today */
+#define SAILOR_TRACE_OCTREE_INT_BOXES 1u  /* RHISceneView::TraceScene as the reference runs it */
+#define SAILOR_OCTREE_ROOT_SIZE 264576u   /* RHI/SceneView.h:91-92, 16536 * 16 */
+typedef struct SailorSceneTrace {
+    uint32_t mode;       /* one of the above; anything else is SAILOR_HIP_ERR_INVALID_ARGUMENT */
+    uint32_t rootSize;   /* 0 = SAILOR_OCTREE_ROOT_SIZE; otherwise 2 .. 2^30 (tests use small roots) */
+    uint64_t* dInserted; /* device out, ceil(n / 64) words, or NULL: bit i = entity i is in the octree at all (Octree.h:397-437 Insert succeeded);
+                            octree mode only (non-NULL in flat mode is SAILOR_HIP_ERR_INVALID_ARGUMENT) */
+} SailorSceneTrace;
+/* sailor_hip_ecs_sweep_range with a choice of visibility test (trace NULL = flat, exactly sailor_hip_ecs_sweep_range).  World matrices and boxes are
+ * the same in both modes.  Only the slice's bits of dVisibility and of trace->dInserted are written; a proper slice of a hierarchy deeper than four
+ * levels is refused as there.  Records on the context's stream only: no synchronisation, no host reads. */
+SAILOR_HIP_API int sailor_hip_ecs_sweep_traced(SailorHipContext* ctx, uint32_t numEntities,
+                                               const SailorTransform* dTransforms, const uint32_t* dParent,
+                                               const uint32_t* levelOffsets, uint32_t numLevels,
+                                               const SailorAABB* dLocalAabb, const float* planes,
+                                               float* dWorld, SailorAABB* dWorldAabb, uint64_t* dVisibility,
+                                               uint32_t entityBegin, uint32_t entityEnd, const SailorSceneTrace* trace);
 SAILOR_HIP_API int sailor_hip_ecs_range_for_rank(uint32_t numEntities, int32_t rank, int32_t worldSize, uint32_t* outBegin, uint32_t* outEnd,
                                                  uint32_t* outWordsPerRank /* or NULL */);
 SAILOR_HIP_API int sailor_hip_exchange_visibility(SailorHipContext* ctx, void* comm, int32_t rank, int32_t worldSize, uint32_t numEntities,
@@ -574,6 +607,11 @@ SAILOR_HIP_API int sailor_hip_shadow_resolve(SailorHipContext* ctx, const float*
  * stay on the host, on these sets. */
 SAILOR_HIP_API int sailor_hip_csm_caster_masks(SailorHipContext* ctx, uint32_t numEntities, const SailorAABB* dWorldAabb, const float* cascadePlanes,
                                                uint32_t numCascades, uint64_t* dMasks);
+/* The same lists as LightingECS.cpp:296 really builds them, `TraceScene(frustums[k], true)` through the octree: trace as for sailor_hip_ecs_sweep_traced
+ * (NULL = flat, exactly sailor_hip_csm_caster_masks); the root's box is tested against each cascade's frustum.  trace->dInserted, when given, gets
+ * ceil(numEntities / 64) words, the same for every cascade.  Records only. */
+SAILOR_HIP_API int sailor_hip_csm_caster_masks_traced(SailorHipContext* ctx, uint32_t numEntities, const SailorAABB* dWorldAabb, const float* cascadePlanes,
+                                                      uint32_t numCascades, uint64_t* dMasks, const SailorSceneTrace* trace);
 
 /* Replaces: FrustumCulling of Content/Shaders/ComputeMeshCulling.shader:96-110 (+ CreateViewFrustum, Math.glsl:185-222)
  * for the Dispatch at RHI/Batch.hpp:188; writes PerInstanceData::isCulled in place for the instances

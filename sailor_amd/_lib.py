@@ -35,6 +35,11 @@ SHADOWMAP_R16F = 0
 SHADOWMAP_RGBA32F = 1
 SHADOWMAP_R32F = 2
 
+TRACE_FLAT_FLOAT_BOXES = 0    # the float world boxes, tested flat (sailor_hip_ecs_sweep)
+TRACE_OCTREE_INT_BOXES = 1    # RHISceneView::TraceScene as the reference runs it: integer boxes in a TOctree
+OCTREE_ROOT_SIZE = 16536 * 16  # RHI/SceneView.h:91-92
+TRACE_MODES = {"flat": TRACE_FLAT_FLOAT_BOXES, "octree": TRACE_OCTREE_INT_BOXES}
+
 
 class SailorHipError(RuntimeError):
     def __init__(self, status: int, where: str, detail: str = ""):
@@ -78,6 +83,17 @@ class CsmDesc(C.Structure):
 class CsmView(C.Structure):  # include/sailor_hip.h SailorCsmView (the transform half of CSMLightState, ECS/LightingECS.cpp:14-38)
     _fields_ = [("componentIndex", C.c_uint32), ("cameraPosition", C.c_float * 4), ("cameraRotation", C.c_float * 4),
                 ("lightPosition", C.c_float * 4), ("lightRotation", C.c_float * 4)]
+
+
+class SceneTrace(C.Structure):  # include/sailor_hip.h SailorSceneTrace
+    _fields_ = [("mode", C.c_uint32), ("rootSize", C.c_uint32), ("dInserted", C.c_void_p)]
+
+
+def trace_mode(name: str) -> int:
+    """'flat' | 'octree' -> SAILOR_TRACE_*; anything else raises"""
+    if name not in TRACE_MODES:
+        raise ValueError(f"unknown trace mode {name!r}: expected one of {sorted(TRACE_MODES)}")
+    return TRACE_MODES[name]
 
 
 class HiZDesc(C.Structure):
@@ -152,6 +168,8 @@ SIGNATURES = {
     "sailor_hip_buffer_copy": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.c_size_t]),
     "sailor_hip_ecs_sweep": (C.c_int, [_P, C.c_uint32, _P, _P, C.POINTER(C.c_uint32), C.c_uint32, _P, C.POINTER(C.c_float), _P, _P, _P]),
     "sailor_hip_ecs_sweep_range": (C.c_int, [_P, C.c_uint32, _P, _P, C.POINTER(C.c_uint32), C.c_uint32, _P, C.POINTER(C.c_float), _P, _P, _P, C.c_uint32, C.c_uint32]),
+    "sailor_hip_ecs_sweep_traced": (C.c_int, [_P, C.c_uint32, _P, _P, C.POINTER(C.c_uint32), C.c_uint32, _P, C.POINTER(C.c_float), _P, _P, _P, C.c_uint32,
+                                              C.c_uint32, C.POINTER(SceneTrace)]),
     "sailor_hip_ecs_range_for_rank": (C.c_int, [C.c_uint32, C.c_int32, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "sailor_hip_exchange_adapt": (C.c_int, [_P, _P, _P, _P]),
     "sailor_hip_exchange_set_slot_words": (C.c_int, [_P, C.c_size_t]),
@@ -162,6 +180,7 @@ SIGNATURES = {
     "sailor_hip_raster_depth_camera": (C.c_int, [_P, C.POINTER(UboFrameData), _P, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_int32, C.c_int32, _P, C.c_uint32, _P]),
     "sailor_hip_shadow_resolve": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "sailor_hip_csm_caster_masks": (C.c_int, [_P, C.c_uint32, _P, C.POINTER(C.c_float), C.c_uint32, _P]),
+    "sailor_hip_csm_caster_masks_traced": (C.c_int, [_P, C.c_uint32, _P, C.POINTER(C.c_float), C.c_uint32, _P, C.POINTER(SceneTrace)]),
     "sailor_hip_hiz_downscale": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32]),
     "sailor_hip_hiz_build": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32]),
     "sailor_hip_mesh_cull_flags": (C.c_int, [_P, C.POINTER(UboFrameData), _P, C.c_uint32, C.c_uint32, C.POINTER(HiZDesc)]),

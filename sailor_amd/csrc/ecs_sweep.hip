@@ -89,6 +89,55 @@ __device__ __forceinline__ bool ecs_bounds_vis(const float* W, const float* la, 
     return vis;
 }
 
+// ---- E4 as the reference runs it: RHISceneView::TraceScene through TOctree (RHI/SceneView.cpp:56,170; ECS/LightingECS.cpp:296) ------------------
+// The octree stores every box TRUNCATED to integers (ECS/StaticMeshRendererECS.cpp:81,96,132 pass GetCenter() / GetExtents() to
+// TOctree::Update(const glm::ivec3&, const glm::ivec3&, ...)), inserts an element only where the root strictly contains it (Containers/Octree.h:44-53:
+// the root is ivec3(0) wide rootSize, RHI/SceneView.h:91-92) and traces Frustum::OverlapsAABB over AABB(ivec3 pos, ivec3 ext) (Octree.h:239-274).  With
+// every truncated extent >= 0 an element lies inside every node on its path and OverlapsAABB is monotone in the box, so the hierarchical walk visits
+// exactly the elements whose own integer box passes (tests/test_oracle_cpu.py holds it): per entity, truncate, test the root containment, test the
+// rebuilt box -- no tree.  A negative extent (a caller's inverted box) makes Contains an overlap test; the walk's answer then depends on the other
+// elements and is a subset of this one (include/sailor_hip.h: a stated divergence).
+struct TraceArgs {
+    int half;                         // rootSize / 2 as the integer TNode::Contains uses (<= 2^29)
+    uint32_t rootVisible;             // bit k: frustum k passes the root's own box (Octree.h:239-247, evaluated once on the host)
+    unsigned long long* inserted;     // one bit per entity, or NULL
+};
+
+// Frustum::OverlapsAABB (Math/Bounds.cpp:245-260): the expression of ecs_bounds_vis, one plane set of 6 x vec4, for the octree mode and the host's
+// root test (the flat paths keep their own copy, so their instructions are exactly those they had before the octree mode)
+__host__ __device__ __forceinline__ bool overlaps_aabb(const float* pl, const float* mn, const float* mx)
+{
+    bool vis = true;
+#pragma unroll
+    for (int p = 0; p < 6; p++) {
+        const float ax = mn[0] * pl[4 * p + 0], bx = mx[0] * pl[4 * p + 0];
+        const float ay = mn[1] * pl[4 * p + 1], by = mx[1] * pl[4 * p + 1];
+        const float az = mn[2] * pl[4 * p + 2], bz = mx[2] * pl[4 * p + 2];
+        const float d = (ax < bx ? bx : ax) + (ay < by ? by : ay) + (az < bz ? bz : az) + pl[4 * p + 3];
+        vis = vis && (d > 0.0f);
+    }
+    return vis;
+}
+
+// The world box as TOctree holds it: returns "inserted" (the root strictly contains the integer box) and the integer box rebuilt as floats,
+// (float)pos -+ (float)ext (Math/Bounds.cpp:473-477).  glm::ivec3(float) is undefined in C++ for NaN, +-Inf and magnitudes >= 2^31: such a
+// component is checked before the conversion and makes the element neither inserted nor visible.  The containment cannot wrap around.
+__device__ __forceinline__ bool octree_int_box(const float* mn, const float* mx, int half, float* imn, float* imx)
+{
+    bool ins = true;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const float c = (mn[a] + mx[a]) * 0.5f, e = (mx[a] - mn[a]) * 0.5f; // AABB::GetCenter / GetExtents (Math/Bounds.cpp:455-463)
+        const bool defined = fabsf(c) < 2147483648.0f && fabsf(e) < 2147483648.0f; // false for NaN and +-Inf as well
+        const int p = (int)(defined ? c : 0.0f), x = (int)(defined ? e : 0.0f); // truncation towards zero
+        // saturating 32-bit p - x and p + x: a clamped sum lies beyond +-half exactly when the true sum does (half <= 2^29)
+        ins = ins && defined && -half < __builtin_elementwise_sub_sat(p, x) && half > __builtin_elementwise_add_sat(p, x);
+        imn[a] = (float)p - (float)x;
+        imx[a] = (float)p + (float)x;
+    }
+    return ins;
+}
+
 // world = parentWorld * relative (TransformECS.cpp:201) or relative for a root (:192-195)
 __device__ __forceinline__ void ecs_world(const float4 pos, const float4 rot, const float4 scl, bool hasParent, const float4* __restrict__ parentWorld, float* W)
 {
@@ -102,6 +151,14 @@ __device__ __forceinline__ void ecs_world(const float4 pos, const float4 rot, co
         const float P[16] = { c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w, c2.x, c2.y, c2.z, c2.w, c3.x, c3.y, c3.z, c3.w };
         mat_mul(P, rel, W);
     }
+}
+
+// The sweep's visibility bit in octree mode (the flat bit of ecs_bounds_vis is replaced); *ins = the element is in the octree
+__device__ __forceinline__ bool trace_scene_vis(const float* omin, const float* omax, const Planes6& planes, const TraceArgs& trace, bool* ins)
+{
+    float imn[3], imx[3];
+    *ins = octree_int_box(omin, omax, trace.half, imn, imx);
+    return *ins && trace.rootVisible && overlaps_aabb(planes.p, imn, imx);
 }
 
 // FUSED levels: the world matrix of an entity of level d is the left-to-right product rel(root) * rel(..) * rel(self), every
@@ -153,10 +210,12 @@ __device__ __forceinline__ void ecs_world_fused(const float4* __restrict__ trs, 
 
 #define ECS_WAVE_F4 352 // float4 slots of LDS per wave: max(TRS 192 + box 96, world 256 + box 96)
 
-template <bool FUSED>
+// OCTREE: visibility as TraceScene over the integer boxes (see TraceArgs) instead of the flat float test; the matrices and boxes are the same
+template <bool FUSED, bool OCTREE>
 __global__ __launch_bounds__(256) void k4_ecs_level(uint32_t lo, uint32_t hi, const float4* __restrict__ trs, const uint32_t* __restrict__ parent,
                                                      const float* __restrict__ localAabb, Planes6 planes, int boxVec,
-                                                     float4* __restrict__ world, float* __restrict__ worldAabb, unsigned long long* __restrict__ visibility)
+                                                     float4* __restrict__ world, float* __restrict__ worldAabb, unsigned long long* __restrict__ visibility,
+                                                     TraceArgs trace)
 {
     // One wave owns one 64-entity visibility word.  The records are AoS (48 B TRS, 24 B box in; 64 B matrix, 24 B box out), so a
     // lane-per-entity access is a 16-byte (or 4-byte) request every 48 / 64 / 24 bytes -- four to six partial-line requests
@@ -172,7 +231,7 @@ __global__ __launch_bounds__(256) void k4_ecs_level(uint32_t lo, uint32_t hi, co
     const uint32_t base = word * 64, i = base + lane;
     const bool active = i >= lo && i < hi;
     const unsigned long long amask = __ballot(active);
-    bool vis = false;
+    bool vis = false, ins = false;
     float W[16], omin[3], omax[3];
     if (amask == ~0ull && boxVec) {
         float4* S = sStage[wave];
@@ -189,6 +248,7 @@ __global__ __launch_bounds__(256) void k4_ecs_level(uint32_t lo, uint32_t hi, co
         if (FUSED) ecs_world_fused(trs, parent, pos, rot, scl, par, W);
         else ecs_world(pos, rot, scl, par != 0xFFFFFFFFu, world + (size_t)(par != 0xFFFFFFFFu ? par : 0u) * 4, W);
         vis = ecs_bounds_vis(W, la, planes, omin, omax);
+        if (OCTREE) vis = trace_scene_vis(omin, omax, planes, trace, &ins);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // every lane has read its inputs: the slots are reused for the outputs
         S[lane * 4 + 0] = make_float4(W[0], W[1], W[2], W[3]);
         S[lane * 4 + 1] = make_float4(W[4], W[5], W[6], W[7]);
@@ -210,6 +270,7 @@ __global__ __launch_bounds__(256) void k4_ecs_level(uint32_t lo, uint32_t hi, co
         if (FUSED) ecs_world_fused(trs, parent, pos, rot, scl, par, W);
         else ecs_world(pos, rot, scl, par != 0xFFFFFFFFu, world + (size_t)(par != 0xFFFFFFFFu ? par : 0u) * 4, W);
         vis = ecs_bounds_vis(W, la, planes, omin, omax);
+        if (OCTREE) vis = trace_scene_vis(omin, omax, planes, trace, &ins);
         float4* ow = world + (size_t)i * 4;
         ow[0] = make_float4(W[0], W[1], W[2], W[3]);
         ow[1] = make_float4(W[4], W[5], W[6], W[7]);
@@ -223,6 +284,13 @@ __global__ __launch_bounds__(256) void k4_ecs_level(uint32_t lo, uint32_t hi, co
         // a word straddling two levels is completed by two stream-ordered launches: keep the other launch's bits
         const unsigned long long old = (amask == ~0ull) ? 0ull : visibility[word];
         visibility[word] = (old & ~amask) | (vmask & amask);
+    }
+    if (OCTREE && trace.inserted) {
+        const unsigned long long imask = __ballot(ins);
+        if (lane == 0 && amask) {
+            const unsigned long long old = (amask == ~0ull) ? 0ull : trace.inserted[word];
+            trace.inserted[word] = (old & ~amask) | (imask & amask);
+        }
     }
 }
 
@@ -248,8 +316,10 @@ __device__ __forceinline__ void msc_plane(const float* p1, const float* p2, floa
 // Math/Bounds.cpp:245-260, the same expression as the camera test above); one ballot word per cascade and 64 entities.
 struct CascadePlanes { float p[SAILOR_NUM_CSM_CASCADES][24]; };
 
+// OCTREE: TraceScene(frustums[k], true) over the integer boxes (see TraceArgs), bit k of rootVisible per cascade
+template <bool OCTREE>
 __global__ __launch_bounds__(256) void k4_csm_caster_masks(uint32_t n, const float* __restrict__ worldAabb, CascadePlanes P, int numCascades,
-                                                            unsigned long long* __restrict__ masks, uint32_t words)
+                                                            unsigned long long* __restrict__ masks, uint32_t words, TraceArgs trace)
 {
     __shared__ float sBox[4][384]; // a wave's 64 boxes = 1 536 contiguous bytes: moved as 96 float4s, then read back one box per lane
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -268,20 +338,31 @@ __global__ __launch_bounds__(256) void k4_csm_caster_masks(uint32_t n, const flo
         const float* b = worldAabb + 6 * (size_t)i;
         mn[0] = b[0]; mn[1] = b[1]; mn[2] = b[2]; mx[0] = b[3]; mx[1] = b[4]; mx[2] = b[5];
     }
+    bool ins = false;
+    float imn[3], imx[3];
+    if (OCTREE) ins = i < n && octree_int_box(mn, mx, trace.half, imn, imx);
 #pragma unroll
     for (int k = 0; k < SAILOR_NUM_CSM_CASCADES; k++) {
         if (k >= numCascades) break;
         bool inside = i < n;
+        if (OCTREE) {
+            inside = ins && ((trace.rootVisible >> k) & 1u) && overlaps_aabb(P.p[k], imn, imx);
+        } else {
 #pragma unroll
-        for (int p = 0; p < 6; p++) {
-            const float ax = mn[0] * P.p[k][4 * p + 0], bx = mx[0] * P.p[k][4 * p + 0];
-            const float ay = mn[1] * P.p[k][4 * p + 1], by = mx[1] * P.p[k][4 * p + 1];
-            const float az = mn[2] * P.p[k][4 * p + 2], bz = mx[2] * P.p[k][4 * p + 2];
-            const float d = (ax < bx ? bx : ax) + (ay < by ? by : ay) + (az < bz ? bz : az) + P.p[k][4 * p + 3];
-            inside = inside && (d > 0.0f);
+            for (int p = 0; p < 6; p++) {
+                const float ax = mn[0] * P.p[k][4 * p + 0], bx = mx[0] * P.p[k][4 * p + 0];
+                const float ay = mn[1] * P.p[k][4 * p + 1], by = mx[1] * P.p[k][4 * p + 1];
+                const float az = mn[2] * P.p[k][4 * p + 2], bz = mx[2] * P.p[k][4 * p + 2];
+                const float d = (ax < bx ? bx : ax) + (ay < by ? by : ay) + (az < bz ? bz : az) + P.p[k][4 * p + 3];
+                inside = inside && (d > 0.0f);
+            }
         }
         const unsigned long long m = __ballot(inside);
         if ((threadIdx.x & 63) == 0 && (i >> 6) < words) masks[(size_t)k * words + (i >> 6)] = m;
+    }
+    if (OCTREE && trace.inserted) {
+        const unsigned long long m = __ballot(ins);
+        if ((threadIdx.x & 63) == 0 && (i >> 6) < words) trace.inserted[i >> 6] = m;
     }
 }
 
@@ -427,18 +508,59 @@ __global__ __launch_bounds__(256) void k4_mesh_frustum_cull(Mat4 view, Mat4 invP
     }
 }
 
+// SailorSceneTrace -> the kernels' TraceArgs; *octree = false for the flat mode.  numPlaneSets frusta of 6 x vec4 at `planes`: bit k of rootVisible
+// is frustum k against the root's own box, AABB(ivec3(0), rootSize * 0.5f) (Containers/Octree.h:239-247).
+static int trace_args(const SailorSceneTrace* trace, const float* planes, uint32_t numPlaneSets, TraceArgs* out, bool* octree)
+{
+    *out = TraceArgs{ 0, 0u, nullptr };
+    *octree = false;
+    if (!trace) return SAILOR_HIP_OK;
+    if (trace->mode != SAILOR_TRACE_FLAT_FLOAT_BOXES && trace->mode != SAILOR_TRACE_OCTREE_INT_BOXES) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (trace->rootSize != 0 && (trace->rootSize < 2 || trace->rootSize > (1u << 30))) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (trace->mode == SAILOR_TRACE_FLAT_FLOAT_BOXES) return trace->dInserted ? SAILOR_HIP_ERR_INVALID_ARGUMENT : SAILOR_HIP_OK; // nothing is inserted flat
+    if ((uintptr_t)trace->dInserted & 7) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    const uint32_t rootSize = trace->rootSize ? trace->rootSize : SAILOR_OCTREE_ROOT_SIZE;
+    const float h = (float)rootSize * 0.5f;
+    const float mn[3] = { 0.0f - h, 0.0f - h, 0.0f - h }, mx[3] = { 0.0f + h, 0.0f + h, 0.0f + h };
+    out->half = (int)(rootSize / 2);
+    for (uint32_t k = 0; k < numPlaneSets; k++)
+        if (overlaps_aabb(planes + 24 * k, mn, mx)) out->rootVisible |= 1u << k;
+    out->inserted = (unsigned long long*)trace->dInserted;
+    *octree = true;
+    return SAILOR_HIP_OK;
+}
+
+template <bool FUSED>
+static void launch_ecs_level(SailorHipContext* ctx, bool octree, uint32_t lo, uint32_t hi, const SailorTransform* dTransforms, const uint32_t* dParent,
+                             const SailorAABB* dLocalAabb, const Planes6& P, int boxVec, float* dWorld, SailorAABB* dWorldAabb, uint64_t* dVisibility,
+                             const TraceArgs& t)
+{
+    const uint32_t words = ((hi + 63) >> 6) - (lo >> 6);
+    if (octree)
+        hipLaunchKernelGGL((k4_ecs_level<FUSED, true>), dim3((words + 3) / 4), dim3(256), 0, ctx->stream, lo, hi, (const float4*)dTransforms, dParent,
+                           (const float*)dLocalAabb, P, boxVec, (float4*)dWorld, (float*)dWorldAabb, (unsigned long long*)dVisibility, t);
+    else
+        hipLaunchKernelGGL((k4_ecs_level<FUSED, false>), dim3((words + 3) / 4), dim3(256), 0, ctx->stream, lo, hi, (const float4*)dTransforms, dParent,
+                           (const float*)dLocalAabb, P, boxVec, (float4*)dWorld, (float*)dWorldAabb, (unsigned long long*)dVisibility, t);
+}
+
 extern "C" {
 
 // [entityBegin, entityEnd): the slice of the entity array this call sweeps (the split of K4 across the ranks of a node, SURVEY.md 8e: contiguous index
 // ranges, one all-gather of the visibility words behind it).  Hierarchies of up to ECS_FUSED_LEVELS levels -- the one-launch form, in which an entity
 // rebuilds its ancestors' relative matrices from their TRS records and so needs nothing another rank computes -- take any slice; a deeper hierarchy
 // reads its parents' WORLD matrices, which only a sweep of the whole set has: a proper slice of one is refused (SAILOR_HIP_ERR_UNSUPPORTED: sweep it whole
-// on every rank).  Only the slice's entries of dWorld / dWorldAabb and the slice's bits of dVisibility are written.
-int sailor_hip_ecs_sweep_range(SailorHipContext* ctx, uint32_t numEntities, const SailorTransform* dTransforms, const uint32_t* dParent,
-                               const uint32_t* levelOffsets, uint32_t numLevels, const SailorAABB* dLocalAabb, const float* planes,
-                               float* dWorld, SailorAABB* dWorldAabb, uint64_t* dVisibility, uint32_t entityBegin, uint32_t entityEnd)
+// on every rank).  Only the slice's entries of dWorld / dWorldAabb and the slice's bits of dVisibility (and of trace->dInserted) are written.
+int sailor_hip_ecs_sweep_traced(SailorHipContext* ctx, uint32_t numEntities, const SailorTransform* dTransforms, const uint32_t* dParent,
+                                const uint32_t* levelOffsets, uint32_t numLevels, const SailorAABB* dLocalAabb, const float* planes,
+                                float* dWorld, SailorAABB* dWorldAabb, uint64_t* dVisibility, uint32_t entityBegin, uint32_t entityEnd,
+                                const SailorSceneTrace* trace)
 {
     if (!ctx || !levelOffsets || !planes) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    TraceArgs t;
+    bool octree;
+    const int rc = trace_args(trace, planes, 1u, &t, &octree);
+    if (rc != SAILOR_HIP_OK) return rc;
     SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device)); // a host thread may drive several contexts
     if (entityBegin > entityEnd || entityEnd > numEntities) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     if (numEntities == 0 || entityBegin == entityEnd) return SAILOR_HIP_OK;
@@ -451,9 +573,7 @@ int sailor_hip_ecs_sweep_range(SailorHipContext* ctx, uint32_t numEntities, cons
     for (uint32_t l = 0; l < numLevels; l++)
         if (levelOffsets[l + 1] < levelOffsets[l] || levelOffsets[l + 1] > numEntities) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     if (numLevels <= ECS_FUSED_LEVELS) { // shallow hierarchy: every level in one launch (ancestors' relative matrices are recomputed)
-        const uint32_t words = ((entityEnd + 63) >> 6) - (entityBegin >> 6);
-        hipLaunchKernelGGL(k4_ecs_level<true>, dim3((words + 3) / 4), dim3(256), 0, ctx->stream, entityBegin, entityEnd, (const float4*)dTransforms, dParent,
-                           (const float*)dLocalAabb, P, boxVec, (float4*)dWorld, (float*)dWorldAabb, (unsigned long long*)dVisibility);
+        launch_ecs_level<true>(ctx, octree, entityBegin, entityEnd, dTransforms, dParent, dLocalAabb, P, boxVec, dWorld, dWorldAabb, dVisibility, t);
         SAILOR_CHECK_LAUNCH(ctx, "k4_ecs_level<fused>");
         return SAILOR_HIP_OK;
     }
@@ -461,12 +581,18 @@ int sailor_hip_ecs_sweep_range(SailorHipContext* ctx, uint32_t numEntities, cons
     for (uint32_t l = 0; l < numLevels; l++) {
         const uint32_t lo = levelOffsets[l], hi = levelOffsets[l + 1];
         if (hi == lo) continue;
-        const uint32_t words = ((hi + 63) >> 6) - (lo >> 6);
-        hipLaunchKernelGGL(k4_ecs_level<false>, dim3((words + 3) / 4), dim3(256), 0, ctx->stream, lo, hi, (const float4*)dTransforms, dParent,
-                           (const float*)dLocalAabb, P, boxVec, (float4*)dWorld, (float*)dWorldAabb, (unsigned long long*)dVisibility);
+        launch_ecs_level<false>(ctx, octree, lo, hi, dTransforms, dParent, dLocalAabb, P, boxVec, dWorld, dWorldAabb, dVisibility, t);
         SAILOR_CHECK_LAUNCH(ctx, "k4_ecs_level");
     }
     return SAILOR_HIP_OK;
+}
+
+int sailor_hip_ecs_sweep_range(SailorHipContext* ctx, uint32_t numEntities, const SailorTransform* dTransforms, const uint32_t* dParent,
+                               const uint32_t* levelOffsets, uint32_t numLevels, const SailorAABB* dLocalAabb, const float* planes,
+                               float* dWorld, SailorAABB* dWorldAabb, uint64_t* dVisibility, uint32_t entityBegin, uint32_t entityEnd)
+{
+    return sailor_hip_ecs_sweep_traced(ctx, numEntities, dTransforms, dParent, levelOffsets, numLevels, dLocalAabb, planes, dWorld, dWorldAabb, dVisibility,
+                                       entityBegin, entityEnd, nullptr);
 }
 
 int sailor_hip_ecs_sweep(SailorHipContext* ctx, uint32_t numEntities, const SailorTransform* dTransforms, const uint32_t* dParent,
@@ -523,10 +649,14 @@ int sailor_hip_mesh_frustum_cull(SailorHipContext* ctx, const SailorUboFrameData
     return sailor_hip_mesh_cull_flags(ctx, frame, dInstances, numInstances, firstInstanceIndex, nullptr);
 }
 
-int sailor_hip_csm_caster_masks(SailorHipContext* ctx, uint32_t numEntities, const SailorAABB* dWorldAabb, const float* cascadePlanes, uint32_t numCascades,
-                                uint64_t* dMasks)
+int sailor_hip_csm_caster_masks_traced(SailorHipContext* ctx, uint32_t numEntities, const SailorAABB* dWorldAabb, const float* cascadePlanes,
+                                       uint32_t numCascades, uint64_t* dMasks, const SailorSceneTrace* trace)
 {
     if (!ctx || !cascadePlanes || numCascades == 0 || numCascades > SAILOR_NUM_CSM_CASCADES) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    TraceArgs t;
+    bool octree;
+    const int rc = trace_args(trace, cascadePlanes, numCascades, &t, &octree);
+    if (rc != SAILOR_HIP_OK) return rc;
     SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device)); // a host thread may drive several contexts
     if (numEntities == 0) return SAILOR_HIP_OK;
     if (!dWorldAabb || !dMasks) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
@@ -534,10 +664,20 @@ int sailor_hip_csm_caster_masks(SailorHipContext* ctx, uint32_t numEntities, con
     memset(&P, 0, sizeof P);
     memcpy(P.p, cascadePlanes, (size_t)numCascades * 24 * sizeof(float));
     const uint32_t words = (numEntities + 63) / 64;
-    hipLaunchKernelGGL(k4_csm_caster_masks, dim3((numEntities + 255) / 256), dim3(256), 0, ctx->stream, numEntities, (const float*)dWorldAabb, P, (int)numCascades,
-                       (unsigned long long*)dMasks, words);
+    if (octree)
+        hipLaunchKernelGGL(k4_csm_caster_masks<true>, dim3((numEntities + 255) / 256), dim3(256), 0, ctx->stream, numEntities, (const float*)dWorldAabb, P,
+                           (int)numCascades, (unsigned long long*)dMasks, words, t);
+    else
+        hipLaunchKernelGGL(k4_csm_caster_masks<false>, dim3((numEntities + 255) / 256), dim3(256), 0, ctx->stream, numEntities, (const float*)dWorldAabb, P,
+                           (int)numCascades, (unsigned long long*)dMasks, words, t);
     SAILOR_CHECK_LAUNCH(ctx, "k4_csm_caster_masks");
     return SAILOR_HIP_OK;
+}
+
+int sailor_hip_csm_caster_masks(SailorHipContext* ctx, uint32_t numEntities, const SailorAABB* dWorldAabb, const float* cascadePlanes, uint32_t numCascades,
+                                uint64_t* dMasks)
+{
+    return sailor_hip_csm_caster_masks_traced(ctx, numEntities, dWorldAabb, cascadePlanes, numCascades, dMasks, nullptr);
 }
 
 int sailor_hip_hiz_downscale(SailorHipContext* ctx, const float* dSrc, int32_t srcWidth, int32_t srcHeight, float* dDst, int32_t dstWidth, int32_t dstHeight)

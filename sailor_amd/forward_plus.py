@@ -360,11 +360,23 @@ def ecs_range_for_rank(n: int, rank: int, world: int):
     return int(b.value), int(e.value), int(per.value)
 
 
+def _scene_trace(trace: str, octree_root_size: int | None, inserted: torch.Tensor | None) -> _lib.SceneTrace:
+    mode = _lib.trace_mode(trace)
+    if mode == _lib.TRACE_FLAT_FLOAT_BOXES and (octree_root_size is not None or inserted is not None):
+        raise ValueError("octree_root_size and inserted words belong to trace='octree'")
+    return _lib.SceneTrace(mode, 0 if octree_root_size is None else octree_root_size, _ptr(inserted))
+
+
 class EcsSweep:
     """K4 on one GPU over level-sorted entities.  rank / world: this GPU sweeps its slice of an equal split only (sailor_hip_ecs_sweep_range); the
-    visibility buffer then has room for every rank's words and exchange_visibility() completes it."""
+    visibility buffer then has room for every rank's words and exchange_visibility() completes it.
+    trace: "flat" tests the float world boxes (the default, sailor_hip_ecs_sweep); "octree" gives RHISceneView::TraceScene's set as the reference
+    computes it over integer-truncated boxes (sailor_hip_ecs_sweep_traced) and fills `.inserted` (one bit per entity: in the octree at all) as well;
+    octree_root_size: the root's size (None = SceneView.h's 264 576).  The matrices and boxes are the same in both modes.  With world > 1 each rank's
+    `.inserted` holds its own slice's words only: exchange_visibility() gathers the visibility words, not the inserted ones."""
 
-    def __init__(self, ctx: HipContext, entities, rank: int = 0, world: int = 1):
+    def __init__(self, ctx: HipContext, entities, rank: int = 0, world: int = 1, trace: str = "flat", octree_root_size: int | None = None):
+        _scene_trace(trace, octree_root_size, None)  # an unknown mode raises before anything is allocated
         self.ctx = ctx
         dev = ctx.device
         self.n = len(entities.parent)
@@ -377,11 +389,21 @@ class EcsSweep:
         self.world = torch.empty((self.n, 16), dtype=torch.float32, device=dev)
         self.world_aabb = torch.empty((self.n, 6), dtype=torch.float32, device=dev)
         self.visibility = torch.zeros(max((self.n + 63) // 64, world * self.words_per_rank), dtype=torch.int64, device=dev)
+        self.trace = trace
+        self.inserted = torch.zeros_like(self.visibility) if trace == "octree" else None
+        self._trace = _scene_trace(trace, octree_root_size, self.inserted)
 
     def run(self, planes: np.ndarray):
         planes = np.ascontiguousarray(planes, np.float32).reshape(24)
         lib = self.ctx._lib
-        if self.world_size == 1:
+        if self.trace != "flat":
+            _lib.check(lib.sailor_hip_ecs_sweep_traced(self.ctx.handle, self.n, _ptr(self.trs), _ptr(self.parent),
+                                                       self.level_offsets.ctypes.data_as(C.POINTER(C.c_uint32)), len(self.level_offsets) - 1,
+                                                       _ptr(self.local_aabb), planes.ctypes.data_as(C.POINTER(C.c_float)),
+                                                       _ptr(self.world), _ptr(self.world_aabb), _ptr(self.visibility), self.begin, self.end,
+                                                       C.byref(self._trace)),
+                       "sailor_hip_ecs_sweep_traced", self.ctx.handle)
+        elif self.world_size == 1:
             _lib.check(lib.sailor_hip_ecs_sweep(self.ctx.handle, self.n, _ptr(self.trs), _ptr(self.parent),
                                                 self.level_offsets.ctypes.data_as(C.POINTER(C.c_uint32)), len(self.level_offsets) - 1,
                                                 _ptr(self.local_aabb), planes.ctypes.data_as(C.POINTER(C.c_float)),
@@ -451,13 +473,24 @@ def shadow_resolve(ctx: "HipContext", depth: torch.Tensor, fmt: int) -> torch.Te
     return out
 
 
-def csm_caster_masks(ctx: "HipContext", world_aabb: torch.Tensor, cascade_planes: np.ndarray) -> torch.Tensor:
-    """sailor_hip_csm_caster_masks: world AABBs [n, 6] (the ECS sweep's output) x cascade frusta [k, 6, 4] -> int64 [k, ceil(n / 64)] bitmasks"""
+def csm_caster_masks(ctx: "HipContext", world_aabb: torch.Tensor, cascade_planes: np.ndarray, trace: str = "flat", octree_root_size: int | None = None,
+                     inserted: torch.Tensor | None = None) -> torch.Tensor:
+    """sailor_hip_csm_caster_masks: world AABBs [n, 6] (the ECS sweep's output) x cascade frusta [k, 6, 4] -> int64 [k, ceil(n / 64)] bitmasks.
+    trace="octree": LightingECS.cpp:296's TraceScene(frustums[k], true) through the octree of integer boxes (sailor_hip_csm_caster_masks_traced);
+    `inserted` (int64 [ceil(n / 64)], octree only) then receives the in-the-octree bits."""
+    tr = _scene_trace(trace, octree_root_size, inserted)
     pl = np.ascontiguousarray(cascade_planes, np.float32).reshape(-1, 24)
     n = world_aabb.shape[0]
+    if inserted is not None and not (inserted.dtype == torch.int64 and inserted.is_contiguous() and inserted.numel() >= (n + 63) // 64):
+        raise ValueError(f"inserted must be a contiguous int64 tensor of at least {(n + 63) // 64} words")
     out = torch.empty((len(pl), (n + 63) // 64), dtype=torch.int64, device=ctx.device)  # every word is written
-    _lib.check(ctx._lib.sailor_hip_csm_caster_masks(ctx.handle, n, _ptr(world_aabb), pl.ctypes.data_as(C.POINTER(C.c_float)), len(pl), _ptr(out)),
-               "sailor_hip_csm_caster_masks", ctx.handle)
+    if trace == "flat":
+        _lib.check(ctx._lib.sailor_hip_csm_caster_masks(ctx.handle, n, _ptr(world_aabb), pl.ctypes.data_as(C.POINTER(C.c_float)), len(pl), _ptr(out)),
+                   "sailor_hip_csm_caster_masks", ctx.handle)
+    else:
+        _lib.check(ctx._lib.sailor_hip_csm_caster_masks_traced(ctx.handle, n, _ptr(world_aabb), pl.ctypes.data_as(C.POINTER(C.c_float)), len(pl), _ptr(out),
+                                                               C.byref(tr)),
+                   "sailor_hip_csm_caster_masks_traced", ctx.handle)
     return out
 
 

@@ -162,12 +162,34 @@ EcsSweepSystem::EcsSweepSystem(const SailorTransform* transforms, const uint32_t
     driver->SubmitCommandList(cmd);
 }
 
+void EcsSweepSystem::SetTraceMode(uint32_t mode, uint32_t rootSize)
+{
+    m_traceMode = mode;
+    m_rootSize = rootSize;
+    if (mode != SAILOR_TRACE_OCTREE_INT_BOXES || m_inserted) return;
+    // cleared once: the sweep writes the entities' bits only, so the bits past m_count in the last word stay what the buffer held
+    auto driver = Renderer::GetDriver();
+    const size_t bytes = 8 * (((size_t)m_count + 63) / 64);
+    m_inserted = driver->CreateBuffer(bytes);
+    const std::vector<uint8_t> zeros(bytes, 0);
+    auto cmd = driver->CreateCommandList();
+    Renderer::GetDriverCommands()->UpdateBuffer(cmd, m_inserted, zeros.data(), bytes);
+    driver->SubmitCommandList(cmd);
+}
+
 int EcsSweepSystem::Tick(const float* cameraWorld, float aspect, float fovDegrees, float zNear, float zFar)
 {
     float planes[24];
     sailor_host_extract_frustum_planes(cameraWorld, aspect, fovDegrees, zNear, zFar, planes, nullptr); // RHI/SceneView.cpp:158
     auto* hip = dynamic_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver());
     if (!hip) return SAILOR_HIP_ERR_UNSUPPORTED;
+    if (m_traceMode != SAILOR_TRACE_FLAT_FLOAT_BOXES) {
+        const SailorSceneTrace trace = { m_traceMode, m_rootSize, m_inserted ? (uint64_t*)m_inserted->m_hip.m_devicePtr : nullptr };
+        return sailor_hip_ecs_sweep_traced(hip->GetContext(), m_count, (const SailorTransform*)m_transforms->m_hip.m_devicePtr,
+                                           (const uint32_t*)m_parent->m_hip.m_devicePtr, m_levelOffsets.data(), (uint32_t)m_levelOffsets.size() - 1,
+                                           (const SailorAABB*)m_localAabb->m_hip.m_devicePtr, planes, (float*)m_world->m_hip.m_devicePtr,
+                                           (SailorAABB*)m_worldAabb->m_hip.m_devicePtr, (uint64_t*)m_visibility->m_hip.m_devicePtr, 0u, m_count, &trace);
+    }
     return sailor_hip_ecs_sweep(hip->GetContext(), m_count, (const SailorTransform*)m_transforms->m_hip.m_devicePtr, (const uint32_t*)m_parent->m_hip.m_devicePtr,
                                 m_levelOffsets.data(), (uint32_t)m_levelOffsets.size() - 1, (const SailorAABB*)m_localAabb->m_hip.m_devicePtr, planes,
                                 (float*)m_world->m_hip.m_devicePtr, (SailorAABB*)m_worldAabb->m_hip.m_devicePtr, (uint64_t*)m_visibility->m_hip.m_devicePtr);

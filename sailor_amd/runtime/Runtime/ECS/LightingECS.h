@@ -71,10 +71,16 @@ public:
     EcsSweepSystem(const SailorTransform* transforms, const uint32_t* parent, const SailorAABB* localAabb, uint32_t count,
                    const uint32_t* levelOffsets, uint32_t numLevels);
     int Tick(const float* cameraWorld, float aspect, float fovDegrees, float zNear, float zFar);
+    // How Tick decides visibility: SAILOR_TRACE_FLAT_FLOAT_BOXES (the default) tests the float world boxes; SAILOR_TRACE_OCTREE_INT_BOXES gives
+    // RHISceneView::TraceScene's set as the reference computes it (integer boxes in the octree, RHI/SceneView.cpp:170) and fills m_inserted too.
+    // rootSize 0 = SAILOR_OCTREE_ROOT_SIZE.
+    void SetTraceMode(uint32_t mode, uint32_t rootSize = 0);
     RHI::RHIBufferPtr m_transforms, m_parent, m_localAabb, m_world, m_worldAabb, m_visibility;
+    RHI::RHIBufferPtr m_inserted; // octree mode: one bit per entity, in the octree at all
     uint32_t m_count = 0;
 private:
     std::vector<uint32_t> m_levelOffsets;
+    uint32_t m_traceMode = SAILOR_TRACE_FLAT_FLOAT_BOXES, m_rootSize = 0;
 };
 
 } // namespace Sailor

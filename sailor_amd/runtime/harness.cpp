@@ -645,3 +645,19 @@ RT_API int sailor_rt_ecs_sweep(SailorRuntime* rt, const void* transforms, const 
     *outVisibility = rt->sweep->m_visibility->m_hip.m_devicePtr;
     return st;
 }
+
+// the same with EcsSweepSystem's trace mode set first (SAILOR_TRACE_*, rootSize 0 = the reference's); *outInserted = the inserted words (octree mode) or NULL
+RT_API int sailor_rt_ecs_sweep_traced(SailorRuntime* rt, const void* transforms, const uint32_t* parent, const void* localAabb, uint32_t count,
+                                      const uint32_t* levelOffsets, uint32_t numLevels, uint32_t mode, uint32_t rootSize, void** outWorld,
+                                      void** outWorldAabb, void** outVisibility, void** outInserted)
+{
+    rt->sweep.reset(new EcsSweepSystem((const SailorTransform*)transforms, parent, (const SailorAABB*)localAabb, count, levelOffsets, numLevels));
+    rt->sweep->SetTraceMode(mode, rootSize);
+    const auto& c = rt->snapshot.m_camera;
+    const int st = rt->sweep->Tick(c.m_world, c.m_aspect, c.m_fov, c.m_zNear, c.m_zFar);
+    *outWorld = rt->sweep->m_world->m_hip.m_devicePtr;
+    *outWorldAabb = rt->sweep->m_worldAabb->m_hip.m_devicePtr;
+    *outVisibility = rt->sweep->m_visibility->m_hip.m_devicePtr;
+    *outInserted = rt->sweep->m_inserted ? rt->sweep->m_inserted->m_hip.m_devicePtr : nullptr;
+    return st;
+}

@@ -66,6 +66,8 @@ def load() -> C.CDLL:
         rt.sailor_rt_buffer.restype = P
         rt.sailor_rt_buffer.argtypes = [P, C.c_char_p, C.POINTER(C.c_size_t)]
         rt.sailor_rt_ecs_sweep.argtypes = [P, P, P, P, C.c_uint32, P, C.c_uint32, C.POINTER(P), C.POINTER(P), C.POINTER(P)]
+        rt.sailor_rt_ecs_sweep_traced.argtypes = [P, P, P, P, C.c_uint32, P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(P), C.POINTER(P), C.POINTER(P),
+                                                  C.POINTER(P)]
         _rt = rt
     return _rt
 
@@ -184,6 +186,19 @@ class Runtime:
         st = self.rt.sailor_rt_build_depth_highz(self.h, depth.data_ptr() if depth is not None else None, depth.shape[1] if depth is not None else 0,
                                                  depth.shape[0] if depth is not None else 0, width, height, levels, C.byref(p))
         return st, p.value
+
+    def ecs_sweep_traced(self, entities, trace: str = "octree", octree_root_size: int | None = None):
+        """EcsSweepSystem (host arrays uploaded by the driver) with its trace mode set, ticked against the scene view's camera (set_camera):
+        returns (status, device pointers of the world matrices, world boxes, visibility words, inserted words -- None in flat mode)"""
+        mode = _lib.trace_mode(trace)
+        trs = np.ascontiguousarray(entities.transforms, np.float32)
+        par = np.ascontiguousarray(entities.parent, np.uint32)
+        box = np.ascontiguousarray(entities.local_aabb, np.float32)
+        offs = np.ascontiguousarray(entities.level_offsets, np.uint32)
+        w, a, v, ins = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        st = self.rt.sailor_rt_ecs_sweep_traced(self.h, trs.ctypes.data, par.ctypes.data, box.ctypes.data, len(par), offs.ctypes.data, len(offs) - 1, mode,
+                                                0 if octree_root_size is None else octree_root_size, C.byref(w), C.byref(a), C.byref(v), C.byref(ins))
+        return st, w.value, a.value, v.value, ins.value
 
     def load_world(self, text: str, width: int, height: int, max_objects: int = 4096):
         """load a `.world`: camera -> scene view, LightComponents -> LightingECS (packed by Tick); returns (transforms float32 [n, 12], parents uint32 [n],
