@@ -657,6 +657,56 @@ SAILOR_HIP_API int sailor_hip_mesh_cull_compact(SailorHipContext* ctx, const Sai
                                                 uint32_t numInstances, uint32_t firstInstanceIndex, SailorDrawIndexedIndirectData* dBatches,
                                                 uint32_t numBatches, void* dWorkspace, size_t workspaceBytes);
 
+/* ---- EyeAdaptation: histogram, average luminance, tone map -- the node right behind the two RenderScene passes ----------------
+ * Replaces: the two Dispatches and the full-screen draw recorded by EyeAdaptationNode::Process (FrameGraph/EyeAdaptationNode.cpp:22-221):
+ * Content/Shaders/ComputeHistogram.shader, Content/Shaders/ComputeAverageLuminance.shader and Content/Shaders/Tonemapping.shader with
+ * Content/Shaders/Formats.glsl:1-51.  Targets are fp32 (the project's canonical form of R16G16B16A16_SFLOAT / R16_SFLOAT,
+ * FrameGraphParser.cpp:196): float4 radiance in -- what sailor_hip_shade* writes --, float4 out, one fp32 word of adapted luminance.
+ * log2 / exp2 are fixed fp32 algorithms (sailor_amd/csrc/eye_adaptation.hip: canonical_log2f, canonical_exp2f), restated in
+ * tests/eye_adaptation_ref.py; counts, luminance and image are reproducible bit for bit.
+ * Kept from the reference: the histogram counts only x < 16 * (width / 16), y < 16 * (height / 16) (its dispatch is extent / 16 by integer
+ * division, :173-174) while numPixels is width * height; the weighted sum is uint32 and wraps at 8K; a black pixel under LUMINANCE is NaN
+ * (Formats.glsl:18 divides by X + Y + Z).  Defined where GLSL is not: a NaN luminance counts in bin 0, +inf in bin 255. */
+
+/* the push constants of the two Dispatches (EyeAdaptationNode.cpp:154-170; ComputeHistogram.shader:21-25, ComputeAverageLuminance.shader:21-27) */
+typedef struct SailorEyeAdaptationConstants {
+    float minLog2Luminance;      /* -8 */
+    float invLog2LuminanceRange; /* 1 / 12 */
+    float log2LuminanceRange;    /* 12 */
+    float numPixels;             /* (float)width * height */
+    float timeCoeff;             /* clamp(1 - exp2(-deltaTime * 3.6), 0, 1) */
+} SailorEyeAdaptationConstants;
+
+/* Tonemapping.shader:6-9 defines; ACES wins over UNCHARTED2 (#if / #elif, :150-154) */
+#define SAILOR_TONEMAP_ACES 1u
+#define SAILOR_TONEMAP_UNCHARTED2 2u
+#define SAILOR_TONEMAP_LUMINANCE 4u
+
+/* The node's state: caller-owned device memory of sailor_hip_eye_adaptation_state_size() bytes, 16-byte aligned -- the `histogram` SSBO
+ * (256 uint32 counts, EyeAdaptationNode.cpp:68) and m_averageLuminance (:87-97).  reset zeroes the counts and stores the luminance (the
+ * reference clears it to 0.5, :97).  state_views: the counts and the luminance word inside it (either out pointer may be NULL) -- for tests,
+ * and for a caller that sums the band histograms of a split frame itself (sailor_hip_allgather_u32). */
+SAILOR_HIP_API size_t sailor_hip_eye_adaptation_state_size(void);
+SAILOR_HIP_API int sailor_hip_eye_adaptation_reset(SailorHipContext* ctx, void* dState, float initialLuminance);
+SAILOR_HIP_API int sailor_hip_eye_adaptation_state_views(const void* dState, const uint32_t** outCounts, const float** outLuminance);
+/* Replaces: the Dispatch at EyeAdaptationNode.cpp:173-176 = ComputeHistogram.shader:37-83.  ADDS the band's counts to the state's.
+ *   dColor : device, float4 per pixel, the rows of `band` (first row = band->fbRowBegin), 16-byte aligned */
+SAILOR_HIP_API int sailor_hip_luminance_histogram(SailorHipContext* ctx, const float* dColor, int32_t width, int32_t height, const SailorBand* band,
+                                                  const SailorEyeAdaptationConstants* constants, void* dState);
+/* Replaces: the Dispatch at EyeAdaptationNode.cpp:179-182 = ComputeAverageLuminance.shader:39-78: reduces the counts, zeroes them for the
+ * next frame and moves the luminance towards the frame's average by timeCoeff. */
+SAILOR_HIP_API int sailor_hip_average_luminance(SailorHipContext* ctx, const SailorEyeAdaptationConstants* constants, void* dState);
+/* Replaces: the render pass and DrawIndexed(6) at EyeAdaptationNode.cpp:192-218 = Tonemapping.shader:135-161.  The draw samples a source of
+ * the target's size at texel centres: a texel fetch, so one width / height serves both.
+ *   dColor / dOut : device, float4 per pixel, the rows of `band`; operatorFlags: SAILOR_TONEMAP_* (anything else is refused)
+ *   whitePoint4, exposure : data.whitePoint / data.exposure.x (:52-56; the shipped node: (1.4, 1.5, 1.4), 1) */
+SAILOR_HIP_API int sailor_hip_tonemap(SailorHipContext* ctx, const float* dColor, float* dOut, int32_t width, int32_t height, const SailorBand* band,
+                                      uint32_t operatorFlags, const float* whitePoint4, float exposure, const void* dState);
+/* The node's whole sequence on the whole frame: histogram, average, tone map (EyeAdaptationNode.cpp:173-218). */
+SAILOR_HIP_API int sailor_hip_eye_adaptation(SailorHipContext* ctx, const float* dColor, float* dOut, int32_t width, int32_t height,
+                                             const SailorEyeAdaptationConstants* constants, uint32_t operatorFlags, const float* whitePoint4,
+                                             float exposure, void* dState);
+
 /* ---- RCCL exchange for split frames (only when the frame is split AND a consumer needs the global list) ----
  * `comm` is an ncclComm_t created by the host.  Collective 1: all-gather of one uint32 (band total) per rank.
  * Collective 2: all-gather of the padded band index segments (each rank contributes `segmentCapacity` uints). */
@@ -734,6 +784,8 @@ SAILOR_HIP_API int sailor_host_pack_light(uint32_t type, uint32_t shadowType, co
                                           const float* intensity, const float* attenuation, const float* cutOffDegrees, const float* bounds,
                                           SailorLightShaderData* outLight);
 
+/* FrameGraph/EyeAdaptationNode.cpp:154-170: the push constants of the node's two Dispatches for a width x height HDR target */
+SAILOR_HIP_API int sailor_host_eye_adaptation_constants(int32_t width, int32_t height, float deltaTime, SailorEyeAdaptationConstants* outConstants);
 
 /* Math/Bounds.cpp:211-243 Frustum::OverlapsSphere / ContainsSphere (scalar): sphere4 = (centre.xyz, radius); 1 / 0, negative = bad argument.
  * OverlapsSphere: no plane has the whole sphere behind it.  ContainsSphere: the sphere lies in front of all six planes by at least its radius. */

@@ -35,6 +35,9 @@ SHADOWMAP_R16F = 0
 SHADOWMAP_RGBA32F = 1
 SHADOWMAP_R32F = 2
 
+TONEMAP_ACES, TONEMAP_UNCHARTED2, TONEMAP_LUMINANCE = 1, 2, 4  # Tonemapping.shader:6-9 defines
+TONEMAP_DEFINES = {"ACES": TONEMAP_ACES, "UNCHARTED2": TONEMAP_UNCHARTED2, "LUMINANCE": TONEMAP_LUMINANCE}
+
 TRACE_FLAT_FLOAT_BOXES = 0    # the float world boxes, tested flat (sailor_hip_ecs_sweep)
 TRACE_OCTREE_INT_BOXES = 1    # RHISceneView::TraceScene as the reference runs it: integer boxes in a TOctree
 OCTREE_ROOT_SIZE = 16536 * 16  # RHI/SceneView.h:91-92
@@ -94,6 +97,21 @@ def trace_mode(name: str) -> int:
     if name not in TRACE_MODES:
         raise ValueError(f"unknown trace mode {name!r}: expected one of {sorted(TRACE_MODES)}")
     return TRACE_MODES[name]
+
+
+class EyeAdaptationConstants(C.Structure):  # include/sailor_hip.h SailorEyeAdaptationConstants (EyeAdaptationNode.cpp:154-170)
+    _fields_ = [("minLog2Luminance", C.c_float), ("invLog2LuminanceRange", C.c_float), ("log2LuminanceRange", C.c_float),
+                ("numPixels", C.c_float), ("timeCoeff", C.c_float)]
+
+
+def tonemap_flags(defines: str) -> int:
+    """'UNCHARTED2 LUMINANCE' (the node's toneMappingDefines string) -> SAILOR_TONEMAP_* bits; an unknown define raises"""
+    flags = 0
+    for name in defines.split():
+        if name not in TONEMAP_DEFINES:
+            raise ValueError(f"unknown tone-mapping define {name!r}: expected some of {sorted(TONEMAP_DEFINES)}")
+        flags |= TONEMAP_DEFINES[name]
+    return flags
 
 
 class HiZDesc(C.Structure):
@@ -187,6 +205,15 @@ SIGNATURES = {
     "sailor_hip_mesh_cull_compact_ex": (C.c_int, [_P, C.POINTER(UboFrameData), _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, C.c_size_t, C.POINTER(HiZDesc)]),
     "sailor_hip_mesh_cull_workspace_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
     "sailor_hip_mesh_cull_compact": (C.c_int, [_P, C.POINTER(UboFrameData), _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, C.c_size_t]),
+    "sailor_hip_eye_adaptation_state_size": (C.c_size_t, []),
+    "sailor_hip_eye_adaptation_reset": (C.c_int, [_P, _P, C.c_float]),
+    "sailor_hip_eye_adaptation_state_views": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
+    "sailor_hip_luminance_histogram": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(Band), C.POINTER(EyeAdaptationConstants), _P]),
+    "sailor_hip_average_luminance": (C.c_int, [_P, C.POINTER(EyeAdaptationConstants), _P]),
+    "sailor_hip_tonemap": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.POINTER(Band), C.c_uint32, C.POINTER(C.c_float), C.c_float, _P]),
+    "sailor_hip_eye_adaptation": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.POINTER(EyeAdaptationConstants), C.c_uint32, C.POINTER(C.c_float),
+                                            C.c_float, _P]),
+    "sailor_host_eye_adaptation_constants": (C.c_int, [C.c_int32, C.c_int32, C.c_float, C.POINTER(EyeAdaptationConstants)]),
     "sailor_hip_allgather_u32": (C.c_int, [_P, _P, _P, _P, C.c_size_t]),
     "sailor_hip_exchange_workspace_size": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "sailor_hip_exchange_light_lists": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_size_t, _P, C.c_size_t]),

@@ -334,6 +334,20 @@ int sailor_host_pack_light(uint32_t type, uint32_t shadowType, const float* worl
     return SAILOR_HIP_OK;
 }
 
+// ---- FrameGraph/EyeAdaptationNode.cpp:154-170: the push constants of the histogram and the average Dispatch ----
+int sailor_host_eye_adaptation_constants(int32_t width, int32_t height, float deltaTime, SailorEyeAdaptationConstants* outConstants)
+{
+    if (width <= 0 || height <= 0 || !outConstants) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    const float minLogLuminance = -8.0f, maxLogLuminance = 4.0f, eyeReaction = 3.6f; // :154-156
+    const float logLuminanceRange = maxLogLuminance - minLogLuminance;               // :158
+    outConstants->minLog2Luminance = minLogLuminance;
+    outConstants->invLog2LuminanceRange = 1.0f / logLuminanceRange;                  // :160
+    outConstants->log2LuminanceRange = logLuminanceRange;
+    outConstants->numPixels = (float)width * height;                                 // :168
+    outConstants->timeCoeff = std::clamp(1.0f - std::exp2(-deltaTime * eyeReaction), 0.0f, 1.0f); // :162
+    return SAILOR_HIP_OK;
+}
+
 // ---- Math/Bounds.cpp:211-243: the scalar sphere tests; their only caller is LightingECS::GetLightsInFrustum (ContainsSphere, :237) ----
 int sailor_host_overlaps_sphere(const float* planes24, const float* sphere4)
 {

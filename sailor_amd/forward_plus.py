@@ -534,3 +534,67 @@ class MeshCull:
         # no ndarray.copy() of the record view: it would not carry the records' padding bytes
         return (self.instances.cpu().numpy().view(self._dtype),
                 self.batches.cpu().numpy().view(np.uint32).reshape(-1, 5).copy())
+
+
+class EyeAdaptation:
+    """EyeAdaptationNode (FrameGraph/EyeAdaptationNode.cpp:22-221): log-luminance histogram, smoothed average luminance, tone map.
+    Owns the node's state -- the `histogram` SSBO and the 1 x 1 average-luminance target -- as one device tensor."""
+
+    def __init__(self, ctx: HipContext, width: int, height: int, defines: str = "UNCHARTED2 LUMINANCE", white_point=(1.4, 1.5, 1.4, 0.0),
+                 exposure: float = 1.0, initial_luminance: float = 0.5):
+        self.ctx, self.width, self.height = ctx, width, height
+        self.flags = _lib.tonemap_flags(defines)
+        self.white_point = (C.c_float * 4)(*[float(v) for v in white_point])
+        self.exposure = float(exposure)
+        words = int(ctx._lib.sailor_hip_eye_adaptation_state_size()) // 4
+        self.state = torch.empty(words, dtype=torch.int32, device=ctx.device)
+        self.whole = host.band_whole_frame(width, height)
+        self.reset(initial_luminance)
+
+    def reset(self, luminance: float = 0.5):
+        _lib.check(self.ctx._lib.sailor_hip_eye_adaptation_reset(self.ctx.handle, _ptr(self.state), luminance), "sailor_hip_eye_adaptation_reset", self.ctx.handle)
+
+    def constants(self, delta_time: float):
+        return host.eye_adaptation_constants(self.width, self.height, delta_time)
+
+    def views(self):
+        """(counts, luminance): views of the 256 counts and the adapted-luminance word inside the state tensor"""
+        counts, lum = C.c_void_p(), C.c_void_p()
+        _lib.check(self.ctx._lib.sailor_hip_eye_adaptation_state_views(_ptr(self.state), C.byref(counts), C.byref(lum)), "sailor_hip_eye_adaptation_state_views")
+        c0, l0 = (counts.value - self.state.data_ptr()) // 4, (lum.value - self.state.data_ptr()) // 4
+        return self.state[c0:c0 + 256], self.state[l0:l0 + 1].view(torch.float32)
+
+    def _check_rows(self, t: torch.Tensor, band: Band):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (band.fbRowCount, self.width, 4), (tuple(t.shape), band)
+
+    def histogram(self, color: torch.Tensor, constants, band: Band | None = None):
+        """adds the counts of the band's rows (`color`: rows x width x 4 float32) to the state's"""
+        band = band or self.whole
+        self._check_rows(color, band)
+        _lib.check(self.ctx._lib.sailor_hip_luminance_histogram(self.ctx.handle, _ptr(color), self.width, self.height, C.byref(band), C.byref(constants),
+                                                                _ptr(self.state)), "sailor_hip_luminance_histogram", self.ctx.handle)
+
+    def average(self, constants):
+        _lib.check(self.ctx._lib.sailor_hip_average_luminance(self.ctx.handle, C.byref(constants), _ptr(self.state)), "sailor_hip_average_luminance",
+                   self.ctx.handle)
+
+    def tonemap(self, color: torch.Tensor, out: torch.Tensor | None = None, band: Band | None = None) -> torch.Tensor:
+        band = band or self.whole
+        self._check_rows(color, band)
+        if out is None:
+            out = torch.empty_like(color)
+        self._check_rows(out, band)
+        _lib.check(self.ctx._lib.sailor_hip_tonemap(self.ctx.handle, _ptr(color), _ptr(out), self.width, self.height, C.byref(band), self.flags,
+                                                    self.white_point, self.exposure, _ptr(self.state)), "sailor_hip_tonemap", self.ctx.handle)
+        return out
+
+    def run(self, color: torch.Tensor, delta_time: float, out: torch.Tensor | None = None) -> torch.Tensor:
+        """the node's whole sequence on a whole frame"""
+        self._check_rows(color, self.whole)
+        if out is None:
+            out = torch.empty_like(color)
+        self._check_rows(out, self.whole)
+        constants = self.constants(delta_time)
+        _lib.check(self.ctx._lib.sailor_hip_eye_adaptation(self.ctx.handle, _ptr(color), _ptr(out), self.width, self.height, C.byref(constants), self.flags,
+                                                           self.white_point, self.exposure, _ptr(self.state)), "sailor_hip_eye_adaptation", self.ctx.handle)
+        return out

@@ -67,6 +67,13 @@ def band_for_rank(width: int, height: int, rank: int, world_size: int) -> Band:
     return b
 
 
+def eye_adaptation_constants(width: int, height: int, delta_time: float) -> "_lib.EyeAdaptationConstants":
+    """EyeAdaptationNode.cpp:154-170: the push constants of the histogram and the average Dispatch"""
+    c = _lib.EyeAdaptationConstants()
+    _lib.check(_lib.load().sailor_host_eye_adaptation_constants(width, height, delta_time, C.byref(c)), "sailor_host_eye_adaptation_constants")
+    return c
+
+
 def transform_matrix(position, rotation_xyzw, scale) -> np.ndarray:
     """Math/Transform.cpp:39-42; returns a column-major float32[16]."""
     trs = np.concatenate([_f32(position, 4), _f32(rotation_xyzw, 4), _f32(scale, 4)])

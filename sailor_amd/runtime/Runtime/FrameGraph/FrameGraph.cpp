@@ -1,4 +1,6 @@
+#include <algorithm>
 #include <cmath>
+#include <sstream>
 #include "FrameGraphNode.h"
 #include "LightCullingNode.h"
 #include "RHIFrameGraph.h"
@@ -34,6 +36,7 @@ template class Sailor::Framegraph::TFrameGraphNode<RenderSceneNode>;
 template class Sailor::Framegraph::TFrameGraphNode<LinearizeDepthNode>;
 template class Sailor::Framegraph::TFrameGraphNode<EnvironmentNode>;
 template class Sailor::Framegraph::TFrameGraphNode<DepthHighZNode>;
+template class Sailor::Framegraph::TFrameGraphNode<EyeAdaptationNode>;
 
 // ---- RHIFrameGraph ----------------------------------------------------------------------------------------------------------
 UboFrameData RHIFrameGraph::FillFrameData(RHICommandListPtr transferCmdList, RHISceneViewSnapshot& snapshot, float deltaTime, float worldTime) const
@@ -347,4 +350,109 @@ void RenderSceneNode::Clear()
 {
     m_pShader.Clear();
     m_surfaceBindings.Clear();
+}
+
+// ---- EyeAdaptationNode (FrameGraph/EyeAdaptationNode.cpp:19-230) ----------------------------------------------------------------
+const char* EyeAdaptationNode::m_name = "EyeAdaptation";
+
+void EyeAdaptationNode::Process(RHIFrameGraphPtr frameGraph, RHICommandListPtr transferCommandList, RHICommandListPtr commandList, const RHISceneViewSnapshot& sceneView)
+{
+    auto driver = Renderer::GetDriver();
+    auto commands = Renderer::GetDriverCommands();
+    commands->BeginDebugRegion(commandList, GetName()); // (:28)
+
+    // BaseFrameGraphNode::GetResolvedAttachment: the resource handed in, or the per-frame target of that name
+    auto resolved = [&](const char* name) -> RHITexturePtr {
+        if (auto t = GetRHIResource(name).DynamicCast<RHITexture>()) return t;
+        auto it = m_unresolvedResourceParams.find(name);
+        return it == m_unresolvedResourceParams.end() ? RHITexturePtr() : frameGraph->GetRenderTarget(it->second);
+    };
+    RHITexturePtr target = resolved("color"); // (:30)
+
+    if (!m_pComputeHistogramShader) m_pComputeHistogramShader = driver->CreateShader("Shaders/ComputeHistogram.shader");      // (:32-38)
+    if (!m_pComputeAverageShader) m_pComputeAverageShader = driver->CreateShader("Shaders/ComputeAverageLuminance.shader");   // (:40-46)
+    if (!m_pToneMappingShader) { // (:48-60)
+        std::string shaderPath, definesStr;
+        if (!TryGetString("toneMappingShader", shaderPath) || shaderPath.empty()) { commands->EndDebugRegion(commandList); return; } // check(!shaderPath.empty())
+        TryGetString("toneMappingDefines", definesStr);
+        TVector<std::string> defines; // Utils::SplitString(definesStr, " ")
+        std::istringstream words(definesStr);
+        for (std::string d; words >> d;) defines.push_back(d);
+        m_pToneMappingShader = driver->CreateShader(shaderPath, defines);
+    }
+
+    RHITexturePtr quarterResolution = resolved("hdrColor");  // (:62)
+    RHITexturePtr fullResolution = resolved("colorSampler"); // (:63)
+    if (!quarterResolution || !fullResolution) { commands->EndDebugRegion(commandList); return; } // check(quarterResolution) (:70)
+
+    if (!m_computeHistogramShaderBindings) { // (:65-80)
+        m_computeHistogramShaderBindings = driver->CreateShaderBindings();
+        auto histogramRes = driver->AddSsboToShaderBindings(m_computeHistogramShaderBindings, "histogram", sizeof(uint32_t), HistogramShades, 0, true);
+        driver->AddStorageImageToShaderBindings(m_computeHistogramShaderBindings, "s_texColor", quarterResolution, 1);
+        static TVector<uint32_t> initialData(HistogramShades); // "We should init the buffer"
+        commands->UpdateShaderBinding(transferCommandList, histogramRes, initialData.data(), sizeof(uint32_t) * HistogramShades, 0);
+    }
+    if (!m_averageLuminance) { // (:82-98)
+        m_averageLuminance = driver->CreateRenderTarget({ 1, 1 }, 1, EFormat::R32_SFLOAT); // R16_SFLOAT there (:91): fp32 is its canonical form here
+        commands->ImageMemoryBarrier(commandList, m_averageLuminance, EImageLayout::TransferDstOptimal);
+        commands->ClearImage(commandList, m_averageLuminance, 0.5f, 0.5f, 0.5f, 0.5f);
+    }
+    if (!m_computeAverageShaderBindings) { // (:100-109)
+        auto histogram = m_computeHistogramShaderBindings->GetOrAddShaderBinding("histogram");
+        m_computeAverageShaderBindings = driver->CreateShaderBindings();
+        driver->AddShaderBinding(m_computeAverageShaderBindings, histogram, "histogram", 0);
+        driver->AddStorageImageToShaderBindings(m_computeAverageShaderBindings, "s_texColor", m_averageLuminance, 1);
+    }
+    if (!m_pToneMappingShader || !m_pComputeHistogramShader || !m_pComputeAverageShader || !target) { // (:111-117)
+        commands->EndDebugRegion(commandList);
+        return;
+    }
+    if (!m_postEffectMaterial) { // (:119-149)
+        m_shaderBindings = driver->CreateShaderBindings();
+        // (FillShadersLayout (:124) reflects the shader's sets; the driver knows Tonemapping.shader's one uniform block)
+        const size_t uniformsSize = m_vectorParams.size() * sizeof(vec4); // "That should be enough to handle all the uniforms"
+        if (uniformsSize > 0) driver->AddBufferToShaderBindings(m_shaderBindings, "data", uniformsSize, 0, EShaderBindingType::UniformBuffer);
+        m_postEffectMaterial = driver->CreateMaterial(m_pToneMappingShader);
+        for (const auto& v : m_vectorParams) { // SetMaterialParameter(cmd, bindings, "data.whitePoint", value) splits at the dot (RHI/GraphicsDriver.h:335-341)
+            const size_t dot = v.first.find('.');
+            if (dot == std::string::npos) continue;
+            commands->SetMaterialParameter(transferCommandList, m_shaderBindings, v.first.substr(0, dot), v.first.substr(dot + 1), &v.second, sizeof(vec4));
+        }
+        auto wp = m_vectorParams.find("data.whitePoint");
+        if (wp != m_vectorParams.end()) m_whitePointLum = (0.2125f * wp->second.x + 0.7154f * wp->second.y) + 0.0721f * wp->second.z; // (:142-145)
+        driver->AddSamplerToShaderBindings(m_shaderBindings, "colorSampler", fullResolution, 1);                       // UpdateShaderBinding(bindings, name, texture) (:147)
+        driver->AddSamplerToShaderBindings(m_shaderBindings, "averageLuminanceSampler", m_averageLuminance, 2);        // (:148)
+    }
+    {
+        const float minLogLuminance = -8.0f, maxLogLuminance = 4.0f, eyeReaction = 3.6f; // (:154-156)
+        const float logLuminanceRange = maxLogLuminance - minLogLuminance;
+        float pushConstantsHistogramm[] = { minLogLuminance, 1.0f / logLuminanceRange };
+        float timeCoeff = std::clamp(1.0f - std::exp2(-sceneView.m_deltaTime * eyeReaction), 0.0f, 1.0f);
+        float pushConstantsAverage[] = { minLogLuminance, logLuminanceRange, (float)quarterResolution->GetExtent().x * quarterResolution->GetExtent().y, timeCoeff };
+
+        commands->ImageMemoryBarrier(commandList, quarterResolution, EImageLayout::General); // ComputeRead (:172)
+        commands->Dispatch(commandList, m_pComputeHistogramShader, (uint32_t)(quarterResolution->GetExtent().x / 16), (uint32_t)(quarterResolution->GetExtent().y / 16), 1,
+                           { m_computeHistogramShaderBindings }, &pushConstantsHistogramm, sizeof(float) * 2); // (:173-176)
+        commands->ImageMemoryBarrier(commandList, m_averageLuminance, EImageLayout::ComputeWrite);
+        commands->Dispatch(commandList, m_pComputeAverageShader, 1, 1, 1, { m_computeAverageShaderBindings }, &pushConstantsAverage, sizeof(float) * 4); // (:179-182)
+        commands->ImageMemoryBarrier(commandList, m_averageLuminance, EImageLayout::ShaderReadOnlyOptimal);
+        commands->ImageMemoryBarrier(commandList, target, EImageLayout::ColorAttachmentOptimal);
+    }
+    commands->ImageMemoryBarrier(commandList, fullResolution, EImageLayout::ShaderReadOnlyOptimal); // (:187-188)
+
+    commands->BeginRenderPass(commandList, TVector<RHITexturePtr> { target }, RHITexturePtr());                       // (:192-200)
+    commands->BindMaterial(commandList, m_postEffectMaterial);                                                         // (:205)
+    commands->BindShaderBindings(commandList, m_postEffectMaterial, { sceneView.m_frameBindings, m_shaderBindings }); // (:215)
+    commands->DrawIndexed(commandList, 6, 1, 0, 0, 0);                                                                 // (:217) the full-screen NDC quad
+    commands->EndRenderPass(commandList);                                                                              // (:218)
+    commands->EndDebugRegion(commandList);
+}
+
+void EyeAdaptationNode::Clear() // (:223-230)
+{
+    m_pToneMappingShader.Clear();
+    m_postEffectMaterial.Clear();
+    m_shaderBindings.Clear();
+    m_pComputeHistogramShader.Clear();
+    m_pComputeAverageShader.Clear();
 }

@@ -102,4 +102,26 @@ protected:
     RHI::RHIShaderBindingSetPtr m_computePrepassDepthHighZBindings;
 };
 
+// The first node behind the two RenderScene passes: Runtime/FrameGraph/EyeAdaptationNode.h.  Resources (DefaultRenderer.renderer:307-319): "hdrColor" = the
+// HDR target the histogram is taken of, "colorSampler" = the HDR target the tone-mapping draw samples, "color" = the LDR target it writes.  Strings
+// "toneMappingShader" / "toneMappingDefines", vec4 "data.whitePoint" / "data.exposure".
+class EyeAdaptationNode : public TFrameGraphNode<EyeAdaptationNode> {
+public:
+    static const uint32_t HistogramShades = 256; // EyeAdaptationNode.h
+    static const char* GetName() { return m_name; }
+    void Process(RHIFrameGraphPtr frameGraph, RHI::RHICommandListPtr transferCommandList, RHI::RHICommandListPtr commandList,
+                 const RHI::RHISceneViewSnapshot& sceneView) override;
+    void Clear() override;
+    RHI::RHITexturePtr GetAverageLuminance() const { return m_averageLuminance; }
+    RHI::RHIShaderBindingSetPtr GetHistogramBindings() const { return m_computeHistogramShaderBindings; }
+
+protected:
+    static const char* m_name;
+    RHI::RHIShaderPtr m_pComputeHistogramShader, m_pComputeAverageShader, m_pToneMappingShader;
+    RHI::RHIShaderBindingSetPtr m_computeHistogramShaderBindings, m_computeAverageShaderBindings, m_shaderBindings;
+    RHI::RHIMaterialPtr m_postEffectMaterial;
+    RHI::RHITexturePtr m_averageLuminance;
+    float m_whitePointLum = 0.0f;
+};
+
 } // namespace Sailor::Framegraph

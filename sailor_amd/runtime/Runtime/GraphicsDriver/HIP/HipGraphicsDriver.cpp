@@ -197,7 +197,11 @@ RHIShaderBindingPtr HipGraphicsDriver::AddSsboToShaderBindings(RHIShaderBindingS
     auto b = set->GetOrAddShaderBinding(name);
     b->m_type = EShaderBindingType::StorageBuffer;
     b->m_binding = shaderBinding;
-    b->m_buffer = CreateBuffer(elementSize * numElements);
+    // EyeAdaptationNode's `histogram` (EyeAdaptationNode.cpp:68: 256 uint32): the kernels keep the node's adapted luminance behind the counts
+    // (include/sailor_hip.h: one caller-owned state), so the allocation has room for the whole state; the 1 x 1 average-luminance target becomes a
+    // view of its luminance word when it is bound beside this SSBO (AddStorageImageToShaderBindings below)
+    const bool eyeAdaptation = name == "histogram" && elementSize == sizeof(uint32_t) && numElements == 256;
+    b->m_buffer = CreateBuffer(eyeAdaptation ? sailor_hip_eye_adaptation_state_size() : elementSize * numElements);
     // The `light` SSBO (LightingECS.cpp:44): LightingECS::Tick counts every slot in lightsNum but only ever uploads the slots of ACTIVE lights
     // (:148-149), so a light that is inactive from registration leaves its slot as the allocation left it.  Here that is defined: the records are
     // zero-filled (type 0, intensity 0) and the prepared views are derived for the whole capacity at creation, so the plain and the prepared entry
@@ -246,6 +250,17 @@ RHIShaderBindingPtr HipGraphicsDriver::AddStorageImageToShaderBindings(RHIShader
     b->m_type = EShaderBindingType::StorageImage;
     b->m_binding = shaderBinding;
     b->m_textures = array;
+    // EyeAdaptationNode.cpp:102-108: the 1 x 1 average-luminance target bound as `s_texColor` beside the `histogram` SSBO -- from here on the target IS
+    // the luminance word of that state (whatever is recorded against it, the ClearImage of :97 included, resolves the buffer when it runs)
+    auto hist = set->Find("histogram");
+    if (name == "s_texColor" && array.size() == 1 && array[0] && array[0]->GetExtent().x == 1 && array[0]->GetExtent().y == 1 && array[0]->m_format == EFormat::R32_SFLOAT &&
+        hist && hist->m_buffer && hist->m_buffer->m_size >= sailor_hip_eye_adaptation_state_size() && !array[0]->m_hipEyeAdaptationState) {
+        const float* lum = nullptr;
+        if (sailor_hip_eye_adaptation_state_views(hist->m_buffer->m_hip.m_devicePtr, nullptr, &lum) == SAILOR_HIP_OK) {
+            array[0]->m_hipEyeAdaptationState = hist->m_buffer;
+            array[0]->m_buffer = WrapBuffer((void*)lum, sizeof(float));
+        }
+    }
     return b;
 }
 
@@ -307,6 +322,33 @@ void HipGraphicsDriver::EndDebugRegion(RHICommandListPtr cmdList)
     cmdList->m_hip.m_commands.push_back([]() { if (roctx().pop) roctx().pop(); return (int)SAILOR_HIP_OK; });
 }
 void HipGraphicsDriver::ImageMemoryBarrier(RHICommandListPtr, RHITexturePtr, EImageLayout) {} // one in-order stream: nothing to do
+
+// The path's only ClearImage is EyeAdaptationNode's (EyeAdaptationNode.cpp:97): a one-channel fp32 target filled with clearColor.r
+void HipGraphicsDriver::ClearImage(RHICommandListPtr cmd, RHITexturePtr dst, float r, float, float, float)
+{
+    SailorHipContext* ctx = m_ctx;
+    cmd->m_hip.m_commands.push_back([this, ctx, dst, r]() {
+        if (!dst || !dst->m_buffer || dst->m_format != EFormat::R32_SFLOAT) return (int)SAILOR_HIP_ERR_UNSUPPORTED;
+        uint32_t bits;
+        memcpy(&bits, &r, 4);
+        BeforeBufferWrite(dst->m_buffer->m_hip.m_devicePtr);
+        return sailor_hip_buffer_fill_u32(ctx, dst->m_buffer->m_hip.m_devicePtr, 0, bits, (size_t)dst->GetExtent().x * dst->GetExtent().y);
+    });
+}
+
+// VulkanGraphicsDriver's SetMaterialParameter finds the variable's offset in the reflected layout of the uniform block; here the one block the path
+// sets this way is Tonemapping.shader:52-56 PostProcessDataUBO { vec4 whitePoint; vec4 exposure; }
+void HipGraphicsDriver::SetMaterialParameter(RHICommandListPtr cmd, RHIShaderBindingSetPtr bindings, const std::string& binding, const std::string& variable,
+                                             const void* value, size_t size)
+{
+    auto b = bindings ? bindings->Find(binding) : RHIShaderBindingPtr();
+    size_t offset;
+    if (binding == "data" && variable == "whitePoint") offset = 0;
+    else if (binding == "data" && variable == "exposure") offset = 16;
+    else { m_lastDispatchStatus = SAILOR_HIP_ERR_UNSUPPORTED; return; }
+    if (!b || b->m_type != EShaderBindingType::UniformBuffer) { m_lastDispatchStatus = SAILOR_HIP_ERR_INVALID_ARGUMENT; return; }
+    UpdateShaderBinding(cmd, b, value, size, offset);
+}
 
 bool HipGraphicsDriver::BlitImage(RHICommandListPtr cmd, RHITexturePtr src, RHITexturePtr dst, ivec4 srcRegionRect, ivec4 dstRegionRect)
 {
@@ -402,6 +444,8 @@ void HipGraphicsDriver::Dispatch(RHICommandListPtr cmd, RHIShaderPtr computeShad
         if (name == "Shaders/Standard.shader") return RecordShade(bindings);
         if (name == "Shaders/ComputeMeshCulling.shader") return RecordMeshCulling(bindings, pc, occlusion);
         if (name == "Shaders/ComputeDepthHighZ.shader") return RecordDepthHighZ(bindings);
+        if (name == "Shaders/ComputeHistogram.shader") return RecordLuminanceHistogram(bindings, pc);
+        if (name == "Shaders/ComputeAverageLuminance.shader") return RecordAverageLuminance(bindings, pc);
         if (name == "Shaders/ComputeBrdfLut.shader") return RecordBrdfLut(bindings);
         if (name == "Shaders/ComputeIrradianceMap.shader") return RecordIrradianceMap(bindings);
         if (name == "Shaders/ComputeEnvMap_IBL.shader") return RecordEnvPrefilter(bindings, pc);
@@ -678,9 +722,12 @@ void HipGraphicsDriver::DrawIndexed(RHICommandListPtr cmd, uint32_t indexCount, 
     }
     const bool fullScreenQuad = indexCount == 6 && instanceCount == 1; // RHIFrameGraph.cpp:106-125 GetFullscreenNdcQuad
     RHIShaderPtr shader = cmd->m_boundMaterial ? cmd->m_boundMaterial->m_shader : RHIShaderPtr();
+    const uint32_t tonemapFlags = !shader ? 0u : (shader->HasDefine("ACES") ? SAILOR_TONEMAP_ACES : 0u) | (shader->HasDefine("UNCHARTED2") ? SAILOR_TONEMAP_UNCHARTED2 : 0u) |
+                                                 (shader->HasDefine("LUMINANCE") ? SAILOR_TONEMAP_LUMINANCE : 0u);
     const bool evsm = shader && shader->HasDefine("EVSM"), vertical = shader && shader->HasDefine("VERTICAL"), horizontal = shader && shader->HasDefine("HORIZONTAL");
-    cmd->m_hip.m_commands.push_back([this, name, bindings, target, fullScreenQuad, evsm, vertical, horizontal]() {
+    cmd->m_hip.m_commands.push_back([this, name, bindings, target, fullScreenQuad, evsm, vertical, horizontal, tonemapFlags]() {
         if (fullScreenQuad && name == "Shaders/LinearizeDepth.shader") return RecordLinearizeDepth(bindings, target);
+        if (fullScreenQuad && name == "Shaders/Tonemapping.shader") return RecordTonemap(bindings, target, tonemapFlags);
         if (fullScreenQuad && name == "Shaders/Blur.shader" && evsm && vertical != horizontal) return RecordEvsmBlur(bindings, target, vertical);
         return (int)SAILOR_HIP_ERR_UNSUPPORTED;
     });
@@ -700,6 +747,68 @@ int HipGraphicsDriver::RecordLinearizeDepth(const TVector<RHIShaderBindingSetPtr
     memcpy(&frame, frameB->m_hostCopy.data(), sizeof frame);
     return sailor_hip_linearize_depth(m_ctx, &frame, (const float*)src->m_buffer->m_hip.m_devicePtr, (float*)target->m_buffer->m_hip.m_devicePtr,
                                       target->GetExtent().x, target->GetExtent().y);
+}
+
+// ---- EyeAdaptationNode (FrameGraph/EyeAdaptationNode.cpp:151-218) ------------------------------------------------------------------------
+int HipGraphicsDriver::RecordLuminanceHistogram(const TVector<RHIShaderBindingSetPtr>& bindings, const TVector<uint8_t>& pcBytes)
+{
+    // EyeAdaptationNode.cpp:173-176: { m_computeHistogramShaderBindings }; ComputeHistogram.shader:14-25: binding 0 `histogram`, 1 `s_texColor`, push constants
+    // { minLog2Luminance, 1 / range }.  The group counts of the Dispatch (extent / 16) are implied by the image: the kernel applies the same truncation.
+    if (bindings.size() != 1 || pcBytes.size() < 2 * sizeof(float)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    auto histB = bindings[0]->Find("histogram");
+    auto colorB = bindings[0]->Find("s_texColor");
+    if (!histB || !histB->m_buffer || histB->m_buffer->m_size < sailor_hip_eye_adaptation_state_size() || !colorB || colorB->m_textures.empty() || !colorB->m_textures[0] ||
+        !colorB->m_textures[0]->m_buffer)
+        return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    const auto& color = colorB->m_textures[0];
+    if (color->m_format != EFormat::R32G32B32A32_SFLOAT) return SAILOR_HIP_ERR_UNSUPPORTED;
+    SailorEyeAdaptationConstants k {};
+    memcpy(&k.minLog2Luminance, pcBytes.data(), 4);
+    memcpy(&k.invLog2LuminanceRange, pcBytes.data() + 4, 4);
+    SailorBand whole;
+    if (sailor_hip_band_whole_frame(color->GetExtent().x, color->GetExtent().y, &whole) != SAILOR_HIP_OK) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    return sailor_hip_luminance_histogram(m_ctx, (const float*)color->m_buffer->m_hip.m_devicePtr, color->GetExtent().x, color->GetExtent().y, &whole, &k,
+                                          histB->m_buffer->m_hip.m_devicePtr);
+}
+
+int HipGraphicsDriver::RecordAverageLuminance(const TVector<RHIShaderBindingSetPtr>& bindings, const TVector<uint8_t>& pcBytes)
+{
+    // EyeAdaptationNode.cpp:179-182: { m_computeAverageShaderBindings }; ComputeAverageLuminance.shader:14-27: binding 0 `histogram`, 1 `s_texColor` (the 1 x 1
+    // luminance target), push constants { minLog2Luminance, log2LuminanceRange, numPixels, timeCoeff }
+    if (bindings.size() != 1 || pcBytes.size() < 4 * sizeof(float)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    auto histB = bindings[0]->Find("histogram");
+    auto lumB = bindings[0]->Find("s_texColor");
+    if (!histB || !histB->m_buffer || !lumB || lumB->m_textures.empty() || !lumB->m_textures[0]) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    // the target must be the luminance word of THIS histogram's state (AddStorageImageToShaderBindings made it so)
+    if (lumB->m_textures[0]->m_hipEyeAdaptationState.GetRawPtr() != histB->m_buffer.GetRawPtr()) return SAILOR_HIP_ERR_UNSUPPORTED;
+    float pc[4];
+    memcpy(pc, pcBytes.data(), sizeof pc);
+    SailorEyeAdaptationConstants k {};
+    k.minLog2Luminance = pc[0]; k.log2LuminanceRange = pc[1]; k.numPixels = pc[2]; k.timeCoeff = pc[3];
+    return sailor_hip_average_luminance(m_ctx, &k, histB->m_buffer->m_hip.m_devicePtr);
+}
+
+int HipGraphicsDriver::RecordTonemap(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& target, uint32_t operatorFlags)
+{
+    // EyeAdaptationNode.cpp:215: { sceneView.m_frameBindings, m_shaderBindings }; Tonemapping.shader:52-59: set 1 binding 0 `data` { whitePoint, exposure },
+    // 1 `colorSampler`, 2 `averageLuminanceSampler`.  The quad's texcoords address the source at texel centres: a texel fetch of a same-size source.
+    if (bindings.size() != 2 || !target || !target->m_buffer) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    auto dataB = bindings[1]->Find("data");
+    auto srcB = bindings[1]->Find("colorSampler");
+    auto lumB = bindings[1]->Find("averageLuminanceSampler");
+    if (!dataB || dataB->m_hostCopy.size() < 32 || !srcB || srcB->m_textures.empty() || !srcB->m_textures[0] || !srcB->m_textures[0]->m_buffer || !lumB ||
+        lumB->m_textures.empty() || !lumB->m_textures[0] || !lumB->m_textures[0]->m_hipEyeAdaptationState)
+        return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    const auto& src = srcB->m_textures[0];
+    if (src->m_format != EFormat::R32G32B32A32_SFLOAT || target->m_format != EFormat::R32G32B32A32_SFLOAT) return SAILOR_HIP_ERR_UNSUPPORTED;
+    if (src->GetExtent().x != target->GetExtent().x || src->GetExtent().y != target->GetExtent().y) return SAILOR_HIP_ERR_INVALID_ARGUMENT; // differing sizes are refused
+    float data[8];
+    memcpy(data, dataB->m_hostCopy.data(), sizeof data);
+    SailorBand whole;
+    if (sailor_hip_band_whole_frame(target->GetExtent().x, target->GetExtent().y, &whole) != SAILOR_HIP_OK) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    BeforeBufferWrite(target->m_buffer->m_hip.m_devicePtr);
+    return sailor_hip_tonemap(m_ctx, (const float*)src->m_buffer->m_hip.m_devicePtr, (float*)target->m_buffer->m_hip.m_devicePtr, target->GetExtent().x,
+                              target->GetExtent().y, &whole, operatorFlags, data, data[4], lumB->m_textures[0]->m_hipEyeAdaptationState->m_hip.m_devicePtr);
 }
 
 int HipGraphicsDriver::RecordEvsmBlur(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& target, bool vertical)

@@ -7,10 +7,14 @@
 //   "Shaders/ComputeMeshCulling.shader"  -> sailor_hip_mesh_cull_compact (binding contract: ComputeMeshCulling.shader:37-58;
 //                                           sailor_hip_mesh_frustum_cull when no indirect buffer is bound)
 //   "Shaders/ComputeDepthHighZ.shader"   -> sailor_hip_hiz_downscale     (binding contract: ComputeDepthHighZ.shader:11-17)
+//   "Shaders/ComputeHistogram.shader" / "ComputeAverageLuminance.shader" (EyeAdaptationNode's two Dispatches)
+//                                        -> sailor_hip_luminance_histogram / sailor_hip_average_luminance (ComputeHistogram.shader:14-25,
+//                                           ComputeAverageLuminance.shader:14-27); the `histogram` SSBO is created with room for the node state
 //   "Shaders/ComputeBrdfLut.shader" / "ComputeIrradianceMap.shader" / "ComputeEnvMap_IBL.shader" (EnvironmentNode's one-off Dispatches)
 //                                        -> sailor_hip_compute_brdf_lut / _compute_irradiance_map / _prefilter_env_level
 // and the one full-screen DRAW in front of the path (6 indices with the material of)
 //   "Shaders/LinearizeDepth.shader"      -> sailor_hip_linearize_depth   (binding contract: LinearizeDepth.shader:15-59)
+//   "Shaders/Tonemapping.shader" {ACES, UNCHARTED2, LUMINANCE} -> sailor_hip_tonemap (binding contract: Tonemapping.shader:52-59)
 //   "Shaders/Blur.shader" {EVSM, HORIZONTAL | VERTICAL} -> sailor_hip_evsm_blur_pass (binding contract: Blur.shader:53-61)
 // and the depth-only instanced draws of the shadow passes (material of)
 //   "Shaders/ShadowCaster.shader" [EVSM]  -> sailor_hip_raster_depth into the pass' depth attachment, and at EndRenderPass sailor_hip_shadow_resolve
@@ -74,10 +78,13 @@ public:
     void BeginDebugRegion(RHI::RHICommandListPtr cmdList, const std::string& title) override;
     void EndDebugRegion(RHI::RHICommandListPtr cmdList) override;
     void ImageMemoryBarrier(RHI::RHICommandListPtr cmd, RHI::RHITexturePtr image, RHI::EImageLayout newLayout) override;
+    void ClearImage(RHI::RHICommandListPtr cmd, RHI::RHITexturePtr dst, float r, float g, float b, float a) override;
     bool BlitImage(RHI::RHICommandListPtr cmd, RHI::RHITexturePtr src, RHI::RHITexturePtr dst, RHI::ivec4 srcRegionRect, RHI::ivec4 dstRegionRect) override;
     void GenerateMipMaps(RHI::RHICommandListPtr cmd, RHI::RHITexturePtr target) override;
     void ConvertEquirect2Cubemap(RHI::RHICommandListPtr cmd, RHI::RHITexturePtr equirect, RHI::RHICubemapPtr cubemap) override;
     void UpdateShaderBinding(RHI::RHICommandListPtr cmd, RHI::RHIShaderBindingPtr binding, const void* data, size_t size, size_t variableOffset = 0) override;
+    void SetMaterialParameter(RHI::RHICommandListPtr cmd, RHI::RHIShaderBindingSetPtr bindings, const std::string& binding, const std::string& variable,
+                              const void* value, size_t size) override;
     void UpdateBuffer(RHI::RHICommandListPtr cmd, RHI::RHIBufferPtr buffer, const void* data, size_t size, size_t offset = 0) override;
     void BeginRenderPass(RHI::RHICommandListPtr cmd, const TVector<RHI::RHITexturePtr>& colorAttachments, RHI::RHITexturePtr depthStencilAttachment) override;
     void BindVertexBuffer(RHI::RHICommandListPtr cmd, RHI::RHIBufferPtr vertexBuffer, uint32_t offset) override;
@@ -101,6 +108,9 @@ private:
     int RecordMeshCulling(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const TVector<uint8_t>& pc, bool occlusion);
     int RecordDepthHighZ(const TVector<RHI::RHIShaderBindingSetPtr>& bindings);
     int RecordLinearizeDepth(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target);
+    int RecordLuminanceHistogram(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const TVector<uint8_t>& pc);
+    int RecordAverageLuminance(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const TVector<uint8_t>& pc);
+    int RecordTonemap(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target, uint32_t operatorFlags);
     int RecordEvsmBlur(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target, bool vertical);
 
     SailorHipContext* m_ctx = nullptr;              // == m_ctxOwner.get(): what the C-ABI calls take

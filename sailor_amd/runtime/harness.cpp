@@ -582,6 +582,36 @@ RT_API int sailor_rt_exchange_light_lists(SailorRuntime* rt, void* globalGridDev
     return hip->ExchangeLightLists(g->m_buffer, c->m_buffer, hip->WrapBuffer(globalGridDevicePtr, gridBytes), hip->WrapBuffer(globalCulledDevicePtr, culledBytes));
 }
 
+// a wrapped RGBA32F device image as a named render target of the graph (the HDR target RenderScene's radiance stands for, an LDR target of the caller's)
+RT_API void sailor_rt_set_color_target(SailorRuntime* rt, const char* name, void* devicePtr, int width, int height)
+{
+    auto* hip = static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver());
+    rt->graph.SetRenderTarget(name, hip->WrapTexture(devicePtr, { width, height }, EFormat::R32G32B32A32_SFLOAT));
+}
+
+// sceneView.m_deltaTime / m_currentTime of the frames processed from here on (EyeAdaptationNode.cpp:162 reads the first)
+RT_API void sailor_rt_set_time(SailorRuntime* rt, float deltaTime, float currentTime)
+{
+    rt->snapshot.m_deltaTime = deltaTime;
+    rt->snapshot.m_currentTime = currentTime;
+}
+
+// the EyeAdaptation node's state, for read-back: the device pointers of its `histogram` SSBO (256 uint32) and of its 1 x 1 average-luminance target (one float)
+RT_API int sailor_rt_eye_adaptation_state(SailorRuntime* rt, void** outHistogram, void** outLuminance)
+{
+    for (const auto& n : rt->graph.GetGraph()) {
+        auto node = n.DynamicCast<EyeAdaptationNode>();
+        if (!node) continue;
+        auto lum = node->GetAverageLuminance();
+        auto hist = node->GetHistogramBindings() ? node->GetHistogramBindings()->Find("histogram") : RHIShaderBindingPtr();
+        if (!lum || !lum->m_buffer || !hist || !hist->m_buffer) return -1;
+        if (outHistogram) *outHistogram = hist->m_buffer->m_hip.m_devicePtr;
+        if (outLuminance) *outLuminance = lum->m_buffer->m_hip.m_devicePtr;
+        return 0;
+    }
+    return -1;
+}
+
 RT_API int sailor_rt_process_frame(SailorRuntime* rt)
 {
     rt->graph.Process(rt->snapshot);

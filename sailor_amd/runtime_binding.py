@@ -56,6 +56,9 @@ def load() -> C.CDLL:
         rt.sailor_rt_render_target.restype = P
         rt.sailor_rt_render_target.argtypes = [P, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         rt.sailor_rt_set_render_target.argtypes = [P, C.c_char_p, P, C.c_int, C.c_int]
+        rt.sailor_rt_set_color_target.argtypes = [P, C.c_char_p, P, C.c_int, C.c_int]
+        rt.sailor_rt_set_time.argtypes = [P, C.c_float, C.c_float]
+        rt.sailor_rt_eye_adaptation_state.argtypes = [P, C.POINTER(P), C.POINTER(P)]
         rt.sailor_rt_shadow_pass.argtypes = [P, C.POINTER(C.c_float), P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, C.c_uint32, P, C.c_int, C.c_int, C.c_float, C.c_float]
         rt.sailor_rt_gpu_culling.argtypes = [P, P, C.c_uint32, C.c_uint32, P, C.c_uint32]
         rt.sailor_rt_process_frame.argtypes = [P]
@@ -228,6 +231,21 @@ class Runtime:
     def set_render_target(self, name: str, tensor):
         """publish a float32 [h, w] device tensor as a named render target (DepthBuffer, ...)"""
         self.rt.sailor_rt_set_render_target(self.h, name.encode(), tensor.data_ptr(), tensor.shape[1], tensor.shape[0])
+
+    def set_color_target(self, name: str, tensor):
+        """publish a float32 [h, w, 4] device tensor as a named RGBA render target (the HDR target RenderScene's radiance stands for, an LDR target)"""
+        self.rt.sailor_rt_set_color_target(self.h, name.encode(), tensor.data_ptr(), tensor.shape[1], tensor.shape[0])
+
+    def set_time(self, delta_time: float, current_time: float = 0.0):
+        """sceneView.m_deltaTime / m_currentTime of the frames processed from here on"""
+        self.rt.sailor_rt_set_time(self.h, delta_time, current_time)
+
+    def eye_adaptation_state(self):
+        """(device pointer of the EyeAdaptation node's 256 histogram counts, device pointer of its adapted-luminance word); raises if the graph has no such node"""
+        hist, lum = C.c_void_p(), C.c_void_p()
+        if self.rt.sailor_rt_eye_adaptation_state(self.h, C.byref(hist), C.byref(lum)) != 0:
+            raise ValueError("the graph has no EyeAdaptation node that has processed a frame")
+        return hist.value, lum.value
 
     def shadow_pass(self, light_matrix, positions, indices, models, first_instance, instance_count, shadow_map, evsm, radius_umbra=0.0, radius_penumbra=0.0):
         """one shadow pass of ShadowPrepassNode (caster draw + fragment stage + blur) over device tensors; the map is float32 [S, S, 4] (EVSM) or float16 [S, S]"""
