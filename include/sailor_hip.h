@@ -707,6 +707,68 @@ SAILOR_HIP_API int sailor_hip_eye_adaptation(SailorHipContext* ctx, const float*
                                              const SailorEyeAdaptationConstants* constants, uint32_t operatorFlags, const float* whitePoint4,
                                              float exposure, void* dState);
 
+/* ---- HBAO: the producer of g_AO (Standard.shader:386 reads it through g_aoSampler) ------------------------------------------------------
+ * Replaces: the GPU work of the HBAO block of the shipped frame graph (DefaultRenderer.renderer:202-264): the Blit DepthBuffer -> HalfDepth
+ * (FrameGraph/BlitNode.cpp:21-124), the PostProcess draw (FrameGraph/PostProcessNode.cpp:22-202) with Content/Shaders/HBAO.shader:81-249 and the
+ * two PostProcess draws with Content/Shaders/HBAO_Blur.shader:67-111 (VERTICAL, HORIZONTAL).  (DepthHighZ between them: sailor_hip_hiz_*.)
+ * Every image is a single-channel fp32 plane in device memory, row 0 = top, texel (i, j) of a w x h target has fragTexcoord
+ * ((i + 0.5) / w, (j + 0.5) / h); the extents of a call are independent of one another.  The R8_UNORM targets (AO, TemporaryR8, g_AO) are fp32
+ * planes that hold what texture() would return from the 8-bit target: rintf(min(max(v, 0), 1) * 255) / 255, NaN -> 0.
+ * The shaders are evaluated as written, in their order, one IEEE rounding per operation, with the evaluation order fixed above for the tone map:
+ * dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z, mat4 * vec4 row by row left to right, v / s = one division per component, length = sqrt(dot),
+ * normalize(v) = v / length(v), rcp(x) = 1 / x, mix(a, b, t) = a (1 - t) + b t, products left to right; tests/hbao_ref.py restates them and the
+ * results are reproducible bit for bit.  Decisions (HBAO.shader lines):
+ *   - main() normalises the normal twice (:116, :199): both kept;  ClipSpaceToViewSpace gets (uv.x, uv.y, depth, 1), not NDC (:91, :112-114): literal;
+ *   - depthSampler / aoSampler: bilinear, clamp-to-edge, the taps and weights of sailor_amd/csrc/sampling.h evaluated per fetch (no corner plane);
+ *   - noiseSampler: nearest, repeat: texel floor(u * nw) mod nw;  round() in SnapTexel: half to even;
+ *   - screenSpace1Meter (:211) is NaN for every perspective projection (clip w of (0, 1, 0, 1) is 0, x / w = 0 / 0), so sampleRadius = occlusionRadius (:213);
+ *   - sinS = sin(PI / 2 - acos(x)) (:133) is evaluated as x, without a clamp;  saturate(x) = x < 0 ? 0 : (x > 1 ? 1 : x) passes a NaN on;
+ *   - non-finite sample coordinates (depth 0, inf, NaN) take the saturating float -> int conversion with NaN -> 0 in the tap computation;
+ *   - the sky check (:190-194) and screenSpaceRadius < 1 (:225) store 1; distanceFactor (:138) is not clamped;
+ *   - the blur's exp2 is the fixed fp32 algorithm of sailor_amd/csrc/canonical_math.h; its loops run over float i = 1 .. radius, all + taps first. */
+
+/* HBAO.shader:50-57 PostProcessDataUBO (std140: floats at 0, 4, 8, 12, 16) */
+typedef struct SailorHbaoParams {
+    float occlusionRadius;      /* shipped: 700 */
+    float occlusionPower;       /* 1.5 */
+    float occlusionAttenuation; /* 0.1 */
+    float occlusionBias;        /* 0.05 */
+    float noiseScale;           /* 25 */
+} SailorHbaoParams;
+
+/* HBAO_Blur.shader:54-59 PostProcessDataUBO (floats at 0, 4, 8) */
+typedef struct SailorHbaoBlurParams {
+    float sharpness;     /* shipped: 0.5 */
+    float distanceScale; /* 2 */
+    float radius;        /* 5; at most 64 */
+} SailorHbaoBlurParams;
+
+/* Replaces: the vkCmdBlitImage with VK_FILTER_NEAREST of a scaled single-channel image (BlitNode.cpp:88-96: depth formats are blitted with Nearest).
+ * Destination texel (i, j) takes source texel (((2 i + 1) * srcWidth) / (2 * dstWidth), ((2 j + 1) * srcHeight) / (2 * dstHeight)), integer division:
+ * the texel that contains the destination centre.  (Equal extents: sailor_hip_buffer_copy.) */
+SAILOR_HIP_API int sailor_hip_blit_nearest(SailorHipContext* ctx, const float* dSrc, int32_t srcWidth, int32_t srcHeight,
+                                           float* dDst, int32_t dstWidth, int32_t dstHeight);
+/* Replaces: the DrawIndexed(6) of PostProcessNode::Process (PostProcessNode.cpp:176-199) with Content/Shaders/HBAO.shader:185-249.
+ *   frame  : invProjection, cameraZNearZFar.x and viewportSize.y are read
+ *   dDepth : `depthSampler` (HalfDepth in the shipped file);  dNoise : `noiseSampler`, noiseWidth x noiseHeight decoded linear float4 texels, 16-byte aligned
+ *   dAo    : device out, the `color` target */
+SAILOR_HIP_API int sailor_hip_hbao(SailorHipContext* ctx, const SailorUboFrameData* frame, const float* dDepth, int32_t depthWidth, int32_t depthHeight,
+                                   const float* dNoise, int32_t noiseWidth, int32_t noiseHeight, const SailorHbaoParams* params,
+                                   float* dAo, int32_t width, int32_t height);
+/* Replaces: the same draw with Content/Shaders/HBAO_Blur.shader:82-111; vertical != 0 is the VERTICAL define (aoPixelSize.x = 0, :88-89), 0 HORIZONTAL.
+ *   dAo : `aoSampler`;  dDepth : `depthSampler` (the raw full-resolution DepthBuffer in the shipped file);  dDst : device out, the `color` target */
+SAILOR_HIP_API int sailor_hip_hbao_blur_pass(SailorHipContext* ctx, const float* dAo, int32_t aoWidth, int32_t aoHeight,
+                                             const float* dDepth, int32_t depthWidth, int32_t depthHeight, const SailorHbaoBlurParams* params,
+                                             float* dDst, int32_t width, int32_t height, int32_t vertical);
+/* The block's four launches (DefaultRenderer.renderer:204-264 without DepthHighZ): blit dDepth -> dHalfDepth, HBAO on dHalfDepth -> dAo, vertical
+ * blur of dAo against dDepth -> dTemp, horizontal blur of dTemp against dDepth -> dOut (g_AO).  The intermediates are the caller's; the launches are
+ * those of the four single calls.  Every argument is checked before the first launch. */
+SAILOR_HIP_API int sailor_hip_hbao_chain(SailorHipContext* ctx, const SailorUboFrameData* frame, const float* dDepth, int32_t depthWidth, int32_t depthHeight,
+                                         float* dHalfDepth, int32_t halfWidth, int32_t halfHeight, const float* dNoise, int32_t noiseWidth, int32_t noiseHeight,
+                                         const SailorHbaoParams* params, float* dAo, int32_t aoWidth, int32_t aoHeight,
+                                         const SailorHbaoBlurParams* blurParams, float* dTemp, int32_t tempWidth, int32_t tempHeight,
+                                         float* dOut, int32_t outWidth, int32_t outHeight);
+
 /* ---- RCCL exchange for split frames (only when the frame is split AND a consumer needs the global list) ----
  * `comm` is an ncclComm_t created by the host.  Collective 1: all-gather of one uint32 (band total) per rank.
  * Collective 2: all-gather of the padded band index segments (each rank contributes `segmentCapacity` uints). */

@@ -114,6 +114,19 @@ def tonemap_flags(defines: str) -> int:
     return flags
 
 
+class HbaoParams(C.Structure):  # include/sailor_hip.h SailorHbaoParams (HBAO.shader:50-57); defaults = DefaultRenderer.renderer:226-230
+    _fields_ = [("occlusionRadius", C.c_float), ("occlusionPower", C.c_float), ("occlusionAttenuation", C.c_float), ("occlusionBias", C.c_float),
+                ("noiseScale", C.c_float)]
+
+
+class HbaoBlurParams(C.Structure):  # include/sailor_hip.h SailorHbaoBlurParams (HBAO_Blur.shader:54-59); DefaultRenderer.renderer:243-245
+    _fields_ = [("sharpness", C.c_float), ("distanceScale", C.c_float), ("radius", C.c_float)]
+
+
+HBAO_SHIPPED = dict(occlusionRadius=700.0, occlusionPower=1.5, occlusionAttenuation=0.1, occlusionBias=0.05, noiseScale=25.0)
+HBAO_BLUR_SHIPPED = dict(sharpness=0.5, distanceScale=2.0, radius=5.0)
+
+
 class HiZDesc(C.Structure):
     _fields_ = [("pyramid", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("levels", C.c_int32)]
 
@@ -214,6 +227,14 @@ SIGNATURES = {
     "sailor_hip_eye_adaptation": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.POINTER(EyeAdaptationConstants), C.c_uint32, C.POINTER(C.c_float),
                                             C.c_float, _P]),
     "sailor_host_eye_adaptation_constants": (C.c_int, [C.c_int32, C.c_int32, C.c_float, C.POINTER(EyeAdaptationConstants)]),
+    "sailor_hip_blit_nearest": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32]),
+    "sailor_hip_hbao": (C.c_int, [_P, C.POINTER(UboFrameData), _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.POINTER(HbaoParams), _P, C.c_int32,
+                                  C.c_int32]),
+    "sailor_hip_hbao_blur_pass": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.POINTER(HbaoBlurParams), _P, C.c_int32, C.c_int32,
+                                            C.c_int32]),
+    "sailor_hip_hbao_chain": (C.c_int, [_P, C.POINTER(UboFrameData), _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32,
+                                        C.POINTER(HbaoParams), _P, C.c_int32, C.c_int32, C.POINTER(HbaoBlurParams), _P, C.c_int32, C.c_int32, _P, C.c_int32,
+                                        C.c_int32]),
     "sailor_hip_allgather_u32": (C.c_int, [_P, _P, _P, _P, C.c_size_t]),
     "sailor_hip_exchange_workspace_size": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "sailor_hip_exchange_light_lists": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_size_t, _P, C.c_size_t]),

@@ -598,3 +598,54 @@ class EyeAdaptation:
         _lib.check(self.ctx._lib.sailor_hip_eye_adaptation(self.ctx.handle, _ptr(color), _ptr(out), self.width, self.height, C.byref(constants), self.flags,
                                                            self.white_point, self.exposure, _ptr(self.state)), "sailor_hip_eye_adaptation", self.ctx.handle)
         return out
+
+
+class Hbao:
+    """The HBAO block of the frame graph (DefaultRenderer.renderer:202-264): Blit DepthBuffer -> HalfDepth, HBAO.shader -> AO, HBAO_Blur.shader VERTICAL ->
+    TemporaryR8 and HORIZONTAL -> g_AO.  Owns the three intermediates and g_AO; `run` returns g_AO, the plane SailorIblDesc.ao takes when it is
+    frame-sized (the default here; `extents=host.hbao_shipped_extents(w, h)` gives the shipped file's square targets).
+    `noise`: the noiseSampler texture as decoded linear float4 texels, (nh, nw, 4) float32 on the device."""
+
+    def __init__(self, ctx: HipContext, width: int, height: int, noise: torch.Tensor, params=None, blur_params=None, extents=None):
+        self.ctx, self.width, self.height = ctx, width, height
+        assert noise.dtype == torch.float32 and noise.is_contiguous() and noise.dim() == 3 and noise.shape[2] == 4, tuple(noise.shape)
+        self.noise = noise
+        self.params = params or host.hbao_params()
+        self.blur_params = blur_params or host.hbao_blur_params()
+        self.extents = extents or ((width // 2, width // 2), (width // 2, width // 2), (width, height), (width, height))
+        plane = lambda e: torch.empty((e[1], e[0]), dtype=torch.float32, device=ctx.device)
+        self.half_depth, self.ao, self.temp, self.g_ao = (plane(e) for e in self.extents)
+
+    def _check_plane(self, t: torch.Tensor):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2, (t.dtype, tuple(t.shape))
+
+    def blit(self, src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
+        self._check_plane(src), self._check_plane(dst)
+        _lib.check(self.ctx._lib.sailor_hip_blit_nearest(self.ctx.handle, _ptr(src), src.shape[1], src.shape[0], _ptr(dst), dst.shape[1], dst.shape[0]),
+                   "sailor_hip_blit_nearest", self.ctx.handle)
+        return dst
+
+    def hbao(self, frame, depth: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        self._check_plane(depth), self._check_plane(out)
+        _lib.check(self.ctx._lib.sailor_hip_hbao(self.ctx.handle, C.byref(frame), _ptr(depth), depth.shape[1], depth.shape[0], _ptr(self.noise),
+                                                 self.noise.shape[1], self.noise.shape[0], C.byref(self.params), _ptr(out), out.shape[1], out.shape[0]),
+                   "sailor_hip_hbao", self.ctx.handle)
+        return out
+
+    def blur_pass(self, ao: torch.Tensor, depth: torch.Tensor, out: torch.Tensor, vertical: bool) -> torch.Tensor:
+        self._check_plane(ao), self._check_plane(depth), self._check_plane(out)
+        _lib.check(self.ctx._lib.sailor_hip_hbao_blur_pass(self.ctx.handle, _ptr(ao), ao.shape[1], ao.shape[0], _ptr(depth), depth.shape[1], depth.shape[0],
+                                                           C.byref(self.blur_params), _ptr(out), out.shape[1], out.shape[0], 1 if vertical else 0),
+                   "sailor_hip_hbao_blur_pass", self.ctx.handle)
+        return out
+
+    def run(self, frame, raw_depth: torch.Tensor) -> torch.Tensor:
+        """the four launches on the raw (reversed-Z) depth attachment, height x width float32; returns g_AO"""
+        self._check_plane(raw_depth)
+        h, a, t, o = self.half_depth, self.ao, self.temp, self.g_ao
+        _lib.check(self.ctx._lib.sailor_hip_hbao_chain(self.ctx.handle, C.byref(frame), _ptr(raw_depth), raw_depth.shape[1], raw_depth.shape[0],
+                                                       _ptr(h), h.shape[1], h.shape[0], _ptr(self.noise), self.noise.shape[1], self.noise.shape[0],
+                                                       C.byref(self.params), _ptr(a), a.shape[1], a.shape[0], C.byref(self.blur_params),
+                                                       _ptr(t), t.shape[1], t.shape[0], _ptr(o), o.shape[1], o.shape[0]),
+                   "sailor_hip_hbao_chain", self.ctx.handle)
+        return o

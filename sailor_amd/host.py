@@ -74,6 +74,25 @@ def eye_adaptation_constants(width: int, height: int, delta_time: float) -> "_li
     return c
 
 
+def hbao_params(**values) -> "_lib.HbaoParams":
+    """HBAO.shader:50-57 PostProcessDataUBO; unnamed members keep the shipped values (DefaultRenderer.renderer:226-230)"""
+    v = dict(_lib.HBAO_SHIPPED)
+    v.update(values)
+    return _lib.HbaoParams(**{k: float(x) for k, x in v.items()})
+
+
+def hbao_blur_params(**values) -> "_lib.HbaoBlurParams":
+    """HBAO_Blur.shader:54-59 PostProcessDataUBO; unnamed members keep the shipped values (DefaultRenderer.renderer:243-245)"""
+    v = dict(_lib.HBAO_BLUR_SHIPPED)
+    v.update(values)
+    return _lib.HbaoBlurParams(**{k: float(x) for k, x in v.items()})
+
+
+def hbao_shipped_extents(width: int, height: int):
+    """(HalfDepth, AO, TemporaryR8, g_AO) as (width, height): DefaultRenderer.renderer:46-72 -- ViewportWidth / 2 squared twice, ViewportWidth squared twice"""
+    return (width // 2, width // 2), (width // 2, width // 2), (width, width), (width, width)
+
+
 def transform_matrix(position, rotation_xyzw, scale) -> np.ndarray:
     """Math/Transform.cpp:39-42; returns a column-major float32[16]."""
     trs = np.concatenate([_f32(position, 4), _f32(rotation_xyzw, 4), _f32(scale, 4)])

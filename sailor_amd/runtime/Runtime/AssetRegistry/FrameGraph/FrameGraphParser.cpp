@@ -207,6 +207,7 @@ FrameGraphBuildReport FrameGraphImporter::BuildFrameGraph(const FrameGraphAsset&
         const uint32_t numMips = std::min(rt.m_maxMipLevel, rt.m_bGenerateMips ? (uint32_t)std::floor(std::log2((float)maxExtent)) + 1 : 1u);
         auto target = driver->CreateRenderTarget({ (int32_t)rt.m_width, (int32_t)rt.m_height }, numMips, canonical_format(rt.m_format));
         if (!target) continue;
+        target->m_bDepthFormat = rt.m_format.rfind("D32_", 0) == 0 || rt.m_format.rfind("D24_", 0) == 0 || rt.m_format.rfind("D16_", 0) == 0; // RHI::IsDepthFormat
         graph.SetRenderTarget(rt.m_name, target);
         report.m_renderTargets++;
     }

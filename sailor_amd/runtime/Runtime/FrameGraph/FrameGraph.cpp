@@ -37,6 +37,8 @@ template class Sailor::Framegraph::TFrameGraphNode<LinearizeDepthNode>;
 template class Sailor::Framegraph::TFrameGraphNode<EnvironmentNode>;
 template class Sailor::Framegraph::TFrameGraphNode<DepthHighZNode>;
 template class Sailor::Framegraph::TFrameGraphNode<EyeAdaptationNode>;
+template class Sailor::Framegraph::TFrameGraphNode<PostProcessNode>;
+template class Sailor::Framegraph::TFrameGraphNode<BlitNode>;
 
 // ---- RHIFrameGraph ----------------------------------------------------------------------------------------------------------
 UboFrameData RHIFrameGraph::FillFrameData(RHICommandListPtr transferCmdList, RHISceneViewSnapshot& snapshot, float deltaTime, float worldTime) const
@@ -456,3 +458,100 @@ void EyeAdaptationNode::Clear() // (:223-230)
     m_pComputeHistogramShader.Clear();
     m_pComputeAverageShader.Clear();
 }
+
+// ---- PostProcessNode (FrameGraph/PostProcessNode.cpp:19-209) ---------------------------------------------------------------------
+const char* PostProcessNode::m_name = "PostProcess";
+
+void PostProcessNode::Process(RHIFrameGraphPtr frameGraph, RHICommandListPtr transferCommandList, RHICommandListPtr commandList, const RHISceneViewSnapshot& sceneView)
+{
+    auto driver = Renderer::GetDriver();
+    auto commands = Renderer::GetDriverCommands();
+    // a per-frame target or a sampler published under that name (FrameGraphParser.cpp:190-195 resolves both kinds)
+    auto byName = [&](const std::string& name) -> RHITexturePtr {
+        if (auto t = frameGraph->GetRenderTarget(name)) return t;
+        return frameGraph->GetSampler(name);
+    };
+    RHITexturePtr target = GetRHIResource("color").DynamicCast<RHITexture>(); // (:29-45; the MSAA surface has no counterpart here)
+    if (!target) {
+        auto it = m_unresolvedResourceParams.find("color");
+        target = frameGraph->GetRenderTarget(it != m_unresolvedResourceParams.end() ? it->second : std::string("BackBuffer"));
+    }
+    if (!m_pShader) { // (:47-59)
+        std::string shaderPath, definesStr;
+        if (!TryGetString("shader", shaderPath) || shaderPath.empty()) return; // check(!shaderPath.empty())
+        TryGetString("defines", definesStr);
+        TVector<std::string> defines; // Utils::SplitString(definesStr, " "); `~` is YAML's null
+        std::istringstream words(definesStr == "~" ? std::string() : definesStr);
+        for (std::string d; words >> d;) defines.push_back(d);
+        m_pShader = driver->CreateShader(shaderPath, defines);
+    }
+    if (!m_pShader || !m_pShader->IsReady() || !target) return; // (:61-64) a shader the backend has no entry point for records nothing
+
+    std::string shaderPath;
+    TryGetString("shader", shaderPath);
+    commands->BeginDebugRegion(commandList, std::string(GetName()) + ":" + shaderPath); // (:66-67)
+    if (!m_postEffectMaterial) { // (:69-108)
+        m_shaderBindings = driver->CreateShaderBindings();
+        driver->FillShadersLayout(m_shaderBindings, { m_pShader }, 1);                                                     // (:74)
+        const size_t uniformsSize = std::max<size_t>(256, m_vectorParams.size() * sizeof(vec4));                           // (:77)
+        driver->AddBufferToShaderBindings(m_shaderBindings, "data", uniformsSize, 0, EShaderBindingType::UniformBuffer); // (:78)
+        m_postEffectMaterial = driver->CreateMaterial(m_pShader);                                                          // (:82)
+        auto setParameter = [&](const std::string& name, const void* value, size_t size) { // SetMaterialParameter(cmd, bindings, "data.radius", value) splits at the dot
+            const size_t dot = name.find('.');
+            if (dot != std::string::npos) commands->SetMaterialParameter(transferCommandList, m_shaderBindings, name.substr(0, dot), name.substr(dot + 1), value, size);
+        };
+        for (const auto& v : m_vectorParams) setParameter(v.first, &v.second, sizeof(vec4)); // (:84-87)
+        for (const auto& f : m_floatParams) setParameter(f.first, &f.second, sizeof(float)); // (:89-92)
+        uint32_t slot = 1;
+        for (const auto& r : m_resourceParams) { // (:94-107) every resource under its own name, `color` included
+            if (auto texture = r.second.DynamicCast<RHITexture>()) driver->AddSamplerToShaderBindings(m_shaderBindings, r.first, texture, slot++);
+        }
+    }
+    for (const auto& r : m_unresolvedResourceParams) { // (:110-125) per-frame targets and late samplers, looked up every frame
+        if (r.first == "color") continue;
+        if (auto texture = byName(r.second)) driver->AddSamplerToShaderBindings(m_shaderBindings, r.first, texture, 0);
+        // (a name that resolves to nothing stays unbound: the draw is then refused with the invalid-argument status when it is submitted)
+    }
+    for (const auto& kv : m_shaderBindings->m_bindings) // (:138-149)
+        if (kv.second->m_type == EShaderBindingType::CombinedImageSampler && !kv.second->m_textures.empty())
+            commands->ImageMemoryBarrier(commandList, kv.second->m_textures[0], EImageLayout::ShaderReadOnlyOptimal);
+    commands->ImageMemoryBarrier(commandList, target, EImageLayout::ColorAttachmentOptimal); // (:151)
+
+    commands->BeginRenderPass(commandList, TVector<RHITexturePtr> { target }, RHITexturePtr());                                                   // (:172-180)
+    commands->BindMaterial(commandList, m_postEffectMaterial);                                                                                     // (:186)
+    commands->BindShaderBindings(commandList, m_postEffectMaterial, { sceneView.m_frameBindings, m_shaderBindings, sceneView.m_rhiLightsData }); // (:189)
+    commands->DrawIndexed(commandList, 6, 1, 0, 0, 0);                                                                                             // (:198) the full-screen NDC quad
+    commands->EndRenderPass(commandList);                                                                                                          // (:199)
+    commands->EndDebugRegion(commandList);
+}
+
+void PostProcessNode::Clear() // (:204-209)
+{
+    m_pShader.Clear();
+    m_postEffectMaterial.Clear();
+    m_shaderBindings.Clear();
+}
+
+// ---- BlitNode (FrameGraph/BlitNode.cpp:18-124, without the MSAA half) ---------------------------------------------------------------
+const char* BlitNode::m_name = "Blit";
+
+void BlitNode::Process(RHIFrameGraphPtr frameGraph, RHICommandListPtr, RHICommandListPtr commandList, const RHISceneViewSnapshot&)
+{
+    auto commands = Renderer::GetDriverCommands();
+    commands->BeginDebugRegion(commandList, GetName()); // (:27)
+    RHITexturePtr src = GetRHIResource("src").DynamicCast<RHITexture>(), dst = GetRHIResource("dst").DynamicCast<RHITexture>(); // (:52-53)
+    for (const auto& r : m_unresolvedResourceParams) { // (:55-65)
+        if (r.first == "src") src = frameGraph->GetRenderTarget(r.second);
+        else if (r.first == "dst") dst = frameGraph->GetRenderTarget(r.second);
+    }
+    if (src && dst) {
+        const bool bIsDepthFormat = src->m_bDepthFormat || dst->m_bDepthFormat; // (:67)
+        const ivec4 srcRegion { 0, 0, src->GetExtent().x, src->GetExtent().y }, dstRegion { 0, 0, dst->GetExtent().x, dst->GetExtent().y }; // (:82-83)
+        commands->ImageMemoryBarrier(commandList, src, EImageLayout::TransferSrcOptimal); // (:85-86)
+        commands->ImageMemoryBarrier(commandList, dst, EImageLayout::TransferDstOptimal);
+        commands->BlitImage(commandList, src, dst, srcRegion, dstRegion, bIsDepthFormat ? ETextureFiltration::Nearest : ETextureFiltration::Linear); // (:88)
+    }
+    commands->EndDebugRegion(commandList); // (:123)
+}
+
+void BlitNode::Clear() {}

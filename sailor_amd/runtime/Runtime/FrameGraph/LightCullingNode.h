@@ -124,4 +124,32 @@ protected:
     float m_whitePointLum = 0.0f;
 };
 
+// The generic full-screen pass: Runtime/FrameGraph/PostProcessNode.h.  Strings "shader" / "defines", float and vec4 parameters named
+// "<block>.<member>" (DefaultRenderer.renderer:222-230), resources: "color" = the target, every other name = a sampler of the shader.
+class PostProcessNode : public TFrameGraphNode<PostProcessNode> {
+public:
+    static const char* GetName() { return m_name; }
+    void Process(RHIFrameGraphPtr frameGraph, RHI::RHICommandListPtr transferCommandList, RHI::RHICommandListPtr commandList,
+                 const RHI::RHISceneViewSnapshot& sceneView) override;
+    void Clear() override;
+
+protected:
+    static const char* m_name;
+    RHI::RHIShaderPtr m_pShader;
+    RHI::RHIMaterialPtr m_postEffectMaterial;
+    RHI::RHIShaderBindingSetPtr m_shaderBindings;
+};
+
+// Runtime/FrameGraph/BlitNode.h without its MSAA half (BlitNode.cpp:90-122, BlitRaw): resources "src" and "dst".
+class BlitNode : public TFrameGraphNode<BlitNode> {
+public:
+    static const char* GetName() { return m_name; }
+    void Process(RHIFrameGraphPtr frameGraph, RHI::RHICommandListPtr transferCommandList, RHI::RHICommandListPtr commandList,
+                 const RHI::RHISceneViewSnapshot& sceneView) override;
+    void Clear() override;
+
+protected:
+    static const char* m_name;
+};
+
 } // namespace Sailor::Framegraph

@@ -78,7 +78,19 @@ RHIBufferPtr HipGraphicsDriver::WrapBuffer(void* devicePtr, size_t size)
     return b;
 }
 
-RHIShaderPtr HipGraphicsDriver::CreateShader(const std::string& assetPath, const TVector<std::string>& defines) { return RHIShaderPtr::Make(assetPath, defines); }
+RHIShaderPtr HipGraphicsDriver::CreateShader(const std::string& assetPath, const TVector<std::string>& defines)
+{
+    // the shaders this backend has entry points for (HipGraphicsDriver.h); any other is created but never "ready", so a node that checks
+    // IsReady() before recording (PostProcessNode.cpp:61-64) records nothing for it
+    static const char* const routed[] = { "Shaders/ComputeLightCulling.shader", "Shaders/Standard.shader", "Shaders/ComputeMeshCulling.shader",
+        "Shaders/ComputeDepthHighZ.shader", "Shaders/ComputeHistogram.shader", "Shaders/ComputeAverageLuminance.shader", "Shaders/ComputeBrdfLut.shader",
+        "Shaders/ComputeIrradianceMap.shader", "Shaders/ComputeEnvMap_IBL.shader", "Shaders/ShadowCaster.shader", "Shaders/LinearizeDepth.shader",
+        "Shaders/Tonemapping.shader", "Shaders/Blur.shader", "Shaders/HBAO.shader", "Shaders/HBAO_Blur.shader" };
+    auto shader = RHIShaderPtr::Make(assetPath, defines);
+    shader->m_bIsReady = false;
+    for (const char* name : routed) if (assetPath == name) shader->m_bIsReady = true;
+    return shader;
+}
 
 static size_t texel_size(EFormat f) { return f == EFormat::R16_SFLOAT ? 2 : (f == EFormat::R32_SFLOAT ? 4 : (f == EFormat::R32G32_SFLOAT ? 8 : 16)); }
 
@@ -190,6 +202,15 @@ void HipGraphicsDriver::BeforeBufferWrite(const void* devicePtr)
 RHIMaterialPtr HipGraphicsDriver::CreateMaterial(RHIShaderPtr shader) { return RHIMaterialPtr::Make(std::move(shader)); }
 
 RHIShaderBindingSetPtr HipGraphicsDriver::CreateShaderBindings() { return RHIShaderBindingSetPtr::Make(); }
+
+// VulkanGraphicsDriver::FillShadersLayout copies the reflected bindings of descriptor set `setNum` into the set.  No reflection here: the set remembers
+// whose layout it follows, and SetMaterialParameter finds the uniform block's member offsets by that name.
+bool HipGraphicsDriver::FillShadersLayout(RHIShaderBindingSetPtr& set, const TVector<RHIShaderPtr>& shaders, uint32_t)
+{
+    if (!set) return false;
+    for (auto& s : shaders) if (s) { set->m_layoutShader = s->m_name; return true; }
+    return false;
+}
 
 RHIShaderBindingPtr HipGraphicsDriver::AddSsboToShaderBindings(RHIShaderBindingSetPtr& set, const std::string& name, size_t elementSize,
                                                                size_t numElements, uint32_t shaderBinding, bool)
@@ -337,26 +358,46 @@ void HipGraphicsDriver::ClearImage(RHICommandListPtr cmd, RHITexturePtr dst, flo
 }
 
 // VulkanGraphicsDriver's SetMaterialParameter finds the variable's offset in the reflected layout of the uniform block; here the one block the path
-// sets this way is Tonemapping.shader:52-56 PostProcessDataUBO { vec4 whitePoint; vec4 exposure; }
+// sets this way were Tonemapping.shader:52-56 PostProcessDataUBO { vec4 whitePoint; vec4 exposure; } alone; with PostProcessNode the blocks of
+// HBAO.shader:50-57 (five floats, std140 offsets 0, 4, 8, 12, 16) and HBAO_Blur.shader:54-59 (three floats: 0, 4, 8) join, so the member table is
+// keyed by the shader whose layout the set follows (FillShadersLayout); a set without one is the tone map's, as before.
 void HipGraphicsDriver::SetMaterialParameter(RHICommandListPtr cmd, RHIShaderBindingSetPtr bindings, const std::string& binding, const std::string& variable,
                                              const void* value, size_t size)
 {
     auto b = bindings ? bindings->Find(binding) : RHIShaderBindingPtr();
-    size_t offset;
-    if (binding == "data" && variable == "whitePoint") offset = 0;
-    else if (binding == "data" && variable == "exposure") offset = 16;
-    else { m_lastDispatchStatus = SAILOR_HIP_ERR_UNSUPPORTED; return; }
+    struct Member { const char* shader; const char* variable; size_t offset; };
+    static const Member members[] = {
+        { "", "whitePoint", 0 }, { "", "exposure", 16 }, { "Shaders/Tonemapping.shader", "whitePoint", 0 }, { "Shaders/Tonemapping.shader", "exposure", 16 },
+        { "Shaders/HBAO.shader", "occlusionRadius", 0 }, { "Shaders/HBAO.shader", "occlusionPower", 4 }, { "Shaders/HBAO.shader", "occlusionAttenuation", 8 },
+        { "Shaders/HBAO.shader", "occlusionBias", 12 }, { "Shaders/HBAO.shader", "noiseScale", 16 },
+        { "Shaders/HBAO_Blur.shader", "sharpness", 0 }, { "Shaders/HBAO_Blur.shader", "distanceScale", 4 }, { "Shaders/HBAO_Blur.shader", "radius", 8 } };
+    const std::string layout = bindings ? bindings->m_layoutShader : std::string();
+    size_t offset = (size_t)-1;
+    if (binding == "data")
+        for (const auto& m : members) if (layout == m.shader && variable == m.variable) offset = m.offset;
+    if (offset == (size_t)-1) { m_lastDispatchStatus = SAILOR_HIP_ERR_UNSUPPORTED; return; }
     if (!b || b->m_type != EShaderBindingType::UniformBuffer) { m_lastDispatchStatus = SAILOR_HIP_ERR_INVALID_ARGUMENT; return; }
     UpdateShaderBinding(cmd, b, value, size, offset);
 }
 
-bool HipGraphicsDriver::BlitImage(RHICommandListPtr cmd, RHITexturePtr src, RHITexturePtr dst, ivec4 srcRegionRect, ivec4 dstRegionRect)
+bool HipGraphicsDriver::BlitImage(RHICommandListPtr cmd, RHITexturePtr src, RHITexturePtr dst, ivec4 srcRegionRect, ivec4 dstRegionRect, ETextureFiltration filtration)
 {
-    // the path's only blit copies level 0 of one cubemap to another of the same size and format (EnvironmentNode.cpp:200-203): a device copy
-    if (!src || !dst || src->m_format != dst->m_format || src->GetExtent().x != dst->GetExtent().x || src->GetExtent().y != dst->GetExtent().y ||
-        srcRegionRect.x != 0 || srcRegionRect.y != 0 || dstRegionRect.x != 0 || dstRegionRect.y != 0 || srcRegionRect.z != dstRegionRect.z ||
-        srcRegionRect.w != dstRegionRect.w || srcRegionRect.z != src->GetExtent().x || srcRegionRect.w != src->GetExtent().y)
-        return false;
+    // whole images of one format only: equal extents are a device copy (level 0 of one cubemap to another, EnvironmentNode.cpp:200-203; a same-size
+    // BlitNode), a scaled one-channel image with Nearest filtration (BlitNode.cpp:88: DepthBuffer -> HalfDepth) is sailor_hip_blit_nearest
+    const bool whole = src && dst && src->m_buffer && dst->m_buffer && src->m_format == dst->m_format && srcRegionRect.x == 0 && srcRegionRect.y == 0 &&
+                       dstRegionRect.x == 0 && dstRegionRect.y == 0 && srcRegionRect.z == src->GetExtent().x && srcRegionRect.w == src->GetExtent().y &&
+                       dstRegionRect.z == dst->GetExtent().x && dstRegionRect.w == dst->GetExtent().y;
+    const bool sameExtent = whole && src->GetExtent().x == dst->GetExtent().x && src->GetExtent().y == dst->GetExtent().y;
+    if (whole && !sameExtent && filtration == ETextureFiltration::Nearest && src->m_format == EFormat::R32_SFLOAT && !src->m_bCubemap && !dst->m_bCubemap) {
+        SailorHipContext* ctx = m_ctx;
+        cmd->m_hip.m_commands.push_back([this, ctx, src, dst]() {
+            BeforeBufferWrite(dst->m_buffer->m_hip.m_devicePtr);
+            return sailor_hip_blit_nearest(ctx, (const float*)texels_of(src), src->GetExtent().x, src->GetExtent().y, (float*)texels_of(dst), dst->GetExtent().x,
+                                           dst->GetExtent().y);
+        });
+        return true;
+    }
+    if (!sameExtent) { m_lastDispatchStatus = SAILOR_HIP_ERR_UNSUPPORTED; return false; }
     const size_t bytes = (size_t)(src->m_bCubemap ? 6 : 1) * src->GetExtent().x * src->GetExtent().y * texel_size(src->m_format);
     SailorHipContext* ctx = m_ctx;
     cmd->m_hip.m_commands.push_back([this, ctx, src, dst, bytes]() {
@@ -713,6 +754,8 @@ void HipGraphicsDriver::DrawIndexed(RHICommandListPtr cmd, uint32_t indexCount, 
     TVector<RHIShaderBindingSetPtr> bindings;
     for (auto& set : cmd->m_boundBindings) {
         auto copy = RHIShaderBindingSetPtr::Make();
+        if (!set) { bindings.push_back(copy); continue; } // (a scene without lights hands PostProcessNode a null lights set)
+        copy->m_layoutShader = set->m_layoutShader;
         for (auto& kv : set->m_bindings) {
             auto b = copy->GetOrAddShaderBinding(kv.first);
             b->m_type = kv.second->m_type; b->m_binding = kv.second->m_binding; b->m_buffer = kv.second->m_buffer;
@@ -729,6 +772,8 @@ void HipGraphicsDriver::DrawIndexed(RHICommandListPtr cmd, uint32_t indexCount, 
         if (fullScreenQuad && name == "Shaders/LinearizeDepth.shader") return RecordLinearizeDepth(bindings, target);
         if (fullScreenQuad && name == "Shaders/Tonemapping.shader") return RecordTonemap(bindings, target, tonemapFlags);
         if (fullScreenQuad && name == "Shaders/Blur.shader" && evsm && vertical != horizontal) return RecordEvsmBlur(bindings, target, vertical);
+        if (fullScreenQuad && name == "Shaders/HBAO.shader") return RecordHbao(bindings, target);
+        if (fullScreenQuad && name == "Shaders/HBAO_Blur.shader" && vertical != horizontal) return RecordHbaoBlur(bindings, target, vertical);
         return (int)SAILOR_HIP_ERR_UNSUPPORTED;
     });
 }
@@ -809,6 +854,52 @@ int HipGraphicsDriver::RecordTonemap(const TVector<RHIShaderBindingSetPtr>& bind
     BeforeBufferWrite(target->m_buffer->m_hip.m_devicePtr);
     return sailor_hip_tonemap(m_ctx, (const float*)src->m_buffer->m_hip.m_devicePtr, (float*)target->m_buffer->m_hip.m_devicePtr, target->GetExtent().x,
                               target->GetExtent().y, &whole, operatorFlags, data, data[4], lumB->m_textures[0]->m_hipEyeAdaptationState->m_hip.m_devicePtr);
+}
+
+// ---- PostProcessNode with the HBAO shaders (FrameGraph/PostProcessNode.cpp:186-199; DefaultRenderer.renderer:220-264) ---------------------------
+// a bound sampler as a one-channel fp32 plane, or null
+static RHITexturePtr plane_of(const RHIShaderBindingSetPtr& set, const char* name)
+{
+    auto b = set ? set->Find(name) : RHIShaderBindingPtr();
+    if (!b || b->m_textures.empty() || !b->m_textures[0] || !b->m_textures[0]->m_buffer || b->m_textures[0]->m_format != EFormat::R32_SFLOAT) return RHITexturePtr();
+    return b->m_textures[0];
+}
+
+int HipGraphicsDriver::RecordHbao(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& target)
+{
+    // PostProcessNode.cpp:189: { sceneView.m_frameBindings, m_shaderBindings, sceneView.m_rhiLightsData }; HBAO.shader:26-36 (set 0 frame), :50-60 (set 1:
+    // binding 0 `data`, 1 `depthSampler`, 2 `noiseSampler`).  A name that resolved to nothing is an invalid argument.
+    if (bindings.size() < 2 || !target || !target->m_buffer || target->m_format != EFormat::R32_SFLOAT) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    auto frameB = bindings[0]->Find("frameData");
+    auto dataB = bindings[1]->Find("data");
+    auto depth = plane_of(bindings[1], "depthSampler");
+    auto noiseB = bindings[1]->Find("noiseSampler");
+    if (!frameB || frameB->m_hostCopy.size() < sizeof(SailorUboFrameData) || !dataB || dataB->m_hostCopy.size() < sizeof(SailorHbaoParams) || !depth || !noiseB ||
+        noiseB->m_textures.empty() || !noiseB->m_textures[0] || !noiseB->m_textures[0]->m_buffer)
+        return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    const auto& noise = noiseB->m_textures[0];
+    if (noise->m_format != EFormat::R32G32B32A32_SFLOAT) return SAILOR_HIP_ERR_UNSUPPORTED;
+    SailorUboFrameData frame;
+    memcpy(&frame, frameB->m_hostCopy.data(), sizeof frame);
+    SailorHbaoParams params;
+    memcpy(&params, dataB->m_hostCopy.data(), sizeof params);
+    BeforeBufferWrite(target->m_buffer->m_hip.m_devicePtr);
+    return sailor_hip_hbao(m_ctx, &frame, (const float*)texels_of(depth), depth->GetExtent().x, depth->GetExtent().y, (const float*)texels_of(noise),
+                           noise->GetExtent().x, noise->GetExtent().y, &params, (float*)texels_of(target), target->GetExtent().x, target->GetExtent().y);
+}
+
+int HipGraphicsDriver::RecordHbaoBlur(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& target, bool vertical)
+{
+    // HBAO_Blur.shader:54-62: set 1 binding 0 `data` { sharpness, distanceScale, radius }, 1 `depthSampler`, 2 `aoSampler`
+    if (bindings.size() < 2 || !target || !target->m_buffer || target->m_format != EFormat::R32_SFLOAT) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    auto dataB = bindings[1]->Find("data");
+    auto depth = plane_of(bindings[1], "depthSampler"), ao = plane_of(bindings[1], "aoSampler");
+    if (!dataB || dataB->m_hostCopy.size() < sizeof(SailorHbaoBlurParams) || !depth || !ao) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    SailorHbaoBlurParams params;
+    memcpy(&params, dataB->m_hostCopy.data(), sizeof params);
+    BeforeBufferWrite(target->m_buffer->m_hip.m_devicePtr);
+    return sailor_hip_hbao_blur_pass(m_ctx, (const float*)texels_of(ao), ao->GetExtent().x, ao->GetExtent().y, (const float*)texels_of(depth), depth->GetExtent().x,
+                                     depth->GetExtent().y, &params, (float*)texels_of(target), target->GetExtent().x, target->GetExtent().y, vertical ? 1 : 0);
 }
 
 int HipGraphicsDriver::RecordEvsmBlur(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& target, bool vertical)

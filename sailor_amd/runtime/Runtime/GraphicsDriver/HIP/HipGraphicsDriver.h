@@ -16,6 +16,9 @@
 //   "Shaders/LinearizeDepth.shader"      -> sailor_hip_linearize_depth   (binding contract: LinearizeDepth.shader:15-59)
 //   "Shaders/Tonemapping.shader" {ACES, UNCHARTED2, LUMINANCE} -> sailor_hip_tonemap (binding contract: Tonemapping.shader:52-59)
 //   "Shaders/Blur.shader" {EVSM, HORIZONTAL | VERTICAL} -> sailor_hip_evsm_blur_pass (binding contract: Blur.shader:53-61)
+//   "Shaders/HBAO.shader"                -> sailor_hip_hbao              (binding contract: HBAO.shader:50-60)
+//   "Shaders/HBAO_Blur.shader" {VERTICAL | HORIZONTAL, exactly one} -> sailor_hip_hbao_blur_pass (binding contract: HBAO_Blur.shader:54-62)
+// a scaled one-channel BlitImage with Nearest filtration -> sailor_hip_blit_nearest
 // and the depth-only instanced draws of the shadow passes (material of)
 //   "Shaders/ShadowCaster.shader" [EVSM]  -> sailor_hip_raster_depth into the pass' depth attachment, and at EndRenderPass sailor_hip_shadow_resolve
 //                                            into its colour attachment (push constant lightMatrix, set 1 `data`, vertex positions, 32-bit indices)
@@ -47,6 +50,7 @@ public:
     void SubmitCommandList(RHI::RHICommandListPtr commandList) override;
     RHI::RHIMaterialPtr CreateMaterial(RHI::RHIShaderPtr shader) override;
     RHI::RHIShaderBindingSetPtr CreateShaderBindings() override;
+    bool FillShadersLayout(RHI::RHIShaderBindingSetPtr& set, const TVector<RHI::RHIShaderPtr>& shaders, uint32_t setNum) override;
     RHI::RHIShaderBindingPtr AddSsboToShaderBindings(RHI::RHIShaderBindingSetPtr& set, const std::string& name, size_t elementSize, size_t numElements,
                                                      uint32_t shaderBinding, bool bBindSsboWithOffset = false) override;
     RHI::RHIShaderBindingPtr AddBufferToShaderBindings(RHI::RHIShaderBindingSetPtr& set, const std::string& name, size_t size, uint32_t shaderBinding,
@@ -79,7 +83,8 @@ public:
     void EndDebugRegion(RHI::RHICommandListPtr cmdList) override;
     void ImageMemoryBarrier(RHI::RHICommandListPtr cmd, RHI::RHITexturePtr image, RHI::EImageLayout newLayout) override;
     void ClearImage(RHI::RHICommandListPtr cmd, RHI::RHITexturePtr dst, float r, float g, float b, float a) override;
-    bool BlitImage(RHI::RHICommandListPtr cmd, RHI::RHITexturePtr src, RHI::RHITexturePtr dst, RHI::ivec4 srcRegionRect, RHI::ivec4 dstRegionRect) override;
+    bool BlitImage(RHI::RHICommandListPtr cmd, RHI::RHITexturePtr src, RHI::RHITexturePtr dst, RHI::ivec4 srcRegionRect, RHI::ivec4 dstRegionRect,
+                   RHI::ETextureFiltration filtration = RHI::ETextureFiltration::Linear) override;
     void GenerateMipMaps(RHI::RHICommandListPtr cmd, RHI::RHITexturePtr target) override;
     void ConvertEquirect2Cubemap(RHI::RHICommandListPtr cmd, RHI::RHITexturePtr equirect, RHI::RHICubemapPtr cubemap) override;
     void UpdateShaderBinding(RHI::RHICommandListPtr cmd, RHI::RHIShaderBindingPtr binding, const void* data, size_t size, size_t variableOffset = 0) override;
@@ -112,6 +117,8 @@ private:
     int RecordAverageLuminance(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const TVector<uint8_t>& pc);
     int RecordTonemap(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target, uint32_t operatorFlags);
     int RecordEvsmBlur(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target, bool vertical);
+    int RecordHbao(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target);
+    int RecordHbaoBlur(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target, bool vertical);
 
     SailorHipContext* m_ctx = nullptr;              // == m_ctxOwner.get(): what the C-ABI calls take
     std::shared_ptr<SailorHipContext> m_ctxOwner;   // destroyed with the last buffer that still refers to it

@@ -20,6 +20,7 @@ public:
     virtual void SubmitCommandList(RHICommandListPtr commandList) = 0;                                     // :149
     virtual RHIMaterialPtr CreateMaterial(RHIShaderPtr shader) = 0;                                        // :138-141 (vertex layout / topology / render state dropped)
     virtual RHIShaderBindingSetPtr CreateShaderBindings() = 0;                                             // :152
+    virtual bool FillShadersLayout(RHIShaderBindingSetPtr& pShaderBindings, const TVector<RHIShaderPtr>& shaders, uint32_t setNum) = 0; // :153
     virtual RHIShaderBindingPtr AddSsboToShaderBindings(RHIShaderBindingSetPtr& pShaderBindings, const std::string& name, size_t elementSize,
                                                         size_t numElements, uint32_t shaderBinding, bool bBindSsboWithOffset = false) = 0; // :154
     virtual RHIShaderBindingPtr AddBufferToShaderBindings(RHIShaderBindingSetPtr& pShaderBindings, const std::string& name, size_t size,
@@ -43,7 +44,8 @@ public:
     virtual void EndDebugRegion(RHICommandListPtr cmdList) = 0;                              // :239
     virtual void ImageMemoryBarrier(RHICommandListPtr cmd, RHITexturePtr image, EImageLayout newLayout) = 0; // :290
     virtual void ClearImage(RHICommandListPtr cmd, RHITexturePtr dst, float r, float g, float b, float a) = 0;   // :294 (a glm::vec4 there)
-    virtual bool BlitImage(RHICommandListPtr cmd, RHITexturePtr src, RHITexturePtr dst, ivec4 srcRegionRect, ivec4 dstRegionRect) = 0;                 // :293 (equal regions only: a copy)
+    virtual bool BlitImage(RHICommandListPtr cmd, RHITexturePtr src, RHITexturePtr dst, ivec4 srcRegionRect, ivec4 dstRegionRect,
+                           ETextureFiltration filtration = ETextureFiltration::Linear) = 0; // :293 (equal extents: a copy; scaled: one channel, Nearest)
     virtual void GenerateMipMaps(RHICommandListPtr cmd, RHITexturePtr target) = 0;                                                                  // :296 (cubemaps)
     virtual void ConvertEquirect2Cubemap(RHICommandListPtr cmd, RHITexturePtr equirect, RHICubemapPtr cubemap) = 0;                                 // :297
     virtual void UpdateShaderBinding(RHICommandListPtr cmd, RHIShaderBindingPtr binding, const void* data, size_t size, size_t variableOffset = 0) = 0; // :303

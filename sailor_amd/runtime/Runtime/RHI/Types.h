@@ -74,6 +74,7 @@ public:
 using RHIBufferPtr = TRefPtr<RHIBuffer>;
 
 enum class EFormat { R32_SFLOAT, R16_SFLOAT, R32G32B32A32_SFLOAT, R32G32_SFLOAT };
+enum class ETextureFiltration { Nearest, Linear }; // RHI/Types.h ETextureFiltration (Bicubic has no user on the path)
 enum class EImageLayout { Undefined, ShaderReadOnlyOptimal, General, ColorAttachmentOptimal, ComputeWrite, TransferSrcOptimal, TransferDstOptimal };
 
 // RHI/Texture.h: here a linear row-major image in device memory (row 0 = top)
@@ -91,6 +92,9 @@ public:
     // HIP backend, EyeAdaptationNode's 1 x 1 average-luminance target only: the node state (include/sailor_hip.h sailor_hip_eye_adaptation_state_size)
     // whose luminance word m_buffer is a view of -- the `histogram` SSBO the target is bound beside (EyeAdaptationNode.cpp:102-108)
     RHIBufferPtr m_hipEyeAdaptationState;
+    // RHI::IsDepthFormat(GetFormat()) of the reference: the canonical fp32 plane of a D32_SFLOAT* / D16_UNORM* target remembers that it is one
+    // (BlitNode.cpp:67,88 picks the blit's filtration by it)
+    bool m_bDepthFormat = false;
     ivec2 GetExtent() const { return m_extent; }
     uint32_t GetMipLevels() const { return m_mipLevels; }
     TRefPtr<RHITexture> GetMipLevel(uint32_t mipLevel) const;
@@ -133,6 +137,9 @@ public:
         return it == m_bindings.end() ? RHIShaderBindingPtr() : it->second;
     }
     std::map<std::string, RHIShaderBindingPtr> m_bindings;
+    // IGraphicsDriver::FillShadersLayout: the shader whose reflected layout this set follows ("" = none assigned).  The HIP backend has no
+    // reflection; it knows the uniform blocks of the shaders it routes by their asset path.
+    std::string m_layoutShader;
 };
 using RHIShaderBindingSetPtr = TRefPtr<RHIShaderBindingSet>;
 
@@ -143,6 +150,9 @@ public:
     std::string m_name;
     std::vector<std::string> m_defines; // the permutation (ShaderCompiler::LoadShader_Immediate(fileId, shader, { "VERTICAL", "EVSM" }), ShadowPrepassNode.cpp:60)
     bool HasDefine(const std::string& d) const { for (auto& x : m_defines) if (x == d) return true; return false; }
+    // RHI/Shader.h IsReady(): compiled and usable.  Here: the backend has an entry point for it (HipGraphicsDriver::CreateShader)
+    bool m_bIsReady = true;
+    bool IsReady() const { return m_bIsReady; }
 };
 using RHIShaderPtr = TRefPtr<RHIShader>;
 

@@ -417,6 +417,17 @@ RT_API int sailor_rt_set_environment_map(SailorRuntime* rt, void* equirect, int 
     return 0;
 }
 
+// A file texture the `.renderer` text names under `samplers:` (g_noiseSampler: Textures/Noise.png), which the parser records and does not load:
+// the caller hands over the decoded linear RGBA32F texels and the graph publishes them under the sampler's name (RHIFrameGraph::SetSampler,
+// what FrameGraphParser.cpp:133-149 does once the TextureImporter has loaded the file).
+RT_API int sailor_rt_set_sampler(SailorRuntime* rt, const char* name, void* texels, int width, int height)
+{
+    auto* hip = static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver());
+    if (!rt || !name || !texels || width <= 0 || height <= 0) return -1;
+    rt->graph.SetSampler(name, hip->WrapTexture(texels, { width, height }, EFormat::R32G32B32A32_SFLOAT));
+    return 0;
+}
+
 // device pointer + geometry of a sampler the graph's nodes published (g_brdfSampler, g_envCubemap, g_irradianceCubemap, ...)
 RT_API void* sailor_rt_sampler(SailorRuntime* rt, const char* name, int* outWidth, int* outHeight, int* outLevels)
 {

@@ -56,6 +56,7 @@ def load() -> C.CDLL:
         rt.sailor_rt_render_target.restype = P
         rt.sailor_rt_render_target.argtypes = [P, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         rt.sailor_rt_set_render_target.argtypes = [P, C.c_char_p, P, C.c_int, C.c_int]
+        rt.sailor_rt_set_sampler.argtypes = [P, C.c_char_p, P, C.c_int, C.c_int]
         rt.sailor_rt_set_color_target.argtypes = [P, C.c_char_p, P, C.c_int, C.c_int]
         rt.sailor_rt_set_time.argtypes = [P, C.c_float, C.c_float]
         rt.sailor_rt_eye_adaptation_state.argtypes = [P, C.POINTER(P), C.POINTER(P)]
@@ -231,6 +232,12 @@ class Runtime:
     def set_render_target(self, name: str, tensor):
         """publish a float32 [h, w] device tensor as a named render target (DepthBuffer, ...)"""
         self.rt.sailor_rt_set_render_target(self.h, name.encode(), tensor.data_ptr(), tensor.shape[1], tensor.shape[0])
+
+    def set_sampler(self, name: str, tensor, width: int, height: int) -> int:
+        """publish a float32 [height, width, 4] device tensor of decoded linear texels under a sampler name of the `.renderer` text
+        (g_noiseSampler: the file texture the parser records and does not load); the tensor must outlive the graph"""
+        assert tuple(tensor.shape) == (height, width, 4) and tensor.is_contiguous(), tuple(tensor.shape)
+        return self.rt.sailor_rt_set_sampler(self.h, name.encode(), tensor.data_ptr(), width, height)
 
     def set_color_target(self, name: str, tensor):
         """publish a float32 [h, w, 4] device tensor as a named RGBA render target (the HDR target RenderScene's radiance stands for, an LDR target)"""
