@@ -769,6 +769,64 @@ SAILOR_HIP_API int sailor_hip_hbao_chain(SailorHipContext* ctx, const SailorUboF
                                          const SailorHbaoBlurParams* blurParams, float* dTemp, int32_t tempWidth, int32_t tempHeight,
                                          float* dOut, int32_t outWidth, int32_t outHeight);
 
+/* ---- Sky: the producer of the `Sky` target and of g_skyCubemap (EnvironmentNode.cpp bakes g_envCubemap / g_irradianceCubemap from it) ------
+ * Replaces: the GPU work of SkyNode::Process (FrameGraph/SkyNode.cpp:524-818) with Content/Shaders/Sky.shader under the define sets {FILL}, {},
+ * {SUN} and {COMPOSE}.  Every image is RGBA32F in device memory, 16-byte aligned (the reference: R16G16B16A16_SFLOAT), row 0 = top, texel (i, j)
+ * of a w x h target has the quad's inTexcoord ((i + 0.5) / w, (j + 0.5) / h); alpha is stored as 0.  The arithmetic is fixed operation by
+ * operation (sailor_amd/csrc/sky.hip's header lists the decisions; tests/sky_ref.py restates it in NumPy float32): every branch is decided by
+ * geometry evaluated in fp32 exactly as written, exp is the fixed algorithm of canonical_math.h with its argument clamp, and only the sums over
+ * the 127 view steps are reassociated.  Not drawn: the cloud march ({CLOUDS}), Stars.shader, SunShafts.shader -- the entry points behave as
+ * the reference does with m_cloudsDensity == 0 (SkyNode.cpp:604-609).
+ * All of them record only (no synchronisation, capturable). */
+
+/* Sky.shader:116-136 PostProcessDataUBO == SkyNode::SkyParams (SkyNode.h:48-67), std140: a vec4 at 0, then 4-byte scalars at 16, 20, .. 80.  84 bytes. */
+typedef struct SailorSkyParams {
+    float lightDirection[4];
+    float cloudsAttenuation1;
+    float cloudsAttenuation2;
+    float cloudsDensity;
+    float cloudsCoverage;
+    float phaseInfluence1;
+    float phaseInfluence2;
+    float eccentrisy1;
+    float eccentrisy2;
+    float fog;
+    float sunIntensity;
+    float ambient;
+    int32_t scatteringSteps;
+    float scatteringDensity;
+    float scatteringIntensity;
+    float scatteringPhase;
+    float sunShaftsIntensity;
+    int32_t sunShaftsDistance;
+} SailorSkyParams;
+
+/* Replaces: the draw "Sky" (SkyNode.cpp:536-563), define FILL = Sky.shader:717-734: SkyLighting with the Earth test of IntersectSphere (:233-243).
+ *   frame : view, invProjection and cameraPosition (centimetres) are read;  dSky : device out, height x width float4 (the node: 256 x 256) */
+SAILOR_HIP_API int sailor_hip_sky_fill(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSkyParams* params,
+                                       float* dSky, int32_t width, int32_t height);
+/* Replaces: one face of "Generate Environment Map" (SkyNode.cpp:764-797), no define: the same integral without the Earth test, under the view
+ * matrix of `face` and the 90 degree PerspectiveRH(.., 0.1, 1000) of SkyNode.cpp:487-495 (sailor_host_sky_face_matrices).
+ *   cameraPosition3 : host, the scene camera's position in centimetres (frameData.m_cameraPosition, :503)
+ *   dCube : device in/out, the level-major RGBA32F cube chain of sailor_hip_generate_mipmaps_cube; face `face` of level 0 is written */
+SAILOR_HIP_API int sailor_hip_sky_env_face(SailorHipContext* ctx, const float* cameraPosition3, const SailorSkyParams* params,
+                                           float* dCube, int32_t size, int32_t face);
+/* Replaces: the draw "Sun" (SkyNode.cpp:611-642), define SUN = Sky.shader:693-715 with the SUN branches of SkyLighting (:309-316, :360-374).
+ *   dClouds : `cloudsSampler` (:710).  NULL = the cleared m_pCloudsTexture, alpha 0; a plane is SAILOR_HIP_ERR_UNSUPPORTED until the cloud march exists
+ *   dSun    : device out, height x width float4 (the node: 32 x 32) */
+SAILOR_HIP_API int sailor_hip_sky_sun(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSkyParams* params,
+                                      const float* dClouds, int32_t cloudsWidth, int32_t cloudsHeight, float* dSun, int32_t width, int32_t height);
+/* Replaces: the draw "Compose" (SkyNode.cpp:644-680), define COMPOSE = Sky.shader:613-643: `skySampler` bilinear with Repeat addressing, `sunSampler`
+ * bilinear clamp-to-edge inside the +-SunAngularR window, merged by max(out, mix(out, sun, min(1, dot(sun, sun)))).
+ *   dOut : device out, float4 per pixel of the width x height target, the rows of `band` only (first row = band->fbRowBegin) */
+SAILOR_HIP_API int sailor_hip_sky_compose(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSkyParams* params,
+                                          const float* dSky, int32_t skyWidth, int32_t skyHeight, const float* dSun, int32_t sunWidth, int32_t sunHeight,
+                                          float* dOut, int32_t width, int32_t height, const SailorBand* band);
+/* The whole cube for callers that do not time-slice it over eight frames (SkyNode.cpp:749-818): six sailor_hip_sky_env_face launches, then
+ * sailor_hip_generate_mipmaps_cube (:800-801).  Every argument is checked before the first launch. */
+SAILOR_HIP_API int sailor_hip_sky_env_cubemap(SailorHipContext* ctx, const float* cameraPosition3, const SailorSkyParams* params,
+                                              float* dCube, int32_t size, int32_t levels);
+
 /* ---- RCCL exchange for split frames (only when the frame is split AND a consumer needs the global list) ----
  * `comm` is an ncclComm_t created by the host.  Collective 1: all-gather of one uint32 (band total) per rank.
  * Collective 2: all-gather of the padded band index segments (each rank contributes `segmentCapacity` uints). */
@@ -845,6 +903,12 @@ SAILOR_HIP_API int sailor_host_csm_matrices(const float* lightView, const float*
 SAILOR_HIP_API int sailor_host_pack_light(uint32_t type, uint32_t shadowType, const float* worldPosition, const float* direction,
                                           const float* intensity, const float* attenuation, const float* cutOffDegrees, const float* bounds,
                                           SailorLightShaderData* outLight);
+
+/* FrameGraph/SkyNode.h:50-67: the member initialisers of SkyNode::SkyParams */
+SAILOR_HIP_API int sailor_host_sky_params_default(SailorSkyParams* outParams);
+/* FrameGraph/SkyNode.cpp:487-495: the view matrix of cube face 0..5 (glm::rotate about Math::vec3_Up / vec3_Right), PerspectiveRH(radians(90), 1,
+ * 0.1, 1000) and its inverse, as the node writes them into the faces' frame data (:502-508) */
+SAILOR_HIP_API int sailor_host_sky_face_matrices(int32_t face, float* outView16, float* outProjection16, float* outInvProjection16);
 
 /* FrameGraph/EyeAdaptationNode.cpp:154-170: the push constants of the node's two Dispatches for a width x height HDR target */
 SAILOR_HIP_API int sailor_host_eye_adaptation_constants(int32_t width, int32_t height, float deltaTime, SailorEyeAdaptationConstants* outConstants);

@@ -127,6 +127,17 @@ HBAO_SHIPPED = dict(occlusionRadius=700.0, occlusionPower=1.5, occlusionAttenuat
 HBAO_BLUR_SHIPPED = dict(sharpness=0.5, distanceScale=2.0, radius=5.0)
 
 
+class SkyParams(C.Structure):  # include/sailor_hip.h SailorSkyParams (Sky.shader:116-136 == SkyNode.h:48-67)
+    _fields_ = [("lightDirection", C.c_float * 4), ("cloudsAttenuation1", C.c_float), ("cloudsAttenuation2", C.c_float), ("cloudsDensity", C.c_float),
+                ("cloudsCoverage", C.c_float), ("phaseInfluence1", C.c_float), ("phaseInfluence2", C.c_float), ("eccentrisy1", C.c_float),
+                ("eccentrisy2", C.c_float), ("fog", C.c_float), ("sunIntensity", C.c_float), ("ambient", C.c_float), ("scatteringSteps", C.c_int32),
+                ("scatteringDensity", C.c_float), ("scatteringIntensity", C.c_float), ("scatteringPhase", C.c_float), ("sunShaftsIntensity", C.c_float),
+                ("sunShaftsDistance", C.c_int32)]
+
+
+SKY_RESOLUTION, SKY_SUN_RESOLUTION, SKY_ENV_CUBEMAP_SIZE, SKY_ENV_CUBEMAP_LEVELS = 256, 32, 256, 8  # SkyNode.h:13-15, SkyNode.cpp:755
+
+
 class HiZDesc(C.Structure):
     _fields_ = [("pyramid", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("levels", C.c_int32)]
 
@@ -235,6 +246,14 @@ SIGNATURES = {
     "sailor_hip_hbao_chain": (C.c_int, [_P, C.POINTER(UboFrameData), _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32,
                                         C.POINTER(HbaoParams), _P, C.c_int32, C.c_int32, C.POINTER(HbaoBlurParams), _P, C.c_int32, C.c_int32, _P, C.c_int32,
                                         C.c_int32]),
+    "sailor_hip_sky_fill": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(SkyParams), _P, C.c_int32, C.c_int32]),
+    "sailor_hip_sky_env_face": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(SkyParams), _P, C.c_int32, C.c_int32]),
+    "sailor_hip_sky_sun": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(SkyParams), _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32]),
+    "sailor_hip_sky_compose": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(SkyParams), _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P,
+                                         C.c_int32, C.c_int32, C.POINTER(Band)]),
+    "sailor_hip_sky_env_cubemap": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(SkyParams), _P, C.c_int32, C.c_int32]),
+    "sailor_host_sky_params_default": (C.c_int, [C.POINTER(SkyParams)]),
+    "sailor_host_sky_face_matrices": (C.c_int, [C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "sailor_hip_allgather_u32": (C.c_int, [_P, _P, _P, _P, C.c_size_t]),
     "sailor_hip_exchange_workspace_size": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "sailor_hip_exchange_light_lists": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_size_t, _P, C.c_size_t]),

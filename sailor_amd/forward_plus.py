@@ -352,6 +352,59 @@ def raw_env_cubemap(ctx: "HipContext", equirect: torch.Tensor, size: int, levels
     return chain
 
 
+def cube_chain_floats(size: int, levels: int) -> int:
+    """float count of the level-major RGBA32F cube chain (sailor_hip_generate_mipmaps_cube)"""
+    return sum(6 * max(size >> l, 1) ** 2 * 4 for l in range(levels))
+
+
+def sky_fill(ctx: "HipContext", frame: UboFrameData, params, width: int = _lib.SKY_RESOLUTION, height: int | None = None) -> torch.Tensor:
+    """Sky.shader {FILL} (SkyNode.cpp:536-563): the atmosphere as seen through `frame` -> float32 [height, width, 4]"""
+    height = width if height is None else height
+    out = torch.empty((height, width, 4), dtype=torch.float32, device=ctx.device)
+    _lib.check(ctx._lib.sailor_hip_sky_fill(ctx.handle, C.byref(frame), C.byref(params), _ptr(out), width, height), "sailor_hip_sky_fill", ctx.handle)
+    return out
+
+
+def sky_sun(ctx: "HipContext", frame: UboFrameData, params, size: int = _lib.SKY_SUN_RESOLUTION, clouds: torch.Tensor | None = None) -> torch.Tensor:
+    """Sky.shader {SUN} (SkyNode.cpp:611-642): the sun disk -> float32 [size, size, 4]; `clouds` = None is the cleared clouds target"""
+    out = torch.empty((size, size, 4), dtype=torch.float32, device=ctx.device)
+    cw, ch = (0, 0) if clouds is None else (clouds.shape[1], clouds.shape[0])
+    _lib.check(ctx._lib.sailor_hip_sky_sun(ctx.handle, C.byref(frame), C.byref(params), _ptr(clouds), cw, ch, _ptr(out), size, size), "sailor_hip_sky_sun",
+               ctx.handle)
+    return out
+
+
+def sky_compose(ctx: "HipContext", frame: UboFrameData, params, sky: torch.Tensor, sun: torch.Tensor, width: int, height: int,
+                band: Band | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Sky.shader {COMPOSE} (SkyNode.cpp:644-680) over the rows of `band` (default: the whole frame) -> float32 [band rows, width, 4]"""
+    for t in (sky, sun):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 3 and t.shape[2] == 4, (t.dtype, tuple(t.shape))
+    band = band or host.band_whole_frame(width, height)
+    if out is None:
+        out = torch.empty((band.fbRowCount, width, 4), dtype=torch.float32, device=ctx.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (band.fbRowCount, width, 4), tuple(out.shape)
+    _lib.check(ctx._lib.sailor_hip_sky_compose(ctx.handle, C.byref(frame), C.byref(params), _ptr(sky), sky.shape[1], sky.shape[0], _ptr(sun), sun.shape[1],
+                                               sun.shape[0], _ptr(out), width, height, C.byref(band)), "sailor_hip_sky_compose", ctx.handle)
+    return out
+
+
+def sky_env_face(ctx: "HipContext", camera_position, params, chain: torch.Tensor, size: int, face: int) -> torch.Tensor:
+    """one face of g_skyCubemap's level 0 (SkyNode.cpp:764-797), written into the flat RGBA32F chain"""
+    cam = np.ascontiguousarray(camera_position, dtype=np.float32).reshape(-1)[:3].copy()
+    _lib.check(ctx._lib.sailor_hip_sky_env_face(ctx.handle, cam.ctypes.data_as(C.POINTER(C.c_float)), C.byref(params), _ptr(chain), size, face),
+               "sailor_hip_sky_env_face", ctx.handle)
+    return chain
+
+
+def sky_env_cubemap(ctx: "HipContext", camera_position, params, size: int = _lib.SKY_ENV_CUBEMAP_SIZE, levels: int = _lib.SKY_ENV_CUBEMAP_LEVELS) -> torch.Tensor:
+    """g_skyCubemap in one call (six faces + GenerateMipMaps, SkyNode.cpp:749-818) -> the flat RGBA32F chain"""
+    cam = np.ascontiguousarray(camera_position, dtype=np.float32).reshape(-1)[:3].copy()
+    chain = torch.zeros(cube_chain_floats(size, levels), dtype=torch.float32, device=ctx.device)
+    _lib.check(ctx._lib.sailor_hip_sky_env_cubemap(ctx.handle, cam.ctypes.data_as(C.POINTER(C.c_float)), C.byref(params), _ptr(chain), size, levels),
+               "sailor_hip_sky_env_cubemap", ctx.handle)
+    return chain
+
+
 def ecs_range_for_rank(n: int, rank: int, world: int):
     """(begin, end, words per rank) of rank's slice of an equal split of n entities in whole visibility words (sailor_hip_ecs_range_for_rank; pure host
     arithmetic, no device)"""

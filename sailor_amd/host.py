@@ -93,6 +93,30 @@ def hbao_shipped_extents(width: int, height: int):
     return (width // 2, width // 2), (width // 2, width // 2), (width, width), (width, width)
 
 
+def sky_params(**overrides) -> "_lib.SkyParams":
+    """SkyNode::SkyParams with the initialisers of SkyNode.h:50-67; `lightDirection` takes 3 or 4 floats (w = 0), the other members by name"""
+    p = _lib.SkyParams()
+    _lib.check(_lib.load().sailor_host_sky_params_default(C.byref(p)), "sailor_host_sky_params_default")
+    for name, value in overrides.items():
+        if name == "lightDirection":
+            v = [float(x) for x in value]
+            p.lightDirection[:] = (v + [0.0])[:4] if len(v) == 3 else v
+        elif name in ("scatteringSteps", "sunShaftsDistance"):
+            setattr(p, name, int(value))
+        elif name in dict(_lib.SkyParams._fields_):
+            setattr(p, name, float(value))
+        else:
+            raise ValueError(f"SkyParams has no member {name!r}")
+    return p
+
+
+def sky_face_matrices(face: int):
+    """SkyNode.cpp:487-508: (view, projection, invProjection) of cube face 0..5, column-major float32[16] each"""
+    v, p, ip = (np.empty(16, np.float32) for _ in range(3))
+    _lib.check(_lib.load().sailor_host_sky_face_matrices(face, _fp(v), _fp(p), _fp(ip)), "sailor_host_sky_face_matrices")
+    return v, p, ip
+
+
 def transform_matrix(position, rotation_xyzw, scale) -> np.ndarray:
     """Math/Transform.cpp:39-42; returns a column-major float32[16]."""
     trs = np.concatenate([_f32(position, 4), _f32(rotation_xyzw, 4), _f32(scale, 4)])

@@ -39,6 +39,7 @@ template class Sailor::Framegraph::TFrameGraphNode<DepthHighZNode>;
 template class Sailor::Framegraph::TFrameGraphNode<EyeAdaptationNode>;
 template class Sailor::Framegraph::TFrameGraphNode<PostProcessNode>;
 template class Sailor::Framegraph::TFrameGraphNode<BlitNode>;
+template class Sailor::Framegraph::TFrameGraphNode<SkyNode>;
 
 // ---- RHIFrameGraph ----------------------------------------------------------------------------------------------------------
 UboFrameData RHIFrameGraph::FillFrameData(RHICommandListPtr transferCmdList, RHISceneViewSnapshot& snapshot, float deltaTime, float worldTime) const
@@ -126,6 +127,14 @@ void EnvironmentNode::Process(RHIFrameGraphPtr frameGraph, RHICommandListPtr, RH
         if (!rawEnvCubemap || !rawEnvCubemap->m_bCubemap) { commands->EndDebugRegion(commandList); return; } // (:143-146)
         const int32_t EnvMapSize = rawEnvCubemap->GetExtent().x;
         const uint32_t EnvMapLevels = rawEnvCubemap->GetMipLevels();
+        if (!m_envMapTexture) // (:150-162) the cubes belong to the Sky node's parameters
+            if (auto pSkyNode = frameGraph->GetGraphNode("Sky").DynamicCast<SkyNode>()) {
+                int32_t key[3];
+                for (int k = 0; k < 3; k++) key[k] = (int32_t)(pSkyNode->GetSkyParams().lightDirection[k] * 10.0f); // SkyNode.h:85-88
+                if (m_bHasSkyKey && (key[0] != m_skyKey[0] || key[1] != m_skyKey[1] || key[2] != m_skyKey[2])) { m_envCubemap.Clear(); m_irradianceCubemap.Clear(); }
+                for (int k = 0; k < 3; k++) m_skyKey[k] = key[k];
+                m_bHasSkyKey = true;
+            }
         const bool bShouldUpdateEnvCubemap = !m_envCubemap, bShouldUpdateIrradianceCubemap = !m_irradianceCubemap; // (:162-163)
         if (!bShouldUpdateEnvCubemap && !bShouldUpdateIrradianceCubemap) { // (:165-173)
             frameGraph->SetSampler("g_envCubemap", m_envCubemap);
@@ -555,3 +564,146 @@ void BlitNode::Process(RHIFrameGraphPtr frameGraph, RHICommandListPtr, RHIComman
 }
 
 void BlitNode::Clear() {}
+
+// ---- SkyNode (FrameGraph/SkyNode.cpp:209-834) -------------------------------------------------------------------------------------------
+const char* SkyNode::m_name = "Sky";
+
+void SkyNode::Process(RHIFrameGraphPtr frameGraph, RHICommandListPtr transferCommandList, RHICommandListPtr commandList, const RHISceneViewSnapshot& sceneView)
+{
+    auto driver = Renderer::GetDriver();
+    auto commands = Renderer::GetDriverCommands();
+    commands->BeginDebugRegion(commandList, GetName()); // (:216)
+
+    if (!m_pSkyShader) { // (:220-232) one asset, five permutations
+        m_pSkyShader = driver->CreateShader("Shaders/Sky.shader", { "FILL" });
+        m_pSkyEnvShader = driver->CreateShader("Shaders/Sky.shader", {});
+        m_pSunShader = driver->CreateShader("Shaders/Sky.shader", { "SUN" });
+        m_pComposeShader = driver->CreateShader("Shaders/Sky.shader", { "COMPOSE" });
+        m_pCloudsShader = driver->CreateShader("Shaders/Sky.shader", { "CLOUDS" });
+    }
+    if (!m_pSunShaftsShader) m_pSunShaftsShader = driver->CreateShader("Shaders/SunShafts.shader"); // (:234-242)
+    if (!m_pBlitShader) m_pBlitShader = driver->CreateShader("Shaders/Blit.shader");                // (:244-252)
+    if (!m_pStarsShader) m_pStarsShader = driver->CreateShader("Shaders/Stars.shader");             // (:341-349)
+    // (:254-339 the CloudsMap texture and the two noise volumes belong to the cloud march: not created)
+
+    if (!m_pSkyTexture) m_pSkyTexture = driver->CreateRenderTarget({ (int32_t)SkyResolution, (int32_t)SkyResolution }, 1, EFormat::R32G32B32A32_SFLOAT); // (:351-363)
+    if (!m_pSunTexture) m_pSunTexture = driver->CreateRenderTarget({ (int32_t)SunResolution, (int32_t)SunResolution }, 1, EFormat::R32G32B32A32_SFLOAT); // (:365-377)
+    if (!m_pCloudsTexture) { // (:379-393)
+        const float size = std::min(frameGraph->GetViewport().x * CloudsResolutionFactor, frameGraph->GetViewport().y * CloudsResolutionFactor);
+        m_pCloudsTexture = driver->CreateRenderTarget({ std::max((int32_t)size, 1), std::max((int32_t)size, 1) }, 1, EFormat::R32G32B32A32_SFLOAT);
+    }
+    // (:405-417) the reference waits for all eight shaders and the star mesh; the four permutations this backend draws are what the node waits for here,
+    // the others stay "not ready" for good and their draws below are left out
+    if (!m_pSkyShader->IsReady() || !m_pSkyEnvShader->IsReady() || !m_pSunShader->IsReady() || !m_pComposeShader->IsReady() || !m_pSkyTexture || !m_pSunTexture ||
+        !m_pCloudsTexture) {
+        commands->EndDebugRegion(commandList);
+        return;
+    }
+
+    if (!m_pSkyMaterial) { // (:419-455)
+        m_pShaderBindings = driver->CreateShaderBindings();
+        driver->FillShadersLayout(m_pShaderBindings, { m_pSkyShader }, 1);
+        const size_t uniformsSize = std::max(sizeof(SkyParams), m_vectorParams.size() * sizeof(vec4));
+        driver->AddBufferToShaderBindings(m_pShaderBindings, "data", uniformsSize, 0, EShaderBindingType::UniformBuffer);
+        driver->AddSamplerToShaderBindings(m_pShaderBindings, "skySampler", m_pSkyTexture, 1);
+        driver->AddSamplerToShaderBindings(m_pShaderBindings, "sunSampler", m_pSunTexture, 2);
+        driver->AddSamplerToShaderBindings(m_pShaderBindings, "cloudsSampler", m_pCloudsTexture, 6);
+        if (auto linearDepth = GetRHIResource("linearDepth").DynamicCast<RHITexture>()) driver->AddSamplerToShaderBindings(m_pShaderBindings, "linearDepth", linearDepth, 9);
+        m_pSkyMaterial = driver->CreateMaterial(m_pSkyShader);
+        m_pSkyEnvMaterial = driver->CreateMaterial(m_pSkyEnvShader);
+        m_pSunMaterial = driver->CreateMaterial(m_pSunShader);
+        m_pComposeMaterial = driver->CreateMaterial(m_pComposeShader);
+        m_pCloudsMaterial = driver->CreateMaterial(m_pCloudsShader);
+        m_pSunShaftsMaterial = driver->CreateMaterial(m_pSunShaftsShader);
+    }
+    if (auto binding = m_pShaderBindings->Find("data")) // (:458-467) every frame
+        commands->UpdateShaderBinding(transferCommandList, binding, &m_skyParams, sizeof(SkyParams));
+    if (!m_pBlitCloudsMaterial) { // (:469-483)
+        m_pBlitCloudsBindings = driver->CreateShaderBindings();
+        driver->FillShadersLayout(m_pBlitCloudsBindings, { m_pBlitShader }, 1);
+        driver->AddSamplerToShaderBindings(m_pBlitCloudsBindings, "colorSampler", m_pCloudsTexture, 0);
+        m_pBlitCloudsMaterial = driver->CreateMaterial(m_pBlitShader);
+    }
+    if (!m_pEnvCubemapBindings[0]) { // (:485-515) the six faces' frame data, with the camera position of the frame that creates them
+        for (uint32_t face = 0; face < 6; face++) {
+            m_pEnvCubemapBindings[face] = driver->CreateShaderBindings();
+            driver->AddBufferToShaderBindings(m_pEnvCubemapBindings[face], "frameData", sizeof(UboFrameData), 0, EShaderBindingType::UniformBuffer);
+            UboFrameData frameData {};
+            sailor_host_sky_face_matrices((int32_t)face, frameData.view, frameData.projection, frameData.invProjection); // (:487-495, :504-507)
+            for (int k = 0; k < 3; k++) frameData.cameraPosition[k] = sceneView.m_camera.m_world[12 + k];                // (:503)
+            frameData.cameraPosition[3] = 1.0f;
+            frameData.viewportSize[0] = 128; frameData.viewportSize[1] = 128;                                            // (:508)
+            commands->UpdateShaderBinding(transferCommandList, m_pEnvCubemapBindings[face]->GetOrAddShaderBinding("frameData"), &frameData, sizeof(frameData));
+        }
+    }
+    if (!m_pStarsMaterial) m_pStarsMaterial = driver->CreateMaterial(m_pStarsShader); // (:517-522)
+
+    auto resolved = [&](const char* name) -> RHITexturePtr { // BaseFrameGraphNode::GetResolvedAttachment
+        if (auto t = GetRHIResource(name).DynamicCast<RHITexture>()) return t;
+        auto it = m_unresolvedResourceParams.find(name);
+        return it == m_unresolvedResourceParams.end() ? RHITexturePtr() : frameGraph->GetRenderTarget(it->second);
+    };
+    RHITexturePtr target = resolved("color"); // (:524)
+    if (!target) { commands->EndDebugRegion(commandList); return; }
+
+    auto fullScreenDraw = [&](const char* region, RHITexturePtr attachment, RHIMaterialPtr material, const TVector<RHIShaderBindingSetPtr>& sets) {
+        commands->BeginDebugRegion(commandList, region);
+        commands->ImageMemoryBarrier(commandList, attachment, EImageLayout::ColorAttachmentOptimal);
+        commands->BeginRenderPass(commandList, TVector<RHITexturePtr> { attachment }, RHITexturePtr());
+        commands->BindMaterial(commandList, material);
+        commands->BindShaderBindings(commandList, material, sets);
+        commands->DrawIndexed(commandList, 6, 1, 0, 0, 0); // the full-screen NDC quad
+        commands->EndRenderPass(commandList);
+        commands->EndDebugRegion(commandList);
+    };
+    fullScreenDraw("Sky", m_pSkyTexture, m_pSkyMaterial, { sceneView.m_frameBindings, m_pShaderBindings }); // (:536-563)
+    if (m_skyParams.cloudsDensity > 0.0f && m_pCloudsShader->IsReady()) { // (:565-603) never ready here: the else branch, whatever the parameter says
+        commands->PushConstants(commandList, m_pCloudsMaterial, sizeof(uint32_t), &m_ditherPatternIndex);
+        fullScreenDraw("Clouds", m_pCloudsTexture, m_pCloudsMaterial, { sceneView.m_frameBindings, m_pShaderBindings });
+    } else { // (:604-609)
+        commands->ImageMemoryBarrier(commandList, m_pCloudsTexture, EImageLayout::TransferDstOptimal);
+        commands->ClearImage(commandList, m_pCloudsTexture, 0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    fullScreenDraw("Sun", m_pSunTexture, m_pSunMaterial, { sceneView.m_frameBindings, m_pShaderBindings });     // (:611-642)
+    fullScreenDraw("Compose", target, m_pComposeMaterial, { sceneView.m_frameBindings, m_pShaderBindings });    // (:644-680)
+    // (:682-747) "Stars & Clouds": the star points, the alpha-blended clouds blit and the sun-shaft multiply -- no entry point, nothing recorded
+    if (m_pStarsShader->IsReady()) fullScreenDraw("Stars", target, m_pStarsMaterial, { sceneView.m_frameBindings, m_pShaderBindings });
+    if (m_pBlitShader->IsReady()) fullScreenDraw("Blit Clouds", target, m_pBlitCloudsMaterial, { sceneView.m_frameBindings, m_pBlitCloudsBindings });
+    if (m_pSunShaftsShader->IsReady()) fullScreenDraw("Sun Shafts", target, m_pSunShaftsMaterial, { sceneView.m_frameBindings, m_pShaderBindings });
+
+    if (m_bIsDirty) { // (:749-818)
+        RHICubemapPtr cubemap = frameGraph->GetSampler("g_skyCubemap");
+        if (cubemap && !cubemap->m_bCubemap) cubemap.Clear(); // DynamicCast<RHICubemap>
+        if (!cubemap) { // (:753-762)
+            cubemap = driver->CreateCubemap({ (int32_t)EnvCubemapSize, (int32_t)EnvCubemapSize }, 8, EFormat::R32G32B32A32_SFLOAT);
+            if (cubemap) {
+                commands->ImageMemoryBarrier(commandList, cubemap, EImageLayout::ShaderReadOnlyOptimal);
+                frameGraph->SetSampler("g_skyCubemap", cubemap);
+            }
+        }
+        if (cubemap) { // (:764-805)
+            const uint32_t face = m_updateEnvCubemapPattern;
+            if (face < 6)
+                fullScreenDraw("Generate Environment Map", cubemap->GetFace(face, 0), m_pSkyEnvMaterial, { m_pEnvCubemapBindings[face], m_pShaderBindings });
+            else { // 6 and 7 both (:798-802)
+                commands->ImageMemoryBarrier(commandList, cubemap, EImageLayout::TransferDstOptimal);
+                commands->GenerateMipMaps(commandList, cubemap);
+            }
+        }
+        if (m_updateEnvCubemapPattern == 7) { // (:807-816)
+            m_bIsDirty = false;
+            if (auto node = frameGraph->GetGraphNode("Environment").DynamicCast<EnvironmentNode>()) node->MarkDirty();
+        }
+        m_updateEnvCubemapPattern++;
+    }
+    commands->EndDebugRegion(commandList); // (:820)
+    m_ditherPatternIndex++;                // (:822)
+}
+
+void SkyNode::Clear() // (:825-834)
+{
+    m_pSkyTexture.Clear(); m_pSunTexture.Clear();
+    m_pSkyShader.Clear(); m_pSkyEnvShader.Clear();
+    m_pSkyMaterial.Clear(); m_pSkyEnvMaterial.Clear();
+    m_pShaderBindings.Clear();
+}

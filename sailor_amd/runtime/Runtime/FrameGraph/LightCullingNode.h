@@ -83,6 +83,10 @@ protected:
     RHI::RHITexturePtr m_brdfSampler;
     RHI::RHITexturePtr m_envMapTexture; // EnvironmentNode.h:43
     bool m_bIsDirty = false;
+    // EnvironmentNode.cpp:150-175 keeps the baked cubes in maps keyed by the Sky node's parameters (SkyParams::operator==: the light direction times ten,
+    // truncated).  One entry of that cache is kept here: a dirty mark under another key bakes again, under the same key it republishes the cubes.
+    bool m_bHasSkyKey = false;
+    int32_t m_skyKey[3] = { 0, 0, 0 };
 };
 
 // The Hi-Z pyramid builder: Runtime/FrameGraph/DepthHighZNode.h.  Resources: "src" = the (half-resolution) depth target, "dst" = the
@@ -150,6 +154,44 @@ public:
 
 protected:
     static const char* m_name;
+};
+
+// The atmosphere, the sun disk and g_skyCubemap: Runtime/FrameGraph/SkyNode.h.  Resources (DefaultRenderer.renderer:145-149): "color" = the Sky target,
+// "linearDepth".  Drawn: Sky.shader {FILL}, {SUN}, {COMPOSE} every frame and {} into one face of g_skyCubemap per frame while dirty.  Created and never
+// recorded (the backend has no entry point: IsReady() is false): Sky.shader {CLOUDS}, Stars.shader, SunShafts.shader and the alpha-blended Blit.shader
+// draw -- the node always takes the m_cloudsDensity == 0 branch (SkyNode.cpp:604-609) and has no star mesh, noise volumes or CloudsMap texture.
+class SkyNode : public TFrameGraphNode<SkyNode> {
+public:
+    static constexpr uint32_t EnvCubemapSize = 256u;      // SkyNode.h:13
+    static constexpr uint32_t SkyResolution = 256u;       // SkyNode.h:14
+    static constexpr uint32_t SunResolution = 32u;        // SkyNode.h:15
+    static constexpr float CloudsResolutionFactor = 0.5f; // SkyNode.h:16
+    using SkyParams = SailorSkyParams;                    // SkyNode.h:48-67 (member initialisers: sailor_host_sky_params_default)
+
+    SkyNode() { sailor_host_sky_params_default(&m_skyParams); }
+    static const char* GetName() { return m_name; }
+    void Process(RHIFrameGraphPtr frameGraph, RHI::RHICommandListPtr transferCommandList, RHI::RHICommandListPtr commandList,
+                 const RHI::RHISceneViewSnapshot& sceneView) override;
+    void Clear() override;
+
+    RHI::RHIShaderBindingSetPtr GetShaderBindings() { return m_pShaderBindings; }
+    void MarkDirty() { m_bIsDirty = true; m_updateEnvCubemapPattern = 0; } // SkyNode.h:103
+    const SkyParams& GetSkyParams() const { return m_skyParams; }           // SkyNode.h:105
+    SkyParams& GetSkyParams() { return m_skyParams; }                       // SkyNode.h:106
+    uint32_t GetUpdateEnvCubemapPattern() const { return m_updateEnvCubemapPattern; } // (not in the reference: read-back for the tests)
+    bool IsDirty() const { return m_bIsDirty; }
+
+protected:
+    static const char* m_name;
+    SkyParams m_skyParams {};
+    RHI::RHIShaderPtr m_pSunShader, m_pSkyShader, m_pSkyEnvShader, m_pStarsShader, m_pComposeShader, m_pCloudsShader, m_pSunShaftsShader, m_pBlitShader;
+    RHI::RHIMaterialPtr m_pStarsMaterial, m_pSkyMaterial, m_pSkyEnvMaterial, m_pSunMaterial, m_pComposeMaterial, m_pCloudsMaterial, m_pSunShaftsMaterial,
+        m_pBlitCloudsMaterial;
+    RHI::RHIShaderBindingSetPtr m_pShaderBindings, m_pBlitCloudsBindings, m_pEnvCubemapBindings[6];
+    RHI::RHITexturePtr m_pSkyTexture, m_pSunTexture, m_pCloudsTexture;
+    uint32_t m_ditherPatternIndex = 0;
+    uint32_t m_updateEnvCubemapPattern = 0; // SkyNode.h:173
+    bool m_bIsDirty = true;                 // SkyNode.h:174
 };
 
 } // namespace Sailor::Framegraph

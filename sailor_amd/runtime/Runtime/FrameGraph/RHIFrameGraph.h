@@ -14,6 +14,11 @@ class RHIFrameGraph {
 public:
     void AddNode(FrameGraphNodePtr node) { m_graph.push_back(node); }
     const std::vector<FrameGraphNodePtr>& GetGraph() const { return m_graph; }
+    FrameGraphNodePtr GetGraphNode(const std::string& tag) const // RHIFrameGraph.cpp GetGraphNode: the first node with that name
+    {
+        for (const auto& node : m_graph) if (node->GetDebugName() == tag) return node;
+        return FrameGraphNodePtr();
+    }
     void SetRenderTarget(const std::string& name, RHI::RHITexturePtr rt) { m_renderTargets[name] = rt; }
     RHI::RHITexturePtr GetRenderTarget(const std::string& name) const
     {

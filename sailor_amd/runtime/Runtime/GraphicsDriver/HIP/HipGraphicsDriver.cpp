@@ -85,10 +85,13 @@ RHIShaderPtr HipGraphicsDriver::CreateShader(const std::string& assetPath, const
     static const char* const routed[] = { "Shaders/ComputeLightCulling.shader", "Shaders/Standard.shader", "Shaders/ComputeMeshCulling.shader",
         "Shaders/ComputeDepthHighZ.shader", "Shaders/ComputeHistogram.shader", "Shaders/ComputeAverageLuminance.shader", "Shaders/ComputeBrdfLut.shader",
         "Shaders/ComputeIrradianceMap.shader", "Shaders/ComputeEnvMap_IBL.shader", "Shaders/ShadowCaster.shader", "Shaders/LinearizeDepth.shader",
-        "Shaders/Tonemapping.shader", "Shaders/Blur.shader", "Shaders/HBAO.shader", "Shaders/HBAO_Blur.shader" };
+        "Shaders/Tonemapping.shader", "Shaders/Blur.shader", "Shaders/HBAO.shader", "Shaders/HBAO_Blur.shader", "Shaders/Sky.shader" };
     auto shader = RHIShaderPtr::Make(assetPath, defines);
     shader->m_bIsReady = false;
     for (const char* name : routed) if (assetPath == name) shader->m_bIsReady = true;
+    // Sky.shader is routed by its define set: {FILL}, {}, {SUN}, {COMPOSE} have entry points, any other permutation ({CLOUDS}, ...) has none
+    if (assetPath == "Shaders/Sky.shader")
+        shader->m_bIsReady = defines.empty() || (defines.size() == 1 && (defines[0] == "FILL" || defines[0] == "SUN" || defines[0] == "COMPOSE"));
     return shader;
 }
 
@@ -123,6 +126,14 @@ RHITexturePtr RHI::RHITexture::GetMipLevel(uint32_t mipLevel) const
     return v;
 }
 
+RHITexturePtr RHI::RHITexture::GetFace(uint32_t face, uint32_t mipLevel) const
+{
+    auto v = GetMipLevel(mipLevel);
+    v->m_bCubemap = false; // one face is a plain image
+    v->m_viewFace = (int32_t)face;
+    return v;
+}
+
 RHITexturePtr HipGraphicsDriver::CreateRenderTarget(ivec2 extent, uint32_t mipLevels, EFormat format)
 {
     if (mipLevels <= 1) return CreateTexture(nullptr, 0, extent, format);
@@ -144,6 +155,7 @@ static void* texels_of(const RHITexturePtr& t)
     size_t texels = 0;
     for (uint32_t l = 0; l < t->m_viewLevel; l++)
         texels += (size_t)(p->m_bCubemap ? 6 : 1) * ((p->m_extent.x >> l) > 1 ? (p->m_extent.x >> l) : 1) * ((p->m_extent.y >> l) > 1 ? (p->m_extent.y >> l) : 1);
+    if (t->m_viewFace >= 0) texels += (size_t)t->m_viewFace * t->m_extent.x * t->m_extent.y;
     return base + texels * texel_size(p->m_format);
 }
 
@@ -344,16 +356,18 @@ void HipGraphicsDriver::EndDebugRegion(RHICommandListPtr cmdList)
 }
 void HipGraphicsDriver::ImageMemoryBarrier(RHICommandListPtr, RHITexturePtr, EImageLayout) {} // one in-order stream: nothing to do
 
-// The path's only ClearImage is EyeAdaptationNode's (EyeAdaptationNode.cpp:97): a one-channel fp32 target filled with clearColor.r
-void HipGraphicsDriver::ClearImage(RHICommandListPtr cmd, RHITexturePtr dst, float r, float, float, float)
+// The path's ClearImages: EyeAdaptationNode's (EyeAdaptationNode.cpp:97), a one-channel fp32 target filled with clearColor.r, and SkyNode's
+// (SkyNode.cpp:607), an RGBA target cleared to one value in all four channels
+void HipGraphicsDriver::ClearImage(RHICommandListPtr cmd, RHITexturePtr dst, float r, float g, float b, float a)
 {
     SailorHipContext* ctx = m_ctx;
-    cmd->m_hip.m_commands.push_back([this, ctx, dst, r]() {
-        if (!dst || !dst->m_buffer || dst->m_format != EFormat::R32_SFLOAT) return (int)SAILOR_HIP_ERR_UNSUPPORTED;
+    cmd->m_hip.m_commands.push_back([this, ctx, dst, r, g, b, a]() {
+        const bool uniformRgba = dst && dst->m_format == EFormat::R32G32B32A32_SFLOAT && r == g && g == b && b == a;
+        if (!dst || !dst->m_buffer || (dst->m_format != EFormat::R32_SFLOAT && !uniformRgba)) return (int)SAILOR_HIP_ERR_UNSUPPORTED;
         uint32_t bits;
         memcpy(&bits, &r, 4);
         BeforeBufferWrite(dst->m_buffer->m_hip.m_devicePtr);
-        return sailor_hip_buffer_fill_u32(ctx, dst->m_buffer->m_hip.m_devicePtr, 0, bits, (size_t)dst->GetExtent().x * dst->GetExtent().y);
+        return sailor_hip_buffer_fill_u32(ctx, dst->m_buffer->m_hip.m_devicePtr, 0, bits, (size_t)dst->GetExtent().x * dst->GetExtent().y * (uniformRgba ? 4 : 1));
     });
 }
 
@@ -370,7 +384,14 @@ void HipGraphicsDriver::SetMaterialParameter(RHICommandListPtr cmd, RHIShaderBin
         { "", "whitePoint", 0 }, { "", "exposure", 16 }, { "Shaders/Tonemapping.shader", "whitePoint", 0 }, { "Shaders/Tonemapping.shader", "exposure", 16 },
         { "Shaders/HBAO.shader", "occlusionRadius", 0 }, { "Shaders/HBAO.shader", "occlusionPower", 4 }, { "Shaders/HBAO.shader", "occlusionAttenuation", 8 },
         { "Shaders/HBAO.shader", "occlusionBias", 12 }, { "Shaders/HBAO.shader", "noiseScale", 16 },
-        { "Shaders/HBAO_Blur.shader", "sharpness", 0 }, { "Shaders/HBAO_Blur.shader", "distanceScale", 4 }, { "Shaders/HBAO_Blur.shader", "radius", 8 } };
+        { "Shaders/HBAO_Blur.shader", "sharpness", 0 }, { "Shaders/HBAO_Blur.shader", "distanceScale", 4 }, { "Shaders/HBAO_Blur.shader", "radius", 8 },
+        // Sky.shader:116-136 (SailorSkyParams): a vec4, then seventeen 4-byte scalars
+        { "Shaders/Sky.shader", "lightDirection", 0 }, { "Shaders/Sky.shader", "cloudsAttenuation1", 16 }, { "Shaders/Sky.shader", "cloudsAttenuation2", 20 },
+        { "Shaders/Sky.shader", "cloudsDensity", 24 }, { "Shaders/Sky.shader", "cloudsCoverage", 28 }, { "Shaders/Sky.shader", "phaseInfluence1", 32 },
+        { "Shaders/Sky.shader", "phaseInfluence2", 36 }, { "Shaders/Sky.shader", "eccentrisy1", 40 }, { "Shaders/Sky.shader", "eccentrisy2", 44 },
+        { "Shaders/Sky.shader", "fog", 48 }, { "Shaders/Sky.shader", "sunIntensity", 52 }, { "Shaders/Sky.shader", "ambient", 56 },
+        { "Shaders/Sky.shader", "scatteringSteps", 60 }, { "Shaders/Sky.shader", "scatteringDensity", 64 }, { "Shaders/Sky.shader", "scatteringIntensity", 68 },
+        { "Shaders/Sky.shader", "scatteringPhase", 72 }, { "Shaders/Sky.shader", "sunShaftsIntensity", 76 }, { "Shaders/Sky.shader", "sunShaftsDistance", 80 } };
     const std::string layout = bindings ? bindings->m_layoutShader : std::string();
     size_t offset = (size_t)-1;
     if (binding == "data")
@@ -768,7 +789,10 @@ void HipGraphicsDriver::DrawIndexed(RHICommandListPtr cmd, uint32_t indexCount, 
     const uint32_t tonemapFlags = !shader ? 0u : (shader->HasDefine("ACES") ? SAILOR_TONEMAP_ACES : 0u) | (shader->HasDefine("UNCHARTED2") ? SAILOR_TONEMAP_UNCHARTED2 : 0u) |
                                                  (shader->HasDefine("LUMINANCE") ? SAILOR_TONEMAP_LUMINANCE : 0u);
     const bool evsm = shader && shader->HasDefine("EVSM"), vertical = shader && shader->HasDefine("VERTICAL"), horizontal = shader && shader->HasDefine("HORIZONTAL");
-    cmd->m_hip.m_commands.push_back([this, name, bindings, target, fullScreenQuad, evsm, vertical, horizontal, tonemapFlags]() {
+    // Sky.shader's permutation: 0 {FILL}, 1 {}, 2 {SUN}, 3 {COMPOSE}, -1 anything else (CreateShader left those "not ready")
+    const int sky = (!shader || !shader->IsReady()) ? -1 : (shader->m_defines.empty() ? 1 : (shader->HasDefine("FILL") ? 0 : (shader->HasDefine("SUN") ? 2 : 3)));
+    cmd->m_hip.m_commands.push_back([this, name, bindings, target, fullScreenQuad, evsm, vertical, horizontal, tonemapFlags, sky]() {
+        if (fullScreenQuad && name == "Shaders/Sky.shader" && sky >= 0) return RecordSky(bindings, target, sky);
         if (fullScreenQuad && name == "Shaders/LinearizeDepth.shader") return RecordLinearizeDepth(bindings, target);
         if (fullScreenQuad && name == "Shaders/Tonemapping.shader") return RecordTonemap(bindings, target, tonemapFlags);
         if (fullScreenQuad && name == "Shaders/Blur.shader" && evsm && vertical != horizontal) return RecordEvsmBlur(bindings, target, vertical);
@@ -900,6 +924,40 @@ int HipGraphicsDriver::RecordHbaoBlur(const TVector<RHIShaderBindingSetPtr>& bin
     BeforeBufferWrite(target->m_buffer->m_hip.m_devicePtr);
     return sailor_hip_hbao_blur_pass(m_ctx, (const float*)texels_of(ao), ao->GetExtent().x, ao->GetExtent().y, (const float*)texels_of(depth), depth->GetExtent().x,
                                      depth->GetExtent().y, &params, (float*)texels_of(target), target->GetExtent().x, target->GetExtent().y, vertical ? 1 : 0);
+}
+
+// ---- SkyNode (FrameGraph/SkyNode.cpp:536-563, :611-680, :764-797) --------------------------------------------------------------------------
+int HipGraphicsDriver::RecordSky(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& target, int permutation)
+{
+    // { sceneView.m_frameBindings | m_pEnvCubemapBindings[face], m_pShaderBindings }; Sky.shader:104-136 (set 0 frame, set 1 binding 0 `data`), :138-153
+    // (1 `skySampler`, 2 `sunSampler`, 6 `cloudsSampler`)
+    if (bindings.size() != 2 || !target || !target->m_buffer || target->m_format != EFormat::R32G32B32A32_SFLOAT) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    auto frameB = bindings[0]->Find("frameData");
+    auto dataB = bindings[1]->Find("data");
+    if (!frameB || frameB->m_hostCopy.size() < sizeof(SailorUboFrameData) || !dataB || dataB->m_hostCopy.size() < sizeof(SailorSkyParams)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    SailorUboFrameData frame;
+    memcpy(&frame, frameB->m_hostCopy.data(), sizeof frame);
+    SailorSkyParams params;
+    memcpy(&params, dataB->m_hostCopy.data(), sizeof params);
+    auto rgba_of = [&](const char* name) -> RHITexturePtr {
+        auto b = bindings[1]->Find(name);
+        if (!b || b->m_textures.empty() || !b->m_textures[0] || !b->m_textures[0]->m_buffer || b->m_textures[0]->m_format != EFormat::R32G32B32A32_SFLOAT) return RHITexturePtr();
+        return b->m_textures[0];
+    };
+    BeforeBufferWrite(target->m_buffer->m_hip.m_devicePtr);
+    if (permutation == 0) return sailor_hip_sky_fill(m_ctx, &frame, &params, (float*)texels_of(target), target->GetExtent().x, target->GetExtent().y);
+    if (permutation == 1) { // one face of a cube: the attachment is cubemap->GetFace(face, 0), whose matrices the node wrote with sailor_host_sky_face_matrices
+        if (target->m_viewFace < 0 || target->m_viewLevel != 0 || !target->m_parent || target->GetExtent().x != target->GetExtent().y) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+        return sailor_hip_sky_env_face(m_ctx, frame.cameraPosition, &params, (float*)target->m_buffer->m_hip.m_devicePtr, target->GetExtent().x, target->m_viewFace);
+    }
+    if (permutation == 2) // `cloudsSampler` is the node's cleared clouds target (SkyNode.cpp:604-609): alpha 0 everywhere = no plane
+        return sailor_hip_sky_sun(m_ctx, &frame, &params, nullptr, 0, 0, (float*)texels_of(target), target->GetExtent().x, target->GetExtent().y);
+    auto sky = rgba_of("skySampler"), sun = rgba_of("sunSampler");
+    if (!sky || !sun) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    SailorBand whole;
+    if (sailor_hip_band_whole_frame(target->GetExtent().x, target->GetExtent().y, &whole) != SAILOR_HIP_OK) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    return sailor_hip_sky_compose(m_ctx, &frame, &params, (const float*)texels_of(sky), sky->GetExtent().x, sky->GetExtent().y, (const float*)texels_of(sun),
+                                  sun->GetExtent().x, sun->GetExtent().y, (float*)texels_of(target), target->GetExtent().x, target->GetExtent().y, &whole);
 }
 
 int HipGraphicsDriver::RecordEvsmBlur(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& target, bool vertical)

@@ -18,6 +18,9 @@
 //   "Shaders/Blur.shader" {EVSM, HORIZONTAL | VERTICAL} -> sailor_hip_evsm_blur_pass (binding contract: Blur.shader:53-61)
 //   "Shaders/HBAO.shader"                -> sailor_hip_hbao              (binding contract: HBAO.shader:50-60)
 //   "Shaders/HBAO_Blur.shader" {VERTICAL | HORIZONTAL, exactly one} -> sailor_hip_hbao_blur_pass (binding contract: HBAO_Blur.shader:54-62)
+//   "Shaders/Sky.shader" by define set: {FILL} -> sailor_hip_sky_fill, {} (into a cube face view) -> sailor_hip_sky_env_face, {SUN} -> sailor_hip_sky_sun,
+//                                           {COMPOSE} -> sailor_hip_sky_compose (binding contract: Sky.shader:104-153); {CLOUDS} and every other permutation,
+//                                           "Shaders/Stars.shader", "Shaders/SunShafts.shader" and "Shaders/Blit.shader" are created "not ready" and never drawn
 // a scaled one-channel BlitImage with Nearest filtration -> sailor_hip_blit_nearest
 // and the depth-only instanced draws of the shadow passes (material of)
 //   "Shaders/ShadowCaster.shader" [EVSM]  -> sailor_hip_raster_depth into the pass' depth attachment, and at EndRenderPass sailor_hip_shadow_resolve
@@ -119,6 +122,7 @@ private:
     int RecordEvsmBlur(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target, bool vertical);
     int RecordHbao(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target);
     int RecordHbaoBlur(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target, bool vertical);
+    int RecordSky(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target, int permutation);
 
     SailorHipContext* m_ctx = nullptr;              // == m_ctxOwner.get(): what the C-ABI calls take
     std::shared_ptr<SailorHipContext> m_ctxOwner;   // destroyed with the last buffer that still refers to it

@@ -89,6 +89,7 @@ public:
     // a mip-level view of a cubemap (RHI/Cubemap.h:24 GetMipLevel): shares m_buffer with its parent
     TRefPtr<RHITexture> m_parent;
     uint32_t m_viewLevel = 0;
+    int32_t m_viewFace = -1;  // >= 0: one face of that level (RHI/Cubemap.h GetFace(face, mipLevel), the attachment SkyNode.cpp:771 renders into)
     // HIP backend, EyeAdaptationNode's 1 x 1 average-luminance target only: the node state (include/sailor_hip.h sailor_hip_eye_adaptation_state_size)
     // whose luminance word m_buffer is a view of -- the `histogram` SSBO the target is bound beside (EyeAdaptationNode.cpp:102-108)
     RHIBufferPtr m_hipEyeAdaptationState;
@@ -98,6 +99,7 @@ public:
     ivec2 GetExtent() const { return m_extent; }
     uint32_t GetMipLevels() const { return m_mipLevels; }
     TRefPtr<RHITexture> GetMipLevel(uint32_t mipLevel) const;
+    TRefPtr<RHITexture> GetFace(uint32_t face, uint32_t mipLevel) const;
 };
 using RHITexturePtr = TRefPtr<RHITexture>;
 using RHICubemapPtr = RHITexturePtr; // RHI/Cubemap.h:15: class RHICubemap : public RHITexture

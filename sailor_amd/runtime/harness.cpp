@@ -404,6 +404,28 @@ RT_API int sailor_rt_set_sky_cubemap(SailorRuntime* rt, void* cubeChain, int siz
     return 0;
 }
 
+// The Sky node of the loaded graph: replace its parameters (SkyNode::GetSkyParams) and, with markDirty != 0, restart its cube bake (SkyNode::MarkDirty)
+static SkyNode* sky_node(SailorRuntime* rt) { return rt ? static_cast<SkyNode*>(rt->graph.GetGraphNode("Sky").DynamicCast<SkyNode>().GetRawPtr()) : nullptr; }
+
+RT_API int sailor_rt_sky_set_params(SailorRuntime* rt, const SailorSkyParams* params, int markDirty)
+{
+    auto* sky = sky_node(rt);
+    if (!sky || !params) return -1;
+    sky->GetSkyParams() = *params;
+    if (markDirty) sky->MarkDirty();
+    return 0;
+}
+
+// m_updateEnvCubemapPattern and m_bIsDirty of the Sky node (SkyNode.h:173-174)
+RT_API int sailor_rt_sky_state(SailorRuntime* rt, int* outPattern, int* outDirty)
+{
+    auto* sky = sky_node(rt);
+    if (!sky) return -1;
+    if (outPattern) *outPattern = (int)sky->GetUpdateEnvCubemapPattern();
+    if (outDirty) *outDirty = sky->IsDirty() ? 1 : 0;
+    return 0;
+}
+
 // The other source of the raw environment: an equirect panorama (the node's "EnvironmentMap" texture, EnvironmentNode.cpp:100-138).  The harness
 // hands over the loaded RGBA32F texture; the node converts it to a 512 x 512 x 6 cube with 10 mips and bakes from that.
 RT_API int sailor_rt_set_environment_map(SailorRuntime* rt, void* equirect, int width, int height, int repeat, int irradianceSize)

@@ -45,6 +45,8 @@ def load() -> C.CDLL:
         rt.sailor_rt_set_ibl.argtypes = [P, P, C.c_int, P, C.c_int, C.c_int, P, C.c_int, C.c_int, P, C.c_int, C.c_int]
         rt.sailor_rt_blur_shadow_map.argtypes = [P, P, P, C.c_int, C.c_float, C.c_float]
         rt.sailor_rt_set_sky_cubemap.argtypes = [P, P, C.c_int, C.c_int, C.c_int, P, C.c_int, C.c_int]
+        rt.sailor_rt_sky_set_params.argtypes = [P, P, C.c_int]
+        rt.sailor_rt_sky_state.argtypes = [P, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         rt.sailor_rt_set_environment_map.argtypes = [P, P, C.c_int, C.c_int, C.c_int, C.c_int]
         rt.sailor_rt_sampler.restype = P
         rt.sailor_rt_sampler.argtypes = [P, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -173,6 +175,17 @@ class Runtime:
         """publish the raw environment cube (flat RGBA32F mip chain, device tensor) as "g_skyCubemap" and mark the Environment node dirty"""
         return self.rt.sailor_rt_set_sky_cubemap(self.h, chain.data_ptr(), size, levels, irradiance_size, ao.data_ptr() if ao is not None else None,
                                                  ao.shape[1] if ao is not None else 0, ao.shape[0] if ao is not None else 0)
+
+    def sky_set_params(self, params, mark_dirty: bool = False) -> int:
+        """replace the Sky node's SkyParams (a _lib.SkyParams); mark_dirty restarts its time-sliced g_skyCubemap bake (SkyNode::MarkDirty)"""
+        return self.rt.sailor_rt_sky_set_params(self.h, C.byref(params), 1 if mark_dirty else 0)
+
+    def sky_state(self):
+        """(m_updateEnvCubemapPattern, m_bIsDirty) of the Sky node; raises if the graph has none"""
+        pattern, dirty = C.c_int(0), C.c_int(0)
+        if self.rt.sailor_rt_sky_state(self.h, C.byref(pattern), C.byref(dirty)) != 0:
+            raise ValueError("the graph has no Sky node")
+        return pattern.value, dirty.value
 
     def set_environment_map(self, equirect, repeat=True, irradiance_size=0):
         """hand the Environment node its "EnvironmentMap" panorama (float32 [H, W, 4] device tensor): it converts it to the raw 512 x 512 x 6 cube"""
