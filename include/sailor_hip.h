@@ -827,6 +827,41 @@ SAILOR_HIP_API int sailor_hip_sky_compose(SailorHipContext* ctx, const SailorUbo
 SAILOR_HIP_API int sailor_hip_sky_env_cubemap(SailorHipContext* ctx, const float* cameraPosition3, const SailorSkyParams* params,
                                               float* dCube, int32_t size, int32_t levels);
 
+/* ---- Bloom (round 9): the Bloom node, FrameGraph/BloomNode.cpp:21-144 -- the mip pyramid over `Main`, rewritten in place ----------------------
+ * tests/golden/DefaultRenderer.renderer:296-304.  `Main` is a level-major chain of RGBA32F planes (level l = max(1, width >> l) x max(1, height >> l),
+ * the layout HipGraphicsDriver::CreateRenderTarget allocates; the reference's levels are rgba16f -- nothing is rounded through half here).
+ * The kernels restate ComputeBloomDownscale.shader:72-127 and ComputeBloomUpscale.shader:44-95 one IEEE operation at a time, their per-group fp32
+ * source-texel arithmetic included (sailor_amd/csrc/bloom.hip lists the decisions); tests/bloom_ref.py is the NumPy restatement they equal bit for bit.
+ * All of them record only (no allocation, no synchronisation, capturable).  Planes are 16-byte aligned. */
+
+/* The node's parameters (DefaultRenderer.renderer:298-302: the .x of its four vec4): 16 bytes */
+typedef struct SailorBloomParams {
+    float threshold;
+    float knee;
+    float bloomIntensity;
+    float dirtIntensity;
+} SailorBloomParams;
+
+/* Texels of the first `levels` levels of a width x height mip chain = the texel offset of level `levels` (0 for levels == 0 and for a bad argument) */
+SAILOR_HIP_API size_t sailor_hip_mip_chain_texels(int32_t width, int32_t height, int32_t levels);
+/* Replaces: one Dispatch of the downscale loop (BloomNode.cpp:110-115), ComputeBloomDownscale.shader:72-127: the 13-tap Karis-weighted filter of
+ * level i into level i + 1, with quadratic_threshold (:21-35) when useThreshold is set (the node: i == 0 only, :101).
+ *   threshold4 : host, the push constant u_threshold as the node packs it (sailor_host_bloom_push_constants)
+ *   dst extents must be max(1, src >> 1); dSrc == dDst is refused */
+SAILOR_HIP_API int sailor_hip_bloom_downscale(SailorHipContext* ctx, const float* dSrc, int32_t srcWidth, int32_t srcHeight, float* dDst, int32_t dstWidth,
+                                              int32_t dstHeight, const float* threshold4, int32_t useThreshold);
+/* Replaces: one Dispatch of the upscale loop (BloomNode.cpp:135-140), ComputeBloomUpscale.shader:44-95: the 3 x 3 tent of level mipLevel added to level
+ * mipLevel - 1, which is read, modified and written; at mipLevel == 1 the lens-dirt term (:88-92) is added as well.
+ *   dDirt : `u_dirt_texture` as decoded linear RGBA32F texels (bilinear, Repeat).  NULL = no dirt term: an extension for hosts without the asset.
+ *   src extents must be max(1, dst >> 1); dSrc == dDst is refused */
+SAILOR_HIP_API int sailor_hip_bloom_upscale(SailorHipContext* ctx, const float* dSrc, int32_t srcWidth, int32_t srcHeight, float* dDst, int32_t dstWidth,
+                                            int32_t dstHeight, int32_t mipLevel, float bloomIntensity, float dirtIntensity, const float* dDirt, int32_t dirtWidth,
+                                            int32_t dirtHeight);
+/* Replaces: the GPU work of BloomNode::Process (BloomNode.cpp:95-141): levels - 1 downscales (threshold on the first), then levels - 1 upscales from
+ * the smallest level up, over the chain whose level 0 is width x height.  levels < 2 is refused; every argument is checked before the first launch. */
+SAILOR_HIP_API int sailor_hip_bloom(SailorHipContext* ctx, float* dChain, int32_t width, int32_t height, int32_t levels, const SailorBloomParams* params,
+                                    const float* dDirt, int32_t dirtWidth, int32_t dirtHeight);
+
 /* ---- RCCL exchange for split frames (only when the frame is split AND a consumer needs the global list) ----
  * `comm` is an ncclComm_t created by the host.  Collective 1: all-gather of one uint32 (band total) per rank.
  * Collective 2: all-gather of the padded band index segments (each rank contributes `segmentCapacity` uints). */
@@ -909,6 +944,10 @@ SAILOR_HIP_API int sailor_host_sky_params_default(SailorSkyParams* outParams);
 /* FrameGraph/SkyNode.cpp:487-495: the view matrix of cube face 0..5 (glm::rotate about Math::vec3_Up / vec3_Right), PerspectiveRH(radians(90), 1,
  * 0.1, 1000) and its inverse, as the node writes them into the faces' frame data (:502-508) */
 SAILOR_HIP_API int sailor_host_sky_face_matrices(int32_t face, float* outView16, float* outProjection16, float* outInvProjection16);
+
+/* FrameGraph/BloomNode.cpp:89-93: PushConstantsDownscale::m_threshold = (threshold, threshold - knee, 2 knee, 0.25 knee) -- as the node writes it: the
+ * shader's comment expects knee * 0.25 to be a quotient's denominator; restated, not repaired */
+SAILOR_HIP_API int sailor_host_bloom_push_constants(float threshold, float knee, float* outThreshold4);
 
 /* FrameGraph/EyeAdaptationNode.cpp:154-170: the push constants of the node's two Dispatches for a width x height HDR target */
 SAILOR_HIP_API int sailor_host_eye_adaptation_constants(int32_t width, int32_t height, float deltaTime, SailorEyeAdaptationConstants* outConstants);

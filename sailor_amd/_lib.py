@@ -138,6 +138,14 @@ class SkyParams(C.Structure):  # include/sailor_hip.h SailorSkyParams (Sky.shade
 SKY_RESOLUTION, SKY_SUN_RESOLUTION, SKY_ENV_CUBEMAP_SIZE, SKY_ENV_CUBEMAP_LEVELS = 256, 32, 256, 8  # SkyNode.h:13-15, SkyNode.cpp:755
 
 
+class BloomParams(C.Structure):  # include/sailor_hip.h SailorBloomParams; defaults = DefaultRenderer.renderer:298-302
+    _fields_ = [("threshold", C.c_float), ("knee", C.c_float), ("bloomIntensity", C.c_float), ("dirtIntensity", C.c_float)]
+
+
+BLOOM_SHIPPED = dict(threshold=3.0, knee=0.2, bloomIntensity=1.3, dirtIntensity=5.0)
+BLOOM_SHIPPED_LEVELS = 8  # DefaultRenderer.renderer:24-31: Main, bGenerateMips, maxMipLevel 8
+
+
 class HiZDesc(C.Structure):
     _fields_ = [("pyramid", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("levels", C.c_int32)]
 
@@ -254,6 +262,11 @@ SIGNATURES = {
     "sailor_hip_sky_env_cubemap": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(SkyParams), _P, C.c_int32, C.c_int32]),
     "sailor_host_sky_params_default": (C.c_int, [C.POINTER(SkyParams)]),
     "sailor_host_sky_face_matrices": (C.c_int, [C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "sailor_hip_mip_chain_texels": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "sailor_hip_bloom_downscale": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int32]),
+    "sailor_hip_bloom_upscale": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, C.c_int32, C.c_int32]),
+    "sailor_hip_bloom": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(BloomParams), _P, C.c_int32, C.c_int32]),
+    "sailor_host_bloom_push_constants": (C.c_int, [C.c_float, C.c_float, C.POINTER(C.c_float)]),
     "sailor_hip_allgather_u32": (C.c_int, [_P, _P, _P, _P, C.c_size_t]),
     "sailor_hip_exchange_workspace_size": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "sailor_hip_exchange_light_lists": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_size_t, _P, C.c_size_t]),

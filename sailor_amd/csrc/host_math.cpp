@@ -348,6 +348,17 @@ int sailor_host_eye_adaptation_constants(int32_t width, int32_t height, float de
     return SAILOR_HIP_OK;
 }
 
+// ---- FrameGraph/BloomNode.cpp:89-93: the downscale's u_threshold ----
+int sailor_host_bloom_push_constants(float threshold, float knee, float* outThreshold4)
+{
+    if (!outThreshold4) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    outThreshold4[0] = threshold;
+    outThreshold4[1] = threshold - knee;
+    outThreshold4[2] = 2.0f * knee;
+    outThreshold4[3] = 0.25f * knee;
+    return SAILOR_HIP_OK;
+}
+
 // ---- Math/Bounds.cpp:211-243: the scalar sphere tests; their only caller is LightingECS::GetLightsInFrustum (ContainsSphere, :237) ----
 int sailor_host_overlaps_sphere(const float* planes24, const float* sphere4)
 {

@@ -405,6 +405,57 @@ def sky_env_cubemap(ctx: "HipContext", camera_position, params, size: int = _lib
     return chain
 
 
+class Bloom:
+    """The Bloom node over a `Main` mip chain (BloomNode.cpp:21-144).  Owns nothing but the parameters: the caller hands in the flat level-major RGBA32F
+    chain (host.mip_chain_texels(width, height, levels) * 4 floats, level 0 = the lit frame) and, optionally, the decoded lens-dirt texels [H, W, 4]."""
+
+    def __init__(self, ctx: "HipContext", width: int, height: int, levels: int = _lib.BLOOM_SHIPPED_LEVELS, params=None, dirt: torch.Tensor | None = None):
+        self.ctx, self.width, self.height, self.levels = ctx, width, height, levels
+        self.params = params if params is not None else host.bloom_params()
+        if dirt is not None:
+            assert dirt.dtype == torch.float32 and dirt.is_contiguous() and dirt.dim() == 3 and dirt.shape[2] == 4, (dirt.dtype, tuple(dirt.shape))
+        self.dirt = dirt
+        self.extents = host.mip_chain_extents(width, height, levels)
+        self.offsets = [host.mip_chain_texels(width, height, l) * 4 for l in range(levels + 1)]  # in floats
+
+    def chain_floats(self) -> int:
+        return self.offsets[-1]
+
+    def level(self, chain: torch.Tensor, l: int) -> torch.Tensor:
+        """level l of the chain as a [h, w, 4] view"""
+        w, h = self.extents[l]
+        return chain[self.offsets[l]:self.offsets[l + 1]].view(h, w, 4)
+
+    def _check(self, chain: torch.Tensor):
+        assert chain.dtype == torch.float32 and chain.is_contiguous() and chain.numel() == self.chain_floats(), (chain.dtype, chain.numel(), self.chain_floats())
+
+    def _dirt_args(self):
+        return (_ptr(self.dirt), self.dirt.shape[1], self.dirt.shape[0]) if self.dirt is not None else (None, 0, 0)
+
+    def downscale(self, chain: torch.Tensor, i: int) -> None:
+        """one Dispatch of the downscale loop: level i -> i + 1 (threshold on for i == 0)"""
+        self._check(chain)
+        (sw, sh), (dw, dh) = self.extents[i], self.extents[i + 1]
+        t = host.bloom_push_constants(self.params.threshold, self.params.knee)
+        _lib.check(self.ctx._lib.sailor_hip_bloom_downscale(self.ctx.handle, _ptr(self.level(chain, i)), sw, sh, _ptr(self.level(chain, i + 1)), dw, dh,
+                                                            t.ctypes.data_as(C.POINTER(C.c_float)), 1 if i == 0 else 0), "sailor_hip_bloom_downscale", self.ctx.handle)
+
+    def upscale(self, chain: torch.Tensor, i: int) -> None:
+        """one Dispatch of the upscale loop: level i added to level i - 1"""
+        self._check(chain)
+        (sw, sh), (dw, dh) = self.extents[i], self.extents[i - 1]
+        _lib.check(self.ctx._lib.sailor_hip_bloom_upscale(self.ctx.handle, _ptr(self.level(chain, i)), sw, sh, _ptr(self.level(chain, i - 1)), dw, dh, i,
+                                                          self.params.bloomIntensity, self.params.dirtIntensity, *self._dirt_args()),
+                   "sailor_hip_bloom_upscale", self.ctx.handle)
+
+    def run(self, chain: torch.Tensor) -> torch.Tensor:
+        """the node's whole Process, in place; records only"""
+        self._check(chain)
+        _lib.check(self.ctx._lib.sailor_hip_bloom(self.ctx.handle, _ptr(chain), self.width, self.height, self.levels, C.byref(self.params), *self._dirt_args()),
+                   "sailor_hip_bloom", self.ctx.handle)
+        return chain
+
+
 def ecs_range_for_rank(n: int, rank: int, world: int):
     """(begin, end, words per rank) of rank's slice of an equal split of n entities in whole visibility words (sailor_hip_ecs_range_for_rank; pure host
     arithmetic, no device)"""

@@ -93,6 +93,30 @@ def hbao_shipped_extents(width: int, height: int):
     return (width // 2, width // 2), (width // 2, width // 2), (width, width), (width, width)
 
 
+def bloom_params(**values) -> "_lib.BloomParams":
+    """The Bloom node's four parameters; unnamed members keep the shipped values (DefaultRenderer.renderer:298-302)"""
+    v = dict(_lib.BLOOM_SHIPPED)
+    v.update(values)
+    return _lib.BloomParams(**{k: float(x) for k, x in v.items()})
+
+
+def bloom_push_constants(threshold: float, knee: float) -> np.ndarray:
+    """BloomNode.cpp:89-93: u_threshold = (t, t - knee, 2 knee, 0.25 knee) as float32[4]"""
+    out = np.empty(4, np.float32)
+    _lib.check(_lib.load().sailor_host_bloom_push_constants(threshold, knee, _fp(out)), "sailor_host_bloom_push_constants")
+    return out
+
+
+def mip_chain_extents(width: int, height: int, levels: int):
+    """[(width, height)] of the levels of a mip chain: max(1, dim >> level)"""
+    return [(max(1, width >> l), max(1, height >> l)) for l in range(levels)]
+
+
+def mip_chain_texels(width: int, height: int, levels: int) -> int:
+    """texels of the first `levels` levels of a level-major chain = the texel offset of level `levels` (sailor_hip_mip_chain_texels)"""
+    return int(_lib.load().sailor_hip_mip_chain_texels(width, height, levels))
+
+
 def sky_params(**overrides) -> "_lib.SkyParams":
     """SkyNode::SkyParams with the initialisers of SkyNode.h:50-67; `lightDirection` takes 3 or 4 floats (w = 0), the other members by name"""
     p = _lib.SkyParams()

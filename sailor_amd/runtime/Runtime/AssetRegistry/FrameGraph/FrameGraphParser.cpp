@@ -214,6 +214,7 @@ FrameGraphBuildReport FrameGraphImporter::BuildFrameGraph(const FrameGraphAsset&
     for (const auto& v : asset.m_values) graph.SetValue(v.first, v.second); // (:128-131)
     for (const auto& n : asset.m_nodes) { // (:151-199)
         auto pNewNode = FrameGraphBuilder::CreateNode(n.m_name);
+        if (!pNewNode && graph.IsNodeEnabled(n.m_name)) pNewNode = FrameGraphBuilder::CreateOptInNode(n.m_name); // this graph opted in (FrameGraphNode.h)
         if (!pNewNode) { // "FrameGraph Node %s is not implemented!" (:155-159)
             report.m_nodesNotImplemented++;
             report.m_notImplemented.push_back(n.m_name);

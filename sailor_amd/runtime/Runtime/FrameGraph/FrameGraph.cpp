@@ -30,6 +30,12 @@ FrameGraphNodePtr FrameGraphBuilder::CreateNode(const std::string& nodeName)
 
 bool FrameGraphBuilder::IsRegistered(const std::string& nodeName) { return Registry().count(nodeName) != 0; }
 
+FrameGraphNodePtr FrameGraphBuilder::CreateOptInNode(const std::string& nodeName)
+{
+    if (nodeName == BloomNode::GetName()) return FrameGraphNodePtr(new BloomNode());
+    return FrameGraphNodePtr();
+}
+
 // force the registration objects of the path's nodes into the library
 template class Sailor::Framegraph::TFrameGraphNode<LightCullingNode>;
 template class Sailor::Framegraph::TFrameGraphNode<RenderSceneNode>;
@@ -707,3 +713,81 @@ void SkyNode::Clear() // (:825-834)
     m_pSkyMaterial.Clear(); m_pSkyEnvMaterial.Clear();
     m_pShaderBindings.Clear();
 }
+
+// ---- BloomNode (FrameGraph/BloomNode.cpp:17-148) -------------------------------------------------------------------------------------------
+const char* BloomNode::m_name = "Bloom";
+
+void BloomNode::Process(RHIFrameGraphPtr frameGraph, RHICommandListPtr, RHICommandListPtr commandList, const RHISceneViewSnapshot&)
+{
+    auto driver = Renderer::GetDriver();
+    auto commands = Renderer::GetDriverCommands();
+    commands->BeginDebugRegion(commandList, GetName()); // (:28)
+
+    RHITexturePtr bloomRenderTarget = GetRHIResource("bloom").DynamicCast<RHITexture>(); // GetResolvedAttachment("bloom") (:30)
+    if (!bloomRenderTarget) {
+        auto it = m_unresolvedResourceParams.find("bloom");
+        if (it != m_unresolvedResourceParams.end()) bloomRenderTarget = frameGraph->GetRenderTarget(it->second);
+    }
+    if (!bloomRenderTarget) { commands->EndDebugRegion(commandList); return; }
+    const size_t numMipBindings = bloomRenderTarget->GetMipLevels() - 1; // (:32)
+
+    if (!m_pComputeDownscaleShader) m_pComputeDownscaleShader = driver->CreateShader("Shaders/ComputeBloomDownscale.shader"); // (:34-40)
+    if (!m_pComputeUpscaleShader) m_pComputeUpscaleShader = driver->CreateShader("Shaders/ComputeBloomUpscale.shader");       // (:42-48)
+    if (!m_pComputeUpscaleShader || !m_pComputeDownscaleShader || !m_pComputeUpscaleShader->IsReady() || !m_pComputeDownscaleShader->IsReady()) { // (:50-54)
+        commands->EndDebugRegion(commandList);
+        return;
+    }
+
+    if (m_computeUpscaleBindings.empty()) { // (:56-72)
+        RHITexturePtr lensDirtTexture = frameGraph->GetSampler("g_lensDirtSampler");
+        m_computeUpscaleBindings.resize(bloomRenderTarget->GetMipLevels());
+        for (uint32_t i = (uint32_t)bloomRenderTarget->GetMipLevels() - 1; i >= 1; --i) {
+            auto readMipLevel = bloomRenderTarget->GetMipLevel(i), writeMipLevel = bloomRenderTarget->GetMipLevel(i - 1); // GetMipLayer
+            m_computeUpscaleBindings[i] = driver->CreateShaderBindings();
+            driver->AddSamplerToShaderBindings(m_computeUpscaleBindings[i], "u_dirt_texture", lensDirtTexture, 2);
+            driver->AddStorageImageToShaderBindings(m_computeUpscaleBindings[i], "u_input_texture", readMipLevel, 0);
+            driver->AddStorageImageToShaderBindings(m_computeUpscaleBindings[i], "u_output_image", writeMipLevel, 1);
+        }
+    }
+    if (m_computeDownscaleBindings.empty()) { // (:74-87)
+        m_computeDownscaleBindings.resize(numMipBindings);
+        for (uint32_t i = 0; i < bloomRenderTarget->GetMipLevels() - 1; ++i) {
+            auto readMipLevel = bloomRenderTarget->GetMipLevel(i), writeMipLevel = bloomRenderTarget->GetMipLevel(i + 1);
+            m_computeDownscaleBindings[i] = driver->CreateShaderBindings();
+            driver->AddStorageImageToShaderBindings(m_computeDownscaleBindings[i], "u_input_texture", readMipLevel, 0);
+            driver->AddStorageImageToShaderBindings(m_computeDownscaleBindings[i], "u_output_image", writeMipLevel, 1);
+        }
+    }
+
+    auto vec = [&](const char* name) { auto it = m_vectorParams.find(name); return it == m_vectorParams.end() ? vec4() : it->second; }; // GetVec4
+    const vec4 threshold = vec("threshold"), knee = vec("knee"); // (:89-90)
+    PushConstantsDownscale downscaleParams {};
+    sailor_host_bloom_push_constants(threshold.x, knee.x, downscaleParams.m_threshold); // (:93)
+
+    commands->ImageMemoryBarrier(commandList, bloomRenderTarget, EImageLayout::General); // (:95)
+    for (uint32_t i = 0; i < bloomRenderTarget->GetMipLevels() - 1; ++i) { // Bloom Downscale (:98-116)
+        downscaleParams.m_useThreshold = i == 0;
+        auto readMipLevel = bloomRenderTarget->GetMipLevel(i), writeMipLevel = bloomRenderTarget->GetMipLevel(i + 1);
+        const float mipSize[2] = { (float)writeMipLevel->GetExtent().x, (float)writeMipLevel->GetExtent().y };
+        commands->ImageMemoryBarrier(commandList, readMipLevel, EImageLayout::General);       // ComputeRead
+        commands->ImageMemoryBarrier(commandList, writeMipLevel, EImageLayout::ComputeWrite);
+        commands->Dispatch(commandList, m_pComputeDownscaleShader, (uint32_t)std::ceil(mipSize[0] / 8), (uint32_t)std::ceil(mipSize[1] / 8), 1u,
+                           { m_computeDownscaleBindings[i] }, &downscaleParams, sizeof(PushConstantsDownscale));
+    }
+
+    PushConstantsUpscale upscaleParams {}; // (:118-120)
+    upscaleParams.m_bloomIntensity = vec("bloomIntensity").x;
+    upscaleParams.m_dirtIntensity = vec("dirtIntensity").x;
+    for (uint32_t i = (uint32_t)bloomRenderTarget->GetMipLevels() - 1; i >= 1; --i) { // Bloom Upscale (:123-141)
+        auto readMipLevel = bloomRenderTarget->GetMipLevel(i), writeMipLevel = bloomRenderTarget->GetMipLevel(i - 1);
+        const float mipSize[2] = { (float)writeMipLevel->GetExtent().x, (float)writeMipLevel->GetExtent().y };
+        upscaleParams.m_mipLevel = i;
+        commands->ImageMemoryBarrier(commandList, readMipLevel, EImageLayout::General);       // ComputeRead
+        commands->ImageMemoryBarrier(commandList, writeMipLevel, EImageLayout::ComputeWrite);
+        commands->Dispatch(commandList, m_pComputeUpscaleShader, (uint32_t)std::ceil(mipSize[0] / 8), (uint32_t)std::ceil(mipSize[1] / 8), 1u,
+                           { m_computeUpscaleBindings[i] }, &upscaleParams, sizeof(PushConstantsUpscale));
+    }
+    commands->EndDebugRegion(commandList); // (:143)
+}
+
+void BloomNode::Clear() {} // (:146-148)

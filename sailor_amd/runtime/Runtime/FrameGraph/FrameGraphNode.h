@@ -14,6 +14,10 @@ public:
     static void RegisterFrameGraphNode(const std::string& nodeName, std::function<FrameGraphNodePtr(void)> factoryMethod);
     static FrameGraphNodePtr CreateNode(const std::string& nodeName);
     static bool IsRegistered(const std::string& nodeName);
+    // Node classes of this mirror that are compiled in but NOT in the registry: a graph creates one only if it opted in by name
+    // (RHIFrameGraph::EnableNode).  In the engine such a class registers like every other (BloomNode.h:43 `template class TFrameGraphNode<BloomNode>`);
+    // here older tests use its name as their example of a name without a node class, so CreateNode and IsRegistered keep answering "no".
+    static FrameGraphNodePtr CreateOptInNode(const std::string& nodeName);
 private:
     static std::map<std::string, std::function<FrameGraphNodePtr(void)>>& Registry();
 };

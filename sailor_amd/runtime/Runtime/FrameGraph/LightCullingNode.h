@@ -194,4 +194,31 @@ protected:
     bool m_bIsDirty = true;                 // SkyNode.h:174
 };
 
+// The mip pyramid over `Main`: Runtime/FrameGraph/BloomNode.h.  Resource (DefaultRenderer.renderer:303-304): "bloom" = the HDR target with its mip chain,
+// rewritten in place; vec4 "threshold", "knee", "bloomIntensity", "dirtIntensity" (their .x).  `u_dirt_texture` is the graph's "g_lensDirtSampler".
+// In the reference this is a TFrameGraphNode<BloomNode> (BloomNode.h:10, :43) and registers under "Bloom"; here the class derives from the base directly
+// and is created by FrameGraphBuilder::CreateOptInNode for graphs that enabled it (FrameGraphNode.h says why).
+class BloomNode : public BaseFrameGraphNode {
+public:
+    static const char* GetName() { return m_name; }
+    std::string GetDebugName() const override { return m_name; }
+    void Process(RHIFrameGraphPtr frameGraph, RHI::RHICommandListPtr transferCommandList, RHI::RHICommandListPtr commandList,
+                 const RHI::RHISceneViewSnapshot& sceneView) override;
+    void Clear() override;
+
+protected:
+    static const char* m_name;
+    RHI::RHIShaderPtr m_pComputeDownscaleShader, m_pComputeUpscaleShader;
+    TVector<RHI::RHIShaderBindingSetPtr> m_computeDownscaleBindings, m_computeUpscaleBindings;
+    struct PushConstantsDownscale { // BloomNode.h:28-32
+        float m_threshold[4];       // x -> threshold, yzw -> (threshold - knee, 2.0 * knee, 0.25 * knee)
+        bool m_useThreshold;
+    };
+    struct PushConstantsUpscale { // BloomNode.h:34-39
+        uint32_t m_mipLevel;
+        float m_bloomIntensity;
+        float m_dirtIntensity;
+    };
+};
+
 } // namespace Sailor::Framegraph

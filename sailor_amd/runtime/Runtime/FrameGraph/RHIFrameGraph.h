@@ -3,6 +3,7 @@
 // specific barrier balancing (:201-246) and command-list chaining (:254-322) are out of scope.
 #pragma once
 #include <map>
+#include <set>
 #include <string>
 #include <vector>
 #include "BaseFrameGraphNode.h"
@@ -34,6 +35,9 @@ public:
     }
     void SetValue(const std::string& name, float v) { m_values[name] = v; } // RHIFrameGraph.h SetValue (FrameGraphParser.cpp:130)
     float GetValue(const std::string& name, float fallback = 0.0f) const { auto it = m_values.find(name); return it == m_values.end() ? fallback : it->second; }
+    // opt-in node classes (FrameGraphBuilder::CreateOptInNode): kept across Clear(), so that it can be set before a `.renderer` text is loaded
+    void EnableNode(const std::string& name) { m_enabledNodes.insert(name); }
+    bool IsNodeEnabled(const std::string& name) const { return m_enabledNodes.count(name) != 0; }
     void SetViewport(int32_t width, int32_t height) { m_viewport = { width, height }; } // App::GetMainWindow()->GetRenderArea()
     RHI::ivec2 GetViewport() const { return m_viewport; }
 
@@ -47,6 +51,7 @@ private:
     std::map<std::string, RHI::RHITexturePtr> m_renderTargets;
     std::map<std::string, RHI::RHITexturePtr> m_samplers;
     std::map<std::string, float> m_values;
+    std::set<std::string> m_enabledNodes;
     RHI::ivec2 m_viewport;
 };
 

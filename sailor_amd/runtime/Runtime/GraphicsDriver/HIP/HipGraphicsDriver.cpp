@@ -85,7 +85,8 @@ RHIShaderPtr HipGraphicsDriver::CreateShader(const std::string& assetPath, const
     static const char* const routed[] = { "Shaders/ComputeLightCulling.shader", "Shaders/Standard.shader", "Shaders/ComputeMeshCulling.shader",
         "Shaders/ComputeDepthHighZ.shader", "Shaders/ComputeHistogram.shader", "Shaders/ComputeAverageLuminance.shader", "Shaders/ComputeBrdfLut.shader",
         "Shaders/ComputeIrradianceMap.shader", "Shaders/ComputeEnvMap_IBL.shader", "Shaders/ShadowCaster.shader", "Shaders/LinearizeDepth.shader",
-        "Shaders/Tonemapping.shader", "Shaders/Blur.shader", "Shaders/HBAO.shader", "Shaders/HBAO_Blur.shader", "Shaders/Sky.shader" };
+        "Shaders/Tonemapping.shader", "Shaders/Blur.shader", "Shaders/HBAO.shader", "Shaders/HBAO_Blur.shader", "Shaders/Sky.shader", "Shaders/ComputeBloomDownscale.shader",
+        "Shaders/ComputeBloomUpscale.shader" };
     auto shader = RHIShaderPtr::Make(assetPath, defines);
     shader->m_bIsReady = false;
     for (const char* name : routed) if (assetPath == name) shader->m_bIsReady = true;
@@ -172,6 +173,16 @@ RHICubemapPtr HipGraphicsDriver::WrapCubemap(void* devicePtr, int size, uint32_t
     auto t = RHITexturePtr::Make();
     t->m_extent = { size, size }; t->m_format = format; t->m_mipLevels = mipLevels; t->m_bCubemap = true;
     t->m_buffer = WrapBuffer(devicePtr, cube_chain_texels(size, mipLevels) * texel_size(format));
+    return t;
+}
+
+RHITexturePtr HipGraphicsDriver::WrapRenderTarget(void* devicePtr, ivec2 extent, uint32_t mipLevels, EFormat format)
+{
+    auto t = RHITexturePtr::Make(); // the layout of CreateRenderTarget: level-major, level l = max(1, extent >> l)
+    t->m_extent = extent; t->m_format = format; t->m_mipLevels = mipLevels < 1 ? 1 : mipLevels;
+    size_t texels = 0;
+    for (uint32_t l = 0; l < t->m_mipLevels; l++) texels += (size_t)((extent.x >> l) > 1 ? (extent.x >> l) : 1) * ((extent.y >> l) > 1 ? (extent.y >> l) : 1);
+    t->m_buffer = WrapBuffer(devicePtr, texels * texel_size(format));
     return t;
 }
 
@@ -511,6 +522,8 @@ void HipGraphicsDriver::Dispatch(RHICommandListPtr cmd, RHIShaderPtr computeShad
         if (name == "Shaders/ComputeBrdfLut.shader") return RecordBrdfLut(bindings);
         if (name == "Shaders/ComputeIrradianceMap.shader") return RecordIrradianceMap(bindings);
         if (name == "Shaders/ComputeEnvMap_IBL.shader") return RecordEnvPrefilter(bindings, pc);
+        if (name == "Shaders/ComputeBloomDownscale.shader") return RecordBloomDownscale(bindings, pc);
+        if (name == "Shaders/ComputeBloomUpscale.shader") return RecordBloomUpscale(bindings, pc);
         return (int)SAILOR_HIP_ERR_UNSUPPORTED;
     });
 }
@@ -1015,6 +1028,50 @@ int HipGraphicsDriver::RecordEnvPrefilter(const TVector<RHIShaderBindingSetPtr>&
     if (env->GetExtent().x != raw->GetExtent().x || env->m_mipLevels != raw->m_mipLevels || env->m_format != raw->m_format) return SAILOR_HIP_ERR_UNSUPPORTED;
     return sailor_hip_prefilter_env_level(m_ctx, (const float*)raw->m_buffer->m_hip.m_devicePtr, (float*)env->m_buffer->m_hip.m_devicePtr, raw->GetExtent().x,
                                           (int32_t)raw->m_mipLevels, (int32_t)view->m_viewLevel, roughness);
+}
+
+// ---- BloomNode (FrameGraph/BloomNode.cpp:110-115, :135-140) ----------------------------------------------------------------------------------
+// a bound RGBA32F image (a mip-level view of the bloom target, the lens-dirt sampler), or null
+static RHITexturePtr rgba_image_of(const TVector<RHIShaderBindingSetPtr>& bindings, const char* name)
+{
+    auto t = texture_of(bindings, name);
+    return (t && t->m_buffer && t->m_format == EFormat::R32G32B32A32_SFLOAT && !t->m_bCubemap) ? t : RHITexturePtr();
+}
+
+int HipGraphicsDriver::RecordBloomDownscale(const TVector<RHIShaderBindingSetPtr>& bindings, const TVector<uint8_t>& pcBytes)
+{
+    // { m_computeDownscaleBindings[i] }; ComputeBloomDownscale.shader:11-18: binding 0 `u_input_texture`, 1 `u_output_image`, push constants { vec4 u_threshold;
+    // bool u_use_threshold } -- the node's struct ends in a C++ bool (BloomNode.h:31): its one byte at offset 16 is what is read.  The group counts of the
+    // Dispatch (ceil(mip / 8)) are implied by the output image.
+    if (bindings.size() != 1 || pcBytes.size() < 17) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    auto src = rgba_image_of(bindings, "u_input_texture"), dst = rgba_image_of(bindings, "u_output_image");
+    if (!src || !dst) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    float threshold[4];
+    memcpy(threshold, pcBytes.data(), sizeof threshold);
+    BeforeBufferWrite(dst->m_buffer->m_hip.m_devicePtr);
+    return sailor_hip_bloom_downscale(m_ctx, (const float*)texels_of(src), src->GetExtent().x, src->GetExtent().y, (float*)texels_of(dst), dst->GetExtent().x,
+                                      dst->GetExtent().y, threshold, pcBytes[16] != 0 ? 1 : 0);
+}
+
+int HipGraphicsDriver::RecordBloomUpscale(const TVector<RHIShaderBindingSetPtr>& bindings, const TVector<uint8_t>& pcBytes)
+{
+    // { m_computeUpscaleBindings[i] }; ComputeBloomUpscale.shader:11-20: binding 0 `u_input_texture`, 1 `u_output_image`, 2 `u_dirt_texture`, push constants
+    // { int u_mip_level; float u_bloom_intensity; float u_dirt_intensity }.  The dirt texture is sampled at mip level 1 only: there a name that resolved to
+    // nothing (no "g_lensDirtSampler" published) is an invalid argument; at the other levels it is not looked at.
+    if (bindings.size() != 1 || pcBytes.size() < 12) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    auto src = rgba_image_of(bindings, "u_input_texture"), dst = rgba_image_of(bindings, "u_output_image");
+    if (!src || !dst) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    uint32_t mipLevel; float bloomIntensity, dirtIntensity;
+    memcpy(&mipLevel, pcBytes.data(), 4); memcpy(&bloomIntensity, pcBytes.data() + 4, 4); memcpy(&dirtIntensity, pcBytes.data() + 8, 4);
+    RHITexturePtr dirt;
+    if (mipLevel == 1u) {
+        dirt = rgba_image_of(bindings, "u_dirt_texture");
+        if (!dirt) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    }
+    BeforeBufferWrite(dst->m_buffer->m_hip.m_devicePtr);
+    return sailor_hip_bloom_upscale(m_ctx, (const float*)texels_of(src), src->GetExtent().x, src->GetExtent().y, (float*)texels_of(dst), dst->GetExtent().x,
+                                    dst->GetExtent().y, (int32_t)mipLevel, bloomIntensity, dirtIntensity, dirt ? (const float*)texels_of(dirt) : nullptr,
+                                    dirt ? dirt->GetExtent().x : 0, dirt ? dirt->GetExtent().y : 0);
 }
 
 int HipGraphicsDriver::RecordDepthHighZ(const TVector<RHIShaderBindingSetPtr>& bindings)

@@ -10,6 +10,9 @@
 //   "Shaders/ComputeHistogram.shader" / "ComputeAverageLuminance.shader" (EyeAdaptationNode's two Dispatches)
 //                                        -> sailor_hip_luminance_histogram / sailor_hip_average_luminance (ComputeHistogram.shader:14-25,
 //                                           ComputeAverageLuminance.shader:14-27); the `histogram` SSBO is created with room for the node state
+//   "Shaders/ComputeBloomDownscale.shader" / "ComputeBloomUpscale.shader" (BloomNode's 2 (levels - 1) Dispatches)
+//                                        -> sailor_hip_bloom_downscale / sailor_hip_bloom_upscale (ComputeBloomDownscale.shader:11-18,
+//                                           ComputeBloomUpscale.shader:11-20); the level views of the bloom target and `u_dirt_texture` are found by name
 //   "Shaders/ComputeBrdfLut.shader" / "ComputeIrradianceMap.shader" / "ComputeEnvMap_IBL.shader" (EnvironmentNode's one-off Dispatches)
 //                                        -> sailor_hip_compute_brdf_lut / _compute_irradiance_map / _prefilter_env_level
 // and the one full-screen DRAW in front of the path (6 indices with the material of)
@@ -80,6 +83,7 @@ public:
     RHI::RHIBufferPtr WrapBuffer(void* devicePtr, size_t size);
     RHI::RHITexturePtr WrapTexture(void* devicePtr, RHI::ivec2 extent, RHI::EFormat format);
     RHI::RHICubemapPtr WrapCubemap(void* devicePtr, int size, uint32_t mipLevels, RHI::EFormat format);
+    RHI::RHITexturePtr WrapRenderTarget(void* devicePtr, RHI::ivec2 extent, uint32_t mipLevels, RHI::EFormat format); // a mip chain laid out like CreateRenderTarget's
 
     // IGraphicsDriverCommands
     void BeginDebugRegion(RHI::RHICommandListPtr cmdList, const std::string& title) override;
@@ -123,6 +127,8 @@ private:
     int RecordHbao(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target);
     int RecordHbaoBlur(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target, bool vertical);
     int RecordSky(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target, int permutation);
+    int RecordBloomDownscale(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const TVector<uint8_t>& pc);
+    int RecordBloomUpscale(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const TVector<uint8_t>& pc);
 
     SailorHipContext* m_ctx = nullptr;              // == m_ctxOwner.get(): what the C-ABI calls take
     std::shared_ptr<SailorHipContext> m_ctxOwner;   // destroyed with the last buffer that still refers to it

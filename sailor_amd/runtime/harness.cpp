@@ -55,11 +55,23 @@ RT_API void sailor_rt_destroy(SailorRuntime* rt)
 
 RT_API int sailor_rt_node_registered(const char* name) { return FrameGraphBuilder::IsRegistered(name) ? 1 : 0; }
 
+// Opt this runtime's graphs in to a node class that is compiled in but not registered (FrameGraphBuilder::CreateOptInNode: "Bloom"): sailor_rt_load_renderer
+// and sailor_rt_build_graph then create it where they meet the name; sailor_rt_node_registered keeps answering 0, and a runtime that did not opt in
+// keeps skipping the entry.  In the engine the class registers normally (BloomNode.h:43); the opt-in exists because this mirror's older tests use "Bloom" as
+// their example of a name without a node class.  0, or -1 for a name that has no such class.
+RT_API int sailor_rt_enable_node(SailorRuntime* rt, const char* name)
+{
+    if (!rt || !name || !FrameGraphBuilder::CreateOptInNode(name)) return -1;
+    rt->graph.EnableNode(name);
+    return 0;
+}
+
 // builds the graph from node names, as FrameGraphImporter does from the .renderer YAML (FrameGraphParser.cpp:153)
 RT_API int sailor_rt_build_graph(SailorRuntime* rt, const char** nodeNames, int count)
 {
     for (int i = 0; i < count; i++) {
         auto node = FrameGraphBuilder::CreateNode(nodeNames[i]);
+        if (!node && rt->graph.IsNodeEnabled(nodeNames[i])) node = FrameGraphBuilder::CreateOptInNode(nodeNames[i]);
         if (!node) return -1;
         if (std::string(nodeNames[i]) == "LightCulling") rt->lightCulling = node;
         if (std::string(nodeNames[i]) == "LinearizeDepth") rt->linearizeDepth = node;
@@ -620,6 +632,16 @@ RT_API void sailor_rt_set_color_target(SailorRuntime* rt, const char* name, void
 {
     auto* hip = static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver());
     rt->graph.SetRenderTarget(name, hip->WrapTexture(devicePtr, { width, height }, EFormat::R32G32B32A32_SFLOAT));
+}
+
+// the same with a mip chain behind level 0 (`Main`, DefaultRenderer.renderer:24-31): devicePtr is a level-major RGBA32F chain of sailor_hip_mip_chain_texels(
+// width, height, levels) texels whose head -- level 0 -- may be the very buffer RenderScene writes its radiance to
+RT_API int sailor_rt_set_color_target_chain(SailorRuntime* rt, const char* name, void* devicePtr, int width, int height, int levels)
+{
+    auto* hip = static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver());
+    if (!rt || !name || !devicePtr || levels < 1 || sailor_hip_mip_chain_texels(width, height, levels) == 0) return -1;
+    rt->graph.SetRenderTarget(name, hip->WrapRenderTarget(devicePtr, { width, height }, (uint32_t)levels, EFormat::R32G32B32A32_SFLOAT));
+    return 0;
 }
 
 // sceneView.m_deltaTime / m_currentTime of the frames processed from here on (EyeAdaptationNode.cpp:162 reads the first)

@@ -61,6 +61,8 @@ def load() -> C.CDLL:
         rt.sailor_rt_set_sampler.argtypes = [P, C.c_char_p, P, C.c_int, C.c_int]
         rt.sailor_rt_set_color_target.argtypes = [P, C.c_char_p, P, C.c_int, C.c_int]
         rt.sailor_rt_set_time.argtypes = [P, C.c_float, C.c_float]
+        rt.sailor_rt_enable_node.argtypes = [P, C.c_char_p]
+        rt.sailor_rt_set_color_target_chain.argtypes = [P, C.c_char_p, P, C.c_int, C.c_int, C.c_int]
         rt.sailor_rt_eye_adaptation_state.argtypes = [P, C.POINTER(P), C.POINTER(P)]
         rt.sailor_rt_shadow_pass.argtypes = [P, C.POINTER(C.c_float), P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, C.c_uint32, P, C.c_int, C.c_int, C.c_float, C.c_float]
         rt.sailor_rt_gpu_culling.argtypes = [P, P, C.c_uint32, C.c_uint32, P, C.c_uint32]
@@ -255,6 +257,19 @@ class Runtime:
     def set_color_target(self, name: str, tensor):
         """publish a float32 [h, w, 4] device tensor as a named RGBA render target (the HDR target RenderScene's radiance stands for, an LDR target)"""
         self.rt.sailor_rt_set_color_target(self.h, name.encode(), tensor.data_ptr(), tensor.shape[1], tensor.shape[0])
+
+    def set_color_target_chain(self, name: str, chain, width: int, height: int, levels: int):
+        """publish a flat float32 device tensor holding a level-major RGBA mip chain (host.mip_chain_texels(width, height, levels) * 4 floats) as a named
+        render target with `levels` mip levels; its head is level 0 and may be the radiance tensor's storage"""
+        from . import host
+        assert chain.is_contiguous() and chain.numel() >= host.mip_chain_texels(width, height, levels) * 4, chain.numel()
+        if self.rt.sailor_rt_set_color_target_chain(self.h, name.encode(), chain.data_ptr(), width, height, levels) != 0:
+            raise ValueError(f"bad mip chain {width} x {height} x {levels}")
+
+    def enable_node(self, name: str):
+        """opt this runtime's graphs in to a node class that is compiled in but not registered ("Bloom"): load_renderer / build_graph then create it"""
+        if self.rt.sailor_rt_enable_node(self.h, name.encode()) != 0:
+            raise ValueError(f"no opt-in node class {name!r}")
 
     def set_time(self, delta_time: float, current_time: float = 0.0):
         """sceneView.m_deltaTime / m_currentTime of the frames processed from here on"""
