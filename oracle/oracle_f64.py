@@ -1,9 +1,11 @@
-"""Independent float64 restatement of K2 (PBR shade), K3 (cascaded-shadow factor) and K4 (ECS transform / bounds / frustum sweep).
+"""Independent float64 restatement of K2 (PBR shade, ambient / IBL term included), K3 (cascaded-shadow factor) and K4 (ECS transform / bounds /
+frustum sweep); further down the EVSM blur, the two cube bakes and the BRDF table.
 
 TEST INFRASTRUCTURE ONLY.  PARITY UNPINNED by the reference (it has no golden vectors): this file exists to harden the fp32 C oracle
 (oracle/sailor_oracle.c), not to replace it.  It was written from the reference's own text only --
 
-  K2   Content/Shaders/Standard.shader:259-341 (CalculateLighting), :377-439 (main), Lighting.glsl:39-76 (NdfGGX, GeometrySchlick*, FresnelSchlick)
+  K2   Content/Shaders/Standard.shader:259-341 (CalculateLighting), :343-372 (AmbientLighting), :377-439 (main), Lighting.glsl:39-76 (NdfGGX,
+       GeometrySchlick*, FresnelSchlick); the samplers of the ambient term by the Vulkan specification (see the round-3 block below)
   K3   Lighting.glsl:168-197 (ManualPCF), :200-216 (SelectCascade), :218-240 (Linstep / ReduceLightBleed / Chebyshev), :242-284 (the two lookups)
   K4   Runtime/Math/Transform.cpp:39-42, Runtime/ECS/TransformECS.cpp:144-212, Runtime/Math/Bounds.cpp:245-260,479-492, Bounds.h:119-130
 
@@ -177,16 +179,45 @@ def calculate_lighting(fr, L, albedo, metallic, roughness, F0, Lo, cos_lo, norma
         return shadow[..., None] * ((diffuse + specular) * L["intensity"].astype(np.float64) * cos_li[..., None]) * falloff[..., None]
 
 
+def seam_margin(d):
+    """How close a cube-map direction is to a face seam: the relative gap (a1 - a2) / a1 between the largest and the second-largest |component| of
+    d [..., 3].  0 is an exact tie (the face is then chosen by the tie rule z over y over x); a fp32 evaluation of a direction whose margin is within
+    rounding of 0 may legitimately select the neighbouring face."""
+    a = np.sort(np.abs(np.asarray(d, np.float64)), -1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return (a[..., 2] - a[..., 1]) / a[..., 2]
+
+
+def ambient_lighting(ibl, albedo, metallic, roughness, ao, F0, Lr, normal, cos_lo):
+    """Standard.shader:343-372 over an array of pixels -> float64[n, 3].  ibl: dict with `irradiance` float[6, S, S, 4] (one level),
+    `env_chain` (flat RGBA32F mip chain), `env_size`, `env_levels`, `brdf_lut` float[H, W, 2]."""
+    irradiance = cube_texture_lod([np.asarray(ibl["irradiance"], np.float64)], normal, np.zeros(len(normal)))[:, :3]   # :346 texture(): one level
+    F = F0 + (1.0 - F0) * np.power(1.0 - cos_lo, 5.0)[:, None]                                                       # :352 FresnelSchlick(F0, cosLo)
+    m = metallic[:, None]
+    kd = (1.0 - F) * (1.0 - m) + 0.0 * m                                                                              # :355 mix(1 - F, 0, metallic)
+    diffuse_ibl = kd * albedo * irradiance                                                                           # :358
+    levels = int(ibl["env_levels"])                                                                                  # :361 textureQueryLevels
+    env = _cube_levels(ibl["env_chain"], int(ibl["env_size"]), levels)
+    specular_irradiance = cube_texture_lod(env, Lr, roughness * levels)[:, :3]                                        # :362
+    brdf = _texture_bilinear(np.asarray(ibl["brdf_lut"]), cos_lo, roughness)                                          # :365 texture(g_brdfSampler, (cosLo, roughness)).rg
+    specular_ibl = (F0 * brdf[:, 0:1] + brdf[:, 1:2]) * specular_irradiance                                          # :368
+    return ao[:, None] * (diffuse_ibl + specular_ibl)                                                                # :371
+
+
 def shade(frame_bytes, W: int, H: int, surface: np.ndarray, lights: np.ndarray, grid: np.ndarray, indices: np.ndarray, csm=None, rows=None,
-          want_conditioning: bool = False):
+          want_conditioning: bool = False, ibl=None, want_seam_margin: bool = False):
     """Standard.shader:377-439 over the synthetic surface: surface float32[3, H, W, 4] = (worldPos, albedo.a) (normal, roughness)
-    (albedo.rgb, metallic); grid uint32[T, 2], indices uint32[...] the canonical cull output; csm = (lightsMatrices[4, 16], [4 maps]) or None.
-    -> radiance float64[H, W, 4] (ambient term 0).  With want_conditioning also returns, per pixel, the smallest NdfGGX denominator met."""
+    (albedo.rgb, metallic); grid uint32[T, 2], indices uint32[...] the canonical cull output; csm = (lightsMatrices[4, 16], [4 maps]) or None;
+    ibl = None (ambient term 0) or the dict of ambient_lighting plus `ao`: float[H, W] (:386: the AO target has the viewport's size, so a fragment
+    reads its own texel) or None (1).  rows = (first, last + 1) shades a band of framebuffer rows, the rest stays 0.
+    -> radiance float64[H, W, 4].  With want_conditioning also returns, per pixel, the smallest NdfGGX denominator met; with want_seam_margin also
+    seam_margin() of the two cube lookups' directions, `normal` and `Lr`, float64[H, W] each."""
     fr = frame_fields(frame_bytes)
     lights = np.asarray(lights).view(LIGHT_DTYPE).reshape(-1) if np.asarray(lights).dtype != LIGHT_DTYPE else np.asarray(lights)
     s = surface.astype(np.float64)
     out = np.zeros((H, W, 4))
     min_denom = np.full((H, W), np.inf)
+    margin_n = np.full((H, W), np.inf); margin_lr = np.full((H, W), np.inf)
     vw, vh = int(fr["viewportSize"][0]), int(fr["viewportSize"][1])
     tiles_x = vw // TILE + min(1, vw % TILE)
     r0, r1 = (0, H) if rows is None else rows
@@ -205,6 +236,11 @@ def shade(frame_bytes, W: int, H: int, surface: np.ndarray, lights: np.ndarray, 
         cos_lo = np.maximum(0.0, (normal * -view_dir).sum(-1))
         F0 = 0.04 * (1.0 - metallic)[..., None] + albedo * metallic[..., None]  # mix(Fdielectric, albedo, metallic)
         acc = np.zeros(world_pos.shape)
+        if ibl is not None:
+            Lr = 2.0 * cos_lo[:, None] * normal + view_dir                      # :396
+            ao = np.ones(len(py)) if ibl.get("ao") is None else np.asarray(ibl["ao"], np.float64)[py, px]
+            acc += ambient_lighting(ibl, albedo, metallic, roughness, ao, F0, Lr, normal, cos_lo)   # :425
+            margin_n[py, px] = seam_margin(normal); margin_lr[py, px] = seam_margin(Lr)
         offset, num = int(grid[t, 0]), int(grid[t, 1])
         for i in range(num):
             index = int(indices[offset + i])
@@ -218,7 +254,8 @@ def shade(frame_bytes, W: int, H: int, surface: np.ndarray, lights: np.ndarray, 
                 min_denom[py, px] = np.minimum(min_denom[py, px], cl * cl * (a2 - 1.0) + 1.0)
         out[py, px, :3] = acc
         out[py, px, 3] = albedo_a
-    return (out, min_denom) if want_conditioning else out
+    ret = (out,) + ((min_denom,) if want_conditioning else ()) + ((margin_n, margin_lr) if want_seam_margin else ())
+    return ret if len(ret) > 1 else out
 
 
 # ---- K4 ---------------------------------------------------------------------------------------------------------------------------------
@@ -289,10 +326,12 @@ EVSM_BLUR_WEIGHTS = np.array([  # Lighting.glsl:87-99
     [0.0539209, 0.0535478, 0.0524437, 0.050654, 0.0482506, 0.0453272, 0.0419936, 0.0383686, 0.034573, 0.0307232, 0.0269255, 0.0232718]], np.float64)
 
 
-def evsm_blur_pass(image: np.ndarray, radius_umbra: int, radius_penumbra: int, vertical: bool) -> np.ndarray:
+def evsm_blur_pass(image: np.ndarray, radius_umbra: int, radius_penumbra: int, vertical: bool, dtype=np.float64) -> np.ndarray:
     """GaussianBlur_Evsm (Lighting.glsl:83-127) as one pass of Blur.shader {EVSM, HORIZONTAL | VERTICAL}: image [H, W, 4], radius = (umbra, penumbra);
-    the taps uv +- i texelSize of a fragment at a texel centre are texel centres: the texel itself, clamp-to-edge."""
-    img = np.asarray(image, np.float64)
+    the taps uv +- i texelSize of a fragment at a texel centre are texel centres: the texel itself, clamp-to-edge.  dtype=np.float32 rounds every
+    operation of the shader's own order (tap + tap, times the weight, added to the sum) to fp32: what a fp32 evaluation gives bit for bit."""
+    img = np.asarray(image, dtype)
+    weights = EVSM_BLUR_WEIGHTS.astype(dtype)
     H, W, _ = img.shape
     step_count = 12
     blur_radius = min(max(radius_umbra, radius_penumbra), step_count)
@@ -304,9 +343,9 @@ def evsm_blur_pass(image: np.ndarray, radius_umbra: int, radius_penumbra: int, v
         plus, minus = np.clip(idx + i, 0, n - 1), np.clip(idx - i, 0, n - 1)
         both = np.take(img, plus, axis=axis) + np.take(img, minus, axis=axis)
         if i < radius_umbra:
-            out[..., 2:4] += both[..., 2:4] * EVSM_BLUR_WEIGHTS[r1 - 1][i]
+            out[..., 2:4] += both[..., 2:4] * weights[r1 - 1][i]
         if i < radius_penumbra:
-            out[..., 0:2] += both[..., 0:2] * EVSM_BLUR_WEIGHTS[r2 - 1][i]
+            out[..., 0:2] += both[..., 0:2] * weights[r2 - 1][i]
     return out
 
 
@@ -453,4 +492,35 @@ def prefilter_env_level(raw_chain: np.ndarray, size0: int, levels: int, level: i
                 weight = cos_li[m].sum()
                 out[face, gy, gx, :3] = (rgb * cos_li[m][:, None]).sum(0) / weight
                 out[face, gy, gx, 3] = 1.0
+    return out
+
+
+def brdf_lut(w: int, h: int, num_samples: int = 1024) -> np.ndarray:
+    """ComputeBrdfLut.shader main() for every texel of a w x h image: float64[h, w, 2] = (DFG1, DFG2); texel (x, y) has cosLo = x / w (raised to the
+    shader's own Epsilon = 0.001) and roughness = y / h.  SampleGGX and GeometrySchlickGGX_IBL from Lighting.glsl:27-37, :65-70."""
+    eps = 0.001
+    i = np.arange(num_samples)
+    u1, u2 = i / float(num_samples), _radical_inverse_vdc(i)                 # SampleHammersley
+    phi = TWO_PI * u1
+    out = np.zeros((h, w, 2))
+    for y in range(h):
+        roughness = y / float(h)
+        alpha = roughness * roughness
+        with np.errstate(divide="ignore", invalid="ignore"):
+            cos_t = np.sqrt((1.0 - u2) / (1.0 + (alpha * alpha - 1.0) * u2))
+        sin_t = np.sqrt(1.0 - cos_t * cos_t)
+        Lh = np.stack([sin_t * np.cos(phi), sin_t * np.sin(phi), cos_t], 1)
+        k = (roughness * roughness) / 2.0
+        for x in range(w):
+            cos_lo = max(x / float(w), eps)
+            Lo = np.array([np.sqrt(1.0 - cos_lo * cos_lo), 0.0, cos_lo])
+            lo_lh = Lh @ Lo
+            Li = 2.0 * lo_lh[:, None] * Lh - Lo
+            cos_li, cos_lh, cos_lo_lh = Li[:, 2], Lh[:, 2], np.maximum(lo_lh, 0.0)
+            m = cos_li > 0.0
+            G = (cos_li[m] / (cos_li[m] * (1.0 - k) + k)) * (cos_lo / (cos_lo * (1.0 - k) + k))
+            Gv = G * cos_lo_lh[m] / (cos_lh[m] * cos_lo)
+            Fc = np.power(1.0 - cos_lo_lh[m], 5.0)
+            out[y, x, 0] = ((1.0 - Fc) * Gv).sum() / num_samples
+            out[y, x, 1] = (Fc * Gv).sum() / num_samples
     return out

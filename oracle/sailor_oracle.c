@@ -542,6 +542,25 @@ static inline void fetch_texel(const void* map, int fmt, int W, int x, int y, fl
     else { const float* p = &((const float*)map)[i * 4]; rgba[0] = p[0]; rgba[1] = p[1]; rgba[2] = p[2]; rgba[3] = p[3]; }
 }
 
+/* float -> int of a texel index or a mip level, DEFINED for every input: NaN -> 0, a value beyond int's range -> the nearest int.  (int)x is
+ * undefined in C for those (x86's cvttss2si happens to give INT_MIN for all three), while the device's v_cvt_i32_f32 saturates exactly like this; a NaN
+ * or infinite texture coordinate (a NaN normal, an infinite roughness) reaches these conversions.  tap_pair then forms x0 + 1 without overflow. */
+static int sat_int(float f)
+{
+    if (!(f == f)) return 0;
+    if (f >= 2147483648.0f) return 2147483647;
+    if (f <= -2147483648.0f) return -2147483647 - 1;
+    return (int)f;
+}
+static void tap_pair(float f, int size, int* i0, int* i1) /* the two clamp-to-edge taps floor(x), floor(x) + 1 of a `size`-texel axis */
+{
+    int a = sat_int(f);
+    a = a < -1 ? -1 : (a > size - 1 ? size - 1 : a);
+    const int b = a + 1;
+    *i0 = a < 0 ? 0 : a;
+    *i1 = b > size - 1 ? size - 1 : b;
+}
+
 /* texture(sampler2D, uv): bilinear, clamp-to-edge (ECS/LightingECS.cpp:58-60: Linear + Clamp), fp32 weights.
  * Canonical order: top = t00*(1-ax) + t10*ax ; bot = t01*(1-ax) + t11*ax ; top*(1-ay) + bot*ay */
 static void sample_bilinear(const void* map, int fmt, int W, int H, float u, float v, float* rgba)
@@ -549,9 +568,8 @@ static void sample_bilinear(const void* map, int fmt, int W, int H, float u, flo
     float x = u * (float)W - 0.5f, y = v * (float)H - 0.5f;
     float fx = floorf(x), fy = floorf(y);
     float ax = x - fx, ay = y - fy;
-    int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
-    x0 = x0 < 0 ? 0 : (x0 > W - 1 ? W - 1 : x0); x1 = x1 < 0 ? 0 : (x1 > W - 1 ? W - 1 : x1);
-    y0 = y0 < 0 ? 0 : (y0 > H - 1 ? H - 1 : y0); y1 = y1 < 0 ? 0 : (y1 > H - 1 ? H - 1 : y1);
+    int x0, y0, x1, y1;
+    tap_pair(fx, W, &x0, &x1); tap_pair(fy, H, &y0, &y1);
     float t00[4], t10[4], t01[4], t11[4];
     fetch_texel(map, fmt, W, x0, y0, t00); fetch_texel(map, fmt, W, x1, y0, t10);
     fetch_texel(map, fmt, W, x0, y1, t01); fetch_texel(map, fmt, W, x1, y1, t11);
@@ -835,9 +853,8 @@ static void bilinear4(const float* tex, int size, float s, float t, float* out) 
     const float x = s * (float)size - 0.5f, y = t * (float)size - 0.5f;
     const float fx = floorf(x), fy = floorf(y);
     const float ax = x - fx, ay = y - fy;
-    int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
-    x0 = x0 < 0 ? 0 : (x0 > size - 1 ? size - 1 : x0); x1 = x1 < 0 ? 0 : (x1 > size - 1 ? size - 1 : x1);
-    y0 = y0 < 0 ? 0 : (y0 > size - 1 ? size - 1 : y0); y1 = y1 < 0 ? 0 : (y1 > size - 1 ? size - 1 : y1);
+    int x0, y0, x1, y1;
+    tap_pair(fx, size, &x0, &x1); tap_pair(fy, size, &y0, &y1);
     for (int c = 0; c < 4; c++) {
         const float t00 = tex[((size_t)y0 * size + x0) * 4 + c], t10 = tex[((size_t)y0 * size + x1) * 4 + c];
         const float t01 = tex[((size_t)y1 * size + x0) * 4 + c], t11 = tex[((size_t)y1 * size + x1) * 4 + c];
@@ -861,7 +878,8 @@ static void cube_sample_lod(const float* cube, int size0, int levels, const floa
     const float maxLod = (float)(levels - 1);
     lod = lod < 0.0f ? 0.0f : (lod > maxLod ? maxLod : lod);
     const float fl = floorf(lod);
-    const int l0 = (int)fl, l1 = l0 + 1 > levels - 1 ? levels - 1 : l0 + 1;
+    int l0, l1; /* (a NaN lod passes the clamp above: level 0 and 1, weight NaN) */
+    tap_pair(fl, levels, &l0, &l1);
     const float f = lod - fl;
     float a[4], b[4];
     cube_sample_level(cube, size0, l0, dir, a);
@@ -874,9 +892,8 @@ static void lut_sample(const float* lut, int W, int H, float u, float v, float* 
     const float x = u * (float)W - 0.5f, y = v * (float)H - 0.5f;
     const float fx = floorf(x), fy = floorf(y);
     const float ax = x - fx, ay = y - fy;
-    int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
-    x0 = x0 < 0 ? 0 : (x0 > W - 1 ? W - 1 : x0); x1 = x1 < 0 ? 0 : (x1 > W - 1 ? W - 1 : x1);
-    y0 = y0 < 0 ? 0 : (y0 > H - 1 ? H - 1 : y0); y1 = y1 < 0 ? 0 : (y1 > H - 1 ? H - 1 : y1);
+    int x0, y0, x1, y1;
+    tap_pair(fx, W, &x0, &x1); tap_pair(fy, H, &y0, &y1);
     for (int c = 0; c < 2; c++) {
         const float t00 = lut[((size_t)y0 * W + x0) * 2 + c], t10 = lut[((size_t)y0 * W + x1) * 2 + c];
         const float t01 = lut[((size_t)y1 * W + x0) * 2 + c], t11 = lut[((size_t)y1 * W + x1) * 2 + c];

@@ -1,6 +1,11 @@
 // Canonical texture sampling shared by shade.hip (K3 shadow lookups, ambient / IBL term) and ibl_prefilter.hip: manual bilinear taps
 // (texel centres at (i + 0.5) / size, clamp-to-edge), the Vulkan cube face table (ties z over y over x) and the cube mip chain
 // layout -- level-major, then face, then size x size float4 texels.  Must match oracle/sailor_oracle.c bit for bit.
+// Non-finite coordinates (a NaN normal, an infinite roughness; a hardware sampler's result for them is undefined, so the choice is this path's own):
+// the (int) conversions below are the device's saturating convert -- NaN -> 0, +-inf -> INT_MAX / INT_MIN -- every tap index is clamped into the
+// image AFTER the conversion and without an addition that could wrap (see bilinear_taps: a roughness of +inf once read the BRDF table at row INT_MIN),
+// so no fetch leaves it, and the weights (inf - inf) are NaN, so the sample is NaN.  The oracle's conversion is defined to
+// give the same (sat_int / tap_pair there; plain (int)x is undefined in C for such values); tests/test_ambient_gpu.py compares these pixels by class.
 #pragma once
 #include "common.h"
 
@@ -12,9 +17,11 @@ __device__ __forceinline__ BilinearTaps bilinear_taps(int W, int H, float u, flo
     const float x = u * (float)W - 0.5f, y = v * (float)H - 0.5f;
     const float fx = floorf(x), fy = floorf(y);
     t.ax = x - fx; t.ay = y - fy;
-    int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
-    t.x0 = min(max(x0, 0), W - 1); t.x1 = min(max(x1, 0), W - 1);
-    t.y0 = min(max(y0, 0), H - 1); t.y1 = min(max(y1, 0), H - 1);
+    // the second tap as clamp(x0, -1, W - 2) + 1, not clamp(x0 + 1, 0, W - 1): the same index for every x0, but x0 = INT_MAX (a +inf coordinate) cannot wrap --
+    // the compiler turns the other form into max(x0, -1) + 1 BEFORE the upper clamp, and INT_MAX + 1 = INT_MIN then passes min(., W - 1) as a negative index
+    const int x0 = (int)fx, y0 = (int)fy;
+    t.x0 = min(max(x0, 0), W - 1); t.x1 = min(max(x0, -1), W - 2) + 1;
+    t.y0 = min(max(y0, 0), H - 1); t.y1 = min(max(y0, -1), H - 2) + 1;
     return t;
 }
 

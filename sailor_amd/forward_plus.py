@@ -317,6 +317,16 @@ def evsm_blur(ctx: "HipContext", moments: torch.Tensor, radius_umbra: int, radiu
     return moments
 
 
+def evsm_blur_pass(ctx: "HipContext", src: torch.Tensor, radius_umbra: int, radius_penumbra: int, vertical: bool, out: torch.Tensor | None = None) -> torch.Tensor:
+    """one pass of the blur ("Blur Horizontal" or "Blur Vertical") from src into another tensor; src float32 [H, W, 4]"""
+    assert src.dtype == torch.float32 and src.dim() == 3 and src.shape[2] == 4 and src.is_contiguous()
+    if out is None:
+        out = torch.empty_like(src)
+    _lib.check(ctx._lib.sailor_hip_evsm_blur_pass(ctx.handle, _ptr(src), _ptr(out), src.shape[1], src.shape[0], radius_umbra, radius_penumbra, int(vertical)),
+               "sailor_hip_evsm_blur_pass", ctx.handle)
+    return out
+
+
 def compute_brdf_lut(ctx: "HipContext", width: int, height: int) -> torch.Tensor:
     """ComputeBrdfLut.shader on the GPU -> float32 [height, width, 2]"""
     out = torch.empty((height, width, 2), dtype=torch.float32, device=ctx.device)

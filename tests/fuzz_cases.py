@@ -3,11 +3,15 @@
   k1k2_case : viewport, light set (radii, spot share, clusters, directional / NaN / infinite / behind-the-eye lights, negative radii), sky tiles,
               roughness-0 pixels; every cull path, random two-band splits -- lists bit for bit, radiance within 1e-4 relative, same finiteness
   k3_case   : viewport, shadow-map size and type, several directional lights, depth ranges that reach all cascades -- radiance within 1e-4 relative
+  ibl_case  : the ambient / IBL term: viewport, light count, cube / table sizes down to 1 with full or truncated chains, AO and shadow maps on or off, the
+              four entry forms, whole frame or two bands, tests/ibl_cases.py's pixel kinds (seam and corner normals, lod and table clamps, hostile pixels
+              and texels) sprinkled over the surface -- radiance within 1e-4 relative, non-finite values by class
   k4_case   : hierarchies (depth 1..6, ragged levels, degenerate / mirrored / huge scales, zero-size boxes) -- matrices / boxes / visibility bit for bit
 A failure names the seed and the case so that `scripts/fuzz_parity.py <cases> <seed> <case>` replays it."""
 import numpy as np
 import torch
 
+import ibl_cases
 from oracle import oracle
 from sailor_amd import _lib, host, synth
 from sailor_amd.forward_plus import EcsSweep, ForwardPlus, PreparedLights, upload_lights, upload_shadow_maps
@@ -179,6 +183,91 @@ def k3_case(ctx, rng, c):
             mb = np.abs(rb[fb]) > 0
             if mb.any():
                 worst = max(worst, float((eb[mb] / np.abs(rb[fb][mb])).max()))
+    return worst
+
+
+IBL_FORMS = {"": (False, False), "_p": (False, True), "_t": (True, False), "_pt": (True, True)}   # suffix -> (the cull's tile lists, prepared lights)
+
+
+def ibl_case(ctx, rng, c):
+    """one case of the ambient term on top of K2 (+ K3); returns the worst relative radiance error over the finite, non-zero values"""
+    W, H = int(rng.integers(16, 161)), int(rng.integers(16, 101))
+    N = int(rng.choice([0, 1, 64, 600]))
+    seed = int(rng.integers(1, 1 << 20))
+    env_size = int(rng.choice([1, 2, 8, 32]))
+    full = env_size.bit_length()
+    env_levels = full if rng.random() < 0.5 else int(rng.integers(1, full + 1))
+    irr_size = int(rng.choice([1, 2, 8]))
+    lut_wh = [(1, 1), (2, 3), (16, 16)][int(rng.integers(0, 3))]
+    with_ao, with_csm = bool(rng.random() < 0.5), bool(rng.random() < 0.5)
+    form = list(IBL_FORMS)[int(rng.integers(0, 4))]
+    hostile = bool(rng.random() < 0.3)
+    cfg = synth.LightSetConfig(count=N, spot_fraction=float(rng.choice([0.0, 0.3])), radius_scale=float(rng.choice([2.0, 6.0, 20.0])), directional_first=with_csm)
+    f = synth.make_frame("tiny_csm", width=W, height=H, seed=seed, shadow_size=int(rng.choice([3, 17, 64])), lights=cfg)
+    shadows = f.shadows if with_csm else None
+    surface = f.surface
+    # the pixel kinds of ibl_cases, sprinkled: a third of the pixels get a seam / corner / axis normal, a third a roughness at a clamp or an integer lod
+    sn, rv = ibl_cases.special_normals(), ibl_cases.roughness_values(env_levels)
+    m = rng.random((H, W)) < 0.33
+    own_normal = surface[1, ..., :3].copy()
+    surface[1, m, :3] = sn[rng.integers(0, len(sn), int(m.sum()))]
+    with np.errstate(invalid="ignore"):   # (a pixel ray on the screen's diagonal under a normal symmetric in x and y has |Lr.x| = |Lr.y| but for rounding: it keeps its own normal)
+        m = ibl_cases.lr_seam_margin(f.cam, surface) < 1e-3
+    surface[1, m, :3] = own_normal[m]
+    m = rng.random((H, W)) < 0.33
+    surface[1, m, 3] = rv[rng.integers(0, len(rv), int(m.sum()))]
+    m = rng.random((H, W)) < 0.33
+    surface[2, m, 3] = np.array([0.0, 0.5, 1.0], np.float32)[rng.integers(0, 3, int(m.sum()))]
+    if hostile:
+        ys, xs = rng.integers(0, H, 8), rng.integers(0, W, 8)
+        surface[1, ys[0], xs[0], 0] = np.nan; surface[1, ys[1], xs[1], :3] = 0.0; surface[0, ys[2], xs[2], 1] = np.inf; surface[0, ys[3], xs[3], 2] = -np.inf
+        surface[1, ys[4], xs[4], 3] = np.nan; surface[1, ys[5], xs[5], 3] = np.inf; surface[1, ys[6], xs[6], 3] = -3.0; surface[2, ys[7], xs[7], 3] = -np.inf
+    ts = ibl_cases.make_ibl(W, H, env_size, env_levels, irr_size, lut_wh, with_ao, seed=seed, hostile=hostile)
+    Tx, Ty = host.num_tiles(W, H)
+    cut = int(rng.integers(1, Ty)) if (Ty >= 2 and rng.random() < 0.5) else None
+    what = (f"ambient case {c}: {W}x{H}, {N} lights, env {env_size} / {env_levels} levels, irradiance {irr_size}, table {lut_wh}, ao {with_ao}, csm {with_csm}, "
+            f"form '{form}', cut {cut}, hostile {hostile}")
+    og, oi, _ = oracle.light_cull(f.cam.frame, W, H, f.lights, f.depth)
+    ocsm = oracle.make_csm(shadows.lights_matrices, shadows.maps)[0] if shadows is not None else None
+    oibl, _keep = oracle.make_ibl(ts.irradiance, ts.env_chain, ts.env_size, ts.env_levels, ts.brdf_lut, ts.ao)
+    ref_all = oracle.shade(f.cam.frame, W, H, surface, f.lights, og, oi, ocsm, ibl=oibl)
+    # the kernel forms Lr with fused multiply-adds, the oracle with a product and a sum: a pixel whose Lr lies within 1e-4 of a cube seam (in float64, from the
+    # inputs) may read the neighbouring face on one side.  A condition on the inputs, as in tests/test_ambient_gpu.py: such pixels are left out, at most 1 %.
+    with np.errstate(invalid="ignore"):
+        left_out = ibl_cases.lr_seam_margin(f.cam, surface) < 1e-4
+    assert left_out.mean() <= 0.01, (what, int(left_out.sum()))
+    l = upload_lights(f.lights, ctx.device)
+    gcsm, gkeep = upload_shadow_maps(shadows, ctx.device) if shadows is not None else (None, None)
+    tile_lists, prep = IBL_FORMS[form]
+    worst = 0.0
+    bands = [None] if cut is None else [host.band_from_tile_rows(W, H, 0, cut), host.band_from_tile_rows(W, H, cut, Ty)]
+    for b in bands:
+        fp = ForwardPlus(ctx, W, H, max(N, 1), band=b, prepared=PreparedLights(ctx, l, N) if prep else None)
+        fp.shade_from_tile_lists = tile_lists
+        rows = slice(fp.band.fbRowBegin, fp.band.fbRowBegin + fp.band.fbRowCount)
+        fp.cull(f.cam.frame, l, N, torch.from_numpy(np.ascontiguousarray(f.depth[rows])).to(ctx.device))
+        desc, keep = ibl_cases.upload_guarded(ts, ctx.device, ao_rows=(rows.start, rows.stop))
+        out = []
+        names = ctx.launches_of(lambda: out.append(fp.shade(f.cam.frame, torch.from_numpy(np.ascontiguousarray(surface[:, rows])).to(ctx.device), l, N, gcsm, ibl=desc)))
+        ctx.synchronize()
+        assert names == ["k2_shade_" + ("csm_" if with_csm else "") + "ibl" + form], (what, names)
+        got, ref = out[0].cpu().numpy(), ref_all[rows]
+        got[left_out[rows]] = ref[left_out[rows]]
+        mism = nonfinite_mismatch(got, ref)
+        if mism is not None:
+            y, x, ch = mism[1][0]
+            raise AssertionError(f"{what}: the {mism[0]} masks differ at {len(mism[1])} values; first {mism[1][0].tolist()} (band row): got {got[y, x]} ref {ref[y, x]} "
+                                 f"surface {surface[:, y + rows.start, x].tolist()}")
+        fin = np.isfinite(ref)
+        err = finite_abs_diff(got, ref, fin)[fin]
+        tol = 1e-4 * np.abs(ref.astype(np.float64))[fin]
+        if not (err <= tol).all():
+            bad = np.argwhere(fin & (finite_abs_diff(got, ref, fin) > 1e-4 * np.abs(ref.astype(np.float64))))
+            y, x, ch = bad[0]
+            raise AssertionError(f"{what}: {len(bad)} values off, first {bad[0].tolist()} (band row): got {got[y, x]} ref {ref[y, x]} surface {surface[:, y + rows.start, x].tolist()}")
+        nz = np.abs(ref[fin]) > 0
+        if nz.any():
+            worst = max(worst, float((err[nz] / np.abs(ref[fin][nz])).max()))
     return worst
 
 

@@ -15,6 +15,7 @@ EXTRA = [int(s) for s in os.environ.get("SAILOR_FUZZ_SEEDS", "").split(",") if s
 K1K2_CASES = int(os.environ.get("SAILOR_FUZZ_K1K2_CASES", "300"))
 K3_CASES = int(os.environ.get("SAILOR_FUZZ_K3_CASES", "100"))
 K4_CASES = int(os.environ.get("SAILOR_FUZZ_K4_CASES", "100"))
+IBL_CASES = int(os.environ.get("SAILOR_FUZZ_IBL_CASES", "60"))
 
 
 @pytest.mark.parametrize("seed", [20250301] + EXTRA)
@@ -41,6 +42,20 @@ def test_random_shadowed_frames(ctx, seed):
             raise AssertionError(f"seed {seed}, K3 case {c}: {e}") from e
     assert worst <= 1e-4
     print(f"[fuzz K3] seed {seed}: {K3_CASES} cases, worst relative radiance error {worst:.2e}")
+
+
+@pytest.mark.parametrize("seed", [20250305] + EXTRA)
+def test_random_ambient_frames(ctx, seed):
+    """the ambient / IBL term on random small frames (fuzz_cases.ibl_case): every entry form, bands, shadow maps, texture sizes down to 1, edge and hostile pixels"""
+    rng = np.random.default_rng(seed)
+    worst = 0.0
+    for c in range(IBL_CASES):
+        try:
+            worst = max(worst, fuzz_cases.ibl_case(ctx, rng, c))
+        except AssertionError as e:
+            raise AssertionError(f"seed {seed}, ambient case {c}: {e}") from e
+    assert worst <= 1e-4
+    print(f"[fuzz ambient] seed {seed}: {IBL_CASES} cases, worst relative radiance error {worst:.2e}")
 
 
 @pytest.mark.parametrize("seed", [20250303] + EXTRA)

@@ -885,6 +885,8 @@ def test_evsm_blur_against_the_float64_restatement(radii):
         oracle.lib().oracle_evsm_blur_pass(oracle._p(img), oracle._p(dst), 29, 41, radii[0], radii[1], vertical)
         ref = oracle_f64.evsm_blur_pass(img, radii[0], radii[1], bool(vertical))
         assert np.abs(dst - ref).max() <= 2e-6 * np.abs(ref).max()
+        # the same restatement with every operation rounded to fp32 IS the C oracle's pass (what the GPU test holds the single passes to)
+        np.testing.assert_array_equal(dst.view(np.uint32), oracle_f64.evsm_blur_pass(img, radii[0], radii[1], bool(vertical), dtype=np.float32).view(np.uint32))
     both = oracle.evsm_blur(img, radii[0], radii[1])
     ref = oracle_f64.evsm_blur_pass(oracle_f64.evsm_blur_pass(img, radii[0], radii[1], False), radii[0], radii[1], True)
     assert np.abs(both - ref).max() <= 4e-6 * np.abs(ref).max()
@@ -1050,3 +1052,105 @@ def test_e4_octree_trace_over_integer_boxes_against_the_flat_float_sweep(n, flip
     assert (float_only, octree_only) == flips_expected
     if n == 1024:   # the four Editor.world objects among them
         assert np.array_equal(fv[:4], tv[:4])
+
+
+# ---- the ambient / IBL term a second time (oracle_f64.ambient_lighting, written from Standard.shader:343-372 and the Vulkan sampling rules) ----
+import ibl_cases  # noqa: E402
+
+
+def _k2_excess(got, ref):
+    """err / tol per pixel under the K2 bound |got - ref| <= 1e-4 |ref| + 1e-7 max|ref| (rgb), float64[H, W]"""
+    err = np.abs(got[..., :3].astype(np.float64) - ref[..., :3])
+    return (err / (1e-4 * np.abs(ref[..., :3]) + 1e-7 * np.abs(ref[..., :3]).max())).max(-1)
+
+
+@pytest.mark.parametrize("name", ["tiny", "tiny_csm"])
+def test_c_oracle_ambient_frames_agree_with_the_float64_restatement(name):
+    """The ambient-lit tiny frames (smooth sky, full chain, 32 x 32 table, AO): the K2 bound between the C oracle and oracle_f64.shade(ibl=...).  Besides
+    the specular-peak pixels of the light sum (as in the test without the ambient term: few, NdfGGX denominator < 1e-3, within 2 %) a pixel may differ
+    only if one of its two cube directions is within 1e-4 of a face seam -- and on a sky that is continuous across the seams not even those do."""
+    from oracle import oracle_f64
+    f = synth.make_frame(name)
+    W, H = f.cam.width, f.cam.height
+    ibl = synth.make_ibl_set(W, H, oracle.compute_brdf_lut(32, 32))
+    g, idx, _ = oracle.light_cull(f.cam.frame, W, H, f.lights, f.depth)
+    ocsm = oracle.make_csm(f.shadows.lights_matrices, f.shadows.maps)[0] if f.shadows is not None else None
+    oibl, _k = oracle.make_ibl(ibl.irradiance, ibl.env_chain, ibl.env_size, ibl.env_levels, ibl.brdf_lut, ibl.ao)
+    got = oracle.shade(f.cam.frame, W, H, f.surface, f.lights, g, idx, ocsm, ibl=oibl)
+    csm = (f.shadows.lights_matrices, f.shadows.maps) if f.shadows is not None else None
+    ref, min_denom, m_n, m_lr = oracle_f64.shade(bytes(f.cam.frame), W, H, f.surface, f.lights, g, idx, csm, want_conditioning=True,
+                                                 ibl=ibl_cases.as_f64_ibl(ibl), want_seam_margin=True)
+    np.testing.assert_array_equal(got[..., 3], ref[..., 3])
+    excess = _k2_excess(got, ref)
+    bad = excess > 1.0
+    print(f"[ambient f64] {name}: C oracle worst err / tol {excess[~bad].max():.3f} over {(~bad).sum()} pixels, {bad.sum()} at a specular peak; "
+          f"{((m_n < 1e-4) | (m_lr < 1e-4)).sum()} within 1e-4 of a seam")
+    assert bad.sum() <= 0.001 * bad.size
+    assert (min_denom[bad] < 1e-3).all(), "a well-conditioned pixel differs between the fp32 oracle and the float64 restatement"
+    assert (excess[bad] <= 200.0).all()   # 2 % against the 1e-4 bound
+
+
+@pytest.mark.parametrize("size", ibl_cases.SIZES)
+@pytest.mark.parametrize("tex", list(ibl_cases.TEXTURE_SETS))
+def test_c_oracle_ambient_edges_agree_with_the_float64_restatement(tex, size):
+    """tests/ibl_cases.py's edge surface under every texture set: the K2 bound on every pixel but those a fp32 evaluation may put on the other cube
+    face (ibl_cases.left_out -- a condition on the INPUTS: at most 1 % of the pixels, never an exact-tie pixel), alpha bit for bit.  This is the
+    CPU confirmation the GPU test of the same inputs relies on."""
+    from oracle import oracle_f64
+    W, H = size
+    e = ibl_cases.make_edge_surface(W, H, ibl_cases.TEXTURE_SETS[tex][1])
+    ts = ibl_cases.make_texture_set(tex, W, H)
+    g, idx, _ = oracle.light_cull(e.cam.frame, W, H, e.lights, e.depth)
+    assert (g[:, 1] == len(e.lights)).all()   # every light reaches every tile
+    oibl, _k = oracle.make_ibl(ts.irradiance, ts.env_chain, ts.env_size, ts.env_levels, ts.brdf_lut, ts.ao)
+    got = oracle.shade(e.cam.frame, W, H, e.surface, e.lights, g, idx, None, ibl=oibl)
+    ref, m_n, m_lr = oracle_f64.shade(bytes(e.cam.frame), W, H, e.surface, e.lights, g, idx, None, ibl=ibl_cases.as_f64_ibl(ts), want_seam_margin=True)
+    out = ibl_cases.left_out(e, m_n, m_lr)
+    assert out.sum() <= 0.01 * out.size and not (out & e.exact_tie).any()
+    assert e.exact_tie.sum() > 0.7 * out.size and (m_n[e.exact_tie] < 1.0).sum() > 0.5 * out.size   # most pixels sit on a seam or a corner
+    np.testing.assert_array_equal(got[..., 3], ref[..., 3])
+    excess = _k2_excess(got, ref)
+    print(f"[ambient f64] edge {W}x{H} set {tex}: C oracle worst err / tol {excess[~out].max():.3f}, {out.sum()} pixels left out")
+    assert np.isfinite(got).all() and (excess[~out] <= 1.0).all(), np.argwhere((excess > 1.0) & ~out)[:5]
+    # the light sum is live and of the ambient term's size: neither hides the other
+    direct = oracle.shade(e.cam.frame, W, H, e.surface, e.lights, g, idx, None)[..., :3].sum(-1)
+    amb = got[..., :3].sum(-1) - direct
+    assert (direct > 0).mean() > 0.5 and 0.1 < np.median(direct[direct > 0]) / np.median(amb[amb > 0]) < 10.0
+
+
+def test_edge_surface_enumerates_its_kinds():
+    for levels in (1, 2, 4, 5):
+        e = ibl_cases.make_edge_surface(40, 24, levels)
+        n, r, m = e.surface[1, ..., :3], e.surface[1, ..., 3], e.surface[2, ..., 3]
+        for v in ibl_cases.special_normals():
+            assert (n == v).all(-1).sum() >= 10
+        for v in ibl_cases.roughness_values(levels):
+            assert (r == v).sum() >= 20, (levels, v)
+        for v in (0.0, 0.5, 1.0):
+            assert (m == v).sum() >= 200
+        view = e.surface[0, ..., :3] - np.array([0.0, 150.0, 0.0], np.float32)
+        cos_lo = np.maximum(np.float32(0), -(n * (view / np.linalg.norm(view, axis=-1, keepdims=True))).sum(-1))
+        assert (cos_lo == 0).sum() >= 100 and (np.abs(cos_lo - 1) < 1e-6).sum() >= 10
+    a = np.abs(ibl_cases.special_normals())
+    a.sort(-1)
+    assert (a[:6, 1] == 0).all() and (a[6:18, 2] == a[6:18, 1]).all() and (a[6:18, 0] < a[6:18, 1]).all() and (a[18:, 0] == a[18:, 2]).all()
+    assert (np.linalg.norm(a.astype(np.float64), axis=-1) <= 1.0).all()
+
+
+@pytest.mark.parametrize("size", [(32, 32), (48, 20), (1, 1)])
+def test_brdf_lut_against_the_float64_restatement(size):
+    """ComputeBrdfLut.shader: the C oracle against oracle_f64.brdf_lut.  Two causes of error, both inherent in ANY fp32 evaluation of the shader:
+    (a) 1 024 sequential fp32 additions into a sum of up to 1 024: half an ulp of the top binade (2^-15) each, 2^-15 after the division by 1 024 in
+    the worst case (equal addends round the same way: row 0 comes within a factor of two of it);  (b) SampleGGX's `alpha * alpha - 1.0`, which keeps
+    alpha^2 = roughness^4 only to 2^-24 absolute: a relative error of 2^-24 / roughness^4 in the quantity that decides the samples near u2 = 1, on
+    values in [0, 1].  Row 0 has alpha^2 = 0 exactly.  The figures are printed: the GPU test bounds the kernel by twice the worst of them."""
+    from oracle import oracle_f64
+    w, h = size
+    got, ref = oracle.compute_brdf_lut(w, h).astype(np.float64), oracle_f64.brdf_lut(w, h)
+    r = (np.arange(h) / h)[:, None, None]
+    with np.errstate(divide="ignore"):
+        bound = 2.0 ** -15 + np.where(r == 0, 0.0, np.minimum(1.0, 2.0 ** -24 / r ** 4))
+    err = np.abs(got - ref)
+    print(f"[brdf lut f64] {w}x{h}: C oracle worst abs error {err.max():.3e}; at roughness >= 1/4 {err[(r >= 0.25)[:, 0, 0]].max() if (r >= 0.25).any() else 0.0:.3e}")
+    assert (err <= bound).all(), np.argwhere(err > bound)[:5]
+    assert ref.min() >= 0.0 and ref.max() <= 1.0 + 1e-9

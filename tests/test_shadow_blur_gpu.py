@@ -4,9 +4,9 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import oracle
+from oracle import oracle, oracle_f64
 from sailor_amd import synth
-from sailor_amd.forward_plus import evsm_blur
+from sailor_amd.forward_plus import evsm_blur, evsm_blur_pass
 
 pytestmark = pytest.mark.gpu
 
@@ -16,9 +16,12 @@ def moments(size, seed=3):
     return np.ascontiguousarray(synth.make_shadow_set(cam, size, seed).maps[0])  # cascade 0: RGBA32F EVSM moments
 
 
-@pytest.mark.parametrize("radii", [(2, 5), (1, 4), (0, 3), (5, 2), (12, 12), (20, 1), (0, 0)])
+SPECIALISED = [(2, 5), (1, 4), (1, 3), (1, 2)]   # ShadowCascadeBlur (ECS/LightingECS.h:68): the pairs shadow_blur.hip compiles unrolled kernels for
+
+
+@pytest.mark.parametrize("radii", [(2, 5), (1, 4), (0, 3), (5, 2), (12, 12), (20, 1), (0, 0), (1, 3), (1, 2)])
 def test_bit_exact_for_the_reference_radii_and_the_caps(ctx, radii):
-    """(2, 5) is ShadowCascadeBlur[0] (ECS/LightingECS.h:68); radii above 12 are capped (Lighting.glsl:101-103); (0, 0) writes zeros."""
+    """The four pairs of ShadowCascadeBlur (ECS/LightingECS.h:68) run unrolled kernels; radii above 12 are capped (Lighting.glsl:101-103); (0, 0) writes zeros."""
     m = moments(96)
     ref = oracle.evsm_blur(m, *radii)
     got = evsm_blur(ctx, torch.from_numpy(m.copy()).to(ctx.device), *radii).cpu().numpy()
@@ -26,11 +29,21 @@ def test_bit_exact_for_the_reference_radii_and_the_caps(ctx, radii):
 
 
 def test_ragged_sizes_and_edges(ctx):
+    """Sizes below one block, one texel wide rows and columns, no multiple of the 256 x 1 / 32 x 8 blocks -- for every unrolled kernel: the two-pass call
+    against the C oracle, and each pass alone (sailor_hip_evsm_blur_pass, horizontal and vertical) against the float64 restatement's pass evaluated
+    in fp32 (the shader's own order of operations, every one rounded: oracle_f64.evsm_blur_pass(dtype=float32)), all bit for bit."""
     rng = np.random.default_rng(5)
     for h, w in ((1, 1), (3, 300), (257, 5), (64, 511)):
         m = (rng.random((h, w, 4)) * 50).astype(np.float32)
-        got = evsm_blur(ctx, torch.from_numpy(m.copy()).to(ctx.device), 2, 5).cpu().numpy()
-        np.testing.assert_array_equal(got.view(np.uint32), oracle.evsm_blur(m, 2, 5).view(np.uint32))
+        d = torch.from_numpy(m).to(ctx.device)
+        for radii in SPECIALISED:
+            got = evsm_blur(ctx, d.clone(), *radii).cpu().numpy()
+            np.testing.assert_array_equal(got.view(np.uint32), oracle.evsm_blur(m, *radii).view(np.uint32), err_msg=f"{h}x{w} radii {radii}")
+            for vertical in (False, True):
+                one = evsm_blur_pass(ctx, d, radii[0], radii[1], vertical).cpu().numpy()
+                ref = oracle_f64.evsm_blur_pass(m, radii[0], radii[1], vertical, dtype=np.float32)
+                assert ref.dtype == np.float32
+                np.testing.assert_array_equal(one.view(np.uint32), ref.view(np.uint32), err_msg=f"{h}x{w} radii {radii} vertical {vertical}")
 
 
 def test_full_size_properties(ctx):
