@@ -775,8 +775,8 @@ SAILOR_HIP_API int sailor_hip_hbao_chain(SailorHipContext* ctx, const SailorUboF
  * of a w x h target has the quad's inTexcoord ((i + 0.5) / w, (j + 0.5) / h); alpha is stored as 0.  The arithmetic is fixed operation by
  * operation (sailor_amd/csrc/sky.hip's header lists the decisions; tests/sky_ref.py restates it in NumPy float32): every branch is decided by
  * geometry evaluated in fp32 exactly as written, exp is the fixed algorithm of canonical_math.h with its argument clamp, and only the sums over
- * the 127 view steps are reassociated.  Not drawn: the cloud march ({CLOUDS}), Stars.shader, SunShafts.shader -- the entry points behave as
- * the reference does with m_cloudsDensity == 0 (SkyNode.cpp:604-609).
+ * the 127 view steps are reassociated.  Not drawn: Stars.shader, SunShafts.shader.  These five entry points behave as the reference does with
+ * m_cloudsDensity == 0 (SkyNode.cpp:604-609); the clouds have entry points of their own below.
  * All of them record only (no synchronisation, capturable). */
 
 /* Sky.shader:116-136 PostProcessDataUBO == SkyNode::SkyParams (SkyNode.h:48-67), std140: a vec4 at 0, then 4-byte scalars at 16, 20, .. 80.  84 bytes. */
@@ -812,7 +812,7 @@ SAILOR_HIP_API int sailor_hip_sky_fill(SailorHipContext* ctx, const SailorUboFra
 SAILOR_HIP_API int sailor_hip_sky_env_face(SailorHipContext* ctx, const float* cameraPosition3, const SailorSkyParams* params,
                                            float* dCube, int32_t size, int32_t face);
 /* Replaces: the draw "Sun" (SkyNode.cpp:611-642), define SUN = Sky.shader:693-715 with the SUN branches of SkyLighting (:309-316, :360-374).
- *   dClouds : `cloudsSampler` (:710).  NULL = the cleared m_pCloudsTexture, alpha 0; a plane is SAILOR_HIP_ERR_UNSUPPORTED until the cloud march exists
+ *   dClouds : `cloudsSampler` (:710).  NULL = the cleared m_pCloudsTexture, alpha 0; a plane is SAILOR_HIP_ERR_UNSUPPORTED here: sailor_hip_sky_sun_clouds takes it
  *   dSun    : device out, height x width float4 (the node: 32 x 32) */
 SAILOR_HIP_API int sailor_hip_sky_sun(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSkyParams* params,
                                       const float* dClouds, int32_t cloudsWidth, int32_t cloudsHeight, float* dSun, int32_t width, int32_t height);
@@ -826,6 +826,36 @@ SAILOR_HIP_API int sailor_hip_sky_compose(SailorHipContext* ctx, const SailorUbo
  * sailor_hip_generate_mipmaps_cube (:800-801).  Every argument is checked before the first launch. */
 SAILOR_HIP_API int sailor_hip_sky_env_cubemap(SailorHipContext* ctx, const float* cameraPosition3, const SailorSkyParams* params,
                                               float* dCube, int32_t size, int32_t levels);
+
+/* ---- Sky, the clouds: what SkyNode::Process adds with m_cloudsDensity > 0 (SkyNode.cpp:565-731) -------------------------------------------------
+ * sailor_amd/csrc/sky_clouds.hip's header lists the decisions; tests/clouds_ref.py restates the three kernels in NumPy float32 and they are held to
+ * it bit for bit.  All planes 16-byte aligned; all entry points record only (no synchronisation, capturable); a refused call records nothing. */
+
+/* Replaces: the draw "Clouds" (SkyNode.cpp:565-603), define CLOUDS = Sky.shader:386-595, :656-692, without DITHER and DISCARD_BY_DEPTH.
+ *   frame  : currentTime, cameraZNearZFar, view, invProjection and cameraPosition are read;  params : scatteringSteps outside 0 .. 10 is refused
+ *   dSky   : `skySampler`, the plane of sailor_hip_sky_fill, bilinear Repeat
+ *   dWeatherMap : `cloudsMapSampler`, mapHeight x mapWidth RGBA8 texels (r first), bilinear Repeat
+ *   dNoiseLow / dNoiseHigh : `cloudsNoiseLowSampler` / `cloudsNoiseHighSampler`, size^3 R8_UNORM bytes, x fastest, trilinear Repeat, base level only
+ *   dNoise : `g_noiseSampler`, noiseHeight x noiseWidth decoded linear float4 texels (the plane the HBAO entry points take), nearest Repeat
+ *   dLinearDepth : `linearDepth`, depthHeight x depthWidth floats, nearest
+ *   dClouds: device out, height x width float4 (the node: min(w, h) / 2 squared); alpha = 1 - transmittance; ROW height - 1 IS THE TOP OF THE VIEW */
+SAILOR_HIP_API int sailor_hip_sky_clouds(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSkyParams* params,
+                                         const float* dSky, int32_t skyWidth, int32_t skyHeight,
+                                         const uint8_t* dWeatherMap, int32_t mapWidth, int32_t mapHeight,
+                                         const uint8_t* dNoiseLow, int32_t lowSize, const uint8_t* dNoiseHigh, int32_t highSize,
+                                         const float* dNoise, int32_t noiseWidth, int32_t noiseHeight,
+                                         const float* dLinearDepth, int32_t depthWidth, int32_t depthHeight,
+                                         float* dClouds, int32_t width, int32_t height);
+/* sailor_hip_sky_sun with `cloudsSampler` honoured (Sky.shader:707-715): where the bilinear clamp-to-edge fetch of the clouds' alpha at uvView.xy is
+ * >= 0.5 (or NaN: uvView divides by its own w) the texel stays (0, 0, 0, 0); elsewhere it holds the bits of sailor_hip_sky_sun.
+ * frame->projection is read as well. */
+SAILOR_HIP_API int sailor_hip_sky_sun_clouds(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSkyParams* params,
+                                             const float* dClouds, int32_t cloudsWidth, int32_t cloudsHeight, float* dSun, int32_t width, int32_t height);
+/* Replaces: the draw "Blit Clouds" (SkyNode.cpp:722-731): Blit.shader (bilinear clamp-to-edge, no y flip) under EBlendMode::AlphaBlending
+ * (VulkanPipileneStates.cpp:245-246): rgb = src.rgb * src.a + dst.rgb * (1 - src.a), a = src.a * src.a - dst.a * (1 - src.a), in place.
+ *   dTarget : device in/out, float4 per pixel of the width x height target, the rows of `band` only (first row = band->fbRowBegin) */
+SAILOR_HIP_API int sailor_hip_sky_blit_clouds(SailorHipContext* ctx, const float* dClouds, int32_t cloudsWidth, int32_t cloudsHeight,
+                                              float* dTarget, int32_t width, int32_t height, const SailorBand* band);
 
 /* ---- Bloom (round 9): the Bloom node, FrameGraph/BloomNode.cpp:21-144 -- the mip pyramid over `Main`, rewritten in place ----------------------
  * tests/golden/DefaultRenderer.renderer:296-304.  `Main` is a level-major chain of RGBA32F planes (level l = max(1, width >> l) x max(1, height >> l),
@@ -944,6 +974,9 @@ SAILOR_HIP_API int sailor_host_sky_params_default(SailorSkyParams* outParams);
 /* FrameGraph/SkyNode.cpp:487-495: the view matrix of cube face 0..5 (glm::rotate about Math::vec3_Up / vec3_Right), PerspectiveRH(radians(90), 1,
  * 0.1, 1000) and its inverse, as the node writes them into the faces' frame data (:502-508) */
 SAILOR_HIP_API int sailor_host_sky_face_matrices(int32_t face, float* outView16, float* outProjection16, float* outInvProjection16);
+/* Sky.shader:247-264 CalculateSunColor(sunDirection) in fp32 (pow(x, 0.5) = sqrt, pow(x, 3) = (x x) x): the colour the cloud march multiplies in, which
+ * does not vary per texel.  The march passes -dirToSun = normalize(lightDirection.xyz). */
+SAILOR_HIP_API int sailor_host_sky_sun_color(const float* sunDirection3, float* outColor3);
 
 /* FrameGraph/BloomNode.cpp:89-93: PushConstantsDownscale::m_threshold = (threshold, threshold - knee, 2 knee, 0.25 knee) -- as the node writes it: the
  * shader's comment expects knee * 0.25 to be a quotient's denominator; restated, not repaired */

@@ -260,6 +260,11 @@ SIGNATURES = {
     "sailor_hip_sky_compose": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(SkyParams), _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P,
                                          C.c_int32, C.c_int32, C.POINTER(Band)]),
     "sailor_hip_sky_env_cubemap": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(SkyParams), _P, C.c_int32, C.c_int32]),
+    "sailor_hip_sky_clouds": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(SkyParams), _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int32,
+                                        _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32]),
+    "sailor_hip_sky_sun_clouds": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(SkyParams), _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32]),
+    "sailor_hip_sky_blit_clouds": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.POINTER(Band)]),
+    "sailor_host_sky_sun_color": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "sailor_host_sky_params_default": (C.c_int, [C.POINTER(SkyParams)]),
     "sailor_host_sky_face_matrices": (C.c_int, [C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "sailor_hip_mip_chain_texels": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),

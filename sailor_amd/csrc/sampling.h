@@ -73,3 +73,50 @@ __device__ __forceinline__ float4 cube_sample_lod(const float4* __restrict__ cub
     return make_float4(a.x * (1.0f - f) + b.x * f, a.y * (1.0f - f) + b.y * f, a.z * (1.0f - f) + b.z * f, a.w * (1.0f - f) + b.w * f);
 }
 
+// ---- Repeat addressing and byte texels (sky_clouds.hip): the cloud march's weather map and noise volumes ---------------------------------------
+// A tap index is wrapped into [0, n) AFTER the saturating conversion: i % n lies in (-n, n), so neither the + n nor the + 1 of the second tap can
+// wrap an int, whatever the coordinate was (NaN -> 0, +-inf -> INT_MAX / INT_MIN).  The weights of a non-finite coordinate are NaN, the sample NaN.
+__device__ __forceinline__ int wrap_tap(int i, int n) { return ((i % n) + n) % n; }
+__device__ __forceinline__ int wrap_next(int i0, int n) { return i0 + 1 == n ? 0 : i0 + 1; }
+__device__ __forceinline__ float unorm8(uint32_t byte) { return (float)byte / 255.0f; }
+
+struct RepeatTap { int i0, i1; float a; };
+__device__ __forceinline__ RepeatTap repeat_tap(int n, float u)
+{
+    RepeatTap t;
+    const float x = u * (float)n - 0.5f, fx = floorf(x);
+    t.a = x - fx;
+    t.i0 = wrap_tap((int)fx, n);
+    t.i1 = wrap_next(t.i0, n);
+    return t;
+}
+
+// sampler3D over an n^3 R8_UNORM volume, x fastest, base level, trilinear, Repeat: the x pairs first, then y (lerp2), then z
+__device__ __forceinline__ float trilinear_repeat_r8(const uint8_t* __restrict__ vol, int n, float u, float v, float w)
+{
+    const RepeatTap X = repeat_tap(n, u), Y = repeat_tap(n, v), Z = repeat_tap(n, w);
+    const uint8_t* __restrict__ z0 = vol + (size_t)Z.i0 * n * n;
+    const uint8_t* __restrict__ z1 = vol + (size_t)Z.i1 * n * n;
+    const int r0 = Y.i0 * n, r1 = Y.i1 * n;
+    const float lo = lerp2(unorm8(z0[r0 + X.i0]), unorm8(z0[r0 + X.i1]), unorm8(z0[r1 + X.i0]), unorm8(z0[r1 + X.i1]), X.a, Y.a);
+    const float hi = lerp2(unorm8(z1[r0 + X.i0]), unorm8(z1[r0 + X.i1]), unorm8(z1[r1 + X.i0]), unorm8(z1[r1 + X.i1]), X.a, Y.a);
+    return lo * (1.0f - Z.a) + hi * Z.a;
+}
+
+// sampler2D over a W x H RGBA8 image (one uint32 per texel, r in the low byte), bilinear, Repeat
+__device__ __forceinline__ float4 bilinear_repeat_rgba8(const uint32_t* __restrict__ tex, int W, int H, float u, float v)
+{
+    const RepeatTap X = repeat_tap(W, u), Y = repeat_tap(H, v);
+    const uint32_t a = tex[Y.i0 * W + X.i0], c = tex[Y.i0 * W + X.i1], d = tex[Y.i1 * W + X.i0], e = tex[Y.i1 * W + X.i1];
+    float4 r;
+    r.x = lerp2(unorm8(a & 255u), unorm8(c & 255u), unorm8(d & 255u), unorm8(e & 255u), X.a, Y.a);
+    r.y = lerp2(unorm8((a >> 8) & 255u), unorm8((c >> 8) & 255u), unorm8((d >> 8) & 255u), unorm8((e >> 8) & 255u), X.a, Y.a);
+    r.z = lerp2(unorm8((a >> 16) & 255u), unorm8((c >> 16) & 255u), unorm8((d >> 16) & 255u), unorm8((e >> 16) & 255u), X.a, Y.a);
+    r.w = lerp2(unorm8(a >> 24), unorm8(c >> 24), unorm8(d >> 24), unorm8(e >> 24), X.a, Y.a);
+    return r;
+}
+
+// nearest tap of a Repeat sampler: texel floor(u * n) mod n
+__device__ __forceinline__ int nearest_repeat(int n, float u) { return wrap_tap((int)floorf(u * (float)n), n); }
+// nearest tap of a clamp-to-edge sampler
+__device__ __forceinline__ int nearest_clamp(int n, float u) { return min(max((int)floorf(u * (float)n), 0), n - 1); }

@@ -398,6 +398,44 @@ def sky_compose(ctx: "HipContext", frame: UboFrameData, params, sky: torch.Tenso
     return out
 
 
+def sky_clouds(ctx: "HipContext", frame: UboFrameData, params, sky: torch.Tensor, weather: torch.Tensor, noise_low: torch.Tensor, noise_high: torch.Tensor,
+               noise: torch.Tensor, linear_depth: torch.Tensor, width: int, height: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Sky.shader {CLOUDS} (SkyNode.cpp:565-603): the cloud march -> float32 [height, width, 4], alpha = 1 - transmittance, row height - 1 = the top of
+    the view.  weather: uint8 [h, w, 4]; noise_low / noise_high: uint8 [n, n, n] (z, y, x); noise: float32 [h, w, 4]; linear_depth: float32 [h, w]"""
+    for t, dt, dims in ((sky, torch.float32, 3), (weather, torch.uint8, 3), (noise_low, torch.uint8, 3), (noise_high, torch.uint8, 3), (noise, torch.float32, 3),
+                        (linear_depth, torch.float32, 2)):
+        assert t.dtype == dt and t.is_contiguous() and t.dim() == dims, (t.dtype, tuple(t.shape))
+    assert sky.shape[2] == 4 and weather.shape[2] == 4 and noise.shape[2] == 4
+    assert len(set(noise_low.shape)) == 1 and len(set(noise_high.shape)) == 1, "the noise volumes are cubes"
+    if out is None:
+        out = torch.empty((height, width, 4), dtype=torch.float32, device=ctx.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (height, width, 4), tuple(out.shape)
+    _lib.check(ctx._lib.sailor_hip_sky_clouds(ctx.handle, C.byref(frame), C.byref(params), _ptr(sky), sky.shape[1], sky.shape[0], _ptr(weather), weather.shape[1],
+                                              weather.shape[0], _ptr(noise_low), noise_low.shape[0], _ptr(noise_high), noise_high.shape[0], _ptr(noise),
+                                              noise.shape[1], noise.shape[0], _ptr(linear_depth), linear_depth.shape[1], linear_depth.shape[0], _ptr(out), width,
+                                              height), "sailor_hip_sky_clouds", ctx.handle)
+    return out
+
+
+def sky_sun_clouds(ctx: "HipContext", frame: UboFrameData, params, clouds: torch.Tensor, size: int = _lib.SKY_SUN_RESOLUTION) -> torch.Tensor:
+    """Sky.shader {SUN} behind the clouds plane (Sky.shader:707-715): zero where the clouds' alpha is >= 0.5 -> float32 [size, size, 4]"""
+    assert clouds.dtype == torch.float32 and clouds.is_contiguous() and clouds.dim() == 3 and clouds.shape[2] == 4, (clouds.dtype, tuple(clouds.shape))
+    out = torch.empty((size, size, 4), dtype=torch.float32, device=ctx.device)
+    _lib.check(ctx._lib.sailor_hip_sky_sun_clouds(ctx.handle, C.byref(frame), C.byref(params), _ptr(clouds), clouds.shape[1], clouds.shape[0], _ptr(out), size,
+                                                  size), "sailor_hip_sky_sun_clouds", ctx.handle)
+    return out
+
+
+def sky_blit_clouds(ctx: "HipContext", clouds: torch.Tensor, target: torch.Tensor, width: int, height: int, band: Band | None = None) -> torch.Tensor:
+    """"Blit Clouds" (SkyNode.cpp:722-731): the clouds plane alpha-blended over the rows of `band` of the target, in place; returns `target`"""
+    band = band or host.band_whole_frame(width, height)
+    assert clouds.dtype == torch.float32 and clouds.is_contiguous() and clouds.dim() == 3 and clouds.shape[2] == 4, (clouds.dtype, tuple(clouds.shape))
+    assert target.dtype == torch.float32 and target.is_contiguous() and tuple(target.shape) == (band.fbRowCount, width, 4), tuple(target.shape)
+    _lib.check(ctx._lib.sailor_hip_sky_blit_clouds(ctx.handle, _ptr(clouds), clouds.shape[1], clouds.shape[0], _ptr(target), width, height, C.byref(band)),
+               "sailor_hip_sky_blit_clouds", ctx.handle)
+    return target
+
+
 def sky_env_face(ctx: "HipContext", camera_position, params, chain: torch.Tensor, size: int, face: int) -> torch.Tensor:
     """one face of g_skyCubemap's level 0 (SkyNode.cpp:764-797), written into the flat RGBA32F chain"""
     cam = np.ascontiguousarray(camera_position, dtype=np.float32).reshape(-1)[:3].copy()

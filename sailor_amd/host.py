@@ -134,6 +134,13 @@ def sky_params(**overrides) -> "_lib.SkyParams":
     return p
 
 
+def sky_sun_color(sun_direction) -> np.ndarray:
+    """Sky.shader:247-264 CalculateSunColor(sunDirection) in fp32; the cloud march passes -dirToSun"""
+    d, out = _f32(sun_direction, 3), np.empty(3, np.float32)
+    _lib.check(_lib.load().sailor_host_sky_sun_color(_fp(d), _fp(out)), "sailor_host_sky_sun_color")
+    return out
+
+
 def sky_face_matrices(face: int):
     """SkyNode.cpp:487-508: (view, projection, invProjection) of cube face 0..5, column-major float32[16] each"""
     v, p, ip = (np.empty(16, np.float32) for _ in range(3))

@@ -590,7 +590,7 @@ void SkyNode::Process(RHIFrameGraphPtr frameGraph, RHICommandListPtr transferCom
     if (!m_pSunShaftsShader) m_pSunShaftsShader = driver->CreateShader("Shaders/SunShafts.shader"); // (:234-242)
     if (!m_pBlitShader) m_pBlitShader = driver->CreateShader("Shaders/Blit.shader");                // (:244-252)
     if (!m_pStarsShader) m_pStarsShader = driver->CreateShader("Shaders/Stars.shader");             // (:341-349)
-    // (:254-339 the CloudsMap texture and the two noise volumes belong to the cloud march: not created)
+    // (:254-339 the CloudsMap texture and the two noise volumes are not loaded or generated here: SetCloudTextures publishes them, or the node stays cloudless)
 
     if (!m_pSkyTexture) m_pSkyTexture = driver->CreateRenderTarget({ (int32_t)SkyResolution, (int32_t)SkyResolution }, 1, EFormat::R32G32B32A32_SFLOAT); // (:351-363)
     if (!m_pSunTexture) m_pSunTexture = driver->CreateRenderTarget({ (int32_t)SunResolution, (int32_t)SunResolution }, 1, EFormat::R32G32B32A32_SFLOAT); // (:365-377)
@@ -598,8 +598,8 @@ void SkyNode::Process(RHIFrameGraphPtr frameGraph, RHICommandListPtr transferCom
         const float size = std::min(frameGraph->GetViewport().x * CloudsResolutionFactor, frameGraph->GetViewport().y * CloudsResolutionFactor);
         m_pCloudsTexture = driver->CreateRenderTarget({ std::max((int32_t)size, 1), std::max((int32_t)size, 1) }, 1, EFormat::R32G32B32A32_SFLOAT);
     }
-    // (:405-417) the reference waits for all eight shaders and the star mesh; the four permutations this backend draws are what the node waits for here,
-    // the others stay "not ready" for good and their draws below are left out
+    // (:405-417) the reference waits for all eight shaders and the star mesh; the four permutations this backend always draws are what the node waits for
+    // here, the clouds and the blit are looked at where they are drawn, the others stay "not ready" for good and their draws below are left out
     if (!m_pSkyShader->IsReady() || !m_pSkyEnvShader->IsReady() || !m_pSunShader->IsReady() || !m_pComposeShader->IsReady() || !m_pSkyTexture || !m_pSunTexture ||
         !m_pCloudsTexture) {
         commands->EndDebugRegion(commandList);
@@ -622,6 +622,14 @@ void SkyNode::Process(RHIFrameGraphPtr frameGraph, RHICommandListPtr transferCom
         m_pCloudsMaterial = driver->CreateMaterial(m_pCloudsShader);
         m_pSunShaftsMaterial = driver->CreateMaterial(m_pSunShaftsShader);
     }
+    if (HasCloudTextures() && m_bCloudTexturesChanged) { // (:431-433) every time the caller publishes textures: the set must not keep the earlier, caller-owned ones
+        driver->AddSamplerToShaderBindings(m_pShaderBindings, "cloudsMapSampler", m_pCloudsMapTexture, 3);
+        driver->AddSamplerToShaderBindings(m_pShaderBindings, "cloudsNoiseLowSampler", m_pCloudsNoiseLowTexture, 4);
+        driver->AddSamplerToShaderBindings(m_pShaderBindings, "cloudsNoiseHighSampler", m_pCloudsNoiseHighTexture, 5);
+        m_bCloudTexturesChanged = false;
+    }
+    if (HasCloudTextures() && !m_pShaderBindings->Find("g_noiseSampler")) // (:439-440) looked for on every frame until the graph has it
+        if (auto noise = frameGraph->GetSampler("g_noiseSampler")) driver->AddSamplerToShaderBindings(m_pShaderBindings, "g_noiseSampler", noise, 8);
     if (auto binding = m_pShaderBindings->Find("data")) // (:458-467) every frame
         commands->UpdateShaderBinding(transferCommandList, binding, &m_skyParams, sizeof(SkyParams));
     if (!m_pBlitCloudsMaterial) { // (:469-483)
@@ -629,6 +637,7 @@ void SkyNode::Process(RHIFrameGraphPtr frameGraph, RHICommandListPtr transferCom
         driver->FillShadersLayout(m_pBlitCloudsBindings, { m_pBlitShader }, 1);
         driver->AddSamplerToShaderBindings(m_pBlitCloudsBindings, "colorSampler", m_pCloudsTexture, 0);
         m_pBlitCloudsMaterial = driver->CreateMaterial(m_pBlitShader);
+        m_pBlitCloudsMaterial->m_blendMode = EBlendMode::AlphaBlending; // RenderState { .., EBlendMode::AlphaBlending, .. } (:476)
     }
     if (!m_pEnvCubemapBindings[0]) { // (:485-515) the six faces' frame data, with the camera position of the frame that creates them
         for (uint32_t face = 0; face < 6; face++) {
@@ -663,7 +672,9 @@ void SkyNode::Process(RHIFrameGraphPtr frameGraph, RHICommandListPtr transferCom
         commands->EndDebugRegion(commandList);
     };
     fullScreenDraw("Sky", m_pSkyTexture, m_pSkyMaterial, { sceneView.m_frameBindings, m_pShaderBindings }); // (:536-563)
-    if (m_skyParams.cloudsDensity > 0.0f && m_pCloudsShader->IsReady()) { // (:565-603) never ready here: the else branch, whatever the parameter says
+    // (:565-603) without published cloud textures: the else branch, whatever the parameter says
+    const bool bClouds = m_skyParams.cloudsDensity > 0.0f && m_pCloudsShader->IsReady() && HasCloudTextures();
+    if (bClouds) {
         commands->PushConstants(commandList, m_pCloudsMaterial, sizeof(uint32_t), &m_ditherPatternIndex);
         fullScreenDraw("Clouds", m_pCloudsTexture, m_pCloudsMaterial, { sceneView.m_frameBindings, m_pShaderBindings });
     } else { // (:604-609)
@@ -672,9 +683,11 @@ void SkyNode::Process(RHIFrameGraphPtr frameGraph, RHICommandListPtr transferCom
     }
     fullScreenDraw("Sun", m_pSunTexture, m_pSunMaterial, { sceneView.m_frameBindings, m_pShaderBindings });     // (:611-642)
     fullScreenDraw("Compose", target, m_pComposeMaterial, { sceneView.m_frameBindings, m_pShaderBindings });    // (:644-680)
-    // (:682-747) "Stars & Clouds": the star points, the alpha-blended clouds blit and the sun-shaft multiply -- no entry point, nothing recorded
+    // (:682-747) "Stars & Clouds": the star points and the sun-shaft multiply -- no entry point, nothing recorded.  The alpha-blended clouds blit is drawn
+    // when the clouds were: over the cleared plane (alpha 0) the reference's blit leaves every colour and turns alpha a into 0 - a, which for the target's
+    // alpha of +0 is +0 again -- leaving it out keeps the cloudless frame's record what it was
     if (m_pStarsShader->IsReady()) fullScreenDraw("Stars", target, m_pStarsMaterial, { sceneView.m_frameBindings, m_pShaderBindings });
-    if (m_pBlitShader->IsReady()) fullScreenDraw("Blit Clouds", target, m_pBlitCloudsMaterial, { sceneView.m_frameBindings, m_pBlitCloudsBindings });
+    if (bClouds && m_pBlitShader->IsReady()) fullScreenDraw("Blit Clouds", target, m_pBlitCloudsMaterial, { sceneView.m_frameBindings, m_pBlitCloudsBindings });
     if (m_pSunShaftsShader->IsReady()) fullScreenDraw("Sun Shafts", target, m_pSunShaftsMaterial, { sceneView.m_frameBindings, m_pShaderBindings });
 
     if (m_bIsDirty) { // (:749-818)

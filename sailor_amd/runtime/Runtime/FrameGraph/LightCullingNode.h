@@ -157,9 +157,10 @@ protected:
 };
 
 // The atmosphere, the sun disk and g_skyCubemap: Runtime/FrameGraph/SkyNode.h.  Resources (DefaultRenderer.renderer:145-149): "color" = the Sky target,
-// "linearDepth".  Drawn: Sky.shader {FILL}, {SUN}, {COMPOSE} every frame and {} into one face of g_skyCubemap per frame while dirty.  Created and never
-// recorded (the backend has no entry point: IsReady() is false): Sky.shader {CLOUDS}, Stars.shader, SunShafts.shader and the alpha-blended Blit.shader
-// draw -- the node always takes the m_cloudsDensity == 0 branch (SkyNode.cpp:604-609) and has no star mesh, noise volumes or CloudsMap texture.
+// "linearDepth".  Drawn: Sky.shader {FILL}, {SUN}, {COMPOSE} every frame and {} into one face of g_skyCubemap per frame while dirty; with the cloud
+// textures published (SetCloudTextures) and m_cloudsDensity > 0 also Sky.shader {CLOUDS} and the alpha-blended Blit.shader draw "Blit Clouds", otherwise
+// the m_cloudsDensity == 0 branch (SkyNode.cpp:604-609).  Created and never recorded (the backend has no entry point: IsReady() is false):
+// Stars.shader and SunShafts.shader -- the node has no star mesh, and it neither loads CloudsMap.png nor generates the noise volumes.
 class SkyNode : public TFrameGraphNode<SkyNode> {
 public:
     static constexpr uint32_t EnvCubemapSize = 256u;      // SkyNode.h:13
@@ -180,6 +181,14 @@ public:
     SkyParams& GetSkyParams() { return m_skyParams; }                       // SkyNode.h:106
     uint32_t GetUpdateEnvCubemapPattern() const { return m_updateEnvCubemapPattern; } // (not in the reference: read-back for the tests)
     bool IsDirty() const { return m_bIsDirty; }
+    // The clouds are opt-in (as the Bloom node is, FrameGraphNode.h): the reference loads Textures/CloudsMap.png and loads or generates the two noise
+    // volumes itself (SkyNode.cpp:254-339); here the caller publishes the three textures, and until it has, the node records what it recorded without them
+    void SetCloudTextures(RHI::RHITexturePtr map, RHI::RHITexturePtr noiseLow, RHI::RHITexturePtr noiseHigh)
+    {
+        m_pCloudsMapTexture = std::move(map); m_pCloudsNoiseLowTexture = std::move(noiseLow); m_pCloudsNoiseHighTexture = std::move(noiseHigh);
+        m_bCloudTexturesChanged = true; // Process re-points bindings 3, 4 and 5 at them
+    }
+    bool HasCloudTextures() const { return m_pCloudsMapTexture && m_pCloudsNoiseLowTexture && m_pCloudsNoiseHighTexture; }
 
 protected:
     static const char* m_name;
@@ -188,10 +197,11 @@ protected:
     RHI::RHIMaterialPtr m_pStarsMaterial, m_pSkyMaterial, m_pSkyEnvMaterial, m_pSunMaterial, m_pComposeMaterial, m_pCloudsMaterial, m_pSunShaftsMaterial,
         m_pBlitCloudsMaterial;
     RHI::RHIShaderBindingSetPtr m_pShaderBindings, m_pBlitCloudsBindings, m_pEnvCubemapBindings[6];
-    RHI::RHITexturePtr m_pSkyTexture, m_pSunTexture, m_pCloudsTexture;
+    RHI::RHITexturePtr m_pSkyTexture, m_pSunTexture, m_pCloudsTexture, m_pCloudsMapTexture, m_pCloudsNoiseLowTexture, m_pCloudsNoiseHighTexture;
     uint32_t m_ditherPatternIndex = 0;
     uint32_t m_updateEnvCubemapPattern = 0; // SkyNode.h:173
     bool m_bIsDirty = true;                 // SkyNode.h:174
+    bool m_bCloudTexturesChanged = false;
 };
 
 // The mip pyramid over `Main`: Runtime/FrameGraph/BloomNode.h.  Resource (DefaultRenderer.renderer:303-304): "bloom" = the HDR target with its mip chain,

@@ -86,17 +86,22 @@ RHIShaderPtr HipGraphicsDriver::CreateShader(const std::string& assetPath, const
         "Shaders/ComputeDepthHighZ.shader", "Shaders/ComputeHistogram.shader", "Shaders/ComputeAverageLuminance.shader", "Shaders/ComputeBrdfLut.shader",
         "Shaders/ComputeIrradianceMap.shader", "Shaders/ComputeEnvMap_IBL.shader", "Shaders/ShadowCaster.shader", "Shaders/LinearizeDepth.shader",
         "Shaders/Tonemapping.shader", "Shaders/Blur.shader", "Shaders/HBAO.shader", "Shaders/HBAO_Blur.shader", "Shaders/Sky.shader", "Shaders/ComputeBloomDownscale.shader",
-        "Shaders/ComputeBloomUpscale.shader" };
+        "Shaders/ComputeBloomUpscale.shader", "Shaders/Blit.shader" };
     auto shader = RHIShaderPtr::Make(assetPath, defines);
     shader->m_bIsReady = false;
     for (const char* name : routed) if (assetPath == name) shader->m_bIsReady = true;
-    // Sky.shader is routed by its define set: {FILL}, {}, {SUN}, {COMPOSE} have entry points, any other permutation ({CLOUDS}, ...) has none
+    // Sky.shader is routed by its define set: {FILL}, {}, {SUN}, {COMPOSE}, {CLOUDS} have entry points, any other permutation (DITHER, ...) has none.
+    // Blit.shader is routed for the one material that draws with it, SkyNode's "Blit Clouds" under AlphaBlending (DrawIndexed)
     if (assetPath == "Shaders/Sky.shader")
-        shader->m_bIsReady = defines.empty() || (defines.size() == 1 && (defines[0] == "FILL" || defines[0] == "SUN" || defines[0] == "COMPOSE"));
+        shader->m_bIsReady = defines.empty() ||
+                             (defines.size() == 1 && (defines[0] == "FILL" || defines[0] == "SUN" || defines[0] == "COMPOSE" || defines[0] == "CLOUDS"));
     return shader;
 }
 
-static size_t texel_size(EFormat f) { return f == EFormat::R16_SFLOAT ? 2 : (f == EFormat::R32_SFLOAT ? 4 : (f == EFormat::R32G32_SFLOAT ? 8 : 16)); }
+static size_t texel_size(EFormat f)
+{
+    return f == EFormat::R8_UNORM ? 1 : (f == EFormat::R16_SFLOAT ? 2 : (f == EFormat::R32_SFLOAT || f == EFormat::R8G8B8A8_UNORM ? 4 : (f == EFormat::R32G32_SFLOAT ? 8 : 16)));
+}
 
 RHITexturePtr HipGraphicsDriver::CreateTexture(const void* pData, size_t size, ivec2 extent, EFormat format)
 {
@@ -215,6 +220,7 @@ void HipGraphicsDriver::SubmitCommandList(RHICommandListPtr commandList)
 // cull's per-tile lists -- and the write must come behind the compaction that is still filling the buffer on the second queue.
 void HipGraphicsDriver::BeforeBufferWrite(const void* devicePtr)
 {
+    if (devicePtr && devicePtr == m_marchedClouds) m_marchedClouds = nullptr; // (the clear of SkyNode.cpp:604-609, or any other write: the SUN draw sees no clouds plane)
     if (devicePtr) m_rasterWorkspaces.erase(devicePtr); // (a depth attachment written by anything but caster draws: its coarse depth no longer bounds it)
     if (!devicePtr || (devicePtr != m_ownGrid && devicePtr != m_ownCulled)) return;
     if (m_packPending) { sailor_hip_context_wait_for(m_ctx, m_ctxAux); m_packPending = false; }
@@ -802,10 +808,14 @@ void HipGraphicsDriver::DrawIndexed(RHICommandListPtr cmd, uint32_t indexCount, 
     const uint32_t tonemapFlags = !shader ? 0u : (shader->HasDefine("ACES") ? SAILOR_TONEMAP_ACES : 0u) | (shader->HasDefine("UNCHARTED2") ? SAILOR_TONEMAP_UNCHARTED2 : 0u) |
                                                  (shader->HasDefine("LUMINANCE") ? SAILOR_TONEMAP_LUMINANCE : 0u);
     const bool evsm = shader && shader->HasDefine("EVSM"), vertical = shader && shader->HasDefine("VERTICAL"), horizontal = shader && shader->HasDefine("HORIZONTAL");
-    // Sky.shader's permutation: 0 {FILL}, 1 {}, 2 {SUN}, 3 {COMPOSE}, -1 anything else (CreateShader left those "not ready")
-    const int sky = (!shader || !shader->IsReady()) ? -1 : (shader->m_defines.empty() ? 1 : (shader->HasDefine("FILL") ? 0 : (shader->HasDefine("SUN") ? 2 : 3)));
-    cmd->m_hip.m_commands.push_back([this, name, bindings, target, fullScreenQuad, evsm, vertical, horizontal, tonemapFlags, sky]() {
+    // Sky.shader's permutation: 0 {FILL}, 1 {}, 2 {SUN}, 3 {COMPOSE}, 4 {CLOUDS}, -1 anything else (CreateShader left those "not ready")
+    const int sky = (!shader || !shader->IsReady()) ? -1
+                    : (shader->m_defines.empty() ? 1 : (shader->HasDefine("FILL") ? 0 : (shader->HasDefine("SUN") ? 2 : (shader->HasDefine("CLOUDS") ? 4 : 3))));
+    const bool alphaBlending = cmd->m_boundMaterial && cmd->m_boundMaterial->m_blendMode == EBlendMode::AlphaBlending;
+    cmd->m_hip.m_commands.push_back([this, name, bindings, target, fullScreenQuad, evsm, vertical, horizontal, tonemapFlags, sky, alphaBlending]() {
+        if (fullScreenQuad && name == "Shaders/Sky.shader" && sky == 4) return RecordSkyClouds(bindings, target);
         if (fullScreenQuad && name == "Shaders/Sky.shader" && sky >= 0) return RecordSky(bindings, target, sky);
+        if (fullScreenQuad && name == "Shaders/Blit.shader" && alphaBlending) return RecordBlitAlphaBlended(bindings, target);
         if (fullScreenQuad && name == "Shaders/LinearizeDepth.shader") return RecordLinearizeDepth(bindings, target);
         if (fullScreenQuad && name == "Shaders/Tonemapping.shader") return RecordTonemap(bindings, target, tonemapFlags);
         if (fullScreenQuad && name == "Shaders/Blur.shader" && evsm && vertical != horizontal) return RecordEvsmBlur(bindings, target, vertical);
@@ -963,14 +973,68 @@ int HipGraphicsDriver::RecordSky(const TVector<RHIShaderBindingSetPtr>& bindings
         if (target->m_viewFace < 0 || target->m_viewLevel != 0 || !target->m_parent || target->GetExtent().x != target->GetExtent().y) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
         return sailor_hip_sky_env_face(m_ctx, frame.cameraPosition, &params, (float*)target->m_buffer->m_hip.m_devicePtr, target->GetExtent().x, target->m_viewFace);
     }
-    if (permutation == 2) // `cloudsSampler` is the node's cleared clouds target (SkyNode.cpp:604-609): alpha 0 everywhere = no plane
+    if (permutation == 2) {
+        // `cloudsSampler` after the clear (SkyNode.cpp:604-609) is alpha 0 everywhere = no plane; after the cloud march it is honoured (Sky.shader:707-715)
+        auto clouds = rgba_of("cloudsSampler");
+        if (clouds && m_marchedClouds && clouds->m_buffer->m_hip.m_devicePtr == m_marchedClouds)
+            return sailor_hip_sky_sun_clouds(m_ctx, &frame, &params, (const float*)texels_of(clouds), clouds->GetExtent().x, clouds->GetExtent().y,
+                                             (float*)texels_of(target), target->GetExtent().x, target->GetExtent().y);
         return sailor_hip_sky_sun(m_ctx, &frame, &params, nullptr, 0, 0, (float*)texels_of(target), target->GetExtent().x, target->GetExtent().y);
+    }
     auto sky = rgba_of("skySampler"), sun = rgba_of("sunSampler");
     if (!sky || !sun) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     SailorBand whole;
     if (sailor_hip_band_whole_frame(target->GetExtent().x, target->GetExtent().y, &whole) != SAILOR_HIP_OK) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     return sailor_hip_sky_compose(m_ctx, &frame, &params, (const float*)texels_of(sky), sky->GetExtent().x, sky->GetExtent().y, (const float*)texels_of(sun),
                                   sun->GetExtent().x, sun->GetExtent().y, (float*)texels_of(target), target->GetExtent().x, target->GetExtent().y, &whole);
+}
+
+// "Clouds" (SkyNode.cpp:565-603): Sky.shader under {CLOUDS}; set 1 by name: 1 `skySampler`, 3 `cloudsMapSampler`, 4 `cloudsNoiseLowSampler`,
+// 5 `cloudsNoiseHighSampler`, 8 `g_noiseSampler`, 9 `linearDepth` (Sky.shader:143-150).  A name that resolved to nothing is an invalid argument.  The push
+// constant (ditherPattern) belongs to the DITHER define, which the node comments out (SkyNode.cpp:230): not read.
+int HipGraphicsDriver::RecordSkyClouds(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& target)
+{
+    if (bindings.size() != 2 || !target || !target->m_buffer || target->m_format != EFormat::R32G32B32A32_SFLOAT) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    auto frameB = bindings[0]->Find("frameData");
+    auto dataB = bindings[1]->Find("data");
+    if (!frameB || frameB->m_hostCopy.size() < sizeof(SailorUboFrameData) || !dataB || dataB->m_hostCopy.size() < sizeof(SailorSkyParams)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    auto bound = [&](const char* name, EFormat format) -> RHITexturePtr {
+        auto b = bindings[1]->Find(name);
+        if (!b || b->m_textures.empty() || !b->m_textures[0] || !b->m_textures[0]->m_buffer || b->m_textures[0]->m_format != format) return RHITexturePtr();
+        return b->m_textures[0];
+    };
+    auto sky = bound("skySampler", EFormat::R32G32B32A32_SFLOAT), map = bound("cloudsMapSampler", EFormat::R8G8B8A8_UNORM);
+    auto low = bound("cloudsNoiseLowSampler", EFormat::R8_UNORM), high = bound("cloudsNoiseHighSampler", EFormat::R8_UNORM);
+    auto noise = bound("g_noiseSampler", EFormat::R32G32B32A32_SFLOAT), depth = bound("linearDepth", EFormat::R32_SFLOAT);
+    if (!sky || !map || !low || !high || !noise || !depth) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    for (const auto& v : { low, high })
+        if (v->GetExtent().x != v->GetExtent().y || v->m_depth != v->GetExtent().x) return SAILOR_HIP_ERR_INVALID_ARGUMENT; // cubes
+    SailorUboFrameData frame;
+    memcpy(&frame, frameB->m_hostCopy.data(), sizeof frame);
+    SailorSkyParams params;
+    memcpy(&params, dataB->m_hostCopy.data(), sizeof params);
+    BeforeBufferWrite(target->m_buffer->m_hip.m_devicePtr);
+    const int st = sailor_hip_sky_clouds(m_ctx, &frame, &params, (const float*)texels_of(sky), sky->GetExtent().x, sky->GetExtent().y, (const uint8_t*)texels_of(map),
+                                         map->GetExtent().x, map->GetExtent().y, (const uint8_t*)texels_of(low), low->GetExtent().x, (const uint8_t*)texels_of(high),
+                                         high->GetExtent().x, (const float*)texels_of(noise), noise->GetExtent().x, noise->GetExtent().y, (const float*)texels_of(depth),
+                                         depth->GetExtent().x, depth->GetExtent().y, (float*)texels_of(target), target->GetExtent().x, target->GetExtent().y);
+    if (st == SAILOR_HIP_OK) m_marchedClouds = target->m_buffer->m_hip.m_devicePtr; // until anything else writes the plane (BeforeBufferWrite)
+    return st;
+}
+
+// "Blit Clouds" (SkyNode.cpp:722-731): Blit.shader (set 1 binding 0 `colorSampler`) drawn over the bound attachment under EBlendMode::AlphaBlending
+int HipGraphicsDriver::RecordBlitAlphaBlended(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& target)
+{
+    if (bindings.size() != 2 || !target || !target->m_buffer || target->m_format != EFormat::R32G32B32A32_SFLOAT) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    auto srcB = bindings[1]->Find("colorSampler");
+    if (!srcB || srcB->m_textures.empty() || !srcB->m_textures[0] || !srcB->m_textures[0]->m_buffer) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    const auto& src = srcB->m_textures[0];
+    if (src->m_format != EFormat::R32G32B32A32_SFLOAT) return SAILOR_HIP_ERR_UNSUPPORTED;
+    SailorBand whole;
+    if (sailor_hip_band_whole_frame(target->GetExtent().x, target->GetExtent().y, &whole) != SAILOR_HIP_OK) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    BeforeBufferWrite(target->m_buffer->m_hip.m_devicePtr);
+    return sailor_hip_sky_blit_clouds(m_ctx, (const float*)texels_of(src), src->GetExtent().x, src->GetExtent().y, (float*)texels_of(target), target->GetExtent().x,
+                                      target->GetExtent().y, &whole);
 }
 
 int HipGraphicsDriver::RecordEvsmBlur(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& target, bool vertical)

@@ -21,9 +21,11 @@
 //   "Shaders/Blur.shader" {EVSM, HORIZONTAL | VERTICAL} -> sailor_hip_evsm_blur_pass (binding contract: Blur.shader:53-61)
 //   "Shaders/HBAO.shader"                -> sailor_hip_hbao              (binding contract: HBAO.shader:50-60)
 //   "Shaders/HBAO_Blur.shader" {VERTICAL | HORIZONTAL, exactly one} -> sailor_hip_hbao_blur_pass (binding contract: HBAO_Blur.shader:54-62)
-//   "Shaders/Sky.shader" by define set: {FILL} -> sailor_hip_sky_fill, {} (into a cube face view) -> sailor_hip_sky_env_face, {SUN} -> sailor_hip_sky_sun,
-//                                           {COMPOSE} -> sailor_hip_sky_compose (binding contract: Sky.shader:104-153); {CLOUDS} and every other permutation,
-//                                           "Shaders/Stars.shader", "Shaders/SunShafts.shader" and "Shaders/Blit.shader" are created "not ready" and never drawn
+//   "Shaders/Sky.shader" by define set: {FILL} -> sailor_hip_sky_fill, {} (into a cube face view) -> sailor_hip_sky_env_face, {SUN} -> sailor_hip_sky_sun
+//                                           (or sailor_hip_sky_sun_clouds once the cloud march has been recorded into `cloudsSampler`),
+//                                           {COMPOSE} -> sailor_hip_sky_compose, {CLOUDS} -> sailor_hip_sky_clouds (binding contract: Sky.shader:104-153);
+//                                           every other permutation, "Shaders/Stars.shader" and "Shaders/SunShafts.shader" are created "not ready", never drawn
+//   "Shaders/Blit.shader" of a material with EBlendMode::AlphaBlending ("Blit Clouds") -> sailor_hip_sky_blit_clouds (binding: `colorSampler`)
 // a scaled one-channel BlitImage with Nearest filtration -> sailor_hip_blit_nearest
 // and the depth-only instanced draws of the shadow passes (material of)
 //   "Shaders/ShadowCaster.shader" [EVSM]  -> sailor_hip_raster_depth into the pass' depth attachment, and at EndRenderPass sailor_hip_shadow_resolve
@@ -127,6 +129,8 @@ private:
     int RecordHbao(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target);
     int RecordHbaoBlur(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target, bool vertical);
     int RecordSky(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target, int permutation);
+    int RecordSkyClouds(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target);
+    int RecordBlitAlphaBlended(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target);
     int RecordBloomDownscale(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const TVector<uint8_t>& pc);
     int RecordBloomUpscale(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const TVector<uint8_t>& pc);
 
@@ -134,6 +138,9 @@ private:
     std::shared_ptr<SailorHipContext> m_ctxOwner;   // destroyed with the last buffer that still refers to it
     int m_status = 0;
     int m_lastDispatchStatus = 0;
+    // SkyNode's m_pCloudsTexture while the last thing recorded into it was the cloud march: the SUN draw that samples it (one material for the clear and the
+    // march, SkyNode.cpp:611-642) goes through sailor_hip_sky_sun_clouds then, through sailor_hip_sky_sun otherwise.  Reset by every write (BeforeBufferWrite)
+    const void* m_marchedClouds = nullptr;
     RHI::RHIBufferPtr m_cullWorkspace;
     RHI::RHIBufferPtr m_meshCullWorkspace;
     int32_t m_cullW = 0, m_cullH = 0, m_cullLights = 0; // geometry of the last light cull: locates its shading-order hint in the workspace

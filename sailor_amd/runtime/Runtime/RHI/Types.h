@@ -73,7 +73,8 @@ public:
 };
 using RHIBufferPtr = TRefPtr<RHIBuffer>;
 
-enum class EFormat { R32_SFLOAT, R16_SFLOAT, R32G32B32A32_SFLOAT, R32G32_SFLOAT };
+enum class EFormat { R32_SFLOAT, R16_SFLOAT, R32G32B32A32_SFLOAT, R32G32_SFLOAT, R8_UNORM, R8G8B8A8_UNORM }; // the 8-bit ones: SkyNode's weather map and noise volumes
+enum class EBlendMode { None, Additive, AlphaBlending, Multiply }; // RHI/Types.h EBlendMode; VulkanPipileneStates.cpp:236-254
 enum class ETextureFiltration { Nearest, Linear }; // RHI/Types.h ETextureFiltration (Bicubic has no user on the path)
 enum class EImageLayout { Undefined, ShaderReadOnlyOptimal, General, ColorAttachmentOptimal, ComputeWrite, TransferSrcOptimal, TransferDstOptimal };
 
@@ -96,6 +97,8 @@ public:
     // RHI::IsDepthFormat(GetFormat()) of the reference: the canonical fp32 plane of a D32_SFLOAT* / D16_UNORM* target remembers that it is one
     // (BlitNode.cpp:67,88 picks the blit's filtration by it)
     bool m_bDepthFormat = false;
+    // a volume (sampler3D, SkyNode.cpp:264-339): m_depth slices of m_extent, x fastest.  1 = a plain image
+    int32_t m_depth = 1;
     ivec2 GetExtent() const { return m_extent; }
     uint32_t GetMipLevels() const { return m_mipLevels; }
     TRefPtr<RHITexture> GetMipLevel(uint32_t mipLevel) const;
@@ -164,6 +167,9 @@ class RHIMaterial : public RHIResource {
 public:
     explicit RHIMaterial(RHIShaderPtr shader) : m_shader(std::move(shader)) {}
     RHIShaderPtr m_shader;
+    // RenderState::m_blendMode, the one member of the render state a full-screen pass executed as a kernel still needs: "Blit Clouds" is Blit.shader
+    // under AlphaBlending (SkyNode.cpp:476-480)
+    EBlendMode m_blendMode = EBlendMode::None;
 };
 using RHIMaterialPtr = TRefPtr<RHIMaterial>;
 

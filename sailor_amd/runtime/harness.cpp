@@ -428,6 +428,23 @@ RT_API int sailor_rt_sky_set_params(SailorRuntime* rt, const SailorSkyParams* pa
     return 0;
 }
 
+// The three textures of the cloud march, which the reference's node loads (Textures/CloudsMap.png) or loads-or-generates (CloudsNoiseLow.bin 128^3,
+// CloudsNoiseHigh.bin 32^3) itself (SkyNode.cpp:254-339): caller-owned device bytes here -- weather = mapHeight x mapWidth RGBA8, the volumes size^3 R8, x fastest.
+// With them published and cloudsDensity > 0 the node draws "Clouds", the sun behind them, "Compose" and "Blit Clouds"; it then needs "g_noiseSampler"
+// (sailor_rt_set_sampler) and its `linearDepth` attachment, and a frame without either returns -1 from sailor_rt_process_frame.
+RT_API int sailor_rt_sky_set_cloud_textures(SailorRuntime* rt, void* weather, int mapWidth, int mapHeight, void* noiseLow, int lowSize, void* noiseHigh, int highSize)
+{
+    auto* hip = static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver());
+    auto* sky = sky_node(rt);
+    if (!sky || !weather || !noiseLow || !noiseHigh || mapWidth <= 0 || mapHeight <= 0 || lowSize <= 0 || highSize <= 0) return -1;
+    auto map = hip->WrapTexture(weather, { mapWidth, mapHeight }, EFormat::R8G8B8A8_UNORM);
+    auto low = hip->WrapTexture(noiseLow, { lowSize, lowSize }, EFormat::R8_UNORM), high = hip->WrapTexture(noiseHigh, { highSize, highSize }, EFormat::R8_UNORM);
+    low->m_depth = lowSize; low->m_buffer->m_size = (size_t)lowSize * lowSize * lowSize;
+    high->m_depth = highSize; high->m_buffer->m_size = (size_t)highSize * highSize * highSize;
+    sky->SetCloudTextures(map, low, high);
+    return 0;
+}
+
 // m_updateEnvCubemapPattern and m_bIsDirty of the Sky node (SkyNode.h:173-174)
 RT_API int sailor_rt_sky_state(SailorRuntime* rt, int* outPattern, int* outDirty)
 {

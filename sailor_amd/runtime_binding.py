@@ -47,6 +47,7 @@ def load() -> C.CDLL:
         rt.sailor_rt_set_sky_cubemap.argtypes = [P, P, C.c_int, C.c_int, C.c_int, P, C.c_int, C.c_int]
         rt.sailor_rt_sky_set_params.argtypes = [P, P, C.c_int]
         rt.sailor_rt_sky_state.argtypes = [P, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        rt.sailor_rt_sky_set_cloud_textures.argtypes = [P, P, C.c_int, C.c_int, P, C.c_int, P, C.c_int]
         rt.sailor_rt_set_environment_map.argtypes = [P, P, C.c_int, C.c_int, C.c_int, C.c_int]
         rt.sailor_rt_sampler.restype = P
         rt.sailor_rt_sampler.argtypes = [P, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -181,6 +182,15 @@ class Runtime:
     def sky_set_params(self, params, mark_dirty: bool = False) -> int:
         """replace the Sky node's SkyParams (a _lib.SkyParams); mark_dirty restarts its time-sliced g_skyCubemap bake (SkyNode::MarkDirty)"""
         return self.rt.sailor_rt_sky_set_params(self.h, C.byref(params), 1 if mark_dirty else 0)
+
+    def sky_set_cloud_textures(self, weather, low, high) -> int:
+        """publish the cloud march's textures to the Sky node (caller-owned uint8 device tensors: weather [h, w, 4], the noise volumes [n, n, n], x fastest);
+        with them and cloudsDensity > 0 the node draws the clouds, the sun behind them and the clouds blit.  -1 if the graph has no Sky node"""
+        assert weather.dim() == 3 and weather.shape[2] == 4 and low.dim() == 3 and high.dim() == 3 and len(set(low.shape)) == 1 and len(set(high.shape)) == 1
+        for t in (weather, low, high):
+            assert t.is_contiguous() and t.element_size() == 1, (t.dtype, tuple(t.shape))
+        return self.rt.sailor_rt_sky_set_cloud_textures(self.h, weather.data_ptr(), weather.shape[1], weather.shape[0], low.data_ptr(), low.shape[0], high.data_ptr(),
+                                                        high.shape[0])
 
     def sky_state(self):
         """(m_updateEnvCubemapPattern, m_bIsDirty) of the Sky node; raises if the graph has none"""
