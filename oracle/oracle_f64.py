@@ -70,14 +70,192 @@ def _texture_bilinear(tex: np.ndarray, u, v):
     return top * (1.0 - ay) + bot * ay
 
 
-def select_cascade(view, world_pos, z_far):
-    """Lighting.glsl:200-216"""
-    p = world_pos @ view[:, :3].T + view[:, 3]
-    depth = np.abs(p[..., 2] / p[..., 3])
+def cascade_thresholds(z_far):
+    """zFar * shadowCascadeLevels[i] (Lighting.glsl:206-212).  Both factors are fp32 values that no pixel enters into -- the table's literals and a
+    uniform -- and ONE correctly rounded fp32 product has one possible result: the reference takes that float as the input it is (with the float64
+    product 20000 * 0.05f = 1000.0000149 a fragment at depth exactly 1000 would sit on the other side of a compare that every fp32 evaluation of
+    the shader decides the same way)."""
+    return (np.float32(z_far) * np.asarray(CASCADE_LEVELS, np.float32)).astype(np.float64)
+
+
+def select_cascade(view, world_pos, z_far, want_margin: bool = False):
+    """Lighting.glsl:200-216.  With want_margin also `decided`: the three compares that choose among cascades 0..3 (the fourth only separates 3 from
+    "beyond the last level", which Standard.shader clamps back to 3) are beyond fp32 rounding -- see the margin block below."""
+    thr = cascade_thresholds(z_far)
+    wp1 = np.concatenate([world_pos, np.ones(world_pos.shape[:-1] + (1,))], -1)
+    z, ez = _row_margin(view[2], wp1)
+    w, ew = _row_margin(view[3], wp1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        d, ed = _div_margin(z, ez, w, ew)
+    depth = np.abs(d)
     layer = np.full(depth.shape, 4, np.int64)
     for i in (3, 2, 1, 0):
-        layer = np.where(depth < z_far * CASCADE_LEVELS[i], i, layer)
-    return layer
+        layer = np.where(depth < thr[i], i, layer)
+    if not want_margin:
+        return layer
+    decided = np.ones(depth.shape, bool)
+    for i in (0, 1, 2):
+        decided &= _decided(depth - thr[i], ed)
+    return layer, decided
+
+
+# ---- conditioning of the shadow term's decisions (want_shadow_margin) --------------------------------------------------------------------------
+# Every compared quantity q of the shadow term is carried as (value, e): e bounds the error of a fp32 evaluation of the same expression in units of
+# 2^-24, to first order, as K * A -- K the number of fp32 roundings a term of the chain passes through as sailor_amd/csrc/shade_body.h writes it
+# (counted beside each expression below), A the expression with every term replaced by its absolute value -- chained through the later steps by
+# their derivatives.  A decision counts as decided when |q| > 2 * 2^-24 * e (K doubled), or when e is 0: every intermediate of the chain is itself a
+# float (checked on the float64 values, which are then exactly what fp32 arithmetic produces: a correctly rounded operation whose exact result is a
+# float returns it), so the fp32 compare IS this compare -- an exact tie included, which is the strict compare's false side in both.
+U24 = 2.0 ** -24
+
+
+def _is_float(v):
+    with np.errstate(over="ignore", invalid="ignore"):
+        return np.asarray(v, np.float64).astype(np.float32).astype(np.float64) == v
+
+
+def _rounded(v, e_in):
+    """e of a fp32 result whose float64 value is v and whose operands carry e_in (already multiplied by the operation's derivatives): one more
+    rounding of size |v|, unless the operands are exact and v is a float"""
+    return np.where((e_in == 0) & _is_float(v), 0.0, e_in + np.abs(v))
+
+
+def _decided(q, e):
+    return (e == 0) | (np.abs(q) > 2.0 * U24 * e)
+
+
+def _row_margin(m, wp1):
+    """one row of mat4 * vec4 in GLSL's order ((c0 x + c1 y) + c2 z) + c3 w -> (value, e).  Seven roundings, four products and three sums, but a term
+    only passes through its own product and the sums after it: K = 4, 4, 3, 2 for the four terms of A (the dot product's standard bound), one less
+    where the product is itself a float (an entry that is 0 or a power of two; w = 1).  0 where every product and partial sum is a float."""
+    t = m * wp1
+    s1 = t[..., 0] + t[..., 1]; s2 = s1 + t[..., 2]; s3 = s2 + t[..., 3]
+    tf = _is_float(t)
+    exact = tf.all(-1) & _is_float(s1) & _is_float(s2) & _is_float(s3)
+    k = np.array([4.0, 4.0, 3.0, 2.0]) - tf
+    return s3, np.where(exact, 0.0, (k * np.abs(t)).sum(-1))
+
+
+def _div_margin(a, ea, b, eb):
+    """a / b: K = 1 beside the operands' own bounds (|1 / b| ea + |a / b^2| eb)"""
+    q = a / b
+    return q, _rounded(q, ea / np.abs(b) + eb * np.abs(a) / (b * b))
+
+
+def _texture_bilinear_margin(tex, u, eu, v, ev):
+    """_texture_bilinear with the bound: the coordinate x = u W - 0.5 is K = 2 (product, difference) on top of W eu; the sample moves by at most the
+    footprint's largest texel difference per unit of x (bilinear filtering is continuous across texel borders, so a floor() that falls the other way
+    changes nothing to first order); the filter itself is K = 6 with A = the filter of |texel| (lerp2: a texel passes through 1 - a, its product and
+    the sum of its row, then the same three of the rows' lerp)."""
+    Hh, Ww = tex.shape[0], tex.shape[1]
+    t = tex.astype(np.float64)
+    x = u * Ww - 0.5; ex = _rounded(x, _rounded(u * Ww, eu * Ww))
+    y = v * Hh - 0.5; ey = _rounded(y, _rounded(v * Hh, ev * Hh))
+    x0 = np.floor(x); y0 = np.floor(y)
+    ax = x - x0; ay = y - y0
+    xi0 = np.clip(x0.astype(np.int64), 0, Ww - 1); xi1 = np.clip(x0.astype(np.int64) + 1, 0, Ww - 1)
+    yi0 = np.clip(y0.astype(np.int64), 0, Hh - 1); yi1 = np.clip(y0.astype(np.int64) + 1, 0, Hh - 1)
+    t00, t10, t01, t11 = t[yi0, xi0], t[yi0, xi1], t[yi1, xi0], t[yi1, xi1]
+    if t.ndim == 3:
+        ax = ax[..., None]; ay = ay[..., None]; ex = ex[..., None]; ey = ey[..., None]
+    lerp = lambda a, b, c, d: (a * (1.0 - ax) + b * ax) * (1.0 - ay) + (c * (1.0 - ax) + d * ax) * ay
+    val = lerp(t00, t10, t01, t11)
+    slope_x = np.maximum(np.abs(t10 - t00), np.abs(t11 - t01)); slope_y = np.maximum(np.abs(t01 - t00), np.abs(t11 - t10))
+    return val, ex * slope_x + ey * slope_y + 6.0 * lerp(np.abs(t00), np.abs(t10), np.abs(t01), np.abs(t11))
+
+
+def _proj_margin(frag, efrag):
+    """projCoords.xyz / w, then x, y -> * 0.5 + 0.5 (K = 1: the product by 0.5 is exact) and y -> 1 - y (K = 1); z is left to the caller"""
+    qx, eqx = _div_margin(frag[..., 0], efrag[..., 0], frag[..., 3], efrag[..., 3])
+    qy, eqy = _div_margin(frag[..., 1], efrag[..., 1], frag[..., 3], efrag[..., 3])
+    qz, eqz = _div_margin(frag[..., 2], efrag[..., 2], frag[..., 3], efrag[..., 3])
+    px = qx * 0.5 + 0.5; epx = _rounded(px, 0.5 * eqx)
+    py1 = qy * 0.5 + 0.5; epy1 = _rounded(py1, 0.5 * eqy)
+    py = 1.0 - py1; epy = _rounded(py, epy1)
+    return px, epx, py, epy, qz, eqz
+
+
+def _reject_margin(px, epx, py, epy, pz, epz, z_min):
+    """the five compares of Lighting.glsl:248-252 / :269-274 -> (rejected bool[n, 5], the pixel's outcome is decided).  They are one short-circuit
+    `or`: a compare that is true beyond rounding decides it whatever the others are."""
+    q = np.stack([px - 1.0, py - 1.0, px, py, pz - z_min], -1)
+    e = np.stack([epx, epy, epx, epy, epz], -1)
+    rejected = np.stack([px > 1.0, py > 1.0, px < 0.0, py < 0.0, pz < z_min], -1)
+    dec = _decided(q, e)
+    return rejected, (rejected & dec).any(-1) | dec.all(-1)
+
+
+def shadow_pcf_margin(tex, frag, efrag, bias, ebias):
+    """shadow_pcf beside the conditioning of its decisions -> dict(factor, rejected, reject_decided, undecided_taps, sixteenths)"""
+    px, epx, py, epy, qz, eqz = _proj_margin(frag, efrag)
+    pz = qz * 0.5 + 0.5; epz = _rounded(pz, 0.5 * eqz)
+    rejected, reject_decided = _reject_margin(px, epx, py, epy, pz, epz, 0.5)
+    outside = rejected.any(-1)
+    texel = 1.0 / np.array([tex.shape[1], tex.shape[0]], np.float64)
+    ref = pz + bias; eref = epz + ebias + np.abs(ref)                                   # K = 1
+    count = np.zeros(px.shape); undecided = np.zeros(px.shape, np.int64)
+    for i in range(16):
+        off = POISSON[i] * 2.0 * texel                                                  # K = 2: 1 / size and one product (the other is by 2)
+        u = px + off[0]; eu = epx + 2.0 * abs(off[0]) + np.abs(u)                       # K = 1
+        v = py + off[1]; ev = epy + 2.0 * abs(off[1]) + np.abs(v)
+        s, es = _texture_bilinear_margin(tex, u, eu, v, ev)
+        d = s * 0.5 + 0.5; ed = 0.5 * es + np.abs(d)                                    # K = 1
+        count += np.where(ref > d, 1.0, 0.0)
+        undecided += ~_decided(ref - d, eref + ed)
+    return dict(factor=np.where(outside, 1.0, count / 16.0), rejected=rejected, reject_decided=reject_decided,
+                undecided_taps=np.where(outside, 0, undecided), sixteenths=np.where(outside, -1, count.astype(np.int64)))
+
+
+EXP_ROUNDINGS = 5.0
+# canonical_expf's own error relative to exp(), counted on its text: y = (p z + r) + 1 lies in [0.707, 1.414]; the last sum rounds by <= 1.42 u, p z + r
+# by <= 0.41 u, the second Cody-Waite step leaves r (|r| <= 0.35) two roundings off and dy / dr = y: <= 0.7 u y, the five Horner steps (two roundings
+# each, magnitudes <= 0.5) enter through z <= 0.12: <= 0.6 u, the polynomial's truncation is 2e-8 = 0.33 u -- 3.5 u over y >= 0.707, i.e. <= 5 u relative.
+
+
+def _chebyshev_margin(m0, em0, m1, em1, current, ecurrent, min_variance):
+    """_chebyshev (linstep 0) -> (value, d < 0, that compare is decided, first-order bound e on the value)"""
+    d = current - m0; ed = ecurrent + em0 + np.abs(d)                                    # K = 1
+    raw = m1 - m0 * m0
+    eraw = em1 + 2.0 * np.abs(m0) * em0 + m0 * m0 + np.abs(raw)                          # K = 2: the square and the difference
+    variance = np.maximum(min_variance, raw)
+    evar = np.where(raw >= min_variance - 2.0 * U24 * eraw, eraw, 0.0)                   # max() is continuous: the bound of the side it may take
+    with np.errstate(divide="ignore", invalid="ignore"):
+        den = variance + d * d
+        pmax = variance / den
+        e = (d * d / (den * den)) * evar + (2.0 * variance * np.abs(d) / (den * den)) * ed + 3.0 * np.abs(pmax)   # K = 3: d d, the sum, the quotient
+    neg = d < 0
+    return np.where(neg, 1.0, np.clip(pmax, 0.0, 1.0)), neg, _decided(d, ed), np.where(neg, 0.0, e)
+
+
+def shadow_evsm_margin(tex, frag, efrag, bias, ebias, cascade):
+    """shadow_evsm beside the conditioning of its decisions -> dict(factor, rejected, reject_decided, d_negative bool[n, 2], d_decided, factor_e)"""
+    px, epx, py, epy, pz, epz = _proj_margin(frag, efrag)
+    rejected, reject_decided = _reject_margin(px, epx, py, epy, pz, epz, 0.0)
+    outside = rejected.any(-1)
+    s, es = _texture_bilinear_margin(tex, px, epx, py, epy)
+    p05 = np.power(0.5, cascade)
+    t = 0.003 * bias * p05; et = 0.003 * p05 * ebias + 2.0 * np.abs(t)                  # K = 2: the literal and its product with bias (p05 is a power of two)
+    a = pz + t; ea = epz + et + np.abs(a)                                                # K = 1
+    arg = 40.0 * a; earg = 40.0 * ea + np.abs(arg)                                       # K = 1
+    current = np.exp(arg); ecurrent = current * (earg + EXP_ROUNDINGS)                   # d exp = exp d arg
+    t = 0.0001 * bias; et = 0.0001 * ebias + 2.0 * np.abs(t)
+    a = pz + t; ea = epz + et + np.abs(a)
+    arg = -40.0 * a; earg = 40.0 * ea + np.abs(arg)
+    neg_current = -np.exp(arg); eneg = np.abs(neg_current) * (earg + EXP_ROUNDINGS)
+    pos, dp, dec_p, e_p = _chebyshev_margin(s[..., 0], es[..., 0], s[..., 1], es[..., 1], current, ecurrent, 0.01)
+    neg, dn, dec_n, e_n = _chebyshev_margin(s[..., 2], es[..., 2], s[..., 3], es[..., 3], neg_current, eneg, 0.0)
+    live = np.where(cascade > 2, 0.0, 1.0)
+    neg = neg * live; e_n = e_n * live; dec_n = dec_n | (live == 0)
+    worst = np.maximum(pos, neg)
+    factor = np.clip(1.0 - worst, 0.0, 1.0)
+    # max() of two values known to within their bounds, each clamped to [0, 1]: the pair that is the larger beyond both bounds carries its own bound alone
+    # (behind the positive moment pos is exactly 1, the clamp's upper end: the negative pair cannot move the result at all); K = 1 for 1 - x
+    with np.errstate(invalid="ignore"):
+        lo = np.maximum(np.clip(pos - U24 * e_p, 0.0, 1.0), np.clip(neg - U24 * e_n, 0.0, 1.0))
+        hi = np.maximum(np.clip(pos + U24 * e_p, 0.0, 1.0), np.clip(neg + U24 * e_n, 0.0, 1.0))
+    factor_e = np.maximum(hi - worst, worst - lo) / U24 + np.abs(1.0 - worst)
+    return dict(factor=np.where(outside, 1.0, factor), rejected=rejected, reject_decided=reject_decided, d_negative=np.stack([dp, dn], -1),
+                d_decided=dec_p & dec_n | outside, factor_e=np.where(outside, 0.0, factor_e))
 
 
 def _chebyshev(m0, m1, current, min_variance, linstep):
@@ -117,37 +295,81 @@ def shadow_evsm(tex, frag_light, bias, cascade):
     return np.where(outside, 1.0, np.clip(1.0 - np.maximum(pos_value, neg_value), 0.0, 1.0))
 
 
-def directional_shadow(fr, light_direction, shadow_type, normal, world_pos, lights_matrices, maps):
-    """Standard.shader:266-283.  lights_matrices: float[4, 16] column-major; maps: 4 images (cascade 0 RGBA, 1..3 single channel) or None entries."""
-    cascade = np.minimum(select_cascade(fr["view"], world_pos, fr["cameraZNearZFar"][1]), 3)
-    ndl = (normal * light_direction).sum(-1)
+def directional_shadow(fr, light_direction, shadow_type, normal, world_pos, lights_matrices, maps, want_shadow_margin: bool = False):
+    """Standard.shader:266-283.  lights_matrices: float[4, 16] column-major; maps: 4 images (cascade 0 RGBA, 1..3 single channel) or None entries.
+    With want_shadow_margin also a dict of per-pixel arrays (see the margin block above):
+      cascade, kind (0 no map bound, 1 the PCF look-up, 2 EVSM), rejected bool[n, 5] (px > 1, py > 1, px < 0, py < 0, pz below the look-up's limit),
+      sixteenths (the PCF count, -1 where no tap is taken), d_negative bool[n, 2] (EVSM's `d < 0` of the positive and the negative pair; only where
+      kind == 2 and nothing rejects), undecided_taps (PCF compares within fp32 rounding), decided (the cascade choice, the rejection and the two
+      `d < 0` are beyond fp32 rounding; PCF taps are counted, not folded in), edges_decided (the cascade choice and the rejection alone),
+      factor (what is returned), factor_bound (first-order bound on a fp32 evaluation's error of the EVSM factor; 0 elsewhere)."""
+    z_far = fr["cameraZNearZFar"][1]
+    if want_shadow_margin:
+        cascade, cascade_decided = select_cascade(fr["view"], world_pos, z_far, want_margin=True)
+    else:
+        cascade = select_cascade(fr["view"], world_pos, z_far)
+    cascade = np.minimum(cascade, 3)
+    nd = normal * light_direction
+    ndl = nd.sum(-1)
     out = np.ones(cascade.shape)
     wp1 = np.concatenate([world_pos, np.ones(world_pos.shape[:-1] + (1,))], -1)
+    if want_shadow_margin:
+        info = dict(cascade=cascade.copy(), kind=np.zeros(cascade.shape, np.int64), rejected=np.zeros(cascade.shape + (5,), bool),
+                    sixteenths=np.full(cascade.shape, -1, np.int64), d_negative=np.zeros(cascade.shape + (2,), bool),
+                    undecided_taps=np.zeros(cascade.shape, np.int64), decided=cascade_decided.copy(), edges_decided=cascade_decided.copy(),
+                    factor_bound=np.zeros(cascade.shape))
+        one = 1.0 - ndl; eone = 5.0 * np.abs(nd).sum(-1) + np.abs(one)                   # K = 5 (dot3: three products, two sums) and K = 1
     for c in range(4):
         sel = cascade == c
         if not sel.any() or maps[c] is None:
             continue
         M = np.asarray(lights_matrices[c], np.float64).reshape(4, 4).T
-        frag = wp1[sel] @ M.T
-        if shadow_type == 2 and c == 0:
+        rows = [_row_margin(M[r], wp1[sel]) for r in range(4)]
+        frag = np.stack([r[0] for r in rows], -1)
+        tex = np.asarray(maps[c])
+        evsm = shadow_type == 2 and c == 0
+        if evsm:
             bias = (1.0 - ndl[sel]) * (1 + c)
-            out[sel] = shadow_evsm(np.asarray(maps[c]), frag, bias, np.full(frag.shape[0], c))
+            out[sel] = shadow_evsm(tex if tex.ndim == 3 else np.stack([tex, 0 * tex, 0 * tex, 0 * tex + 1], -1), frag, bias, np.full(frag.shape[0], c))
         else:
             bias = np.maximum(0.000075 * (1.0 - ndl[sel]), 0.000005)
-            tex = np.asarray(maps[c])
-            out[sel] = shadow_pcf(tex if tex.ndim == 2 else tex[..., 0], frag, bias)
-    return out
+            tex = tex if tex.ndim == 2 else tex[..., 0]
+            out[sel] = shadow_pcf(tex, frag, bias)
+        if want_shadow_margin:
+            efrag = np.stack([r[1] for r in rows], -1)
+            if evsm:
+                tex4 = tex if tex.ndim == 3 else np.stack([tex, 0 * tex, 0 * tex, 0 * tex + 1], -1)
+                m = shadow_evsm_margin(tex4, frag, efrag, bias, eone[sel] * (1 + c), np.full(frag.shape[0], c))
+                info["d_negative"][sel] = m["d_negative"] & ~m["rejected"].any(-1)[:, None]
+                info["decided"][sel] &= m["reject_decided"] & m["d_decided"]
+                info["factor_bound"][sel] = U24 * m["factor_e"]
+            else:
+                m = shadow_pcf_margin(tex, frag, efrag, bias, 0.000075 * eone[sel] + 2.0 * bias)   # K = 2: the literal and its product (max picks one side)
+                info["sixteenths"][sel] = m["sixteenths"]
+                info["undecided_taps"][sel] = m["undecided_taps"]
+                info["decided"][sel] &= m["reject_decided"]
+            assert np.array_equal(m["factor"], out[sel], equal_nan=True), "the margin restatement computes another factor"
+            info["kind"][sel] = 2 if evsm else 1
+            info["edges_decided"][sel] &= m["reject_decided"]
+            info["rejected"][sel] = m["rejected"]
+    if want_shadow_margin:
+        info["factor"] = out
+    return (out, info) if want_shadow_margin else out
 
 
-def calculate_lighting(fr, L, albedo, metallic, roughness, F0, Lo, cos_lo, normal, world_pos, csm):
-    """Standard.shader:259-341 for ONE light over an array of pixels -> float64[..., 3]"""
+def calculate_lighting(fr, L, albedo, metallic, roughness, F0, Lo, cos_lo, normal, world_pos, csm, shadow_margin=None):
+    """Standard.shader:259-341 for ONE light over an array of pixels -> float64[..., 3].  shadow_margin: a dict that a shadowed directional light
+    fills with directional_shadow's margin arrays and `unshadowed`, its term before the shadow factor."""
     ltype = int(L["type"])
     pos = L["worldPosition"].astype(np.float64); direction = L["direction"].astype(np.float64)
     att = L["attenuation"].astype(np.float64); cut = L["cutOff"].astype(np.float64)
     falloff = np.ones(world_pos.shape[:-1]); shadow = np.ones(world_pos.shape[:-1])
     with np.errstate(divide="ignore", invalid="ignore"):
         if ltype == 0:
-            if csm is not None:
+            if csm is not None and shadow_margin is not None:
+                shadow, info = directional_shadow(fr, direction, int(L["shadowType"]), normal, world_pos, csm[0], csm[1], want_shadow_margin=True)
+                shadow_margin.update(info)
+            elif csm is not None:
                 shadow = directional_shadow(fr, direction, int(L["shadowType"]), normal, world_pos, csm[0], csm[1])
         elif ltype == 1:
             distance = np.sqrt(((pos - world_pos) ** 2).sum(-1))
@@ -176,7 +398,10 @@ def calculate_lighting(fr, L, albedo, metallic, roughness, F0, Lo, cos_lo, norma
         kd = (1.0 - F) * (1.0 - metallic)[..., None]  # mix(1 - F, 0, metallic)
         diffuse = kd * albedo
         specular = (F * (D * G)[..., None]) / np.maximum(EPSILON, 4.0 * cos_li * cos_lo)[..., None]
-        return shadow[..., None] * ((diffuse + specular) * L["intensity"].astype(np.float64) * cos_li[..., None]) * falloff[..., None]
+        term = (diffuse + specular) * L["intensity"].astype(np.float64) * cos_li[..., None]
+        if shadow_margin is not None and "cascade" in shadow_margin:
+            shadow_margin["unshadowed"] = term
+        return shadow[..., None] * term * falloff[..., None]
 
 
 def seam_margin(d):
@@ -205,19 +430,29 @@ def ambient_lighting(ibl, albedo, metallic, roughness, ao, F0, Lr, normal, cos_l
 
 
 def shade(frame_bytes, W: int, H: int, surface: np.ndarray, lights: np.ndarray, grid: np.ndarray, indices: np.ndarray, csm=None, rows=None,
-          want_conditioning: bool = False, ibl=None, want_seam_margin: bool = False):
+          want_conditioning: bool = False, ibl=None, want_seam_margin: bool = False, want_shadow_margin: bool = False):
     """Standard.shader:377-439 over the synthetic surface: surface float32[3, H, W, 4] = (worldPos, albedo.a) (normal, roughness)
     (albedo.rgb, metallic); grid uint32[T, 2], indices uint32[...] the canonical cull output; csm = (lightsMatrices[4, 16], [4 maps]) or None;
     ibl = None (ambient term 0) or the dict of ambient_lighting plus `ao`: float[H, W] (:386: the AO target has the viewport's size, so a fragment
     reads its own texel) or None (1).  rows = (first, last + 1) shades a band of framebuffer rows, the rest stays 0.
     -> radiance float64[H, W, 4].  With want_conditioning also returns, per pixel, the smallest NdfGGX denominator met; with want_seam_margin also
-    seam_margin() of the two cube lookups' directions, `normal` and `Lr`, float64[H, W] each."""
+    seam_margin() of the two cube lookups' directions, `normal` and `Lr`, float64[H, W] each; with want_shadow_margin also (last) a dict on the shadow
+    term's conditioning (the margin block above directional_shadow):
+      left_out        bool[H, W]: a discrete decision of some directional light's shadow term (cascade, rejection, a PCF tap, EVSM's `d < 0`) is within
+                      fp32 rounding, or the first-order bound on the EVSM factor's fp32 error times that light's unshadowed term exceeds the pixel's K2
+                      tolerance 1e-4 |ref| + 1e-7 max |ref|
+      taps_only       bool[H, W]: left out for undecided PCF taps and nothing else
+      tap_allowance   float64[H, W, 3]: sum over lights of undecided_taps / 16 times |unshadowed term| -- what such a pixel may still differ by
+      undecided_taps  int[H, W]
+      lights          {light index: directional_shadow's arrays as [H, W, ...] planes plus `unshadowed` [H, W, 3]}: what the coverage counts read"""
     fr = frame_fields(frame_bytes)
     lights = np.asarray(lights).view(LIGHT_DTYPE).reshape(-1) if np.asarray(lights).dtype != LIGHT_DTYPE else np.asarray(lights)
     s = surface.astype(np.float64)
     out = np.zeros((H, W, 4))
     min_denom = np.full((H, W), np.inf)
     margin_n = np.full((H, W), np.inf); margin_lr = np.full((H, W), np.inf)
+    sm = dict(undecided=np.zeros((H, W), bool), undecided_taps=np.zeros((H, W), np.int64), tap_allowance=np.zeros((H, W, 3)),
+              smooth=np.zeros((H, W, 3)), lights={})
     vw, vh = int(fr["viewportSize"][0]), int(fr["viewportSize"][1])
     tiles_x = vw // TILE + min(1, vw % TILE)
     r0, r1 = (0, H) if rows is None else rows
@@ -246,7 +481,18 @@ def shade(frame_bytes, W: int, H: int, surface: np.ndarray, lights: np.ndarray, 
             index = int(indices[offset + i])
             if index == 0xFFFFFFFF:
                 break
-            acc += calculate_lighting(fr, lights[index], albedo, metallic, roughness, F0, -view_dir, cos_lo, normal, world_pos, csm)
+            info = {} if want_shadow_margin else None
+            acc += calculate_lighting(fr, lights[index], albedo, metallic, roughness, F0, -view_dir, cos_lo, normal, world_pos, csm, info)
+            if info:
+                planes = sm["lights"].setdefault(index, {})
+                for k, v in info.items():
+                    if k not in planes:
+                        planes[k] = np.zeros((H, W) + v.shape[1:], v.dtype)
+                    planes[k][py, px] = v
+                sm["undecided"][py, px] |= ~info["decided"]
+                sm["undecided_taps"][py, px] += info["undecided_taps"]
+                sm["tap_allowance"][py, px] += (info["undecided_taps"] / 16.0)[:, None] * np.abs(info["unshadowed"])
+                sm["smooth"][py, px] += info["factor_bound"][:, None] * np.abs(info["unshadowed"])
             if want_conditioning:
                 Lh = _normalize(-lights[index]["direction"].astype(np.float64) - view_dir)
                 cl = np.maximum(0.0, (normal * Lh).sum(-1))
@@ -254,7 +500,13 @@ def shade(frame_bytes, W: int, H: int, surface: np.ndarray, lights: np.ndarray, 
                 min_denom[py, px] = np.minimum(min_denom[py, px], cl * cl * (a2 - 1.0) + 1.0)
         out[py, px, :3] = acc
         out[py, px, 3] = albedo_a
-    ret = (out,) + ((min_denom,) if want_conditioning else ()) + ((margin_n, margin_lr) if want_seam_margin else ())
+    if want_shadow_margin:
+        a = np.abs(out[..., :3])
+        with np.errstate(invalid="ignore"):
+            smooth_bad = ~(sm["smooth"] <= 1e-4 * a + 1e-7 * a.max()).all(-1)
+        sm["left_out"] = sm["undecided"] | smooth_bad | (sm["undecided_taps"] > 0)
+        sm["taps_only"] = (sm["undecided_taps"] > 0) & ~sm["undecided"] & ~smooth_bad
+    ret = (out,) + ((min_denom,) if want_conditioning else ()) + ((margin_n, margin_lr) if want_seam_margin else ()) + ((sm,) if want_shadow_margin else ())
     return ret if len(ret) > 1 else out
 
 

@@ -279,9 +279,12 @@ def upload_lights(lights: np.ndarray, device) -> torch.Tensor:
 
 
 def upload_shadow_maps(shadows, device) -> tuple[CsmDesc, list]:
-    """-> (CsmDesc with device pointers, tensors to keep alive)."""
+    """-> (CsmDesc with device pointers, tensors to keep alive).  A map that is None is passed as a null pointer: no map bound, shadow factor 1."""
     keep, maps = [], []
     for m in shadows.maps:
+        if m is None:
+            maps.append((0, 0, 0, _lib.SHADOWMAP_R16F))
+            continue
         t = torch.from_numpy(np.ascontiguousarray(m)).to(device)
         keep.append(t)
         fmt = _lib.SHADOWMAP_R16F if m.dtype == np.float16 else (_lib.SHADOWMAP_RGBA32F if m.ndim == 3 else _lib.SHADOWMAP_R32F)
