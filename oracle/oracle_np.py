@@ -50,8 +50,11 @@ def _plane(p1, p2, F=F):
     return c / ln
 
 
-def tile_frustum(inv_proj, tx, ty, vp_w, vp_h, F=F):
-    x0, y0, x1, y1 = F(tx * TILE), F(ty * TILE), F((tx + 1) * TILE), F((ty + 1) * TILE)
+def rect_frustum(inv_proj, x0, y0, x1, y1, vp_w, vp_h, F=F):
+    """The four side planes (left, right, top, bottom) and the centre of the screen rectangle [x0, x1] x [y0, y1] (pixels), in the op order of
+    ComputeLightCulling.shader:57-95: a tile's rectangle gives the tile's frustum, a group column's, a group row's or a tile-row band's rectangle
+    gives the planes a pre-filter of the HIP path evaluates for it."""
+    x0, y0, x1, y1 = F(x0), F(y0), F(x1), F(y1)
     vs0 = _screen_to_view(inv_proj, x0, y0, -1.0, 1.0, vp_w, vp_h, F)
     vs1 = _screen_to_view(inv_proj, x1, y0, -1.0, 1.0, vp_w, vp_h, F)
     vs2 = _screen_to_view(inv_proj, x0, y1, -1.0, 1.0, vp_w, vp_h, F)
@@ -61,29 +64,54 @@ def tile_frustum(inv_proj, tx, ty, vp_w, vp_h, F=F):
     return planes, vs4[0], vs4[1]
 
 
-def overlap_table(frame_bytes, W: int, H: int, lights: np.ndarray, depth: np.ndarray, dtype=np.float32):
+def tile_frustum(inv_proj, tx, ty, vp_w, vp_h, F=F):
+    return rect_frustum(inv_proj, tx * TILE, ty * TILE, (tx + 1) * TILE, (ty + 1) * TILE, vp_w, vp_h, F)
+
+
+def view_positions(frame_bytes, lights: np.ndarray, dtype=np.float32):
+    """(px, py, pz) of every light as ComputeLightCulling.shader:164-169 computes them, in `dtype` (pz already carries the "Reverse Z" sign)"""
+    T = dtype
+    view32, _, _, _ = _frame_fields(frame_bytes)
+    view = view32.astype(T)
+    wp = lights["worldPosition"].astype(T)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        p = _mul_glsl(view, wp[:, 0], wp[:, 1], wp[:, 2], T(1.0))
+        return p[0] / p[3], p[1] / p[3], (p[2] / p[3]) * T(-1.0)
+
+
+def overlap_table(frame_bytes, W: int, H: int, lights: np.ndarray, depth: np.ndarray, dtype=np.float32, want_operands: bool = False, tile_rows=None):
     """The per-(tile, light) decisions of Math.glsl:224-239 SphereFrustumOverlaps (+ the directional rule of :153-162) evaluated in `dtype`,
     and how close each decision is to flipping: `slack[t, j]` = the smallest relative distance of any of the six comparisons from its
     boundary.  With dtype = float64 this is the "truth" the float32 restatements are held against (tests/test_oracle_cpu.py): the two may
-    only disagree where float64 itself says the sphere touches a plane or a depth bound to within rounding."""
+    only disagree where float64 itself says the sphere touches a plane or a depth bound to within rounding.
+
+    want_operands: a third result, the operands of the six comparisons in `dtype` -- "near" = pz - r [N] against "z_near" [T] (rejected where
+    near > z_near), "far" = pz + r [N] against "z_far" [T] (rejected where far < z_far), "d" [T, N, 4] (left, right, top, bottom) against
+    "neg_r" = -r [N] (rejected where d < neg_r), and "px", "py", "pz".  tile_rows = (r0, r1): the tables of those tile rows only."""
     T = dtype
     view32, inv32, vp_w, vp_h = _frame_fields(frame_bytes)
     view, inv_proj = view32.astype(T), inv32.astype(T)
     Tx, Ty = (W - 1) // TILE + 1, (H - 1) // TILE + 1
+    r0, r1 = (0, Ty) if tile_rows is None else tile_rows
     ltype = lights["type"].astype(np.uint32)
     radius = lights["bounds"][:, 0].astype(T)
     wp = lights["worldPosition"].astype(T)
-    p = _mul_glsl(view, wp[:, 0], wp[:, 1], wp[:, 2], T(1.0))
-    px, py, pz = p[0] / p[3], p[1] / p[3], (p[2] / p[3]) * T(-1.0)
     depth_bits = np.ascontiguousarray(depth, np.float32).view(np.uint32)
-    ok = np.zeros((Ty * Tx, len(lights)), bool)
-    slack = np.full((Ty * Tx, len(lights)), np.inf)
+    nt = (r1 - r0) * Tx
+    ok = np.zeros((nt, len(lights)), bool)
+    slack = np.full((nt, len(lights)), np.inf)
     lx = np.arange(TILE)
-    scale = np.abs(px) + np.abs(py) + np.abs(pz) + np.abs(radius)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        for ty in range(Ty):
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        p = _mul_glsl(view, wp[:, 0], wp[:, 1], wp[:, 2], T(1.0))
+        px, py, pz = p[0] / p[3], p[1] / p[3], (p[2] / p[3]) * T(-1.0)
+        scale = np.abs(px) + np.abs(py) + np.abs(pz) + np.abs(radius)
+        if want_operands:
+            ops = {"near": pz - radius, "far": pz + radius, "neg_r": -radius, "px": px, "py": py, "pz": pz,
+                   "z_near": np.zeros(nt, T), "z_far": np.zeros(nt, T), "d": np.zeros((nt, len(lights), 4), T)}
+        for ty in range(r0, r1):
             rows = np.clip(H - 1 - (TILE * ty + lx), 0, H - 1)
             for tx in range(Tx):
+                t = (ty - r0) * Tx + tx
                 cols = np.minimum(TILE * tx + lx, W - 1)
                 bits = depth_bits[np.ix_(rows, cols)]
                 z_far, z_near = T(bits.max().view(np.float32)), T(bits.min().view(np.float32))
@@ -92,15 +120,19 @@ def overlap_table(frame_bytes, W: int, H: int, lights: np.ndarray, depth: np.nda
                 planes, _, _ = tile_frustum(inv_proj, tx, ty, vp_w, vp_h, T)
                 o = ~((pz - radius > z_near) | (pz + radius < z_far))
                 s = np.minimum(np.abs((pz - radius) - z_near), np.abs((pz + radius) - z_far)) / (scale + np.abs(z_near) + np.abs(z_far))
-                for pl in planes:
+                for k, pl in enumerate(planes):
                     d = (pl[0] * px + pl[1] * py) + pl[2] * pz
                     o &= ~(d < -radius)
                     s = np.minimum(s, np.abs(d + radius) / scale)
+                    if want_operands:
+                        ops["d"][t, :, k] = d
+                if want_operands:
+                    ops["z_near"][t], ops["z_far"][t] = z_near, z_far
                 o |= ltype == 0
                 s = np.where(ltype == 0, np.inf, s)
-                ok[ty * Tx + tx] = o
-                slack[ty * Tx + tx] = s
-    return ok, slack
+                ok[t] = o
+                slack[t] = s
+    return (ok, slack, ops) if want_operands else (ok, slack)
 
 
 def light_cull(frame_bytes, W: int, H: int, lights: np.ndarray, depth: np.ndarray, tile_rows=None):

@@ -45,7 +45,9 @@
 // y = const), used only for spheres entirely in front of the eye and with a relative margin ~1000x the fp32 error;
 // depth is left entirely to the exact test.  So the candidate sequence of every tile -- and therefore its first 196,
 // its selection and its order -- is the sequence the brute-force walk produces.  tests/test_light_cull_gpu.py checks
-// default == brute force == oracle.
+// default == brute force == oracle on synthetic light sets; tests/test_cull_gpu.py on spheres placed ON tile planes, band
+// planes and depth bounds to the float (tests/cull_cases.py), and tests/test_cull_cpu.py restates this pre-filter in fp32:
+// with the margin it drops no light a tile lists, without it `band_edges` counts the lights it would.
 //
 // No MFMA: sphere/plane tests and compaction, not a contraction.  Compiled with -ffp-contract=off.
 #include "common.h"
