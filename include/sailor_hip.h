@@ -51,6 +51,7 @@ extern "C" {
 #define SAILOR_LIGHTS_PER_TILE 128             /* Constants.glsl:15 ; FrameGraph/LightCullingNode.h:15 */
 #define SAILOR_GPU_CULLING_GROUP_SIZE 256      /* Constants.glsl:18 ; RHI/Renderer.h:32 */
 #define SAILOR_NUM_CSM_CASCADES 4              /* Constants.glsl:23 ; ECS/LightingECS.h:65 */
+#define SAILOR_SHADOW_CASCADE_LEVELS { 0.05f, 0.1f, 0.333333f, 0.5f } /* Constants.glsl ShadowCascadeLevels (tests/golden/reference_constants.json), fractions of zFar */
 #define SAILOR_LIGHTS_MAX_NUM 65535            /* ECS/LightingECS.h:54 (the reference's SSBO capacity) */
 
 /* ---- POD mirrors of the reference's GPU-visible structs ------------------------------------------------ */
@@ -768,6 +769,60 @@ SAILOR_HIP_API int sailor_hip_hbao_chain(SailorHipContext* ctx, const SailorUboF
                                          const SailorHbaoParams* params, float* dAo, int32_t aoWidth, int32_t aoHeight,
                                          const SailorHbaoBlurParams* blurParams, float* dTemp, int32_t tempWidth, int32_t tempHeight,
                                          float* dOut, int32_t outWidth, int32_t outHeight);
+
+/* ---- The frame's tail: motion blur into Main and the Debug view into BackBuffer (DefaultRenderer.renderer:322-353) -----------------------
+ * Replaces: the GPU work of the last two PostProcess draws (FrameGraph/PostProcessNode.cpp:176-199) of the shipped frame graph, with
+ * Content/Shaders/MotionBlur.shader:63-102 and Content/Shaders/Debug.shader:115-178.  Colour images are RGBA32F device planes, 16-byte aligned; depth,
+ * linear depth and g_AO are single-channel fp32 planes; row 0 = top; texel (i, j) of a w x h target has fragTexcoord ((i + 0.5) / w, (j + 0.5) / h) and
+ * gl_FragCoord (i + 0.5, j + 0.5); the extents of a call are independent of one another.  The shaders are evaluated as written, one IEEE rounding
+ * per written operation, with the evaluation orders fixed above for HBAO (mat4 * vec4 row by row left to right, v / s = one division per component,
+ * length = sqrt(dot), mix(a, b, t) = a (1 - t) + b t); tests/tail_ref.py restates them and the results are reproducible bit for bit.  The entry
+ * points only record: no synchronisation, capturable into a graph.  Decisions:
+ *   - inverse(frame.projection), inverse(frame.view) and previousFrame.projection * previousFrame.view are uniform per draw: computed once on the host
+ *     with the glm order of sailor_host_mat4_inverse / sailor_host_mat4_mul and passed to the kernel by value.  frame.invProjection is not used: the
+ *     shader writes the literal inverse(frame.projection) (MotionBlur.shader:69);
+ *   - min(x, y) = y < x ? y : x and max(x, y) = x < y ? y : x, the GLSL definitions: min(1, NaN) = 1.  On the first frame the previous frame data
+ *     is all zeros (RHIFrameGraph.cpp:189), previousClipPos is 0 / 0 everywhere and the velocity is (intensity, intensity);
+ *   - the velocity has no lower clamp (:81-82); clamp(x, 0, 1) = min(max(x, 0), 1); length = sqrt(dot) and the early-out `<= 0.0001` as written (:87);
+ *   - int(data.samples) truncates, the loop runs int(samples) - 1 taps, the division is by float(data.samples); output alpha is 1;
+ *   - depthSampler / colorSampler / ldrSceneSampler / g_aoSampler: bilinear, clamp-to-edge, the taps and weights of sailor_amd/csrc/sampling.h
+ *     evaluated per fetch, non-finite coordinates through the saturating float -> int conversion (NaN -> 0) that HBAO documents;
+ *     linearDepthSampler: Nearest (DefaultRenderer.renderer:85-90), texel min(max(int(floor(u * w)), 0), w - 1);
+ *   - LIGHT_TILES adds 0.05 once per listed light, as sequential fp32 additions onto linearDepth / 50000 (not n * 0.05). */
+
+/* MotionBlur.shader:50-55 PostProcessDataUBO (std140: floats at 0, 4, 8) */
+typedef struct SailorMotionBlurParams {
+    float intensity; /* shipped: 1 (DefaultRenderer.renderer:328-330) */
+    float samples;   /* 10; finite, within [1, 64] */
+    float maxSpeed;  /* 50; not 0 */
+} SailorMotionBlurParams;
+
+/* Debug.shader's define sets that have an entry point: none, or exactly one of AO, LIGHT_TILES, CASCADES (:119, :121, :145) */
+#define SAILOR_DEBUG_VIEW_SCENE 0
+#define SAILOR_DEBUG_VIEW_AO 1
+#define SAILOR_DEBUG_VIEW_LIGHT_TILES 2
+#define SAILOR_DEBUG_VIEW_CASCADES 3
+
+/* Replaces: the DrawIndexed(6) of PostProcessNode::Process with Content/Shaders/MotionBlur.shader:63-102.
+ *   frame / previousFrame : `frameData` / `previousFrameData` (set 0, bindings 0 and 1); projection and view of both are read
+ *   dDepth : `depthSampler` (the raw DepthBuffer);  dColor : `colorSampler` (Secondary);  dOut : device out, the `color` target (Main, level 0)
+ * Refused with SAILOR_HIP_ERR_INVALID_ARGUMENT, recording nothing: a null or misaligned pointer, a non-positive extent, samples not finite, below 1 or
+ * above 64, maxSpeed == 0, dOut overlapping dColor. */
+SAILOR_HIP_API int sailor_hip_motion_blur(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorUboFrameData* previousFrame,
+                                          const float* dDepth, int32_t depthWidth, int32_t depthHeight, const float* dColor, int32_t colorWidth, int32_t colorHeight,
+                                          const SailorMotionBlurParams* params, float* dOut, int32_t width, int32_t height);
+/* Replaces: the same draw with Content/Shaders/Debug.shader:115-178 under the define set `mode` names.
+ *   frame        : viewportSize (LIGHT_TILES) and cameraZNearZFar.y (CASCADES) are read
+ *   dLdrScene    : `ldrSceneSampler` (SCENE, CASCADES);  dLinearDepth : `linearDepthSampler` (LIGHT_TILES, CASCADES)
+ *   dLightsGrid / dCulledLights : the light cull's two SSBOs (LIGHT_TILES; ignored otherwise);  dAo : `g_aoSampler` (AO)
+ *   dOut         : device out, the `color` target (BackBuffer)
+ * A mode that needs a buffer it was given as null is refused with SAILOR_HIP_ERR_INVALID_ARGUMENT, like a misaligned pointer, a non-positive extent, an
+ * unknown mode, dOut overlapping dLdrScene, and -- LIGHT_TILES -- a target whose extent is not frame.viewportSize (gl_FragCoord indexes the frame's tiles).
+ * A list entry past the reference's culledLights capacity (tiles * 128 + 1 words) ends its list like the sentinel. */
+SAILOR_HIP_API int sailor_hip_debug_view(SailorHipContext* ctx, const SailorUboFrameData* frame, int32_t mode, const float* dLdrScene, int32_t sceneWidth,
+                                         int32_t sceneHeight, const float* dLinearDepth, int32_t depthWidth, int32_t depthHeight,
+                                         const SailorLightsGrid* dLightsGrid, const uint32_t* dCulledLights, const float* dAo, int32_t aoWidth, int32_t aoHeight,
+                                         float* dOut, int32_t width, int32_t height);
 
 /* ---- Sky: the producer of the `Sky` target and of g_skyCubemap (EnvironmentNode.cpp bakes g_envCubemap / g_irradianceCubemap from it) ------
  * Replaces: the GPU work of SkyNode::Process (FrameGraph/SkyNode.cpp:524-818) with Content/Shaders/Sky.shader under the define sets {FILL}, {},

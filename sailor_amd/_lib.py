@@ -127,6 +127,16 @@ HBAO_SHIPPED = dict(occlusionRadius=700.0, occlusionPower=1.5, occlusionAttenuat
 HBAO_BLUR_SHIPPED = dict(sharpness=0.5, distanceScale=2.0, radius=5.0)
 
 
+class MotionBlurParams(C.Structure):  # include/sailor_hip.h SailorMotionBlurParams (MotionBlur.shader:50-55); defaults = DefaultRenderer.renderer:328-330
+    _fields_ = [("intensity", C.c_float), ("samples", C.c_float), ("maxSpeed", C.c_float)]
+
+
+MOTION_BLUR_SHIPPED = dict(intensity=1.0, samples=10.0, maxSpeed=50.0)
+DEBUG_VIEW_SCENE, DEBUG_VIEW_AO, DEBUG_VIEW_LIGHT_TILES, DEBUG_VIEW_CASCADES = 0, 1, 2, 3  # SAILOR_DEBUG_VIEW_*: Debug.shader's define sets
+DEBUG_VIEW_MODES = {"": DEBUG_VIEW_SCENE, "AO": DEBUG_VIEW_AO, "LIGHT_TILES": DEBUG_VIEW_LIGHT_TILES, "CASCADES": DEBUG_VIEW_CASCADES}
+SHADOW_CASCADE_LEVELS = (0.05, 0.1, 0.333333, 0.5)  # SAILOR_SHADOW_CASCADE_LEVELS (Constants.glsl)
+
+
 class SkyParams(C.Structure):  # include/sailor_hip.h SailorSkyParams (Sky.shader:116-136 == SkyNode.h:48-67)
     _fields_ = [("lightDirection", C.c_float * 4), ("cloudsAttenuation1", C.c_float), ("cloudsAttenuation2", C.c_float), ("cloudsDensity", C.c_float),
                 ("cloudsCoverage", C.c_float), ("phaseInfluence1", C.c_float), ("phaseInfluence2", C.c_float), ("eccentrisy1", C.c_float),
@@ -254,6 +264,10 @@ SIGNATURES = {
     "sailor_hip_hbao_chain": (C.c_int, [_P, C.POINTER(UboFrameData), _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32,
                                         C.POINTER(HbaoParams), _P, C.c_int32, C.c_int32, C.POINTER(HbaoBlurParams), _P, C.c_int32, C.c_int32, _P, C.c_int32,
                                         C.c_int32]),
+    "sailor_hip_motion_blur": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(UboFrameData), _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32,
+                                         C.POINTER(MotionBlurParams), _P, C.c_int32, C.c_int32]),
+    "sailor_hip_debug_view": (C.c_int, [_P, C.POINTER(UboFrameData), C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32,
+                                        C.c_int32, _P, C.c_int32, C.c_int32]),
     "sailor_hip_sky_fill": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(SkyParams), _P, C.c_int32, C.c_int32]),
     "sailor_hip_sky_env_face": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(SkyParams), _P, C.c_int32, C.c_int32]),
     "sailor_hip_sky_sun": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(SkyParams), _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32]),

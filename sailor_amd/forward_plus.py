@@ -804,3 +804,43 @@ class Hbao:
                                                        _ptr(t), t.shape[1], t.shape[0], _ptr(o), o.shape[1], o.shape[0]),
                    "sailor_hip_hbao_chain", self.ctx.handle)
         return o
+
+
+class MotionBlur:
+    """The MotionBlur PostProcess entry of the frame graph (DefaultRenderer.renderer:322-334; MotionBlur.shader:63-102): `colorSampler` and `depthSampler`
+    in, the `color` target out.  Owns its output (height x width RGBA32F); `run` returns it."""
+
+    def __init__(self, ctx: HipContext, width: int, height: int, params=None):
+        self.ctx, self.width, self.height = ctx, width, height
+        self.params = params or host.motion_blur_params()
+        self.out = torch.empty((height, width, 4), dtype=torch.float32, device=ctx.device)
+
+    def run(self, frame, previous_frame, raw_depth: torch.Tensor, color: torch.Tensor) -> torch.Tensor:
+        assert raw_depth.dtype == torch.float32 and raw_depth.is_contiguous() and raw_depth.dim() == 2, tuple(raw_depth.shape)
+        assert color.dtype == torch.float32 and color.is_contiguous() and color.dim() == 3 and color.shape[2] == 4, tuple(color.shape)
+        _lib.check(self.ctx._lib.sailor_hip_motion_blur(self.ctx.handle, C.byref(frame), C.byref(previous_frame), _ptr(raw_depth), raw_depth.shape[1],
+                                                        raw_depth.shape[0], _ptr(color), color.shape[1], color.shape[0], C.byref(self.params), _ptr(self.out),
+                                                        self.width, self.height), "sailor_hip_motion_blur", self.ctx.handle)
+        return self.out
+
+
+class DebugView:
+    """The Debug PostProcess entry (DefaultRenderer.renderer:344-353; Debug.shader:115-178) under one of its routed define sets: "" (the scene copy), "AO",
+    "LIGHT_TILES", "CASCADES".  Owns its output (height x width RGBA32F); `run` returns it.  Arguments a mode does not read may be None."""
+
+    def __init__(self, ctx: HipContext, width: int, height: int, define: str = ""):
+        if define not in _lib.DEBUG_VIEW_MODES:
+            raise ValueError(f"no entry point for Debug.shader under {define!r}: expected one of {sorted(_lib.DEBUG_VIEW_MODES)}")
+        self.ctx, self.width, self.height, self.mode = ctx, width, height, _lib.DEBUG_VIEW_MODES[define]
+        self.out = torch.empty((height, width, 4), dtype=torch.float32, device=ctx.device)
+
+    def run(self, frame, scene: torch.Tensor | None = None, linear_depth: torch.Tensor | None = None, lights_grid: torch.Tensor | None = None,
+            culled_lights: torch.Tensor | None = None, ao: torch.Tensor | None = None) -> torch.Tensor:
+        for t in (scene, linear_depth, lights_grid, culled_lights, ao):
+            assert t is None or t.is_contiguous()
+        w = lambda t: 0 if t is None else t.shape[1]
+        h = lambda t: 0 if t is None else t.shape[0]
+        _lib.check(self.ctx._lib.sailor_hip_debug_view(self.ctx.handle, C.byref(frame), self.mode, _ptr(scene), w(scene), h(scene), _ptr(linear_depth),
+                                                       w(linear_depth), h(linear_depth), _ptr(lights_grid), _ptr(culled_lights), _ptr(ao), w(ao), h(ao),
+                                                       _ptr(self.out), self.width, self.height), "sailor_hip_debug_view", self.ctx.handle)
+        return self.out

@@ -93,6 +93,13 @@ def hbao_shipped_extents(width: int, height: int):
     return (width // 2, width // 2), (width // 2, width // 2), (width, width), (width, width)
 
 
+def motion_blur_params(**values) -> "_lib.MotionBlurParams":
+    """MotionBlur.shader:50-55 PostProcessDataUBO; unnamed members keep the shipped values (DefaultRenderer.renderer:328-330)"""
+    v = dict(_lib.MOTION_BLUR_SHIPPED)
+    v.update(values)
+    return _lib.MotionBlurParams(**{k: float(x) for k, x in v.items()})
+
+
 def bloom_params(**values) -> "_lib.BloomParams":
     """The Bloom node's four parameters; unnamed members keep the shipped values (DefaultRenderer.renderer:298-302)"""
     v = dict(_lib.BLOOM_SHIPPED)

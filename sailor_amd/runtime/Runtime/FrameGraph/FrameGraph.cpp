@@ -48,15 +48,19 @@ template class Sailor::Framegraph::TFrameGraphNode<BlitNode>;
 template class Sailor::Framegraph::TFrameGraphNode<SkyNode>;
 
 // ---- RHIFrameGraph ----------------------------------------------------------------------------------------------------------
-UboFrameData RHIFrameGraph::FillFrameData(RHICommandListPtr transferCmdList, RHISceneViewSnapshot& snapshot, float deltaTime, float worldTime) const
+UboFrameData RHIFrameGraph::FillFrameData(RHICommandListPtr transferCmdList, RHISceneViewSnapshot& snapshot, const UboFrameData& previousFrame, float deltaTime,
+                                          float worldTime) const
 {
     // RHIFrameGraph.cpp:56-70
     UboFrameData frameData {};
     snapshot.m_frameBindings = Renderer::GetDriver()->CreateShaderBindings();
     Renderer::GetDriver()->AddBufferToShaderBindings(snapshot.m_frameBindings, "frameData", sizeof(UboFrameData), 0, EShaderBindingType::UniformBuffer);
+    Renderer::GetDriver()->AddBufferToShaderBindings(snapshot.m_frameBindings, "previousFrameData", sizeof(UboFrameData), 1, EShaderBindingType::UniformBuffer); // (:58)
     sailor_host_fill_frame_data(snapshot.m_camera.m_world, snapshot.m_camera.m_fov, snapshot.m_camera.m_aspect, snapshot.m_camera.m_zNear,
                                 snapshot.m_camera.m_zFar, m_viewport.x, m_viewport.y, worldTime, deltaTime, &frameData);
     Renderer::GetDriverCommands()->UpdateShaderBinding(transferCmdList, snapshot.m_frameBindings->GetOrAddShaderBinding("frameData"), &frameData, sizeof(frameData));
+    Renderer::GetDriverCommands()->UpdateShaderBinding(transferCmdList, snapshot.m_frameBindings->GetOrAddShaderBinding("previousFrameData"), &previousFrame,
+                                                       sizeof(previousFrame)); // (:70)
     return frameData;
 }
 
@@ -65,7 +69,7 @@ void RHIFrameGraph::Process(RHISceneViewSnapshot& snapshot)
     auto driver = Renderer::GetDriver();
     auto transferCmdList = driver->CreateCommandList();
     auto cmdList = driver->CreateCommandList();
-    FillFrameData(transferCmdList, snapshot, snapshot.m_deltaTime, snapshot.m_currentTime);
+    m_prevFrameData = FillFrameData(transferCmdList, snapshot, m_prevFrameData, snapshot.m_deltaTime, snapshot.m_currentTime); // (:189)
     if (snapshot.m_rhiLightsData) { // RHIFrameGraph.cpp:128-163: the IBL samplers and the AO target join the lights set (bindings 3, 4, 5, 9)
         struct { const char* name; RHITexturePtr tex; uint32_t binding; } ibl[] = {
             { "g_irradianceCubemap", GetSampler("g_irradianceCubemap"), 3 }, { "g_brdfSampler", GetSampler("g_brdfSampler"), 4 },
@@ -88,6 +92,7 @@ void RHIFrameGraph::Clear()
     for (auto& node : m_graph) node->Clear();
     m_graph.clear();
     m_renderTargets.clear();
+    m_prevFrameData = UboFrameData {}; // (a graph built next starts with a first frame)
 }
 
 // ---- EnvironmentNode (FrameGraph/EnvironmentNode.cpp:19-281) --------------------------------------------------------------------

@@ -41,7 +41,14 @@ public:
     void SetViewport(int32_t width, int32_t height) { m_viewport = { width, height }; } // App::GetMainWindow()->GetRenderArea()
     RHI::ivec2 GetViewport() const { return m_viewport; }
 
-    RHI::UboFrameData FillFrameData(RHI::RHICommandListPtr transferCmdList, RHI::RHISceneViewSnapshot& snapshot, float deltaTime, float worldTime) const;
+    // RHIFrameGraph.cpp:50-72: `frameData` (set 0, binding 0) and `previousFrameData` (binding 1: what MotionBlur.shader:38-48 reads) of the scene view's
+    // frame bindings; returns the frame data it uploaded.  The four-argument form passes m_prevFrameData, as RHIFrameGraph.cpp:189 does.
+    RHI::UboFrameData FillFrameData(RHI::RHICommandListPtr transferCmdList, RHI::RHISceneViewSnapshot& snapshot, const RHI::UboFrameData& previousFrame, float deltaTime,
+                                    float worldTime) const;
+    RHI::UboFrameData FillFrameData(RHI::RHICommandListPtr transferCmdList, RHI::RHISceneViewSnapshot& snapshot, float deltaTime, float worldTime) const
+    {
+        return FillFrameData(transferCmdList, snapshot, m_prevFrameData, deltaTime, worldTime);
+    }
     // One frame: FillFrameData, then node->Process in graph order, then submit (record-then-submit)
     void Process(RHI::RHISceneViewSnapshot& snapshot);
     void Clear();
@@ -53,6 +60,9 @@ private:
     std::map<std::string, float> m_values;
     std::set<std::string> m_enabledNodes;
     RHI::ivec2 m_viewport;
+    // RHIFrameGraph.h:72 `RHI::UboFrameData m_prevFrameData{}`: all zeros on a graph's first frame, afterwards what the last Process() uploaded as `frameData`
+    // (RHIFrameGraph.cpp:189).  The reference builds a new RHIFrameGraph per `.renderer` file; here Clear() zeroes it with the graph.
+    RHI::UboFrameData m_prevFrameData {};
 };
 
 } // namespace Sailor::Framegraph

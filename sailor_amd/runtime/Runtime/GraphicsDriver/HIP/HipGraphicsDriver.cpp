@@ -95,7 +95,20 @@ RHIShaderPtr HipGraphicsDriver::CreateShader(const std::string& assetPath, const
     if (assetPath == "Shaders/Sky.shader")
         shader->m_bIsReady = defines.empty() ||
                              (defines.size() == 1 && (defines[0] == "FILL" || defines[0] == "SUN" || defines[0] == "COMPOSE" || defines[0] == "CLOUDS"));
+    // The frame's tail (DefaultRenderer.renderer:322-353), for a driver that opted in (EnableShader): MotionBlur.shader has no permutation; Debug.shader is
+    // routed by its define set: {} (the scene copy), {AO}, {LIGHT_TILES}, {CASCADES}
+    if (assetPath == "Shaders/MotionBlur.shader") shader->m_bIsReady = IsShaderEnabled(assetPath);
+    if (assetPath == "Shaders/Debug.shader")
+        shader->m_bIsReady = IsShaderEnabled(assetPath) &&
+                             (defines.empty() || (defines.size() == 1 && (defines[0] == "AO" || defines[0] == "LIGHT_TILES" || defines[0] == "CASCADES")));
     return shader;
+}
+
+bool HipGraphicsDriver::EnableShader(const std::string& assetPath)
+{
+    if (assetPath != "Shaders/MotionBlur.shader" && assetPath != "Shaders/Debug.shader") return false;
+    m_enabledShaders.insert(assetPath);
+    return true;
 }
 
 static size_t texel_size(EFormat f)
@@ -402,6 +415,8 @@ void HipGraphicsDriver::SetMaterialParameter(RHICommandListPtr cmd, RHIShaderBin
         { "Shaders/HBAO.shader", "occlusionRadius", 0 }, { "Shaders/HBAO.shader", "occlusionPower", 4 }, { "Shaders/HBAO.shader", "occlusionAttenuation", 8 },
         { "Shaders/HBAO.shader", "occlusionBias", 12 }, { "Shaders/HBAO.shader", "noiseScale", 16 },
         { "Shaders/HBAO_Blur.shader", "sharpness", 0 }, { "Shaders/HBAO_Blur.shader", "distanceScale", 4 }, { "Shaders/HBAO_Blur.shader", "radius", 8 },
+        // MotionBlur.shader:50-55 (SailorMotionBlurParams): three floats
+        { "Shaders/MotionBlur.shader", "intensity", 0 }, { "Shaders/MotionBlur.shader", "samples", 4 }, { "Shaders/MotionBlur.shader", "maxSpeed", 8 },
         // Sky.shader:116-136 (SailorSkyParams): a vec4, then seventeen 4-byte scalars
         { "Shaders/Sky.shader", "lightDirection", 0 }, { "Shaders/Sky.shader", "cloudsAttenuation1", 16 }, { "Shaders/Sky.shader", "cloudsAttenuation2", 20 },
         { "Shaders/Sky.shader", "cloudsDensity", 24 }, { "Shaders/Sky.shader", "cloudsCoverage", 28 }, { "Shaders/Sky.shader", "phaseInfluence1", 32 },
@@ -812,7 +827,12 @@ void HipGraphicsDriver::DrawIndexed(RHICommandListPtr cmd, uint32_t indexCount, 
     const int sky = (!shader || !shader->IsReady()) ? -1
                     : (shader->m_defines.empty() ? 1 : (shader->HasDefine("FILL") ? 0 : (shader->HasDefine("SUN") ? 2 : (shader->HasDefine("CLOUDS") ? 4 : 3))));
     const bool alphaBlending = cmd->m_boundMaterial && cmd->m_boundMaterial->m_blendMode == EBlendMode::AlphaBlending;
-    cmd->m_hip.m_commands.push_back([this, name, bindings, target, fullScreenQuad, evsm, vertical, horizontal, tonemapFlags, sky, alphaBlending]() {
+    // the frame's tail: drawn only with a shader CreateShader marked ready (the opt-in); Debug.shader's permutation: SAILOR_DEBUG_VIEW_*, -1 = none
+    const bool tail = shader && shader->IsReady();
+    const int debugMode = !tail ? -1
+                          : (shader->m_defines.empty() ? SAILOR_DEBUG_VIEW_SCENE
+                             : (shader->HasDefine("AO") ? SAILOR_DEBUG_VIEW_AO : (shader->HasDefine("LIGHT_TILES") ? SAILOR_DEBUG_VIEW_LIGHT_TILES : SAILOR_DEBUG_VIEW_CASCADES)));
+    cmd->m_hip.m_commands.push_back([this, name, bindings, target, fullScreenQuad, evsm, vertical, horizontal, tonemapFlags, sky, alphaBlending, tail, debugMode]() {
         if (fullScreenQuad && name == "Shaders/Sky.shader" && sky == 4) return RecordSkyClouds(bindings, target);
         if (fullScreenQuad && name == "Shaders/Sky.shader" && sky >= 0) return RecordSky(bindings, target, sky);
         if (fullScreenQuad && name == "Shaders/Blit.shader" && alphaBlending) return RecordBlitAlphaBlended(bindings, target);
@@ -821,6 +841,8 @@ void HipGraphicsDriver::DrawIndexed(RHICommandListPtr cmd, uint32_t indexCount, 
         if (fullScreenQuad && name == "Shaders/Blur.shader" && evsm && vertical != horizontal) return RecordEvsmBlur(bindings, target, vertical);
         if (fullScreenQuad && name == "Shaders/HBAO.shader") return RecordHbao(bindings, target);
         if (fullScreenQuad && name == "Shaders/HBAO_Blur.shader" && vertical != horizontal) return RecordHbaoBlur(bindings, target, vertical);
+        if (fullScreenQuad && name == "Shaders/MotionBlur.shader" && tail) return RecordMotionBlur(bindings, target);
+        if (fullScreenQuad && name == "Shaders/Debug.shader" && tail) return RecordDebugView(bindings, target, debugMode);
         return (int)SAILOR_HIP_ERR_UNSUPPORTED;
     });
 }
@@ -947,6 +969,75 @@ int HipGraphicsDriver::RecordHbaoBlur(const TVector<RHIShaderBindingSetPtr>& bin
     BeforeBufferWrite(target->m_buffer->m_hip.m_devicePtr);
     return sailor_hip_hbao_blur_pass(m_ctx, (const float*)texels_of(ao), ao->GetExtent().x, ao->GetExtent().y, (const float*)texels_of(depth), depth->GetExtent().x,
                                      depth->GetExtent().y, &params, (float*)texels_of(target), target->GetExtent().x, target->GetExtent().y, vertical ? 1 : 0);
+}
+
+// ---- PostProcessNode with the frame's tail (DefaultRenderer.renderer:322-353) -------------------------------------------------------------------
+// a bound sampler as an RGBA32F image (level 0 of a mip chain such as Main: texels_of / GetExtent address it), or null
+static RHITexturePtr rgba_of(const RHIShaderBindingSetPtr& set, const char* name)
+{
+    auto b = set ? set->Find(name) : RHIShaderBindingPtr();
+    if (!b || b->m_textures.empty() || !b->m_textures[0] || !b->m_textures[0]->m_buffer || b->m_textures[0]->m_format != EFormat::R32G32B32A32_SFLOAT || b->m_textures[0]->m_bCubemap)
+        return RHITexturePtr();
+    return b->m_textures[0];
+}
+
+int HipGraphicsDriver::RecordMotionBlur(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& target)
+{
+    // PostProcessNode.cpp:189: { sceneView.m_frameBindings, m_shaderBindings, sceneView.m_rhiLightsData }; MotionBlur.shader:26-48 (set 0: binding 0 `frameData`,
+    // 1 `previousFrameData`), :50-58 (set 1: binding 0 `data`, 1 `depthSampler`, 2 `colorSampler`).  A name that resolved to nothing is an invalid argument.
+    // `color: Main` with Main a mip chain: the attachment is the chain, whose texels start with level 0 and whose extent is level 0's.
+    if (bindings.size() < 2 || !target || !target->m_buffer || target->m_format != EFormat::R32G32B32A32_SFLOAT) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    auto frameB = bindings[0]->Find("frameData"), prevB = bindings[0]->Find("previousFrameData");
+    auto dataB = bindings[1]->Find("data");
+    auto depth = plane_of(bindings[1], "depthSampler");
+    auto color = rgba_of(bindings[1], "colorSampler");
+    if (!frameB || frameB->m_hostCopy.size() < sizeof(SailorUboFrameData) || !prevB || prevB->m_hostCopy.size() < sizeof(SailorUboFrameData) || !dataB ||
+        dataB->m_hostCopy.size() < sizeof(SailorMotionBlurParams) || !depth || !color)
+        return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    SailorUboFrameData frame, previous;
+    memcpy(&frame, frameB->m_hostCopy.data(), sizeof frame);
+    memcpy(&previous, prevB->m_hostCopy.data(), sizeof previous);
+    SailorMotionBlurParams params;
+    memcpy(&params, dataB->m_hostCopy.data(), sizeof params);
+    BeforeBufferWrite(target->m_buffer->m_hip.m_devicePtr);
+    return sailor_hip_motion_blur(m_ctx, &frame, &previous, (const float*)texels_of(depth), depth->GetExtent().x, depth->GetExtent().y, (const float*)texels_of(color),
+                                  color->GetExtent().x, color->GetExtent().y, &params, (float*)texels_of(target), target->GetExtent().x, target->GetExtent().y);
+}
+
+int HipGraphicsDriver::RecordDebugView(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& target, int mode)
+{
+    // Debug.shader:81-113: set 0 `frameData`; set 1: binding 1 `ldrSceneSampler`, 2 `linearDepthSampler`; set 2 = sceneView.m_rhiLightsData, which
+    // PostProcessNode binds third (PostProcessNode.cpp:189): 1 `culledLights`, 2 `lightsGrid`, 9 `g_aoSampler`.  The shader declares all of them under every
+    // define set, so a name that resolved to nothing refuses the draw whichever mode reads it -- except the lights set's, which a scene without lights
+    // does not have: those are required by the mode that reads them (the entry point refuses a null it needs).
+    if (bindings.size() < 2 || mode < 0 || !target || !target->m_buffer || target->m_format != EFormat::R32G32B32A32_SFLOAT) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    auto frameB = bindings[0]->Find("frameData");
+    auto scene = rgba_of(bindings[1], "ldrSceneSampler");
+    auto depth = plane_of(bindings[1], "linearDepthSampler");
+    if (!frameB || frameB->m_hostCopy.size() < sizeof(SailorUboFrameData) || !scene || !depth) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    SailorUboFrameData frame;
+    memcpy(&frame, frameB->m_hostCopy.data(), sizeof frame);
+    const RHIShaderBindingSetPtr lights = bindings.size() > 2 ? bindings[2] : RHIShaderBindingSetPtr();
+    const SailorLightsGrid* grid = nullptr;
+    const uint32_t* culled = nullptr;
+    RHITexturePtr ao;
+    if (mode == SAILOR_DEBUG_VIEW_LIGHT_TILES && lights) {
+        auto gridB = lights->Find("lightsGrid"), culledB = lights->Find("culledLights");
+        int32_t tx = 0, ty = 0;
+        // the SSBOs must hold what the view indexes: an entry per tile of the frame, the reference's list capacity (LightCullingNode.cpp:63-66)
+        if (gridB && culledB && gridB->m_buffer && culledB->m_buffer && sailor_hip_num_tiles(frame.viewportSize[0], frame.viewportSize[1], &tx, &ty) == SAILOR_HIP_OK &&
+            gridB->m_buffer->m_size >= (size_t)tx * ty * sizeof(SailorLightsGrid) && culledB->m_buffer->m_size >= ((size_t)tx * ty * SAILOR_LIGHTS_PER_TILE + 1) * 4) {
+            grid = (const SailorLightsGrid*)gridB->m_buffer->m_hip.m_devicePtr;
+            culled = (const uint32_t*)culledB->m_buffer->m_hip.m_devicePtr;
+        }
+        // the two SSBOs are filled by the compaction on the second queue: the view reads them behind it
+        if (m_packPending) { sailor_hip_context_wait_for(m_ctx, m_ctxAux); m_packPending = false; }
+    }
+    if (mode == SAILOR_DEBUG_VIEW_AO) ao = plane_of(lights, "g_aoSampler");
+    BeforeBufferWrite(target->m_buffer->m_hip.m_devicePtr);
+    return sailor_hip_debug_view(m_ctx, &frame, mode, (const float*)texels_of(scene), scene->GetExtent().x, scene->GetExtent().y, (const float*)texels_of(depth),
+                                 depth->GetExtent().x, depth->GetExtent().y, grid, culled, ao ? (const float*)texels_of(ao) : nullptr, ao ? ao->GetExtent().x : 0,
+                                 ao ? ao->GetExtent().y : 0, (float*)texels_of(target), target->GetExtent().x, target->GetExtent().y);
 }
 
 // ---- SkyNode (FrameGraph/SkyNode.cpp:536-563, :611-680, :764-797) --------------------------------------------------------------------------

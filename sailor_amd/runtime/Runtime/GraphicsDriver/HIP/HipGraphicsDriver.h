@@ -25,6 +25,11 @@
 //                                           (or sailor_hip_sky_sun_clouds once the cloud march has been recorded into `cloudsSampler`),
 //                                           {COMPOSE} -> sailor_hip_sky_compose, {CLOUDS} -> sailor_hip_sky_clouds (binding contract: Sky.shader:104-153);
 //                                           every other permutation, "Shaders/Stars.shader" and "Shaders/SunShafts.shader" are created "not ready", never drawn
+//   "Shaders/MotionBlur.shader"          -> sailor_hip_motion_blur       (binding contract: MotionBlur.shader:26-58: set 0 `frameData` / `previousFrameData`,
+//                                           set 1 `data`, `depthSampler`, `colorSampler`) -- only for a driver that opted in with EnableShader
+//   "Shaders/Debug.shader" {} | {AO} | {LIGHT_TILES} | {CASCADES} -> sailor_hip_debug_view (binding contract: Debug.shader:81-113: set 1 `ldrSceneSampler`,
+//                                           `linearDepthSampler`, set 2 `lightsGrid`, `culledLights`, `g_aoSampler`) -- likewise opt-in; any other define set is
+//                                           created "not ready"
 //   "Shaders/Blit.shader" of a material with EBlendMode::AlphaBlending ("Blit Clouds") -> sailor_hip_sky_blit_clouds (binding: `colorSampler`)
 // a scaled one-channel BlitImage with Nearest filtration -> sailor_hip_blit_nearest
 // and the depth-only instanced draws of the shadow passes (material of)
@@ -33,6 +38,8 @@
 #pragma once
 #include <map>
 #include <memory>
+#include <set>
+#include <string>
 #include "../../RHI/GraphicsDriver.h"
 
 namespace Sailor::GraphicsDriver::HIP {
@@ -46,6 +53,13 @@ public:
     int GetLastDispatchStatus() const { return m_lastDispatchStatus; }
     // the prepared views of a `light` SSBO: created with it, derived for every slot on (re-)creation (HipGraphicsDriver.cpp)
     bool EnsurePreparedLights(RHI::RHIShaderBindingPtr binding, bool zeroRecords);
+
+    // Opt this driver in to a shader that has an entry point but is not routed by default: "Shaders/MotionBlur.shader", "Shaders/Debug.shader".  CreateShader
+    // marks them ready only afterwards (Debug.shader only under a define set that has an entry point); without the opt-in it behaves as it always did.  As with
+    // the Bloom node class, the opt-in exists only because older tests of this mirror use MotionBlur.shader as their example of a shader WITHOUT an entry point
+    // (a PostProcess entry that must be created and record nothing); in the engine the backend would simply route both.  false for any other path.
+    bool EnableShader(const std::string& assetPath);
+    bool IsShaderEnabled(const std::string& assetPath) const { return m_enabledShaders.count(assetPath) != 0; }
 
     // IGraphicsDriver
     void WaitIdle() override;
@@ -128,6 +142,8 @@ private:
     int RecordEvsmBlur(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target, bool vertical);
     int RecordHbao(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target);
     int RecordHbaoBlur(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target, bool vertical);
+    int RecordMotionBlur(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target);
+    int RecordDebugView(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target, int mode);
     int RecordSky(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target, int permutation);
     int RecordSkyClouds(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target);
     int RecordBlitAlphaBlended(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target);
@@ -138,6 +154,7 @@ private:
     std::shared_ptr<SailorHipContext> m_ctxOwner;   // destroyed with the last buffer that still refers to it
     int m_status = 0;
     int m_lastDispatchStatus = 0;
+    std::set<std::string> m_enabledShaders; // EnableShader
     // SkyNode's m_pCloudsTexture while the last thing recorded into it was the cloud march: the SUN draw that samples it (one material for the clear and the
     // march, SkyNode.cpp:611-642) goes through sailor_hip_sky_sun_clouds then, through sailor_hip_sky_sun otherwise.  Reset by every write (BeforeBufferWrite)
     const void* m_marchedClouds = nullptr;

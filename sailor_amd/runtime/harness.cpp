@@ -66,6 +66,18 @@ RT_API int sailor_rt_enable_node(SailorRuntime* rt, const char* name)
     return 0;
 }
 
+// Opt this runtime's driver in to a shader that has an entry point but is not routed by default: "Shaders/MotionBlur.shader" or "Shaders/Debug.shader" (the
+// frame's tail).  PostProcess nodes created afterwards find the shader ready and draw with it; a runtime that did not opt in keeps creating it "not ready",
+// so its nodes record nothing, and sailor_rt_enable_node("MotionBlur") keeps failing: there is no such node class.  In the engine the backend would simply route
+// both; as with Bloom, the opt-in exists only because this mirror's older tests use MotionBlur.shader as their example of a shader without an entry point.
+// 0, or -1 for any other path or a null runtime.
+RT_API int sailor_rt_enable_shader(SailorRuntime* rt, const char* path)
+{
+    if (!rt || !path || !rt->renderer) return -1;
+    auto* hip = static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver());
+    return hip && hip->EnableShader(path) ? 0 : -1;
+}
+
 // builds the graph from node names, as FrameGraphImporter does from the .renderer YAML (FrameGraphParser.cpp:153)
 RT_API int sailor_rt_build_graph(SailorRuntime* rt, const char** nodeNames, int count)
 {
@@ -715,6 +727,15 @@ RT_API int sailor_rt_process_frame_overwriting_lists(SailorRuntime* rt, const vo
     driver->SubmitCommandList(cmdList);
     rt->frames++;
     return static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(driver)->GetLastDispatchStatus();
+}
+
+// the launch log of the driver's context (sailor_hip_context_launch_log): how many kernels the frames recorded so far, and the names of the last few --
+// what lets a test say that a node recorded nothing
+RT_API int sailor_rt_launch_log(SailorRuntime* rt, uint64_t* outCount, const char** outNames, int maxNames)
+{
+    if (!rt) return -1;
+    auto* hip = static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver());
+    return hip ? sailor_hip_context_launch_log(hip->GetContext(), outCount, outNames, maxNames) : -1;
 }
 
 RT_API void sailor_rt_wait_idle(SailorRuntime*) { Renderer::GetDriver()->WaitIdle(); }

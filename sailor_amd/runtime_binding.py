@@ -63,6 +63,8 @@ def load() -> C.CDLL:
         rt.sailor_rt_set_color_target.argtypes = [P, C.c_char_p, P, C.c_int, C.c_int]
         rt.sailor_rt_set_time.argtypes = [P, C.c_float, C.c_float]
         rt.sailor_rt_enable_node.argtypes = [P, C.c_char_p]
+        rt.sailor_rt_enable_shader.argtypes = [P, C.c_char_p]
+        rt.sailor_rt_launch_log.argtypes = [P, C.POINTER(C.c_uint64), C.POINTER(C.c_char_p), C.c_int]
         rt.sailor_rt_set_color_target_chain.argtypes = [P, C.c_char_p, P, C.c_int, C.c_int, C.c_int]
         rt.sailor_rt_eye_adaptation_state.argtypes = [P, C.POINTER(P), C.POINTER(P)]
         rt.sailor_rt_shadow_pass.argtypes = [P, C.POINTER(C.c_float), P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, C.c_uint32, P, C.c_int, C.c_int, C.c_float, C.c_float]
@@ -280,6 +282,20 @@ class Runtime:
         """opt this runtime's graphs in to a node class that is compiled in but not registered ("Bloom"): load_renderer / build_graph then create it"""
         if self.rt.sailor_rt_enable_node(self.h, name.encode()) != 0:
             raise ValueError(f"no opt-in node class {name!r}")
+
+    def enable_shader(self, path: str):
+        """opt this runtime in to a shader that has an entry point but is not routed by default ("Shaders/MotionBlur.shader", "Shaders/Debug.shader"):
+        PostProcess entries loaded afterwards draw with it"""
+        if self.rt.sailor_rt_enable_shader(self.h, path.encode()) != 0:
+            raise ValueError(f"no opt-in shader {path!r}")
+
+    def launch_log(self, max_names: int = 16):
+        """(count, names): how many kernels the driver's context has launched, and the names of the last few, oldest first"""
+        count = C.c_uint64()
+        names = (C.c_char_p * max_names)()
+        if self.rt.sailor_rt_launch_log(self.h, C.byref(count), names, max_names) != 0:
+            raise ValueError("no launch log")
+        return int(count.value), [n.decode() for n in names if n is not None]
 
     def set_time(self, delta_time: float, current_time: float = 0.0):
         """sceneView.m_deltaTime / m_currentTime of the frames processed from here on"""
