@@ -26,9 +26,9 @@
 //     bloomIntensity (16 / 16 of it), and the dirt term, to the destination's alpha.
 //   * u_threshold is the node's (BloomNode.cpp:93): (t, t - knee, 2 knee, 0.25 knee) -- .w is a product where the shader's comment expects a quotient.
 //     Restated, not repaired (sailor_host_bloom_push_constants).
-//   * max(x, y) = x < y ? y : x, min(x, y) = y < x ? y : x, clamp(x, lo, hi) = x < lo ? lo : (x > hi ? hi : x): a NaN passes through clamp.
+//   * max is glsl_max of common.h; clamp(x, lo, hi) = x < lo ? lo : (x > hi ? hi : x): a NaN passes through clamp.
 //   * texture(u_dirt_texture, uv) (u_mip_level == 1 only): four-tap fp32 bilinear with Repeat addressing, no mips
-//     (Content/Textures/Bokeh__Lens_Dirt_9.jpg.asset), over the caller's decoded linear float4 texels -- k_sky_compose's fetch with all four channels.
+//     (Content/Textures/Bokeh__Lens_Dirt_9.jpg.asset), over the caller's decoded linear float4 texels -- sample_repeat_f4 of sampling.h.
 //     A NULL dirt plane means "no dirt term": an extension for hosts without the asset.
 //
 // Shape.  One output texel per lane, a float4 (16 B) each, 256-thread blocks of 64 x 4 texels so that a wave's rows are contiguous in x.  The nine
@@ -37,9 +37,9 @@
 // those rows; the upscale streams the destination once in, once out.  The small levels are one launch each (launch-latency bound; not folded).
 #include "common.h"
 #include "sampling.h"
+#include "texel_pass.h"
 #include <math.h>
 
-#define BLOOM_MAX_EXTENT 32768
 #define BLOOM_MAX_LEVELS 16
 
 struct BloomAxis { int i[3]; }; // the source index of neighbour d = -1, 0, +1; outside [0, readDim) = no texel
@@ -67,7 +67,6 @@ __device__ __forceinline__ float4 bloom_tap(const float4* __restrict__ src, int 
 
 __device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ float4 mul4(float4 a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
-__device__ __forceinline__ float glsl_max(float x, float y) { return x < y ? y : x; }
 
 __device__ __forceinline__ float4 karis_avg(float4 c) // :38-47
 {
@@ -78,7 +77,7 @@ __device__ __forceinline__ float4 karis_avg(float4 c) // :38-47
 __global__ __launch_bounds__(256) void k_bloom_downscale(const float4* __restrict__ src, int RW, int RH, float4* __restrict__ dst, int W, int H,
                                                          float4 threshold, int useThreshold)
 {
-    const int x = (int)(blockIdx.x * 64 + (threadIdx.x & 63)), y = (int)(blockIdx.y * 4 + (threadIdx.x >> 6));
+    const int x = texel_i(), y = texel_j();
     if (x >= W || y >= H) return;
     const BloomAxis ix = bloom_src_index(x, (float)RW, 1.0f / (float)W), iy = bloom_src_index(y, (float)RH, 1.0f / (float)H);
     const float4 A = bloom_tap(src, RW, RH, ix.i[0], iy.i[0]), B = bloom_tap(src, RW, RH, ix.i[1], iy.i[0]), C = bloom_tap(src, RW, RH, ix.i[2], iy.i[0]);
@@ -107,22 +106,11 @@ __global__ __launch_bounds__(256) void k_bloom_downscale(const float4* __restric
     dst[(size_t)y * (size_t)W + x] = c;
 }
 
-// texture() with Linear filtration and Repeat addressing, all four channels
-__device__ __forceinline__ float4 bloom_sample_repeat(const float4* __restrict__ tex, int W, int H, float u, float v)
-{
-    const float x = u * (float)W - 0.5f, y = v * (float)H - 0.5f;
-    const float fx = floorf(x), fy = floorf(y);
-    const float ax = x - fx, ay = y - fy;
-    const int x0 = (((int)fx % W) + W) % W, y0 = (((int)fy % H) + H) % H, x1 = (x0 + 1) % W, y1 = (y0 + 1) % H;
-    const float4 a = tex[(size_t)y0 * W + x0], c = tex[(size_t)y0 * W + x1], d = tex[(size_t)y1 * W + x0], e = tex[(size_t)y1 * W + x1];
-    return make_float4(lerp2(a.x, c.x, d.x, e.x, ax, ay), lerp2(a.y, c.y, d.y, e.y, ax, ay), lerp2(a.z, c.z, d.z, e.z, ax, ay), lerp2(a.w, c.w, d.w, e.w, ax, ay));
-}
-
 template <bool DIRT>
 __global__ __launch_bounds__(256) void k_bloom_upscale(const float4* __restrict__ src, int RW, int RH, float4* __restrict__ dst, int W, int H,
                                                        float bloomIntensity, float dirtIntensity, const float4* __restrict__ dirt, int DW, int DH)
 {
-    const int x = (int)(blockIdx.x * 64 + (threadIdx.x & 63)), y = (int)(blockIdx.y * 4 + (threadIdx.x >> 6));
+    const int x = texel_i(), y = texel_j();
     if (x >= W || y >= H) return;
     const float texelX = 1.0f / (float)W, texelY = 1.0f / (float)H;
     const BloomAxis ix = bloom_src_index(x, (float)RW, texelX), iy = bloom_src_index(y, (float)RH, texelY);
@@ -143,30 +131,27 @@ __global__ __launch_bounds__(256) void k_bloom_upscale(const float4* __restrict_
     out = add4(out, mul4(bloom, bloomIntensity)); // :86
     if (DIRT) { // :88-92
         const float u = ((float)x + 0.5f) * texelX, v = ((float)y + 0.5f) * texelY;
-        const float4 t = mul4(bloom_sample_repeat(dirt, DW, DH, u, v), dirtIntensity);
+        const float4 t = mul4(sample_repeat_f4(dirt, DW, DH, u, v), dirtIntensity);
         out = add4(out, mul4(make_float4(t.x * bloom.x, t.y * bloom.y, t.z * bloom.z, t.w * bloom.w), bloomIntensity));
     }
     *o = out;
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------------
-static bool bloom_extent_ok(int32_t w, int32_t h) { return w > 0 && h > 0 && w <= BLOOM_MAX_EXTENT && h <= BLOOM_MAX_EXTENT; }
-static bool bloom_aligned(const void* p) { return p && ((uintptr_t)p & 15) == 0; }
 static int32_t bloom_half(int32_t d) { return (d >> 1) > 1 ? (d >> 1) : 1; }
-static dim3 bloom_grid(int32_t w, int32_t h) { return dim3((unsigned)((w + 63) / 64), (unsigned)((h + 3) / 4)); }
 
 // `big` and `small` are neighbouring levels of one chain
 static bool bloom_pair_ok(SailorHipContext* ctx, const float* a, float* b, int32_t bigW, int32_t bigH, int32_t smallW, int32_t smallH)
 {
-    return ctx && bloom_aligned(a) && bloom_aligned(b) && a != b && bloom_extent_ok(bigW, bigH) && smallW == bloom_half(bigW) && smallH == bloom_half(bigH);
+    return ctx && aligned(a, 16) && aligned(b, 16) && a != b && extent_ok(bigW, bigH) && smallW == bloom_half(bigW) && smallH == bloom_half(bigH);
 }
-static bool bloom_dirt_ok(const float* dirt, int32_t w, int32_t h) { return !dirt || (bloom_aligned(dirt) && bloom_extent_ok(w, h)); }
+static bool bloom_dirt_ok(const float* dirt, int32_t w, int32_t h) { return !dirt || (aligned(dirt, 16) && extent_ok(w, h)); }
 
 extern "C" {
 
 size_t sailor_hip_mip_chain_texels(int32_t width, int32_t height, int32_t levels)
 {
-    if (!bloom_extent_ok(width, height) || levels < 0 || levels > BLOOM_MAX_LEVELS) return 0;
+    if (!extent_ok(width, height) || levels < 0 || levels > BLOOM_MAX_LEVELS) return 0;
     size_t n = 0;
     for (int32_t l = 0; l < levels; l++) n += (size_t)((width >> l) > 1 ? (width >> l) : 1) * (size_t)((height >> l) > 1 ? (height >> l) : 1);
     return n;
@@ -177,7 +162,7 @@ int sailor_hip_bloom_downscale(SailorHipContext* ctx, const float* dSrc, int32_t
 {
     if (!bloom_pair_ok(ctx, dSrc, dDst, srcWidth, srcHeight, dstWidth, dstHeight) || !threshold4) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
-    sailor_launch(ctx, k_bloom_downscale, bloom_grid(dstWidth, dstHeight), dim3(256), (const float4*)dSrc, (int)srcWidth, (int)srcHeight, (float4*)dDst, (int)dstWidth,
+    sailor_launch(ctx, k_bloom_downscale, texel_grid(dstWidth, dstHeight), dim3(256), (const float4*)dSrc, (int)srcWidth, (int)srcHeight, (float4*)dDst, (int)dstWidth,
                   (int)dstHeight, make_float4(threshold4[0], threshold4[1], threshold4[2], threshold4[3]), useThreshold ? 1 : 0);
     SAILOR_CHECK_LAUNCH(ctx, "k_bloom_downscale");
     return SAILOR_HIP_OK;
@@ -190,10 +175,10 @@ int sailor_hip_bloom_upscale(SailorHipContext* ctx, const float* dSrc, int32_t s
         return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
     if (mipLevel == 1 && dDirt)
-        sailor_launch(ctx, k_bloom_upscale<true>, bloom_grid(dstWidth, dstHeight), dim3(256), (const float4*)dSrc, (int)srcWidth, (int)srcHeight, (float4*)dDst, (int)dstWidth,
+        sailor_launch(ctx, k_bloom_upscale<true>, texel_grid(dstWidth, dstHeight), dim3(256), (const float4*)dSrc, (int)srcWidth, (int)srcHeight, (float4*)dDst, (int)dstWidth,
                       (int)dstHeight, bloomIntensity, dirtIntensity, (const float4*)dDirt, (int)dirtWidth, (int)dirtHeight);
     else
-        sailor_launch(ctx, k_bloom_upscale<false>, bloom_grid(dstWidth, dstHeight), dim3(256), (const float4*)dSrc, (int)srcWidth, (int)srcHeight, (float4*)dDst, (int)dstWidth,
+        sailor_launch(ctx, k_bloom_upscale<false>, texel_grid(dstWidth, dstHeight), dim3(256), (const float4*)dSrc, (int)srcWidth, (int)srcHeight, (float4*)dDst, (int)dstWidth,
                       (int)dstHeight, bloomIntensity, dirtIntensity, (const float4*)nullptr, 0, 0);
     SAILOR_CHECK_LAUNCH(ctx, "k_bloom_upscale");
     return SAILOR_HIP_OK;
@@ -203,7 +188,7 @@ int sailor_hip_bloom(SailorHipContext* ctx, float* dChain, int32_t width, int32_
                      int32_t dirtWidth, int32_t dirtHeight)
 {
     // every argument is checked before the first launch: a refused call records nothing
-    if (!ctx || !bloom_aligned(dChain) || !params || !bloom_extent_ok(width, height) || levels < 2 || levels > BLOOM_MAX_LEVELS || !bloom_dirt_ok(dDirt, dirtWidth, dirtHeight))
+    if (!ctx || !aligned(dChain, 16) || !params || !extent_ok(width, height) || levels < 2 || levels > BLOOM_MAX_LEVELS || !bloom_dirt_ok(dDirt, dirtWidth, dirtHeight))
         return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     float* level[BLOOM_MAX_LEVELS];
     int32_t w[BLOOM_MAX_LEVELS], h[BLOOM_MAX_LEVELS];

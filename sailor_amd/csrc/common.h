@@ -115,3 +115,17 @@ __device__ __forceinline__ float4 glsl_mul(const Mat4& M, float x, float y, floa
     r.w = ((M.m[3] * x + M.m[7] * y) + M.m[11] * z) + M.m[15] * w;
     return r;
 }
+// GLSL min, max and clamp(x, 0, 1) by their definitions.  A NaN fails every comparison, so a NaN x passes through all three and min(1, NaN) = 1;
+// -0 < 0 is false, so -0 stays -0.  min(max(x, 0), 1) and x < 0 ? 0 : (x > 1 ? 1 : x) therefore agree on every input; the first is the one spelling
+// (the compiler does not see them as equal; profiles/r10/README.md has what each costs).
+__device__ __forceinline__ float glsl_min(float x, float y) { return y < x ? y : x; }
+__device__ __forceinline__ float glsl_max(float x, float y) { return x < y ? y : x; }
+__device__ __forceinline__ float glsl_saturate(float x) { return glsl_min(glsl_max(x, 0.0f), 1.0f); }
+
+// the sum of v over the 64 lanes of a wave, in every lane: a butterfly, so the order of the additions is fixed
+__device__ __forceinline__ float wave_sum(float v)
+{
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v = v + __shfl_xor(v, d, 64);
+    return v;
+}

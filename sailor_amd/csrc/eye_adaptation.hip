@@ -31,7 +31,7 @@
 // remainder of a size that is no multiple of 16 is not counted while numPixels stays width x height; the weighted sum is uint32 and wraps
 // at 8K; a black pixel under LUMINANCE divides by X + Y + Z = 0 and comes out NaN (Formats.glsl:18).
 // Defined where GLSL leaves it open: a NaN luminance counts in bin 0, +inf in bin 255, no input indexes outside the 256 bins; clamp()
-// is x < lo ? lo : (x > hi ? hi : x), which passes a NaN through.
+// is glsl_saturate of common.h, which passes a NaN through.
 #include "common.h"
 #include "canonical_math.h"
 #include <math.h>
@@ -50,7 +50,7 @@ __device__ __forceinline__ uint32_t color_to_bin(const float4 c, const float min
     if (!(lum >= 0.005f)) return 0u;                                    // :43-46 (and NaN, which GLSL leaves open)
     if (lum == INFINITY) return 255u;
     float t = (canonical_log2f(lum) - minLog) * invRange;               // :50
-    t = t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
+    t = glsl_saturate(t);
     const float f = t * 254.0f + 1.0f;                                  // :53
     return f < 256.0f ? (uint32_t)f : 255u;                             // (only NaN constants get past the clamp)
 }
@@ -142,7 +142,6 @@ struct TonemapArgs {
     float exposure;
 };
 
-__device__ __forceinline__ float ea_dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
 __host__ __device__ __forceinline__ float uncharted2_partial(float x) // Tonemapping.shader:115-124
 {
     const float A = 0.15f, B = 0.50f, C = 0.10f, D = 0.20f, E = 0.02f, F = 0.30f;
@@ -154,7 +153,6 @@ __device__ __forceinline__ float aces_fit(float v) // :89-94
     const float b = v * (0.983729f * v + 0.4329510f) + 0.238081f;
     return a / b;
 }
-__device__ __forceinline__ float clamp01(float x) { return x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x); }
 
 #define EA_OP_ACES 1
 #define EA_OP_UNCHARTED2 2
@@ -166,21 +164,21 @@ __device__ __forceinline__ float4 tonemap_pixel(const float4 in, const float sca
     constexpr bool ACES = (OPS & EA_OP_ACES) != 0, U2 = !ACES && (OPS & EA_OP_UNCHARTED2) != 0, LUM = (OPS & EA_OP_LUMINANCE) != 0; // :150-154: ACES wins
     float cx, cy, cz, Yx = 0.0f, Yy = 0.0f;
     if (LUM) { // :142-148 + Formats.glsl:1-25
-        const float X = ea_dot3(0.4124564f, 0.3575761f, 0.1804375f, in.x, in.y, in.z);
-        const float Y = ea_dot3(0.2126729f, 0.7151522f, 0.0721750f, in.x, in.y, in.z);
-        const float Z = ea_dot3(0.0193339f, 0.1191920f, 0.9503041f, in.x, in.y, in.z);
-        const float inv = 1.0f / ea_dot3(X, Y, Z, 1.0f, 1.0f, 1.0f);
+        const float X = dot3f(0.4124564f, 0.3575761f, 0.1804375f, in.x, in.y, in.z);
+        const float Y = dot3f(0.2126729f, 0.7151522f, 0.0721750f, in.x, in.y, in.z);
+        const float Z = dot3f(0.0193339f, 0.1191920f, 0.9503041f, in.x, in.y, in.z);
+        const float inv = 1.0f / dot3f(X, Y, Z, 1.0f, 1.0f, 1.0f);
         Yx = X * inv; Yy = Y * inv;
         cx = cy = cz = Y / scale;
     } else { cx = in.x / scale; cy = in.y / scale; cz = in.z / scale; } // :140
     if (ACES) { // :96-109
-        const float ix = aces_fit(ea_dot3(0.59719f, 0.35458f, 0.04823f, cx, cy, cz));
-        const float iy = aces_fit(ea_dot3(0.07600f, 0.90834f, 0.01566f, cx, cy, cz));
-        const float iz = aces_fit(ea_dot3(0.02840f, 0.13383f, 0.83777f, cx, cy, cz));
-        cx = clamp01(ea_dot3(1.60475f, -0.53108f, -0.07367f, ix, iy, iz));
+        const float ix = aces_fit(dot3f(0.59719f, 0.35458f, 0.04823f, cx, cy, cz));
+        const float iy = aces_fit(dot3f(0.07600f, 0.90834f, 0.01566f, cx, cy, cz));
+        const float iz = aces_fit(dot3f(0.02840f, 0.13383f, 0.83777f, cx, cy, cz));
+        cx = glsl_saturate(dot3f(1.60475f, -0.53108f, -0.07367f, ix, iy, iz));
         if (!LUM) { // under LUMINANCE only color.x reaches the output (:157)
-            cy = clamp01(ea_dot3(-0.10208f, 1.10813f, -0.00605f, ix, iy, iz));
-            cz = clamp01(ea_dot3(-0.00327f, -0.07276f, 1.07602f, ix, iy, iz));
+            cy = glsl_saturate(dot3f(-0.10208f, 1.10813f, -0.00605f, ix, iy, iz));
+            cz = glsl_saturate(dot3f(-0.00327f, -0.07276f, 1.07602f, ix, iy, iz));
         }
     } else if (U2) { // :126-131
         cx = uncharted2_partial(cx * A.exposure) * A.whiteScale[0];
@@ -191,9 +189,9 @@ __device__ __forceinline__ float4 tonemap_pixel(const float4 in, const float sca
     }
     if (LUM) { // :157 + Formats.glsl:27-51
         const float X = cx * Yx / Yy, Y = cx, Z = cx * ((1.0f - Yx) - Yy) / Yy;
-        cx = ea_dot3(3.2404542f, -1.5371385f, -0.4985314f, X, Y, Z);
-        cy = ea_dot3(-0.9692660f, 1.8760108f, 0.0415560f, X, Y, Z);
-        cz = ea_dot3(0.0556434f, -0.2040259f, 1.0572252f, X, Y, Z);
+        cx = dot3f(3.2404542f, -1.5371385f, -0.4985314f, X, Y, Z);
+        cy = dot3f(-0.9692660f, 1.8760108f, 0.0415560f, X, Y, Z);
+        cz = dot3f(0.0556434f, -0.2040259f, 1.0572252f, X, Y, Z);
     }
     return make_float4(cx, cy, cz, in.w); // alpha is the sampled texel's (:137)
 }

@@ -16,7 +16,7 @@
 // Decisions where "as written" needs one (HBAO.shader line numbers):
 //   * main() normalises the normal a second time (:199 around :116): both are kept.
 //   * ClipSpaceToViewSpace is fed (uv.x, uv.y, depth, 1) -- texture coordinates, not NDC (:91, :112-114).  Literal.
-//   * depthSampler / aoSampler: bilinear, clamp-to-edge = bilinear_taps + lerp2 of sampling.h.  SnapTexel puts most sample points on texel corners, but
+//   * depthSampler / aoSampler: bilinear, clamp-to-edge = sample_clamp_f1 of sampling.h.  SnapTexel puts most sample points on texel corners, but
 //     (k * (1 / W)) * W is not always k in fp32, so the weights are not always one half: the four taps are evaluated, there is no "corner depth" plane.
 //   * noiseSampler: nearest, repeat (Content/Textures/Noise.png.asset:5-6): texel floor(u * nw) mod nw of the caller's decoded linear float4 texels.
 //   * round() of SnapTexel is round-half-to-even (rintf = v_rndne_f32); GLSL leaves the tie open.
@@ -24,9 +24,10 @@
 //     is NaN and min(x, y) = "y < x ? y : x" returns data.occlusionRadius: sampleRadius = occlusionRadius.  The else branch (:215-219) is dead.
 //   * sinS = sin(PI / 2 - acos(x)) (:133) is x; implemented as x (no clamp: a NaN stays NaN and fails both comparisons of :135).  acos' GLSL precision
 //     is far wider than the difference, and the pass then has no transcendental function at all.  tests/hbao_ref.py's float64 form keeps sin / acos.
-//   * saturate(x) = x < 0 ? 0 : (x > 1 ? 1 : x): a NaN passes through and becomes 0 only in the final store.
+//   * saturate(x) = glsl_saturate of common.h: a NaN passes through and becomes 0 only in the final store.
 //   * hostile depth (0, inf, NaN) makes sample coordinates non-finite; the float -> int conversion of the tap computation is then the saturating one
-//     with NaN -> 0 (what v_cvt_i32_f32 does), spelled out in taps_saturating below instead of left to an undefined C++ cast.
+//     with NaN -> 0 (what v_cvt_i32_f32 does), spelled out in bilinear_taps_saturating of sampling.h instead of left to an undefined C++ cast
+//     (sampling.h's header says why the library has both).
 //   * the sky check (:190-194) and screenSpaceRadius < 1 (:225) store 1; distanceFactor (:138) is not clamped and may be negative.
 //   * only .r of the targets exists.
 //
@@ -36,40 +37,9 @@
 // The blur is one destination texel per lane as well: 2 + 4 * radius bilinear fetches, of which the AO taps hit the cache.
 #include "common.h"
 #include "sampling.h"
+#include "texel_pass.h"
 #include "canonical_math.h"
 #include <math.h>
-#include <limits.h>
-
-// float -> int as v_cvt_i32_f32 defines it: NaN -> 0, saturating at the ends of int32
-__device__ __forceinline__ int cvt_i32_saturating(float x)
-{
-    if (x != x) return 0;
-    if (x >= 2147483648.0f) return INT_MAX;
-    if (x <= -2147483648.0f) return INT_MIN;
-    return (int)x;
-}
-
-// bilinear_taps of sampling.h (the same float arithmetic, the same taps wherever its cast is defined) with the conversion above; the clamp runs before
-// the + 1, so no integer overflows either
-__device__ __forceinline__ BilinearTaps taps_saturating(int W, int H, float u, float v)
-{
-    BilinearTaps t;
-    const float x = u * (float)W - 0.5f, y = v * (float)H - 0.5f;
-    const float fx = floorf(x), fy = floorf(y);
-    t.ax = x - fx; t.ay = y - fy;
-    const int x0 = min(max(cvt_i32_saturating(fx), -1), W - 1), y0 = min(max(cvt_i32_saturating(fy), -1), H - 1);
-    t.x0 = max(x0, 0); t.x1 = min(x0 + 1, W - 1);
-    t.y0 = max(y0, 0); t.y1 = min(y0 + 1, H - 1);
-    return t;
-}
-
-__device__ __forceinline__ float sample_plane(const float* __restrict__ p, int W, int H, float u, float v)
-{
-    const BilinearTaps t = taps_saturating(W, H, u, v);
-    const float* __restrict__ r0 = p + (size_t)t.y0 * (size_t)W;
-    const float* __restrict__ r1 = p + (size_t)t.y1 * (size_t)W;
-    return lerp2(r0[t.x0], r0[t.x1], r1[t.x0], r1[t.x1], t.ax, t.ay);
-}
 
 // what texture() returns from an R8_UNORM target after v was written to it; NaN -> 0
 __device__ __forceinline__ float store_unorm8(float v)
@@ -78,13 +48,11 @@ __device__ __forceinline__ float store_unorm8(float v)
     return rintf(c * 255.0f) / 255.0f;
 }
 
-__device__ __forceinline__ float saturate_glsl(float x) { return x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x); }
-
 // ---- a. nearest down-scaling blit -------------------------------------------------------------------------------------------------------
 // the source texel that contains the destination texel's centre: ((2 i + 1) srcW) / (2 dstW) in integers
 __global__ __launch_bounds__(256) void k_blit_nearest(const float* __restrict__ src, int srcW, int srcH, float* __restrict__ dst, int dstW, int dstH)
 {
-    const int i = (int)(blockIdx.x * 64 + (threadIdx.x & 63)), j = (int)(blockIdx.y * 4 + (threadIdx.x >> 6));
+    const int i = texel_i(), j = texel_j();
     if (i >= dstW || j >= dstH) return;
     const int sx = (int)(((long long)(2 * (long long)i + 1) * srcW) / (2 * (long long)dstW));
     const int sy = (int)(((long long)(2 * (long long)j + 1) * srcH) / (2 * (long long)dstH));
@@ -132,22 +100,22 @@ __constant__ float c_hbaoDirections[16] = { // :69-79
 __global__ __launch_bounds__(256) void k_hbao(const float* __restrict__ depth, int DW, int DH, const float4* __restrict__ noise, int NW, int NH,
                                               float* __restrict__ ao, int W, int H, const HbaoArgs A)
 {
-    const int i = (int)(blockIdx.x * 64 + (threadIdx.x & 63)), j = (int)(blockIdx.y * 4 + (threadIdx.x >> 6));
+    const int i = texel_i(), j = texel_j();
     if (i >= W || j >= H) return;
     float* __restrict__ out = ao + (size_t)j * (size_t)W + i;
     const float u = ((float)i + 0.5f) / (float)W, v = ((float)j + 0.5f) / (float)H;
     const float sizeX = (float)DW, sizeY = (float)DH;     // :196 depthTextureSize
     const float invX = 1.0f / sizeX, invY = 1.0f / sizeY; // rcp(depthTextureSize)
 
-    const float d = sample_plane(depth, DW, DH, u, v);
+    const float d = sample_clamp_f1(depth, DW, DH, u, v);
     V3 P = clip_to_view(A.invProjection, u, v, d); // :187
     if (P.z > 49000.0f) { *out = store_unorm8(1.0f); return; } // :190-194
 
     V3 N;
     { // :94-117 GetViewSpaceNormal, then :199
         const float uL = u + -1.0f * invX, uR = u + 1.0f * invX, vD = v + -1.0f * invY, vU = v + 1.0f * invY;
-        const float dL = sample_plane(depth, DW, DH, uL, v), dR = sample_plane(depth, DW, DH, uR, v);
-        const float dD = sample_plane(depth, DW, DH, u, vD), dU = sample_plane(depth, DW, DH, u, vU);
+        const float dL = sample_clamp_f1(depth, DW, DH, uL, v), dR = sample_clamp_f1(depth, DW, DH, uR, v);
+        const float dD = sample_clamp_f1(depth, DW, DH, u, vD), dU = sample_clamp_f1(depth, DW, DH, u, vU);
         const float ddx = smaller_abs_delta(dL, d, dR), ddy = smaller_abs_delta(dD, d, dU);
         const V3 r = clip_to_view(A.invProjection, uR, v, d + ddx), t = clip_to_view(A.invProjection, u, vU, d + ddy);
         const V3 right = {r.x - P.x, r.y - P.y, r.z - P.z}, up = {t.x - P.x, t.y - P.y, t.z - P.z};
@@ -161,7 +129,7 @@ __global__ __launch_bounds__(256) void k_hbao(const float* __restrict__ depth, i
     float4 nz;
     { // :203 nearest, repeat
         const int kx = cvt_i32_saturating(floorf((u * A.p.noiseScale) * (float)NW)), ky = cvt_i32_saturating(floorf((v * A.p.noiseScale) * (float)NH));
-        const int tx = ((kx % NW) + NW) % NW, ty = ((ky % NH) + NH) % NH;
+        const int tx = wrap_tap(kx, NW), ty = wrap_tap(ky, NH);
         nz = noise[(size_t)ty * NW + tx];
     }
     const float offX = (nz.x * 2.0f - 1.0f) / 4.0f, offY = (nz.y * 2.0f - 1.0f) / 4.0f; // :204
@@ -198,14 +166,14 @@ __global__ __launch_bounds__(256) void k_hbao(const float* __restrict__ depth, i
         for (int s = 0; s < 8; s++) { // :174-180
             const float t = (float)s / 8.0f;
             const float su = snap_texel(startX * (1.0f - t) + endX * t, sizeX, invX), sv = snap_texel(startY * (1.0f - t) + endY * t, sizeY, invY);
-            const V3 S = clip_to_view(A.invProjection, su, sv, sample_plane(depth, DW, DH, su, sv));
+            const V3 S = clip_to_view(A.invProjection, su, sv, sample_clamp_f1(depth, DW, DH, su, sv));
             // :124-145 SampleAO
             const V3 hv = {S.x - P.x, S.y - P.y, S.z - P.z};
             const float len = sqrtf(dot3f(hv.x, hv.y, hv.z, hv.x, hv.y, hv.z));
             const float sinS = dot3f(N.x, N.y, N.z, hv.x / len, hv.y / len, hv.z / len); // :133
             float occ = 0.0f;
             if (len < R2 && sinS > sinH + bias3) { // :135
-                const float falloffZ = 1.0f - saturate_glsl(fabsf(hv.z) * 0.007f);
+                const float falloffZ = 1.0f - glsl_saturate(fabsf(hv.z) * 0.007f);
                 const float distanceFactor = 1.0f - (len * invR2) * invAtt;
                 occ = ((sinS - sinH) * distanceFactor) * falloffZ;
                 sinH = sinS;
@@ -214,7 +182,7 @@ __global__ __launch_bounds__(256) void k_hbao(const float* __restrict__ depth, i
         }
         occlusionFactor = occlusionFactor + occlusion;
     }
-    *out = store_unorm8(1.0f - saturate_glsl((A.p.occlusionPower / 8.0f) * occlusionFactor)); // :247
+    *out = store_unorm8(1.0f - glsl_saturate((A.p.occlusionPower / 8.0f) * occlusionFactor)); // :247
 }
 
 // ---- c. the bilateral blur pass ---------------------------------------------------------------------------------------------------------
@@ -222,18 +190,18 @@ template <bool VERTICAL>
 __global__ __launch_bounds__(256) void k_hbao_blur(const float* __restrict__ ao, int AW, int AH, const float* __restrict__ depth, int DW, int DH,
                                                    float* __restrict__ dst, int W, int H, const SailorHbaoBlurParams p)
 {
-    const int i = (int)(blockIdx.x * 64 + (threadIdx.x & 63)), j = (int)(blockIdx.y * 4 + (threadIdx.x >> 6));
+    const int i = texel_i(), j = texel_j();
     if (i >= W || j >= H) return;
     const float u = ((float)i + 0.5f) / (float)W, v = ((float)j + 0.5f) / (float)H;
     const float pixX = VERTICAL ? 0.0f : 1.0f / (float)DW, pixY = VERTICAL ? 1.0f / (float)DH : 0.0f; // HBAO_Blur.shader:84-90
-    const float centerD = sample_plane(depth, DW, DH, u, v);
-    float totalC = sample_plane(ao, AW, AH, u, v), totalW = 1.0f; // :92-96
+    const float centerD = sample_clamp_f1(depth, DW, DH, u, v);
+    float totalC = sample_clamp_f1(ao, AW, AH, u, v), totalW = 1.0f; // :92-96
     const float sigma = p.radius * p.sharpness;                      // :72
     const float falloff = 1.0f / ((2.0f * sigma) * sigma);           // :73
     for (int side = 0; side < 2; side++) // :98-108: all + taps, then all - taps
         for (float r = 1.0f; r <= p.radius; r += 1.0f) {
             const float su = side ? u - pixX * r : u + pixX * r, sv = side ? v - pixY * r : v + pixY * r;
-            const float c = sample_plane(ao, AW, AH, su, sv), d = sample_plane(depth, DW, DH, su, sv); // :69-70
+            const float c = sample_clamp_f1(ao, AW, AH, su, sv), d = sample_clamp_f1(depth, DW, DH, su, sv); // :69-70
             const float diff = (d - centerD) * p.distanceScale;                                        // :75
             const float w = canonical_exp2f(((-r * r) * falloff) - diff * diff);                       // :76
             totalW = totalW + w;
@@ -243,10 +211,7 @@ __global__ __launch_bounds__(256) void k_hbao_blur(const float* __restrict__ ao,
 }
 
 // ---- entry points -----------------------------------------------------------------------------------------------------------------------
-#define HBAO_MAX_EXTENT 32768
 #define HBAO_MAX_BLUR_RADIUS 64.0f
-static bool extent_ok(int32_t w, int32_t h) { return w > 0 && h > 0 && w <= HBAO_MAX_EXTENT && h <= HBAO_MAX_EXTENT; }
-static dim3 texel_grid(int32_t w, int32_t h) { return dim3((unsigned)((w + 63) / 64), (unsigned)((h + 3) / 4)); }
 
 static bool blit_args_ok(SailorHipContext* ctx, const float* s, int32_t sw, int32_t sh, float* d, int32_t dw, int32_t dh)
 {
@@ -255,7 +220,7 @@ static bool blit_args_ok(SailorHipContext* ctx, const float* s, int32_t sw, int3
 static bool hbao_args_ok(SailorHipContext* ctx, const SailorUboFrameData* frame, const float* d, int32_t dw, int32_t dh, const float* n, int32_t nw, int32_t nh,
                          const SailorHbaoParams* p, float* ao, int32_t w, int32_t h)
 {
-    return ctx && frame && d && n && p && ao && d != ao && ((uintptr_t)n & 15) == 0 && extent_ok(dw, dh) && extent_ok(nw, nh) && extent_ok(w, h);
+    return ctx && frame && d && p && ao && d != ao && aligned(n, 16) && extent_ok(dw, dh) && extent_ok(nw, nh) && extent_ok(w, h);
 }
 static bool blur_args_ok(SailorHipContext* ctx, const float* a, int32_t aw, int32_t ah, const float* d, int32_t dw, int32_t dh, const SailorHbaoBlurParams* p,
                          float* o, int32_t w, int32_t h)

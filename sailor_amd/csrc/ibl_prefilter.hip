@@ -10,6 +10,7 @@
 // the canonical cube sampler -- is the oracle's arithmetic.  Tolerance-checked like the rest of the shading path.
 #include "common.h"
 #include "sampling.h"
+#include "texel_pass.h"
 
 #define PF_TWO_PI 6.283185307179586f
 #define PF_PI 3.14159265359f
@@ -56,13 +57,6 @@ __device__ __forceinline__ void pf_to_world(const PfFrame& f, float hx, float hy
     oz = (f.Sz * hx + f.Tz * hy) + f.Nz * hz;
 }
 
-__device__ __forceinline__ float pf_wave_sum(float v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 // ---- ComputeIrradianceMap.shader:78-101 ----
 #define IRR_SAMPLES (64u * 1024u)
 __global__ __launch_bounds__(256) void k_irradiance_map(const float4* __restrict__ env, int envSize, int envLevels, float4* __restrict__ out, int size)
@@ -87,7 +81,7 @@ __global__ __launch_bounds__(256) void k_irradiance_map(const float4* __restrict
         const float4 t = cube_sample_level(env, envSize, 0, sface, ss, st);
         r += (2.0f * t.x) * cosTheta; g += (2.0f * t.y) * cosTheta; b += (2.0f * t.z) * cosTheta;
     }
-    r = pf_wave_sum(r); g = pf_wave_sum(g); b = pf_wave_sum(b);
+    r = wave_sum(r); g = wave_sum(g); b = wave_sum(b);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) { sPart[0][wave] = r; sPart[1][wave] = g; sPart[2][wave] = b; }
     __syncthreads();
@@ -134,7 +128,7 @@ __global__ __launch_bounds__(256) void k_prefilter_env(const float4* __restrict_
             weight += cosLi;
         }
     }
-    r = pf_wave_sum(r); g = pf_wave_sum(g); b = pf_wave_sum(b); weight = pf_wave_sum(weight);
+    r = wave_sum(r); g = wave_sum(g); b = wave_sum(b); weight = wave_sum(weight);
     if (lane == 0) outLevel[texel] = make_float4(r / weight, g / weight, b / weight, 1.0f);
 }
 
@@ -144,7 +138,7 @@ __global__ __launch_bounds__(256) void k_prefilter_env(const float4* __restrict_
 __global__ __launch_bounds__(256) void k_equirect_to_cube(const float4* __restrict__ equirect, int eqW, int eqH, int repeat,
                                                           float4* __restrict__ cube, int size, int coverW, int coverH)
 {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6), face = blockIdx.z;
+    const int x = texel_i(), y = texel_j(), face = blockIdx.z;
     if (x >= size || y >= size || x >= coverW || y >= coverH) return;
     const float PI = 3.141592f, TwoPI = 2.0f * PI;
     const PfFrame f = pf_frame(x, y, face, size); // the same face table (ComputeEquirect2Cube.shader:27-33), before normalisation
@@ -156,8 +150,8 @@ __global__ __launch_bounds__(256) void k_equirect_to_cube(const float4* __restri
     const float ax = px - fx, ay = py - fy;
     int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
     if (repeat) {
-        x0 = ((x0 % eqW) + eqW) % eqW; x1 = ((x1 % eqW) + eqW) % eqW;
-        y0 = ((y0 % eqH) + eqH) % eqH; y1 = ((y1 % eqH) + eqH) % eqH;
+        x0 = wrap_tap(x0, eqW); x1 = wrap_tap(x1, eqW);
+        y0 = wrap_tap(y0, eqH); y1 = wrap_tap(y1, eqH);
     } else {
         x0 = min(max(x0, 0), eqW - 1); x1 = min(max(x1, 0), eqW - 1);
         y0 = min(max(y0, 0), eqH - 1); y1 = min(max(y1, 0), eqH - 1);
@@ -186,13 +180,14 @@ extern "C" {
 int sailor_hip_equirect_to_cube(SailorHipContext* ctx, const float* dEquirect, int32_t eqWidth, int32_t eqHeight, int32_t repeat,
                                 float* dCube, int32_t size, int32_t coverWidth, int32_t coverHeight)
 {
-    if (!ctx || !dEquirect || !dCube || eqWidth <= 0 || eqHeight <= 0 || eqWidth > 32768 || eqHeight > 32768 || size <= 0 || size > 8192)
-        return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (!ctx || !dEquirect || !dCube || !extent_ok(eqWidth, eqHeight) || size <= 0 || size > 8192) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     if (((uintptr_t)dEquirect & 15) || ((uintptr_t)dCube & 15) || coverWidth < 0 || coverHeight < 0) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device)); // a host thread may drive several contexts
     const int cw = coverWidth < size ? coverWidth : size, ch = coverHeight < size ? coverHeight : size;
     if (cw == 0 || ch == 0) return SAILOR_HIP_OK;
-    hipLaunchKernelGGL(k_equirect_to_cube, dim3((cw + 63) / 64, (ch + 3) / 4, 6), dim3(256), 0, ctx->stream,
+    dim3 grid = texel_grid(cw, ch);
+    grid.z = 6;
+    hipLaunchKernelGGL(k_equirect_to_cube, grid, dim3(256), 0, ctx->stream,
                        (const float4*)dEquirect, eqWidth, eqHeight, repeat ? 1 : 0, (float4*)dCube, size, cw, ch);
     SAILOR_CHECK_LAUNCH(ctx, "k_equirect_to_cube");
     return SAILOR_HIP_OK;

@@ -15,13 +15,13 @@
 //   * inverse(frame.projection) (:69), inverse(frame.view) (:72) and previousFrame.projection * previousFrame.view (:74) are uniform per draw: the entry
 //     point computes them once on the host with host_math.cpp's inverse / mul (glm's order, what sailor_host_mat4_inverse / _mul export) and passes them
 //     by value.  frame.invProjection is NOT used: the shader writes the literal inverse().
-//   * min(x, y) = y < x ? y : x, max(x, y) = x < y ? y : x (the GLSL definitions), so min(1, NaN) = 1 (:81-82).  On the first frame previousFrame is all
+//   * min, max and clamp(x, 0, 1) are the GLSL definitions of common.h, so min(1, NaN) = 1 (:81-82).  On the first frame previousFrame is all
 //     zeros (RHIFrameGraph.cpp:189: m_prevFrameData is value-initialised), previousClipPos is 0 / 0 everywhere and the velocity is (intensity, intensity).
 //   * no lower clamp on the velocity (:81-82 clamp above only): a large negative velocity piles the taps up on the 0 edge.
-//   * clamp(x, 0, 1) = min(max(x, 0), 1) (:95); the early-out is length(velocity) <= 0.0001 (:87) -- a NaN length fails it and blurs.
+//   * clamp(x, 0, 1) (:95) passes a NaN through; the early-out is length(velocity) <= 0.0001 (:87) -- a NaN length fails it and blurs.
 //   * int(data.samples) truncates, the loop runs int(samples) - 1 taps (:93), the division is by float(data.samples) itself (:100).  Alpha is 1.
 //   * depthSampler / colorSampler: bilinear, clamp-to-edge, the taps and weights of sampling.h evaluated per fetch, with the saturating float -> int
-//     conversion (NaN -> 0) hbao.hip documents for non-finite coordinates.
+//     conversion (NaN -> 0) its header documents for non-finite coordinates (bilinear_taps_saturating).
 // Debug.shader line numbers:
 //   * no define: texture(ldrSceneSampler, uv) (:117).  AO (:120): the one-channel g_aoSampler, bilinear, broadcast to four channels.
 //   * LIGHT_TILES (:122-144), literal: screenUv.y = viewportSize.y - gl_FragCoord.y, tileId = ivec2(screenUv) / 16, numTiles = floor(viewportSize / 16)
@@ -40,52 +40,8 @@
 // count pass, which would add a launch, a workspace and a dependency for 0.4 % of the frame's texels' worth of reads.  Not measured against it.
 #include "common.h"
 #include "sampling.h"
+#include "texel_pass.h"
 #include <math.h>
-#include <limits.h>
-
-// float -> int as v_cvt_i32_f32 defines it: NaN -> 0, saturating at the ends of int32 (hbao.hip)
-__device__ __forceinline__ int tail_cvt_i32(float x)
-{
-    if (x != x) return 0;
-    if (x >= 2147483648.0f) return INT_MAX;
-    if (x <= -2147483648.0f) return INT_MIN;
-    return (int)x;
-}
-
-// bilinear_taps of sampling.h with the conversion above; the clamp runs before the + 1, so no integer overflows
-__device__ __forceinline__ BilinearTaps tail_taps(int W, int H, float u, float v)
-{
-    BilinearTaps t;
-    const float x = u * (float)W - 0.5f, y = v * (float)H - 0.5f;
-    const float fx = floorf(x), fy = floorf(y);
-    t.ax = x - fx; t.ay = y - fy;
-    const int x0 = min(max(tail_cvt_i32(fx), -1), W - 1), y0 = min(max(tail_cvt_i32(fy), -1), H - 1);
-    t.x0 = max(x0, 0); t.x1 = min(x0 + 1, W - 1);
-    t.y0 = max(y0, 0); t.y1 = min(y0 + 1, H - 1);
-    return t;
-}
-
-__device__ __forceinline__ float tail_sample_plane(const float* __restrict__ p, int W, int H, float u, float v)
-{
-    const BilinearTaps t = tail_taps(W, H, u, v);
-    const float* __restrict__ r0 = p + (size_t)t.y0 * (size_t)W;
-    const float* __restrict__ r1 = p + (size_t)t.y1 * (size_t)W;
-    return lerp2(r0[t.x0], r0[t.x1], r1[t.x0], r1[t.x1], t.ax, t.ay);
-}
-
-__device__ __forceinline__ float4 tail_sample_rgba(const float4* __restrict__ p, int W, int H, float u, float v)
-{
-    const BilinearTaps t = tail_taps(W, H, u, v);
-    const float4* __restrict__ r0 = p + (size_t)t.y0 * (size_t)W;
-    const float4* __restrict__ r1 = p + (size_t)t.y1 * (size_t)W;
-    const float4 a = r0[t.x0], c = r0[t.x1], d = r1[t.x0], e = r1[t.x1];
-    return make_float4(lerp2(a.x, c.x, d.x, e.x, t.ax, t.ay), lerp2(a.y, c.y, d.y, e.y, t.ax, t.ay), lerp2(a.z, c.z, d.z, e.z, t.ax, t.ay),
-                       lerp2(a.w, c.w, d.w, e.w, t.ax, t.ay));
-}
-
-__device__ __forceinline__ float glsl_min(float x, float y) { return y < x ? y : x; }
-__device__ __forceinline__ float glsl_max(float x, float y) { return x < y ? y : x; }
-__device__ __forceinline__ float glsl_clamp01(float x) { return glsl_min(glsl_max(x, 0.0f), 1.0f); }
 
 // ---- a. motion blur -----------------------------------------------------------------------------------------------------------------------
 struct MotionBlurArgs {
@@ -98,12 +54,12 @@ struct MotionBlurArgs {
 __global__ __launch_bounds__(256) void k_motion_blur(const float* __restrict__ depth, int DW, int DH, const float4* __restrict__ color, int CW, int CH,
                                                      float4* __restrict__ dst, int W, int H, const MotionBlurArgs A)
 {
-    const int i = (int)(blockIdx.x * 64 + (threadIdx.x & 63)), j = (int)(blockIdx.y * 4 + (threadIdx.x >> 6));
+    const int i = texel_i(), j = texel_j();
     if (i >= W || j >= H) return;
     float4* __restrict__ out = dst + (size_t)j * (size_t)W + i;
     const float u = ((float)i + 0.5f) / (float)W, v = ((float)j + 0.5f) / (float)H;
 
-    const float d = tail_sample_plane(depth, DW, DH, u, v); // :65
+    const float d = sample_clamp_f1(depth, DW, DH, u, v); // :65
     const float ndcX = u * 2.0f - 1.0f, ndcY = v * 2.0f - 1.0f; // :66
     float4 viewPos = glsl_mul(A.invProjection, ndcX, ndcY, d, 1.0f); // :69
     const float vw = viewPos.w;
@@ -116,15 +72,15 @@ __global__ __launch_bounds__(256) void k_motion_blur(const float* __restrict__ d
     velX = glsl_min(1.0f, velX) * A.p.intensity;                      // :81
     velY = glsl_min(1.0f, velY) * A.p.intensity;                      // :82
 
-    const float4 c0 = tail_sample_rgba(color, CW, CH, u, v); // :84
+    const float4 c0 = sample_clamp_f4_saturating(color, CW, CH, u, v); // :84
     float r = c0.x, g = c0.y, b = c0.z;
     if (sqrtf(velX * velX + velY * velY) <= 0.0001f) { *out = make_float4(r, g, b, 1.0f); return; } // :87-91
 
     float tu = u, tv = v;
     const int n = (int)A.p.samples; // the entry point keeps samples within [1, 64]
     for (int k = 1; k < n; k++) {   // :93-98
-        tu = glsl_clamp01(tu + velX); tv = glsl_clamp01(tv + velY);
-        const float4 c = tail_sample_rgba(color, CW, CH, tu, tv);
+        tu = glsl_saturate(tu + velX); tv = glsl_saturate(tv + velY);
+        const float4 c = sample_clamp_f4_saturating(color, CW, CH, tu, tv);
         r = r + c.x; g = g + c.y; b = b + c.z;
     }
     *out = make_float4(r / A.p.samples, g / A.p.samples, b / A.p.samples, 1.0f); // :100-101
@@ -144,14 +100,14 @@ __global__ __launch_bounds__(256) void k_debug_view(const float4* __restrict__ s
                                                     const SailorLightsGrid* __restrict__ grid, const uint32_t* __restrict__ culled, const float* __restrict__ ao,
                                                     int AW, int AH, float4* __restrict__ dst, int W, int H, const DebugViewArgs A)
 {
-    const int i = (int)(blockIdx.x * 64 + (threadIdx.x & 63)), j = (int)(blockIdx.y * 4 + (threadIdx.x >> 6));
+    const int i = texel_i(), j = texel_j();
     if (i >= W || j >= H) return;
     float4* __restrict__ out = dst + (size_t)j * (size_t)W + i;
     const float u = ((float)i + 0.5f) / (float)W, v = ((float)j + 0.5f) / (float)H;
 
-    if (MODE == SAILOR_DEBUG_VIEW_SCENE) { *out = tail_sample_rgba(scene, SW, SH, u, v); return; } // :117
+    if (MODE == SAILOR_DEBUG_VIEW_SCENE) { *out = sample_clamp_f4_saturating(scene, SW, SH, u, v); return; } // :117
     if (MODE == SAILOR_DEBUG_VIEW_AO) { // :120
-        const float a = tail_sample_plane(ao, AW, AH, u, v);
+        const float a = sample_clamp_f1(ao, AW, AH, u, v);
         *out = make_float4(a, a, a, a);
         return;
     }
@@ -175,7 +131,7 @@ __global__ __launch_bounds__(256) void k_debug_view(const float4* __restrict__ s
         return;
     }
     // CASCADES (:146-173)
-    float4 o = tail_sample_rgba(scene, SW, SH, u, v);
+    float4 o = sample_clamp_f4_saturating(scene, SW, SH, u, v);
     int layer = SAILOR_NUM_CSM_CASCADES;
 #pragma unroll
     for (int k = SAILOR_NUM_CSM_CASCADES - 1; k >= 0; k--) // the first k that passes = the lowest one
@@ -186,16 +142,7 @@ __global__ __launch_bounds__(256) void k_debug_view(const float4* __restrict__ s
 }
 
 // ---- entry points -------------------------------------------------------------------------------------------------------------------------
-#define TAIL_MAX_EXTENT 32768
 #define TAIL_MAX_SAMPLES 64.0f
-static bool tail_extent_ok(int32_t w, int32_t h) { return w > 0 && h > 0 && w <= TAIL_MAX_EXTENT && h <= TAIL_MAX_EXTENT; }
-static dim3 tail_grid(int32_t w, int32_t h) { return dim3((unsigned)((w + 63) / 64), (unsigned)((h + 3) / 4)); }
-static bool aligned(const void* p, size_t a) { return p && ((uintptr_t)p & (a - 1)) == 0; }
-static bool overlaps(const void* a, size_t aBytes, const void* b, size_t bBytes)
-{
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + bBytes && b0 < a0 + aBytes;
-}
 
 extern "C" {
 
@@ -203,8 +150,8 @@ int sailor_hip_motion_blur(SailorHipContext* ctx, const SailorUboFrameData* fram
                            int32_t depthHeight, const float* dColor, int32_t colorWidth, int32_t colorHeight, const SailorMotionBlurParams* params, float* dOut,
                            int32_t width, int32_t height)
 {
-    if (!ctx || !frame || !previousFrame || !params || !aligned(dDepth, 4) || !aligned(dColor, 16) || !aligned(dOut, 16) || !tail_extent_ok(depthWidth, depthHeight) ||
-        !tail_extent_ok(colorWidth, colorHeight) || !tail_extent_ok(width, height))
+    if (!ctx || !frame || !previousFrame || !params || !aligned(dDepth, 4) || !aligned(dColor, 16) || !aligned(dOut, 16) || !extent_ok(depthWidth, depthHeight) ||
+        !extent_ok(colorWidth, colorHeight) || !extent_ok(width, height))
         return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     // the loop count is int(samples): a NaN, an infinity or anything outside [1, 64] is refused rather than run without an end; 1 / maxSpeed = 0 has no velocity
     if (!(params->samples >= 1.0f && params->samples <= TAIL_MAX_SAMPLES) || params->maxSpeed == 0.0f) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
@@ -215,7 +162,7 @@ int sailor_hip_motion_blur(SailorHipContext* ctx, const SailorUboFrameData* fram
     sailor_host_mat4_inverse(frame->view, A.invView.m);
     sailor_host_mat4_mul(previousFrame->projection, previousFrame->view, A.prevViewProjection.m);
     A.p = *params;
-    sailor_launch(ctx, k_motion_blur, tail_grid(width, height), dim3(256), dDepth, (int)depthWidth, (int)depthHeight, (const float4*)dColor, (int)colorWidth,
+    sailor_launch(ctx, k_motion_blur, texel_grid(width, height), dim3(256), dDepth, (int)depthWidth, (int)depthHeight, (const float4*)dColor, (int)colorWidth,
                   (int)colorHeight, (float4*)dOut, (int)width, (int)height, A);
     SAILOR_CHECK_LAUNCH(ctx, "k_motion_blur");
     return SAILOR_HIP_OK;
@@ -225,14 +172,14 @@ int sailor_hip_debug_view(SailorHipContext* ctx, const SailorUboFrameData* frame
                           const float* dLinearDepth, int32_t depthWidth, int32_t depthHeight, const SailorLightsGrid* dLightsGrid, const uint32_t* dCulledLights,
                           const float* dAo, int32_t aoWidth, int32_t aoHeight, float* dOut, int32_t width, int32_t height)
 {
-    if (!ctx || !frame || !aligned(dOut, 16) || !tail_extent_ok(width, height)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (!ctx || !frame || !aligned(dOut, 16) || !extent_ok(width, height)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     const bool needScene = mode == SAILOR_DEBUG_VIEW_SCENE || mode == SAILOR_DEBUG_VIEW_CASCADES;
     const bool needDepth = mode == SAILOR_DEBUG_VIEW_LIGHT_TILES || mode == SAILOR_DEBUG_VIEW_CASCADES;
     if (mode < SAILOR_DEBUG_VIEW_SCENE || mode > SAILOR_DEBUG_VIEW_CASCADES) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    if (needScene && (!aligned(dLdrScene, 16) || !tail_extent_ok(sceneWidth, sceneHeight) || overlaps(dOut, (size_t)width * height * 16, dLdrScene, (size_t)sceneWidth * sceneHeight * 16)))
+    if (needScene && (!aligned(dLdrScene, 16) || !extent_ok(sceneWidth, sceneHeight) || overlaps(dOut, (size_t)width * height * 16, dLdrScene, (size_t)sceneWidth * sceneHeight * 16)))
         return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    if (needDepth && (!aligned(dLinearDepth, 4) || !tail_extent_ok(depthWidth, depthHeight))) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    if (mode == SAILOR_DEBUG_VIEW_AO && (!aligned(dAo, 4) || !tail_extent_ok(aoWidth, aoHeight))) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (needDepth && (!aligned(dLinearDepth, 4) || !extent_ok(depthWidth, depthHeight))) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (mode == SAILOR_DEBUG_VIEW_AO && (!aligned(dAo, 4) || !extent_ok(aoWidth, aoHeight))) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     DebugViewArgs A {};
     A.viewportW = frame->viewportSize[0]; A.viewportH = frame->viewportSize[1];
     A.zFar = frame->cameraZNearZFar[1];
@@ -244,7 +191,7 @@ int sailor_hip_debug_view(SailorHipContext* ctx, const SailorUboFrameData* frame
         A.culledCapacity = (uint32_t)((size_t)tx * ty * KEEP + 1);
     }
     SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
-    const dim3 grid = tail_grid(width, height), block(256);
+    const dim3 grid = texel_grid(width, height), block(256);
 #define TAIL_LAUNCH(M)                                                                                                                                         \
     sailor_launch(ctx, k_debug_view<M>, grid, block, (const float4*)dLdrScene, (int)sceneWidth, (int)sceneHeight, dLinearDepth, (int)depthWidth, (int)depthHeight, \
                   dLightsGrid, dCulledLights, dAo, (int)aoWidth, (int)aoHeight, (float4*)dOut, (int)width, (int)height, A)

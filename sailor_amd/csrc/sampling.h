@@ -1,13 +1,20 @@
-// Canonical texture sampling shared by shade.hip (K3 shadow lookups, ambient / IBL term) and ibl_prefilter.hip: manual bilinear taps
-// (texel centres at (i + 0.5) / size, clamp-to-edge), the Vulkan cube face table (ties z over y over x) and the cube mip chain
-// layout -- level-major, then face, then size x size float4 texels.  Must match oracle/sailor_oracle.c bit for bit.
+// Canonical texture sampling, the only place of the library that turns a coordinate into tap indices.  For shade.hip (K3 shadow lookups, ambient / IBL
+// term) and ibl_prefilter.hip: manual bilinear taps (texel centres at (i + 0.5) / size, clamp-to-edge), the Vulkan cube face table (ties z over y over x)
+// and the cube mip chain layout -- level-major, then face, then size x size float4 texels.  Must match oracle/sailor_oracle.c bit for bit.
+// For the post-process passes (hbao.hip, post_tail.hip, bloom.hip, sky.hip, sky_clouds.hip): Repeat addressing, byte texels and whole-plane samples.
 // Non-finite coordinates (a NaN normal, an infinite roughness; a hardware sampler's result for them is undefined, so the choice is this path's own):
 // the (int) conversions below are the device's saturating convert -- NaN -> 0, +-inf -> INT_MAX / INT_MIN -- every tap index is clamped into the
 // image AFTER the conversion and without an addition that could wrap (see bilinear_taps: a roughness of +inf once read the BRDF table at row INT_MIN),
 // so no fetch leaves it, and the weights (inf - inf) are NaN, so the sample is NaN.  The oracle's conversion is defined to
 // give the same (sat_int / tap_pair there; plain (int)x is undefined in C for such values); tests/test_ambient_gpu.py compares these pixels by class.
+// Two conversions, on purpose.  bilinear_taps keeps the plain (int): it is the shade's hot path, its coordinates come from normals and roughness, which
+// are finite for every sane input, and v_cvt_i32_f32 is what the cast compiles to.  bilinear_taps_saturating spells the same conversion out
+// (cvt_i32_saturating) for the passes whose coordinates are computed from the depth buffer -- HBAO's ray march, motion blur's reprojection -- where one
+// hostile texel (0, inf, NaN) makes them non-finite as a matter of course: there nothing is left to what a compiler makes of an undefined cast.  The float
+// arithmetic and, wherever the cast is defined, the taps of the two are the same.
 #pragma once
 #include "common.h"
+#include <limits.h>
 
 struct BilinearTaps { int x0, x1, y0, y1; float ax, ay; };
 
@@ -73,7 +80,7 @@ __device__ __forceinline__ float4 cube_sample_lod(const float4* __restrict__ cub
     return make_float4(a.x * (1.0f - f) + b.x * f, a.y * (1.0f - f) + b.y * f, a.z * (1.0f - f) + b.z * f, a.w * (1.0f - f) + b.w * f);
 }
 
-// ---- Repeat addressing and byte texels (sky_clouds.hip): the cloud march's weather map and noise volumes ---------------------------------------
+// ---- Repeat addressing and byte texels: the cloud march's weather map and noise volumes, the sky and dirt planes ---------------------------------
 // A tap index is wrapped into [0, n) AFTER the saturating conversion: i % n lies in (-n, n), so neither the + n nor the + 1 of the second tap can
 // wrap an int, whatever the coordinate was (NaN -> 0, +-inf -> INT_MAX / INT_MIN).  The weights of a non-finite coordinate are NaN, the sample NaN.
 __device__ __forceinline__ int wrap_tap(int i, int n) { return ((i % n) + n) % n; }
@@ -120,3 +127,60 @@ __device__ __forceinline__ float4 bilinear_repeat_rgba8(const uint32_t* __restri
 __device__ __forceinline__ int nearest_repeat(int n, float u) { return wrap_tap((int)floorf(u * (float)n), n); }
 // nearest tap of a clamp-to-edge sampler
 __device__ __forceinline__ int nearest_clamp(int n, float u) { return min(max((int)floorf(u * (float)n), 0), n - 1); }
+
+// ---- Whole planes: the samplers of the post-process passes -----------------------------------------------------------------------------------------
+// float -> int as v_cvt_i32_f32 defines it: NaN -> 0, saturating at the ends of int32
+__device__ __forceinline__ int cvt_i32_saturating(float x)
+{
+    if (x != x) return 0;
+    if (x >= 2147483648.0f) return INT_MAX;
+    if (x <= -2147483648.0f) return INT_MIN;
+    return (int)x;
+}
+
+// bilinear_taps (the same float arithmetic, the same taps wherever its cast is defined) with the conversion above; the clamp runs before the + 1, so no
+// integer overflows either
+__device__ __forceinline__ BilinearTaps bilinear_taps_saturating(int W, int H, float u, float v)
+{
+    BilinearTaps t;
+    const float x = u * (float)W - 0.5f, y = v * (float)H - 0.5f;
+    const float fx = floorf(x), fy = floorf(y);
+    t.ax = x - fx; t.ay = y - fy;
+    const int x0 = min(max(cvt_i32_saturating(fx), -1), W - 1), y0 = min(max(cvt_i32_saturating(fy), -1), H - 1);
+    t.x0 = max(x0, 0); t.x1 = min(x0 + 1, W - 1);
+    t.y0 = max(y0, 0); t.y1 = min(y0 + 1, H - 1);
+    return t;
+}
+
+// sampler2D over a W x H float plane, bilinear, clamp-to-edge, the saturating taps
+__device__ __forceinline__ float sample_clamp_f1(const float* __restrict__ p, int W, int H, float u, float v)
+{
+    const BilinearTaps t = bilinear_taps_saturating(W, H, u, v);
+    const float* __restrict__ r0 = p + (size_t)t.y0 * (size_t)W;
+    const float* __restrict__ r1 = p + (size_t)t.y1 * (size_t)W;
+    return lerp2(r0[t.x0], r0[t.x1], r1[t.x0], r1[t.x1], t.ax, t.ay);
+}
+
+// the four taps of a W-wide float4 plane, all four channels
+__device__ __forceinline__ float4 lerp2_f4(const float4* __restrict__ p, int W, const BilinearTaps t)
+{
+    const float4* __restrict__ r0 = p + (size_t)t.y0 * (size_t)W;
+    const float4* __restrict__ r1 = p + (size_t)t.y1 * (size_t)W;
+    const float4 a = r0[t.x0], c = r0[t.x1], d = r1[t.x0], e = r1[t.x1];
+    return make_float4(lerp2(a.x, c.x, d.x, e.x, t.ax, t.ay), lerp2(a.y, c.y, d.y, e.y, t.ax, t.ay), lerp2(a.z, c.z, d.z, e.z, t.ax, t.ay),
+                       lerp2(a.w, c.w, d.w, e.w, t.ax, t.ay));
+}
+// sampler2D over a W x H float4 plane, bilinear: clamp-to-edge with either tap computation, and Repeat
+__device__ __forceinline__ float4 sample_clamp_f4(const float4* __restrict__ p, int W, int H, float u, float v)
+{
+    return lerp2_f4(p, W, bilinear_taps(W, H, u, v));
+}
+__device__ __forceinline__ float4 sample_clamp_f4_saturating(const float4* __restrict__ p, int W, int H, float u, float v)
+{
+    return lerp2_f4(p, W, bilinear_taps_saturating(W, H, u, v));
+}
+__device__ __forceinline__ float4 sample_repeat_f4(const float4* __restrict__ p, int W, int H, float u, float v)
+{
+    const RepeatTap X = repeat_tap(W, u), Y = repeat_tap(H, v);
+    return lerp2_f4(p, W, {X.i0, X.i1, Y.i0, Y.i1, X.a, Y.a});
+}

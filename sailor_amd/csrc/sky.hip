@@ -12,7 +12,7 @@
 // Arithmetic.  tests/sky_ref.py (Ref32) restates this file operation by operation in NumPy float32 and is its specification.  The library is compiled
 // with -ffp-contract=off, IEEE division and square root: every expression below is evaluated as written, with the library's conventions
 // dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z, mat4 * vec4 row by row left to right, length = sqrt(dot), normalize(v) = v / length(v),
-// mix(a, b, t) = a (1 - t) + b t, min(x, y) = y < x ? y : x, max(x, y) = x < y ? y : x.  Every branch of SkyLighting (outer <= 0, inner > 0, the
+// mix(a, b, t) = a (1 - t) + b t, min and max by their GLSL definitions (common.h).  Every branch of SkyLighting (outer <= 0, inner > 0, the
 // discriminant sign, length(destination - origin) < 0.01, h1 < 0, theta < zeta, the sun's Earth test) is decided by geometry computed in that order
 // and never by an accumulated sum.  With R = 6 371 000 in fp32, c = dot(r0, r0) - sr * sr cancels catastrophically and heights are quantised to 0.5 m:
 // the fp32 result is the specification.  Only the sums over the 127 view steps (densityR, densityMie, resR, resMie) are reassociated -- they are sums
@@ -71,12 +71,6 @@ __device__ __forceinline__ float wave_inclusive_scan(float v, int lane)
         const float t = __shfl_up(v, d, 64);
         if (lane >= d) v = v + t;
     }
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = v + __shfl_xor(v, d, 64);
     return v;
 }
 
@@ -158,7 +152,7 @@ __global__ __launch_bounds__(256) void k_sky_march(float4* __restrict__ out, int
 // ---- b. SUN (:693-715 and the SUN branches of SkyLighting) ---------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_sky_sun(float4* __restrict__ out, int W, int H, const SkyUniforms U)
 {
-    const int i = (int)(blockIdx.x * 64 + (threadIdx.x & 63)), j = (int)(blockIdx.y * 4 + (threadIdx.x >> 6));
+    const int i = texel_i(), j = texel_j();
     if (i >= W || j >= H) return;
     float4* __restrict__ o = out + (size_t)j * (size_t)W + i;
     *o = make_float4(0.0f, 0.0f, 0.0f, 0.0f); // :705
@@ -169,21 +163,6 @@ __global__ __launch_bounds__(256) void k_sky_sun(float4* __restrict__ out, int W
 }
 
 // ---- c. COMPOSE (:613-643) -------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float4 sample_repeat_f4(const float4* __restrict__ tex, int W, int H, float u, float v)
-{
-    const float x = u * (float)W - 0.5f, y = v * (float)H - 0.5f;
-    const float fx = floorf(x), fy = floorf(y);
-    const float ax = x - fx, ay = y - fy;
-    const int x0 = (((int)fx % W) + W) % W, y0 = (((int)fy % H) + H) % H, x1 = (x0 + 1) % W, y1 = (y0 + 1) % H;
-    const float4 a = tex[(size_t)y0 * W + x0], c = tex[(size_t)y0 * W + x1], d = tex[(size_t)y1 * W + x0], e = tex[(size_t)y1 * W + x1];
-    return make_float4(lerp2(a.x, c.x, d.x, e.x, ax, ay), lerp2(a.y, c.y, d.y, e.y, ax, ay), lerp2(a.z, c.z, d.z, e.z, ax, ay), 0.0f);
-}
-__device__ __forceinline__ float4 sample_clamp_f4(const float4* __restrict__ tex, int W, int H, float u, float v)
-{
-    const BilinearTaps b = bilinear_taps(W, H, u, v);
-    const float4 a = tex[(size_t)b.y0 * W + b.x0], c = tex[(size_t)b.y0 * W + b.x1], d = tex[(size_t)b.y1 * W + b.x0], e = tex[(size_t)b.y1 * W + b.x1];
-    return make_float4(lerp2(a.x, c.x, d.x, e.x, b.ax, b.ay), lerp2(a.y, c.y, d.y, e.y, b.ax, b.ay), lerp2(a.z, c.z, d.z, e.z, b.ax, b.ay), 0.0f);
-}
 __device__ __forceinline__ float sky_merge(float o, float s, float t) // :642 max(out, mix(out, sun, t))
 {
     const float m = o * (1.0f - t) + s * t;
@@ -193,12 +172,13 @@ __device__ __forceinline__ float sky_merge(float o, float s, float t) // :642 ma
 __global__ __launch_bounds__(256) void k_sky_compose(const float4* __restrict__ sky, int SW, int SH, const float4* __restrict__ sun, int NW, int NH,
                                                      float4* __restrict__ out, int W, int H, int rowBegin, int rowCount, const SkyUniforms U)
 {
-    const int i = (int)(blockIdx.x * 64 + (threadIdx.x & 63)), r = (int)(blockIdx.y * 4 + (threadIdx.x >> 6));
+    const int i = texel_i(), r = texel_j();
     if (i >= W || r >= rowCount) return;
     const int j = rowBegin + r;
     const float u = ((float)i + 0.5f) / (float)W, v = ((float)j + 0.5f) / (float)H;
     const S3 dir = sky_view_direction(U, u, 1.0f - v); // :614-619
     float4 c = sample_repeat_f4(sky, SW, SH, u, v);    // :621
+    c.w = 0.0f;
     const S3 rel = sky_sub(dir, U.sun);
     const float dx = sky_dot(rel, U.right), dy = sky_dot(rel, U.up); // :626-627
     if (dx > -SKY_SUN_R && dy > -SKY_SUN_R && dx < SKY_SUN_R && dy < SKY_SUN_R && sky_dot(dir, U.sun) > 0.0f) { // :631-635
@@ -258,7 +238,7 @@ int sailor_host_sky_face_matrices(int32_t face, float* outView16, float* outProj
 
 int sailor_hip_sky_fill(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSkyParams* params, float* dSky, int32_t width, int32_t height)
 {
-    if (!ctx || !frame || !params || !sky_aligned(dSky) || !sky_extent_ok(width, height)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (!ctx || !frame || !params || !aligned(dSky, 16) || !extent_ok(width, height)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     SkyUniforms U;
     if (!sky_uniforms(frame->view, frame->invProjection, frame->cameraPosition, params, &U)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
@@ -270,7 +250,7 @@ int sailor_hip_sky_fill(SailorHipContext* ctx, const SailorUboFrameData* frame, 
 
 int sailor_hip_sky_env_face(SailorHipContext* ctx, const float* cameraPosition3, const SailorSkyParams* params, float* dCube, int32_t size, int32_t face)
 {
-    if (!ctx || !cameraPosition3 || !params || !sky_aligned(dCube) || !sky_extent_ok(size, size) || face < 0 || face > 5) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (!ctx || !cameraPosition3 || !params || !aligned(dCube, 16) || !extent_ok(size, size) || face < 0 || face > 5) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     float view[16], projection[16], invProjection[16];
     if (sailor_host_sky_face_matrices(face, view, projection, invProjection) != SAILOR_HIP_OK) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     SkyUniforms U;
@@ -285,13 +265,13 @@ int sailor_hip_sky_env_face(SailorHipContext* ctx, const float* cameraPosition3,
 int sailor_hip_sky_sun(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSkyParams* params, const float* dClouds, int32_t cloudsWidth,
                        int32_t cloudsHeight, float* dSun, int32_t width, int32_t height)
 {
-    if (!ctx || !frame || !params || !sky_aligned(dSun) || !sky_extent_ok(width, height)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (!ctx || !frame || !params || !aligned(dSun, 16) || !extent_ok(width, height)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     (void)cloudsWidth; (void)cloudsHeight;
     if (dClouds) { ctx->lastError = "sailor_hip_sky_sun: a clouds plane is taken by sailor_hip_sky_sun_clouds"; return SAILOR_HIP_ERR_UNSUPPORTED; }
     SkyUniforms U;
     if (!sky_uniforms(frame->view, frame->invProjection, frame->cameraPosition, params, &U)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
-    sailor_launch(ctx, k_sky_sun, sky_texel_grid(width, height), dim3(256), (float4*)dSun, (int)width, (int)height, U);
+    sailor_launch(ctx, k_sky_sun, texel_grid(width, height), dim3(256), (float4*)dSun, (int)width, (int)height, U);
     SAILOR_CHECK_LAUNCH(ctx, "k_sky_sun");
     return SAILOR_HIP_OK;
 }
@@ -300,16 +280,16 @@ int sailor_hip_sky_compose(SailorHipContext* ctx, const SailorUboFrameData* fram
                            int32_t skyHeight, const float* dSun, int32_t sunWidth, int32_t sunHeight, float* dOut, int32_t width, int32_t height,
                            const SailorBand* band)
 {
-    if (!ctx || !frame || !params || !band || !sky_extent_ok(width, height) || !sky_extent_ok(skyWidth, skyHeight) || !sky_extent_ok(sunWidth, sunHeight))
+    if (!ctx || !frame || !params || !band || !extent_ok(width, height) || !extent_ok(skyWidth, skyHeight) || !extent_ok(sunWidth, sunHeight))
         return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     if (!sailor_hip_band_is_valid(width, height, band)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    if (!sky_aligned(dSky) || !sky_aligned(dSun)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (!aligned(dSky, 16) || !aligned(dSun, 16)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     if (!band->fbRowCount) return SAILOR_HIP_OK; // a rank without rows holds no target
-    if (!sky_aligned(dOut) || dOut == dSky || dOut == dSun) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (!aligned(dOut, 16) || dOut == dSky || dOut == dSun) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     SkyUniforms U;
     if (!sky_uniforms(frame->view, frame->invProjection, frame->cameraPosition, params, &U)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
-    sailor_launch(ctx, k_sky_compose, sky_texel_grid(width, band->fbRowCount), dim3(256), (const float4*)dSky, (int)skyWidth, (int)skyHeight, (const float4*)dSun,
+    sailor_launch(ctx, k_sky_compose, texel_grid(width, band->fbRowCount), dim3(256), (const float4*)dSky, (int)skyWidth, (int)skyHeight, (const float4*)dSun,
                   (int)sunWidth, (int)sunHeight, (float4*)dOut, (int)width, (int)height, (int)band->fbRowBegin, (int)band->fbRowCount, U);
     SAILOR_CHECK_LAUNCH(ctx, "k_sky_compose");
     return SAILOR_HIP_OK;
@@ -318,7 +298,7 @@ int sailor_hip_sky_compose(SailorHipContext* ctx, const SailorUboFrameData* fram
 int sailor_hip_sky_env_cubemap(SailorHipContext* ctx, const float* cameraPosition3, const SailorSkyParams* params, float* dCube, int32_t size, int32_t levels)
 {
     // every argument is checked before the first launch (the mip generator's own limits included): a refused call records nothing
-    if (!ctx || !cameraPosition3 || !params || !sky_aligned(dCube) || size <= 0 || size > 8192 || levels <= 0 || levels > 16) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (!ctx || !cameraPosition3 || !params || !aligned(dCube, 16) || size <= 0 || size > 8192 || levels <= 0 || levels > 16) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     for (int32_t face = 0; face < 6; face++) { // SkyNode.cpp:768-797, one face per frame there
         const int st = sailor_hip_sky_env_face(ctx, cameraPosition3, params, dCube, size, face);
         if (st != SAILOR_HIP_OK) return st;

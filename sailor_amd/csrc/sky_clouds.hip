@@ -7,7 +7,7 @@
 // Images are RGBA32F in device memory as in sky.hip; texel (i, j) of a w x h target has the quad's inTexcoord ((i + 0.5) / w, (j + 0.5) / h).
 // tests/clouds_ref.py (Ref32) restates this file operation by operation in NumPy float32 and is its specification; the conventions are those
 // sky.hip's header lists (no contraction, dot = (x x + y y) + z z, IEEE division and square root, exp(x) = canonical_exp2f(x * log2(e)),
-// min(x, y) = y < x ? y : x, max(x, y) = x < y ? y : x, clamp(x, 0, 1) = min(max(x, 0), 1), mix(a, b, t) = a (1 - t) + b t).
+// min, max and clamp(x, 0, 1) by their GLSL definitions (common.h), mix(a, b, t) = a (1 - t) + b t).
 //
 // Decisions (Sky.shader line numbers):
 //   Quirks restated, not repaired
@@ -74,10 +74,6 @@ struct CloudsUniforms {
     float zFar;
 };
 
-__device__ __forceinline__ float c_max(float x, float y) { return x < y ? y : x; }
-__device__ __forceinline__ float c_min(float x, float y) { return y < x ? y : x; }
-__device__ __forceinline__ float c_sat(float x) { return c_min(c_max(x, 0.0f), 1.0f); }
-
 struct CloudsTextures {
     const uint32_t* __restrict__ weather; int mapW, mapH;
     const uint8_t* __restrict__ low; int lowN;
@@ -91,18 +87,18 @@ __device__ __forceinline__ float clouds_density(const CloudsUniforms& U, const C
     const float cloudsLow = trilinear_repeat_r8(T.low, T.lowN, U.shift1.x + px / 9000.0f, U.shift1.y + py / 9000.0f, U.shift1.z + pz / 9000.0f);
     const float cloudsHigh = trilinear_repeat_r8(T.high, T.highN, U.shift2.x + px / 1300.0f, U.shift2.y + py / 1300.0f, U.shift2.z + pz / 1300.0f);
     const float4 weather = bilinear_repeat_rgba8(T.weather, T.mapW, T.mapH, px / 409600.0f + 0.2f, pz / 409600.0f + 0.1f);
-    const float height = c_sat((fabsf(py) - CLOUDS_START_R) / (CLOUDS_END_R - CLOUDS_START_R)); // :389
-    const float SRb = c_sat(height / 0.07f);
+    const float height = glsl_saturate((fabsf(py) - CLOUDS_START_R) / (CLOUDS_END_R - CLOUDS_START_R)); // :389
+    const float SRb = glsl_saturate(height / 0.07f);
     const float wb35 = weather.z * 0.35f;
-    const float SRt = c_sat(1.0f - (height - wb35) / (weather.z - wb35));
+    const float SRt = glsl_saturate(1.0f - (height - wb35) / (weather.z - wb35));
     const float SA = SRb * SRt;
-    const float DRb = height * c_sat(height / 0.15f);
-    const float DRt = height * c_sat(1.0f - (height - 0.9f) / (1.0f - 0.9f));
+    const float DRb = height * glsl_saturate(height / 0.15f);
+    const float DRt = height * glsl_saturate(1.0f - (height - 0.9f) / (1.0f - 0.9f));
     const float DA = (((DRb * DRt) * weather.w) * 2.0f) * U.p.cloudsDensity;
     const float SNsample = cloudsLow * 0.85f + cloudsHigh * 0.15f;
-    const float WMc = c_max(weather.x, (c_sat(U.p.cloudsCoverage - 0.5f) * weather.y) * 2.0f);
+    const float WMc = glsl_max(weather.x, (glsl_saturate(U.p.cloudsCoverage - 0.5f) * weather.y) * 2.0f);
     const float lo = 1.0f - U.p.cloudsCoverage * WMc;
-    return c_sat((SNsample * SA - lo) / (1.0f - lo)) * DA;
+    return glsl_saturate((SNsample * SA - lo) / (1.0f - lo)) * DA;
 }
 
 // CloudsSampleDirectDensity (:427-448)
@@ -149,32 +145,27 @@ __global__ __launch_bounds__(256) void k_sky_clouds(const float4* __restrict__ s
 
     const float linearDepth = fabsf(depth[(size_t)nearest_clamp(DH, v) * DW + nearest_clamp(DW, u)]); // :656
     S3 viewDir = sky_normalize(sky_view_direction(U.sky, u, 1.0f - v)); // :664-669, :677
-    float3 color; // :671
-    {
-        const RepeatTap X = repeat_tap(SW, u), Y = repeat_tap(SH, v);
-        const float4 a = sky[(size_t)Y.i0 * SW + X.i0], c = sky[(size_t)Y.i0 * SW + X.i1], d = sky[(size_t)Y.i1 * SW + X.i0], e = sky[(size_t)Y.i1 * SW + X.i1];
-        color = make_float3(lerp2(a.x, c.x, d.x, e.x, X.a, Y.a), lerp2(a.y, c.y, d.y, e.y, X.a, Y.a), lerp2(a.z, c.z, d.z, e.z, X.a, Y.a));
-    }
+    const float4 color = sample_repeat_f4(sky, SW, SH, u, v); // :671 (.rgb)
     const float skyTone = color.z / (1.0f + color.z); // :674-675
     float horizon = 1.0f - sky_exp(-fabsf(viewDir.y) * U.p.fog); // :680
     horizon = (horizon * horizon) * horizon;
     const S3 origin = U.sky.origin, sun = U.sky.sun;
     const float originHeight = sky_len(origin);
-    horizon = horizon + (1.0f - c_sat((CLOUDS_START_R - originHeight) / 500.0f)); // :682
-    horizon = c_sat(horizon);
+    horizon = horizon + (1.0f - glsl_saturate((CLOUDS_START_R - originHeight) / 500.0f)); // :682
+    horizon = glsl_saturate(horizon);
     const float maxTraceDistance = fabsf(linearDepth - U.zFar) < 1.0f ? CLOUDS_BIG_DISTANCE : linearDepth; // :686
 
     // CloudsMarching (:450-595)
     float colorLow = 0.0f, transmittanceLow = 1.0f;
     const float2 si = ray_sphere(origin, viewDir, CLOUDS_START_R), ei = ray_sphere(origin, viewDir, CLOUDS_END_R);
-    const float shiftStart = si.x < 0.0f ? c_max(0.0f, si.y) : si.x;
-    const float shiftEnd = c_min(maxTraceDistance, ei.x < 0.0f ? c_max(0.0f, ei.y) : ei.x);
+    const float shiftStart = si.x < 0.0f ? glsl_max(0.0f, si.y) : si.x;
+    const float shiftEnd = glsl_min(maxTraceDistance, ei.x < 0.0f ? glsl_max(0.0f, ei.y) : ei.x);
     const bool early = (shiftStart > shiftEnd && ei.x < 0.0f) || shiftStart > CLOUDS_BIG_DISTANCE; // :463-466, :500-503
     if (!early) {
         S3 traceStart = origin; // :468-494
         if (originHeight < CLOUDS_START_R) traceStart = sky_madd(origin, viewDir, shiftStart);
         else if (originHeight > CLOUDS_END_R) traceStart = sky_madd(origin, viewDir, shiftEnd);
-        const float mu = c_max(0.0f, sky_dot(viewDir, sun)); // :506
+        const float mu = glsl_max(0.0f, sky_dot(viewDir, sun)); // :506
         const int steps = U.p.scatteringSteps;
         {
             float dB = 1.0f, dC = 1.0f; // :512-517
@@ -207,7 +198,7 @@ __global__ __launch_bounds__(256) void k_sky_clouds(const float4* __restrict__ s
                     const float m2 = sky_exp(kA * sunDensity);     // :561
                     const float m3 = U.p.cloudsAttenuation2 * density; // :562
                     const float2 e = ray_sphere(local, sun, SKY_R);    // :564
-                    if (c_max(e.x, e.y) < 0.0f) colorLow = colorLow + ((s_phase[k][tid] * m2) * m3) * transmittanceLow; // :567-570
+                    if (glsl_max(e.x, e.y) < 0.0f) colorLow = colorLow + ((s_phase[k][tid] * m2) * m3) * transmittanceLow; // :567-570
                     transmittanceLow = transmittanceLow * sky_exp(kA * density); // :572
                     dA = dA * U.p.scatteringDensity;
                 }
@@ -230,20 +221,11 @@ __global__ __launch_bounds__(256) void k_sky_clouds(const float4* __restrict__ s
     out[(size_t)j * (size_t)W + i] = make_float4(rgb[0], rgb[1], rgb[2], alpha);
 }
 
-// bilinear, clamp-to-edge, all four channels of a W x H float4 plane
-__device__ __forceinline__ float4 clouds_sample_clamp(const float4* __restrict__ tex, int W, int H, float u, float v)
-{
-    const BilinearTaps b = bilinear_taps(W, H, u, v);
-    const float4 a = tex[(size_t)b.y0 * W + b.x0], c = tex[(size_t)b.y0 * W + b.x1], d = tex[(size_t)b.y1 * W + b.x0], e = tex[(size_t)b.y1 * W + b.x1];
-    return make_float4(lerp2(a.x, c.x, d.x, e.x, b.ax, b.ay), lerp2(a.y, c.y, d.y, e.y, b.ax, b.ay), lerp2(a.z, c.z, d.z, e.z, b.ax, b.ay),
-                       lerp2(a.w, c.w, d.w, e.w, b.ax, b.ay));
-}
-
 // ---- b. SUN behind clouds (:693-715) --------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_sky_sun_clouds(const float4* __restrict__ clouds, int CW, int CH, float4* __restrict__ out, int W, int H,
                                                         const SkyUniforms U, const Mat4 projView)
 {
-    const int i = (int)(blockIdx.x * 64 + (threadIdx.x & 63)), j = (int)(blockIdx.y * 4 + (threadIdx.x >> 6));
+    const int i = texel_i(), j = texel_j();
     if (i >= W || j >= H) return;
     const float tx = ((float)i + 0.5f) / (float)W, ty = 1.0f - ((float)j + 0.5f) / (float)H;
     const float ax = -SKY_SUN_R * (1.0f - tx) + SKY_SUN_R * tx, ay = -SKY_SUN_R * (1.0f - ty) + SKY_SUN_R * ty; // :696-697
@@ -251,7 +233,7 @@ __global__ __launch_bounds__(256) void k_sky_sun_clouds(const float4* __restrict
     const float4 clip = glsl_mul(projView, direction.x, direction.y, direction.z, 0.0f);                      // :707
     const float w = (clip.w + 1.0f) * 0.5f;
     const float cu = ((clip.x + 1.0f) * 0.5f) / w, cv = ((clip.y + 1.0f) * 0.5f) / w;                          // :708
-    const float alpha = clouds_sample_clamp(clouds, CW, CH, cu, cv).w;                                         // :710
+    const float alpha = sample_clamp_f4(clouds, CW, CH, cu, cv).w;                                         // :710
     const float v = alpha < 0.5f ? sky_sun_texel(U, tx, ty) : 0.0f;                                           // :712-715
     out[(size_t)j * (size_t)W + i] = make_float4(v, v, v, 0.0f);
 }
@@ -260,10 +242,10 @@ __global__ __launch_bounds__(256) void k_sky_sun_clouds(const float4* __restrict
 __global__ __launch_bounds__(256) void k_sky_blit_clouds(const float4* __restrict__ clouds, int CW, int CH, float4* __restrict__ target, int W, int H,
                                                          int rowBegin, int rowCount)
 {
-    const int i = (int)(blockIdx.x * 64 + (threadIdx.x & 63)), r = (int)(blockIdx.y * 4 + (threadIdx.x >> 6));
+    const int i = texel_i(), r = texel_j();
     if (i >= W || r >= rowCount) return;
     const int j = rowBegin + r;
-    const float4 src = clouds_sample_clamp(clouds, CW, CH, ((float)i + 0.5f) / (float)W, ((float)j + 0.5f) / (float)H);
+    const float4 src = sample_clamp_f4(clouds, CW, CH, ((float)i + 0.5f) / (float)W, ((float)j + 0.5f) / (float)H);
     float4* __restrict__ t = target + (size_t)r * (size_t)W + i;
     const float4 dst = *t;
     const float k = 1.0f - src.w;
@@ -299,11 +281,11 @@ int sailor_hip_sky_clouds(SailorHipContext* ctx, const SailorUboFrameData* frame
                           int32_t depthWidth, int32_t depthHeight, float* dClouds, int32_t width, int32_t height)
 {
     if (!ctx || !frame || !params) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    if (!sky_extent_ok(width, height) || !sky_extent_ok(skyWidth, skyHeight) || !sky_extent_ok(mapWidth, mapHeight) || !sky_extent_ok(noiseWidth, noiseHeight) ||
-        !sky_extent_ok(depthWidth, depthHeight) || lowSize <= 0 || lowSize > 1024 || highSize <= 0 || highSize > 1024)
+    if (!extent_ok(width, height) || !extent_ok(skyWidth, skyHeight) || !extent_ok(mapWidth, mapHeight) || !extent_ok(noiseWidth, noiseHeight) ||
+        !extent_ok(depthWidth, depthHeight) || lowSize <= 0 || lowSize > 1024 || highSize <= 0 || highSize > 1024)
         return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    if (!sky_aligned(dSky) || !sky_aligned(dWeatherMap) || !sky_aligned(dNoiseLow) || !sky_aligned(dNoiseHigh) || !sky_aligned(dNoise) ||
-        !sky_aligned(dLinearDepth) || !sky_aligned(dClouds))
+    if (!aligned(dSky, 16) || !aligned(dWeatherMap, 16) || !aligned(dNoiseLow, 16) || !aligned(dNoiseHigh, 16) || !aligned(dNoise, 16) ||
+        !aligned(dLinearDepth, 16) || !aligned(dClouds, 16))
         return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     if ((const void*)dClouds == dSky || (const void*)dClouds == dNoise || (const void*)dClouds == dLinearDepth || (const void*)dClouds == dWeatherMap ||
         (const void*)dClouds == dNoiseLow || (const void*)dClouds == dNoiseHigh)
@@ -337,7 +319,7 @@ int sailor_hip_sky_clouds(SailorHipContext* ctx, const SailorUboFrameData* frame
 int sailor_hip_sky_sun_clouds(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSkyParams* params, const float* dClouds, int32_t cloudsWidth,
                               int32_t cloudsHeight, float* dSun, int32_t width, int32_t height)
 {
-    if (!ctx || !frame || !params || !sky_aligned(dSun) || !sky_aligned(dClouds) || !sky_extent_ok(width, height) || !sky_extent_ok(cloudsWidth, cloudsHeight) ||
+    if (!ctx || !frame || !params || !aligned(dSun, 16) || !aligned(dClouds, 16) || !extent_ok(width, height) || !extent_ok(cloudsWidth, cloudsHeight) ||
         (const void*)dSun == dClouds)
         return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     SkyUniforms U;
@@ -345,7 +327,7 @@ int sailor_hip_sky_sun_clouds(SailorHipContext* ctx, const SailorUboFrameData* f
     Mat4 projView;
     if (sailor_host_mat4_mul(frame->projection, frame->view, projView.m) != SAILOR_HIP_OK) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
-    sailor_launch(ctx, k_sky_sun_clouds, sky_texel_grid(width, height), dim3(256), (const float4*)dClouds, (int)cloudsWidth, (int)cloudsHeight, (float4*)dSun,
+    sailor_launch(ctx, k_sky_sun_clouds, texel_grid(width, height), dim3(256), (const float4*)dClouds, (int)cloudsWidth, (int)cloudsHeight, (float4*)dSun,
                   (int)width, (int)height, U, projView);
     SAILOR_CHECK_LAUNCH(ctx, "k_sky_sun_clouds");
     return SAILOR_HIP_OK;
@@ -354,13 +336,13 @@ int sailor_hip_sky_sun_clouds(SailorHipContext* ctx, const SailorUboFrameData* f
 int sailor_hip_sky_blit_clouds(SailorHipContext* ctx, const float* dClouds, int32_t cloudsWidth, int32_t cloudsHeight, float* dTarget, int32_t width,
                                int32_t height, const SailorBand* band)
 {
-    if (!ctx || !band || !sky_extent_ok(width, height) || !sky_extent_ok(cloudsWidth, cloudsHeight)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (!ctx || !band || !extent_ok(width, height) || !extent_ok(cloudsWidth, cloudsHeight)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     if (!sailor_hip_band_is_valid(width, height, band)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    if (!sky_aligned(dClouds)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (!aligned(dClouds, 16)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     if (!band->fbRowCount) return SAILOR_HIP_OK; // a rank without rows holds no target
-    if (!sky_aligned(dTarget) || (const void*)dTarget == dClouds) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (!aligned(dTarget, 16) || (const void*)dTarget == dClouds) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
-    sailor_launch(ctx, k_sky_blit_clouds, sky_texel_grid(width, band->fbRowCount), dim3(256), (const float4*)dClouds, (int)cloudsWidth, (int)cloudsHeight,
+    sailor_launch(ctx, k_sky_blit_clouds, texel_grid(width, band->fbRowCount), dim3(256), (const float4*)dClouds, (int)cloudsWidth, (int)cloudsHeight,
                   (float4*)dTarget, (int)width, (int)height, (int)band->fbRowBegin, (int)band->fbRowCount);
     SAILOR_CHECK_LAUNCH(ctx, "k_sky_blit_clouds");
     return SAILOR_HIP_OK;

@@ -4,6 +4,7 @@
 #pragma once
 #include "common.h"
 #include "sampling.h"
+#include "texel_pass.h"
 #include "canonical_math.h"
 #include <math.h>
 
@@ -117,11 +118,6 @@ __device__ __forceinline__ float sky_sun_texel(const SkyUniforms& U, float tx, f
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------------
-#define SKY_MAX_EXTENT 32768
-static bool sky_extent_ok(int32_t w, int32_t h) { return w > 0 && h > 0 && w <= SKY_MAX_EXTENT && h <= SKY_MAX_EXTENT; }
-static bool sky_aligned(const void* p) { return p && ((uintptr_t)p & 15) == 0; }
-static dim3 sky_texel_grid(int32_t w, int32_t h) { return dim3((unsigned)((w + 63) / 64), (unsigned)((h + 3) / 4)); }
-
 static bool sky_uniforms(const float* view16, const float* invProjection16, const float* cameraPosition3, const SailorSkyParams* p, SkyUniforms* U)
 {
     memcpy(U->invProjection.m, invProjection16, sizeof U->invProjection.m);

@@ -555,18 +555,52 @@ static void* buffer_of(const RHIShaderBindingSetPtr& set, const char* name)
     return (b && b->m_buffer) ? b->m_buffer->m_hip.m_devicePtr : nullptr;
 }
 
+// texture `index` of the first of `bindings` that has one under `name` (it may be null, and need not have a buffer)
+static RHITexturePtr texture_of(const TVector<RHIShaderBindingSetPtr>& bindings, const char* name, size_t index = 0)
+{
+    for (const auto& set : bindings)
+        if (set) if (auto b = set->Find(name)) if (b->m_textures.size() > index) return b->m_textures[index];
+    return RHITexturePtr();
+}
+// the first texture bound under `name` in this set, or null (the eye adaptation's luminance target counts by the state behind it, not by a buffer)
+static RHITexturePtr first_texture(const RHIShaderBindingSetPtr& set, const char* name)
+{
+    auto b = set ? set->Find(name) : RHIShaderBindingPtr();
+    return (b && !b->m_textures.empty() && b->m_textures[0]) ? b->m_textures[0] : RHITexturePtr();
+}
+// ... with a buffer behind it: what a Record* function reads texels from
+static RHITexturePtr bound_texture(const RHIShaderBindingSetPtr& set, const char* name)
+{
+    auto t = first_texture(set, name);
+    return (t && t->m_buffer) ? t : RHITexturePtr();
+}
+// ... of this format and, where the entry point addresses one 2D image (texels_of / GetExtent: level 0 of a mip chain such as Main), no cubemap.  A caller
+// that answers a wrong format with UNSUPPORTED rather than INVALID_ARGUMENT looks the texture up without a format and tests it itself.
+static RHITexturePtr bound_texture(const RHIShaderBindingSetPtr& set, const char* name, EFormat format, bool refuseCubemap = false)
+{
+    auto t = bound_texture(set, name);
+    return (t && t->m_format == format && !(refuseCubemap && t->m_bCubemap)) ? t : RHITexturePtr();
+}
+// the host copy of the block bound under `name` (`frameData`, `data` ...) as a T; false where nothing is bound or the copy is too small
+template <typename T>
+static bool host_copy_of(const RHIShaderBindingSetPtr& set, const char* name, T& out)
+{
+    auto b = set ? set->Find(name) : RHIShaderBindingPtr();
+    if (!b || b->m_hostCopy.size() < sizeof(T)) return false;
+    memcpy(&out, b->m_hostCopy.data(), sizeof(T));
+    return true;
+}
+
 int HipGraphicsDriver::RecordLightCulling(const TVector<RHIShaderBindingSetPtr>& bindings, const TVector<uint8_t>& pcBytes)
 {
     // LightCullingNode.cpp:76: { sceneView.m_rhiLightsData, m_culledLights, sceneView.m_frameBindings }
     if (bindings.size() != 3 || pcBytes.size() < sizeof(SailorLightCullPushConstants) - 4) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     SailorLightCullPushConstants pc {};
     memcpy(&pc, pcBytes.data(), pcBytes.size() < sizeof pc ? pcBytes.size() : sizeof pc);
-    auto frameB = bindings[2]->Find("frameData");
-    auto depthB = bindings[1]->Find("sceneDepth");
+    auto depth = bound_texture(bindings[1], "sceneDepth");
     auto culledB = bindings[1]->Find("culledLights");
-    if (!frameB || frameB->m_hostCopy.size() < sizeof(SailorUboFrameData) || !depthB || depthB->m_textures.empty() || !culledB) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     SailorUboFrameData frame;
-    memcpy(&frame, frameB->m_hostCopy.data(), sizeof frame);
+    if (!host_copy_of(bindings[2], "frameData", frame) || !depth || !culledB) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     SailorBand band;
     if (m_worldSize > 1) {
         // Split frame: the node sized its push constants by the depth attachment it was given (LightCullingNode.cpp:55-57) -- the band's rows.
@@ -591,7 +625,7 @@ int HipGraphicsDriver::RecordLightCulling(const TVector<RHIShaderBindingSetPtr>&
     if (m_packPending) { sailor_hip_context_wait_for(m_ctx, m_ctxAux); m_packPending = false; } // (a second cull in one submit: its workspace is the one the pending pack reads)
     const bool defer = m_ctxAux != nullptr;
     const int st = sailor_hip_light_cull_prepared(m_ctx, &frame, &pc, (const SailorLightShaderData*)buffer_of(bindings[0], "light"),
-                                                  (const float*)depthB->m_textures[0]->m_buffer->m_hip.m_devicePtr, grid, culled,
+                                                  (const float*)depth->m_buffer->m_hip.m_devicePtr, grid, culled,
                                                   culledB->m_buffer->m_size / 4, m_cullWorkspace->m_hip.m_devicePtr, m_cullWorkspace->m_size, &band,
                                                   defer ? SAILOR_CULL_DEFER_PACK : SAILOR_CULL_DEFAULT,
                                                   prepared ? lightB->m_hipPreparedLights->m_hip.m_devicePtr : nullptr, prepared ? lightB->m_hipPreparedCapacity : 0);
@@ -650,12 +684,10 @@ int HipGraphicsDriver::RecordShade(const TVector<RHIShaderBindingSetPtr>& bindin
     // Standard.shader:180-251: set 0 frame, set 1 lights {0 light, 1 culledLights, 2 lightsGrid, 6 lightsMatrices, 8 shadowMaps},
     // set 2 the surface/radiance buffers that stand in for the rasterised fragments (per-instance / material / textures sets)
     if (bindings.size() != 3) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    auto frameB = bindings[0]->Find("frameData");
     auto surfaceB = bindings[2]->Find("surface");
     auto countB = bindings[1]->Find("light");
-    if (!frameB || frameB->m_hostCopy.size() < sizeof(SailorUboFrameData) || !surfaceB || !surfaceB->m_buffer || !countB) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     SailorUboFrameData frame;
-    memcpy(&frame, frameB->m_hostCopy.data(), sizeof frame);
+    if (!host_copy_of(bindings[0], "frameData", frame) || !surfaceB || !surfaceB->m_buffer || !countB) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     const int W = frame.viewportSize[0], H = frame.viewportSize[1];
     SailorCsmDesc csm {};
     bool hasCsm = false;
@@ -677,11 +709,8 @@ int HipGraphicsDriver::RecordShade(const TVector<RHIShaderBindingSetPtr>& bindin
     SailorIblDesc ibl {};
     bool hasIbl = false;
     {
-        auto tex = [&](const char* name) -> RHITexturePtr {
-            auto b = bindings[1]->Find(name);
-            return (b && !b->m_textures.empty() && b->m_textures[0] && b->m_textures[0]->m_buffer) ? b->m_textures[0] : RHITexturePtr();
-        };
-        auto irr = tex("g_irradianceCubemap"), lut = tex("g_brdfSampler"), env = tex("g_envCubemap"), ao = tex("g_aoSampler");
+        auto irr = bound_texture(bindings[1], "g_irradianceCubemap"), lut = bound_texture(bindings[1], "g_brdfSampler");
+        auto env = bound_texture(bindings[1], "g_envCubemap"), ao = bound_texture(bindings[1], "g_aoSampler");
         if (irr && lut && env) {
             ibl.irradiance = (const float*)irr->m_buffer->m_hip.m_devicePtr; ibl.irrSize = irr->m_extent.x;
             ibl.env = (const float*)env->m_buffer->m_hip.m_devicePtr; ibl.envSize = env->m_extent.x; ibl.envLevels = (int32_t)env->m_mipLevels;
@@ -851,14 +880,10 @@ int HipGraphicsDriver::RecordLinearizeDepth(const TVector<RHIShaderBindingSetPtr
 {
     // LinearizeDepthNode.cpp:89: { sceneView.m_frameBindings, m_linearizeDepth }; LinearizeDepth.shader:15-28 (set 0 frame), :58 (set 1 depthSampler)
     if (bindings.size() != 2 || !target || !target->m_buffer) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    auto frameB = bindings[0]->Find("frameData");
-    auto depthB = bindings[1]->Find("depthSampler");
-    if (!frameB || frameB->m_hostCopy.size() < sizeof(SailorUboFrameData) || !depthB || depthB->m_textures.empty() || !depthB->m_textures[0]->m_buffer)
-        return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    const auto& src = depthB->m_textures[0];
-    if (src->GetExtent().x != target->GetExtent().x || src->GetExtent().y != target->GetExtent().y) return SAILOR_HIP_ERR_UNSUPPORTED; // 1:1 texel fetch only
+    auto src = bound_texture(bindings[1], "depthSampler");
     SailorUboFrameData frame;
-    memcpy(&frame, frameB->m_hostCopy.data(), sizeof frame);
+    if (!host_copy_of(bindings[0], "frameData", frame) || !src) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (src->GetExtent().x != target->GetExtent().x || src->GetExtent().y != target->GetExtent().y) return SAILOR_HIP_ERR_UNSUPPORTED; // 1:1 texel fetch only
     return sailor_hip_linearize_depth(m_ctx, &frame, (const float*)src->m_buffer->m_hip.m_devicePtr, (float*)target->m_buffer->m_hip.m_devicePtr,
                                       target->GetExtent().x, target->GetExtent().y);
 }
@@ -870,11 +895,8 @@ int HipGraphicsDriver::RecordLuminanceHistogram(const TVector<RHIShaderBindingSe
     // { minLog2Luminance, 1 / range }.  The group counts of the Dispatch (extent / 16) are implied by the image: the kernel applies the same truncation.
     if (bindings.size() != 1 || pcBytes.size() < 2 * sizeof(float)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     auto histB = bindings[0]->Find("histogram");
-    auto colorB = bindings[0]->Find("s_texColor");
-    if (!histB || !histB->m_buffer || histB->m_buffer->m_size < sailor_hip_eye_adaptation_state_size() || !colorB || colorB->m_textures.empty() || !colorB->m_textures[0] ||
-        !colorB->m_textures[0]->m_buffer)
-        return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    const auto& color = colorB->m_textures[0];
+    auto color = bound_texture(bindings[0], "s_texColor");
+    if (!histB || !histB->m_buffer || histB->m_buffer->m_size < sailor_hip_eye_adaptation_state_size() || !color) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     if (color->m_format != EFormat::R32G32B32A32_SFLOAT) return SAILOR_HIP_ERR_UNSUPPORTED;
     SailorEyeAdaptationConstants k {};
     memcpy(&k.minLog2Luminance, pcBytes.data(), 4);
@@ -891,10 +913,10 @@ int HipGraphicsDriver::RecordAverageLuminance(const TVector<RHIShaderBindingSetP
     // luminance target), push constants { minLog2Luminance, log2LuminanceRange, numPixels, timeCoeff }
     if (bindings.size() != 1 || pcBytes.size() < 4 * sizeof(float)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     auto histB = bindings[0]->Find("histogram");
-    auto lumB = bindings[0]->Find("s_texColor");
-    if (!histB || !histB->m_buffer || !lumB || lumB->m_textures.empty() || !lumB->m_textures[0]) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    auto lum = first_texture(bindings[0], "s_texColor"); // (not bound_texture: a target that is no state's word may have no buffer and is UNSUPPORTED below)
+    if (!histB || !histB->m_buffer || !lum) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     // the target must be the luminance word of THIS histogram's state (AddStorageImageToShaderBindings made it so)
-    if (lumB->m_textures[0]->m_hipEyeAdaptationState.GetRawPtr() != histB->m_buffer.GetRawPtr()) return SAILOR_HIP_ERR_UNSUPPORTED;
+    if (lum->m_hipEyeAdaptationState.GetRawPtr() != histB->m_buffer.GetRawPtr()) return SAILOR_HIP_ERR_UNSUPPORTED;
     float pc[4];
     memcpy(pc, pcBytes.data(), sizeof pc);
     SailorEyeAdaptationConstants k {};
@@ -907,51 +929,30 @@ int HipGraphicsDriver::RecordTonemap(const TVector<RHIShaderBindingSetPtr>& bind
     // EyeAdaptationNode.cpp:215: { sceneView.m_frameBindings, m_shaderBindings }; Tonemapping.shader:52-59: set 1 binding 0 `data` { whitePoint, exposure },
     // 1 `colorSampler`, 2 `averageLuminanceSampler`.  The quad's texcoords address the source at texel centres: a texel fetch of a same-size source.
     if (bindings.size() != 2 || !target || !target->m_buffer) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    auto dataB = bindings[1]->Find("data");
-    auto srcB = bindings[1]->Find("colorSampler");
-    auto lumB = bindings[1]->Find("averageLuminanceSampler");
-    if (!dataB || dataB->m_hostCopy.size() < 32 || !srcB || srcB->m_textures.empty() || !srcB->m_textures[0] || !srcB->m_textures[0]->m_buffer || !lumB ||
-        lumB->m_textures.empty() || !lumB->m_textures[0] || !lumB->m_textures[0]->m_hipEyeAdaptationState)
-        return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    const auto& src = srcB->m_textures[0];
+    auto src = bound_texture(bindings[1], "colorSampler");
+    auto lum = first_texture(bindings[1], "averageLuminanceSampler");
+    float data[8];
+    if (!host_copy_of(bindings[1], "data", data) || !src || !lum || !lum->m_hipEyeAdaptationState) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     if (src->m_format != EFormat::R32G32B32A32_SFLOAT || target->m_format != EFormat::R32G32B32A32_SFLOAT) return SAILOR_HIP_ERR_UNSUPPORTED;
     if (src->GetExtent().x != target->GetExtent().x || src->GetExtent().y != target->GetExtent().y) return SAILOR_HIP_ERR_INVALID_ARGUMENT; // differing sizes are refused
-    float data[8];
-    memcpy(data, dataB->m_hostCopy.data(), sizeof data);
     SailorBand whole;
     if (sailor_hip_band_whole_frame(target->GetExtent().x, target->GetExtent().y, &whole) != SAILOR_HIP_OK) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     BeforeBufferWrite(target->m_buffer->m_hip.m_devicePtr);
     return sailor_hip_tonemap(m_ctx, (const float*)src->m_buffer->m_hip.m_devicePtr, (float*)target->m_buffer->m_hip.m_devicePtr, target->GetExtent().x,
-                              target->GetExtent().y, &whole, operatorFlags, data, data[4], lumB->m_textures[0]->m_hipEyeAdaptationState->m_hip.m_devicePtr);
+                              target->GetExtent().y, &whole, operatorFlags, data, data[4], lum->m_hipEyeAdaptationState->m_hip.m_devicePtr);
 }
 
 // ---- PostProcessNode with the HBAO shaders (FrameGraph/PostProcessNode.cpp:186-199; DefaultRenderer.renderer:220-264) ---------------------------
-// a bound sampler as a one-channel fp32 plane, or null
-static RHITexturePtr plane_of(const RHIShaderBindingSetPtr& set, const char* name)
-{
-    auto b = set ? set->Find(name) : RHIShaderBindingPtr();
-    if (!b || b->m_textures.empty() || !b->m_textures[0] || !b->m_textures[0]->m_buffer || b->m_textures[0]->m_format != EFormat::R32_SFLOAT) return RHITexturePtr();
-    return b->m_textures[0];
-}
-
 int HipGraphicsDriver::RecordHbao(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& target)
 {
     // PostProcessNode.cpp:189: { sceneView.m_frameBindings, m_shaderBindings, sceneView.m_rhiLightsData }; HBAO.shader:26-36 (set 0 frame), :50-60 (set 1:
     // binding 0 `data`, 1 `depthSampler`, 2 `noiseSampler`).  A name that resolved to nothing is an invalid argument.
     if (bindings.size() < 2 || !target || !target->m_buffer || target->m_format != EFormat::R32_SFLOAT) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    auto frameB = bindings[0]->Find("frameData");
-    auto dataB = bindings[1]->Find("data");
-    auto depth = plane_of(bindings[1], "depthSampler");
-    auto noiseB = bindings[1]->Find("noiseSampler");
-    if (!frameB || frameB->m_hostCopy.size() < sizeof(SailorUboFrameData) || !dataB || dataB->m_hostCopy.size() < sizeof(SailorHbaoParams) || !depth || !noiseB ||
-        noiseB->m_textures.empty() || !noiseB->m_textures[0] || !noiseB->m_textures[0]->m_buffer)
-        return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    const auto& noise = noiseB->m_textures[0];
-    if (noise->m_format != EFormat::R32G32B32A32_SFLOAT) return SAILOR_HIP_ERR_UNSUPPORTED;
+    auto depth = bound_texture(bindings[1], "depthSampler", EFormat::R32_SFLOAT), noise = bound_texture(bindings[1], "noiseSampler");
     SailorUboFrameData frame;
-    memcpy(&frame, frameB->m_hostCopy.data(), sizeof frame);
     SailorHbaoParams params;
-    memcpy(&params, dataB->m_hostCopy.data(), sizeof params);
+    if (!host_copy_of(bindings[0], "frameData", frame) || !host_copy_of(bindings[1], "data", params) || !depth || !noise) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (noise->m_format != EFormat::R32G32B32A32_SFLOAT) return SAILOR_HIP_ERR_UNSUPPORTED;
     BeforeBufferWrite(target->m_buffer->m_hip.m_devicePtr);
     return sailor_hip_hbao(m_ctx, &frame, (const float*)texels_of(depth), depth->GetExtent().x, depth->GetExtent().y, (const float*)texels_of(noise),
                            noise->GetExtent().x, noise->GetExtent().y, &params, (float*)texels_of(target), target->GetExtent().x, target->GetExtent().y);
@@ -961,44 +962,28 @@ int HipGraphicsDriver::RecordHbaoBlur(const TVector<RHIShaderBindingSetPtr>& bin
 {
     // HBAO_Blur.shader:54-62: set 1 binding 0 `data` { sharpness, distanceScale, radius }, 1 `depthSampler`, 2 `aoSampler`
     if (bindings.size() < 2 || !target || !target->m_buffer || target->m_format != EFormat::R32_SFLOAT) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    auto dataB = bindings[1]->Find("data");
-    auto depth = plane_of(bindings[1], "depthSampler"), ao = plane_of(bindings[1], "aoSampler");
-    if (!dataB || dataB->m_hostCopy.size() < sizeof(SailorHbaoBlurParams) || !depth || !ao) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    auto depth = bound_texture(bindings[1], "depthSampler", EFormat::R32_SFLOAT), ao = bound_texture(bindings[1], "aoSampler", EFormat::R32_SFLOAT);
     SailorHbaoBlurParams params;
-    memcpy(&params, dataB->m_hostCopy.data(), sizeof params);
+    if (!host_copy_of(bindings[1], "data", params) || !depth || !ao) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     BeforeBufferWrite(target->m_buffer->m_hip.m_devicePtr);
     return sailor_hip_hbao_blur_pass(m_ctx, (const float*)texels_of(ao), ao->GetExtent().x, ao->GetExtent().y, (const float*)texels_of(depth), depth->GetExtent().x,
                                      depth->GetExtent().y, &params, (float*)texels_of(target), target->GetExtent().x, target->GetExtent().y, vertical ? 1 : 0);
 }
 
 // ---- PostProcessNode with the frame's tail (DefaultRenderer.renderer:322-353) -------------------------------------------------------------------
-// a bound sampler as an RGBA32F image (level 0 of a mip chain such as Main: texels_of / GetExtent address it), or null
-static RHITexturePtr rgba_of(const RHIShaderBindingSetPtr& set, const char* name)
-{
-    auto b = set ? set->Find(name) : RHIShaderBindingPtr();
-    if (!b || b->m_textures.empty() || !b->m_textures[0] || !b->m_textures[0]->m_buffer || b->m_textures[0]->m_format != EFormat::R32G32B32A32_SFLOAT || b->m_textures[0]->m_bCubemap)
-        return RHITexturePtr();
-    return b->m_textures[0];
-}
-
 int HipGraphicsDriver::RecordMotionBlur(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& target)
 {
     // PostProcessNode.cpp:189: { sceneView.m_frameBindings, m_shaderBindings, sceneView.m_rhiLightsData }; MotionBlur.shader:26-48 (set 0: binding 0 `frameData`,
     // 1 `previousFrameData`), :50-58 (set 1: binding 0 `data`, 1 `depthSampler`, 2 `colorSampler`).  A name that resolved to nothing is an invalid argument.
     // `color: Main` with Main a mip chain: the attachment is the chain, whose texels start with level 0 and whose extent is level 0's.
     if (bindings.size() < 2 || !target || !target->m_buffer || target->m_format != EFormat::R32G32B32A32_SFLOAT) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    auto frameB = bindings[0]->Find("frameData"), prevB = bindings[0]->Find("previousFrameData");
-    auto dataB = bindings[1]->Find("data");
-    auto depth = plane_of(bindings[1], "depthSampler");
-    auto color = rgba_of(bindings[1], "colorSampler");
-    if (!frameB || frameB->m_hostCopy.size() < sizeof(SailorUboFrameData) || !prevB || prevB->m_hostCopy.size() < sizeof(SailorUboFrameData) || !dataB ||
-        dataB->m_hostCopy.size() < sizeof(SailorMotionBlurParams) || !depth || !color)
-        return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    auto depth = bound_texture(bindings[1], "depthSampler", EFormat::R32_SFLOAT);
+    auto color = bound_texture(bindings[1], "colorSampler", EFormat::R32G32B32A32_SFLOAT, true);
     SailorUboFrameData frame, previous;
-    memcpy(&frame, frameB->m_hostCopy.data(), sizeof frame);
-    memcpy(&previous, prevB->m_hostCopy.data(), sizeof previous);
     SailorMotionBlurParams params;
-    memcpy(&params, dataB->m_hostCopy.data(), sizeof params);
+    if (!host_copy_of(bindings[0], "frameData", frame) || !host_copy_of(bindings[0], "previousFrameData", previous) || !host_copy_of(bindings[1], "data", params) ||
+        !depth || !color)
+        return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     BeforeBufferWrite(target->m_buffer->m_hip.m_devicePtr);
     return sailor_hip_motion_blur(m_ctx, &frame, &previous, (const float*)texels_of(depth), depth->GetExtent().x, depth->GetExtent().y, (const float*)texels_of(color),
                                   color->GetExtent().x, color->GetExtent().y, &params, (float*)texels_of(target), target->GetExtent().x, target->GetExtent().y);
@@ -1011,12 +996,10 @@ int HipGraphicsDriver::RecordDebugView(const TVector<RHIShaderBindingSetPtr>& bi
     // define set, so a name that resolved to nothing refuses the draw whichever mode reads it -- except the lights set's, which a scene without lights
     // does not have: those are required by the mode that reads them (the entry point refuses a null it needs).
     if (bindings.size() < 2 || mode < 0 || !target || !target->m_buffer || target->m_format != EFormat::R32G32B32A32_SFLOAT) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    auto frameB = bindings[0]->Find("frameData");
-    auto scene = rgba_of(bindings[1], "ldrSceneSampler");
-    auto depth = plane_of(bindings[1], "linearDepthSampler");
-    if (!frameB || frameB->m_hostCopy.size() < sizeof(SailorUboFrameData) || !scene || !depth) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    auto scene = bound_texture(bindings[1], "ldrSceneSampler", EFormat::R32G32B32A32_SFLOAT, true);
+    auto depth = bound_texture(bindings[1], "linearDepthSampler", EFormat::R32_SFLOAT);
     SailorUboFrameData frame;
-    memcpy(&frame, frameB->m_hostCopy.data(), sizeof frame);
+    if (!host_copy_of(bindings[0], "frameData", frame) || !scene || !depth) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     const RHIShaderBindingSetPtr lights = bindings.size() > 2 ? bindings[2] : RHIShaderBindingSetPtr();
     const SailorLightsGrid* grid = nullptr;
     const uint32_t* culled = nullptr;
@@ -1033,7 +1016,7 @@ int HipGraphicsDriver::RecordDebugView(const TVector<RHIShaderBindingSetPtr>& bi
         // the two SSBOs are filled by the compaction on the second queue: the view reads them behind it
         if (m_packPending) { sailor_hip_context_wait_for(m_ctx, m_ctxAux); m_packPending = false; }
     }
-    if (mode == SAILOR_DEBUG_VIEW_AO) ao = plane_of(lights, "g_aoSampler");
+    if (mode == SAILOR_DEBUG_VIEW_AO) ao = bound_texture(lights, "g_aoSampler", EFormat::R32_SFLOAT);
     BeforeBufferWrite(target->m_buffer->m_hip.m_devicePtr);
     return sailor_hip_debug_view(m_ctx, &frame, mode, (const float*)texels_of(scene), scene->GetExtent().x, scene->GetExtent().y, (const float*)texels_of(depth),
                                  depth->GetExtent().x, depth->GetExtent().y, grid, culled, ao ? (const float*)texels_of(ao) : nullptr, ao ? ao->GetExtent().x : 0,
@@ -1046,18 +1029,11 @@ int HipGraphicsDriver::RecordSky(const TVector<RHIShaderBindingSetPtr>& bindings
     // { sceneView.m_frameBindings | m_pEnvCubemapBindings[face], m_pShaderBindings }; Sky.shader:104-136 (set 0 frame, set 1 binding 0 `data`), :138-153
     // (1 `skySampler`, 2 `sunSampler`, 6 `cloudsSampler`)
     if (bindings.size() != 2 || !target || !target->m_buffer || target->m_format != EFormat::R32G32B32A32_SFLOAT) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    auto frameB = bindings[0]->Find("frameData");
-    auto dataB = bindings[1]->Find("data");
-    if (!frameB || frameB->m_hostCopy.size() < sizeof(SailorUboFrameData) || !dataB || dataB->m_hostCopy.size() < sizeof(SailorSkyParams)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     SailorUboFrameData frame;
-    memcpy(&frame, frameB->m_hostCopy.data(), sizeof frame);
     SailorSkyParams params;
-    memcpy(&params, dataB->m_hostCopy.data(), sizeof params);
-    auto rgba_of = [&](const char* name) -> RHITexturePtr {
-        auto b = bindings[1]->Find(name);
-        if (!b || b->m_textures.empty() || !b->m_textures[0] || !b->m_textures[0]->m_buffer || b->m_textures[0]->m_format != EFormat::R32G32B32A32_SFLOAT) return RHITexturePtr();
-        return b->m_textures[0];
-    };
+    if (!host_copy_of(bindings[0], "frameData", frame) || !host_copy_of(bindings[1], "data", params)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    // (a cubemap under one of the node's samplers is not refused here, as it is for the frame's tail: the node binds its own 2D targets)
+    auto rgba_of = [&](const char* name) { return bound_texture(bindings[1], name, EFormat::R32G32B32A32_SFLOAT); };
     BeforeBufferWrite(target->m_buffer->m_hip.m_devicePtr);
     if (permutation == 0) return sailor_hip_sky_fill(m_ctx, &frame, &params, (float*)texels_of(target), target->GetExtent().x, target->GetExtent().y);
     if (permutation == 1) { // one face of a cube: the attachment is cubemap->GetFace(face, 0), whose matrices the node wrote with sailor_host_sky_face_matrices
@@ -1086,24 +1062,16 @@ int HipGraphicsDriver::RecordSky(const TVector<RHIShaderBindingSetPtr>& bindings
 int HipGraphicsDriver::RecordSkyClouds(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& target)
 {
     if (bindings.size() != 2 || !target || !target->m_buffer || target->m_format != EFormat::R32G32B32A32_SFLOAT) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    auto frameB = bindings[0]->Find("frameData");
-    auto dataB = bindings[1]->Find("data");
-    if (!frameB || frameB->m_hostCopy.size() < sizeof(SailorUboFrameData) || !dataB || dataB->m_hostCopy.size() < sizeof(SailorSkyParams)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    auto bound = [&](const char* name, EFormat format) -> RHITexturePtr {
-        auto b = bindings[1]->Find(name);
-        if (!b || b->m_textures.empty() || !b->m_textures[0] || !b->m_textures[0]->m_buffer || b->m_textures[0]->m_format != format) return RHITexturePtr();
-        return b->m_textures[0];
-    };
+    SailorUboFrameData frame;
+    SailorSkyParams params;
+    if (!host_copy_of(bindings[0], "frameData", frame) || !host_copy_of(bindings[1], "data", params)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    auto bound = [&](const char* name, EFormat format) { return bound_texture(bindings[1], name, format); };
     auto sky = bound("skySampler", EFormat::R32G32B32A32_SFLOAT), map = bound("cloudsMapSampler", EFormat::R8G8B8A8_UNORM);
     auto low = bound("cloudsNoiseLowSampler", EFormat::R8_UNORM), high = bound("cloudsNoiseHighSampler", EFormat::R8_UNORM);
     auto noise = bound("g_noiseSampler", EFormat::R32G32B32A32_SFLOAT), depth = bound("linearDepth", EFormat::R32_SFLOAT);
     if (!sky || !map || !low || !high || !noise || !depth) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     for (const auto& v : { low, high })
         if (v->GetExtent().x != v->GetExtent().y || v->m_depth != v->GetExtent().x) return SAILOR_HIP_ERR_INVALID_ARGUMENT; // cubes
-    SailorUboFrameData frame;
-    memcpy(&frame, frameB->m_hostCopy.data(), sizeof frame);
-    SailorSkyParams params;
-    memcpy(&params, dataB->m_hostCopy.data(), sizeof params);
     BeforeBufferWrite(target->m_buffer->m_hip.m_devicePtr);
     const int st = sailor_hip_sky_clouds(m_ctx, &frame, &params, (const float*)texels_of(sky), sky->GetExtent().x, sky->GetExtent().y, (const uint8_t*)texels_of(map),
                                          map->GetExtent().x, map->GetExtent().y, (const uint8_t*)texels_of(low), low->GetExtent().x, (const uint8_t*)texels_of(high),
@@ -1117,9 +1085,8 @@ int HipGraphicsDriver::RecordSkyClouds(const TVector<RHIShaderBindingSetPtr>& bi
 int HipGraphicsDriver::RecordBlitAlphaBlended(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& target)
 {
     if (bindings.size() != 2 || !target || !target->m_buffer || target->m_format != EFormat::R32G32B32A32_SFLOAT) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    auto srcB = bindings[1]->Find("colorSampler");
-    if (!srcB || srcB->m_textures.empty() || !srcB->m_textures[0] || !srcB->m_textures[0]->m_buffer) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    const auto& src = srcB->m_textures[0];
+    auto src = bound_texture(bindings[1], "colorSampler");
+    if (!src) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     if (src->m_format != EFormat::R32G32B32A32_SFLOAT) return SAILOR_HIP_ERR_UNSUPPORTED;
     SailorBand whole;
     if (sailor_hip_band_whole_frame(target->GetExtent().x, target->GetExtent().y, &whole) != SAILOR_HIP_OK) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
@@ -1133,27 +1100,16 @@ int HipGraphicsDriver::RecordEvsmBlur(const TVector<RHIShaderBindingSetPtr>& bin
     // ShadowPrepassNode.cpp:309,343: { sceneView.m_frameBindings, m_pBlurShaderBindings }; Blur.shader:53-61: set 1 binding 0 `data` (blurRadius.xy =
     // [umbra, penumbra], uploaded at :286), binding 1 `colorSampler`
     if (bindings.size() != 2 || !target || !target->m_buffer) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    auto dataB = bindings[1]->Find("data");
-    auto srcB = bindings[1]->Find("colorSampler");
-    if (!dataB || dataB->m_hostCopy.size() < 8 || !srcB || srcB->m_textures.empty() || !srcB->m_textures[0] || !srcB->m_textures[0]->m_buffer)
-        return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    const auto& src = srcB->m_textures[0];
+    auto src = bound_texture(bindings[1], "colorSampler");
+    float radius[2];
+    if (!host_copy_of(bindings[1], "data", radius) || !src) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     if (src->m_format != EFormat::R32G32B32A32_SFLOAT || target->m_format != EFormat::R32G32B32A32_SFLOAT) return SAILOR_HIP_ERR_UNSUPPORTED;
     if (src->GetExtent().x != target->GetExtent().x || src->GetExtent().y != target->GetExtent().y) return SAILOR_HIP_ERR_UNSUPPORTED;
-    float radius[2];
-    memcpy(radius, dataB->m_hostCopy.data(), 8);
     return sailor_hip_evsm_blur_pass(m_ctx, (const float*)src->m_buffer->m_hip.m_devicePtr, (float*)target->m_buffer->m_hip.m_devicePtr,
                                      target->GetExtent().x, target->GetExtent().y, (int32_t)radius[0], (int32_t)radius[1], vertical ? 1 : 0); // ivec2(data.blurRadius.xy) (Blur.shader:94)
 }
 
 // ---- EnvironmentNode's one-off Dispatches (FrameGraph/EnvironmentNode.cpp:86-91, :223-231, :264-269) ------------------------------------------
-static RHITexturePtr texture_of(const TVector<RHIShaderBindingSetPtr>& bindings, const char* name, size_t index = 0)
-{
-    for (const auto& set : bindings)
-        if (set) if (auto b = set->Find(name)) if (b->m_textures.size() > index) return b->m_textures[index];
-    return RHITexturePtr();
-}
-
 int HipGraphicsDriver::RecordBrdfLut(const TVector<RHIShaderBindingSetPtr>& bindings)
 {
     auto dst = texture_of(bindings, "dst"); // ComputeBrdfLut.shader:24 (rg16f there; two fp32 channels here)
@@ -1186,7 +1142,8 @@ int HipGraphicsDriver::RecordEnvPrefilter(const TVector<RHIShaderBindingSetPtr>&
 }
 
 // ---- BloomNode (FrameGraph/BloomNode.cpp:110-115, :135-140) ----------------------------------------------------------------------------------
-// a bound RGBA32F image (a mip-level view of the bloom target, the lens-dirt sampler), or null
+// a bound RGBA32F image (a mip-level view of the bloom target, the lens-dirt sampler), or null.  On texture_of, not bound_texture: the node's
+// Dispatch does not say which of its sets holds a name, so every set is searched.
 static RHITexturePtr rgba_image_of(const TVector<RHIShaderBindingSetPtr>& bindings, const char* name)
 {
     auto t = texture_of(bindings, name);
@@ -1246,18 +1203,17 @@ int HipGraphicsDriver::RecordMeshCulling(const TVector<RHIShaderBindingSetPtr>& 
     if (bindings.size() < 2 || pcBytes.size() < 12) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     uint32_t pc[3];
     memcpy(pc, pcBytes.data(), 12);
-    RHIShaderBindingPtr frameB;
+    RHIShaderBindingSetPtr frameSet;
     void* data = nullptr;
     void* batches = nullptr;
     for (const auto& set : bindings) {
         if (!set) continue;
-        if (auto f = set->Find("frameData")) frameB = f;
+        if (set->Find("frameData")) frameSet = set;
         if (void* d = buffer_of(set, "data")) data = d;
         if (void* d = buffer_of(set, "drawIndexedIndirect")) batches = d;
     }
-    if (!frameB || frameB->m_hostCopy.size() < sizeof(SailorUboFrameData)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     SailorUboFrameData frame;
-    memcpy(&frame, frameB->m_hostCopy.data(), sizeof frame);
+    if (!host_copy_of(frameSet, "frameData", frame)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     SailorHiZDesc hiz {};
     const SailorHiZDesc* pHiz = nullptr;
     if (occlusion) {
