@@ -830,8 +830,8 @@ SAILOR_HIP_API int sailor_hip_debug_view(SailorHipContext* ctx, const SailorUboF
  * of a w x h target has the quad's inTexcoord ((i + 0.5) / w, (j + 0.5) / h); alpha is stored as 0.  The arithmetic is fixed operation by
  * operation (sailor_amd/csrc/sky.hip's header lists the decisions; tests/sky_ref.py restates it in NumPy float32): every branch is decided by
  * geometry evaluated in fp32 exactly as written, exp is the fixed algorithm of canonical_math.h with its argument clamp, and only the sums over
- * the 127 view steps are reassociated.  Not drawn: Stars.shader, SunShafts.shader.  These five entry points behave as the reference does with
- * m_cloudsDensity == 0 (SkyNode.cpp:604-609); the clouds have entry points of their own below.
+ * the 127 view steps are reassociated.  These five entry points behave as the reference does with m_cloudsDensity == 0 (SkyNode.cpp:604-609);
+ * the clouds, and the star points and sun shafts of the region "Stars & Clouds" (:692-747), have entry points of their own below.
  * All of them record only (no synchronisation, capturable). */
 
 /* Sky.shader:116-136 PostProcessDataUBO == SkyNode::SkyParams (SkyNode.h:48-67), std140: a vec4 at 0, then 4-byte scalars at 16, 20, .. 80.  84 bytes. */
@@ -911,6 +911,34 @@ SAILOR_HIP_API int sailor_hip_sky_sun_clouds(SailorHipContext* ctx, const Sailor
  *   dTarget : device in/out, float4 per pixel of the width x height target, the rows of `band` only (first row = band->fbRowBegin) */
 SAILOR_HIP_API int sailor_hip_sky_blit_clouds(SailorHipContext* ctx, const float* dClouds, int32_t cloudsWidth, int32_t cloudsHeight,
                                               float* dTarget, int32_t width, int32_t height, const SailorBand* band);
+
+/* ---- Sky, "Stars & Clouds": the star points before and the sun shafts after the clouds blit (SkyNode.cpp:692-747) -----------------------------------
+ * sailor_amd/csrc/sky_stars.hip's header lists the decisions -- the reading of the EBlendMode::Multiply state among them --; tests/stars_ref.py restates
+ * the kernels in NumPy float32 and they are held to it bit for bit.  Both work in place on the rows of `band` of the target (first row =
+ * band->fbRowBegin), record only (no allocation, no synchronisation, capturable), and a refused call records nothing. */
+
+/* Replaces: the draw "Sun Shafts" (SkyNode.cpp:733-739), SunShafts.shader:96-140 under EBlendMode::Multiply (VulkanPipileneStates.cpp:248-254), read as
+ * rgb = Cs Cd + Cs (1 - Ad) + Cd (1 - As), a = As As - Ad Ad.  uvView and both early-outs are computed on the host; a fragment that returns early is
+ * (0, 0, 0, 0) and is still blended, so the pass is recorded in every case.
+ *   frame  : view and projection are read;  params : lightDirection, sunShaftsIntensity, sunShaftsDistance (outside 1 .. 1024: SAILOR_HIP_ERR_INVALID_ARGUMENT)
+ *   dClouds: `cloudsSampler`, the plane of sailor_hip_sky_clouds, bilinear clamp-to-edge, the base level;  it must not overlap dTarget */
+SAILOR_HIP_API int sailor_hip_sky_sun_shafts(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSkyParams* params,
+                                             const float* dClouds, int32_t cloudsWidth, int32_t cloudsHeight,
+                                             float* dTarget, int32_t width, int32_t height, const SailorBand* band);
+/* Replaces: the point-list draw of the star mesh (SkyNode.cpp:694-720), Stars.shader under EBlendMode::Additive, gl_PointSize = 1, no depth test.
+ * Stars that share a pixel are added in index order (Vulkan's primitive order): the same bits on every run, no float atomics.
+ *   frame   : view, projection, invProjection, cameraPosition; viewportSize must equal (width, height)
+ *   model16 : host, the push constant: sailor_host_sky_stars_model
+ *   dPositions / dColors : device, count x 3 and count x 4 floats (sailor_host_sky_star_mesh), 16-byte aligned; count above 65 536 is refused
+ *   dClouds : `cloudsSampler`; NULL = the cleared m_pCloudsTexture, alpha 0
+ * Needs a workspace of sailor_hip_sky_stars_workspace_bytes(count) bound to the context beforehand (sailor_hip_sky_stars_bind_workspace: the caller's
+ * device memory, 16-byte aligned, not owned, NULL unbinds); without one the call is refused.  The query returns 0 for a count it refuses. */
+SAILOR_HIP_API size_t sailor_hip_sky_stars_workspace_bytes(int32_t count);
+SAILOR_HIP_API int sailor_hip_sky_stars_bind_workspace(SailorHipContext* ctx, void* dWorkspace, size_t workspaceBytes);
+SAILOR_HIP_API int sailor_hip_sky_stars(SailorHipContext* ctx, const SailorUboFrameData* frame, const float* model16,
+                                        const float* dPositions, const float* dColors, int32_t count,
+                                        const float* dClouds, int32_t cloudsWidth, int32_t cloudsHeight,
+                                        float* dTarget, int32_t width, int32_t height, const SailorBand* band);
 
 /* ---- Bloom (round 9): the Bloom node, FrameGraph/BloomNode.cpp:21-144 -- the mip pyramid over `Main`, rewritten in place ----------------------
  * tests/golden/DefaultRenderer.renderer:296-304.  `Main` is a level-major chain of RGBA32F planes (level l = max(1, width >> l) x max(1, height >> l),
@@ -1032,6 +1060,18 @@ SAILOR_HIP_API int sailor_host_sky_face_matrices(int32_t face, float* outView16,
 /* Sky.shader:247-264 CalculateSunColor(sunDirection) in fp32 (pow(x, 0.5) = sqrt, pow(x, 3) = (x x) x): the colour the cloud march multiplies in, which
  * does not vary per texel.  The march passes -dirToSun = normalize(lightDirection.xyz). */
 SAILOR_HIP_API int sailor_host_sky_sun_color(const float* sunDirection3, float* outColor3);
+
+/* FrameGraph/SkyNode.cpp:47-58: the node's temperature table from the `colors` rows of StarsColor.yaml (11 floats each: K, CMF, x, y, P, R, G, B, r, g, b):
+ * row (K / 100 - 10), clamped to 0 .. 390, takes (R, G, B); later rows overwrite earlier ones.  outTable: 391 x 3 floats, zero where no row lands. */
+SAILOR_HIP_API int sailor_host_sky_star_color_table(const float* rows, uint32_t rowCount, float* outTable);
+/* FrameGraph/SkyNode.cpp:61-91 with Core/Utils.cpp:454-464 and SkyNode.cpp:836-875: the BSC5 bytes (a packed 28-byte header, then abs(starCount) packed
+ * 32-byte entries) -> positions (x, y, z) and colours (r, g, b, a), pow(c, 1 / 2.2) applied.  sailor_amd/csrc/host_math.cpp lists the decisions where the
+ * reference indexes out of range.  *outCount = the catalogue's star count; a catalogue shorter than its header or than the entries it counts, or a
+ * capacity below the count, is SAILOR_HIP_ERR_INVALID_ARGUMENT and nothing is written past `capacity` stars. */
+SAILOR_HIP_API int sailor_host_sky_star_mesh(const uint8_t* catalogue, size_t bytes, const float* table, float* outPositions, float* outColors,
+                                             uint32_t capacity, uint32_t* outCount);
+/* FrameGraph/SkyNode.cpp:208-211 and :698: translate(mat4(1), cameraPosition) * toMat4(precession), the star draw's push constant */
+SAILOR_HIP_API int sailor_host_sky_stars_model(const float* cameraPosition3, float* outMat4);
 
 /* FrameGraph/BloomNode.cpp:89-93: PushConstantsDownscale::m_threshold = (threshold, threshold - knee, 2 knee, 0.25 knee) -- as the node writes it: the
  * shader's comment expects knee * 0.25 to be a quotient's denominator; restated, not repaired */

@@ -146,6 +146,7 @@ class SkyParams(C.Structure):  # include/sailor_hip.h SailorSkyParams (Sky.shade
 
 
 SKY_RESOLUTION, SKY_SUN_RESOLUTION, SKY_ENV_CUBEMAP_SIZE, SKY_ENV_CUBEMAP_LEVELS = 256, 32, 256, 8  # SkyNode.h:13-15, SkyNode.cpp:755
+SKY_STAR_TABLE_ROWS = 391  # sailor_host_sky_star_color_table: s_rgbTemperatures with the entry index 390 addresses
 
 
 class BloomParams(C.Structure):  # include/sailor_hip.h SailorBloomParams; defaults = DefaultRenderer.renderer:298-302
@@ -278,7 +279,17 @@ SIGNATURES = {
                                         _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32]),
     "sailor_hip_sky_sun_clouds": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(SkyParams), _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32]),
     "sailor_hip_sky_blit_clouds": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.POINTER(Band)]),
+    "sailor_hip_sky_sun_shafts": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(SkyParams), _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32,
+                                            C.POINTER(Band)]),
+    "sailor_hip_sky_stars_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "sailor_hip_sky_stars_bind_workspace": (C.c_int, [_P, _P, C.c_size_t]),
+    "sailor_hip_sky_stars": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(C.c_float), _P, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int32,
+                                       C.c_int32, C.POINTER(Band)]),
     "sailor_host_sky_sun_color": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "sailor_host_sky_star_color_table": (C.c_int, [C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float)]),
+    "sailor_host_sky_star_mesh": (C.c_int, [_P, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32,
+                                            C.POINTER(C.c_uint32)]),
+    "sailor_host_sky_stars_model": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "sailor_host_sky_params_default": (C.c_int, [C.POINTER(SkyParams)]),
     "sailor_host_sky_face_matrices": (C.c_int, [C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "sailor_hip_mip_chain_texels": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),

@@ -37,6 +37,9 @@ struct SailorHipContext {
     size_t exchangeSegHint = 0;        // slot size (uint32) of the next exchange's second gather; 0 = the worst case (tiles of the largest band x 128)
     hipEvent_t exchangeEvent = nullptr;
     bool exchangeEventValid = false;   // (an exchange recorded under stream capture leaves no event to wait on: adapt then waits for the stream)
+    // sailor_hip_sky_stars_bind_workspace: the caller's device memory for the star draw's per-star pixels and fragments (sky_stars.hip); not owned
+    void* starsWorkspace = nullptr;
+    size_t starsWorkspaceBytes = 0;
 };
 
 static inline int sailor_map_hip_error(SailorHipContext* ctx, hipError_t e, const char* what)

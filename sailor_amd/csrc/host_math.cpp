@@ -15,6 +15,7 @@
 #include "../../include/sailor_hip.h"
 #include <cmath>
 #include <cstring>
+#include <cstdlib>
 #include <vector>
 #include <new>
 #include <algorithm>
@@ -117,19 +118,30 @@ M4 ortho_rh_no(float left, float right, float bottom, float top, float zNear, fl
     return r;
 }
 
-M4 transform_matrix(const SailorTransform& t)
+// glm::translate(mat4(1), v): Result[3] = m[0]*v[0] + m[1]*v[1] + m[2]*v[2] + m[3]
+M4 translation(const float* v)
 {
     const M4 I = identity();
-    // glm::translate(m, v): Result[3] = m[0]*v[0] + m[1]*v[1] + m[2]*v[2] + m[3]
     M4 T = I;
-    T[3] = ((I[0] * t.position[0] + I[1] * t.position[1]) + I[2] * t.position[2]) + I[3];
-    // glm::mat4_cast(quat), quat memory order x,y,z,w
-    const float x = t.rotation[0], y = t.rotation[1], z = t.rotation[2], w = t.rotation[3];
+    T[3] = ((I[0] * v[0] + I[1] * v[1]) + I[2] * v[2]) + I[3];
+    return T;
+}
+// glm::mat4_cast(quat)
+M4 mat4_cast(float x, float y, float z, float w)
+{
     const float qxx = x * x, qyy = y * y, qzz = z * z, qxz = x * z, qxy = x * y, qyz = y * z, qwx = w * x, qwy = w * y, qwz = w * z;
-    M4 R = I;
+    M4 R = identity();
     R[0][0] = 1.0f - 2.0f * (qyy + qzz); R[0][1] = 2.0f * (qxy + qwz); R[0][2] = 2.0f * (qxz - qwy);
     R[1][0] = 2.0f * (qxy - qwz); R[1][1] = 1.0f - 2.0f * (qxx + qzz); R[1][2] = 2.0f * (qyz + qwx);
     R[2][0] = 2.0f * (qxz + qwy); R[2][1] = 2.0f * (qyz - qwx); R[2][2] = 1.0f - 2.0f * (qxx + qyy);
+    return R;
+}
+
+M4 transform_matrix(const SailorTransform& t)
+{
+    const M4 I = identity();
+    const M4 T = translation(t.position);
+    const M4 R = mat4_cast(t.rotation[0], t.rotation[1], t.rotation[2], t.rotation[3]); // quat memory order x,y,z,w
     // glm::scale(m, v): Result[i] = m[i] * v[i]; Result[3] = m[3]
     M4 S;
     S[0] = I[0] * t.scale[0]; S[1] = I[1] * t.scale[1]; S[2] = I[2] * t.scale[2]; S[3] = I[3];
@@ -411,6 +423,109 @@ int sailor_host_lights_in_frustum(const float* planes24, const float* cameraPosi
         else insert(outPoint, outPointDistance, np, i, d);
     }
     *outNumDirectional = nd; *outNumPoint = np; *outNumSpot = ns;
+    return SAILOR_HIP_OK;
+}
+
+} // extern "C"
+
+// ---- FrameGraph/SkyNode.cpp:31-91, :836-875 and Core/Utils.cpp:454-464: the star mesh of the Sky node from the Bright Star Catalogue ----------------
+// The reference indexes out of range on real data: the shipped catalogue holds the spectral bytes ' ' and 'p' (s_starTemperatureRanges[spectralType -
+// 'A'] has 25 entries for 'A' .. 'Y') and the sub-type bytes m p e N I C + / and space ('9' - subType wraps), and clamp(index, 0, 390) addresses
+// s_rgbTemperatures[390].  Decisions:
+//   * the integer arithmetic wraps in uint32 as written: subIndex = '9' - subType, subIndex * rangeStep, temperature / 100 - 10 reinterpreted as int32;
+//   * a float -> integer conversion saturates (NaN -> 0): uint32_t(x) into [0, 2^32 - 1];
+//   * a spectral byte outside 'A' .. 'Y' takes the range {0, 0};
+//   * the table has 391 entries, so that both clamps (:52: min(index, 390u); :866: clamp(index, 0, 390)) address it;
+//   * no byte pattern indexes outside a table or reads past `bytes`: a catalogue shorter than its header, or than the entries its header counts, is refused.
+namespace {
+constexpr uint32_t kMaxRgbTemperatures = (40000 / 100) - (1000 / 100); // SkyNode.h:163
+constexpr size_t kStarHeaderBytes = 28, kStarEntryBytes = 32;          // SkyNode.h:20-44: seven int32; float, double, double, char[2], int16, float, float packed
+
+uint32_t saturating_u32(float x)
+{
+    if (!(x > 0.0f)) return 0u; // NaN, zero and the negatives
+    if (x >= 4294967296.0f) return 4294967295u;
+    return (uint32_t)x;
+}
+
+// MorganKeenanToTemperature (:836-861)
+uint32_t morgan_keenan_temperature(uint8_t spectralType, uint8_t subType)
+{
+    static const float ranges[25][2] = {
+        { 7300, 10000 }, { 10000, 30000 }, { 2400, 3200 }, { 100000, 1000000 }, { 0, 0 }, { 6000, 7300 }, { 5300, 6000 }, { 0, 0 }, { 0, 0 },
+        { 0, 0 }, { 3800, 5300 }, { 1300, 2100 }, { 2500, 3800 }, { 0, 0 }, { 30000, 40000 }, { 0, 0 }, { 0, 0 }, { 0, 0 }, { 2400, 3500 }, { 600, 1300 },
+        { 0, 0 }, { 0, 0 }, { 25000, 40000 }, { 0, 0 }, { 0, 600 } };
+    static const float none[2] = { 0, 0 };
+    const float* range = spectralType >= 'A' && spectralType <= 'Y' ? ranges[spectralType - 'A'] : none;
+    const uint32_t rangeStep = saturating_u32((range[1] - range[0]) / 9);
+    const uint32_t subIndex = (uint32_t)'9' - (uint32_t)(int32_t)(int8_t)subType; // char is signed where the reference is built
+    return saturating_u32(range[0] + (float)(subIndex * rangeStep));
+}
+
+// TemperatureToColor (:863-869): the row of the 391-entry table
+uint32_t temperature_row(uint32_t temperature)
+{
+    const int32_t index = (int32_t)((temperature / 100u) - 10u);
+    return (uint32_t)std::min(std::max(index, 0), (int32_t)kMaxRgbTemperatures);
+}
+} // namespace
+
+extern "C" {
+
+int sailor_host_sky_star_color_table(const float* rows, uint32_t rowCount, float* outTable)
+{
+    if ((rowCount && !rows) || !outTable) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    std::memset(outTable, 0, sizeof(float) * 3 * (kMaxRgbTemperatures + 1)); // s_rgbTemperatures is a static: zero-initialised
+    for (uint32_t i = 0; i < rowCount; i++) {
+        const float* line = rows + 11 * (size_t)i;
+        const uint32_t index = std::min(saturating_u32((line[0] / 100.0f) - 10.0f), kMaxRgbTemperatures); // :51-52
+        for (int c = 0; c < 3; c++) outTable[3 * index + c] = line[5 + c];                                 // :55-57
+    }
+    return SAILOR_HIP_OK;
+}
+
+int sailor_host_sky_star_mesh(const uint8_t* catalogue, size_t bytes, const float* table, float* outPositions, float* outColors, uint32_t capacity,
+                              uint32_t* outCount)
+{
+    if (!catalogue || !table || !outCount || bytes < kStarHeaderBytes) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    int32_t starCount;
+    std::memcpy(&starCount, catalogue + 8, 4);                                   // m_starCount
+    const uint64_t count = (uint64_t)std::llabs((long long)starCount);           // :66 abs(header->m_starCount)
+    if (count > (bytes - kStarHeaderBytes) / kStarEntryBytes) return SAILOR_HIP_ERR_INVALID_ARGUMENT; // a truncated catalogue
+    *outCount = (uint32_t)count;
+    if (count > capacity) return SAILOR_HIP_ERR_INVALID_ARGUMENT;                // (outCount says how much room the mesh needs)
+    if (count && (!outPositions || !outColors)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    for (uint64_t i = 0; i < count; i++) {
+        const uint8_t* e = catalogue + kStarHeaderBytes + kStarEntryBytes * i;
+        double sra0, sdec0;
+        int16_t mag;
+        std::memcpy(&sra0, e + 4, 8); std::memcpy(&sdec0, e + 12, 8); std::memcpy(&mag, e + 22, 2);
+        const float ra = (float)sra0, dec = (float)sdec0;                        // :76
+        const float cosd = cosf(dec);                                            // Utils.cpp:454-464, radialDistance = 1
+        float p[3] = { (1.0f * sinf(ra)) * cosd, (1.0f * cosf(ra)) * cosd, 1.0f * sinf(dec) };
+        const float divisor = ((float)mag / 100.0f) + 0.4f;                      // :77; a negative divisor mirrors the star, as written
+        for (int c = 0; c < 3; c++) outPositions[3 * i + c] = (p[c] / divisor) * 5000.0f; // :79-81
+        const float* rgb = table + 3 * (size_t)temperature_row(morgan_keenan_temperature(e[20], e[21])); // :83
+        const float color[4] = { rgb[0], rgb[1], rgb[2], 1.0f };
+        for (int c = 0; c < 4; c++) outColors[4 * i + c] = powf(color[c], 1 / 2.2f); // :85-88
+    }
+    return SAILOR_HIP_OK;
+}
+
+int sailor_host_sky_stars_model(const float* cameraPosition3, float* outMat4)
+{
+    if (!cameraPosition3 || !outMat4) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    // SkyNode.cpp:208-209: glm::angleAxis(angle, axis) = (axis * sin(angle / 2), cos(angle / 2)); Math::vec3_Backward = (0, 0, 1), vec3_Right = (1, 0, 0)
+    struct Q { float w, x, y, z; };
+    auto angleAxis = [](float angle, float ax, float ay, float az) { const float s = sinf(angle * 0.5f); return Q { cosf(angle * 0.5f), ax * s, ay * s, az * s }; };
+    auto qmul = [](const Q& p, const Q& q) { // glm: operator*(qua, qua)
+        return Q { p.w * q.w - p.x * q.x - p.y * q.y - p.z * q.z, p.w * q.x + p.x * q.w + p.y * q.z - p.z * q.y,
+                   p.w * q.y + p.y * q.w + p.z * q.x - p.x * q.z, p.w * q.z + p.z * q.w + p.x * q.y - p.y * q.x };
+    };
+    const Q rz = angleAxis(0.01118f, 0.0f, 0.0f, 1.0f);
+    const Q q = qmul(qmul(rz, angleAxis(-0.00972f, 1.0f, 0.0f, 0.0f)), rz);
+    // :211 toMat4(precession) and :698 translate(mat4(1), cameraPosition) * it
+    store(mul(translation(cameraPosition3), mat4_cast(q.x, q.y, q.z, q.w)), outMat4);
     return SAILOR_HIP_OK;
 }
 

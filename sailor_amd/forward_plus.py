@@ -439,6 +439,46 @@ def sky_blit_clouds(ctx: "HipContext", clouds: torch.Tensor, target: torch.Tenso
     return target
 
 
+def sky_sun_shafts(ctx: "HipContext", frame: UboFrameData, params, clouds: torch.Tensor, target: torch.Tensor, width: int, height: int,
+                   band: Band | None = None) -> torch.Tensor:
+    """"Sun Shafts" (SkyNode.cpp:733-739): SunShafts.shader blended under the Multiply state over the rows of `band` of the target, in place; returns `target`"""
+    band = band or host.band_whole_frame(width, height)
+    assert clouds.dtype == torch.float32 and clouds.is_contiguous() and clouds.dim() == 3 and clouds.shape[2] == 4, (clouds.dtype, tuple(clouds.shape))
+    assert target.dtype == torch.float32 and target.is_contiguous() and tuple(target.shape) == (band.fbRowCount, width, 4), tuple(target.shape)
+    _lib.check(ctx._lib.sailor_hip_sky_sun_shafts(ctx.handle, C.byref(frame), C.byref(params), _ptr(clouds), clouds.shape[1], clouds.shape[0], _ptr(target),
+                                                  width, height, C.byref(band)), "sailor_hip_sky_sun_shafts", ctx.handle)
+    return target
+
+
+class SkyStars:
+    """The star draw of the Sky node (SkyNode.cpp:694-720).  Holds the mesh of host.sky_star_mesh on the device and the workspace the draw needs; draw()
+    binds that workspace to the context and records the two launches."""
+
+    def __init__(self, ctx: "HipContext", positions, colors):
+        positions, colors = np.ascontiguousarray(positions, np.float32).reshape(-1, 3), np.ascontiguousarray(colors, np.float32).reshape(-1, 4)
+        assert positions.shape[0] == colors.shape[0], (positions.shape, colors.shape)
+        self.ctx, self.count = ctx, positions.shape[0]
+        # (an empty tensor has no storage: a count of 0 keeps one element so that the pointers are real)
+        self.positions = torch.from_numpy(np.concatenate([positions.reshape(-1), np.zeros(3, np.float32)])).to(ctx.device)
+        self.colors = torch.from_numpy(np.concatenate([colors.reshape(-1), np.zeros(4, np.float32)])).to(ctx.device)
+        self.workspace = torch.empty(max(16, int(ctx._lib.sailor_hip_sky_stars_workspace_bytes(self.count))), dtype=torch.uint8, device=ctx.device)
+
+    def draw(self, frame: UboFrameData, model, clouds: torch.Tensor | None, target: torch.Tensor, width: int, height: int, band: Band | None = None) -> torch.Tensor:
+        """adds the stars to the rows of `band` of the target, in place; `clouds` = None is the cleared clouds target; returns `target`"""
+        ctx = self.ctx
+        band = band or host.band_whole_frame(width, height)
+        assert target.dtype == torch.float32 and target.is_contiguous() and tuple(target.shape) == (band.fbRowCount, width, 4), tuple(target.shape)
+        if clouds is not None:
+            assert clouds.dtype == torch.float32 and clouds.is_contiguous() and clouds.dim() == 3 and clouds.shape[2] == 4, (clouds.dtype, tuple(clouds.shape))
+        cw, ch = (0, 0) if clouds is None else (clouds.shape[1], clouds.shape[0])
+        model = np.ascontiguousarray(model, dtype=np.float32).reshape(16)
+        _lib.check(ctx._lib.sailor_hip_sky_stars_bind_workspace(ctx.handle, _ptr(self.workspace), self.workspace.numel()), "sailor_hip_sky_stars_bind_workspace",
+                   ctx.handle)
+        _lib.check(ctx._lib.sailor_hip_sky_stars(ctx.handle, C.byref(frame), model.ctypes.data_as(C.POINTER(C.c_float)), _ptr(self.positions), _ptr(self.colors),
+                                                 self.count, _ptr(clouds), cw, ch, _ptr(target), width, height, C.byref(band)), "sailor_hip_sky_stars", ctx.handle)
+        return target
+
+
 def sky_env_face(ctx: "HipContext", camera_position, params, chain: torch.Tensor, size: int, face: int) -> torch.Tensor:
     """one face of g_skyCubemap's level 0 (SkyNode.cpp:764-797), written into the flat RGBA32F chain"""
     cam = np.ascontiguousarray(camera_position, dtype=np.float32).reshape(-1)[:3].copy()

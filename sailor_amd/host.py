@@ -148,6 +148,32 @@ def sky_sun_color(sun_direction) -> np.ndarray:
     return out
 
 
+def sky_star_color_table(rows) -> np.ndarray:
+    """SkyNode.cpp:47-58: the `colors` rows of StarsColor.yaml ([n, 11] floats) -> the node's temperature table, float32 [391, 3]"""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    assert rows.ndim == 2 and rows.shape[1] == 11, rows.shape
+    out = np.empty((_lib.SKY_STAR_TABLE_ROWS, 3), np.float32)
+    _lib.check(_lib.load().sailor_host_sky_star_color_table(_fp(rows), rows.shape[0], _fp(out)), "sailor_host_sky_star_color_table")
+    return out
+
+
+def sky_star_mesh(catalogue: bytes, table):
+    """SkyNode.cpp:61-91: the BSC5 bytes and the temperature table -> (positions float32 [n, 3], colours float32 [n, 4]); a truncated catalogue raises"""
+    table = _f32(table, _lib.SKY_STAR_TABLE_ROWS * 3)
+    data = bytes(catalogue)
+    capacity = max(0, len(data) - 28) // 32
+    pos, col, count = np.empty((capacity, 3), np.float32), np.empty((capacity, 4), np.float32), C.c_uint32()
+    _lib.check(_lib.load().sailor_host_sky_star_mesh(data, len(data), _fp(table), _fp(pos), _fp(col), capacity, C.byref(count)), "sailor_host_sky_star_mesh")
+    return pos[:count.value].copy(), col[:count.value].copy()
+
+
+def sky_stars_model(camera_position) -> np.ndarray:
+    """SkyNode.cpp:208-211, :698: translate(cameraPosition) * toMat4(precession), column-major float32[16]"""
+    cam, out = np.ascontiguousarray(camera_position, dtype=np.float32).reshape(-1)[:3].copy(), np.empty(16, np.float32)
+    _lib.check(_lib.load().sailor_host_sky_stars_model(_fp(cam), _fp(out)), "sailor_host_sky_stars_model")
+    return out
+
+
 def sky_face_matrices(face: int):
     """SkyNode.cpp:487-508: (view, projection, invProjection) of cube face 0..5, column-major float32[16] each"""
     v, p, ip = (np.empty(16, np.float32) for _ in range(3))

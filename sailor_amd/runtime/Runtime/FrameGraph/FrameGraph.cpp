@@ -626,6 +626,7 @@ void SkyNode::Process(RHIFrameGraphPtr frameGraph, RHICommandListPtr transferCom
         m_pComposeMaterial = driver->CreateMaterial(m_pComposeShader);
         m_pCloudsMaterial = driver->CreateMaterial(m_pCloudsShader);
         m_pSunShaftsMaterial = driver->CreateMaterial(m_pSunShaftsShader);
+        m_pSunShaftsMaterial->m_blendMode = EBlendMode::Multiply; // renderStateMultiply (:453-454)
     }
     if (HasCloudTextures() && m_bCloudTexturesChanged) { // (:431-433) every time the caller publishes textures: the set must not keep the earlier, caller-owned ones
         driver->AddSamplerToShaderBindings(m_pShaderBindings, "cloudsMapSampler", m_pCloudsMapTexture, 3);
@@ -656,7 +657,10 @@ void SkyNode::Process(RHIFrameGraphPtr frameGraph, RHICommandListPtr transferCom
             commands->UpdateShaderBinding(transferCommandList, m_pEnvCubemapBindings[face]->GetOrAddShaderBinding("frameData"), &frameData, sizeof(frameData));
         }
     }
-    if (!m_pStarsMaterial) m_pStarsMaterial = driver->CreateMaterial(m_pStarsShader); // (:517-522)
+    if (!m_pStarsMaterial) { // (:517-522)
+        m_pStarsMaterial = driver->CreateMaterial(m_pStarsShader);
+        m_pStarsMaterial->m_blendMode = EBlendMode::Additive; // RenderState { .., EBlendMode::Additive, EFillMode::Point, .. } (:520)
+    }
 
     auto resolved = [&](const char* name) -> RHITexturePtr { // BaseFrameGraphNode::GetResolvedAttachment
         if (auto t = GetRHIResource(name).DynamicCast<RHITexture>()) return t;
@@ -688,10 +692,25 @@ void SkyNode::Process(RHIFrameGraphPtr frameGraph, RHICommandListPtr transferCom
     }
     fullScreenDraw("Sun", m_pSunTexture, m_pSunMaterial, { sceneView.m_frameBindings, m_pShaderBindings });     // (:611-642)
     fullScreenDraw("Compose", target, m_pComposeMaterial, { sceneView.m_frameBindings, m_pShaderBindings });    // (:644-680)
-    // (:682-747) "Stars & Clouds": the star points and the sun-shaft multiply -- no entry point, nothing recorded.  The alpha-blended clouds blit is drawn
-    // when the clouds were: over the cleared plane (alpha 0) the reference's blit leaves every colour and turns alpha a into 0 - a, which for the target's
-    // alpha of +0 is +0 again -- leaving it out keeps the cloudless frame's record what it was
-    if (m_pStarsShader->IsReady()) fullScreenDraw("Stars", target, m_pStarsMaterial, { sceneView.m_frameBindings, m_pShaderBindings });
+    // (:682-747) "Stars & Clouds", three draws into the target: the star points, the clouds blit, the sun shafts.  The first and the last are recorded for a
+    // driver that opted in to their shaders, the stars once the mesh has been published (the reference waits for its mesh task, :395-417).  The alpha-blended
+    // clouds blit is drawn when the clouds were: over the cleared plane (alpha 0) the reference's blit leaves every colour and turns alpha a into 0 - a,
+    // which for the target's alpha of +0 is +0 again -- leaving it out keeps the cloudless frame's record what it was
+    if (m_pStarsShader->IsReady() && HasStars()) {
+        commands->BeginDebugRegion(commandList, "Stars");
+        commands->BindVertexBuffer(commandList, m_starsVertexBuffer, 0); // (:694-695)
+        commands->BindIndexBuffer(commandList, m_starsIndexBuffer, 0);
+        float model[16];                                                  // (:697-698) translate(mat4(1), cameraPosition) * m_starsModelView, SetLocation (:690) included
+        sailor_host_sky_stars_model(&sceneView.m_camera.m_world[12], model);
+        commands->ImageMemoryBarrier(commandList, target, EImageLayout::ColorAttachmentOptimal); // (:701)
+        commands->BeginRenderPass(commandList, TVector<RHITexturePtr> { target }, RHITexturePtr());  // (:704-712; no depth test: the depth attachment is not needed)
+        commands->BindMaterial(commandList, m_pStarsMaterial);                                        // (:714-716)
+        commands->BindShaderBindings(commandList, m_pStarsMaterial, { sceneView.m_frameBindings, m_pShaderBindings });
+        commands->PushConstants(commandList, m_pStarsMaterial, sizeof(model), model);
+        commands->DrawIndexed(commandList, m_starsCount, 1u, 0u, 0u, 0u);                             // (:720)
+        commands->EndRenderPass(commandList);
+        commands->EndDebugRegion(commandList);
+    }
     if (bClouds && m_pBlitShader->IsReady()) fullScreenDraw("Blit Clouds", target, m_pBlitCloudsMaterial, { sceneView.m_frameBindings, m_pBlitCloudsBindings });
     if (m_pSunShaftsShader->IsReady()) fullScreenDraw("Sun Shafts", target, m_pSunShaftsMaterial, { sceneView.m_frameBindings, m_pShaderBindings });
 

@@ -159,8 +159,10 @@ protected:
 // The atmosphere, the sun disk and g_skyCubemap: Runtime/FrameGraph/SkyNode.h.  Resources (DefaultRenderer.renderer:145-149): "color" = the Sky target,
 // "linearDepth".  Drawn: Sky.shader {FILL}, {SUN}, {COMPOSE} every frame and {} into one face of g_skyCubemap per frame while dirty; with the cloud
 // textures published (SetCloudTextures) and m_cloudsDensity > 0 also Sky.shader {CLOUDS} and the alpha-blended Blit.shader draw "Blit Clouds", otherwise
-// the m_cloudsDensity == 0 branch (SkyNode.cpp:604-609).  Created and never recorded (the backend has no entry point: IsReady() is false):
-// Stars.shader and SunShafts.shader -- the node has no star mesh, and it neither loads CloudsMap.png nor generates the noise volumes.
+// the m_cloudsDensity == 0 branch (SkyNode.cpp:604-609).  For a driver that opted in (HipGraphicsDriver::EnableShader) also the star points in front of
+// the clouds blit -- once the caller has published the star mesh (SetStars) -- and the sun-shaft draw behind it (SkyNode.cpp:692-747); without the opt-in
+// Stars.shader and SunShafts.shader are created "not ready" and never recorded.  The node neither parses the catalogue (sailor_host_sky_star_mesh does),
+// nor loads CloudsMap.png, nor generates the noise volumes.
 class SkyNode : public TFrameGraphNode<SkyNode> {
 public:
     static constexpr uint32_t EnvCubemapSize = 256u;      // SkyNode.h:13
@@ -189,6 +191,14 @@ public:
         m_bCloudTexturesChanged = true; // Process re-points bindings 3, 4 and 5 at them
     }
     bool HasCloudTextures() const { return m_pCloudsMapTexture && m_pCloudsNoiseLowTexture && m_pCloudsNoiseHighTexture; }
+    // The star mesh (m_starsMesh, SkyNode.cpp:61-108), published by the caller like the cloud textures: until it has been, the star draw is left out and the
+    // node otherwise works.  vertexBuffer: the VertexP3C4 mesh de-interleaved -- count x 3 floats of positions, then, at the next 16-byte boundary, count x 4
+    // floats of colours (sailor_host_sky_star_mesh's two outputs); indexBuffer: count uint32, index i = i (:90)
+    void SetStars(RHI::RHIBufferPtr vertexBuffer, RHI::RHIBufferPtr indexBuffer, uint32_t count)
+    {
+        m_starsVertexBuffer = std::move(vertexBuffer); m_starsIndexBuffer = std::move(indexBuffer); m_starsCount = count;
+    }
+    bool HasStars() const { return m_starsVertexBuffer && m_starsIndexBuffer; }
 
 protected:
     static const char* m_name;
@@ -198,6 +208,8 @@ protected:
         m_pBlitCloudsMaterial;
     RHI::RHIShaderBindingSetPtr m_pShaderBindings, m_pBlitCloudsBindings, m_pEnvCubemapBindings[6];
     RHI::RHITexturePtr m_pSkyTexture, m_pSunTexture, m_pCloudsTexture, m_pCloudsMapTexture, m_pCloudsNoiseLowTexture, m_pCloudsNoiseHighTexture;
+    RHI::RHIBufferPtr m_starsVertexBuffer, m_starsIndexBuffer; // m_starsMesh (SkyNode.h:151)
+    uint32_t m_starsCount = 0;
     uint32_t m_ditherPatternIndex = 0;
     uint32_t m_updateEnvCubemapPattern = 0; // SkyNode.h:173
     bool m_bIsDirty = true;                 // SkyNode.h:174

@@ -101,12 +101,16 @@ RHIShaderPtr HipGraphicsDriver::CreateShader(const std::string& assetPath, const
     if (assetPath == "Shaders/Debug.shader")
         shader->m_bIsReady = IsShaderEnabled(assetPath) &&
                              (defines.empty() || (defines.size() == 1 && (defines[0] == "AO" || defines[0] == "LIGHT_TILES" || defines[0] == "CASCADES")));
+    // The first and the last draw of SkyNode's "Stars & Clouds" (SkyNode.cpp:692-747), likewise opt-in: the Sky and clouds tests record a frame without them
+    if (assetPath == "Shaders/Stars.shader" || assetPath == "Shaders/SunShafts.shader") shader->m_bIsReady = IsShaderEnabled(assetPath);
     return shader;
 }
 
 bool HipGraphicsDriver::EnableShader(const std::string& assetPath)
 {
-    if (assetPath != "Shaders/MotionBlur.shader" && assetPath != "Shaders/Debug.shader") return false;
+    if (assetPath != "Shaders/MotionBlur.shader" && assetPath != "Shaders/Debug.shader" && assetPath != "Shaders/Stars.shader" &&
+        assetPath != "Shaders/SunShafts.shader")
+        return false;
     m_enabledShaders.insert(assetPath);
     return true;
 }
@@ -855,13 +859,22 @@ void HipGraphicsDriver::DrawIndexed(RHICommandListPtr cmd, uint32_t indexCount, 
     // Sky.shader's permutation: 0 {FILL}, 1 {}, 2 {SUN}, 3 {COMPOSE}, 4 {CLOUDS}, -1 anything else (CreateShader left those "not ready")
     const int sky = (!shader || !shader->IsReady()) ? -1
                     : (shader->m_defines.empty() ? 1 : (shader->HasDefine("FILL") ? 0 : (shader->HasDefine("SUN") ? 2 : (shader->HasDefine("CLOUDS") ? 4 : 3))));
-    const bool alphaBlending = cmd->m_boundMaterial && cmd->m_boundMaterial->m_blendMode == EBlendMode::AlphaBlending;
+    const EBlendMode blend = cmd->m_boundMaterial ? cmd->m_boundMaterial->m_blendMode : EBlendMode::None;
+    const bool alphaBlending = blend == EBlendMode::AlphaBlending;
+    // the star mesh and its push constant (the model matrix), captured at record time like the caster draws'
+    RHIBufferPtr starVertices = cmd->m_vertexBuffer, starIndices = cmd->m_indexBuffer;
+    TVector<uint8_t> pushConstants = cmd->m_pushConstants;
     // the frame's tail: drawn only with a shader CreateShader marked ready (the opt-in); Debug.shader's permutation: SAILOR_DEBUG_VIEW_*, -1 = none
     const bool tail = shader && shader->IsReady();
     const int debugMode = !tail ? -1
                           : (shader->m_defines.empty() ? SAILOR_DEBUG_VIEW_SCENE
                              : (shader->HasDefine("AO") ? SAILOR_DEBUG_VIEW_AO : (shader->HasDefine("LIGHT_TILES") ? SAILOR_DEBUG_VIEW_LIGHT_TILES : SAILOR_DEBUG_VIEW_CASCADES)));
-    cmd->m_hip.m_commands.push_back([this, name, bindings, target, fullScreenQuad, evsm, vertical, horizontal, tonemapFlags, sky, alphaBlending, tail, debugMode]() {
+    cmd->m_hip.m_commands.push_back([this, name, bindings, target, fullScreenQuad, evsm, vertical, horizontal, tonemapFlags, sky, alphaBlending, tail, debugMode, blend,
+                                     starVertices, starIndices, pushConstants, indexCount, instanceCount, firstIndex, vertexOffset]() {
+        // the point list of the star mesh: DrawIndexed(count, 1, 0, 0, 0) (SkyNode.cpp:720), not the quad
+        if (name == "Shaders/Stars.shader" && tail && instanceCount == 1 && firstIndex == 0 && vertexOffset == 0)
+            return RecordStars(bindings, target, starVertices, starIndices, indexCount, pushConstants, blend);
+        if (fullScreenQuad && name == "Shaders/SunShafts.shader" && tail) return RecordSunShafts(bindings, target, blend);
         if (fullScreenQuad && name == "Shaders/Sky.shader" && sky == 4) return RecordSkyClouds(bindings, target);
         if (fullScreenQuad && name == "Shaders/Sky.shader" && sky >= 0) return RecordSky(bindings, target, sky);
         if (fullScreenQuad && name == "Shaders/Blit.shader" && alphaBlending) return RecordBlitAlphaBlended(bindings, target);
@@ -1093,6 +1106,54 @@ int HipGraphicsDriver::RecordBlitAlphaBlended(const TVector<RHIShaderBindingSetP
     BeforeBufferWrite(target->m_buffer->m_hip.m_devicePtr);
     return sailor_hip_sky_blit_clouds(m_ctx, (const float*)texels_of(src), src->GetExtent().x, src->GetExtent().y, (float*)texels_of(target), target->GetExtent().x,
                                       target->GetExtent().y, &whole);
+}
+
+// The star points (SkyNode.cpp:694-720): Stars.shader drawn as a point list over the bound attachment under EBlendMode::Additive.  Set 0 `frameData`, set 1
+// binding 6 `cloudsSampler` (Stars.shader:97; not bound = the cleared plane), the push constant `model` (:37-40).  The vertex buffer is the de-interleaved
+// VertexP3C4 mesh SkyNode::SetStars documents: count x 3 floats of positions, then, at the next 16-byte boundary, count x 4 floats of colours; the index
+// buffer holds count identity indices (SkyNode.cpp:90) and is only checked for its size.  The draw's workspace belongs to the driver.
+int HipGraphicsDriver::RecordStars(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& target, const RHIBufferPtr& vertices, const RHIBufferPtr& indices,
+                                   uint32_t count, const TVector<uint8_t>& pc, EBlendMode blend)
+{
+    if (bindings.size() != 2 || !target || !target->m_buffer || target->m_format != EFormat::R32G32B32A32_SFLOAT) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    SailorUboFrameData frame;
+    if (!host_copy_of(bindings[0], "frameData", frame) || !vertices || !indices || pc.size() < 64 || count > 65536u) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (blend != EBlendMode::Additive) return SAILOR_HIP_ERR_UNSUPPORTED;
+    const size_t colorsAt = ((size_t)count * 12 + 15) / 16 * 16;
+    if (vertices->m_size < colorsAt + (size_t)count * 16 || indices->m_size < (size_t)count * 4) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    float model[16];
+    memcpy(model, pc.data(), 64);
+    auto clouds = bound_texture(bindings[1], "cloudsSampler", EFormat::R32G32B32A32_SFLOAT);
+    const size_t need = sailor_hip_sky_stars_workspace_bytes((int32_t)count);
+    if (need && (!m_starsWorkspace || m_starsWorkspace->m_size < need)) {
+        m_starsWorkspace = CreateBuffer(need);
+        if (!m_starsWorkspace) return SAILOR_HIP_ERR_OUT_OF_MEMORY;
+    }
+    if (m_starsWorkspace) sailor_hip_sky_stars_bind_workspace(m_ctx, m_starsWorkspace->m_hip.m_devicePtr, m_starsWorkspace->m_size);
+    SailorBand whole;
+    if (sailor_hip_band_whole_frame(target->GetExtent().x, target->GetExtent().y, &whole) != SAILOR_HIP_OK) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    BeforeBufferWrite(target->m_buffer->m_hip.m_devicePtr);
+    const char* mesh = (const char*)vertices->m_hip.m_devicePtr;
+    return sailor_hip_sky_stars(m_ctx, &frame, model, (const float*)mesh, (const float*)(mesh + colorsAt), (int32_t)count, clouds ? (const float*)texels_of(clouds) : nullptr,
+                                clouds ? clouds->GetExtent().x : 0, clouds ? clouds->GetExtent().y : 0, (float*)texels_of(target), target->GetExtent().x,
+                                target->GetExtent().y, &whole);
+}
+
+// "Sun Shafts" (SkyNode.cpp:733-739): SunShafts.shader drawn over the bound attachment under EBlendMode::Multiply.  Set 0 `frameData`, set 1 binding 0 `data`,
+// binding 6 `cloudsSampler` (SunShafts.shader:50-72).  A `cloudsSampler` that resolved to nothing is an invalid argument: the pass has nothing to walk through.
+int HipGraphicsDriver::RecordSunShafts(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& target, EBlendMode blend)
+{
+    if (bindings.size() < 2 || !target || !target->m_buffer || target->m_format != EFormat::R32G32B32A32_SFLOAT) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    auto clouds = bound_texture(bindings[1], "cloudsSampler", EFormat::R32G32B32A32_SFLOAT);
+    SailorUboFrameData frame;
+    SailorSkyParams params;
+    if (!clouds || !host_copy_of(bindings[0], "frameData", frame) || !host_copy_of(bindings[1], "data", params)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (blend != EBlendMode::Multiply) return SAILOR_HIP_ERR_UNSUPPORTED;
+    SailorBand whole;
+    if (sailor_hip_band_whole_frame(target->GetExtent().x, target->GetExtent().y, &whole) != SAILOR_HIP_OK) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    BeforeBufferWrite(target->m_buffer->m_hip.m_devicePtr);
+    return sailor_hip_sky_sun_shafts(m_ctx, &frame, &params, (const float*)texels_of(clouds), clouds->GetExtent().x, clouds->GetExtent().y, (float*)texels_of(target),
+                                     target->GetExtent().x, target->GetExtent().y, &whole);
 }
 
 int HipGraphicsDriver::RecordEvsmBlur(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& target, bool vertical)

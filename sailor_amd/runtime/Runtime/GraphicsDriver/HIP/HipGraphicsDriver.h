@@ -24,7 +24,11 @@
 //   "Shaders/Sky.shader" by define set: {FILL} -> sailor_hip_sky_fill, {} (into a cube face view) -> sailor_hip_sky_env_face, {SUN} -> sailor_hip_sky_sun
 //                                           (or sailor_hip_sky_sun_clouds once the cloud march has been recorded into `cloudsSampler`),
 //                                           {COMPOSE} -> sailor_hip_sky_compose, {CLOUDS} -> sailor_hip_sky_clouds (binding contract: Sky.shader:104-153);
-//                                           every other permutation, "Shaders/Stars.shader" and "Shaders/SunShafts.shader" are created "not ready", never drawn
+//                                           every other permutation is created "not ready", never drawn
+//   "Shaders/Stars.shader" of a material with EBlendMode::Additive, drawn as DrawIndexed(count, 1, 0, 0, 0) over the star mesh -> sailor_hip_sky_stars
+//                                           (binding contract: Stars.shader:13-40, :92-97: set 0 `frameData`, set 1 `cloudsSampler`, push constant `model`)
+//   "Shaders/SunShafts.shader" of a material with EBlendMode::Multiply -> sailor_hip_sky_sun_shafts (binding contract: SunShafts.shader:26-72: set 0
+//                                           `frameData`, set 1 `data`, `cloudsSampler`) -- both only for a driver that opted in with EnableShader
 //   "Shaders/MotionBlur.shader"          -> sailor_hip_motion_blur       (binding contract: MotionBlur.shader:26-58: set 0 `frameData` / `previousFrameData`,
 //                                           set 1 `data`, `depthSampler`, `colorSampler`) -- only for a driver that opted in with EnableShader
 //   "Shaders/Debug.shader" {} | {AO} | {LIGHT_TILES} | {CASCADES} -> sailor_hip_debug_view (binding contract: Debug.shader:81-113: set 1 `ldrSceneSampler`,
@@ -54,7 +58,9 @@ public:
     // the prepared views of a `light` SSBO: created with it, derived for every slot on (re-)creation (HipGraphicsDriver.cpp)
     bool EnsurePreparedLights(RHI::RHIShaderBindingPtr binding, bool zeroRecords);
 
-    // Opt this driver in to a shader that has an entry point but is not routed by default: "Shaders/MotionBlur.shader", "Shaders/Debug.shader".  CreateShader
+    // Opt this driver in to a shader that has an entry point but is not routed by default: "Shaders/MotionBlur.shader", "Shaders/Debug.shader" (the frame's
+    // tail), "Shaders/Stars.shader", "Shaders/SunShafts.shader" (the Sky node's star points and sun shafts: the older Sky and clouds tests record a frame
+    // without them).  CreateShader
     // marks them ready only afterwards (Debug.shader only under a define set that has an entry point); without the opt-in it behaves as it always did.  As with
     // the Bloom node class, the opt-in exists only because older tests of this mirror use MotionBlur.shader as their example of a shader WITHOUT an entry point
     // (a PostProcess entry that must be created and record nothing); in the engine the backend would simply route both.  false for any other path.
@@ -147,6 +153,9 @@ private:
     int RecordSky(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target, int permutation);
     int RecordSkyClouds(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target);
     int RecordBlitAlphaBlended(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target);
+    int RecordStars(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target, const RHI::RHIBufferPtr& vertices,
+                    const RHI::RHIBufferPtr& indices, uint32_t count, const TVector<uint8_t>& pc, RHI::EBlendMode blend);
+    int RecordSunShafts(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target, RHI::EBlendMode blend);
     int RecordBloomDownscale(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const TVector<uint8_t>& pc);
     int RecordBloomUpscale(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const TVector<uint8_t>& pc);
 
@@ -159,6 +168,7 @@ private:
     // march, SkyNode.cpp:611-642) goes through sailor_hip_sky_sun_clouds then, through sailor_hip_sky_sun otherwise.  Reset by every write (BeforeBufferWrite)
     const void* m_marchedClouds = nullptr;
     RHI::RHIBufferPtr m_cullWorkspace;
+    RHI::RHIBufferPtr m_starsWorkspace; // the star draw's per-star pixels and fragments (sailor_hip_sky_stars_workspace_bytes), grown when a larger mesh is drawn
     RHI::RHIBufferPtr m_meshCullWorkspace;
     int32_t m_cullW = 0, m_cullH = 0, m_cullLights = 0; // geometry of the last light cull: locates its shading-order hint in the workspace
     bool m_cullOrderValid = false;

@@ -10,6 +10,7 @@
 #include "Runtime/AssetRegistry/FrameGraph/FrameGraphParser.h"
 #include "Runtime/AssetRegistry/World/WorldPrefabImporter.h"
 #include <cstdio>
+#include <vector>
 
 using namespace Sailor;
 using namespace Sailor::RHI;
@@ -67,7 +68,8 @@ RT_API int sailor_rt_enable_node(SailorRuntime* rt, const char* name)
 }
 
 // Opt this runtime's driver in to a shader that has an entry point but is not routed by default: "Shaders/MotionBlur.shader" or "Shaders/Debug.shader" (the
-// frame's tail).  PostProcess nodes created afterwards find the shader ready and draw with it; a runtime that did not opt in keeps creating it "not ready",
+// frame's tail), "Shaders/Stars.shader" or "Shaders/SunShafts.shader" (the Sky node's star points and sun shafts; before the first frame, when the node
+// creates its shaders).  PostProcess nodes created afterwards find the shader ready and draw with it; a runtime that did not opt in keeps creating it "not ready",
 // so its nodes record nothing, and sailor_rt_enable_node("MotionBlur") keeps failing: there is no such node class.  In the engine the backend would simply route
 // both; as with Bloom, the opt-in exists only because this mirror's older tests use MotionBlur.shader as their example of a shader without an entry point.
 // 0, or -1 for any other path or a null runtime.
@@ -454,6 +456,23 @@ RT_API int sailor_rt_sky_set_cloud_textures(SailorRuntime* rt, void* weather, in
     low->m_depth = lowSize; low->m_buffer->m_size = (size_t)lowSize * lowSize * lowSize;
     high->m_depth = highSize; high->m_buffer->m_size = (size_t)highSize * highSize * highSize;
     sky->SetCloudTextures(map, low, high);
+    return 0;
+}
+
+// The star mesh of the Sky node, which the reference parses from Content/BSC5 itself (SkyNode.cpp:31-113): caller-owned device memory here --
+// `vertices` = count x 3 floats of positions and, at the next 16-byte boundary, count x 4 floats of colours (the outputs of sailor_host_sky_star_mesh).  The
+// index buffer (index i = i, :90) is created here.  With the mesh published and "Shaders/Stars.shader" enabled the node draws the star points.
+RT_API int sailor_rt_sky_set_stars(SailorRuntime* rt, void* vertices, int count)
+{
+    auto* hip = static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver());
+    auto* sky = sky_node(rt);
+    if (!sky || !hip || !vertices || count <= 0 || count > 65536) return -1;
+    const size_t colorsAt = ((size_t)count * 12 + 15) / 16 * 16;
+    std::vector<uint32_t> identity((size_t)count);
+    for (int i = 0; i < count; i++) identity[(size_t)i] = (uint32_t)i;
+    auto indices = hip->CreateBuffer(identity.size() * 4);
+    if (!indices || sailor_hip_buffer_upload(hip->GetContext(), indices->m_hip.m_devicePtr, 0, identity.data(), identity.size() * 4) != SAILOR_HIP_OK) return -1;
+    sky->SetStars(hip->WrapBuffer(vertices, colorsAt + (size_t)count * 16), indices, (uint32_t)count);
     return 0;
 }
 

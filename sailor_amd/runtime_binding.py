@@ -48,6 +48,7 @@ def load() -> C.CDLL:
         rt.sailor_rt_sky_set_params.argtypes = [P, P, C.c_int]
         rt.sailor_rt_sky_state.argtypes = [P, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         rt.sailor_rt_sky_set_cloud_textures.argtypes = [P, P, C.c_int, C.c_int, P, C.c_int, P, C.c_int]
+        rt.sailor_rt_sky_set_stars.argtypes = [P, P, C.c_int]
         rt.sailor_rt_set_environment_map.argtypes = [P, P, C.c_int, C.c_int, C.c_int, C.c_int]
         rt.sailor_rt_sampler.restype = P
         rt.sailor_rt_sampler.argtypes = [P, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -194,6 +195,12 @@ class Runtime:
         return self.rt.sailor_rt_sky_set_cloud_textures(self.h, weather.data_ptr(), weather.shape[1], weather.shape[0], low.data_ptr(), low.shape[0], high.data_ptr(),
                                                         high.shape[0])
 
+    def sky_set_stars(self, vertices, count: int) -> int:
+        """publish the star mesh to the Sky node: `vertices` = star_vertices(positions, colours) on the device, caller-owned.  With it and
+        "Shaders/Stars.shader" enabled the node draws the star points.  -1 if the graph has no Sky node"""
+        assert vertices.is_contiguous() and vertices.element_size() == 4 and vertices.numel() >= (count * 3 + 3) // 4 * 4 + count * 4, (vertices.dtype, vertices.numel())
+        return self.rt.sailor_rt_sky_set_stars(self.h, vertices.data_ptr(), count)
+
     def sky_state(self):
         """(m_updateEnvCubemapPattern, m_bIsDirty) of the Sky node; raises if the graph has none"""
         pattern, dirty = C.c_int(0), C.c_int(0)
@@ -284,8 +291,9 @@ class Runtime:
             raise ValueError(f"no opt-in node class {name!r}")
 
     def enable_shader(self, path: str):
-        """opt this runtime in to a shader that has an entry point but is not routed by default ("Shaders/MotionBlur.shader", "Shaders/Debug.shader"):
-        PostProcess entries loaded afterwards draw with it"""
+        """opt this runtime in to a shader that has an entry point but is not routed by default ("Shaders/MotionBlur.shader", "Shaders/Debug.shader":
+        PostProcess entries loaded afterwards draw with it; "Shaders/Stars.shader", "Shaders/SunShafts.shader": the Sky node draws its star points and sun
+        shafts, when enabled before the first frame)"""
         if self.rt.sailor_rt_enable_shader(self.h, path.encode()) != 0:
             raise ValueError(f"no opt-in shader {path!r}")
 
@@ -356,3 +364,16 @@ class Runtime:
         n = C.c_size_t(0)
         p = self.rt.sailor_rt_buffer(self.h, name.encode(), C.byref(n))
         return p, n.value
+
+
+def star_vertices(positions, colors):
+    """the star mesh as the Sky node's vertex buffer: the VertexP3C4 mesh de-interleaved -- count x 3 floats of positions, then, at the next 16-byte
+    boundary, count x 4 floats of colours -> float32 [n]"""
+    import numpy as np
+    positions, colors = np.ascontiguousarray(positions, np.float32).reshape(-1, 3), np.ascontiguousarray(colors, np.float32).reshape(-1, 4)
+    count = positions.shape[0]
+    assert colors.shape[0] == count
+    out = np.zeros((count * 3 + 3) // 4 * 4 + count * 4, np.float32)
+    out[:count * 3] = positions.reshape(-1)
+    out[(count * 3 + 3) // 4 * 4:] = colors.reshape(-1)
+    return out
