@@ -137,6 +137,35 @@ DEBUG_VIEW_MODES = {"": DEBUG_VIEW_SCENE, "AO": DEBUG_VIEW_AO, "LIGHT_TILES": DE
 SHADOW_CASCADE_LEVELS = (0.05, 0.1, 0.333333, 0.5)  # SAILOR_SHADOW_CASCADE_LEVELS (Constants.glsl)
 
 
+class BlurParams(C.Structure):  # include/sailor_hip.h SailorBlurParams (Blur.shader:54-59): three vec4s
+    _fields_ = [("blurRadius", C.c_float * 4), ("blurCenter", C.c_float * 4), ("blurSampleCount", C.c_float * 4)]
+
+
+class ChromaticAberrationParams(C.Structure):  # include/sailor_hip.h SailorChromaticAberrationParams (ChromaticAberation.shader:52-55)
+    _fields_ = [("offset", C.c_float * 4)]
+
+
+BLUR_HORIZONTAL, BLUR_VERTICAL, BLUR_RADIAL = 1, 2, 4  # SAILOR_BLUR_*: Blur.shader's defines outside EVSM
+BLUR_DEFINES = {"HORIZONTAL": BLUR_HORIZONTAL, "VERTICAL": BLUR_VERTICAL, "RADIAL": BLUR_RADIAL}
+BLUR_GAUSS_SHIPPED = dict(blurRadius=(4.0, 2.0, 0.0, 0.0))  # DefaultRenderer.renderer:178 (a commented entry)
+BLUR_RADIAL_SHIPPED = dict(blurRadius=(20.0, 0.0, 0.0, 0.0), blurSampleCount=(10.0, 0.0, 0.0, 0.0), blurCenter=(0.5, 0.5, 0.0, 0.0))  # :164-166
+CHROMATIC_ABERRATION_SHIPPED = dict(offset=(0.00225, 0.00345, 0.00455, 0.0))  # :362
+
+
+def blur_flags(defines: str) -> int:
+    """'HORIZONTAL' | 'RADIAL VERTICAL' | '' (a PostProcess entry's `defines` string) -> SAILOR_BLUR_* bits; EVSM without RADIAL has its own entry point
+    (sailor_hip_evsm_blur_pass) and raises here, like an unknown define; with RADIAL the shader never reaches its EVSM branch"""
+    names = defines.split()
+    flags = 0
+    for name in names:
+        if name == "EVSM" and "RADIAL" in names:
+            continue
+        if name not in BLUR_DEFINES:
+            raise ValueError(f"no entry point for Blur.shader under {defines!r}: expected some of {sorted(BLUR_DEFINES)}")
+        flags |= BLUR_DEFINES[name]
+    return flags
+
+
 class SkyParams(C.Structure):  # include/sailor_hip.h SailorSkyParams (Sky.shader:116-136 == SkyNode.h:48-67)
     _fields_ = [("lightDirection", C.c_float * 4), ("cloudsAttenuation1", C.c_float), ("cloudsAttenuation2", C.c_float), ("cloudsDensity", C.c_float),
                 ("cloudsCoverage", C.c_float), ("phaseInfluence1", C.c_float), ("phaseInfluence2", C.c_float), ("eccentrisy1", C.c_float),
@@ -269,6 +298,9 @@ SIGNATURES = {
                                          C.POINTER(MotionBlurParams), _P, C.c_int32, C.c_int32]),
     "sailor_hip_debug_view": (C.c_int, [_P, C.POINTER(UboFrameData), C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32,
                                         C.c_int32, _P, C.c_int32, C.c_int32]),
+    "sailor_hip_blur": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(BlurParams), C.c_uint32, _P, C.c_int32, C.c_int32]),
+    "sailor_hip_chromatic_aberration": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(ChromaticAberrationParams), _P, C.c_int32, C.c_int32]),
+    "sailor_hip_blit_linear": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32]),
     "sailor_hip_sky_fill": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(SkyParams), _P, C.c_int32, C.c_int32]),
     "sailor_hip_sky_env_face": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(SkyParams), _P, C.c_int32, C.c_int32]),
     "sailor_hip_sky_sun": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(SkyParams), _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32]),

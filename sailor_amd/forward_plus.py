@@ -884,3 +884,49 @@ class DebugView:
                                                        w(linear_depth), h(linear_depth), _ptr(lights_grid), _ptr(culled_lights), _ptr(ao), w(ao), h(ao),
                                                        _ptr(self.out), self.width, self.height), "sailor_hip_debug_view", self.ctx.handle)
         return self.out
+
+
+def _check_rgba(t: torch.Tensor):
+    assert t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 3 and t.shape[2] == 4, (t.dtype, tuple(t.shape))
+
+
+class Blur:
+    """A Blur.shader PostProcess entry outside the shadow pass (DefaultRenderer.renderer:157-181; Blur.shader:66-98): the Gauss blur under "", "HORIZONTAL",
+    "VERTICAL" or both, the radial one under any set with "RADIAL".  `colorSampler` (any extent) in, the `color` target out.  Owns its output (height x width
+    RGBA32F; the Gauss blur writes alpha 0); `run` returns it."""
+
+    def __init__(self, ctx: HipContext, width: int, height: int, defines: str = "", params=None):
+        self.ctx, self.width, self.height, self.flags = ctx, width, height, _lib.blur_flags(defines)
+        self.params = params or host.blur_params(**(_lib.BLUR_RADIAL_SHIPPED if self.flags & _lib.BLUR_RADIAL else _lib.BLUR_GAUSS_SHIPPED))
+        self.out = torch.empty((height, width, 4), dtype=torch.float32, device=ctx.device)
+
+    def run(self, color: torch.Tensor) -> torch.Tensor:
+        _check_rgba(color)
+        _lib.check(self.ctx._lib.sailor_hip_blur(self.ctx.handle, _ptr(color), color.shape[1], color.shape[0], C.byref(self.params), self.flags, _ptr(self.out),
+                                                 self.width, self.height), "sailor_hip_blur", self.ctx.handle)
+        return self.out
+
+
+class ChromaticAberration:
+    """The ChromaticAberation.shader PostProcess entry (DefaultRenderer.renderer:355-366; ChromaticAberation.shader:62-73): `colorSampler` (any extent) in, the
+    `color` target out.  Owns its output (height x width RGBA32F, alpha 1); `run` returns it."""
+
+    def __init__(self, ctx: HipContext, width: int, height: int, params=None):
+        self.ctx, self.width, self.height = ctx, width, height
+        self.params = params or host.chromatic_aberration_params()
+        self.out = torch.empty((height, width, 4), dtype=torch.float32, device=ctx.device)
+
+    def run(self, color: torch.Tensor) -> torch.Tensor:
+        _check_rgba(color)
+        _lib.check(self.ctx._lib.sailor_hip_chromatic_aberration(self.ctx.handle, _ptr(color), color.shape[1], color.shape[0], C.byref(self.params), _ptr(self.out),
+                                                                 self.width, self.height), "sailor_hip_chromatic_aberration", self.ctx.handle)
+        return self.out
+
+
+def blit_linear(ctx: HipContext, src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
+    """The Blit entry of a scaled image with Linear filtration (BlitNode.cpp:88-96): src -> dst, both (h, w, 4) RGBA32F or both (h, w) one-channel fp32"""
+    assert src.dtype == dst.dtype == torch.float32 and src.is_contiguous() and dst.is_contiguous(), (src.dtype, dst.dtype)
+    assert src.dim() == dst.dim() and (src.dim() == 2 or (src.dim() == 3 and src.shape[2] == dst.shape[2] == 4)), (tuple(src.shape), tuple(dst.shape))
+    _lib.check(ctx._lib.sailor_hip_blit_linear(ctx.handle, _ptr(src), src.shape[1], src.shape[0], _ptr(dst), dst.shape[1], dst.shape[0], 4 if src.dim() == 3 else 1),
+               "sailor_hip_blit_linear", ctx.handle)
+    return dst

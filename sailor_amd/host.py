@@ -100,6 +100,32 @@ def motion_blur_params(**values) -> "_lib.MotionBlurParams":
     return _lib.MotionBlurParams(**{k: float(x) for k, x in v.items()})
 
 
+def _vec4(x):
+    """a scalar (the member's .x) or up to four components -> four floats"""
+    c = [float(t) for t in np.atleast_1d(np.asarray(x, np.float64))]
+    assert 1 <= len(c) <= 4, x
+    return tuple(c + [0.0] * (4 - len(c)))
+
+
+def blur_params(**values) -> "_lib.BlurParams":
+    """Blur.shader:54-59 PostProcessDataUBO: blurRadius, blurCenter, blurSampleCount, each a scalar (its .x) or up to four components; unnamed members are
+    zero, as in a PostProcess entry that does not set them (_lib.BLUR_GAUSS_SHIPPED / BLUR_RADIAL_SHIPPED: the shipped file's commented entries)"""
+    p = _lib.BlurParams()
+    for k, x in values.items():
+        getattr(p, k)[:] = _vec4(x)   # (an unknown member raises AttributeError)
+    return p
+
+
+def chromatic_aberration_params(**values) -> "_lib.ChromaticAberrationParams":
+    """ChromaticAberation.shader:52-55 PostProcessDataUBO; without `offset` it is the shipped commented entry's (DefaultRenderer.renderer:362)"""
+    v = dict(_lib.CHROMATIC_ABERRATION_SHIPPED)
+    v.update(values)
+    p = _lib.ChromaticAberrationParams()
+    for k, x in v.items():
+        getattr(p, k)[:] = _vec4(x)
+    return p
+
+
 def bloom_params(**values) -> "_lib.BloomParams":
     """The Bloom node's four parameters; unnamed members keep the shipped values (DefaultRenderer.renderer:298-302)"""
     v = dict(_lib.BLOOM_SHIPPED)

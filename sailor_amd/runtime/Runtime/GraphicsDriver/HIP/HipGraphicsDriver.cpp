@@ -86,7 +86,7 @@ RHIShaderPtr HipGraphicsDriver::CreateShader(const std::string& assetPath, const
         "Shaders/ComputeDepthHighZ.shader", "Shaders/ComputeHistogram.shader", "Shaders/ComputeAverageLuminance.shader", "Shaders/ComputeBrdfLut.shader",
         "Shaders/ComputeIrradianceMap.shader", "Shaders/ComputeEnvMap_IBL.shader", "Shaders/ShadowCaster.shader", "Shaders/LinearizeDepth.shader",
         "Shaders/Tonemapping.shader", "Shaders/Blur.shader", "Shaders/HBAO.shader", "Shaders/HBAO_Blur.shader", "Shaders/Sky.shader", "Shaders/ComputeBloomDownscale.shader",
-        "Shaders/ComputeBloomUpscale.shader", "Shaders/Blit.shader" };
+        "Shaders/ComputeBloomUpscale.shader", "Shaders/Blit.shader", "Shaders/ChromaticAberation.shader" };
     auto shader = RHIShaderPtr::Make(assetPath, defines);
     shader->m_bIsReady = false;
     for (const char* name : routed) if (assetPath == name) shader->m_bIsReady = true;
@@ -421,6 +421,9 @@ void HipGraphicsDriver::SetMaterialParameter(RHICommandListPtr cmd, RHIShaderBin
         { "Shaders/HBAO_Blur.shader", "sharpness", 0 }, { "Shaders/HBAO_Blur.shader", "distanceScale", 4 }, { "Shaders/HBAO_Blur.shader", "radius", 8 },
         // MotionBlur.shader:50-55 (SailorMotionBlurParams): three floats
         { "Shaders/MotionBlur.shader", "intensity", 0 }, { "Shaders/MotionBlur.shader", "samples", 4 }, { "Shaders/MotionBlur.shader", "maxSpeed", 8 },
+        // Blur.shader:54-59 (SailorBlurParams): three vec4s; ChromaticAberation.shader:52-55 (SailorChromaticAberrationParams): one
+        { "Shaders/Blur.shader", "blurRadius", 0 }, { "Shaders/Blur.shader", "blurCenter", 16 }, { "Shaders/Blur.shader", "blurSampleCount", 32 },
+        { "Shaders/ChromaticAberation.shader", "offset", 0 },
         // Sky.shader:116-136 (SailorSkyParams): a vec4, then seventeen 4-byte scalars
         { "Shaders/Sky.shader", "lightDirection", 0 }, { "Shaders/Sky.shader", "cloudsAttenuation1", 16 }, { "Shaders/Sky.shader", "cloudsAttenuation2", 20 },
         { "Shaders/Sky.shader", "cloudsDensity", 24 }, { "Shaders/Sky.shader", "cloudsCoverage", 28 }, { "Shaders/Sky.shader", "phaseInfluence1", 32 },
@@ -451,6 +454,17 @@ bool HipGraphicsDriver::BlitImage(RHICommandListPtr cmd, RHITexturePtr src, RHIT
             BeforeBufferWrite(dst->m_buffer->m_hip.m_devicePtr);
             return sailor_hip_blit_nearest(ctx, (const float*)texels_of(src), src->GetExtent().x, src->GetExtent().y, (float*)texels_of(dst), dst->GetExtent().x,
                                            dst->GetExtent().y);
+        });
+        return true;
+    }
+    // ... and a scaled colour or one-channel image with Linear filtration (BlitNode.cpp:88: Main -> QuarterMain1) is sailor_hip_blit_linear
+    const bool rgba = whole && src->m_format == EFormat::R32G32B32A32_SFLOAT;
+    if (whole && !sameExtent && filtration == ETextureFiltration::Linear && (rgba || src->m_format == EFormat::R32_SFLOAT) && !src->m_bCubemap && !dst->m_bCubemap) {
+        SailorHipContext* ctx = m_ctx;
+        cmd->m_hip.m_commands.push_back([this, ctx, src, dst, rgba]() {
+            BeforeBufferWrite(dst->m_buffer->m_hip.m_devicePtr);
+            return sailor_hip_blit_linear(ctx, (const float*)texels_of(src), src->GetExtent().x, src->GetExtent().y, (float*)texels_of(dst), dst->GetExtent().x,
+                                          dst->GetExtent().y, rgba ? 4 : 1);
         });
         return true;
     }
@@ -856,6 +870,9 @@ void HipGraphicsDriver::DrawIndexed(RHICommandListPtr cmd, uint32_t indexCount, 
     const uint32_t tonemapFlags = !shader ? 0u : (shader->HasDefine("ACES") ? SAILOR_TONEMAP_ACES : 0u) | (shader->HasDefine("UNCHARTED2") ? SAILOR_TONEMAP_UNCHARTED2 : 0u) |
                                                  (shader->HasDefine("LUMINANCE") ? SAILOR_TONEMAP_LUMINANCE : 0u);
     const bool evsm = shader && shader->HasDefine("EVSM"), vertical = shader && shader->HasDefine("VERTICAL"), horizontal = shader && shader->HasDefine("HORIZONTAL");
+    // Blur.shader outside the shadow pass' {EVSM, HORIZONTAL | VERTICAL}: RADIAL wins over EVSM by the shader's #ifdef order (Blur.shader:78-96)
+    const bool radial = shader && shader->HasDefine("RADIAL");
+    const uint32_t blurFlags = (horizontal ? SAILOR_BLUR_HORIZONTAL : 0u) | (vertical ? SAILOR_BLUR_VERTICAL : 0u) | (radial ? SAILOR_BLUR_RADIAL : 0u);
     // Sky.shader's permutation: 0 {FILL}, 1 {}, 2 {SUN}, 3 {COMPOSE}, 4 {CLOUDS}, -1 anything else (CreateShader left those "not ready")
     const int sky = (!shader || !shader->IsReady()) ? -1
                     : (shader->m_defines.empty() ? 1 : (shader->HasDefine("FILL") ? 0 : (shader->HasDefine("SUN") ? 2 : (shader->HasDefine("CLOUDS") ? 4 : 3))));
@@ -869,8 +886,8 @@ void HipGraphicsDriver::DrawIndexed(RHICommandListPtr cmd, uint32_t indexCount, 
     const int debugMode = !tail ? -1
                           : (shader->m_defines.empty() ? SAILOR_DEBUG_VIEW_SCENE
                              : (shader->HasDefine("AO") ? SAILOR_DEBUG_VIEW_AO : (shader->HasDefine("LIGHT_TILES") ? SAILOR_DEBUG_VIEW_LIGHT_TILES : SAILOR_DEBUG_VIEW_CASCADES)));
-    cmd->m_hip.m_commands.push_back([this, name, bindings, target, fullScreenQuad, evsm, vertical, horizontal, tonemapFlags, sky, alphaBlending, tail, debugMode, blend,
-                                     starVertices, starIndices, pushConstants, indexCount, instanceCount, firstIndex, vertexOffset]() {
+    cmd->m_hip.m_commands.push_back([this, name, bindings, target, fullScreenQuad, evsm, vertical, horizontal, radial, blurFlags, tonemapFlags, sky, alphaBlending, tail,
+                                     debugMode, blend, starVertices, starIndices, pushConstants, indexCount, instanceCount, firstIndex, vertexOffset]() {
         // the point list of the star mesh: DrawIndexed(count, 1, 0, 0, 0) (SkyNode.cpp:720), not the quad
         if (name == "Shaders/Stars.shader" && tail && instanceCount == 1 && firstIndex == 0 && vertexOffset == 0)
             return RecordStars(bindings, target, starVertices, starIndices, indexCount, pushConstants, blend);
@@ -880,7 +897,9 @@ void HipGraphicsDriver::DrawIndexed(RHICommandListPtr cmd, uint32_t indexCount, 
         if (fullScreenQuad && name == "Shaders/Blit.shader" && alphaBlending) return RecordBlitAlphaBlended(bindings, target);
         if (fullScreenQuad && name == "Shaders/LinearizeDepth.shader") return RecordLinearizeDepth(bindings, target);
         if (fullScreenQuad && name == "Shaders/Tonemapping.shader") return RecordTonemap(bindings, target, tonemapFlags);
+        if (fullScreenQuad && name == "Shaders/Blur.shader" && (radial || !evsm)) return RecordBlur(bindings, target, blurFlags);
         if (fullScreenQuad && name == "Shaders/Blur.shader" && evsm && vertical != horizontal) return RecordEvsmBlur(bindings, target, vertical);
+        if (fullScreenQuad && name == "Shaders/ChromaticAberation.shader") return RecordChromaticAberration(bindings, target);
         if (fullScreenQuad && name == "Shaders/HBAO.shader") return RecordHbao(bindings, target);
         if (fullScreenQuad && name == "Shaders/HBAO_Blur.shader" && vertical != horizontal) return RecordHbaoBlur(bindings, target, vertical);
         if (fullScreenQuad && name == "Shaders/MotionBlur.shader" && tail) return RecordMotionBlur(bindings, target);
@@ -1036,6 +1055,43 @@ int HipGraphicsDriver::RecordDebugView(const TVector<RHIShaderBindingSetPtr>& bi
                                  ao ? ao->GetExtent().y : 0, (float*)texels_of(target), target->GetExtent().x, target->GetExtent().y);
 }
 
+// ---- PostProcessNode with Blur.shader outside the shadow pass and ChromaticAberation.shader (DefaultRenderer.renderer:157-181, :355-366) -----------
+// PostProcessNode.cpp:189: { sceneView.m_frameBindings, m_shaderBindings, sceneView.m_rhiLightsData }; both shaders read set 1 alone: binding 0 `data`,
+// 1 `colorSampler` (Blur.shader:54-61, ChromaticAberation.shader:52-57).  `colorSampler` and the `color` target may be mip chains (Main): texels and extent
+// are level 0's.  A name that resolved to nothing is an invalid argument, an image that is not RGBA32F is unsupported; resources the shader does not declare
+// (the shipped aberration entry passes `depthStencil`) are ignored.
+static int post_effect_images(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& target, RHITexturePtr& color)
+{
+    if (bindings.size() < 2 || !target || !target->m_buffer) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    color = bound_texture(bindings[1], "colorSampler");
+    if (!color) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (color->m_format != EFormat::R32G32B32A32_SFLOAT || target->m_format != EFormat::R32G32B32A32_SFLOAT || color->m_bCubemap || target->m_bCubemap)
+        return SAILOR_HIP_ERR_UNSUPPORTED;
+    return SAILOR_HIP_OK;
+}
+
+int HipGraphicsDriver::RecordBlur(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& target, uint32_t flags)
+{
+    RHITexturePtr color;
+    SailorBlurParams params;
+    if (const int st = post_effect_images(bindings, target, color)) return st;
+    if (!host_copy_of(bindings[1], "data", params)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    BeforeBufferWrite(target->m_buffer->m_hip.m_devicePtr);
+    return sailor_hip_blur(m_ctx, (const float*)texels_of(color), color->GetExtent().x, color->GetExtent().y, &params, flags, (float*)texels_of(target),
+                           target->GetExtent().x, target->GetExtent().y);
+}
+
+int HipGraphicsDriver::RecordChromaticAberration(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& target)
+{
+    RHITexturePtr color;
+    SailorChromaticAberrationParams params;
+    if (const int st = post_effect_images(bindings, target, color)) return st;
+    if (!host_copy_of(bindings[1], "data", params)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    BeforeBufferWrite(target->m_buffer->m_hip.m_devicePtr);
+    return sailor_hip_chromatic_aberration(m_ctx, (const float*)texels_of(color), color->GetExtent().x, color->GetExtent().y, &params, (float*)texels_of(target),
+                                           target->GetExtent().x, target->GetExtent().y);
+}
+
 // ---- SkyNode (FrameGraph/SkyNode.cpp:536-563, :611-680, :764-797) --------------------------------------------------------------------------
 int HipGraphicsDriver::RecordSky(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& target, int permutation)
 {
@@ -1159,8 +1215,8 @@ int HipGraphicsDriver::RecordSunShafts(const TVector<RHIShaderBindingSetPtr>& bi
 int HipGraphicsDriver::RecordEvsmBlur(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& target, bool vertical)
 {
     // ShadowPrepassNode.cpp:309,343: { sceneView.m_frameBindings, m_pBlurShaderBindings }; Blur.shader:53-61: set 1 binding 0 `data` (blurRadius.xy =
-    // [umbra, penumbra], uploaded at :286), binding 1 `colorSampler`
-    if (bindings.size() != 2 || !target || !target->m_buffer) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    // [umbra, penumbra], uploaded at :286), binding 1 `colorSampler`.  A PostProcess entry with these defines binds the lights set third (PostProcessNode.cpp:189)
+    if (bindings.size() < 2 || !target || !target->m_buffer) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     auto src = bound_texture(bindings[1], "colorSampler");
     float radius[2];
     if (!host_copy_of(bindings[1], "data", radius) || !src) return SAILOR_HIP_ERR_INVALID_ARGUMENT;

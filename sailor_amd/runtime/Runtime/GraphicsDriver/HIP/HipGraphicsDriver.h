@@ -19,6 +19,9 @@
 //   "Shaders/LinearizeDepth.shader"      -> sailor_hip_linearize_depth   (binding contract: LinearizeDepth.shader:15-59)
 //   "Shaders/Tonemapping.shader" {ACES, UNCHARTED2, LUMINANCE} -> sailor_hip_tonemap (binding contract: Tonemapping.shader:52-59)
 //   "Shaders/Blur.shader" {EVSM, HORIZONTAL | VERTICAL} -> sailor_hip_evsm_blur_pass (binding contract: Blur.shader:53-61)
+//   "Shaders/Blur.shader" under any define set with RADIAL, or without EVSM -> sailor_hip_blur (binding contract: Blur.shader:54-61: set 1 `data`,
+//                                           `colorSampler`; HORIZONTAL / VERTICAL / RADIAL become SAILOR_BLUR_* flags)
+//   "Shaders/ChromaticAberation.shader"  -> sailor_hip_chromatic_aberration (binding contract: ChromaticAberation.shader:52-57: set 1 `data`, `colorSampler`)
 //   "Shaders/HBAO.shader"                -> sailor_hip_hbao              (binding contract: HBAO.shader:50-60)
 //   "Shaders/HBAO_Blur.shader" {VERTICAL | HORIZONTAL, exactly one} -> sailor_hip_hbao_blur_pass (binding contract: HBAO_Blur.shader:54-62)
 //   "Shaders/Sky.shader" by define set: {FILL} -> sailor_hip_sky_fill, {} (into a cube face view) -> sailor_hip_sky_env_face, {SUN} -> sailor_hip_sky_sun
@@ -36,6 +39,7 @@
 //                                           created "not ready"
 //   "Shaders/Blit.shader" of a material with EBlendMode::AlphaBlending ("Blit Clouds") -> sailor_hip_sky_blit_clouds (binding: `colorSampler`)
 // a scaled one-channel BlitImage with Nearest filtration -> sailor_hip_blit_nearest
+// a scaled RGBA32F or one-channel BlitImage with Linear filtration -> sailor_hip_blit_linear
 // and the depth-only instanced draws of the shadow passes (material of)
 //   "Shaders/ShadowCaster.shader" [EVSM]  -> sailor_hip_raster_depth into the pass' depth attachment, and at EndRenderPass sailor_hip_shadow_resolve
 //                                            into its colour attachment (push constant lightMatrix, set 1 `data`, vertex positions, 32-bit indices)
@@ -150,6 +154,8 @@ private:
     int RecordHbaoBlur(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target, bool vertical);
     int RecordMotionBlur(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target);
     int RecordDebugView(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target, int mode);
+    int RecordBlur(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target, uint32_t flags);
+    int RecordChromaticAberration(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target);
     int RecordSky(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target, int permutation);
     int RecordSkyClouds(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target);
     int RecordBlitAlphaBlended(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target);
