@@ -1179,6 +1179,101 @@ SAILOR_HIP_API int sailor_host_csm_plan_passes(SailorCsmSnapshots* snapshots, ui
                                                const uint64_t* overlapMasks, const uint32_t* shadowTypes, const uint64_t* lastChangedFrame,
                                                const SailorCsmView* view, uint32_t* outRender, uint64_t* outMasks);
 
+/* ---- RenderScene: the surface pass (surface.hip) ---------------------------------------------------------------------------------------------
+ * Replaces: the vertex stage of Content/Shaders/Standard.shader:126-139, the rasteriser between the stages and the material half of its fragment
+ * stage (:379-389, :438) for the draws of FrameGraph/RenderSceneNode.cpp -- it PRODUCES the three planes sailor_hip_shade* consume.
+ * The rasterisation rules are the depth prepass's (sailor_hip_raster_depth_camera: near-plane cut, 1/256-pixel snapping, 64-bit edge functions,
+ * top-left rule, optional back-face cull, z = (z0 + (z1 - z0) w1) + (z2 - z0) w2, fragments outside (0, 1] do not exist), so the depth of the pass is
+ * bit for bit the prepass's.  Depth test GreaterOrEqual (RHI/Types.h:536-537) in Vulkan's primitive order: a fragment wins its pixel if its z is
+ * greater than what is stored, or equal and it is drawn later -- kept order-free as a 64-bit key per pixel, depthBits << 32 | (order + 1) under an
+ * unsigned maximum, order = primBase + d * 2 * numTriangles + 2 * triangle + part (d = the instance's position in the draw, part = the half of a
+ * triangle the near plane cut in two); low word 0 = no primitive.  Varyings are perspective-correct: l_k = float(e_k) / area, q_k = l_k / w_k,
+ * s = (q0 + q1) + q2, b_k = q_k / s, a = (a0 b0 + a1 b1) + a2 b2; a vertex cut on the near plane gets a = aI + (aO - aI) t with the position's t.
+ * texture() is the base level, bilinear, Repeat over RGBA8 texels; SAILOR_TEXTURE_SRGB decodes r, g, b per tap through sailor_host_srgb_table before
+ * filtering.  NOT reproduced: the implicit mip selection of texture() (textures have one level here), anisotropy, ALPHA_CUTOUT / the Masked tag,
+ * Standard_glTF.shader.  A sampler index >= numTextures reads descriptor 0 (the reference binds g_defaultSampler there), a materialInstance >=
+ * numMaterials reads material 0, a descriptor without texels samples as 0: no fetch leaves a table.
+ * All entry points record only (no allocation, no synchronisation, capturable); a refused call launches nothing and leaves a text in last_error. */
+
+/* RHI/Types.h:720-727 VertexP3N3T3B3UV2C4, interleaved, 72 bytes */
+typedef struct SailorVertexP3N3T3B3UV2C4 {
+    float texcoord[2];
+    float position[3];
+    float normal[3];
+    float tangent[3];
+    float bitangent[3];
+    float color[4];
+} SailorVertexP3N3T3B3UV2C4;
+
+/* Standard.shader:164-178 MaterialData, std430: 80 bytes */
+typedef struct SailorMaterialData {
+    float albedo[4];
+    float ambient[4];
+    float emission[4];
+    float metallic;
+    float roughness;
+    float ao;
+    uint32_t albedoSampler;
+    uint32_t metalnessSampler;
+    uint32_t normalSampler;
+    uint32_t roughnessSampler;
+    uint32_t _pad;
+} SailorMaterialData;
+
+/* one entry of Standard.shader:124 textureSamplers[]: a width x height RGBA8 image, one uint32 per texel (r in the low byte), row 0 first */
+#define SAILOR_TEXTURE_SRGB 1u /* R8G8B8A8_SRGB (TextureAssetInfo.h:31, the default); without it UNORM (normal maps, ModelImporter.cpp:176) */
+typedef struct SailorTextureDesc {
+    const uint32_t* texels; /* device */
+    int32_t width;
+    int32_t height;
+    uint32_t flags;
+    uint32_t _pad;
+} SailorTextureDesc;
+
+/* one DrawIndexed of RenderSceneNode.cpp (BindVertexBuffer / BindIndexBuffer / DrawIndexed): the draw kernel stores it into slot drawIndex of the
+ * workspace, from where the resolve finds a key's draw by its primBase.  Slots are used in rising order with rising primBase. */
+#define SAILOR_SURFACE_CULL_BACK 1u /* ECullMode::Back, frontFace counter-clockwise, as SAILOR_RASTER_CULL_BACK */
+typedef struct SailorSurfaceDraw {
+    const SailorVertexP3N3T3B3UV2C4* dVertices; /* device, already offset by vertexOffset */
+    const uint32_t* dIndices;                   /* device, 3 x numTriangles, already offset by firstIndex */
+    const uint32_t* dInstanceIds;               /* device, numDrawn instance indices in drawing order, or NULL for firstInstance .. firstInstance + numDrawn - 1 */
+    uint32_t numTriangles;
+    uint32_t numDrawn;
+    uint32_t primBase;                          /* the order of the draw's first primitive: the previous draw's primBase + its sailor_hip_surface_draw_prims */
+    uint32_t flags;                             /* SAILOR_SURFACE_CULL_BACK */
+    uint32_t firstInstance;
+    uint32_t _pad;
+} SailorSurfaceDraw;
+
+/* the workspace of one pass over the rows of `band`: a header, the sRGB table, one 64-bit key per pixel of the band, maxDraws descriptors; 0 = invalid */
+SAILOR_HIP_API size_t sailor_hip_surface_workspace_bytes(int32_t width, int32_t height, const SailorBand* band, uint32_t maxDraws);
+/* where the keys begin in a workspace: uint64 per pixel of the band, row-major, depthBits << 32 | (order + 1) (tests and diagnostics) */
+SAILOR_HIP_API size_t sailor_hip_surface_keys_offset(void);
+/* Replaces: BeginRenderPass(Main, DepthBuffer) at RenderSceneNode.cpp.  Keys = prepass depth bits << 32 (dDepthOrNull: the raw width x height depth
+ * attachment of the WHOLE frame, as sailor_hip_raster_depth_camera leaves it), or 0; every descriptor slot empty. */
+SAILOR_HIP_API int sailor_hip_surface_begin(SailorHipContext* ctx, const float* dDepthOrNull, int32_t width, int32_t height, const SailorBand* band,
+                                            void* dWorkspace, size_t workspaceBytes);
+/* Replaces: one DrawIndexed with Standard.shader's vertex stage (:128-131) and the fixed-function rasteriser: k_surface_visibility. */
+SAILOR_HIP_API int sailor_hip_surface_draw(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSurfaceDraw* draw,
+                                           const SailorPerInstanceData* dInstances, uint32_t drawIndex, int32_t width, int32_t height, const SailorBand* band,
+                                           void* dWorkspace, size_t workspaceBytes);
+/* Replaces: the varyings (:132-138) and the material half of the fragment stage (:382-389, :438) at the winning fragment of every pixel: k_surface_resolve.
+ *   dSurface : device out, 3 planes of float4, each the band's rows x width, planeStride float4 apart (what sailor_hip_shade* read):
+ *              P0 = worldPosition, albedo.a; P1 = normal, roughness; P2 = albedo.rgb, metallic; an uncovered pixel gets 0, (0, 0, 1, 1), 0
+ *   dDepthOutOrNull : device out, the band's rows x width floats: the final depth (equal to the prepass depth wherever the same draws were prepassed)
+ *   dCoverageOrNull : device out, the band's rows x width bytes: 1 where a primitive of this pass owns the pixel */
+SAILOR_HIP_API int sailor_hip_surface_resolve(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorPerInstanceData* dInstances,
+                                              const SailorMaterialData* dMaterials, uint32_t numMaterials, const SailorTextureDesc* dTextures, uint32_t numTextures,
+                                              int32_t width, int32_t height, const SailorBand* band, const void* dWorkspace, size_t workspaceBytes,
+                                              float* dSurface, size_t planeStride, float* dDepthOutOrNull, uint8_t* dCoverageOrNull);
+/* Replaces: the colour writes of the pass over what `Blit Sky -> Main` left: target = covered ? radiance : target (both the band's rows x width float4). */
+SAILOR_HIP_API int sailor_hip_surface_composite(SailorHipContext* ctx, const float* dRadiance, const void* dWorkspace, size_t workspaceBytes, float* dTarget,
+                                                int32_t width, int32_t height, const SailorBand* band);
+/* The sRGB transfer function (c <= 0.04045 ? c / 12.92 : ((c + 0.055) / 1.055)^2.4, c = i / 255) in double, rounded once to fp32. */
+SAILOR_HIP_API int sailor_host_srgb_table(float out[256]);
+/* numDrawn * 2 * numTriangles (saturating at 2^64 - 1): what a draw adds to the running primBase.  sailor_hip_surface_draw refuses a draw whose primBase + this reaches 2^32 - 1. */
+SAILOR_HIP_API int sailor_hip_surface_draw_prims(uint32_t numTriangles, uint32_t numDrawn, uint64_t* out);
+
 #ifdef __cplusplus
 }
 #endif

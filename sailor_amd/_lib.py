@@ -195,6 +195,35 @@ class IblDesc(C.Structure):  # include/sailor_hip.h SailorIblDesc (Standard.shad
                 ("brdfLut", C.c_void_p), ("lutW", C.c_int32), ("lutH", C.c_int32), ("ao", C.c_void_p)]
 
 
+class VertexP3N3T3B3UV2C4(C.Structure):  # RHI/Types.h:720-727, interleaved
+    _fields_ = [("texcoord", C.c_float * 2), ("position", C.c_float * 3), ("normal", C.c_float * 3), ("tangent", C.c_float * 3),
+                ("bitangent", C.c_float * 3), ("color", C.c_float * 4)]
+
+
+class MaterialData(C.Structure):  # Standard.shader:164-178, std430
+    _fields_ = [("albedo", C.c_float * 4), ("ambient", C.c_float * 4), ("emission", C.c_float * 4), ("metallic", C.c_float), ("roughness", C.c_float),
+                ("ao", C.c_float), ("albedoSampler", C.c_uint32), ("metalnessSampler", C.c_uint32), ("normalSampler", C.c_uint32),
+                ("roughnessSampler", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class TextureDesc(C.Structure):  # include/sailor_hip.h SailorTextureDesc: one entry of Standard.shader:124 textureSamplers[]
+    _fields_ = [("texels", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class SurfaceDraw(C.Structure):  # include/sailor_hip.h SailorSurfaceDraw: one DrawIndexed of RenderSceneNode.cpp
+    _fields_ = [("dVertices", C.c_void_p), ("dIndices", C.c_void_p), ("dInstanceIds", C.c_void_p), ("numTriangles", C.c_uint32), ("numDrawn", C.c_uint32),
+                ("primBase", C.c_uint32), ("flags", C.c_uint32), ("firstInstance", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+TEXTURE_SRGB = 1        # SAILOR_TEXTURE_SRGB
+SURFACE_CULL_BACK = 1   # SAILOR_SURFACE_CULL_BACK
+# the same records as NumPy dtypes (what the tests and upload helpers build)
+VERTEX_DTYPE = [("texcoord", "<f4", 2), ("position", "<f4", 3), ("normal", "<f4", 3), ("tangent", "<f4", 3), ("bitangent", "<f4", 3), ("color", "<f4", 4)]
+MATERIAL_DTYPE = [("albedo", "<f4", 4), ("ambient", "<f4", 4), ("emission", "<f4", 4), ("metallic", "<f4"), ("roughness", "<f4"), ("ao", "<f4"),
+                  ("albedoSampler", "<u4"), ("metalnessSampler", "<u4"), ("normalSampler", "<u4"), ("roughnessSampler", "<u4"), ("_pad", "<u4")]
+
+assert C.sizeof(VertexP3N3T3B3UV2C4) == 72 and C.sizeof(MaterialData) == 80
+assert C.sizeof(TextureDesc) == 24 and C.sizeof(SurfaceDraw) == 48
 assert C.sizeof(UboFrameData) == 232 and C.sizeof(LightCullPushConstants) == 88 and C.sizeof(LightShaderData) == 112
 
 _P = C.c_void_p
@@ -358,6 +387,15 @@ SIGNATURES = {
     "sailor_host_csm_snapshot_get": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), _P, _P, C.POINTER(C.c_int32), C.POINTER(CsmView)]),
     "sailor_host_csm_plan_passes": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, C.POINTER(CsmView), _P, _P]),
     "sailor_host_pack_light": (C.c_int, [C.c_uint32, C.c_uint32] + [C.POINTER(C.c_float)] * 6 + [C.POINTER(LightShaderData)]),
+    "sailor_hip_surface_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.POINTER(Band), C.c_uint32]),
+    "sailor_hip_surface_begin": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(Band), _P, C.c_size_t]),
+    "sailor_hip_surface_draw": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(SurfaceDraw), _P, C.c_uint32, C.c_int32, C.c_int32, C.POINTER(Band), _P, C.c_size_t]),
+    "sailor_hip_surface_resolve": (C.c_int, [_P, C.POINTER(UboFrameData), _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, C.c_int32, C.POINTER(Band), _P, C.c_size_t,
+                                             _P, C.c_size_t, _P, _P]),
+    "sailor_hip_surface_composite": (C.c_int, [_P, _P, _P, C.c_size_t, _P, C.c_int32, C.c_int32, C.POINTER(Band)]),
+    "sailor_hip_surface_keys_offset": (C.c_size_t, []),
+    "sailor_host_srgb_table": (C.c_int, [C.POINTER(C.c_float)]),
+    "sailor_hip_surface_draw_prims": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

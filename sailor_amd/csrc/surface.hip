@@ -1,0 +1,578 @@
+// RenderScene's producer of the surface buffer: Standard.shader's vertex stage (:126-139), the rasteriser between the stages and the material half of
+// the fragment stage (:379-389, :438) as a VISIBILITY BUFFER for gfx950.  include/sailor_hip.h has the pinned rules; tests/surface_ref.py restates them
+// sequentially (draw by draw, a >= test against a depth array) and the kernels are held to it bit for bit.
+//
+//   k_surface_begin       one 64-bit key per pixel of the band = prepass depth bits << 32 (or 0); empty descriptor slots; the sRGB table
+//   k_surface_visibility  per draw: a lane per (instance, triangle) sets its triangle up as k_raster_depth does; small triangles are filled by their
+//                         lane, large ones are handed round the wave -- the 8 x 8 blocks of a 64 x 64 superblock one per lane, the blocks an edge does
+//                         not rule out one lane per texel.  A fragment READS the pixel's key and issues the 64-bit atomicMax only if its own is larger:
+//                         behind a prepass almost every losing fragment ends at that plain load.
+//   k_surface_resolve     a lane per pixel: key -> draw (binary search of primBase over the descriptors) -> instance, triangle, part; the set-up again,
+//                         the edge functions at this pixel, the varyings one by one (never all 54 vertex values at once), material, four samples.
+//   k_surface_composite   target = covered ? radiance : target
+//
+// The depth of a fragment and everything in front of it (clip, cut, snap, edges, top-left) are raster.hip's, so that the depth is the prepass's bit for
+// bit.  raster.hip keeps its set-up functions static and reads tightly packed positions; the few of them needed here are COPIED below (surf_cut,
+// surf_floor_div256, surf_edge, surf_top_left, and surface_setup = raster_setup over interleaved vertices that also reports where each vertex came from).
+#include "common.h"
+#include "sampling.h"
+#include "texel_pass.h"
+#include <math.h>
+
+#define SURF_SMALL_BOX 64   // pixels a lane fills on its own
+#define SURF_VERTEX_FLOATS 18
+#define SURF_INSTANCE_FLOATS 24
+#define SURF_HEADER_BYTES 64
+#define SURF_TABLE_BYTES 1024
+#define SURF_MAX_DRAWS (1u << 20)
+#define SURF_SLICE_LANES 262144ull
+#define SURF_SLICES_MAX 256ull
+
+struct SurfHeader { uint32_t maxDraws, rows, width, fbRowBegin; uint32_t pad[12]; };
+struct SurfSrgb { float v[256]; };
+
+struct SurfTri { long long x0, y0, x1, y1, x2, y2; float z0, z1, z2; int i0, i1, j0, j1; bool valid; };
+// where the three vertices of a set-up triangle came from: vertex k is source vertex I[k], or -- cut[k] -- the point I[k] + (O[k] - I[k]) * t[k] of an
+// edge the near plane cut; w[k] is its clip w
+struct SurfSrc { uint32_t I[3], O[3]; float t[3], w[3]; bool cut[3]; };
+
+// ---- copied from raster.hip (static there) --------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ long long surf_floor_div256(long long a) { return a >= 0 ? a / 256 : -((-a + 255) / 256); }
+__device__ __forceinline__ float4 surf_cut(const float4& I, float dI, const float4& O, float dO, float& t)
+{
+    t = dI / (dI - dO);
+    return make_float4(I.x + (O.x - I.x) * t, I.y + (O.y - I.y) * t, I.z + (O.z - I.z) * t, I.w + (O.w - I.w) * t);
+}
+__device__ __forceinline__ long long surf_edge(long long ax, long long ay, long long bx, long long by, long long px, long long py)
+{
+    return (bx - ax) * (py - ay) - (by - ay) * (px - ax);
+}
+__device__ __forceinline__ bool surf_top_left(long long ax, long long ay, long long bx, long long by)
+{
+    const long long dx = bx - ax, dy = by - ay;
+    return (dy == 0 && dx > 0) || dy < 0;
+}
+
+// raster_setup of raster.hip (hasView form: clip = projection * (view * (model * position)), DepthOnly.shader:51 == Standard.shader:131) over interleaved
+// vertices; rows [rowBegin, rowEnd) of the frame only.  S reports the vertices' sources for the varyings (dead code where it is not read).
+__device__ __forceinline__ SurfTri surface_setup(const Mat4& P, const Mat4& V, const float* __restrict__ model, const float* __restrict__ vertices,
+                                                 const uint32_t* __restrict__ tri, int W, int H, int rowBegin, int rowEnd, bool cullBack, int part, bool& hasSecond,
+                                                 SurfSrc& S)
+{
+    SurfTri t;
+    t.valid = false;
+    hasSecond = false;
+    float4 c[3];
+    const uint32_t v0 = tri[0], v1 = tri[1], v2 = tri[2];
+    Mat4 M;
+#pragma unroll
+    for (int q = 0; q < 16; q++) M.m[q] = model[q];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const float* p = vertices + SURF_VERTEX_FLOATS * (size_t)(k == 0 ? v0 : (k == 1 ? v1 : v2)) + 2;
+        const float4 a = glsl_mul(M, p[0], p[1], p[2], 1.0f);
+        const float4 bq = glsl_mul(V, a.x, a.y, a.z, a.w);
+        c[k] = glsl_mul(P, bq.x, bq.y, bq.z, bq.w);
+    }
+    S.I[0] = v0; S.I[1] = v1; S.I[2] = v2;
+    S.O[0] = v0; S.O[1] = v1; S.O[2] = v2;
+    S.t[0] = S.t[1] = S.t[2] = 0.0f;
+    S.cut[0] = S.cut[1] = S.cut[2] = false;
+    const float d0 = c[0].w - c[0].z, d1 = c[1].w - c[1].z, d2 = c[2].w - c[2].z;
+    const int mask = (d0 >= 0.0f ? 1 : 0) | (d1 >= 0.0f ? 2 : 0) | (d2 >= 0.0f ? 4 : 0);
+    if (mask == 0) return t;
+    if (mask != 7) {
+        const bool one = (mask & (mask - 1)) == 0;
+        const int r = one ? (mask == 1 ? 0 : (mask == 2 ? 1 : 2)) : (mask == 6 ? 1 : (mask == 5 ? 2 : 0)); // the rotation that brings A to the front
+        const float4 A = r == 0 ? c[0] : (r == 1 ? c[1] : c[2]), B = r == 0 ? c[1] : (r == 1 ? c[2] : c[0]), C = r == 0 ? c[2] : (r == 1 ? c[0] : c[1]);
+        const float dA = r == 0 ? d0 : (r == 1 ? d1 : d2), dB = r == 0 ? d1 : (r == 1 ? d2 : d0), dC = r == 0 ? d2 : (r == 1 ? d0 : d1);
+        const uint32_t iA = r == 0 ? v0 : (r == 1 ? v1 : v2), iB = r == 0 ? v1 : (r == 1 ? v2 : v0), iC = r == 0 ? v2 : (r == 1 ? v0 : v1);
+        S.I[0] = iA; S.O[0] = iA;
+        if (one) {
+            if (part) return t;
+            c[0] = A; c[1] = surf_cut(A, dA, B, dB, S.t[1]); c[2] = surf_cut(A, dA, C, dC, S.t[2]);
+            S.I[1] = iA; S.O[1] = iB; S.cut[1] = true;
+            S.I[2] = iA; S.O[2] = iC; S.cut[2] = true;
+        } else {
+            float tBC;
+            const float4 BC = surf_cut(B, dB, C, dC, tBC);
+            hasSecond = true;
+            c[0] = A;
+            if (part == 0) {
+                c[1] = B; c[2] = BC;
+                S.I[1] = iB; S.O[1] = iB;
+                S.I[2] = iB; S.O[2] = iC; S.t[2] = tBC; S.cut[2] = true;
+            } else {
+                c[1] = BC; c[2] = surf_cut(A, dA, C, dC, S.t[2]);
+                S.I[1] = iB; S.O[1] = iC; S.t[1] = tBC; S.cut[1] = true;
+                S.I[2] = iA; S.O[2] = iC; S.cut[2] = true;
+            }
+        }
+    } else if (part) return t;
+    long long X[3], Y[3];
+    float Z[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const float4 clip = c[k];
+        if (!(clip.w > 0.0f)) return t;
+        const float nx = clip.x / clip.w, ny = clip.y / clip.w, nz = clip.z / clip.w;
+        const float xf = (nx + 1.0f) * ((float)W * 0.5f);
+        const float yf = (ny + 1.0f) * ((float)H * -0.5f) + (float)H;
+        const float sx = xf * 256.0f, sy = yf * 256.0f;
+        if (!(fabsf(sx) < 1.0e9f) || !(fabsf(sy) < 1.0e9f)) return t;
+        X[k] = (long long)rintf(sx); Y[k] = (long long)rintf(sy); Z[k] = nz;
+        S.w[k] = clip.w;
+    }
+    const long long area2 = (X[1] - X[0]) * (Y[2] - Y[0]) - (X[2] - X[0]) * (Y[1] - Y[0]);
+    if (area2 == 0) return t;
+    if (cullBack && area2 > 0) return t; // Vulkan's signed area is -area2 / 2, front = counter-clockwise = positive (see the oracle)
+    if (area2 < 0) { // the winding swap takes the varyings' sources along
+        long long s = X[1]; X[1] = X[2]; X[2] = s; s = Y[1]; Y[1] = Y[2]; Y[2] = s; const float z = Z[1]; Z[1] = Z[2]; Z[2] = z;
+        const uint32_t i = S.I[1]; S.I[1] = S.I[2]; S.I[2] = i; const uint32_t o = S.O[1]; S.O[1] = S.O[2]; S.O[2] = o;
+        const float tt = S.t[1]; S.t[1] = S.t[2]; S.t[2] = tt; const float w = S.w[1]; S.w[1] = S.w[2]; S.w[2] = w;
+        const bool cu = S.cut[1]; S.cut[1] = S.cut[2]; S.cut[2] = cu;
+    }
+    t.x0 = X[0]; t.y0 = Y[0]; t.x1 = X[1]; t.y1 = Y[1]; t.x2 = X[2]; t.y2 = Y[2];
+    t.z0 = Z[0]; t.z1 = Z[1]; t.z2 = Z[2];
+    const long long minx = min(X[0], min(X[1], X[2])), maxx = max(X[0], max(X[1], X[2]));
+    const long long miny = min(Y[0], min(Y[1], Y[2])), maxy = max(Y[0], max(Y[1], Y[2]));
+    long long i0 = surf_floor_div256(minx - 128 + 255), i1 = surf_floor_div256(maxx - 128);
+    long long j0 = surf_floor_div256(miny - 128 + 255), j1 = surf_floor_div256(maxy - 128);
+    if (i0 < 0) i0 = 0;
+    if (j0 < rowBegin) j0 = rowBegin;
+    if (i1 > W - 1) i1 = W - 1;
+    if (j1 > rowEnd - 1) j1 = rowEnd - 1;
+    if (i1 < i0 || j1 < j0) return t;
+    t.i0 = (int)i0; t.i1 = (int)i1; t.j0 = (int)j0; t.j1 = (int)j1;
+    t.valid = true;
+    return t;
+}
+
+__device__ __forceinline__ long long surf_bcast64(long long v, int src)
+{
+    const int lo = __shfl((int)(unsigned int)(unsigned long long)v, src, 64), hi = __shfl((int)((unsigned long long)v >> 32), src, 64);
+    return (long long)(((unsigned long long)(unsigned int)hi << 32) | (unsigned int)lo);
+}
+
+// the depth test of one fragment, GreaterOrEqual in primitive order: the larger key wins.  A relaxed atomic load first (other waves run atomicMax on the
+// same word): a fragment that has already lost never reaches the atomic, and a stale value can only be SMALLER than the key now stored, so no winner is
+// dropped.
+__device__ __forceinline__ void surf_fragment(unsigned long long* p, float z, unsigned int orderPlus1)
+{
+    const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | orderPlus1;
+    if (key > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p, key);
+}
+
+// ---- workspace ------------------------------------------------------------------------------------------------------------------------------------
+struct SurfWorkspace { SurfHeader* header; float* srgb; unsigned long long* keys; SailorSurfaceDraw* draws; };
+static __host__ __device__ __forceinline__ SurfWorkspace surf_workspace(void* base, size_t pixels)
+{
+    SurfWorkspace w;
+    char* b = reinterpret_cast<char*>(base);
+    w.header = reinterpret_cast<SurfHeader*>(b);
+    w.srgb = reinterpret_cast<float*>(b + SURF_HEADER_BYTES);
+    w.keys = reinterpret_cast<unsigned long long*>(b + SURF_HEADER_BYTES + SURF_TABLE_BYTES);
+    w.draws = reinterpret_cast<SailorSurfaceDraw*>(b + SURF_HEADER_BYTES + SURF_TABLE_BYTES + pixels * 8);
+    return w;
+}
+
+__global__ __launch_bounds__(256) void k_surface_begin(const float* __restrict__ depth, int W, int rowBegin, int rows, uint32_t maxDraws, void* __restrict__ workspace,
+                                                       SurfSrgb table)
+{
+    const size_t pixels = (size_t)rows * W;
+    const SurfWorkspace ws = surf_workspace(workspace, pixels);
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (g < pixels) ws.keys[g] = depth ? (unsigned long long)__float_as_uint(depth[(size_t)rowBegin * W + g]) << 32 : 0ull;
+    if (g < maxDraws) {
+        SailorSurfaceDraw e;
+        e.dVertices = nullptr; e.dIndices = nullptr; e.dInstanceIds = nullptr;
+        e.numTriangles = 0; e.numDrawn = 0; e.primBase = 0xFFFFFFFFu; e.flags = 0; e.firstInstance = 0; e._pad = 0;
+        ws.draws[g] = e;
+    }
+    if (g < 256) ws.srgb[g] = table.v[g];
+    if (g == 0) {
+        SurfHeader h;
+        memset(&h, 0, sizeof h);
+        h.maxDraws = maxDraws; h.rows = (uint32_t)rows; h.width = (uint32_t)W; h.fbRowBegin = (uint32_t)rowBegin;
+        *ws.header = h;
+    }
+}
+
+// ---- the draw -------------------------------------------------------------------------------------------------------------------------------------
+// gridDim.y SLICES: a draw of few triangles has few waves, and a wave fills its large triangles alone, superblock after superblock (the two triangles of a ground
+// quad would be two waves' work, whatever the frame's size).  Such a draw is launched gridDim.y times over: every slice sets all triangles up again (cheap: there are
+// few), slice 0 fills the small ones, and of a large triangle's superblocks slice y takes those whose running number is y modulo the slices.  The keys do not
+// depend on who writes them.
+__global__ __launch_bounds__(256) void k_surface_visibility(Mat4 P, Mat4 V, SailorSurfaceDraw draw, const float* __restrict__ instances, uint32_t drawIndex, int W, int H,
+                                                            int rowBegin, int rows, void* __restrict__ workspace)
+{
+    const SurfWorkspace ws = surf_workspace(workspace, (size_t)rows * W);
+    const unsigned int slice = blockIdx.y, slices = gridDim.y;
+    if (blockIdx.x == 0 && slice == 0 && threadIdx.x == 0) ws.draws[drawIndex] = draw; // the resolve finds the draw here
+    unsigned long long* keys = ws.keys;
+    const float* __restrict__ vertices = reinterpret_cast<const float*>(draw.dVertices);
+    const unsigned long long total = (unsigned long long)draw.numDrawn * draw.numTriangles;
+    const unsigned long long id = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool have = id < total;
+    uint32_t d = 0, tri = 0, inst = 0;
+    if (have) {
+        d = (uint32_t)(id / draw.numTriangles); tri = (uint32_t)(id - (unsigned long long)d * draw.numTriangles);
+        inst = draw.dInstanceIds ? draw.dInstanceIds[d] : draw.firstInstance + d;
+    }
+    const bool cullBack = (draw.flags & SAILOR_SURFACE_CULL_BACK) != 0;
+    // a triangle cut by the near plane can leave a quad: its second half is a second trip through the same code, taken only by waves that hold one
+    bool again = false;
+    for (int part = 0; part < 2; part++) {
+        if (part && !__any(again)) break;
+        SurfTri t;
+        t.valid = false;
+        bool second = false;
+        if (have && (part == 0 || again)) {
+            SurfSrc S;
+            t = surface_setup(P, V, instances + SURF_INSTANCE_FLOATS * (size_t)inst, vertices, draw.dIndices + 3 * (size_t)tri, W, H, rowBegin, rowBegin + rows, cullBack,
+                              part, second, S);
+        }
+        const unsigned int orderPlus1 = draw.primBase + (unsigned int)(2ull * id) + (unsigned int)part + 1u; // (the entry point has checked the range)
+        const bool small = t.valid && (long long)(t.i1 - t.i0 + 1) * (t.j1 - t.j0 + 1) <= SURF_SMALL_BOX;
+        if (small && slice == 0) {
+            const float area = (float)surf_edge(t.x0, t.y0, t.x1, t.y1, t.x2, t.y2);
+            const bool tl0 = surf_top_left(t.x1, t.y1, t.x2, t.y2), tl1 = surf_top_left(t.x2, t.y2, t.x0, t.y0), tl2 = surf_top_left(t.x0, t.y0, t.x1, t.y1);
+            // the three edge functions walked texel by texel in exact integer steps, as k_raster_depth does
+            const long long px0 = 256ll * t.i0 + 128, py0 = 256ll * t.j0 + 128;
+            long long r0 = surf_edge(t.x1, t.y1, t.x2, t.y2, px0, py0), r1 = surf_edge(t.x2, t.y2, t.x0, t.y0, px0, py0), r2 = surf_edge(t.x0, t.y0, t.x1, t.y1, px0, py0);
+            const long long dx0 = -256ll * (t.y2 - t.y1), dx1 = -256ll * (t.y0 - t.y2), dx2 = -256ll * (t.y1 - t.y0);
+            const long long dy0 = 256ll * (t.x2 - t.x1), dy1 = 256ll * (t.x0 - t.x2), dy2 = 256ll * (t.x1 - t.x0);
+            for (int j = t.j0; j <= t.j1; j++, r0 += dy0, r1 += dy1, r2 += dy2) {
+                long long e0 = r0, e1 = r1, e2 = r2;
+                for (int i = t.i0; i <= t.i1; i++, e0 += dx0, e1 += dx1, e2 += dx2) {
+                    if (e0 < 0 || e1 < 0 || e2 < 0) continue;
+                    if ((e0 == 0 && !tl0) || (e1 == 0 && !tl1) || (e2 == 0 && !tl2)) continue;
+                    const float z = (t.z0 + (t.z1 - t.z0) * ((float)e1 / area)) + (t.z2 - t.z0) * ((float)e2 / area);
+                    if (z > 0.0f && z <= 1.0f) surf_fragment(keys + (size_t)(j - rowBegin) * W + i, z, orderPlus1);
+                }
+            }
+        }
+        // the large ones: the whole wave on one triangle at a time
+        unsigned long long todo = __ballot(t.valid && !small);
+        while (todo) {
+            const int src = __builtin_ctzll(todo);
+            todo &= todo - 1ull;
+            SurfTri b;
+            b.x0 = surf_bcast64(t.x0, src); b.y0 = surf_bcast64(t.y0, src); b.x1 = surf_bcast64(t.x1, src); b.y1 = surf_bcast64(t.y1, src);
+            b.x2 = surf_bcast64(t.x2, src); b.y2 = surf_bcast64(t.y2, src);
+            b.z0 = __shfl(t.z0, src, 64); b.z1 = __shfl(t.z1, src, 64); b.z2 = __shfl(t.z2, src, 64);
+            b.i0 = __shfl(t.i0, src, 64); b.i1 = __shfl(t.i1, src, 64); b.j0 = __shfl(t.j0, src, 64); b.j1 = __shfl(t.j1, src, 64);
+            const unsigned int bOrder = (unsigned int)__shfl((int)orderPlus1, src, 64);
+            const float area = (float)surf_edge(b.x0, b.y0, b.x1, b.y1, b.x2, b.y2);
+            const bool tl0 = surf_top_left(b.x1, b.y1, b.x2, b.y2), tl1 = surf_top_left(b.x2, b.y2, b.x0, b.y0), tl2 = surf_top_left(b.x0, b.y0, b.x1, b.y1);
+            // 64 x 64-texel superblocks of the box one after the other; of each, the 8 x 8 blocks one per lane: a block wholly outside an edge is dropped
+            // (an edge function is affine, so its largest value over the block sits at a corner texel)
+            unsigned int number = 0;
+            for (int sj = b.j0 >> 6; sj <= (b.j1 >> 6); sj++)
+                for (int si = b.i0 >> 6; si <= (b.i1 >> 6); si++) {
+                    if (number++ % slices != slice) continue;
+                    const int bi = si * 8 + (lane & 7), bj = sj * 8 + (lane >> 3);
+                    bool alive = bi >= (b.i0 >> 3) && bi <= (b.i1 >> 3) && bj >= (b.j0 >> 3) && bj <= (b.j1 >> 3);
+                    if (alive) {
+                        long long m0 = -0x7FFFFFFFFFFFFFFFll, m1 = m0, m2 = m0;
+#pragma unroll
+                        for (int c = 0; c < 4; c++) {
+                            const long long px = 256ll * (bi * 8 + ((c & 1) ? 7 : 0)) + 128, py = 256ll * (bj * 8 + ((c & 2) ? 7 : 0)) + 128;
+                            m0 = max(m0, surf_edge(b.x1, b.y1, b.x2, b.y2, px, py)); m1 = max(m1, surf_edge(b.x2, b.y2, b.x0, b.y0, px, py));
+                            m2 = max(m2, surf_edge(b.x0, b.y0, b.x1, b.y1, px, py));
+                        }
+                        alive = m0 >= 0 && m1 >= 0 && m2 >= 0;
+                    }
+                    unsigned long long live = __ballot(alive);
+                    while (live) { // the surviving blocks, one lane per texel
+                        const int s2 = __builtin_ctzll(live);
+                        live &= live - 1ull;
+                        const int i = (si * 8 + (s2 & 7)) * 8 + (lane & 7), j = (sj * 8 + (s2 >> 3)) * 8 + (lane >> 3);
+                        if (i >= b.i0 && i <= b.i1 && j >= b.j0 && j <= b.j1) {
+                            const long long px = 256ll * i + 128, py = 256ll * j + 128;
+                            const long long e0 = surf_edge(b.x1, b.y1, b.x2, b.y2, px, py), e1 = surf_edge(b.x2, b.y2, b.x0, b.y0, px, py),
+                                            e2 = surf_edge(b.x0, b.y0, b.x1, b.y1, px, py);
+                            const bool in = !(e0 < 0 || e1 < 0 || e2 < 0) && !((e0 == 0 && !tl0) || (e1 == 0 && !tl1) || (e2 == 0 && !tl2));
+                            if (in) {
+                                const float z = (b.z0 + (b.z1 - b.z0) * ((float)e1 / area)) + (b.z2 - b.z0) * ((float)e2 / area);
+                                if (z > 0.0f && z <= 1.0f) surf_fragment(keys + (size_t)(j - rowBegin) * W + i, z, bOrder);
+                            }
+                        }
+                    }
+                }
+        }
+        if (part == 0) again = second;
+    }
+}
+
+// ---- the resolve ----------------------------------------------------------------------------------------------------------------------------------
+// varying c of source vertex v under the instance's model m (Standard.shader:128-138): 0-1 texcoord, 2-4 worldPosition = (model * vec4(p, 1)).xyz / .w,
+// 5-8 color, 9-17 tangentBasis = mat3(model) * mat3(inTangent, inBitangent, inNormal), column by column.  c is a compile-time constant where it is called.
+__device__ __forceinline__ float surf_varying(const float* __restrict__ v, const float* __restrict__ m, int c)
+{
+    if (c < 2) return v[c];
+    if (c < 5) {
+        const int r = c - 2;
+        const float x = v[2], y = v[3], z = v[4];
+        const float a = ((m[r] * x + m[4 + r] * y) + m[8 + r] * z) + m[12 + r] * 1.0f;
+        const float w = ((m[3] * x + m[7] * y) + m[11] * z) + m[15] * 1.0f;
+        return a / w;
+    }
+    if (c < 9) return v[14 + (c - 5)];
+    const int col = (c - 9) / 3, r = (c - 9) % 3;
+    const float* __restrict__ a = v + (col == 0 ? 8 : (col == 1 ? 11 : 5));
+    return (m[r] * a[0] + m[4 + r] * a[1]) + m[8 + r] * a[2];
+}
+
+// texture(textureSamplers[index], uv): base level, bilinear, Repeat; SRGB decodes r, g, b per tap through the table before the filter
+__device__ __forceinline__ float4 surf_texture(const SailorTextureDesc* __restrict__ textures, uint32_t numTextures, uint32_t index, const float* __restrict__ srgb,
+                                               float u, float v)
+{
+    const SailorTextureDesc d = textures[index < numTextures ? index : 0u];
+    if (!d.texels || d.width <= 0 || d.height <= 0) return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (!(d.flags & SAILOR_TEXTURE_SRGB)) return bilinear_repeat_rgba8(d.texels, d.width, d.height, u, v);
+    const RepeatTap X = repeat_tap(d.width, u), Y = repeat_tap(d.height, v);
+    const uint32_t a = d.texels[Y.i0 * d.width + X.i0], c = d.texels[Y.i0 * d.width + X.i1], e = d.texels[Y.i1 * d.width + X.i0], f = d.texels[Y.i1 * d.width + X.i1];
+    float4 r;
+    r.x = lerp2(srgb[a & 255u], srgb[c & 255u], srgb[e & 255u], srgb[f & 255u], X.a, Y.a);
+    r.y = lerp2(srgb[(a >> 8) & 255u], srgb[(c >> 8) & 255u], srgb[(e >> 8) & 255u], srgb[(f >> 8) & 255u], X.a, Y.a);
+    r.z = lerp2(srgb[(a >> 16) & 255u], srgb[(c >> 16) & 255u], srgb[(e >> 16) & 255u], srgb[(f >> 16) & 255u], X.a, Y.a);
+    r.w = lerp2(unorm8(a >> 24), unorm8(c >> 24), unorm8(e >> 24), unorm8(f >> 24), X.a, Y.a);
+    return r;
+}
+
+__global__ __launch_bounds__(256) void k_surface_resolve(Mat4 P, Mat4 V, const float* __restrict__ instances, const SailorMaterialData* __restrict__ materials,
+                                                         uint32_t numMaterials, const SailorTextureDesc* __restrict__ textures, uint32_t numTextures, int W, int H,
+                                                         int rowBegin, int rows, uint32_t maxDraws, const void* __restrict__ workspace, float4* __restrict__ surface, size_t planeStride,
+                                                         float* __restrict__ depthOut, uint8_t* __restrict__ coverage)
+{
+    const int i = texel_i(), jb = texel_j();
+    if (i >= W || jb >= rows) return;
+    const SurfWorkspace ws = surf_workspace(const_cast<void*>(workspace), (size_t)rows * W);
+    const size_t at = (size_t)jb * W + i;
+    const unsigned long long key = ws.keys[at];
+    const unsigned int low = (unsigned int)key;
+    if (depthOut) depthOut[at] = __uint_as_float((unsigned int)(key >> 32));
+    float4 p0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), p1 = make_float4(0.0f, 0.0f, 1.0f, 1.0f), p2 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    bool covered = false;
+    if (low != 0u) {
+        const unsigned int order = low - 1u;
+        // the last descriptor whose primBase does not exceed the order (empty slots hold 0xFFFFFFFF)
+        unsigned int lo = 0, hi = maxDraws; // (from the workspace's size, as begin derived it)
+        while (hi - lo > 1u) {
+            const unsigned int mid = lo + ((hi - lo) >> 1);
+            if (ws.draws[mid].primBase <= order) lo = mid; else hi = mid;
+        }
+        const SailorSurfaceDraw draw = ws.draws[lo];
+        const unsigned int rel = order - draw.primBase;
+        const unsigned int per = 2u * draw.numTriangles;
+        const unsigned int d = per ? rel / per : 0xFFFFFFFFu;
+        if (draw.primBase <= order && d < draw.numDrawn) {
+            const unsigned int r = rel - d * per, tri = r >> 1;
+            const int part = (int)(r & 1u);
+            const uint32_t inst = draw.dInstanceIds ? draw.dInstanceIds[d] : draw.firstInstance + d;
+            const float* __restrict__ model = instances + SURF_INSTANCE_FLOATS * (size_t)inst;
+            const float* __restrict__ vertices = reinterpret_cast<const float*>(draw.dVertices);
+            bool second;
+            SurfSrc S;
+            const SurfTri t = surface_setup(P, V, model, vertices, draw.dIndices + 3 * (size_t)tri, W, H, rowBegin, rowBegin + rows,
+                                            (draw.flags & SAILOR_SURFACE_CULL_BACK) != 0, part, second, S);
+            if (t.valid) {
+                covered = true;
+                const long long px = 256ll * i + 128, py = 256ll * (jb + rowBegin) + 128;
+                const float area = (float)surf_edge(t.x0, t.y0, t.x1, t.y1, t.x2, t.y2);
+                const float l0 = (float)surf_edge(t.x1, t.y1, t.x2, t.y2, px, py) / area, l1 = (float)surf_edge(t.x2, t.y2, t.x0, t.y0, px, py) / area,
+                            l2 = (float)surf_edge(t.x0, t.y0, t.x1, t.y1, px, py) / area;
+                const float q0 = l0 / S.w[0], q1 = l1 / S.w[1], q2 = l2 / S.w[2];
+                const float s = (q0 + q1) + q2;
+                const float b0 = q0 / s, b1 = q1 / s, b2 = q2 / s;
+                const float* __restrict__ vI0 = vertices + SURF_VERTEX_FLOATS * (size_t)S.I[0];
+                const float* __restrict__ vI1 = vertices + SURF_VERTEX_FLOATS * (size_t)S.I[1];
+                const float* __restrict__ vI2 = vertices + SURF_VERTEX_FLOATS * (size_t)S.I[2];
+                const float* __restrict__ vO1 = vertices + SURF_VERTEX_FLOATS * (size_t)S.O[1];
+                const float* __restrict__ vO2 = vertices + SURF_VERTEX_FLOATS * (size_t)S.O[2];
+                float a[18]; // (statically indexed under full unrolling: registers)
+#pragma unroll
+                for (int c = 0; c < 18; c++) {
+                    const float a0 = surf_varying(vI0, model, c); // (vertex 0 is never a cut one)
+                    float a1 = surf_varying(vI1, model, c), a2 = surf_varying(vI2, model, c);
+                    if (S.cut[1]) a1 = a1 + (surf_varying(vO1, model, c) - a1) * S.t[1];
+                    if (S.cut[2]) a2 = a2 + (surf_varying(vO2, model, c) - a2) * S.t[2];
+                    a[c] = (a0 * b0 + a1 * b1) + a2 * b2;
+                }
+                const uint32_t mi = reinterpret_cast<const uint32_t*>(model)[20]; // PerInstanceData.materialInstance, flat
+                const SailorMaterialData mat = materials[mi < numMaterials ? mi : 0u];
+                const float u = a[0], v = a[1];
+                const float4 tA = surf_texture(textures, numTextures, mat.albedoSampler, ws.srgb, u, v);
+                const float tM = surf_texture(textures, numTextures, mat.metalnessSampler, ws.srgb, u, v).x;
+                const float tR = surf_texture(textures, numTextures, mat.roughnessSampler, ws.srgb, u, v).x;
+                const float4 tN = surf_texture(textures, numTextures, mat.normalSampler, ws.srgb, u, v);
+                // :383-385
+                const float ar = (mat.albedo[0] * tA.x) * a[5], ag = (mat.albedo[1] * tA.y) * a[6], ab = (mat.albedo[2] * tA.z) * a[7], aa = (mat.albedo[3] * tA.w) * a[8];
+                const float metallic = mat.metallic * tM, roughness = mat.roughness * tR;
+                // :388-389
+                float nx = 2.0f * tN.x - 1.0f, ny = 2.0f * tN.y - 1.0f, nz = 2.0f * tN.z - 1.0f;
+                float len = sqrtf(dot3f(nx, ny, nz, nx, ny, nz));
+                nx = nx / len; ny = ny / len; nz = nz / len;
+                float wx = (a[9] * nx + a[12] * ny) + a[15] * nz, wy = (a[10] * nx + a[13] * ny) + a[16] * nz, wz = (a[11] * nx + a[14] * ny) + a[17] * nz;
+                len = sqrtf(dot3f(wx, wy, wz, wx, wy, wz));
+                wx = wx / len; wy = wy / len; wz = wz / len;
+                p0 = make_float4(a[2], a[3], a[4], aa);
+                p1 = make_float4(wx, wy, wz, roughness);
+                p2 = make_float4(ar, ag, ab, metallic);
+            }
+        }
+    }
+    surface[at] = p0;
+    surface[planeStride + at] = p1;
+    surface[2 * planeStride + at] = p2;
+    if (coverage) coverage[at] = covered ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void k_surface_composite(const float4* __restrict__ radiance, const void* __restrict__ workspace, float4* __restrict__ target, int W, int rows)
+{
+    const int i = texel_i(), jb = texel_j();
+    if (i >= W || jb >= rows) return;
+    const SurfWorkspace ws = surf_workspace(const_cast<void*>(workspace), (size_t)rows * W);
+    const size_t at = (size_t)jb * W + i;
+    if ((unsigned int)ws.keys[at] != 0u) target[at] = radiance[at];
+}
+
+// ---- entry points ---------------------------------------------------------------------------------------------------------------------------------
+static int surf_refuse(SailorHipContext* ctx, const char* what)
+{
+    if (ctx) ctx->lastError = what;
+    return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+}
+static bool surf_band_ok(int32_t width, int32_t height, const SailorBand* band)
+{
+    return band && extent_ok(width, height) && sailor_hip_band_is_valid(width, height, band) == 1 && band->fbRowCount > 0;
+}
+static size_t surf_fixed_bytes(int32_t width, const SailorBand* band)
+{
+    return (size_t)SURF_HEADER_BYTES + SURF_TABLE_BYTES + (size_t)band->fbRowCount * width * 8;
+}
+// the descriptor slots a workspace of `bytes` holds
+static uint32_t surf_max_draws(int32_t width, const SailorBand* band, size_t bytes)
+{
+    const size_t fixed = surf_fixed_bytes(width, band);
+    if (bytes < fixed + sizeof(SailorSurfaceDraw)) return 0;
+    const size_t n = (bytes - fixed) / sizeof(SailorSurfaceDraw);
+    return (uint32_t)(n < SURF_MAX_DRAWS ? n : SURF_MAX_DRAWS);
+}
+
+extern "C" {
+
+int sailor_host_srgb_table(float out[256])
+{
+    if (!out) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    for (int i = 0; i < 256; i++) {
+        const double c = (double)i / 255.0;
+        out[i] = (float)(c <= 0.04045 ? c / 12.92 : pow((c + 0.055) / 1.055, 2.4));
+    }
+    return SAILOR_HIP_OK;
+}
+
+size_t sailor_hip_surface_keys_offset(void) { return (size_t)SURF_HEADER_BYTES + SURF_TABLE_BYTES; }
+
+int sailor_hip_surface_draw_prims(uint32_t numTriangles, uint32_t numDrawn, uint64_t* out)
+{
+    if (!out) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    const uint64_t n = (uint64_t)numDrawn * (uint64_t)numTriangles;
+    *out = n > 0x7FFFFFFFFFFFFFFFull ? 0xFFFFFFFFFFFFFFFFull : 2ull * n; // saturates
+    return SAILOR_HIP_OK;
+}
+
+size_t sailor_hip_surface_workspace_bytes(int32_t width, int32_t height, const SailorBand* band, uint32_t maxDraws)
+{
+    if (!surf_band_ok(width, height, band) || maxDraws == 0 || maxDraws > SURF_MAX_DRAWS) return 0;
+    return surf_fixed_bytes(width, band) + (size_t)maxDraws * sizeof(SailorSurfaceDraw);
+}
+
+int sailor_hip_surface_begin(SailorHipContext* ctx, const float* dDepthOrNull, int32_t width, int32_t height, const SailorBand* band, void* dWorkspace,
+                             size_t workspaceBytes)
+{
+    if (!ctx) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (!surf_band_ok(width, height, band)) return surf_refuse(ctx, "sailor_hip_surface_begin: the band is not valid for the frame");
+    if (!aligned(dWorkspace, 16)) return surf_refuse(ctx, "sailor_hip_surface_begin: the workspace is NULL or not 16-byte aligned");
+    const uint32_t maxDraws = surf_max_draws(width, band, workspaceBytes);
+    if (maxDraws == 0) return surf_refuse(ctx, "sailor_hip_surface_begin: the workspace is too small");
+    static const SurfSrgb table = [] { SurfSrgb t; sailor_host_srgb_table(t.v); return t; }();
+    SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t pixels = (size_t)band->fbRowCount * width;
+    size_t threads = pixels > maxDraws ? pixels : maxDraws;
+    if (threads < 256) threads = 256;
+    sailor_launch(ctx, k_surface_begin, dim3((unsigned)((threads + 255) / 256)), dim3(256), dDepthOrNull, (int)width, (int)band->fbRowBegin, (int)band->fbRowCount, maxDraws,
+                  dWorkspace, table);
+    SAILOR_CHECK_LAUNCH(ctx, "k_surface_begin");
+    return SAILOR_HIP_OK;
+}
+
+int sailor_hip_surface_draw(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSurfaceDraw* draw, const SailorPerInstanceData* dInstances,
+                            uint32_t drawIndex, int32_t width, int32_t height, const SailorBand* band, void* dWorkspace, size_t workspaceBytes)
+{
+    if (!ctx) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (!frame || !draw) return surf_refuse(ctx, "sailor_hip_surface_draw: frame or draw is NULL");
+    if (!surf_band_ok(width, height, band)) return surf_refuse(ctx, "sailor_hip_surface_draw: the band is not valid for the frame");
+    if (!aligned(dWorkspace, 16)) return surf_refuse(ctx, "sailor_hip_surface_draw: the workspace is NULL or not 16-byte aligned");
+    const uint32_t maxDraws = surf_max_draws(width, band, workspaceBytes);
+    if (maxDraws == 0) return surf_refuse(ctx, "sailor_hip_surface_draw: the workspace is too small");
+    if (drawIndex >= maxDraws) return surf_refuse(ctx, "sailor_hip_surface_draw: drawIndex is beyond the workspace's descriptor slots");
+    if (draw->flags & ~SAILOR_SURFACE_CULL_BACK) return surf_refuse(ctx, "sailor_hip_surface_draw: unknown flags");
+    const unsigned long long total = (unsigned long long)draw->numDrawn * draw->numTriangles;
+    if (total && (!draw->dVertices || !draw->dIndices || !dInstances)) return surf_refuse(ctx, "sailor_hip_surface_draw: a vertex, index or instance buffer is NULL");
+    if (total > 0x7FFFFFFFull || (unsigned long long)draw->primBase + 2ull * total >= 0xFFFFFFFFull) return surf_refuse(ctx, "sailor_hip_surface_draw: primBase + the draw's primitives reaches 2^32 - 1");
+    Mat4 P, V;
+    memcpy(P.m, frame->projection, 64);
+    memcpy(V.m, frame->view, 64);
+    SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
+    const unsigned long long blocks = total ? (total + 255) / 256 : 1; // (an empty draw still leaves its descriptor)
+    // slices (see the kernel): about SURF_SLICE_LANES lanes in flight for a draw of few triangles, one slice from that many triangles on
+    const unsigned long long want = total ? SURF_SLICE_LANES / total : 1;
+    const unsigned slices = (unsigned)(want < 1 ? 1 : (want > SURF_SLICES_MAX ? SURF_SLICES_MAX : want));
+    sailor_launch(ctx, k_surface_visibility, dim3((unsigned)blocks, slices), dim3(256), P, V, *draw, reinterpret_cast<const float*>(dInstances), drawIndex, (int)width, (int)height,
+                  (int)band->fbRowBegin, (int)band->fbRowCount, dWorkspace);
+    SAILOR_CHECK_LAUNCH(ctx, "k_surface_visibility");
+    return SAILOR_HIP_OK;
+}
+
+int sailor_hip_surface_resolve(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorPerInstanceData* dInstances, const SailorMaterialData* dMaterials,
+                               uint32_t numMaterials, const SailorTextureDesc* dTextures, uint32_t numTextures, int32_t width, int32_t height, const SailorBand* band,
+                               const void* dWorkspace, size_t workspaceBytes, float* dSurface, size_t planeStride, float* dDepthOutOrNull, uint8_t* dCoverageOrNull)
+{
+    if (!ctx) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (!frame || !dInstances || !dMaterials || !dTextures || numMaterials == 0 || numTextures == 0)
+        return surf_refuse(ctx, "sailor_hip_surface_resolve: frame, instances, materials or textures missing");
+    if (!surf_band_ok(width, height, band)) return surf_refuse(ctx, "sailor_hip_surface_resolve: the band is not valid for the frame");
+    const uint32_t maxDraws = surf_max_draws(width, band, workspaceBytes);
+    if (!aligned(dWorkspace, 16) || maxDraws == 0) return surf_refuse(ctx, "sailor_hip_surface_resolve: the workspace is NULL, misaligned or too small");
+    if (!aligned(dSurface, 16)) return surf_refuse(ctx, "sailor_hip_surface_resolve: the surface is NULL or not 16-byte aligned");
+    if (planeStride < (size_t)band->fbRowCount * width) return surf_refuse(ctx, "sailor_hip_surface_resolve: planeStride is smaller than the band's rows x width");
+    if (dDepthOutOrNull && !aligned(dDepthOutOrNull, 4)) return surf_refuse(ctx, "sailor_hip_surface_resolve: the depth output is misaligned");
+    Mat4 P, V;
+    memcpy(P.m, frame->projection, 64);
+    memcpy(V.m, frame->view, 64);
+    SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
+    sailor_launch(ctx, k_surface_resolve, texel_grid(width, band->fbRowCount), dim3(256), P, V, reinterpret_cast<const float*>(dInstances), dMaterials, numMaterials, dTextures,
+                  numTextures, (int)width, (int)height, (int)band->fbRowBegin, (int)band->fbRowCount, maxDraws, dWorkspace, reinterpret_cast<float4*>(dSurface), planeStride,
+                  dDepthOutOrNull, dCoverageOrNull);
+    SAILOR_CHECK_LAUNCH(ctx, "k_surface_resolve");
+    return SAILOR_HIP_OK;
+}
+
+int sailor_hip_surface_composite(SailorHipContext* ctx, const float* dRadiance, const void* dWorkspace, size_t workspaceBytes, float* dTarget, int32_t width,
+                                 int32_t height, const SailorBand* band)
+{
+    if (!ctx) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (!surf_band_ok(width, height, band)) return surf_refuse(ctx, "sailor_hip_surface_composite: the band is not valid for the frame");
+    if (!aligned(dWorkspace, 16) || surf_max_draws(width, band, workspaceBytes) == 0) return surf_refuse(ctx, "sailor_hip_surface_composite: the workspace is NULL, misaligned or too small");
+    if (!aligned(dRadiance, 16) || !aligned(dTarget, 16)) return surf_refuse(ctx, "sailor_hip_surface_composite: radiance or target is NULL or not 16-byte aligned");
+    SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
+    sailor_launch(ctx, k_surface_composite, texel_grid(width, band->fbRowCount), dim3(256), reinterpret_cast<const float4*>(dRadiance), dWorkspace,
+                  reinterpret_cast<float4*>(dTarget), (int)width, (int)band->fbRowCount);
+    SAILOR_CHECK_LAUNCH(ctx, "k_surface_composite");
+    return SAILOR_HIP_OK;
+}
+
+} // extern "C"

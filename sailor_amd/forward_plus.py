@@ -930,3 +930,81 @@ def blit_linear(ctx: HipContext, src: torch.Tensor, dst: torch.Tensor) -> torch.
     _lib.check(ctx._lib.sailor_hip_blit_linear(ctx.handle, _ptr(src), src.shape[1], src.shape[0], _ptr(dst), dst.shape[1], dst.shape[0], 4 if src.dim() == 3 else 1),
                "sailor_hip_blit_linear", ctx.handle)
     return dst
+
+
+def upload_textures(ctx: HipContext, images, srgb) -> tuple[torch.Tensor, int, list]:
+    """Standard.shader:124 textureSamplers[]: a list of uint8 [H, W, 4] arrays (r first) and their sRGB flags -> (device table of SailorTextureDesc, its
+    length, the tensors that must stay alive)"""
+    assert len(images) == len(srgb) and len(images) > 0
+    keep, table = [], (_lib.TextureDesc * len(images))()
+    for k, (img, s) in enumerate(zip(images, srgb)):
+        img = np.ascontiguousarray(img, np.uint8)
+        assert img.ndim == 3 and img.shape[2] == 4 and img.shape[0] > 0 and img.shape[1] > 0, img.shape
+        t = torch.from_numpy(img.view(np.uint32).reshape(img.shape[0], img.shape[1]).view(np.int32)).to(ctx.device)
+        keep.append(t)
+        table[k] = _lib.TextureDesc(t.data_ptr(), img.shape[1], img.shape[0], _lib.TEXTURE_SRGB if s else 0, 0)
+    d = torch.from_numpy(np.frombuffer(bytes(table), np.uint8).copy()).to(ctx.device)
+    keep.append(d)
+    return d, len(images), keep
+
+
+class SurfacePass:
+    """RenderScene's producer of the surface buffer (sailor_hip_surface_*): begin -> draw per DrawIndexed -> resolve -> the shade -> composite.  Owns the
+    workspace (keys and draw descriptors) and the running primBase / drawIndex."""
+
+    def __init__(self, ctx: HipContext, width: int, height: int, band: Band | None = None, max_draws: int = 64):
+        self.ctx, self.W, self.H = ctx, width, height
+        self.band = band if band is not None else host.band_whole_frame(width, height)
+        self.rows = self.band.fbRowCount
+        n = ctx._lib.sailor_hip_surface_workspace_bytes(width, height, C.byref(self.band), max_draws)
+        if n == 0:
+            raise _lib.SailorHipError(-1, "sailor_hip_surface_workspace_bytes")
+        self.workspace = torch.empty(n, dtype=torch.uint8, device=ctx.device)
+        self.prim_base = self.draw_index = 0
+
+    def begin(self, depth: torch.Tensor | None = None, prim_base: int = 0):
+        """depth: the prepass's raw depth of the WHOLE frame, float32 [H, W], or None"""
+        assert depth is None or (depth.dtype == torch.float32 and depth.shape == (self.H, self.W) and depth.is_contiguous())
+        _lib.check(self.ctx._lib.sailor_hip_surface_begin(self.ctx.handle, _ptr(depth), self.W, self.H, C.byref(self.band), _ptr(self.workspace), self.workspace.numel()),
+                   "sailor_hip_surface_begin", self.ctx.handle)
+        self.prim_base, self.draw_index = prim_base, 0
+
+    def draw(self, frame: UboFrameData, vertices: torch.Tensor, indices: torch.Tensor, instances: torch.Tensor, instance_ids: torch.Tensor | None = None,
+             num_drawn: int | None = None, first_instance: int = 0, cull_back: bool = False):
+        """vertices: 72-byte records; indices: int32, 3 per triangle; instances: the 96-byte PerInstanceData SSBO; instance_ids: int32 or None"""
+        if num_drawn is None:
+            num_drawn = instance_ids.numel() if instance_ids is not None else instances.numel() * instances.element_size() // 96 - first_instance
+        nt = indices.numel() // 3
+        d = _lib.SurfaceDraw(_ptr(vertices), _ptr(indices), _ptr(instance_ids), nt, num_drawn, self.prim_base, _lib.SURFACE_CULL_BACK if cull_back else 0,
+                             first_instance, 0)
+        _lib.check(self.ctx._lib.sailor_hip_surface_draw(self.ctx.handle, C.byref(frame), C.byref(d), _ptr(instances), self.draw_index, self.W, self.H,
+                                                         C.byref(self.band), _ptr(self.workspace), self.workspace.numel()), "sailor_hip_surface_draw", self.ctx.handle)
+        self.prim_base += host.surface_draw_prims(nt, num_drawn)
+        self.draw_index += 1
+
+    def resolve(self, frame: UboFrameData, instances: torch.Tensor, materials: torch.Tensor, textures: torch.Tensor, num_textures: int, want_depth: bool = True,
+                want_coverage: bool = True):
+        """-> (surface float32 [3, rows, W, 4], depth float32 [rows, W] | None, coverage uint8 [rows, W] | None)"""
+        dev = self.ctx.device
+        surface = torch.empty((3, self.rows, self.W, 4), dtype=torch.float32, device=dev)
+        depth = torch.empty((self.rows, self.W), dtype=torch.float32, device=dev) if want_depth else None
+        cov = torch.empty((self.rows, self.W), dtype=torch.uint8, device=dev) if want_coverage else None
+        _lib.check(self.ctx._lib.sailor_hip_surface_resolve(self.ctx.handle, C.byref(frame), _ptr(instances), _ptr(materials),
+                                                            materials.numel() * materials.element_size() // 80, _ptr(textures), num_textures, self.W, self.H,
+                                                            C.byref(self.band), _ptr(self.workspace), self.workspace.numel(), _ptr(surface), self.rows * self.W,
+                                                            _ptr(depth), _ptr(cov)), "sailor_hip_surface_resolve", self.ctx.handle)
+        return surface, depth, cov
+
+    def composite(self, radiance: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        """target = covered ? radiance : target; both float32 [rows, W, 4]"""
+        for t in (radiance, target):
+            assert t.dtype == torch.float32 and t.shape == (self.rows, self.W, 4) and t.is_contiguous()
+        _lib.check(self.ctx._lib.sailor_hip_surface_composite(self.ctx.handle, _ptr(radiance), _ptr(self.workspace), self.workspace.numel(), _ptr(target), self.W,
+                                                              self.H, C.byref(self.band)), "sailor_hip_surface_composite", self.ctx.handle)
+        return target
+
+    def download_keys(self) -> np.ndarray:
+        """the keys as uint64 [rows, W]: depth bits << 32 | (order + 1)"""
+        self.ctx.synchronize()
+        at, n = self.ctx._lib.sailor_hip_surface_keys_offset(), self.rows * self.W * 8
+        return self.workspace[at: at + n].cpu().numpy().view(np.uint64).reshape(self.rows, self.W)

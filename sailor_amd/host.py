@@ -429,3 +429,17 @@ def make_csm_desc(lights_matrices: np.ndarray, maps: list) -> CsmDesc:
         d.maps[k] = ptr or None
         d.width[k], d.height[k], d.format[k] = w, h, fmt
     return d
+
+
+def srgb_table() -> np.ndarray:
+    """sailor_host_srgb_table: the sRGB transfer function of the 256 byte values (double, rounded once to fp32)"""
+    out = np.zeros(256, np.float32)
+    _lib.check(_lib.load().sailor_host_srgb_table(_fp(out)), "sailor_host_srgb_table")
+    return out
+
+
+def surface_draw_prims(num_triangles: int, num_drawn: int) -> int:
+    """sailor_hip_surface_draw_prims: what a draw adds to the surface pass's running primBase"""
+    out = C.c_uint64()
+    _lib.check(_lib.load().sailor_hip_surface_draw_prims(num_triangles, num_drawn, C.byref(out)), "sailor_hip_surface_draw_prims")
+    return int(out.value)

@@ -355,6 +355,25 @@ void RenderSceneNode::Process(RHIFrameGraphPtr, RHICommandListPtr, RHICommandLis
     if (!m_pShader) m_pShader = driver->CreateShader("Shaders/Standard.shader");
     auto surface = GetRHIResource("surface").DynamicCast<RHIBuffer>();
     auto radiance = GetRHIResource("radiance").DynamicCast<RHIBuffer>();
+    if (!surface && !sceneView.m_batches.empty()) { // the reference's own recording (RenderSceneNode.cpp): real draws into (color, depthStencil)
+        auto color = GetRHIResource("color").DynamicCast<RHITexture>();
+        auto depth = GetRHIResource("depthStencil").DynamicCast<RHITexture>();
+        if (!color) return;
+        if (!m_pMaterial) m_pMaterial = driver->CreateMaterial(m_pShader);
+        std::string tag;
+        commands->BeginDebugRegion(commandList, std::string(GetName()) + (TryGetString("Tag", tag) ? " QueueTag:" + tag : ""));
+        commands->BeginRenderPass(commandList, TVector<RHITexturePtr> { color }, depth);
+        commands->BindMaterial(commandList, m_pMaterial);
+        commands->BindShaderBindings(commandList, m_pMaterial, { sceneView.m_frameBindings, sceneView.m_rhiLightsData, sceneView.m_sceneBindings });
+        for (const auto& b : sceneView.m_batches) {
+            commands->BindVertexBuffer(commandList, b.m_vertexBuffer, 0);
+            commands->BindIndexBuffer(commandList, b.m_indexBuffer, 0);
+            commands->DrawIndexed(commandList, b.m_indexCount, b.m_instanceCount, b.m_firstIndex, b.m_vertexOffset, b.m_firstInstance);
+        }
+        commands->EndRenderPass(commandList);
+        commands->EndDebugRegion(commandList);
+        return;
+    }
     if (!surface || !radiance) return;
     if (!m_surfaceBindings) {
         m_surfaceBindings = driver->CreateShaderBindings();
@@ -371,6 +390,7 @@ void RenderSceneNode::Process(RHIFrameGraphPtr, RHICommandListPtr, RHICommandLis
 void RenderSceneNode::Clear()
 {
     m_pShader.Clear();
+    m_pMaterial.Clear();
     m_surfaceBindings.Clear();
 }
 

@@ -42,8 +42,10 @@ protected:
 };
 
 // The shading consumer of the lists: RenderSceneNode (FrameGraph/RenderSceneNode.cpp:109) records raster draws whose
-// fragment shader is Standard.shader; here the fragment work is one compute dispatch over a surface buffer
-// (resources "surface" = 3 float4 planes, "radiance" = float4 per pixel).
+// fragment shader is Standard.shader.  With a "surface" resource (3 float4 planes; "radiance" = float4 per pixel) the fragment work is one compute
+// dispatch over that buffer, as before the surface pass existed.  Without one, and with batches in the scene view, the node records the reference's
+// draws: BeginRenderPass("color", "depthStencil"), BindMaterial(Standard), BindShaderBindings, and per batch BindVertexBuffer / BindIndexBuffer /
+// DrawIndexed, EndRenderPass -- the HIP backend rasterises, resolves, shades and composites behind them (sailor_hip_surface_*).
 class RenderSceneNode : public TFrameGraphNode<RenderSceneNode> {
 public:
     static const char* GetName() { return m_name; }
@@ -54,6 +56,7 @@ public:
 protected:
     static const char* m_name;
     RHI::RHIShaderPtr m_pShader;
+    RHI::RHIMaterialPtr m_pMaterial;
     RHI::RHIShaderBindingSetPtr m_surfaceBindings;
 };
 

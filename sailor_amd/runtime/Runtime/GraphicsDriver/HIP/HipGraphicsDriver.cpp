@@ -700,7 +700,8 @@ int HipGraphicsDriver::ExchangeLightLists(RHIBufferPtr bandGrid, RHIBufferPtr ba
 int HipGraphicsDriver::RecordShade(const TVector<RHIShaderBindingSetPtr>& bindings)
 {
     // Standard.shader:180-251: set 0 frame, set 1 lights {0 light, 1 culledLights, 2 lightsGrid, 6 lightsMatrices, 8 shadowMaps},
-    // set 2 the surface/radiance buffers that stand in for the rasterised fragments (per-instance / material / textures sets)
+    // set 2 the surface/radiance buffers: the driver's own planes behind RenderScene's draws (RecordSurfaceEnd: per-instance / material / textures sets resolved
+    // by sailor_hip_surface_resolve), or a caller's buffers that stand in for the rasterised fragments
     if (bindings.size() != 3) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     auto surfaceB = bindings[2]->Find("surface");
     auto countB = bindings[1]->Find("light");
@@ -774,6 +775,92 @@ int HipGraphicsDriver::RecordShade(const TVector<RHIShaderBindingSetPtr>& bindin
                                      prepared ? lightB->m_hipPreparedLights->m_hip.m_devicePtr : nullptr, prepared ? lightB->m_hipPreparedCapacity : 0);
 }
 
+// ---- RenderScene's draws: Standard.shader's vertex stage, the rasteriser and the material half of its fragment stage (sailor_hip_surface_*) ----------------
+#define SURFACE_MAX_DRAWS 4096u
+static RHIBufferPtr scene_buffer(const TVector<RHIShaderBindingSetPtr>& bindings, const char* name)
+{
+    for (auto& set : bindings)
+        if (set) if (auto b = set->Find(name)) if (b->m_buffer) return b->m_buffer;
+    return RHIBufferPtr();
+}
+
+int HipGraphicsDriver::RecordSurfaceDraw(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& color, const RHITexturePtr& depth, const RHIBufferPtr& vertices,
+                                         const RHIBufferPtr& indices, bool first, uint32_t drawIndex, uint32_t indexCount, uint32_t instanceCount, uint32_t firstIndex,
+                                         uint32_t vertexOffset, uint32_t firstInstance)
+{
+    if (first) m_surfaceBegun = false;
+    SailorUboFrameData frame;
+    RHIBufferPtr instances = scene_buffer(bindings, "data");
+    if (bindings.empty() || !host_copy_of(bindings[0], "frameData", frame) || !color || !color->m_buffer || !vertices || !indices || !instances)
+        return SAILOR_HIP_ERR_INVALID_ARGUMENT; // a missing binding
+    if (m_worldSize > 1) return SAILOR_HIP_ERR_UNSUPPORTED; // (the pass runs on whole frames here)
+    const int W = color->GetExtent().x, H = color->GetExtent().y;
+    if (W != frame.viewportSize[0] || H != frame.viewportSize[1] || color->m_format != EFormat::R32G32B32A32_SFLOAT) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (depth && (depth->GetExtent().x != W || depth->GetExtent().y != H || depth->m_format != EFormat::R32_SFLOAT || !depth->m_buffer)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if ((size_t)firstIndex + indexCount > indices->m_size / 4 || ((size_t)firstInstance + instanceCount) * sizeof(SailorPerInstanceData) > instances->m_size ||
+        (size_t)vertexOffset * sizeof(SailorVertexP3N3T3B3UV2C4) > vertices->m_size)
+        return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    SailorBand band;
+    sailor_hip_band_whole_frame(W, H, &band);
+    const size_t bytes = sailor_hip_surface_workspace_bytes(W, H, &band, SURFACE_MAX_DRAWS);
+    if (first) {
+        if (!m_surfaceWorkspace || m_surfaceWorkspace->m_size != bytes) m_surfaceWorkspace = CreateBuffer(bytes);
+        if (!m_surfaceWorkspace) return SAILOR_HIP_ERR_OUT_OF_MEMORY;
+        // BeginRenderPass(Main, DepthBuffer): the keys start from the prepass depth (GreaterOrEqual, RHI/Types.h:536-537)
+        const int st = sailor_hip_surface_begin(m_ctx, depth ? (const float*)depth->m_buffer->m_hip.m_devicePtr : nullptr, W, H, &band, m_surfaceWorkspace->m_hip.m_devicePtr, bytes);
+        if (st != SAILOR_HIP_OK) return st;
+        m_surfacePrimBase = 0;
+        m_surfaceBegun = true;
+    }
+    if (!m_surfaceBegun || !m_surfaceWorkspace || m_surfaceWorkspace->m_size != bytes || m_surfacePrimBase > 0xFFFFFFFFull) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    SailorSurfaceDraw d {};
+    d.dVertices = (const SailorVertexP3N3T3B3UV2C4*)vertices->m_hip.m_devicePtr + vertexOffset;
+    d.dIndices = (const uint32_t*)indices->m_hip.m_devicePtr + firstIndex;
+    d.dInstanceIds = nullptr;
+    d.numTriangles = indexCount / 3; d.numDrawn = instanceCount; d.primBase = (uint32_t)m_surfacePrimBase;
+    d.flags = SAILOR_SURFACE_CULL_BACK; // the reference's materials cull back faces (ECullMode::Back, frontFace counter-clockwise)
+    d.firstInstance = firstInstance;
+    const int st = sailor_hip_surface_draw(m_ctx, &frame, &d, (const SailorPerInstanceData*)instances->m_hip.m_devicePtr, drawIndex, W, H, &band,
+                                           m_surfaceWorkspace->m_hip.m_devicePtr, bytes);
+    if (st != SAILOR_HIP_OK) { m_surfaceBegun = false; return st; }
+    uint64_t prims = 0;
+    sailor_hip_surface_draw_prims(d.numTriangles, d.numDrawn, &prims);
+    m_surfacePrimBase += prims;
+    return SAILOR_HIP_OK;
+}
+
+int HipGraphicsDriver::RecordSurfaceEnd(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& color)
+{
+    if (!m_surfaceBegun) return SAILOR_HIP_ERR_INVALID_ARGUMENT; // a draw of the pass was refused: nothing to resolve
+    m_surfaceBegun = false;
+    SailorUboFrameData frame;
+    RHIBufferPtr instances = scene_buffer(bindings, "data"), materials = scene_buffer(bindings, "material"), textures = scene_buffer(bindings, "textureSamplers");
+    if (bindings.size() < 2 || !host_copy_of(bindings[0], "frameData", frame) || !color || !color->m_buffer || !instances || !materials || !textures)
+        return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    const int W = color->GetExtent().x, H = color->GetExtent().y;
+    SailorBand band;
+    sailor_hip_band_whole_frame(W, H, &band);
+    const size_t pixels = (size_t)W * H, bytes = m_surfaceWorkspace->m_size;
+    if (!m_surfacePlanes || m_surfacePlanes->m_size != pixels * 48) m_surfacePlanes = CreateBuffer(pixels * 48);
+    if (!m_surfaceRadiance || m_surfaceRadiance->m_size != pixels * 16) m_surfaceRadiance = CreateBuffer(pixels * 16);
+    if (!m_surfacePlanes || !m_surfaceRadiance) return SAILOR_HIP_ERR_OUT_OF_MEMORY;
+    int st = sailor_hip_surface_resolve(m_ctx, &frame, (const SailorPerInstanceData*)instances->m_hip.m_devicePtr, (const SailorMaterialData*)materials->m_hip.m_devicePtr,
+                                        (uint32_t)(materials->m_size / sizeof(SailorMaterialData)), (const SailorTextureDesc*)textures->m_hip.m_devicePtr,
+                                        (uint32_t)(textures->m_size / sizeof(SailorTextureDesc)), W, H, &band, m_surfaceWorkspace->m_hip.m_devicePtr, bytes,
+                                        (float*)m_surfacePlanes->m_hip.m_devicePtr, pixels, nullptr, nullptr);
+    if (st != SAILOR_HIP_OK) return st;
+    // the rest of the fragment stage: the shade over the planes, exactly as over a caller's surface
+    auto own = RHIShaderBindingSetPtr::Make();
+    own->GetOrAddShaderBinding("surface")->m_buffer = m_surfacePlanes;
+    own->GetOrAddShaderBinding("radiance")->m_buffer = m_surfaceRadiance;
+    if (!bindings[1]) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    st = RecordShade({ bindings[0], bindings[1], own });
+    if (st != SAILOR_HIP_OK) return st;
+    BeforeBufferWrite(color->m_buffer->m_hip.m_devicePtr);
+    return sailor_hip_surface_composite(m_ctx, (const float*)m_surfaceRadiance->m_hip.m_devicePtr, m_surfaceWorkspace->m_hip.m_devicePtr, bytes,
+                                        (float*)color->m_buffer->m_hip.m_devicePtr, W, H, &band);
+}
+
 // ---- the render-pass subset: state is kept on the command list, a 6-index draw of a known full-screen material becomes a
 // kernel launch at submit time (record-then-submit, like Dispatch) ---------------------------------------------------------------
 void HipGraphicsDriver::BeginRenderPass(RHICommandListPtr cmd, const TVector<RHITexturePtr>& colorAttachments, RHITexturePtr depthStencilAttachment)
@@ -781,6 +868,7 @@ void HipGraphicsDriver::BeginRenderPass(RHICommandListPtr cmd, const TVector<RHI
     cmd->m_colorAttachments = colorAttachments;
     cmd->m_depthAttachment = depthStencilAttachment;
     cmd->m_casterDraws = 0;
+    cmd->m_surfaceDraws = 0;
 }
 
 void HipGraphicsDriver::BindVertexBuffer(RHICommandListPtr cmd, RHIBufferPtr vertexBuffer, uint32_t) { cmd->m_vertexBuffer = vertexBuffer; }
@@ -803,8 +891,14 @@ void HipGraphicsDriver::EndRenderPass(RHICommandListPtr cmd)
                                              color->m_buffer->m_hip.m_devicePtr);
         });
     }
+    if (cmd->m_surfaceDraws > 0) { // RenderScene's pass: the fragment stage of every pixel's winning fragment, then the colour writes
+        RHITexturePtr color = cmd->m_colorAttachments.empty() ? RHITexturePtr() : cmd->m_colorAttachments[0];
+        TVector<RHIShaderBindingSetPtr> bindings = cmd->m_boundBindings;
+        cmd->m_hip.m_commands.push_back([this, bindings, color]() { return RecordSurfaceEnd(bindings, color); });
+    }
     cmd->m_depthAttachment.Clear();
     cmd->m_casterDraws = 0;
+    cmd->m_surfaceDraws = 0;
     cmd->m_colorAttachments.clear();
     cmd->m_boundMaterial.Clear();
     cmd->m_boundBindings.clear();
@@ -847,6 +941,16 @@ void HipGraphicsDriver::DrawIndexed(RHICommandListPtr cmd, uint32_t indexCount, 
                                            (const float*)instances->m_hip.m_devicePtr + 16 * (size_t)firstInstance, nullptr, instanceCount, depth->GetExtent().x,
                                            depth->GetExtent().y, (float*)depth->m_buffer->m_hip.m_devicePtr, (first ? SAILOR_RASTER_CLEAR : 0u) | SAILOR_RASTER_CULL_BACK,
                                            ws ? (uint32_t*)ws->m_hip.m_devicePtr : nullptr);
+        });
+        return;
+    }
+    if (name == "Shaders/Standard.shader") { // a batch of RenderSceneNode (RenderSceneNode.cpp via RHIRecordDrawCall, RHI/Batch.hpp)
+        RHITexturePtr color = cmd->m_colorAttachments.empty() ? RHITexturePtr() : cmd->m_colorAttachments[0], depth = cmd->m_depthAttachment;
+        RHIBufferPtr vb = cmd->m_vertexBuffer, ib = cmd->m_indexBuffer;
+        TVector<RHIShaderBindingSetPtr> bindings = cmd->m_boundBindings;
+        const uint32_t drawIndex = cmd->m_surfaceDraws++;
+        cmd->m_hip.m_commands.push_back([this, bindings, color, depth, vb, ib, drawIndex, indexCount, instanceCount, firstIndex, vertexOffset, firstInstance]() {
+            return RecordSurfaceDraw(bindings, color, depth, vb, ib, drawIndex == 0, drawIndex, indexCount, instanceCount, firstIndex, vertexOffset, firstInstance);
         });
         return;
     }

@@ -41,6 +41,8 @@
 // a scaled one-channel BlitImage with Nearest filtration -> sailor_hip_blit_nearest
 // a scaled RGBA32F or one-channel BlitImage with Linear filtration -> sailor_hip_blit_linear
 // and the depth-only instanced draws of the shadow passes (material of)
+//   "Shaders/Standard.shader" drawn with DrawIndexed (RenderSceneNode's batches) -> sailor_hip_surface_begin at the pass's first such draw, sailor_hip_surface_draw
+//       per draw, and at EndRenderPass sailor_hip_surface_resolve -> the shade over driver-owned planes -> sailor_hip_surface_composite into the colour attachment
 //   "Shaders/ShadowCaster.shader" [EVSM]  -> sailor_hip_raster_depth into the pass' depth attachment, and at EndRenderPass sailor_hip_shadow_resolve
 //                                            into its colour attachment (push constant lightMatrix, set 1 `data`, vertex positions, 32-bit indices)
 #pragma once
@@ -140,6 +142,10 @@ public:
 private:
     int RecordLightCulling(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const TVector<uint8_t>& pc);
     int RecordShade(const TVector<RHI::RHIShaderBindingSetPtr>& bindings);
+    int RecordSurfaceDraw(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& color, const RHI::RHITexturePtr& depth,
+                          const RHI::RHIBufferPtr& vertices, const RHI::RHIBufferPtr& indices, bool first, uint32_t drawIndex, uint32_t indexCount,
+                          uint32_t instanceCount, uint32_t firstIndex, uint32_t vertexOffset, uint32_t firstInstance);
+    int RecordSurfaceEnd(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& color);
     int RecordBrdfLut(const TVector<RHI::RHIShaderBindingSetPtr>& bindings);
     int RecordIrradianceMap(const TVector<RHI::RHIShaderBindingSetPtr>& bindings);
     int RecordEnvPrefilter(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const TVector<uint8_t>& pc);
@@ -176,6 +182,11 @@ private:
     RHI::RHIBufferPtr m_cullWorkspace;
     RHI::RHIBufferPtr m_starsWorkspace; // the star draw's per-star pixels and fragments (sailor_hip_sky_stars_workspace_bytes), grown when a larger mesh is drawn
     RHI::RHIBufferPtr m_meshCullWorkspace;
+    // the surface pass of the render pass being executed (Standard.shader draws): workspace (keys, descriptors), the planes the resolve writes and the shade
+    // reads, the shade's radiance; the running primBase; begun = the first draw's sailor_hip_surface_begin went through
+    RHI::RHIBufferPtr m_surfaceWorkspace, m_surfacePlanes, m_surfaceRadiance;
+    uint64_t m_surfacePrimBase = 0;
+    bool m_surfaceBegun = false;
     int32_t m_cullW = 0, m_cullH = 0, m_cullLights = 0; // geometry of the last light cull: locates its shading-order hint in the workspace
     bool m_cullOrderValid = false;
     std::map<const void*, RHI::RHIBufferPtr> m_rasterWorkspaces; // depth attachment -> the rasteriser's workspace (coarse depth, mesh box, giants' queue)

@@ -9,12 +9,22 @@ struct CameraData { // ECS/CameraECS.h: what the nodes read from sceneView.m_cam
     float m_fov = 90.0f, m_aspect = 1.0f, m_zNear = 1.0f, m_zFar = 20000.0f;
 };
 
+// One batch of RHISceneViewProxy / RHIRecordDrawCall (RHI/Batch.hpp) as RenderSceneNode.cpp draws it: a mesh's buffers and the arguments of its DrawIndexed
+struct RHISceneBatch {
+    RHIBufferPtr m_vertexBuffer, m_indexBuffer; // VertexP3N3T3B3UV2C4 records; uint32 indices
+    uint32_t m_indexCount = 0, m_instanceCount = 0, m_firstIndex = 0, m_vertexOffset = 0, m_firstInstance = 0;
+};
+
 struct RHISceneViewSnapshot {
     CameraData m_camera;
     float m_deltaTime = 0.0f, m_currentTime = 0.0f;
     uint32_t m_totalNumLights = 0;           // RHI/SceneView.h:75, filled at ECS/LightingECS.cpp:404
     RHIShaderBindingSetPtr m_frameBindings;  // :78, filled by RHIFrameGraph::FillFrameData
     RHIShaderBindingSetPtr m_rhiLightsData;  // :79, LightingECS::m_lightsData (binding 0 `light`, 6 `lightsMatrices`, 8 `shadowMaps`)
+    // what RenderSceneNode.cpp draws: the batches of the view, and Standard.shader's sets 2-4 as one set -- `data` (PerInstanceDataSSBO), `material`
+    // (MaterialDataSSBO), `textureSamplers` (a device table of SailorTextureDesc)
+    TVector<RHISceneBatch> m_batches;
+    RHIShaderBindingSetPtr m_sceneBindings;
 };
 
 } // namespace Sailor::RHI

@@ -184,6 +184,7 @@ public:
     TRefPtr<class RHIBuffer> m_vertexBuffer, m_indexBuffer;   // BindVertexBuffer / BindIndexBuffer
     TVector<uint8_t> m_pushConstants;                          // PushConstants(material, size, ptr)
     uint32_t m_casterDraws = 0;                                // depth-only draws recorded in the current pass (the first one clears)
+    uint32_t m_surfaceDraws = 0;                               // Standard.shader draws recorded in the current pass (the first one begins the surface pass)
     TRefPtr<class RHIMaterial> m_boundMaterial;
     TVector<TRefPtr<class RHIShaderBindingSet>> m_boundBindings;
 };

@@ -387,6 +387,41 @@ RT_API void sailor_rt_set_surface(SailorRuntime* rt, void* surfaceDevicePtr, voi
     if (rt->renderScene) { rt->renderScene->SetRHIResource("surface", rt->surface); rt->renderScene->SetRHIResource("radiance", rt->radiance); }
 }
 
+// The scene RenderScene draws when it has no "surface" resource (RHISceneViewSnapshot::m_batches / m_sceneBindings): one vertex and one index buffer shared by
+// the batches (as a mesh pool is), the per-instance, material and texture-descriptor SSBOs (a null pointer leaves that binding out), and the batches as host
+// records {indexCount, instanceCount, firstIndex, vertexOffset, firstInstance}.  numBatches = 0 clears the scene.
+RT_API int sailor_rt_set_scene(SailorRuntime* rt, void* vertices, uint32_t numVertices, void* indices, uint32_t numIndices, void* instances, uint32_t numInstances,
+                               void* materials, uint32_t numMaterials, void* textures, uint32_t numTextures, const uint32_t* batches, int numBatches)
+{
+    if (!rt || numBatches < 0 || (numBatches > 0 && !batches)) return -1;
+    auto* hip = static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver());
+    rt->snapshot.m_batches.clear();
+    rt->snapshot.m_sceneBindings = Renderer::GetDriver()->CreateShaderBindings();
+    if (instances) rt->snapshot.m_sceneBindings->GetOrAddShaderBinding("data")->m_buffer = hip->WrapBuffer(instances, (size_t)numInstances * sizeof(SailorPerInstanceData));
+    if (materials) rt->snapshot.m_sceneBindings->GetOrAddShaderBinding("material")->m_buffer = hip->WrapBuffer(materials, (size_t)numMaterials * sizeof(SailorMaterialData));
+    if (textures) rt->snapshot.m_sceneBindings->GetOrAddShaderBinding("textureSamplers")->m_buffer = hip->WrapBuffer(textures, (size_t)numTextures * sizeof(SailorTextureDesc));
+    RHIBufferPtr vb = vertices ? hip->WrapBuffer(vertices, (size_t)numVertices * sizeof(SailorVertexP3N3T3B3UV2C4)) : RHIBufferPtr();
+    RHIBufferPtr ib = indices ? hip->WrapBuffer(indices, (size_t)numIndices * 4) : RHIBufferPtr();
+    for (int i = 0; i < numBatches; i++) {
+        RHISceneBatch b;
+        b.m_vertexBuffer = vb; b.m_indexBuffer = ib;
+        b.m_indexCount = batches[5 * i]; b.m_instanceCount = batches[5 * i + 1]; b.m_firstIndex = batches[5 * i + 2]; b.m_vertexOffset = batches[5 * i + 3];
+        b.m_firstInstance = batches[5 * i + 4];
+        rt->snapshot.m_batches.push_back(b);
+    }
+    return 0;
+}
+
+// RenderScene's attachments for those draws: "color" (RGBA32F, e.g. Main) and "depthStencil" (the raw R32F DepthBuffer of the prepass, or null)
+RT_API int sailor_rt_set_scene_targets(SailorRuntime* rt, void* color, void* depth, int width, int height)
+{
+    if (!rt || !rt->renderScene || !color) return -1;
+    auto* hip = static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver());
+    rt->renderScene->SetRHIResource("color", hip->WrapTexture(color, { width, height }, EFormat::R32G32B32A32_SFLOAT));
+    if (depth) rt->renderScene->SetRHIResource("depthStencil", hip->WrapTexture(depth, { width, height }, EFormat::R32_SFLOAT));
+    return 0;
+}
+
 RT_API void sailor_rt_set_shadow_maps(SailorRuntime* rt, void* const* mapDevicePtrs, const int* sizes, const int* formats, const float* lightsMatrices64)
 {
     auto* hip = static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver());

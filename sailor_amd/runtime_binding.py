@@ -70,6 +70,8 @@ def load() -> C.CDLL:
         rt.sailor_rt_eye_adaptation_state.argtypes = [P, C.POINTER(P), C.POINTER(P)]
         rt.sailor_rt_shadow_pass.argtypes = [P, C.POINTER(C.c_float), P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, C.c_uint32, P, C.c_int, C.c_int, C.c_float, C.c_float]
         rt.sailor_rt_gpu_culling.argtypes = [P, P, C.c_uint32, C.c_uint32, P, C.c_uint32]
+        rt.sailor_rt_set_scene.argtypes = [P, P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, P, C.c_int]
+        rt.sailor_rt_set_scene_targets.argtypes = [P, P, P, C.c_int, C.c_int]
         rt.sailor_rt_process_frame.argtypes = [P]
         rt.sailor_rt_process_frame_overwriting_lists.argtypes = [P, P, C.c_size_t, P, C.c_size_t]
         rt.sailor_rt_set_frame_split.argtypes = [P, C.c_int, C.c_int, P]
@@ -330,6 +332,22 @@ class Runtime:
 
     def set_surface(self, surface_tensor, radiance_tensor):
         self.rt.sailor_rt_set_surface(self.h, surface_tensor.data_ptr(), radiance_tensor.data_ptr(), surface_tensor.shape[2], surface_tensor.shape[1])
+
+    def set_scene(self, vertices, indices, instances, materials, textures, num_textures: int, batches):
+        """what RenderScene draws without a `surface` resource: device tensors of 72-byte vertices, int32 indices, 96-byte instances, 80-byte materials and
+        the SailorTextureDesc table (any of the last three None = that binding missing), and batches uint32 [n, 5] = indexCount, instanceCount, firstIndex,
+        vertexOffset, firstInstance"""
+        nbytes = lambda t: t.numel() * t.element_size()
+        b = np.ascontiguousarray(batches, np.uint32).reshape(-1, 5)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _lib.check(self.rt.sailor_rt_set_scene(self.h, ptr(vertices), nbytes(vertices) // 72, ptr(indices), indices.numel(), ptr(instances),
+                                               0 if instances is None else nbytes(instances) // 96, ptr(materials), 0 if materials is None else nbytes(materials) // 80,
+                                               ptr(textures), num_textures, b.ctypes.data, len(b)), "sailor_rt_set_scene")
+
+    def set_scene_targets(self, color, depth=None):
+        """RenderScene's colour attachment (float32 [H, W, 4]) and the prepass's raw depth (float32 [H, W]) or None"""
+        _lib.check(self.rt.sailor_rt_set_scene_targets(self.h, color.data_ptr(), None if depth is None else depth.data_ptr(), color.shape[1], color.shape[0]),
+                   "sailor_rt_set_scene_targets")
 
     def set_shadow_maps(self, map_tensors, formats, lights_matrices):
         ptrs = (C.c_void_p * 4)(*[t.data_ptr() for t in map_tensors])
