@@ -1179,7 +1179,7 @@ SAILOR_HIP_API int sailor_host_csm_plan_passes(SailorCsmSnapshots* snapshots, ui
                                                const uint64_t* overlapMasks, const uint32_t* shadowTypes, const uint64_t* lastChangedFrame,
                                                const SailorCsmView* view, uint32_t* outRender, uint64_t* outMasks);
 
-/* ---- RenderScene: the surface pass (surface.hip) ---------------------------------------------------------------------------------------------
+/* ---- RenderScene: the surface pass (surface.hip; the Masked queue: surface_masked.hip, below) ---------------------------------------------------------------------------------------------
  * Replaces: the vertex stage of Content/Shaders/Standard.shader:126-139, the rasteriser between the stages and the material half of its fragment
  * stage (:379-389, :438) for the draws of FrameGraph/RenderSceneNode.cpp -- it PRODUCES the three planes sailor_hip_shade* consume.
  * The rasterisation rules are the depth prepass's (sailor_hip_raster_depth_camera: near-plane cut, 1/256-pixel snapping, 64-bit edge functions,
@@ -1190,7 +1190,7 @@ SAILOR_HIP_API int sailor_host_csm_plan_passes(SailorCsmSnapshots* snapshots, ui
  * triangle the near plane cut in two); low word 0 = no primitive.  Varyings are perspective-correct: l_k = float(e_k) / area, q_k = l_k / w_k,
  * s = (q0 + q1) + q2, b_k = q_k / s, a = (a0 b0 + a1 b1) + a2 b2; a vertex cut on the near plane gets a = aI + (aO - aI) t with the position's t.
  * texture() is the base level, bilinear, Repeat over RGBA8 texels; SAILOR_TEXTURE_SRGB decodes r, g, b per tap through sailor_host_srgb_table before
- * filtering.  NOT reproduced: the implicit mip selection of texture() (textures have one level here), anisotropy, ALPHA_CUTOUT / the Masked tag,
+ * filtering.  NOT reproduced: the implicit mip selection of texture() (textures have one level here), anisotropy,
  * Standard_glTF.shader.  A sampler index >= numTextures reads descriptor 0 (the reference binds g_defaultSampler there), a materialInstance >=
  * numMaterials reads material 0, a descriptor without texels samples as 0: no fetch leaves a table.
  * All entry points record only (no allocation, no synchronisation, capturable); a refused call launches nothing and leaves a text in last_error. */
@@ -1233,6 +1233,7 @@ typedef struct SailorTextureDesc {
 /* one DrawIndexed of RenderSceneNode.cpp (BindVertexBuffer / BindIndexBuffer / DrawIndexed): the draw kernel stores it into slot drawIndex of the
  * workspace, from where the resolve finds a key's draw by its primBase.  Slots are used in rising order with rising primBase. */
 #define SAILOR_SURFACE_CULL_BACK 1u /* ECullMode::Back, frontFace counter-clockwise, as SAILOR_RASTER_CULL_BACK */
+#define SAILOR_SURFACE_ALPHA_CUTOUT 2u /* the ALPHA_CUTOUT permutation of Standard.shader: sailor_hip_surface_draw_masked only, sailor_hip_surface_draw refuses it */
 typedef struct SailorSurfaceDraw {
     const SailorVertexP3N3T3B3UV2C4* dVertices; /* device, already offset by vertexOffset */
     const uint32_t* dIndices;                   /* device, 3 x numTriangles, already offset by firstIndex */
@@ -1240,7 +1241,7 @@ typedef struct SailorSurfaceDraw {
     uint32_t numTriangles;
     uint32_t numDrawn;
     uint32_t primBase;                          /* the order of the draw's first primitive: the previous draw's primBase + its sailor_hip_surface_draw_prims */
-    uint32_t flags;                             /* SAILOR_SURFACE_CULL_BACK */
+    uint32_t flags;                             /* SAILOR_SURFACE_CULL_BACK; SAILOR_SURFACE_ALPHA_CUTOUT through sailor_hip_surface_draw_masked only */
     uint32_t firstInstance;
     uint32_t _pad;
 } SailorSurfaceDraw;
@@ -1273,6 +1274,40 @@ SAILOR_HIP_API int sailor_hip_surface_composite(SailorHipContext* ctx, const flo
 SAILOR_HIP_API int sailor_host_srgb_table(float out[256]);
 /* numDrawn * 2 * numTriangles (saturating at 2^64 - 1): what a draw adds to the running primBase.  sailor_hip_surface_draw refuses a draw whose primBase + this reaches 2^32 - 1. */
 SAILOR_HIP_API int sailor_hip_surface_draw_prims(uint32_t numTriangles, uint32_t numDrawn, uint64_t* out);
+
+/* ---- The Masked render queue: ALPHA_CUTOUT in the surface pass (surface_masked.hip) ----------------------------------------------------------
+ * Replaces: the `Tag: Masked` draws of FrameGraph/RenderSceneNode.cpp and of FrameGraph/DepthPrepassNode.cpp.  A glTF material with alphaMode == "MASK"
+ * (AssetRegistry/Model/ModelImporter.cpp:213-229) gets the render queue Masked, the define ALPHA_CUTOUT and IsRequiredCustomDepthShader() == true; a
+ * material that requires a custom depth shader is its own depth material (DepthPrepassNode.cpp:86-90, :107-115, :246-255), so the Masked prepass runs
+ * Standard.shader with ALPHA_CUTOUT against no colour attachment, and a discarded fragment writes no depth.  RenderSceneNode.cpp applies the same tag
+ * filter with colour and depth writes.  Standard.shader:383 `material.albedo = material.albedo * texture(textureSamplers[material.albedoSampler],
+ * vin.texcoord) * vin.color`, :403-408 `if (material.albedo.a < 0.5) discard;`.
+ * Pinned:
+ *  1. The tested value is alpha = (mat.albedo[3] * tA.w) * a[8], in exactly the operation order of k_surface_resolve.  tA.w is the bilinear Repeat
+ *     fetch of the albedo sampler's alpha (never sRGB-decoded); a[8] is the perspective-correct vertex colour alpha; a[0], a[1] (the texcoord) and a[8]
+ *     are interpolated by the formula above: l_k = float(e_k) / area, q_k = l_k / w_k, s = (q0 + q1) + q2, b_k = q_k / s, a = (a0 b0 + a1 b1) + a2 b2; a
+ *     vertex cut on the near plane is aI + (aO - aI) t.  So at every pixel a cutout draw owns, the resolve's P0.w is, bit for bit, the alpha the draw tested.
+ *  2. A fragment is discarded iff alpha < 0.5f.  A NaN alpha survives, as in GLSL.
+ *  3. The look-up rules of the resolve hold for the alpha fetch: a materialInstance >= numMaterials reads material 0, a sampler index >= numTextures reads
+ *     descriptor 0, a descriptor without texels samples 0 (so everything finite is discarded).
+ *  4. A discarded fragment does not exist: it writes no key and no depth and takes no part in ties.  Discard is a pure function of the fragment, so the
+ *     keys stay order-free; the decision is taken in the draw, before the key is issued (exact inside test and z -> plain load of the pixel's key -> alpha
+ *     only if the key would win -> atomicMax only for a survivor).  sailor_hip_surface_resolve, _composite and sailor_hip_surface_draw are unchanged.
+ *  5. NOT reproduced: Standard_glTF.shader (alphaCutoff as a material field: the threshold here is the constant 0.5), the Transparent queue, masked shadow
+ *     casters, and a DepthPrepass node in the runtime mirror (a Masked prepass is begin(opaque depth), the masked draws, sailor_hip_surface_store_depth).
+ * Both entry points record only; a refused call launches nothing and leaves its text in last_error. */
+
+/* Replaces: one DrawIndexed of a material with or without ALPHA_CUTOUT: k_surface_visibility_masked.  The checks and refusals of sailor_hip_surface_draw;
+ * flags may also hold SAILOR_SURFACE_ALPHA_CUTOUT, which requires dMaterials / dTextures (the tables sailor_hip_surface_resolve gets) to be present.  Without
+ * the flag the keys are sailor_hip_surface_draw's and the tables are not read. */
+SAILOR_HIP_API int sailor_hip_surface_draw_masked(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSurfaceDraw* draw,
+                                                  const SailorPerInstanceData* dInstances, const SailorMaterialData* dMaterials, uint32_t numMaterials,
+                                                  const SailorTextureDesc* dTextures, uint32_t numTextures, uint32_t drawIndex, int32_t width, int32_t height,
+                                                  const SailorBand* band, void* dWorkspace, size_t workspaceBytes);
+/* Replaces: the depth writes of a pass that held cutout draws (a Masked DepthPrepass; a z-writing RenderScene pass): k_surface_store_depth writes the
+ * high word of every key of the band into the band's rows of dDepth, the raw width x height depth attachment of the WHOLE frame. */
+SAILOR_HIP_API int sailor_hip_surface_store_depth(SailorHipContext* ctx, const void* dWorkspace, size_t workspaceBytes, float* dDepth, int32_t width,
+                                                  int32_t height, const SailorBand* band);
 
 #ifdef __cplusplus
 }

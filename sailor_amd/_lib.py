@@ -217,6 +217,7 @@ class SurfaceDraw(C.Structure):  # include/sailor_hip.h SailorSurfaceDraw: one D
 
 TEXTURE_SRGB = 1        # SAILOR_TEXTURE_SRGB
 SURFACE_CULL_BACK = 1   # SAILOR_SURFACE_CULL_BACK
+SURFACE_ALPHA_CUTOUT = 2  # SAILOR_SURFACE_ALPHA_CUTOUT (sailor_hip_surface_draw_masked only)
 # the same records as NumPy dtypes (what the tests and upload helpers build)
 VERTEX_DTYPE = [("texcoord", "<f4", 2), ("position", "<f4", 3), ("normal", "<f4", 3), ("tangent", "<f4", 3), ("bitangent", "<f4", 3), ("color", "<f4", 4)]
 MATERIAL_DTYPE = [("albedo", "<f4", 4), ("ambient", "<f4", 4), ("emission", "<f4", 4), ("metallic", "<f4"), ("roughness", "<f4"), ("ao", "<f4"),
@@ -393,6 +394,9 @@ SIGNATURES = {
     "sailor_hip_surface_resolve": (C.c_int, [_P, C.POINTER(UboFrameData), _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, C.c_int32, C.POINTER(Band), _P, C.c_size_t,
                                              _P, C.c_size_t, _P, _P]),
     "sailor_hip_surface_composite": (C.c_int, [_P, _P, _P, C.c_size_t, _P, C.c_int32, C.c_int32, C.POINTER(Band)]),
+    "sailor_hip_surface_draw_masked": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(SurfaceDraw), _P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32,
+                                                 C.POINTER(Band), _P, C.c_size_t]),
+    "sailor_hip_surface_store_depth": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_int32, C.c_int32, C.POINTER(Band)]),
     "sailor_hip_surface_keys_offset": (C.c_size_t, []),
     "sailor_host_srgb_table": (C.c_int, [C.POINTER(C.c_float)]),
     "sailor_hip_surface_draw_prims": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),

@@ -12,169 +12,11 @@
 //   k_surface_composite   target = covered ? radiance : target
 //
 // The depth of a fragment and everything in front of it (clip, cut, snap, edges, top-left) are raster.hip's, so that the depth is the prepass's bit for
-// bit.  raster.hip keeps its set-up functions static and reads tightly packed positions; the few of them needed here are COPIED below (surf_cut,
-// surf_floor_div256, surf_edge, surf_top_left, and surface_setup = raster_setup over interleaved vertices that also reports where each vertex came from).
-#include "common.h"
-#include "sampling.h"
-#include "texel_pass.h"
-#include <math.h>
+// bit.  raster.hip keeps its set-up functions static and reads tightly packed positions; the few of them needed here are COPIED in surface_common.h
+// (surf_cut, surf_floor_div256, surf_edge, surf_top_left, and surface_setup = raster_setup over interleaved vertices that also reports where each vertex came
+// from), which this file shares with surface_masked.hip (the Masked queue: ALPHA_CUTOUT in the draw).
+#include "surface_common.h"
 
-#define SURF_SMALL_BOX 64   // pixels a lane fills on its own
-#define SURF_VERTEX_FLOATS 18
-#define SURF_INSTANCE_FLOATS 24
-#define SURF_HEADER_BYTES 64
-#define SURF_TABLE_BYTES 1024
-#define SURF_MAX_DRAWS (1u << 20)
-#define SURF_SLICE_LANES 262144ull
-#define SURF_SLICES_MAX 256ull
-
-struct SurfHeader { uint32_t maxDraws, rows, width, fbRowBegin; uint32_t pad[12]; };
-struct SurfSrgb { float v[256]; };
-
-struct SurfTri { long long x0, y0, x1, y1, x2, y2; float z0, z1, z2; int i0, i1, j0, j1; bool valid; };
-// where the three vertices of a set-up triangle came from: vertex k is source vertex I[k], or -- cut[k] -- the point I[k] + (O[k] - I[k]) * t[k] of an
-// edge the near plane cut; w[k] is its clip w
-struct SurfSrc { uint32_t I[3], O[3]; float t[3], w[3]; bool cut[3]; };
-
-// ---- copied from raster.hip (static there) --------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ long long surf_floor_div256(long long a) { return a >= 0 ? a / 256 : -((-a + 255) / 256); }
-__device__ __forceinline__ float4 surf_cut(const float4& I, float dI, const float4& O, float dO, float& t)
-{
-    t = dI / (dI - dO);
-    return make_float4(I.x + (O.x - I.x) * t, I.y + (O.y - I.y) * t, I.z + (O.z - I.z) * t, I.w + (O.w - I.w) * t);
-}
-__device__ __forceinline__ long long surf_edge(long long ax, long long ay, long long bx, long long by, long long px, long long py)
-{
-    return (bx - ax) * (py - ay) - (by - ay) * (px - ax);
-}
-__device__ __forceinline__ bool surf_top_left(long long ax, long long ay, long long bx, long long by)
-{
-    const long long dx = bx - ax, dy = by - ay;
-    return (dy == 0 && dx > 0) || dy < 0;
-}
-
-// raster_setup of raster.hip (hasView form: clip = projection * (view * (model * position)), DepthOnly.shader:51 == Standard.shader:131) over interleaved
-// vertices; rows [rowBegin, rowEnd) of the frame only.  S reports the vertices' sources for the varyings (dead code where it is not read).
-__device__ __forceinline__ SurfTri surface_setup(const Mat4& P, const Mat4& V, const float* __restrict__ model, const float* __restrict__ vertices,
-                                                 const uint32_t* __restrict__ tri, int W, int H, int rowBegin, int rowEnd, bool cullBack, int part, bool& hasSecond,
-                                                 SurfSrc& S)
-{
-    SurfTri t;
-    t.valid = false;
-    hasSecond = false;
-    float4 c[3];
-    const uint32_t v0 = tri[0], v1 = tri[1], v2 = tri[2];
-    Mat4 M;
-#pragma unroll
-    for (int q = 0; q < 16; q++) M.m[q] = model[q];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const float* p = vertices + SURF_VERTEX_FLOATS * (size_t)(k == 0 ? v0 : (k == 1 ? v1 : v2)) + 2;
-        const float4 a = glsl_mul(M, p[0], p[1], p[2], 1.0f);
-        const float4 bq = glsl_mul(V, a.x, a.y, a.z, a.w);
-        c[k] = glsl_mul(P, bq.x, bq.y, bq.z, bq.w);
-    }
-    S.I[0] = v0; S.I[1] = v1; S.I[2] = v2;
-    S.O[0] = v0; S.O[1] = v1; S.O[2] = v2;
-    S.t[0] = S.t[1] = S.t[2] = 0.0f;
-    S.cut[0] = S.cut[1] = S.cut[2] = false;
-    const float d0 = c[0].w - c[0].z, d1 = c[1].w - c[1].z, d2 = c[2].w - c[2].z;
-    const int mask = (d0 >= 0.0f ? 1 : 0) | (d1 >= 0.0f ? 2 : 0) | (d2 >= 0.0f ? 4 : 0);
-    if (mask == 0) return t;
-    if (mask != 7) {
-        const bool one = (mask & (mask - 1)) == 0;
-        const int r = one ? (mask == 1 ? 0 : (mask == 2 ? 1 : 2)) : (mask == 6 ? 1 : (mask == 5 ? 2 : 0)); // the rotation that brings A to the front
-        const float4 A = r == 0 ? c[0] : (r == 1 ? c[1] : c[2]), B = r == 0 ? c[1] : (r == 1 ? c[2] : c[0]), C = r == 0 ? c[2] : (r == 1 ? c[0] : c[1]);
-        const float dA = r == 0 ? d0 : (r == 1 ? d1 : d2), dB = r == 0 ? d1 : (r == 1 ? d2 : d0), dC = r == 0 ? d2 : (r == 1 ? d0 : d1);
-        const uint32_t iA = r == 0 ? v0 : (r == 1 ? v1 : v2), iB = r == 0 ? v1 : (r == 1 ? v2 : v0), iC = r == 0 ? v2 : (r == 1 ? v0 : v1);
-        S.I[0] = iA; S.O[0] = iA;
-        if (one) {
-            if (part) return t;
-            c[0] = A; c[1] = surf_cut(A, dA, B, dB, S.t[1]); c[2] = surf_cut(A, dA, C, dC, S.t[2]);
-            S.I[1] = iA; S.O[1] = iB; S.cut[1] = true;
-            S.I[2] = iA; S.O[2] = iC; S.cut[2] = true;
-        } else {
-            float tBC;
-            const float4 BC = surf_cut(B, dB, C, dC, tBC);
-            hasSecond = true;
-            c[0] = A;
-            if (part == 0) {
-                c[1] = B; c[2] = BC;
-                S.I[1] = iB; S.O[1] = iB;
-                S.I[2] = iB; S.O[2] = iC; S.t[2] = tBC; S.cut[2] = true;
-            } else {
-                c[1] = BC; c[2] = surf_cut(A, dA, C, dC, S.t[2]);
-                S.I[1] = iB; S.O[1] = iC; S.t[1] = tBC; S.cut[1] = true;
-                S.I[2] = iA; S.O[2] = iC; S.cut[2] = true;
-            }
-        }
-    } else if (part) return t;
-    long long X[3], Y[3];
-    float Z[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const float4 clip = c[k];
-        if (!(clip.w > 0.0f)) return t;
-        const float nx = clip.x / clip.w, ny = clip.y / clip.w, nz = clip.z / clip.w;
-        const float xf = (nx + 1.0f) * ((float)W * 0.5f);
-        const float yf = (ny + 1.0f) * ((float)H * -0.5f) + (float)H;
-        const float sx = xf * 256.0f, sy = yf * 256.0f;
-        if (!(fabsf(sx) < 1.0e9f) || !(fabsf(sy) < 1.0e9f)) return t;
-        X[k] = (long long)rintf(sx); Y[k] = (long long)rintf(sy); Z[k] = nz;
-        S.w[k] = clip.w;
-    }
-    const long long area2 = (X[1] - X[0]) * (Y[2] - Y[0]) - (X[2] - X[0]) * (Y[1] - Y[0]);
-    if (area2 == 0) return t;
-    if (cullBack && area2 > 0) return t; // Vulkan's signed area is -area2 / 2, front = counter-clockwise = positive (see the oracle)
-    if (area2 < 0) { // the winding swap takes the varyings' sources along
-        long long s = X[1]; X[1] = X[2]; X[2] = s; s = Y[1]; Y[1] = Y[2]; Y[2] = s; const float z = Z[1]; Z[1] = Z[2]; Z[2] = z;
-        const uint32_t i = S.I[1]; S.I[1] = S.I[2]; S.I[2] = i; const uint32_t o = S.O[1]; S.O[1] = S.O[2]; S.O[2] = o;
-        const float tt = S.t[1]; S.t[1] = S.t[2]; S.t[2] = tt; const float w = S.w[1]; S.w[1] = S.w[2]; S.w[2] = w;
-        const bool cu = S.cut[1]; S.cut[1] = S.cut[2]; S.cut[2] = cu;
-    }
-    t.x0 = X[0]; t.y0 = Y[0]; t.x1 = X[1]; t.y1 = Y[1]; t.x2 = X[2]; t.y2 = Y[2];
-    t.z0 = Z[0]; t.z1 = Z[1]; t.z2 = Z[2];
-    const long long minx = min(X[0], min(X[1], X[2])), maxx = max(X[0], max(X[1], X[2]));
-    const long long miny = min(Y[0], min(Y[1], Y[2])), maxy = max(Y[0], max(Y[1], Y[2]));
-    long long i0 = surf_floor_div256(minx - 128 + 255), i1 = surf_floor_div256(maxx - 128);
-    long long j0 = surf_floor_div256(miny - 128 + 255), j1 = surf_floor_div256(maxy - 128);
-    if (i0 < 0) i0 = 0;
-    if (j0 < rowBegin) j0 = rowBegin;
-    if (i1 > W - 1) i1 = W - 1;
-    if (j1 > rowEnd - 1) j1 = rowEnd - 1;
-    if (i1 < i0 || j1 < j0) return t;
-    t.i0 = (int)i0; t.i1 = (int)i1; t.j0 = (int)j0; t.j1 = (int)j1;
-    t.valid = true;
-    return t;
-}
-
-__device__ __forceinline__ long long surf_bcast64(long long v, int src)
-{
-    const int lo = __shfl((int)(unsigned int)(unsigned long long)v, src, 64), hi = __shfl((int)((unsigned long long)v >> 32), src, 64);
-    return (long long)(((unsigned long long)(unsigned int)hi << 32) | (unsigned int)lo);
-}
-
-// the depth test of one fragment, GreaterOrEqual in primitive order: the larger key wins.  A relaxed atomic load first (other waves run atomicMax on the
-// same word): a fragment that has already lost never reaches the atomic, and a stale value can only be SMALLER than the key now stored, so no winner is
-// dropped.
-__device__ __forceinline__ void surf_fragment(unsigned long long* p, float z, unsigned int orderPlus1)
-{
-    const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | orderPlus1;
-    if (key > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p, key);
-}
-
-// ---- workspace ------------------------------------------------------------------------------------------------------------------------------------
-struct SurfWorkspace { SurfHeader* header; float* srgb; unsigned long long* keys; SailorSurfaceDraw* draws; };
-static __host__ __device__ __forceinline__ SurfWorkspace surf_workspace(void* base, size_t pixels)
-{
-    SurfWorkspace w;
-    char* b = reinterpret_cast<char*>(base);
-    w.header = reinterpret_cast<SurfHeader*>(b);
-    w.srgb = reinterpret_cast<float*>(b + SURF_HEADER_BYTES);
-    w.keys = reinterpret_cast<unsigned long long*>(b + SURF_HEADER_BYTES + SURF_TABLE_BYTES);
-    w.draws = reinterpret_cast<SailorSurfaceDraw*>(b + SURF_HEADER_BYTES + SURF_TABLE_BYTES + pixels * 8);
-    return w;
-}
 
 __global__ __launch_bounds__(256) void k_surface_begin(const float* __restrict__ depth, int W, int rowBegin, int rows, uint32_t maxDraws, void* __restrict__ workspace,
                                                        SurfSrgb table)
@@ -325,22 +167,6 @@ __device__ __forceinline__ float surf_varying(const float* __restrict__ v, const
     return (m[r] * a[0] + m[4 + r] * a[1]) + m[8 + r] * a[2];
 }
 
-// texture(textureSamplers[index], uv): base level, bilinear, Repeat; SRGB decodes r, g, b per tap through the table before the filter
-__device__ __forceinline__ float4 surf_texture(const SailorTextureDesc* __restrict__ textures, uint32_t numTextures, uint32_t index, const float* __restrict__ srgb,
-                                               float u, float v)
-{
-    const SailorTextureDesc d = textures[index < numTextures ? index : 0u];
-    if (!d.texels || d.width <= 0 || d.height <= 0) return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (!(d.flags & SAILOR_TEXTURE_SRGB)) return bilinear_repeat_rgba8(d.texels, d.width, d.height, u, v);
-    const RepeatTap X = repeat_tap(d.width, u), Y = repeat_tap(d.height, v);
-    const uint32_t a = d.texels[Y.i0 * d.width + X.i0], c = d.texels[Y.i0 * d.width + X.i1], e = d.texels[Y.i1 * d.width + X.i0], f = d.texels[Y.i1 * d.width + X.i1];
-    float4 r;
-    r.x = lerp2(srgb[a & 255u], srgb[c & 255u], srgb[e & 255u], srgb[f & 255u], X.a, Y.a);
-    r.y = lerp2(srgb[(a >> 8) & 255u], srgb[(c >> 8) & 255u], srgb[(e >> 8) & 255u], srgb[(f >> 8) & 255u], X.a, Y.a);
-    r.z = lerp2(srgb[(a >> 16) & 255u], srgb[(c >> 16) & 255u], srgb[(e >> 16) & 255u], srgb[(f >> 16) & 255u], X.a, Y.a);
-    r.w = lerp2(unorm8(a >> 24), unorm8(c >> 24), unorm8(e >> 24), unorm8(f >> 24), X.a, Y.a);
-    return r;
-}
 
 __global__ __launch_bounds__(256) void k_surface_resolve(Mat4 P, Mat4 V, const float* __restrict__ instances, const SailorMaterialData* __restrict__ materials,
                                                          uint32_t numMaterials, const SailorTextureDesc* __restrict__ textures, uint32_t numTextures, int W, int H,
@@ -440,27 +266,6 @@ __global__ __launch_bounds__(256) void k_surface_composite(const float4* __restr
 }
 
 // ---- entry points ---------------------------------------------------------------------------------------------------------------------------------
-static int surf_refuse(SailorHipContext* ctx, const char* what)
-{
-    if (ctx) ctx->lastError = what;
-    return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-}
-static bool surf_band_ok(int32_t width, int32_t height, const SailorBand* band)
-{
-    return band && extent_ok(width, height) && sailor_hip_band_is_valid(width, height, band) == 1 && band->fbRowCount > 0;
-}
-static size_t surf_fixed_bytes(int32_t width, const SailorBand* band)
-{
-    return (size_t)SURF_HEADER_BYTES + SURF_TABLE_BYTES + (size_t)band->fbRowCount * width * 8;
-}
-// the descriptor slots a workspace of `bytes` holds
-static uint32_t surf_max_draws(int32_t width, const SailorBand* band, size_t bytes)
-{
-    const size_t fixed = surf_fixed_bytes(width, band);
-    if (bytes < fixed + sizeof(SailorSurfaceDraw)) return 0;
-    const size_t n = (bytes - fixed) / sizeof(SailorSurfaceDraw);
-    return (uint32_t)(n < SURF_MAX_DRAWS ? n : SURF_MAX_DRAWS);
-}
 
 extern "C" {
 

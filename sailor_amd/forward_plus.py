@@ -970,17 +970,34 @@ class SurfacePass:
         self.prim_base, self.draw_index = prim_base, 0
 
     def draw(self, frame: UboFrameData, vertices: torch.Tensor, indices: torch.Tensor, instances: torch.Tensor, instance_ids: torch.Tensor | None = None,
-             num_drawn: int | None = None, first_instance: int = 0, cull_back: bool = False):
-        """vertices: 72-byte records; indices: int32, 3 per triangle; instances: the 96-byte PerInstanceData SSBO; instance_ids: int32 or None"""
+             num_drawn: int | None = None, first_instance: int = 0, cull_back: bool = False, alpha_cutout: bool = False, materials: torch.Tensor | None = None,
+             textures: torch.Tensor | None = None, num_textures: int = 0):
+        """vertices: 72-byte records; indices: int32, 3 per triangle; instances: the 96-byte PerInstanceData SSBO; instance_ids: int32 or None.
+        alpha_cutout: the ALPHA_CUTOUT permutation (Standard.shader:403-408) through sailor_hip_surface_draw_masked, which needs the resolve's material and
+        texture tables"""
         if num_drawn is None:
             num_drawn = instance_ids.numel() if instance_ids is not None else instances.numel() * instances.element_size() // 96 - first_instance
         nt = indices.numel() // 3
-        d = _lib.SurfaceDraw(_ptr(vertices), _ptr(indices), _ptr(instance_ids), nt, num_drawn, self.prim_base, _lib.SURFACE_CULL_BACK if cull_back else 0,
-                             first_instance, 0)
-        _lib.check(self.ctx._lib.sailor_hip_surface_draw(self.ctx.handle, C.byref(frame), C.byref(d), _ptr(instances), self.draw_index, self.W, self.H,
-                                                         C.byref(self.band), _ptr(self.workspace), self.workspace.numel()), "sailor_hip_surface_draw", self.ctx.handle)
+        flags = (_lib.SURFACE_CULL_BACK if cull_back else 0) | (_lib.SURFACE_ALPHA_CUTOUT if alpha_cutout else 0)
+        d = _lib.SurfaceDraw(_ptr(vertices), _ptr(indices), _ptr(instance_ids), nt, num_drawn, self.prim_base, flags, first_instance, 0)
+        if alpha_cutout:
+            _lib.check(self.ctx._lib.sailor_hip_surface_draw_masked(self.ctx.handle, C.byref(frame), C.byref(d), _ptr(instances), _ptr(materials),
+                                                                    0 if materials is None else materials.numel() * materials.element_size() // 80, _ptr(textures),
+                                                                    num_textures, self.draw_index, self.W, self.H, C.byref(self.band), _ptr(self.workspace),
+                                                                    self.workspace.numel()), "sailor_hip_surface_draw_masked", self.ctx.handle)
+        else:
+            _lib.check(self.ctx._lib.sailor_hip_surface_draw(self.ctx.handle, C.byref(frame), C.byref(d), _ptr(instances), self.draw_index, self.W, self.H,
+                                                             C.byref(self.band), _ptr(self.workspace), self.workspace.numel()), "sailor_hip_surface_draw", self.ctx.handle)
         self.prim_base += host.surface_draw_prims(nt, num_drawn)
         self.draw_index += 1
+
+    def store_depth(self, depth: torch.Tensor) -> torch.Tensor:
+        """the keys' depth into the band's rows of `depth`, the raw depth attachment of the WHOLE frame, float32 [H, W]: the depth write of a pass that held
+        cutout draws"""
+        assert depth.dtype == torch.float32 and depth.shape == (self.H, self.W) and depth.is_contiguous()
+        _lib.check(self.ctx._lib.sailor_hip_surface_store_depth(self.ctx.handle, _ptr(self.workspace), self.workspace.numel(), _ptr(depth), self.W, self.H,
+                                                                C.byref(self.band)), "sailor_hip_surface_store_depth", self.ctx.handle)
+        return depth
 
     def resolve(self, frame: UboFrameData, instances: torch.Tensor, materials: torch.Tensor, textures: torch.Tensor, num_textures: int, want_depth: bool = True,
                 want_coverage: bool = True):
@@ -1008,3 +1025,14 @@ class SurfacePass:
         self.ctx.synchronize()
         at, n = self.ctx._lib.sailor_hip_surface_keys_offset(), self.rows * self.W * 8
         return self.workspace[at: at + n].cpu().numpy().view(np.uint64).reshape(self.rows, self.W)
+
+
+def masked_depth_prepass(sp: SurfacePass, frame: UboFrameData, depth: torch.Tensor, draws, instances: torch.Tensor, materials: torch.Tensor, textures: torch.Tensor,
+                         num_textures: int) -> torch.Tensor:
+    """DepthPrepass with `Tag: Masked` (DepthPrepassNode.cpp:246-255: Standard.shader with ALPHA_CUTOUT against no colour attachment): begin from `depth` (the
+    Opaque prepass's raw depth of the whole frame), the masked draws, the keys' depth back into `depth`.  draws: dicts of SurfacePass.draw's keyword arguments
+    (vertices, indices, instance_ids, num_drawn, first_instance, cull_back)."""
+    sp.begin(depth)
+    for d in draws:
+        sp.draw(frame, instances=instances, alpha_cutout=True, materials=materials, textures=textures, num_textures=num_textures, **d)
+    return sp.store_depth(depth)

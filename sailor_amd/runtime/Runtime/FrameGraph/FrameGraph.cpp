@@ -361,11 +361,25 @@ void RenderSceneNode::Process(RHIFrameGraphPtr, RHICommandListPtr, RHICommandLis
         if (!color) return;
         if (!m_pMaterial) m_pMaterial = driver->CreateMaterial(m_pShader);
         std::string tag;
-        commands->BeginDebugRegion(commandList, std::string(GetName()) + (TryGetString("Tag", tag) ? " QueueTag:" + tag : ""));
+        const bool tagged = TryGetString("Tag", tag);
+        commands->BeginDebugRegion(commandList, std::string(GetName()) + (tagged ? " QueueTag:" + tag : ""));
         commands->BeginRenderPass(commandList, TVector<RHITexturePtr> { color }, depth);
         commands->BindMaterial(commandList, m_pMaterial);
         commands->BindShaderBindings(commandList, m_pMaterial, { sceneView.m_frameBindings, sceneView.m_rhiLightsData, sceneView.m_sceneBindings });
+        RHIMaterialPtr bound = m_pMaterial;
         for (const auto& b : sceneView.m_batches) {
+            if (!b.m_tag.empty() && !(tagged && b.m_tag == tag)) continue; // the render queue filter: an untagged batch belongs to every queue
+            RHIMaterialPtr material = m_pMaterial;
+            if (b.m_bAlphaCutout || b.m_bDoubleSided) { // the batch's own material: the ALPHA_CUTOUT permutation (ModelImporter.cpp:213-229), ECullMode::None
+                RHIMaterialPtr& variant = m_pVariants[(b.m_bAlphaCutout ? 2 : 0) + (b.m_bDoubleSided ? 1 : 0) - 1];
+                if (!variant) {
+                    if (b.m_bAlphaCutout && !m_pCutoutShader) m_pCutoutShader = driver->CreateShader("Shaders/Standard.shader", { "ALPHA_CUTOUT" });
+                    variant = driver->CreateMaterial(b.m_bAlphaCutout ? m_pCutoutShader : m_pShader);
+                    variant->m_bDoubleSided = b.m_bDoubleSided;
+                }
+                material = variant;
+            }
+            if (material.GetRawPtr() != bound.GetRawPtr()) { commands->BindMaterial(commandList, material); bound = material; }
             commands->BindVertexBuffer(commandList, b.m_vertexBuffer, 0);
             commands->BindIndexBuffer(commandList, b.m_indexBuffer, 0);
             commands->DrawIndexed(commandList, b.m_indexCount, b.m_instanceCount, b.m_firstIndex, b.m_vertexOffset, b.m_firstInstance);
@@ -391,6 +405,8 @@ void RenderSceneNode::Clear()
 {
     m_pShader.Clear();
     m_pMaterial.Clear();
+    m_pCutoutShader.Clear();
+    for (auto& v : m_pVariants) v.Clear();
     m_surfaceBindings.Clear();
 }
 

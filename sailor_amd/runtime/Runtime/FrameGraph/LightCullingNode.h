@@ -46,6 +46,8 @@ protected:
 // dispatch over that buffer, as before the surface pass existed.  Without one, and with batches in the scene view, the node records the reference's
 // draws: BeginRenderPass("color", "depthStencil"), BindMaterial(Standard), BindShaderBindings, and per batch BindVertexBuffer / BindIndexBuffer /
 // DrawIndexed, EndRenderPass -- the HIP backend rasterises, resolves, shades and composites behind them (sailor_hip_surface_*).
+// The node's `Tag` is the render queue it draws (RenderSceneNode.cpp: `Tag: Opaque`, then `Tag: Masked` in DefaultRenderer.renderer): a batch is drawn if its own
+// tag is empty or equal to the node's; a batch with ALPHA_CUTOUT is drawn with a material of CreateShader("Shaders/Standard.shader", { "ALPHA_CUTOUT" }).
 class RenderSceneNode : public TFrameGraphNode<RenderSceneNode> {
 public:
     static const char* GetName() { return m_name; }
@@ -57,6 +59,9 @@ protected:
     static const char* m_name;
     RHI::RHIShaderPtr m_pShader;
     RHI::RHIMaterialPtr m_pMaterial;
+    // the materials of batches that are not the default one: [0] double-sided, [1] ALPHA_CUTOUT, [2] both (created when the first such batch is drawn)
+    RHI::RHIShaderPtr m_pCutoutShader;
+    RHI::RHIMaterialPtr m_pVariants[3];
     RHI::RHIShaderBindingSetPtr m_surfaceBindings;
 };
 

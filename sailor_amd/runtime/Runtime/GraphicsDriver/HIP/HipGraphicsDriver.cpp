@@ -786,7 +786,7 @@ static RHIBufferPtr scene_buffer(const TVector<RHIShaderBindingSetPtr>& bindings
 
 int HipGraphicsDriver::RecordSurfaceDraw(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& color, const RHITexturePtr& depth, const RHIBufferPtr& vertices,
                                          const RHIBufferPtr& indices, bool first, uint32_t drawIndex, uint32_t indexCount, uint32_t instanceCount, uint32_t firstIndex,
-                                         uint32_t vertexOffset, uint32_t firstInstance)
+                                         uint32_t vertexOffset, uint32_t firstInstance, uint32_t flags)
 {
     if (first) m_surfaceBegun = false;
     SailorUboFrameData frame;
@@ -818,10 +818,18 @@ int HipGraphicsDriver::RecordSurfaceDraw(const TVector<RHIShaderBindingSetPtr>& 
     d.dIndices = (const uint32_t*)indices->m_hip.m_devicePtr + firstIndex;
     d.dInstanceIds = nullptr;
     d.numTriangles = indexCount / 3; d.numDrawn = instanceCount; d.primBase = (uint32_t)m_surfacePrimBase;
-    d.flags = SAILOR_SURFACE_CULL_BACK; // the reference's materials cull back faces (ECullMode::Back, frontFace counter-clockwise)
+    d.flags = flags; // SAILOR_SURFACE_CULL_BACK: the reference's materials cull back faces (ECullMode::Back, frontFace counter-clockwise) unless double-sided
     d.firstInstance = firstInstance;
-    const int st = sailor_hip_surface_draw(m_ctx, &frame, &d, (const SailorPerInstanceData*)instances->m_hip.m_devicePtr, drawIndex, W, H, &band,
-                                           m_surfaceWorkspace->m_hip.m_devicePtr, bytes);
+    int st;
+    if (flags & SAILOR_SURFACE_ALPHA_CUTOUT) { // the ALPHA_CUTOUT permutation: `material` and `textureSamplers` of the bound sets decide the discard in the draw
+        RHIBufferPtr materials = scene_buffer(bindings, "material"), textures = scene_buffer(bindings, "textureSamplers");
+        if (!materials || !textures) { m_surfaceBegun = false; return SAILOR_HIP_ERR_INVALID_ARGUMENT; }
+        st = sailor_hip_surface_draw_masked(m_ctx, &frame, &d, (const SailorPerInstanceData*)instances->m_hip.m_devicePtr, (const SailorMaterialData*)materials->m_hip.m_devicePtr,
+                                            (uint32_t)(materials->m_size / sizeof(SailorMaterialData)), (const SailorTextureDesc*)textures->m_hip.m_devicePtr,
+                                            (uint32_t)(textures->m_size / sizeof(SailorTextureDesc)), drawIndex, W, H, &band, m_surfaceWorkspace->m_hip.m_devicePtr, bytes);
+    } else
+        st = sailor_hip_surface_draw(m_ctx, &frame, &d, (const SailorPerInstanceData*)instances->m_hip.m_devicePtr, drawIndex, W, H, &band,
+                                     m_surfaceWorkspace->m_hip.m_devicePtr, bytes);
     if (st != SAILOR_HIP_OK) { m_surfaceBegun = false; return st; }
     uint64_t prims = 0;
     sailor_hip_surface_draw_prims(d.numTriangles, d.numDrawn, &prims);
@@ -829,7 +837,7 @@ int HipGraphicsDriver::RecordSurfaceDraw(const TVector<RHIShaderBindingSetPtr>& 
     return SAILOR_HIP_OK;
 }
 
-int HipGraphicsDriver::RecordSurfaceEnd(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& color)
+int HipGraphicsDriver::RecordSurfaceEnd(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& color, const RHITexturePtr& depthToStore)
 {
     if (!m_surfaceBegun) return SAILOR_HIP_ERR_INVALID_ARGUMENT; // a draw of the pass was refused: nothing to resolve
     m_surfaceBegun = false;
@@ -857,8 +865,15 @@ int HipGraphicsDriver::RecordSurfaceEnd(const TVector<RHIShaderBindingSetPtr>& b
     st = RecordShade({ bindings[0], bindings[1], own });
     if (st != SAILOR_HIP_OK) return st;
     BeforeBufferWrite(color->m_buffer->m_hip.m_devicePtr);
-    return sailor_hip_surface_composite(m_ctx, (const float*)m_surfaceRadiance->m_hip.m_devicePtr, m_surfaceWorkspace->m_hip.m_devicePtr, bytes,
-                                        (float*)color->m_buffer->m_hip.m_devicePtr, W, H, &band);
+    st = sailor_hip_surface_composite(m_ctx, (const float*)m_surfaceRadiance->m_hip.m_devicePtr, m_surfaceWorkspace->m_hip.m_devicePtr, bytes,
+                                      (float*)color->m_buffer->m_hip.m_devicePtr, W, H, &band);
+    if (st != SAILOR_HIP_OK || !depthToStore) return st;
+    // a pass that held a cutout draw writes its depth: the attachment gets the keys' depth (the opaque draws' depth is the prepass's already; a masked fragment
+    // that survived writes its own, a discarded one none)
+    if (!depthToStore->m_buffer || depthToStore->GetExtent().x != W || depthToStore->GetExtent().y != H || depthToStore->m_format != EFormat::R32_SFLOAT)
+        return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    BeforeBufferWrite(depthToStore->m_buffer->m_hip.m_devicePtr);
+    return sailor_hip_surface_store_depth(m_ctx, m_surfaceWorkspace->m_hip.m_devicePtr, bytes, (float*)depthToStore->m_buffer->m_hip.m_devicePtr, W, H, &band);
 }
 
 // ---- the render-pass subset: state is kept on the command list, a 6-index draw of a known full-screen material becomes a
@@ -869,6 +884,7 @@ void HipGraphicsDriver::BeginRenderPass(RHICommandListPtr cmd, const TVector<RHI
     cmd->m_depthAttachment = depthStencilAttachment;
     cmd->m_casterDraws = 0;
     cmd->m_surfaceDraws = 0;
+    cmd->m_surfaceCutout = false;
 }
 
 void HipGraphicsDriver::BindVertexBuffer(RHICommandListPtr cmd, RHIBufferPtr vertexBuffer, uint32_t) { cmd->m_vertexBuffer = vertexBuffer; }
@@ -894,11 +910,13 @@ void HipGraphicsDriver::EndRenderPass(RHICommandListPtr cmd)
     if (cmd->m_surfaceDraws > 0) { // RenderScene's pass: the fragment stage of every pixel's winning fragment, then the colour writes
         RHITexturePtr color = cmd->m_colorAttachments.empty() ? RHITexturePtr() : cmd->m_colorAttachments[0];
         TVector<RHIShaderBindingSetPtr> bindings = cmd->m_boundBindings;
-        cmd->m_hip.m_commands.push_back([this, bindings, color]() { return RecordSurfaceEnd(bindings, color); });
+        RHITexturePtr depthToStore = cmd->m_surfaceCutout ? cmd->m_depthAttachment : RHITexturePtr();
+        cmd->m_hip.m_commands.push_back([this, bindings, color, depthToStore]() { return RecordSurfaceEnd(bindings, color, depthToStore); });
     }
     cmd->m_depthAttachment.Clear();
     cmd->m_casterDraws = 0;
     cmd->m_surfaceDraws = 0;
+    cmd->m_surfaceCutout = false;
     cmd->m_colorAttachments.clear();
     cmd->m_boundMaterial.Clear();
     cmd->m_boundBindings.clear();
@@ -949,8 +967,12 @@ void HipGraphicsDriver::DrawIndexed(RHICommandListPtr cmd, uint32_t indexCount, 
         RHIBufferPtr vb = cmd->m_vertexBuffer, ib = cmd->m_indexBuffer;
         TVector<RHIShaderBindingSetPtr> bindings = cmd->m_boundBindings;
         const uint32_t drawIndex = cmd->m_surfaceDraws++;
-        cmd->m_hip.m_commands.push_back([this, bindings, color, depth, vb, ib, drawIndex, indexCount, instanceCount, firstIndex, vertexOffset, firstInstance]() {
-            return RecordSurfaceDraw(bindings, color, depth, vb, ib, drawIndex == 0, drawIndex, indexCount, instanceCount, firstIndex, vertexOffset, firstInstance);
+        // the permutation and the cull mode of the bound material: { "ALPHA_CUTOUT" } goes to sailor_hip_surface_draw_masked
+        const uint32_t flags = (cmd->m_boundMaterial->m_bDoubleSided ? 0u : SAILOR_SURFACE_CULL_BACK) |
+                               (cmd->m_boundMaterial->m_shader->HasDefine("ALPHA_CUTOUT") ? SAILOR_SURFACE_ALPHA_CUTOUT : 0u);
+        if (flags & SAILOR_SURFACE_ALPHA_CUTOUT) cmd->m_surfaceCutout = true;
+        cmd->m_hip.m_commands.push_back([this, bindings, color, depth, vb, ib, drawIndex, indexCount, instanceCount, firstIndex, vertexOffset, firstInstance, flags]() {
+            return RecordSurfaceDraw(bindings, color, depth, vb, ib, drawIndex == 0, drawIndex, indexCount, instanceCount, firstIndex, vertexOffset, firstInstance, flags);
         });
         return;
     }

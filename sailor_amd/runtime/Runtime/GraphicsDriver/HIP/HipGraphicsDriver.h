@@ -43,6 +43,8 @@
 // and the depth-only instanced draws of the shadow passes (material of)
 //   "Shaders/Standard.shader" drawn with DrawIndexed (RenderSceneNode's batches) -> sailor_hip_surface_begin at the pass's first such draw, sailor_hip_surface_draw
 //       per draw, and at EndRenderPass sailor_hip_surface_resolve -> the shade over driver-owned planes -> sailor_hip_surface_composite into the colour attachment
+//   "Shaders/Standard.shader" { "ALPHA_CUTOUT" } drawn with DrawIndexed (a Masked batch) -> sailor_hip_surface_draw_masked with `material` and `textureSamplers` of the
+//       bound sets; a pass that held one ends with sailor_hip_surface_store_depth into its depth attachment after the composite
 //   "Shaders/ShadowCaster.shader" [EVSM]  -> sailor_hip_raster_depth into the pass' depth attachment, and at EndRenderPass sailor_hip_shadow_resolve
 //                                            into its colour attachment (push constant lightMatrix, set 1 `data`, vertex positions, 32-bit indices)
 #pragma once
@@ -144,8 +146,8 @@ private:
     int RecordShade(const TVector<RHI::RHIShaderBindingSetPtr>& bindings);
     int RecordSurfaceDraw(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& color, const RHI::RHITexturePtr& depth,
                           const RHI::RHIBufferPtr& vertices, const RHI::RHIBufferPtr& indices, bool first, uint32_t drawIndex, uint32_t indexCount,
-                          uint32_t instanceCount, uint32_t firstIndex, uint32_t vertexOffset, uint32_t firstInstance);
-    int RecordSurfaceEnd(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& color);
+                          uint32_t instanceCount, uint32_t firstIndex, uint32_t vertexOffset, uint32_t firstInstance, uint32_t flags);
+    int RecordSurfaceEnd(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& color, const RHI::RHITexturePtr& depthToStore);
     int RecordBrdfLut(const TVector<RHI::RHIShaderBindingSetPtr>& bindings);
     int RecordIrradianceMap(const TVector<RHI::RHIShaderBindingSetPtr>& bindings);
     int RecordEnvPrefilter(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const TVector<uint8_t>& pc);

@@ -13,6 +13,12 @@ struct CameraData { // ECS/CameraECS.h: what the nodes read from sceneView.m_cam
 struct RHISceneBatch {
     RHIBufferPtr m_vertexBuffer, m_indexBuffer; // VertexP3N3T3B3UV2C4 records; uint32 indices
     uint32_t m_indexCount = 0, m_instanceCount = 0, m_firstIndex = 0, m_vertexOffset = 0, m_firstInstance = 0;
+    // the batch's material, as far as RenderSceneNode.cpp and the backend need it (AssetRegistry/Model/ModelImporter.cpp:213-229): its render queue tag
+    // ("Opaque", "Masked"; empty = drawn by every RenderScene node, as before the tags existed), ALPHA_CUTOUT (alphaMode == "MASK") and the cull mode
+    // (doubleSided = ECullMode::None).  The defaults are the batch of before: untagged, no cutout, back faces culled.
+    std::string m_tag;
+    bool m_bAlphaCutout = false;
+    bool m_bDoubleSided = false;
 };
 
 struct RHISceneViewSnapshot {

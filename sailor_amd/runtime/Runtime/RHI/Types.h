@@ -170,6 +170,8 @@ public:
     // RenderState::m_blendMode, the one member of the render state a full-screen pass executed as a kernel still needs: "Blit Clouds" is Blit.shader
     // under AlphaBlending (SkyNode.cpp:476-480)
     EBlendMode m_blendMode = EBlendMode::None;
+    // RenderState::m_cullMode == ECullMode::None (a glTF doubleSided material); otherwise back faces are culled.  Read by the draws of Standard.shader only.
+    bool m_bDoubleSided = false;
 };
 using RHIMaterialPtr = TRefPtr<RHIMaterial>;
 
@@ -185,6 +187,7 @@ public:
     TVector<uint8_t> m_pushConstants;                          // PushConstants(material, size, ptr)
     uint32_t m_casterDraws = 0;                                // depth-only draws recorded in the current pass (the first one clears)
     uint32_t m_surfaceDraws = 0;                               // Standard.shader draws recorded in the current pass (the first one begins the surface pass)
+    bool m_surfaceCutout = false;                              // ... one of them with ALPHA_CUTOUT: the pass ends with the depth write (sailor_hip_surface_store_depth)
     TRefPtr<class RHIMaterial> m_boundMaterial;
     TVector<TRefPtr<class RHIShaderBindingSet>> m_boundBindings;
 };

@@ -9,6 +9,7 @@
 #include "Runtime/RHI/Renderer.h"
 #include "Runtime/AssetRegistry/FrameGraph/FrameGraphParser.h"
 #include "Runtime/AssetRegistry/World/WorldPrefabImporter.h"
+#include "scene_tags.h"
 #include <cstdio>
 #include <vector>
 
@@ -24,6 +25,7 @@ struct SailorRuntime {
     RHIFrameGraph graph;
     RHISceneViewSnapshot snapshot;
     FrameGraphNodePtr lightCulling, renderScene, linearizeDepth, environment;
+    std::vector<FrameGraphNodePtr> queueNodes; // the RenderScene nodes sailor_rt_build_graph created with a queue ("RenderScene:Masked"): they get the scene's targets too
     RHITexturePtr depthHighZ;
     RHITexturePtr depth, rawDepth;
     RHIBufferPtr surface, radiance;
@@ -50,6 +52,7 @@ RT_API void sailor_rt_destroy(SailorRuntime* rt)
     rt->lighting.reset();
     rt->depth.Clear(); rt->surface.Clear(); rt->radiance.Clear(); rt->depthHighZ.Clear();
     rt->lightCulling.Clear(); rt->renderScene.Clear(); rt->linearizeDepth.Clear(); rt->environment.Clear(); rt->rawDepth.Clear();
+    rt->queueNodes.clear();
     rt->snapshot = RHISceneViewSnapshot();
     delete rt;
 }
@@ -84,6 +87,15 @@ RT_API int sailor_rt_enable_shader(SailorRuntime* rt, const char* path)
 RT_API int sailor_rt_build_graph(SailorRuntime* rt, const char** nodeNames, int count)
 {
     for (int i = 0; i < count; i++) {
+        // "RenderScene:<Tag>" is a RenderScene node with that `Tag` (DefaultRenderer.renderer lists RenderScene twice: `Tag: Opaque`, then `Tag: Masked`)
+        if (std::string(nodeNames[i]).rfind("RenderScene:", 0) == 0) {
+            auto queue = FrameGraphBuilder::CreateNode("RenderScene");
+            if (!queue) return -1;
+            queue->SetString("Tag", nodeNames[i] + 12);
+            rt->queueNodes.push_back(queue);
+            rt->graph.AddNode(queue);
+            continue;
+        }
         auto node = FrameGraphBuilder::CreateNode(nodeNames[i]);
         if (!node && rt->graph.IsNodeEnabled(nodeNames[i])) node = FrameGraphBuilder::CreateOptInNode(nodeNames[i]);
         if (!node) return -1;
@@ -214,6 +226,7 @@ RT_API int sailor_rt_load_renderer(SailorRuntime* rt, const char* yamlText, int*
     if (!asset.Deserialize(yamlText ? yamlText : "", rt->graph.GetViewport().x, rt->graph.GetViewport().y)) return -1;
     rt->graph.Clear();
     rt->lightCulling.Clear(); rt->renderScene.Clear(); rt->linearizeDepth.Clear(); rt->environment.Clear();
+    rt->queueNodes.clear();
     const FrameGraphBuildReport report = FrameGraphImporter::BuildFrameGraph(asset, rt->graph);
     for (const auto& node : rt->graph.GetGraph()) { // the harness' setters address these nodes directly
         const std::string name = node->GetDebugName();
@@ -412,13 +425,36 @@ RT_API int sailor_rt_set_scene(SailorRuntime* rt, void* vertices, uint32_t numVe
     return 0;
 }
 
+// The materials of the batches sailor_rt_set_scene set (call it afterwards; sailor_rt_set_scene itself leaves every batch untagged, without cutout, back faces
+// culled): `tags` is the batches' render queue tags in order, separated by commas, an empty field = untagged (scene_tags.h; NULL = all untagged); flags[i] is
+// SAILOR_RT_BATCH_ALPHA_CUTOUT | SAILOR_RT_BATCH_DOUBLE_SIDED of batch i.  -1, and nothing changed, unless numBatches is the scene's and both parse.
+RT_API int sailor_rt_set_scene_tags(SailorRuntime* rt, const char* tags, const uint32_t* flags, int numBatches)
+{
+    if (!rt || numBatches < 0 || (size_t)numBatches != rt->snapshot.m_batches.size()) return -1;
+    std::vector<std::string> parsed;
+    if (!sailor_rt_parse_scene_tags(tags, numBatches, parsed) || !sailor_rt_scene_flags_ok(flags, numBatches)) return -1;
+    for (int i = 0; i < numBatches; i++) {
+        RHISceneBatch& b = rt->snapshot.m_batches[(size_t)i];
+        b.m_tag = parsed[(size_t)i];
+        b.m_bAlphaCutout = (flags[i] & SAILOR_RT_BATCH_ALPHA_CUTOUT) != 0;
+        b.m_bDoubleSided = (flags[i] & SAILOR_RT_BATCH_DOUBLE_SIDED) != 0;
+    }
+    return 0;
+}
+
 // RenderScene's attachments for those draws: "color" (RGBA32F, e.g. Main) and "depthStencil" (the raw R32F DepthBuffer of the prepass, or null)
 RT_API int sailor_rt_set_scene_targets(SailorRuntime* rt, void* color, void* depth, int width, int height)
 {
-    if (!rt || !rt->renderScene || !color) return -1;
+    if (!rt || (!rt->renderScene && rt->queueNodes.empty()) || !color) return -1;
     auto* hip = static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver());
-    rt->renderScene->SetRHIResource("color", hip->WrapTexture(color, { width, height }, EFormat::R32G32B32A32_SFLOAT));
-    if (depth) rt->renderScene->SetRHIResource("depthStencil", hip->WrapTexture(depth, { width, height }, EFormat::R32_SFLOAT));
+    std::vector<FrameGraphNodePtr> nodes = rt->queueNodes; // every queue's pass renders into the same attachments (DefaultRenderer.renderer: Main, DepthBuffer)
+    if (rt->renderScene) nodes.push_back(rt->renderScene);
+    auto colorTexture = hip->WrapTexture(color, { width, height }, EFormat::R32G32B32A32_SFLOAT);
+    auto depthTexture = depth ? hip->WrapTexture(depth, { width, height }, EFormat::R32_SFLOAT) : RHITexturePtr();
+    for (auto& node : nodes) {
+        node->SetRHIResource("color", colorTexture);
+        if (depthTexture) node->SetRHIResource("depthStencil", depthTexture);
+    }
     return 0;
 }
 

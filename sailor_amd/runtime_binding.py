@@ -72,6 +72,7 @@ def load() -> C.CDLL:
         rt.sailor_rt_gpu_culling.argtypes = [P, P, C.c_uint32, C.c_uint32, P, C.c_uint32]
         rt.sailor_rt_set_scene.argtypes = [P, P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, P, C.c_int]
         rt.sailor_rt_set_scene_targets.argtypes = [P, P, P, C.c_int, C.c_int]
+        rt.sailor_rt_set_scene_tags.argtypes = [P, C.c_char_p, P, C.c_int]
         rt.sailor_rt_process_frame.argtypes = [P]
         rt.sailor_rt_process_frame_overwriting_lists.argtypes = [P, P, C.c_size_t, P, C.c_size_t]
         rt.sailor_rt_set_frame_split.argtypes = [P, C.c_int, C.c_int, P]
@@ -343,6 +344,13 @@ class Runtime:
         _lib.check(self.rt.sailor_rt_set_scene(self.h, ptr(vertices), nbytes(vertices) // 72, ptr(indices), indices.numel(), ptr(instances),
                                                0 if instances is None else nbytes(instances) // 96, ptr(materials), 0 if materials is None else nbytes(materials) // 80,
                                                ptr(textures), num_textures, b.ctypes.data, len(b)), "sailor_rt_set_scene")
+
+    def set_scene_tags(self, tags, flags):
+        """the materials of set_scene's batches, after set_scene: tags = one render queue tag per batch ("Opaque", "Masked", "" = untagged: drawn by every
+        RenderScene node), flags = one int per batch, BATCH_ALPHA_CUTOUT | BATCH_DOUBLE_SIDED"""
+        assert len(tags) == len(flags)
+        f = np.ascontiguousarray(flags, np.uint32)
+        _lib.check(self.rt.sailor_rt_set_scene_tags(self.h, ",".join(tags).encode(), f.ctypes.data if len(f) else None, len(f)), "sailor_rt_set_scene_tags")
 
     def set_scene_targets(self, color, depth=None):
         """RenderScene's colour attachment (float32 [H, W, 4]) and the prepass's raw depth (float32 [H, W]) or None"""
