@@ -1309,6 +1309,58 @@ SAILOR_HIP_API int sailor_hip_surface_draw_masked(SailorHipContext* ctx, const S
 SAILOR_HIP_API int sailor_hip_surface_store_depth(SailorHipContext* ctx, const void* dWorkspace, size_t workspaceBytes, float* dDepth, int32_t width,
                                                   int32_t height, const SailorBand* band);
 
+/* ---- DebugDraw: the line-list pass of the Gizmo material (debug_lines.hip) ---------------------------------------------------------------------
+ * Replaces: the draw FrameGraph/DebugDrawNode.cpp:19-79 replays -- RHI/DebugContext.cpp:382-398 (DrawDebugMesh: one DrawIndexed over the line list that
+ * DrawLine :76-98 and the shapes :100-158 built) with Content/Shaders/Gizmo.shader under the material of DebugContext.cpp:272: LineList, lineWidth 1, depth
+ * test and depth write, no bias, GREATER_OR_EQUAL, blend None.  The pass is sailor_hip_surface_begin(current DepthBuffer) -> sailor_hip_debug_lines_draw ->
+ * sailor_hip_debug_lines_resolve; the key layout (depthBits << 32 | order + 1), the workspace and the fragment's depth test are the surface pass's.
+ * Vulkan leaves non-strict line rasterisation partly to the implementation.  Pinned:
+ *  1. Vertex stage: clip = viewProjection * vec4(position, 1), ((c0 x + c1 y) + c2 z) + c3 (Gizmo.shader:22); segment s has the vertices dIndices[2s],
+ *     dIndices[2s + 1], or 2s, 2s + 1 without an index buffer (the identity DebugContext uploads).
+ *  2. Clip, in clip space and fp32, against the distances w - z, w + x, w - x, w + y, w - y in this order, tIn = 0, tOut = 1: both ends < 0 rejects; one end
+ *     < 0 gives t = dA / (dA - dB), which raises tIn (A outside) or lowers tOut (B outside); tIn > tOut rejects.  The clipped ends are computed from the
+ *     ORIGINAL ends, P0 = tIn > 0 ? A + (B - A) tIn : A, P1 = tOut < 1 ? A + (B - A) tOut : B, for x, y, z, w and the four colour channels; an end with
+ *     !(w > 0) rejects.  (The far plane is the per-fragment z > 0 of rule 5.)
+ *  3. Snap: the surface pass's -- nx = x / w, xf = (nx + 1) (W 0.5), yf = (ny + 1) (H -0.5) + H, X = rintf(256 xf), rejected unless |256 xf| < 1e9.
+ *  4. Coverage, exact in integers, closed-form per major-axis step: x-major iff |dX| >= |dY|; dX == dY == 0 has no fragment.  x-major, pixel centre
+ *     M = 256 c + 128: column c has a fragment iff X0 <= M < X1 (dX > 0) or X1 < M <= X0 (dX < 0) -- start included, end excluded; its row is
+ *     floor((Y0 dX + dY (M - X0)) / (256 dX)), an exact integer floor: the pixel that contains the line's point at that centre.  y-major is the mirror
+ *     image.  A fragment outside the frame or the band's rows does not exist.
+ *  5. Attributes: t = float(M - X0) / float(dX); z = z0 + (z1 - z0) t with z_k = z / w of the clipped ends (a line's depth is linear in screen space); a
+ *     fragment exists only if z > 0 && z <= 1.  Colour is perspective-correct: q0 = (1 - t) / w0, q1 = t / w1, b = q1 / (q0 + q1), c = c0 + (c1 - c0) b, in
+ *     exactly this operation order.
+ *  6. Order: primBase + the segment's index; the larger key wins, so equal depth goes to the later segment, and a line at the seeded depth wins over it.
+ *     Keys are order-free, so any distribution of the work gives the same bits.
+ * All entry points record only (no allocation, no synchronisation, capturable); a refused call launches nothing and leaves its text in last_error.  One draw
+ * per pass (DebugContext issues exactly one); a draw of no segments records nothing. */
+
+/* RHI/Types.h VertexP3C4, interleaved, 28 bytes */
+typedef struct SailorVertexP3C4 {
+    float position[3];
+    float color[4];
+} SailorVertexP3C4;
+
+/* DebugContext.cpp:393-397: BindVertexBuffer / BindIndexBuffer / DrawIndexed(numRenderedVertices, 1, 0, 0, 0) */
+typedef struct SailorDebugLinesDraw {
+    const SailorVertexP3C4* dVertices; /* device */
+    const uint32_t* dIndices;          /* device, 2 x numSegments, or NULL: the identity */
+    uint32_t numSegments;
+    uint32_t primBase;                 /* the order of the first segment */
+} SailorDebugLinesDraw;
+
+/* Replaces: the DrawIndexed of DebugContext.cpp:397 up to the depth test: k_debug_lines_draw issues the keys of every fragment into a workspace that
+ * sailor_hip_surface_begin seeded.  viewProjection: the push constant of :395, column-major.  Refused: a draw whose primBase + numSegments reaches 2^32 - 1. */
+SAILOR_HIP_API int sailor_hip_debug_lines_draw(SailorHipContext* ctx, const float viewProjection[16], const SailorDebugLinesDraw* draw, int32_t width,
+                                               int32_t height, const SailorBand* band, void* dWorkspace, size_t workspaceBytes);
+/* Replaces: Gizmo.shader:34 `outColor = fragColor` and the colour and depth writes of the pass: k_debug_lines_resolve writes, at every pixel a segment owns
+ * (low word of the key != 0), all four channels of the colour into dTarget (the band's rows x width float4) and the key's depth into the band's rows of
+ * dDepth, the raw width x height depth attachment of the WHOLE frame, as sailor_hip_surface_store_depth does.  Other pixels keep both. */
+SAILOR_HIP_API int sailor_hip_debug_lines_resolve(SailorHipContext* ctx, const float viewProjection[16], const SailorDebugLinesDraw* draw, int32_t width,
+                                                  int32_t height, const SailorBand* band, const void* dWorkspace, size_t workspaceBytes, float* dTarget,
+                                                  float* dDepth);
+/* numSegments: what the draw adds to a running primBase, by analogy with sailor_hip_surface_draw_prims. */
+SAILOR_HIP_API int sailor_hip_debug_lines_prims(uint32_t numSegments, uint64_t* out);
+
 #ifdef __cplusplus
 }
 #endif

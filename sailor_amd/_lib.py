@@ -215,6 +215,11 @@ class SurfaceDraw(C.Structure):  # include/sailor_hip.h SailorSurfaceDraw: one D
                 ("primBase", C.c_uint32), ("flags", C.c_uint32), ("firstInstance", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class DebugLinesDraw(C.Structure):  # include/sailor_hip.h SailorDebugLinesDraw: the one DrawIndexed of DebugContext::DrawDebugMesh
+    _fields_ = [("dVertices", C.c_void_p), ("dIndices", C.c_void_p), ("numSegments", C.c_uint32), ("primBase", C.c_uint32)]
+
+
+VERTEX_P3C4_DTYPE = [("position", "<f4", 3), ("color", "<f4", 4)]  # SailorVertexP3C4, 28 bytes
 TEXTURE_SRGB = 1        # SAILOR_TEXTURE_SRGB
 SURFACE_CULL_BACK = 1   # SAILOR_SURFACE_CULL_BACK
 SURFACE_ALPHA_CUTOUT = 2  # SAILOR_SURFACE_ALPHA_CUTOUT (sailor_hip_surface_draw_masked only)
@@ -400,6 +405,9 @@ SIGNATURES = {
     "sailor_hip_surface_keys_offset": (C.c_size_t, []),
     "sailor_host_srgb_table": (C.c_int, [C.POINTER(C.c_float)]),
     "sailor_hip_surface_draw_prims": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "sailor_hip_debug_lines_draw": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(DebugLinesDraw), C.c_int32, C.c_int32, C.POINTER(Band), _P, C.c_size_t]),
+    "sailor_hip_debug_lines_resolve": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(DebugLinesDraw), C.c_int32, C.c_int32, C.POINTER(Band), _P, C.c_size_t, _P, _P]),
+    "sailor_hip_debug_lines_prims": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

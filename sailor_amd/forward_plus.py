@@ -1036,3 +1036,39 @@ def masked_depth_prepass(sp: SurfacePass, frame: UboFrameData, depth: torch.Tens
     for d in draws:
         sp.draw(frame, instances=instances, alpha_cutout=True, materials=materials, textures=textures, num_textures=num_textures, **d)
     return sp.store_depth(depth)
+
+
+class DebugLinesPass:
+    """The DebugDraw node's pass (sailor_hip_debug_lines_*): begin from the current DepthBuffer -> the one draw of DebugContext::DrawDebugMesh -> resolve into
+    Main and DepthBuffer.  Owns a surface-pass workspace (the keys)."""
+
+    def __init__(self, ctx: HipContext, width: int, height: int, band: Band | None = None):
+        self.surface = SurfacePass(ctx, width, height, band, max_draws=1)
+        self.ctx, self.W, self.H, self.band, self.rows, self.workspace = ctx, width, height, self.surface.band, self.surface.rows, self.surface.workspace
+        self._draw, self._vp = None, None
+
+    def begin(self, depth: torch.Tensor | None):
+        """depth: the raw DepthBuffer of the WHOLE frame, float32 [H, W] (or None: keys of 0)"""
+        self.surface.begin(depth)
+        self._draw = None
+
+    def draw(self, view_projection, vertices: torch.Tensor, indices: torch.Tensor | None = None, num_segments: int | None = None, prim_base: int = 0):
+        """view_projection: 16 floats, column-major (the push constant); vertices: 28-byte VertexP3C4 records; indices: int32, 2 per segment, or None"""
+        if num_segments is None:
+            num_segments = indices.numel() // 2 if indices is not None else vertices.numel() * vertices.element_size() // 56
+        self._vp = (C.c_float * 16)(*[float(x) for x in np.asarray(view_projection, np.float32).reshape(16)])
+        self._draw = _lib.DebugLinesDraw(_ptr(vertices), _ptr(indices), num_segments, prim_base)
+        _lib.check(self.ctx._lib.sailor_hip_debug_lines_draw(self.ctx.handle, self._vp, C.byref(self._draw), self.W, self.H, C.byref(self.band), _ptr(self.workspace),
+                                                             self.workspace.numel()), "sailor_hip_debug_lines_draw", self.ctx.handle)
+
+    def resolve(self, target: torch.Tensor, depth: torch.Tensor):
+        """target: float32 [rows, W, 4] (the band's rows of Main); depth: float32 [H, W] (the whole DepthBuffer); both written where a segment owns the pixel"""
+        assert self._draw is not None, "resolve() before draw()"
+        assert target.dtype == torch.float32 and target.shape == (self.rows, self.W, 4) and target.is_contiguous()
+        assert depth.dtype == torch.float32 and depth.shape == (self.H, self.W) and depth.is_contiguous()
+        _lib.check(self.ctx._lib.sailor_hip_debug_lines_resolve(self.ctx.handle, self._vp, C.byref(self._draw), self.W, self.H, C.byref(self.band), _ptr(self.workspace),
+                                                                self.workspace.numel(), _ptr(target), _ptr(depth)), "sailor_hip_debug_lines_resolve", self.ctx.handle)
+        return target, depth
+
+    def download_keys(self) -> np.ndarray:
+        return self.surface.download_keys()

@@ -443,3 +443,86 @@ def surface_draw_prims(num_triangles: int, num_drawn: int) -> int:
     out = C.c_uint64()
     _lib.check(_lib.load().sailor_hip_surface_draw_prims(num_triangles, num_drawn, C.byref(out)), "sailor_hip_surface_draw_prims")
     return int(out.value)
+
+
+def debug_lines_prims(num_segments: int) -> int:
+    """sailor_hip_debug_lines_prims: what the DebugDraw pass's draw adds to a running primBase"""
+    out = C.c_uint64()
+    _lib.check(_lib.load().sailor_hip_debug_lines_prims(num_segments, C.byref(out)), "sailor_hip_debug_lines_prims")
+    return int(out.value)
+
+
+# ---- RHI/DebugContext.cpp: the line lists of the debug shapes, in the reference's segment order and fp32 arithmetic.  Each returns VertexP3C4 records
+# (_lib.VERTEX_P3C4_DTYPE), two per segment: what DrawLine (:76-98) appends. -------------------------------------------------------------------------
+def _v3(v) -> np.ndarray:
+    return np.asarray(v, np.float32).reshape(3)
+
+
+def debug_line(start, end, color) -> np.ndarray:
+    """DebugContext::DrawLine (:76-98): both vertices get the colour"""
+    out = np.zeros(2, _lib.VERTEX_P3C4_DTYPE)
+    out["position"][0], out["position"][1] = _v3(start), _v3(end)
+    out["color"][:] = np.asarray(color, np.float32).reshape(4)
+    return out
+
+
+def _debug_lines(pairs, color) -> np.ndarray:
+    return np.concatenate([debug_line(a, b, c if c is not None else color) for a, b, *rest in pairs for c in [rest[0] if rest else None]])
+
+
+def debug_aabb(aabb_min, aabb_max, color) -> np.ndarray:
+    """DebugContext::DrawAABB (:100-116): 12 segments"""
+    a, b = _v3(aabb_min), _v3(aabb_max)
+    v = lambda x, y, z: np.array([x[0], y[1], z[2]], np.float32)  # noqa: E731
+    return _debug_lines([(a, v(b, a, a)), (a, v(a, b, a)), (a, v(a, a, b)),
+                         (b, v(a, b, b)), (b, v(b, a, b)), (b, v(b, b, a)),
+                         (v(a, b, b), v(a, b, a)), (v(a, b, b), v(a, a, b)), (v(a, a, b), v(b, a, b)),
+                         (v(b, a, b), v(b, a, a)), (v(b, a, a), v(b, b, a)), (v(b, b, a), v(a, b, a))], color)
+
+
+def debug_frustum(corners, color) -> np.ndarray:
+    """DebugContext::DrawFrustum (:140-158) over Frustum::GetCorners() (extract_frustum_planes' second result): 12 segments, the second four white"""
+    c = np.asarray(corners, np.float32).reshape(8, 3)
+    white = (1.0, 1.0, 1.0, 1.0)
+    return _debug_lines([(c[4], c[5]), (c[5], c[6]), (c[6], c[7]), (c[7], c[4]),
+                         (c[0], c[1], white), (c[1], c[2], white), (c[2], c[3], white), (c[3], c[0], white),
+                         (c[4], c[0]), (c[5], c[1]), (c[6], c[2]), (c[7], c[3])], color)
+
+
+def debug_origin(position, origin, size: float) -> np.ndarray:
+    """DebugContext::DrawOrigin (:129-138): origin * vec4(size, 0, 0, 0) etc. as glm's mat4 * vec4, (c0 x + c1 y) + (c2 z + c3 w), from `position`; red, green, blue"""
+    p, m, s = _v3(position), np.asarray(origin, np.float32).reshape(4, 4), np.float32(size)  # m[c] = column c
+    z = np.float32(0.0)
+    axis = lambda x, y, w: ((m[0] * x + m[1] * y) + (m[2] * w + m[3] * z))[:3]  # noqa: E731
+    return _debug_lines([(p, p + axis(s, z, z), (1, 0, 0, 1)), (p, p + axis(z, s, z), (0, 1, 0, 1)), (p, p + axis(z, z, s), (0, 0, 1, 1))], None)
+
+
+def debug_arrow(start, end, color) -> np.ndarray:
+    """DebugContext::DrawArrow (:118-127): the segment and a three-axis cross of a tenth of its length at the end"""
+    a, b = _v3(start), _v3(end)
+    d = b - a
+    length = np.float32(np.sqrt(np.float32(np.float32(d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]))) * np.float32(0.1)
+    up, left, forward = np.array([0, 1, 0], np.float32), np.array([-1, 0, 0], np.float32), np.array([0, 0, -1], np.float32)
+    return _debug_lines([(a, b), (b + up * length, b + (-up) * length), (b + left * length, b + (-left) * length),
+                         (b + forward * length, b + (-forward) * length)], color)
+
+
+def debug_sphere(position, radius: float, color) -> np.ndarray:
+    """DebugContext::DrawSphere (:17-63) in fp32 with its (i - 1) / (j - 1) indexing: 8 latitude bands x (1 + 7 x 3) = 176 segments"""
+    p, r, pi, n = _v3(position), np.float32(radius), np.float32(3.1415926), 7  # Math::Pi (Math.h:14)
+    pairs = []
+    for i in range(n + 1):
+        lat0 = pi * (np.float32(-0.5) + np.float32(i - 1) / np.float32(n))
+        lat1 = pi * (np.float32(-0.5) + np.float32(i) / np.float32(n))
+        z0, zr0, z1, zr1 = np.sin(lat0), np.cos(lat0), np.sin(lat1), np.cos(lat1)
+        v3 = v4 = None
+        for j in range(n + 1):
+            lng = np.float32(2) * pi * np.float32(j - 1) / np.float32(n)
+            x, y = np.cos(lng), np.sin(lng)
+            v1 = p + np.array([r * x * zr0, r * z0, r * y * zr0], np.float32)
+            v2 = p + np.array([r * x * zr1, r * z1, r * y * zr1], np.float32)
+            if v3 is not None:
+                pairs += [(v1, v3), (v2, v4)]
+            pairs.append((v1, v2))
+            v3, v4 = v1, v2
+    return _debug_lines(pairs, color)

@@ -5,6 +5,7 @@
 #include "LightCullingNode.h"
 #include "RHIFrameGraph.h"
 #include "../RHI/Renderer.h"
+#include "../RHI/DebugContext.h"
 
 using namespace Sailor;
 using namespace Sailor::RHI;
@@ -46,6 +47,7 @@ template class Sailor::Framegraph::TFrameGraphNode<EyeAdaptationNode>;
 template class Sailor::Framegraph::TFrameGraphNode<PostProcessNode>;
 template class Sailor::Framegraph::TFrameGraphNode<BlitNode>;
 template class Sailor::Framegraph::TFrameGraphNode<SkyNode>;
+template class Sailor::Framegraph::TFrameGraphNode<DebugDrawNode>;
 
 // ---- RHIFrameGraph ----------------------------------------------------------------------------------------------------------
 UboFrameData RHIFrameGraph::FillFrameData(RHICommandListPtr transferCmdList, RHISceneViewSnapshot& snapshot, const UboFrameData& previousFrame, float deltaTime,
@@ -786,6 +788,40 @@ void SkyNode::Clear() // (:825-834)
     m_pSkyMaterial.Clear(); m_pSkyEnvMaterial.Clear();
     m_pShaderBindings.Clear();
 }
+
+// ---- DebugDrawNode (FrameGraph/DebugDrawNode.cpp:19-83) -----------------------------------------------------------------------------------
+const char* DebugDrawNode::m_name = "DebugDraw";
+
+void DebugDrawNode::Process(RHIFrameGraphPtr frameGraph, RHICommandListPtr, RHICommandListPtr commandList, const RHISceneViewSnapshot& sceneView)
+{
+    auto commands = Renderer::GetDriverCommands();
+    commands->BeginDebugRegion(commandList, GetName()); // (:24)
+    auto resolved = [&](const char* name) -> RHITexturePtr { // GetRHIResource / GetResolvedAttachment
+        if (auto t = GetRHIResource(name).DynamicCast<RHITexture>()) return t;
+        auto it = m_unresolvedResourceParams.find(name);
+        return it == m_unresolvedResourceParams.end() ? RHITexturePtr() : frameGraph->GetRenderTarget(it->second);
+    };
+    RHITexturePtr target = resolved("color"), depthAttachment = resolved("depthStencil");
+    if (!depthAttachment) depthAttachment = frameGraph->GetRenderTarget("DepthBuffer"); // (:30-34)
+    if (!target) return;                                                                // (:36-39, without EndDebugRegion there too)
+    commands->ImageMemoryBarrier(commandList, target, EImageLayout::ColorAttachmentOptimal); // (:43-44)
+    if (depthAttachment) commands->ImageMemoryBarrier(commandList, depthAttachment, EImageLayout::General);
+    if (sceneView.m_debugContext) {
+        // what the world records into the secondary list: DrawDebugMesh(projection * view) of the view's camera -- the matrices FillFrameData uploads
+        UboFrameData frame {};
+        float viewProjection[16];
+        sailor_host_fill_frame_data(sceneView.m_camera.m_world, sceneView.m_camera.m_fov, sceneView.m_camera.m_aspect, sceneView.m_camera.m_zNear, sceneView.m_camera.m_zFar,
+                                    frameGraph->GetViewport().x, frameGraph->GetViewport().y, sceneView.m_currentTime, sceneView.m_deltaTime, &frame);
+        sailor_host_mat4_mul(frame.projection, frame.view, viewProjection);
+        // RenderSecondaryCommandBuffers(cmd, { list }, { color }, depth, area, offset, no clear) (:51-76)
+        commands->BeginRenderPass(commandList, TVector<RHITexturePtr> { target }, depthAttachment);
+        sceneView.m_debugContext->DrawDebugMesh(commandList, viewProjection);
+        commands->EndRenderPass(commandList);
+    }
+    commands->EndDebugRegion(commandList); // (:78)
+}
+
+void DebugDrawNode::Clear() {}
 
 // ---- BloomNode (FrameGraph/BloomNode.cpp:17-148) -------------------------------------------------------------------------------------------
 const char* BloomNode::m_name = "Bloom";

@@ -224,6 +224,21 @@ protected:
     bool m_bCloudTexturesChanged = false;
 };
 
+// Everything DebugContext collected, behind the RenderScene passes: Runtime/FrameGraph/DebugDrawNode.{h,cpp}.  Resources (DefaultRenderer.renderer:289-293):
+// "color" = Main, "depthStencil" = DepthBuffer (the default when none is given, DebugDrawNode.cpp:30-34).  The reference replays a SECONDARY command list the
+// world recorded DebugContext::DrawDebugMesh(projection * view) into (RenderSecondaryCommandBuffers, :51-76); this mirror has no secondary lists, so the node
+// records the same calls DIRECTLY into its command list: BeginRenderPass(color, depthStencil), DrawDebugMesh of the scene view's context, EndRenderPass.
+class DebugDrawNode : public TFrameGraphNode<DebugDrawNode> {
+public:
+    static const char* GetName() { return m_name; }
+    void Process(RHIFrameGraphPtr frameGraph, RHI::RHICommandListPtr transferCommandList, RHI::RHICommandListPtr commandList,
+                 const RHI::RHISceneViewSnapshot& sceneView) override;
+    void Clear() override;
+
+protected:
+    static const char* m_name;
+};
+
 // The mip pyramid over `Main`: Runtime/FrameGraph/BloomNode.h.  Resource (DefaultRenderer.renderer:303-304): "bloom" = the HDR target with its mip chain,
 // rewritten in place; vec4 "threshold", "knee", "bloomIntensity", "dirtIntensity" (their .x).  `u_dirt_texture` is the graph's "g_lensDirtSampler".
 // In the reference this is a TFrameGraphNode<BloomNode> (BloomNode.h:10, :43) and registers under "Bloom"; here the class derives from the base directly

@@ -86,7 +86,7 @@ RHIShaderPtr HipGraphicsDriver::CreateShader(const std::string& assetPath, const
         "Shaders/ComputeDepthHighZ.shader", "Shaders/ComputeHistogram.shader", "Shaders/ComputeAverageLuminance.shader", "Shaders/ComputeBrdfLut.shader",
         "Shaders/ComputeIrradianceMap.shader", "Shaders/ComputeEnvMap_IBL.shader", "Shaders/ShadowCaster.shader", "Shaders/LinearizeDepth.shader",
         "Shaders/Tonemapping.shader", "Shaders/Blur.shader", "Shaders/HBAO.shader", "Shaders/HBAO_Blur.shader", "Shaders/Sky.shader", "Shaders/ComputeBloomDownscale.shader",
-        "Shaders/ComputeBloomUpscale.shader", "Shaders/Blit.shader", "Shaders/ChromaticAberation.shader" };
+        "Shaders/ComputeBloomUpscale.shader", "Shaders/Blit.shader", "Shaders/ChromaticAberation.shader", "Shaders/Gizmo.shader" };
     auto shader = RHIShaderPtr::Make(assetPath, defines);
     shader->m_bIsReady = false;
     for (const char* name : routed) if (assetPath == name) shader->m_bIsReady = true;
@@ -837,6 +837,44 @@ int HipGraphicsDriver::RecordSurfaceDraw(const TVector<RHIShaderBindingSetPtr>& 
     return SAILOR_HIP_OK;
 }
 
+// DebugContext::DrawDebugMesh's draw (DebugContext.cpp:391-397) inside DebugDrawNode's pass: the Gizmo material's state (:272: depth test and write,
+// GREATER_OR_EQUAL, blend None, LineList) as begin from the depth attachment -> draw -> resolve into both attachments.  The keys live in the surface pass'
+// workspace: RenderScene's pass has ended by then.
+int HipGraphicsDriver::RecordDebugLines(const RHITexturePtr& color, const RHITexturePtr& depth, const RHIBufferPtr& vertices, const RHIBufferPtr& indices,
+                                        const TVector<uint8_t>& pushConstants, uint32_t indexCount, uint32_t firstIndex, uint32_t vertexOffset)
+{
+    m_surfaceBegun = false;
+    if (!color || !color->m_buffer || !depth || !depth->m_buffer || !vertices || pushConstants.size() < 64) return SAILOR_HIP_ERR_INVALID_ARGUMENT; // a missing binding
+    if (m_worldSize > 1) return SAILOR_HIP_ERR_UNSUPPORTED; // (the pass runs on whole frames here)
+    const int W = color->GetExtent().x, H = color->GetExtent().y;
+    if (color->m_format != EFormat::R32G32B32A32_SFLOAT || depth->GetExtent().x != W || depth->GetExtent().y != H || depth->m_format != EFormat::R32_SFLOAT)
+        return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    const uint32_t numSegments = indexCount / 2;
+    if ((indices && (size_t)firstIndex + indexCount > indices->m_size / 4) || (size_t)vertexOffset * sizeof(SailorVertexP3C4) > vertices->m_size ||
+        (!indices && ((size_t)vertexOffset + firstIndex + indexCount) * sizeof(SailorVertexP3C4) > vertices->m_size))
+        return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    SailorBand band;
+    sailor_hip_band_whole_frame(W, H, &band);
+    const size_t bytes = sailor_hip_surface_workspace_bytes(W, H, &band, SURFACE_MAX_DRAWS);
+    if (!m_surfaceWorkspace || m_surfaceWorkspace->m_size != bytes) m_surfaceWorkspace = CreateBuffer(bytes);
+    if (!m_surfaceWorkspace) return SAILOR_HIP_ERR_OUT_OF_MEMORY;
+    float viewProjection[16];
+    memcpy(viewProjection, pushConstants.data(), 64);
+    SailorDebugLinesDraw d {};
+    d.dVertices = (const SailorVertexP3C4*)vertices->m_hip.m_devicePtr + vertexOffset;
+    d.dIndices = indices ? (const uint32_t*)indices->m_hip.m_devicePtr + firstIndex : nullptr;
+    if (!indices) d.dVertices += firstIndex;
+    d.numSegments = numSegments; d.primBase = 0;
+    float* depthPtr = (float*)depth->m_buffer->m_hip.m_devicePtr;
+    int st = sailor_hip_surface_begin(m_ctx, depthPtr, W, H, &band, m_surfaceWorkspace->m_hip.m_devicePtr, bytes);
+    if (st != SAILOR_HIP_OK) return st;
+    st = sailor_hip_debug_lines_draw(m_ctx, viewProjection, &d, W, H, &band, m_surfaceWorkspace->m_hip.m_devicePtr, bytes);
+    if (st != SAILOR_HIP_OK) return st;
+    BeforeBufferWrite(color->m_buffer->m_hip.m_devicePtr);
+    BeforeBufferWrite(depthPtr);
+    return sailor_hip_debug_lines_resolve(m_ctx, viewProjection, &d, W, H, &band, m_surfaceWorkspace->m_hip.m_devicePtr, bytes, (float*)color->m_buffer->m_hip.m_devicePtr, depthPtr);
+}
+
 int HipGraphicsDriver::RecordSurfaceEnd(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& color, const RHITexturePtr& depthToStore)
 {
     if (!m_surfaceBegun) return SAILOR_HIP_ERR_INVALID_ARGUMENT; // a draw of the pass was refused: nothing to resolve
@@ -973,6 +1011,15 @@ void HipGraphicsDriver::DrawIndexed(RHICommandListPtr cmd, uint32_t indexCount, 
         if (flags & SAILOR_SURFACE_ALPHA_CUTOUT) cmd->m_surfaceCutout = true;
         cmd->m_hip.m_commands.push_back([this, bindings, color, depth, vb, ib, drawIndex, indexCount, instanceCount, firstIndex, vertexOffset, firstInstance, flags]() {
             return RecordSurfaceDraw(bindings, color, depth, vb, ib, drawIndex == 0, drawIndex, indexCount, instanceCount, firstIndex, vertexOffset, firstInstance, flags);
+        });
+        return;
+    }
+    if (name == "Shaders/Gizmo.shader" && cmd->m_boundMaterial->m_topology == EPrimitiveTopology::LineList) { // DebugContext::DrawDebugMesh (DebugContext.cpp:397)
+        RHITexturePtr color = cmd->m_colorAttachments.empty() ? RHITexturePtr() : cmd->m_colorAttachments[0], depth = cmd->m_depthAttachment;
+        RHIBufferPtr vb = cmd->m_vertexBuffer, ib = cmd->m_indexBuffer;
+        TVector<uint8_t> pc = cmd->m_pushConstants; // viewProjection, captured at record time
+        cmd->m_hip.m_commands.push_back([this, color, depth, vb, ib, pc, indexCount, firstIndex, vertexOffset]() {
+            return RecordDebugLines(color, depth, vb, ib, pc, indexCount, firstIndex, vertexOffset);
         });
         return;
     }

@@ -45,6 +45,9 @@
 //       per draw, and at EndRenderPass sailor_hip_surface_resolve -> the shade over driver-owned planes -> sailor_hip_surface_composite into the colour attachment
 //   "Shaders/Standard.shader" { "ALPHA_CUTOUT" } drawn with DrawIndexed (a Masked batch) -> sailor_hip_surface_draw_masked with `material` and `textureSamplers` of the
 //       bound sets; a pass that held one ends with sailor_hip_surface_store_depth into its depth attachment after the composite
+//   "Shaders/Gizmo.shader" of a LineList material drawn with DrawIndexed (DebugContext::DrawDebugMesh inside DebugDrawNode's pass) -> sailor_hip_surface_begin from
+//       the pass' depth attachment, sailor_hip_debug_lines_draw, sailor_hip_debug_lines_resolve into the colour and the depth attachment (push constant viewProjection,
+//       VertexP3C4 vertices, 32-bit indices)
 //   "Shaders/ShadowCaster.shader" [EVSM]  -> sailor_hip_raster_depth into the pass' depth attachment, and at EndRenderPass sailor_hip_shadow_resolve
 //                                            into its colour attachment (push constant lightMatrix, set 1 `data`, vertex positions, 32-bit indices)
 #pragma once
@@ -147,6 +150,8 @@ private:
     int RecordSurfaceDraw(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& color, const RHI::RHITexturePtr& depth,
                           const RHI::RHIBufferPtr& vertices, const RHI::RHIBufferPtr& indices, bool first, uint32_t drawIndex, uint32_t indexCount,
                           uint32_t instanceCount, uint32_t firstIndex, uint32_t vertexOffset, uint32_t firstInstance, uint32_t flags);
+    int RecordDebugLines(const RHI::RHITexturePtr& color, const RHI::RHITexturePtr& depth, const RHI::RHIBufferPtr& vertices, const RHI::RHIBufferPtr& indices,
+                         const TVector<uint8_t>& pushConstants, uint32_t indexCount, uint32_t firstIndex, uint32_t vertexOffset);
     int RecordSurfaceEnd(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& color, const RHI::RHITexturePtr& depthToStore);
     int RecordBrdfLut(const TVector<RHI::RHIShaderBindingSetPtr>& bindings);
     int RecordIrradianceMap(const TVector<RHI::RHIShaderBindingSetPtr>& bindings);

@@ -31,6 +31,9 @@ struct RHISceneViewSnapshot {
     // (MaterialDataSSBO), `textureSamplers` (a device table of SailorTextureDesc)
     TVector<RHISceneBatch> m_batches;
     RHIShaderBindingSetPtr m_sceneBindings;
+    // :81 m_debugDrawSecondaryCmdList is a secondary command list the world's DebugContext recorded DrawDebugMesh into; secondary lists are not mirrored, so
+    // the snapshot carries the context itself and DebugDrawNode records its draw directly (null = no debug drawing)
+    const class DebugContext* m_debugContext = nullptr;
 };
 
 } // namespace Sailor::RHI

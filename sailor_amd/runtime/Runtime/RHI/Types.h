@@ -74,6 +74,7 @@ public:
 using RHIBufferPtr = TRefPtr<RHIBuffer>;
 
 enum class EFormat { R32_SFLOAT, R16_SFLOAT, R32G32B32A32_SFLOAT, R32G32_SFLOAT, R8_UNORM, R8G8B8A8_UNORM }; // the 8-bit ones: SkyNode's weather map and noise volumes
+enum class EPrimitiveTopology { TriangleList, LineList }; // RHI/Types.h EPrimitiveTopology, the two the path draws with
 enum class EBlendMode { None, Additive, AlphaBlending, Multiply }; // RHI/Types.h EBlendMode; VulkanPipileneStates.cpp:236-254
 enum class ETextureFiltration { Nearest, Linear }; // RHI/Types.h ETextureFiltration (Bicubic has no user on the path)
 enum class EImageLayout { Undefined, ShaderReadOnlyOptimal, General, ColorAttachmentOptimal, ComputeWrite, TransferSrcOptimal, TransferDstOptimal };
@@ -172,6 +173,8 @@ public:
     EBlendMode m_blendMode = EBlendMode::None;
     // RenderState::m_cullMode == ECullMode::None (a glTF doubleSided material); otherwise back faces are culled.  Read by the draws of Standard.shader only.
     bool m_bDoubleSided = false;
+    // the topology the material's pipeline was created with (CreateMaterial(vertexDescription, topology, ...)): LineList for DebugContext's Gizmo material
+    EPrimitiveTopology m_topology = EPrimitiveTopology::TriangleList;
 };
 using RHIMaterialPtr = TRefPtr<RHIMaterial>;
 

@@ -7,6 +7,7 @@
 #include "Runtime/FrameGraph/RHIFrameGraph.h"
 #include "Runtime/GraphicsDriver/HIP/HipGraphicsDriver.h"
 #include "Runtime/RHI/Renderer.h"
+#include "Runtime/RHI/DebugContext.h"
 #include "Runtime/AssetRegistry/FrameGraph/FrameGraphParser.h"
 #include "Runtime/AssetRegistry/World/WorldPrefabImporter.h"
 #include "scene_tags.h"
@@ -30,6 +31,7 @@ struct SailorRuntime {
     RHITexturePtr depth, rawDepth;
     RHIBufferPtr surface, radiance;
     std::unique_ptr<EcsSweepSystem> sweep;
+    DebugContext debug; // the world's DebugContext (Engine/World.h): the snapshot points at it
     int frames = 0;
 };
 
@@ -40,6 +42,7 @@ RT_API SailorRuntime* sailor_rt_create(int device, void* stream, int ownStream, 
     if (outStatus) *outStatus = rt->renderer->GetStatus();
     if (rt->renderer->GetStatus() != SAILOR_HIP_OK) { delete rt; return nullptr; }
     rt->lighting.reset(new LightingECS());
+    rt->snapshot.m_debugContext = &rt->debug;
     return rt;
 }
 
@@ -50,6 +53,7 @@ RT_API void sailor_rt_destroy(SailorRuntime* rt)
     rt->graph.Clear();
     rt->sweep.reset();
     rt->lighting.reset();
+    rt->debug.Clear();
     rt->depth.Clear(); rt->surface.Clear(); rt->radiance.Clear(); rt->depthHighZ.Clear();
     rt->lightCulling.Clear(); rt->renderScene.Clear(); rt->linearizeDepth.Clear(); rt->environment.Clear(); rt->rawDepth.Clear();
     rt->queueNodes.clear();
@@ -784,6 +788,63 @@ RT_API int sailor_rt_eye_adaptation_state(SailorRuntime* rt, void** outHistogram
         return 0;
     }
     return -1;
+}
+
+// ---- the world's DebugContext (RHI/DebugContext.h): what game code calls through World::GetDebugContext(); the DebugDraw node draws what it holds ----------------
+RT_API int sailor_rt_debug_draw_line(SailorRuntime* rt, const float* start3, const float* end3, const float* color4, float duration)
+{
+    if (!rt || !start3 || !end3 || !color4) return -1;
+    rt->debug.DrawLine(start3, end3, color4, duration);
+    return 0;
+}
+RT_API int sailor_rt_debug_draw_aabb(SailorRuntime* rt, const float* min3, const float* max3, const float* color4, float duration)
+{
+    if (!rt || !min3 || !max3 || !color4) return -1;
+    rt->debug.DrawAABB(min3, max3, color4, duration);
+    return 0;
+}
+RT_API int sailor_rt_debug_draw_frustum(SailorRuntime* rt, const float* corners24, const float* color4, float duration)
+{
+    if (!rt || !corners24 || !color4) return -1;
+    rt->debug.DrawFrustum(corners24, color4, duration);
+    return 0;
+}
+RT_API int sailor_rt_debug_draw_origin(SailorRuntime* rt, const float* position3, const float* origin16, float size, float duration)
+{
+    if (!rt || !position3 || !origin16) return -1;
+    rt->debug.DrawOrigin(position3, origin16, size, duration);
+    return 0;
+}
+RT_API int sailor_rt_debug_draw_sphere(SailorRuntime* rt, const float* position3, float radius, const float* color4, float duration)
+{
+    if (!rt || !position3 || !color4) return -1;
+    rt->debug.DrawSphere(position3, radius, color4, duration);
+    return 0;
+}
+RT_API int sailor_rt_debug_draw_arrow(SailorRuntime* rt, const float* start3, const float* end3, const float* color4, float duration)
+{
+    if (!rt || !start3 || !end3 || !color4) return -1;
+    rt->debug.DrawArrow(start3, end3, color4, duration);
+    return 0;
+}
+// DebugContext::Tick(transferCmd, deltaTime) as the world's tick calls it before the frame is rendered: upload, then the lifetimes.  Returns the number of
+// vertices the next frame draws (m_numRenderedVertices), -1 without a runtime.
+RT_API int sailor_rt_debug_tick(SailorRuntime* rt, float deltaTime)
+{
+    if (!rt) return -1;
+    auto transferCmd = Renderer::GetDriver()->CreateCommandList();
+    rt->debug.Tick(transferCmd, deltaTime);
+    Renderer::GetDriver()->SubmitCommandList(transferCmd);
+    return (int)rt->debug.GetNumRenderedVertices();
+}
+// the line list as it stands (after the last tick's expiry): up to maxVertices VertexP3C4 records into outVertices (may be null); returns the vertex count
+RT_API int sailor_rt_debug_vertices(SailorRuntime* rt, float* outVertices, int maxVertices)
+{
+    if (!rt) return -1;
+    const auto& v = rt->debug.GetLineVertices();
+    if (outVertices)
+        for (size_t i = 0; i < v.size() && (int)i < maxVertices; i++) memcpy(outVertices + 7 * i, &v[i], sizeof(SailorVertexP3C4));
+    return (int)v.size();
 }
 
 RT_API int sailor_rt_process_frame(SailorRuntime* rt)

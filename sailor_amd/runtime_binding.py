@@ -74,6 +74,13 @@ def load() -> C.CDLL:
         rt.sailor_rt_set_scene_targets.argtypes = [P, P, P, C.c_int, C.c_int]
         rt.sailor_rt_set_scene_tags.argtypes = [P, C.c_char_p, P, C.c_int]
         rt.sailor_rt_process_frame.argtypes = [P]
+        for shape in ("line", "aabb", "arrow"):
+            getattr(rt, f"sailor_rt_debug_draw_{shape}").argtypes = [P, P, P, P, C.c_float]
+        rt.sailor_rt_debug_draw_frustum.argtypes = [P, P, P, C.c_float]
+        rt.sailor_rt_debug_draw_origin.argtypes = [P, P, P, C.c_float, C.c_float]
+        rt.sailor_rt_debug_draw_sphere.argtypes = [P, P, C.c_float, P, C.c_float]
+        rt.sailor_rt_debug_tick.argtypes = [P, C.c_float]
+        rt.sailor_rt_debug_vertices.argtypes = [P, P, C.c_int]
         rt.sailor_rt_process_frame_overwriting_lists.argtypes = [P, P, C.c_size_t, P, C.c_size_t]
         rt.sailor_rt_set_frame_split.argtypes = [P, C.c_int, C.c_int, P]
         rt.sailor_rt_exchange_light_lists.argtypes = [P, P, C.c_size_t, P, C.c_size_t]
@@ -371,6 +378,51 @@ class Runtime:
     def exchange_light_lists(self, global_grid, global_culled):
         _lib.check(self.rt.sailor_rt_exchange_light_lists(self.h, global_grid.data_ptr(), global_grid.numel() * global_grid.element_size(),
                                                           global_culled.data_ptr(), global_culled.numel() * global_culled.element_size()), "sailor_rt_exchange_light_lists")
+
+    # ---- the world's DebugContext (RHI/DebugContext.cpp): what the DebugDraw node draws; `duration` is the line's lifetime in seconds of debug_tick ----
+    @staticmethod
+    def _fv(v, n):
+        a = np.ascontiguousarray(v, np.float32).reshape(-1)
+        assert a.size == n, (a.size, n)
+        return a
+
+    def debug_draw_line(self, start, end, color, duration: float = 0.0):
+        a, b, c = self._fv(start, 3), self._fv(end, 3), self._fv(color, 4)
+        assert self.rt.sailor_rt_debug_draw_line(self.h, a.ctypes.data, b.ctypes.data, c.ctypes.data, duration) == 0
+
+    def debug_draw_aabb(self, aabb_min, aabb_max, color, duration: float = 0.0):
+        a, b, c = self._fv(aabb_min, 3), self._fv(aabb_max, 3), self._fv(color, 4)
+        assert self.rt.sailor_rt_debug_draw_aabb(self.h, a.ctypes.data, b.ctypes.data, c.ctypes.data, duration) == 0
+
+    def debug_draw_arrow(self, start, end, color, duration: float = 0.0):
+        a, b, c = self._fv(start, 3), self._fv(end, 3), self._fv(color, 4)
+        assert self.rt.sailor_rt_debug_draw_arrow(self.h, a.ctypes.data, b.ctypes.data, c.ctypes.data, duration) == 0
+
+    def debug_draw_frustum(self, corners, color, duration: float = 0.0):
+        """corners: Frustum::GetCorners(), 8 x 3 (host.extract_frustum_planes' second result)"""
+        a, c = self._fv(corners, 24), self._fv(color, 4)
+        assert self.rt.sailor_rt_debug_draw_frustum(self.h, a.ctypes.data, c.ctypes.data, duration) == 0
+
+    def debug_draw_origin(self, position, origin, size: float = 1.0, duration: float = 0.0):
+        a, m = self._fv(position, 3), self._fv(origin, 16)
+        assert self.rt.sailor_rt_debug_draw_origin(self.h, a.ctypes.data, m.ctypes.data, size, duration) == 0
+
+    def debug_draw_sphere(self, position, radius: float, color, duration: float = 0.0):
+        a, c = self._fv(position, 3), self._fv(color, 4)
+        assert self.rt.sailor_rt_debug_draw_sphere(self.h, a.ctypes.data, radius, c.ctypes.data, duration) == 0
+
+    def debug_tick(self, delta_time: float) -> int:
+        """DebugContext::Tick: upload the line list, then run the lifetimes down by delta_time (a line below zero leaves AFTER the frame of this tick);
+        returns the number of vertices the next frame draws"""
+        return self.rt.sailor_rt_debug_tick(self.h, delta_time)
+
+    def debug_vertices(self) -> np.ndarray:
+        """the line list as it stands: VertexP3C4 records (_lib.VERTEX_P3C4_DTYPE), two per line"""
+        n = self.rt.sailor_rt_debug_vertices(self.h, None, 0)
+        out = np.zeros(max(n, 0), _lib.VERTEX_P3C4_DTYPE)
+        if n > 0:
+            self.rt.sailor_rt_debug_vertices(self.h, out.ctypes.data, n)
+        return out
 
     def process_frame(self) -> int:
         return self.rt.sailor_rt_process_frame(self.h)
