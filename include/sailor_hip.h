@@ -1361,6 +1361,103 @@ SAILOR_HIP_API int sailor_hip_debug_lines_resolve(SailorHipContext* ctx, const f
 /* numSegments: what the draw adds to a running primBase, by analogy with sailor_hip_surface_draw_prims. */
 SAILOR_HIP_API int sailor_hip_debug_lines_prims(uint32_t numSegments, uint64_t* out);
 
+/* ---- RenderImGui: ordered alpha-blended UI triangles (ui_draw.hip) ----------------------------------------------------------------------------
+ * Replaces: the draws FrameGraph/RenderImGuiNode.cpp:21-60 replays -- Submodules/ImGuiApi.cpp:190-276 (ImGui_RenderDrawData: per draw list and per command a
+ * scissor and one DrawIndexed) with Content/Shaders/ImGuiUI.shader under the material of ImGuiApi.cpp:295-332: TriangleList over VertexP2UV2C1, no depth test,
+ * no depth write, no cull, one sample, EBlendMode::AlphaBlending, one RGBA8 UNORM texture (Linear, Repeat, one level).  The pass is ONE
+ * sailor_hip_ui_draw over the flattened commands of the frame (sailor_host_ui_flatten).  Pinned:
+ *  1. Vertex fetch: SailorVertexP2UV2C1, 20 bytes, 4-byte aligned; a colour channel is c = (float)byte / 255.0f, r in the low byte.  Indices are 16-bit or
+ *     32-bit (indexBytes of the draw).  Triangle k of a command has the indices firstIndex + 3k .. + 2 and the vertices vertexOffset + index; an index
+ *     position outside the index buffer or a vertex outside [0, numVertices) drops its triangle: no fetch leaves a buffer.  indexCount % 3 trailing indices
+ *     are ignored.
+ *  2. Vertex stage and viewport (ImGuiUI.shader, ImGuiApi.cpp:108-113): nx = px * scale.x + translate.x -- two fp32 roundings, no fused multiply-add --, ny
+ *     likewise; xf = (nx + 1.0f) * ((float)W * 0.5f), yf = (ny + 1.0f) * ((float)H * 0.5f).  The viewport's height is positive: no flip, row 0 is the top.
+ *  3. Rasterisation is the depth prepass's after projection: X = rintf(xf * 256.0f), a triangle with !(|xf * 256| < 1e9) on any coordinate (NaN included) is
+ *     dropped; 64-bit integer edge functions at the pixel centre (256 i + 128, 256 j + 128), the top-left rule, both windings drawn (a winding swap
+ *     exchanges vertices 1 and 2 WITH their colour and uv), zero area dropped.  No near-plane cut (z = 0, w = 1); no depth test, read or write.
+ *  4. Scissor: pixel (i, j) belongs to a command iff scissor[0] <= i < scissor[0] + scissor[2] and scissor[1] <= j < scissor[1] + scissor[3];
+ *     sailor_host_ui_flatten computes offset and extent in fp32 exactly as ImGuiApi.cpp:236-252 does (the extent is the truncated DIFFERENCE).  A zero
+ *     extent that survived the float test draws nothing.
+ *  5. Varyings: w = 1, so interpolation is affine: l_k = float(e_k) / area, a = (a0 l0 + a1 l1) + a2 l2 for the four colour channels and both texcoords.
+ *     This is the surface pass's order with q_k = l_k; DECISION: the surface pass's b_k = q_k / s is not applied (s is 1 up to rounding; the rule above
+ *     is the whole formula).
+ *  6. Texture: the surface pass's fetch of a SailorTextureDesc without SAILOR_TEXTURE_SRGB -- base level, bilinear, Repeat, RGBA8 texels as UNORM, no sRGB
+ *     decode.  One texture per pass (ImGuiApi.cpp:255-262).  A descriptor without texels samples as 0.  DECISION: a descriptor WITH SAILOR_TEXTURE_SRGB is
+ *     refused rather than silently read as UNORM.
+ *  7. Fragment and blend (VulkanPipileneStates.cpp:245-246), one IEEE rounding per written operation, in place on an fp32 RGBA plane:
+ *        src = colour * texel (per channel);  rgb = src.rgb * src.a + dst.rgb * (1.0f - src.a);  a = src.a * src.a - dst.a * (1.0f - src.a)
+ *     (the alpha op is SUBTRACT).  Triangles blend in command order, then index order within a command -- Vulkan's primitive order --, and a pixel's result is
+ *     that sequential chain bit for bit.  A fragment with src.a == 0 still blends (the alpha line changes dst.a).
+ *  8. NOT reproduced: the reference's attachment is B8G8R8A8_SRGB -- its hardware blends in linear light and re-quantises to 8 bits after every fragment;
+ *     BackBuffer here is an fp32 plane (as sailor_hip_debug_view leaves it) and keeps the unquantised chain.  MSAA does not apply (bSupportMultisampling is
+ *     false).  User textures per command (the reference has none).
+ *  9. sailor_hip_ui_draw only records: no allocation, no synchronisation, capturable.  A refused call launches nothing and leaves a text in last_error.
+ *     Refused: a null or misaligned pointer, a non-positive extent, an index width other than 2 or 4, a command range outside the index buffer, a workspace
+ *     smaller than the size query's answer, a scissor outside the target (negative offset or extent, or offset + extent beyond width / height), more than
+ *     SAILOR_UI_MAX_COMMANDS commands.
+ * DECISION (the cumulative triangle counts): the caller hands the commands twice, `commands` on the host and `dCommands`, the same array on the device.  The
+ * host copy is what the call checks and sizes its launches from; the device copy is what the kernels read, and k_ui_scan computes the cumulative triangle
+ * counts from it on the device.  The kernels bound every fetch by the buffer sizes themselves, so a device copy that differs from the host copy draws
+ * something else but reads and writes nothing out of bounds. */
+
+/* RHI/Types.h:656-661 VertexP2UV2C1, interleaved, 20 bytes; m_color is fetched as R8G8B8A8_UNORM (Renderer.cpp:78-82) */
+typedef struct SailorVertexP2UV2C1 {
+    float position[2];
+    float uv[2];
+    uint32_t color;
+} SailorVertexP2UV2C1;
+
+/* one DrawIndexed of ImGuiApi.cpp:265-270 under the SetViewport of :247-252: scissor = offset x, offset y, extent x, extent y */
+typedef struct SailorUiCommand {
+    uint32_t firstIndex;   /* IdxOffset + the lists before it */
+    uint32_t indexCount;   /* ElemCount */
+    int32_t vertexOffset;  /* VtxOffset + the lists before it */
+    int32_t scissor[4];
+} SailorUiCommand;
+
+#define SAILOR_UI_MAX_COMMANDS 16384u
+
+/* the workspace of one sailor_hip_ui_draw over at most numTriangles triangles (the sum of indexCount / 3 over the commands): the cumulative counts of
+ * SAILOR_UI_MAX_COMMANDS commands and one set-up record per triangle.  It does not depend on the extent (the blend keeps its pixels in registers); width and
+ * height are checked only.  *out = 0 and INVALID_ARGUMENT for a non-positive extent. */
+SAILOR_HIP_API int sailor_hip_ui_workspace_bytes(uint32_t numTriangles, int32_t width, int32_t height, size_t* out);
+/* Replaces: ImGui_RenderDrawData's draws and the blend of the pass: k_ui_scan (cumulative triangle counts), k_ui_setup (a lane per triangle: rules 1 to 4
+ * into a record), k_ui_blend (a block per 32 x 32 pixels of the band: rules 3 to 7 in primitive order, one store per touched pixel).
+ *   dVertices, numVertices : device, the merged vertex buffer      dIndices, indexBytes, numIndices : device, the merged index buffer, 2 or 4 bytes an index
+ *   commands / dCommands   : host / device copies of the flat command array (see DECISION above)
+ *   scale, translate       : the push constants of ImGuiApi.cpp:118-125       texture : host struct, copied at record time; texels on the device
+ *   dTarget                : device, the band's rows x width float4, blended in place
+ * A band's target holds its own rows only; a band without rows, a draw without commands or without triangles records nothing. */
+SAILOR_HIP_API int sailor_hip_ui_draw(SailorHipContext* ctx, const SailorVertexP2UV2C1* dVertices, uint32_t numVertices, const void* dIndices, uint32_t indexBytes,
+                                      uint32_t numIndices, const SailorUiCommand* commands, const SailorUiCommand* dCommands, uint32_t numCommands,
+                                      const float scale[2], const float translate[2], const SailorTextureDesc* texture, void* dWorkspace, size_t workspaceBytes,
+                                      float* dTarget, int32_t width, int32_t height, const SailorBand* band);
+
+/* ImDrawData as plain data, for sailor_host_ui_flatten: per list its buffer sizes and commands, per command what ImDrawCmd holds */
+#define SAILOR_UI_CALLBACK_NONE 0u
+#define SAILOR_UI_CALLBACK_RESET 1u /* ImDrawCallback_ResetRenderState: re-issues the set-up state, draws nothing */
+#define SAILOR_UI_CALLBACK_USER 2u  /* any other UserCallback: draws nothing */
+typedef struct SailorUiDrawCmd {
+    float clipRect[4];   /* ImDrawCmd::ClipRect: x1, y1, x2, y2 */
+    uint32_t elemCount;
+    uint32_t idxOffset;
+    uint32_t vtxOffset;
+    uint32_t callback;   /* SAILOR_UI_CALLBACK_* */
+} SailorUiDrawCmd;
+typedef struct SailorUiDrawList {
+    uint32_t vtxCount;   /* VtxBuffer.Size */
+    uint32_t idxCount;   /* IdxBuffer.Size */
+    uint32_t firstCmd;   /* the list's commands are cmds[firstCmd .. firstCmd + cmdCount) */
+    uint32_t cmdCount;
+} SailorUiDrawList;
+/* ImGui_SetupRenderState's push constants (:118-125) and ImGui_RenderDrawData's loop (:197-275) in fp32: width = (int)(displaySize.x * framebufferScale.x),
+ * height likewise; *outNumCommands = 0 when either is <= 0.  Otherwise outPushConstants = scale.x, scale.y, translate.x, translate.y and, per command that
+ * is no callback and survives `clipMax <= clipMin` after the clamps, one SailorUiCommand with the global offsets and the scissor of :250-251.  At most
+ * maxCommands are written (outCommands may be NULL to count); *outNumCommands is the number there are.  outWidth / outHeight (may be NULL) get width, height. */
+SAILOR_HIP_API int sailor_host_ui_flatten(const float displayPos[2], const float displaySize[2], const float framebufferScale[2], const SailorUiDrawList* lists,
+                                          uint32_t numLists, const SailorUiDrawCmd* cmds, uint32_t numCmds, float outPushConstants[4], SailorUiCommand* outCommands,
+                                          uint32_t maxCommands, uint32_t* outNumCommands, int32_t* outWidth, int32_t* outHeight);
+
 #ifdef __cplusplus
 }
 #endif

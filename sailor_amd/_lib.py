@@ -219,7 +219,23 @@ class DebugLinesDraw(C.Structure):  # include/sailor_hip.h SailorDebugLinesDraw:
     _fields_ = [("dVertices", C.c_void_p), ("dIndices", C.c_void_p), ("numSegments", C.c_uint32), ("primBase", C.c_uint32)]
 
 
+class UiCommand(C.Structure):  # include/sailor_hip.h SailorUiCommand: one DrawIndexed of ImGui_RenderDrawData under its scissor
+    _fields_ = [("firstIndex", C.c_uint32), ("indexCount", C.c_uint32), ("vertexOffset", C.c_int32), ("scissor", C.c_int32 * 4)]
+
+
+class UiDrawCmd(C.Structure):  # include/sailor_hip.h SailorUiDrawCmd: what an ImDrawCmd holds
+    _fields_ = [("clipRect", C.c_float * 4), ("elemCount", C.c_uint32), ("idxOffset", C.c_uint32), ("vtxOffset", C.c_uint32), ("callback", C.c_uint32)]
+
+
+class UiDrawList(C.Structure):  # include/sailor_hip.h SailorUiDrawList: an ImDrawList's buffer sizes and its run of commands
+    _fields_ = [("vtxCount", C.c_uint32), ("idxCount", C.c_uint32), ("firstCmd", C.c_uint32), ("cmdCount", C.c_uint32)]
+
+
 VERTEX_P3C4_DTYPE = [("position", "<f4", 3), ("color", "<f4", 4)]  # SailorVertexP3C4, 28 bytes
+VERTEX_P2UV2C1_DTYPE = [("position", "<f4", 2), ("uv", "<f4", 2), ("color", "<u4")]  # SailorVertexP2UV2C1, 20 bytes, r in the low byte
+UI_COMMAND_DTYPE = [("firstIndex", "<u4"), ("indexCount", "<u4"), ("vertexOffset", "<i4"), ("scissor", "<i4", 4)]  # SailorUiCommand, 28 bytes
+UI_MAX_COMMANDS = 16384  # SAILOR_UI_MAX_COMMANDS
+UI_CALLBACK_NONE, UI_CALLBACK_RESET, UI_CALLBACK_USER = 0, 1, 2  # SAILOR_UI_CALLBACK_*
 TEXTURE_SRGB = 1        # SAILOR_TEXTURE_SRGB
 SURFACE_CULL_BACK = 1   # SAILOR_SURFACE_CULL_BACK
 SURFACE_ALPHA_CUTOUT = 2  # SAILOR_SURFACE_ALPHA_CUTOUT (sailor_hip_surface_draw_masked only)
@@ -408,6 +424,12 @@ SIGNATURES = {
     "sailor_hip_debug_lines_draw": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(DebugLinesDraw), C.c_int32, C.c_int32, C.POINTER(Band), _P, C.c_size_t]),
     "sailor_hip_debug_lines_resolve": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(DebugLinesDraw), C.c_int32, C.c_int32, C.POINTER(Band), _P, C.c_size_t, _P, _P]),
     "sailor_hip_debug_lines_prims": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint64)]),
+    "sailor_hip_ui_workspace_bytes": (C.c_int, [C.c_uint32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    "sailor_hip_ui_draw": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, _P, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                     C.POINTER(TextureDesc), _P, C.c_size_t, _P, C.c_int32, C.c_int32, C.POINTER(Band)]),
+    "sailor_host_ui_flatten": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(UiDrawList), C.c_uint32, C.POINTER(UiDrawCmd),
+                                         C.c_uint32, C.POINTER(C.c_float), C.POINTER(UiCommand), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int32)]),
 }
 
 _lib = None

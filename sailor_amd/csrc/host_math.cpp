@@ -623,4 +623,57 @@ int sailor_host_csm_plan_passes(SailorCsmSnapshots* state, uint32_t firstSnapsho
     return SAILOR_HIP_OK;
 }
 
+// ImGui_SetupRenderState (Submodules/ImGuiApi.cpp:118-125) and ImGui_RenderDrawData's loop (:197-275), over ImDrawData as plain data.  fp32 throughout;
+// the casts are the reference's: (int) of a product for the size, (int32_t) of the clamped ends and of their DIFFERENCE for the scissor.
+int sailor_host_ui_flatten(const float* displayPos, const float* displaySize, const float* framebufferScale, const SailorUiDrawList* lists, uint32_t numLists,
+                           const SailorUiDrawCmd* cmds, uint32_t numCmds, float* outPushConstants, SailorUiCommand* outCommands, uint32_t maxCommands,
+                           uint32_t* outNumCommands, int32_t* outWidth, int32_t* outHeight)
+{
+    if (!displayPos || !displaySize || !framebufferScale || (numLists && !lists) || (numCmds && !cmds) || !outPushConstants || !outNumCommands)
+        return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    *outNumCommands = 0;
+    // (a product that does not fit an int -- NaN, beyond 2^31 -- has no defined cast: refused)
+    const float fw = displaySize[0] * framebufferScale[0], fh = displaySize[1] * framebufferScale[1];
+    if (!(fw > -2147483648.0f && fw < 2147483648.0f) || !(fh > -2147483648.0f && fh < 2147483648.0f)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    const int width = (int)fw, height = (int)fh; // :198-199
+    if (outWidth) *outWidth = width;
+    if (outHeight) *outHeight = height;
+    outPushConstants[0] = 2.0f / displaySize[0]; // :119-123
+    outPushConstants[1] = 2.0f / displaySize[1];
+    outPushConstants[2] = -1.0f - displayPos[0] * outPushConstants[0];
+    outPushConstants[3] = -1.0f - displayPos[1] * outPushConstants[1];
+    if (width <= 0 || height <= 0) return SAILOR_HIP_OK; // :201-202
+    for (uint32_t n = 0; n < numLists; n++)
+        if ((uint64_t)lists[n].firstCmd + lists[n].cmdCount > numCmds) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    uint64_t globalVtxOffset = 0, globalIdxOffset = 0;
+    uint32_t count = 0;
+    for (uint32_t n = 0; n < numLists; n++) {
+        for (uint32_t i = 0; i < lists[n].cmdCount; i++) {
+            const SailorUiDrawCmd& pcmd = cmds[lists[n].firstCmd + i];
+            if (pcmd.callback != SAILOR_UI_CALLBACK_NONE) continue; // :224-232: a reset re-issues the state this flat form carries once, a user callback draws nothing
+            float minX = (pcmd.clipRect[0] - displayPos[0]) * framebufferScale[0], minY = (pcmd.clipRect[1] - displayPos[1]) * framebufferScale[1]; // :236-237
+            float maxX = (pcmd.clipRect[2] - displayPos[0]) * framebufferScale[0], maxY = (pcmd.clipRect[3] - displayPos[1]) * framebufferScale[1];
+            if (minX < 0.0f) minX = 0.0f; // :240-243
+            if (minY < 0.0f) minY = 0.0f;
+            if (maxX > (float)width) maxX = (float)width;
+            if (maxY > (float)height) maxY = (float)height;
+            if (maxX <= minX || maxY <= minY) continue; // :244-245
+            if (!(maxX > minX) || !(maxY > minY)) continue; // (a NaN ClipRect fails :244's test and would reach an undefined cast: left out)
+            const uint64_t first = (uint64_t)pcmd.idxOffset + globalIdxOffset, vertex = (uint64_t)pcmd.vtxOffset + globalVtxOffset;
+            if (first > 0xFFFFFFFFull || vertex > 0x7FFFFFFFull) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+            if (outCommands && count < maxCommands) {
+                SailorUiCommand& c = outCommands[count];
+                c.firstIndex = (uint32_t)first; c.indexCount = pcmd.elemCount; c.vertexOffset = (int32_t)vertex; // :265-270
+                c.scissor[0] = (int32_t)minX; c.scissor[1] = (int32_t)minY;                                      // :250
+                c.scissor[2] = (int32_t)(maxX - minX); c.scissor[3] = (int32_t)(maxY - minY);                    // :251
+            }
+            count++;
+        }
+        globalIdxOffset += lists[n].idxCount; // :273-274
+        globalVtxOffset += lists[n].vtxCount;
+    }
+    *outNumCommands = count;
+    return SAILOR_HIP_OK;
+}
+
 } // extern "C"

@@ -1072,3 +1072,60 @@ class DebugLinesPass:
 
     def download_keys(self) -> np.ndarray:
         return self.surface.download_keys()
+
+
+class UiPass:
+    """The RenderImGui node's pass (sailor_hip_ui_draw): the flattened commands of a frame's draw data blended in primitive order into the band's rows of an
+    fp32 RGBA target.  Owns the workspace (grown by reserve(), outside any recorded region) and the font texture's descriptor."""
+
+    def __init__(self, ctx: HipContext, width: int, height: int, band: Band | None = None, max_triangles: int = 0):
+        self.ctx, self.W, self.H = ctx, width, height
+        self.band = band if band is not None else host.band_whole_frame(width, height)
+        self.rows = self.band.fbRowCount
+        self.workspace, self.capacity = None, -1
+        self._texture, self._keep = _lib.TextureDesc(None, 0, 0, 0, 0), None
+        self.reserve(max_triangles)
+
+    def reserve(self, num_triangles: int):
+        """a workspace for draws of up to num_triangles triangles (allocates: not inside a capture)"""
+        if num_triangles > self.capacity:
+            n = C.c_size_t()
+            _lib.check(self.ctx._lib.sailor_hip_ui_workspace_bytes(num_triangles, self.W, self.H, C.byref(n)), "sailor_hip_ui_workspace_bytes")
+            self.workspace, self.capacity = torch.empty(n.value, dtype=torch.uint8, device=self.ctx.device), num_triangles
+
+    def set_texture(self, image: np.ndarray | None):
+        """the font atlas: uint8 [h, w, 4], r first (R8G8B8A8_UNORM), or None: a descriptor without texels, which samples as 0"""
+        if image is None:
+            self._texture, self._keep = _lib.TextureDesc(None, 0, 0, 0, 0), None
+            return
+        img = np.ascontiguousarray(image, np.uint8)
+        assert img.ndim == 3 and img.shape[2] == 4 and img.shape[0] > 0 and img.shape[1] > 0, img.shape
+        self._keep = torch.from_numpy(img.view(np.uint32).reshape(img.shape[0], img.shape[1]).view(np.int32)).to(self.ctx.device)
+        self._texture = _lib.TextureDesc(self._keep.data_ptr(), img.shape[1], img.shape[0], 0, 0)
+
+    def draw(self, target: torch.Tensor, vertices: torch.Tensor, indices: torch.Tensor, commands: np.ndarray, d_commands: torch.Tensor | None, scale, translate):
+        """target: float32 [rows, W, 4], blended in place; vertices: 20-byte VertexP2UV2C1 records (uint8 tensor); indices: int16 or int32 tensor;
+        commands: records of _lib.UI_COMMAND_DTYPE on the host, d_commands the same bytes on the device (None without commands)"""
+        assert target.dtype == torch.float32 and target.shape == (self.rows, self.W, 4) and target.is_contiguous()
+        assert indices.element_size() in (2, 4)
+        commands = np.ascontiguousarray(commands, _lib.UI_COMMAND_DTYPE)
+        assert int((commands["indexCount"] // 3).sum()) <= self.capacity, "reserve() more triangles first"
+        self._scale = (C.c_float * 2)(float(scale[0]), float(scale[1]))
+        self._translate = (C.c_float * 2)(float(translate[0]), float(translate[1]))
+        _lib.check(self.ctx._lib.sailor_hip_ui_draw(self.ctx.handle, _ptr(vertices), vertices.numel() * vertices.element_size() // 20, _ptr(indices),
+                                                    indices.element_size(), indices.numel(), commands.ctypes.data if len(commands) else None, _ptr(d_commands),
+                                                    len(commands), self._scale, self._translate, C.byref(self._texture), _ptr(self.workspace),
+                                                    self.workspace.numel(), _ptr(target), self.W, self.H, C.byref(self.band)), "sailor_hip_ui_draw", self.ctx.handle)
+        return target
+
+    def draw_flat(self, target: torch.Tensor, flat: dict, index_bytes: int = 2):
+        """host.ui_flatten's result: uploads the buffers and draws (allocates: not inside a capture)"""
+        dev = self.ctx.device
+        v = torch.from_numpy(np.ascontiguousarray(flat["vertices"]).view(np.uint8).copy()).to(dev)
+        idx = np.ascontiguousarray(flat["indices"], np.uint32)
+        i = torch.from_numpy(idx.astype(np.uint16).view(np.int16) if index_bytes == 2 else idx.view(np.int32)).to(dev)
+        c = np.ascontiguousarray(flat["commands"], _lib.UI_COMMAND_DTYPE)
+        dc = torch.from_numpy(c.view(np.uint8).copy()).to(dev) if len(c) else None
+        self.reserve(int((c["indexCount"] // 3).sum()))
+        self._buffers = (v, i, dc)
+        return self.draw(target, v, i, c, dc, flat["scale"], flat["translate"])

@@ -526,3 +526,102 @@ def debug_sphere(position, radius: float, color) -> np.ndarray:
             pairs.append((v1, v2))
             v3, v4 = v1, v2
     return _debug_lines(pairs, color)
+
+
+# ---- Submodules/ImGuiApi.cpp: draw data for the RenderImGui pass as plain data, and small draw-list builders for callers without ImGui.  Draw data is a dict:
+# display_pos, display_size, framebuffer_scale (pairs) and lists; a list is a dict of vertices (records of _lib.VERTEX_P2UV2C1_DTYPE), indices (unsigned) and
+# cmds; a command is a dict of clip_rect (x1, y1, x2, y2), elem_count, idx_offset, vtx_offset and callback (_lib.UI_CALLBACK_*). ---------------------------------
+def ui_color(r: float, g: float, b: float, a: float) -> int:
+    """IM_COL32 from floats in [0, 1]: r in the low byte"""
+    q = [int(round(min(max(float(c), 0.0), 1.0) * 255.0)) for c in (r, g, b, a)]
+    return q[0] | (q[1] << 8) | (q[2] << 16) | (q[3] << 24)
+
+
+def ui_flatten(draw_data: dict) -> dict:
+    """sailor_host_ui_flatten: -> width, height, scale, translate (the push constants), commands (records of _lib.UI_COMMAND_DTYPE; skipped commands left
+    out), and the merged vertices and indices in list order (ImGui_UpdateDrawData :170-185)"""
+    lists = draw_data.get("lists", [])
+    cl = (_lib.UiDrawList * max(len(lists), 1))()
+    flat = [c for l in lists for c in l["cmds"]]
+    cc = (_lib.UiDrawCmd * max(len(flat), 1))()
+    first = 0
+    for n, l in enumerate(lists):
+        cl[n] = _lib.UiDrawList(len(l["vertices"]), len(l["indices"]), first, len(l["cmds"]))
+        first += len(l["cmds"])
+    for n, c in enumerate(flat):
+        cc[n] = _lib.UiDrawCmd((C.c_float * 4)(*[float(x) for x in c["clip_rect"]]), int(c.get("elem_count", 0)), int(c.get("idx_offset", 0)),
+                               int(c.get("vtx_offset", 0)), int(c.get("callback", _lib.UI_CALLBACK_NONE)))
+    f2 = lambda v: (C.c_float * 2)(*[float(x) for x in v])  # noqa: E731
+    pc, count, w, h = (C.c_float * 4)(), C.c_uint32(), C.c_int32(), C.c_int32()
+    out = (_lib.UiCommand * max(len(flat), 1))()
+    _lib.check(_lib.load().sailor_host_ui_flatten(f2(draw_data["display_pos"]), f2(draw_data["display_size"]), f2(draw_data["framebuffer_scale"]), cl, len(lists), cc,
+                                                  len(flat), pc, out, len(flat), C.byref(count), C.byref(w), C.byref(h)), "sailor_host_ui_flatten")
+    commands = np.frombuffer(bytes(out), _lib.UI_COMMAND_DTYPE)[: count.value].copy()
+    vertices = np.concatenate([np.asarray(l["vertices"], _lib.VERTEX_P2UV2C1_DTYPE) for l in lists]) if lists else np.zeros(0, _lib.VERTEX_P2UV2C1_DTYPE)
+    indices = np.concatenate([np.asarray(l["indices"], np.uint32) for l in lists]) if lists else np.zeros(0, np.uint32)
+    return dict(width=int(w.value), height=int(h.value), scale=np.float32([pc[0], pc[1]]), translate=np.float32([pc[2], pc[3]]), commands=commands,
+                vertices=vertices, indices=indices)
+
+
+class UiDrawList:
+    """An ImDrawList as far as the pass reads it: vertices, indices and commands.  clip() opens a command (as PushClipRect does), the shape calls append to
+    the open one.  white_uv: the atlas texel ImGui keeps white for untextured shapes (ImFontAtlas::TexUvWhitePixel)."""
+
+    def __init__(self, white_uv=(0.0, 0.0)):
+        self.white_uv, self._v, self._i, self.cmds = white_uv, [], [], []
+
+    def clip(self, x1: float, y1: float, x2: float, y2: float):
+        self.cmds.append(dict(clip_rect=(x1, y1, x2, y2), elem_count=0, idx_offset=len(self._i), vtx_offset=0, callback=_lib.UI_CALLBACK_NONE))
+        return self
+
+    def callback(self, kind: int):
+        """AddCallback: a command that draws nothing; the next shape needs a clip() of its own"""
+        self.cmds.append(dict(clip_rect=(0.0, 0.0, 0.0, 0.0), elem_count=0, idx_offset=len(self._i), vtx_offset=0, callback=kind))
+        return self
+
+    def _add(self, verts, idx):
+        assert self.cmds and self.cmds[-1]["callback"] == _lib.UI_CALLBACK_NONE, "open a command with clip() first"
+        base = len(self._v)
+        self._v += verts
+        self._i += [base + k for k in idx]
+        self.cmds[-1]["elem_count"] += len(idx)
+        return self
+
+    def quad(self, x0, y0, x1, y1, uv0, uv1, color: int):
+        """PrimRectUV: a, b, c and a, c, d over the corners (x0, y0), (x1, y0), (x1, y1), (x0, y1) -- a glyph quad when uv spans a glyph's cell"""
+        return self._add([((x0, y0), (uv0[0], uv0[1]), color), ((x1, y0), (uv1[0], uv0[1]), color), ((x1, y1), (uv1[0], uv1[1]), color),
+                          ((x0, y1), (uv0[0], uv1[1]), color)], [0, 1, 2, 0, 2, 3])
+
+    def rect(self, x0, y0, x1, y1, color: int):
+        """PrimRect: a filled rect, two triangles, every vertex at the white pixel"""
+        return self.quad(x0, y0, x1, y1, self.white_uv, self.white_uv, color)
+
+    def triangle(self, p0, p1, p2, colors, uvs=None):
+        uvs = uvs or [self.white_uv] * 3
+        c = colors if isinstance(colors, (list, tuple)) else [colors] * 3
+        return self._add([(tuple(p0), tuple(uvs[0]), c[0]), (tuple(p1), tuple(uvs[1]), c[1]), (tuple(p2), tuple(uvs[2]), c[2])], [0, 1, 2])
+
+    def rect_aa(self, x0, y0, x1, y1, color: int, fringe: float = 1.0):
+        """AddConvexPolyFilled with anti-aliasing over a rect: the inner rect in `color` and, round it, a fringe of thin triangles whose outer vertices
+        have alpha 0 (inner ring pulled in by half the fringe, outer ring pushed out by half)"""
+        h, clear = 0.5 * fringe, color & 0x00FFFFFF
+        inner = [(x0 + h, y0 + h), (x1 - h, y0 + h), (x1 - h, y1 - h), (x0 + h, y1 - h)]
+        outer = [(x0 - h, y0 - h), (x1 + h, y0 - h), (x1 + h, y1 + h), (x0 - h, y1 + h)]
+        verts = [(p, self.white_uv, color) for p in inner] + [(p, self.white_uv, clear) for p in outer]
+        idx = [0, 1, 2, 0, 2, 3]
+        for k in range(4):
+            n = (k + 1) % 4
+            idx += [k, 4 + k, 4 + n, k, 4 + n, n]
+        return self._add(verts, idx)
+
+    def data(self) -> dict:
+        v = np.zeros(len(self._v), _lib.VERTEX_P2UV2C1_DTYPE)
+        for k, (p, uv, c) in enumerate(self._v):
+            v["position"][k], v["uv"][k], v["color"][k] = p, uv, c
+        return dict(vertices=v, indices=np.asarray(self._i, np.uint32), cmds=[dict(c) for c in self.cmds])
+
+
+def ui_draw_data(lists, display_size, display_pos=(0.0, 0.0), framebuffer_scale=(1.0, 1.0)) -> dict:
+    """ImDrawData over UiDrawList builders or list dicts"""
+    return dict(display_pos=tuple(display_pos), display_size=tuple(display_size), framebuffer_scale=tuple(framebuffer_scale),
+                lists=[l.data() if isinstance(l, UiDrawList) else l for l in lists])

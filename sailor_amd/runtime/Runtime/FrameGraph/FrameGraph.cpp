@@ -48,6 +48,7 @@ template class Sailor::Framegraph::TFrameGraphNode<PostProcessNode>;
 template class Sailor::Framegraph::TFrameGraphNode<BlitNode>;
 template class Sailor::Framegraph::TFrameGraphNode<SkyNode>;
 template class Sailor::Framegraph::TFrameGraphNode<DebugDrawNode>;
+template class Sailor::Framegraph::TFrameGraphNode<RenderImGuiNode>;
 
 // ---- RHIFrameGraph ----------------------------------------------------------------------------------------------------------
 UboFrameData RHIFrameGraph::FillFrameData(RHICommandListPtr transferCmdList, RHISceneViewSnapshot& snapshot, const UboFrameData& previousFrame, float deltaTime,
@@ -822,6 +823,54 @@ void DebugDrawNode::Process(RHIFrameGraphPtr frameGraph, RHICommandListPtr, RHIC
 }
 
 void DebugDrawNode::Clear() {}
+
+// ---- RenderImGuiNode (FrameGraph/RenderImGuiNode.cpp:21-60) over ImGuiApi::ImGui_RenderDrawData (Submodules/ImGuiApi.cpp:92-127, :190-276) --------------
+const char* RenderImGuiNode::m_name = "RenderImGui";
+
+void RenderImGuiNode::Process(RHIFrameGraphPtr frameGraph, RHICommandListPtr, RHICommandListPtr commandList, const RHISceneViewSnapshot& sceneView)
+{
+    auto commands = Renderer::GetDriverCommands();
+    commands->BeginDebugRegion(commandList, GetName());
+    auto resolved = [&](const char* name) -> RHITexturePtr { // GetRHIResource / GetResolvedAttachment
+        if (auto t = GetRHIResource(name).DynamicCast<RHITexture>()) return t;
+        auto it = m_unresolvedResourceParams.find(name);
+        return it == m_unresolvedResourceParams.end() ? RHITexturePtr() : frameGraph->GetRenderTarget(it->second);
+    };
+    RHITexturePtr target = resolved("color"), depthAttachment = frameGraph->GetRenderTarget("DepthBuffer"); // (:28-38)
+    if (!target || !depthAttachment) return;                                                                // (:40-41, without EndDebugRegion there too)
+    const RHIImGuiDrawData* ui = sceneView.m_drawImGui;
+    if (!ui || !ui->m_material || !ui->m_vertexBuffer || !ui->m_indexBuffer) { // (no task: nothing was recorded, nothing to replay)
+        commands->EndDebugRegion(commandList);
+        return;
+    }
+    // ImGui_RenderDrawData (:197-275) through the flat form: the commands that are no callback and survive the clip test, with global offsets and scissors
+    float pushConstants[4];
+    uint32_t count = 0;
+    int32_t width = 0, height = 0;
+    TVector<SailorUiCommand> flat(ui->m_cmds.size() ? ui->m_cmds.size() : 1);
+    const int st = sailor_host_ui_flatten(ui->m_displayPos, ui->m_displaySize, ui->m_framebufferScale, ui->m_lists.data(), (uint32_t)ui->m_lists.size(), ui->m_cmds.data(),
+                                          (uint32_t)ui->m_cmds.size(), pushConstants, flat.data(), (uint32_t)flat.size(), &count, &width, &height);
+    if (st == SAILOR_HIP_OK && width > 0 && height > 0) {
+        commands->ImageMemoryBarrier(commandList, target, EImageLayout::ColorAttachmentOptimal);
+        commands->BeginRenderPass(commandList, TVector<RHITexturePtr> { target }, depthAttachment); // RenderSecondaryCommandBuffers(..., no clear) (:45-58)
+        // ImGui_SetupRenderState (:92-127)
+        commands->BindMaterial(commandList, ui->m_material);
+        commands->BindVertexBuffer(commandList, ui->m_vertexBuffer, 0);
+        commands->BindIndexBuffer(commandList, ui->m_indexBuffer, 0, true);
+        commands->SetViewport(commandList, 0, 0, (float)width, (float)height, ivec2 { 0, 0 }, ivec2 { width, height }, 0, 1.0f);
+        commands->PushConstants(commandList, ui->m_material, sizeof(pushConstants), pushConstants);
+        for (uint32_t i = 0; i < count && i < flat.size(); i++) { // (:236-270)
+            const SailorUiCommand& c = flat[i];
+            commands->SetViewport(commandList, 0, 0, (float)width, (float)height, ivec2 { c.scissor[0], c.scissor[1] }, ivec2 { c.scissor[2], c.scissor[3] }, 0, 1.0f);
+            commands->BindShaderBindings(commandList, ui->m_material, { ui->m_shaderBindings });
+            commands->DrawIndexed(commandList, c.indexCount, 1, c.firstIndex, (uint32_t)c.vertexOffset, 0);
+        }
+        commands->EndRenderPass(commandList);
+    }
+    commands->EndDebugRegion(commandList);
+}
+
+void RenderImGuiNode::Clear() {}
 
 // ---- BloomNode (FrameGraph/BloomNode.cpp:17-148) -------------------------------------------------------------------------------------------
 const char* BloomNode::m_name = "Bloom";

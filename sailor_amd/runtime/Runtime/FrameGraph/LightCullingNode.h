@@ -239,6 +239,22 @@ protected:
     static const char* m_name;
 };
 
+// The editor's UI over the finished frame: Runtime/FrameGraph/RenderImGuiNode.{h,cpp}.  Resources (DefaultRenderer.renderer, the last entry): "color" =
+// BackBuffer, "depthStencil" = DepthBuffer.  The reference waits for the task that recorded ImGuiApi::ImGui_RenderDrawData (Submodules/ImGuiApi.cpp:190-276)
+// into a SECONDARY command list and replays it (RenderSecondaryCommandBuffers, no clear, :21-60); this mirror has no secondary lists, so the node records the
+// same calls DIRECTLY into its command list from the snapshot's draw data: BindMaterial, BindVertexBuffer, BindIndexBuffer (16-bit), SetViewport,
+// PushConstants, and per command SetViewport with its scissor, BindShaderBindings and DrawIndexed.
+class RenderImGuiNode : public TFrameGraphNode<RenderImGuiNode> {
+public:
+    static const char* GetName() { return m_name; }
+    void Process(RHIFrameGraphPtr frameGraph, RHI::RHICommandListPtr transferCommandList, RHI::RHICommandListPtr commandList,
+                 const RHI::RHISceneViewSnapshot& sceneView) override;
+    void Clear() override;
+
+protected:
+    static const char* m_name;
+};
+
 // The mip pyramid over `Main`: Runtime/FrameGraph/BloomNode.h.  Resource (DefaultRenderer.renderer:303-304): "bloom" = the HDR target with its mip chain,
 // rewritten in place; vec4 "threshold", "knee", "bloomIntensity", "dirtIntensity" (their .x).  `u_dirt_texture` is the graph's "g_lensDirtSampler".
 // In the reference this is a TFrameGraphNode<BloomNode> (BloomNode.h:10, :43) and registers under "Bloom"; here the class derives from the base directly

@@ -1,5 +1,6 @@
 #include "HipGraphicsDriver.h"
 #include <dlfcn.h>
+#include <algorithm>
 #include "../../RHI/Renderer.h"
 
 #include <cstdio>
@@ -86,7 +87,7 @@ RHIShaderPtr HipGraphicsDriver::CreateShader(const std::string& assetPath, const
         "Shaders/ComputeDepthHighZ.shader", "Shaders/ComputeHistogram.shader", "Shaders/ComputeAverageLuminance.shader", "Shaders/ComputeBrdfLut.shader",
         "Shaders/ComputeIrradianceMap.shader", "Shaders/ComputeEnvMap_IBL.shader", "Shaders/ShadowCaster.shader", "Shaders/LinearizeDepth.shader",
         "Shaders/Tonemapping.shader", "Shaders/Blur.shader", "Shaders/HBAO.shader", "Shaders/HBAO_Blur.shader", "Shaders/Sky.shader", "Shaders/ComputeBloomDownscale.shader",
-        "Shaders/ComputeBloomUpscale.shader", "Shaders/Blit.shader", "Shaders/ChromaticAberation.shader", "Shaders/Gizmo.shader" };
+        "Shaders/ComputeBloomUpscale.shader", "Shaders/Blit.shader", "Shaders/ChromaticAberation.shader", "Shaders/Gizmo.shader", "Shaders/ImGuiUI.shader" };
     auto shader = RHIShaderPtr::Make(assetPath, defines);
     shader->m_bIsReady = false;
     for (const char* name : routed) if (assetPath == name) shader->m_bIsReady = true;
@@ -875,6 +876,44 @@ int HipGraphicsDriver::RecordDebugLines(const RHITexturePtr& color, const RHITex
     return sailor_hip_debug_lines_resolve(m_ctx, viewProjection, &d, W, H, &band, m_surfaceWorkspace->m_hip.m_devicePtr, bytes, (float*)color->m_buffer->m_hip.m_devicePtr, depthPtr);
 }
 
+// Grows the workspace of the UI pass for draws of up to numTriangles triangles.  An allocation: called where draw data is handed over and where a pass is
+// recorded, never from a submitted command.
+bool HipGraphicsDriver::ReserveUiWorkspace(uint32_t numTriangles)
+{
+    size_t bytes = 0;
+    if (sailor_hip_ui_workspace_bytes(numTriangles, 1, 1, &bytes) != SAILOR_HIP_OK) return false;
+    if (!m_uiWorkspace || m_uiWorkspace->m_size < bytes) m_uiWorkspace = CreateBuffer(bytes);
+    return (bool)m_uiWorkspace;
+}
+
+// RenderImGuiNode's pass: every ImGuiUI.shader draw the pass recorded, in order, as one sailor_hip_ui_draw into the colour attachment (no depth test, read or
+// write: the depth attachment is not touched)
+int HipGraphicsDriver::RecordUi(const RHITexturePtr& color, const RHIBufferPtr& vertices, const RHIBufferPtr& indices, bool bIndexUint16, const TVector<uint8_t>& pushConstants,
+                                const RHITexturePtr& font, const TVector<SailorUiCommand>& uiCommands, const RHIBufferPtr& dCommands)
+{
+    if (!color || !color->m_buffer || !vertices || !indices || !dCommands || !m_uiWorkspace || pushConstants.size() < 16) return SAILOR_HIP_ERR_INVALID_ARGUMENT; // a missing binding
+    if (m_worldSize > 1) return SAILOR_HIP_ERR_UNSUPPORTED; // (the pass runs on whole frames here)
+    if (color->m_format != EFormat::R32G32B32A32_SFLOAT) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    const int W = color->GetExtent().x, H = color->GetExtent().y;
+    SailorBand band;
+    sailor_hip_band_whole_frame(W, H, &band);
+    float pc[4];
+    memcpy(pc, pushConstants.data(), 16);
+    SailorTextureDesc texture {};
+    if (font && font->m_buffer && font->m_format == EFormat::R8G8B8A8_UNORM) {
+        texture.texels = (const uint32_t*)font->m_buffer->m_hip.m_devicePtr;
+        texture.width = font->GetExtent().x; texture.height = font->GetExtent().y;
+    }
+    const uint32_t indexBytes = bIndexUint16 ? 2u : 4u;
+    int st = sailor_hip_buffer_upload(m_ctx, dCommands->m_hip.m_devicePtr, 0, uiCommands.data(), uiCommands.size() * sizeof(SailorUiCommand));
+    if (st != SAILOR_HIP_OK) return st;
+    BeforeBufferWrite(color->m_buffer->m_hip.m_devicePtr);
+    return sailor_hip_ui_draw(m_ctx, (const SailorVertexP2UV2C1*)vertices->m_hip.m_devicePtr, (uint32_t)(vertices->m_size / sizeof(SailorVertexP2UV2C1)),
+                              indices->m_hip.m_devicePtr, indexBytes, (uint32_t)(indices->m_size / indexBytes), uiCommands.data(),
+                              (const SailorUiCommand*)dCommands->m_hip.m_devicePtr, (uint32_t)uiCommands.size(), pc, pc + 2, &texture, m_uiWorkspace->m_hip.m_devicePtr,
+                              m_uiWorkspace->m_size, (float*)color->m_buffer->m_hip.m_devicePtr, W, H, &band);
+}
+
 int HipGraphicsDriver::RecordSurfaceEnd(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& color, const RHITexturePtr& depthToStore)
 {
     if (!m_surfaceBegun) return SAILOR_HIP_ERR_INVALID_ARGUMENT; // a draw of the pass was refused: nothing to resolve
@@ -923,10 +962,22 @@ void HipGraphicsDriver::BeginRenderPass(RHICommandListPtr cmd, const TVector<RHI
     cmd->m_casterDraws = 0;
     cmd->m_surfaceDraws = 0;
     cmd->m_surfaceCutout = false;
+    cmd->m_uiCommands.clear();
+    cmd->m_scissorOffset = { 0, 0 };
+    cmd->m_scissorExtent = { -1, -1 };
 }
 
 void HipGraphicsDriver::BindVertexBuffer(RHICommandListPtr cmd, RHIBufferPtr vertexBuffer, uint32_t) { cmd->m_vertexBuffer = vertexBuffer; }
-void HipGraphicsDriver::BindIndexBuffer(RHICommandListPtr cmd, RHIBufferPtr indexBuffer, uint32_t, bool) { cmd->m_indexBuffer = indexBuffer; }
+void HipGraphicsDriver::BindIndexBuffer(RHICommandListPtr cmd, RHIBufferPtr indexBuffer, uint32_t, bool bUint16InsteadOfUint32)
+{
+    cmd->m_indexBuffer = indexBuffer;
+    cmd->m_bIndexUint16 = bUint16InsteadOfUint32;
+}
+void HipGraphicsDriver::SetViewport(RHICommandListPtr cmd, float, float, float, float, ivec2 scissorOffset, ivec2 scissorExtent, float, float)
+{
+    cmd->m_scissorOffset = scissorOffset; // (the viewport itself is the attachment's extent on this path; the scissor is per draw)
+    cmd->m_scissorExtent = scissorExtent;
+}
 void HipGraphicsDriver::PushConstants(RHICommandListPtr cmd, RHIMaterialPtr, size_t size, const void* ptr)
 {
     cmd->m_pushConstants.assign((const uint8_t*)ptr, (const uint8_t*)ptr + size); // captured at record time (vkCmdPushConstants)
@@ -950,6 +1001,22 @@ void HipGraphicsDriver::EndRenderPass(RHICommandListPtr cmd)
         TVector<RHIShaderBindingSetPtr> bindings = cmd->m_boundBindings;
         RHITexturePtr depthToStore = cmd->m_surfaceCutout ? cmd->m_depthAttachment : RHITexturePtr();
         cmd->m_hip.m_commands.push_back([this, bindings, color, depthToStore]() { return RecordSurfaceEnd(bindings, color, depthToStore); });
+    }
+    if (!cmd->m_uiCommands.empty()) { // RenderImGuiNode's pass: one ordered blend over every command the pass recorded
+        RHITexturePtr color = cmd->m_colorAttachments.empty() ? RHITexturePtr() : cmd->m_colorAttachments[0];
+        RHIBufferPtr vb = cmd->m_uiVertexBuffer, ib = cmd->m_uiIndexBuffer;
+        RHITexturePtr font = cmd->m_uiTexture;
+        TVector<uint8_t> pc = cmd->m_uiPushConstants;
+        TVector<SailorUiCommand> ui = std::move(cmd->m_uiCommands);
+        const bool index16 = cmd->m_bUiIndexUint16;
+        // at record time, not at submit: the device copy of the commands and a workspace for their triangles
+        uint64_t triangles = 0;
+        for (auto& c : ui) triangles += c.indexCount / 3u;
+        ReserveUiWorkspace((uint32_t)std::min<uint64_t>(triangles, 0xFFFFFFFFull));
+        RHIBufferPtr dCommands = CreateBuffer(ui.size() * sizeof(SailorUiCommand));
+        cmd->m_hip.m_commands.push_back([this, color, vb, ib, index16, pc, font, ui, dCommands]() { return RecordUi(color, vb, ib, index16, pc, font, ui, dCommands); });
+        cmd->m_uiCommands.clear();
+        cmd->m_uiVertexBuffer.Clear(); cmd->m_uiIndexBuffer.Clear(); cmd->m_uiTexture.Clear();
     }
     cmd->m_depthAttachment.Clear();
     cmd->m_casterDraws = 0;
@@ -1021,6 +1088,24 @@ void HipGraphicsDriver::DrawIndexed(RHICommandListPtr cmd, uint32_t indexCount, 
         cmd->m_hip.m_commands.push_back([this, color, depth, vb, ib, pc, indexCount, firstIndex, vertexOffset]() {
             return RecordDebugLines(color, depth, vb, ib, pc, indexCount, firstIndex, vertexOffset);
         });
+        return;
+    }
+    if (name == "Shaders/ImGuiUI.shader" && cmd->m_boundMaterial->m_topology == EPrimitiveTopology::TriangleList &&
+        cmd->m_boundMaterial->m_blendMode == EBlendMode::AlphaBlending) { // a command of ImGui_RenderDrawData (ImGuiApi.cpp:265-270)
+        if (cmd->m_uiCommands.empty()) { // the state of ImGui_SetupRenderState: one vertex buffer, one index buffer, one texture and one set of push constants a pass
+            cmd->m_uiVertexBuffer = cmd->m_vertexBuffer; cmd->m_uiIndexBuffer = cmd->m_indexBuffer; cmd->m_bUiIndexUint16 = cmd->m_bIndexUint16;
+            cmd->m_uiPushConstants = cmd->m_pushConstants;
+            cmd->m_uiTexture.Clear();
+            for (auto& set : cmd->m_boundBindings)
+                if (set) if (auto b = set->Find("sTexture")) if (!b->m_textures.empty()) cmd->m_uiTexture = b->m_textures[0];
+        }
+        SailorUiCommand c {};
+        c.firstIndex = firstIndex; c.indexCount = indexCount; c.vertexOffset = (int32_t)vertexOffset;
+        RHITexturePtr color = cmd->m_colorAttachments.empty() ? RHITexturePtr() : cmd->m_colorAttachments[0];
+        const bool whole = cmd->m_scissorExtent.x < 0 || cmd->m_scissorExtent.y < 0;
+        c.scissor[0] = whole ? 0 : cmd->m_scissorOffset.x; c.scissor[1] = whole ? 0 : cmd->m_scissorOffset.y;
+        c.scissor[2] = whole ? (color ? color->GetExtent().x : 0) : cmd->m_scissorExtent.x; c.scissor[3] = whole ? (color ? color->GetExtent().y : 0) : cmd->m_scissorExtent.y;
+        cmd->m_uiCommands.push_back(c);
         return;
     }
     RHITexturePtr target = cmd->m_colorAttachments.empty() ? RHITexturePtr() : cmd->m_colorAttachments[0];

@@ -48,6 +48,10 @@
 //   "Shaders/Gizmo.shader" of a LineList material drawn with DrawIndexed (DebugContext::DrawDebugMesh inside DebugDrawNode's pass) -> sailor_hip_surface_begin from
 //       the pass' depth attachment, sailor_hip_debug_lines_draw, sailor_hip_debug_lines_resolve into the colour and the depth attachment (push constant viewProjection,
 //       VertexP3C4 vertices, 32-bit indices)
+//   "Shaders/ImGuiUI.shader" of a TriangleList material under AlphaBlending drawn with DrawIndexed (RenderImGuiNode's pass) -> the commands of one render pass are
+//       gathered, each with the scissor SetViewport left, and EndRenderPass issues ONE sailor_hip_ui_draw over them into the colour attachment (push constants
+//       scale / translate, VertexP2UV2C1 vertices, 16- or 32-bit indices, `sTexture` of the bound set as the SailorTextureDesc): order across commands lives
+//       inside the kernel.  The workspace is grown by ReserveUiWorkspace (whoever hands draw data over calls it) or when the pass is recorded, never at submit.
 //   "Shaders/ShadowCaster.shader" [EVSM]  -> sailor_hip_raster_depth into the pass' depth attachment, and at EndRenderPass sailor_hip_shadow_resolve
 //                                            into its colour attachment (push constant lightMatrix, set 1 `data`, vertex positions, 32-bit indices)
 #pragma once
@@ -76,6 +80,7 @@ public:
     // the Bloom node class, the opt-in exists only because older tests of this mirror use MotionBlur.shader as their example of a shader WITHOUT an entry point
     // (a PostProcess entry that must be created and record nothing); in the engine the backend would simply route both.  false for any other path.
     bool EnableShader(const std::string& assetPath);
+    bool ReserveUiWorkspace(uint32_t numTriangles); // the UI pass' workspace, grown outside the submitted commands (see "Shaders/ImGuiUI.shader" above)
     bool IsShaderEnabled(const std::string& assetPath) const { return m_enabledShaders.count(assetPath) != 0; }
 
     // IGraphicsDriver
@@ -135,6 +140,8 @@ public:
     void BindVertexBuffer(RHI::RHICommandListPtr cmd, RHI::RHIBufferPtr vertexBuffer, uint32_t offset) override;
     void BindIndexBuffer(RHI::RHICommandListPtr cmd, RHI::RHIBufferPtr indexBuffer, uint32_t offset, bool bUint16InsteadOfUint32 = false) override;
     void PushConstants(RHI::RHICommandListPtr cmd, RHI::RHIMaterialPtr material, size_t size, const void* ptr) override;
+    void SetViewport(RHI::RHICommandListPtr cmd, float x, float y, float width, float height, RHI::ivec2 scissorOffset, RHI::ivec2 scissorExtent, float minDepth,
+                     float maxDepth) override;
     void EndRenderPass(RHI::RHICommandListPtr cmd) override;
     void BindMaterial(RHI::RHICommandListPtr cmd, RHI::RHIMaterialPtr material) override;
     void BindShaderBindings(RHI::RHICommandListPtr cmd, RHI::RHIMaterialPtr material, const TVector<RHI::RHIShaderBindingSetPtr>& bindings) override;
@@ -152,6 +159,8 @@ private:
                           uint32_t instanceCount, uint32_t firstIndex, uint32_t vertexOffset, uint32_t firstInstance, uint32_t flags);
     int RecordDebugLines(const RHI::RHITexturePtr& color, const RHI::RHITexturePtr& depth, const RHI::RHIBufferPtr& vertices, const RHI::RHIBufferPtr& indices,
                          const TVector<uint8_t>& pushConstants, uint32_t indexCount, uint32_t firstIndex, uint32_t vertexOffset);
+    int RecordUi(const RHI::RHITexturePtr& color, const RHI::RHIBufferPtr& vertices, const RHI::RHIBufferPtr& indices, bool bIndexUint16,
+                 const TVector<uint8_t>& pushConstants, const RHI::RHITexturePtr& font, const TVector<SailorUiCommand>& uiCommands, const RHI::RHIBufferPtr& dCommands);
     int RecordSurfaceEnd(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& color, const RHI::RHITexturePtr& depthToStore);
     int RecordBrdfLut(const TVector<RHI::RHIShaderBindingSetPtr>& bindings);
     int RecordIrradianceMap(const TVector<RHI::RHIShaderBindingSetPtr>& bindings);
@@ -192,6 +201,7 @@ private:
     // the surface pass of the render pass being executed (Standard.shader draws): workspace (keys, descriptors), the planes the resolve writes and the shade
     // reads, the shade's radiance; the running primBase; begun = the first draw's sailor_hip_surface_begin went through
     RHI::RHIBufferPtr m_surfaceWorkspace, m_surfacePlanes, m_surfaceRadiance;
+    RHI::RHIBufferPtr m_uiWorkspace;
     uint64_t m_surfacePrimBase = 0;
     bool m_surfaceBegun = false;
     int32_t m_cullW = 0, m_cullH = 0, m_cullLights = 0; // geometry of the last light cull: locates its shading-order hint in the workspace

@@ -56,6 +56,8 @@ public:
     virtual void BindVertexBuffer(RHICommandListPtr cmd, RHIBufferPtr vertexBuffer, uint32_t offset) = 0;                                           // :316
     virtual void BindIndexBuffer(RHICommandListPtr cmd, RHIBufferPtr indexBuffer, uint32_t offset, bool bUint16InsteadOfUint32 = false) = 0;          // :317
     virtual void PushConstants(RHICommandListPtr cmd, RHIMaterialPtr material, size_t size, const void* ptr) = 0;                                      // :324
+    virtual void SetViewport(RHICommandListPtr cmd, float x, float y, float width, float height, ivec2 scissorOffset, ivec2 scissorExtent, float minDepth,
+                             float maxDepth) = 0;                                                                                                          // :320 (the scissor is what the path reads)
     virtual void EndRenderPass(RHICommandListPtr cmd) = 0;                                                                                          // :273
     virtual void BindMaterial(RHICommandListPtr cmd, RHIMaterialPtr material) = 0;                                                                  // :276
     virtual void BindShaderBindings(RHICommandListPtr cmd, RHIMaterialPtr material, const TVector<RHIShaderBindingSetPtr>& bindings) = 0;           // :282

@@ -34,6 +34,22 @@ struct RHISceneViewSnapshot {
     // :81 m_debugDrawSecondaryCmdList is a secondary command list the world's DebugContext recorded DrawDebugMesh into; secondary lists are not mirrored, so
     // the snapshot carries the context itself and DebugDrawNode records its draw directly (null = no debug drawing)
     const class DebugContext* m_debugContext = nullptr;
+    // :82 m_drawImGui is the task that records ImGuiApi::ImGui_RenderDrawData into a secondary command list; here the finished frame's draw data itself, as
+    // plain arrays, with what ImGuiApi's backend data holds for it (null = no UI this frame).  RenderImGuiNode records its draws directly.
+    const struct RHIImGuiDrawData* m_drawImGui = nullptr;
+};
+
+// ImDrawData (DisplayPos, DisplaySize, FramebufferScale, the lists' merged buffers as ImGui_UpdateDrawData :170-185 uploads them, the commands) and
+// ImGuiApi::Data: the material of ImGui_Init (:295-332), its shader bindings with the font atlas as `sTexture`, the frame's vertex and index buffer
+struct RHIImGuiDrawData {
+    float m_displayPos[2] = { 0, 0 }, m_displaySize[2] = { 0, 0 }, m_framebufferScale[2] = { 1, 1 };
+    TVector<VertexP2UV2C1> m_vertices;      // every list's VtxBuffer, in list order
+    TVector<uint16_t> m_indices;            // every list's IdxBuffer (sizeof(ImDrawIdx) == 2)
+    TVector<SailorUiDrawList> m_lists;      // per list: its buffer sizes and its run of commands
+    TVector<SailorUiDrawCmd> m_cmds;        // per command: ClipRect, ElemCount, IdxOffset, VtxOffset, the callback kind
+    RHIMaterialPtr m_material;
+    RHIShaderBindingSetPtr m_shaderBindings;
+    RHIBufferPtr m_vertexBuffer, m_indexBuffer;
 };
 
 } // namespace Sailor::RHI

@@ -60,6 +60,7 @@ struct ivec2 { int32_t x = 0, y = 0; };
 struct ivec4 { int32_t x = 0, y = 0, z = 0, w = 0; };
 
 using UboFrameData = SailorUboFrameData; // RHI/Types.h:751-761
+using VertexP2UV2C1 = SailorVertexP2UV2C1; // RHI/Types.h:656-661: m_position, m_uv, m_color (R8G8B8A8_UNORM, Renderer.cpp:78-82): ImDrawVert
 
 // RHI/Buffer.h: a device allocation.  m_hip.m_devicePtr is either owned (created through IGraphicsDriver) or wrapped.
 class RHIBuffer : public RHIResource {
@@ -193,6 +194,14 @@ public:
     bool m_surfaceCutout = false;                              // ... one of them with ALPHA_CUTOUT: the pass ends with the depth write (sailor_hip_surface_store_depth)
     TRefPtr<class RHIMaterial> m_boundMaterial;
     TVector<TRefPtr<class RHIShaderBindingSet>> m_boundBindings;
+    bool m_bIndexUint16 = false;                               // BindIndexBuffer(..., bUint16InsteadOfUint32)
+    ivec2 m_scissorOffset, m_scissorExtent;                    // SetViewport's scissor; an extent of (-1, -1): none set, the whole attachment
+    // ImGuiUI.shader draws recorded in the current pass, each with the scissor that was set when it was recorded: the pass ends with ONE ordered blend over them
+    TVector<SailorUiCommand> m_uiCommands;
+    TVector<uint8_t> m_uiPushConstants;
+    TRefPtr<class RHIBuffer> m_uiVertexBuffer, m_uiIndexBuffer;
+    bool m_bUiIndexUint16 = false;
+    TRefPtr<class RHITexture> m_uiTexture;                     // `sTexture` of the bound set
 };
 using RHICommandListPtr = TRefPtr<RHICommandList>;
 

@@ -11,6 +11,7 @@
 #include "Runtime/AssetRegistry/FrameGraph/FrameGraphParser.h"
 #include "Runtime/AssetRegistry/World/WorldPrefabImporter.h"
 #include "scene_tags.h"
+#include <algorithm>
 #include <cstdio>
 #include <vector>
 
@@ -32,6 +33,7 @@ struct SailorRuntime {
     RHIBufferPtr surface, radiance;
     std::unique_ptr<EcsSweepSystem> sweep;
     DebugContext debug; // the world's DebugContext (Engine/World.h): the snapshot points at it
+    RHIImGuiDrawData ui; // the frame's ImDrawData and ImGuiApi's backend data: the snapshot points at it while there is draw data
     int frames = 0;
 };
 
@@ -54,6 +56,8 @@ RT_API void sailor_rt_destroy(SailorRuntime* rt)
     rt->sweep.reset();
     rt->lighting.reset();
     rt->debug.Clear();
+    rt->snapshot.m_drawImGui = nullptr;
+    rt->ui = RHIImGuiDrawData();
     rt->depth.Clear(); rt->surface.Clear(); rt->radiance.Clear(); rt->depthHighZ.Clear();
     rt->lightCulling.Clear(); rt->renderScene.Clear(); rt->linearizeDepth.Clear(); rt->environment.Clear(); rt->rawDepth.Clear();
     rt->queueNodes.clear();
@@ -845,6 +849,74 @@ RT_API int sailor_rt_debug_vertices(SailorRuntime* rt, float* outVertices, int m
     if (outVertices)
         for (size_t i = 0; i < v.size() && (int)i < maxVertices; i++) memcpy(outVertices + 7 * i, &v[i], sizeof(SailorVertexP3C4));
     return (int)v.size();
+}
+
+// ---- the frame's ImGui draw data (Submodules/ImGuiApi.cpp): what ImGui::Render() left, as plain arrays -- per list its buffer sizes and its run of commands,
+// the lists' vertex and 16-bit index buffers one behind the other.  Mirrors ImGui_Init (:295-332: the material of ImGuiUI.shader -- TriangleList,
+// AlphaBlending --, the RGBA8 font atlas as `sTexture`; done at the first call and whenever a font is given) and ImGui_UpdateDrawData (:129-188: create or
+// grow the frame's vertex and index buffer, upload every list).  numLists == 0 or a null vertex pointer takes the draw data away.  Returns the number of
+// commands that will draw, -1 on a bad argument.
+RT_API int sailor_rt_set_ui_draw_data(SailorRuntime* rt, const float* displayPos2, const float* displaySize2, const float* framebufferScale2, const void* vertices,
+                                      uint32_t numVertices, const uint16_t* indices, uint32_t numIndices, const SailorUiDrawList* lists, uint32_t numLists,
+                                      const SailorUiDrawCmd* cmds, uint32_t numCmds, const void* fontRgba8, int fontWidth, int fontHeight)
+{
+    if (!rt) return -1;
+    if (!vertices || !numLists) { rt->snapshot.m_drawImGui = nullptr; return 0; }
+    if (!displayPos2 || !displaySize2 || !framebufferScale2 || !indices || !lists || (numCmds && !cmds) || !numVertices || !numIndices) return -1;
+    uint64_t vtx = 0, idx = 0;
+    for (uint32_t n = 0; n < numLists; n++) {
+        if ((uint64_t)lists[n].firstCmd + lists[n].cmdCount > numCmds) return -1;
+        vtx += lists[n].vtxCount; idx += lists[n].idxCount;
+    }
+    if (vtx != numVertices || idx != numIndices) return -1; // the lists' buffers are exactly what was handed over
+    auto* driver = static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver());
+    auto commands = Renderer::GetDriverCommands();
+    RHIImGuiDrawData& ui = rt->ui;
+    if (!ui.m_material) { // ImGui_Init
+        auto shader = driver->CreateShader("Shaders/ImGuiUI.shader");
+        if (!shader || !shader->IsReady()) return -1;
+        ui.m_material = driver->CreateMaterial(shader);
+        ui.m_material->m_blendMode = EBlendMode::AlphaBlending;
+        ui.m_material->m_topology = EPrimitiveTopology::TriangleList;
+        ui.m_material->m_bDoubleSided = true; // ECullMode::None
+    }
+    if (fontRgba8 && fontWidth > 0 && fontHeight > 0) {
+        auto font = driver->CreateTexture(fontRgba8, (size_t)fontWidth * fontHeight * 4, ivec2 { fontWidth, fontHeight }, EFormat::R8G8B8A8_UNORM);
+        if (!font) return -1;
+        ui.m_shaderBindings = driver->CreateShaderBindings();
+        driver->AddSamplerToShaderBindings(ui.m_shaderBindings, "sTexture", font, 0);
+    }
+    if (!ui.m_shaderBindings) ui.m_shaderBindings = driver->CreateShaderBindings(); // no atlas yet: `sTexture` unbound, which samples as 0
+    for (int k = 0; k < 2; k++) { ui.m_displayPos[k] = displayPos2[k]; ui.m_displaySize[k] = displaySize2[k]; ui.m_framebufferScale[k] = framebufferScale2[k]; }
+    ui.m_vertices.assign((const VertexP2UV2C1*)vertices, (const VertexP2UV2C1*)vertices + numVertices);
+    ui.m_indices.assign(indices, indices + numIndices);
+    ui.m_lists.assign(lists, lists + numLists);
+    ui.m_cmds.assign(cmds, cmds + numCmds);
+    // ImGui_UpdateDrawData
+    const size_t vertexSize = ui.m_vertices.size() * sizeof(VertexP2UV2C1), indexSize = ui.m_indices.size() * sizeof(uint16_t);
+    if (!ui.m_vertexBuffer || ui.m_vertexBuffer->m_size < vertexSize) ui.m_vertexBuffer = driver->CreateBuffer(vertexSize);
+    if (!ui.m_indexBuffer || ui.m_indexBuffer->m_size < indexSize) ui.m_indexBuffer = driver->CreateBuffer((indexSize + 3) / 4 * 4);
+    if (!ui.m_vertexBuffer || !ui.m_indexBuffer) return -1;
+    auto transferCmd = driver->CreateCommandList();
+    size_t vOffset = 0, iOffset = 0;
+    for (uint32_t n = 0; n < numLists; n++) { // (:173-185)
+        const size_t vSize = lists[n].vtxCount * sizeof(VertexP2UV2C1), iSize = lists[n].idxCount * sizeof(uint16_t);
+        if (vSize) commands->UpdateBuffer(transferCmd, ui.m_vertexBuffer, (const char*)ui.m_vertices.data() + vOffset, vSize, vOffset);
+        if (iSize) commands->UpdateBuffer(transferCmd, ui.m_indexBuffer, (const char*)ui.m_indices.data() + iOffset, iSize, iOffset);
+        vOffset += vSize; iOffset += iSize;
+    }
+    driver->SubmitCommandList(transferCmd);
+    // what will draw, and a workspace for it: grown here, outside the frame's recorded commands
+    float pc[4];
+    uint32_t count = 0;
+    if (sailor_host_ui_flatten(ui.m_displayPos, ui.m_displaySize, ui.m_framebufferScale, ui.m_lists.data(), numLists, ui.m_cmds.data(), numCmds, pc, nullptr, 0, &count, nullptr,
+                               nullptr) != SAILOR_HIP_OK)
+        return -1;
+    uint64_t triangles = 0;
+    for (auto& c : ui.m_cmds) triangles += c.elemCount / 3u;
+    if (!driver->ReserveUiWorkspace((uint32_t)std::min<uint64_t>(triangles, 0xFFFFFFFFull))) return -1;
+    rt->snapshot.m_drawImGui = &rt->ui;
+    return (int)count;
 }
 
 RT_API int sailor_rt_process_frame(SailorRuntime* rt)

@@ -81,6 +81,7 @@ def load() -> C.CDLL:
         rt.sailor_rt_debug_draw_sphere.argtypes = [P, P, C.c_float, P, C.c_float]
         rt.sailor_rt_debug_tick.argtypes = [P, C.c_float]
         rt.sailor_rt_debug_vertices.argtypes = [P, P, C.c_int]
+        rt.sailor_rt_set_ui_draw_data.argtypes = [P, P, P, P, P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, P, C.c_int, C.c_int]
         rt.sailor_rt_process_frame_overwriting_lists.argtypes = [P, P, C.c_size_t, P, C.c_size_t]
         rt.sailor_rt_set_frame_split.argtypes = [P, C.c_int, C.c_int, P]
         rt.sailor_rt_exchange_light_lists.argtypes = [P, P, C.c_size_t, P, C.c_size_t]
@@ -423,6 +424,35 @@ class Runtime:
         if n > 0:
             self.rt.sailor_rt_debug_vertices(self.h, out.ctypes.data, n)
         return out
+
+    def set_ui_draw_data(self, draw_data: dict | None, font: np.ndarray | None = None) -> int:
+        """The frame's ImGui draw data (sailor_amd.host.ui_draw_data: display_pos, display_size, framebuffer_scale, lists of vertices, indices and cmds), which
+        the RenderImGui node draws over its colour attachment; None takes it away.  font: the atlas, uint8 [h, w, 4] (R8G8B8A8_UNORM), bound as `sTexture`
+        from this call on.  Indices are 16-bit, as ImDrawIdx is.  Returns the number of commands that will draw."""
+        lists = draw_data.get("lists", []) if draw_data else []
+        if not lists or sum(len(l["vertices"]) for l in lists) == 0:
+            assert self.rt.sailor_rt_set_ui_draw_data(self.h, None, None, None, None, 0, None, 0, None, 0, None, 0, None, 0, 0) == 0
+            return 0
+        flat = [c for l in lists for c in l["cmds"]]
+        cl, cc, first = (_lib.UiDrawList * len(lists))(), (_lib.UiDrawCmd * max(len(flat), 1))(), 0
+        for n, l in enumerate(lists):
+            cl[n] = _lib.UiDrawList(len(l["vertices"]), len(l["indices"]), first, len(l["cmds"]))
+            first += len(l["cmds"])
+        for n, c in enumerate(flat):
+            cc[n] = _lib.UiDrawCmd((C.c_float * 4)(*[float(x) for x in c["clip_rect"]]), int(c.get("elem_count", 0)), int(c.get("idx_offset", 0)),
+                                   int(c.get("vtx_offset", 0)), int(c.get("callback", _lib.UI_CALLBACK_NONE)))
+        v = np.ascontiguousarray(np.concatenate([np.asarray(l["vertices"], _lib.VERTEX_P2UV2C1_DTYPE) for l in lists]))
+        i = np.concatenate([np.asarray(l["indices"], np.uint32) for l in lists])
+        assert len(i) and int(i.max()) < 65536, "ImDrawIdx is 16 bits"
+        i = np.ascontiguousarray(i.astype(np.uint16))
+        pos, size, fbs = (np.ascontiguousarray(draw_data[k], np.float32) for k in ("display_pos", "display_size", "framebuffer_scale"))
+        f = None if font is None else np.ascontiguousarray(font, np.uint8)
+        assert f is None or (f.ndim == 3 and f.shape[2] == 4)
+        n = self.rt.sailor_rt_set_ui_draw_data(self.h, pos.ctypes.data, size.ctypes.data, fbs.ctypes.data, v.ctypes.data, len(v), i.ctypes.data, len(i), cl, len(lists), cc,
+                                               len(flat), None if f is None else f.ctypes.data, 0 if f is None else f.shape[1], 0 if f is None else f.shape[0])
+        if n < 0:
+            raise _lib.SailorHipError(-1, "sailor_rt_set_ui_draw_data")
+        return n
 
     def process_frame(self) -> int:
         return self.rt.sailor_rt_process_frame(self.h)
