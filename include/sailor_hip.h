@@ -1190,8 +1190,8 @@ SAILOR_HIP_API int sailor_host_csm_plan_passes(SailorCsmSnapshots* snapshots, ui
  * triangle the near plane cut in two); low word 0 = no primitive.  Varyings are perspective-correct: l_k = float(e_k) / area, q_k = l_k / w_k,
  * s = (q0 + q1) + q2, b_k = q_k / s, a = (a0 b0 + a1 b1) + a2 b2; a vertex cut on the near plane gets a = aI + (aO - aI) t with the position's t.
  * texture() is the base level, bilinear, Repeat over RGBA8 texels; SAILOR_TEXTURE_SRGB decodes r, g, b per tap through sailor_host_srgb_table before
- * filtering.  NOT reproduced: the implicit mip selection of texture() (textures have one level here), anisotropy,
- * Standard_glTF.shader.  A sampler index >= numTextures reads descriptor 0 (the reference binds g_defaultSampler there), a materialInstance >=
+ * filtering.  NOT reproduced: the implicit mip selection of texture() (textures have one level here), anisotropy.
+ * (Standard_glTF.shader: the glTF section below.)  A sampler index >= numTextures reads descriptor 0 (the reference binds g_defaultSampler there), a materialInstance >=
  * numMaterials reads material 0, a descriptor without texels samples as 0: no fetch leaves a table.
  * All entry points record only (no allocation, no synchronisation, capturable); a refused call launches nothing and leaves a text in last_error. */
 
@@ -1241,7 +1241,7 @@ typedef struct SailorSurfaceDraw {
     uint32_t numTriangles;
     uint32_t numDrawn;
     uint32_t primBase;                          /* the order of the draw's first primitive: the previous draw's primBase + its sailor_hip_surface_draw_prims */
-    uint32_t flags;                             /* SAILOR_SURFACE_CULL_BACK; SAILOR_SURFACE_ALPHA_CUTOUT through sailor_hip_surface_draw_masked only */
+    uint32_t flags;                             /* SAILOR_SURFACE_CULL_BACK; SAILOR_SURFACE_ALPHA_CUTOUT through sailor_hip_surface_draw_masked and _draw_gltf only; SAILOR_SURFACE_GLTF (below) through _draw_gltf only */
     uint32_t firstInstance;
     uint32_t _pad;
 } SailorSurfaceDraw;
@@ -1293,8 +1293,8 @@ SAILOR_HIP_API int sailor_hip_surface_draw_prims(uint32_t numTriangles, uint32_t
  *  4. A discarded fragment does not exist: it writes no key and no depth and takes no part in ties.  Discard is a pure function of the fragment, so the
  *     keys stay order-free; the decision is taken in the draw, before the key is issued (exact inside test and z -> plain load of the pixel's key -> alpha
  *     only if the key would win -> atomicMax only for a survivor).  sailor_hip_surface_resolve, _composite and sailor_hip_surface_draw are unchanged.
- *  5. NOT reproduced: Standard_glTF.shader (alphaCutoff as a material field: the threshold here is the constant 0.5), the Transparent queue, masked shadow
- *     casters, and a DepthPrepass node in the runtime mirror (a Masked prepass is begin(opaque depth), the masked draws, sailor_hip_surface_store_depth).
+ *  5. NOT reproduced: the Transparent queue, masked shadow casters (Standard_glTF.shader's alphaCutoff as a material field: sailor_hip_surface_draw_gltf,
+ *     below; the threshold HERE is the constant 0.5), and a DepthPrepass node in the runtime mirror (a Masked prepass is begin(opaque depth), the masked draws, sailor_hip_surface_store_depth).
  * Both entry points record only; a refused call launches nothing and leaves its text in last_error. */
 
 /* Replaces: one DrawIndexed of a material with or without ALPHA_CUTOUT: k_surface_visibility_masked.  The checks and refusals of sailor_hip_surface_draw;
@@ -1308,6 +1308,80 @@ SAILOR_HIP_API int sailor_hip_surface_draw_masked(SailorHipContext* ctx, const S
  * high word of every key of the band into the band's rows of dDepth, the raw width x height depth attachment of the WHOLE frame. */
 SAILOR_HIP_API int sailor_hip_surface_store_depth(SailorHipContext* ctx, const void* dWorkspace, size_t workspaceBytes, float* dDepth, int32_t width,
                                                   int32_t height, const SailorBand* band);
+
+/* ---- glTF materials: Standard_glTF.shader in the surface pass (surface_gltf.hip) -------------------------------------------------------------------
+ * Replaces: Content/Shaders/Standard_glTF.shader, the shader AssetRegistry/Model/ModelImporter.cpp:156-231 gives every imported model, where it differs from
+ * Standard.shader: the vertex stage's tangentBasis (:136-138), MaterialData (:42-58), the material half of the fragment stage (:389-396), the emissive
+ * term (:399, :432) and the ALPHA_CUTOUT threshold (:411).  The light loop, CalculateLighting and AmbientLighting are Standard.shader's under other field
+ * names, so the shade kernels are unchanged: this section PRODUCES their inputs (the three planes, the `ao` plane of SailorIblDesc) and adds the emissive
+ * term behind them.  A pass may mix both shaders; the flag of the draw that owns a pixel decides.
+ * Pinned:
+ *  1. One material table.  SailorGltfMaterialData is the std430 image of :42-58 and has SailorMaterialData's 80-byte array stride, so `dMaterials` stays ONE
+ *     array of 80-byte slots (the engine's single material SSBO); a slot is read as SailorGltfMaterialData by a draw that carries SAILOR_SURFACE_GLTF and as
+ *     SailorMaterialData by one that does not.  A materialInstance >= numMaterials reads slot 0 as the record of the draw that asks.
+ *  2. The position transform (:130-133) is Standard.shader's: a glTF draw without ALPHA_CUTOUT issues sailor_hip_surface_draw's keys bit for bit.
+ *  3. ALPHA_CUTOUT: rules 1-4 of the masked section with alpha = (baseColorFactor[3] * tA.w) * a[8], tA fetched through baseColorSampler, and a fragment
+ *     discarded iff alpha < alphaCutoff -- one fp32 compare: a NaN on either side survives, alphaCutoff == 0 discards nothing (not even alpha 0, nor -0).
+ *  4. tangentBasis: varyings 9..17 of a vertex are N * (T | B | Nv) column by column, (N[0] a0 + N[1] a1) + N[2] a2 with N[c] the columns of
+ *     N = transpose(inverse(mat3(model))), m[c][r] = model[4 c + r], inverse in glm's 3 x 3 form, one rounding per written operation:
+ *       det = + m00 (m11 m22 - m21 m12) - m10 (m01 m22 - m21 m02) + m20 (m01 m12 - m11 m02)        (left to right), oneOverDet = 1.0f / det
+ *       I00 = + (m11 m22 - m21 m12) oneOverDet   I10 = - (m10 m22 - m20 m12) oneOverDet   I20 = + (m10 m21 - m20 m11) oneOverDet
+ *       I01 = - (m01 m22 - m21 m02) oneOverDet   I11 = + (m00 m22 - m20 m02) oneOverDet   I21 = - (m00 m21 - m20 m01) oneOverDet
+ *       I02 = + (m01 m12 - m11 m02) oneOverDet   I12 = - (m00 m12 - m10 m02) oneOverDet   I22 = + (m00 m11 - m10 m01) oneOverDet
+ *     N[c][r] = I[r][c].  A singular model gives non-finite normals; they pass through.  Every other varying and the interpolation are the surface pass's.
+ *  5. The fetches of a glTF pixel, each the surface pass's texture() under its descriptor's own sRGB flag (ModelImporter leaves orm, occlusion and emissive
+ *     textures at the sRGB default and only the normal map UNORM; no special case here): tA (baseColorSampler), tO (ormSampler; ONE fetch, .z and .y used),
+ *     tOcc = .x of occlusionSampler, tE (emissiveSampler), tN (normalSampler).
+ *       P0 = (worldPosition, (baseColorFactor[3] tA.w) a[8])       P2 = ((baseColorFactor[k] tA.k) a[5 + k], metallicFactor tO.z)      P1.w = roughnessFactor tO.y
+ *       n = normalize(2 tN - 1) as in the surface pass, then n *= normalScale on all three components, then P1.xyz = normalize(tangentBasis * n)
+ *       emissive = (emissiveFactor[k] tE.k for k = 0..2, tOcc)          (emissiveFactor[3] is not read)
+ *       aoOut = (tOcc < aoIn) ? tOcc : aoIn        GLSL's min(x, y) = y < x ? y : x with x = g_AO (:392).  A NaN aoIn stays NaN; a NaN tOcc leaves aoIn.
+ *     The SSBO's occlusionStrength is overwritten at :392 and never read.
+ *  6. A pixel owned by a draw without SAILOR_SURFACE_GLTF gets sailor_hip_surface_resolve's three planes bit for bit, emissive (0, 0, 0, 1) and aoOut = aoIn's
+ *     bits; an uncovered pixel the same.  aoIn is 1.0f everywhere if dAoInOrNull is NULL.
+ *  7. The composite adds the emissive term behind the shade: rgb = emissive.rgb + radiance.rgb, one fp32 add per channel.  The reference sums
+ *     ((emissive + ao ambient) + L1) + ...; the shade has formed fma(ambient, ao, sum L) already, so this is ONE re-association, inside the shade's bound.
+ * NOT reproduced: the Transparent queue (alphaMode BLEND), masked shadow casters.
+ * All entry points record only (no allocation, no synchronisation, capturable); a refused call launches nothing and leaves its text in last_error. */
+
+/* Standard_glTF.shader:42-58 MaterialData, std430: two vec4 (0, 16), five floats (32..48), five uints (52..68), padded to the vec4 alignment: 80 bytes */
+typedef struct SailorGltfMaterialData {
+    float baseColorFactor[4];
+    float emissiveFactor[4];
+    float metallicFactor;
+    float roughnessFactor;
+    float occlusionStrength;
+    float normalScale;
+    float alphaCutoff;
+    uint32_t baseColorSampler;
+    uint32_t normalSampler;
+    uint32_t ormSampler;
+    uint32_t occlusionSampler;
+    uint32_t emissiveSampler;
+    uint32_t _pad[2];
+} SailorGltfMaterialData;
+
+#define SAILOR_SURFACE_GLTF 4u /* the draw's material is Standard_glTF.shader's: sailor_hip_surface_draw_gltf only; the two other draw calls refuse it */
+
+/* Replaces: one DrawIndexed of a Standard_glTF.shader material, with or without ALPHA_CUTOUT: k_surface_visibility_gltf.  The arguments, checks and refusals
+ * of sailor_hip_surface_draw_masked; flags must hold SAILOR_SURFACE_GLTF and may hold CULL_BACK and ALPHA_CUTOUT; the descriptor is stored with the flag,
+ * from where sailor_hip_surface_resolve_gltf reads it.  dMaterials: the one table of rule 1. */
+SAILOR_HIP_API int sailor_hip_surface_draw_gltf(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSurfaceDraw* draw,
+                                                const SailorPerInstanceData* dInstances, const SailorMaterialData* dMaterials, uint32_t numMaterials,
+                                                const SailorTextureDesc* dTextures, uint32_t numTextures, uint32_t drawIndex, int32_t width, int32_t height,
+                                                const SailorBand* band, void* dWorkspace, size_t workspaceBytes);
+/* Replaces: sailor_hip_surface_resolve for a pass that may hold glTF draws: k_surface_resolve_gltf.  Its arguments, and
+ *   dAoInOrNull  : device, the band's rows x width floats: g_AO at the pixel (what the shade's SailorIblDesc.ao would be); NULL = 1.0f
+ *   dAoOutOrNull : device out, the band's rows x width floats: rule 5's aoOut, what the shade reads as SailorIblDesc.ao instead; may be dAoInOrNull itself
+ *   dEmissive    : device out, float4 per pixel of the band: rule 5's emissive, for sailor_hip_surface_composite_gltf */
+SAILOR_HIP_API int sailor_hip_surface_resolve_gltf(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorPerInstanceData* dInstances,
+                                                   const SailorMaterialData* dMaterials, uint32_t numMaterials, const SailorTextureDesc* dTextures, uint32_t numTextures,
+                                                   int32_t width, int32_t height, const SailorBand* band, const void* dWorkspace, size_t workspaceBytes,
+                                                   float* dSurface, size_t planeStride, float* dDepthOutOrNull, uint8_t* dCoverageOrNull,
+                                                   const float* dAoInOrNull, float* dAoOutOrNull, float* dEmissive);
+/* Replaces: sailor_hip_surface_composite for such a pass: target = covered ? (emissive.rgb + radiance.rgb, radiance.a) : target (rule 7). */
+SAILOR_HIP_API int sailor_hip_surface_composite_gltf(SailorHipContext* ctx, const float* dRadiance, const float* dEmissive, const void* dWorkspace,
+                                                     size_t workspaceBytes, float* dTarget, int32_t width, int32_t height, const SailorBand* band);
 
 /* ---- DebugDraw: the line-list pass of the Gizmo material (debug_lines.hip) ---------------------------------------------------------------------
  * Replaces: the draw FrameGraph/DebugDrawNode.cpp:19-79 replays -- RHI/DebugContext.cpp:382-398 (DrawDebugMesh: one DrawIndexed over the line list that

@@ -206,6 +206,12 @@ class MaterialData(C.Structure):  # Standard.shader:164-178, std430
                 ("roughnessSampler", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class GltfMaterialData(C.Structure):  # Standard_glTF.shader:42-58, std430
+    _fields_ = [("baseColorFactor", C.c_float * 4), ("emissiveFactor", C.c_float * 4), ("metallicFactor", C.c_float), ("roughnessFactor", C.c_float),
+                ("occlusionStrength", C.c_float), ("normalScale", C.c_float), ("alphaCutoff", C.c_float), ("baseColorSampler", C.c_uint32),
+                ("normalSampler", C.c_uint32), ("ormSampler", C.c_uint32), ("occlusionSampler", C.c_uint32), ("emissiveSampler", C.c_uint32), ("_pad", C.c_uint32 * 2)]
+
+
 class TextureDesc(C.Structure):  # include/sailor_hip.h SailorTextureDesc: one entry of Standard.shader:124 textureSamplers[]
     _fields_ = [("texels", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("flags", C.c_uint32), ("_pad", C.c_uint32)]
 
@@ -239,12 +245,17 @@ UI_CALLBACK_NONE, UI_CALLBACK_RESET, UI_CALLBACK_USER = 0, 1, 2  # SAILOR_UI_CAL
 TEXTURE_SRGB = 1        # SAILOR_TEXTURE_SRGB
 SURFACE_CULL_BACK = 1   # SAILOR_SURFACE_CULL_BACK
 SURFACE_ALPHA_CUTOUT = 2  # SAILOR_SURFACE_ALPHA_CUTOUT (sailor_hip_surface_draw_masked only)
+SURFACE_GLTF = 4        # SAILOR_SURFACE_GLTF (sailor_hip_surface_draw_gltf only)
 # the same records as NumPy dtypes (what the tests and upload helpers build)
 VERTEX_DTYPE = [("texcoord", "<f4", 2), ("position", "<f4", 3), ("normal", "<f4", 3), ("tangent", "<f4", 3), ("bitangent", "<f4", 3), ("color", "<f4", 4)]
 MATERIAL_DTYPE = [("albedo", "<f4", 4), ("ambient", "<f4", 4), ("emission", "<f4", 4), ("metallic", "<f4"), ("roughness", "<f4"), ("ao", "<f4"),
                   ("albedoSampler", "<u4"), ("metalnessSampler", "<u4"), ("normalSampler", "<u4"), ("roughnessSampler", "<u4"), ("_pad", "<u4")]
+# SailorGltfMaterialData (Standard_glTF.shader:42-58, std430): the same 80-byte slot of the one material table, read by a draw that carries SURFACE_GLTF
+GLTF_MATERIAL_DTYPE = [("baseColorFactor", "<f4", 4), ("emissiveFactor", "<f4", 4), ("metallicFactor", "<f4"), ("roughnessFactor", "<f4"),
+                       ("occlusionStrength", "<f4"), ("normalScale", "<f4"), ("alphaCutoff", "<f4"), ("baseColorSampler", "<u4"), ("normalSampler", "<u4"),
+                       ("ormSampler", "<u4"), ("occlusionSampler", "<u4"), ("emissiveSampler", "<u4"), ("_pad", "<u4", 2)]
 
-assert C.sizeof(VertexP3N3T3B3UV2C4) == 72 and C.sizeof(MaterialData) == 80
+assert C.sizeof(VertexP3N3T3B3UV2C4) == 72 and C.sizeof(MaterialData) == 80 and C.sizeof(GltfMaterialData) == 80
 assert C.sizeof(TextureDesc) == 24 and C.sizeof(SurfaceDraw) == 48
 assert C.sizeof(UboFrameData) == 232 and C.sizeof(LightCullPushConstants) == 88 and C.sizeof(LightShaderData) == 112
 
@@ -418,6 +429,11 @@ SIGNATURES = {
     "sailor_hip_surface_draw_masked": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(SurfaceDraw), _P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32,
                                                  C.POINTER(Band), _P, C.c_size_t]),
     "sailor_hip_surface_store_depth": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_int32, C.c_int32, C.POINTER(Band)]),
+    "sailor_hip_surface_draw_gltf": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(SurfaceDraw), _P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32,
+                                               C.POINTER(Band), _P, C.c_size_t]),
+    "sailor_hip_surface_resolve_gltf": (C.c_int, [_P, C.POINTER(UboFrameData), _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, C.c_int32, C.POINTER(Band), _P, C.c_size_t,
+                                                  _P, C.c_size_t, _P, _P, _P, _P, _P]),
+    "sailor_hip_surface_composite_gltf": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P, C.c_int32, C.c_int32, C.POINTER(Band)]),
     "sailor_hip_surface_keys_offset": (C.c_size_t, []),
     "sailor_host_srgb_table": (C.c_int, [C.POINTER(C.c_float)]),
     "sailor_hip_surface_draw_prims": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),

@@ -14,7 +14,7 @@
 // The depth of a fragment and everything in front of it (clip, cut, snap, edges, top-left) are raster.hip's, so that the depth is the prepass's bit for
 // bit.  raster.hip keeps its set-up functions static and reads tightly packed positions; the few of them needed here are COPIED in surface_common.h
 // (surf_cut, surf_floor_div256, surf_edge, surf_top_left, and surface_setup = raster_setup over interleaved vertices that also reports where each vertex came
-// from), which this file shares with surface_masked.hip (the Masked queue: ALPHA_CUTOUT in the draw).
+// from), which this file shares with surface_masked.hip (the Masked queue: ALPHA_CUTOUT in the draw) and surface_gltf.hip (Standard_glTF.shader).
 #include "surface_common.h"
 
 
@@ -148,25 +148,7 @@ __global__ __launch_bounds__(256) void k_surface_visibility(Mat4 P, Mat4 V, Sail
     }
 }
 
-// ---- the resolve ----------------------------------------------------------------------------------------------------------------------------------
-// varying c of source vertex v under the instance's model m (Standard.shader:128-138): 0-1 texcoord, 2-4 worldPosition = (model * vec4(p, 1)).xyz / .w,
-// 5-8 color, 9-17 tangentBasis = mat3(model) * mat3(inTangent, inBitangent, inNormal), column by column.  c is a compile-time constant where it is called.
-__device__ __forceinline__ float surf_varying(const float* __restrict__ v, const float* __restrict__ m, int c)
-{
-    if (c < 2) return v[c];
-    if (c < 5) {
-        const int r = c - 2;
-        const float x = v[2], y = v[3], z = v[4];
-        const float a = ((m[r] * x + m[4 + r] * y) + m[8 + r] * z) + m[12 + r] * 1.0f;
-        const float w = ((m[3] * x + m[7] * y) + m[11] * z) + m[15] * 1.0f;
-        return a / w;
-    }
-    if (c < 9) return v[14 + (c - 5)];
-    const int col = (c - 9) / 3, r = (c - 9) % 3;
-    const float* __restrict__ a = v + (col == 0 ? 8 : (col == 1 ? 11 : 5));
-    return (m[r] * a[0] + m[4 + r] * a[1]) + m[8 + r] * a[2];
-}
-
+// ---- the resolve (surf_varying: surface_common.h) ---------------------------------------------------------------------------------------------------
 
 __global__ __launch_bounds__(256) void k_surface_resolve(Mat4 P, Mat4 V, const float* __restrict__ instances, const SailorMaterialData* __restrict__ materials,
                                                          uint32_t numMaterials, const SailorTextureDesc* __restrict__ textures, uint32_t numTextures, int W, int H,

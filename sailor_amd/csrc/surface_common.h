@@ -1,5 +1,6 @@
-// What the two surface-pass translation units share (surface.hip: the Opaque queue; surface_masked.hip: the Masked queue with ALPHA_CUTOUT): the set-up
-// copied from raster.hip, the depth test of one fragment, the workspace layout, the texture taps and the checks of the entry points.
+// What the surface-pass translation units share (surface.hip: the Opaque queue; surface_masked.hip: the Masked queue with ALPHA_CUTOUT; surface_gltf.hip:
+// Standard_glTF.shader's materials): the set-up copied from raster.hip, the depth test of one fragment, the workspace layout, the varyings of a vertex, the
+// texture taps and the checks of the entry points.
 #pragma once
 #include "common.h"
 #include "sampling.h"
@@ -187,6 +188,24 @@ __device__ __forceinline__ float surf_texture_alpha(const uint32_t* __restrict__
     const RepeatTap X = repeat_tap(width, u), Y = repeat_tap(height, v);
     const uint32_t a = texels[Y.i0 * width + X.i0], c = texels[Y.i0 * width + X.i1], e = texels[Y.i1 * width + X.i0], f = texels[Y.i1 * width + X.i1];
     return lerp2(unorm8(a >> 24), unorm8(c >> 24), unorm8(e >> 24), unorm8(f >> 24), X.a, Y.a);
+}
+
+// varying c of source vertex v under the instance's model m (Standard.shader:128-138): 0-1 texcoord, 2-4 worldPosition = (model * vec4(p, 1)).xyz / .w,
+// 5-8 color, 9-17 tangentBasis = mat3(model) * mat3(inTangent, inBitangent, inNormal), column by column.  c is a compile-time constant where it is called.
+__device__ __forceinline__ float surf_varying(const float* __restrict__ v, const float* __restrict__ m, int c)
+{
+    if (c < 2) return v[c];
+    if (c < 5) {
+        const int r = c - 2;
+        const float x = v[2], y = v[3], z = v[4];
+        const float a = ((m[r] * x + m[4 + r] * y) + m[8 + r] * z) + m[12 + r] * 1.0f;
+        const float w = ((m[3] * x + m[7] * y) + m[11] * z) + m[15] * 1.0f;
+        return a / w;
+    }
+    if (c < 9) return v[14 + (c - 5)];
+    const int col = (c - 9) / 3, r = (c - 9) % 3;
+    const float* __restrict__ a = v + (col == 0 ? 8 : (col == 1 ? 11 : 5));
+    return (m[r] * a[0] + m[4 + r] * a[1]) + m[8 + r] * a[2];
 }
 
 // ---- what every entry point checks ------------------------------------------------------------------------------------------------------------------

@@ -971,16 +971,21 @@ class SurfacePass:
 
     def draw(self, frame: UboFrameData, vertices: torch.Tensor, indices: torch.Tensor, instances: torch.Tensor, instance_ids: torch.Tensor | None = None,
              num_drawn: int | None = None, first_instance: int = 0, cull_back: bool = False, alpha_cutout: bool = False, materials: torch.Tensor | None = None,
-             textures: torch.Tensor | None = None, num_textures: int = 0):
+             textures: torch.Tensor | None = None, num_textures: int = 0, gltf: bool = False):
         """vertices: 72-byte records; indices: int32, 3 per triangle; instances: the 96-byte PerInstanceData SSBO; instance_ids: int32 or None.
         alpha_cutout: the ALPHA_CUTOUT permutation (Standard.shader:403-408) through sailor_hip_surface_draw_masked, which needs the resolve's material and
-        texture tables"""
+        texture tables.  gltf: the draw's material is Standard_glTF.shader's (sailor_hip_surface_draw_gltf); such a pass ends with resolve_gltf / composite_gltf"""
         if num_drawn is None:
             num_drawn = instance_ids.numel() if instance_ids is not None else instances.numel() * instances.element_size() // 96 - first_instance
         nt = indices.numel() // 3
-        flags = (_lib.SURFACE_CULL_BACK if cull_back else 0) | (_lib.SURFACE_ALPHA_CUTOUT if alpha_cutout else 0)
+        flags = (_lib.SURFACE_CULL_BACK if cull_back else 0) | (_lib.SURFACE_ALPHA_CUTOUT if alpha_cutout else 0) | (_lib.SURFACE_GLTF if gltf else 0)
         d = _lib.SurfaceDraw(_ptr(vertices), _ptr(indices), _ptr(instance_ids), nt, num_drawn, self.prim_base, flags, first_instance, 0)
-        if alpha_cutout:
+        if gltf:
+            _lib.check(self.ctx._lib.sailor_hip_surface_draw_gltf(self.ctx.handle, C.byref(frame), C.byref(d), _ptr(instances), _ptr(materials),
+                                                                  0 if materials is None else materials.numel() * materials.element_size() // 80, _ptr(textures),
+                                                                  num_textures, self.draw_index, self.W, self.H, C.byref(self.band), _ptr(self.workspace),
+                                                                  self.workspace.numel()), "sailor_hip_surface_draw_gltf", self.ctx.handle)
+        elif alpha_cutout:
             _lib.check(self.ctx._lib.sailor_hip_surface_draw_masked(self.ctx.handle, C.byref(frame), C.byref(d), _ptr(instances), _ptr(materials),
                                                                     0 if materials is None else materials.numel() * materials.element_size() // 80, _ptr(textures),
                                                                     num_textures, self.draw_index, self.W, self.H, C.byref(self.band), _ptr(self.workspace),
@@ -1018,6 +1023,32 @@ class SurfacePass:
             assert t.dtype == torch.float32 and t.shape == (self.rows, self.W, 4) and t.is_contiguous()
         _lib.check(self.ctx._lib.sailor_hip_surface_composite(self.ctx.handle, _ptr(radiance), _ptr(self.workspace), self.workspace.numel(), _ptr(target), self.W,
                                                               self.H, C.byref(self.band)), "sailor_hip_surface_composite", self.ctx.handle)
+        return target
+
+    def resolve_gltf(self, frame: UboFrameData, instances: torch.Tensor, materials: torch.Tensor, textures: torch.Tensor, num_textures: int,
+                     ao_in: torch.Tensor | None = None, want_depth: bool = True, want_coverage: bool = True, want_ao: bool = True):
+        """resolve() for a pass that may hold glTF draws.  ao_in: g_AO over the band, float32 [rows, W], or None (1 everywhere).
+        -> (surface, depth | None, coverage | None, ao_out float32 [rows, W] | None -- what the shade reads as its IBL desc's ao --, emissive float32 [rows, W, 4])"""
+        dev = self.ctx.device
+        assert ao_in is None or (ao_in.dtype == torch.float32 and ao_in.shape == (self.rows, self.W) and ao_in.is_contiguous())
+        surface = torch.empty((3, self.rows, self.W, 4), dtype=torch.float32, device=dev)
+        depth = torch.empty((self.rows, self.W), dtype=torch.float32, device=dev) if want_depth else None
+        cov = torch.empty((self.rows, self.W), dtype=torch.uint8, device=dev) if want_coverage else None
+        ao_out = torch.empty((self.rows, self.W), dtype=torch.float32, device=dev) if want_ao else None
+        emissive = torch.empty((self.rows, self.W, 4), dtype=torch.float32, device=dev)
+        _lib.check(self.ctx._lib.sailor_hip_surface_resolve_gltf(self.ctx.handle, C.byref(frame), _ptr(instances), _ptr(materials),
+                                                                 materials.numel() * materials.element_size() // 80, _ptr(textures), num_textures, self.W, self.H,
+                                                                 C.byref(self.band), _ptr(self.workspace), self.workspace.numel(), _ptr(surface), self.rows * self.W,
+                                                                 _ptr(depth), _ptr(cov), _ptr(ao_in), _ptr(ao_out), _ptr(emissive)),
+                   "sailor_hip_surface_resolve_gltf", self.ctx.handle)
+        return surface, depth, cov, ao_out, emissive
+
+    def composite_gltf(self, radiance: torch.Tensor, emissive: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        """target = covered ? (emissive.rgb + radiance.rgb, radiance.a) : target; all float32 [rows, W, 4]"""
+        for t in (radiance, emissive, target):
+            assert t.dtype == torch.float32 and t.shape == (self.rows, self.W, 4) and t.is_contiguous()
+        _lib.check(self.ctx._lib.sailor_hip_surface_composite_gltf(self.ctx.handle, _ptr(radiance), _ptr(emissive), _ptr(self.workspace), self.workspace.numel(),
+                                                                   _ptr(target), self.W, self.H, C.byref(self.band)), "sailor_hip_surface_composite_gltf", self.ctx.handle)
         return target
 
     def download_keys(self) -> np.ndarray:

@@ -373,7 +373,16 @@ void RenderSceneNode::Process(RHIFrameGraphPtr, RHICommandListPtr, RHICommandLis
         for (const auto& b : sceneView.m_batches) {
             if (!b.m_tag.empty() && !(tagged && b.m_tag == tag)) continue; // the render queue filter: an untagged batch belongs to every queue
             RHIMaterialPtr material = m_pMaterial;
-            if (b.m_bAlphaCutout || b.m_bDoubleSided) { // the batch's own material: the ALPHA_CUTOUT permutation (ModelImporter.cpp:213-229), ECullMode::None
+            if (b.m_bGltf) { // an imported model's material: Standard_glTF.shader (ModelImporter.cpp:156-231), with the same two variations
+                RHIMaterialPtr& variant = m_pGltfMaterials[(b.m_bAlphaCutout ? 2 : 0) + (b.m_bDoubleSided ? 1 : 0)];
+                if (!variant) {
+                    RHIShaderPtr& shader = b.m_bAlphaCutout ? m_pGltfCutoutShader : m_pGltfShader;
+                    if (!shader) shader = b.m_bAlphaCutout ? driver->CreateShader("Shaders/Standard_glTF.shader", { "ALPHA_CUTOUT" }) : driver->CreateShader("Shaders/Standard_glTF.shader");
+                    variant = driver->CreateMaterial(shader);
+                    variant->m_bDoubleSided = b.m_bDoubleSided;
+                }
+                material = variant;
+            } else if (b.m_bAlphaCutout || b.m_bDoubleSided) { // the batch's own material: the ALPHA_CUTOUT permutation (ModelImporter.cpp:213-229), ECullMode::None
                 RHIMaterialPtr& variant = m_pVariants[(b.m_bAlphaCutout ? 2 : 0) + (b.m_bDoubleSided ? 1 : 0) - 1];
                 if (!variant) {
                     if (b.m_bAlphaCutout && !m_pCutoutShader) m_pCutoutShader = driver->CreateShader("Shaders/Standard.shader", { "ALPHA_CUTOUT" });
@@ -410,6 +419,9 @@ void RenderSceneNode::Clear()
     m_pMaterial.Clear();
     m_pCutoutShader.Clear();
     for (auto& v : m_pVariants) v.Clear();
+    m_pGltfShader.Clear();
+    m_pGltfCutoutShader.Clear();
+    for (auto& v : m_pGltfMaterials) v.Clear();
     m_surfaceBindings.Clear();
 }
 

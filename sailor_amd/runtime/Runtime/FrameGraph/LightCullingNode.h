@@ -62,6 +62,9 @@ protected:
     // the materials of batches that are not the default one: [0] double-sided, [1] ALPHA_CUTOUT, [2] both (created when the first such batch is drawn)
     RHI::RHIShaderPtr m_pCutoutShader;
     RHI::RHIMaterialPtr m_pVariants[3];
+    // the materials of glTF batches (RHISceneBatch::m_bGltf), Shaders/Standard_glTF.shader: [0] plain, [1] double-sided, [2] ALPHA_CUTOUT, [3] both
+    RHI::RHIShaderPtr m_pGltfShader, m_pGltfCutoutShader;
+    RHI::RHIMaterialPtr m_pGltfMaterials[4];
     RHI::RHIShaderBindingSetPtr m_surfaceBindings;
 };
 

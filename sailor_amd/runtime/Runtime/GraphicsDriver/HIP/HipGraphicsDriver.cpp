@@ -83,7 +83,7 @@ RHIShaderPtr HipGraphicsDriver::CreateShader(const std::string& assetPath, const
 {
     // the shaders this backend has entry points for (HipGraphicsDriver.h); any other is created but never "ready", so a node that checks
     // IsReady() before recording (PostProcessNode.cpp:61-64) records nothing for it
-    static const char* const routed[] = { "Shaders/ComputeLightCulling.shader", "Shaders/Standard.shader", "Shaders/ComputeMeshCulling.shader",
+    static const char* const routed[] = { "Shaders/ComputeLightCulling.shader", "Shaders/Standard.shader", "Shaders/Standard_glTF.shader", "Shaders/ComputeMeshCulling.shader",
         "Shaders/ComputeDepthHighZ.shader", "Shaders/ComputeHistogram.shader", "Shaders/ComputeAverageLuminance.shader", "Shaders/ComputeBrdfLut.shader",
         "Shaders/ComputeIrradianceMap.shader", "Shaders/ComputeEnvMap_IBL.shader", "Shaders/ShadowCaster.shader", "Shaders/LinearizeDepth.shader",
         "Shaders/Tonemapping.shader", "Shaders/Blur.shader", "Shaders/HBAO.shader", "Shaders/HBAO_Blur.shader", "Shaders/Sky.shader", "Shaders/ComputeBloomDownscale.shader",
@@ -736,6 +736,7 @@ int HipGraphicsDriver::RecordShade(const TVector<RHIShaderBindingSetPtr>& bindin
             ibl.env = (const float*)env->m_buffer->m_hip.m_devicePtr; ibl.envSize = env->m_extent.x; ibl.envLevels = (int32_t)env->m_mipLevels;
             ibl.brdfLut = (const float*)lut->m_buffer->m_hip.m_devicePtr; ibl.lutW = lut->m_extent.x; ibl.lutH = lut->m_extent.y;
             ibl.ao = (ao && ao->m_extent.x == W && ao->m_extent.y == H) ? (const float*)ao->m_buffer->m_hip.m_devicePtr : nullptr;
+            if (m_shadeAoOverride) ibl.ao = m_shadeAoOverride; // behind a pass with glTF draws: min(g_AO, the occlusion texel), RecordSurfaceEnd
             hasIbl = true;
         }
     }
@@ -822,7 +823,16 @@ int HipGraphicsDriver::RecordSurfaceDraw(const TVector<RHIShaderBindingSetPtr>& 
     d.flags = flags; // SAILOR_SURFACE_CULL_BACK: the reference's materials cull back faces (ECullMode::Back, frontFace counter-clockwise) unless double-sided
     d.firstInstance = firstInstance;
     int st;
-    if (flags & SAILOR_SURFACE_ALPHA_CUTOUT) { // the ALPHA_CUTOUT permutation: `material` and `textureSamplers` of the bound sets decide the discard in the draw
+    if (flags & SAILOR_SURFACE_GLTF) { // Standard_glTF.shader: the tables are read by the draw only under ALPHA_CUTOUT, which requires them
+        RHIBufferPtr materials = scene_buffer(bindings, "material"), textures = scene_buffer(bindings, "textureSamplers");
+        if ((flags & SAILOR_SURFACE_ALPHA_CUTOUT) && (!materials || !textures)) { m_surfaceBegun = false; return SAILOR_HIP_ERR_INVALID_ARGUMENT; }
+        st = sailor_hip_surface_draw_gltf(m_ctx, &frame, &d, (const SailorPerInstanceData*)instances->m_hip.m_devicePtr,
+                                          materials ? (const SailorMaterialData*)materials->m_hip.m_devicePtr : nullptr,
+                                          materials ? (uint32_t)(materials->m_size / sizeof(SailorMaterialData)) : 0u,
+                                          textures ? (const SailorTextureDesc*)textures->m_hip.m_devicePtr : nullptr,
+                                          textures ? (uint32_t)(textures->m_size / sizeof(SailorTextureDesc)) : 0u, drawIndex, W, H, &band,
+                                          m_surfaceWorkspace->m_hip.m_devicePtr, bytes);
+    } else if (flags & SAILOR_SURFACE_ALPHA_CUTOUT) { // the ALPHA_CUTOUT permutation: `material` and `textureSamplers` of the bound sets decide the discard in the draw
         RHIBufferPtr materials = scene_buffer(bindings, "material"), textures = scene_buffer(bindings, "textureSamplers");
         if (!materials || !textures) { m_surfaceBegun = false; return SAILOR_HIP_ERR_INVALID_ARGUMENT; }
         st = sailor_hip_surface_draw_masked(m_ctx, &frame, &d, (const SailorPerInstanceData*)instances->m_hip.m_devicePtr, (const SailorMaterialData*)materials->m_hip.m_devicePtr,
@@ -914,7 +924,7 @@ int HipGraphicsDriver::RecordUi(const RHITexturePtr& color, const RHIBufferPtr& 
                               m_uiWorkspace->m_size, (float*)color->m_buffer->m_hip.m_devicePtr, W, H, &band);
 }
 
-int HipGraphicsDriver::RecordSurfaceEnd(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& color, const RHITexturePtr& depthToStore)
+int HipGraphicsDriver::RecordSurfaceEnd(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& color, const RHITexturePtr& depthToStore, bool gltf)
 {
     if (!m_surfaceBegun) return SAILOR_HIP_ERR_INVALID_ARGUMENT; // a draw of the pass was refused: nothing to resolve
     m_surfaceBegun = false;
@@ -929,7 +939,22 @@ int HipGraphicsDriver::RecordSurfaceEnd(const TVector<RHIShaderBindingSetPtr>& b
     if (!m_surfacePlanes || m_surfacePlanes->m_size != pixels * 48) m_surfacePlanes = CreateBuffer(pixels * 48);
     if (!m_surfaceRadiance || m_surfaceRadiance->m_size != pixels * 16) m_surfaceRadiance = CreateBuffer(pixels * 16);
     if (!m_surfacePlanes || !m_surfaceRadiance) return SAILOR_HIP_ERR_OUT_OF_MEMORY;
-    int st = sailor_hip_surface_resolve(m_ctx, &frame, (const SailorPerInstanceData*)instances->m_hip.m_devicePtr, (const SailorMaterialData*)materials->m_hip.m_devicePtr,
+    int st;
+    if (gltf) {
+        // a pass that recorded a Standard_glTF.shader draw: the resolve also writes the emissive term and the occlusion the shade is to read, min(g_AO, the
+        // occlusion texel) -- g_AO = the `g_aoSampler` binding of the lights set if bound at the frame's extent (what RecordShade would hand the shade), else 1
+        if (!m_surfaceAo || m_surfaceAo->m_size != pixels * 4) m_surfaceAo = CreateBuffer(pixels * 4);
+        if (!m_surfaceEmissive || m_surfaceEmissive->m_size != pixels * 16) m_surfaceEmissive = CreateBuffer(pixels * 16);
+        if (!m_surfaceAo || !m_surfaceEmissive) return SAILOR_HIP_ERR_OUT_OF_MEMORY;
+        auto ao = bindings[1] ? bound_texture(bindings[1], "g_aoSampler") : RHITexturePtr();
+        const float* aoIn = (ao && ao->m_extent.x == W && ao->m_extent.y == H) ? (const float*)ao->m_buffer->m_hip.m_devicePtr : nullptr;
+        st = sailor_hip_surface_resolve_gltf(m_ctx, &frame, (const SailorPerInstanceData*)instances->m_hip.m_devicePtr, (const SailorMaterialData*)materials->m_hip.m_devicePtr,
+                                             (uint32_t)(materials->m_size / sizeof(SailorMaterialData)), (const SailorTextureDesc*)textures->m_hip.m_devicePtr,
+                                             (uint32_t)(textures->m_size / sizeof(SailorTextureDesc)), W, H, &band, m_surfaceWorkspace->m_hip.m_devicePtr, bytes,
+                                             (float*)m_surfacePlanes->m_hip.m_devicePtr, pixels, nullptr, nullptr, aoIn, (float*)m_surfaceAo->m_hip.m_devicePtr,
+                                             (float*)m_surfaceEmissive->m_hip.m_devicePtr);
+    } else
+        st = sailor_hip_surface_resolve(m_ctx, &frame, (const SailorPerInstanceData*)instances->m_hip.m_devicePtr, (const SailorMaterialData*)materials->m_hip.m_devicePtr,
                                         (uint32_t)(materials->m_size / sizeof(SailorMaterialData)), (const SailorTextureDesc*)textures->m_hip.m_devicePtr,
                                         (uint32_t)(textures->m_size / sizeof(SailorTextureDesc)), W, H, &band, m_surfaceWorkspace->m_hip.m_devicePtr, bytes,
                                         (float*)m_surfacePlanes->m_hip.m_devicePtr, pixels, nullptr, nullptr);
@@ -939,11 +964,15 @@ int HipGraphicsDriver::RecordSurfaceEnd(const TVector<RHIShaderBindingSetPtr>& b
     own->GetOrAddShaderBinding("surface")->m_buffer = m_surfacePlanes;
     own->GetOrAddShaderBinding("radiance")->m_buffer = m_surfaceRadiance;
     if (!bindings[1]) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    m_shadeAoOverride = gltf ? (const float*)m_surfaceAo->m_hip.m_devicePtr : nullptr;
     st = RecordShade({ bindings[0], bindings[1], own });
+    m_shadeAoOverride = nullptr;
     if (st != SAILOR_HIP_OK) return st;
     BeforeBufferWrite(color->m_buffer->m_hip.m_devicePtr);
-    st = sailor_hip_surface_composite(m_ctx, (const float*)m_surfaceRadiance->m_hip.m_devicePtr, m_surfaceWorkspace->m_hip.m_devicePtr, bytes,
-                                      (float*)color->m_buffer->m_hip.m_devicePtr, W, H, &band);
+    st = gltf ? sailor_hip_surface_composite_gltf(m_ctx, (const float*)m_surfaceRadiance->m_hip.m_devicePtr, (const float*)m_surfaceEmissive->m_hip.m_devicePtr,
+                                                  m_surfaceWorkspace->m_hip.m_devicePtr, bytes, (float*)color->m_buffer->m_hip.m_devicePtr, W, H, &band)
+              : sailor_hip_surface_composite(m_ctx, (const float*)m_surfaceRadiance->m_hip.m_devicePtr, m_surfaceWorkspace->m_hip.m_devicePtr, bytes,
+                                             (float*)color->m_buffer->m_hip.m_devicePtr, W, H, &band);
     if (st != SAILOR_HIP_OK || !depthToStore) return st;
     // a pass that held a cutout draw writes its depth: the attachment gets the keys' depth (the opaque draws' depth is the prepass's already; a masked fragment
     // that survived writes its own, a discarded one none)
@@ -962,6 +991,7 @@ void HipGraphicsDriver::BeginRenderPass(RHICommandListPtr cmd, const TVector<RHI
     cmd->m_casterDraws = 0;
     cmd->m_surfaceDraws = 0;
     cmd->m_surfaceCutout = false;
+    cmd->m_surfaceGltf = false;
     cmd->m_uiCommands.clear();
     cmd->m_scissorOffset = { 0, 0 };
     cmd->m_scissorExtent = { -1, -1 };
@@ -1000,7 +1030,8 @@ void HipGraphicsDriver::EndRenderPass(RHICommandListPtr cmd)
         RHITexturePtr color = cmd->m_colorAttachments.empty() ? RHITexturePtr() : cmd->m_colorAttachments[0];
         TVector<RHIShaderBindingSetPtr> bindings = cmd->m_boundBindings;
         RHITexturePtr depthToStore = cmd->m_surfaceCutout ? cmd->m_depthAttachment : RHITexturePtr();
-        cmd->m_hip.m_commands.push_back([this, bindings, color, depthToStore]() { return RecordSurfaceEnd(bindings, color, depthToStore); });
+        const bool gltf = cmd->m_surfaceGltf;
+        cmd->m_hip.m_commands.push_back([this, bindings, color, depthToStore, gltf]() { return RecordSurfaceEnd(bindings, color, depthToStore, gltf); });
     }
     if (!cmd->m_uiCommands.empty()) { // RenderImGuiNode's pass: one ordered blend over every command the pass recorded
         RHITexturePtr color = cmd->m_colorAttachments.empty() ? RHITexturePtr() : cmd->m_colorAttachments[0];
@@ -1067,15 +1098,18 @@ void HipGraphicsDriver::DrawIndexed(RHICommandListPtr cmd, uint32_t indexCount, 
         });
         return;
     }
-    if (name == "Shaders/Standard.shader") { // a batch of RenderSceneNode (RenderSceneNode.cpp via RHIRecordDrawCall, RHI/Batch.hpp)
+    if (name == "Shaders/Standard.shader" || name == "Shaders/Standard_glTF.shader") { // a batch of RenderSceneNode (RenderSceneNode.cpp via RHIRecordDrawCall, RHI/Batch.hpp)
         RHITexturePtr color = cmd->m_colorAttachments.empty() ? RHITexturePtr() : cmd->m_colorAttachments[0], depth = cmd->m_depthAttachment;
         RHIBufferPtr vb = cmd->m_vertexBuffer, ib = cmd->m_indexBuffer;
         TVector<RHIShaderBindingSetPtr> bindings = cmd->m_boundBindings;
         const uint32_t drawIndex = cmd->m_surfaceDraws++;
-        // the permutation and the cull mode of the bound material: { "ALPHA_CUTOUT" } goes to sailor_hip_surface_draw_masked
+        // the permutation and the cull mode of the bound material: { "ALPHA_CUTOUT" } goes to sailor_hip_surface_draw_masked, Standard_glTF.shader (an imported
+        // model's, with or without the define) to sailor_hip_surface_draw_gltf
         const uint32_t flags = (cmd->m_boundMaterial->m_bDoubleSided ? 0u : SAILOR_SURFACE_CULL_BACK) |
-                               (cmd->m_boundMaterial->m_shader->HasDefine("ALPHA_CUTOUT") ? SAILOR_SURFACE_ALPHA_CUTOUT : 0u);
+                               (cmd->m_boundMaterial->m_shader->HasDefine("ALPHA_CUTOUT") ? SAILOR_SURFACE_ALPHA_CUTOUT : 0u) |
+                               (name == "Shaders/Standard_glTF.shader" ? SAILOR_SURFACE_GLTF : 0u);
         if (flags & SAILOR_SURFACE_ALPHA_CUTOUT) cmd->m_surfaceCutout = true;
+        if (flags & SAILOR_SURFACE_GLTF) cmd->m_surfaceGltf = true;
         cmd->m_hip.m_commands.push_back([this, bindings, color, depth, vb, ib, drawIndex, indexCount, instanceCount, firstIndex, vertexOffset, firstInstance, flags]() {
             return RecordSurfaceDraw(bindings, color, depth, vb, ib, drawIndex == 0, drawIndex, indexCount, instanceCount, firstIndex, vertexOffset, firstInstance, flags);
         });

@@ -45,6 +45,9 @@
 //       per draw, and at EndRenderPass sailor_hip_surface_resolve -> the shade over driver-owned planes -> sailor_hip_surface_composite into the colour attachment
 //   "Shaders/Standard.shader" { "ALPHA_CUTOUT" } drawn with DrawIndexed (a Masked batch) -> sailor_hip_surface_draw_masked with `material` and `textureSamplers` of the
 //       bound sets; a pass that held one ends with sailor_hip_surface_store_depth into its depth attachment after the composite
+//   "Shaders/Standard_glTF.shader", with or without { "ALPHA_CUTOUT" }, drawn with DrawIndexed (a batch of an imported model) -> sailor_hip_surface_draw_gltf; a pass that
+//       held one ends with sailor_hip_surface_resolve_gltf (aoIn = `g_aoSampler` of the lights set if bound) -> the shade, reading the driver's aoOut as its ao ->
+//       sailor_hip_surface_composite_gltf.  A pass without one records exactly the launches above.
 //   "Shaders/Gizmo.shader" of a LineList material drawn with DrawIndexed (DebugContext::DrawDebugMesh inside DebugDrawNode's pass) -> sailor_hip_surface_begin from
 //       the pass' depth attachment, sailor_hip_debug_lines_draw, sailor_hip_debug_lines_resolve into the colour and the depth attachment (push constant viewProjection,
 //       VertexP3C4 vertices, 32-bit indices)
@@ -161,7 +164,7 @@ private:
                          const TVector<uint8_t>& pushConstants, uint32_t indexCount, uint32_t firstIndex, uint32_t vertexOffset);
     int RecordUi(const RHI::RHITexturePtr& color, const RHI::RHIBufferPtr& vertices, const RHI::RHIBufferPtr& indices, bool bIndexUint16,
                  const TVector<uint8_t>& pushConstants, const RHI::RHITexturePtr& font, const TVector<SailorUiCommand>& uiCommands, const RHI::RHIBufferPtr& dCommands);
-    int RecordSurfaceEnd(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& color, const RHI::RHITexturePtr& depthToStore);
+    int RecordSurfaceEnd(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& color, const RHI::RHITexturePtr& depthToStore, bool gltf);
     int RecordBrdfLut(const TVector<RHI::RHIShaderBindingSetPtr>& bindings);
     int RecordIrradianceMap(const TVector<RHI::RHIShaderBindingSetPtr>& bindings);
     int RecordEnvPrefilter(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const TVector<uint8_t>& pc);
@@ -201,6 +204,10 @@ private:
     // the surface pass of the render pass being executed (Standard.shader draws): workspace (keys, descriptors), the planes the resolve writes and the shade
     // reads, the shade's radiance; the running primBase; begun = the first draw's sailor_hip_surface_begin went through
     RHI::RHIBufferPtr m_surfaceWorkspace, m_surfacePlanes, m_surfaceRadiance;
+    // behind a pass that recorded a Standard_glTF.shader draw: the occlusion the shade reads (min(g_AO, the occlusion texel)) and the emissive term the
+    // composite adds; the override is set only around that pass's RecordShade
+    RHI::RHIBufferPtr m_surfaceAo, m_surfaceEmissive;
+    const float* m_shadeAoOverride = nullptr;
     RHI::RHIBufferPtr m_uiWorkspace;
     uint64_t m_surfacePrimBase = 0;
     bool m_surfaceBegun = false;

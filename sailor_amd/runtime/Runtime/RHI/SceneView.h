@@ -19,6 +19,9 @@ struct RHISceneBatch {
     std::string m_tag;
     bool m_bAlphaCutout = false;
     bool m_bDoubleSided = false;
+    // the batch's shader is Shaders/Standard_glTF.shader, what ModelImporter.cpp:156-231 gives every imported model, and its material slots are that shader's
+    // MaterialData; false = Shaders/Standard.shader
+    bool m_bGltf = false;
 };
 
 struct RHISceneViewSnapshot {

@@ -192,6 +192,7 @@ public:
     uint32_t m_casterDraws = 0;                                // depth-only draws recorded in the current pass (the first one clears)
     uint32_t m_surfaceDraws = 0;                               // Standard.shader draws recorded in the current pass (the first one begins the surface pass)
     bool m_surfaceCutout = false;                              // ... one of them with ALPHA_CUTOUT: the pass ends with the depth write (sailor_hip_surface_store_depth)
+    bool m_surfaceGltf = false;                                // ... one of them with Standard_glTF.shader: the pass ends with the glTF resolve and composite
     TRefPtr<class RHIMaterial> m_boundMaterial;
     TVector<TRefPtr<class RHIShaderBindingSet>> m_boundBindings;
     bool m_bIndexUint16 = false;                               // BindIndexBuffer(..., bUint16InsteadOfUint32)

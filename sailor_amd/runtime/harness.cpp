@@ -450,6 +450,16 @@ RT_API int sailor_rt_set_scene_tags(SailorRuntime* rt, const char* tags, const u
     return 0;
 }
 
+// The shaders of the batches sailor_rt_set_scene set (call it afterwards; sailor_rt_set_scene itself leaves every batch on Standard.shader): shaders[i] is
+// SAILOR_RT_SHADER_STANDARD (0) or SAILOR_RT_SHADER_STANDARD_GLTF (1) of batch i -- a glTF batch's material slots are Standard_glTF.shader's MaterialData.
+// -1, and nothing changed, unless numBatches is the scene's and every entry is one of the two.
+RT_API int sailor_rt_set_scene_shaders(SailorRuntime* rt, const uint32_t* shaders, int numBatches)
+{
+    if (!rt || numBatches < 0 || (size_t)numBatches != rt->snapshot.m_batches.size() || !sailor_rt_scene_shaders_ok(shaders, numBatches)) return -1;
+    for (int i = 0; i < numBatches; i++) rt->snapshot.m_batches[(size_t)i].m_bGltf = shaders[i] == SAILOR_RT_SHADER_STANDARD_GLTF;
+    return 0;
+}
+
 // RenderScene's attachments for those draws: "color" (RGBA32F, e.g. Main) and "depthStencil" (the raw R32F DepthBuffer of the prepass, or null)
 RT_API int sailor_rt_set_scene_targets(SailorRuntime* rt, void* color, void* depth, int width, int height)
 {

@@ -35,6 +35,17 @@ inline bool sailor_rt_parse_scene_tags(const char* text, int count, std::vector<
     return true;
 }
 
+// the shader of one batch, as sailor_rt_set_scene_shaders takes it
+#define SAILOR_RT_SHADER_STANDARD 0u
+#define SAILOR_RT_SHADER_STANDARD_GLTF 1u
+inline bool sailor_rt_scene_shaders_ok(const uint32_t* shaders, int count)
+{
+    if (count < 0 || (count > 0 && !shaders)) return false;
+    for (int i = 0; i < count; i++)
+        if (shaders[i] != SAILOR_RT_SHADER_STANDARD && shaders[i] != SAILOR_RT_SHADER_STANDARD_GLTF) return false;
+    return true;
+}
+
 // the flags of one batch: only the two known bits
 inline bool sailor_rt_scene_flags_ok(const uint32_t* flags, int count)
 {

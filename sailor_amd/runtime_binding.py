@@ -73,6 +73,7 @@ def load() -> C.CDLL:
         rt.sailor_rt_set_scene.argtypes = [P, P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, P, C.c_int]
         rt.sailor_rt_set_scene_targets.argtypes = [P, P, P, C.c_int, C.c_int]
         rt.sailor_rt_set_scene_tags.argtypes = [P, C.c_char_p, P, C.c_int]
+        rt.sailor_rt_set_scene_shaders.argtypes = [P, P, C.c_int]
         rt.sailor_rt_process_frame.argtypes = [P]
         for shape in ("line", "aabb", "arrow"):
             getattr(rt, f"sailor_rt_debug_draw_{shape}").argtypes = [P, P, P, P, C.c_float]
@@ -359,6 +360,12 @@ class Runtime:
         assert len(tags) == len(flags)
         f = np.ascontiguousarray(flags, np.uint32)
         _lib.check(self.rt.sailor_rt_set_scene_tags(self.h, ",".join(tags).encode(), f.ctypes.data if len(f) else None, len(f)), "sailor_rt_set_scene_tags")
+
+    def set_scene_shaders(self, shaders):
+        """the shaders of set_scene's batches, after set_scene: one int per batch, SHADER_STANDARD (Standard.shader) or SHADER_STANDARD_GLTF (Standard_glTF.shader,
+        what an imported model's material uses: its slots of the material table are that shader's records)"""
+        s = np.ascontiguousarray(shaders, np.uint32)
+        _lib.check(self.rt.sailor_rt_set_scene_shaders(self.h, s.ctypes.data if len(s) else None, len(s)), "sailor_rt_set_scene_shaders")
 
     def set_scene_targets(self, color, depth=None):
         """RenderScene's colour attachment (float32 [H, W, 4]) and the prepass's raw depth (float32 [H, W]) or None"""
