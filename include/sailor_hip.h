@@ -639,7 +639,13 @@ typedef struct SailorHiZDesc {
 } SailorHiZDesc;
 
 /* Replaces: Content/Shaders/ComputeDepthHighZ.shader:22-30 for one Dispatch of FrameGraph/DepthHighZNode.cpp:90-95 -- out(pos) = the minimum
- * over the bilinear footprint of the source at (pos + 0.5) / outputSize (texels with non-zero weight, clamp-to-edge). */
+ * over the bilinear footprint of the source at (pos + 0.5) / outputSize (texels with non-zero weight, clamp-to-edge: x = u W - 0.5, i0 = floor(x),
+ * i1 = i0 + 1 on the floor itself, never floor(x + 1.0f), which rounds up to the next integer for x = -2^-25).
+ * One stated divergence (the sampler convention): a neighbour texel counts whenever the FP32 fraction of x is not exactly 0.  For a same-size step
+ * the exact position ((2 i + 1) src - dst) / (2 dst) is an integer, but the fp32 evaluation leaves a non-zero fraction on 25 of the 960 columns
+ * of a 960 -> 960 step (the shipped pyramid's own first step in x) and on 2 of the 131 columns of 131 -> 131; those texels take the minimum with
+ * the next column as well.  Any hardware sampler quantises such a fraction to 0.  The effect is conservative (a farther depth).  None for powers of
+ * two, 48 -> 16, 36 -> 12, 96 -> 96 and every 2:1 step.  Counted by tests/test_mesh_cull_cpu.py against exact rational sample positions. */
 SAILOR_HIP_API int sailor_hip_hiz_downscale(SailorHipContext* ctx, const float* dSrc, int32_t srcWidth, int32_t srcHeight, float* dDst,
                                             int32_t dstWidth, int32_t dstHeight);
 /* The node's whole loop (DepthHighZNode.cpp:78-96): mip 0 from the depth attachment "src", mip i + 1 from mip i. */

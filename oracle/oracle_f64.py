@@ -1,5 +1,6 @@
 """Independent float64 restatement of K2 (PBR shade, ambient / IBL term included), K3 (cascaded-shadow factor) and K4 (ECS transform / bounds /
-frustum sweep); further down the EVSM blur, the two cube bakes and the BRDF table.
+frustum sweep); further down the EVSM blur, the two cube bakes and the BRDF table, and at the end the instance visibility path (instance cull, Hi-Z
+pyramid, draw compaction).
 
 TEST INFRASTRUCTURE ONLY.  PARITY UNPINNED by the reference (it has no golden vectors): this file exists to harden the fp32 C oracle
 (oracle/sailor_oracle.c), not to replace it.  It was written from the reference's own text only --
@@ -776,3 +777,328 @@ def brdf_lut(w: int, h: int, num_samples: int = 1024) -> np.ndarray:
             out[y, x, 0] = ((1.0 - Fc) * Gv).sum() / num_samples
             out[y, x, 1] = (Fc * Gv).sum() / num_samples
     return out
+
+
+# =====================================================================================================================================
+# Instance visibility: the instance cull, the Hi-Z pyramid and the draw compaction, written from ComputeMeshCulling.shader:62-177, Math.glsl:185-239
+# (CreateViewFrustum, SphereFrustumOverlaps) and :296-315 (ProjectSphere), ComputeDepthHighZ.shader, DepthHighZNode.cpp:74-96 and, for the pyramid's
+# `reduction: Min` sampler, from the Vulkan rules: x = u W - 0.5, i0 = floor(x), i1 = i0 + 1, weights (1 - frac, frac), both indices clamped to the
+# edge, the MINIMUM over the texels whose weight is not zero, an explicit lod clamped to the chain.  float64, vectorised over instances / texels.
+# Shared with the C oracle: the 96-byte instance record, the level-major pyramid layout and the five-word indirect record -- nothing else.
+#
+# Every discrete decision carries a margin q and a bound e (units of 2^-24, first order) built as the shadow term's are (_rounded / _decided above):
+# each fp32 operation of the chain adds one rounding of the size of its result to the bounds its operands carry, multiplied through by the
+# operation's derivatives; a chain whose every intermediate is a float has e = 0 and its compare IS the fp32 compare, an exact tie included.  The
+# helpers below do that bookkeeping one operation at a time, so the operation count is the count of calls and the magnitudes are the values.
+# What the sampler rules leave open is reported as not decided rather than guessed: a NaN coordinate, a NaN texel inside a footprint.
+# =====================================================================================================================================
+def _add(a, ea, b, eb):
+    v = a + b
+    return v, _rounded(v, ea + eb)
+
+
+def _mul(a, ea, b, eb):
+    v = a * b
+    return v, _rounded(v, np.abs(b) * ea + np.abs(a) * eb)
+
+
+def _sqrt(a, ea):
+    v = np.sqrt(a)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return v, _rounded(v, np.where(ea == 0, 0.0, ea / (2.0 * v)))
+
+
+def _row_margin_e(m, w, ew):
+    """_row_margin for a vector that carries bounds of its own: |m_j| ew_j beside the row's roundings; 0 only where the operands are exact too"""
+    t = m * w
+    s1 = t[..., 0] + t[..., 1]; s2 = s1 + t[..., 2]; s3 = s2 + t[..., 3]
+    tf = _is_float(t) & (ew == 0)
+    exact = tf.all(-1) & _is_float(s1) & _is_float(s2) & _is_float(s3)
+    k = np.array([4.0, 4.0, 3.0, 2.0]) - tf
+    return s3, np.where(exact, 0.0, (k * np.abs(t) + np.abs(m) * ew).sum(-1))
+
+
+def _dot3_margin(a, ea, b, eb):
+    """(a0 b0 + a1 b1) + a2 b2 -> (value, e); a, b, ea, eb are lists of three"""
+    p = [_mul(a[i], ea[i], b[i], eb[i]) for i in range(3)]
+    s, es = _add(p[0][0], p[0][1], p[1][0], p[1][1])
+    return _add(s, es, p[2][0], p[2][1])
+
+
+def _any_decided(outcome, dec):
+    """a short-circuit `or` of compares: one that is true beyond rounding decides it, otherwise all must be decided"""
+    return (outcome & dec).any(-1) | dec.all(-1)
+
+
+def hiz_level_sizes(width: int, height: int, levels: int):
+    """the pyramid's layout: level l is max(H >> l, 1) rows of max(W >> l, 1) floats, levels one behind the other -> ([(w, h)], offsets int64[levels + 1])"""
+    sizes = [(max(width >> l, 1), max(height >> l, 1)) for l in range(levels)]
+    return sizes, np.concatenate([[0], np.cumsum([w * h for w, h in sizes])]).astype(np.int64)
+
+
+def view_frustum_margin(fr):
+    """Math.glsl:185-222 CreateViewFrustum(frame.viewportSize, frame.invProjection) -> (normals float64[4, 3], e[4, 3]) in the order left, right, top,
+    bottom.  The corners sit at clip +-1 exactly (0 / size and size / size are exact); eyePos is the origin, so v0 = p1, v2 = p2 and plane.w = 0."""
+    inv = fr["invProjection"]
+    W, H = float(fr["viewportSize"][0]), float(fr["viewportSize"][1])
+    vs = []
+    for sx, sy in ((0.0, 0.0), (W, 0.0), (0.0, H), (W, H)):
+        clip = np.array([sx / W * 2.0 - 1.0, sy / H * 2.0 - 1.0, -1.0, 1.0])
+        rows = [_row_margin_e(inv[r], clip, np.zeros(4)) for r in range(4)]
+        comp = [_div_margin(rows[r][0], rows[r][1], rows[3][0], rows[3][1]) for r in range(3)]
+        vs.append(([comp[0][0], comp[1][0], -comp[2][0]], [comp[0][1], comp[1][1], comp[2][1]]))
+    normals, errs = np.zeros((4, 3)), np.zeros((4, 3))
+    for p, (ia, ib) in enumerate(((2, 0), (1, 3), (0, 1), (3, 2))):
+        (a, ea), (b, eb) = vs[ia], vs[ib]
+        c, ec = [], []
+        for i, j in ((1, 2), (2, 0), (0, 1)):                                          # cross(a, b).k = a_i b_j - b_i a_j
+            t0, e0 = _mul(a[i], ea[i], b[j], eb[j]); t1, e1 = _mul(b[i], eb[i], a[j], ea[j])
+            v, e = _add(t0, e0, -t1, e1)
+            c.append(v); ec.append(e)
+        d, ed = _dot3_margin(c, ec, c, ec)
+        ln, eln = _sqrt(d, ed)
+        for k in range(3):
+            normals[p, k], errs[p, k] = _div_margin(c[k], ec[k], ln, eln)
+    return normals, errs
+
+
+def _fetch_axis(x, ex, size):
+    """one axis of the bilinear footprint at unnormalised coordinate x (= u size - 0.5) -> dict: c0, c1 the clamped texel indices, use1 (the second
+    one has a non-zero weight), frac, the distances to the floor (nearest integer) and to the clamps, decided.  The set {c0, c1 if use1} changes only
+    where x crosses an integer k, and not at all for k < 0 or k > size - 1 (both indices clamp to the same edge texel on either side) or in a level of
+    one texel."""
+    with np.errstate(invalid="ignore"):
+        fl = np.floor(x)
+        frac = x - fl
+        k = np.rint(x)
+        d_int = np.abs(x - k)
+        d_clamp = np.minimum(np.abs(x), np.abs(x - (size - 1.0)))
+    nan = np.isnan(x)
+    i0 = np.clip(np.where(nan, 0.0, fl), -1.0, float(size)).astype(np.int64)
+    c0 = np.clip(i0, 0, size - 1)
+    c1 = np.where(nan, c0, np.clip(i0 + 1, 0, size - 1))
+    use1 = ~(frac == 0.0)
+    with np.errstate(invalid="ignore"):
+        decided = ~nan & (np.isinf(x) | (ex == 0) | (d_int > 2.0 * U24 * ex) | (k < 0) | (k > size - 1) | (size == 1))
+    return dict(c0=c0, c1=c1, use1=use1, frac=frac, d_floor=d_int, d_clamp=d_clamp, decided=decided, x=x)
+
+
+def hiz_fetch_min(tex: np.ndarray, u, v, eu=0.0, ev=0.0) -> dict:
+    """texture(sampler2D with reduction Min, uv) of ONE level tex[H, W]: -> dict(value, texels int64[n, 4] (row * W + column, -1 = zero weight), fx, fy,
+    decided).  u, v arrays; eu, ev their bounds (0: the coordinates are the floats they are).  The minimum skips NaN texels; `nan` marks the fetches
+    whose footprint holds one (the sampler's rule for them is not specified)."""
+    tex = np.asarray(tex, np.float64)
+    H, W = tex.shape
+    u, v = np.atleast_1d(np.asarray(u, np.float64)), np.atleast_1d(np.asarray(v, np.float64))
+    with np.errstate(all="ignore"):
+        x, ex = _add(*_mul(u, eu, float(W), 0.0), -0.5, 0.0)
+        y, ey = _add(*_mul(v, ev, float(H), 0.0), -0.5, 0.0)
+        fx, fy = _fetch_axis(x, np.broadcast_to(ex, x.shape), W), _fetch_axis(y, np.broadcast_to(ey, y.shape), H)
+        texels = np.stack([fy["c0"] * W + fx["c0"], np.where(fx["use1"], fy["c0"] * W + fx["c1"], -1), np.where(fy["use1"], fy["c1"] * W + fx["c0"], -1),
+                           np.where(fx["use1"] & fy["use1"], fy["c1"] * W + fx["c1"], -1)], -1)
+        taps = np.where(texels >= 0, tex.reshape(-1)[np.clip(texels, 0, None)], np.inf)
+        value = np.fmin.reduce(taps, -1)
+    return dict(value=value, texels=texels, fx=fx, fy=fy, decided=fx["decided"] & fy["decided"], nan=np.isnan(taps).any(-1))
+
+
+def mesh_cull_flags(frame_bytes, instances: np.ndarray, hiz=None) -> dict:
+    """ComputeMeshCulling.shader step 2 per 96-byte record: FrustumCulling (:96-110), and with hiz = (flat pyramid, width, height, levels)
+    `|| OcclusionCulling` (:62-94).  -> dict of per-instance arrays:
+      frustum (culled by FrustumCulling), gate (ProjectSphere returned true), level, footprint int64[n, 4] (indices into the flat pyramid, -1 = no
+      texel: gate failed or zero weight), depth_sphere, occluded, culled (the final flag), center [n, 3], radius, m (= max(width, height)), uv [n, 2];
+      compares: z_out bool[n, 2] (cz - r > zFar, cz + r < zNear), plane_out bool[n, 4]; margins q_* with their `*_decided` masks:
+      q_z [n, 2], q_plane [n, 4], q_gate, d_pow2 (distance of m to the nearest power of two that separates two levels of this chain), fx / fy (the
+      _fetch_axis dicts: frac, d_floor, d_clamp), q_depth; frustum_decided, gate_decided, level_decided, footprint_decided, depth_decided and
+      decided = every decision on the path taken is decided."""
+    fr = frame_fields(frame_bytes)
+    rec = np.ascontiguousarray(instances).view(np.uint8).reshape(-1, 96)
+    f = np.ascontiguousarray(rec[:, :80]).view(np.float32).astype(np.float64).reshape(-1, 20)
+    n = len(f)
+    M = f[:, :16].reshape(n, 4, 4).transpose(0, 2, 1)                                  # M[i, row, column]
+    sb = f[:, 16:20]
+    z_near, z_far = float(fr["cameraZNearZFar"][0]), float(fr["cameraZNearZFar"][1])
+    with np.errstate(all="ignore"):
+        c = np.concatenate([sb[:, :3], np.ones((n, 1))], 1)
+        wrow = [_row_margin_e(M[:, r, :], c, np.zeros((n, 4))) for r in range(4)]
+        wc = np.stack([w[0] for w in wrow], -1); ewc = np.stack([w[1] for w in wrow], -1)
+        vrow = [_row_margin_e(fr["view"][r][None, :], wc, ewc) for r in range(4)]
+        cx, ecx = _div_margin(vrow[0][0], vrow[0][1], vrow[3][0], vrow[3][1])
+        cy, ecy = _div_margin(vrow[1][0], vrow[1][1], vrow[3][0], vrow[3][1])
+        cz, ecz = _div_margin(vrow[2][0], vrow[2][1], vrow[3][0], vrow[3][1])
+        cz = -cz                                                                       # center.z *= -1.0f: exact
+        col0 = [M[:, 0, 0], M[:, 1, 0], M[:, 2, 0]]
+        d, ed = _dot3_margin(col0, [0.0] * 3, col0, [0.0] * 3)
+        scale, escale = _sqrt(d, ed)
+        r, er = _mul(sb[:, 3], 0.0, scale, escale)
+        # SphereFrustumOverlaps(center, radius, frustum, zNear = cameraZNearZFar.y, zFar = cameraZNearZFar.x) (:107, Math.glsl:224-239)
+        a, ea = _add(cz, ecz, -r, er)
+        b, eb = _add(cz, ecz, r, er)
+        q_z = np.stack([a - z_far, b - z_near], -1)
+        z_out = np.stack([a > z_far, b < z_near], -1)
+        z_dec = np.stack([_decided(a - z_far, ea), _decided(b - z_near, eb)], -1)
+        normals, en = view_frustum_margin(fr)
+        q_plane, plane_dec, plane_out = [], [], []
+        for p in range(4):
+            dt, edt = _dot3_margin(list(normals[p]), list(en[p]), [cx, cy, cz], [ecx, ecy, ecz])
+            q_plane.append(dt + r); plane_dec.append(_decided(dt + r, edt + er)); plane_out.append(dt < -r)      # plane.w = 0: dot - 0 is exact
+        q_plane = np.stack(q_plane, -1); plane_dec = np.stack(plane_dec, -1); plane_out = np.stack(plane_out, -1)
+        all_out = np.concatenate([z_out, plane_out], -1)
+        frustum = all_out.any(-1)
+        frustum_decided = _any_decided(all_out, np.concatenate([z_dec, plane_dec], -1))
+        out = dict(frustum=frustum, frustum_decided=frustum_decided, z_out=z_out, plane_out=plane_out, q_z=q_z, q_plane=q_plane, z_decided=z_dec,
+                   plane_decided=plane_dec, center=np.stack([cx, cy, cz], -1), radius=r)
+        if hiz is None:
+            out.update(culled=frustum, decided=frustum_decided)
+            return out
+        pyr, W, H, levels = np.asarray(hiz[0], np.float64).reshape(-1), int(hiz[1]), int(hiz[2]), int(hiz[3])
+        sizes, offs = hiz_level_sizes(W, H, levels)
+        assert pyr.size == offs[-1]
+        P00, P11 = fr["projection"][0, 0], fr["projection"][1, 1]
+        # ProjectSphere (Math.glsl:296-315)
+        g, eg = _add(r, er, z_near, 0.0)
+        gate = ~(cz < g)
+        gate_decided = _decided(cz - g, ecz + eg)
+        rr, err = _mul(r, er, r, er)
+
+        def axis(ca, eca, P):
+            c0, c1 = -ca, -cz
+            s0 = _mul(c0, eca, c0, eca); s1 = _mul(c1, ecz, c1, ecz)
+            dd, edd = _add(s0[0], s0[1], s1[0], s1[1])
+            s, es = _add(dd, edd, -rr, err)
+            v0, ev0 = _sqrt(s, es)
+            t_a = _mul(v0, ev0, c0, eca); t_b = _mul(r, er, c1, ecz); t_c = _mul(r, er, c0, eca); t_d = _mul(v0, ev0, c1, ecz)
+            mn0 = _add(t_a[0], t_a[1], -t_b[0], t_b[1]); mn1 = _add(t_c[0], t_c[1], t_d[0], t_d[1])
+            mx0 = _add(t_a[0], t_a[1], t_b[0], t_b[1]); mx1 = _add(-t_c[0], t_c[1], t_d[0], t_d[1])
+            lo = _mul(*_div_margin(mn0[0], mn0[1], mn1[0], mn1[1]), P, 0.0)
+            hi = _mul(*_div_margin(mx0[0], mx0[1], mx1[0], mx1[1]), P, 0.0)
+            return lo, hi
+
+        (lox, hix), (loy, hiy) = axis(cx, ecx, P00), axis(cy, ecy, P11)
+        to_uv = lambda t, s: _add(*_mul(t[0], t[1], s, 0.0), 0.5, 0.0)
+        ax, ay, az, aw = to_uv(lox, 0.5), to_uv(hiy, -0.5), to_uv(hix, 0.5), to_uv(loy, -0.5)    # aabb.xwzy * (0.5, -0.5, 0.5, -0.5) + 0.5
+        width, ewidth = _mul(*_add(az[0], az[1], -ax[0], ax[1]), float(W), 0.0)
+        height, eheight = _mul(*_add(aw[0], aw[1], -ay[0], ay[1]), float(H), 0.0)
+        m = np.where(width < height, height, width)
+        m = np.where(np.isnan(width) | np.isnan(height), np.nan, m)                    # max() of a NaN is not specified: not decided below
+        em = np.maximum(ewidth, eheight)
+        lg = np.where(m > 0, np.floor(np.log2(np.where(m > 0, m, 1.0))), -np.inf)      # floor(log2(m)); m <= 0, NaN -> below the chain
+        level = np.clip(np.where(np.isnan(lg), 0.0, lg), 0, levels - 1).astype(np.int64)
+        if levels > 1:
+            d_pow2 = np.min(np.abs(m[:, None] - 2.0 ** np.arange(1, levels)[None, :]), -1)
+        else:
+            d_pow2 = np.full(n, np.inf)
+        level_decided = np.isfinite(m) & ((em == 0) | (d_pow2 > 2.0 * U24 * em) | (levels == 1))
+        u, eu = _mul(*_add(ax[0], ax[1], az[0], az[1]), 0.5, 0.0)
+        v, ev = _mul(*_add(ay[0], ay[1], aw[0], aw[1]), 0.5, 0.0)
+        wl = np.array([s[0] for s in sizes])[level]; hl = np.array([s[1] for s in sizes])[level]
+        x, ex = _add(*_mul(u, eu, wl.astype(np.float64), 0.0), -0.5, 0.0)
+        y, ey = _add(*_mul(v, ev, hl.astype(np.float64), 0.0), -0.5, 0.0)
+        fx = {k: np.zeros(n, a.dtype) for k, a in _fetch_axis(np.zeros(1), np.zeros(1), 1).items()}
+        fy = {k: a.copy() for k, a in fx.items()}
+        for lv in range(levels):
+            sel = level == lv
+            if sel.any():
+                for dst, src in ((fx, _fetch_axis(x[sel], np.broadcast_to(ex, (n,))[sel], sizes[lv][0])),
+                                 (fy, _fetch_axis(y[sel], np.broadcast_to(ey, (n,))[sel], sizes[lv][1]))):
+                    for k in dst:
+                        dst[k][sel] = src[k]
+        base = offs[level]
+        t00 = base + fy["c0"] * wl + fx["c0"]
+        t10 = np.where(fx["use1"], base + fy["c0"] * wl + fx["c1"], -1)
+        t01 = np.where(fy["use1"], base + fy["c1"] * wl + fx["c0"], -1)
+        t11 = np.where(fx["use1"] & fy["use1"], base + fy["c1"] * wl + fx["c1"], -1)
+        footprint = np.where(gate[:, None], np.stack([t00, t10, t01, t11], -1), -1)
+        texels = np.where(footprint >= 0, pyr[np.clip(footprint, 0, None)], np.inf)
+        depth = texels.min(-1)                                                         # NaN texels: reported as not decided
+        den, eden = _add(cz, ecz, -r, er)
+        ds, eds = _div_margin(z_near, 0.0, den, eden)
+        occluded = gate & (ds < depth)
+        depth_decided = _decided(ds - depth, eds) & ~np.isnan(texels).any(-1)
+        footprint_decided = fx["decided"] & fy["decided"]
+        # float64 neither overflows nor goes denormal where fp32 does: outside fp32's normal range nothing below counts as decided
+        in_range = np.ones(n, bool)
+        for t in (wc[:, 0], wc[:, 1], wc[:, 2], wc[:, 3], cx, cy, cz, r, rr, cx * cx, cy * cy, cz * cz, r * cx, r * cy, r * cz, lox[0], hix[0], loy[0], hiy[0],
+                  width, height, ds):
+            in_range &= np.isfinite(t) & ((t == 0) | ((np.abs(t) > 2.0 ** -120) & (np.abs(t) < 2.0 ** 120)))
+        decided = frustum_decided & (frustum | (gate_decided & (~gate | (level_decided & footprint_decided & depth_decided & in_range))))
+    out.update(gate=gate, gate_decided=gate_decided, q_gate=cz - g, m=m, level=level, level_raw=lg, level_decided=level_decided, d_pow2=d_pow2, uv=np.stack([u, v], -1),
+               fx=fx, fy=fy, footprint=footprint, footprint_decided=footprint_decided, depth_sphere=ds, depth=depth, q_depth=ds - depth,
+               depth_decided=depth_decided, occluded=occluded, culled=frustum | occluded, decided=decided, level_size=np.stack([wl, hl], -1))
+    return out
+
+
+def footprint_sets(footprint: np.ndarray):
+    """int64[n, 4] with -1 = none -> a list of frozensets of pyramid texel indices"""
+    return [frozenset(int(t) for t in row if t >= 0) for row in footprint]
+
+
+def _hiz_axis_exact(src: int, dst: int):
+    """texel i of `dst` samples u = (i + 0.5) / dst: x = u src - 0.5 = ((2 i + 1) src - dst) / (2 dst), in integers -> (c0, c1), c1 == c0 where the
+    second weight is 0"""
+    i = np.arange(dst, dtype=np.int64)
+    num, den = (2 * i + 1) * src - dst, 2 * dst
+    i0 = num // den                                                                    # floor, also for negatives
+    c0 = np.clip(i0, 0, src - 1)
+    return c0, np.where(num % den == 0, c0, np.clip(i0 + 1, 0, src - 1))
+
+
+def _hiz_axis_fp32(src: int, dst: int):
+    """the same position as a fp32 evaluation of the shader's expression gives it: (float(i) + 0.5) / float(dst), times float(src), minus 0.5"""
+    i = np.arange(dst).astype(np.float32)
+    x = (i + np.float32(0.5)) / np.float32(dst) * np.float32(src) - np.float32(0.5)
+    fl = np.floor(x)
+    i0 = fl.astype(np.int64)
+    c0 = np.clip(i0, 0, src - 1)
+    return c0, np.where(x - fl == 0, c0, np.clip(i0 + 1, 0, src - 1))
+
+
+def hiz_downscale(src: np.ndarray, dst_w: int, dst_h: int) -> dict:
+    """ComputeDepthHighZ.shader:22-30 over src[H, W] -> dict: values float64[dst_h, dst_w] (minimum over the EXACT footprint), agree bool (the
+    footprint of a fp32 evaluation of the position is the same set of texels), cols / rows (how many output columns / rows differ: the
+    sampler-convention texels lie on them), nan (a NaN texel in the footprint: the sampler's rule for it is not specified)"""
+    src = np.asarray(src, np.float64)
+    sh, sw = src.shape
+    x0, x1 = _hiz_axis_exact(sw, dst_w); y0, y1 = _hiz_axis_exact(sh, dst_h)
+    fx0, fx1 = _hiz_axis_fp32(sw, dst_w); fy0, fy1 = _hiz_axis_fp32(sh, dst_h)
+    col_ok = (x0 == fx0) & (x1 == fx1); row_ok = (y0 == fy0) & (y1 == fy1)
+    taps = np.stack([src[np.ix_(y0, x0)], src[np.ix_(y0, x1)], src[np.ix_(y1, x0)], src[np.ix_(y1, x1)]])
+    with np.errstate(invalid="ignore"):
+        values = np.fmin.reduce(taps)
+    return dict(values=values, agree=row_ok[:, None] & col_ok[None, :], cols=int((~col_ok).sum()), rows=int((~row_ok).sum()), nan=np.isnan(taps).any(0),
+                axes=(x0, x1, y0, y1))
+
+
+def hiz_build(depth: np.ndarray, width: int, height: int, levels: int, given: np.ndarray | None = None) -> dict:
+    """DepthHighZNode.cpp:74-96: mip 0 from the depth attachment, mip i + 1 from mip i.  -> dict: pyramid float64 (flat, level-major), agree bool (flat),
+    nan bool (flat), convention [(cols, rows)] per level.  With `given` (a flat pyramid, the implementation's own) every level is computed from the
+    level below of THAT pyramid: each step is then checked on identical input and `agree` is the step's own footprint agreement.  Without it the
+    chain is the reference's own and a texel agrees only if every texel under it does."""
+    sizes, offs = hiz_level_sizes(width, height, levels)
+    out = np.zeros(offs[-1]); agree = np.zeros(offs[-1], bool); nan = np.zeros(offs[-1], bool)
+    src = np.asarray(depth, np.float64); src_agree = np.ones(src.shape, bool)
+    convention = []
+    for l, (w, h) in enumerate(sizes):
+        d = hiz_downscale(src, w, h)
+        x0, x1, y0, y1 = d["axes"]
+        ok = d["agree"] & src_agree[np.ix_(y0, x0)] & src_agree[np.ix_(y0, x1)] & src_agree[np.ix_(y1, x0)] & src_agree[np.ix_(y1, x1)]
+        out[offs[l]:offs[l + 1]] = d["values"].reshape(-1); agree[offs[l]:offs[l + 1]] = ok.reshape(-1); nan[offs[l]:offs[l + 1]] = d["nan"].reshape(-1)
+        convention.append((d["cols"], d["rows"]))
+        if given is None:
+            src, src_agree = d["values"], ok
+        else:
+            src, src_agree = np.asarray(given, np.float64)[offs[l]:offs[l + 1]].reshape(h, w), np.ones((h, w), bool)
+    return dict(pyramid=out, agree=agree, nan=nan, convention=convention)
+
+
+def compact_partition(words: np.ndarray, batches: np.ndarray):
+    """ComputeMeshCulling.shader step 3 (:146-177) stated as what it computes: per batch (indexCount, instanceCount, firstIndex, vertexOffset,
+    firstInstance) the records whose isCulled word (word 21 of 24) is 0, in their order, at the front of the batch's range; instanceCount = their
+    number; every record behind the kept prefix, and every record no batch owns, as it was.  words uint32[n, 24] AFTER step 2 -> (words, batches)"""
+    words = np.ascontiguousarray(words, np.uint32).reshape(-1, 24)
+    out, bt = words.copy(), np.ascontiguousarray(batches, np.uint32).reshape(-1, 5).copy()
+    for b in range(len(bt)):
+        f, c = int(bt[b, 4]), int(bt[b, 1])
+        keep = np.nonzero(words[f:f + c, 21] == 0)[0] + f
+        out[f:f + len(keep)] = words[keep]
+        bt[b, 1] = len(keep)
+    return out, bt

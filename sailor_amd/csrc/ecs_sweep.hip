@@ -383,8 +383,10 @@ __device__ __forceinline__ int hiz_coord(float x, int size)
 __device__ __forceinline__ float hiz_fetch_min(const float* __restrict__ tex, int W, int H, float u, float v)
 {
     const float x = u * (float)W - 0.5f, y = v * (float)H - 0.5f;
-    const float fx = x - floorf(x), fy = y - floorf(y);
-    const int x0 = hiz_coord(x, W), x1 = hiz_coord(x + 1.0f, W), y0 = hiz_coord(y, H), y1 = hiz_coord(y + 1.0f, H);
+    const float flx = floorf(x), fly = floorf(y);
+    const float fx = x - flx, fy = y - fly;
+    // i1 = i0 + 1 on the floors: floorf(x + 1.0f) is one texel too far where the sum rounds up to an integer (x = -2^-25 gives 1.0f)
+    const int x0 = hiz_coord(flx, W), x1 = hiz_coord(flx + 1.0f, W), y0 = hiz_coord(fly, H), y1 = hiz_coord(fly + 1.0f, H);
     const bool useX1 = !(fx == 0.0f), useY1 = !(fy == 0.0f);
     float m = tex[(size_t)y0 * W + x0];
     if (useX1) { const float t = tex[(size_t)y0 * W + x1]; m = t < m ? t : m; }

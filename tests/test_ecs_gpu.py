@@ -198,3 +198,126 @@ def test_a_slice_of_a_deep_hierarchy_is_refused(ctx):
     ow, oa, ov = oracle.ecs_sweep(ents.transforms, ents.parent, ents.local_aabb, planes)
     np.testing.assert_array_equal(world.cpu().numpy().view(np.uint32), ow.view(np.uint32))
     np.testing.assert_array_equal(vis.cpu().numpy().view(np.uint64), ov)
+
+
+# ---- unaligned box arrays and exact plane ties ---------------------------------------------------------------------------------------------------
+def _sweep_direct(ctx, ents, planes, box_offset: int, trs_byte_offset: int = 0):
+    """sailor_hip_ecs_sweep through the C-ABI with dLocalAabb / dWorldAabb advanced by `box_offset` boxes inside buffers that many boxes longer (every
+    access stays inside its allocation) -> (rc, world, world boxes [n, 6], visibility, the whole box buffer)"""
+    lib = _lib.load()
+    n = len(ents.parent)
+    dev = ctx.device
+    trs = torch.zeros((n + 1, 12), dtype=torch.float32, device=dev)
+    trs[:n] = torch.from_numpy(ents.transforms)
+    parent = torch.from_numpy(ents.parent.view(np.int32)).to(dev)
+    local = torch.zeros((n + box_offset, 6), dtype=torch.float32, device=dev)
+    local[box_offset:] = torch.from_numpy(ents.local_aabb)
+    world = torch.full((n, 16), -7.0, dtype=torch.float32, device=dev)
+    boxes = torch.full((n + box_offset, 6), -7.0, dtype=torch.float32, device=dev)
+    vis = torch.full(((n + 63) // 64,), 0x55, dtype=torch.int64, device=dev)
+    offs = np.ascontiguousarray(ents.level_offsets, np.uint32)
+    pl = np.ascontiguousarray(planes, np.float32).reshape(24)
+    rc = lib.sailor_hip_ecs_sweep(ctx.handle, n, trs.data_ptr() + trs_byte_offset, parent.data_ptr(), offs.ctypes.data_as(C.POINTER(C.c_uint32)), len(offs) - 1,
+                                  local.data_ptr() + 24 * box_offset, pl.ctypes.data_as(C.POINTER(C.c_float)), world.data_ptr(),
+                                  boxes.data_ptr() + 24 * box_offset, vis.data_ptr())
+    ctx.synchronize()
+    return rc, world.cpu().numpy(), boxes.cpu().numpy()[box_offset:], vis.cpu().numpy().view(np.uint64), boxes.cpu().numpy()
+
+
+@pytest.mark.parametrize("levels", [3, 6])
+def test_sweep_with_box_arrays_off_the_16_byte_grid(ctx, levels):
+    """torch allocations are 256-byte aligned, so k4_ecs_level's boxVec == 0 path had never run on a full 64-entity word: 200 entities (three full
+    words and a ragged one) with both box arrays advanced by one box (24 bytes = 8 mod 16), as one fused launch (3 levels) and level by level (6)"""
+    ents = synth.make_entities(200)
+    if levels == 6:
+        ents.level_offsets = np.array([0, 70, 140, 150, 170, 190, 200], np.uint32)
+        ents.parent[:] = 0xFFFFFFFF
+        for lvl in range(1, 6):
+            lo, hi, plo = int(ents.level_offsets[lvl]), int(ents.level_offsets[lvl + 1]), int(ents.level_offsets[lvl - 1])
+            ents.parent[lo:hi] = plo + (np.arange(hi - lo) % (lo - plo))
+            ents.transforms[lo:hi, 0:3] *= np.float32(0.01)
+            ents.transforms[lo:hi, 8:11] = 1.0
+    planes = camera_planes(synth.make_camera(1920, 1080))
+    rc, world, boxes, vis, whole = _sweep_direct(ctx, ents, planes, 1)
+    assert rc == 0
+    ow, oa, ov = oracle.ecs_sweep(ents.transforms, ents.parent, ents.local_aabb, planes)
+    np.testing.assert_array_equal(world.view(np.uint32), ow.view(np.uint32))
+    np.testing.assert_array_equal(boxes.view(np.uint32), oa.view(np.uint32))
+    np.testing.assert_array_equal(vis, ov)
+    assert (whole[0] == -7.0).all(), "the box in front of the advanced pointer is not written"
+
+
+def test_caster_masks_with_a_box_array_off_the_16_byte_grid(ctx):
+    """k4_csm_caster_masks' unstaged path on full words: the world boxes advanced by one box"""
+    lib = _lib.load()
+    ents = synth.make_entities(200)
+    cam = synth.make_camera(1920, 1080)
+    _, oa, _ = oracle.ecs_sweep(ents.transforms, ents.parent, ents.local_aabb, camera_planes(cam))
+    sh = synth.make_shadow_set(cam, 16)
+    planes = np.ascontiguousarray(np.stack([host.extract_frustum_planes_matrix(sh.lights_matrices[k])[0] for k in range(4)]), np.float32).reshape(-1, 24)
+    boxes = torch.zeros((201, 6), dtype=torch.float32, device=ctx.device)
+    boxes[1:] = torch.from_numpy(oa)
+    out = torch.full((4, 4), 0x55, dtype=torch.int64, device=ctx.device)
+    rc = lib.sailor_hip_csm_caster_masks(ctx.handle, 200, boxes.data_ptr() + 24, planes.ctypes.data_as(C.POINTER(C.c_float)), 4, out.data_ptr())
+    ctx.synchronize()
+    assert rc == 0
+    ref = oracle.csm_caster_masks(oa, planes)
+    np.testing.assert_array_equal(out.cpu().numpy().view(np.uint64), ref)
+    assert 0 < int(np.unpackbits(ref.view(np.uint8)).sum()) < 800
+
+
+def test_a_misaligned_transform_array_is_refused_before_any_launch(ctx):
+    ents = synth.make_entities(200)
+    planes = camera_planes(synth.make_camera(1920, 1080))
+    rc, world, boxes, vis, _ = _sweep_direct(ctx, ents, planes, 0, trs_byte_offset=8)
+    assert rc == -1
+    assert (world == -7.0).all() and (boxes == -7.0).all() and (vis == 0x55).all(), "nothing was launched"
+
+
+def _tie_entities(coords, axis: int, low_side: bool):
+    """unrotated unit-scale roots whose world box has its minimum (low_side) or maximum along `axis` at the given coordinates: the translation is an
+    integer and the local box carries the rest, so the world box is exact"""
+    n = len(coords)
+    ents = synth.make_entities(n, editor_world=False)
+    ents.parent[:] = 0xFFFFFFFF
+    ents.level_offsets = np.array([0, n], np.uint32)
+    ents.transforms[:] = np.float32([0, 0, 0, 1, 0, 0, 0, 1, 1, 1, 1, 1])
+    ents.local_aabb[:] = np.float32([-1, -1, -1, 1, 1, 1])
+    ents.local_aabb[:, axis + (0 if low_side else 3)] = coords
+    ents.local_aabb[:, axis + (3 if low_side else 0)] = coords + np.float32(5.0 if low_side else -5.0)
+    return ents
+
+
+@pytest.mark.parametrize("plane, axis, low_side", [((-1.0, 0.0, 0.0, 100.0), 0, True), ((0.0, 1.0, 0.0, -100.0), 1, False)])
+def test_sweep_plane_ties(ctx, plane, axis, low_side):
+    """Frustum::OverlapsAABB is `d > 0`: a box that touches an axis-aligned plane (d == 0) is invisible, one float inside it is visible.  Hand-made
+    planes: (-1, 0, 0, 100) against a box whose min.x is 100, (0, 1, 0, -100) against one whose max.y is 100; the other five planes are (0, 0, 0, 1).
+    (A box whose max is -100 cannot be swept to a tie: AABB::Apply seeds the maximum with FLT_MIN, see test_flt_min_quirk_all_negative_box; the cascade
+    test below has it.)"""
+    inside = np.float32(-1.0 if low_side else 1.0)
+    coords = np.float32([100.0, np.nextafter(np.float32(100.0), np.float32(100.0) + inside), np.nextafter(np.float32(100.0), np.float32(100.0) - inside)])
+    ents = _tie_entities(coords, axis, low_side)
+    planes = np.tile(np.float32([0, 0, 0, 1]), (6, 1))
+    planes[2] = plane
+    sweep = EcsSweep(ctx, ents)
+    _, aabb, vis = sweep.run(planes)
+    ctx.synchronize()
+    _, oa, ov = oracle.ecs_sweep(ents.transforms, ents.parent, ents.local_aabb, planes)
+    np.testing.assert_array_equal(aabb.cpu().numpy().view(np.uint32), oa.view(np.uint32))
+    np.testing.assert_array_equal(vis.cpu().numpy().view(np.uint64), ov)
+    assert oa[0, axis + (0 if low_side else 3)] == 100.0
+    assert int(ov[0]) == 0b010, "the tie and the float outside are invisible, the float inside is visible"
+
+
+def test_cascade_plane_ties(ctx):
+    """the same compare in k4_csm_caster_masks on hand-made world boxes: plane (1, 0, 0, 100), max.x == -100 is outside (d == 0), the next float is in"""
+    from sailor_amd.forward_plus import csm_caster_masks
+    up = np.nextafter(np.float32(-100.0), np.float32(0.0)); down = np.nextafter(np.float32(-100.0), np.float32(-200.0))
+    boxes = np.float32([[-105, -1, -1, -100.0, 1, 1], [-105, -1, -1, up, 1, 1], [-105, -1, -1, down, 1, 1]])
+    planes = np.tile(np.float32([0, 0, 0, 1]), (1, 6, 1))
+    planes[0, 4] = [1, 0, 0, 100]
+    got = csm_caster_masks(ctx, torch.from_numpy(boxes).to(ctx.device), planes)
+    ctx.synchronize()
+    ref = oracle.csm_caster_masks(boxes, planes)
+    np.testing.assert_array_equal(got.cpu().numpy().view(np.uint64), ref)
+    assert int(ref[0, 0]) == 0b010
