@@ -1247,7 +1247,7 @@ typedef struct SailorSurfaceDraw {
     uint32_t numTriangles;
     uint32_t numDrawn;
     uint32_t primBase;                          /* the order of the draw's first primitive: the previous draw's primBase + its sailor_hip_surface_draw_prims */
-    uint32_t flags;                             /* SAILOR_SURFACE_CULL_BACK; SAILOR_SURFACE_ALPHA_CUTOUT through sailor_hip_surface_draw_masked and _draw_gltf only; SAILOR_SURFACE_GLTF (below) through _draw_gltf only */
+    uint32_t flags;                             /* SAILOR_SURFACE_CULL_BACK; SAILOR_SURFACE_ALPHA_CUTOUT through sailor_hip_surface_draw_masked, _draw_gltf and _draw_indirect only; SAILOR_SURFACE_GLTF (below) through _draw_gltf and _draw_indirect only */
     uint32_t firstInstance;
     uint32_t _pad;
 } SailorSurfaceDraw;
@@ -1300,7 +1300,8 @@ SAILOR_HIP_API int sailor_hip_surface_draw_prims(uint32_t numTriangles, uint32_t
  *     keys stay order-free; the decision is taken in the draw, before the key is issued (exact inside test and z -> plain load of the pixel's key -> alpha
  *     only if the key would win -> atomicMax only for a survivor).  sailor_hip_surface_resolve, _composite and sailor_hip_surface_draw are unchanged.
  *  5. NOT reproduced: the Transparent queue, masked shadow casters (Standard_glTF.shader's alphaCutoff as a material field: sailor_hip_surface_draw_gltf,
- *     below; the threshold HERE is the constant 0.5), and a DepthPrepass node in the runtime mirror (a Masked prepass is begin(opaque depth), the masked draws, sailor_hip_surface_store_depth).
+ *     below; the threshold HERE is the constant 0.5).  (A Masked prepass is begin(opaque depth), the masked draws, sailor_hip_surface_store_depth: what the runtime
+ *     mirror's DepthPrepass node records through DrawIndexedIndirect.)
  * Both entry points record only; a refused call launches nothing and leaves its text in last_error. */
 
 /* Replaces: one DrawIndexed of a material with or without ALPHA_CUTOUT: k_surface_visibility_masked.  The checks and refusals of sailor_hip_surface_draw;
@@ -1367,7 +1368,7 @@ typedef struct SailorGltfMaterialData {
     uint32_t _pad[2];
 } SailorGltfMaterialData;
 
-#define SAILOR_SURFACE_GLTF 4u /* the draw's material is Standard_glTF.shader's: sailor_hip_surface_draw_gltf only; the two other draw calls refuse it */
+#define SAILOR_SURFACE_GLTF 4u /* the draw's material is Standard_glTF.shader's: sailor_hip_surface_draw_gltf and _draw_indirect only; sailor_hip_surface_draw and _draw_masked refuse it */
 
 /* Replaces: one DrawIndexed of a Standard_glTF.shader material, with or without ALPHA_CUTOUT: k_surface_visibility_gltf.  The arguments, checks and refusals
  * of sailor_hip_surface_draw_masked; flags must hold SAILOR_SURFACE_GLTF and may hold CULL_BACK and ALPHA_CUTOUT; the descriptor is stored with the flag,
@@ -1388,6 +1389,43 @@ SAILOR_HIP_API int sailor_hip_surface_resolve_gltf(SailorHipContext* ctx, const 
 /* Replaces: sailor_hip_surface_composite for such a pass: target = covered ? (emissive.rgb + radiance.rgb, radiance.a) : target (rule 7). */
 SAILOR_HIP_API int sailor_hip_surface_composite_gltf(SailorHipContext* ctx, const float* dRadiance, const float* dEmissive, const void* dWorkspace,
                                                      size_t workspaceBytes, float* dTarget, int32_t width, int32_t height, const SailorBand* band);
+
+/* ---- GPU-driven draws: DrawIndexedIndirect in the surface pass (surface_indirect.hip) ---------------------------------------------------------------
+ * Replaces: the scene draws as the reference records them -- every one a DrawIndexedIndirect (RHI/Batch.hpp:169, :289; RHI/GraphicsDriver.h:323;
+ * VulkanGraphicsDriver.cpp:2607-2620 issues drawCount > 1 one command at a time), whose command the "GPU Culling" dispatch (Batch.hpp:174-190,
+ * ComputeMeshCulling.shader:146-177 == sailor_hip_mesh_cull_compact[_ex]) has rewritten on the device: instanceCount is the number of survivors and the
+ * per-instance records of the batch are compacted in place behind firstInstance.  The host never learns the count; the draw reads it where it runs.
+ * Pinned:
+ *  1. `draw` is the command AS THE HOST WROTE IT (Batch.hpp:148-153): dVertices and dIndices already offset by vertexOffset / firstIndex, numTriangles from
+ *     indexCount, numDrawn the CAPACITY -- the un-culled instanceCount.  The grid and the primBase arithmetic are sized from it.  dInstanceIds must be NULL
+ *     (refused otherwise); draw->firstInstance is ignored.
+ *  2. The kernel reads two words of *dCommand when it RUNS, with plain loads: instanceCount and firstInstance.  Nothing of *dCommand is read at record
+ *     time, so a captured graph replays against whatever the buffer holds then.
+ *  3. Drawn instances: n = min(instanceCount, capacity, numInstanceRecords - firstInstance), and n = 0 when firstInstance >= numInstanceRecords.  Instance
+ *     d < n is record firstInstance + d; no fetch leaves a table.  A lane whose d >= n does not exist: no set-up, no part in the ballots of the
+ *     large-triangle path.  A block whose every lane is beyond n leaves after the one uniform load (block 0 stays: it stores the descriptor).
+ *  4. The descriptor stored in slot drawIndex holds numDrawn = n and firstInstance as read, so sailor_hip_surface_resolve[_gltf], _composite[_gltf] and
+ *     _store_depth work unchanged.  A command with n == 0 still leaves its descriptor.
+ *  5. order = primBase + d * 2 * numTriangles + 2 * triangle + part as in every draw of the pass.  The NEXT draw's primBase advances by the capacity:
+ *     sailor_hip_surface_draw_prims(numTriangles, capacity).  Order only has to be monotone, so the winners are those of direct draws of the survivors; the
+ *     low words of the keys differ from such a pass's where a draw behind a partially counted one owns the pixel.  The 2^32 - 1 refusal is checked against
+ *     the capacity.
+ *  6. The slices of a draw of few triangles (gridDim.y) are chosen from the capacity: a draw of large capacity and few survivors runs its large triangles
+ *     unsliced.  What that costs has not been measured.
+ *  7. flags: SAILOR_SURFACE_CULL_BACK; SAILOR_SURFACE_ALPHA_CUTOUT (requires the tables); SAILOR_SURFACE_GLTF picks k_surface_visibility_indirect_gltf,
+ *     its absence k_surface_visibility_indirect.  Without ALPHA_CUTOUT the keys are sailor_hip_surface_draw's and the tables are not read.
+ *  8. Checks and refusals: those of sailor_hip_surface_draw_masked / _gltf, plus dCommand NULL or not 4-byte aligned, plus dInstanceIds != NULL.
+ * NOT reproduced -- a DECISION: indexCount, firstIndex and vertexOffset are taken from the host's copy (`draw`), not from *dCommand.  The reference's host
+ * wrote them in the same frame and no GPU pass of the reference rewrites them.  Also not reproduced: indirect shadow casters, drawCount > 1 in one call
+ * (the caller loops, as the Vulkan driver does).
+ * The call records only (no allocation, no synchronisation, capturable); a refused call launches nothing and leaves its text in last_error. */
+
+/* Replaces: one command of DrawIndexedIndirect (RHI/GraphicsDriver.h:323; VulkanGraphicsDriver.cpp:2607-2620 issues drawCount > 1 one by one). */
+SAILOR_HIP_API int sailor_hip_surface_draw_indirect(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSurfaceDraw* draw,
+                                                    const SailorDrawIndexedIndirectData* dCommand, const SailorPerInstanceData* dInstances,
+                                                    uint32_t numInstanceRecords, const SailorMaterialData* dMaterials, uint32_t numMaterials,
+                                                    const SailorTextureDesc* dTextures, uint32_t numTextures, uint32_t drawIndex, int32_t width, int32_t height,
+                                                    const SailorBand* band, void* dWorkspace, size_t workspaceBytes);
 
 /* ---- DebugDraw: the line-list pass of the Gizmo material (debug_lines.hip) ---------------------------------------------------------------------
  * Replaces: the draw FrameGraph/DebugDrawNode.cpp:19-79 replays -- RHI/DebugContext.cpp:382-398 (DrawDebugMesh: one DrawIndexed over the line list that

@@ -434,6 +434,8 @@ SIGNATURES = {
     "sailor_hip_surface_resolve_gltf": (C.c_int, [_P, C.POINTER(UboFrameData), _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, C.c_int32, C.POINTER(Band), _P, C.c_size_t,
                                                   _P, C.c_size_t, _P, _P, _P, _P, _P]),
     "sailor_hip_surface_composite_gltf": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P, C.c_int32, C.c_int32, C.POINTER(Band)]),
+    "sailor_hip_surface_draw_indirect": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(SurfaceDraw), _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32,
+                                                   C.c_int32, C.c_int32, C.POINTER(Band), _P, C.c_size_t]),
     "sailor_hip_surface_keys_offset": (C.c_size_t, []),
     "sailor_host_srgb_table": (C.c_int, [C.POINTER(C.c_float)]),
     "sailor_hip_surface_draw_prims": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),

@@ -1,0 +1,95 @@
+// GPU-driven draws in the surface pass: one command of DrawIndexedIndirect (RHI/GraphicsDriver.h:323) as the reference records every scene draw
+// (RHI/Batch.hpp:169, :289).  The host knows the command as it wrote it (Batch.hpp:148-153) -- the un-culled instanceCount is the CAPACITY of the draw --,
+// the "GPU Culling" dispatch (ComputeMeshCulling.shader:146-177; sailor_hip_mesh_cull_compact) rewrites instanceCount and compacts the records in place, and
+// the draw reads the count where it runs: the host never learns how many instances survive.  include/sailor_hip.h has the pinned rules; tests/indirect_ref.py
+// restates them and the kernels are held to the existing restatements of the surviving draws bit for bit.
+//
+//   k_surface_visibility_indirect        surface_masked_body.h's draw for Standard.shader (with or without ALPHA_CUTOUT), the grid sized from the capacity.
+//   k_surface_visibility_indirect_gltf   the same for Standard_glTF.shader.
+//
+// Each begins with ONE wave-uniform plain load of the command's instanceCount and firstInstance, clamps the count (rule 3) and hands the body a descriptor
+// that holds numDrawn = n and firstInstance as read.  From there on the body is what the direct draws run: a lane at or beyond n * numTriangles has no
+// triangle (`have` is false: no set-up, no part in the ballots), the descriptor block 0 stores is the clamped one, and order = primBase + 2 * id + part with
+// id = d * numTriangles + triangle does not depend on the count.  A block whose first lane is beyond the count leaves right after the load.
+#include "surface_masked_body.h"
+
+// rule 3: n = min(instanceCount, capacity, numInstanceRecords - firstInstance), 0 when firstInstance >= numInstanceRecords
+__device__ __forceinline__ bool surf_indirect_command(SailorSurfaceDraw& draw, const uint32_t* __restrict__ command, uint32_t numInstanceRecords)
+{
+    const uint32_t count = command[1], first = command[4]; // SailorDrawIndexedIndirectData.instanceCount, .firstInstance: uniform addresses, plain loads
+    const uint32_t room = first < numInstanceRecords ? numInstanceRecords - first : 0u;
+    uint32_t n = count < draw.numDrawn ? count : draw.numDrawn; // (numDrawn arrives as the capacity)
+    n = n < room ? n : room;
+    draw.numDrawn = n;
+    draw.firstInstance = first;
+    // block 0 stays for the descriptor, whatever the count
+    return blockIdx.x == 0 || (unsigned long long)blockIdx.x * 256ull < (unsigned long long)n * draw.numTriangles;
+}
+
+__global__ __launch_bounds__(256) void k_surface_visibility_indirect(Mat4 P, Mat4 V, SailorSurfaceDraw draw, const uint32_t* __restrict__ command,
+                                                                     uint32_t numInstanceRecords, const float* __restrict__ instances,
+                                                                     const SailorMaterialData* __restrict__ materials, uint32_t numMaterials,
+                                                                     const SailorTextureDesc* __restrict__ textures, uint32_t numTextures, uint32_t drawIndex, int W,
+                                                                     int H, int rowBegin, int rows, void* __restrict__ workspace)
+{
+    if (!surf_indirect_command(draw, command, numInstanceRecords)) return;
+    surf_visibility_masked<false>(P, V, draw, instances, materials, numMaterials, textures, numTextures, drawIndex, W, H, rowBegin, rows, workspace);
+}
+
+__global__ __launch_bounds__(256) void k_surface_visibility_indirect_gltf(Mat4 P, Mat4 V, SailorSurfaceDraw draw, const uint32_t* __restrict__ command,
+                                                                          uint32_t numInstanceRecords, const float* __restrict__ instances,
+                                                                          const SailorMaterialData* __restrict__ materials, uint32_t numMaterials,
+                                                                          const SailorTextureDesc* __restrict__ textures, uint32_t numTextures, uint32_t drawIndex,
+                                                                          int W, int H, int rowBegin, int rows, void* __restrict__ workspace)
+{
+    if (!surf_indirect_command(draw, command, numInstanceRecords)) return;
+    surf_visibility_masked<true>(P, V, draw, instances, materials, numMaterials, textures, numTextures, drawIndex, W, H, rowBegin, rows, workspace);
+}
+
+// ---- entry point ----------------------------------------------------------------------------------------------------------------------------------
+extern "C" {
+
+int sailor_hip_surface_draw_indirect(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSurfaceDraw* draw,
+                                     const SailorDrawIndexedIndirectData* dCommand, const SailorPerInstanceData* dInstances, uint32_t numInstanceRecords,
+                                     const SailorMaterialData* dMaterials, uint32_t numMaterials, const SailorTextureDesc* dTextures, uint32_t numTextures,
+                                     uint32_t drawIndex, int32_t width, int32_t height, const SailorBand* band, void* dWorkspace, size_t workspaceBytes)
+{
+    if (!ctx) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (!frame || !draw) return surf_refuse(ctx, "sailor_hip_surface_draw_indirect: frame or draw is NULL");
+    if (!aligned(dCommand, 4)) return surf_refuse(ctx, "sailor_hip_surface_draw_indirect: the command is NULL or not 4-byte aligned");
+    if (!surf_band_ok(width, height, band)) return surf_refuse(ctx, "sailor_hip_surface_draw_indirect: the band is not valid for the frame");
+    if (!aligned(dWorkspace, 16)) return surf_refuse(ctx, "sailor_hip_surface_draw_indirect: the workspace is NULL or not 16-byte aligned");
+    const uint32_t maxDraws = surf_max_draws(width, band, workspaceBytes);
+    if (maxDraws == 0) return surf_refuse(ctx, "sailor_hip_surface_draw_indirect: the workspace is too small");
+    if (drawIndex >= maxDraws) return surf_refuse(ctx, "sailor_hip_surface_draw_indirect: drawIndex is beyond the workspace's descriptor slots");
+    if (draw->flags & ~(SAILOR_SURFACE_CULL_BACK | SAILOR_SURFACE_ALPHA_CUTOUT | SAILOR_SURFACE_GLTF)) return surf_refuse(ctx, "sailor_hip_surface_draw_indirect: unknown flags");
+    if (draw->dInstanceIds) return surf_refuse(ctx, "sailor_hip_surface_draw_indirect: dInstanceIds must be NULL (the instances are firstInstance + d of the command)");
+    if ((draw->flags & SAILOR_SURFACE_ALPHA_CUTOUT) && (!dMaterials || !dTextures || numMaterials == 0 || numTextures == 0))
+        return surf_refuse(ctx, "sailor_hip_surface_draw_indirect: ALPHA_CUTOUT needs materials and textures");
+    const unsigned long long total = (unsigned long long)draw->numDrawn * draw->numTriangles; // the CAPACITY's lanes
+    if (total && (!draw->dVertices || !draw->dIndices || !dInstances)) return surf_refuse(ctx, "sailor_hip_surface_draw_indirect: a vertex, index or instance buffer is NULL");
+    if (total > 0x7FFFFFFFull || (unsigned long long)draw->primBase + 2ull * total >= 0xFFFFFFFFull)
+        return surf_refuse(ctx, "sailor_hip_surface_draw_indirect: primBase + the capacity's primitives reaches 2^32 - 1");
+    Mat4 P, V;
+    memcpy(P.m, frame->projection, 64);
+    memcpy(V.m, frame->view, 64);
+    SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
+    const unsigned long long blocks = total ? (total + 255) / 256 : 1; // (an empty draw still leaves its descriptor)
+    const unsigned long long want = total ? SURF_SLICE_LANES / total : 1; // the slices of sailor_hip_surface_draw, from the capacity: the count is not known here
+    const unsigned slices = (unsigned)(want < 1 ? 1 : (want > SURF_SLICES_MAX ? SURF_SLICES_MAX : want));
+    const uint32_t* command = reinterpret_cast<const uint32_t*>(dCommand);
+    if (draw->flags & SAILOR_SURFACE_GLTF) {
+        sailor_launch(ctx, k_surface_visibility_indirect_gltf, dim3((unsigned)blocks, slices), dim3(256), P, V, *draw, command, numInstanceRecords,
+                      reinterpret_cast<const float*>(dInstances), dMaterials, numMaterials, dTextures, numTextures, drawIndex, (int)width, (int)height,
+                      (int)band->fbRowBegin, (int)band->fbRowCount, dWorkspace);
+        SAILOR_CHECK_LAUNCH(ctx, "k_surface_visibility_indirect_gltf");
+    } else {
+        sailor_launch(ctx, k_surface_visibility_indirect, dim3((unsigned)blocks, slices), dim3(256), P, V, *draw, command, numInstanceRecords,
+                      reinterpret_cast<const float*>(dInstances), dMaterials, numMaterials, dTextures, numTextures, drawIndex, (int)width, (int)height,
+                      (int)band->fbRowBegin, (int)band->fbRowCount, dWorkspace);
+        SAILOR_CHECK_LAUNCH(ctx, "k_surface_visibility_indirect");
+    }
+    return SAILOR_HIP_OK;
+}
+
+} // extern "C"

@@ -996,6 +996,26 @@ class SurfacePass:
         self.prim_base += host.surface_draw_prims(nt, num_drawn)
         self.draw_index += 1
 
+    def draw_indirect(self, frame: UboFrameData, vertices: torch.Tensor, indices: torch.Tensor, instances: torch.Tensor, command: torch.Tensor, capacity: int,
+                      command_index: int = 0, num_instance_records: int | None = None, cull_back: bool = False, alpha_cutout: bool = False,
+                      materials: torch.Tensor | None = None, textures: torch.Tensor | None = None, num_textures: int = 0, gltf: bool = False):
+        """One command of DrawIndexedIndirect (sailor_hip_surface_draw_indirect).  command: the device buffer of 20-byte DrawIndexedIndirectData, e.g.
+        MeshCull's `batches`; command_index: which of them.  capacity: the instanceCount the host wrote (the un-culled count); the kernel reads the count
+        and firstInstance of the command when it runs, and the running primBase advances by the capacity.  num_instance_records: the records `instances`
+        holds for the draw's guard (default: all of the tensor)."""
+        if num_instance_records is None:
+            num_instance_records = instances.numel() * instances.element_size() // 96
+        nt = indices.numel() // 3
+        flags = (_lib.SURFACE_CULL_BACK if cull_back else 0) | (_lib.SURFACE_ALPHA_CUTOUT if alpha_cutout else 0) | (_lib.SURFACE_GLTF if gltf else 0)
+        d = _lib.SurfaceDraw(_ptr(vertices), _ptr(indices), None, nt, capacity, self.prim_base, flags, 0, 0)
+        _lib.check(self.ctx._lib.sailor_hip_surface_draw_indirect(self.ctx.handle, C.byref(frame), C.byref(d), command.data_ptr() + 20 * command_index, _ptr(instances),
+                                                                  num_instance_records, _ptr(materials),
+                                                                  0 if materials is None else materials.numel() * materials.element_size() // 80, _ptr(textures),
+                                                                  num_textures, self.draw_index, self.W, self.H, C.byref(self.band), _ptr(self.workspace),
+                                                                  self.workspace.numel()), "sailor_hip_surface_draw_indirect", self.ctx.handle)
+        self.prim_base += host.surface_draw_prims(nt, capacity)
+        self.draw_index += 1
+
     def store_depth(self, depth: torch.Tensor) -> torch.Tensor:
         """the keys' depth into the band's rows of `depth`, the raw depth attachment of the WHOLE frame, float32 [H, W]: the depth write of a pass that held
         cutout draws"""

@@ -3,6 +3,7 @@
 #include <sstream>
 #include "FrameGraphNode.h"
 #include "LightCullingNode.h"
+#include "DepthPrepassNode.h"
 #include "RHIFrameGraph.h"
 #include "../RHI/Renderer.h"
 #include "../RHI/DebugContext.h"
@@ -40,6 +41,7 @@ FrameGraphNodePtr FrameGraphBuilder::CreateOptInNode(const std::string& nodeName
 // force the registration objects of the path's nodes into the library
 template class Sailor::Framegraph::TFrameGraphNode<LightCullingNode>;
 template class Sailor::Framegraph::TFrameGraphNode<RenderSceneNode>;
+template class Sailor::Framegraph::TFrameGraphNode<DepthPrepassNode>;
 template class Sailor::Framegraph::TFrameGraphNode<LinearizeDepthNode>;
 template class Sailor::Framegraph::TFrameGraphNode<EnvironmentNode>;
 template class Sailor::Framegraph::TFrameGraphNode<DepthHighZNode>;
@@ -350,7 +352,7 @@ void LightCullingNode::Clear()
 // ---- RenderSceneNode (shading consumer) ---------------------------------------------------------------------------------------
 const char* RenderSceneNode::m_name = "RenderScene";
 
-void RenderSceneNode::Process(RHIFrameGraphPtr, RHICommandListPtr, RHICommandListPtr commandList, const RHISceneViewSnapshot& sceneView)
+void RenderSceneNode::Process(RHIFrameGraphPtr frameGraph, RHICommandListPtr transferCommandList, RHICommandListPtr commandList, const RHISceneViewSnapshot& sceneView)
 {
     if (!sceneView.m_rhiLightsData || !sceneView.m_rhiLightsData->Find("culledLights")) return; // RenderSceneNode.cpp:142-146: silent early return
     auto driver = Renderer::GetDriver();
@@ -359,17 +361,34 @@ void RenderSceneNode::Process(RHIFrameGraphPtr, RHICommandListPtr, RHICommandLis
     auto surface = GetRHIResource("surface").DynamicCast<RHIBuffer>();
     auto radiance = GetRHIResource("radiance").DynamicCast<RHIBuffer>();
     if (!surface && !sceneView.m_batches.empty()) { // the reference's own recording (RenderSceneNode.cpp): real draws into (color, depthStencil)
-        auto color = GetRHIResource("color").DynamicCast<RHITexture>();
-        auto depth = GetRHIResource("depthStencil").DynamicCast<RHITexture>();
+        auto resolved = [&](const char* name) -> RHITexturePtr { // GetRHIResource / GetResolvedAttachment: a per-frame target is looked up by its name
+            if (auto t = GetRHIResource(name).DynamicCast<RHITexture>()) return t;
+            auto it = m_unresolvedResourceParams.find(name);
+            return it == m_unresolvedResourceParams.end() ? RHITexturePtr() : frameGraph->GetRenderTarget(it->second);
+        };
+        auto color = resolved("color");
+        auto depth = resolved("depthStencil");
         if (!color) return;
         if (!m_pMaterial) m_pMaterial = driver->CreateMaterial(m_pShader);
         std::string tag;
         const bool tagged = TryGetString("Tag", tag);
+        // `GPUCulling: true`: the Batch.hpp:53-191 sequence -- the node's own records and commands, the cull on the transfer list, indirect draws
+        std::string culling;
+        const bool gpuCulling = TryGetString("GPUCulling", culling) && culling == "true";
+        RHIShaderBindingSetPtr sceneSet = sceneView.m_sceneBindings;
+        if (gpuCulling) {
+            TVector<size_t> selected;
+            for (size_t i = 0; i < sceneView.m_batches.size(); i++)
+                if (sceneView.m_batches[i].m_tag.empty() || (tagged && sceneView.m_batches[i].m_tag == tag)) selected.push_back(i);
+            sceneSet = m_draws.Update(transferCommandList, sceneView, selected, true, resolved("depthHighZ"));
+            if (!sceneSet) return; // nothing of this queue in the view
+        }
         commands->BeginDebugRegion(commandList, std::string(GetName()) + (tagged ? " QueueTag:" + tag : ""));
         commands->BeginRenderPass(commandList, TVector<RHITexturePtr> { color }, depth);
         commands->BindMaterial(commandList, m_pMaterial);
-        commands->BindShaderBindings(commandList, m_pMaterial, { sceneView.m_frameBindings, sceneView.m_rhiLightsData, sceneView.m_sceneBindings });
+        commands->BindShaderBindings(commandList, m_pMaterial, { sceneView.m_frameBindings, sceneView.m_rhiLightsData, sceneSet });
         RHIMaterialPtr bound = m_pMaterial;
+        size_t command = 0;
         for (const auto& b : sceneView.m_batches) {
             if (!b.m_tag.empty() && !(tagged && b.m_tag == tag)) continue; // the render queue filter: an untagged batch belongs to every queue
             RHIMaterialPtr material = m_pMaterial;
@@ -392,6 +411,7 @@ void RenderSceneNode::Process(RHIFrameGraphPtr, RHICommandListPtr, RHICommandLis
                 material = variant;
             }
             if (material.GetRawPtr() != bound.GetRawPtr()) { commands->BindMaterial(commandList, material); bound = material; }
+            if (gpuCulling) { m_draws.Draw(commandList, b, command++); continue; }
             commands->BindVertexBuffer(commandList, b.m_vertexBuffer, 0);
             commands->BindIndexBuffer(commandList, b.m_indexBuffer, 0);
             commands->DrawIndexed(commandList, b.m_indexCount, b.m_instanceCount, b.m_firstIndex, b.m_vertexOffset, b.m_firstInstance);
@@ -423,6 +443,160 @@ void RenderSceneNode::Clear()
     m_pGltfCutoutShader.Clear();
     for (auto& v : m_pGltfMaterials) v.Clear();
     m_surfaceBindings.Clear();
+    m_draws.Clear();
+}
+
+// ---- SceneIndirectDraws: RHIRecordDrawCall / RHIRecordDrawCallGPUCulling (RHI/Batch.hpp:53-191, :193-290) -------------------------------------
+RHIShaderBindingSetPtr SceneIndirectDraws::Update(RHICommandListPtr transferCommandList, const RHISceneViewSnapshot& sceneView, const TVector<size_t>& selected,
+                                                  bool bGpuCulling, RHITexturePtr depthHighZ)
+{
+    auto driver = Renderer::GetDriver();
+    auto commands = Renderer::GetDriverCommands();
+    m_numCommands = 0;
+    auto sceneData = sceneView.m_sceneBindings ? sceneView.m_sceneBindings->Find("data") : RHIShaderBindingPtr();
+    if (selected.empty() || !sceneData || !sceneData->m_buffer) return RHIShaderBindingSetPtr();
+    // Batch.hpp:74-91: the indirect buffer grows with a slack, and is bound as "drawIndexedIndirect"
+    const size_t indirectBufferSize = selected.size() * sizeof(SailorDrawIndexedIndirectData);
+    if (!m_indirectBuffer || m_indirectBuffer->m_size < indirectBufferSize) {
+        m_indirectBuffer = driver->CreateIndirectBuffer(indirectBufferSize + 256);
+        if (!m_indirectBuffer) return RHIShaderBindingSetPtr();
+        m_indirectBinding = driver->CreateShaderBindings();
+        m_indirectBinding->GetOrAddShaderBinding("drawIndexedIndirect")->m_buffer = m_indirectBuffer;
+    }
+    // :137-160 the commands as the host writes them; under culling firstInstance addresses the node's own packed records
+    TVector<SailorDrawIndexedIndirectData> drawIndirect;
+    uint32_t totalNumInstances = 0;
+    for (size_t i : selected) {
+        const RHISceneBatch& b = sceneView.m_batches[i];
+        SailorDrawIndexedIndirectData data {};
+        data.indexCount = b.m_indexCount; data.instanceCount = b.m_instanceCount; data.firstIndex = b.m_firstIndex; data.vertexOffset = (int32_t)b.m_vertexOffset;
+        data.firstInstance = bGpuCulling ? totalNumInstances : b.m_firstInstance;
+        drawIndirect.push_back(data);
+        totalNumInstances += b.m_instanceCount;
+    }
+    commands->BeginDebugRegion(transferCommandList, "Update Indirect Buffer");
+    commands->UpdateBuffer(transferCommandList, m_indirectBuffer, drawIndirect.data(), indirectBufferSize, 0); // (:165)
+    commands->EndDebugRegion(transferCommandList);
+    m_numCommands = selected.size();
+    if (!bGpuCulling) return sceneView.m_sceneBindings; // RHIRecordDrawCall: counts un-culled, no dispatch
+    // the node's m_perInstanceData, refilled every frame (DepthPrepassNode.cpp:185-230): the compaction is in place and would otherwise corrupt the next
+    // node's input.  The reference refills from the proxies' host arrays; the view's records are device-resident here, so the refill is a device copy.
+    const size_t need = (size_t)(totalNumInstances ? totalNumInstances : 1u) * sizeof(SailorPerInstanceData);
+    if (!m_instances || m_instances->m_size != need) {
+        m_instances = driver->CreateBuffer(need);
+        if (!m_instances) return RHIShaderBindingSetPtr();
+        m_perInstanceData = driver->CreateShaderBindings();
+        m_perInstanceData->GetOrAddShaderBinding("data")->m_buffer = m_instances;
+    }
+    // what the draws and the pass's resolve read: the node's compacted copy beside the view's tables of THIS frame (rebuilt every frame: the view's set may be
+    // another one, with other tables, from one frame to the next)
+    m_sceneBindings = driver->CreateShaderBindings();
+    for (auto& kv : sceneView.m_sceneBindings->m_bindings) m_sceneBindings->m_bindings[kv.first] = kv.second;
+    m_sceneBindings->m_bindings["data"] = m_perInstanceData->Find("data");
+    uint32_t packed = 0;
+    for (size_t i : selected) {
+        const RHISceneBatch& b = sceneView.m_batches[i];
+        commands->CopyBuffer(transferCommandList, sceneData->m_buffer, m_instances, (size_t)b.m_instanceCount * sizeof(SailorPerInstanceData),
+                             (size_t)b.m_firstInstance * sizeof(SailorPerInstanceData), (size_t)packed * sizeof(SailorPerInstanceData));
+        packed += b.m_instanceCount;
+    }
+    // RenderSceneNode.cpp:126-139 / DepthPrepassNode.cpp: the culling shader with OCCLUSION_CULLING and the "depthHighZ" attachment as a sampler, when resolved
+    const bool occlusion = depthHighZ && depthHighZ->m_buffer;
+    if (!m_pCullShader || occlusion != m_bCullOcclusion) {
+        m_pCullShader = occlusion ? driver->CreateShader("Shaders/ComputeMeshCulling.shader", { "OCCLUSION_CULLING" }) : driver->CreateShader("Shaders/ComputeMeshCulling.shader");
+        m_bCullOcclusion = occlusion;
+    }
+    m_cullBindings = driver->CreateShaderBindings();
+    if (occlusion) driver->AddSamplerToShaderBindings(m_cullBindings, "depthHighZ", depthHighZ, 0);
+    struct PushConstants { uint32_t m_numBatches = 0, m_numInstances = 0, m_firstInstanceIndex = 0; } constants; // (:174-184)
+    constants.m_numBatches = (uint32_t)selected.size();
+    constants.m_numInstances = totalNumInstances;
+    constants.m_firstInstanceIndex = 0;
+    if (totalNumInstances == 0) return m_sceneBindings;
+    commands->BeginDebugRegion(transferCommandList, "GPU Culling");
+    commands->Dispatch(transferCommandList, m_pCullShader, 256, 1, 1, { m_cullBindings, m_perInstanceData, m_indirectBinding, sceneView.m_frameBindings }, &constants,
+                       sizeof constants); // (:188) the pyramid it reads is the previous frame's: the transfer list is submitted before the graphics list
+    commands->EndDebugRegion(transferCommandList);
+    return m_sceneBindings;
+}
+
+void SceneIndirectDraws::Draw(RHICommandListPtr commandList, const RHISceneBatch& batch, size_t i) const
+{
+    auto commands = Renderer::GetDriverCommands();
+    commands->BindVertexBuffer(commandList, batch.m_vertexBuffer, 0);
+    commands->BindIndexBuffer(commandList, batch.m_indexBuffer, 0);
+    commands->DrawIndexedIndirect(commandList, m_indirectBuffer, i * sizeof(SailorDrawIndexedIndirectData), 1, sizeof(SailorDrawIndexedIndirectData)); // (:169)
+}
+
+void SceneIndirectDraws::Clear()
+{
+    m_indirectBuffer.Clear(); m_instances.Clear();
+    m_indirectBinding.Clear(); m_perInstanceData.Clear(); m_sceneBindings.Clear(); m_cullBindings.Clear();
+    m_pCullShader.Clear();
+    m_numCommands = 0;
+}
+
+// ---- DepthPrepassNode (FrameGraph/DepthPrepassNode.cpp:50-303) ----------------------------------------------------------------------------------
+const char* DepthPrepassNode::m_name = "DepthPrepass";
+
+void DepthPrepassNode::Process(RHIFrameGraphPtr frameGraph, RHICommandListPtr transferCommandList, RHICommandListPtr commandList,
+                               const RHISceneViewSnapshot& sceneView)
+{
+    auto driver = Renderer::GetDriver();
+    auto commands = Renderer::GetDriverCommands();
+    auto resolved = [&](const char* name) -> RHITexturePtr { // GetRHIResource / GetResolvedAttachment: a per-frame target is looked up by its name
+        if (auto t = GetRHIResource(name).DynamicCast<RHITexture>()) return t;
+        auto it = m_unresolvedResourceParams.find(name);
+        return it == m_unresolvedResourceParams.end() ? RHITexturePtr() : frameGraph->GetRenderTarget(it->second);
+    };
+    auto depth = resolved("depthStencil");
+    if (!depth || sceneView.m_batches.empty()) return;
+    std::string tag, value;
+    const bool tagged = TryGetString("Tag", tag);
+    const bool clearDepth = TryGetString("ClearDepth", value) && value == "true";
+    const bool gpuCulling = TryGetString("GPUCulling", value) && value == "true";
+    TVector<size_t> selected;
+    for (size_t i = 0; i < sceneView.m_batches.size(); i++)
+        if (sceneView.m_batches[i].m_tag.empty() || (tagged && sceneView.m_batches[i].m_tag == tag)) selected.push_back(i);
+    RHIShaderBindingSetPtr sceneSet = m_draws.Update(transferCommandList, sceneView, selected, gpuCulling, resolved("depthHighZ"));
+    if (!sceneSet) return; // nothing of this queue in the view
+    if (!m_pDepthShader) m_pDepthShader = driver->CreateShader("Shaders/DepthOnly.shader");
+    commands->BeginDebugRegion(commandList, std::string(GetName()) + (tagged ? " QueueTag:" + tag : ""));
+    commands->BeginRenderPass(commandList, TVector<RHITexturePtr> {}, depth, clearDepth); // no colour attachment
+    RHIMaterialPtr bound;
+    for (size_t k = 0; k < selected.size(); k++) {
+        const RHISceneBatch& b = sceneView.m_batches[selected[k]];
+        RHIMaterialPtr material;
+        if (b.m_bAlphaCutout) { // IsRequiredCustomDepthShader(): the batch's material is its own depth material (:86-90, :107-115, :246-255)
+            RHIShaderPtr& shader = m_pCutoutShaders[b.m_bGltf ? 1 : 0];
+            if (!shader) shader = driver->CreateShader(b.m_bGltf ? "Shaders/Standard_glTF.shader" : "Shaders/Standard.shader", { "ALPHA_CUTOUT" });
+            RHIMaterialPtr& variant = m_pCutoutMaterials[(b.m_bGltf ? 2 : 0) + (b.m_bDoubleSided ? 1 : 0)];
+            if (!variant) { variant = driver->CreateMaterial(shader); variant->m_bDoubleSided = b.m_bDoubleSided; }
+            material = variant;
+        } else {
+            RHIMaterialPtr& variant = m_pDepthMaterials[b.m_bDoubleSided ? 1 : 0];
+            if (!variant) { variant = driver->CreateMaterial(m_pDepthShader); variant->m_bDoubleSided = b.m_bDoubleSided; }
+            material = variant;
+        }
+        if (material.GetRawPtr() != bound.GetRawPtr()) {
+            commands->BindMaterial(commandList, material);
+            if (b.m_bAlphaCutout) commands->BindShaderBindings(commandList, material, { sceneView.m_frameBindings, sceneView.m_rhiLightsData, sceneSet });
+            else commands->BindShaderBindings(commandList, material, { sceneView.m_frameBindings, sceneSet }); // DepthOnly.shader: frame and PerInstanceDataSSBO
+            bound = material;
+        }
+        m_draws.Draw(commandList, b, k);
+    }
+    commands->EndRenderPass(commandList);
+    commands->EndDebugRegion(commandList);
+}
+
+void DepthPrepassNode::Clear()
+{
+    m_pDepthShader.Clear();
+    for (auto& s : m_pCutoutShaders) s.Clear();
+    for (auto& m : m_pDepthMaterials) m.Clear();
+    for (auto& m : m_pCutoutMaterials) m.Clear();
+    m_draws.Clear();
 }
 
 // ---- EyeAdaptationNode (FrameGraph/EyeAdaptationNode.cpp:19-230) ----------------------------------------------------------------

@@ -1,6 +1,7 @@
 // Mirrors Runtime/FrameGraph/LightCullingNode.h:10-37.
 #pragma once
 #include "FrameGraphNode.h"
+#include "SceneIndirectDraws.h"
 
 namespace Sailor::Framegraph {
 
@@ -48,6 +49,8 @@ protected:
 // DrawIndexed, EndRenderPass -- the HIP backend rasterises, resolves, shades and composites behind them (sailor_hip_surface_*).
 // The node's `Tag` is the render queue it draws (RenderSceneNode.cpp: `Tag: Opaque`, then `Tag: Masked` in DefaultRenderer.renderer): a batch is drawn if its own
 // tag is empty or equal to the node's; a batch with ALPHA_CUTOUT is drawn with a material of CreateShader("Shaders/Standard.shader", { "ALPHA_CUTOUT" }).
+// With the string `GPUCulling: true` those draws are DrawIndexedIndirect behind a "GPU Culling" dispatch on the transfer list (SceneIndirectDraws); "depthHighZ"
+// switches the dispatch's OCCLUSION_CULLING on.
 class RenderSceneNode : public TFrameGraphNode<RenderSceneNode> {
 public:
     static const char* GetName() { return m_name; }
@@ -66,6 +69,12 @@ protected:
     RHI::RHIShaderPtr m_pGltfShader, m_pGltfCutoutShader;
     RHI::RHIMaterialPtr m_pGltfMaterials[4];
     RHI::RHIShaderBindingSetPtr m_surfaceBindings;
+    // `GPUCulling: true` (DefaultRenderer.renderer): the draws are recorded as RHIRecordDrawCallGPUCulling records them (SceneIndirectDraws.h); without the
+    // string the node records DrawIndexed with host counts, as before
+    SceneIndirectDraws m_draws;
+
+public:
+    const SceneIndirectDraws& GetIndirectDraws() const { return m_draws; }
 };
 
 // The one-off image-based-lighting bake: Runtime/FrameGraph/EnvironmentNode.h.  Raw environment = the frame graph's sampler

@@ -69,6 +69,17 @@ RHIBufferPtr HipGraphicsDriver::CreateBuffer(size_t size)
     return b;
 }
 
+// RHI/GraphicsDriver.h:91.  The buffer keeps the bytes of its last UpdateBuffer (zeros until then): DrawIndexedIndirect reads the host's copy of a command
+// there, the kernels read what a GPU pass made of it in device memory.
+RHIBufferPtr HipGraphicsDriver::CreateIndirectBuffer(size_t size)
+{
+    auto b = CreateBuffer(size);
+    if (!b) return b;
+    b->m_bIndirect = true;
+    b->m_hostCopy.assign(size, 0);
+    return b;
+}
+
 RHIBufferPtr HipGraphicsDriver::WrapBuffer(void* devicePtr, size_t size)
 {
     auto b = RHIBufferPtr::Make();
@@ -87,7 +98,7 @@ RHIShaderPtr HipGraphicsDriver::CreateShader(const std::string& assetPath, const
         "Shaders/ComputeDepthHighZ.shader", "Shaders/ComputeHistogram.shader", "Shaders/ComputeAverageLuminance.shader", "Shaders/ComputeBrdfLut.shader",
         "Shaders/ComputeIrradianceMap.shader", "Shaders/ComputeEnvMap_IBL.shader", "Shaders/ShadowCaster.shader", "Shaders/LinearizeDepth.shader",
         "Shaders/Tonemapping.shader", "Shaders/Blur.shader", "Shaders/HBAO.shader", "Shaders/HBAO_Blur.shader", "Shaders/Sky.shader", "Shaders/ComputeBloomDownscale.shader",
-        "Shaders/ComputeBloomUpscale.shader", "Shaders/Blit.shader", "Shaders/ChromaticAberation.shader", "Shaders/Gizmo.shader", "Shaders/ImGuiUI.shader" };
+        "Shaders/ComputeBloomUpscale.shader", "Shaders/Blit.shader", "Shaders/ChromaticAberation.shader", "Shaders/Gizmo.shader", "Shaders/ImGuiUI.shader", "Shaders/DepthOnly.shader" };
     auto shader = RHIShaderPtr::Make(assetPath, defines);
     shader->m_bIsReady = false;
     for (const char* name : routed) if (assetPath == name) shader->m_bIsReady = true;
@@ -383,7 +394,7 @@ const Roctx& roctx() { static Roctx r; return r; }
 void HipGraphicsDriver::BeginDebugRegion(RHICommandListPtr cmdList, const std::string& title)
 {
     cmdList->m_debugRegions.push_back(title);
-    cmdList->m_hip.m_commands.push_back([title]() { if (roctx().push) roctx().push(title.c_str()); return (int)SAILOR_HIP_OK; });
+    cmdList->m_hip.m_commands.push_back([this, title]() { m_executedRegions.push_back(title); if (roctx().push) roctx().push(title.c_str()); return (int)SAILOR_HIP_OK; });
 }
 void HipGraphicsDriver::EndDebugRegion(RHICommandListPtr cmdList)
 {
@@ -537,10 +548,25 @@ void HipGraphicsDriver::UpdateShaderBinding(RHICommandListPtr cmd, RHIShaderBind
 void HipGraphicsDriver::UpdateBuffer(RHICommandListPtr cmd, RHIBufferPtr buffer, const void* data, size_t size, size_t offset)
 {
     TVector<uint8_t> staged((const uint8_t*)data, (const uint8_t*)data + size); // payload captured at record time
+    // an indirect buffer's host copy follows at record time, like a UBO binding's: a DrawIndexedIndirect recorded after this reads it
+    if (buffer && buffer->m_bIndirect && offset <= buffer->m_hostCopy.size() && size <= buffer->m_hostCopy.size() - offset)
+        memcpy(buffer->m_hostCopy.data() + offset, data, size);
     SailorHipContext* ctx = m_ctx;
     cmd->m_hip.m_commands.push_back([this, ctx, buffer, staged = std::move(staged), offset]() {
         BeforeBufferWrite(buffer->m_hip.m_devicePtr);
         return sailor_hip_buffer_upload(ctx, buffer->m_hip.m_devicePtr, offset, staged.data(), staged.size());
+    });
+}
+
+void HipGraphicsDriver::CopyBuffer(RHICommandListPtr cmd, RHIBufferPtr src, RHIBufferPtr dst, size_t size, size_t srcOffset, size_t dstOffset)
+{
+    SailorHipContext* ctx = m_ctx;
+    cmd->m_hip.m_commands.push_back([this, ctx, src, dst, size, srcOffset, dstOffset]() {
+        if (!src || !dst || srcOffset > src->m_size || size > src->m_size - srcOffset || dstOffset > dst->m_size || size > dst->m_size - dstOffset)
+            return (int)SAILOR_HIP_ERR_INVALID_ARGUMENT;
+        if (size == 0) return (int)SAILOR_HIP_OK;
+        BeforeBufferWrite(dst->m_hip.m_devicePtr);
+        return sailor_hip_buffer_copy(ctx, dst->m_hip.m_devicePtr, dstOffset, src->m_hip.m_devicePtr, srcOffset, size);
     });
 }
 
@@ -984,10 +1010,12 @@ int HipGraphicsDriver::RecordSurfaceEnd(const TVector<RHIShaderBindingSetPtr>& b
 
 // ---- the render-pass subset: state is kept on the command list, a 6-index draw of a known full-screen material becomes a
 // kernel launch at submit time (record-then-submit, like Dispatch) ---------------------------------------------------------------
-void HipGraphicsDriver::BeginRenderPass(RHICommandListPtr cmd, const TVector<RHITexturePtr>& colorAttachments, RHITexturePtr depthStencilAttachment)
+void HipGraphicsDriver::BeginRenderPass(RHICommandListPtr cmd, const TVector<RHITexturePtr>& colorAttachments, RHITexturePtr depthStencilAttachment,
+                                        bool bClearDepthStencil)
 {
     cmd->m_colorAttachments = colorAttachments;
     cmd->m_depthAttachment = depthStencilAttachment;
+    cmd->m_bClearDepth = bClearDepthStencil;
     cmd->m_casterDraws = 0;
     cmd->m_surfaceDraws = 0;
     cmd->m_surfaceCutout = false;
@@ -1026,7 +1054,12 @@ void HipGraphicsDriver::EndRenderPass(RHICommandListPtr cmd)
                                              color->m_buffer->m_hip.m_devicePtr);
         });
     }
-    if (cmd->m_surfaceDraws > 0) { // RenderScene's pass: the fragment stage of every pixel's winning fragment, then the colour writes
+    if (cmd->m_surfaceDraws > 0 && cmd->m_colorAttachments.empty()) {
+        // a pass with no colour attachment whose draws went to the surface pass (DepthPrepassNode): the keys' depth into the depth attachment and nothing
+        // else -- no resolve, no shade, no composite
+        RHITexturePtr depth = cmd->m_depthAttachment;
+        cmd->m_hip.m_commands.push_back([this, depth]() { return RecordSurfaceEndDepthOnly(depth); });
+    } else if (cmd->m_surfaceDraws > 0) { // RenderScene's pass: the fragment stage of every pixel's winning fragment, then the colour writes
         RHITexturePtr color = cmd->m_colorAttachments.empty() ? RHITexturePtr() : cmd->m_colorAttachments[0];
         TVector<RHIShaderBindingSetPtr> bindings = cmd->m_boundBindings;
         RHITexturePtr depthToStore = cmd->m_surfaceCutout ? cmd->m_depthAttachment : RHITexturePtr();
@@ -1053,6 +1086,7 @@ void HipGraphicsDriver::EndRenderPass(RHICommandListPtr cmd)
     cmd->m_casterDraws = 0;
     cmd->m_surfaceDraws = 0;
     cmd->m_surfaceCutout = false;
+    cmd->m_bClearDepth = false;
     cmd->m_colorAttachments.clear();
     cmd->m_boundMaterial.Clear();
     cmd->m_boundBindings.clear();
@@ -1198,6 +1232,109 @@ void HipGraphicsDriver::DrawIndexed(RHICommandListPtr cmd, uint32_t indexCount, 
         if (fullScreenQuad && name == "Shaders/Debug.shader" && tail) return RecordDebugView(bindings, target, debugMode);
         return (int)SAILOR_HIP_ERR_UNSUPPORTED;
     });
+}
+
+// RHI/GraphicsDriver.h:323.  drawCount > 1 is issued one command at a time, as VulkanGraphicsDriver.cpp:2607-2620 does.  Routed by the bound material exactly as
+// DrawIndexed routes: Standard.shader and Standard_glTF.shader with or without ALPHA_CUTOUT, m_bDoubleSided = no back-face cull, and Shaders/DepthOnly.shader
+// (DepthPrepassNode's depth material: the same position transform, no flag, no tables).  Each command takes the next descriptor slot of the pass.  Any other
+// shader (ShadowCaster, Gizmo, the UI, ...) and a command that lies beyond the buffer's host copy are SAILOR_HIP_ERR_UNSUPPORTED: indirect shadow casters are
+// out of scope.
+void HipGraphicsDriver::DrawIndexedIndirect(RHICommandListPtr cmd, RHIBufferPtr buffer, size_t offset, uint32_t drawCount, uint32_t stride)
+{
+    const std::string name = (cmd->m_boundMaterial && cmd->m_boundMaterial->m_shader) ? cmd->m_boundMaterial->m_shader->m_name : std::string();
+    const bool standard = name == "Shaders/Standard.shader" || name == "Shaders/Standard_glTF.shader", depthOnly = name == "Shaders/DepthOnly.shader";
+    if (!standard && !depthOnly) {
+        cmd->m_hip.m_commands.push_back([]() { return (int)SAILOR_HIP_ERR_UNSUPPORTED; });
+        return;
+    }
+    RHITexturePtr color = cmd->m_colorAttachments.empty() ? RHITexturePtr() : cmd->m_colorAttachments[0], depth = cmd->m_depthAttachment;
+    RHIBufferPtr vb = cmd->m_vertexBuffer, ib = cmd->m_indexBuffer;
+    TVector<RHIShaderBindingSetPtr> bindings = cmd->m_boundBindings;
+    const bool clearDepth = cmd->m_bClearDepth;
+    const uint32_t flags = (cmd->m_boundMaterial->m_bDoubleSided ? 0u : SAILOR_SURFACE_CULL_BACK) |
+                           (standard && cmd->m_boundMaterial->m_shader->HasDefine("ALPHA_CUTOUT") ? SAILOR_SURFACE_ALPHA_CUTOUT : 0u) |
+                           (name == "Shaders/Standard_glTF.shader" ? SAILOR_SURFACE_GLTF : 0u);
+    for (uint32_t i = 0; i < drawCount; i++) {
+        const size_t at = offset + (size_t)i * stride;
+        if (!buffer || !buffer->m_bIndirect || at > buffer->m_hostCopy.size() || buffer->m_hostCopy.size() - at < sizeof(SailorDrawIndexedIndirectData)) {
+            cmd->m_hip.m_commands.push_back([]() { return (int)SAILOR_HIP_ERR_UNSUPPORTED; }); // no host copy of this command
+            continue;
+        }
+        SailorDrawIndexedIndirectData host; // the command as the host wrote it, at record time
+        memcpy(&host, buffer->m_hostCopy.data() + at, sizeof host);
+        const uint32_t drawIndex = cmd->m_surfaceDraws++;
+        if (flags & SAILOR_SURFACE_ALPHA_CUTOUT) cmd->m_surfaceCutout = true;
+        if (flags & SAILOR_SURFACE_GLTF) cmd->m_surfaceGltf = true;
+        cmd->m_hip.m_commands.push_back([this, bindings, color, depth, vb, ib, drawIndex, clearDepth, host, buffer, at, flags]() {
+            return RecordSurfaceDrawIndirect(bindings, color, depth, vb, ib, drawIndex == 0, clearDepth, drawIndex, host, buffer, at, flags);
+        });
+    }
+}
+
+int HipGraphicsDriver::RecordSurfaceDrawIndirect(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& color, const RHITexturePtr& depth,
+                                                 const RHIBufferPtr& vertices, const RHIBufferPtr& indices, bool first, bool clearDepth, uint32_t drawIndex,
+                                                 const SailorDrawIndexedIndirectData& host, const RHIBufferPtr& command, size_t commandOffset, uint32_t flags)
+{
+    if (first) m_surfaceBegun = false;
+    SailorUboFrameData frame;
+    RHIBufferPtr instances = scene_buffer(bindings, "data");
+    const RHITexturePtr& extentOf = color ? color : depth; // a depth-only pass has the depth attachment's extent
+    if (bindings.empty() || !host_copy_of(bindings[0], "frameData", frame) || !extentOf || !extentOf->m_buffer || !vertices || !indices || !instances || !command)
+        return SAILOR_HIP_ERR_INVALID_ARGUMENT; // a missing binding
+    if (m_worldSize > 1) return SAILOR_HIP_ERR_UNSUPPORTED; // (the pass runs on whole frames here, as the direct route)
+    const int W = extentOf->GetExtent().x, H = extentOf->GetExtent().y;
+    if (W != frame.viewportSize[0] || H != frame.viewportSize[1] || (color && color->m_format != EFormat::R32G32B32A32_SFLOAT)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (depth && (depth->GetExtent().x != W || depth->GetExtent().y != H || depth->m_format != EFormat::R32_SFLOAT || !depth->m_buffer)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if ((size_t)host.firstIndex + host.indexCount > indices->m_size / 4 || host.vertexOffset < 0 ||
+        (size_t)host.vertexOffset * sizeof(SailorVertexP3N3T3B3UV2C4) > vertices->m_size || commandOffset % 4 != 0 ||
+        commandOffset + sizeof(SailorDrawIndexedIndirectData) > command->m_size)
+        return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    SailorBand band;
+    sailor_hip_band_whole_frame(W, H, &band);
+    const size_t bytes = sailor_hip_surface_workspace_bytes(W, H, &band, SURFACE_MAX_DRAWS);
+    if (first) {
+        if (!m_surfaceWorkspace || m_surfaceWorkspace->m_size != bytes) m_surfaceWorkspace = CreateBuffer(bytes);
+        if (!m_surfaceWorkspace) return SAILOR_HIP_ERR_OUT_OF_MEMORY;
+        // the keys start from the depth attachment, or from cleared keys when the pass clears depth (DepthPrepassNode's `ClearDepth`)
+        const float* start = (depth && !clearDepth) ? (const float*)depth->m_buffer->m_hip.m_devicePtr : nullptr;
+        const int st = sailor_hip_surface_begin(m_ctx, start, W, H, &band, m_surfaceWorkspace->m_hip.m_devicePtr, bytes);
+        if (st != SAILOR_HIP_OK) return st;
+        m_surfacePrimBase = 0;
+        m_surfaceBegun = true;
+    }
+    if (!m_surfaceBegun || !m_surfaceWorkspace || m_surfaceWorkspace->m_size != bytes || m_surfacePrimBase > 0xFFFFFFFFull) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    SailorSurfaceDraw d {};
+    d.dVertices = (const SailorVertexP3N3T3B3UV2C4*)vertices->m_hip.m_devicePtr + host.vertexOffset;
+    d.dIndices = (const uint32_t*)indices->m_hip.m_devicePtr + host.firstIndex;
+    d.numTriangles = host.indexCount / 3; d.numDrawn = host.instanceCount; // the capacity: the un-culled count the host wrote
+    d.primBase = (uint32_t)m_surfacePrimBase;
+    d.flags = flags;
+    RHIBufferPtr materials = scene_buffer(bindings, "material"), textures = scene_buffer(bindings, "textureSamplers");
+    if ((flags & SAILOR_SURFACE_ALPHA_CUTOUT) && (!materials || !textures)) { m_surfaceBegun = false; return SAILOR_HIP_ERR_INVALID_ARGUMENT; }
+    const int st = sailor_hip_surface_draw_indirect(m_ctx, &frame, &d, (const SailorDrawIndexedIndirectData*)((const uint8_t*)command->m_hip.m_devicePtr + commandOffset),
+                                                    (const SailorPerInstanceData*)instances->m_hip.m_devicePtr, (uint32_t)(instances->m_size / sizeof(SailorPerInstanceData)),
+                                                    materials ? (const SailorMaterialData*)materials->m_hip.m_devicePtr : nullptr,
+                                                    materials ? (uint32_t)(materials->m_size / sizeof(SailorMaterialData)) : 0u,
+                                                    textures ? (const SailorTextureDesc*)textures->m_hip.m_devicePtr : nullptr,
+                                                    textures ? (uint32_t)(textures->m_size / sizeof(SailorTextureDesc)) : 0u, drawIndex, W, H, &band,
+                                                    m_surfaceWorkspace->m_hip.m_devicePtr, bytes);
+    if (st != SAILOR_HIP_OK) { m_surfaceBegun = false; return st; }
+    uint64_t prims = 0;
+    sailor_hip_surface_draw_prims(d.numTriangles, d.numDrawn, &prims); // the next draw's primBase advances by the capacity
+    m_surfacePrimBase += prims;
+    return SAILOR_HIP_OK;
+}
+
+int HipGraphicsDriver::RecordSurfaceEndDepthOnly(const RHITexturePtr& depth)
+{
+    if (!m_surfaceBegun) return SAILOR_HIP_ERR_INVALID_ARGUMENT; // a draw of the pass was refused: nothing to store
+    m_surfaceBegun = false;
+    if (!depth || !depth->m_buffer || depth->m_format != EFormat::R32_SFLOAT) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    const int W = depth->GetExtent().x, H = depth->GetExtent().y;
+    SailorBand band;
+    sailor_hip_band_whole_frame(W, H, &band);
+    BeforeBufferWrite(depth->m_buffer->m_hip.m_devicePtr);
+    return sailor_hip_surface_store_depth(m_ctx, m_surfaceWorkspace->m_hip.m_devicePtr, m_surfaceWorkspace->m_size, (float*)depth->m_buffer->m_hip.m_devicePtr, W, H, &band);
 }
 
 int HipGraphicsDriver::RecordLinearizeDepth(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& target)

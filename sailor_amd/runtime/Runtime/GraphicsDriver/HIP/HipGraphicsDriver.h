@@ -48,6 +48,10 @@
 //   "Shaders/Standard_glTF.shader", with or without { "ALPHA_CUTOUT" }, drawn with DrawIndexed (a batch of an imported model) -> sailor_hip_surface_draw_gltf; a pass that
 //       held one ends with sailor_hip_surface_resolve_gltf (aoIn = `g_aoSampler` of the lights set if bound) -> the shade, reading the driver's aoOut as its ao ->
 //       sailor_hip_surface_composite_gltf.  A pass without one records exactly the launches above.
+//   the same three, and "Shaders/DepthOnly.shader", drawn with DrawIndexedIndirect (DepthPrepassNode; RenderSceneNode under `GPUCulling: true`) ->
+//       sailor_hip_surface_draw_indirect per command: the host's copy of the command from the indirect buffer (CreateIndirectBuffer keeps the bytes of its last
+//       UpdateBuffer), instanceCount and firstInstance read on the device.  A pass WITHOUT a colour attachment begins from its depth attachment (or from cleared
+//       keys) and ends with sailor_hip_surface_store_depth alone.  Any other shader under DrawIndexedIndirect: SAILOR_HIP_ERR_UNSUPPORTED.
 //   "Shaders/Gizmo.shader" of a LineList material drawn with DrawIndexed (DebugContext::DrawDebugMesh inside DebugDrawNode's pass) -> sailor_hip_surface_begin from
 //       the pass' depth attachment, sailor_hip_debug_lines_draw, sailor_hip_debug_lines_resolve into the colour and the depth attachment (push constant viewProjection,
 //       VertexP3C4 vertices, 32-bit indices)
@@ -73,6 +77,10 @@ public:
     int GetStatus() const { return m_status; }
     SailorHipContext* GetContext() const { return m_ctx; }
     int GetLastDispatchStatus() const { return m_lastDispatchStatus; }
+    // The debug regions in the order SubmitCommandList EXECUTED their BeginDebugRegion commands since the last ClearExecutedRegions: the order in which the
+    // regions' work went onto the stream.  For tests: the mesh cull's kernels are not in the context's launch log, their "GPU Culling" region is here.
+    const TVector<std::string>& GetExecutedRegions() const { return m_executedRegions; }
+    void ClearExecutedRegions() { m_executedRegions.clear(); }
     // the prepared views of a `light` SSBO: created with it, derived for every slot on (re-)creation (HipGraphicsDriver.cpp)
     bool EnsurePreparedLights(RHI::RHIShaderBindingPtr binding, bool zeroRecords);
 
@@ -90,6 +98,7 @@ public:
     void WaitIdle() override;
     RHI::RHICommandListPtr CreateCommandList(bool bIsSecondary = false) override;
     RHI::RHIBufferPtr CreateBuffer(size_t size) override;
+    RHI::RHIBufferPtr CreateIndirectBuffer(size_t size) override;
     RHI::RHIShaderPtr CreateShader(const std::string& assetPath, const TVector<std::string>& defines = {}) override;
     RHI::RHITexturePtr CreateTexture(const void* pData, size_t size, RHI::ivec2 extent, RHI::EFormat format) override;
     RHI::RHITexturePtr CreateRenderTarget(RHI::ivec2 extent, uint32_t mipLevels, RHI::EFormat format) override;
@@ -139,7 +148,8 @@ public:
     void SetMaterialParameter(RHI::RHICommandListPtr cmd, RHI::RHIShaderBindingSetPtr bindings, const std::string& binding, const std::string& variable,
                               const void* value, size_t size) override;
     void UpdateBuffer(RHI::RHICommandListPtr cmd, RHI::RHIBufferPtr buffer, const void* data, size_t size, size_t offset = 0) override;
-    void BeginRenderPass(RHI::RHICommandListPtr cmd, const TVector<RHI::RHITexturePtr>& colorAttachments, RHI::RHITexturePtr depthStencilAttachment) override;
+    void BeginRenderPass(RHI::RHICommandListPtr cmd, const TVector<RHI::RHITexturePtr>& colorAttachments, RHI::RHITexturePtr depthStencilAttachment,
+                         bool bClearDepthStencil = false) override;
     void BindVertexBuffer(RHI::RHICommandListPtr cmd, RHI::RHIBufferPtr vertexBuffer, uint32_t offset) override;
     void BindIndexBuffer(RHI::RHICommandListPtr cmd, RHI::RHIBufferPtr indexBuffer, uint32_t offset, bool bUint16InsteadOfUint32 = false) override;
     void PushConstants(RHI::RHICommandListPtr cmd, RHI::RHIMaterialPtr material, size_t size, const void* ptr) override;
@@ -150,6 +160,8 @@ public:
     void BindShaderBindings(RHI::RHICommandListPtr cmd, RHI::RHIMaterialPtr material, const TVector<RHI::RHIShaderBindingSetPtr>& bindings) override;
     void DrawIndexed(RHI::RHICommandListPtr cmd, uint32_t indexCount, uint32_t instanceCount, uint32_t firstIndex, uint32_t vertexOffset,
                      uint32_t firstInstance) override;
+    void DrawIndexedIndirect(RHI::RHICommandListPtr cmd, RHI::RHIBufferPtr buffer, size_t offset, uint32_t drawCount, uint32_t stride) override;
+    void CopyBuffer(RHI::RHICommandListPtr cmd, RHI::RHIBufferPtr src, RHI::RHIBufferPtr dst, size_t size, size_t srcOffset = 0, size_t dstOffset = 0) override;
     void Dispatch(RHI::RHICommandListPtr cmd, RHI::RHIShaderPtr computeShader, uint32_t groupSizeX, uint32_t groupSizeY, uint32_t groupSizeZ,
                   const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const void* pPushConstantsData = nullptr,
                   uint32_t sizePushConstantsData = 0) override;
@@ -160,6 +172,12 @@ private:
     int RecordSurfaceDraw(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& color, const RHI::RHITexturePtr& depth,
                           const RHI::RHIBufferPtr& vertices, const RHI::RHIBufferPtr& indices, bool first, uint32_t drawIndex, uint32_t indexCount,
                           uint32_t instanceCount, uint32_t firstIndex, uint32_t vertexOffset, uint32_t firstInstance, uint32_t flags);
+    // one command of DrawIndexedIndirect in the surface pass: `host` is the command as the indirect buffer's host copy holds it, `command` the buffer and the
+    // byte offset the kernel reads instanceCount and firstInstance from.  A pass without a colour attachment is a depth-only pass (DepthPrepassNode)
+    int RecordSurfaceDrawIndirect(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& color, const RHI::RHITexturePtr& depth,
+                                  const RHI::RHIBufferPtr& vertices, const RHI::RHIBufferPtr& indices, bool first, bool clearDepth, uint32_t drawIndex,
+                                  const SailorDrawIndexedIndirectData& host, const RHI::RHIBufferPtr& command, size_t commandOffset, uint32_t flags);
+    int RecordSurfaceEndDepthOnly(const RHI::RHITexturePtr& depth);
     int RecordDebugLines(const RHI::RHITexturePtr& color, const RHI::RHITexturePtr& depth, const RHI::RHIBufferPtr& vertices, const RHI::RHIBufferPtr& indices,
                          const TVector<uint8_t>& pushConstants, uint32_t indexCount, uint32_t firstIndex, uint32_t vertexOffset);
     int RecordUi(const RHI::RHITexturePtr& color, const RHI::RHIBufferPtr& vertices, const RHI::RHIBufferPtr& indices, bool bIndexUint16,
@@ -194,6 +212,7 @@ private:
     std::shared_ptr<SailorHipContext> m_ctxOwner;   // destroyed with the last buffer that still refers to it
     int m_status = 0;
     int m_lastDispatchStatus = 0;
+    TVector<std::string> m_executedRegions;
     std::set<std::string> m_enabledShaders; // EnableShader
     // SkyNode's m_pCloudsTexture while the last thing recorded into it was the cloud march: the SUN draw that samples it (one material for the clear and the
     // march, SkyNode.cpp:611-642) goes through sailor_hip_sky_sun_clouds then, through sailor_hip_sky_sun otherwise.  Reset by every write (BeforeBufferWrite)

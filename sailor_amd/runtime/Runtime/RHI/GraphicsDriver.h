@@ -13,6 +13,7 @@ public:
     virtual void WaitIdle() = 0;                                                                           // :83
     virtual RHICommandListPtr CreateCommandList(bool bIsSecondary = false) = 0;                            // :88
     virtual RHIBufferPtr CreateBuffer(size_t size) = 0;                                                    // :89
+    virtual RHIBufferPtr CreateIndirectBuffer(size_t size) = 0;                                            // :91 (here: also keeps the bytes of its last UpdateBuffer on the host)
     virtual RHIShaderPtr CreateShader(const std::string& assetPath, const TVector<std::string>& defines = {}) = 0; // :97 (SPIR-V there; here the asset path + permutation)
     virtual RHITexturePtr CreateTexture(const void* pData, size_t size, ivec2 extent, EFormat format) = 0; // :98-108
     virtual RHITexturePtr CreateRenderTarget(ivec2 extent, uint32_t mipLevels, EFormat format) = 0;        // :110-117 (filtration, clamping, usage dropped)
@@ -52,7 +53,8 @@ public:
     virtual void SetMaterialParameter(RHICommandListPtr cmd, RHIShaderBindingSetPtr bindings, const std::string& binding, const std::string& variable,
                                       const void* value, size_t size) = 0;                                                                              // :305
     virtual void UpdateBuffer(RHICommandListPtr cmd, RHIBufferPtr buffer, const void* data, size_t size, size_t offset = 0) = 0;                       // :304
-    virtual void BeginRenderPass(RHICommandListPtr cmd, const TVector<RHITexturePtr>& colorAttachments, RHITexturePtr depthStencilAttachment) = 0; // :246-255 (area, clear values dropped)
+    virtual void BeginRenderPass(RHICommandListPtr cmd, const TVector<RHITexturePtr>& colorAttachments, RHITexturePtr depthStencilAttachment,
+                                 bool bClearDepthStencil = false) = 0; // :246-255 (area and clear values dropped; the depth clear is to 0, reversed Z's far plane)
     virtual void BindVertexBuffer(RHICommandListPtr cmd, RHIBufferPtr vertexBuffer, uint32_t offset) = 0;                                           // :316
     virtual void BindIndexBuffer(RHICommandListPtr cmd, RHIBufferPtr indexBuffer, uint32_t offset, bool bUint16InsteadOfUint32 = false) = 0;          // :317
     virtual void PushConstants(RHICommandListPtr cmd, RHIMaterialPtr material, size_t size, const void* ptr) = 0;                                      // :324
@@ -63,6 +65,10 @@ public:
     virtual void BindShaderBindings(RHICommandListPtr cmd, RHIMaterialPtr material, const TVector<RHIShaderBindingSetPtr>& bindings) = 0;           // :282
     virtual void DrawIndexed(RHICommandListPtr cmd, uint32_t indexCount, uint32_t instanceCount, uint32_t firstIndex, uint32_t vertexOffset,
                              uint32_t firstInstance) = 0;                                                                                           // :285
+    virtual void DrawIndexedIndirect(RHICommandListPtr cmd, RHIBufferPtr buffer, size_t offset, uint32_t drawCount, uint32_t stride) = 0;                // :323
+    // the recorded form of IGraphicsDriver::CopyBuffer_Immediate (:192).  Not in the reference's command interface: its nodes refill their per-instance SSBO
+    // from host arrays (UpdateShaderBinding); the mirror's scene data is device-resident, so the refill is a device copy
+    virtual void CopyBuffer(RHICommandListPtr cmd, RHIBufferPtr src, RHIBufferPtr dst, size_t size, size_t srcOffset = 0, size_t dstOffset = 0) = 0;
     virtual void Dispatch(RHICommandListPtr cmd, RHIShaderPtr computeShader, uint32_t groupSizeX, uint32_t groupSizeY, uint32_t groupSizeZ,
                           const TVector<RHIShaderBindingSetPtr>& bindings, const void* pPushConstantsData = nullptr,
                           uint32_t sizePushConstantsData = 0) = 0;                                                                                       // :310-314

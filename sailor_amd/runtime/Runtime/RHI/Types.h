@@ -67,6 +67,10 @@ class RHIBuffer : public RHIResource {
 public:
     struct { void* m_devicePtr = nullptr; bool m_bOwned = false; } m_hip;
     size_t m_size = 0;
+    // an indirect buffer (IGraphicsDriver::CreateIndirectBuffer) keeps the bytes of its last UpdateBuffer, as UBO bindings keep m_hostCopy: DrawIndexedIndirect
+    // takes indexCount, firstIndex, vertexOffset and the un-culled instanceCount from them ("the command as the host wrote it", include/sailor_hip.h)
+    bool m_bIndirect = false;
+    TVector<uint8_t> m_hostCopy;
     ~RHIBuffer() override;
     // The context the allocation belongs to, shared with the driver that made it: a buffer (or a texture / binding holding one) may outlive
     // the driver object, and the context is destroyed by whoever lets go of it last.
@@ -191,6 +195,7 @@ public:
     TVector<uint8_t> m_pushConstants;                          // PushConstants(material, size, ptr)
     uint32_t m_casterDraws = 0;                                // depth-only draws recorded in the current pass (the first one clears)
     uint32_t m_surfaceDraws = 0;                               // Standard.shader draws recorded in the current pass (the first one begins the surface pass)
+    bool m_bClearDepth = false;                                // BeginRenderPass(..., bClearDepthStencil): a surface pass then starts from cleared keys
     bool m_surfaceCutout = false;                              // ... one of them with ALPHA_CUTOUT: the pass ends with the depth write (sailor_hip_surface_store_depth)
     bool m_surfaceGltf = false;                                // ... one of them with Standard_glTF.shader: the pass ends with the glTF resolve and composite
     TRefPtr<class RHIMaterial> m_boundMaterial;

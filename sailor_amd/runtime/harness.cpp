@@ -4,6 +4,7 @@
 #include <string>
 #include "Runtime/ECS/LightingECS.h"
 #include "Runtime/FrameGraph/LightCullingNode.h"
+#include "Runtime/FrameGraph/DepthPrepassNode.h"
 #include "Runtime/FrameGraph/RHIFrameGraph.h"
 #include "Runtime/GraphicsDriver/HIP/HipGraphicsDriver.h"
 #include "Runtime/RHI/Renderer.h"
@@ -687,6 +688,75 @@ RT_API int sailor_rt_gpu_culling(SailorRuntime* rt, void* instancesDevicePtr, ui
     return hip->GetLastDispatchStatus();
 }
 
+// The indirect buffer of node `nodeIndex` of the graph (a DepthPrepass node, or a RenderScene node under `GPUCulling: true`) after its last frame, downloaded
+// (this waits for the device): up to maxCommands records of 5 words into `out`.  Returns the number of commands the node wrote, -1 for any other node and
+// before the node's first frame.
+static void* node_indirect_buffer(SailorRuntime* rt, int nodeIndex, int* outCommands)
+{
+    if (!rt || nodeIndex < 0 || (size_t)nodeIndex >= rt->graph.GetGraph().size()) return nullptr;
+    const auto& node = rt->graph.GetGraph()[(size_t)nodeIndex];
+    const SceneIndirectDraws* draws = nullptr;
+    if (auto prepass = node.DynamicCast<DepthPrepassNode>()) draws = &prepass->GetIndirectDraws();
+    else if (auto scene = node.DynamicCast<RenderSceneNode>()) draws = &scene->GetIndirectDraws();
+    if (!draws || !draws->GetIndirectBuffer()) return nullptr;
+    if (outCommands) *outCommands = (int)draws->GetNumCommands();
+    return draws->GetIndirectBuffer()->m_hip.m_devicePtr;
+}
+RT_API int sailor_rt_node_indirect_commands(SailorRuntime* rt, int nodeIndex, uint32_t* out, int maxCommands)
+{
+    int count = 0;
+    void* device = node_indirect_buffer(rt, nodeIndex, &count);
+    if (!device) return -1;
+    auto* hip = static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver());
+    hip->WaitIdle();
+    const int n = count < maxCommands ? count : maxCommands;
+    if (out && n > 0 && sailor_hip_buffer_download(hip->GetContext(), out, device, 0, (size_t)n * sizeof(SailorDrawIndexedIndirectData)) != SAILOR_HIP_OK) return -1;
+    return count;
+}
+
+// The debug regions of the last sailor_rt_process_frame in the order the driver EXECUTED their BeginDebugRegion commands while it submitted the frame's lists
+// (HipGraphicsDriver::GetExecutedRegions), joined by ';'.  Returns their number.
+RT_API int sailor_rt_last_frame_regions(SailorRuntime* rt, char* out, int outSize)
+{
+    if (!rt) return -1;
+    auto* hip = static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver());
+    std::string s;
+    for (const auto& r : hip->GetExecutedRegions()) s += (s.empty() ? "" : ";") + r;
+    if (out && outSize > 0) snprintf(out, (size_t)outSize, "%s", s.c_str());
+    return (int)hip->GetExecutedRegions().size();
+}
+
+// One depth-only pass of one DrawIndexedIndirect over batch 0 of the scene with a material of `shaderPath`, recorded and submitted at once: what a node would
+// record with that material.  Returns the driver's status afterwards (it stays the status sailor_rt_process_frame returns): 0 for a routed shader,
+// SAILOR_HIP_ERR_UNSUPPORTED for any other.
+RT_API int sailor_rt_draw_indexed_indirect(SailorRuntime* rt, const char* shaderPath, void* depthDevicePtr, int width, int height)
+{
+    if (!rt || !shaderPath || !depthDevicePtr || rt->snapshot.m_batches.empty()) return -1;
+    auto* hip = static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver());
+    auto driver = Renderer::GetDriver();
+    auto commands = Renderer::GetDriverCommands();
+    auto cmd = driver->CreateCommandList();
+    rt->graph.FillFrameData(cmd, rt->snapshot, rt->snapshot.m_deltaTime, rt->snapshot.m_currentTime);
+    const RHISceneBatch& b = rt->snapshot.m_batches[0];
+    SailorDrawIndexedIndirectData data {};
+    data.indexCount = b.m_indexCount; data.instanceCount = b.m_instanceCount; data.firstIndex = b.m_firstIndex; data.vertexOffset = (int32_t)b.m_vertexOffset;
+    data.firstInstance = b.m_firstInstance;
+    auto indirect = driver->CreateIndirectBuffer(sizeof data);
+    if (!indirect) return -1;
+    commands->UpdateBuffer(cmd, indirect, &data, sizeof data, 0);
+    auto material = driver->CreateMaterial(driver->CreateShader(shaderPath));
+    commands->BeginRenderPass(cmd, TVector<RHITexturePtr> {}, hip->WrapTexture(depthDevicePtr, { width, height }, EFormat::R32_SFLOAT), true);
+    commands->BindMaterial(cmd, material);
+    commands->BindShaderBindings(cmd, material, { rt->snapshot.m_frameBindings, rt->snapshot.m_sceneBindings });
+    commands->BindVertexBuffer(cmd, b.m_vertexBuffer, 0);
+    commands->BindIndexBuffer(cmd, b.m_indexBuffer, 0);
+    commands->DrawIndexedIndirect(cmd, indirect, 0, 1, sizeof data);
+    commands->EndRenderPass(cmd);
+    driver->SubmitCommandList(cmd);
+    driver->WaitIdle(); // (the indirect buffer is released with this scope)
+    return hip->GetLastDispatchStatus();
+}
+
 // DefaultRenderer.renderer's DepthHighZ target (R32_SFLOAT, mips, reduction Min) + one run of the DepthHighZ node over a wrapped depth image.
 // The pyramid stays bound for the following sailor_rt_gpu_culling calls; levels <= 0 drops it again.
 RT_API int sailor_rt_build_depth_highz(SailorRuntime* rt, void* depthDevicePtr, int depthWidth, int depthHeight, int width, int height, int levels, void** outPyramid)
@@ -931,6 +1001,7 @@ RT_API int sailor_rt_set_ui_draw_data(SailorRuntime* rt, const float* displayPos
 
 RT_API int sailor_rt_process_frame(SailorRuntime* rt)
 {
+    static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver())->ClearExecutedRegions();
     rt->graph.Process(rt->snapshot);
     rt->frames++;
     return static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver())->GetLastDispatchStatus();

@@ -75,6 +75,9 @@ def load() -> C.CDLL:
         rt.sailor_rt_set_scene_tags.argtypes = [P, C.c_char_p, P, C.c_int]
         rt.sailor_rt_set_scene_shaders.argtypes = [P, P, C.c_int]
         rt.sailor_rt_process_frame.argtypes = [P]
+        rt.sailor_rt_node_indirect_commands.argtypes = [P, C.c_int, P, C.c_int]
+        rt.sailor_rt_draw_indexed_indirect.argtypes = [P, C.c_char_p, P, C.c_int, C.c_int]
+        rt.sailor_rt_last_frame_regions.argtypes = [P, C.c_char_p, C.c_int]
         for shape in ("line", "aabb", "arrow"):
             getattr(rt, f"sailor_rt_debug_draw_{shape}").argtypes = [P, P, P, P, C.c_float]
         rt.sailor_rt_debug_draw_frustum.argtypes = [P, P, P, C.c_float]
@@ -460,6 +463,25 @@ class Runtime:
         if n < 0:
             raise _lib.SailorHipError(-1, "sailor_rt_set_ui_draw_data")
         return n
+
+    def node_indirect_commands(self, node_index: int, max_commands: int = 64) -> np.ndarray:
+        """the indirect buffer of node `node_index` of the graph (a DepthPrepass node, a RenderScene node under `GPUCulling: true`) after its last frame,
+        downloaded: uint32 [commands, 5] = (indexCount, instanceCount, firstIndex, vertexOffset, firstInstance)"""
+        out = np.zeros((max_commands, 5), np.uint32)
+        n = self.rt.sailor_rt_node_indirect_commands(self.h, node_index, out.ctypes.data, max_commands)
+        if n < 0:
+            raise ValueError(f"node {node_index} owns no indirect buffer")
+        return out[:min(n, max_commands)]
+
+    def last_frame_regions(self):
+        """the debug regions of the last process_frame in the order the driver executed their BeginDebugRegion commands while it submitted the frame's lists"""
+        buf = C.create_string_buffer(1 << 14)
+        n = self.rt.sailor_rt_last_frame_regions(self.h, buf, len(buf))
+        return buf.value.decode().split(";") if n > 0 else []
+
+    def draw_indexed_indirect(self, shader_path: str, depth) -> int:
+        """one depth-only pass of one DrawIndexedIndirect over the scene's batch 0 with a material of that shader, submitted at once -> the driver's status"""
+        return self.rt.sailor_rt_draw_indexed_indirect(self.h, shader_path.encode(), depth.data_ptr(), depth.shape[1], depth.shape[0])
 
     def process_frame(self) -> int:
         return self.rt.sailor_rt_process_frame(self.h)
