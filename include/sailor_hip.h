@@ -234,6 +234,10 @@ SAILOR_HIP_API int sailor_hip_buffer_download(SailorHipContext* ctx, void* dstHo
 /* device-to-device copy on the context's stream (the BlitImage of equally sized images, e.g. EnvironmentNode.cpp:200-203) */
 SAILOR_HIP_API int sailor_hip_buffer_copy(SailorHipContext* ctx, void* dstDevice, size_t dstOffset, const void* srcDevice, size_t srcOffset, size_t bytes);
 SAILOR_HIP_API int sailor_hip_buffer_fill_u32(SailorHipContext* ctx, void* dstDevice, size_t dstOffset, uint32_t value, size_t count);
+/* `count` records of `wordsPerRecord` (1 .. 4) words each, every record = value[0 .. wordsPerRecord): IGraphicsDriverCommands::ClearImage (:294) of a target
+ * with more than one channel to a colour whose channels differ (ClearNode.cpp:104-106) */
+SAILOR_HIP_API int sailor_hip_buffer_fill_pattern(SailorHipContext* ctx, void* dstDevice, size_t dstOffset, const uint32_t* value, uint32_t wordsPerRecord,
+                                                  size_t count);
 
 /* ---- bands ---------------------------------------------------------------------------------------------- */
 SAILOR_HIP_API int sailor_hip_num_tiles(int32_t width, int32_t height, int32_t* outTilesX, int32_t* outTilesY); /* LightCullingNode.cpp:56-57 */
@@ -613,6 +617,33 @@ SAILOR_HIP_API int sailor_hip_csm_caster_masks(SailorHipContext* ctx, uint32_t n
  * ceil(numEntities / 64) words, the same for every cascade.  Records only. */
 SAILOR_HIP_API int sailor_hip_csm_caster_masks_traced(SailorHipContext* ctx, uint32_t numEntities, const SailorAABB* dWorldAabb, const float* cascadePlanes,
                                                       uint32_t numCascades, uint64_t* dMasks, const SailorSceneTrace* trace);
+
+/* Replaces: the host loop that fills a shadow pass's per-instance SSBO, FrameGraph/ShadowPrepassNode.cpp:155-201 (a memcpy of every proxy's
+ * `gpuMatricesData` run into the `data` binding: ShadowPrepassNode::PerInstanceData { mat4 model; }, 64 bytes) -- from a cascade's bitmask, on the device.
+ * One job: for every set bit i of dMask in [begin, end), in ASCENDING i, out[j] = dInstances[i].model; *dCount = the number of set bits in the range.
+ *   dMask    : device, bit i = instance i of the scene's SSBO, LSB first (the layout of sailor_hip_csm_caster_masks / sailor_host_csm_plan_passes);
+ *              only words that hold bits of [begin, end) are read, bits at or past `end` are ignored
+ *   dOut     : device, capacity x 16 floats, 16-byte aligned; with capacity < count only the first `capacity` matrices are written, and nothing behind them
+ *   dCount   : device, one word, always the full count
+ * The order inside a batch is the canonical one (by index); the reference's is its octree's walk order, and the rasteriser's result does not depend on it.
+ * The output is a pure function of the inputs.  Records on the context's stream only: no upload, no read-back, no synchronisation (the jobs travel in the
+ * kernels' arguments).  dWorkspace: device scratch, 4-byte aligned, sailor_hip_shadow_gather_workspace_bytes(jobs, numJobs) bytes -- 4 per 1 024 bits of
+ * every job's range; it depends on the ranges only. */
+typedef struct SailorShadowGatherJob {
+    const uint64_t* dMask;
+    uint32_t begin, end;
+    float* dOut;
+    uint32_t capacity;
+    uint32_t _pad;
+    uint32_t* dCount;
+} SailorShadowGatherJob;
+SAILOR_HIP_API size_t sailor_hip_shadow_gather_workspace_bytes(const SailorShadowGatherJob* jobs, uint32_t numJobs);
+/* numJobs jobs (passes x batches) over one instance buffer in one call: two launches per 32 jobs.  The jobs' outputs must not overlap. */
+SAILOR_HIP_API int sailor_hip_shadow_gather_instances_batched(SailorHipContext* ctx, const SailorPerInstanceData* dInstances, uint32_t numInstances,
+                                                              const SailorShadowGatherJob* jobs, uint32_t numJobs, void* dWorkspace, size_t workspaceBytes);
+SAILOR_HIP_API int sailor_hip_shadow_gather_instances(SailorHipContext* ctx, const SailorPerInstanceData* dInstances, uint32_t numInstances,
+                                                      const uint64_t* dMask, uint32_t begin, uint32_t end, float* dOut, uint32_t capacity, uint32_t* dCount,
+                                                      void* dWorkspace, size_t workspaceBytes);
 
 /* Replaces: FrustumCulling of Content/Shaders/ComputeMeshCulling.shader:96-110 (+ CreateViewFrustum, Math.glsl:185-222)
  * for the Dispatch at RHI/Batch.hpp:188; writes PerInstanceData::isCulled in place for the instances
@@ -1210,6 +1241,10 @@ typedef struct SailorVertexP3N3T3B3UV2C4 {
     float bitangent[3];
     float color[4];
 } SailorVertexP3N3T3B3UV2C4;
+/* The vertex input of ShadowCaster.shader:46-59 is inPosition alone: dPositions[v] = dVertices[v].position, numVertices packed vec3 -- what
+ * sailor_hip_raster_depth takes as dPositions -- for the shadow passes of meshes that live in a scene's interleaved vertex buffer.  Records only. */
+SAILOR_HIP_API int sailor_hip_shadow_extract_positions(SailorHipContext* ctx, const SailorVertexP3N3T3B3UV2C4* dVertices, uint32_t numVertices,
+                                                       float* dPositions);
 
 /* Standard.shader:164-178 MaterialData, std430: 80 bytes */
 typedef struct SailorMaterialData {

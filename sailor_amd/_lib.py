@@ -92,6 +92,11 @@ class SceneTrace(C.Structure):  # include/sailor_hip.h SailorSceneTrace
     _fields_ = [("mode", C.c_uint32), ("rootSize", C.c_uint32), ("dInserted", C.c_void_p)]
 
 
+class ShadowGatherJob(C.Structure):  # include/sailor_hip.h SailorShadowGatherJob
+    _fields_ = [("dMask", C.c_void_p), ("begin", C.c_uint32), ("end", C.c_uint32), ("dOut", C.c_void_p), ("capacity", C.c_uint32), ("_pad", C.c_uint32),
+                ("dCount", C.c_void_p)]
+
+
 def trace_mode(name: str) -> int:
     """'flat' | 'octree' -> SAILOR_TRACE_*; anything else raises"""
     if name not in TRACE_MODES:
@@ -333,6 +338,11 @@ SIGNATURES = {
     "sailor_hip_shadow_resolve": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "sailor_hip_csm_caster_masks": (C.c_int, [_P, C.c_uint32, _P, C.POINTER(C.c_float), C.c_uint32, _P]),
     "sailor_hip_csm_caster_masks_traced": (C.c_int, [_P, C.c_uint32, _P, C.POINTER(C.c_float), C.c_uint32, _P, C.POINTER(SceneTrace)]),
+    "sailor_hip_shadow_gather_workspace_bytes": (C.c_size_t, [C.POINTER(ShadowGatherJob), C.c_uint32]),
+    "sailor_hip_shadow_gather_instances_batched": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(ShadowGatherJob), C.c_uint32, _P, C.c_size_t]),
+    "sailor_hip_shadow_gather_instances": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, C.c_size_t]),
+    "sailor_hip_buffer_fill_pattern": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_uint32), C.c_uint32, C.c_size_t]),
+    "sailor_hip_shadow_extract_positions": (C.c_int, [_P, _P, C.c_uint32, _P]),
     "sailor_hip_hiz_downscale": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32]),
     "sailor_hip_hiz_build": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32]),
     "sailor_hip_mesh_cull_flags": (C.c_int, [_P, C.POINTER(UboFrameData), _P, C.c_uint32, C.c_uint32, C.POINTER(HiZDesc)]),

@@ -5,7 +5,7 @@
 
 extern "C" {
 
-int sailor_hip_version(void) { return 1000 * 0 + 9; }
+int sailor_hip_version(void) { return 1000 * 0 + 10; }
 
 const char* sailor_hip_status_string(int status)
 {
@@ -185,6 +185,17 @@ __global__ void k_fill_u32(uint32_t* dst, uint32_t value, size_t count)
     for (; i < count; i += stride) dst[i] = value;
 }
 
+// word i of the stream = component (i mod wordsPerRecord) of the pattern (selects, no indexed private array)
+__global__ void k_fill_pattern(uint32_t* dst, uint4 pattern, uint32_t wordsPerRecord, size_t words)
+{
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (; i < words; i += stride) {
+        const uint32_t c = (uint32_t)(i % wordsPerRecord);
+        dst[i] = c == 0 ? pattern.x : (c == 1 ? pattern.y : (c == 2 ? pattern.z : pattern.w));
+    }
+}
+
 // sailor_hip_copy_probe: the box's yardstick -- a float4-per-lane streaming copy, the access pattern MI355X_MICROARCH.md's 6.29 TB/s figure was taken with
 __global__ __launch_bounds__(256) void k_copy_probe(const float4* __restrict__ src, float4* __restrict__ dst, size_t count4)
 {
@@ -237,6 +248,20 @@ int sailor_hip_buffer_fill_u32(SailorHipContext* ctx, void* dstDevice, size_t ds
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(k_fill_u32, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, (uint32_t*)((char*)dstDevice + dstOffset), value, count);
     SAILOR_CHECK_LAUNCH(ctx, "k_fill_u32");
+    return SAILOR_HIP_OK;
+}
+
+int sailor_hip_buffer_fill_pattern(SailorHipContext* ctx, void* dstDevice, size_t dstOffset, const uint32_t* value, uint32_t wordsPerRecord, size_t count)
+{
+    if (!ctx || !dstDevice || !value || (dstOffset & 3) || wordsPerRecord < 1 || wordsPerRecord > 4) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device)); // a host thread may drive several contexts
+    if (!count) return SAILOR_HIP_OK;
+    const size_t words = count * wordsPerRecord;
+    size_t blocks = (words + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    const uint4 pattern = make_uint4(value[0], value[wordsPerRecord > 1 ? 1 : 0], value[wordsPerRecord > 2 ? 2 : 0], value[wordsPerRecord > 3 ? 3 : 0]);
+    hipLaunchKernelGGL(k_fill_pattern, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, (uint32_t*)((char*)dstDevice + dstOffset), pattern, wordsPerRecord, words);
+    SAILOR_CHECK_LAUNCH(ctx, "k_fill_pattern");
     return SAILOR_HIP_OK;
 }
 

@@ -689,6 +689,59 @@ def csm_caster_masks(ctx: "HipContext", world_aabb: torch.Tensor, cascade_planes
     return out
 
 
+def shadow_extract_positions(ctx: "HipContext", vertices: torch.Tensor) -> torch.Tensor:
+    """sailor_hip_shadow_extract_positions: the 72-byte vertices of a scene (any contiguous tensor of 72 n bytes) -> float32 [n, 3] positions, what
+    raster_depth draws from"""
+    n = vertices.numel() * vertices.element_size() // 72
+    if not vertices.is_contiguous() or vertices.numel() * vertices.element_size() != 72 * n:
+        raise ValueError("vertices must be a contiguous tensor of whole 72-byte records")
+    out = torch.empty((n, 3), dtype=torch.float32, device=ctx.device)
+    _lib.check(ctx._lib.sailor_hip_shadow_extract_positions(ctx.handle, _ptr(vertices), n, _ptr(out)), "sailor_hip_shadow_extract_positions", ctx.handle)
+    return out
+
+
+def shadow_gather_instances_batched(ctx: "HipContext", instances: torch.Tensor, jobs, workspace: torch.Tensor | None = None) -> torch.Tensor | None:
+    """sailor_hip_shadow_gather_instances_batched: `instances` = the scene's 96-byte PerInstanceData records (any contiguous tensor of 96 n bytes);
+    jobs = [(mask int64 words, begin, end, out float32 [capacity, 16], count int32 [1]), ...] -- passes x batches in one call.  Per job, out[j] = the
+    model matrix of the j-th set bit of [begin, end), ascending; count = the set bits of the range, also where `out` is shorter.  Records only.
+    Returns the workspace it used (pass it back in to allocate nothing)."""
+    n = instances.numel() * instances.element_size() // 96
+    if not instances.is_contiguous() or instances.numel() * instances.element_size() != 96 * n:
+        raise ValueError("instances must be a contiguous tensor of whole 96-byte records")
+    arr = (_lib.ShadowGatherJob * max(len(jobs), 1))()
+    for k, (mask, begin, end, out, count, *cap) in enumerate(jobs):   # (a sixth entry: a capacity below the rows of `out`)
+        if not (mask.dtype == torch.int64 and mask.is_contiguous() and mask.numel() >= (end + 63) // 64):
+            raise ValueError(f"job {k}: mask must be a contiguous int64 tensor of at least {(end + 63) // 64} words")
+        if not (out.dtype == torch.float32 and out.is_contiguous() and out.numel() % 16 == 0 and count.dtype == torch.int32 and count.numel() >= 1):
+            raise ValueError(f"job {k}: out must be contiguous float32 [capacity, 16] and count int32 [1]")
+        if cap and not 0 <= cap[0] <= out.numel() // 16:
+            raise ValueError(f"job {k}: capacity {cap[0]} exceeds the {out.numel() // 16} matrices of out")
+        arr[k] = _lib.ShadowGatherJob(mask.data_ptr(), begin, end, out.data_ptr(), cap[0] if cap else out.numel() // 16, 0, count.data_ptr())
+    need = int(ctx._lib.sailor_hip_shadow_gather_workspace_bytes(arr, len(jobs)))
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=ctx.device)
+    _lib.check(ctx._lib.sailor_hip_shadow_gather_instances_batched(ctx.handle, _ptr(instances), n, arr, len(jobs), _ptr(workspace),
+                                                                   workspace.numel() * workspace.element_size()),
+               "sailor_hip_shadow_gather_instances_batched", ctx.handle)
+    return workspace
+
+
+def shadow_gather_instances(ctx: "HipContext", instances: torch.Tensor, mask: torch.Tensor, begin: int, end: int, capacity: int | None = None,
+                            workspace: torch.Tensor | None = None):
+    """One job of the above into fresh tensors: (models float32 [capacity, 16], count int32 [1]); capacity defaults to end - begin"""
+    cap = max(end - begin, 0) if capacity is None else capacity
+    out = torch.empty((cap, 16), dtype=torch.float32, device=ctx.device)
+    count = torch.empty(1, dtype=torch.int32, device=ctx.device)
+    job = _lib.ShadowGatherJob(mask.data_ptr(), begin, end, out.data_ptr(), cap, 0, count.data_ptr())
+    need = int(ctx._lib.sailor_hip_shadow_gather_workspace_bytes(C.byref(job), 1))
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=ctx.device)
+    _lib.check(ctx._lib.sailor_hip_shadow_gather_instances(ctx.handle, _ptr(instances), instances.numel() * instances.element_size() // 96, _ptr(mask), begin,
+                                                           end, _ptr(out), cap, _ptr(count), _ptr(workspace), workspace.numel() * workspace.element_size()),
+               "sailor_hip_shadow_gather_instances", ctx.handle)
+    return out, count
+
+
 def hiz_build(ctx: "HipContext", depth: torch.Tensor, width: int, height: int, levels: int) -> torch.Tensor:
     """DepthHighZNode's loop on the GPU: raw depth [H, W] float32 -> flat level-major min pyramid"""
     total = sum(max(width >> l, 1) * max(height >> l, 1) for l in range(levels))

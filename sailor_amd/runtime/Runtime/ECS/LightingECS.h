@@ -10,7 +10,7 @@
 namespace Sailor {
 
 enum class ELightType : uint32_t { Directional = 0, Point = 1, Spot = 2, Area = 3 };          // Engine/Types.h:31-37
-enum class EShadowType : uint32_t { None = 0, PCF = 1, EVSM = 2 };                            // RHI/SceneView.h:13-18
+using EShadowType = RHI::EShadowType;                                                         // RHI/SceneView.h:13-18
 enum class EMobilityType : uint8_t { Static = 0, Stationary = 1, Dynamic = 2 };               // Engine/Types.h:24-29
 
 struct LightData { // ECS/LightingECS.h:18-33 (+ the owner transform's position / forward vector)
@@ -27,6 +27,28 @@ struct LightData { // ECS/LightingECS.h:18-33 (+ the owner transform's position 
     size_t m_frameLastChange = 0;                             // ECS/ECS.h:36: the owner's frame this record was packed for
     size_t m_ownerFrameLastChange = 0;                        // GameObject::GetFrameLastChange(): the frame the owner's transform last changed
     EMobilityType m_ownerMobility = EMobilityType::Stationary; // Engine/GameObject.h:124
+    // the owner's transform as PrepareCSMPasses needs it (RHILightProxy::m_lightTransform, :227-228): m_worldPosition above, and its rotation (x, y, z, w)
+    float m_ownerRotation[4] = { 0.0f, 0.0f, 0.0f, 1.0f };
+};
+
+// What RHISceneView::TraceScene and the proxies give LightingECS::PrepareCSMPasses, flat over the scene's instances (`data` of the view's scene bindings):
+// the world boxes on the device (what sailor_hip_ecs_sweep writes), m_bCastShadows as a bitmask (empty = every instance casts), the frame each instance last
+// changed (RHISceneViewProxy::m_frame), how the overlap sets are traced, and the cascade maps' resolutions (ECS/LightingECS.h:67 unless overridden).
+struct CsmCasterData {
+    RHI::RHIBufferPtr m_worldAabb;
+    uint32_t m_numInstances = 0;
+    TVector<uint64_t> m_castShadows;
+    TVector<uint64_t> m_lastChangedFrame;
+    uint32_t m_traceMode = SAILOR_TRACE_FLAT_FLOAT_BOXES, m_rootSize = 0;
+    RHI::ivec2 m_resolutions[SAILOR_NUM_CSM_CASCADES] = { { 4096, 4096 }, { 4096, 4096 }, { 4096, 4096 }, { 4096, 4096 } };
+};
+
+// One pass as the host half of PrepareCSMPasses decides it (:295-366), before it gets its map and matrix
+struct CsmPassPlan {
+    uint32_t m_cascade = 0;
+    EShadowType m_shadowType = EShadowType::None;
+    TVector<uint32_t> m_internalCommandsList;
+    TVector<uint64_t> m_casterMask; // the final set, m_bCastShadows ANDed in
 };
 
 // One UpdateShaderBinding of LightingECS::Tick: `m_count` consecutive records written from record slot `m_startIndex` on.
@@ -57,7 +79,35 @@ public:
     void FillLightingData(RHI::RHISceneViewSnapshot& snapshot) const; // LightingECS.cpp:403-405
     RHI::RHIShaderBindingSetPtr GetLightsData() const { return m_lightsData; }
 
+    // ---- the cascades (ECS/LightingECS.cpp:262-371, :373-406) ----
+    static constexpr uint32_t NumCascades = SAILOR_NUM_CSM_CASCADES;   // ECS/LightingECS.h:65
+    static constexpr uint32_t MaxShadowsInView = 1024;                  // ECS/LightingECS.h:53
+    static constexpr float ShadowCascadeBlur[NumCascades][2] = { { 2, 5 }, { 1, 4 }, { 1, 3 }, { 1, 2 } }; // ECS/LightingECS.h:68
+    ~LightingECS();
+    // The scene's caster data (null = none: FillShadowPasses then leaves the snapshot's list empty and the bindings alone, as before this existed)
+    void SetCasterData(const CsmCasterData* casters);
+    bool HasCasterData() const { return m_bHasCasters; }
+    // The host half of PrepareCSMPasses for ONE directional light (:283-367), on overlap sets that are already there: the cascades' shadow types (:303), the
+    // removal, the snapshot comparison and the snapshots' update through sailor_host_csm_plan_passes, the dependency indices `alreadyPlacedPasses + shift`
+    // (:307-331), m_bCastShadows (ShadowPrepassNode.cpp:110).  overlapMasks: NumCascades x ceil(numInstances / 64) words.  No device.
+    static TVector<CsmPassPlan> PlanLightPasses(SailorCsmSnapshots* snapshots, uint32_t firstSnapshot, uint32_t alreadyPlacedPasses, uint32_t numInstances,
+                                                const uint64_t* overlapMasks, EShadowType lightShadowType, const uint64_t* lastChangedFrame,
+                                                const SailorCsmView* view, const uint64_t* castShadows);
+    // per batch of the view: the popcount of the pass's mask over the batch's instance range, and the runs' offsets (in batch order)
+    static uint32_t CountBatchRuns(const TVector<uint64_t>& mask, const TVector<RHI::RHISceneBatch>& batches, TVector<RHI::RHIShadowBatchRun>& outRuns);
+    // FillLightingData's shadow half (:377-401) for the snapshot's one camera: GetLightsInFrustum, PrepareCSMPasses -> snapshot.m_shadowMapsToUpdate.  The
+    // overlap sets come from sailor_hip_csm_caster_masks[_traced] over the caster data's boxes and cross to the host for the planning (one wait per frame).
+    int FillShadowPasses(RHI::RHISceneViewSnapshot& snapshot);
+    const TVector<RHI::RHITexturePtr>& GetCsmShadowMaps() const { return m_csmShadowMaps; }
+
 private:
+    int EnsureCsmShadowMaps(EShadowType firstCascadeType);
+    bool m_bHasCasters = false;
+    CsmCasterData m_casters;
+    TVector<RHI::RHITexturePtr> m_csmShadowMaps;   // :53-63, owned here, persistent across frames
+    EShadowType m_csmFirstCascadeType = EShadowType::None;
+    RHI::RHIBufferPtr m_csmMasks;                  // NumCascades x words, device
+    SailorCsmSnapshots* m_csmSnapshots = nullptr;  // LightingECS::m_csmSnapshots
     std::vector<LightData> m_components;
     std::vector<std::pair<uint32_t, uint32_t>> m_skipList; // (first slot, count) runs of static lights Tick steps over (LightingECS.h:106)
     std::vector<LightUploadRun> m_lastUploads;
@@ -75,6 +125,8 @@ public:
     // RHISceneView::TraceScene's set as the reference computes it (integer boxes in the octree, RHI/SceneView.cpp:170) and fills m_inserted too.
     // rootSize 0 = SAILOR_OCTREE_ROOT_SIZE.
     void SetTraceMode(uint32_t mode, uint32_t rootSize = 0);
+    uint32_t GetTraceMode() const { return m_traceMode; }
+    uint32_t GetRootSize() const { return m_rootSize; }
     RHI::RHIBufferPtr m_transforms, m_parent, m_localAabb, m_world, m_worldAabb, m_visibility;
     RHI::RHIBufferPtr m_inserted; // octree mode: one bit per entity, in the octree at all
     uint32_t m_count = 0;

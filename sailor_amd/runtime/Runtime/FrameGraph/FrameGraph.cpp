@@ -4,6 +4,8 @@
 #include "FrameGraphNode.h"
 #include "LightCullingNode.h"
 #include "DepthPrepassNode.h"
+#include "ShadowPrepassNode.h"
+#include "ClearNode.h"
 #include "RHIFrameGraph.h"
 #include "../RHI/Renderer.h"
 #include "../RHI/DebugContext.h"
@@ -35,6 +37,8 @@ bool FrameGraphBuilder::IsRegistered(const std::string& nodeName) { return Regis
 FrameGraphNodePtr FrameGraphBuilder::CreateOptInNode(const std::string& nodeName)
 {
     if (nodeName == BloomNode::GetName()) return FrameGraphNodePtr(new BloomNode());
+    if (nodeName == ShadowPrepassNode::GetName()) return FrameGraphNodePtr(new ShadowPrepassNode());
+    if (nodeName == ClearNode::GetName()) return FrameGraphNodePtr(new ClearNode());
     return FrameGraphNodePtr();
 }
 
@@ -1135,3 +1139,221 @@ void BloomNode::Process(RHIFrameGraphPtr frameGraph, RHICommandListPtr, RHIComma
 }
 
 void BloomNode::Clear() {} // (:146-148)
+
+// ---- ClearNode (FrameGraph/ClearNode.cpp:19-109) ----------------------------------------------------------------------------------------------
+const char* ClearNode::m_name = "Clear";
+
+void ClearNode::Process(RHIFrameGraphPtr frameGraph, RHICommandListPtr, RHICommandListPtr commandList, const RHISceneViewSnapshot&)
+{
+    auto commands = Renderer::GetDriverCommands();
+    // (:28-56) an RHISurface target: surfaces -- an MSAA target with its resolved twin -- are not mirrored, a `bIsSurface` target is a plain texture here
+    RHITexturePtr dst = GetRHIResource("target").DynamicCast<RHITexture>(); // (:57-60)
+    bool bIsDepthFormat = dst && dst->m_bDepthFormat;
+    if (!dst) { // (:61-90) by name from m_unresolvedResourceParams
+        for (const auto& r : m_unresolvedResourceParams) {
+            if (r.first == "target") {
+                dst = frameGraph->GetRenderTarget(r.second);
+                // (:69-85) "MSAA render targets are resolved inside the VulkanDriver": the clear of the internal MSAA depth target has no counterpart, the path
+                // has no MSAA.  The per-frame "DepthBuffer" is the driver's depth buffer there, a depth format whatever texture the host wrapped for it here
+                bIsDepthFormat = dst && (dst->m_bDepthFormat || r.second == "DepthBuffer");
+                break;
+            }
+        }
+    }
+    if (!dst) return; // (the reference dereferences it: a `.renderer` file naming no target is its caller's error)
+    commands->ImageMemoryBarrier(commandList, dst, EImageLayout::TransferDstOptimal); // (:92)
+    if (bIsDepthFormat) { // (:93-101)
+        const float clearDepth = GetFloat("clearDepth"), clearStencil = GetFloat("clearStencil");
+        commands->BeginDebugRegion(commandList, GetName());
+        commands->ClearDepthStencil(commandList, dst, clearDepth, (uint32_t)clearStencil);
+        commands->EndDebugRegion(commandList);
+    } else { // (:102-108) in the target's storage format: the fp32 channels of its canonical form (FrameGraphParser.cpp canonical_format); level 0 of a mip chain
+        const vec4 clearColor = GetVec4("clearColor");
+        commands->BeginDebugRegion(commandList, GetName());
+        commands->ClearImage(commandList, dst, clearColor.x, clearColor.y, clearColor.z, clearColor.w);
+        commands->EndDebugRegion(commandList);
+    }
+}
+
+void ClearNode::Clear() {} // (:111-113)
+
+// ---- ShadowPrepassNode (FrameGraph/ShadowPrepassNode.cpp:20-376) --------------------------------------------------------------------------------
+const char* ShadowPrepassNode::m_name = "ShadowPrepass";
+
+RHIMaterialPtr ShadowPrepassNode::GetOrAddShadowMaterial(EShadowType shadowType) // (:20-45)
+{
+    auto& material = shadowType == EShadowType::EVSM ? m_shadowMaterial_Evsm : m_shadowMaterial_Pcf;
+    if (!material) {
+        auto driver = Renderer::GetDriver();
+        auto pShader = shadowType == EShadowType::EVSM ? driver->CreateShader("Shaders/ShadowCaster.shader", { "EVSM" }) : driver->CreateShader("Shaders/ShadowCaster.shader");
+        if (pShader && pShader->IsReady()) material = driver->CreateMaterial(pShader); // RenderState: depth test and write, ECullMode::Back, GreaterOrEqual (:39)
+    }
+    return material;
+}
+
+void ShadowPrepassNode::Process(RHIFrameGraphPtr, RHICommandListPtr transferCommandList, RHICommandListPtr commandList, const RHISceneViewSnapshot& sceneView)
+{
+    auto driver = Renderer::GetDriver();
+    auto commands = Renderer::GetDriverCommands();
+    if (!m_pBlurVerticalShader) { // (:54-77)
+        m_pBlurVerticalShader = driver->CreateShader("Shaders/Blur.shader", { "VERTICAL", "EVSM" });
+        m_pBlurVerticalMaterial = driver->CreateMaterial(m_pBlurVerticalShader);
+        m_pBlurHorizontalShader = driver->CreateShader("Shaders/Blur.shader", { "HORIZONTAL", "EVSM" });
+        m_pBlurHorizontalMaterial = driver->CreateMaterial(m_pBlurHorizontalShader);
+        m_pBlurShaderBindings = driver->CreateShaderBindings();
+        driver->FillShadersLayout(m_pBlurShaderBindings, { m_pBlurVerticalShader }, 1);
+        RHIShaderBindingPtr blurDataBinding = driver->AddBufferToShaderBindings(m_pBlurShaderBindings, "data", sizeof(float) * 4 * 3, 0, EShaderBindingType::UniformBuffer);
+        const float defaultBlurRadius = 3.0f;
+        const float blurData[12] = { defaultBlurRadius, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+        commands->UpdateShaderBinding(transferCommandList, blurDataBinding, blurData, sizeof blurData);
+    }
+    // (:79 adds the binding again every frame, which finds it; here AddBufferToShaderBindings would zero a uniform block's bytes, so it is looked up)
+    RHIShaderBindingPtr blurDataBinding = m_pBlurShaderBindings->Find("data");
+    if (sceneView.m_shadowMapsToUpdate.empty()) return; // (:87-90)
+    // (:81-85, behind the early return and every frame: the lights set's `lightsMatrices` may be replaced by a caller that hands maps in)
+    m_lightMatrices = sceneView.m_rhiLightsData ? sceneView.m_rhiLightsData->Find("lightsMatrices") : RHIShaderBindingPtr();
+    auto sceneData = sceneView.m_sceneBindings ? sceneView.m_sceneBindings->Find("data") : RHIShaderBindingPtr();
+    if (!m_lightMatrices || !sceneData || !sceneData->m_buffer) return;
+
+    commands->BeginDebugRegion(commandList, GetName()); // (:92)
+    const uint32_t NumShadowPasses = (uint32_t)sceneView.m_shadowMapsToUpdate.size();
+    // (:96-138) "Filter sceneView by tag": the passes arrive filtered -- m_bCastShadows is in their masks, the batches' runs are counted
+    uint32_t numMeshes = 0;
+    TVector<uint32_t> passFirst(NumShadowPasses);
+    size_t words = 0;
+    for (uint32_t passIndex = 0; passIndex < NumShadowPasses; passIndex++) {
+        passFirst[passIndex] = numMeshes;
+        numMeshes += sceneView.m_shadowMapsToUpdate[passIndex].m_numCasters;
+        words = std::max(words, sceneView.m_shadowMapsToUpdate[passIndex].m_casterMask.size());
+    }
+    if (numMeshes == 0) { // (:140-143; the reference returns with the region open)
+        commands->EndDebugRegion(commandList);
+        return;
+    }
+    if (!m_perInstanceData || m_sizePerInstanceData < sizeof(PerInstanceData) * numMeshes) { // (:145-151) one SSBO for all passes
+        m_perInstanceData = driver->CreateShaderBindings();
+        driver->AddSsboToShaderBindings(m_perInstanceData, "data", sizeof(PerInstanceData), numMeshes, 0);
+        m_sizePerInstanceData = sizeof(PerInstanceData) * numMeshes;
+    }
+    RHIShaderBindingPtr storageBinding = m_perInstanceData->GetOrAddShaderBinding("data"); // (:153)
+    // (:155-201) the SSBO's contents: where the reference memcpys every batch's matrices on the host and uploads them, the passes' masks go to the device and the
+    // runs are gathered there, in ascending instance order inside a run (the reference's order is its octree's walk; the rasteriser's result does not depend on it)
+    const uint32_t numInstances = (uint32_t)(sceneData->m_buffer->m_size / sizeof(SailorPerInstanceData));
+    const size_t maskBytes = words * 8;
+    if (!m_masks || m_masks->m_size < NumShadowPasses * maskBytes) m_masks = driver->CreateBuffer(std::max<size_t>(NumShadowPasses, 4) * maskBytes);
+    if (!m_masks || !storageBinding->m_buffer) { commands->EndDebugRegion(commandList); return; }
+    TVector<IGraphicsDriverCommands::ShadowGatherRun> runs;
+    for (uint32_t i = 0; i < NumShadowPasses; i++) {
+        const auto& shadowPass = sceneView.m_shadowMapsToUpdate[i];
+        if (shadowPass.m_numCasters == 0) continue;
+        commands->UpdateBuffer(transferCommandList, m_masks, shadowPass.m_casterMask.data(), shadowPass.m_casterMask.size() * 8, i * maskBytes);
+        for (size_t b = 0; b < shadowPass.m_batchRuns.size() && b < sceneView.m_batches.size(); b++) {
+            const RHISceneBatch& batch = sceneView.m_batches[b];
+            if (shadowPass.m_batchRuns[b].m_count == 0) continue;
+            IGraphicsDriverCommands::ShadowGatherRun run;
+            run.m_maskOffset = i * maskBytes;
+            run.m_begin = std::min(batch.m_firstInstance, numInstances);
+            run.m_end = (uint32_t)std::min<uint64_t>((uint64_t)batch.m_firstInstance + batch.m_instanceCount, std::min<uint64_t>(numInstances, shadowPass.m_casterMask.size() * 64));
+            run.m_dstFirst = passFirst[i] + shadowPass.m_batchRuns[b].m_offset; // storageIndex[j] (:182)
+            run.m_capacity = shadowPass.m_batchRuns[b].m_count;
+            runs.push_back(run);
+        }
+    }
+    commands->GatherShadowInstances(transferCommandList, sceneData->m_buffer, numInstances, m_masks, storageBinding->m_buffer, runs); // (in place of :194-201)
+    // the caster draws' vertex input
+    TVector<std::pair<RHIBufferPtr, RHIBufferPtr>> positions;
+    auto positionsOf = [&](const RHIBufferPtr& vertexBuffer) -> RHIBufferPtr {
+        if (!vertexBuffer) return RHIBufferPtr();
+        for (auto& p : positions) if (p.first.GetRawPtr() == vertexBuffer.GetRawPtr()) return p.second;
+        for (auto& p : m_positions) if (p.first.GetRawPtr() == vertexBuffer.GetRawPtr()) { positions.push_back(p); return p.second; }
+        const uint32_t numVertices = (uint32_t)(vertexBuffer->m_size / sizeof(SailorVertexP3N3T3B3UV2C4));
+        auto extracted = driver->CreateBuffer(std::max<size_t>((size_t)numVertices * 12, 4));
+        if (extracted) commands->ExtractVertexPositions(transferCommandList, vertexBuffer, numVertices, extracted);
+        positions.emplace_back(vertexBuffer, extracted);
+        return extracted;
+    };
+    for (const auto& batch : sceneView.m_batches) positionsOf(batch.m_vertexBuffer);
+    m_positions = positions;
+
+    // RHIRecordDrawCall / RHIDrawCall (RHI/Batch.hpp) for the batches of pass `from`, drawn inside the current render pass.  Plain DrawIndexed per batch, not an
+    // indirect buffer: the counts are the host's own popcounts, so an indirect command would carry nothing the host does not know, and ShadowCaster.shader under
+    // DrawIndexedIndirect stays refused by the backend (HipGraphicsDriver.cpp DrawIndexedIndirect).
+    auto drawBatches = [&](uint32_t from, RHIMaterialPtr material) -> uint32_t {
+        const auto& pass = sceneView.m_shadowMapsToUpdate[from];
+        uint32_t drawn = 0;
+        for (size_t b = 0; b < pass.m_batchRuns.size() && b < sceneView.m_batches.size(); b++) {
+            const RHISceneBatch& batch = sceneView.m_batches[b];
+            auto vertexPositions = positionsOf(batch.m_vertexBuffer);
+            if (pass.m_batchRuns[b].m_count == 0 || !vertexPositions || !batch.m_indexBuffer) continue;
+            commands->BindMaterial(commandList, material);
+            commands->BindShaderBindings(commandList, material, { sceneView.m_frameBindings, m_perInstanceData }); // shaderBindingsByMaterial (:208-212)
+            commands->BindVertexBuffer(commandList, vertexPositions, 0);
+            commands->BindIndexBuffer(commandList, batch.m_indexBuffer, 0);
+            commands->DrawIndexed(commandList, batch.m_indexCount, pass.m_batchRuns[b].m_count, batch.m_firstIndex, batch.m_vertexOffset,
+                                  passFirst[from] + pass.m_batchRuns[b].m_offset);
+            drawn++;
+        }
+        return drawn;
+    };
+
+    for (uint32_t index = 0; index < NumShadowPasses; index++) { // (:219-365)
+        const auto& shadowPass = sceneView.m_shadowMapsToUpdate[index];
+        auto material = GetOrAddShadowMaterial(shadowPass.m_shadowType);
+        if (!material || !shadowPass.m_shadowMap) continue; // (:118-125 bIsDepthMaterialReady)
+        RHITexturePtr depthAttachment = driver->GetOrAddTemporaryRenderTarget(EFormat::R32_SFLOAT, shadowPass.m_shadowMap->GetExtent()); // (:227) the depth buffer's format
+        if (!depthAttachment) continue;
+        commands->BeginDebugRegion(commandList, "Record Shadow Map Pass " + std::to_string(index)); // (:221-229)
+        commands->ImageMemoryBarrier(commandList, shadowPass.m_shadowMap, EImageLayout::ColorAttachmentOptimal); // (:233)
+        commands->ImageMemoryBarrier(commandList, depthAttachment, EImageLayout::General);                        // (:234)
+        commands->BeginRenderPass(commandList, TVector<RHITexturePtr> { shadowPass.m_shadowMap }, depthAttachment, true); // (:236-245) clears colour to 0 and depth to 0
+        commands->PushConstants(commandList, material, 64, shadowPass.m_lightMatrix); // (:249)
+        uint32_t drawn = drawBatches(index, material);                                // (:251-257)
+        for (uint32_t dependencyPass : shadowPass.m_internalCommandsList)             // (:259-271) into the same attachment, without a clear
+            if (dependencyPass < NumShadowPasses) drawn += drawBatches(dependencyPass, material);
+        commands->UpdateShaderBinding(transferCommandList, m_lightMatrices, shadowPass.m_lightMatrix, 64, 64 * (size_t)shadowPass.m_lighMatrixIndex); // (:273-276)
+        commands->EndRenderPass(commandList); // (:278)
+        // the backend clears with the pass's first draw and writes the map behind its last; a pass that drew nothing leaves the render pass's own clear
+        if (drawn == 0) commands->ClearImage(commandList, shadowPass.m_shadowMap, 0.0f, 0.0f, 0.0f, 0.0f);
+        // (:283) `m_blurRadius.length() > 0.1f` is glm's member length(), the component count 2: every EVSM pass is blurred
+        if (shadowPass.m_shadowType == EShadowType::EVSM && blurDataBinding) {
+            RHITexturePtr blurAttachment = driver->GetOrAddTemporaryRenderTarget(shadowPass.m_shadowMap->m_format, shadowPass.m_shadowMap->GetExtent()); // (:285)
+            if (blurAttachment) {
+                commands->UpdateShaderBinding(commandList, blurDataBinding, shadowPass.m_blurRadius, sizeof(float) * 2); // (:286)
+                commands->BeginDebugRegion(commandList, "Blur Horizontal"); // (:289-324)
+                driver->AddSamplerToShaderBindings(m_pBlurShaderBindings, "colorSampler", shadowPass.m_shadowMap, 1);
+                commands->ImageMemoryBarrier(commandList, shadowPass.m_shadowMap, EImageLayout::ShaderReadOnlyOptimal);
+                commands->ImageMemoryBarrier(commandList, blurAttachment, EImageLayout::ColorAttachmentOptimal);
+                commands->BeginRenderPass(commandList, TVector<RHITexturePtr> { blurAttachment }, RHITexturePtr());
+                commands->BindMaterial(commandList, m_pBlurHorizontalMaterial);
+                commands->BindShaderBindings(commandList, m_pBlurHorizontalMaterial, { sceneView.m_frameBindings, m_pBlurShaderBindings });
+                commands->DrawIndexed(commandList, 6, 1, 0, 0, 0);
+                commands->EndRenderPass(commandList);
+                commands->ImageMemoryBarrier(commandList, shadowPass.m_shadowMap, EImageLayout::ColorAttachmentOptimal);
+                commands->ImageMemoryBarrier(commandList, blurAttachment, EImageLayout::ShaderReadOnlyOptimal);
+                commands->EndDebugRegion(commandList);
+                commands->BeginDebugRegion(commandList, "Blur Vertical"); // (:327-355)
+                driver->AddSamplerToShaderBindings(m_pBlurShaderBindings, "colorSampler", blurAttachment, 1);
+                commands->BeginRenderPass(commandList, TVector<RHITexturePtr> { shadowPass.m_shadowMap }, RHITexturePtr());
+                commands->BindMaterial(commandList, m_pBlurVerticalMaterial);
+                commands->BindShaderBindings(commandList, m_pBlurVerticalMaterial, { sceneView.m_frameBindings, m_pBlurShaderBindings });
+                commands->DrawIndexed(commandList, 6, 1, 0, 0, 0);
+                commands->EndRenderPass(commandList);
+                commands->EndDebugRegion(commandList);
+                driver->ReleaseTemporaryRenderTarget(blurAttachment); // (:357)
+            }
+        }
+        driver->ReleaseTemporaryRenderTarget(depthAttachment); // (:360)
+        commands->EndDebugRegion(commandList);
+    }
+    commands->EndDebugRegion(commandList); // (:367)
+}
+
+void ShadowPrepassNode::Clear() // (:370-376)
+{
+    m_lightMatrices.Clear();
+    m_perInstanceData.Clear();
+    m_shadowMaterial_Pcf.Clear();
+    m_shadowMaterial_Evsm.Clear();
+    m_masks.Clear();
+    m_positions.clear();
+}

@@ -1,6 +1,7 @@
 #include "HipGraphicsDriver.h"
 #include <dlfcn.h>
 #include <algorithm>
+#include <cmath>
 #include "../../RHI/Renderer.h"
 
 #include <cstdio>
@@ -409,11 +410,102 @@ void HipGraphicsDriver::ClearImage(RHICommandListPtr cmd, RHITexturePtr dst, flo
     SailorHipContext* ctx = m_ctx;
     cmd->m_hip.m_commands.push_back([this, ctx, dst, r, g, b, a]() {
         const bool uniformRgba = dst && dst->m_format == EFormat::R32G32B32A32_SFLOAT && r == g && g == b && b == a;
+        if (dst && dst->m_buffer && !uniformRgba && (dst->m_format == EFormat::R32G32B32A32_SFLOAT || dst->m_format == EFormat::R32G32_SFLOAT)) {
+            // ClearNode's (ClearNode.cpp:104-106): a colour whose channels differ, in the target's storage format -- the fp32 channels it has, (r, g, b, a) or (r, g)
+            const float color[4] = { r, g, b, a };
+            uint32_t bits[4];
+            memcpy(bits, color, 16);
+            BeforeBufferWrite(dst->m_buffer->m_hip.m_devicePtr);
+            return sailor_hip_buffer_fill_pattern(ctx, texels_of(dst), 0, bits, dst->m_format == EFormat::R32G32_SFLOAT ? 2u : 4u,
+                                                  (size_t)dst->GetExtent().x * dst->GetExtent().y);
+        }
+        if (dst && dst->m_buffer && dst->m_format == EFormat::R16_SFLOAT && r == 0.0f && !std::signbit(r) && ((size_t)dst->GetExtent().x * dst->GetExtent().y) % 2 == 0) {
+            // an R16F shadow map cleared to the render pass's clear colour 0 (ShadowPrepassNode.cpp:236-245 with nothing drawn): two texels per word
+            BeforeBufferWrite(dst->m_buffer->m_hip.m_devicePtr);
+            return sailor_hip_buffer_fill_u32(ctx, dst->m_buffer->m_hip.m_devicePtr, 0, 0u, (size_t)dst->GetExtent().x * dst->GetExtent().y / 2);
+        }
         if (!dst || !dst->m_buffer || (dst->m_format != EFormat::R32_SFLOAT && !uniformRgba)) return (int)SAILOR_HIP_ERR_UNSUPPORTED;
         uint32_t bits;
         memcpy(&bits, &r, 4);
         BeforeBufferWrite(dst->m_buffer->m_hip.m_devicePtr);
         return sailor_hip_buffer_fill_u32(ctx, dst->m_buffer->m_hip.m_devicePtr, 0, bits, (size_t)dst->GetExtent().x * dst->GetExtent().y * (uniformRgba ? 4 : 1));
+    });
+}
+
+// RHI/GraphicsDriver.h:295 -> vkCmdClearDepthStencilImage.  A depth target is one fp32 plane here (FrameGraphParser.cpp: the D32 / D24 / D16 formats), so the
+// depth value fills it and the stencil value has nowhere to go.  Any other format is refused, as Vulkan refuses a colour image here.
+void HipGraphicsDriver::ClearDepthStencil(RHICommandListPtr cmd, RHITexturePtr dst, float depth, uint32_t)
+{
+    SailorHipContext* ctx = m_ctx;
+    cmd->m_hip.m_commands.push_back([this, ctx, dst, depth]() {
+        if (!dst || !dst->m_buffer || dst->m_format != EFormat::R32_SFLOAT) return (int)SAILOR_HIP_ERR_UNSUPPORTED;
+        uint32_t bits;
+        memcpy(&bits, &depth, 4);
+        BeforeBufferWrite(dst->m_buffer->m_hip.m_devicePtr);
+        return sailor_hip_buffer_fill_u32(ctx, dst->m_buffer->m_hip.m_devicePtr, 0, bits, (size_t)dst->GetExtent().x * dst->GetExtent().y);
+    });
+}
+
+RHITexturePtr HipGraphicsDriver::GetOrAddTemporaryRenderTarget(EFormat format, ivec2 extent)
+{
+    for (auto& t : m_temporaryRenderTargets)
+        if (!t.m_bInUse && t.m_target->m_format == format && t.m_target->GetExtent().x == extent.x && t.m_target->GetExtent().y == extent.y) {
+            t.m_bInUse = true;
+            return t.m_target;
+        }
+    auto target = CreateRenderTarget(extent, 1, format);
+    if (target) m_temporaryRenderTargets.push_back({ target, true });
+    return target;
+}
+
+void HipGraphicsDriver::ReleaseTemporaryRenderTarget(RHITexturePtr renderTarget)
+{
+    for (auto& t : m_temporaryRenderTargets)
+        if (t.m_target.GetRawPtr() == renderTarget.GetRawPtr()) t.m_bInUse = false;
+}
+
+void HipGraphicsDriver::GatherShadowInstances(RHICommandListPtr cmd, RHIBufferPtr instances, uint32_t numInstances, RHIBufferPtr masks, RHIBufferPtr dst,
+                                              const TVector<ShadowGatherRun>& runs)
+{
+    if (runs.empty()) return;
+    if (!instances || !masks || !dst) { cmd->m_hip.m_commands.push_back([]() { return (int)SAILOR_HIP_ERR_INVALID_ARGUMENT; }); return; }
+    // everything a run addresses is checked against the buffers' sizes here, when the command is recorded; the scratch is grown here too, not at submit
+    bool ok = (size_t)numInstances * sizeof(SailorPerInstanceData) <= instances->m_size;
+    TVector<SailorShadowGatherJob> jobs(runs.size());
+    for (size_t i = 0; i < runs.size() && ok; i++) {
+        const ShadowGatherRun& r = runs[i];
+        ok = r.m_begin <= r.m_end && r.m_end <= numInstances && r.m_maskOffset % 8 == 0 && r.m_maskOffset <= masks->m_size &&
+             ((size_t)r.m_end + 63) / 64 * 8 <= masks->m_size - r.m_maskOffset && ((size_t)r.m_dstFirst + r.m_capacity) * 64 <= dst->m_size;
+        jobs[i].begin = r.m_begin; jobs[i].end = r.m_end; jobs[i].capacity = r.m_capacity; jobs[i]._pad = 0;
+    }
+    if (!ok) { cmd->m_hip.m_commands.push_back([]() { return (int)SAILOR_HIP_ERR_INVALID_ARGUMENT; }); return; }
+    const size_t need = sailor_hip_shadow_gather_workspace_bytes(jobs.data(), (uint32_t)jobs.size());
+    if (!m_shadowGatherWorkspace || m_shadowGatherWorkspace->m_size < need) m_shadowGatherWorkspace = CreateBuffer(need + 256);
+    if (!m_shadowGatherCounts || m_shadowGatherCounts->m_size < 4 * jobs.size()) m_shadowGatherCounts = CreateBuffer(4 * jobs.size() + 256);
+    RHIBufferPtr workspace = m_shadowGatherWorkspace, counts = m_shadowGatherCounts;
+    if (!workspace || !counts) { cmd->m_hip.m_commands.push_back([]() { return (int)SAILOR_HIP_ERR_OUT_OF_MEMORY; }); return; }
+    SailorHipContext* ctx = m_ctx;
+    TVector<ShadowGatherRun> recorded = runs;
+    cmd->m_hip.m_commands.push_back([this, ctx, instances, numInstances, masks, dst, workspace, counts, recorded, jobs]() mutable {
+        for (size_t i = 0; i < jobs.size(); i++) { // the device addresses as they are when the command runs
+            jobs[i].dMask = (const uint64_t*)((const char*)masks->m_hip.m_devicePtr + recorded[i].m_maskOffset);
+            jobs[i].dOut = (float*)dst->m_hip.m_devicePtr + 16 * (size_t)recorded[i].m_dstFirst;
+            jobs[i].dCount = (uint32_t*)counts->m_hip.m_devicePtr + i;
+        }
+        BeforeBufferWrite(dst->m_hip.m_devicePtr);
+        return sailor_hip_shadow_gather_instances_batched(ctx, (const SailorPerInstanceData*)instances->m_hip.m_devicePtr, numInstances, jobs.data(),
+                                                          (uint32_t)jobs.size(), workspace->m_hip.m_devicePtr, workspace->m_size);
+    });
+}
+
+void HipGraphicsDriver::ExtractVertexPositions(RHICommandListPtr cmd, RHIBufferPtr vertices, uint32_t numVertices, RHIBufferPtr positions)
+{
+    SailorHipContext* ctx = m_ctx;
+    cmd->m_hip.m_commands.push_back([this, ctx, vertices, numVertices, positions]() {
+        if (!vertices || !positions || (size_t)numVertices * sizeof(SailorVertexP3N3T3B3UV2C4) > vertices->m_size || (size_t)numVertices * 12 > positions->m_size)
+            return (int)SAILOR_HIP_ERR_INVALID_ARGUMENT;
+        BeforeBufferWrite(positions->m_hip.m_devicePtr);
+        return sailor_hip_shadow_extract_positions(ctx, (const SailorVertexP3N3T3B3UV2C4*)vertices->m_hip.m_devicePtr, numVertices, (float*)positions->m_hip.m_devicePtr);
     });
 }
 

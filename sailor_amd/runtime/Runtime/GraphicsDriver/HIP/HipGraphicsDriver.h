@@ -61,6 +61,10 @@
 //       inside the kernel.  The workspace is grown by ReserveUiWorkspace (whoever hands draw data over calls it) or when the pass is recorded, never at submit.
 //   "Shaders/ShadowCaster.shader" [EVSM]  -> sailor_hip_raster_depth into the pass' depth attachment, and at EndRenderPass sailor_hip_shadow_resolve
 //                                            into its colour attachment (push constant lightMatrix, set 1 `data`, vertex positions, 32-bit indices)
+// and for the ShadowPrepass and Clear nodes: GatherShadowInstances -> sailor_hip_shadow_gather_instances_batched (the pass's `data` SSBO from its caster
+// bitmasks, in place of the reference's host upload), ExtractVertexPositions -> sailor_hip_shadow_extract_positions, ClearDepthStencil and ClearImage ->
+// sailor_hip_buffer_fill_u32 / sailor_hip_buffer_fill_pattern over the target's fp32 channels, GetOrAddTemporaryRenderTarget / ReleaseTemporaryRenderTarget
+// (a pool: a steady-state frame allocates nothing)
 #pragma once
 #include <map>
 #include <memory>
@@ -103,6 +107,8 @@ public:
     RHI::RHITexturePtr CreateTexture(const void* pData, size_t size, RHI::ivec2 extent, RHI::EFormat format) override;
     RHI::RHITexturePtr CreateRenderTarget(RHI::ivec2 extent, uint32_t mipLevels, RHI::EFormat format) override;
     RHI::RHICubemapPtr CreateCubemap(RHI::ivec2 extent, uint32_t mipLevels, RHI::EFormat format) override;
+    RHI::RHITexturePtr GetOrAddTemporaryRenderTarget(RHI::EFormat format, RHI::ivec2 extent) override;
+    void ReleaseTemporaryRenderTarget(RHI::RHITexturePtr renderTarget) override;
     void SubmitCommandList(RHI::RHICommandListPtr commandList) override;
     RHI::RHIMaterialPtr CreateMaterial(RHI::RHIShaderPtr shader) override;
     RHI::RHIShaderBindingSetPtr CreateShaderBindings() override;
@@ -140,6 +146,10 @@ public:
     void EndDebugRegion(RHI::RHICommandListPtr cmdList) override;
     void ImageMemoryBarrier(RHI::RHICommandListPtr cmd, RHI::RHITexturePtr image, RHI::EImageLayout newLayout) override;
     void ClearImage(RHI::RHICommandListPtr cmd, RHI::RHITexturePtr dst, float r, float g, float b, float a) override;
+    void ClearDepthStencil(RHI::RHICommandListPtr cmd, RHI::RHITexturePtr dst, float depth, uint32_t stencil) override;
+    void GatherShadowInstances(RHI::RHICommandListPtr cmd, RHI::RHIBufferPtr instances, uint32_t numInstances, RHI::RHIBufferPtr masks, RHI::RHIBufferPtr dst,
+                               const TVector<ShadowGatherRun>& runs) override;
+    void ExtractVertexPositions(RHI::RHICommandListPtr cmd, RHI::RHIBufferPtr vertices, uint32_t numVertices, RHI::RHIBufferPtr positions) override;
     bool BlitImage(RHI::RHICommandListPtr cmd, RHI::RHITexturePtr src, RHI::RHITexturePtr dst, RHI::ivec4 srcRegionRect, RHI::ivec4 dstRegionRect,
                    RHI::ETextureFiltration filtration = RHI::ETextureFiltration::Linear) override;
     void GenerateMipMaps(RHI::RHICommandListPtr cmd, RHI::RHITexturePtr target) override;
@@ -233,6 +243,10 @@ private:
     int32_t m_cullW = 0, m_cullH = 0, m_cullLights = 0; // geometry of the last light cull: locates its shading-order hint in the workspace
     bool m_cullOrderValid = false;
     std::map<const void*, RHI::RHIBufferPtr> m_rasterWorkspaces; // depth attachment -> the rasteriser's workspace (coarse depth, mesh box, giants' queue)
+    // GetOrAddTemporaryRenderTarget's pool, and GatherShadowInstances' scratch (chunk offsets; one count word per run), grown when a command is RECORDED
+    struct TemporaryRenderTarget { RHI::RHITexturePtr m_target; bool m_bInUse = false; };
+    TVector<TemporaryRenderTarget> m_temporaryRenderTargets;
+    RHI::RHIBufferPtr m_shadowGatherWorkspace, m_shadowGatherCounts;
     uint32_t m_exchangesClipped = 0; // exchanges whose global lists arrived clipped (reported by the exchange after them)
     // Round 4: the light cull stops after its per-tile lists (SAILOR_CULL_DEFER_PACK); the compaction into the node's `lightsGrid` / `culledLights`
     // SSBOs is recorded on a second context (own stream) and runs BESIDE the RenderScene shade, which reads the per-tile lists when the two SSBOs

@@ -18,6 +18,10 @@ public:
     virtual RHITexturePtr CreateTexture(const void* pData, size_t size, ivec2 extent, EFormat format) = 0; // :98-108
     virtual RHITexturePtr CreateRenderTarget(ivec2 extent, uint32_t mipLevels, EFormat format) = 0;        // :110-117 (filtration, clamping, usage dropped)
     virtual RHICubemapPtr CreateCubemap(ivec2 extent, uint32_t mipLevels, EFormat format) = 0;             // :137-143
+    // :119-120 the pool of temporary render targets (ShadowPrepassNode.cpp:227, :285, :357, :360): a released target is handed out again to the next request
+    // of its format and extent, so a steady-state frame allocates none
+    virtual RHITexturePtr GetOrAddTemporaryRenderTarget(EFormat format, ivec2 extent) = 0;
+    virtual void ReleaseTemporaryRenderTarget(RHITexturePtr renderTarget) = 0;
     virtual void SubmitCommandList(RHICommandListPtr commandList) = 0;                                     // :149
     virtual RHIMaterialPtr CreateMaterial(RHIShaderPtr shader) = 0;                                        // :138-141 (vertex layout / topology / render state dropped)
     virtual RHIShaderBindingSetPtr CreateShaderBindings() = 0;                                             // :152
@@ -45,6 +49,7 @@ public:
     virtual void EndDebugRegion(RHICommandListPtr cmdList) = 0;                              // :239
     virtual void ImageMemoryBarrier(RHICommandListPtr cmd, RHITexturePtr image, EImageLayout newLayout) = 0; // :290
     virtual void ClearImage(RHICommandListPtr cmd, RHITexturePtr dst, float r, float g, float b, float a) = 0;   // :294 (a glm::vec4 there)
+    virtual void ClearDepthStencil(RHICommandListPtr cmd, RHITexturePtr dst, float depth, uint32_t stencil) = 0;  // :295 (the canonical fp32 plane has no stencil: the value is dropped)
     virtual bool BlitImage(RHICommandListPtr cmd, RHITexturePtr src, RHITexturePtr dst, ivec4 srcRegionRect, ivec4 dstRegionRect,
                            ETextureFiltration filtration = ETextureFiltration::Linear) = 0; // :293 (equal extents: a copy; scaled: one channel, Nearest)
     virtual void GenerateMipMaps(RHICommandListPtr cmd, RHITexturePtr target) = 0;                                                                  // :296 (cubemaps)
@@ -69,6 +74,16 @@ public:
     // the recorded form of IGraphicsDriver::CopyBuffer_Immediate (:192).  Not in the reference's command interface: its nodes refill their per-instance SSBO
     // from host arrays (UpdateShaderBinding); the mirror's scene data is device-resident, so the refill is a device copy
     virtual void CopyBuffer(RHICommandListPtr cmd, RHIBufferPtr src, RHIBufferPtr dst, size_t size, size_t srcOffset = 0, size_t dstOffset = 0) = 0;
+    // Two more commands the reference's interface does not have, both for ShadowPrepassNode and for the same reason as CopyBuffer: where the reference fills
+    // the pass's per-instance SSBO from host arrays (ShadowPrepassNode.cpp:155-201, UpdateShaderBinding), the mirror's instances are device-resident and the
+    // runs are gathered on the device from the passes' bitmasks (sailor_hip_shadow_gather_instances_batched).  One job = one run: the bits [begin, end) of the
+    // mask that starts `maskOffset` bytes into `masks`, its matrices written from record `dstFirst` of `dst` on, at most `capacity` of them.
+    struct ShadowGatherRun { size_t m_maskOffset = 0; uint32_t m_begin = 0, m_end = 0, m_dstFirst = 0, m_capacity = 0; };
+    virtual void GatherShadowInstances(RHICommandListPtr cmd, RHIBufferPtr instances, uint32_t numInstances, RHIBufferPtr masks, RHIBufferPtr dst,
+                                       const TVector<ShadowGatherRun>& runs) = 0;
+    // ... and the caster draws' vertex input: ShadowCaster.shader reads inPosition alone, the backend's rasteriser takes packed vec3 positions
+    // (sailor_hip_shadow_extract_positions): positions[v] = vertices[v].m_position
+    virtual void ExtractVertexPositions(RHICommandListPtr cmd, RHIBufferPtr vertices, uint32_t numVertices, RHIBufferPtr positions) = 0;
     virtual void Dispatch(RHICommandListPtr cmd, RHIShaderPtr computeShader, uint32_t groupSizeX, uint32_t groupSizeY, uint32_t groupSizeZ,
                           const TVector<RHIShaderBindingSetPtr>& bindings, const void* pPushConstantsData = nullptr,
                           uint32_t sizePushConstantsData = 0) = 0;                                                                                       // :310-314

@@ -24,12 +24,33 @@ struct RHISceneBatch {
     bool m_bGltf = false;
 };
 
+enum class EShadowType : uint32_t { None = 0, PCF = 1, EVSM = 2 }; // RHI/SceneView.h:13-18
+
+// RHI/SceneView.h:56-65 RHIUpdateShadowMapCommand: one shadow pass of ShadowPrepassNode::Process, as LightingECS::PrepareCSMPasses hands it over.  In place of
+// m_meshList (a vector of proxies) the pass carries its caster set as a bitmask over the scene's instances (`data` of m_sceneBindings), LSB first -- the
+// cascade's overlap set without what an earlier re-rendered cascade of the same type overlaps (ECS/LightingECS.cpp:305-332), ANDed with m_bCastShadows
+// (the node's own filter, ShadowPrepassNode.cpp:110, applied where the mask is made) -- and what the host derives from the mask by popcount: per batch of
+// the view, how many of the batch's instances the pass draws and where their run of matrices begins inside the pass's slice of the node's SSBO.
+struct RHIShadowBatchRun { uint32_t m_count = 0, m_offset = 0; };
+struct RHIUpdateShadowMapCommand {
+    uint32_t m_lighMatrixIndex = 0;
+    EShadowType m_shadowType = EShadowType::None;
+    float m_blurRadius[2] = { 0.0f, 0.0f }; // [Umbra, Penumbra]
+    RHITexturePtr m_shadowMap;
+    float m_lightMatrix[16] = {};
+    TVector<uint32_t> m_internalCommandsList;
+    TVector<uint64_t> m_casterMask;         // ceil(instances / 64) words
+    TVector<RHIShadowBatchRun> m_batchRuns; // one per entry of RHISceneViewSnapshot::m_batches
+    uint32_t m_numCasters = 0;              // the sum of the runs' counts
+};
+
 struct RHISceneViewSnapshot {
     CameraData m_camera;
     float m_deltaTime = 0.0f, m_currentTime = 0.0f;
     uint32_t m_totalNumLights = 0;           // RHI/SceneView.h:75, filled at ECS/LightingECS.cpp:404
     RHIShaderBindingSetPtr m_frameBindings;  // :78, filled by RHIFrameGraph::FillFrameData
     RHIShaderBindingSetPtr m_rhiLightsData;  // :79, LightingECS::m_lightsData (binding 0 `light`, 6 `lightsMatrices`, 8 `shadowMaps`)
+    TVector<RHIUpdateShadowMapCommand> m_shadowMapsToUpdate; // :76, filled by LightingECS::FillShadowPasses (ECS/LightingECS.cpp:399-400) when the view has caster data
     // what RenderSceneNode.cpp draws: the batches of the view, and Standard.shader's sets 2-4 as one set -- `data` (PerInstanceDataSSBO), `material`
     // (MaterialDataSSBO), `textureSamplers` (a device table of SailorTextureDesc)
     TVector<RHISceneBatch> m_batches;

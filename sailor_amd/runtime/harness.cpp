@@ -999,9 +999,140 @@ RT_API int sailor_rt_set_ui_draw_data(SailorRuntime* rt, const float* displayPos
     return (int)count;
 }
 
+// ---- the cascades: what LightingECS::PrepareCSMPasses reads of the scene, and what it decided ------------------------------------------------------------
+// The scene's caster data, after sailor_rt_set_scene: the world boxes of the scene's instances on the device (numInstances x SailorAABB, what
+// sailor_hip_ecs_sweep writes), m_bCastShadows as a host bitmask (NULL = every instance casts), the frame each instance last changed (host, one per instance),
+// the cascade maps' resolutions (4 ints, NULL = ECS/LightingECS.h:67) and how the overlap sets are traced (SAILOR_TRACE_*; ~0u = as the runtime's sweep
+// system does, flat without one; rootSize 0 = the reference's).  From then on every sailor_rt_process_frame runs FillLightingData's shadow half first and
+// a ShadowPrepass node draws what it asks for.  A null box pointer takes the caster data away again.
+RT_API int sailor_rt_set_caster_data(SailorRuntime* rt, void* worldAabbDevicePtr, uint32_t numInstances, const uint64_t* castShadows, const uint64_t* lastChangedFrames,
+                                     const int* resolutions, uint32_t traceMode, uint32_t rootSize)
+{
+    if (!rt) return -1;
+    if (!worldAabbDevicePtr) { rt->lighting->SetCasterData(nullptr); rt->snapshot.m_shadowMapsToUpdate.clear(); return 0; }
+    if (numInstances && !lastChangedFrames) return -1;
+    auto* hip = static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver());
+    CsmCasterData casters;
+    casters.m_worldAabb = hip->WrapBuffer(worldAabbDevicePtr, (size_t)numInstances * sizeof(SailorAABB));
+    casters.m_numInstances = numInstances;
+    const size_t words = ((size_t)numInstances + 63) / 64;
+    if (castShadows) casters.m_castShadows.assign(castShadows, castShadows + words);
+    casters.m_lastChangedFrame.assign(lastChangedFrames, lastChangedFrames + numInstances);
+    for (int k = 0; resolutions && k < SAILOR_NUM_CSM_CASCADES; k++) {
+        if (resolutions[k] <= 0) return -1;
+        casters.m_resolutions[k] = { resolutions[k], resolutions[k] };
+    }
+    if (traceMode == ~0u) { casters.m_traceMode = rt->sweep ? rt->sweep->GetTraceMode() : SAILOR_TRACE_FLAT_FLOAT_BOXES; casters.m_rootSize = rt->sweep ? rt->sweep->GetRootSize() : 0u; }
+    else if (traceMode == SAILOR_TRACE_FLAT_FLOAT_BOXES || traceMode == SAILOR_TRACE_OCTREE_INT_BOXES) { casters.m_traceMode = traceMode; casters.m_rootSize = rootSize; }
+    else return -1;
+    rt->lighting->SetCasterData(&casters);
+    return 0;
+}
+
+// the owner's rotation of one light (x, y, z, w): with its position the light's transform, whose inverse is RHILightProxy::m_lightMatrix (LightingECS.cpp:227)
+RT_API int sailor_rt_set_light_rotation(SailorRuntime* rt, int index, const float* rotation4)
+{
+    if (!rt || !rotation4 || index < 0 || (size_t)index >= rt->lighting->Num()) return -1;
+    memcpy(rt->lighting->GetComponentData((size_t)index).m_ownerRotation, rotation4, 16);
+    return 0;
+}
+
+// sceneView.m_shadowMapsToUpdate of the last frame: per pass 8 words {m_lighMatrixIndex, m_shadowType, casters, dependencies, up to three dependency indices, 0};
+// outMasks (may be null): the passes' caster masks, `wordsPerMask` words each.  Returns the number of passes.
+RT_API int sailor_rt_shadow_passes(SailorRuntime* rt, uint32_t* outInfo, uint64_t* outMasks, uint32_t wordsPerMask, int maxPasses)
+{
+    if (!rt) return -1;
+    const auto& passes = rt->snapshot.m_shadowMapsToUpdate;
+    for (int i = 0; i < (int)passes.size() && i < maxPasses; i++) {
+        const auto& p = passes[(size_t)i];
+        if (outInfo) {
+            uint32_t* o = outInfo + 8 * i;
+            o[0] = p.m_lighMatrixIndex; o[1] = (uint32_t)p.m_shadowType; o[2] = p.m_numCasters; o[3] = (uint32_t)p.m_internalCommandsList.size();
+            for (int k = 0; k < 3; k++) o[4 + k] = k < (int)p.m_internalCommandsList.size() ? p.m_internalCommandsList[(size_t)k] : 0u;
+            o[7] = 0;
+        }
+        if (outMasks)
+            for (uint32_t w = 0; w < wordsPerMask; w++) outMasks[(size_t)i * wordsPerMask + w] = w < p.m_casterMask.size() ? p.m_casterMask[w] : 0ull;
+    }
+    return (int)passes.size();
+}
+
+// cascade map k of the runtime's LightingECS (m_csmShadowMaps, LightingECS.cpp:53-63): device pointer, size and SAILOR_SHADOWMAP_* format; null before the first
+// frame with caster data
+RT_API void* sailor_rt_csm_shadow_map(SailorRuntime* rt, int cascade, int* outSize, int* outFormat)
+{
+    if (!rt || cascade < 0 || (size_t)cascade >= rt->lighting->GetCsmShadowMaps().size()) return nullptr;
+    const auto& map = rt->lighting->GetCsmShadowMaps()[(size_t)cascade];
+    if (outSize) *outSize = map->GetExtent().x;
+    if (outFormat) *outFormat = map->m_format == EFormat::R16_SFLOAT ? SAILOR_SHADOWMAP_R16_SFLOAT : SAILOR_SHADOWMAP_R32G32B32A32_SFLOAT;
+    return map->m_buffer->m_hip.m_devicePtr;
+}
+
+// `lightsMatrices` of the lights set as the frames recorded so far left it: 4 x mat4 (a uniform block on this backend: its bytes live on the host)
+RT_API int sailor_rt_lights_matrices(SailorRuntime* rt, float* out64)
+{
+    auto b = rt && rt->lighting->GetLightsData() ? rt->lighting->GetLightsData()->Find("lightsMatrices") : RHIShaderBindingPtr();
+    if (!b || b->m_hostCopy.size() < 256 || !out64) return -1;
+    memcpy(out64, b->m_hostCopy.data(), 256);
+    return 0;
+}
+
+// LightingECS's pass planning without a renderer (no device needed): the host half of PrepareCSMPasses (LightingECS::PlanLightPasses) and the batches' runs
+// (LightingECS::CountBatchRuns) over overlap sets the caller supplies, with m_csmSnapshots carried from frame to frame by the planner.
+struct SailorCsmPlanner { SailorCsmSnapshots* snapshots = nullptr; };
+RT_API SailorCsmPlanner* sailor_rt_csm_planner_create() { return new SailorCsmPlanner(); }
+RT_API void sailor_rt_csm_planner_destroy(SailorCsmPlanner* planner)
+{
+    if (planner) sailor_host_csm_snapshots_destroy(planner->snapshots);
+    delete planner;
+}
+// One frame: numLights directional lights in component order (their shadow types, their SailorCsmView of this frame), overlapMasks = numLights x 4 x
+// ceil(numInstances / 64) words, batchRanges = numBatches x (firstInstance, instanceCount).  Per pass: outInfo 8 words {light, m_lighMatrixIndex, m_shadowType,
+// casters, dependencies, up to three dependency indices}, outMasks ceil(numInstances / 64) words, outRuns numBatches x (count, offset).  Returns the number of
+// passes (the first maxPasses are written), -1 on a bad argument.
+RT_API int sailor_rt_csm_planner_frame(SailorCsmPlanner* planner, uint32_t numLights, const uint32_t* lightShadowTypes, const SailorCsmView* views, uint32_t numInstances,
+                                       const uint64_t* overlapMasks, const uint64_t* lastChangedFrame, const uint64_t* castShadows, const uint32_t* batchRanges,
+                                       uint32_t numBatches, uint32_t maxPasses, uint32_t* outInfo, uint64_t* outMasks, uint32_t* outRuns)
+{
+    if (!planner || (numLights && (!lightShadowTypes || !views || !overlapMasks)) || (numInstances && !lastChangedFrame) || (numBatches && !batchRanges)) return -1;
+    const uint32_t numCsmSnapshots = numLights * LightingECS::NumCascades; // ECS/LightingECS.cpp:391-397
+    if (planner->snapshots && sailor_host_csm_snapshots_count(planner->snapshots) != numCsmSnapshots) { sailor_host_csm_snapshots_destroy(planner->snapshots); planner->snapshots = nullptr; }
+    if (!planner->snapshots) planner->snapshots = sailor_host_csm_snapshots_create();
+    if (!planner->snapshots) return -1;
+    const size_t words = ((size_t)numInstances + 63) / 64;
+    TVector<RHISceneBatch> batches(numBatches);
+    for (uint32_t b = 0; b < numBatches; b++) { batches[b].m_firstInstance = batchRanges[2 * b]; batches[b].m_instanceCount = batchRanges[2 * b + 1]; }
+    uint32_t placed = 0;
+    for (uint32_t light = 0; light < numLights; light++) {
+        const auto plans = LightingECS::PlanLightPasses(planner->snapshots, light * LightingECS::NumCascades, placed, numInstances,
+                                                        overlapMasks + (size_t)light * LightingECS::NumCascades * words, (EShadowType)lightShadowTypes[light],
+                                                        lastChangedFrame, views + light, castShadows);
+        for (const CsmPassPlan& plan : plans) {
+            if (placed < maxPasses) {
+                TVector<RHIShadowBatchRun> runs;
+                const uint32_t casters = LightingECS::CountBatchRuns(plan.m_casterMask, batches, runs);
+                if (outInfo) {
+                    uint32_t* o = outInfo + 8 * (size_t)placed;
+                    o[0] = light; o[1] = plan.m_cascade; o[2] = (uint32_t)plan.m_shadowType; o[3] = casters; o[4] = (uint32_t)plan.m_internalCommandsList.size();
+                    for (int k = 0; k < 3; k++) o[5 + k] = k < (int)plan.m_internalCommandsList.size() ? plan.m_internalCommandsList[(size_t)k] : 0u;
+                }
+                if (outMasks) memcpy(outMasks + (size_t)placed * words, plan.m_casterMask.data(), words * 8);
+                if (outRuns)
+                    for (uint32_t b = 0; b < numBatches; b++) { outRuns[((size_t)placed * numBatches + b) * 2] = runs[b].m_count; outRuns[((size_t)placed * numBatches + b) * 2 + 1] = runs[b].m_offset; }
+            }
+            placed++;
+        }
+    }
+    return (int)placed;
+}
+
 RT_API int sailor_rt_process_frame(SailorRuntime* rt)
 {
     static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver())->ClearExecutedRegions();
+    if (rt->lighting->HasCasterData()) { // FillLightingData's shadow half (ECS/LightingECS.cpp:377-401): the world's tick runs it before the frame is rendered
+        const int st = rt->lighting->FillShadowPasses(rt->snapshot);
+        if (st != SAILOR_HIP_OK) return st;
+    }
     rt->graph.Process(rt->snapshot);
     rt->frames++;
     return static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver())->GetLastDispatchStatus();
@@ -1016,6 +1147,10 @@ RT_API int sailor_rt_process_frame_overwriting_lists(SailorRuntime* rt, const vo
     auto commands = Renderer::GetDriverCommands();
     auto node = rt->lightCulling.DynamicCast<LightCullingNode>();
     if (!node) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (rt->lighting->HasCasterData()) { // as sailor_rt_process_frame: this frame's shadow passes, not the last one's
+        const int st = rt->lighting->FillShadowPasses(rt->snapshot);
+        if (st != SAILOR_HIP_OK) return st;
+    }
     auto transferCmdList = driver->CreateCommandList();
     auto cmdList = driver->CreateCommandList();
     rt->graph.FillFrameData(transferCmdList, rt->snapshot, rt->snapshot.m_deltaTime, rt->snapshot.m_currentTime);

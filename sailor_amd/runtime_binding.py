@@ -95,8 +95,53 @@ def load() -> C.CDLL:
         rt.sailor_rt_ecs_sweep.argtypes = [P, P, P, P, C.c_uint32, P, C.c_uint32, C.POINTER(P), C.POINTER(P), C.POINTER(P)]
         rt.sailor_rt_ecs_sweep_traced.argtypes = [P, P, P, P, C.c_uint32, P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(P), C.POINTER(P), C.POINTER(P),
                                                   C.POINTER(P)]
+        rt.sailor_rt_set_caster_data.argtypes = [P, P, C.c_uint32, P, P, P, C.c_uint32, C.c_uint32]
+        rt.sailor_rt_set_light_rotation.argtypes = [P, C.c_int, P]
+        rt.sailor_rt_shadow_passes.argtypes = [P, P, P, C.c_uint32, C.c_int]
+        rt.sailor_rt_csm_shadow_map.restype = P
+        rt.sailor_rt_csm_shadow_map.argtypes = [P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        rt.sailor_rt_lights_matrices.argtypes = [P, P]
+        rt.sailor_rt_csm_planner_create.restype = P
+        rt.sailor_rt_csm_planner_destroy.argtypes = [P]
+        rt.sailor_rt_csm_planner_frame.argtypes = [P, C.c_uint32, P, P, C.c_uint32, P, P, P, P, C.c_uint32, C.c_uint32, P, P, P]
         _rt = rt
     return _rt
+
+
+class CsmPlanner:
+    """LightingECS's pass planning without a device (sailor_rt_csm_planner_*): the host half of PrepareCSMPasses over overlap sets the caller supplies, with
+    the snapshots carried from frame to frame.  frame() returns one dict per pass: light, cascade (m_lighMatrixIndex), shadow_type, casters, dependencies
+    (m_internalCommandsList), mask (uint64 words) and runs (uint32 [batches, 2] = count, offset of the batch's run in the pass's slice of the SSBO)."""
+
+    def __init__(self):
+        self.rt = load()
+        self.h = self.rt.sailor_rt_csm_planner_create()
+
+    def close(self):
+        if self.h:
+            self.rt.sailor_rt_csm_planner_destroy(self.h)
+            self.h = None
+
+    def frame(self, light_shadow_types, views, num_instances: int, overlap_masks, last_changed_frame, cast_shadows=None, batch_ranges=()):
+        n = len(light_shadow_types)
+        words = (num_instances + 63) // 64
+        types = np.ascontiguousarray(light_shadow_types, np.uint32)
+        view_array = (_lib.CsmView * max(n, 1))(*views)
+        masks = np.ascontiguousarray(overlap_masks, np.uint64).reshape(n, 4, words)
+        frames = np.ascontiguousarray(last_changed_frame, np.uint64)
+        assert len(frames) == num_instances
+        cast = None if cast_shadows is None else np.ascontiguousarray(cast_shadows, np.uint64)
+        assert cast is None or len(cast) == words
+        ranges = np.ascontiguousarray(batch_ranges, np.uint32).reshape(-1, 2)
+        cap = 4 * max(n, 1)
+        info, out_masks, runs = np.zeros((cap, 8), np.uint32), np.zeros((cap, max(words, 1)), np.uint64), np.zeros((cap, max(len(ranges), 1), 2), np.uint32)
+        count = self.rt.sailor_rt_csm_planner_frame(self.h, n, types.ctypes.data, view_array, num_instances, masks.ctypes.data, frames.ctypes.data,
+                                                    None if cast is None else cast.ctypes.data, ranges.ctypes.data if len(ranges) else None, len(ranges), cap,
+                                                    info.ctypes.data, out_masks.ctypes.data, runs.ctypes.data)
+        if count < 0:
+            raise ValueError("sailor_rt_csm_planner_frame refused its arguments")
+        return [{"light": int(i[0]), "cascade": int(i[1]), "shadow_type": int(i[2]), "casters": int(i[3]), "dependencies": [int(d) for d in i[5:5 + int(i[4])]],
+                 "mask": out_masks[p, :words].copy(), "runs": runs[p, :len(ranges)].copy()} for p, i in enumerate(info[:count])]
 
 
 def parse_world(text: str):
@@ -381,6 +426,52 @@ class Runtime:
         fmts = (C.c_int * 4)(*formats)
         lm = np.ascontiguousarray(lights_matrices, np.float32).reshape(64)
         self.rt.sailor_rt_set_shadow_maps(self.h, ptrs, sizes, fmts, lm.ctypes.data)
+
+    def set_caster_data(self, world_aabb, last_changed_frames, cast_shadows=None, resolutions=None, trace: str | None = None, octree_root_size: int | None = None):
+        """The scene's caster data, after set_scene: world_aabb = float32 [n, 6] device tensor of the scene's instances' world boxes (the ECS sweep's output;
+        it must outlive the runtime's use of it), last_changed_frames = one frame number per instance, cast_shadows = m_bCastShadows as uint64 words or None
+        (every instance casts), resolutions = the four cascade maps' sizes or None (the reference's 4096), trace = "flat" | "octree" | None (as the runtime's
+        sweep system traces).  From then on process_frame() plans the cascades first and a ShadowPrepass node draws them.  world_aabb None takes it away."""
+        if world_aabb is None:
+            _lib.check(self.rt.sailor_rt_set_caster_data(self.h, None, 0, None, None, None, 0, 0), "sailor_rt_set_caster_data")
+            return
+        n = world_aabb.shape[0]
+        assert world_aabb.is_contiguous() and world_aabb.numel() * world_aabb.element_size() == 24 * n, tuple(world_aabb.shape)
+        frames = np.ascontiguousarray(last_changed_frames, np.uint64)
+        assert len(frames) == n
+        cast = None if cast_shadows is None else np.ascontiguousarray(cast_shadows, np.uint64)
+        assert cast is None or len(cast) == (n + 63) // 64
+        res = None if resolutions is None else (C.c_int * 4)(*[int(r) for r in resolutions])
+        mode = 0xFFFFFFFF if trace is None else _lib.trace_mode(trace)
+        _lib.check(self.rt.sailor_rt_set_caster_data(self.h, world_aabb.data_ptr(), n, None if cast is None else cast.ctypes.data, frames.ctypes.data, res, mode,
+                                                     0 if octree_root_size is None else octree_root_size), "sailor_rt_set_caster_data")
+
+    def set_light_rotation(self, index: int, rotation):
+        """the owner's rotation (x, y, z, w) of light `index`: with its position the transform whose inverse is the light's view matrix"""
+        q = np.ascontiguousarray(rotation, np.float32).reshape(4)
+        _lib.check(self.rt.sailor_rt_set_light_rotation(self.h, index, q.ctypes.data), "sailor_rt_set_light_rotation")
+
+    def shadow_passes(self, num_instances: int = 0):
+        """sceneView.m_shadowMapsToUpdate of the last process_frame(): one dict per pass -- cascade (m_lighMatrixIndex), shadow_type, casters, dependencies
+        (m_internalCommandsList) and, with num_instances, mask (the pass's caster set as uint64 words)"""
+        words = (num_instances + 63) // 64
+        info, masks = np.zeros((64, 8), np.uint32), np.zeros((64, max(words, 1)), np.uint64)
+        n = self.rt.sailor_rt_shadow_passes(self.h, info.ctypes.data, masks.ctypes.data if words else None, words, 64)
+        return [{"cascade": int(i[0]), "shadow_type": int(i[1]), "casters": int(i[2]), "dependencies": [int(d) for d in i[4:4 + int(i[3])]],
+                 "mask": masks[p, :words].copy()} for p, i in enumerate(info[:max(n, 0)])]
+
+    def csm_shadow_map(self, cascade: int):
+        """(device pointer, size, SAILOR_SHADOWMAP_* format) of cascade map `cascade` of the runtime's LightingECS; pointer None before it exists"""
+        size, fmt = C.c_int(0), C.c_int(0)
+        p = self.rt.sailor_rt_csm_shadow_map(self.h, cascade, C.byref(size), C.byref(fmt))
+        return p, size.value, fmt.value
+
+    def lights_matrices(self) -> np.ndarray:
+        """`lightsMatrices` of the lights set: float32 [4, 16]"""
+        out = np.zeros((4, 16), np.float32)
+        if self.rt.sailor_rt_lights_matrices(self.h, out.ctypes.data) != 0:
+            raise ValueError("the lights set has no lightsMatrices")
+        return out
 
     def set_frame_split(self, rank: int, world_size: int, comm=None):
         """this runtime renders tile-row band `rank` of `world_size`; per-pixel targets set afterwards hold the band's rows"""
