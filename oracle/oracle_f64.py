@@ -669,13 +669,40 @@ def _radical_inverse_vdc(i):
     return b.astype(np.float64) * 2.3283064365386963e-10
 
 
-def _sampling_vector(gx, gy, face, size):
-    """GetSamplingVector (ComputeIrradianceMap.shader / ComputeEnvMap_IBL.shader): the direction of output texel (gx, gy) of `face`"""
-    st = np.array([gx / size, gy / size])
-    uv = 2.0 * np.array([st[0], 1.0 - st[1]]) - 1.0
-    ret = [(1.0, uv[1], -uv[0]), (-1.0, uv[1], uv[0]), (uv[0], 1.0, -uv[1]), (uv[0], -1.0, uv[1]), (uv[0], uv[1], 1.0), (-uv[0], uv[1], -1.0)][face]
-    ret = np.array(ret, np.float64)
+# The laws of the bakes that a restatement could get wrong without a smooth sky noticing.  Every bake below takes `law`; tests/test_ibl_bake_cpu.py
+# flips one entry at a time and requires a named case of tests/ibl_bake_cases.py to see it.
+BAKE_LAW = dict(
+    lod_bias=1.0,            # ComputeEnvMap_IBL.shader: mip = max(0.5 * log2(ws / wt) + 1, 0)
+    texel_offset=0.0,        # GetSamplingVector: st = gl_GlobalInvocationID.xy / size -- the texel's CORNER, no + 0.5
+    swap_faces_2_3=False,    # the +Y / -Y rows of the sampling-vector table
+    swap_hammersley=False,   # SampleHammersley: (i / N, RadicalInverse_VdC(i)), in that order
+    cos_weight=True,         # the pre-filter weighs every sample with cosLi
+    equirect_pi=float(np.float32(3.141592)),  # ComputeEquirect2Cube.shader's own `const float PI = 3.141592`, as the float it is
+    force_lod=None,          # not a law: roughness 0 leaves the lod to 0 / 0 (see prefilter_env_level); a test pins either outcome with this
+)
+
+
+def _sampling_vector(gx, gy, face, size, law=BAKE_LAW):
+    """GetSamplingVector (ComputeIrradianceMap.shader / ComputeEnvMap_IBL.shader / ComputeEquirect2Cube.shader): the direction of output texel
+    (gx, gy) of `face`, NOT normalised; gx, gy may be arrays"""
+    o = law["texel_offset"]
+    ux, uy = 2.0 * ((gx + o) / size) - 1.0, 2.0 * (1.0 - (gy + o) / size) - 1.0
+    one = np.ones_like(ux)
+    table = [(one, uy, -ux), (-one, uy, ux), (ux, one, -uy), (ux, -one, uy), (ux, uy, one), (-ux, uy, -one)]
+    if law["swap_faces_2_3"]:
+        table[2], table[3] = table[3], table[2]
+    return np.stack(table[face], -1)
+
+
+def _texel_normal(gx, gy, face, size, law=BAKE_LAW):
+    ret = _sampling_vector(np.float64(gx), np.float64(gy), face, size, law)
     return ret / np.linalg.norm(ret)
+
+
+def _hammersley(num_samples, law=BAKE_LAW):
+    i = np.arange(num_samples)
+    u1, u2 = i / float(num_samples), _radical_inverse_vdc(i)
+    return (u2, u1) if law["swap_hammersley"] else (u1, u2)
 
 
 def _basis(N):
@@ -691,61 +718,161 @@ def _basis(N):
 TWO_PI = 2.0 * PI  # Constants.glsl (TwoPI = 2 * PI with Math.glsl's PI)
 
 
-def compute_irradiance_map(env_chain: np.ndarray, env_size: int, env_levels: int, size: int, num_samples: int = 64 * 1024) -> np.ndarray:
-    """ComputeIrradianceMap.shader main(): [6, size, size, 4] float64 (alpha 1)"""
-    levels_list = _cube_levels(env_chain, env_size, env_levels)
-    i = np.arange(num_samples)
-    u1, u2 = i / float(num_samples), _radical_inverse_vdc(i)          # SampleHammersley: (i * InvNumSamples, RadicalInverse_VdC(i))
+SEAM_TIE = 64 * 2.0 ** -24
+
+
+def cube_seam_spread(levels_list, d, lod):
+    """The canonical cube sampler filters INSIDE a face (clamp-to-edge), so textureLod jumps where the face changes, and a direction whose two largest
+    |components| tie picks its face by the last bit of a float evaluation.  For the directions d [n, 3] whose two largest |components| are within SEAM_TIE
+    (relative: the dozen float operations behind a sample direction, with room) this returns max - min, per channel, of textureLod over the faces such an
+    evaluation could pick -- each axis in turn nudged ahead of the others --; 0 for every other direction.  [n, 4].  What a bake may differ by on account
+    of its ties is the weighted sum of these, which its float64 restatement below returns on request."""
+    srt = np.sort(np.abs(d), axis=1)
+    idx = np.flatnonzero(srt[:, 2] - srt[:, 1] <= SEAM_TIE * srt[:, 2])
+    out = np.zeros((len(d), 4))
+    if idx.size:
+        cands = []
+        for k in range(3):
+            nudge = np.ones(3)
+            nudge[k] += 4.0 * SEAM_TIE
+            cands.append(cube_texture_lod(levels_list, d[idx] * nudge, lod[idx]))
+        out[idx] = np.max(cands, axis=0) - np.min(cands, axis=0)
+    return out
+
+
+def compute_irradiance_map(env_chain: np.ndarray, env_size: int, env_levels: int, size: int, num_samples: int = 64 * 1024, law=BAKE_LAW,
+                           want_spread: bool = False):
+    """ComputeIrradianceMap.shader main(): [6, size, size, 4] float64 (alpha 1); want_spread: also the share of each texel that rests on face ties
+    (cube_seam_spread), same shape"""
+    levels_list = _cube_levels(env_chain, env_size, env_levels)[:1]   # textureLod(envMap, Li, 0) is level 0 alone
+    spread = np.zeros((6, size, size, 4))
+    u1, u2 = _hammersley(num_samples, law)                             # SampleHammersley: (i * InvNumSamples, RadicalInverse_VdC(i))
     u1p = np.sqrt(np.maximum(0.0, 1.0 - u1 * u1))                      # SampleHemisphere(u1, u2)
     hemi = np.stack([np.cos(TWO_PI * u2) * u1p, np.sin(TWO_PI * u2) * u1p, u1], 1)
     out = np.zeros((6, size, size, 4))
     for face in range(6):
         for gy in range(size):
             for gx in range(size):
-                N = _sampling_vector(gx, gy, face, size)
+                N = _texel_normal(gx, gy, face, size, law)
                 S, T = _basis(N)
                 Li = hemi[:, 0:1] * S + hemi[:, 1:2] * T + hemi[:, 2:3] * N
                 cos_theta = np.maximum(0.0, Li @ N)
-                rgb = cube_texture_lod(levels_list, Li, np.zeros(num_samples))[:, :3]
+                f, s, t = _cube_face_st(Li)
+                rgb = _cube_bilinear(levels_list[0], f, s, t)[:, :3]
                 out[face, gy, gx, :3] = (2.0 * rgb * cos_theta[:, None]).sum(0) / num_samples
                 out[face, gy, gx, 3] = 1.0
-    return out
+                if want_spread:
+                    spread[face, gy, gx] = (2.0 * cube_seam_spread(levels_list, Li, np.zeros(num_samples)) * cos_theta[:, None]).sum(0) / num_samples
+    return (out, spread) if want_spread else out
 
 
-def prefilter_env_level(raw_chain: np.ndarray, size0: int, levels: int, level: int, roughness: float, num_samples: int = 1024) -> np.ndarray:
-    """ComputeEnvMap_IBL.shader main() for one output level: [6, s, s, 4] float64 with s = size0 >> level"""
+def prefilter_env_level(raw_chain: np.ndarray, size0: int, levels: int, level: int, roughness: float, num_samples: int = 1024, law=BAKE_LAW,
+                        want_spread: bool = False):
+    """ComputeEnvMap_IBL.shader main() for one output level: [6, s, s, 4] float64 with s = max(size0 >> level, 1); want_spread: also the share of each
+    texel that rests on face ties (cube_seam_spread), same shape.
+    The lod is max(0.5 * log2(ws / wt) + 1, 0) with a max that DROPS a NaN (fmaxf, which the kernel and the C oracle pin for GLSL's undefined case).  At
+    roughness 0 every sample has Lh = N and pdf = 0 / (PI * denom^2) with denom = 1 - dot(N, N)^2, a rounding residue: 0 / 0 = NaN -> lod 0 where
+    it is exactly zero, 0 / tiny = 0 -> ws = inf -> the last level where it is not.  Which of the two a texel gets is decided by the last bit of
+    dot(N, N) in the arithmetic at hand, so float64 cannot predict a float's choice: law["force_lod"] evaluates either outcome for all texels."""
     levels_list = _cube_levels(raw_chain, size0, levels)
     s_out = max(size0 >> level, 1)
     wt = 4.0 * PI / (6.0 * size0 * size0)
-    i = np.arange(num_samples)
-    u1, u2 = i / float(num_samples), _radical_inverse_vdc(i)
+    u1, u2 = _hammersley(num_samples, law)
     alpha = roughness * roughness                                       # SampleGGX (Lighting.glsl:27-37)
     cos_t = np.sqrt((1.0 - u2) / (1.0 + (alpha * alpha - 1.0) * u2))
     sin_t = np.sqrt(1.0 - cos_t * cos_t)
     phi = TWO_PI * u1
     ggx = np.stack([sin_t * np.cos(phi), sin_t * np.sin(phi), cos_t], 1)
-    out = np.zeros((6, s_out, s_out, 4))
+    alpha_sq = alpha * alpha                                            # NdfGGX (Lighting.glsl:41-48)
+    frames = [(N,) + _basis(N) for N in (_texel_normal(gx, gy, face, s_out, law) for face in range(6) for gy in range(s_out) for gx in range(s_out))]
+    N, S, T = (np.array([f[k] for f in frames])[:, None, :] for k in range(3))     # [texels, 1, 3]
+    out, spread = np.zeros((6 * s_out * s_out, 4)), np.zeros((6 * s_out * s_out, 4))
+    for lo in range(0, len(frames), 256):                               # a few hundred texels at a time: [texels, samples, 3]
+        n, s_, t_ = N[lo:lo + 256], S[lo:lo + 256], T[lo:lo + 256]
+        Lh = ggx[None, :, 0:1] * s_ + ggx[None, :, 1:2] * t_ + ggx[None, :, 2:3] * n
+        lh_n = (Lh * n).sum(-1)
+        Li = 2.0 * lh_n[..., None] * Lh - n                             # Lo = N
+        cos_li = (Li * n).sum(-1)
+        m = cos_li > 0.0                                                # the samples the shader keeps; the others get weight 0 below
+        cos_lh = np.maximum(lh_n, 0.0)
+        denom = cos_lh * cos_lh * (alpha_sq - 1.0) + 1.0
+        with np.errstate(divide="ignore", invalid="ignore"):
+            pdf = alpha_sq / (PI * denom * denom) * 0.25
+            ws = 1.0 / (num_samples * pdf)
+            mip = np.fmax(0.5 * np.log2(ws / wt) + law["lod_bias"], 0.0)
+        if law["force_lod"] is not None:
+            mip = np.full(mip.shape, float(law["force_lod"]))
+        mip = np.where(m, mip, 0.0)
+        d = np.where(m[..., None], Li, n)
+        w = np.where(m, cos_li if law["cos_weight"] else 1.0, 0.0)[..., None]
+        rgba = cube_texture_lod(levels_list, d.reshape(-1, 3), mip.reshape(-1)).reshape(d.shape[:2] + (4,))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out[lo:lo + 256] = np.where(m[..., None], rgba * w, 0.0).sum(1) / w.sum(1)
+            if want_spread:
+                sp = cube_seam_spread(levels_list, d.reshape(-1, 3), np.clip(mip, 0.0, levels - 1.0).reshape(-1)).reshape(d.shape[:2] + (4,))
+                spread[lo:lo + 256] = (sp * w).sum(1) / w.sum(1)
+    out[:, 3] = 1.0
+    out, spread = out.reshape(6, s_out, s_out, 4), spread.reshape(6, s_out, s_out, 4)
+    return (out, spread) if want_spread else out
+
+
+def equirect_taps(w: int, h: int, size: int, law=BAKE_LAW):
+    """ComputeEquirect2Cube.shader for every texel of a size x size x 6 cube: the unnormalised texel coordinates (px, py), each [6, size, size], at which
+    `texture(src, (phi / TwoPI, theta / PI))` reads a w x h image whose texel centres sit at i + 0.5.  The direction is taken from the texel's corner
+    through the face table; PI is the shader's own literal (a float), TwoPI = 2 * PI."""
+    pi = law["equirect_pi"]
+    gy, gx = np.meshgrid(np.arange(size, dtype=np.float64), np.arange(size, dtype=np.float64), indexing="ij")
+    px, py = np.zeros((6, size, size)), np.zeros((6, size, size))
     for face in range(6):
-        for gy in range(s_out):
-            for gx in range(s_out):
-                N = _sampling_vector(gx, gy, face, s_out)
-                S, T = _basis(N)
-                Lh = ggx[:, 0:1] * S + ggx[:, 1:2] * T + ggx[:, 2:3] * N
-                Li = 2.0 * (Lh @ N)[:, None] * Lh - N                   # Lo = N
-                cos_li = Li @ N
-                m = cos_li > 0.0
-                cos_lh = np.maximum(Lh[m] @ N, 0.0)
-                alpha_sq = alpha * alpha                                # NdfGGX (Lighting.glsl:41-48)
-                denom = cos_lh * cos_lh * (alpha_sq - 1.0) + 1.0
-                with np.errstate(divide="ignore", invalid="ignore"):
-                    pdf = alpha_sq / (PI * denom * denom) * 0.25
-                    ws = 1.0 / (num_samples * pdf)
-                    mip = np.maximum(0.5 * np.log2(ws / wt) + 1.0, 0.0)
-                rgb = cube_texture_lod(levels_list, Li[m], mip)[:, :3]
-                weight = cos_li[m].sum()
-                out[face, gy, gx, :3] = (rgb * cos_li[m][:, None]).sum(0) / weight
-                out[face, gy, gx, 3] = 1.0
+        v = _sampling_vector(gx, gy, face, size, law)
+        v = v / np.linalg.norm(v, axis=-1, keepdims=True)
+        phi, theta = np.arctan2(v[..., 2], v[..., 0]), np.arccos(np.clip(v[..., 1], -1.0, 1.0))
+        px[face], py[face] = phi / (2.0 * pi) * w - 0.5, theta / pi * h - 0.5
+    return px, py
+
+
+def equirect_to_cube(equirect: np.ndarray, size: int, repeat: bool = True, cover=None, out: np.ndarray | None = None, law=BAKE_LAW) -> np.ndarray:
+    """ComputeEquirect2Cube.shader main() over a float [h, w, 4] image -> float64 [6, size, size, 4].  The sampler is the Vulkan one at the base level
+    (a compute shader has no derivatives): four taps around (px, py), weights (1 - frac, frac), the tap indices wrapped (Repeat) or clamped to the
+    edge.  `cover` = (w, h): only texels with x < w and y < h are written, the rest keep what `out` held (zeros by default)."""
+    img = np.asarray(equirect, np.float64)
+    h, w = img.shape[:2]
+    px, py = equirect_taps(w, h, size, law)
+    fx, fy = np.floor(px), np.floor(py)
+    ax, ay = (px - fx)[..., None], (py - fy)[..., None]
+    x0, y0 = fx.astype(np.int64), fy.astype(np.int64)
+    x1, y1 = x0 + 1, y0 + 1
+    if repeat:
+        x0, x1, y0, y1 = x0 % w, x1 % w, y0 % h, y1 % h
+    else:
+        x0, x1, y0, y1 = np.clip(x0, 0, w - 1), np.clip(x1, 0, w - 1), np.clip(y0, 0, h - 1), np.clip(y1, 0, h - 1)
+    top = img[y0, x0] * (1.0 - ax) + img[y0, x1] * ax
+    bot = img[y1, x0] * (1.0 - ax) + img[y1, x1] * ax
+    full = top * (1.0 - ay) + bot * ay
+    out = np.zeros((6, size, size, 4)) if out is None else out
+    cw, ch = (size, size) if cover is None else (min(cover[0], size), min(cover[1], size))
+    out[:, :ch, :cw] = full[:, :ch, :cw]
     return out
+
+
+def generate_mipmaps_cube(level0: np.ndarray, size0: int, levels: int) -> np.ndarray:
+    """The 2:1 chain as include/sailor_hip.h states it for sailor_hip_generate_mipmaps_cube, in float32 and in its order of additions, so that a
+    compare is bit for bit: level l is max(size0 >> l, 1) wide, a texel is ((a + b) + (c + d)) * 0.25 over the 2 x 2 block under it, an odd source
+    drops its last row and column, a 1 x 1 source repeats.  -> the flat level-major RGBA32F chain"""
+    f32 = np.float32
+    src = np.ascontiguousarray(level0, f32).reshape(6, size0, size0, 4)
+    chain = [src.reshape(-1)]
+    with np.errstate(over="ignore", invalid="ignore"):
+        for l in range(1, levels):
+            ss, ds = src.shape[1], max(size0 >> l, 1)
+            if ss == 1:
+                a = b = c = d = src
+            else:
+                e = src[:, :2 * ds, :2 * ds]
+                a, b, c, d = e[:, 0::2, 0::2], e[:, 0::2, 1::2], e[:, 1::2, 0::2], e[:, 1::2, 1::2]
+            src = np.ascontiguousarray(((a + b) + (c + d)) * f32(0.25), f32)
+            chain.append(src.reshape(-1))
+    return np.concatenate(chain)
 
 
 def brdf_lut(w: int, h: int, num_samples: int = 1024) -> np.ndarray:

@@ -998,7 +998,9 @@ ORACLE_API void oracle_compute_irradiance_map(const float* env, int envSize, int
                     float Li[3], texel[4];
                     tangent_to_world(h, N, S, T, Li);
                     const float cosTheta = fmaxf(0.0f, (Li[0] * N[0] + Li[1] * N[1]) + Li[2] * N[2]);
-                    cube_sample_lod(env, envSize, envLevels, Li, 0.0f, texel);
+                    /* textureLod(envMap, Li, 0) reads level 0 alone: cube_sample_lod would add level 1 times a weight of exactly 0, the same number
+                     * for finite texels, but a NaN or an infinity in level 1 would reach the sum, which neither the shader nor the kernel lets it */
+                    cube_sample_level(env, envSize, 0, Li, texel);
                     for (int c = 0; c < 3; c++) irr[c] += (2.0f * texel[c]) * cosTheta;
                 }
                 float* o = out + (((size_t)face * size + y) * size + x) * 4;
