@@ -1611,6 +1611,103 @@ SAILOR_HIP_API int sailor_host_ui_flatten(const float displayPos[2], const float
                                           uint32_t numLists, const SailorUiDrawCmd* cmds, uint32_t numCmds, float outPushConstants[4], SailorUiCommand* outCommands,
                                           uint32_t maxCommands, uint32_t* outNumCommands, int32_t* outWidth, int32_t* outHeight);
 
+/* ---- ExperimentalParticles: update, shadow map, lit draw (particles.hip) ---------------------------------------------------------------------------
+ * Replaces: FrameGraph/ParticlesNode.cpp:184-257 -- the Dispatch of Content/Experimental/MeshParticles/ComputeParticles.shader:85-137 on the transfer
+ * list, the node-owned R32_SFLOAT shadow map drawn with Particle.shader under SHADOW_CASTER (ParticleShadow.mat), and the colour pass of Particle.shader
+ * (Particle.mat) into Main / DepthBuffer.
+ * Pinned:
+ *  1. Update.  frame = uint(mod(currentTime * float(fps), float(numFrames))), current = uint(mod(float(instanceId), float(traceFrames))) (GLSL's mod takes
+ *     floats: the uints are converted, as written at :100-101), mod(x, y) = x - y * floor(x / y), decay = pow(traceDecay, float(current)).  uint(f) is
+ *     the device's saturating conversion (NaN and negatives -> 0).  The two record indices (:106-107) are
+ *       (frame - current [- 1]) * numInstances / traceFrames + instanceId / traceFrames
+ *     in 32-bit UNSIGNED arithmetic that wraps.  `max(0, uintExpr)`: GLSL has max(int, int) and max(uint, uint) but no mixed form; the literal 0 is an int
+ *     and converts implicitly to uint (int -> uint is an implicit conversion, uint -> int is not), so the call resolves to max(uint, uint) and clamps
+ *     nothing.  A record index >= numRecords reads an ALL-ZERO record (what robust buffer access gives an SSBO load); the kernel never reads outside the
+ *     buffer.  So while frame < current + 1 -- the first frames of a loop -- a trail instance gets the zero record.
+ *  2. model = translate((p1 + p2) * 0.5) * rotation * scale, the two products as full 4 x 4 GLSL products (column j = ((c0 b0j + c1 b1j) + c2 b2j) + c3 b3j).
+ *     rotation = rotationMatrix(cross(up, dir), acos(dot(up, dir))) (:60-82) with up = (0, 0, 1), dir = normalize(p2 - p1), applied only if
+ *     length(axis) > 0, else the identity; scale = diag(s, s, distance(p2, p1), 1), s = size2 * decay * 1.5.  dot = (xx + yy) + zz, IEEE division and
+ *     square root, normalize(v) = v / sqrt(dot(v, v)); sinf, cosf, acosf, powf are the device library's.  Kept, not repaired: dir == +-up gives the
+ *     identity (-up is not flipped); p1 == p2 gives a NaN direction, a NaN axis, a false compare, the identity and a zz scale of 0; a zero record gives
+ *     an all-zero scale, so the instance draws nothing.
+ *  3. colorOld = (rgb2, a2 * decay) of the old record, color the same of the new one, isCulled = enabled > 0.5 ? 1 : 0 (no shader reads it).
+ *     materialInstance and the 8 bytes of padding are NOT written.
+ *  4. Shadow map.  The only attachment, no depth test: the LAST primitive in primitive order that covers a texel owns it, whatever its depth.
+ *     clip = (lightsMatrices[0] * model) * vec4(p, 1) (Particle.shader:125, GLSL's left-to-right product), then the rules of sailor_hip_raster_depth:
+ *     near-plane cut, flipped viewport, 1/256-texel snapping, 64-bit edge functions, top-left rule, cull Back, z by the raster formula, fragments outside
+ *     (0, 1] do not exist.  order = (instance * numTriangles + triangle) * 2 + part.  A key per texel, (order + 1) << 32 | depthBits, under an unsigned
+ *     maximum; a store pass writes the low word, an untouched texel is 0 (the clear value).
+ *  5. Colour pass.  Depth test and write against DepthBuffer, GreaterOrEqual in primitive order: the surface pass's key, depthBits << 32 | (order + 1),
+ *     seeded from the depth buffer; clip = projection * (view * (model * p)).  Varyings at the winning fragment by the surface pass's formula:
+ *     worldPosition = (model * p).xyz / w, color = color * (1 - a) + colorOld * a with a = (p.z + 1) / 2 (mix, :130), N = mat3(model) * inNormal
+ *     (tangentBasis * (0, 0, 1) is its third column: the first two meet zeros).  Fragment (:246-252): n = normalize(N), lighting = max(0, dot(-light[0].direction, n)),
+ *     shadow = ShadowCalculation_Pcf(map, lightsMatrices[0] * vec4(worldPosition, 1), 0.00001) (Lighting.glsl:242-261, :168-196: divide by w, all three
+ *     coordinates * 0.5 + 0.5, y flipped, 1 outside [0, 1]^2 or for z < 0.5, sixteen bilinear Clamp taps `.r * 0.5 + 0.5`, currentDepth + bias > pcfDepth),
+ *     rgb = color.rgb * max(0.05, min(lighting, shadow)), alpha the interpolated colour's.  Where a particle primitive owns the pixel, Main (RGBA32F) and
+ *     DepthBuffer are written; everything else in both is left as it was.
+ * Light record 0 and matrix 0 are read on the device.  All entry points record only (no allocation, no read-back, no wait: capturable); a refused call
+ * launches nothing, returns SAILOR_HIP_ERR_INVALID_ARGUMENT and leaves its text in last_error. */
+
+/* ParticlesNode.h:44-51 ParticleData == ComputeParticles.shader:20-27.  80 bytes. */
+typedef struct SailorParticleData {
+    float enabled, size1, size2, _nouse; /*  0 */
+    float xyz1[3], _w1;                  /* 16 */
+    float rgba1[4];                      /* 32 */
+    float xyz2[3], _w2;                  /* 48 */
+    float rgba2[4];                      /* 64 */
+} SailorParticleData;
+
+/* ParticlesNode.h:62-71 PerInstanceData == Particle.shader:34-41, std430.  112 bytes. */
+typedef struct SailorParticleInstance {
+    float model[16];            /*   0 */
+    float color[4];             /*  64 */
+    float colorOld[4];          /*  80 */
+    uint32_t materialInstance;  /*  96 */
+    uint32_t isCulled;          /* 100 */
+    uint32_t _pad[2];           /* 104 */
+} SailorParticleInstance;
+
+/* ParticlesNode.h:53-60 PushConstants == ComputeParticles.shader:51-58.  20 bytes. */
+typedef struct SailorParticlesConstants {
+    uint32_t numInstances; /*  0 */
+    uint32_t numFrames;    /*  4 */
+    uint32_t fps;          /*  8 */
+    uint32_t traceFrames;  /* 12 */
+    float traceDecay;      /* 16 */
+} SailorParticlesConstants;
+
+/* the particle mesh (BindVertexBuffer / BindIndexBuffer / DrawIndexed of ParticlesNode.cpp:223-225, :254-256), drawn numInstances times */
+typedef struct SailorParticlesDraw {
+    const SailorVertexP3N3T3B3UV2C4* dVertices; /* device, already offset by vertexOffset */
+    const uint32_t* dIndices;                   /* device, 3 x numTriangles, already offset by firstIndex */
+    uint32_t numTriangles;
+    uint32_t _pad;
+} SailorParticlesDraw;
+
+/* Replaces: Dispatch(256, 1, 1) of ComputeParticles.shader (ParticlesNode.cpp:192): k_particles_update, a lane per instance (the shader's 256-thread
+ * partition is not observable).  frame: currentTime is read.  dRecords: device, numRecords records (16-byte aligned); dInstances: device,
+ * constants->numInstances instances.  Refused: NULL / misaligned pointers, overlapping buffers, numInstances, traceFrames or numFrames == 0, numInstances above 2^31 - 1,
+ * traceDecay not finite or not > 0, currentTime * fps not finite or negative. */
+SAILOR_HIP_API int sailor_hip_particles_update(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorParticlesConstants* constants,
+                                               const SailorParticleData* dRecords, uint32_t numRecords, SailorParticleInstance* dInstances);
+/* the workspace both passes use, one after the other: a 64-bit key per texel of the larger of the map and the frame; 0 = invalid extents */
+SAILOR_HIP_API size_t sailor_hip_particles_workspace_bytes(int32_t mapWidth, int32_t mapHeight, int32_t width, int32_t height);
+/* Replaces: the shadow pass of ParticlesNode.cpp:196-229: k_particles_seed (keys = 0), k_particles_cast, k_particles_store_map.
+ *   dLightsMatrices : device, matrix 0 is read       dShadowMap : device out, mapWidth x mapHeight floats, every texel written
+ * Refused besides the above: a map that overlaps the instances or the workspace, numInstances == 0, numTriangles == 0, extents outside 1 .. 32768,
+ * numInstances * 2 * numTriangles reaching 2^32 - 1, a workspace smaller than 8 * mapWidth * mapHeight bytes. */
+SAILOR_HIP_API int sailor_hip_particles_shadow(SailorHipContext* ctx, const SailorParticlesDraw* draw, const SailorParticleInstance* dInstances, uint32_t numInstances,
+                                               const float* dLightsMatrices, float* dShadowMap, int32_t mapWidth, int32_t mapHeight, void* dWorkspace,
+                                               size_t workspaceBytes);
+/* Replaces: the colour pass of ParticlesNode.cpp:232-257: k_particles_seed (keys = depth bits << 32), k_particles_visibility, k_particles_resolve.
+ *   frame : view and projection are read      dLights : device, record 0 is read      dShadowMap : device, what sailor_hip_particles_shadow wrote
+ *   dMain : device in / out, width x height float4       dDepth : device in / out, width x height floats
+ * Refused as above, with dMain / dDepth against the map, the instances and the workspace, and a workspace smaller than 8 * width * height bytes. */
+SAILOR_HIP_API int sailor_hip_particles_draw(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorParticlesDraw* draw,
+                                             const SailorParticleInstance* dInstances, uint32_t numInstances, const SailorLightShaderData* dLights,
+                                             const float* dLightsMatrices, const float* dShadowMap, int32_t mapWidth, int32_t mapHeight, float* dMain,
+                                             float* dDepth, int32_t width, int32_t height, void* dWorkspace, size_t workspaceBytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -260,6 +260,30 @@ GLTF_MATERIAL_DTYPE = [("baseColorFactor", "<f4", 4), ("emissiveFactor", "<f4", 
                        ("occlusionStrength", "<f4"), ("normalScale", "<f4"), ("alphaCutoff", "<f4"), ("baseColorSampler", "<u4"), ("normalSampler", "<u4"),
                        ("ormSampler", "<u4"), ("occlusionSampler", "<u4"), ("emissiveSampler", "<u4"), ("_pad", "<u4", 2)]
 
+class ParticleData(C.Structure):  # include/sailor_hip.h SailorParticleData (ParticlesNode.h:44-51)
+    _fields_ = [("enabled", C.c_float), ("size1", C.c_float), ("size2", C.c_float), ("_nouse", C.c_float), ("xyz1", C.c_float * 3), ("_w1", C.c_float),
+                ("rgba1", C.c_float * 4), ("xyz2", C.c_float * 3), ("_w2", C.c_float), ("rgba2", C.c_float * 4)]
+
+
+class ParticleInstance(C.Structure):  # include/sailor_hip.h SailorParticleInstance (ParticlesNode.h:62-71, std430)
+    _fields_ = [("model", C.c_float * 16), ("color", C.c_float * 4), ("colorOld", C.c_float * 4), ("materialInstance", C.c_uint32), ("isCulled", C.c_uint32),
+                ("_pad", C.c_uint32 * 2)]
+
+
+class ParticlesConstants(C.Structure):  # include/sailor_hip.h SailorParticlesConstants (ParticlesNode.h:53-60)
+    _fields_ = [("numInstances", C.c_uint32), ("numFrames", C.c_uint32), ("fps", C.c_uint32), ("traceFrames", C.c_uint32), ("traceDecay", C.c_float)]
+
+
+class ParticlesDraw(C.Structure):  # include/sailor_hip.h SailorParticlesDraw: the particle mesh
+    _fields_ = [("dVertices", C.c_void_p), ("dIndices", C.c_void_p), ("numTriangles", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+PARTICLE_DATA_DTYPE = [("enabled", "<f4"), ("size1", "<f4"), ("size2", "<f4"), ("_nouse", "<f4"), ("xyz1", "<f4", 3), ("_w1", "<f4"), ("rgba1", "<f4", 4),
+                       ("xyz2", "<f4", 3), ("_w2", "<f4"), ("rgba2", "<f4", 4)]  # SailorParticleData, 80 bytes
+PARTICLE_INSTANCE_DTYPE = [("model", "<f4", 16), ("color", "<f4", 4), ("colorOld", "<f4", 4), ("materialInstance", "<u4"), ("isCulled", "<u4"),
+                           ("_pad", "<u4", 2)]  # SailorParticleInstance, 112 bytes
+assert C.sizeof(ParticleData) == 80 and C.sizeof(ParticleInstance) == 112 and C.sizeof(ParticlesConstants) == 20 and C.sizeof(ParticlesDraw) == 24
+
 assert C.sizeof(VertexP3N3T3B3UV2C4) == 72 and C.sizeof(MaterialData) == 80 and C.sizeof(GltfMaterialData) == 80
 assert C.sizeof(TextureDesc) == 24 and C.sizeof(SurfaceDraw) == 48
 assert C.sizeof(UboFrameData) == 232 and C.sizeof(LightCullPushConstants) == 88 and C.sizeof(LightShaderData) == 112
@@ -458,6 +482,11 @@ SIGNATURES = {
     "sailor_host_ui_flatten": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(UiDrawList), C.c_uint32, C.POINTER(UiDrawCmd),
                                          C.c_uint32, C.POINTER(C.c_float), C.POINTER(UiCommand), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_int32),
                                          C.POINTER(C.c_int32)]),
+    "sailor_hip_particles_update": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(ParticlesConstants), _P, C.c_uint32, _P]),
+    "sailor_hip_particles_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "sailor_hip_particles_shadow": (C.c_int, [_P, C.POINTER(ParticlesDraw), _P, C.c_uint32, _P, _P, C.c_int32, C.c_int32, _P, C.c_size_t]),
+    "sailor_hip_particles_draw": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(ParticlesDraw), _P, C.c_uint32, _P, _P, _P, C.c_int32, C.c_int32, _P, _P,
+                                            C.c_int32, C.c_int32, _P, C.c_size_t]),
 }
 
 _lib = None

@@ -41,27 +41,14 @@ __device__ __forceinline__ bool surf_top_left(long long ax, long long ay, long l
     return (dy == 0 && dx > 0) || dy < 0;
 }
 
-// raster_setup of raster.hip (hasView form: clip = projection * (view * (model * position)), DepthOnly.shader:51 == Standard.shader:131) over interleaved
-// vertices; rows [rowBegin, rowEnd) of the frame only.  S reports the vertices' sources for the varyings (dead code where it is not read).
-__device__ __forceinline__ SurfTri surface_setup(const Mat4& P, const Mat4& V, const float* __restrict__ model, const float* __restrict__ vertices,
-                                                 const uint32_t* __restrict__ tri, int W, int H, int rowBegin, int rowEnd, bool cullBack, int part, bool& hasSecond,
-                                                 SurfSrc& S)
+// raster_setup of raster.hip from the clip positions c[0..2] of the triangle's vertices v0, v1, v2 on: the near-plane cut, the snap, the cull and the box;
+// rows [rowBegin, rowEnd) of the frame only.  S reports the vertices' sources for the varyings (dead code where it is not read).
+__device__ __forceinline__ SurfTri surface_setup_clip(float4 (&c)[3], const uint32_t v0, const uint32_t v1, const uint32_t v2, int W, int H, int rowBegin, int rowEnd,
+                                                      bool cullBack, int part, bool& hasSecond, SurfSrc& S)
 {
     SurfTri t;
     t.valid = false;
     hasSecond = false;
-    float4 c[3];
-    const uint32_t v0 = tri[0], v1 = tri[1], v2 = tri[2];
-    Mat4 M;
-#pragma unroll
-    for (int q = 0; q < 16; q++) M.m[q] = model[q];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const float* p = vertices + SURF_VERTEX_FLOATS * (size_t)(k == 0 ? v0 : (k == 1 ? v1 : v2)) + 2;
-        const float4 a = glsl_mul(M, p[0], p[1], p[2], 1.0f);
-        const float4 bq = glsl_mul(V, a.x, a.y, a.z, a.w);
-        c[k] = glsl_mul(P, bq.x, bq.y, bq.z, bq.w);
-    }
     S.I[0] = v0; S.I[1] = v1; S.I[2] = v2;
     S.O[0] = v0; S.O[1] = v1; S.O[2] = v2;
     S.t[0] = S.t[1] = S.t[2] = 0.0f;
@@ -134,6 +121,40 @@ __device__ __forceinline__ SurfTri surface_setup(const Mat4& P, const Mat4& V, c
     t.i0 = (int)i0; t.i1 = (int)i1; t.j0 = (int)j0; t.j1 = (int)j1;
     t.valid = true;
     return t;
+}
+
+// hasView form: clip = projection * (view * (model * position)) (DepthOnly.shader:51 == Standard.shader:131) over interleaved vertices
+__device__ __forceinline__ SurfTri surface_setup(const Mat4& P, const Mat4& V, const float* __restrict__ model, const float* __restrict__ vertices,
+                                                 const uint32_t* __restrict__ tri, int W, int H, int rowBegin, int rowEnd, bool cullBack, int part, bool& hasSecond,
+                                                 SurfSrc& S)
+{
+    float4 c[3];
+    const uint32_t v0 = tri[0], v1 = tri[1], v2 = tri[2];
+    Mat4 M;
+#pragma unroll
+    for (int q = 0; q < 16; q++) M.m[q] = model[q];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const float* p = vertices + SURF_VERTEX_FLOATS * (size_t)(k == 0 ? v0 : (k == 1 ? v1 : v2)) + 2;
+        const float4 a = glsl_mul(M, p[0], p[1], p[2], 1.0f);
+        const float4 bq = glsl_mul(V, a.x, a.y, a.z, a.w);
+        c[k] = glsl_mul(P, bq.x, bq.y, bq.z, bq.w);
+    }
+    return surface_setup_clip(c, v0, v1, v2, W, H, rowBegin, rowEnd, cullBack, part, hasSecond, S);
+}
+
+// one matrix: clip = LM * position (a caster draw: LM = lightMatrix * model, raster.hip's form without a view)
+__device__ __forceinline__ SurfTri surface_setup_matrix(const Mat4& LM, const float* __restrict__ vertices, const uint32_t* __restrict__ tri, int W, int H, int rowBegin,
+                                                        int rowEnd, bool cullBack, int part, bool& hasSecond, SurfSrc& S)
+{
+    float4 c[3];
+    const uint32_t v0 = tri[0], v1 = tri[1], v2 = tri[2];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const float* p = vertices + SURF_VERTEX_FLOATS * (size_t)(k == 0 ? v0 : (k == 1 ? v1 : v2)) + 2;
+        c[k] = glsl_mul(LM, p[0], p[1], p[2], 1.0f);
+    }
+    return surface_setup_clip(c, v0, v1, v2, W, H, rowBegin, rowEnd, cullBack, part, hasSecond, S);
 }
 
 __device__ __forceinline__ long long surf_bcast64(long long v, int src)

@@ -133,6 +133,39 @@ def bloom_params(**values) -> "_lib.BloomParams":
     return _lib.BloomParams(**{k: float(x) for k, x in v.items()})
 
 
+def particles_constants(num_particles: int, num_frames: int, fps: int, trace_frames: int, trace_decay: float) -> "_lib.ParticlesConstants":
+    """ParticlesNode.cpp:184-189: the push constants of the update Dispatch; numInstances = n * traceFrames (:130-154)"""
+    return _lib.ParticlesConstants(numInstances=int(num_particles) * int(trace_frames), numFrames=int(num_frames), fps=int(fps), traceFrames=int(trace_frames),
+                                   traceDecay=float(trace_decay))
+
+
+def pack_particles(enabled, size1, size2, xyz1, rgba1, xyz2, rgba2) -> np.ndarray:
+    """arrays over the records -> SailorParticleData records (_lib.PARTICLE_DATA_DTYPE, 80 bytes each); the two unused words are 0"""
+    n = len(np.atleast_1d(enabled))
+    r = np.zeros(n, dtype=_lib.PARTICLE_DATA_DTYPE)
+    r["enabled"], r["size1"], r["size2"] = enabled, size1, size2
+    r["xyz1"], r["rgba1"] = np.asarray(xyz1, np.float32).reshape(n, 3), np.asarray(rgba1, np.float32).reshape(n, 4)
+    r["xyz2"], r["rgba2"] = np.asarray(xyz2, np.float32).reshape(n, 3), np.asarray(rgba2, np.float32).reshape(n, 4)
+    return r
+
+
+def particle_instances(records: np.ndarray, num_particles: int, trace_frames: int, material_instance: int = 0) -> np.ndarray:
+    """ParticlesNode.cpp:130-152: the instance buffer as the node builds it once on the host (_lib.PARTICLE_INSTANCE_DTYPE): instance i belongs to particle
+    i // traceFrames; model = translate(x2, y2, z2) * scale(size2), color = 1, colorOld = 0, materialInstance set"""
+    n = int(num_particles) * int(trace_frames)
+    inst = np.zeros(n, dtype=_lib.PARTICLE_INSTANCE_DTYPE)
+    j = np.arange(n) // int(trace_frames)
+    m = np.zeros((n, 4, 4), np.float32)  # [column][row]
+    s = records["size2"][j]
+    m[:, 0, 0] = m[:, 1, 1] = m[:, 2, 2] = s
+    m[:, 3, :3] = records["xyz2"][j]
+    m[:, 3, 3] = 1.0
+    inst["model"] = m.reshape(n, 16)
+    inst["color"] = 1.0
+    inst["materialInstance"] = material_instance
+    return inst
+
+
 def bloom_push_constants(threshold: float, knee: float) -> np.ndarray:
     """BloomNode.cpp:89-93: u_threshold = (t, t - knee, 2 knee, 0.25 knee) as float32[4]"""
     out = np.empty(4, np.float32)

@@ -6,6 +6,7 @@
 #include "DepthPrepassNode.h"
 #include "ShadowPrepassNode.h"
 #include "ClearNode.h"
+#include "ParticlesNode.h"
 #include "RHIFrameGraph.h"
 #include "../RHI/Renderer.h"
 #include "../RHI/DebugContext.h"
@@ -39,6 +40,7 @@ FrameGraphNodePtr FrameGraphBuilder::CreateOptInNode(const std::string& nodeName
     if (nodeName == BloomNode::GetName()) return FrameGraphNodePtr(new BloomNode());
     if (nodeName == ShadowPrepassNode::GetName()) return FrameGraphNodePtr(new ShadowPrepassNode());
     if (nodeName == ClearNode::GetName()) return FrameGraphNodePtr(new ClearNode());
+    if (nodeName == ParticlesNode::GetName()) return FrameGraphNodePtr(new ParticlesNode());
     return FrameGraphNodePtr();
 }
 
@@ -1357,3 +1359,113 @@ void ShadowPrepassNode::Clear() // (:370-376)
     m_masks.Clear();
     m_positions.clear();
 }
+
+// ---- ParticlesNode (FrameGraph/ParticlesNode.cpp:22-264) ------------------------------------------------------------------------------------------
+const char* ParticlesNode::m_name = "ExperimentalParticles";
+
+void ParticlesNode::SetParticles(const Header& header, std::vector<ParticleData> records, RHIBufferPtr vertexBuffer, RHIBufferPtr indexBuffer, uint32_t indexCount,
+                                 uint32_t materialInstance)
+{
+    m_particlesHeader = header;
+    m_particlesHeader.m_bIsLoaded = true; // (:48-51)
+    m_particlesDataBinary = std::move(records);
+    m_vertexBuffer = vertexBuffer; m_indexBuffer = indexBuffer; m_indexCount = indexCount; m_materialInstance = materialInstance;
+    m_instances.Clear(); m_particlesFrames.Clear(); m_perInstanceData.Clear(); m_numInstances = 0; // (built again from the new records)
+}
+
+void ParticlesNode::Process(RHIFrameGraphPtr frameGraph, RHICommandListPtr transferCommandList, RHICommandListPtr commandList, const RHISceneViewSnapshot& sceneView)
+{
+    auto driver = Renderer::GetDriver();
+    auto commands = Renderer::GetDriverCommands();
+    std::string particlesPath;
+    if (!m_particlesHeader.m_bIsLoaded || !TryGetString("particlesData", particlesPath)) return; // (:35-57) nothing loaded: silently
+    if (!m_shadowMap) { // (:59-70) Linear, Clamp; 4096 x 4096 there
+        m_shadowMap = driver->CreateRenderTarget(m_shadowMapExtent, 1, EFormat::R32_SFLOAT);
+        m_shadowMapBinding = driver->CreateShaderBindings();
+        driver->AddSamplerToShaderBindings(m_shadowMapBinding, "shadowMapSampler", m_shadowMap, 0);
+    }
+    if (!m_material || !m_shadowMaterial) { // (:72-105)
+        std::string particleModel, particleShadowMaterial;
+        if (!TryGetString("particleModel", particleModel)) return;
+        if (!TryGetString("particleShadowMaterial", particleShadowMaterial)) return;
+        if (!m_vertexBuffer || !m_indexBuffer || m_indexCount < 3) return; // m_mesh
+        // Particle.mat / ParticleShadow.mat: Particle.shader without and with SHADOW_CASTER, cull Back, no blending; depth test and write for the first only
+        m_material = driver->CreateMaterial(driver->CreateShader("Experimental/MeshParticles/Particle.shader"));
+        m_shadowMaterial = driver->CreateMaterial(driver->CreateShader("Experimental/MeshParticles/Particle.shader", { "SHADOW_CASTER" }));
+    }
+    if (!m_pComputeShader) m_pComputeShader = driver->CreateShader("Experimental/MeshParticles/ComputeParticles.shader"); // (:107-113)
+    if (!m_shadowMap || !m_material || !m_material->m_shader->IsReady() || !m_shadowMaterial || !m_shadowMaterial->m_shader->IsReady() || !m_pComputeShader->IsReady())
+        return; // (:115-118)
+    if (!m_instances) { // (:120-164) once, on the host
+        const uint32_t count = m_particlesHeader.m_n * m_particlesHeader.m_traceFrames;
+        if (count == 0 || m_particlesDataBinary.size() < m_particlesHeader.m_n) return;
+        std::vector<PerInstanceData> instances(count);
+        for (uint32_t i = 0; i < count; i++) {
+            const ParticleData& p = m_particlesDataBinary[i / m_particlesHeader.m_traceFrames];
+            PerInstanceData inst {};
+            inst.model[0] = inst.model[5] = inst.model[10] = p.size2; // Transform { position (x2, y2, z2), scale size2 }.Matrix()
+            inst.model[12] = p.xyz2[0]; inst.model[13] = p.xyz2[1]; inst.model[14] = p.xyz2[2]; inst.model[15] = 1.0f;
+            inst.materialInstance = m_materialInstance;
+            inst.color[0] = inst.color[1] = inst.color[2] = inst.color[3] = 1.0f;
+            instances[i] = inst;
+        }
+        m_numInstances = count;
+        m_perInstanceData = driver->CreateShaderBindings();
+        auto data = driver->AddSsboToShaderBindings(m_perInstanceData, "data", sizeof(PerInstanceData), count, 0);
+        auto frames = driver->AddSsboToShaderBindings(m_perInstanceData, "particlesData", sizeof(ParticleData), m_particlesDataBinary.size(), 1);
+        m_instances = data ? data->m_buffer : RHIBufferPtr();
+        m_particlesFrames = frames ? frames->m_buffer : RHIBufferPtr();
+        if (!m_instances || !m_particlesFrames) { m_instances.Clear(); return; }
+        // (CreateBuffer_Immediate there; here the uploads are recorded in front of the Dispatch on the same list)
+        commands->UpdateBuffer(transferCommandList, m_instances, instances.data(), instances.size() * sizeof(PerInstanceData));
+        commands->UpdateBuffer(transferCommandList, m_particlesFrames, m_particlesDataBinary.data(), m_particlesDataBinary.size() * sizeof(ParticleData));
+        m_particlesDataBinary.clear(); // (:163)
+    }
+    auto resolved = [&](const char* name) -> RHITexturePtr {
+        if (auto t = GetRHIResource(name).DynamicCast<RHITexture>()) return t;
+        auto it = m_unresolvedResourceParams.find(name);
+        return it == m_unresolvedResourceParams.end() ? RHITexturePtr() : frameGraph->GetRenderTarget(it->second);
+    };
+    RHITexturePtr colorAttachment = resolved("color"), depthAttachment = resolved("depthStencil"); // (:166-171)
+    if (!depthAttachment) depthAttachment = frameGraph->GetRenderTarget("DepthBuffer");
+    if (!colorAttachment || !depthAttachment) return;
+    // (:173-175; the material's own set and the texture samplers hold nothing Particle.shader reads)
+    TVector<RHIShaderBindingSetPtr> sets({ sceneView.m_frameBindings, sceneView.m_rhiLightsData, m_perInstanceData, m_shadowMapBinding });
+    TVector<RHIShaderBindingSetPtr> computeSets({ m_perInstanceData, sceneView.m_frameBindings });
+    PushConstants constants {}; // (:184-189)
+    constants.numInstances = m_numInstances;
+    constants.numFrames = m_particlesHeader.m_frames;
+    constants.fps = m_particlesHeader.m_fps;
+    constants.traceFrames = m_particlesHeader.m_traceFrames;
+    constants.traceDecay = m_particlesHeader.m_traceDecay;
+    commands->BeginDebugRegion(transferCommandList, GetName()); // (:191-193)
+    commands->Dispatch(transferCommandList, m_pComputeShader, 256, 1, 1, computeSets, &constants, sizeof(constants));
+    commands->EndDebugRegion(transferCommandList);
+
+    commands->BeginDebugRegion(commandList, GetName()); // (:196) Shadows
+    {
+        commands->ImageMemoryBarrier(commandList, m_shadowMap, EImageLayout::ColorAttachmentOptimal);
+        const ivec2 extent = m_shadowMap->GetExtent();
+        commands->BeginRenderPass(commandList, TVector<RHITexturePtr> { m_shadowMap }, RHITexturePtr(), true); // (:203-212) the only attachment, cleared to 0
+        commands->BindMaterial(commandList, m_shadowMaterial);
+        commands->SetViewport(commandList, 0.0f, (float)extent.y, (float)extent.x, -(float)extent.y, { 0, 0 }, extent, 0.0f, 1.0f); // (:215-220) flipped
+        commands->BindShaderBindings(commandList, m_material, sets);
+        commands->BindVertexBuffer(commandList, m_vertexBuffer, 0);
+        commands->BindIndexBuffer(commandList, m_indexBuffer, 0);
+        commands->DrawIndexed(commandList, m_indexCount, m_numInstances, 0, 0, 0);
+        commands->EndRenderPass(commandList);
+        commands->ImageMemoryBarrier(commandList, m_shadowMap, EImageLayout::ShaderReadOnlyOptimal);
+    }
+    commands->BeginRenderPass(commandList, TVector<RHITexturePtr> { colorAttachment }, depthAttachment, false); // (:232-240)
+    const ivec2 extent = colorAttachment->GetExtent();
+    commands->BindMaterial(commandList, m_material);
+    commands->SetViewport(commandList, 0.0f, (float)extent.y, (float)extent.x, -(float)extent.y, { 0, 0 }, extent, 0.0f, 1.0f);
+    commands->BindShaderBindings(commandList, m_material, sets);
+    commands->BindVertexBuffer(commandList, m_vertexBuffer, 0);
+    commands->BindIndexBuffer(commandList, m_indexBuffer, 0);
+    commands->DrawIndexed(commandList, m_indexCount, m_numInstances, 0, 0, 0);
+    commands->EndRenderPass(commandList);
+    commands->EndDebugRegion(commandList); // (:259)
+}
+
+void ParticlesNode::Clear() {} // (:262-264)

@@ -116,6 +116,10 @@ RHIShaderPtr HipGraphicsDriver::CreateShader(const std::string& assetPath, const
                              (defines.empty() || (defines.size() == 1 && (defines[0] == "AO" || defines[0] == "LIGHT_TILES" || defines[0] == "CASCADES")));
     // The first and the last draw of SkyNode's "Stars & Clouds" (SkyNode.cpp:692-747), likewise opt-in: the Sky and clouds tests record a frame without them
     if (assetPath == "Shaders/Stars.shader" || assetPath == "Shaders/SunShafts.shader") shader->m_bIsReady = IsShaderEnabled(assetPath);
+    // ParticlesNode's shaders: the compute shader has no permutation; Particle.shader is routed by its define set, {} (Particle.mat) and {SHADOW_CASTER}
+    // (ParticleShadow.mat)
+    if (assetPath == "Experimental/MeshParticles/ComputeParticles.shader") shader->m_bIsReady = defines.empty();
+    if (assetPath == "Experimental/MeshParticles/Particle.shader") shader->m_bIsReady = defines.empty() || (defines.size() == 1 && defines[0] == "SHADOW_CASTER");
     return shader;
 }
 
@@ -682,6 +686,7 @@ void HipGraphicsDriver::Dispatch(RHICommandListPtr cmd, RHIShaderPtr computeShad
         if (name == "Shaders/ComputeEnvMap_IBL.shader") return RecordEnvPrefilter(bindings, pc);
         if (name == "Shaders/ComputeBloomDownscale.shader") return RecordBloomDownscale(bindings, pc);
         if (name == "Shaders/ComputeBloomUpscale.shader") return RecordBloomUpscale(bindings, pc);
+        if (name == "Experimental/MeshParticles/ComputeParticles.shader") return RecordParticlesUpdate(bindings, pc);
         return (int)SAILOR_HIP_ERR_UNSUPPORTED;
     });
 }
@@ -1238,6 +1243,17 @@ void HipGraphicsDriver::DrawIndexed(RHICommandListPtr cmd, uint32_t indexCount, 
         if (flags & SAILOR_SURFACE_GLTF) cmd->m_surfaceGltf = true;
         cmd->m_hip.m_commands.push_back([this, bindings, color, depth, vb, ib, drawIndex, indexCount, instanceCount, firstIndex, vertexOffset, firstInstance, flags]() {
             return RecordSurfaceDraw(bindings, color, depth, vb, ib, drawIndex == 0, drawIndex, indexCount, instanceCount, firstIndex, vertexOffset, firstInstance, flags);
+        });
+        return;
+    }
+    if (name == "Experimental/MeshParticles/Particle.shader" && cmd->m_boundMaterial->m_shader->IsReady()) { // ParticlesNode.cpp:225 (the map) and :256 (the colour pass)
+        RHITexturePtr color = cmd->m_colorAttachments.empty() ? RHITexturePtr() : cmd->m_colorAttachments[0], depth = cmd->m_depthAttachment;
+        RHIBufferPtr vb = cmd->m_vertexBuffer, ib = cmd->m_indexBuffer;
+        TVector<RHIShaderBindingSetPtr> bindings = cmd->m_boundBindings;
+        const bool shadowCaster = cmd->m_boundMaterial->m_shader->HasDefine("SHADOW_CASTER");
+        ReserveParticlesBuffers(color, bindings, shadowCaster); // at record time, like the UI pass's workspace
+        cmd->m_hip.m_commands.push_back([this, bindings, color, depth, vb, ib, shadowCaster, indexCount, instanceCount, firstIndex, vertexOffset, firstInstance]() {
+            return RecordParticlesDraw(bindings, color, depth, vb, ib, shadowCaster, indexCount, instanceCount, firstIndex, vertexOffset, firstInstance);
         });
         return;
     }
@@ -1867,4 +1883,96 @@ int HipGraphicsDriver::RecordMeshCulling(const TVector<RHIShaderBindingSetPtr>& 
     if (!m_meshCullWorkspace) return SAILOR_HIP_ERR_OUT_OF_MEMORY;
     return sailor_hip_mesh_cull_compact_ex(m_ctx, &frame, (SailorPerInstanceData*)data, pc[1], pc[2], (SailorDrawIndexedIndirectData*)batches, pc[0],
                                            m_meshCullWorkspace->m_hip.m_devicePtr, m_meshCullWorkspace->m_size, pHiz);
+}
+
+// ---- ExperimentalParticles (FrameGraph/ParticlesNode.cpp:174-257) -------------------------------------------------------------------------------------
+// computeSets = { m_perInstanceData, sceneView.m_frameBindings } (:175): `data`, `particlesData`, `frameData`, found by name
+int HipGraphicsDriver::RecordParticlesUpdate(const TVector<RHIShaderBindingSetPtr>& bindings, const TVector<uint8_t>& pcBytes)
+{
+    if (pcBytes.size() < sizeof(SailorParticlesConstants)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    SailorParticlesConstants pc;
+    memcpy(&pc, pcBytes.data(), sizeof pc);
+    RHIShaderBindingSetPtr frameSet;
+    RHIBufferPtr instances, records;
+    for (const auto& set : bindings) {
+        if (!set) continue;
+        if (set->Find("frameData")) frameSet = set;
+        if (auto b = set->Find("data")) if (b->m_buffer) instances = b->m_buffer;
+        if (auto b = set->Find("particlesData")) if (b->m_buffer) records = b->m_buffer;
+    }
+    SailorUboFrameData frame;
+    if (!instances || !records || !host_copy_of(frameSet, "frameData", frame)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (instances->m_size / sizeof(SailorParticleInstance) < pc.numInstances) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    BeforeBufferWrite(instances->m_hip.m_devicePtr);
+    return sailor_hip_particles_update(m_ctx, &frame, &pc, (const SailorParticleData*)records->m_hip.m_devicePtr, (uint32_t)(records->m_size / sizeof(SailorParticleData)),
+                                       (SailorParticleInstance*)instances->m_hip.m_devicePtr);
+}
+
+// What a Particle.shader draw needs besides its bindings, reserved while the draw is recorded so that executing the list allocates nothing: the keys of the larger
+// of the map and the attachment, and 64 bytes for matrix 0 of the lights set's host block.  The extents are those the recorded command will find.
+void HipGraphicsDriver::ReserveParticlesBuffers(const RHITexturePtr& color, const TVector<RHIShaderBindingSetPtr>& bindings, bool shadowCaster)
+{
+    if (!m_particlesLightMatrix) m_particlesLightMatrix = CreateBuffer(64);
+    auto map = shadowCaster ? color : texture_of(bindings, "shadowMapSampler");
+    if (!map || !color) return; // (the command answers with INVALID_ARGUMENT)
+    const size_t need = sailor_hip_particles_workspace_bytes(map->GetExtent().x, map->GetExtent().y, color->GetExtent().x, color->GetExtent().y);
+    if (need != 0 && (!m_particlesWorkspace || m_particlesWorkspace->m_size < need)) m_particlesWorkspace = CreateBuffer(need);
+}
+
+// sets = { frame, lights, per-instance data, ..., the shadow map's } (:174): `frameData`, `light`, `lightsMatrices`, `data`, `shadowMapSampler`, found by name
+int HipGraphicsDriver::RecordParticlesDraw(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& color, const RHITexturePtr& depth, const RHIBufferPtr& vertices,
+                                           const RHIBufferPtr& indices, bool shadowCaster, uint32_t indexCount, uint32_t instanceCount, uint32_t firstIndex,
+                                           uint32_t vertexOffset, uint32_t firstInstance)
+{
+    if (!color || !color->m_buffer || !vertices || !indices || indexCount < 3) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    RHIShaderBindingSetPtr frameSet;
+    RHIShaderBindingPtr matrices;
+    RHIBufferPtr instances, lights;
+    for (const auto& set : bindings) {
+        if (!set) continue;
+        if (set->Find("frameData")) frameSet = set;
+        if (auto b = set->Find("data")) if (b->m_buffer) instances = b->m_buffer;
+        if (auto b = set->Find("light")) if (b->m_buffer) lights = b->m_buffer;
+        if (auto b = set->Find("lightsMatrices")) matrices = b;
+    }
+    if (!instances || !matrices || instances->m_size / sizeof(SailorParticleInstance) < (uint64_t)firstInstance + instanceCount) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    // matrix 0 onto the device: the block's host copy here, a device buffer where a caller bound one
+    const float* dMatrices = matrices->m_buffer ? (const float*)matrices->m_buffer->m_hip.m_devicePtr : nullptr;
+    if (!dMatrices) {
+        if (matrices->m_hostCopy.size() < 64) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+        if (!m_particlesLightMatrix) return SAILOR_HIP_ERR_OUT_OF_MEMORY; // (reserved when the draw was recorded)
+        if (!m_particlesLightMatrixValid || memcmp(m_particlesLightMatrixCopy, matrices->m_hostCopy.data(), 64) != 0) { // a frame's two draws and a still light: one copy
+            const int st = sailor_hip_buffer_upload(m_ctx, m_particlesLightMatrix->m_hip.m_devicePtr, 0, matrices->m_hostCopy.data(), 64);
+            if (st != SAILOR_HIP_OK) return st;
+            memcpy(m_particlesLightMatrixCopy, matrices->m_hostCopy.data(), 64);
+            m_particlesLightMatrixValid = true;
+        }
+        dMatrices = (const float*)m_particlesLightMatrix->m_hip.m_devicePtr;
+    }
+    SailorParticlesDraw draw {};
+    draw.dVertices = (const SailorVertexP3N3T3B3UV2C4*)vertices->m_hip.m_devicePtr + vertexOffset;
+    draw.dIndices = (const uint32_t*)indices->m_hip.m_devicePtr + firstIndex;
+    draw.numTriangles = indexCount / 3;
+    const SailorParticleInstance* dInstances = (const SailorParticleInstance*)instances->m_hip.m_devicePtr + firstInstance;
+    auto map = shadowCaster ? color : texture_of(bindings, "shadowMapSampler");
+    if (!map || !map->m_buffer || map->m_format != EFormat::R32_SFLOAT || map->m_parent) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    const ivec2 mapExtent = map->GetExtent(), extent = shadowCaster ? mapExtent : color->GetExtent();
+    const size_t need = sailor_hip_particles_workspace_bytes(mapExtent.x, mapExtent.y, extent.x, extent.y);
+    if (need == 0) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (!m_particlesWorkspace || m_particlesWorkspace->m_size < need) return SAILOR_HIP_ERR_WORKSPACE_TOO_SMALL; // (reserved when the draw was recorded)
+    if (shadowCaster) {
+        if (depth) return SAILOR_HIP_ERR_UNSUPPORTED; // (the map is the pass's only attachment: with a depth attachment the order would not decide)
+        BeforeBufferWrite(map->m_buffer->m_hip.m_devicePtr);
+        return sailor_hip_particles_shadow(m_ctx, &draw, dInstances, instanceCount, dMatrices, (float*)map->m_buffer->m_hip.m_devicePtr, mapExtent.x, mapExtent.y,
+                                           m_particlesWorkspace->m_hip.m_devicePtr, m_particlesWorkspace->m_size);
+    }
+    SailorUboFrameData frame;
+    if (!depth || !depth->m_buffer || depth->m_parent || !lights || color->m_format != EFormat::R32G32B32A32_SFLOAT || depth->GetExtent().x != extent.x ||
+        depth->GetExtent().y != extent.y || !host_copy_of(frameSet, "frameData", frame))
+        return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    BeforeBufferWrite(color->m_buffer->m_hip.m_devicePtr);
+    BeforeBufferWrite(depth->m_buffer->m_hip.m_devicePtr);
+    return sailor_hip_particles_draw(m_ctx, &frame, &draw, dInstances, instanceCount, (const SailorLightShaderData*)lights->m_hip.m_devicePtr, dMatrices,
+                                     (const float*)map->m_buffer->m_hip.m_devicePtr, mapExtent.x, mapExtent.y, (float*)texels_of(color),
+                                     (float*)depth->m_buffer->m_hip.m_devicePtr, extent.x, extent.y, m_particlesWorkspace->m_hip.m_devicePtr, m_particlesWorkspace->m_size);
 }

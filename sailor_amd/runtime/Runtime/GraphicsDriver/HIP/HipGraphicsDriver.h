@@ -65,6 +65,14 @@
 // bitmasks, in place of the reference's host upload), ExtractVertexPositions -> sailor_hip_shadow_extract_positions, ClearDepthStencil and ClearImage ->
 // sailor_hip_buffer_fill_u32 / sailor_hip_buffer_fill_pattern over the target's fp32 channels, GetOrAddTemporaryRenderTarget / ReleaseTemporaryRenderTarget
 // (a pool: a steady-state frame allocates nothing)
+// and for the ExperimentalParticles node:
+//   "Experimental/MeshParticles/ComputeParticles.shader" (Dispatch) -> sailor_hip_particles_update (binding contract: ComputeParticles.shader:29-58: set 0 `data`,
+//       `particlesData`, set 1 `frameData`, the 20-byte push constants)
+//   "Experimental/MeshParticles/Particle.shader" { "SHADOW_CASTER" } drawn with DrawIndexed into a pass with ONE colour attachment and no depth attachment
+//       -> sailor_hip_particles_shadow into that attachment; {} into a colour and a depth attachment -> sailor_hip_particles_draw (binding contract:
+//       Particle.shader:48-115: `frameData`, `light`, `lightsMatrices`, `data`, `shadowMapSampler`).  Any other define set is created "not ready".  The
+//       lights set's `lightsMatrices` is a host block on this path: its first matrix is staged into a driver-owned device buffer when its bytes change; that buffer
+//       and the passes' workspace are reserved while the draw is recorded.
 #pragma once
 #include <map>
 #include <memory>
@@ -217,6 +225,17 @@ private:
     int RecordSunShafts(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& target, RHI::EBlendMode blend);
     int RecordBloomDownscale(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const TVector<uint8_t>& pc);
     int RecordBloomUpscale(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const TVector<uint8_t>& pc);
+    int RecordParticlesUpdate(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const TVector<uint8_t>& pc);
+    // one DrawIndexed of Particle.shader: shadowCaster -> into `color` alone (the node's map); else into `color` and `depth`
+    int RecordParticlesDraw(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& color, const RHI::RHITexturePtr& depth,
+                            const RHI::RHIBufferPtr& vertices, const RHI::RHIBufferPtr& indices, bool shadowCaster, uint32_t indexCount, uint32_t instanceCount,
+                            uint32_t firstIndex, uint32_t vertexOffset, uint32_t firstInstance);
+    // the passes' keys and matrix 0 of `lightsMatrices` on the device: both reserved when the draw is RECORDED (ReserveParticlesBuffers), never at submit; the
+    // matrix is copied again only when the block's bytes differ from the last copy
+    void ReserveParticlesBuffers(const RHI::RHITexturePtr& color, const TVector<RHI::RHIShaderBindingSetPtr>& bindings, bool shadowCaster);
+    RHI::RHIBufferPtr m_particlesWorkspace, m_particlesLightMatrix;
+    float m_particlesLightMatrixCopy[16] = {};
+    bool m_particlesLightMatrixValid = false;
 
     SailorHipContext* m_ctx = nullptr;              // == m_ctxOwner.get(): what the C-ABI calls take
     std::shared_ptr<SailorHipContext> m_ctxOwner;   // destroyed with the last buffer that still refers to it

@@ -5,6 +5,7 @@
 #include "Runtime/ECS/LightingECS.h"
 #include "Runtime/FrameGraph/LightCullingNode.h"
 #include "Runtime/FrameGraph/DepthPrepassNode.h"
+#include "Runtime/FrameGraph/ParticlesNode.h"
 #include "Runtime/FrameGraph/RHIFrameGraph.h"
 #include "Runtime/GraphicsDriver/HIP/HipGraphicsDriver.h"
 #include "Runtime/RHI/Renderer.h"
@@ -563,6 +564,41 @@ RT_API int sailor_rt_sky_set_stars(SailorRuntime* rt, void* vertices, int count)
     auto indices = hip->CreateBuffer(identity.size() * 4);
     if (!indices || sailor_hip_buffer_upload(hip->GetContext(), indices->m_hip.m_devicePtr, 0, identity.data(), identity.size() * 4) != SAILOR_HIP_OK) return -1;
     sky->SetStars(hip->WrapBuffer(vertices, colorsAt + (size_t)count * 16), indices, (uint32_t)count);
+    return 0;
+}
+
+// What the ExperimentalParticles node's loaders read themselves (ParticlesNode.cpp:35-52: Particle_2.yaml's header and the .dat records; :89-101: the first mesh
+// of Particle.gltf), published in one call: the header fields, `records` = numRecords x SailorParticleData on the HOST (the node uploads them once, :156), the mesh
+// as caller-owned device memory (SailorVertexP3N3T3B3UV2C4 vertices, uint32 indices).  mapWidth x mapHeight is the extent of the node's shadow map (4096 x 4096 in
+// the reference, :66), materialInstance what the material's `material` binding would have given the instances (:148).  0, or -1 without such a node in the graph.
+RT_API int sailor_rt_set_particles(SailorRuntime* rt, uint32_t n, uint32_t frames, uint32_t fps, uint32_t traceFrames, float traceDecay, const void* records,
+                                   uint32_t numRecords, void* vertices, uint32_t numVertices, void* indices, uint32_t numIndices, uint32_t materialInstance, int mapWidth,
+                                   int mapHeight)
+{
+    auto* hip = static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver());
+    auto* node = rt ? static_cast<ParticlesNode*>(rt->graph.GetGraphNode("ExperimentalParticles").DynamicCast<ParticlesNode>().GetRawPtr()) : nullptr;
+    if (!node || !hip || !records || numRecords < n || !vertices || !indices || numVertices == 0 || numIndices < 3 || mapWidth <= 0 || mapHeight <= 0) return -1;
+    ParticlesNode::Header header;
+    header.m_n = n; header.m_frames = frames; header.m_fps = fps; header.m_traceFrames = traceFrames; header.m_traceDecay = traceDecay;
+    const auto* first = static_cast<const SailorParticleData*>(records);
+    node->SetShadowMapExtent({ mapWidth, mapHeight });
+    node->SetParticles(header, std::vector<SailorParticleData>(first, first + numRecords), hip->WrapBuffer(vertices, (size_t)numVertices * sizeof(SailorVertexP3N3T3B3UV2C4)),
+                       hip->WrapBuffer(indices, (size_t)numIndices * 4), numIndices, materialInstance);
+    return 0;
+}
+
+// the node's instance SSBO and its shadow map once a frame has created them (device pointers; NULL before)
+RT_API int sailor_rt_particles_buffers(SailorRuntime* rt, void** outInstances, uint32_t* outNumInstances, void** outShadowMap, int* outWidth, int* outHeight)
+{
+    auto* node = rt ? static_cast<ParticlesNode*>(rt->graph.GetGraphNode("ExperimentalParticles").DynamicCast<ParticlesNode>().GetRawPtr()) : nullptr;
+    if (!node) return -1;
+    auto instances = node->GetInstances();
+    auto map = node->GetShadowMap();
+    if (outInstances) *outInstances = instances ? instances->m_hip.m_devicePtr : nullptr;
+    if (outNumInstances) *outNumInstances = instances ? (uint32_t)(instances->m_size / sizeof(SailorParticleInstance)) : 0;
+    if (outShadowMap) *outShadowMap = map && map->m_buffer ? map->m_buffer->m_hip.m_devicePtr : nullptr;
+    if (outWidth) *outWidth = map ? map->GetExtent().x : 0;
+    if (outHeight) *outHeight = map ? map->GetExtent().y : 0;
     return 0;
 }
 

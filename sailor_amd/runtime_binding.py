@@ -49,6 +49,9 @@ def load() -> C.CDLL:
         rt.sailor_rt_sky_state.argtypes = [P, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         rt.sailor_rt_sky_set_cloud_textures.argtypes = [P, P, C.c_int, C.c_int, P, C.c_int, P, C.c_int]
         rt.sailor_rt_sky_set_stars.argtypes = [P, P, C.c_int]
+        rt.sailor_rt_set_particles.argtypes = [P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, C.c_uint32,
+                                               C.c_int, C.c_int]
+        rt.sailor_rt_particles_buffers.argtypes = [P, C.POINTER(P), C.POINTER(C.c_uint32), C.POINTER(P), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         rt.sailor_rt_set_environment_map.argtypes = [P, P, C.c_int, C.c_int, C.c_int, C.c_int]
         rt.sailor_rt_sampler.restype = P
         rt.sailor_rt_sampler.argtypes = [P, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -260,6 +263,25 @@ class Runtime:
         "Shaders/Stars.shader" enabled the node draws the star points.  -1 if the graph has no Sky node"""
         assert vertices.is_contiguous() and vertices.element_size() == 4 and vertices.numel() >= (count * 3 + 3) // 4 * 4 + count * 4, (vertices.dtype, vertices.numel())
         return self.rt.sailor_rt_sky_set_stars(self.h, vertices.data_ptr(), count)
+
+    def set_particles(self, particles: int, frames: int, fps: int, trace_frames: int, trace_decay: float, records, vertices, indices, map_extent=(4096, 4096),
+                      material_instance: int = 0) -> int:
+        """publish what the ExperimentalParticles node's loaders would have loaded: the header fields, `records` (host, _lib.PARTICLE_DATA_DTYPE), the particle
+        mesh on the device (72-byte vertices, uint32 indices; caller-owned) and the extent of the node's shadow map.  -1 if the graph has no such node"""
+        import numpy as np
+        records = np.ascontiguousarray(records)
+        assert records.dtype.itemsize == 80 and vertices.is_contiguous() and indices.is_contiguous()
+        num_vertices, num_indices = vertices.numel() * vertices.element_size() // 72, indices.numel() * indices.element_size() // 4
+        return self.rt.sailor_rt_set_particles(self.h, particles, frames, fps, trace_frames, trace_decay, records.ctypes.data, len(records), vertices.data_ptr(),
+                                               num_vertices, indices.data_ptr(), num_indices, material_instance, map_extent[0], map_extent[1])
+
+    def particles_buffers(self):
+        """(device pointer of the ExperimentalParticles node's instance SSBO, its instance count, device pointer of its shadow map, the map's width, height);
+        the pointers are None before the node's first frame; raises if the graph has no such node"""
+        inst, count, smap, w, h = C.c_void_p(), C.c_uint32(0), C.c_void_p(), C.c_int(0), C.c_int(0)
+        if self.rt.sailor_rt_particles_buffers(self.h, C.byref(inst), C.byref(count), C.byref(smap), C.byref(w), C.byref(h)) != 0:
+            raise ValueError("the graph has no ExperimentalParticles node")
+        return inst.value, count.value, smap.value, w.value, h.value
 
     def sky_state(self):
         """(m_updateEnvCubemapPattern, m_bIsDirty) of the Sky node; raises if the graph has none"""

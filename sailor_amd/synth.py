@@ -547,3 +547,19 @@ def perspective_reversed_z(width: int, height: int, near: float = 0.1, f: float 
     m = np.zeros(16, np.float32)
     m[0], m[5], m[2 * 4 + 3], m[3 * 4 + 2] = f * height / width, f, -1.0, near
     return m
+
+
+def face_cube_mesh():
+    """the cube spanning [-1, 1]^3 as SailorVertexP3N3T3B3UV2C4 vertices float32 [24, 18] (texcoord, position, normal, tangent, bitangent, colour) and
+    indices uint32 [12, 3], counter-clockwise from outside: four vertices a face, white"""
+    verts, tris = [], []
+    for axis in range(3):
+        for sign in (1.0, -1.0):
+            n = np.zeros(3); n[axis] = sign
+            u = np.zeros(3); u[(axis + 1) % 3] = 1.0
+            v = np.cross(n, u)                      # u x v = n
+            base = len(verts)
+            for (a, b), uv in zip(((-1, -1), (1, -1), (1, 1), (-1, 1)), ((0, 0), (1, 0), (1, 1), (0, 1))):
+                verts.append(np.concatenate([uv, n + a * u + b * v, n, u, v, (1, 1, 1, 1)]))
+            tris += [(base, base + 1, base + 2), (base, base + 2, base + 3)]
+    return np.asarray(verts, np.float32), np.asarray(tris, np.uint32)
