@@ -191,9 +191,7 @@ static const char* dbgl_check(const float* viewProjection, const SailorDebugLine
                               size_t workspaceBytes)
 {
     if (!viewProjection || !draw) return "the matrix or the draw is NULL";
-    if (!surf_band_ok(width, height, band)) return "the band is not valid for the frame";
-    if (!aligned(dWorkspace, 16)) return "the workspace is NULL or not 16-byte aligned";
-    if (surf_max_draws(width, band, workspaceBytes) == 0) return "the workspace is too small";
+    if (const char* why = surf_workspace_why(width, height, band, dWorkspace, workspaceBytes, true)) return why;
     if (draw->numSegments && !aligned(draw->dVertices, 4)) return "the vertex buffer is NULL or not 4-byte aligned";
     if (draw->dIndices && !aligned(draw->dIndices, 4)) return "the index buffer is not 4-byte aligned";
     if ((unsigned long long)draw->primBase + draw->numSegments >= 0xFFFFFFFFull) return "primBase + the draw's segments reaches 2^32 - 1";
@@ -214,16 +212,13 @@ int sailor_hip_debug_lines_draw(SailorHipContext* ctx, const float* viewProjecti
 {
     if (!ctx) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     if (const char* why = dbgl_check(viewProjection, draw, width, height, band, dWorkspace, workspaceBytes))
-        return surf_refuse(ctx, (std::string("sailor_hip_debug_lines_draw: ") + why).c_str());
+        return surf_refuse(ctx, "sailor_hip_debug_lines_draw", why);
     if (draw->numSegments == 0) return SAILOR_HIP_OK; // nothing to record
     Mat4 VP;
     memcpy(VP.m, viewProjection, 64);
     SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
-    // slices (see the kernel): about SURF_SLICE_LANES lanes in flight for a draw of few segments, one slice from that many segments on
-    const unsigned long long want = SURF_SLICE_LANES / draw->numSegments;
-    const unsigned slices = (unsigned)(want < 1 ? 1 : (want > SURF_SLICES_MAX ? SURF_SLICES_MAX : want));
-    sailor_launch(ctx, k_debug_lines_draw, dim3((unsigned)(((unsigned long long)draw->numSegments + 255) / 256), slices), dim3(256), VP, *draw, (int)width, (int)height,
-                  (int)band->fbRowBegin, (int)band->fbRowCount, dWorkspace);
+    sailor_launch(ctx, k_debug_lines_draw, dim3((unsigned)(((unsigned long long)draw->numSegments + 255) / 256), surf_slices(draw->numSegments)), dim3(256), VP, *draw,
+                  (int)width, (int)height, (int)band->fbRowBegin, (int)band->fbRowCount, dWorkspace);
     SAILOR_CHECK_LAUNCH(ctx, "k_debug_lines_draw");
     return SAILOR_HIP_OK;
 }
@@ -235,7 +230,7 @@ int sailor_hip_debug_lines_resolve(SailorHipContext* ctx, const float* viewProje
     const char* why = dbgl_check(viewProjection, draw, width, height, band, dWorkspace, workspaceBytes);
     if (!why && !aligned(dTarget, 16)) why = "the target is NULL or not 16-byte aligned";
     if (!why && !aligned(dDepth, 4)) why = "the depth attachment is NULL or not 4-byte aligned";
-    if (why) return surf_refuse(ctx, (std::string("sailor_hip_debug_lines_resolve: ") + why).c_str());
+    if (why) return surf_refuse(ctx, "sailor_hip_debug_lines_resolve", why);
     if (draw->numSegments == 0) return SAILOR_HIP_OK;
     Mat4 VP;
     memcpy(VP.m, viewProjection, 64);

@@ -270,8 +270,7 @@ static const char* part_draw_refusal(const SailorParticlesDraw* draw, const Sail
 static dim3 part_raster_grid(uint32_t numInstances, uint32_t numTriangles)
 {
     const unsigned long long total = (unsigned long long)numInstances * numTriangles; // (< 2^31: see part_draw_refusal)
-    const unsigned long long want = SURF_SLICE_LANES / total;
-    return dim3((unsigned)((total + 255) / 256), (unsigned)(want < 1 ? 1 : (want > SURF_SLICES_MAX ? SURF_SLICES_MAX : want)));
+    return dim3((unsigned)((total + 255) / 256), surf_slices(total));
 }
 
 extern "C" {

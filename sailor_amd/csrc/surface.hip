@@ -281,10 +281,8 @@ int sailor_hip_surface_begin(SailorHipContext* ctx, const float* dDepthOrNull, i
                              size_t workspaceBytes)
 {
     if (!ctx) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    if (!surf_band_ok(width, height, band)) return surf_refuse(ctx, "sailor_hip_surface_begin: the band is not valid for the frame");
-    if (!aligned(dWorkspace, 16)) return surf_refuse(ctx, "sailor_hip_surface_begin: the workspace is NULL or not 16-byte aligned");
-    const uint32_t maxDraws = surf_max_draws(width, band, workspaceBytes);
-    if (maxDraws == 0) return surf_refuse(ctx, "sailor_hip_surface_begin: the workspace is too small");
+    uint32_t maxDraws = 0;
+    if (const char* why = surf_workspace_why(width, height, band, dWorkspace, workspaceBytes, true, &maxDraws)) return surf_refuse(ctx, "sailor_hip_surface_begin", why);
     static const SurfSrgb table = [] { SurfSrgb t; sailor_host_srgb_table(t.v); return t; }();
     SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
     const size_t pixels = (size_t)band->fbRowCount * width;
@@ -299,26 +297,12 @@ int sailor_hip_surface_begin(SailorHipContext* ctx, const float* dDepthOrNull, i
 int sailor_hip_surface_draw(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSurfaceDraw* draw, const SailorPerInstanceData* dInstances,
                             uint32_t drawIndex, int32_t width, int32_t height, const SailorBand* band, void* dWorkspace, size_t workspaceBytes)
 {
-    if (!ctx) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    if (!frame || !draw) return surf_refuse(ctx, "sailor_hip_surface_draw: frame or draw is NULL");
-    if (!surf_band_ok(width, height, band)) return surf_refuse(ctx, "sailor_hip_surface_draw: the band is not valid for the frame");
-    if (!aligned(dWorkspace, 16)) return surf_refuse(ctx, "sailor_hip_surface_draw: the workspace is NULL or not 16-byte aligned");
-    const uint32_t maxDraws = surf_max_draws(width, band, workspaceBytes);
-    if (maxDraws == 0) return surf_refuse(ctx, "sailor_hip_surface_draw: the workspace is too small");
-    if (drawIndex >= maxDraws) return surf_refuse(ctx, "sailor_hip_surface_draw: drawIndex is beyond the workspace's descriptor slots");
-    if (draw->flags & ~SAILOR_SURFACE_CULL_BACK) return surf_refuse(ctx, "sailor_hip_surface_draw: unknown flags");
-    const unsigned long long total = (unsigned long long)draw->numDrawn * draw->numTriangles;
-    if (total && (!draw->dVertices || !draw->dIndices || !dInstances)) return surf_refuse(ctx, "sailor_hip_surface_draw: a vertex, index or instance buffer is NULL");
-    if (total > 0x7FFFFFFFull || (unsigned long long)draw->primBase + 2ull * total >= 0xFFFFFFFFull) return surf_refuse(ctx, "sailor_hip_surface_draw: primBase + the draw's primitives reaches 2^32 - 1");
-    Mat4 P, V;
-    memcpy(P.m, frame->projection, 64);
-    memcpy(V.m, frame->view, 64);
+    SurfDrawSetup s;
+    if (const int st = surf_draw_prologue(ctx, "sailor_hip_surface_draw", SAILOR_SURFACE_CULL_BACK, false, nullptr, frame, draw, dInstances, false, drawIndex, width, height,
+                                          band, dWorkspace, workspaceBytes, s))
+        return st;
     SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
-    const unsigned long long blocks = total ? (total + 255) / 256 : 1; // (an empty draw still leaves its descriptor)
-    // slices (see the kernel): about SURF_SLICE_LANES lanes in flight for a draw of few triangles, one slice from that many triangles on
-    const unsigned long long want = total ? SURF_SLICE_LANES / total : 1;
-    const unsigned slices = (unsigned)(want < 1 ? 1 : (want > SURF_SLICES_MAX ? SURF_SLICES_MAX : want));
-    sailor_launch(ctx, k_surface_visibility, dim3((unsigned)blocks, slices), dim3(256), P, V, *draw, reinterpret_cast<const float*>(dInstances), drawIndex, (int)width, (int)height,
+    sailor_launch(ctx, k_surface_visibility, s.grid, dim3(256), s.P, s.V, *draw, reinterpret_cast<const float*>(dInstances), drawIndex, (int)width, (int)height,
                   (int)band->fbRowBegin, (int)band->fbRowCount, dWorkspace);
     SAILOR_CHECK_LAUNCH(ctx, "k_surface_visibility");
     return SAILOR_HIP_OK;
@@ -329,21 +313,14 @@ int sailor_hip_surface_resolve(SailorHipContext* ctx, const SailorUboFrameData* 
                                const void* dWorkspace, size_t workspaceBytes, float* dSurface, size_t planeStride, float* dDepthOutOrNull, uint8_t* dCoverageOrNull)
 {
     if (!ctx) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    if (!frame || !dInstances || !dMaterials || !dTextures || numMaterials == 0 || numTextures == 0)
-        return surf_refuse(ctx, "sailor_hip_surface_resolve: frame, instances, materials or textures missing");
-    if (!surf_band_ok(width, height, band)) return surf_refuse(ctx, "sailor_hip_surface_resolve: the band is not valid for the frame");
-    const uint32_t maxDraws = surf_max_draws(width, band, workspaceBytes);
-    if (!aligned(dWorkspace, 16) || maxDraws == 0) return surf_refuse(ctx, "sailor_hip_surface_resolve: the workspace is NULL, misaligned or too small");
-    if (!aligned(dSurface, 16)) return surf_refuse(ctx, "sailor_hip_surface_resolve: the surface is NULL or not 16-byte aligned");
-    if (planeStride < (size_t)band->fbRowCount * width) return surf_refuse(ctx, "sailor_hip_surface_resolve: planeStride is smaller than the band's rows x width");
-    if (dDepthOutOrNull && !aligned(dDepthOutOrNull, 4)) return surf_refuse(ctx, "sailor_hip_surface_resolve: the depth output is misaligned");
-    Mat4 P, V;
-    memcpy(P.m, frame->projection, 64);
-    memcpy(V.m, frame->view, 64);
+    SurfResolveSetup s;
+    if (const char* why = surf_resolve_why(frame, dInstances && surf_tables_ok(dMaterials, numMaterials, dTextures, numTextures), width, height, band, dWorkspace,
+                                           workspaceBytes, dSurface, planeStride, dDepthOutOrNull, s))
+        return surf_refuse(ctx, "sailor_hip_surface_resolve", why);
     SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
-    sailor_launch(ctx, k_surface_resolve, texel_grid(width, band->fbRowCount), dim3(256), P, V, reinterpret_cast<const float*>(dInstances), dMaterials, numMaterials, dTextures,
-                  numTextures, (int)width, (int)height, (int)band->fbRowBegin, (int)band->fbRowCount, maxDraws, dWorkspace, reinterpret_cast<float4*>(dSurface), planeStride,
-                  dDepthOutOrNull, dCoverageOrNull);
+    sailor_launch(ctx, k_surface_resolve, texel_grid(width, band->fbRowCount), dim3(256), s.P, s.V, reinterpret_cast<const float*>(dInstances), dMaterials, numMaterials,
+                  dTextures, numTextures, (int)width, (int)height, (int)band->fbRowBegin, (int)band->fbRowCount, s.maxDraws, dWorkspace, reinterpret_cast<float4*>(dSurface),
+                  planeStride, dDepthOutOrNull, dCoverageOrNull);
     SAILOR_CHECK_LAUNCH(ctx, "k_surface_resolve");
     return SAILOR_HIP_OK;
 }
@@ -352,9 +329,9 @@ int sailor_hip_surface_composite(SailorHipContext* ctx, const float* dRadiance, 
                                  int32_t height, const SailorBand* band)
 {
     if (!ctx) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    if (!surf_band_ok(width, height, band)) return surf_refuse(ctx, "sailor_hip_surface_composite: the band is not valid for the frame");
-    if (!aligned(dWorkspace, 16) || surf_max_draws(width, band, workspaceBytes) == 0) return surf_refuse(ctx, "sailor_hip_surface_composite: the workspace is NULL, misaligned or too small");
-    if (!aligned(dRadiance, 16) || !aligned(dTarget, 16)) return surf_refuse(ctx, "sailor_hip_surface_composite: radiance or target is NULL or not 16-byte aligned");
+    const char* why = surf_workspace_why(width, height, band, dWorkspace, workspaceBytes, false);
+    if (!why && (!aligned(dRadiance, 16) || !aligned(dTarget, 16))) why = "radiance or target is NULL or not 16-byte aligned";
+    if (why) return surf_refuse(ctx, "sailor_hip_surface_composite", why);
     SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
     sailor_launch(ctx, k_surface_composite, texel_grid(width, band->fbRowCount), dim3(256), reinterpret_cast<const float4*>(dRadiance), dWorkspace,
                   reinterpret_cast<float4*>(dTarget), (int)width, (int)band->fbRowCount);

@@ -1,6 +1,9 @@
 // What the surface-pass translation units share (surface.hip: the Opaque queue; surface_masked.hip: the Masked queue with ALPHA_CUTOUT; surface_gltf.hip:
 // Standard_glTF.shader's materials): the set-up copied from raster.hip, the depth test of one fragment, the workspace layout, the varyings of a vertex, the
-// texture taps and the checks of the entry points.
+// texture taps and the checks of the entry points.  Those checks are written once, host-only, at the end of this file: surf_workspace_why (band, workspace
+// alignment, descriptor slots) for every entry that takes the workspace, surf_draw_prologue (every check of the four draw entries, their matrices and their
+// grid with its slices) and surf_resolve_why (the two resolves).  An entry keeps the checks that are its own and its launch; surf_refuse puts the entry's
+// name in front of the reason.
 #pragma once
 #include "common.h"
 #include "sampling.h"
@@ -230,9 +233,10 @@ __device__ __forceinline__ float surf_varying(const float* __restrict__ v, const
 }
 
 // ---- what every entry point checks ------------------------------------------------------------------------------------------------------------------
-static int surf_refuse(SailorHipContext* ctx, const char* what)
+// last_error = "<the entry's name>: <what>"
+static int surf_refuse(SailorHipContext* ctx, const char* who, const char* what)
 {
-    if (ctx) ctx->lastError = what;
+    if (ctx) ctx->lastError = std::string(who) + ": " + what;
     return SAILOR_HIP_ERR_INVALID_ARGUMENT;
 }
 static bool surf_band_ok(int32_t width, int32_t height, const SailorBand* band)
@@ -250,4 +254,73 @@ static uint32_t surf_max_draws(int32_t width, const SailorBand* band, size_t byt
     if (bytes < fixed + sizeof(SailorSurfaceDraw)) return 0;
     const size_t n = (bytes - fixed) / sizeof(SailorSurfaceDraw);
     return (uint32_t)(n < SURF_MAX_DRAWS ? n : SURF_MAX_DRAWS);
+}
+// The band is valid for the frame, the workspace is 16-byte aligned and holds at least one descriptor slot: why not, or NULL.  `split`: an entry that
+// writes the workspace tells a bad pointer from a small workspace; one that only reads it has a single message for both.
+static const char* surf_workspace_why(int32_t width, int32_t height, const SailorBand* band, const void* dWorkspace, size_t workspaceBytes, bool split,
+                                      uint32_t* maxDraws = nullptr)
+{
+    if (!surf_band_ok(width, height, band)) return "the band is not valid for the frame";
+    const uint32_t n = surf_max_draws(width, band, workspaceBytes);
+    if (maxDraws) *maxDraws = n;
+    if (split && !aligned(dWorkspace, 16)) return "the workspace is NULL or not 16-byte aligned";
+    if (split && n == 0) return "the workspace is too small";
+    if (!aligned(dWorkspace, 16) || n == 0) return "the workspace is NULL, misaligned or too small";
+    return nullptr;
+}
+// the slices of a draw of `lanes` triangles or segments (see k_surface_visibility): about SURF_SLICE_LANES lanes in flight for a draw of few, one slice from
+// that many on
+static unsigned surf_slices(unsigned long long lanes)
+{
+    const unsigned long long want = lanes ? SURF_SLICE_LANES / lanes : 1;
+    return (unsigned)(want < 1 ? 1 : (want > SURF_SLICES_MAX ? SURF_SLICES_MAX : want));
+}
+static bool surf_tables_ok(const SailorMaterialData* dMaterials, uint32_t numMaterials, const SailorTextureDesc* dTextures, uint32_t numTextures)
+{
+    return dMaterials && dTextures && numMaterials != 0 && numTextures != 0;
+}
+
+// What the four draw entries (sailor_hip_surface_draw, _masked, _gltf, _indirect) check, in one order, and what their launches share: the two matrices,
+// the lanes of the draw and the grid.  `allowed` = the flag bits the entry accepts, needGltf = SAILOR_SURFACE_GLTF has to be among the draw's, `tables` =
+// surf_tables_ok of the entry's tables (read under ALPHA_CUTOUT only); dCommand = NULL for a direct entry, the address of the indirect entry's command
+// pointer: that entry checks the command and dInstanceIds as well, and its lanes are the CAPACITY's (the count is not known on the host).
+struct SurfDrawSetup { Mat4 P, V; unsigned long long total; dim3 grid; };
+static int surf_draw_prologue(SailorHipContext* ctx, const char* who, uint32_t allowed, bool needGltf, const SailorDrawIndexedIndirectData* const* dCommand,
+                              const SailorUboFrameData* frame, const SailorSurfaceDraw* draw, const SailorPerInstanceData* dInstances, bool tables, uint32_t drawIndex,
+                              int32_t width, int32_t height, const SailorBand* band, const void* dWorkspace, size_t workspaceBytes, SurfDrawSetup& s)
+{
+    if (!ctx) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (!frame || !draw) return surf_refuse(ctx, who, "frame or draw is NULL");
+    if (dCommand && !aligned(*dCommand, 4)) return surf_refuse(ctx, who, "the command is NULL or not 4-byte aligned");
+    uint32_t maxDraws = 0;
+    if (const char* why = surf_workspace_why(width, height, band, dWorkspace, workspaceBytes, true, &maxDraws)) return surf_refuse(ctx, who, why);
+    if (drawIndex >= maxDraws) return surf_refuse(ctx, who, "drawIndex is beyond the workspace's descriptor slots");
+    if (draw->flags & ~allowed) return surf_refuse(ctx, who, "unknown flags");
+    if (needGltf && !(draw->flags & SAILOR_SURFACE_GLTF)) return surf_refuse(ctx, who, "the draw does not carry SAILOR_SURFACE_GLTF");
+    if (dCommand && draw->dInstanceIds) return surf_refuse(ctx, who, "dInstanceIds must be NULL (the instances are firstInstance + d of the command)");
+    if ((draw->flags & SAILOR_SURFACE_ALPHA_CUTOUT) && !tables) return surf_refuse(ctx, who, "ALPHA_CUTOUT needs materials and textures");
+    s.total = (unsigned long long)draw->numDrawn * draw->numTriangles;
+    if (s.total && (!draw->dVertices || !draw->dIndices || !dInstances)) return surf_refuse(ctx, who, "a vertex, index or instance buffer is NULL");
+    if (s.total > 0x7FFFFFFFull || (unsigned long long)draw->primBase + 2ull * s.total >= 0xFFFFFFFFull)
+        return surf_refuse(ctx, who, dCommand ? "primBase + the capacity's primitives reaches 2^32 - 1" : "primBase + the draw's primitives reaches 2^32 - 1");
+    memcpy(s.P.m, frame->projection, 64);
+    memcpy(s.V.m, frame->view, 64);
+    s.grid = dim3((unsigned)(s.total ? (s.total + 255) / 256 : 1), surf_slices(s.total)); // (an empty draw still leaves its descriptor)
+    return SAILOR_HIP_OK;
+}
+
+// What sailor_hip_surface_resolve and _resolve_gltf check alike (`rest` = the instances are there and surf_tables_ok of the tables), and the matrices and
+// the descriptor slots their kernels take: why not, or NULL
+struct SurfResolveSetup { Mat4 P, V; uint32_t maxDraws; };
+static const char* surf_resolve_why(const SailorUboFrameData* frame, bool rest, int32_t width, int32_t height, const SailorBand* band, const void* dWorkspace,
+                                    size_t workspaceBytes, const float* dSurface, size_t planeStride, const float* dDepthOutOrNull, SurfResolveSetup& s)
+{
+    if (!frame || !rest) return "frame, instances, materials or textures missing";
+    if (const char* why = surf_workspace_why(width, height, band, dWorkspace, workspaceBytes, false, &s.maxDraws)) return why;
+    if (!aligned(dSurface, 16)) return "the surface is NULL or not 16-byte aligned";
+    if (planeStride < (size_t)band->fbRowCount * width) return "planeStride is smaller than the band's rows x width";
+    if (dDepthOutOrNull && !aligned(dDepthOutOrNull, 4)) return "the depth output is misaligned";
+    memcpy(s.P.m, frame->projection, 64);
+    memcpy(s.V.m, frame->view, 64);
+    return nullptr;
 }

@@ -190,30 +190,14 @@ int sailor_hip_surface_draw_gltf(SailorHipContext* ctx, const SailorUboFrameData
                                  const SailorMaterialData* dMaterials, uint32_t numMaterials, const SailorTextureDesc* dTextures, uint32_t numTextures,
                                  uint32_t drawIndex, int32_t width, int32_t height, const SailorBand* band, void* dWorkspace, size_t workspaceBytes)
 {
-    if (!ctx) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    if (!frame || !draw) return surf_refuse(ctx, "sailor_hip_surface_draw_gltf: frame or draw is NULL");
-    if (!surf_band_ok(width, height, band)) return surf_refuse(ctx, "sailor_hip_surface_draw_gltf: the band is not valid for the frame");
-    if (!aligned(dWorkspace, 16)) return surf_refuse(ctx, "sailor_hip_surface_draw_gltf: the workspace is NULL or not 16-byte aligned");
-    const uint32_t maxDraws = surf_max_draws(width, band, workspaceBytes);
-    if (maxDraws == 0) return surf_refuse(ctx, "sailor_hip_surface_draw_gltf: the workspace is too small");
-    if (drawIndex >= maxDraws) return surf_refuse(ctx, "sailor_hip_surface_draw_gltf: drawIndex is beyond the workspace's descriptor slots");
-    if (draw->flags & ~(SAILOR_SURFACE_CULL_BACK | SAILOR_SURFACE_ALPHA_CUTOUT | SAILOR_SURFACE_GLTF)) return surf_refuse(ctx, "sailor_hip_surface_draw_gltf: unknown flags");
-    if (!(draw->flags & SAILOR_SURFACE_GLTF)) return surf_refuse(ctx, "sailor_hip_surface_draw_gltf: the draw does not carry SAILOR_SURFACE_GLTF");
-    if ((draw->flags & SAILOR_SURFACE_ALPHA_CUTOUT) && (!dMaterials || !dTextures || numMaterials == 0 || numTextures == 0))
-        return surf_refuse(ctx, "sailor_hip_surface_draw_gltf: ALPHA_CUTOUT needs materials and textures");
-    const unsigned long long total = (unsigned long long)draw->numDrawn * draw->numTriangles;
-    if (total && (!draw->dVertices || !draw->dIndices || !dInstances)) return surf_refuse(ctx, "sailor_hip_surface_draw_gltf: a vertex, index or instance buffer is NULL");
-    if (total > 0x7FFFFFFFull || (unsigned long long)draw->primBase + 2ull * total >= 0xFFFFFFFFull)
-        return surf_refuse(ctx, "sailor_hip_surface_draw_gltf: primBase + the draw's primitives reaches 2^32 - 1");
-    Mat4 P, V;
-    memcpy(P.m, frame->projection, 64);
-    memcpy(V.m, frame->view, 64);
+    SurfDrawSetup s;
+    if (const int st = surf_draw_prologue(ctx, "sailor_hip_surface_draw_gltf", SAILOR_SURFACE_CULL_BACK | SAILOR_SURFACE_ALPHA_CUTOUT | SAILOR_SURFACE_GLTF, true, nullptr, frame,
+                                          draw, dInstances, surf_tables_ok(dMaterials, numMaterials, dTextures, numTextures), drawIndex, width, height, band, dWorkspace,
+                                          workspaceBytes, s))
+        return st;
     SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
-    const unsigned long long blocks = total ? (total + 255) / 256 : 1; // (an empty draw still leaves its descriptor)
-    const unsigned long long want = total ? SURF_SLICE_LANES / total : 1; // the slices of sailor_hip_surface_draw
-    const unsigned slices = (unsigned)(want < 1 ? 1 : (want > SURF_SLICES_MAX ? SURF_SLICES_MAX : want));
-    sailor_launch(ctx, k_surface_visibility_gltf, dim3((unsigned)blocks, slices), dim3(256), P, V, *draw, reinterpret_cast<const float*>(dInstances), dMaterials, numMaterials,
-                  dTextures, numTextures, drawIndex, (int)width, (int)height, (int)band->fbRowBegin, (int)band->fbRowCount, dWorkspace);
+    sailor_launch(ctx, k_surface_visibility_gltf, s.grid, dim3(256), s.P, s.V, *draw, reinterpret_cast<const float*>(dInstances), dMaterials, numMaterials, dTextures,
+                  numTextures, drawIndex, (int)width, (int)height, (int)band->fbRowBegin, (int)band->fbRowCount, dWorkspace);
     SAILOR_CHECK_LAUNCH(ctx, "k_surface_visibility_gltf");
     return SAILOR_HIP_OK;
 }
@@ -224,23 +208,15 @@ int sailor_hip_surface_resolve_gltf(SailorHipContext* ctx, const SailorUboFrameD
                                     const float* dAoInOrNull, float* dAoOutOrNull, float* dEmissive)
 {
     if (!ctx) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    if (!frame || !dInstances || !dMaterials || !dTextures || numMaterials == 0 || numTextures == 0)
-        return surf_refuse(ctx, "sailor_hip_surface_resolve_gltf: frame, instances, materials or textures missing");
-    if (!surf_band_ok(width, height, band)) return surf_refuse(ctx, "sailor_hip_surface_resolve_gltf: the band is not valid for the frame");
-    const uint32_t maxDraws = surf_max_draws(width, band, workspaceBytes);
-    if (!aligned(dWorkspace, 16) || maxDraws == 0) return surf_refuse(ctx, "sailor_hip_surface_resolve_gltf: the workspace is NULL, misaligned or too small");
-    if (!aligned(dSurface, 16)) return surf_refuse(ctx, "sailor_hip_surface_resolve_gltf: the surface is NULL or not 16-byte aligned");
-    if (planeStride < (size_t)band->fbRowCount * width) return surf_refuse(ctx, "sailor_hip_surface_resolve_gltf: planeStride is smaller than the band's rows x width");
-    if (dDepthOutOrNull && !aligned(dDepthOutOrNull, 4)) return surf_refuse(ctx, "sailor_hip_surface_resolve_gltf: the depth output is misaligned");
-    if ((dAoInOrNull && !aligned(dAoInOrNull, 4)) || (dAoOutOrNull && !aligned(dAoOutOrNull, 4)))
-        return surf_refuse(ctx, "sailor_hip_surface_resolve_gltf: an occlusion plane is misaligned");
-    if (!aligned(dEmissive, 16)) return surf_refuse(ctx, "sailor_hip_surface_resolve_gltf: the emissive plane is NULL or not 16-byte aligned");
-    Mat4 P, V;
-    memcpy(P.m, frame->projection, 64);
-    memcpy(V.m, frame->view, 64);
+    SurfResolveSetup s;
+    const char* why = surf_resolve_why(frame, dInstances && surf_tables_ok(dMaterials, numMaterials, dTextures, numTextures), width, height, band, dWorkspace, workspaceBytes,
+                                       dSurface, planeStride, dDepthOutOrNull, s);
+    if (!why && ((dAoInOrNull && !aligned(dAoInOrNull, 4)) || (dAoOutOrNull && !aligned(dAoOutOrNull, 4)))) why = "an occlusion plane is misaligned";
+    if (!why && !aligned(dEmissive, 16)) why = "the emissive plane is NULL or not 16-byte aligned";
+    if (why) return surf_refuse(ctx, "sailor_hip_surface_resolve_gltf", why);
     SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
-    sailor_launch(ctx, k_surface_resolve_gltf, texel_grid(width, band->fbRowCount), dim3(256), P, V, reinterpret_cast<const float*>(dInstances), dMaterials, numMaterials,
-                  dTextures, numTextures, (int)width, (int)height, (int)band->fbRowBegin, (int)band->fbRowCount, maxDraws, dWorkspace, reinterpret_cast<float4*>(dSurface),
+    sailor_launch(ctx, k_surface_resolve_gltf, texel_grid(width, band->fbRowCount), dim3(256), s.P, s.V, reinterpret_cast<const float*>(dInstances), dMaterials, numMaterials,
+                  dTextures, numTextures, (int)width, (int)height, (int)band->fbRowBegin, (int)band->fbRowCount, s.maxDraws, dWorkspace, reinterpret_cast<float4*>(dSurface),
                   planeStride, dDepthOutOrNull, dCoverageOrNull, dAoInOrNull, dAoOutOrNull, reinterpret_cast<float4*>(dEmissive));
     SAILOR_CHECK_LAUNCH(ctx, "k_surface_resolve_gltf");
     return SAILOR_HIP_OK;
@@ -250,11 +226,9 @@ int sailor_hip_surface_composite_gltf(SailorHipContext* ctx, const float* dRadia
                                       float* dTarget, int32_t width, int32_t height, const SailorBand* band)
 {
     if (!ctx) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    if (!surf_band_ok(width, height, band)) return surf_refuse(ctx, "sailor_hip_surface_composite_gltf: the band is not valid for the frame");
-    if (!aligned(dWorkspace, 16) || surf_max_draws(width, band, workspaceBytes) == 0)
-        return surf_refuse(ctx, "sailor_hip_surface_composite_gltf: the workspace is NULL, misaligned or too small");
-    if (!aligned(dRadiance, 16) || !aligned(dEmissive, 16) || !aligned(dTarget, 16))
-        return surf_refuse(ctx, "sailor_hip_surface_composite_gltf: radiance, emissive or target is NULL or not 16-byte aligned");
+    const char* why = surf_workspace_why(width, height, band, dWorkspace, workspaceBytes, false);
+    if (!why && (!aligned(dRadiance, 16) || !aligned(dEmissive, 16) || !aligned(dTarget, 16))) why = "radiance, emissive or target is NULL or not 16-byte aligned";
+    if (why) return surf_refuse(ctx, "sailor_hip_surface_composite_gltf", why);
     SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
     sailor_launch(ctx, k_surface_composite_gltf, texel_grid(width, band->fbRowCount), dim3(256), reinterpret_cast<const float4*>(dRadiance),
                   reinterpret_cast<const float4*>(dEmissive), dWorkspace, reinterpret_cast<float4*>(dTarget), (int)width, (int)band->fbRowCount);

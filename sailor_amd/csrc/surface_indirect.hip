@@ -54,39 +54,20 @@ int sailor_hip_surface_draw_indirect(SailorHipContext* ctx, const SailorUboFrame
                                      const SailorMaterialData* dMaterials, uint32_t numMaterials, const SailorTextureDesc* dTextures, uint32_t numTextures,
                                      uint32_t drawIndex, int32_t width, int32_t height, const SailorBand* band, void* dWorkspace, size_t workspaceBytes)
 {
-    if (!ctx) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    if (!frame || !draw) return surf_refuse(ctx, "sailor_hip_surface_draw_indirect: frame or draw is NULL");
-    if (!aligned(dCommand, 4)) return surf_refuse(ctx, "sailor_hip_surface_draw_indirect: the command is NULL or not 4-byte aligned");
-    if (!surf_band_ok(width, height, band)) return surf_refuse(ctx, "sailor_hip_surface_draw_indirect: the band is not valid for the frame");
-    if (!aligned(dWorkspace, 16)) return surf_refuse(ctx, "sailor_hip_surface_draw_indirect: the workspace is NULL or not 16-byte aligned");
-    const uint32_t maxDraws = surf_max_draws(width, band, workspaceBytes);
-    if (maxDraws == 0) return surf_refuse(ctx, "sailor_hip_surface_draw_indirect: the workspace is too small");
-    if (drawIndex >= maxDraws) return surf_refuse(ctx, "sailor_hip_surface_draw_indirect: drawIndex is beyond the workspace's descriptor slots");
-    if (draw->flags & ~(SAILOR_SURFACE_CULL_BACK | SAILOR_SURFACE_ALPHA_CUTOUT | SAILOR_SURFACE_GLTF)) return surf_refuse(ctx, "sailor_hip_surface_draw_indirect: unknown flags");
-    if (draw->dInstanceIds) return surf_refuse(ctx, "sailor_hip_surface_draw_indirect: dInstanceIds must be NULL (the instances are firstInstance + d of the command)");
-    if ((draw->flags & SAILOR_SURFACE_ALPHA_CUTOUT) && (!dMaterials || !dTextures || numMaterials == 0 || numTextures == 0))
-        return surf_refuse(ctx, "sailor_hip_surface_draw_indirect: ALPHA_CUTOUT needs materials and textures");
-    const unsigned long long total = (unsigned long long)draw->numDrawn * draw->numTriangles; // the CAPACITY's lanes
-    if (total && (!draw->dVertices || !draw->dIndices || !dInstances)) return surf_refuse(ctx, "sailor_hip_surface_draw_indirect: a vertex, index or instance buffer is NULL");
-    if (total > 0x7FFFFFFFull || (unsigned long long)draw->primBase + 2ull * total >= 0xFFFFFFFFull)
-        return surf_refuse(ctx, "sailor_hip_surface_draw_indirect: primBase + the capacity's primitives reaches 2^32 - 1");
-    Mat4 P, V;
-    memcpy(P.m, frame->projection, 64);
-    memcpy(V.m, frame->view, 64);
+    SurfDrawSetup s; // (the grid and its slices from the capacity: the count is not known here)
+    if (const int st = surf_draw_prologue(ctx, "sailor_hip_surface_draw_indirect", SAILOR_SURFACE_CULL_BACK | SAILOR_SURFACE_ALPHA_CUTOUT | SAILOR_SURFACE_GLTF, false, &dCommand,
+                                          frame, draw, dInstances, surf_tables_ok(dMaterials, numMaterials, dTextures, numTextures), drawIndex, width, height, band, dWorkspace,
+                                          workspaceBytes, s))
+        return st;
     SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
-    const unsigned long long blocks = total ? (total + 255) / 256 : 1; // (an empty draw still leaves its descriptor)
-    const unsigned long long want = total ? SURF_SLICE_LANES / total : 1; // the slices of sailor_hip_surface_draw, from the capacity: the count is not known here
-    const unsigned slices = (unsigned)(want < 1 ? 1 : (want > SURF_SLICES_MAX ? SURF_SLICES_MAX : want));
     const uint32_t* command = reinterpret_cast<const uint32_t*>(dCommand);
     if (draw->flags & SAILOR_SURFACE_GLTF) {
-        sailor_launch(ctx, k_surface_visibility_indirect_gltf, dim3((unsigned)blocks, slices), dim3(256), P, V, *draw, command, numInstanceRecords,
-                      reinterpret_cast<const float*>(dInstances), dMaterials, numMaterials, dTextures, numTextures, drawIndex, (int)width, (int)height,
-                      (int)band->fbRowBegin, (int)band->fbRowCount, dWorkspace);
+        sailor_launch(ctx, k_surface_visibility_indirect_gltf, s.grid, dim3(256), s.P, s.V, *draw, command, numInstanceRecords, reinterpret_cast<const float*>(dInstances),
+                      dMaterials, numMaterials, dTextures, numTextures, drawIndex, (int)width, (int)height, (int)band->fbRowBegin, (int)band->fbRowCount, dWorkspace);
         SAILOR_CHECK_LAUNCH(ctx, "k_surface_visibility_indirect_gltf");
     } else {
-        sailor_launch(ctx, k_surface_visibility_indirect, dim3((unsigned)blocks, slices), dim3(256), P, V, *draw, command, numInstanceRecords,
-                      reinterpret_cast<const float*>(dInstances), dMaterials, numMaterials, dTextures, numTextures, drawIndex, (int)width, (int)height,
-                      (int)band->fbRowBegin, (int)band->fbRowCount, dWorkspace);
+        sailor_launch(ctx, k_surface_visibility_indirect, s.grid, dim3(256), s.P, s.V, *draw, command, numInstanceRecords, reinterpret_cast<const float*>(dInstances),
+                      dMaterials, numMaterials, dTextures, numTextures, drawIndex, (int)width, (int)height, (int)band->fbRowBegin, (int)band->fbRowCount, dWorkspace);
         SAILOR_CHECK_LAUNCH(ctx, "k_surface_visibility_indirect");
     }
     return SAILOR_HIP_OK;

@@ -40,29 +40,13 @@ int sailor_hip_surface_draw_masked(SailorHipContext* ctx, const SailorUboFrameDa
                                    const SailorMaterialData* dMaterials, uint32_t numMaterials, const SailorTextureDesc* dTextures, uint32_t numTextures,
                                    uint32_t drawIndex, int32_t width, int32_t height, const SailorBand* band, void* dWorkspace, size_t workspaceBytes)
 {
-    if (!ctx) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    if (!frame || !draw) return surf_refuse(ctx, "sailor_hip_surface_draw_masked: frame or draw is NULL");
-    if (!surf_band_ok(width, height, band)) return surf_refuse(ctx, "sailor_hip_surface_draw_masked: the band is not valid for the frame");
-    if (!aligned(dWorkspace, 16)) return surf_refuse(ctx, "sailor_hip_surface_draw_masked: the workspace is NULL or not 16-byte aligned");
-    const uint32_t maxDraws = surf_max_draws(width, band, workspaceBytes);
-    if (maxDraws == 0) return surf_refuse(ctx, "sailor_hip_surface_draw_masked: the workspace is too small");
-    if (drawIndex >= maxDraws) return surf_refuse(ctx, "sailor_hip_surface_draw_masked: drawIndex is beyond the workspace's descriptor slots");
-    if (draw->flags & ~(SAILOR_SURFACE_CULL_BACK | SAILOR_SURFACE_ALPHA_CUTOUT)) return surf_refuse(ctx, "sailor_hip_surface_draw_masked: unknown flags");
-    if ((draw->flags & SAILOR_SURFACE_ALPHA_CUTOUT) && (!dMaterials || !dTextures || numMaterials == 0 || numTextures == 0))
-        return surf_refuse(ctx, "sailor_hip_surface_draw_masked: ALPHA_CUTOUT needs materials and textures");
-    const unsigned long long total = (unsigned long long)draw->numDrawn * draw->numTriangles;
-    if (total && (!draw->dVertices || !draw->dIndices || !dInstances)) return surf_refuse(ctx, "sailor_hip_surface_draw_masked: a vertex, index or instance buffer is NULL");
-    if (total > 0x7FFFFFFFull || (unsigned long long)draw->primBase + 2ull * total >= 0xFFFFFFFFull)
-        return surf_refuse(ctx, "sailor_hip_surface_draw_masked: primBase + the draw's primitives reaches 2^32 - 1");
-    Mat4 P, V;
-    memcpy(P.m, frame->projection, 64);
-    memcpy(V.m, frame->view, 64);
+    SurfDrawSetup s;
+    if (const int st = surf_draw_prologue(ctx, "sailor_hip_surface_draw_masked", SAILOR_SURFACE_CULL_BACK | SAILOR_SURFACE_ALPHA_CUTOUT, false, nullptr, frame, draw, dInstances,
+                                          surf_tables_ok(dMaterials, numMaterials, dTextures, numTextures), drawIndex, width, height, band, dWorkspace, workspaceBytes, s))
+        return st;
     SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
-    const unsigned long long blocks = total ? (total + 255) / 256 : 1; // (an empty draw still leaves its descriptor)
-    const unsigned long long want = total ? SURF_SLICE_LANES / total : 1; // the slices of sailor_hip_surface_draw
-    const unsigned slices = (unsigned)(want < 1 ? 1 : (want > SURF_SLICES_MAX ? SURF_SLICES_MAX : want));
-    sailor_launch(ctx, k_surface_visibility_masked, dim3((unsigned)blocks, slices), dim3(256), P, V, *draw, reinterpret_cast<const float*>(dInstances), dMaterials, numMaterials,
-                  dTextures, numTextures, drawIndex, (int)width, (int)height, (int)band->fbRowBegin, (int)band->fbRowCount, dWorkspace);
+    sailor_launch(ctx, k_surface_visibility_masked, s.grid, dim3(256), s.P, s.V, *draw, reinterpret_cast<const float*>(dInstances), dMaterials, numMaterials, dTextures,
+                  numTextures, drawIndex, (int)width, (int)height, (int)band->fbRowBegin, (int)band->fbRowCount, dWorkspace);
     SAILOR_CHECK_LAUNCH(ctx, "k_surface_visibility_masked");
     return SAILOR_HIP_OK;
 }
@@ -70,10 +54,9 @@ int sailor_hip_surface_draw_masked(SailorHipContext* ctx, const SailorUboFrameDa
 int sailor_hip_surface_store_depth(SailorHipContext* ctx, const void* dWorkspace, size_t workspaceBytes, float* dDepth, int32_t width, int32_t height, const SailorBand* band)
 {
     if (!ctx) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    if (!surf_band_ok(width, height, band)) return surf_refuse(ctx, "sailor_hip_surface_store_depth: the band is not valid for the frame");
-    if (!aligned(dWorkspace, 16) || surf_max_draws(width, band, workspaceBytes) == 0)
-        return surf_refuse(ctx, "sailor_hip_surface_store_depth: the workspace is NULL, misaligned or too small");
-    if (!aligned(dDepth, 4)) return surf_refuse(ctx, "sailor_hip_surface_store_depth: the depth attachment is NULL or not 4-byte aligned");
+    const char* why = surf_workspace_why(width, height, band, dWorkspace, workspaceBytes, false);
+    if (!why && !aligned(dDepth, 4)) why = "the depth attachment is NULL or not 4-byte aligned";
+    if (why) return surf_refuse(ctx, "sailor_hip_surface_store_depth", why);
     SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
     sailor_launch(ctx, k_surface_store_depth, texel_grid(width, band->fbRowCount), dim3(256), dWorkspace, dDepth, (int)width, (int)band->fbRowBegin, (int)band->fbRowCount);
     SAILOR_CHECK_LAUNCH(ctx, "k_surface_store_depth");

@@ -342,7 +342,7 @@ int sailor_hip_ui_draw(SailorHipContext* ctx, const SailorVertexP2UV2C1* dVertic
     if (!why && triangles && (!aligned(dVertices, 4) || !numVertices)) why = "the vertex buffer is NULL, empty or not 4-byte aligned";
     if (!why && triangles && !aligned(dIndices, indexBytes)) why = "the index buffer is NULL or not aligned to its index width";
     if (!why && workspaceBytes < ui_workspace_bytes((size_t)triangles)) why = "the workspace is smaller than sailor_hip_ui_workspace_bytes answers";
-    if (why) return surf_refuse(ctx, (std::string("sailor_hip_ui_draw: ") + why).c_str());
+    if (why) return surf_refuse(ctx, "sailor_hip_ui_draw", why);
     if (triangles == 0 || band->fbRowCount == 0) return SAILOR_HIP_OK; // nothing to record
     UiDraw d;
     d.vertices = dVertices; d.indices = dIndices; d.commands = dCommands;

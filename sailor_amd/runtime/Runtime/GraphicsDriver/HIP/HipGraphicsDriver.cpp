@@ -909,66 +909,94 @@ static RHIBufferPtr scene_buffer(const TVector<RHIShaderBindingSetPtr>& bindings
     return RHIBufferPtr();
 }
 
-int HipGraphicsDriver::RecordSurfaceDraw(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& color, const RHITexturePtr& depth, const RHIBufferPtr& vertices,
-                                         const RHIBufferPtr& indices, bool first, uint32_t drawIndex, uint32_t indexCount, uint32_t instanceCount, uint32_t firstIndex,
-                                         uint32_t vertexOffset, uint32_t firstInstance, uint32_t flags)
+// the `material` / `textureSamplers` tables of the bound sets as the C entries take them: NULL / 0 where a table is not bound
+struct SurfaceTables {
+    const SailorMaterialData* materials = nullptr; uint32_t numMaterials = 0;
+    const SailorTextureDesc* textures = nullptr; uint32_t numTextures = 0;
+    bool bound = false; // both tables are
+};
+static SurfaceTables surface_tables(const TVector<RHIShaderBindingSetPtr>& bindings)
+{
+    SurfaceTables t;
+    RHIBufferPtr materials = scene_buffer(bindings, "material"), textures = scene_buffer(bindings, "textureSamplers");
+    if (materials) { t.materials = (const SailorMaterialData*)materials->m_hip.m_devicePtr; t.numMaterials = (uint32_t)(materials->m_size / sizeof(SailorMaterialData)); }
+    if (textures) { t.textures = (const SailorTextureDesc*)textures->m_hip.m_devicePtr; t.numTextures = (uint32_t)(textures->m_size / sizeof(SailorTextureDesc)); }
+    t.bound = materials && textures;
+    return t;
+}
+
+int HipGraphicsDriver::SurfaceWorkspace(int W, int H, bool create, SurfacePass& pass)
+{
+    pass.W = W; pass.H = H;
+    sailor_hip_band_whole_frame(W, H, &pass.band);
+    pass.bytes = sailor_hip_surface_workspace_bytes(W, H, &pass.band, SURFACE_MAX_DRAWS);
+    if (create && (!m_surfaceWorkspace || m_surfaceWorkspace->m_size != pass.bytes)) m_surfaceWorkspace = CreateBuffer(pass.bytes);
+    return create && !m_surfaceWorkspace ? SAILOR_HIP_ERR_OUT_OF_MEMORY : SAILOR_HIP_OK;
+}
+
+template <typename Issue>
+int HipGraphicsDriver::RecordSurfacePassDraw(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& color, const RHITexturePtr& depth, bool first, bool needColor,
+                                             bool clearDepth, bool buffersBound, bool rangesOk, Issue&& issue)
 {
     if (first) m_surfaceBegun = false;
-    SailorUboFrameData frame;
-    RHIBufferPtr instances = scene_buffer(bindings, "data");
-    if (bindings.empty() || !host_copy_of(bindings[0], "frameData", frame) || !color || !color->m_buffer || !vertices || !indices || !instances)
+    SurfacePass pass;
+    const RHITexturePtr& extentOf = (color || needColor) ? color : depth; // a depth-only pass has the depth attachment's extent
+    if (bindings.empty() || !host_copy_of(bindings[0], "frameData", pass.frame) || !extentOf || !extentOf->m_buffer || !buffersBound)
         return SAILOR_HIP_ERR_INVALID_ARGUMENT; // a missing binding
     if (m_worldSize > 1) return SAILOR_HIP_ERR_UNSUPPORTED; // (the pass runs on whole frames here)
-    const int W = color->GetExtent().x, H = color->GetExtent().y;
-    if (W != frame.viewportSize[0] || H != frame.viewportSize[1] || color->m_format != EFormat::R32G32B32A32_SFLOAT) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    const int W = extentOf->GetExtent().x, H = extentOf->GetExtent().y;
+    if (W != pass.frame.viewportSize[0] || H != pass.frame.viewportSize[1] || (color && color->m_format != EFormat::R32G32B32A32_SFLOAT)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     if (depth && (depth->GetExtent().x != W || depth->GetExtent().y != H || depth->m_format != EFormat::R32_SFLOAT || !depth->m_buffer)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    if ((size_t)firstIndex + indexCount > indices->m_size / 4 || ((size_t)firstInstance + instanceCount) * sizeof(SailorPerInstanceData) > instances->m_size ||
-        (size_t)vertexOffset * sizeof(SailorVertexP3N3T3B3UV2C4) > vertices->m_size)
-        return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    SailorBand band;
-    sailor_hip_band_whole_frame(W, H, &band);
-    const size_t bytes = sailor_hip_surface_workspace_bytes(W, H, &band, SURFACE_MAX_DRAWS);
+    if (!rangesOk) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    int st = SurfaceWorkspace(W, H, first, pass);
+    if (st != SAILOR_HIP_OK) return st;
     if (first) {
-        if (!m_surfaceWorkspace || m_surfaceWorkspace->m_size != bytes) m_surfaceWorkspace = CreateBuffer(bytes);
-        if (!m_surfaceWorkspace) return SAILOR_HIP_ERR_OUT_OF_MEMORY;
-        // BeginRenderPass(Main, DepthBuffer): the keys start from the prepass depth (GreaterOrEqual, RHI/Types.h:536-537)
-        const int st = sailor_hip_surface_begin(m_ctx, depth ? (const float*)depth->m_buffer->m_hip.m_devicePtr : nullptr, W, H, &band, m_surfaceWorkspace->m_hip.m_devicePtr, bytes);
+        // BeginRenderPass(Main, DepthBuffer): the keys start from the prepass depth (GreaterOrEqual, RHI/Types.h:536-537), or from cleared keys when the pass
+        // clears depth (DepthPrepassNode's `ClearDepth`)
+        const float* start = (depth && !clearDepth) ? (const float*)depth->m_buffer->m_hip.m_devicePtr : nullptr;
+        st = sailor_hip_surface_begin(m_ctx, start, W, H, &pass.band, m_surfaceWorkspace->m_hip.m_devicePtr, pass.bytes);
         if (st != SAILOR_HIP_OK) return st;
         m_surfacePrimBase = 0;
         m_surfaceBegun = true;
     }
-    if (!m_surfaceBegun || !m_surfaceWorkspace || m_surfaceWorkspace->m_size != bytes || m_surfacePrimBase > 0xFFFFFFFFull) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (!m_surfaceBegun || !m_surfaceWorkspace || m_surfaceWorkspace->m_size != pass.bytes || m_surfacePrimBase > 0xFFFFFFFFull) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     SailorSurfaceDraw d {};
-    d.dVertices = (const SailorVertexP3N3T3B3UV2C4*)vertices->m_hip.m_devicePtr + vertexOffset;
-    d.dIndices = (const uint32_t*)indices->m_hip.m_devicePtr + firstIndex;
-    d.dInstanceIds = nullptr;
-    d.numTriangles = indexCount / 3; d.numDrawn = instanceCount; d.primBase = (uint32_t)m_surfacePrimBase;
-    d.flags = flags; // SAILOR_SURFACE_CULL_BACK: the reference's materials cull back faces (ECullMode::Back, frontFace counter-clockwise) unless double-sided
-    d.firstInstance = firstInstance;
-    int st;
-    if (flags & SAILOR_SURFACE_GLTF) { // Standard_glTF.shader: the tables are read by the draw only under ALPHA_CUTOUT, which requires them
-        RHIBufferPtr materials = scene_buffer(bindings, "material"), textures = scene_buffer(bindings, "textureSamplers");
-        if ((flags & SAILOR_SURFACE_ALPHA_CUTOUT) && (!materials || !textures)) { m_surfaceBegun = false; return SAILOR_HIP_ERR_INVALID_ARGUMENT; }
-        st = sailor_hip_surface_draw_gltf(m_ctx, &frame, &d, (const SailorPerInstanceData*)instances->m_hip.m_devicePtr,
-                                          materials ? (const SailorMaterialData*)materials->m_hip.m_devicePtr : nullptr,
-                                          materials ? (uint32_t)(materials->m_size / sizeof(SailorMaterialData)) : 0u,
-                                          textures ? (const SailorTextureDesc*)textures->m_hip.m_devicePtr : nullptr,
-                                          textures ? (uint32_t)(textures->m_size / sizeof(SailorTextureDesc)) : 0u, drawIndex, W, H, &band,
-                                          m_surfaceWorkspace->m_hip.m_devicePtr, bytes);
-    } else if (flags & SAILOR_SURFACE_ALPHA_CUTOUT) { // the ALPHA_CUTOUT permutation: `material` and `textureSamplers` of the bound sets decide the discard in the draw
-        RHIBufferPtr materials = scene_buffer(bindings, "material"), textures = scene_buffer(bindings, "textureSamplers");
-        if (!materials || !textures) { m_surfaceBegun = false; return SAILOR_HIP_ERR_INVALID_ARGUMENT; }
-        st = sailor_hip_surface_draw_masked(m_ctx, &frame, &d, (const SailorPerInstanceData*)instances->m_hip.m_devicePtr, (const SailorMaterialData*)materials->m_hip.m_devicePtr,
-                                            (uint32_t)(materials->m_size / sizeof(SailorMaterialData)), (const SailorTextureDesc*)textures->m_hip.m_devicePtr,
-                                            (uint32_t)(textures->m_size / sizeof(SailorTextureDesc)), drawIndex, W, H, &band, m_surfaceWorkspace->m_hip.m_devicePtr, bytes);
-    } else
-        st = sailor_hip_surface_draw(m_ctx, &frame, &d, (const SailorPerInstanceData*)instances->m_hip.m_devicePtr, drawIndex, W, H, &band,
-                                     m_surfaceWorkspace->m_hip.m_devicePtr, bytes);
+    d.primBase = (uint32_t)m_surfacePrimBase;
+    st = issue(pass, d);
     if (st != SAILOR_HIP_OK) { m_surfaceBegun = false; return st; }
     uint64_t prims = 0;
-    sailor_hip_surface_draw_prims(d.numTriangles, d.numDrawn, &prims);
+    sailor_hip_surface_draw_prims(d.numTriangles, d.numDrawn, &prims); // (of an indirect draw: the capacity's)
     m_surfacePrimBase += prims;
     return SAILOR_HIP_OK;
+}
+
+int HipGraphicsDriver::RecordSurfaceDraw(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& color, const RHITexturePtr& depth, const RHIBufferPtr& vertices,
+                                         const RHIBufferPtr& indices, bool first, uint32_t drawIndex, uint32_t indexCount, uint32_t instanceCount, uint32_t firstIndex,
+                                         uint32_t vertexOffset, uint32_t firstInstance, uint32_t flags)
+{
+    RHIBufferPtr instances = scene_buffer(bindings, "data");
+    const bool buffersBound = vertices && indices && instances;
+    const bool rangesOk = buffersBound && (size_t)firstIndex + indexCount <= indices->m_size / 4 &&
+                          ((size_t)firstInstance + instanceCount) * sizeof(SailorPerInstanceData) <= instances->m_size &&
+                          (size_t)vertexOffset * sizeof(SailorVertexP3N3T3B3UV2C4) <= vertices->m_size;
+    // the direct route needs a colour attachment and always starts the keys from the depth attachment
+    return RecordSurfacePassDraw(bindings, color, depth, first, true, false, buffersBound, rangesOk, [&](const SurfacePass& pass, SailorSurfaceDraw& d) {
+        d.dVertices = (const SailorVertexP3N3T3B3UV2C4*)vertices->m_hip.m_devicePtr + vertexOffset;
+        d.dIndices = (const uint32_t*)indices->m_hip.m_devicePtr + firstIndex;
+        d.numTriangles = indexCount / 3; d.numDrawn = instanceCount;
+        d.flags = flags; // SAILOR_SURFACE_CULL_BACK: the reference's materials cull back faces (ECullMode::Back, frontFace counter-clockwise) unless double-sided
+        d.firstInstance = firstInstance;
+        const SailorPerInstanceData* dInstances = (const SailorPerInstanceData*)instances->m_hip.m_devicePtr;
+        void* workspace = m_surfaceWorkspace->m_hip.m_devicePtr;
+        if (!(flags & (SAILOR_SURFACE_GLTF | SAILOR_SURFACE_ALPHA_CUTOUT)))
+            return sailor_hip_surface_draw(m_ctx, &pass.frame, &d, dInstances, drawIndex, pass.W, pass.H, &pass.band, workspace, pass.bytes);
+        // the ALPHA_CUTOUT permutation: `material` and `textureSamplers` of the bound sets decide the discard in the draw.  Standard_glTF.shader: the tables
+        // are read by the draw only under ALPHA_CUTOUT, which requires them
+        const SurfaceTables t = surface_tables(bindings);
+        if ((flags & SAILOR_SURFACE_ALPHA_CUTOUT) && !t.bound) return (int)SAILOR_HIP_ERR_INVALID_ARGUMENT;
+        return (flags & SAILOR_SURFACE_GLTF ? sailor_hip_surface_draw_gltf : sailor_hip_surface_draw_masked)(
+            m_ctx, &pass.frame, &d, dInstances, t.materials, t.numMaterials, t.textures, t.numTextures, drawIndex, pass.W, pass.H, &pass.band, workspace, pass.bytes);
+    });
 }
 
 // DebugContext::DrawDebugMesh's draw (DebugContext.cpp:391-397) inside DebugDrawNode's pass: the Gizmo material's state (:272: depth test and write,
@@ -987,11 +1015,9 @@ int HipGraphicsDriver::RecordDebugLines(const RHITexturePtr& color, const RHITex
     if ((indices && (size_t)firstIndex + indexCount > indices->m_size / 4) || (size_t)vertexOffset * sizeof(SailorVertexP3C4) > vertices->m_size ||
         (!indices && ((size_t)vertexOffset + firstIndex + indexCount) * sizeof(SailorVertexP3C4) > vertices->m_size))
         return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    SailorBand band;
-    sailor_hip_band_whole_frame(W, H, &band);
-    const size_t bytes = sailor_hip_surface_workspace_bytes(W, H, &band, SURFACE_MAX_DRAWS);
-    if (!m_surfaceWorkspace || m_surfaceWorkspace->m_size != bytes) m_surfaceWorkspace = CreateBuffer(bytes);
-    if (!m_surfaceWorkspace) return SAILOR_HIP_ERR_OUT_OF_MEMORY;
+    SurfacePass pass;
+    int st = SurfaceWorkspace(W, H, true, pass);
+    if (st != SAILOR_HIP_OK) return st;
     float viewProjection[16];
     memcpy(viewProjection, pushConstants.data(), 64);
     SailorDebugLinesDraw d {};
@@ -1000,13 +1026,14 @@ int HipGraphicsDriver::RecordDebugLines(const RHITexturePtr& color, const RHITex
     if (!indices) d.dVertices += firstIndex;
     d.numSegments = numSegments; d.primBase = 0;
     float* depthPtr = (float*)depth->m_buffer->m_hip.m_devicePtr;
-    int st = sailor_hip_surface_begin(m_ctx, depthPtr, W, H, &band, m_surfaceWorkspace->m_hip.m_devicePtr, bytes);
+    st = sailor_hip_surface_begin(m_ctx, depthPtr, W, H, &pass.band, m_surfaceWorkspace->m_hip.m_devicePtr, pass.bytes);
     if (st != SAILOR_HIP_OK) return st;
-    st = sailor_hip_debug_lines_draw(m_ctx, viewProjection, &d, W, H, &band, m_surfaceWorkspace->m_hip.m_devicePtr, bytes);
+    st = sailor_hip_debug_lines_draw(m_ctx, viewProjection, &d, W, H, &pass.band, m_surfaceWorkspace->m_hip.m_devicePtr, pass.bytes);
     if (st != SAILOR_HIP_OK) return st;
     BeforeBufferWrite(color->m_buffer->m_hip.m_devicePtr);
     BeforeBufferWrite(depthPtr);
-    return sailor_hip_debug_lines_resolve(m_ctx, viewProjection, &d, W, H, &band, m_surfaceWorkspace->m_hip.m_devicePtr, bytes, (float*)color->m_buffer->m_hip.m_devicePtr, depthPtr);
+    return sailor_hip_debug_lines_resolve(m_ctx, viewProjection, &d, W, H, &pass.band, m_surfaceWorkspace->m_hip.m_devicePtr, pass.bytes,
+                                          (float*)color->m_buffer->m_hip.m_devicePtr, depthPtr);
 }
 
 // Grows the workspace of the UI pass for draws of up to numTriangles triangles.  An allocation: called where draw data is handed over and where a pass is
@@ -1052,8 +1079,9 @@ int HipGraphicsDriver::RecordSurfaceEnd(const TVector<RHIShaderBindingSetPtr>& b
     if (!m_surfaceBegun) return SAILOR_HIP_ERR_INVALID_ARGUMENT; // a draw of the pass was refused: nothing to resolve
     m_surfaceBegun = false;
     SailorUboFrameData frame;
-    RHIBufferPtr instances = scene_buffer(bindings, "data"), materials = scene_buffer(bindings, "material"), textures = scene_buffer(bindings, "textureSamplers");
-    if (bindings.size() < 2 || !host_copy_of(bindings[0], "frameData", frame) || !color || !color->m_buffer || !instances || !materials || !textures)
+    RHIBufferPtr instances = scene_buffer(bindings, "data");
+    const SurfaceTables t = surface_tables(bindings);
+    if (bindings.size() < 2 || !host_copy_of(bindings[0], "frameData", frame) || !color || !color->m_buffer || !instances || !t.bound)
         return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     const int W = color->GetExtent().x, H = color->GetExtent().y;
     SailorBand band;
@@ -1071,16 +1099,12 @@ int HipGraphicsDriver::RecordSurfaceEnd(const TVector<RHIShaderBindingSetPtr>& b
         if (!m_surfaceAo || !m_surfaceEmissive) return SAILOR_HIP_ERR_OUT_OF_MEMORY;
         auto ao = bindings[1] ? bound_texture(bindings[1], "g_aoSampler") : RHITexturePtr();
         const float* aoIn = (ao && ao->m_extent.x == W && ao->m_extent.y == H) ? (const float*)ao->m_buffer->m_hip.m_devicePtr : nullptr;
-        st = sailor_hip_surface_resolve_gltf(m_ctx, &frame, (const SailorPerInstanceData*)instances->m_hip.m_devicePtr, (const SailorMaterialData*)materials->m_hip.m_devicePtr,
-                                             (uint32_t)(materials->m_size / sizeof(SailorMaterialData)), (const SailorTextureDesc*)textures->m_hip.m_devicePtr,
-                                             (uint32_t)(textures->m_size / sizeof(SailorTextureDesc)), W, H, &band, m_surfaceWorkspace->m_hip.m_devicePtr, bytes,
-                                             (float*)m_surfacePlanes->m_hip.m_devicePtr, pixels, nullptr, nullptr, aoIn, (float*)m_surfaceAo->m_hip.m_devicePtr,
-                                             (float*)m_surfaceEmissive->m_hip.m_devicePtr);
+        st = sailor_hip_surface_resolve_gltf(m_ctx, &frame, (const SailorPerInstanceData*)instances->m_hip.m_devicePtr, t.materials, t.numMaterials, t.textures, t.numTextures,
+                                             W, H, &band, m_surfaceWorkspace->m_hip.m_devicePtr, bytes, (float*)m_surfacePlanes->m_hip.m_devicePtr, pixels, nullptr, nullptr,
+                                             aoIn, (float*)m_surfaceAo->m_hip.m_devicePtr, (float*)m_surfaceEmissive->m_hip.m_devicePtr);
     } else
-        st = sailor_hip_surface_resolve(m_ctx, &frame, (const SailorPerInstanceData*)instances->m_hip.m_devicePtr, (const SailorMaterialData*)materials->m_hip.m_devicePtr,
-                                        (uint32_t)(materials->m_size / sizeof(SailorMaterialData)), (const SailorTextureDesc*)textures->m_hip.m_devicePtr,
-                                        (uint32_t)(textures->m_size / sizeof(SailorTextureDesc)), W, H, &band, m_surfaceWorkspace->m_hip.m_devicePtr, bytes,
-                                        (float*)m_surfacePlanes->m_hip.m_devicePtr, pixels, nullptr, nullptr);
+        st = sailor_hip_surface_resolve(m_ctx, &frame, (const SailorPerInstanceData*)instances->m_hip.m_devicePtr, t.materials, t.numMaterials, t.textures, t.numTextures, W, H,
+                                        &band, m_surfaceWorkspace->m_hip.m_devicePtr, bytes, (float*)m_surfacePlanes->m_hip.m_devicePtr, pixels, nullptr, nullptr);
     if (st != SAILOR_HIP_OK) return st;
     // the rest of the fragment stage: the shade over the planes, exactly as over a caller's surface
     auto own = RHIShaderBindingSetPtr::Make();
@@ -1196,6 +1220,18 @@ void HipGraphicsDriver::BindShaderBindings(RHICommandListPtr cmd, RHIMaterialPtr
     cmd->m_boundBindings = bindings;
 }
 
+// The flag word of a surface draw from the bound material (shader `name`): m_bDoubleSided = no back-face cull; the { "ALPHA_CUTOUT" } permutation of
+// Standard.shader goes to sailor_hip_surface_draw_masked, Standard_glTF.shader (an imported model's, with or without the define) to sailor_hip_surface_draw_gltf;
+// DepthOnly.shader has neither.  What the pass has to do at its end for them (store the depth, the glTF resolve) is noted on the command list.
+static uint32_t surface_draw_flags(const RHICommandListPtr& cmd, const std::string& name)
+{
+    const bool gltf = name == "Shaders/Standard_glTF.shader", standard = gltf || name == "Shaders/Standard.shader";
+    const bool cutout = standard && cmd->m_boundMaterial->m_shader->HasDefine("ALPHA_CUTOUT");
+    if (cutout) cmd->m_surfaceCutout = true;
+    if (gltf) cmd->m_surfaceGltf = true;
+    return (cmd->m_boundMaterial->m_bDoubleSided ? 0u : SAILOR_SURFACE_CULL_BACK) | (cutout ? SAILOR_SURFACE_ALPHA_CUTOUT : 0u) | (gltf ? SAILOR_SURFACE_GLTF : 0u);
+}
+
 void HipGraphicsDriver::DrawIndexed(RHICommandListPtr cmd, uint32_t indexCount, uint32_t instanceCount, uint32_t firstIndex, uint32_t vertexOffset, uint32_t firstInstance)
 {
     const std::string name = (cmd->m_boundMaterial && cmd->m_boundMaterial->m_shader) ? cmd->m_boundMaterial->m_shader->m_name : std::string();
@@ -1234,13 +1270,7 @@ void HipGraphicsDriver::DrawIndexed(RHICommandListPtr cmd, uint32_t indexCount, 
         RHIBufferPtr vb = cmd->m_vertexBuffer, ib = cmd->m_indexBuffer;
         TVector<RHIShaderBindingSetPtr> bindings = cmd->m_boundBindings;
         const uint32_t drawIndex = cmd->m_surfaceDraws++;
-        // the permutation and the cull mode of the bound material: { "ALPHA_CUTOUT" } goes to sailor_hip_surface_draw_masked, Standard_glTF.shader (an imported
-        // model's, with or without the define) to sailor_hip_surface_draw_gltf
-        const uint32_t flags = (cmd->m_boundMaterial->m_bDoubleSided ? 0u : SAILOR_SURFACE_CULL_BACK) |
-                               (cmd->m_boundMaterial->m_shader->HasDefine("ALPHA_CUTOUT") ? SAILOR_SURFACE_ALPHA_CUTOUT : 0u) |
-                               (name == "Shaders/Standard_glTF.shader" ? SAILOR_SURFACE_GLTF : 0u);
-        if (flags & SAILOR_SURFACE_ALPHA_CUTOUT) cmd->m_surfaceCutout = true;
-        if (flags & SAILOR_SURFACE_GLTF) cmd->m_surfaceGltf = true;
+        const uint32_t flags = surface_draw_flags(cmd, name);
         cmd->m_hip.m_commands.push_back([this, bindings, color, depth, vb, ib, drawIndex, indexCount, instanceCount, firstIndex, vertexOffset, firstInstance, flags]() {
             return RecordSurfaceDraw(bindings, color, depth, vb, ib, drawIndex == 0, drawIndex, indexCount, instanceCount, firstIndex, vertexOffset, firstInstance, flags);
         });
@@ -1359,9 +1389,6 @@ void HipGraphicsDriver::DrawIndexedIndirect(RHICommandListPtr cmd, RHIBufferPtr 
     RHIBufferPtr vb = cmd->m_vertexBuffer, ib = cmd->m_indexBuffer;
     TVector<RHIShaderBindingSetPtr> bindings = cmd->m_boundBindings;
     const bool clearDepth = cmd->m_bClearDepth;
-    const uint32_t flags = (cmd->m_boundMaterial->m_bDoubleSided ? 0u : SAILOR_SURFACE_CULL_BACK) |
-                           (standard && cmd->m_boundMaterial->m_shader->HasDefine("ALPHA_CUTOUT") ? SAILOR_SURFACE_ALPHA_CUTOUT : 0u) |
-                           (name == "Shaders/Standard_glTF.shader" ? SAILOR_SURFACE_GLTF : 0u);
     for (uint32_t i = 0; i < drawCount; i++) {
         const size_t at = offset + (size_t)i * stride;
         if (!buffer || !buffer->m_bIndirect || at > buffer->m_hostCopy.size() || buffer->m_hostCopy.size() - at < sizeof(SailorDrawIndexedIndirectData)) {
@@ -1371,8 +1398,7 @@ void HipGraphicsDriver::DrawIndexedIndirect(RHICommandListPtr cmd, RHIBufferPtr 
         SailorDrawIndexedIndirectData host; // the command as the host wrote it, at record time
         memcpy(&host, buffer->m_hostCopy.data() + at, sizeof host);
         const uint32_t drawIndex = cmd->m_surfaceDraws++;
-        if (flags & SAILOR_SURFACE_ALPHA_CUTOUT) cmd->m_surfaceCutout = true;
-        if (flags & SAILOR_SURFACE_GLTF) cmd->m_surfaceGltf = true;
+        const uint32_t flags = surface_draw_flags(cmd, name); // (here: a command that is not recorded leaves no note on the pass)
         cmd->m_hip.m_commands.push_back([this, bindings, color, depth, vb, ib, drawIndex, clearDepth, host, buffer, at, flags]() {
             return RecordSurfaceDrawIndirect(bindings, color, depth, vb, ib, drawIndex == 0, clearDepth, drawIndex, host, buffer, at, flags);
         });
@@ -1383,54 +1409,24 @@ int HipGraphicsDriver::RecordSurfaceDrawIndirect(const TVector<RHIShaderBindingS
                                                  const RHIBufferPtr& vertices, const RHIBufferPtr& indices, bool first, bool clearDepth, uint32_t drawIndex,
                                                  const SailorDrawIndexedIndirectData& host, const RHIBufferPtr& command, size_t commandOffset, uint32_t flags)
 {
-    if (first) m_surfaceBegun = false;
-    SailorUboFrameData frame;
     RHIBufferPtr instances = scene_buffer(bindings, "data");
-    const RHITexturePtr& extentOf = color ? color : depth; // a depth-only pass has the depth attachment's extent
-    if (bindings.empty() || !host_copy_of(bindings[0], "frameData", frame) || !extentOf || !extentOf->m_buffer || !vertices || !indices || !instances || !command)
-        return SAILOR_HIP_ERR_INVALID_ARGUMENT; // a missing binding
-    if (m_worldSize > 1) return SAILOR_HIP_ERR_UNSUPPORTED; // (the pass runs on whole frames here, as the direct route)
-    const int W = extentOf->GetExtent().x, H = extentOf->GetExtent().y;
-    if (W != frame.viewportSize[0] || H != frame.viewportSize[1] || (color && color->m_format != EFormat::R32G32B32A32_SFLOAT)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    if (depth && (depth->GetExtent().x != W || depth->GetExtent().y != H || depth->m_format != EFormat::R32_SFLOAT || !depth->m_buffer)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    if ((size_t)host.firstIndex + host.indexCount > indices->m_size / 4 || host.vertexOffset < 0 ||
-        (size_t)host.vertexOffset * sizeof(SailorVertexP3N3T3B3UV2C4) > vertices->m_size || commandOffset % 4 != 0 ||
-        commandOffset + sizeof(SailorDrawIndexedIndirectData) > command->m_size)
-        return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    SailorBand band;
-    sailor_hip_band_whole_frame(W, H, &band);
-    const size_t bytes = sailor_hip_surface_workspace_bytes(W, H, &band, SURFACE_MAX_DRAWS);
-    if (first) {
-        if (!m_surfaceWorkspace || m_surfaceWorkspace->m_size != bytes) m_surfaceWorkspace = CreateBuffer(bytes);
-        if (!m_surfaceWorkspace) return SAILOR_HIP_ERR_OUT_OF_MEMORY;
-        // the keys start from the depth attachment, or from cleared keys when the pass clears depth (DepthPrepassNode's `ClearDepth`)
-        const float* start = (depth && !clearDepth) ? (const float*)depth->m_buffer->m_hip.m_devicePtr : nullptr;
-        const int st = sailor_hip_surface_begin(m_ctx, start, W, H, &band, m_surfaceWorkspace->m_hip.m_devicePtr, bytes);
-        if (st != SAILOR_HIP_OK) return st;
-        m_surfacePrimBase = 0;
-        m_surfaceBegun = true;
-    }
-    if (!m_surfaceBegun || !m_surfaceWorkspace || m_surfaceWorkspace->m_size != bytes || m_surfacePrimBase > 0xFFFFFFFFull) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    SailorSurfaceDraw d {};
-    d.dVertices = (const SailorVertexP3N3T3B3UV2C4*)vertices->m_hip.m_devicePtr + host.vertexOffset;
-    d.dIndices = (const uint32_t*)indices->m_hip.m_devicePtr + host.firstIndex;
-    d.numTriangles = host.indexCount / 3; d.numDrawn = host.instanceCount; // the capacity: the un-culled count the host wrote
-    d.primBase = (uint32_t)m_surfacePrimBase;
-    d.flags = flags;
-    RHIBufferPtr materials = scene_buffer(bindings, "material"), textures = scene_buffer(bindings, "textureSamplers");
-    if ((flags & SAILOR_SURFACE_ALPHA_CUTOUT) && (!materials || !textures)) { m_surfaceBegun = false; return SAILOR_HIP_ERR_INVALID_ARGUMENT; }
-    const int st = sailor_hip_surface_draw_indirect(m_ctx, &frame, &d, (const SailorDrawIndexedIndirectData*)((const uint8_t*)command->m_hip.m_devicePtr + commandOffset),
-                                                    (const SailorPerInstanceData*)instances->m_hip.m_devicePtr, (uint32_t)(instances->m_size / sizeof(SailorPerInstanceData)),
-                                                    materials ? (const SailorMaterialData*)materials->m_hip.m_devicePtr : nullptr,
-                                                    materials ? (uint32_t)(materials->m_size / sizeof(SailorMaterialData)) : 0u,
-                                                    textures ? (const SailorTextureDesc*)textures->m_hip.m_devicePtr : nullptr,
-                                                    textures ? (uint32_t)(textures->m_size / sizeof(SailorTextureDesc)) : 0u, drawIndex, W, H, &band,
-                                                    m_surfaceWorkspace->m_hip.m_devicePtr, bytes);
-    if (st != SAILOR_HIP_OK) { m_surfaceBegun = false; return st; }
-    uint64_t prims = 0;
-    sailor_hip_surface_draw_prims(d.numTriangles, d.numDrawn, &prims); // the next draw's primBase advances by the capacity
-    m_surfacePrimBase += prims;
-    return SAILOR_HIP_OK;
+    const bool buffersBound = vertices && indices && instances && command;
+    // (the instance range is the kernel's to check: it is handed the number of records)
+    const bool rangesOk = buffersBound && (size_t)host.firstIndex + host.indexCount <= indices->m_size / 4 && host.vertexOffset >= 0 &&
+                          (size_t)host.vertexOffset * sizeof(SailorVertexP3N3T3B3UV2C4) <= vertices->m_size && commandOffset % 4 == 0 &&
+                          commandOffset + sizeof(SailorDrawIndexedIndirectData) <= command->m_size;
+    return RecordSurfacePassDraw(bindings, color, depth, first, false, clearDepth, buffersBound, rangesOk, [&](const SurfacePass& pass, SailorSurfaceDraw& d) {
+        d.dVertices = (const SailorVertexP3N3T3B3UV2C4*)vertices->m_hip.m_devicePtr + host.vertexOffset;
+        d.dIndices = (const uint32_t*)indices->m_hip.m_devicePtr + host.firstIndex;
+        d.numTriangles = host.indexCount / 3; d.numDrawn = host.instanceCount; // the capacity: the un-culled count the host wrote
+        d.flags = flags;
+        const SurfaceTables t = surface_tables(bindings);
+        if ((flags & SAILOR_SURFACE_ALPHA_CUTOUT) && !t.bound) return (int)SAILOR_HIP_ERR_INVALID_ARGUMENT;
+        return sailor_hip_surface_draw_indirect(m_ctx, &pass.frame, &d, (const SailorDrawIndexedIndirectData*)((const uint8_t*)command->m_hip.m_devicePtr + commandOffset),
+                                                (const SailorPerInstanceData*)instances->m_hip.m_devicePtr, (uint32_t)(instances->m_size / sizeof(SailorPerInstanceData)),
+                                                t.materials, t.numMaterials, t.textures, t.numTextures, drawIndex, pass.W, pass.H, &pass.band,
+                                                m_surfaceWorkspace->m_hip.m_devicePtr, pass.bytes);
+    });
 }
 
 int HipGraphicsDriver::RecordSurfaceEndDepthOnly(const RHITexturePtr& depth)

@@ -187,6 +187,18 @@ public:
 private:
     int RecordLightCulling(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const TVector<uint8_t>& pc);
     int RecordShade(const TVector<RHI::RHIShaderBindingSetPtr>& bindings);
+    // The surface pass a recorded draw works in: the frame data of set 0, the attachments' extent, the whole-frame band and the workspace's size.
+    struct SurfacePass { SailorUboFrameData frame; int W = 0, H = 0; SailorBand band {}; size_t bytes = 0; };
+    // the band and the size of the surface workspace of a W x H pass; `create`: m_surfaceWorkspace is (re)created at that size
+    int SurfaceWorkspace(int W, int H, bool create, SurfacePass& pass);
+    // Begins (first) or continues the pass for one recorded draw and records the draw.  Checks in this order: the bindings and the draw's own buffers
+    // (buffersBound), the frame split, the attachments (needColor: a pass without a colour attachment is refused, else it is a depth-only pass of the depth
+    // attachment's extent), the draw's host-side ranges (rangesOk).  On `first` the workspace is created and the keys start from the depth attachment, or
+    // from cleared keys if clearDepth.  `issue(pass, d)` then completes the descriptor d (primBase is set) and calls the C entry; a draw it refuses
+    // un-begins the pass (RecordSurfaceEnd then has nothing to resolve), one it records advances the pass's primBase.
+    template <typename Issue>
+    int RecordSurfacePassDraw(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& color, const RHI::RHITexturePtr& depth, bool first,
+                              bool needColor, bool clearDepth, bool buffersBound, bool rangesOk, Issue&& issue);
     int RecordSurfaceDraw(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& color, const RHI::RHITexturePtr& depth,
                           const RHI::RHIBufferPtr& vertices, const RHI::RHIBufferPtr& indices, bool first, uint32_t drawIndex, uint32_t indexCount,
                           uint32_t instanceCount, uint32_t firstIndex, uint32_t vertexOffset, uint32_t firstInstance, uint32_t flags);
