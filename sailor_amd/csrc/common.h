@@ -10,10 +10,7 @@
 
 #define SAILOR_HIP_BUILD 1
 #include "../../include/sailor_hip.h"
-
-#define TILE SAILOR_LIGHTS_CULLING_TILE_SIZE
-#define CAND SAILOR_LIGHTS_CANDIDATES_PER_TILE
-#define KEEP SAILOR_LIGHTS_PER_TILE
+#include "host_rules.h" // TILE / CAND / KEEP, align_up, the band rule, the large-set threshold, the environment knobs: plain C++
 
 struct SailorHipContext {
     int device = 0;
@@ -77,8 +74,6 @@ static inline int sailor_map_hip_error(SailorHipContext* ctx, hipError_t e, cons
         hipError_t _e = hipGetLastError();                                          \
         if (_e != hipSuccess) return sailor_map_hip_error((ctx), _e, name);         \
     } while (0)
-
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // Every kernel of the path is launched through this: an ordinary launch on the context's stream, or -- while timing slots are armed
 // (sailor_hip_context_time_launches) -- the same launch with a start / stop event pair attached to ITS dispatch packet (hipExtLaunchKernel): the

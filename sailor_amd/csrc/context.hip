@@ -273,18 +273,10 @@ int sailor_hip_num_tiles(int32_t width, int32_t height, int32_t* outTilesX, int3
     return SAILOR_HIP_OK;
 }
 
-static void band_from_rows(int32_t height, int32_t r0, int32_t r1, SailorBand* b)
+// (the band rule itself: host_rules.h)
+int sailor_hip_band_is_valid(int32_t width, int32_t height, const SailorBand* band)
 {
-    b->tileRowBegin = r0;
-    b->tileRowEnd = r1;
-    // tile row t covers framebuffer rows H-1-16t-15 .. H-1-16t, clamped to [0, H)
-    int32_t lo = height - TILE * r1;
-    int32_t hi = height - TILE * r0;
-    if (lo < 0) lo = 0;
-    if (hi > height) hi = height;
-    if (hi < lo) hi = lo;
-    b->fbRowBegin = lo;
-    b->fbRowCount = hi - lo;
+    return (width > 0 && height > 0 && band_is_valid(height, band)) ? 1 : 0;
 }
 
 int sailor_hip_band_whole_frame(int32_t width, int32_t height, SailorBand* outBand)

@@ -51,81 +51,16 @@
 //
 // No MFMA: sphere/plane tests and compaction, not a contraction.  Compiled with -ffp-contract=off.
 #include "common.h"
+#include "cull_plan.h" // CullLayout, CullPlan and the constants both depend on (BANDS_PER_BLOCK, GROUP, CAPG, HEAVY_*, PACK_TILES, SEL_LIGHTS, SETUP_STRIPS, GLW_ROWS)
 #include "light_record.h"
 #include <vector>
 
-#define BANDS_PER_BLOCK 24   // group columns / rows whose masks one light block of k01_prepare builds when the lights alone do not fill the chip
-#define MAX_BANDS_PER_BLOCK 256 // ... and at most (LDS for their planes); with >= 1024 light blocks a block builds all of its lights' masks
 #define QCAP 128             // LDS candidate queue of the overflow path of k1_tile_cull (ring buffer: < 64 pending + <= 64 new)
-#define GROUP 4              // k1_group_lists: tiles per group edge (4x4 tiles share one candidate list)
-#define CAPG 2048            // entries per group list; a denser group falls back to walking the masks per tile
 #define GROUP_OVERFLOW 0xFFFFFFFFu
 #define GROUP_OVERFLOW_LISTED 0xFFFFFFFEu // ... the same for a group that is in k1_group_lists' cluster list
 #define GROUP_LISTED 0x40000000u // flag in a group's count: a light cluster k1_group_lists found room for in its list (k1_tile_cull starts with those)
-// A group with more candidates than this is listed as a light cluster: its tiles get a block each.  Measured 512 / 384 / 256: whole frame 25.5 / 26.1 /
-// 30.6 us for k1_tile_cull, a cluster band of an 8-way split 15.4 / 9.7 / 8.0 -- the whole frame hides a long block behind its other 8 000, a band
-// IS its longest block; below 384 too many groups qualify.  So: by the size of the band.
-#define HEAVY_MIN_FRAME 512
-#define HEAVY_MIN_BAND 384
-#define HEAVY_MAX 96            // ... and that list's room (16 head blocks of k1_tile_cull per entry: the empty ones are dispatched in front of everything else -- 4 096 of them cost ~3 us)
 #define CHUNK 512            // group candidates staged in LDS per step of k1_tile_cull (16 KB of LDS per block: 8 blocks per CU)
-
-#define PACK_TILES 64        // tiles per k1_pack block
-#define SEL_LIGHTS 1024      // lights per block of k0_band_count / k0_band_scatter
 #define CL_STEPS (CAPG / 4 / 64) // cluster tiles: 64-candidate steps per wave for the longest listable group (8)
-
-#define BAND_FORM_MAX_TILES 12000 // (see layout_has_hint)
-
-struct CullLayout {
-    int Tx, Ty, bandRows, bandTiles, numBands, words, groupsX, groupsY, numGroups, packBlocks;
-    size_t offLightView, offLightType, offTileInfo, offMasks, offDirWords, offGroupCount, offGroupList, offTileNum, offTileNum8, offTileLists, offDirFlag, offHeavy,
-           offLightMap, offSelState, offSelKeep, total;
-    int selBlocks;
-};
-
-static CullLayout make_layout(int W, int H, int N, const SailorBand& band)
-{
-    CullLayout L;
-    L.Tx = (W - 1) / TILE + 1;
-    L.Ty = (H - 1) / TILE + 1;
-    L.bandRows = band.tileRowEnd - band.tileRowBegin;
-    L.bandTiles = L.bandRows * L.Tx;
-    L.words = (N + 63) / 64;
-    if (L.words < 1) L.words = 1;
-    const size_t n = (size_t)(N > 0 ? N : 1);
-    const size_t tiles = (size_t)(L.bandTiles > 0 ? L.bandTiles : 1);
-    L.groupsX = (L.Tx + GROUP - 1) / GROUP;
-    L.groupsY = (L.bandRows + GROUP - 1) / GROUP;
-    L.numGroups = L.groupsX * L.groupsY;
-    L.numBands = L.groupsX + L.groupsY;      // group columns first, then the band's group rows (4 tiles wide / high)
-    L.packBlocks = (L.bandTiles + PACK_TILES - 1) / PACK_TILES;
-    const size_t groups = (size_t)(L.numGroups > 0 ? L.numGroups : 1);
-    // Sections whose size depends on the geometry only come first, those that scale with the light count last: the offset of anything a later
-    // call looks up from (width, height, band) alone -- the per-tile lists, their lengths -- is then the same for every lightsNum <= the capacity the
-    // workspace was sized for (a cull may run with fewer lights than the capacity; round 2 computed the hint's address from the capacity and
-    // the cull's own layout from lightsNum, which only agree when the two are equal).
-    size_t o = 0;
-    L.offTileInfo = o; o = align_up(o + tiles * 64, 256);
-    L.offGroupCount = o; o = align_up(o + groups * 4, 256);
-    L.offDirFlag = o; o = align_up(o + 4, 256);
-    L.offHeavy = o; o = align_up(o + (1 + HEAVY_MAX) * 4, 256); // [0] = light-cluster groups listed by k1_group_lists (zeroed by k01_prepare), then their indices
-    L.offGroupList = o; o = align_up(o + groups * CAPG * 4, 256);
-    L.offTileNum = o; o = align_up(o + tiles * 4, 256);
-    L.offTileNum8 = o; o = align_up(o + tiles + 64, 256);      // the same lengths (<= 128) as bytes: what k1_pack adds up for its base (32 KB at 4K instead of 130)
-    L.offTileLists = o; o = align_up(o + tiles * KEEP * 4, 256); // one fixed 128-entry slot per tile (only the list's own bytes are ever touched)
-    L.offLightView = o; o = align_up(o + n * 16, 256);
-    L.offLightType = o; o = align_up(o + n * 4, 256);
-    L.offMasks = o; o = align_up(o + (size_t)(L.numBands > 0 ? L.numBands : 1) * L.words * 8, 256);
-    L.offDirWords = o; o = align_up(o + (size_t)L.words * 8, 256);
-    // the band's own light set (k0_band_count / k0_band_scatter: split frames with large light sets): compact index -> light index; [0] the number of
-    // selected lights, [2 + b] block b's count; block b's sixteen ballot words
-    L.selBlocks = (int)((n + SEL_LIGHTS - 1) / SEL_LIGHTS);
-    L.offLightMap = o; o = align_up(o + n * 4, 256);
-    L.offSelState = o; o = align_up(o + (size_t)(2 + L.selBlocks) * 4, 256);
-    L.offSelKeep = o; o = align_up(o + (size_t)L.selBlocks * 16 * 8, 256);
-    L.total = o;
-    return L;
-}
 
 // ------------------------------------------------------------------------------------------------------------
 // Frustum of a screen rectangle: ComputeLightCulling.shader:57-95 CreateFrustum / Math.glsl:185-222 CreateViewFrustum
@@ -370,7 +305,7 @@ __device__ __forceinline__ uint32_t depth_bits(const float* __restrict__ depth, 
     return __float_as_uint(depth[(size_t)(row - bandRow0) * W + col]);
 }
 
-#define SETUP_STRIPS 2 // 16-tile strips per block: the whole role is one round of resident blocks at 4K, 8 float4 loads in flight per lane
+// (SETUP_STRIPS 16-tile strips per block: cull_plan.h)
 __device__ __forceinline__ void k1_tile_setup(const int block, unsigned char* __restrict__ lds, const PrepareArgs& a)
 {
     uint32_t (*sMin)[16 * SETUP_STRIPS] = reinterpret_cast<uint32_t (*)[16 * SETUP_STRIPS]>(lds);                       // [4][32]
@@ -787,7 +722,7 @@ __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v)
     return v;
 }
 
-#define GLW_ROWS 4  // rows of 128 words per step
+// (GLW_ROWS rows of 128 words per step: cull_plan.h)
 #define GLW_Q 256   // queued words per wave (ring; < 64 pending + <= 128 new per row)
 template <bool EXACT> // EXACT: words is a multiple of 128 * GLW_ROWS, no load needs a bounds check
 __global__ __launch_bounds__(256) void k1_group_lists_wide(const unsigned long long* __restrict__ masks, const unsigned long long* __restrict__ dirWords,
@@ -1561,36 +1496,15 @@ __global__ void k_grid_rebase(SailorLightsGrid* grid, int T, uint32_t base)
 // ------------------------------------------------------------------------------------------------------------
 // host entry points
 // ------------------------------------------------------------------------------------------------------------
-static bool band_valid(int W, int H, const SailorBand* b)
+// What a cull left in the workspace is found again from (width, height, band, light count) alone.  The checks every such look-up makes, then the layout;
+// false: the entry refuses, with its own status.  (band == null: the whole frame.)
+static bool cull_layout_of(int32_t width, int32_t height, int32_t lights, const SailorBand* band, CullLayout* L)
 {
-    if (!b) return false;
-    const int Ty = (H - 1) / TILE + 1;
-    if (b->tileRowBegin < 0 || b->tileRowEnd > Ty || b->tileRowBegin > b->tileRowEnd) return false;
-    int lo = H - TILE * b->tileRowEnd, hi = H - TILE * b->tileRowBegin;
-    if (lo < 0) lo = 0;
-    if (hi > H) hi = H;
-    if (hi < lo) hi = lo;
-    return b->fbRowBegin == lo && b->fbRowCount == hi - lo;
-}
-
-// The BAND FORM of the shade (shade.hip: split blocks for the long tiles in front of the one-block-per-tile grid) is what sailor_hip_light_cull_tile_order
-// switches on by handing a band's per-tile list lengths to the shade.  Every band of a split frame gets it -- the split threshold rises with the band's
-// size (shade_body.h: SPLIT_MIN_*) -- but a band of more than BAND_FORM_MAX_TILES tiles under a LARGE light set (from 131 072 lights on: an eighth of the
-// 8K frame under a million lights, 16 320 tiles): such a set means short lists and next to no long tiles (225 of 16 320 there), so there is no tail to cut,
-// and the band takes the whole frame's form -- one block per tile on the XCD-aware grid -- whose launch pipelines better beside the next frame's cull
-// (step 116.5 against 126.3 us, same box; the 4K frame's halves under 65 536 lights: 103.2 / 95.7 us in the band form, 108.0 / 91.9 in the other).
-// SAILOR_BAND_FORM_TILES=<n> overrides the limit (A / B; 0: never the band form).
-static int band_form_max_tiles()
-{
-    static const int v = [] { const char* e = getenv("SAILOR_BAND_FORM_TILES"); return e ? atoi(e) : -1; }();
-    return v;
-}
-static bool layout_has_hint(const CullLayout& L, const int lightsCapacity)
-{
-    if (L.bandRows >= L.Ty || L.bandTiles <= 0) return false;
-    const int limit = band_form_max_tiles();
-    if (limit >= 0) return L.bandTiles <= limit;
-    return L.bandTiles <= BAND_FORM_MAX_TILES || lightsCapacity < 131072;
+    SailorBand whole;
+    if (width <= 0 || height <= 0 || lights < 0) return false;
+    if (!(band = band_or_whole_frame(height, band, &whole))) return false;
+    *L = make_layout(width, height, lights, *band);
+    return true;
 }
 
 static int launch_pack(SailorHipContext* ctx, const CullLayout& L, char* ws, SailorLightsGrid* dLightsGrid, uint32_t* dCulledLights, size_t culledCapacity)
@@ -1605,20 +1519,101 @@ static int launch_pack(SailorHipContext* ctx, const CullLayout& L, char* ws, Sai
     return SAILOR_HIP_OK;
 }
 
-extern "C" {
-
-int sailor_hip_band_is_valid(int32_t width, int32_t height, const SailorBand* band)
+// The argument structs of one cull, from its plan: nothing is decided here.  (sa is filled only if the plan selects.)
+static void fill_cull_args(const CullPlan& P, const CullLayout& L, const SailorUboFrameData* frame, const int W, const int H, const int N, const SailorBand* band,
+                           const uint32_t flags, const SailorLightShaderData* dLights, const float* dLinearDepth, char* ws, const void* dPreparedLights,
+                           const int32_t preparedCapacity, SelectArgs& sa, PrepareArgs& pa, CullArgs& ca)
 {
-    return (width > 0 && height > 0 && band_valid(width, height, band)) ? 1 : 0;
+    memcpy(pa.view.m, frame->view, 64);
+    memcpy(pa.invProj.m, frame->invProjection, 64);
+    pa.lights = dLights; pa.depth = dLinearDepth;
+    pa.soaPosRadius = nullptr; pa.soaType = nullptr;
+    pa.prepPosRadius = nullptr; pa.prepType = nullptr; pa.prepStaged = nullptr;
+    if (dPreparedLights) {
+        const void *pr = nullptr, *ty = nullptr, *st = nullptr;
+        sailor_hip_prepared_lights_views(preparedCapacity, dPreparedLights, &pr, &ty, &st);
+        if (flags & SAILOR_CULL_PREPARE_LIGHTS) { // the views are this call's OUTPUT (for the shade and for later culls); the light role reads the records
+            pa.prepPosRadius = (float4*)pr; pa.prepType = (uint32_t*)ty; pa.prepStaged = (float4*)st;
+        } else { pa.soaPosRadius = (const float4*)pr; pa.soaType = (const uint32_t*)ty; }
+    }
+    pa.lightView = (float4*)(ws + L.offLightView); pa.lightType = (uint32_t*)(ws + L.offLightType); pa.tileInfo = (float4*)(ws + L.offTileInfo);
+    pa.selCount = nullptr;
+    if (P.select) {
+        memcpy(sa.view.m, frame->view, 64);
+        memcpy(sa.invProj.m, frame->invProjection, 64);
+        sa.lights = dLights; sa.soaPosRadius = pa.soaPosRadius; sa.soaType = pa.soaType;
+        sa.prepPosRadius = pa.prepPosRadius; sa.prepType = pa.prepType; sa.prepStaged = pa.prepStaged;
+        sa.lightView = pa.lightView; sa.lightType = pa.lightType; sa.lightMap = (uint32_t*)(ws + L.offLightMap); sa.state = (uint32_t*)(ws + L.offSelState);
+        sa.keep = (unsigned long long*)(ws + L.offSelKeep);
+        sa.N = N; sa.vpW = frame->viewportSize[0]; sa.vpH = frame->viewportSize[1]; sa.Tx = L.Tx; sa.tileRow0 = band->tileRowBegin; sa.bandRows = L.bandRows;
+        sa.planeMargin = 1e-3f;
+        sa.stageSelectedOnly = (flags & SAILOR_CULL_PREPARE_SELECTED) ? 1 : 0;
+        pa.selCount = sa.state;
+        pa.prepPosRadius = nullptr; pa.prepType = nullptr; pa.prepStaged = nullptr; // (derived by k0_band_count; the light role reads the compact records)
+    }
+    pa.masks = (unsigned long long*)(ws + L.offMasks); pa.dirWords = (unsigned long long*)(ws + L.offDirWords);
+    pa.N = N; pa.words = L.words;
+    pa.lightBlocks = P.lightBlocks; pa.numBands = P.numBands; pa.bandsPerBlock = P.bandsPerBlock; pa.lightRoleBlocks = P.lightRoleBlocks; pa.intervals = P.intervals ? 1 : 0;
+    pa.stripsPerRow = P.stripsPerRow; pa.setupBlocks = P.setupBlocks; pa.frustumBlocks = P.frustumBlocks;
+    pa.vpW = frame->viewportSize[0]; pa.vpH = frame->viewportSize[1]; pa.W = W; pa.H = H; pa.Tx = L.Tx; pa.Ty = L.Ty;
+    pa.tileRow0 = band->tileRowBegin; pa.bandRow0 = band->fbRowBegin; pa.bandRows = L.bandRows; pa.groupsX = L.groupsX;
+    pa.vecOK = (((uintptr_t)dLinearDepth & 15) == 0 && (W & 3) == 0) ? 1 : 0;
+    pa.rawDepth = (flags & SAILOR_CULL_RAW_DEPTH) ? 1 : 0;
+    pa.zNearCam = frame->cameraZNearZFar[0];
+    pa.planeMargin = 1e-3f;
+    pa.dirFlag = (uint32_t*)(ws + L.offDirFlag);
+    pa.heavy = (uint32_t*)(ws + L.offHeavy);
+
+    ca.lightView = pa.lightView; ca.lightType = pa.lightType; ca.tileInfo = pa.tileInfo; ca.masks = pa.masks;
+    ca.groupCount = (const uint32_t*)(ws + L.offGroupCount); ca.groupList = (const uint32_t*)(ws + L.offGroupList);
+    ca.tileNum = (uint32_t*)(ws + L.offTileNum); ca.tileNum8 = (uint8_t*)(ws + L.offTileNum8); ca.tileLists = (uint32_t*)(ws + L.offTileLists);
+    ca.dirFlag = pa.dirFlag;
+    ca.N = N; ca.words = L.words; ca.Tx = L.Tx; ca.groupsX = L.groupsX; ca.bandRows = L.bandRows;
+    ca.heavy = (const uint32_t*)(ws + L.offHeavy); ca.headRows = P.headRows;
+    ca.lightMap = P.select ? (const uint32_t*)(ws + L.offLightMap) : nullptr; ca.selCount = pa.selCount;
 }
+
+// The launches of one cull up to the pack, as the plan says (CullPlan has the order).
+static int launch_cull(SailorHipContext* ctx, const CullPlan& P, const CullLayout& L, char* ws, const SelectArgs& sa, const PrepareArgs& pa, const CullArgs& ca)
+{
+    using WideListsKernel = void (*)(const unsigned long long*, const unsigned long long*, int, int, uint32_t*, uint32_t*, const uint32_t*, const uint32_t*);
+    using TileCullKernel = void (*)(CullArgs);
+    // (the tables name `true` first: the order in which the instantiations are first named is their order in the code object, which is held byte for byte)
+    static const WideListsKernel wideLists[2] = { k1_group_lists_wide<true>, k1_group_lists_wide<false> }; // [!wideExact]
+    // (COOP: the block-wide selection; SEL: behind the band selection -- compact indices, translated when a list leaves)
+    static const TileCullKernel tileCull[2][2] = { { k1_tile_cull<true, true>, k1_tile_cull<true, false> }, { k1_tile_cull<false, true>, k1_tile_cull<false, false> } }; // [!coop][!select]
+    if (P.select) {
+        sailor_launch(ctx, k0_band_count, dim3(P.selectGrid), dim3(256), sa);
+        SAILOR_CHECK_LAUNCH(ctx, "k0_band_count");
+        sailor_launch(ctx, k0_band_scatter, dim3(P.selectGrid), dim3(256), sa);
+        SAILOR_CHECK_LAUNCH(ctx, "k0_band_scatter");
+    }
+    sailor_launch(ctx, k01_prepare, dim3(P.prepareGrid), dim3(256), pa);
+    SAILOR_CHECK_LAUNCH(ctx, "k01_prepare");
+    if (P.brute) {
+        sailor_launch(ctx, k1_tile_cull_brute, dim3(P.cullGridX, P.cullGridY), dim3(256), ca);
+        SAILOR_CHECK_LAUNCH(ctx, "k1_tile_cull<brute>");
+        return SAILOR_HIP_OK;
+    }
+    uint32_t* groupCount = (uint32_t*)(ws + L.offGroupCount);
+    uint32_t* groupList = (uint32_t*)(ws + L.offGroupList);
+    const dim3 listsGrid(P.listsGridX, P.listsGridY);
+    if (P.wide) // (wideExact never runs behind the selection: its selCount is null)
+        sailor_launch(ctx, wideLists[!P.wideExact], listsGrid, dim3(256), pa.masks, pa.dirWords, L.words, L.groupsX, groupCount, groupList, (const uint32_t*)pa.dirFlag, pa.selCount);
+    else
+        sailor_launch(ctx, k1_group_lists, listsGrid, dim3(256), pa.masks, pa.dirWords, L.words, L.groupsX, groupCount, groupList, pa.heavy, P.heavyMin, pa.selCount);
+    SAILOR_CHECK_LAUNCH(ctx, P.wide ? "k1_group_lists_wide" : "k1_group_lists");
+    sailor_launch(ctx, tileCull[!P.coop][!P.select], dim3(P.cullGridX, P.cullGridY), dim3(256), ca);
+    SAILOR_CHECK_LAUNCH(ctx, "k1_tile_cull");
+    return SAILOR_HIP_OK;
+}
+
+extern "C" {
 
 size_t sailor_hip_light_cull_workspace_size(int32_t width, int32_t height, int32_t lightsCapacity, const SailorBand* band)
 {
-    if (width <= 0 || height <= 0 || lightsCapacity < 0) return 0;
-    SailorBand whole;
-    if (!band) { sailor_hip_band_whole_frame(width, height, &whole); band = &whole; }
-    if (!band_valid(width, height, band)) return 0;
-    return make_layout(width, height, lightsCapacity, *band).total;
+    CullLayout L;
+    return cull_layout_of(width, height, lightsCapacity, band, &L) ? L.total : 0;
 }
 
 int sailor_hip_light_cull(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorLightCullPushConstants* pc,
@@ -1636,6 +1631,7 @@ int sailor_hip_light_cull_prepared(SailorHipContext* ctx, const SailorUboFrameDa
                                    void* dWorkspace, size_t workspaceBytes, const SailorBand* band, uint32_t flags,
                                    const void* dPreparedLights, int32_t preparedCapacity)
 {
+    // ---- 1. check (in this order: it decides which status wins when two faults are present) ----
     if (!ctx || !frame || !pc || !dLinearDepth || !dLightsGrid || !dCulledLights || !dWorkspace) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     const int W = pc->viewportSize[0], H = pc->viewportSize[1], N = pc->lightsNum;
     if (W <= 0 || H <= 0 || N < 0 || (N > 0 && !dLights && !dPreparedLights)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
@@ -1645,8 +1641,7 @@ int sailor_hip_light_cull_prepared(SailorHipContext* ctx, const SailorUboFrameDa
     // Appendix A: the depth extent (push constants) and the window viewport (frame UBO) must agree
     if (frame->viewportSize[0] != W || frame->viewportSize[1] != H) return SAILOR_HIP_ERR_UNSUPPORTED;
     SailorBand whole;
-    if (!band) { sailor_hip_band_whole_frame(W, H, &whole); band = &whole; }
-    if (!band_valid(W, H, band)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (!(band = band_or_whole_frame(H, band, &whole))) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     const CullLayout L = make_layout(W, H, N, *band);
     if (pc->numTiles[0] != L.Tx || pc->numTiles[1] != L.Ty) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     if (workspaceBytes < L.total) return SAILOR_HIP_ERR_WORKSPACE_TOO_SMALL;
@@ -1657,136 +1652,28 @@ int sailor_hip_light_cull_prepared(SailorHipContext* ctx, const SailorUboFrameDa
     if ((unsigned long long)L.bandTiles * KEEP > 0x7FFFFFFFull) return SAILOR_HIP_ERR_UNSUPPORTED;
     if (((uintptr_t)dWorkspace & 255) != 0) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
-
-    hipStream_t s = ctx->stream;
-    char* ws = (char*)dWorkspace;
-
     if (L.bandTiles == 0) {
-        SAILOR_TRY_HIP(ctx, hipMemsetAsync(dCulledLights, 0, 4, s));
+        SAILOR_TRY_HIP(ctx, hipMemsetAsync(dCulledLights, 0, 4, ctx->stream));
         return SAILOR_HIP_OK;
     }
-
-    // The side-plane margin argument needs a sane perspective; tiny light counts are cheaper brute force.
-    const float p00 = fabsf(frame->projection[0]), p11 = fabsf(frame->projection[5]);
-    const bool sane = p00 > 1e-2f && p11 > 1e-2f && p00 < 1e4f && p11 < 1e4f;
-    const bool brute = (flags & SAILOR_CULL_BRUTE_FORCE) || !sane || N < 512;
-
+    // ---- 2. plan, 3. arguments, 4. launch ----
+    const CullPlan P = plan_cull(L, N, flags, frame->projection[0], frame->projection[5]);
+    char* ws = (char*)dWorkspace;
+    SelectArgs sa;
     PrepareArgs pa;
-    memcpy(pa.view.m, frame->view, 64);
-    memcpy(pa.invProj.m, frame->invProjection, 64);
-    pa.lights = dLights; pa.depth = dLinearDepth;
-    pa.soaPosRadius = nullptr; pa.soaType = nullptr;
-    pa.prepPosRadius = nullptr; pa.prepType = nullptr; pa.prepStaged = nullptr;
-    if (dPreparedLights) {
-        const void *pr = nullptr, *ty = nullptr, *st = nullptr;
-        sailor_hip_prepared_lights_views(preparedCapacity, dPreparedLights, &pr, &ty, &st);
-        if (flags & SAILOR_CULL_PREPARE_LIGHTS) { // the views are this call's OUTPUT (for the shade and for later culls); the light role reads the records
-            pa.prepPosRadius = (float4*)pr; pa.prepType = (uint32_t*)ty; pa.prepStaged = (float4*)st;
-        } else { pa.soaPosRadius = (const float4*)pr; pa.soaType = (const uint32_t*)ty; }
-    }
-    pa.lightView = (float4*)(ws + L.offLightView); pa.lightType = (uint32_t*)(ws + L.offLightType); pa.tileInfo = (float4*)(ws + L.offTileInfo);
-    // A band of a split frame with a large light set: the lights that can reach the band are selected first (k0_band_count + k0_band_scatter) and the chain runs on them.
-    // From 131 072 lights on (below, the light role and the group lists of a band sit at their launch floors whatever the count); SAILOR_CULL_BAND_SELECT
-    // forces it for any set the pre-filter runs on, SAILOR_CULL_NO_BAND_SELECT switches it off.  (Two launches, no block waits for another: any
-    // number of blocks.)
-    uint32_t* selState = (uint32_t*)(ws + L.offSelState);
-    const bool select = !brute && L.bandRows < L.Ty && !(flags & SAILOR_CULL_NO_BAND_SELECT) && ((flags & SAILOR_CULL_BAND_SELECT) || N >= 131072);
-    pa.selCount = nullptr;
-    if (select) {
-        SelectArgs sa;
-        memcpy(sa.view.m, frame->view, 64);
-        memcpy(sa.invProj.m, frame->invProjection, 64);
-        sa.lights = dLights; sa.soaPosRadius = pa.soaPosRadius; sa.soaType = pa.soaType;
-        sa.prepPosRadius = pa.prepPosRadius; sa.prepType = pa.prepType; sa.prepStaged = pa.prepStaged;
-        sa.lightView = pa.lightView; sa.lightType = pa.lightType; sa.lightMap = (uint32_t*)(ws + L.offLightMap); sa.state = selState;
-        sa.keep = (unsigned long long*)(ws + L.offSelKeep);
-        sa.N = N; sa.vpW = frame->viewportSize[0]; sa.vpH = frame->viewportSize[1]; sa.Tx = L.Tx; sa.tileRow0 = band->tileRowBegin; sa.bandRows = L.bandRows;
-        sa.planeMargin = 1e-3f;
-        sa.stageSelectedOnly = (flags & SAILOR_CULL_PREPARE_SELECTED) ? 1 : 0;
-        sailor_launch(ctx, k0_band_count, dim3((unsigned)L.selBlocks), dim3(256), sa);
-        SAILOR_CHECK_LAUNCH(ctx, "k0_band_count");
-        sailor_launch(ctx, k0_band_scatter, dim3((unsigned)L.selBlocks), dim3(256), sa);
-        SAILOR_CHECK_LAUNCH(ctx, "k0_band_scatter");
-        pa.selCount = selState;
-        pa.prepPosRadius = nullptr; pa.prepType = nullptr; pa.prepStaged = nullptr; // (derived by k0_band_count; the light role reads the compact records)
-    }
-    pa.masks = (unsigned long long*)(ws + L.offMasks); pa.dirWords = (unsigned long long*)(ws + L.offDirWords);
-    pa.N = N; pa.words = L.words;
-    pa.lightBlocks = (N + 255) / 256;
-    pa.numBands = brute ? 0 : L.numBands;
-    // Few lights: the bands are spread over several blocks per 256 lights (parallelism; every block repeats the cheap transform).  Many lights
-    // (the 1 M of configs[4]): the light blocks fill the chip by themselves, and repeating the 112-byte record reads per split is what costs.
-    const int perBlock = (pa.lightBlocks >= 1024 || (flags & SAILOR_CULL_INTERVAL_MASKS)) ? MAX_BANDS_PER_BLOCK : BANDS_PER_BLOCK;
-    const int splits = brute ? 1 : (L.numBands + perBlock - 1) / perBlock;
-    pa.bandsPerBlock = brute ? 0 : (L.numBands + splits - 1) / splits; // the bands spread evenly over the splits
-    pa.lightRoleBlocks = pa.lightBlocks * splits;
-    // the masks by bisection for each light's band intervals instead of 2 x numBands plane tests: needs all bands in one block
-    pa.intervals = (!brute && splits == 1 && (pa.lightBlocks >= 1024 || (flags & SAILOR_CULL_INTERVAL_MASKS))) ? 1 : 0;
-    pa.stripsPerRow = (L.Tx + 16 * SETUP_STRIPS - 1) / (16 * SETUP_STRIPS);
-    pa.setupBlocks = pa.stripsPerRow * L.bandRows;
-    pa.frustumBlocks = (L.bandTiles + 255) / 256;
-    pa.vpW = frame->viewportSize[0]; pa.vpH = frame->viewportSize[1]; pa.W = W; pa.H = H; pa.Tx = L.Tx; pa.Ty = L.Ty;
-    pa.tileRow0 = band->tileRowBegin; pa.bandRow0 = band->fbRowBegin; pa.bandRows = L.bandRows; pa.groupsX = L.groupsX;
-    pa.vecOK = (((uintptr_t)dLinearDepth & 15) == 0 && (W & 3) == 0) ? 1 : 0;
-    pa.rawDepth = (flags & SAILOR_CULL_RAW_DEPTH) ? 1 : 0;
-    pa.zNearCam = frame->cameraZNearZFar[0];
-    pa.planeMargin = 1e-3f;
-    pa.dirFlag = (uint32_t*)(ws + L.offDirFlag);
-    pa.heavy = (uint32_t*)(ws + L.offHeavy);
-    sailor_launch(ctx, k01_prepare, dim3(pa.lightRoleBlocks + pa.frustumBlocks + pa.setupBlocks), dim3(256), pa);
-    SAILOR_CHECK_LAUNCH(ctx, "k01_prepare");
-
     CullArgs ca;
-    ca.lightView = pa.lightView; ca.lightType = pa.lightType; ca.tileInfo = pa.tileInfo; ca.masks = pa.masks;
-    ca.groupCount = (const uint32_t*)(ws + L.offGroupCount); ca.groupList = (const uint32_t*)(ws + L.offGroupList);
-    ca.tileNum = (uint32_t*)(ws + L.offTileNum); ca.tileNum8 = (uint8_t*)(ws + L.offTileNum8); ca.tileLists = (uint32_t*)(ws + L.offTileLists);
-    ca.dirFlag = pa.dirFlag;
-    ca.N = N; ca.words = L.words; ca.Tx = L.Tx; ca.groupsX = L.groupsX; ca.bandRows = L.bandRows;
-    ca.heavy = (const uint32_t*)(ws + L.offHeavy); ca.headRows = 0;
-    ca.lightMap = select ? (const uint32_t*)(ws + L.offLightMap) : nullptr; ca.selCount = pa.selCount;
-    if (brute) {
-        sailor_launch(ctx, k1_tile_cull_brute, dim3(L.groupsX, L.bandRows), dim3(256), ca);
-        SAILOR_CHECK_LAUNCH(ctx, "k1_tile_cull<brute>");
-    } else {
-        const bool wide = L.words >= 4096 && (L.words & 1) == 0;
-        if (wide)
-        {
-            // (round 6: a 4 x 4 patch of groups per block halved the masks' traffic, shortened nothing and slowed the frame pipeline: removed)
-            const dim3 wideGrid((unsigned)(((L.groupsX + 3) / 4) * L.groupsY));
-            if (L.words % (128 * GLW_ROWS) == 0 && !select)
-                sailor_launch(ctx, k1_group_lists_wide<true>, wideGrid, dim3(256), pa.masks, pa.dirWords, L.words, L.groupsX, (uint32_t*)(ws + L.offGroupCount),
-                                   (uint32_t*)(ws + L.offGroupList), (const uint32_t*)(ws + L.offDirFlag), (const uint32_t*)nullptr);
-            else
-                sailor_launch(ctx, k1_group_lists_wide<false>, wideGrid, dim3(256), pa.masks, pa.dirWords, L.words, L.groupsX, (uint32_t*)(ws + L.offGroupCount),
-                                   (uint32_t*)(ws + L.offGroupList), (const uint32_t*)(ws + L.offDirFlag), pa.selCount);
-        }
-        else {
-            sailor_launch(ctx, k1_group_lists, dim3(L.groupsX, L.groupsY), dim3(256), pa.masks, pa.dirWords, L.words, L.groupsX, (uint32_t*)(ws + L.offGroupCount),
-                               (uint32_t*)(ws + L.offGroupList), (uint32_t*)(ws + L.offHeavy), (uint32_t)(L.bandRows * 2 > L.Ty ? HEAVY_MIN_FRAME : HEAVY_MIN_BAND), pa.selCount);
-            ca.headRows = (16 * HEAVY_MAX + L.groupsX - 1) / L.groupsX; // grid rows for the listed clusters' tiles (a block each), in front of the tile rows
-        }
-        SAILOR_CHECK_LAUNCH(ctx, wide ? "k1_group_lists_wide" : "k1_group_lists");
-        // (the block-wide selection everywhere but on the long lists of the wide path: see k1_tile_cull)
-        const bool coop = !wide;
-        const dim3 cgrid(L.groupsX, ca.headRows + L.bandRows);
-        // (COOP: the block-wide selection; SEL: behind the band selection -- compact indices, translated when a list leaves)
-        if (coop) { if (select) sailor_launch(ctx, k1_tile_cull<true, true>, cgrid, dim3(256), ca); else sailor_launch(ctx, k1_tile_cull<true, false>, cgrid, dim3(256), ca); }
-        else { if (select) sailor_launch(ctx, k1_tile_cull<false, true>, cgrid, dim3(256), ca); else sailor_launch(ctx, k1_tile_cull<false, false>, cgrid, dim3(256), ca); }
-        SAILOR_CHECK_LAUNCH(ctx, "k1_tile_cull");
-    }
-    if (flags & SAILOR_CULL_DEFER_PACK) return SAILOR_HIP_OK; // the caller records sailor_hip_light_cull_pack where it wants it (another stream, beside the shade)
+    fill_cull_args(P, L, frame, W, H, N, band, flags, dLights, dLinearDepth, ws, dPreparedLights, preparedCapacity, sa, pa, ca);
+    const int status = launch_cull(ctx, P, L, ws, sa, pa, ca);
+    if (status != SAILOR_HIP_OK || (flags & SAILOR_CULL_DEFER_PACK)) return status; // (deferred: the caller records sailor_hip_light_cull_pack where it wants it -- another stream, beside the shade)
     return launch_pack(ctx, L, ws, dLightsGrid, dCulledLights, culledCapacity);
 }
 
 int sailor_hip_light_cull_pack(SailorHipContext* ctx, int32_t width, int32_t height, int32_t lightsCapacity, const SailorBand* band, const void* dWorkspace,
                                SailorLightsGrid* dLightsGrid, uint32_t* dCulledLights, size_t culledCapacity)
 {
-    if (!ctx || !dWorkspace || !dLightsGrid || !dCulledLights || width <= 0 || height <= 0 || lightsCapacity < 0) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    SailorBand whole;
-    if (!band) { sailor_hip_band_whole_frame(width, height, &whole); band = &whole; }
-    if (!band_valid(width, height, band)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     // (everything the pack reads lies in the part of the workspace whose layout depends on the geometry alone)
-    const CullLayout L = make_layout(width, height, lightsCapacity, *band);
+    CullLayout L;
+    if (!ctx || !dWorkspace || !dLightsGrid || !dCulledLights || !cull_layout_of(width, height, lightsCapacity, band, &L)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     if (culledCapacity < 1 || culledCapacity < (size_t)L.bandTiles * KEEP) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     if (((uintptr_t)dWorkspace & 255) != 0) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
@@ -1800,11 +1687,8 @@ int sailor_hip_light_cull_pack(SailorHipContext* ctx, int32_t width, int32_t hei
 int sailor_hip_light_cull_tile_lists(int32_t width, int32_t height, int32_t lightsCapacity, const SailorBand* band, const void* dWorkspace,
                                      const uint32_t** outTileNum, const uint32_t** outTileLists)
 {
-    if (!dWorkspace || width <= 0 || height <= 0 || lightsCapacity < 0) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    SailorBand whole;
-    if (!band) { sailor_hip_band_whole_frame(width, height, &whole); band = &whole; }
-    if (!band_valid(width, height, band)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    const CullLayout L = make_layout(width, height, lightsCapacity, *band);
+    CullLayout L;
+    if (!dWorkspace || !cull_layout_of(width, height, lightsCapacity, band, &L)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     if (outTileNum) *outTileNum = (const uint32_t*)((const char*)dWorkspace + L.offTileNum);
     if (outTileLists) *outTileLists = (const uint32_t*)((const char*)dWorkspace + L.offTileLists);
     return SAILOR_HIP_OK;
@@ -1849,12 +1733,10 @@ int sailor_hip_linearize_depth(SailorHipContext* ctx, const SailorUboFrameData* 
 
 const uint32_t* sailor_hip_light_cull_tile_order(int32_t width, int32_t height, int32_t lightsCapacity, const SailorBand* band, const void* dWorkspace)
 {
-    if (!dWorkspace || width <= 0 || height <= 0 || lightsCapacity < 0) return nullptr;
-    SailorBand whole;
-    if (!band) { sailor_hip_band_whole_frame(width, height, &whole); band = &whole; }
-    if (!band_valid(width, height, band)) return nullptr;
-    const CullLayout L = make_layout(width, height, lightsCapacity, *band);
-    if (!layout_has_hint(L, lightsCapacity)) return nullptr; // whole frame: the one-block-per-tile form in raster order
+    static const EnvKnob bandFormTiles = env_knob_read("SAILOR_BAND_FORM_TILES"); // (A / B: any n >= 0; this entry has no context, so a negative one is ignored in silence)
+    CullLayout L;
+    if (!dWorkspace || !cull_layout_of(width, height, lightsCapacity, band, &L)) return nullptr;
+    if (!band_takes_band_form(L, lightsCapacity, env_knob(bandFormTiles, 0, INT_MAX, nullptr, nullptr))) return nullptr; // the one-block-per-tile form in raster order
     // (the band's list lengths as bytes, one per tile in tile order -- every cull writes them: the band shade's split blocks find the long tiles there)
     return (const uint32_t*)((const char*)dWorkspace + L.offTileNum8);
 }
@@ -1865,11 +1747,8 @@ const uint32_t* sailor_hip_light_cull_tile_order(int32_t width, int32_t height, 
 int sailor_hip_light_cull_band_selection(int32_t width, int32_t height, int32_t lightsNum, const SailorBand* band, const void* dWorkspace,
                                          const uint32_t** outSelectedCount, const uint32_t** outLightMap)
 {
-    if (!dWorkspace || width <= 0 || height <= 0 || lightsNum < 0) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    SailorBand whole;
-    if (!band) { sailor_hip_band_whole_frame(width, height, &whole); band = &whole; }
-    if (!band_valid(width, height, band)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    const CullLayout L = make_layout(width, height, lightsNum, *band);
+    CullLayout L;
+    if (!dWorkspace || !cull_layout_of(width, height, lightsNum, band, &L)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     if (outSelectedCount) *outSelectedCount = (const uint32_t*)((const char*)dWorkspace + L.offSelState);
     if (outLightMap) *outLightMap = (const uint32_t*)((const char*)dWorkspace + L.offLightMap);
     return SAILOR_HIP_OK;
@@ -1882,11 +1761,8 @@ int sailor_hip_light_cull_band_selection(int32_t width, int32_t height, int32_t 
 int sailor_hip_light_cull_diagnostics(SailorHipContext* ctx, int32_t width, int32_t height, int32_t lightsNum, const SailorBand* band,
                                       const void* dWorkspace, uint64_t* out8)
 {
-    if (!ctx || !dWorkspace || !out8 || width <= 0 || height <= 0 || lightsNum < 0) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    SailorBand whole;
-    if (!band) { sailor_hip_band_whole_frame(width, height, &whole); band = &whole; }
-    if (!band_valid(width, height, band)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    const CullLayout L = make_layout(width, height, lightsNum, *band);
+    CullLayout L;
+    if (!ctx || !dWorkspace || !out8 || !cull_layout_of(width, height, lightsNum, band, &L)) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     std::vector<unsigned long long> masks((size_t)L.numBands * L.words);
     std::vector<uint32_t> counts((size_t)L.numGroups);
     SAILOR_TRY_HIP(ctx, hipStreamSynchronize(ctx->stream));

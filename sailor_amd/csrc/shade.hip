@@ -324,6 +324,25 @@ extern "C" int sailor_hip_compute_brdf_lut(SailorHipContext* ctx, float* dLut, i
     return SAILOR_HIP_OK;
 }
 
+// A kernel family = one kernel in its four variants, indexed (prepared lights ? 1 : 0) | (tile lists ? 2 : 0): plain, _p, _t, _pt.  `Third` is the argument
+// the families differ in: IblArgs for the per-tile grid's kernels (SHADE_ENTRY), the band's tile count for the band form's (SHADE_BAND_ENTRY).
+template <typename Third> struct ShadeFamily {
+    void (*kernel[4])(ShadeArgs, CsmArgs, Third, const float4*, size_t, const SailorLightShaderData*, const SailorLightsGrid*, const uint32_t*, float4*);
+    const char* name[4]; // (the launched variant's name, for sailor_hip_context_launch_log)
+};
+#define SHADE_FAMILY(K) { { K, K##_p, K##_t, K##_pt }, { #K, #K "_p", #K "_t", #K "_pt" } }
+static const ShadeFamily<IblArgs> shadeGridFamilies[4] = { SHADE_FAMILY(k2_shade), SHADE_FAMILY(k2_shade_csm), SHADE_FAMILY(k2_shade_ibl), SHADE_FAMILY(k2_shade_csm_ibl) }; // [csm | ibl << 1]
+static const ShadeFamily<int> shadeBandFamilies[2] = { SHADE_FAMILY(k2_shade_band), SHADE_FAMILY(k2_shade_band_csm) };                                                       // [csm]
+#undef SHADE_FAMILY
+
+template <typename Third, typename... Rest>
+static const char* launch_shade(SailorHipContext* ctx, const ShadeFamily<Third>& family, const int variant, const dim3 grid, const unsigned dynamicLds, const ShadeArgs& A,
+                                const CsmArgs& C, const Third& third, Rest... rest)
+{
+    sailor_launch_lds(ctx, family.kernel[variant], grid, dim3(256), dynamicLds, A, C, third, rest...);
+    return family.name[variant];
+}
+
 // dTileNum == null: (dLightsGrid, dCulledLights) in the reference's layout; else dCulledLights = the cull's per-tile slots and dLightsGrid is not read
 static int shade_impl(SailorHipContext* ctx, const SailorUboFrameData* frame, const float* dSurface, size_t surfacePlaneStride,
                       const SailorLightShaderData* dLights, int32_t lightsNum,
@@ -337,9 +356,7 @@ static int shade_impl(SailorHipContext* ctx, const SailorUboFrameData* frame, co
     const int W = frame->viewportSize[0], H = frame->viewportSize[1];
     if (W <= 0 || H <= 0) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     SailorBand whole;
-    if (!band) { sailor_hip_band_whole_frame(W, H, &whole); band = &whole; }
-    const int Ty = (H - 1) / TILE + 1;
-    if (!sailor_hip_band_is_valid(W, H, band)) return SAILOR_HIP_ERR_INVALID_ARGUMENT; // tile rows AND their framebuffer rows, as the cull checks them
+    if (!(band = band_or_whole_frame(H, band, &whole))) return SAILOR_HIP_ERR_INVALID_ARGUMENT; // tile rows AND their framebuffer rows, as the cull checks them
     if (surfacePlaneStride < (size_t)band->fbRowCount * W) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     if (((uintptr_t)dSurface & 15) || ((uintptr_t)dRadiance & 15) || (!dPreparedLights && ((uintptr_t)dLights & 15))) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
 
@@ -356,10 +373,8 @@ static int shade_impl(SailorHipContext* ctx, const SailorUboFrameData* frame, co
     A.fbRows = band->fbRowCount;
     A.lightsNum = lightsNum;
     // (A / B knobs, read once; a value outside its range is ignored and says so: [1, 128] -- a list has at most 128 entries)
-    static const int splitMinRaw = [] { const char* e = getenv("SAILOR_SPLIT_MIN"); return e ? atoi(e) : -1; }();
-    static const bool splitMinSet = getenv("SAILOR_SPLIT_MIN") != nullptr;
-    const int splitMinEnv = (splitMinRaw >= 1 && splitMinRaw <= KEEP) ? splitMinRaw : -1;
-    if (splitMinSet && splitMinEnv < 0) ctx->lastError = "SAILOR_SPLIT_MIN outside [1, 128]: ignored";
+    static const EnvKnob splitMinKnob = env_knob_read("SAILOR_SPLIT_MIN");
+    const int splitMinEnv = env_knob(splitMinKnob, 1, KEEP, &ctx->lastError, "SAILOR_SPLIT_MIN outside [1, 128]: ignored");
     A.order = reinterpret_cast<const uint8_t*>(dTileOrder); // (the band's list lengths as bytes: sailor_hip_light_cull_tile_order)
     const int bandTiles = (band->tileRowEnd - band->tileRowBegin) * A.Tx;
     if (bandTiles == 0) return SAILOR_HIP_OK;
@@ -399,13 +414,8 @@ static int shade_impl(SailorHipContext* ctx, const SailorUboFrameData* frame, co
     if (dPreparedLights) L = reinterpret_cast<const SailorLightShaderData*>((const char*)dPreparedLights + prepared_layout(preparedCapacity).offStaged);
     // (tile lists: the kernels' `grid` argument is tileNum, their `culled` the per-tile slots -- see k2_shade_body)
     const SailorLightsGrid* G = dTileNum ? reinterpret_cast<const SailorLightsGrid*>(dTileNum) : dLightsGrid;
-    const char* kname = "k2_shade"; // (the launched variant's name, for sailor_hip_context_launch_log)
-    // (bandLds: the wave-slot reserve of a band's shade, below; 0 on the whole frame)
-#define LAUNCH_SHADE(K) do { if (dPreparedLights && dTileNum) { kname = #K "_pt"; sailor_launch_lds(ctx, K##_pt, grid, dim3(256), bandLds, A, C, I, S, surfacePlaneStride, L, G, dCulledLights, Rd); } \
-                             else if (dPreparedLights) { kname = #K "_p"; sailor_launch_lds(ctx, K##_p, grid, dim3(256), bandLds, A, C, I, S, surfacePlaneStride, L, G, dCulledLights, Rd); } \
-                             else if (dTileNum) { kname = #K "_t"; sailor_launch_lds(ctx, K##_t, grid, dim3(256), bandLds, A, C, I, S, surfacePlaneStride, L, G, dCulledLights, Rd); } \
-                             else { kname = #K; sailor_launch_lds(ctx, K, grid, dim3(256), bandLds, A, C, I, S, surfacePlaneStride, L, G, dCulledLights, Rd); } } while (0)
-    const bool partial = band->tileRowEnd - band->tileRowBegin < Ty;
+    // ---- a band's launch form: partial, splitBand, reserve, bandLds ----
+    const bool partial = A.bandTileRows < tile_rows_of(H);
     const bool splitBand = dTileOrder && partial && !ibl; // a band of a split frame with the cull's length bytes: long tiles are split across four blocks
     // A band's shade does not take the whole chip: SHADE_BAND_RESERVE bytes of dynamic LDS that nobody touches cap it at six blocks (24 of 32 wave slots)
     // per CU.  A split frame is a pipeline of short launches -- the NEXT frame's cull chain runs beside this kernel on another stream -- and with every wave
@@ -414,29 +424,21 @@ static int shade_impl(SailorHipContext* ctx, const SailorUboFrameData* frame, co
     // For bands of up to three rounds of resident blocks (an eighth of the 4K frame is two) -- a larger band is bound by the shade's throughput like the
     // whole frame, and the cap costs it what it costs there (half the 4K frame: 108 -> 120 us per step) -- and for any band under a large light set, whose
     // cull chain is as long as its shade (an eighth of the 8K frame under a million lights: 16 320 tiles, 80 us of cull beside 78 us of shade; 152 -> 134 us).
-    static const int bandLdsRaw = [] { const char* e = getenv("SAILOR_BAND_SHADE_LDS"); return e ? atoi(e) : -1; }();
-    static const bool bandLdsSet = getenv("SAILOR_BAND_SHADE_LDS") != nullptr;
-    // (a launch may claim 64 KB of LDS in all; the kernels' static ShadeLds comes off that)
-    const int bandLdsEnv = (bandLdsRaw >= 0 && (size_t)bandLdsRaw + sizeof(ShadeLds) <= 65536u) ? bandLdsRaw : -1;
-    if (bandLdsSet && bandLdsEnv < 0) ctx->lastError = "SAILOR_BAND_SHADE_LDS negative or beyond 64 KB minus the kernel's own LDS: ignored";
     // (round 5: NOT for the shadowed band kernels -- seven waves per SIMD by their registers, so a CU's eighth block slot is the chain's already; capped at six
     // an eighth of C4 took 62.2 us per step instead of 56.8: profiles/r05/ab_band_csm_waves.txt, probe Q)
-    const bool reserve = (bandTiles <= 3 * 8 * ctx->numCUs || lightsNum >= 131072) && !(hasCsm && splitBand);
+    const bool reserve = (bandTiles <= 3 * 8 * ctx->numCUs || lightsNum >= LARGE_LIGHT_SET) && !(hasCsm && splitBand);
+    // (a launch may claim 64 KB of LDS in all; the kernels' static ShadeLds comes off that)
+    static const EnvKnob bandLdsKnob = env_knob_read("SAILOR_BAND_SHADE_LDS");
+    const int bandLdsEnv = env_knob(bandLdsKnob, 0, 65536 - (long)sizeof(ShadeLds), &ctx->lastError,
+                                    "SAILOR_BAND_SHADE_LDS negative or beyond 64 KB minus the kernel's own LDS: ignored");
+    // (the wave-slot reserve: 0 on the whole frame)
     const unsigned bandLds = (!partial || ibl) ? 0u : (bandLdsEnv >= 0 ? (unsigned)bandLdsEnv : (reserve ? (unsigned)SHADE_BAND_RESERVE : 0u));
-    if (hasCsm && ibl) LAUNCH_SHADE(k2_shade_csm_ibl);
-    else if (hasCsm && !splitBand) LAUNCH_SHADE(k2_shade_csm);
-    else if (ibl) LAUNCH_SHADE(k2_shade_ibl);
-    else if (splitBand) {
-        const dim3 bgrid((unsigned)SPLIT_BLOCKS + (unsigned)bandTiles);
-#define LAUNCH_BAND(K) do { if (dPreparedLights && dTileNum) { kname = #K "_pt"; sailor_launch_lds(ctx, K##_pt, bgrid, dim3(256), bandLds, A, C, bandTiles, S, surfacePlaneStride, L, G, dCulledLights, Rd); } \
-                            else if (dPreparedLights) { kname = #K "_p"; sailor_launch_lds(ctx, K##_p, bgrid, dim3(256), bandLds, A, C, bandTiles, S, surfacePlaneStride, L, G, dCulledLights, Rd); } \
-                            else if (dTileNum) { kname = #K "_t"; sailor_launch_lds(ctx, K##_t, bgrid, dim3(256), bandLds, A, C, bandTiles, S, surfacePlaneStride, L, G, dCulledLights, Rd); } \
-                            else { kname = #K; sailor_launch_lds(ctx, K, bgrid, dim3(256), bandLds, A, C, bandTiles, S, surfacePlaneStride, L, G, dCulledLights, Rd); } } while (0)
-        if (hasCsm) LAUNCH_BAND(k2_shade_band_csm);
-        else LAUNCH_BAND(k2_shade_band);
-#undef LAUNCH_BAND
-    } else LAUNCH_SHADE(k2_shade);
-#undef LAUNCH_SHADE
+    // ---- the kernel: its family (the band form has no ambient term: splitBand implies !ibl), then its variant ----
+    const int variant = (dPreparedLights ? 1 : 0) | (dTileNum ? 2 : 0);
+    const char* kname = splitBand
+        ? launch_shade(ctx, shadeBandFamilies[hasCsm ? 1 : 0], variant, dim3((unsigned)SPLIT_BLOCKS + (unsigned)bandTiles), bandLds, A, C, bandTiles, S, surfacePlaneStride, L, G,
+                       dCulledLights, Rd)
+        : launch_shade(ctx, shadeGridFamilies[(hasCsm ? 1 : 0) | (ibl ? 2 : 0)], variant, grid, bandLds, A, C, I, S, surfacePlaneStride, L, G, dCulledLights, Rd);
     SAILOR_CHECK_LAUNCH(ctx, kname);
     return SAILOR_HIP_OK;
 }
