@@ -157,7 +157,7 @@ __global__ __launch_bounds__(256) void k_particles_raster(Mat4 P, Mat4 V, const 
             else t = surface_setup(P, V, model, vertices, draw.dIndices + 3 * (size_t)tri, W, H, 0, H, true, part, second, S);
         }
         const unsigned int orderPlus1 = (unsigned int)(2ull * id) + (unsigned int)part + 1u; // (the entry point has checked the range)
-        surf_fill(t, orderPlus1, blockIdx.y, gridDim.y, lane, [&](int i, int j, float z, unsigned int tag) {
+        surf_fill(t, orderPlus1, SurfNoPayload(), SurfNoBcast(), blockIdx.y, gridDim.y, lane, [&](int i, int j, float z, unsigned int tag, auto&&...) {
             unsigned long long* p = keys + (size_t)j * W + i;
             if (MAP) {
                 const unsigned long long key = ((unsigned long long)tag << 32) | __float_as_uint(z);

@@ -13,7 +13,7 @@
 // block raises it to the smallest depth it wrote there; a triangle (or a block of one) whose largest possible depth does not exceed it is
 // skipped.  Bounds only -- stale values are merely less effective -- so the depth buffer is the same with and without it; shadow casters overdraw
 // each texel hundreds of times (every box along the light direction lands on it), and this is what makes the passes finish.
-#include "common.h"
+#include "raster_prims.h"
 #include <hip/hip_fp16.h>
 
 #ifndef RASTER_SMALL_BOX
@@ -31,8 +31,6 @@ __device__ unsigned long long gStats[16]; // [8..]: per-wave durations on the 10
 #define STAT(i, v)
 #endif
 
-struct RasterTri { long long x0, y0, x1, y1, x2, y2; float z0, z1, z2; int i0, i1, j0, j1; bool valid; };
-
 // clip = (lightMatrix * model) * vec4(p, 1): GLSL order
 __device__ __forceinline__ Mat4 raster_mul(const Mat4& a, const float* __restrict__ b)
 {
@@ -45,27 +43,15 @@ __device__ __forceinline__ Mat4 raster_mul(const Mat4& a, const float* __restric
     return o;
 }
 
-__device__ __forceinline__ long long raster_floor_div256(long long a) { return a >= 0 ? a / 256 : -((-a + 255) / 256); }
-
-// A vertex beyond the near plane of the reversed depth range (z_clip > w_clip, which includes everything behind the eye) cannot be projected:
-// such a triangle is cut against w - z = 0 in clip space first.  The new vertex on an edge is always computed from its inside end,
-// P = I + (O - I) * (dI / (dI - dO)) with d = w - z, one rounding per operation.  One vertex inside (A; B, C follow it in the triangle's
-// own order): the triangle (A, AB, AC).  Two inside (A, B; C outside follows them): the quad A, B, BC, AC as the triangles
-// (A, B, BC) = part 0 and (A, BC, AC) = part 1.  Triangles wholly inside are untouched (their fragments beyond the plane fail z <= 1).
-__device__ __forceinline__ float4 raster_cut(const float4& I, float dI, const float4& O, float dO)
-{
-    const float t = dI / (dI - dO);
-    return make_float4(I.x + (O.x - I.x) * t, I.y + (O.y - I.y) * t, I.z + (O.z - I.z) * t, I.w + (O.w - I.w) * t);
-}
-
 // hasView: clip = projection * (view * (model * position)) (DepthOnly.shader:51, LM = projection); else clip = (lightMatrix * model) * position
-__device__ __forceinline__ RasterTri raster_setup(const Mat4& LM, bool hasView, const Mat4& V, const float* __restrict__ model, const float* __restrict__ positions,
-                                                   const uint32_t* __restrict__ tri, int W, int H, bool cullBack, int part, bool& hasSecond)
+__device__ __forceinline__ SurfTri raster_setup(const Mat4& LM, bool hasView, const Mat4& V, const float* __restrict__ model, const float* __restrict__ positions,
+                                                 const uint32_t* __restrict__ tri, int W, int H, bool cullBack, int part, bool& hasSecond)
 {
-    RasterTri t;
+    SurfTri t;
     t.valid = false;
     hasSecond = false;
     float4 c[3];
+    float tCut; // (surf_cut's t: for the surface pass's varyings, not read here)
 #pragma unroll
     for (int k = 0; k < 3; k++) {
         const float* p = positions + 3 * (size_t)tri[k];
@@ -88,13 +74,13 @@ __device__ __forceinline__ RasterTri raster_setup(const Mat4& LM, bool hasView, 
         const float dA = r == 0 ? d0 : (r == 1 ? d1 : d2), dB = r == 0 ? d1 : (r == 1 ? d2 : d0), dC = r == 0 ? d2 : (r == 1 ? d0 : d1);
         if (one) {
             if (part) return t;
-            c[0] = A; c[1] = raster_cut(A, dA, B, dB); c[2] = raster_cut(A, dA, C, dC);
+            c[0] = A; c[1] = surf_cut(A, dA, B, dB, tCut); c[2] = surf_cut(A, dA, C, dC, tCut);
         } else {
-            const float4 BC = raster_cut(B, dB, C, dC);
+            const float4 BC = surf_cut(B, dB, C, dC, tCut);
             hasSecond = true;
             c[0] = A;
             if (part == 0) { c[1] = B; c[2] = BC; }
-            else { c[1] = BC; c[2] = raster_cut(A, dA, C, dC); }
+            else { c[1] = BC; c[2] = surf_cut(A, dA, C, dC, tCut); }
         }
     } else if (part) return t;
     long long X[3], Y[3];
@@ -118,8 +104,8 @@ __device__ __forceinline__ RasterTri raster_setup(const Mat4& LM, bool hasView, 
     t.z0 = Z[0]; t.z1 = Z[1]; t.z2 = Z[2];
     const long long minx = min(X[0], min(X[1], X[2])), maxx = max(X[0], max(X[1], X[2]));
     const long long miny = min(Y[0], min(Y[1], Y[2])), maxy = max(Y[0], max(Y[1], Y[2]));
-    long long i0 = raster_floor_div256(minx - 128 + 255), i1 = raster_floor_div256(maxx - 128);
-    long long j0 = raster_floor_div256(miny - 128 + 255), j1 = raster_floor_div256(maxy - 128);
+    long long i0 = surf_floor_div256(minx - 128 + 255), i1 = surf_floor_div256(maxx - 128);
+    long long j0 = surf_floor_div256(miny - 128 + 255), j1 = surf_floor_div256(maxy - 128);
     if (i0 < 0) i0 = 0;
     if (j0 < 0) j0 = 0;
     if (i1 > W - 1) i1 = W - 1;
@@ -130,16 +116,6 @@ __device__ __forceinline__ RasterTri raster_setup(const Mat4& LM, bool hasView, 
     return t;
 }
 
-__device__ __forceinline__ long long raster_edge(long long ax, long long ay, long long bx, long long by, long long px, long long py)
-{
-    return (bx - ax) * (py - ay) - (by - ay) * (px - ax);
-}
-__device__ __forceinline__ bool raster_top_left(long long ax, long long ay, long long bx, long long by)
-{
-    const long long dx = bx - ax, dy = by - ay;
-    return (dy == 0 && dx > 0) || dy < 0;
-}
-
 // The depth test of one fragment: atomicMax over float bits (depths are > 0).  (Round 6: reading the stored depth before the atomic measured slower, the
 // caster draws being bound by that round trip: DESIGN.md §4 raster.)
 __device__ __forceinline__ void raster_depth_test(unsigned int* __restrict__ p, const float z)
@@ -147,25 +123,19 @@ __device__ __forceinline__ void raster_depth_test(unsigned int* __restrict__ p, 
     atomicMax(p, __float_as_uint(z)); // positive floats order like their bits
 }
 
-__device__ __forceinline__ long long bcast64(long long v, int src)
-{
-    const int lo = __shfl((int)(unsigned int)(unsigned long long)v, src, 64), hi = __shfl((int)((unsigned long long)v >> 32), src, 64);
-    return (long long)(((unsigned long long)(unsigned int)hi << 32) | (unsigned int)lo);
-}
-
 #define RASTER_Z_MARGIN 1.0e-6f // covers the rounding of the per-texel interpolation when a bound is derived from other points of the same plane
 
 // z of the triangle's plane at texel (i, j), the per-texel formula (edge functions need not be non-negative here)
-__device__ __forceinline__ float raster_plane_z(const RasterTri& t, float area, int i, int j)
+__device__ __forceinline__ float raster_plane_z(const SurfTri& t, float area, int i, int j)
 {
     const long long px = 256ll * i + 128, py = 256ll * j + 128;
-    const long long e1 = raster_edge(t.x2, t.y2, t.x0, t.y0, px, py), e2 = raster_edge(t.x0, t.y0, t.x1, t.y1, px, py);
+    const long long e1 = surf_edge(t.x2, t.y2, t.x0, t.y0, px, py), e2 = surf_edge(t.x0, t.y0, t.x1, t.y1, px, py);
     return (t.z0 + (t.z1 - t.z0) * ((float)e1 / area)) + (t.z2 - t.z0) * ((float)e2 / area);
 }
 
 // Bounds over the texel rectangle [xa, xb] x [ya, yb]: an edge function and the depth plane are affine, so their extremes sit at corner texels.
 // m* = largest value of each edge function (all >= 0 <=> the rectangle may touch the triangle), n* = smallest (all > 0 <=> it lies inside it).
-__device__ __forceinline__ void raster_box_bounds(const RasterTri& t, float area, int xa, int ya, int xb, int yb, long long& m0, long long& m1, long long& m2,
+__device__ __forceinline__ void raster_box_bounds(const SurfTri& t, float area, int xa, int ya, int xb, int yb, long long& m0, long long& m1, long long& m2,
                                                   long long& n0, long long& n1, long long& n2, float& zhi, float& zlo)
 {
     m0 = m1 = m2 = -0x7FFFFFFFFFFFFFFFll; n0 = n1 = n2 = 0x7FFFFFFFFFFFFFFFll;
@@ -174,7 +144,7 @@ __device__ __forceinline__ void raster_box_bounds(const RasterTri& t, float area
     for (int c = 0; c < 4; c++) {
         const int cx = (c & 1) ? xb : xa, cy = (c & 2) ? yb : ya;
         const long long px = 256ll * cx + 128, py = 256ll * cy + 128;
-        const long long e0 = raster_edge(t.x1, t.y1, t.x2, t.y2, px, py), e1 = raster_edge(t.x2, t.y2, t.x0, t.y0, px, py), e2 = raster_edge(t.x0, t.y0, t.x1, t.y1, px, py);
+        const long long e0 = surf_edge(t.x1, t.y1, t.x2, t.y2, px, py), e1 = surf_edge(t.x2, t.y2, t.x0, t.y0, px, py), e2 = surf_edge(t.x0, t.y0, t.x1, t.y1, px, py);
         m0 = max(m0, e0); m1 = max(m1, e1); m2 = max(m2, e2);
         n0 = min(n0, e0); n1 = min(n1, e1); n2 = min(n2, e2);
         const float z = (t.z0 + (t.z1 - t.z0) * ((float)e1 / area)) + (t.z2 - t.z0) * ((float)e2 / area);
@@ -184,16 +154,16 @@ __device__ __forceinline__ void raster_box_bounds(const RasterTri& t, float area
 
 // ---- the large triangles' inner levels, shared by k_raster_depth (a wave works through its own large triangles) and k_raster_giant (sixty-four waves share one) ----
 struct RasterEdges { float area; bool tl0, tl1, tl2; };
-__device__ __forceinline__ RasterEdges raster_edges(const RasterTri& b)
+__device__ __forceinline__ RasterEdges raster_edges(const SurfTri& b)
 {
     RasterEdges e;
-    e.area = (float)raster_edge(b.x0, b.y0, b.x1, b.y1, b.x2, b.y2);
-    e.tl0 = raster_top_left(b.x1, b.y1, b.x2, b.y2); e.tl1 = raster_top_left(b.x2, b.y2, b.x0, b.y0); e.tl2 = raster_top_left(b.x0, b.y0, b.x1, b.y1);
+    e.area = (float)surf_edge(b.x0, b.y0, b.x1, b.y1, b.x2, b.y2);
+    e.tl0 = surf_top_left(b.x1, b.y1, b.x2, b.y2); e.tl1 = surf_top_left(b.x2, b.y2, b.x0, b.y0); e.tl2 = surf_top_left(b.x0, b.y0, b.x1, b.y1);
     return e;
 }
 
 // level 2: can anything of the triangle still win in superblock (si, sj)?  (also raises the superblock's bound when the triangle covers all of it)
-__device__ __forceinline__ bool raster_superblock_alive(const RasterTri& b, const RasterEdges& E, float zmaxB, int si, int sj, int W, int H, unsigned int* __restrict__ coarse2, int SW)
+__device__ __forceinline__ bool raster_superblock_alive(const SurfTri& b, const RasterEdges& E, float zmaxB, int si, int sj, int W, int H, unsigned int* __restrict__ coarse2, int SW)
 {
     long long m0, m1, m2, n0, n1, n2;
     float zhi, zlo;
@@ -211,7 +181,7 @@ __device__ __forceinline__ bool raster_superblock_alive(const RasterTri& b, cons
 }
 
 // level 1 and the fill: superblock (csi, csj) of triangle b by the whole wave -- its 8 x 8 blocks one per lane, the surviving blocks one lane per texel
-__device__ __forceinline__ void raster_superblock(const RasterTri& b, const RasterEdges& E, float zmaxB, int csi, int csj, int lane, int W, int H,
+__device__ __forceinline__ void raster_superblock(const SurfTri& b, const RasterEdges& E, float zmaxB, int csi, int csj, int lane, int W, int H,
                                                   unsigned int* __restrict__ depthBits, unsigned int* __restrict__ coarse, unsigned int* __restrict__ coarse2, int CW, int SW)
 {
     const float area = E.area;
@@ -244,8 +214,8 @@ __device__ __forceinline__ void raster_superblock(const RasterTri& b, const Rast
         float z = 2.0f;
         if (i >= b.i0 && i <= b.i1 && j >= b.j0 && j <= b.j1) {
             const long long px = 256ll * i + 128, py = 256ll * j + 128;
-            const long long e0 = raster_edge(b.x1, b.y1, b.x2, b.y2, px, py), e1 = raster_edge(b.x2, b.y2, b.x0, b.y0, px, py),
-                            e2 = raster_edge(b.x0, b.y0, b.x1, b.y1, px, py);
+            const long long e0 = surf_edge(b.x1, b.y1, b.x2, b.y2, px, py), e1 = surf_edge(b.x2, b.y2, b.x0, b.y0, px, py),
+                            e2 = surf_edge(b.x0, b.y0, b.x1, b.y1, px, py);
             const bool in = !(e0 < 0 || e1 < 0 || e2 < 0) && !((e0 == 0 && !E.tl0) || (e1 == 0 && !E.tl1) || (e2 == 0 && !E.tl2));
             if (in) {
                 z = (b.z0 + (b.z1 - b.z0) * ((float)e1 / area)) + (b.z2 - b.z0) * ((float)e2 / area);
@@ -279,7 +249,7 @@ __device__ __forceinline__ void raster_superblock(const RasterTri& b, const Rast
 #endif
 #define RASTER_GIANT_WORDS 24 // x0 y0 x1 y1 x2 y2 (int64 each), z0 z1 z2, i0 i1 j0 j1, zmax, pad
 #define RASTER_GIANT_GRID 1024u // queue entries that get blocks of their own in one launch of k_raster_giant (x 16 blocks of four waves each)
-__device__ __forceinline__ bool raster_giant_push(unsigned int* __restrict__ giants, unsigned int giantCap, const RasterTri& b, float zmaxB, int lane)
+__device__ __forceinline__ bool raster_giant_push(unsigned int* __restrict__ giants, unsigned int giantCap, const SurfTri& b, float zmaxB, int lane)
 {
     unsigned int slot = 0;
     if (lane == 0) slot = atomicAdd(giants, 1u);
@@ -305,7 +275,7 @@ __global__ __launch_bounds__(256) void k_raster_giant(const unsigned int* __rest
     // blocks behind every chunk of every draw -- and walks the queue in strides)
     for (unsigned int entry = blockIdx.x; entry < count; entry += gridDim.x) {
     const unsigned int* e = giants + 4 + (size_t)entry * RASTER_GIANT_WORDS;
-    RasterTri b;
+    SurfTri b;
     long long xy[6];
 #pragma unroll
     for (int k = 0; k < 6; k++) xy[k] = (long long)(((unsigned long long)e[2 * k + 1] << 32) | e[2 * k]);
@@ -428,7 +398,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     bool again = false;
     for (int part = 0; part < 2; part++) {
         if (part && !__any(again)) break;
-        RasterTri t;
+        SurfTri t;
         t.valid = false;
         bool second = false;
         if (have) {
@@ -450,12 +420,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                 hidden = zmaxTri <= fminf(fminf(__uint_as_float(r0[t.i0 >> 3]), __uint_as_float(r0[t.i1 >> 3])), fminf(__uint_as_float(r1[t.i0 >> 3]), __uint_as_float(r1[t.i1 >> 3])));
             }
             if (!hidden) {
-                const float area = (float)raster_edge(t.x0, t.y0, t.x1, t.y1, t.x2, t.y2);
-                const bool tl0 = raster_top_left(t.x1, t.y1, t.x2, t.y2), tl1 = raster_top_left(t.x2, t.y2, t.x0, t.y0), tl2 = raster_top_left(t.x0, t.y0, t.x1, t.y1);
+                const float area = (float)surf_edge(t.x0, t.y0, t.x1, t.y1, t.x2, t.y2);
+                const bool tl0 = surf_top_left(t.x1, t.y1, t.x2, t.y2), tl1 = surf_top_left(t.x2, t.y2, t.x0, t.y0), tl2 = surf_top_left(t.x0, t.y0, t.x1, t.y1);
                 // (round 6: the three edge functions walked texel by texel -- exact integer steps of 256 sub-pixels, -256 (by - ay) along x and 256 (bx - ax)
                 // along y -- instead of six 64-bit multiplications per texel: the far cascades are made of these triangles)
                 const long long px0 = 256ll * t.i0 + 128, py0 = 256ll * t.j0 + 128;
-                long long r0 = raster_edge(t.x1, t.y1, t.x2, t.y2, px0, py0), r1 = raster_edge(t.x2, t.y2, t.x0, t.y0, px0, py0), r2 = raster_edge(t.x0, t.y0, t.x1, t.y1, px0, py0);
+                long long r0 = surf_edge(t.x1, t.y1, t.x2, t.y2, px0, py0), r1 = surf_edge(t.x2, t.y2, t.x0, t.y0, px0, py0), r2 = surf_edge(t.x0, t.y0, t.x1, t.y1, px0, py0);
                 const long long dx0 = -256ll * (t.y2 - t.y1), dx1 = -256ll * (t.y0 - t.y2), dx2 = -256ll * (t.y1 - t.y0);
                 const long long dy0 = 256ll * (t.x2 - t.x1), dy1 = 256ll * (t.x0 - t.x2), dy2 = 256ll * (t.x1 - t.x0);
                 for (int j = t.j0; j <= t.j1; j++, r0 += dy0, r1 += dy1, r2 += dy2) {
@@ -474,8 +444,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         while (todo) {
             const int src = __builtin_ctzll(todo);
             todo &= todo - 1ull;
-            RasterTri b;
-            b.x0 = bcast64(t.x0, src); b.y0 = bcast64(t.y0, src); b.x1 = bcast64(t.x1, src); b.y1 = bcast64(t.y1, src); b.x2 = bcast64(t.x2, src); b.y2 = bcast64(t.y2, src);
+            SurfTri b;
+            b.x0 = surf_bcast64(t.x0, src); b.y0 = surf_bcast64(t.y0, src); b.x1 = surf_bcast64(t.x1, src); b.y1 = surf_bcast64(t.y1, src); b.x2 = surf_bcast64(t.x2, src); b.y2 = surf_bcast64(t.y2, src);
             b.z0 = __shfl(t.z0, src, 64); b.z1 = __shfl(t.z1, src, 64); b.z2 = __shfl(t.z2, src, 64);
             b.i0 = __shfl(t.i0, src, 64); b.i1 = __shfl(t.i1, src, 64); b.j0 = __shfl(t.j0, src, 64); b.j1 = __shfl(t.j1, src, 64);
             const float zmaxB = __shfl(zmaxTri, src, 64);

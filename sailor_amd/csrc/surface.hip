@@ -12,11 +12,11 @@
 //   k_surface_composite   target = covered ? radiance : target
 //
 // The depth of a fragment and everything in front of it (clip, cut, snap, edges, top-left) are raster.hip's, so that the depth is the prepass's bit for
-// bit.  raster.hip keeps its set-up functions static and reads tightly packed positions; the few of them needed here are COPIED in surface_common.h
-// (surf_cut, surf_floor_div256, surf_edge, surf_top_left, and surface_setup = raster_setup over interleaved vertices that also reports where each vertex came
-// from), which this file shares with surface_masked.hip (the Masked queue: ALPHA_CUTOUT in the draw) and surface_gltf.hip (Standard_glTF.shader).
-#include "surface_common.h"
-
+// bit.  The helpers are written once, in raster_prims.h, for both (SurfTri, surf_cut, surf_floor_div256, surf_edge, surf_top_left, surf_bcast64).  raster.hip
+// reads tightly packed positions and keeps its own raster_setup; surface_setup (surface_common.h) is that set-up over interleaved vertices, which also
+// reports where each vertex came from.  The fill of a set-up triangle is surface_fill.h's, shared with surface_masked.hip (the Masked queue:
+// ALPHA_CUTOUT in the draw), surface_gltf.hip (Standard_glTF.shader), surface_indirect.hip and particles.hip.
+#include "surface_fill.h"
 
 __global__ __launch_bounds__(256) void k_surface_begin(const float* __restrict__ depth, int W, int rowBegin, int rows, uint32_t maxDraws, void* __restrict__ workspace,
                                                        SurfSrgb table)
@@ -76,74 +76,9 @@ __global__ __launch_bounds__(256) void k_surface_visibility(Mat4 P, Mat4 V, Sail
                               part, second, S);
         }
         const unsigned int orderPlus1 = draw.primBase + (unsigned int)(2ull * id) + (unsigned int)part + 1u; // (the entry point has checked the range)
-        const bool small = t.valid && (long long)(t.i1 - t.i0 + 1) * (t.j1 - t.j0 + 1) <= SURF_SMALL_BOX;
-        if (small && slice == 0) {
-            const float area = (float)surf_edge(t.x0, t.y0, t.x1, t.y1, t.x2, t.y2);
-            const bool tl0 = surf_top_left(t.x1, t.y1, t.x2, t.y2), tl1 = surf_top_left(t.x2, t.y2, t.x0, t.y0), tl2 = surf_top_left(t.x0, t.y0, t.x1, t.y1);
-            // the three edge functions walked texel by texel in exact integer steps, as k_raster_depth does
-            const long long px0 = 256ll * t.i0 + 128, py0 = 256ll * t.j0 + 128;
-            long long r0 = surf_edge(t.x1, t.y1, t.x2, t.y2, px0, py0), r1 = surf_edge(t.x2, t.y2, t.x0, t.y0, px0, py0), r2 = surf_edge(t.x0, t.y0, t.x1, t.y1, px0, py0);
-            const long long dx0 = -256ll * (t.y2 - t.y1), dx1 = -256ll * (t.y0 - t.y2), dx2 = -256ll * (t.y1 - t.y0);
-            const long long dy0 = 256ll * (t.x2 - t.x1), dy1 = 256ll * (t.x0 - t.x2), dy2 = 256ll * (t.x1 - t.x0);
-            for (int j = t.j0; j <= t.j1; j++, r0 += dy0, r1 += dy1, r2 += dy2) {
-                long long e0 = r0, e1 = r1, e2 = r2;
-                for (int i = t.i0; i <= t.i1; i++, e0 += dx0, e1 += dx1, e2 += dx2) {
-                    if (e0 < 0 || e1 < 0 || e2 < 0) continue;
-                    if ((e0 == 0 && !tl0) || (e1 == 0 && !tl1) || (e2 == 0 && !tl2)) continue;
-                    const float z = (t.z0 + (t.z1 - t.z0) * ((float)e1 / area)) + (t.z2 - t.z0) * ((float)e2 / area);
-                    if (z > 0.0f && z <= 1.0f) surf_fragment(keys + (size_t)(j - rowBegin) * W + i, z, orderPlus1);
-                }
-            }
-        }
-        // the large ones: the whole wave on one triangle at a time
-        unsigned long long todo = __ballot(t.valid && !small);
-        while (todo) {
-            const int src = __builtin_ctzll(todo);
-            todo &= todo - 1ull;
-            SurfTri b;
-            b.x0 = surf_bcast64(t.x0, src); b.y0 = surf_bcast64(t.y0, src); b.x1 = surf_bcast64(t.x1, src); b.y1 = surf_bcast64(t.y1, src);
-            b.x2 = surf_bcast64(t.x2, src); b.y2 = surf_bcast64(t.y2, src);
-            b.z0 = __shfl(t.z0, src, 64); b.z1 = __shfl(t.z1, src, 64); b.z2 = __shfl(t.z2, src, 64);
-            b.i0 = __shfl(t.i0, src, 64); b.i1 = __shfl(t.i1, src, 64); b.j0 = __shfl(t.j0, src, 64); b.j1 = __shfl(t.j1, src, 64);
-            const unsigned int bOrder = (unsigned int)__shfl((int)orderPlus1, src, 64);
-            const float area = (float)surf_edge(b.x0, b.y0, b.x1, b.y1, b.x2, b.y2);
-            const bool tl0 = surf_top_left(b.x1, b.y1, b.x2, b.y2), tl1 = surf_top_left(b.x2, b.y2, b.x0, b.y0), tl2 = surf_top_left(b.x0, b.y0, b.x1, b.y1);
-            // 64 x 64-texel superblocks of the box one after the other; of each, the 8 x 8 blocks one per lane: a block wholly outside an edge is dropped
-            // (an edge function is affine, so its largest value over the block sits at a corner texel)
-            unsigned int number = 0;
-            for (int sj = b.j0 >> 6; sj <= (b.j1 >> 6); sj++)
-                for (int si = b.i0 >> 6; si <= (b.i1 >> 6); si++) {
-                    if (number++ % slices != slice) continue;
-                    const int bi = si * 8 + (lane & 7), bj = sj * 8 + (lane >> 3);
-                    bool alive = bi >= (b.i0 >> 3) && bi <= (b.i1 >> 3) && bj >= (b.j0 >> 3) && bj <= (b.j1 >> 3);
-                    if (alive) {
-                        long long m0 = -0x7FFFFFFFFFFFFFFFll, m1 = m0, m2 = m0;
-#pragma unroll
-                        for (int c = 0; c < 4; c++) {
-                            const long long px = 256ll * (bi * 8 + ((c & 1) ? 7 : 0)) + 128, py = 256ll * (bj * 8 + ((c & 2) ? 7 : 0)) + 128;
-                            m0 = max(m0, surf_edge(b.x1, b.y1, b.x2, b.y2, px, py)); m1 = max(m1, surf_edge(b.x2, b.y2, b.x0, b.y0, px, py));
-                            m2 = max(m2, surf_edge(b.x0, b.y0, b.x1, b.y1, px, py));
-                        }
-                        alive = m0 >= 0 && m1 >= 0 && m2 >= 0;
-                    }
-                    unsigned long long live = __ballot(alive);
-                    while (live) { // the surviving blocks, one lane per texel
-                        const int s2 = __builtin_ctzll(live);
-                        live &= live - 1ull;
-                        const int i = (si * 8 + (s2 & 7)) * 8 + (lane & 7), j = (sj * 8 + (s2 >> 3)) * 8 + (lane >> 3);
-                        if (i >= b.i0 && i <= b.i1 && j >= b.j0 && j <= b.j1) {
-                            const long long px = 256ll * i + 128, py = 256ll * j + 128;
-                            const long long e0 = surf_edge(b.x1, b.y1, b.x2, b.y2, px, py), e1 = surf_edge(b.x2, b.y2, b.x0, b.y0, px, py),
-                                            e2 = surf_edge(b.x0, b.y0, b.x1, b.y1, px, py);
-                            const bool in = !(e0 < 0 || e1 < 0 || e2 < 0) && !((e0 == 0 && !tl0) || (e1 == 0 && !tl1) || (e2 == 0 && !tl2));
-                            if (in) {
-                                const float z = (b.z0 + (b.z1 - b.z0) * ((float)e1 / area)) + (b.z2 - b.z0) * ((float)e2 / area);
-                                if (z > 0.0f && z <= 1.0f) surf_fragment(keys + (size_t)(j - rowBegin) * W + i, z, bOrder);
-                            }
-                        }
-                    }
-                }
-        }
+        surf_fill(t, orderPlus1, SurfNoPayload(), SurfNoBcast(), slice, slices, lane, [&](int i, int j, float z, unsigned int tag, auto&&...) {
+            surf_fragment(keys + (size_t)(j - rowBegin) * W + i, z, tag);
+        });
         if (part == 0) again = second;
     }
 }

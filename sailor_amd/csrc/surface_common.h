@@ -1,5 +1,5 @@
 // What the surface-pass translation units share (surface.hip: the Opaque queue; surface_masked.hip: the Masked queue with ALPHA_CUTOUT; surface_gltf.hip:
-// Standard_glTF.shader's materials): the set-up copied from raster.hip, the depth test of one fragment, the workspace layout, the varyings of a vertex, the
+// Standard_glTF.shader's materials): the set-up (raster.hip's rules over interleaved vertices, on the helpers of raster_prims.h), the depth test of one fragment, the workspace layout, the varyings of a vertex, the
 // texture taps and the checks of the entry points.  Those checks are written once, host-only, at the end of this file: surf_workspace_why (band, workspace
 // alignment, descriptor slots) for every entry that takes the workspace, surf_draw_prologue (every check of the four draw entries, their matrices and their
 // grid with its slices) and surf_resolve_why (the two resolves).  An entry keeps the checks that are its own and its launch; surf_refuse puts the entry's
@@ -8,7 +8,7 @@
 #include "common.h"
 #include "sampling.h"
 #include "texel_pass.h"
-#include <math.h>
+#include "raster_prims.h"
 
 #define SURF_SMALL_BOX 64   // pixels a lane fills on its own
 #define SURF_VERTEX_FLOATS 18
@@ -22,27 +22,9 @@
 struct SurfHeader { uint32_t maxDraws, rows, width, fbRowBegin; uint32_t pad[12]; };
 struct SurfSrgb { float v[256]; };
 
-struct SurfTri { long long x0, y0, x1, y1, x2, y2; float z0, z1, z2; int i0, i1, j0, j1; bool valid; };
 // where the three vertices of a set-up triangle came from: vertex k is source vertex I[k], or -- cut[k] -- the point I[k] + (O[k] - I[k]) * t[k] of an
 // edge the near plane cut; w[k] is its clip w
 struct SurfSrc { uint32_t I[3], O[3]; float t[3], w[3]; bool cut[3]; };
-
-// ---- copied from raster.hip (static there) --------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ long long surf_floor_div256(long long a) { return a >= 0 ? a / 256 : -((-a + 255) / 256); }
-__device__ __forceinline__ float4 surf_cut(const float4& I, float dI, const float4& O, float dO, float& t)
-{
-    t = dI / (dI - dO);
-    return make_float4(I.x + (O.x - I.x) * t, I.y + (O.y - I.y) * t, I.z + (O.z - I.z) * t, I.w + (O.w - I.w) * t);
-}
-__device__ __forceinline__ long long surf_edge(long long ax, long long ay, long long bx, long long by, long long px, long long py)
-{
-    return (bx - ax) * (py - ay) - (by - ay) * (px - ax);
-}
-__device__ __forceinline__ bool surf_top_left(long long ax, long long ay, long long bx, long long by)
-{
-    const long long dx = bx - ax, dy = by - ay;
-    return (dy == 0 && dx > 0) || dy < 0;
-}
 
 // raster_setup of raster.hip from the clip positions c[0..2] of the triangle's vertices v0, v1, v2 on: the near-plane cut, the snap, the cull and the box;
 // rows [rowBegin, rowEnd) of the frame only.  S reports the vertices' sources for the varyings (dead code where it is not read).
@@ -158,12 +140,6 @@ __device__ __forceinline__ SurfTri surface_setup_matrix(const Mat4& LM, const fl
         c[k] = glsl_mul(LM, p[0], p[1], p[2], 1.0f);
     }
     return surface_setup_clip(c, v0, v1, v2, W, H, rowBegin, rowEnd, cullBack, part, hasSecond, S);
-}
-
-__device__ __forceinline__ long long surf_bcast64(long long v, int src)
-{
-    const int lo = __shfl((int)(unsigned int)(unsigned long long)v, src, 64), hi = __shfl((int)((unsigned long long)v >> 32), src, 64);
-    return (long long)(((unsigned long long)(unsigned int)hi << 32) | (unsigned int)lo);
 }
 
 // the depth test of one fragment, GreaterOrEqual in primitive order: the larger key wins.  A relaxed atomic load first (other waves run atomicMax on the

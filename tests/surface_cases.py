@@ -344,7 +344,8 @@ CASES = {
     "constant_material_quad": (constant_material_quad, lambda r: r["covered"].all()),
 }
 CULL_BACK_CASES = ("shared_edge_quad", "tie_coplanar_reversed_indices", "near_plane", "materials_and_normal_map")
-BAND_CASES = ("near_plane", "materials_and_normal_map", "grazing_quad")   # 72 x 40: three tile rows
+# 72 x 40: three tile rows; the last is 200 x 136, 4 x 3 superblocks of a large triangle in bands whose first row is no multiple of 64
+BAND_CASES = ("near_plane", "materials_and_normal_map", "grazing_quad", "triangle_larger_than_the_frame")
 GOLDEN_CASES = ("near_plane", "instance_indirection", "texture_2x3_srgb")
 NUM_SOUPS = 40
 

@@ -88,7 +88,12 @@ def test_a_prepass_with_geometry_the_scene_does_not_draw_keeps_its_depth_uncover
 def test_bands_concatenate_to_the_whole_frame(rendered):
     for name in cases.BAND_CASES:
         s, whole = cases.CASES[name][0](), rendered[name]
-        for bounds in ((0, 24, 40), (0, 8, 24, 40)):   # framebuffer rows of tile-row bands of the 72 x 40 frame (tile row t = rows H - 16 (t + 1) .. H - 16 t)
+        H = s["H"]
+        tile_rows = -(-H // 16)
+        for world in (2, 3):
+            # framebuffer rows of the bands of `world` ranks: rank r holds tile rows r T / world .. (r + 1) T / world, and tile row t = rows
+            # H - 16 (t + 1) .. H - 16 t, the topmost cut at row 0 (72 x 40: 0 / 24 / 40 and 0 / 8 / 24 / 40; 200 x 136: 0 / 72 / 136 and 0 / 40 / 88 / 136)
+            bounds = sorted(max(0, H - 16 * (r * tile_rows // world)) for r in range(world + 1))
             parts = [ref.render(s, rows=(a, b)) for a, b in zip(bounds[:-1], bounds[1:])]
             np.testing.assert_array_equal(np.concatenate([p["keys"] for p in parts]), whole["keys"])
             assert ref.same_bits_or_class(np.concatenate([p["planes"] for p in parts], axis=1), whole["planes"]).all()
