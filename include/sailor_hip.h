@@ -1227,7 +1227,8 @@ SAILOR_HIP_API int sailor_host_csm_plan_passes(SailorCsmSnapshots* snapshots, ui
  * triangle the near plane cut in two); low word 0 = no primitive.  Varyings are perspective-correct: l_k = float(e_k) / area, q_k = l_k / w_k,
  * s = (q0 + q1) + q2, b_k = q_k / s, a = (a0 b0 + a1 b1) + a2 b2; a vertex cut on the near plane gets a = aI + (aO - aI) t with the position's t.
  * texture() is the base level, bilinear, Repeat over RGBA8 texels; SAILOR_TEXTURE_SRGB decodes r, g, b per tap through sailor_host_srgb_table before
- * filtering.  NOT reproduced: the implicit mip selection of texture() (textures have one level here), anisotropy.
+ * filtering.  The implicit mip selection of texture() (a descriptor with levels > 1): the `_lod` entry points of the mip-mapped section below; every entry
+ * point of this section, of the Masked, glTF and indirect sections ignores SailorTextureDesc.levels and reads level 0.  NOT reproduced: anisotropy.
  * (Standard_glTF.shader: the glTF section below.)  A sampler index >= numTextures reads descriptor 0 (the reference binds g_defaultSampler there), a materialInstance >=
  * numMaterials reads material 0, a descriptor without texels samples as 0: no fetch leaves a table.
  * All entry points record only (no allocation, no synchronisation, capturable); a refused call launches nothing and leaves a text in last_error. */
@@ -1268,7 +1269,8 @@ typedef struct SailorTextureDesc {
     int32_t width;
     int32_t height;
     uint32_t flags;
-    uint32_t _pad;
+    uint32_t levels;        /* the mip levels behind `texels`, clamped to 1 .. floor(log2(max(width, height))) + 1 (0 reads as 1): the mip-mapped section below;
+                               read by the `_lod` entry points only */
 } SailorTextureDesc;
 
 /* one DrawIndexed of RenderSceneNode.cpp (BindVertexBuffer / BindIndexBuffer / DrawIndexed): the draw kernel stores it into slot drawIndex of the
@@ -1461,6 +1463,65 @@ SAILOR_HIP_API int sailor_hip_surface_draw_indirect(SailorHipContext* ctx, const
                                                     uint32_t numInstanceRecords, const SailorMaterialData* dMaterials, uint32_t numMaterials,
                                                     const SailorTextureDesc* dTextures, uint32_t numTextures, uint32_t drawIndex, int32_t width, int32_t height,
                                                     const SailorBand* band, void* dWorkspace, size_t workspaceBytes);
+
+/* ---- Mip-mapped material textures: chain generation and the implicit level of detail (texture_mips.hip, surface_lod.hip) ------------------------------
+ * Replaces: TextureAssetInfo.h:34 (m_bShouldGenerateMips = true), TextureImporter.cpp:247-295 (mipLevels = floor(log2(max(w, h))) + 1),
+ * VulkanCommandBuffer.cpp:814-907 (the chain, built by 2:1 VK_FILTER_LINEAR blits) and VulkanSamplers.cpp:37-40 (mipmapMode LINEAR, mipLodBias 0, minLod 0,
+ * maxLod 64): every texture(textureSamplers[...], vin.texcoord) of Standard.shader and Standard_glTF.shader is a trilinear fetch at an implicit level of
+ * detail, the one behind ALPHA_CUTOUT included.  Vulkan leaves the scale factor partly to the implementation.  Pinned:
+ *  1. The chain.  A descriptor has n = clamp(levels, 1, full) levels, full = floor(log2(max(width, height))) + 1 in integers, levels == 0 reads as 1.  Level l
+ *     has max(width >> l, 1) x max(height >> l, 1) texels and begins sailor_hip_mip_chain_texels(width, height, l) uint32 texels behind `texels`.
+ *  2. Generation, level l + 1 from level l, per channel: decode the byte (r, g, b through sailor_host_srgb_table under SAILOR_TEXTURE_SRGB; alpha and
+ *     unflagged channels as byte / 255.0f), filter with sailor_hip_blit_linear's tap set (bilinear_taps at ((x + 0.5) / wd, (y + 0.5) / hd), lerp2: for even
+ *     extents the 2 x 2 mean with weights of exactly 0.5), encode: sRGB -> the number of entries of sailor_host_srgb_encode_table that are <= x; UNORM ->
+ *     (uint)floorf(x * 255.0f + 0.5f).
+ *  3. Derivatives.  For pixel (i, j), j the framebuffer row, uv(X, Y) = (a[0], a[1]) of the surface pass's varying formula for the owning part's set-up,
+ *     evaluated with the exact integer edge functions at the centre (256 X + 128, 256 Y + 128) whether or not that centre lies in the triangle or the frame
+ *     (Vulkan's helper invocations).  Fine derivatives inside the quad at (i & ~1, j & ~1), one fp32 subtraction each:
+ *       d/dx = uv(i | 1, j) - uv(i & ~1, j)           d/dy = uv(i, j | 1) - uv(i, j & ~1)
+ *     A pure function of (the owning primitive's set-up, the pixel): keys stay order-free, a band needs no neighbour rows.
+ *  4. Scale factor, per descriptor (its own w, h), one rounding per written operation:
+ *       ax = dudx * float(w), bx = dvdx * float(h), rx = ax * ax + bx * bx;  ay = dudy * float(w), by = dvdy * float(h), ry = ay * ay + by * by;
+ *       r2 = ry > rx ? ry : rx
+ *  5. Level selection: !(r2 > 1.0f) -> level 0 alone (magnification, zero, NaN); else r2 >= 4^(n-1) -> level n - 1 alone (+inf); else
+ *       lambda = 0.5f * canonical_log2f(r2), hi = (int)lambda; hi >= n - 1 -> level n - 1 alone; else delta = lambda - float(hi), lo = hi + 1 and per channel
+ *       t = t_hi * (1.0f - delta) + t_lo * delta
+ *     with each t_l the surface pass's base-level fetch (repeat_tap, lerp2, sRGB per tap) over level l's extents.  n == 1 is that fetch bit for bit; no
+ *     derivative is formed.  A descriptor without texels samples 0.
+ *  6. ALPHA_CUTOUT through the `_lod` draws tests alpha with tA.w fetched by rules 3-5 through the albedo / base-colour sampler, in the draw, before the key is
+ *     issued; the neighbour centres' edge functions are affine steps of the fragment's own (exact).  At every pixel such a draw owns,
+ *     sailor_hip_surface_resolve_lod's P0.w is, bit for bit, the alpha that was tested.  Without ALPHA_CUTOUT the keys are sailor_hip_surface_draw's.
+ * NOT reproduced: anisotropy (maxAnisotropy = 8 is implementation-defined), textureLod and bias, the UI and particle textures, formats other than RGBA8, the
+ * Transparent queue.
+ * All device entry points record only (no allocation, no synchronisation, capturable); a refused call launches nothing and leaves its text in last_error. */
+
+/* floor(log2(max(width, height))) + 1 by integer operations; 0 for an extent outside 1 .. 32768 */
+SAILOR_HIP_API uint32_t sailor_hip_texture_mip_levels(int32_t width, int32_t height);
+/* out[k - 1] = the sRGB transfer function of (k - 0.5) / 255 in double, rounded once to fp32, k = 1 .. 255: the byte of x is the number of entries <= x */
+SAILOR_HIP_API int sailor_host_srgb_encode_table(float out[255]);
+/* Replaces: GenerateMipMaps for one 2-D RGBA8 image (VulkanCommandBuffer.cpp:814-907): k_texture_mip_down, one launch per level, in place.  dTexels holds
+ * level 0 and room for sailor_hip_mip_chain_texels(width, height, levels) texels; flags = SAILOR_TEXTURE_SRGB or 0.  Refused: dTexels NULL or not 4-byte
+ * aligned, an extent outside 1 .. 32768, levels outside 1 .. sailor_hip_texture_mip_levels(width, height), unknown flag bits. */
+SAILOR_HIP_API int sailor_hip_texture_generate_mips(SailorHipContext* ctx, uint32_t* dTexels, int32_t width, int32_t height, uint32_t levels, uint32_t flags);
+/* sailor_hip_surface_resolve_gltf with every fetch (four of a Standard pixel, five of a glTF pixel) by rules 3-5: k_surface_resolve_lod.  Its arguments,
+ * checks and refusals; a pass of either or both shaders. */
+SAILOR_HIP_API int sailor_hip_surface_resolve_lod(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorPerInstanceData* dInstances,
+                                                  const SailorMaterialData* dMaterials, uint32_t numMaterials, const SailorTextureDesc* dTextures, uint32_t numTextures,
+                                                  int32_t width, int32_t height, const SailorBand* band, const void* dWorkspace, size_t workspaceBytes,
+                                                  float* dSurface, size_t planeStride, float* dDepthOutOrNull, uint8_t* dCoverageOrNull,
+                                                  const float* dAoInOrNull, float* dAoOutOrNull, float* dEmissive);
+/* sailor_hip_surface_draw_masked / _draw_gltf with rule 6: k_surface_visibility_lod, or k_surface_visibility_lod_gltf if the draw carries SAILOR_SURFACE_GLTF
+ * (optional here).  Their arguments, checks and refusals. */
+SAILOR_HIP_API int sailor_hip_surface_draw_lod(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSurfaceDraw* draw,
+                                               const SailorPerInstanceData* dInstances, const SailorMaterialData* dMaterials, uint32_t numMaterials,
+                                               const SailorTextureDesc* dTextures, uint32_t numTextures, uint32_t drawIndex, int32_t width, int32_t height,
+                                               const SailorBand* band, void* dWorkspace, size_t workspaceBytes);
+/* sailor_hip_surface_draw_indirect with rule 6: k_surface_visibility_indirect_lod[_gltf].  Its arguments, checks and refusals. */
+SAILOR_HIP_API int sailor_hip_surface_draw_indirect_lod(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSurfaceDraw* draw,
+                                                        const SailorDrawIndexedIndirectData* dCommand, const SailorPerInstanceData* dInstances,
+                                                        uint32_t numInstanceRecords, const SailorMaterialData* dMaterials, uint32_t numMaterials,
+                                                        const SailorTextureDesc* dTextures, uint32_t numTextures, uint32_t drawIndex, int32_t width, int32_t height,
+                                                        const SailorBand* band, void* dWorkspace, size_t workspaceBytes);
 
 /* ---- DebugDraw: the line-list pass of the Gizmo material (debug_lines.hip) ---------------------------------------------------------------------
  * Replaces: the draw FrameGraph/DebugDrawNode.cpp:19-79 replays -- RHI/DebugContext.cpp:382-398 (DrawDebugMesh: one DrawIndexed over the line list that

@@ -218,7 +218,7 @@ class GltfMaterialData(C.Structure):  # Standard_glTF.shader:42-58, std430
 
 
 class TextureDesc(C.Structure):  # include/sailor_hip.h SailorTextureDesc: one entry of Standard.shader:124 textureSamplers[]
-    _fields_ = [("texels", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+    _fields_ = [("texels", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("flags", C.c_uint32), ("levels", C.c_uint32)]
 
 
 class SurfaceDraw(C.Structure):  # include/sailor_hip.h SailorSurfaceDraw: one DrawIndexed of RenderSceneNode.cpp
@@ -285,7 +285,7 @@ PARTICLE_INSTANCE_DTYPE = [("model", "<f4", 16), ("color", "<f4", 4), ("colorOld
 assert C.sizeof(ParticleData) == 80 and C.sizeof(ParticleInstance) == 112 and C.sizeof(ParticlesConstants) == 20 and C.sizeof(ParticlesDraw) == 24
 
 assert C.sizeof(VertexP3N3T3B3UV2C4) == 72 and C.sizeof(MaterialData) == 80 and C.sizeof(GltfMaterialData) == 80
-assert C.sizeof(TextureDesc) == 24 and C.sizeof(SurfaceDraw) == 48
+assert C.sizeof(TextureDesc) == 24 and TextureDesc.levels.offset == 20 and C.sizeof(SurfaceDraw) == 48
 assert C.sizeof(UboFrameData) == 232 and C.sizeof(LightCullPushConstants) == 88 and C.sizeof(LightShaderData) == 112
 
 _P = C.c_void_p
@@ -470,6 +470,15 @@ SIGNATURES = {
     "sailor_hip_surface_composite_gltf": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P, C.c_int32, C.c_int32, C.POINTER(Band)]),
     "sailor_hip_surface_draw_indirect": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(SurfaceDraw), _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32,
                                                    C.c_int32, C.c_int32, C.POINTER(Band), _P, C.c_size_t]),
+    "sailor_hip_texture_mip_levels": (C.c_uint32, [C.c_int32, C.c_int32]),
+    "sailor_host_srgb_encode_table": (C.c_int, [C.POINTER(C.c_float)]),
+    "sailor_hip_texture_generate_mips": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32]),
+    "sailor_hip_surface_resolve_lod": (C.c_int, [_P, C.POINTER(UboFrameData), _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, C.c_int32, C.POINTER(Band), _P, C.c_size_t,
+                                                 _P, C.c_size_t, _P, _P, _P, _P, _P]),
+    "sailor_hip_surface_draw_lod": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(SurfaceDraw), _P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32,
+                                              C.POINTER(Band), _P, C.c_size_t]),
+    "sailor_hip_surface_draw_indirect_lod": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(SurfaceDraw), _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32,
+                                                       C.c_int32, C.c_int32, C.POINTER(Band), _P, C.c_size_t]),
     "sailor_hip_surface_keys_offset": (C.c_size_t, []),
     "sailor_host_srgb_table": (C.c_int, [C.POINTER(C.c_float)]),
     "sailor_hip_surface_draw_prims": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),

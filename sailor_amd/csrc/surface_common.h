@@ -164,21 +164,28 @@ static __host__ __device__ __forceinline__ SurfWorkspace surf_workspace(void* ba
     return w;
 }
 
-// texture(textureSamplers[index], uv): base level, bilinear, Repeat; SRGB decodes r, g, b per tap through the table before the filter
-__device__ __forceinline__ float4 surf_texture(const SailorTextureDesc* __restrict__ textures, uint32_t numTextures, uint32_t index, const float* __restrict__ srgb,
-                                               float u, float v)
+// the bilinear Repeat fetch of one width x height RGBA8 level; SRGB decodes r, g, b per tap through the table before the filter
+__device__ __forceinline__ float4 surf_texels_fetch(const uint32_t* __restrict__ texels, int width, int height, uint32_t flags, const float* __restrict__ srgb, float u,
+                                                    float v)
 {
-    const SailorTextureDesc d = textures[index < numTextures ? index : 0u];
-    if (!d.texels || d.width <= 0 || d.height <= 0) return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (!(d.flags & SAILOR_TEXTURE_SRGB)) return bilinear_repeat_rgba8(d.texels, d.width, d.height, u, v);
-    const RepeatTap X = repeat_tap(d.width, u), Y = repeat_tap(d.height, v);
-    const uint32_t a = d.texels[Y.i0 * d.width + X.i0], c = d.texels[Y.i0 * d.width + X.i1], e = d.texels[Y.i1 * d.width + X.i0], f = d.texels[Y.i1 * d.width + X.i1];
+    if (!(flags & SAILOR_TEXTURE_SRGB)) return bilinear_repeat_rgba8(texels, width, height, u, v);
+    const RepeatTap X = repeat_tap(width, u), Y = repeat_tap(height, v);
+    const uint32_t a = texels[Y.i0 * width + X.i0], c = texels[Y.i0 * width + X.i1], e = texels[Y.i1 * width + X.i0], f = texels[Y.i1 * width + X.i1];
     float4 r;
     r.x = lerp2(srgb[a & 255u], srgb[c & 255u], srgb[e & 255u], srgb[f & 255u], X.a, Y.a);
     r.y = lerp2(srgb[(a >> 8) & 255u], srgb[(c >> 8) & 255u], srgb[(e >> 8) & 255u], srgb[(f >> 8) & 255u], X.a, Y.a);
     r.z = lerp2(srgb[(a >> 16) & 255u], srgb[(c >> 16) & 255u], srgb[(e >> 16) & 255u], srgb[(f >> 16) & 255u], X.a, Y.a);
     r.w = lerp2(unorm8(a >> 24), unorm8(c >> 24), unorm8(e >> 24), unorm8(f >> 24), X.a, Y.a);
     return r;
+}
+
+// texture(textureSamplers[index], uv): base level, bilinear, Repeat (the implicit level of detail: surface_lod.h)
+__device__ __forceinline__ float4 surf_texture(const SailorTextureDesc* __restrict__ textures, uint32_t numTextures, uint32_t index, const float* __restrict__ srgb,
+                                               float u, float v)
+{
+    const SailorTextureDesc d = textures[index < numTextures ? index : 0u];
+    if (!d.texels || d.width <= 0 || d.height <= 0) return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    return surf_texels_fetch(d.texels, d.width, d.height, d.flags, srgb, u, v);
 }
 
 // the alpha of texture(textureSamplers[index], uv) alone: surf_texture's .w (alpha is never sRGB-decoded, so both of its branches compute exactly this)
@@ -206,6 +213,39 @@ __device__ __forceinline__ float surf_varying(const float* __restrict__ v, const
     const int col = (c - 9) / 3, r = (c - 9) % 3;
     const float* __restrict__ a = v + (col == 0 ? 8 : (col == 1 ? 11 : 5));
     return (m[r] * a[0] + m[4 + r] * a[1]) + m[8 + r] * a[2];
+}
+
+// the matrix under the tangent basis, three columns of three: mat3(model) (Standard.shader:138) or transpose(inverse(mat3(model))) in glm's form
+// (Standard_glTF.shader:136; the header's rule 4), one rounding per written operation
+__device__ __forceinline__ void surf_basis_matrix(const float* __restrict__ m, bool gltf, float n[9])
+{
+    const float m00 = m[0], m01 = m[1], m02 = m[2], m10 = m[4], m11 = m[5], m12 = m[6], m20 = m[8], m21 = m[9], m22 = m[10];
+    if (!gltf) {
+        n[0] = m00; n[1] = m01; n[2] = m02; n[3] = m10; n[4] = m11; n[5] = m12; n[6] = m20; n[7] = m21; n[8] = m22;
+        return;
+    }
+    const float c00 = m11 * m22 - m21 * m12, c01 = m01 * m22 - m21 * m02, c02 = m01 * m12 - m11 * m02;
+    const float det = (m00 * c00 - m10 * c01) + m20 * c02;
+    const float oneOverDet = 1.0f / det;
+    // N[c][r] = I[r][c]: column c of N is row c of the inverse
+    n[0] = c00 * oneOverDet;                        // I00
+    n[1] = -(m10 * m22 - m20 * m12) * oneOverDet;   // I10
+    n[2] = (m10 * m21 - m20 * m11) * oneOverDet;    // I20
+    n[3] = -c01 * oneOverDet;                       // I01
+    n[4] = (m00 * m22 - m20 * m02) * oneOverDet;    // I11
+    n[5] = -(m00 * m21 - m20 * m01) * oneOverDet;   // I21
+    n[6] = c02 * oneOverDet;                        // I02
+    n[7] = -(m00 * m12 - m10 * m02) * oneOverDet;   // I12
+    n[8] = (m00 * m11 - m10 * m01) * oneOverDet;    // I22
+}
+
+// surf_varying with the tangent basis (c = 9..17) under the matrix n of surf_basis_matrix
+__device__ __forceinline__ float surf_varying_basis(const float* __restrict__ v, const float* __restrict__ m, const float n[9], int c)
+{
+    if (c < 9) return surf_varying(v, m, c);
+    const int col = (c - 9) / 3, r = (c - 9) % 3;
+    const float* __restrict__ a = v + (col == 0 ? 8 : (col == 1 ? 11 : 5));
+    return (n[r] * a[0] + n[3 + r] * a[1]) + n[6 + r] * a[2];
 }
 
 // ---- what every entry point checks ------------------------------------------------------------------------------------------------------------------

@@ -20,39 +20,6 @@ __global__ __launch_bounds__(256) void k_surface_visibility_gltf(Mat4 P, Mat4 V,
     surf_visibility_masked<true>(P, V, draw, instances, materials, numMaterials, textures, numTextures, drawIndex, W, H, rowBegin, rows, workspace);
 }
 
-// the matrix under the tangent basis, three columns of three: mat3(model) (Standard.shader:138) or transpose(inverse(mat3(model))) in glm's form
-// (Standard_glTF.shader:136; the header's rule 4), one rounding per written operation
-__device__ __forceinline__ void surf_basis_matrix(const float* __restrict__ m, bool gltf, float n[9])
-{
-    const float m00 = m[0], m01 = m[1], m02 = m[2], m10 = m[4], m11 = m[5], m12 = m[6], m20 = m[8], m21 = m[9], m22 = m[10];
-    if (!gltf) {
-        n[0] = m00; n[1] = m01; n[2] = m02; n[3] = m10; n[4] = m11; n[5] = m12; n[6] = m20; n[7] = m21; n[8] = m22;
-        return;
-    }
-    const float c00 = m11 * m22 - m21 * m12, c01 = m01 * m22 - m21 * m02, c02 = m01 * m12 - m11 * m02;
-    const float det = (m00 * c00 - m10 * c01) + m20 * c02;
-    const float oneOverDet = 1.0f / det;
-    // N[c][r] = I[r][c]: column c of N is row c of the inverse
-    n[0] = c00 * oneOverDet;                        // I00
-    n[1] = -(m10 * m22 - m20 * m12) * oneOverDet;   // I10
-    n[2] = (m10 * m21 - m20 * m11) * oneOverDet;    // I20
-    n[3] = -c01 * oneOverDet;                       // I01
-    n[4] = (m00 * m22 - m20 * m02) * oneOverDet;    // I11
-    n[5] = -(m00 * m21 - m20 * m01) * oneOverDet;   // I21
-    n[6] = c02 * oneOverDet;                        // I02
-    n[7] = -(m00 * m12 - m10 * m02) * oneOverDet;   // I12
-    n[8] = (m00 * m11 - m10 * m01) * oneOverDet;    // I22
-}
-
-// surf_varying with the tangent basis (c = 9..17) under the matrix n of surf_basis_matrix
-__device__ __forceinline__ float surf_varying_basis(const float* __restrict__ v, const float* __restrict__ m, const float n[9], int c)
-{
-    if (c < 9) return surf_varying(v, m, c);
-    const int col = (c - 9) / 3, r = (c - 9) % 3;
-    const float* __restrict__ a = v + (col == 0 ? 8 : (col == 1 ? 11 : 5));
-    return (n[r] * a[0] + n[3 + r] * a[1]) + n[6 + r] * a[2];
-}
-
 __global__ __launch_bounds__(256) void k_surface_resolve_gltf(Mat4 P, Mat4 V, const float* __restrict__ instances, const SailorMaterialData* __restrict__ materials,
                                                               uint32_t numMaterials, const SailorTextureDesc* __restrict__ textures, uint32_t numTextures, int W, int H,
                                                               int rowBegin, int rows, uint32_t maxDraws, const void* __restrict__ workspace, float4* __restrict__ surface,

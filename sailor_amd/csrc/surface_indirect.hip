@@ -13,19 +13,6 @@
 // id = d * numTriangles + triangle does not depend on the count.  A block whose first lane is beyond the count leaves right after the load.
 #include "surface_masked_body.h"
 
-// rule 3: n = min(instanceCount, capacity, numInstanceRecords - firstInstance), 0 when firstInstance >= numInstanceRecords
-__device__ __forceinline__ bool surf_indirect_command(SailorSurfaceDraw& draw, const uint32_t* __restrict__ command, uint32_t numInstanceRecords)
-{
-    const uint32_t count = command[1], first = command[4]; // SailorDrawIndexedIndirectData.instanceCount, .firstInstance: uniform addresses, plain loads
-    const uint32_t room = first < numInstanceRecords ? numInstanceRecords - first : 0u;
-    uint32_t n = count < draw.numDrawn ? count : draw.numDrawn; // (numDrawn arrives as the capacity)
-    n = n < room ? n : room;
-    draw.numDrawn = n;
-    draw.firstInstance = first;
-    // block 0 stays for the descriptor, whatever the count
-    return blockIdx.x == 0 || (unsigned long long)blockIdx.x * 256ull < (unsigned long long)n * draw.numTriangles;
-}
-
 __global__ __launch_bounds__(256) void k_surface_visibility_indirect(Mat4 P, Mat4 V, SailorSurfaceDraw draw, const uint32_t* __restrict__ command,
                                                                      uint32_t numInstanceRecords, const float* __restrict__ instances,
                                                                      const SailorMaterialData* __restrict__ materials, uint32_t numMaterials,

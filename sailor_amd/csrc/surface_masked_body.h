@@ -1,8 +1,12 @@
 // The draw kernel of the Masked queue as a body two translation units instantiate: surface_masked.hip (Standard.shader's ALPHA_CUTOUT: albedo[3] through
 // albedoSampler against the constant 0.5) and surface_gltf.hip (Standard_glTF.shader's: baseColorFactor[3] through baseColorSampler against the material's
 // alphaCutoff).  GLTF is a template argument, so each kernel holds its own record's offsets and, for Standard, no threshold word at all.
+// LOD (default false: the kernels as they were) makes the alpha fetch the implicit-level-of-detail one of surface_lod.h: the lane also carries the level
+// count of the albedo descriptor and the six steps of the edge functions to the next pixel, so a fragment can evaluate uv at its quad's other centres.
 #pragma once
+#include <type_traits>
 #include "surface_fill.h"
+#include "surface_lod.h"
 
 // what the alpha of a fragment needs of its triangle, prepared once by the owning lane: the three clip w, (u, v, colour alpha) of the three set-up
 // vertices -- the cut lerp aI + (aO - aI) t applied, in the order the winding swap left (SurfSrc's) --, the material's albedo[3] and the resolved albedo
@@ -10,12 +14,16 @@
 // in a vector register on purpose: as a wave-uniform flag it would hold a pair of scalar registers as a mask through all the loops, and the scalar file is full.
 // cutoff: the material's alphaCutoff, read and carried by the glTF kernel only.
 struct SurfAlpha { float w[3], u[3], v[3], c[3]; float albedoA; const uint32_t* texels; int width, height; float cutoff; };
+// LOD: dx[k], dy[k] = what edge function k gains one pixel to the right / one row down (exact: the neighbour's edge functions are affine steps of the
+// pixel's own); levels = the descriptor's level count n (1: today's fetch, no derivative)
+struct SurfAlphaLod : SurfAlpha { long long dx[3], dy[3]; int levels; };
+template <bool LOD> using SurfAlphaOf = std::conditional_t<LOD, SurfAlphaLod, SurfAlpha>;
 
 // the part of SurfAlpha that belongs to the instance, not to the triangle's part: read once per lane BEFORE the loop over the parts, so that the two tables and
 // their lengths are dead (and their scalar registers free) while the triangles are filled.  The table is one array of 80-byte slots; GLTF decides which record
 // a slot is read as.
-template <bool GLTF>
-__device__ __forceinline__ void surf_alpha_material(SurfAlpha& A, const float* __restrict__ model, const SailorMaterialData* __restrict__ materials, uint32_t numMaterials,
+template <bool GLTF, bool LOD = false>
+__device__ __forceinline__ void surf_alpha_material(SurfAlphaOf<LOD>& A, const float* __restrict__ model, const SailorMaterialData* __restrict__ materials, uint32_t numMaterials,
                                                     const SailorTextureDesc* __restrict__ textures, uint32_t numTextures)
 {
     const uint32_t mi = reinterpret_cast<const uint32_t*>(model)[20]; // PerInstanceData.materialInstance, flat
@@ -33,6 +41,14 @@ __device__ __forceinline__ void surf_alpha_material(SurfAlpha& A, const float* _
     const SailorTextureDesc d = textures[index < numTextures ? index : 0u];
     const bool texels = d.texels && d.width > 0 && d.height > 0;
     A.texels = texels ? d.texels : nullptr; A.width = texels ? d.width : 0; A.height = texels ? d.height : 0;
+    if constexpr (LOD) A.levels = texels ? surf_level_count(d.width, d.height, d.levels) : 1;
+}
+
+// the steps of the three edge functions of a set-up triangle (surf_fill's dx, dy)
+__device__ __forceinline__ void surf_alpha_steps(SurfAlphaLod& A, const SurfTri& t)
+{
+    A.dx[0] = -256ll * (t.y2 - t.y1); A.dx[1] = -256ll * (t.y0 - t.y2); A.dx[2] = -256ll * (t.y1 - t.y0);
+    A.dy[0] = 256ll * (t.x2 - t.x1); A.dy[1] = 256ll * (t.x0 - t.x2); A.dy[2] = 256ll * (t.x1 - t.x0);
 }
 
 __device__ __forceinline__ void surf_alpha_vertices(SurfAlpha& A, const SurfSrc& S, const float* __restrict__ vertices)
@@ -49,10 +65,10 @@ __device__ __forceinline__ void surf_alpha_vertices(SurfAlpha& A, const SurfSrc&
     }
 }
 
-template <bool GLTF>
-__device__ __forceinline__ SurfAlpha surf_alpha_bcast(const SurfAlpha& a, int src)
+template <bool GLTF, bool LOD = false>
+__device__ __forceinline__ SurfAlphaOf<LOD> surf_alpha_bcast(const SurfAlphaOf<LOD>& a, int src)
 {
-    SurfAlpha b;
+    SurfAlphaOf<LOD> b;
 #pragma unroll
     for (int k = 0; k < 3; k++) { b.w[k] = __shfl(a.w[k], src, 64); b.u[k] = __shfl(a.u[k], src, 64); b.v[k] = __shfl(a.v[k], src, 64); b.c[k] = __shfl(a.c[k], src, 64); }
     b.albedoA = __shfl(a.albedoA, src, 64);
@@ -66,14 +82,24 @@ __device__ __forceinline__ SurfAlpha surf_alpha_bcast(const SurfAlpha& a, int sr
     for (int k = 0; k < 3; k++) { SURF_KEEP_VECTOR(b.w[k]); SURF_KEEP_VECTOR(b.u[k]); SURF_KEEP_VECTOR(b.v[k]); SURF_KEEP_VECTOR(b.c[k]); }
     SURF_KEEP_VECTOR(b.albedoA); SURF_KEEP_VECTOR(b.texels); SURF_KEEP_VECTOR(b.width); SURF_KEEP_VECTOR(b.height);
     if constexpr (GLTF) SURF_KEEP_VECTOR(b.cutoff);
+    if constexpr (LOD) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            b.dx[k] = surf_bcast64(a.dx[k], src); b.dy[k] = surf_bcast64(a.dy[k], src);
+            SURF_KEEP_VECTOR(b.dx[k]); SURF_KEEP_VECTOR(b.dy[k]);
+        }
+        b.levels = __shfl(a.levels, src, 64);
+        SURF_KEEP_VECTOR(b.levels);
+    }
     return b;
 }
 
 // Standard.shader:383 + :403-408 at the pixel whose edge functions are e0, e1, e2: alpha = (mat.albedo[3] * tA.w) * a[8] in k_surface_resolve's operation
 // order (the barycentrics and the three varyings by the header's formula), kept unless alpha < 0.5f -- a NaN alpha survives, as in GLSL.
 // Standard_glTF.shader:389 + :410-415: the same alpha from baseColorFactor[3], kept unless alpha < alphaCutoff (a NaN on either side survives).
-template <bool GLTF>
-__device__ __forceinline__ bool surf_alpha_keeps(const SurfAlpha& A, long long e0, long long e1, long long e2, float area)
+// LOD: tA.w is the implicit-level-of-detail fetch; (i, j) is the fragment's pixel, whose parity says where its quad's other centres lie.
+template <bool GLTF, bool LOD = false>
+__device__ __forceinline__ bool surf_alpha_keeps(const SurfAlphaOf<LOD>& A, int i, int j, long long e0, long long e1, long long e2, float area)
 {
     if (A.height < 0) return true;
     const float l0 = (float)e0 / area, l1 = (float)e1 / area, l2 = (float)e2 / area;
@@ -83,25 +109,35 @@ __device__ __forceinline__ bool surf_alpha_keeps(const SurfAlpha& A, long long e
     const float u = (A.u[0] * b0 + A.u[1] * b1) + A.u[2] * b2;
     const float v = (A.v[0] * b0 + A.v[1] * b1) + A.v[2] * b2;
     const float c = (A.c[0] * b0 + A.c[1] * b1) + A.c[2] * b2;
-    const float alpha = (A.albedoA * surf_texture_alpha(A.texels, A.width, A.height, u, v)) * c;
+    float tA;
+    if constexpr (LOD) {
+        if (A.levels > 1) {
+            float ux, vx, uy, vy;
+            const bool left = (i & 1) != 0, up = (j & 1) != 0; // the row mate is to the left of an odd column, the column mate above an odd row
+            surf_uv_at(A.u, A.v, A.w, e0 + (left ? -A.dx[0] : A.dx[0]), e1 + (left ? -A.dx[1] : A.dx[1]), e2 + (left ? -A.dx[2] : A.dx[2]), area, ux, vx);
+            surf_uv_at(A.u, A.v, A.w, e0 + (up ? -A.dy[0] : A.dy[0]), e1 + (up ? -A.dy[1] : A.dy[1]), e2 + (up ? -A.dy[2] : A.dy[2]), area, uy, vy);
+            tA = surf_texture_alpha_lod(A.texels, A.width, A.height, A.levels, u, v, surf_derivs(i, j, u, v, ux, vx, uy, vy));
+        } else tA = surf_texture_alpha(A.texels, A.width, A.height, u, v);
+    } else tA = surf_texture_alpha(A.texels, A.width, A.height, u, v);
+    const float alpha = (A.albedoA * tA) * c;
     if constexpr (GLTF) return !(alpha < A.cutoff);
     else return !(alpha < 0.5f);
 }
 
 // surf_fragment with the discard between the plain load and the atomic: only a fragment whose key would win evaluates alpha, only a survivor issues the
 // atomicMax.  (A stale load can only be smaller than what is stored: a fragment that would lose anyway may evaluate alpha in vain, never the reverse.)
-template <bool GLTF>
-__device__ __forceinline__ void surf_fragment_masked(unsigned long long* p, float z, unsigned int orderPlus1, const SurfAlpha& A, long long e0, long long e1,
-                                                     long long e2, float area)
+template <bool GLTF, bool LOD = false>
+__device__ __forceinline__ void surf_fragment_masked(unsigned long long* p, int i, int j, float z, unsigned int orderPlus1, const SurfAlphaOf<LOD>& A, long long e0,
+                                                     long long e1, long long e2, float area)
 {
     const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | orderPlus1;
     if (key > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-        if (surf_alpha_keeps<GLTF>(A, e0, e1, e2, area)) atomicMax(p, key);
+        if (surf_alpha_keeps<GLTF, LOD>(A, i, j, e0, e1, e2, area)) atomicMax(p, key);
     }
 }
 
 // the slices (gridDim.y) are k_surface_visibility's; without SAILOR_SURFACE_ALPHA_CUTOUT in draw.flags the keys are k_surface_visibility's
-template <bool GLTF>
+template <bool GLTF, bool LOD = false>
 __device__ __forceinline__ void surf_visibility_masked(const Mat4& P, const Mat4& V, const SailorSurfaceDraw& draw, const float* __restrict__ instances,
                                                        const SailorMaterialData* __restrict__ materials, uint32_t numMaterials,
                                                        const SailorTextureDesc* __restrict__ textures, uint32_t numTextures, uint32_t drawIndex, int W, int H,
@@ -122,10 +158,10 @@ __device__ __forceinline__ void surf_visibility_masked(const Mat4& P, const Mat4
         d = (uint32_t)(id / draw.numTriangles); tri = (uint32_t)(id - (unsigned long long)d * draw.numTriangles);
         inst = draw.dInstanceIds ? draw.dInstanceIds[d] : draw.firstInstance + d;
     }
-    SurfAlpha A;
+    SurfAlphaOf<LOD> A;
     memset(&A, 0, sizeof A);
     A.height = -1;
-    if (have && (draw.flags & SAILOR_SURFACE_ALPHA_CUTOUT)) surf_alpha_material<GLTF>( // (the entry point has checked that materials and textures are there)
+    if (have && (draw.flags & SAILOR_SURFACE_ALPHA_CUTOUT)) surf_alpha_material<GLTF, LOD>( // (the entry point has checked that materials and textures are there)
         A, instances + SURF_INSTANCE_FLOATS * (size_t)inst, materials, numMaterials, textures, numTextures);
     bool again = false;
     for (int part = 0; part < 2; part++) {
@@ -141,14 +177,31 @@ __device__ __forceinline__ void surf_visibility_masked(const Mat4& P, const Mat4
             int Wl = W, rowB = rowBegin, rowE = rowBegin + rows, fl = (int)draw.flags;
             asm volatile("" : "+s"(Wl), "+s"(rowB), "+s"(rowE), "+s"(fl));
             t = surface_setup(P, V, model, vertices, draw.dIndices + 3 * (size_t)tri, Wl, H, rowB, rowE, (fl & (int)SAILOR_SURFACE_CULL_BACK) != 0, part, second, S);
-            if (A.height >= 0 && t.valid) surf_alpha_vertices(A, S, vertices);
+            if (A.height >= 0 && t.valid) {
+                surf_alpha_vertices(A, S, vertices);
+                if constexpr (LOD) surf_alpha_steps(A, t);
+            }
         }
         const unsigned int orderPlus1 = draw.primBase + (unsigned int)(2ull * id) + (unsigned int)part + 1u; // (the entry point has checked the range)
         // the fill: the alpha words are the payload, carried to the wave once per large triangle
-        surf_fill(t, orderPlus1, A, [](const SurfAlpha& a, int src) { return surf_alpha_bcast<GLTF>(a, src); }, slice, slices, lane,
-                  [&](int i, int j, float z, unsigned int tag, const SurfAlpha& a, long long e0, long long e1, long long e2, float area) {
-                      surf_fragment_masked<GLTF>(keys + (size_t)(j - rowBegin) * W + i, z, tag, a, e0, e1, e2, area);
+        surf_fill(t, orderPlus1, A, [](const SurfAlphaOf<LOD>& a, int src) { return surf_alpha_bcast<GLTF, LOD>(a, src); }, slice, slices, lane,
+                  [&](int i, int j, float z, unsigned int tag, const SurfAlphaOf<LOD>& a, long long e0, long long e1, long long e2, float area) {
+                      surf_fragment_masked<GLTF, LOD>(keys + (size_t)(j - rowBegin) * W + i, i, j, z, tag, a, e0, e1, e2, area);
                   });
         if (part == 0) again = second;
     }
+}
+
+// the command of an indirect draw, read where the draw runs (surface_indirect.hip, surface_lod.hip).  Rule 3 of the indirect section:
+// n = min(instanceCount, capacity, numInstanceRecords - firstInstance), 0 when firstInstance >= numInstanceRecords
+__device__ __forceinline__ bool surf_indirect_command(SailorSurfaceDraw& draw, const uint32_t* __restrict__ command, uint32_t numInstanceRecords)
+{
+    const uint32_t count = command[1], first = command[4]; // SailorDrawIndexedIndirectData.instanceCount, .firstInstance: uniform addresses, plain loads
+    const uint32_t room = first < numInstanceRecords ? numInstanceRecords - first : 0u;
+    uint32_t n = count < draw.numDrawn ? count : draw.numDrawn; // (numDrawn arrives as the capacity)
+    n = n < room ? n : room;
+    draw.numDrawn = n;
+    draw.firstInstance = first;
+    // block 0 stays for the descriptor, whatever the count
+    return blockIdx.x == 0 || (unsigned long long)blockIdx.x * 256ull < (unsigned long long)n * draw.numTriangles;
 }

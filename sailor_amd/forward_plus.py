@@ -985,17 +985,26 @@ def blit_linear(ctx: HipContext, src: torch.Tensor, dst: torch.Tensor) -> torch.
     return dst
 
 
-def upload_textures(ctx: HipContext, images, srgb) -> tuple[torch.Tensor, int, list]:
+def upload_textures(ctx: HipContext, images, srgb, mips: bool = False) -> tuple[torch.Tensor, int, list]:
     """Standard.shader:124 textureSamplers[]: a list of uint8 [H, W, 4] arrays (r first) and their sRGB flags -> (device table of SailorTextureDesc, its
-    length, the tensors that must stay alive)"""
+    length, the tensors that must stay alive).  mips: allocate the full chain behind every image, upload level 0, record sailor_hip_texture_generate_mips and
+    set the descriptor's `levels` (what the `_lod` entry points read); without it the descriptors hold one level, as before."""
     assert len(images) == len(srgb) and len(images) > 0
     keep, table = [], (_lib.TextureDesc * len(images))()
     for k, (img, s) in enumerate(zip(images, srgb)):
         img = np.ascontiguousarray(img, np.uint8)
         assert img.ndim == 3 and img.shape[2] == 4 and img.shape[0] > 0 and img.shape[1] > 0, img.shape
-        t = torch.from_numpy(img.view(np.uint32).reshape(img.shape[0], img.shape[1]).view(np.int32)).to(ctx.device)
+        h, w = img.shape[:2]
+        flags, levels = _lib.TEXTURE_SRGB if s else 0, 0
+        t = torch.from_numpy(img.view(np.uint32).reshape(h, w).view(np.int32)).to(ctx.device)
+        if mips:
+            levels = host.texture_mip_levels(w, h)
+            chain = torch.zeros(host.mip_chain_texels(w, h, levels), dtype=torch.int32, device=ctx.device)
+            chain[: h * w] = t.reshape(-1)
+            t = chain
+            _lib.check(ctx._lib.sailor_hip_texture_generate_mips(ctx.handle, _ptr(t), w, h, levels, flags), "sailor_hip_texture_generate_mips", ctx.handle)
         keep.append(t)
-        table[k] = _lib.TextureDesc(t.data_ptr(), img.shape[1], img.shape[0], _lib.TEXTURE_SRGB if s else 0, 0)
+        table[k] = _lib.TextureDesc(t.data_ptr(), w, h, flags, levels)
     d = torch.from_numpy(np.frombuffer(bytes(table), np.uint8).copy()).to(ctx.device)
     keep.append(d)
     return d, len(images), keep
@@ -1024,8 +1033,9 @@ class SurfacePass:
 
     def draw(self, frame: UboFrameData, vertices: torch.Tensor, indices: torch.Tensor, instances: torch.Tensor, instance_ids: torch.Tensor | None = None,
              num_drawn: int | None = None, first_instance: int = 0, cull_back: bool = False, alpha_cutout: bool = False, materials: torch.Tensor | None = None,
-             textures: torch.Tensor | None = None, num_textures: int = 0, gltf: bool = False):
+             textures: torch.Tensor | None = None, num_textures: int = 0, gltf: bool = False, lod: bool = False):
         """vertices: 72-byte records; indices: int32, 3 per triangle; instances: the 96-byte PerInstanceData SSBO; instance_ids: int32 or None.
+        lod: through sailor_hip_surface_draw_lod -- the alpha behind ALPHA_CUTOUT is fetched at the implicit level of detail; such a pass ends with resolve_lod.
         alpha_cutout: the ALPHA_CUTOUT permutation (Standard.shader:403-408) through sailor_hip_surface_draw_masked, which needs the resolve's material and
         texture tables.  gltf: the draw's material is Standard_glTF.shader's (sailor_hip_surface_draw_gltf); such a pass ends with resolve_gltf / composite_gltf"""
         if num_drawn is None:
@@ -1033,7 +1043,12 @@ class SurfacePass:
         nt = indices.numel() // 3
         flags = (_lib.SURFACE_CULL_BACK if cull_back else 0) | (_lib.SURFACE_ALPHA_CUTOUT if alpha_cutout else 0) | (_lib.SURFACE_GLTF if gltf else 0)
         d = _lib.SurfaceDraw(_ptr(vertices), _ptr(indices), _ptr(instance_ids), nt, num_drawn, self.prim_base, flags, first_instance, 0)
-        if gltf:
+        if lod:
+            _lib.check(self.ctx._lib.sailor_hip_surface_draw_lod(self.ctx.handle, C.byref(frame), C.byref(d), _ptr(instances), _ptr(materials),
+                                                                 0 if materials is None else materials.numel() * materials.element_size() // 80, _ptr(textures),
+                                                                 num_textures, self.draw_index, self.W, self.H, C.byref(self.band), _ptr(self.workspace),
+                                                                 self.workspace.numel()), "sailor_hip_surface_draw_lod", self.ctx.handle)
+        elif gltf:
             _lib.check(self.ctx._lib.sailor_hip_surface_draw_gltf(self.ctx.handle, C.byref(frame), C.byref(d), _ptr(instances), _ptr(materials),
                                                                   0 if materials is None else materials.numel() * materials.element_size() // 80, _ptr(textures),
                                                                   num_textures, self.draw_index, self.W, self.H, C.byref(self.band), _ptr(self.workspace),
@@ -1051,8 +1066,8 @@ class SurfacePass:
 
     def draw_indirect(self, frame: UboFrameData, vertices: torch.Tensor, indices: torch.Tensor, instances: torch.Tensor, command: torch.Tensor, capacity: int,
                       command_index: int = 0, num_instance_records: int | None = None, cull_back: bool = False, alpha_cutout: bool = False,
-                      materials: torch.Tensor | None = None, textures: torch.Tensor | None = None, num_textures: int = 0, gltf: bool = False):
-        """One command of DrawIndexedIndirect (sailor_hip_surface_draw_indirect).  command: the device buffer of 20-byte DrawIndexedIndirectData, e.g.
+                      materials: torch.Tensor | None = None, textures: torch.Tensor | None = None, num_textures: int = 0, gltf: bool = False, lod: bool = False):
+        """One command of DrawIndexedIndirect (sailor_hip_surface_draw_indirect; lod: sailor_hip_surface_draw_indirect_lod, as in draw()).  command: the device buffer of 20-byte DrawIndexedIndirectData, e.g.
         MeshCull's `batches`; command_index: which of them.  capacity: the instanceCount the host wrote (the un-culled count); the kernel reads the count
         and firstInstance of the command when it runs, and the running primBase advances by the capacity.  num_instance_records: the records `instances`
         holds for the draw's guard (default: all of the tensor)."""
@@ -1061,11 +1076,11 @@ class SurfacePass:
         nt = indices.numel() // 3
         flags = (_lib.SURFACE_CULL_BACK if cull_back else 0) | (_lib.SURFACE_ALPHA_CUTOUT if alpha_cutout else 0) | (_lib.SURFACE_GLTF if gltf else 0)
         d = _lib.SurfaceDraw(_ptr(vertices), _ptr(indices), None, nt, capacity, self.prim_base, flags, 0, 0)
-        _lib.check(self.ctx._lib.sailor_hip_surface_draw_indirect(self.ctx.handle, C.byref(frame), C.byref(d), command.data_ptr() + 20 * command_index, _ptr(instances),
-                                                                  num_instance_records, _ptr(materials),
-                                                                  0 if materials is None else materials.numel() * materials.element_size() // 80, _ptr(textures),
-                                                                  num_textures, self.draw_index, self.W, self.H, C.byref(self.band), _ptr(self.workspace),
-                                                                  self.workspace.numel()), "sailor_hip_surface_draw_indirect", self.ctx.handle)
+        name = "sailor_hip_surface_draw_indirect_lod" if lod else "sailor_hip_surface_draw_indirect"
+        _lib.check(getattr(self.ctx._lib, name)(self.ctx.handle, C.byref(frame), C.byref(d), command.data_ptr() + 20 * command_index, _ptr(instances),
+                                                num_instance_records, _ptr(materials), 0 if materials is None else materials.numel() * materials.element_size() // 80,
+                                                _ptr(textures), num_textures, self.draw_index, self.W, self.H, C.byref(self.band), _ptr(self.workspace),
+                                                self.workspace.numel()), name, self.ctx.handle)
         self.prim_base += host.surface_draw_prims(nt, capacity)
         self.draw_index += 1
 
@@ -1098,8 +1113,15 @@ class SurfacePass:
                                                               self.H, C.byref(self.band)), "sailor_hip_surface_composite", self.ctx.handle)
         return target
 
+    def resolve_lod(self, frame: UboFrameData, instances: torch.Tensor, materials: torch.Tensor, textures: torch.Tensor, num_textures: int,
+                    ao_in: torch.Tensor | None = None, want_depth: bool = True, want_coverage: bool = True, want_ao: bool = True):
+        """resolve_gltf() with every fetch at its implicit level of detail (sailor_hip_surface_resolve_lod); a table of one-level descriptors gives
+        resolve_gltf()'s bits"""
+        return self.resolve_gltf(frame, instances, materials, textures, num_textures, ao_in, want_depth, want_coverage, want_ao, entry="sailor_hip_surface_resolve_lod")
+
     def resolve_gltf(self, frame: UboFrameData, instances: torch.Tensor, materials: torch.Tensor, textures: torch.Tensor, num_textures: int,
-                     ao_in: torch.Tensor | None = None, want_depth: bool = True, want_coverage: bool = True, want_ao: bool = True):
+                     ao_in: torch.Tensor | None = None, want_depth: bool = True, want_coverage: bool = True, want_ao: bool = True,
+                     entry: str = "sailor_hip_surface_resolve_gltf"):
         """resolve() for a pass that may hold glTF draws.  ao_in: g_AO over the band, float32 [rows, W], or None (1 everywhere).
         -> (surface, depth | None, coverage | None, ao_out float32 [rows, W] | None -- what the shade reads as its IBL desc's ao --, emissive float32 [rows, W, 4])"""
         dev = self.ctx.device
@@ -1109,11 +1131,10 @@ class SurfacePass:
         cov = torch.empty((self.rows, self.W), dtype=torch.uint8, device=dev) if want_coverage else None
         ao_out = torch.empty((self.rows, self.W), dtype=torch.float32, device=dev) if want_ao else None
         emissive = torch.empty((self.rows, self.W, 4), dtype=torch.float32, device=dev)
-        _lib.check(self.ctx._lib.sailor_hip_surface_resolve_gltf(self.ctx.handle, C.byref(frame), _ptr(instances), _ptr(materials),
-                                                                 materials.numel() * materials.element_size() // 80, _ptr(textures), num_textures, self.W, self.H,
-                                                                 C.byref(self.band), _ptr(self.workspace), self.workspace.numel(), _ptr(surface), self.rows * self.W,
-                                                                 _ptr(depth), _ptr(cov), _ptr(ao_in), _ptr(ao_out), _ptr(emissive)),
-                   "sailor_hip_surface_resolve_gltf", self.ctx.handle)
+        _lib.check(getattr(self.ctx._lib, entry)(self.ctx.handle, C.byref(frame), _ptr(instances), _ptr(materials),
+                                                 materials.numel() * materials.element_size() // 80, _ptr(textures), num_textures, self.W, self.H,
+                                                 C.byref(self.band), _ptr(self.workspace), self.workspace.numel(), _ptr(surface), self.rows * self.W,
+                                                 _ptr(depth), _ptr(cov), _ptr(ao_in), _ptr(ao_out), _ptr(emissive)), entry, self.ctx.handle)
         return surface, depth, cov, ao_out, emissive
 
     def composite_gltf(self, radiance: torch.Tensor, emissive: torch.Tensor, target: torch.Tensor) -> torch.Tensor:

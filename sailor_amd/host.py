@@ -471,6 +471,19 @@ def srgb_table() -> np.ndarray:
     return out
 
 
+def srgb_encode_table() -> np.ndarray:
+    """sailor_host_srgb_encode_table: the 255 rounding boundaries of the sRGB encode, out[k - 1] = the decode of (k - 0.5) / 255 (double, rounded once to fp32);
+    the byte of x is the number of entries <= x"""
+    out = np.zeros(255, np.float32)
+    _lib.check(_lib.load().sailor_host_srgb_encode_table(_fp(out)), "sailor_host_srgb_encode_table")
+    return out
+
+
+def texture_mip_levels(width: int, height: int) -> int:
+    """sailor_hip_texture_mip_levels: floor(log2(max(width, height))) + 1, 0 for an extent outside 1 .. 32768"""
+    return int(_lib.load().sailor_hip_texture_mip_levels(width, height))
+
+
 def surface_draw_prims(num_triangles: int, num_drawn: int) -> int:
     """sailor_hip_surface_draw_prims: what a draw adds to the surface pass's running primBase"""
     out = C.c_uint64()

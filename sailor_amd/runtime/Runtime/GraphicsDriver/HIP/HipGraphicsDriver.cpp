@@ -134,16 +134,19 @@ bool HipGraphicsDriver::EnableShader(const std::string& assetPath)
 
 static size_t texel_size(EFormat f)
 {
-    return f == EFormat::R8_UNORM ? 1 : (f == EFormat::R16_SFLOAT ? 2 : (f == EFormat::R32_SFLOAT || f == EFormat::R8G8B8A8_UNORM ? 4 : (f == EFormat::R32G32_SFLOAT ? 8 : 16)));
+    return f == EFormat::R8_UNORM ? 1 : (f == EFormat::R16_SFLOAT ? 2 : (f == EFormat::R32_SFLOAT || f == EFormat::R8G8B8A8_UNORM || f == EFormat::R8G8B8A8_SRGB ? 4 : (f == EFormat::R32G32_SFLOAT ? 8 : 16)));
 }
 
-RHITexturePtr HipGraphicsDriver::CreateTexture(const void* pData, size_t size, ivec2 extent, EFormat format)
+RHITexturePtr HipGraphicsDriver::CreateTexture(const void* pData, size_t size, ivec2 extent, EFormat format, uint32_t mipLevels)
 {
     auto t = RHITexturePtr::Make();
     t->m_extent = extent;
     t->m_format = format;
     const size_t bytes = (size_t)extent.x * extent.y * texel_size(format);
-    t->m_buffer = CreateBuffer(bytes);
+    // a mip chain (TextureImporter.cpp:247-295): level-major behind level 0, like a render target's; the levels are GenerateMipMaps' to fill
+    const uint32_t full = sailor_hip_texture_mip_levels(extent.x, extent.y);
+    t->m_mipLevels = mipLevels < 1 ? 1 : (mipLevels > full && full ? full : mipLevels);
+    t->m_buffer = CreateBuffer(t->m_mipLevels > 1 ? sailor_hip_mip_chain_texels(extent.x, extent.y, (int32_t)t->m_mipLevels) * texel_size(format) : bytes);
     if (!t->m_buffer) return RHITexturePtr();
     if (pData) sailor_hip_buffer_upload(m_ctx, t->m_buffer->m_hip.m_devicePtr, 0, pData, size < bytes ? size : bytes);
     return t;
@@ -587,11 +590,15 @@ bool HipGraphicsDriver::BlitImage(RHICommandListPtr cmd, RHITexturePtr src, RHIT
 }
 
 // VulkanGraphicsDriver.cpp:1642-1653 -> VulkanCommandBuffer::GenerateMipMaps: the linear 2:1 blit chain.  The path calls it on the raw
-// environment cube only (EnvironmentNode.cpp:137).
+// environment cube (EnvironmentNode.cpp:137); the TextureImporter calls it on every 2-D material texture it loads (TextureAssetInfo.h:34): an RGBA8 chain,
+// sRGB or UNORM, in place behind level 0.
 void HipGraphicsDriver::GenerateMipMaps(RHICommandListPtr cmd, RHITexturePtr target)
 {
     SailorHipContext* ctx = m_ctx;
     cmd->m_hip.m_commands.push_back([ctx, target]() {
+        if (target && target->m_buffer && !target->m_bCubemap && !target->m_parent && (target->m_format == EFormat::R8G8B8A8_UNORM || target->m_format == EFormat::R8G8B8A8_SRGB))
+            return sailor_hip_texture_generate_mips(ctx, (uint32_t*)target->m_buffer->m_hip.m_devicePtr, target->GetExtent().x, target->GetExtent().y, target->GetMipLevels(),
+                                                    target->m_format == EFormat::R8G8B8A8_SRGB ? SAILOR_TEXTURE_SRGB : 0u);
         if (!target || !target->m_bCubemap || target->m_format != EFormat::R32G32B32A32_SFLOAT) return (int)SAILOR_HIP_ERR_INVALID_ARGUMENT;
         return sailor_hip_generate_mipmaps_cube(ctx, (float*)target->m_buffer->m_hip.m_devicePtr, target->GetExtent().x, (int32_t)target->GetMipLevels());
     });
@@ -914,6 +921,7 @@ struct SurfaceTables {
     const SailorMaterialData* materials = nullptr; uint32_t numMaterials = 0;
     const SailorTextureDesc* textures = nullptr; uint32_t numTextures = 0;
     bool bound = false; // both tables are
+    bool lod = false;   // a texture of the table has more than one level (RHIBuffer::m_hipTextureLevels): the pass takes the `_lod` entry points
 };
 static SurfaceTables surface_tables(const TVector<RHIShaderBindingSetPtr>& bindings)
 {
@@ -922,6 +930,8 @@ static SurfaceTables surface_tables(const TVector<RHIShaderBindingSetPtr>& bindi
     if (materials) { t.materials = (const SailorMaterialData*)materials->m_hip.m_devicePtr; t.numMaterials = (uint32_t)(materials->m_size / sizeof(SailorMaterialData)); }
     if (textures) { t.textures = (const SailorTextureDesc*)textures->m_hip.m_devicePtr; t.numTextures = (uint32_t)(textures->m_size / sizeof(SailorTextureDesc)); }
     t.bound = materials && textures;
+    if (textures)
+        for (uint32_t levels : textures->m_hipTextureLevels) t.lod = t.lod || levels > 1;
     return t;
 }
 
@@ -988,12 +998,15 @@ int HipGraphicsDriver::RecordSurfaceDraw(const TVector<RHIShaderBindingSetPtr>& 
         d.firstInstance = firstInstance;
         const SailorPerInstanceData* dInstances = (const SailorPerInstanceData*)instances->m_hip.m_devicePtr;
         void* workspace = m_surfaceWorkspace->m_hip.m_devicePtr;
-        if (!(flags & (SAILOR_SURFACE_GLTF | SAILOR_SURFACE_ALPHA_CUTOUT)))
+        const SurfaceTables t = surface_tables(bindings);
+        if (!(flags & (SAILOR_SURFACE_GLTF | SAILOR_SURFACE_ALPHA_CUTOUT)) && !t.lod)
             return sailor_hip_surface_draw(m_ctx, &pass.frame, &d, dInstances, drawIndex, pass.W, pass.H, &pass.band, workspace, pass.bytes);
         // the ALPHA_CUTOUT permutation: `material` and `textureSamplers` of the bound sets decide the discard in the draw.  Standard_glTF.shader: the tables
         // are read by the draw only under ALPHA_CUTOUT, which requires them
-        const SurfaceTables t = surface_tables(bindings);
         if ((flags & SAILOR_SURFACE_ALPHA_CUTOUT) && !t.bound) return (int)SAILOR_HIP_ERR_INVALID_ARGUMENT;
+        if (t.lod) // mip-mapped textures: every draw of the pass through the entry that tests alpha at the implicit level of detail
+            return sailor_hip_surface_draw_lod(m_ctx, &pass.frame, &d, dInstances, t.materials, t.numMaterials, t.textures, t.numTextures, drawIndex, pass.W, pass.H, &pass.band,
+                                               workspace, pass.bytes);
         return (flags & SAILOR_SURFACE_GLTF ? sailor_hip_surface_draw_gltf : sailor_hip_surface_draw_masked)(
             m_ctx, &pass.frame, &d, dInstances, t.materials, t.numMaterials, t.textures, t.numTextures, drawIndex, pass.W, pass.H, &pass.band, workspace, pass.bytes);
     });
@@ -1081,6 +1094,7 @@ int HipGraphicsDriver::RecordSurfaceEnd(const TVector<RHIShaderBindingSetPtr>& b
     SailorUboFrameData frame;
     RHIBufferPtr instances = scene_buffer(bindings, "data");
     const SurfaceTables t = surface_tables(bindings);
+    gltf = gltf || t.lod; // mip-mapped textures: the resolve with the implicit level of detail serves both shaders and ends like the glTF one
     if (bindings.size() < 2 || !host_copy_of(bindings[0], "frameData", frame) || !color || !color->m_buffer || !instances || !t.bound)
         return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     const int W = color->GetExtent().x, H = color->GetExtent().y;
@@ -1099,7 +1113,8 @@ int HipGraphicsDriver::RecordSurfaceEnd(const TVector<RHIShaderBindingSetPtr>& b
         if (!m_surfaceAo || !m_surfaceEmissive) return SAILOR_HIP_ERR_OUT_OF_MEMORY;
         auto ao = bindings[1] ? bound_texture(bindings[1], "g_aoSampler") : RHITexturePtr();
         const float* aoIn = (ao && ao->m_extent.x == W && ao->m_extent.y == H) ? (const float*)ao->m_buffer->m_hip.m_devicePtr : nullptr;
-        st = sailor_hip_surface_resolve_gltf(m_ctx, &frame, (const SailorPerInstanceData*)instances->m_hip.m_devicePtr, t.materials, t.numMaterials, t.textures, t.numTextures,
+        st = (t.lod ? sailor_hip_surface_resolve_lod : sailor_hip_surface_resolve_gltf)(
+                                             m_ctx, &frame, (const SailorPerInstanceData*)instances->m_hip.m_devicePtr, t.materials, t.numMaterials, t.textures, t.numTextures,
                                              W, H, &band, m_surfaceWorkspace->m_hip.m_devicePtr, bytes, (float*)m_surfacePlanes->m_hip.m_devicePtr, pixels, nullptr, nullptr,
                                              aoIn, (float*)m_surfaceAo->m_hip.m_devicePtr, (float*)m_surfaceEmissive->m_hip.m_devicePtr);
     } else
@@ -1422,7 +1437,8 @@ int HipGraphicsDriver::RecordSurfaceDrawIndirect(const TVector<RHIShaderBindingS
         d.flags = flags;
         const SurfaceTables t = surface_tables(bindings);
         if ((flags & SAILOR_SURFACE_ALPHA_CUTOUT) && !t.bound) return (int)SAILOR_HIP_ERR_INVALID_ARGUMENT;
-        return sailor_hip_surface_draw_indirect(m_ctx, &pass.frame, &d, (const SailorDrawIndexedIndirectData*)((const uint8_t*)command->m_hip.m_devicePtr + commandOffset),
+        return (t.lod ? sailor_hip_surface_draw_indirect_lod : sailor_hip_surface_draw_indirect)(
+                                                m_ctx, &pass.frame, &d, (const SailorDrawIndexedIndirectData*)((const uint8_t*)command->m_hip.m_devicePtr + commandOffset),
                                                 (const SailorPerInstanceData*)instances->m_hip.m_devicePtr, (uint32_t)(instances->m_size / sizeof(SailorPerInstanceData)),
                                                 t.materials, t.numMaterials, t.textures, t.numTextures, drawIndex, pass.W, pass.H, &pass.band,
                                                 m_surfaceWorkspace->m_hip.m_devicePtr, pass.bytes);

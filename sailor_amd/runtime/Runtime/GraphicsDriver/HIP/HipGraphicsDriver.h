@@ -52,6 +52,11 @@
 //       sailor_hip_surface_draw_indirect per command: the host's copy of the command from the indirect buffer (CreateIndirectBuffer keeps the bytes of its last
 //       UpdateBuffer), instanceCount and firstInstance read on the device.  A pass WITHOUT a colour attachment begins from its depth attachment (or from cleared
 //       keys) and ends with sailor_hip_surface_store_depth alone.  Any other shader under DrawIndexedIndirect: SAILOR_HIP_ERR_UNSUPPORTED.
+//   all of these over a `textureSamplers` table of which the host knows a texture of more than one level (RHIBuffer::m_hipTextureLevels, RHITexture::GetMipLevels()
+//       per descriptor; sailor_rt_set_scene_texture_levels) -> sailor_hip_surface_draw_lod / sailor_hip_surface_draw_indirect_lod per draw, and the pass ends with
+//       sailor_hip_surface_resolve_lod -> the shade -> sailor_hip_surface_composite_gltf: every texture() at its implicit level of detail.  Without that knowledge
+//       the routes above, launch for launch.
+//   GenerateMipMaps of a 2-D R8G8B8A8_SRGB / R8G8B8A8_UNORM texture (CreateTexture with mipLevels > 1: the chain behind level 0) -> sailor_hip_texture_generate_mips
 //   "Shaders/Gizmo.shader" of a LineList material drawn with DrawIndexed (DebugContext::DrawDebugMesh inside DebugDrawNode's pass) -> sailor_hip_surface_begin from
 //       the pass' depth attachment, sailor_hip_debug_lines_draw, sailor_hip_debug_lines_resolve into the colour and the depth attachment (push constant viewProjection,
 //       VertexP3C4 vertices, 32-bit indices)
@@ -112,7 +117,7 @@ public:
     RHI::RHIBufferPtr CreateBuffer(size_t size) override;
     RHI::RHIBufferPtr CreateIndirectBuffer(size_t size) override;
     RHI::RHIShaderPtr CreateShader(const std::string& assetPath, const TVector<std::string>& defines = {}) override;
-    RHI::RHITexturePtr CreateTexture(const void* pData, size_t size, RHI::ivec2 extent, RHI::EFormat format) override;
+    RHI::RHITexturePtr CreateTexture(const void* pData, size_t size, RHI::ivec2 extent, RHI::EFormat format, uint32_t mipLevels = 1) override;
     RHI::RHITexturePtr CreateRenderTarget(RHI::ivec2 extent, uint32_t mipLevels, RHI::EFormat format) override;
     RHI::RHICubemapPtr CreateCubemap(RHI::ivec2 extent, uint32_t mipLevels, RHI::EFormat format) override;
     RHI::RHITexturePtr GetOrAddTemporaryRenderTarget(RHI::EFormat format, RHI::ivec2 extent) override;

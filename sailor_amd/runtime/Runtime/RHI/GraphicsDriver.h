@@ -15,7 +15,7 @@ public:
     virtual RHIBufferPtr CreateBuffer(size_t size) = 0;                                                    // :89
     virtual RHIBufferPtr CreateIndirectBuffer(size_t size) = 0;                                            // :91 (here: also keeps the bytes of its last UpdateBuffer on the host)
     virtual RHIShaderPtr CreateShader(const std::string& assetPath, const TVector<std::string>& defines = {}) = 0; // :97 (SPIR-V there; here the asset path + permutation)
-    virtual RHITexturePtr CreateTexture(const void* pData, size_t size, ivec2 extent, EFormat format) = 0; // :98-108
+    virtual RHITexturePtr CreateTexture(const void* pData, size_t size, ivec2 extent, EFormat format, uint32_t mipLevels = 1) = 0; // :98-108 (pData: level 0)
     virtual RHITexturePtr CreateRenderTarget(ivec2 extent, uint32_t mipLevels, EFormat format) = 0;        // :110-117 (filtration, clamping, usage dropped)
     virtual RHICubemapPtr CreateCubemap(ivec2 extent, uint32_t mipLevels, EFormat format) = 0;             // :137-143
     // :119-120 the pool of temporary render targets (ShadowPrepassNode.cpp:227, :285, :357, :360): a released target is handed out again to the next request
@@ -52,7 +52,7 @@ public:
     virtual void ClearDepthStencil(RHICommandListPtr cmd, RHITexturePtr dst, float depth, uint32_t stencil) = 0;  // :295 (the canonical fp32 plane has no stencil: the value is dropped)
     virtual bool BlitImage(RHICommandListPtr cmd, RHITexturePtr src, RHITexturePtr dst, ivec4 srcRegionRect, ivec4 dstRegionRect,
                            ETextureFiltration filtration = ETextureFiltration::Linear) = 0; // :293 (equal extents: a copy; scaled: one channel, Nearest)
-    virtual void GenerateMipMaps(RHICommandListPtr cmd, RHITexturePtr target) = 0;                                                                  // :296 (cubemaps)
+    virtual void GenerateMipMaps(RHICommandListPtr cmd, RHITexturePtr target) = 0;                                                                  // :296 (cubemaps; 2-D RGBA8 textures)
     virtual void ConvertEquirect2Cubemap(RHICommandListPtr cmd, RHITexturePtr equirect, RHICubemapPtr cubemap) = 0;                                 // :297
     virtual void UpdateShaderBinding(RHICommandListPtr cmd, RHIShaderBindingPtr binding, const void* data, size_t size, size_t variableOffset = 0) = 0; // :303
     virtual void SetMaterialParameter(RHICommandListPtr cmd, RHIShaderBindingSetPtr bindings, const std::string& binding, const std::string& variable,

@@ -71,6 +71,9 @@ public:
     // takes indexCount, firstIndex, vertexOffset and the un-culled instanceCount from them ("the command as the host wrote it", include/sailor_hip.h)
     bool m_bIndirect = false;
     TVector<uint8_t> m_hostCopy;
+    // a `textureSamplers` table: RHITexture::GetMipLevels() of every descriptor's texture, a host copy (empty: not known, every texture one level).  The
+    // surface pass takes the entry points with the implicit level of detail iff an entry exceeds 1.
+    TVector<uint32_t> m_hipTextureLevels;
     ~RHIBuffer() override;
     // The context the allocation belongs to, shared with the driver that made it: a buffer (or a texture / binding holding one) may outlive
     // the driver object, and the context is destroyed by whoever lets go of it last.
@@ -78,7 +81,7 @@ public:
 };
 using RHIBufferPtr = TRefPtr<RHIBuffer>;
 
-enum class EFormat { R32_SFLOAT, R16_SFLOAT, R32G32B32A32_SFLOAT, R32G32_SFLOAT, R8_UNORM, R8G8B8A8_UNORM }; // the 8-bit ones: SkyNode's weather map and noise volumes
+enum class EFormat { R32_SFLOAT, R16_SFLOAT, R32G32B32A32_SFLOAT, R32G32_SFLOAT, R8_UNORM, R8G8B8A8_UNORM, R8G8B8A8_SRGB }; // the 8-bit ones: SkyNode's weather map and noise volumes, material textures
 enum class EPrimitiveTopology { TriangleList, LineList }; // RHI/Types.h EPrimitiveTopology, the two the path draws with
 enum class EBlendMode { None, Additive, AlphaBlending, Multiply }; // RHI/Types.h EBlendMode; VulkanPipileneStates.cpp:236-254
 enum class ETextureFiltration { Nearest, Linear }; // RHI/Types.h ETextureFiltration (Bicubic has no user on the path)

@@ -435,6 +435,34 @@ RT_API int sailor_rt_set_scene(SailorRuntime* rt, void* vertices, uint32_t numVe
     return 0;
 }
 
+// RHITexture::GetMipLevels() of the textures behind the scene's `textureSamplers` table, one per descriptor, after sailor_rt_set_scene (which forgets them):
+// what the engine knows of its textures on the host.  The surface pass takes the entry points with the implicit level of detail iff an entry exceeds 1;
+// without this call the route is the one-level one.  -1, and nothing changed, unless n is the table's length.
+RT_API int sailor_rt_set_scene_texture_levels(SailorRuntime* rt, const uint32_t* levels, int n)
+{
+    if (!rt || n < 0 || (n > 0 && !levels) || !rt->snapshot.m_sceneBindings) return -1;
+    auto binding = rt->snapshot.m_sceneBindings->Find("textureSamplers");
+    if (!binding || !binding->m_buffer || binding->m_buffer->m_size != (size_t)n * sizeof(SailorTextureDesc)) return -1;
+    binding->m_buffer->m_hipTextureLevels.assign(levels, levels + n);
+    return 0;
+}
+
+// IGraphicsDriver::CreateTexture with a full chain + IGraphicsDriverCommands::GenerateMipMaps for one 2-D RGBA8 image, as the TextureImporter does for every
+// texture it loads: the whole chain (sailor_hip_mip_chain_texels(width, height, full) texels) back into `outChain`.  -1 on any refusal.
+RT_API int sailor_rt_generate_texture_mips(SailorRuntime* rt, const void* rgba8, int width, int height, int srgb, uint32_t* outChain, size_t outTexels)
+{
+    auto* hip = static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver());
+    const uint32_t full = sailor_hip_texture_mip_levels(width, height);
+    if (!rt || !rgba8 || !outChain || !full || outTexels != sailor_hip_mip_chain_texels(width, height, (int32_t)full)) return -1;
+    auto texture = hip->CreateTexture(rgba8, (size_t)width * height * 4, ivec2 { width, height }, srgb ? EFormat::R8G8B8A8_SRGB : EFormat::R8G8B8A8_UNORM, full);
+    if (!texture || texture->GetMipLevels() != full) return -1;
+    auto cmd = hip->CreateCommandList();
+    hip->GenerateMipMaps(cmd, texture);
+    hip->SubmitCommandList(cmd);
+    hip->WaitIdle();
+    return sailor_hip_buffer_download(hip->GetContext(), outChain, texture->m_buffer->m_hip.m_devicePtr, 0, outTexels * 4) == SAILOR_HIP_OK ? 0 : -1;
+}
+
 // The materials of the batches sailor_rt_set_scene set (call it afterwards; sailor_rt_set_scene itself leaves every batch untagged, without cutout, back faces
 // culled): `tags` is the batches' render queue tags in order, separated by commas, an empty field = untagged (scene_tags.h; NULL = all untagged); flags[i] is
 // SAILOR_RT_BATCH_ALPHA_CUTOUT | SAILOR_RT_BATCH_DOUBLE_SIDED of batch i.  -1, and nothing changed, unless numBatches is the scene's and both parse.

@@ -74,6 +74,8 @@ def load() -> C.CDLL:
         rt.sailor_rt_shadow_pass.argtypes = [P, C.POINTER(C.c_float), P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, C.c_uint32, P, C.c_int, C.c_int, C.c_float, C.c_float]
         rt.sailor_rt_gpu_culling.argtypes = [P, P, C.c_uint32, C.c_uint32, P, C.c_uint32]
         rt.sailor_rt_set_scene.argtypes = [P, P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, P, C.c_uint32, P, C.c_int]
+        rt.sailor_rt_set_scene_texture_levels.argtypes = [P, P, C.c_int]
+        rt.sailor_rt_generate_texture_mips.argtypes = [P, P, C.c_int, C.c_int, C.c_int, P, C.c_size_t]
         rt.sailor_rt_set_scene_targets.argtypes = [P, P, P, C.c_int, C.c_int]
         rt.sailor_rt_set_scene_tags.argtypes = [P, C.c_char_p, P, C.c_int]
         rt.sailor_rt_set_scene_shaders.argtypes = [P, P, C.c_int]
@@ -413,16 +415,29 @@ class Runtime:
     def set_surface(self, surface_tensor, radiance_tensor):
         self.rt.sailor_rt_set_surface(self.h, surface_tensor.data_ptr(), radiance_tensor.data_ptr(), surface_tensor.shape[2], surface_tensor.shape[1])
 
-    def set_scene(self, vertices, indices, instances, materials, textures, num_textures: int, batches):
+    def set_scene(self, vertices, indices, instances, materials, textures, num_textures: int, batches, texture_levels=None):
         """what RenderScene draws without a `surface` resource: device tensors of 72-byte vertices, int32 indices, 96-byte instances, 80-byte materials and
         the SailorTextureDesc table (any of the last three None = that binding missing), and batches uint32 [n, 5] = indexCount, instanceCount, firstIndex,
-        vertexOffset, firstInstance"""
+        vertexOffset, firstInstance.  texture_levels: RHITexture::GetMipLevels() of the table's textures, one int per descriptor (the host's knowledge of
+        them): with an entry above 1 the pass takes the entry points with the implicit level of detail; None: the one-level route"""
         nbytes = lambda t: t.numel() * t.element_size()
         b = np.ascontiguousarray(batches, np.uint32).reshape(-1, 5)
         ptr = lambda t: None if t is None else t.data_ptr()
         _lib.check(self.rt.sailor_rt_set_scene(self.h, ptr(vertices), nbytes(vertices) // 72, ptr(indices), indices.numel(), ptr(instances),
                                                0 if instances is None else nbytes(instances) // 96, ptr(materials), 0 if materials is None else nbytes(materials) // 80,
                                                ptr(textures), num_textures, b.ctypes.data, len(b)), "sailor_rt_set_scene")
+        if texture_levels is not None:
+            levels = np.ascontiguousarray(texture_levels, np.uint32)
+            _lib.check(self.rt.sailor_rt_set_scene_texture_levels(self.h, levels.ctypes.data if len(levels) else None, len(levels)), "sailor_rt_set_scene_texture_levels")
+
+    def generate_texture_mips(self, image, srgb: bool) -> np.ndarray:
+        """IGraphicsDriver::CreateTexture with a full chain + GenerateMipMaps for one uint8 [H, W, 4] image -> the whole chain as uint32 texels, level after level"""
+        from . import host
+        img = np.ascontiguousarray(image, np.uint8)
+        h, w = img.shape[:2]
+        out = np.zeros(host.mip_chain_texels(w, h, host.texture_mip_levels(w, h)), np.uint32)
+        _lib.check(self.rt.sailor_rt_generate_texture_mips(self.h, img.ctypes.data, w, h, 1 if srgb else 0, out.ctypes.data, out.size), "sailor_rt_generate_texture_mips")
+        return out
 
     def set_scene_tags(self, tags, flags):
         """the materials of set_scene's batches, after set_scene: tags = one render queue tag per batch ("Opaque", "Masked", "" = untagged: drawn by every
