@@ -1284,7 +1284,7 @@ typedef struct SailorSurfaceDraw {
     uint32_t numTriangles;
     uint32_t numDrawn;
     uint32_t primBase;                          /* the order of the draw's first primitive: the previous draw's primBase + its sailor_hip_surface_draw_prims */
-    uint32_t flags;                             /* SAILOR_SURFACE_CULL_BACK; SAILOR_SURFACE_ALPHA_CUTOUT through sailor_hip_surface_draw_masked, _draw_gltf and _draw_indirect only; SAILOR_SURFACE_GLTF (below) through _draw_gltf and _draw_indirect only */
+    uint32_t flags;                             /* SAILOR_SURFACE_CULL_BACK; SAILOR_SURFACE_ALPHA_CUTOUT through sailor_hip_surface_draw_masked, _draw_gltf and _draw_indirect only; SAILOR_SURFACE_GLTF (below) through _draw_gltf and _draw_indirect only; SAILOR_SURFACE_BLEND_* (the Transparent section) through _peel_draw and _peel_draw_gltf only */
     uint32_t firstInstance;
     uint32_t _pad;
 } SailorSurfaceDraw;
@@ -1336,8 +1336,8 @@ SAILOR_HIP_API int sailor_hip_surface_draw_prims(uint32_t numTriangles, uint32_t
  *  4. A discarded fragment does not exist: it writes no key and no depth and takes no part in ties.  Discard is a pure function of the fragment, so the
  *     keys stay order-free; the decision is taken in the draw, before the key is issued (exact inside test and z -> plain load of the pixel's key -> alpha
  *     only if the key would win -> atomicMax only for a survivor).  sailor_hip_surface_resolve, _composite and sailor_hip_surface_draw are unchanged.
- *  5. NOT reproduced: the Transparent queue, masked shadow casters (Standard_glTF.shader's alphaCutoff as a material field: sailor_hip_surface_draw_gltf,
- *     below; the threshold HERE is the constant 0.5).  (A Masked prepass is begin(opaque depth), the masked draws, sailor_hip_surface_store_depth: what the runtime
+ *  5. NOT reproduced: masked shadow casters.  (The Transparent queue has its own section, below; Standard_glTF.shader's alphaCutoff as a material field is
+ *     sailor_hip_surface_draw_gltf's, below: the threshold HERE is the constant 0.5.)  (A Masked prepass is begin(opaque depth), the masked draws, sailor_hip_surface_store_depth: what the runtime
  *     mirror's DepthPrepass node records through DrawIndexedIndirect.)
  * Both entry points record only; a refused call launches nothing and leaves its text in last_error. */
 
@@ -1385,7 +1385,7 @@ SAILOR_HIP_API int sailor_hip_surface_store_depth(SailorHipContext* ctx, const v
  *     bits; an uncovered pixel the same.  aoIn is 1.0f everywhere if dAoInOrNull is NULL.
  *  7. The composite adds the emissive term behind the shade: rgb = emissive.rgb + radiance.rgb, one fp32 add per channel.  The reference sums
  *     ((emissive + ao ambient) + L1) + ...; the shade has formed fma(ambient, ao, sum L) already, so this is ONE re-association, inside the shade's bound.
- * NOT reproduced: the Transparent queue (alphaMode BLEND), masked shadow casters.
+ * NOT reproduced: masked shadow casters.  (The Transparent queue, alphaMode BLEND: its own section, below.)
  * All entry points record only (no allocation, no synchronisation, capturable); a refused call launches nothing and leaves its text in last_error. */
 
 /* Standard_glTF.shader:42-58 MaterialData, std430: two vec4 (0, 16), five floats (32..48), five uints (52..68), padded to the vec4 alignment: 80 bytes */
@@ -1492,7 +1492,7 @@ SAILOR_HIP_API int sailor_hip_surface_draw_indirect(SailorHipContext* ctx, const
  *     issued; the neighbour centres' edge functions are affine steps of the fragment's own (exact).  At every pixel such a draw owns,
  *     sailor_hip_surface_resolve_lod's P0.w is, bit for bit, the alpha that was tested.  Without ALPHA_CUTOUT the keys are sailor_hip_surface_draw's.
  * NOT reproduced: anisotropy (maxAnisotropy = 8 is implementation-defined), textureLod and bias, the UI and particle textures, formats other than RGBA8, the
- * Transparent queue.
+ * Transparent queue at an implicit level of detail (its draws and resolves read level 0).
  * All device entry points record only (no allocation, no synchronisation, capturable); a refused call launches nothing and leaves its text in last_error. */
 
 /* floor(log2(max(width, height))) + 1 by integer operations; 0 for an extent outside 1 .. 32768 */
@@ -1522,6 +1522,74 @@ SAILOR_HIP_API int sailor_hip_surface_draw_indirect_lod(SailorHipContext* ctx, c
                                                         uint32_t numInstanceRecords, const SailorMaterialData* dMaterials, uint32_t numMaterials,
                                                         const SailorTextureDesc* dTextures, uint32_t numTextures, uint32_t drawIndex, int32_t width, int32_t height,
                                                         const SailorBand* band, void* dWorkspace, size_t workspaceBytes);
+
+/* ---- The Transparent render queue: ordered blended draws in the surface pass (surface_transparent.hip) -------------------------------------------
+ * Replaces: a RenderScene node with `Tag: Transparent` (FrameGraph/RenderSceneNode.cpp filters proxies by any tag).  ModelImporter.cpp:213-229 gives a glTF
+ * material with alphaMode == "BLEND" the render queue Transparent, depth test on and z-write OFF; MaterialImporter.cpp:329-357 lets a .mat file choose
+ * blendMode from None / Additive / AlphaBlending / Multiply; VulkanPipileneStates.cpp:236-254 holds the blend states.  A transparent pass is a list of
+ * draws, each of Standard or Standard_glTF, issued in the host's order against the depth attachment the prepass and the opaque passes left.
+ * Pinned:
+ *  1. A fragment exists iff it does in the Masked section (set-up, near-plane cut, snap, cull, top-left rule, fill) AND passes z >= depth[pixel], compared
+ *     as the uint32 images of two non-negative floats -- what the surface pass's depth test does against a key seeded by sailor_hip_surface_begin; equal
+ *     depth passes -- AND, under SAILOR_SURFACE_ALPHA_CUTOUT, survives the discard rule of its shader.  A discarded fragment occupies no layer.  The depth
+ *     attachment is READ ONLY: depth is never written.
+ *  2. The fragments of a pixel are blended in ascending primitive order, the orderPlus1 = primBase + 2 (instance * numTriangles + triangle) + part + 1 the
+ *     keys carry: within a draw instance, then triangle, then the part the near plane made; across draws the order they were issued in.  Depth plays no
+ *     part in the order.
+ *  3. The source colour of a fragment: src.rgb = what the shade kernels produce from the three planes sailor_hip_surface_resolve / _resolve_gltf give if
+ *     that fragment owns the pixel, plus -- when an emissive plane is passed -- emissive.rgb exactly as sailor_hip_surface_composite_gltf adds it
+ *     (emissive.k + radiance.k).  src.a = the resolve's P0.w bit for bit (outColor.a = material.albedo.a, Standard.shader:438).  The tile's light lists,
+ *     g_AO and the shadow maps are the opaque pass's: the reference culls lights against the prepass depth too, so a transparent fragment in front of it sees
+ *     that tile's list.  Reproduced, not fixed.
+ *  4. The blend, per draw, from SAILOR_SURFACE_BLEND_* in the draw's flags; one fp32 rounding per written operation, no contraction; the source products
+ *     first, then the destination's, then the add or the subtract:
+ *       NONE     : dst = src, all four channels (what ModelImporter gives a BLEND material: an overwrite without depth write)
+ *       ADDITIVE : dst = src + dst, all four channels
+ *       ALPHA    : dst.rgb = src.rgb * src.a + dst.rgb * (1 - src.a);  dst.a = src.a * src.a - dst.a * (1 - src.a)    (the alpha op is SUBTRACT)
+ *       MULTIPLY : SAILOR_HIP_ERR_UNSUPPORTED for scene draws (VK_BLEND_OP_MULTIPLY_EXT: the decision recorded for the sun shafts stands)
+ *     A fragment with src.a == 0 still blends; NaN and Inf pass through.
+ *  5. The target is the RGBA32F Main plane, as for every other pass; MSAA does not apply.
+ * Mechanism: the pass is peeled by primitive order.  Layer k holds, at each pixel, that pixel's k-th fragment in primitive order:
+ *   sailor_hip_surface_peel_begin (zero keys; `last` zeroed for layer 0 only) -> every draw through _peel_draw / _peel_draw_gltf (a fragment of rule 1 with
+ *   orderPlus1 > last[pixel] issues (0xFFFFFFFF - orderPlus1) << 32 | zbits by plain load and atomicMax: the maximum is the smallest order beyond the previous
+ *   layer, order-free) -> _peel_commit (a non-zero key becomes zbits << 32 | orderPlus1, last[pixel] = orderPlus1, the committed pixels are added to *dCount)
+ *   -> the workspace is an ordinary surface workspace: sailor_hip_surface_resolve / _resolve_gltf (dDepthOutOrNull = NULL) and the shade, unchanged ->
+ *   sailor_hip_surface_blend.  A pass of L layers is L such rounds and one more { begin, draws, commit } whose count is the OVERFLOW: the pixels that still
+ *   had a fragment left.  Every layer rasterises the pass again.  Indirect draws and the `_lod` fetch are not part of this section.
+ * All entry points record only (no allocation, no synchronisation, capturable); a refused call launches nothing and leaves its text in last_error. */
+#define SAILOR_SURFACE_BLEND_SHIFT 3u /* SailorSurfaceDraw.flags bits 3-4: the draw's EBlendMode; accepted by sailor_hip_surface_peel_draw / _peel_draw_gltf only */
+#define SAILOR_SURFACE_BLEND_MASK 3u
+#define SAILOR_SURFACE_BLEND_NONE 0u
+#define SAILOR_SURFACE_BLEND_ADDITIVE 1u
+#define SAILOR_SURFACE_BLEND_ALPHA 2u
+#define SAILOR_SURFACE_BLEND_MULTIPLY 3u /* refused: SAILOR_HIP_ERR_UNSUPPORTED */
+
+/* Begins one layer: sailor_hip_surface_begin without a depth (zero keys, empty descriptor slots, the sRGB table).
+ *   dLast     : device, the band's rows x width uint32: the orderPlus1 each pixel committed last (0: none)
+ *   startPass : non-zero zeroes dLast (layer 0 of a pass); 0 leaves it (every later layer and the overflow round) */
+SAILOR_HIP_API int sailor_hip_surface_peel_begin(SailorHipContext* ctx, int32_t width, int32_t height, const SailorBand* band, void* dWorkspace,
+                                                 size_t workspaceBytes, uint32_t* dLast, int32_t startPass);
+/* One DrawIndexed of a transparent pass: k_surface_peel.  The arguments, checks and refusals of sailor_hip_surface_draw_masked; flags may also hold a blend
+ * mode (MULTIPLY: SAILOR_HIP_ERR_UNSUPPORTED).  Every layer issues the same draws with the same drawIndex and primBase.
+ *   dDepth : device, the raw width x height depth attachment of the WHOLE frame (as sailor_hip_surface_store_depth takes it); read only
+ *   dLast  : as above; read only here */
+SAILOR_HIP_API int sailor_hip_surface_peel_draw(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSurfaceDraw* draw,
+                                                const SailorPerInstanceData* dInstances, const SailorMaterialData* dMaterials, uint32_t numMaterials,
+                                                const SailorTextureDesc* dTextures, uint32_t numTextures, uint32_t drawIndex, int32_t width, int32_t height,
+                                                const SailorBand* band, void* dWorkspace, size_t workspaceBytes, const float* dDepth, const uint32_t* dLast);
+/* The same for a Standard_glTF.shader material: k_surface_peel_gltf; flags must hold SAILOR_SURFACE_GLTF, as for sailor_hip_surface_draw_gltf. */
+SAILOR_HIP_API int sailor_hip_surface_peel_draw_gltf(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSurfaceDraw* draw,
+                                                     const SailorPerInstanceData* dInstances, const SailorMaterialData* dMaterials, uint32_t numMaterials,
+                                                     const SailorTextureDesc* dTextures, uint32_t numTextures, uint32_t drawIndex, int32_t width, int32_t height,
+                                                     const SailorBand* band, void* dWorkspace, size_t workspaceBytes, const float* dDepth, const uint32_t* dLast);
+/* Ends a layer's draws: k_surface_peel_commit.  *dCount (device, uint32) += the pixels of the band that committed a fragment; the caller zeroes it. */
+SAILOR_HIP_API int sailor_hip_surface_peel_commit(SailorHipContext* ctx, int32_t width, int32_t height, const SailorBand* band, void* dWorkspace,
+                                                  size_t workspaceBytes, uint32_t* dLast, uint32_t* dCount);
+/* Rule 4 at every pixel the committed layer owns: k_surface_blend.  dRadiance: the shade's output; dSurfaceP0: the first plane of the resolve's surface (its
+ * .w is src.a); dEmissiveOrNull: sailor_hip_surface_resolve_gltf's emissive plane, or NULL for a pass resolved by sailor_hip_surface_resolve; all float4 per
+ * pixel of the band, as dTarget.  A pixel without a fragment keeps the target's bits. */
+SAILOR_HIP_API int sailor_hip_surface_blend(SailorHipContext* ctx, const float* dRadiance, const float* dSurfaceP0, const float* dEmissiveOrNull,
+                                            const void* dWorkspace, size_t workspaceBytes, float* dTarget, int32_t width, int32_t height, const SailorBand* band);
 
 /* ---- DebugDraw: the line-list pass of the Gizmo material (debug_lines.hip) ---------------------------------------------------------------------
  * Replaces: the draw FrameGraph/DebugDrawNode.cpp:19-79 replays -- RHI/DebugContext.cpp:382-398 (DrawDebugMesh: one DrawIndexed over the line list that

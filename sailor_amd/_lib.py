@@ -251,6 +251,9 @@ TEXTURE_SRGB = 1        # SAILOR_TEXTURE_SRGB
 SURFACE_CULL_BACK = 1   # SAILOR_SURFACE_CULL_BACK
 SURFACE_ALPHA_CUTOUT = 2  # SAILOR_SURFACE_ALPHA_CUTOUT (sailor_hip_surface_draw_masked only)
 SURFACE_GLTF = 4        # SAILOR_SURFACE_GLTF (sailor_hip_surface_draw_gltf only)
+SURFACE_BLEND_SHIFT, SURFACE_BLEND_MASK = 3, 3   # SAILOR_SURFACE_BLEND_SHIFT / _MASK (sailor_hip_surface_peel_draw / _peel_draw_gltf only)
+SURFACE_BLEND_NONE, SURFACE_BLEND_ADDITIVE, SURFACE_BLEND_ALPHA, SURFACE_BLEND_MULTIPLY = 0, 1, 2, 3   # EBlendMode; MULTIPLY is refused
+SURFACE_BLEND_MODES = {"none": SURFACE_BLEND_NONE, "additive": SURFACE_BLEND_ADDITIVE, "alpha": SURFACE_BLEND_ALPHA, "multiply": SURFACE_BLEND_MULTIPLY}
 # the same records as NumPy dtypes (what the tests and upload helpers build)
 VERTEX_DTYPE = [("texcoord", "<f4", 2), ("position", "<f4", 3), ("normal", "<f4", 3), ("tangent", "<f4", 3), ("bitangent", "<f4", 3), ("color", "<f4", 4)]
 MATERIAL_DTYPE = [("albedo", "<f4", 4), ("ambient", "<f4", 4), ("emission", "<f4", 4), ("metallic", "<f4"), ("roughness", "<f4"), ("ao", "<f4"),
@@ -479,6 +482,13 @@ SIGNATURES = {
                                               C.POINTER(Band), _P, C.c_size_t]),
     "sailor_hip_surface_draw_indirect_lod": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(SurfaceDraw), _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32,
                                                        C.c_int32, C.c_int32, C.POINTER(Band), _P, C.c_size_t]),
+    "sailor_hip_surface_peel_begin": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(Band), _P, C.c_size_t, _P, C.c_int32]),
+    "sailor_hip_surface_peel_draw": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(SurfaceDraw), _P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32,
+                                               C.POINTER(Band), _P, C.c_size_t, _P, _P]),
+    "sailor_hip_surface_peel_draw_gltf": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(SurfaceDraw), _P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_int32,
+                                                    C.c_int32, C.POINTER(Band), _P, C.c_size_t, _P, _P]),
+    "sailor_hip_surface_peel_commit": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(Band), _P, C.c_size_t, _P, _P]),
+    "sailor_hip_surface_blend": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, C.c_int32, C.c_int32, C.POINTER(Band)]),
     "sailor_hip_surface_keys_offset": (C.c_size_t, []),
     "sailor_host_srgb_table": (C.c_int, [C.POINTER(C.c_float)]),
     "sailor_hip_surface_draw_prims": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),

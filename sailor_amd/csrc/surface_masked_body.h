@@ -3,6 +3,7 @@
 // alphaCutoff).  GLTF is a template argument, so each kernel holds its own record's offsets and, for Standard, no threshold word at all.
 // LOD (default false: the kernels as they were) makes the alpha fetch the implicit-level-of-detail one of surface_lod.h: the lane also carries the level
 // count of the albedo descriptor and the six steps of the edge functions to the next pixel, so a fragment can evaluate uv at its quad's other centres.
+// PEEL (default false, likewise) is the Transparent queue's draw of surface_transparent.hip: the same fragments against a read-only depth plane, keyed by order.
 #pragma once
 #include <type_traits>
 #include "surface_fill.h"
@@ -136,18 +137,39 @@ __device__ __forceinline__ void surf_fragment_masked(unsigned long long* p, int 
     }
 }
 
-// the slices (gridDim.y) are k_surface_visibility's; without SAILOR_SURFACE_ALPHA_CUTOUT in draw.flags the keys are k_surface_visibility's
+// PEEL (surface_transparent.hip, the Transparent queue): the depth attachment is read only and a pixel keeps, of the fragments beyond the order it committed
+// last, the one of the SMALLEST order.  depth = the raw depth of the whole frame, last = the band's rows of the orders committed so far (0: none), both as
+// uint32 words, both plain loads.  The key is (0xFFFFFFFF - orderPlus1) << 32 | zbits, so the maximum is the smallest order; it is issued as
+// surf_fragment_masked issues its own: plain load, the discard only for a fragment that would win, then the atomicMax.
+struct SurfPeel { const uint32_t* depth; const uint32_t* last; };
 template <bool GLTF, bool LOD = false>
+__device__ __forceinline__ void surf_fragment_peel(unsigned long long* p, const SurfPeel& peel, size_t atFrame, size_t atBand, int i, int j, float z, unsigned int orderPlus1,
+                                                   const SurfAlphaOf<LOD>& A, long long e0, long long e1, long long e2, float area)
+{
+    const unsigned int zbits = __float_as_uint(z);
+    if (zbits < peel.depth[atFrame]) return;    // GreaterOrEqual on the images of two non-negative floats: equal depth passes; nothing is written back
+    if (orderPlus1 <= peel.last[atBand]) return; // blended by an earlier layer
+    const unsigned long long key = ((unsigned long long)(0xFFFFFFFFu - orderPlus1) << 32) | zbits;
+    if (key > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+        if (surf_alpha_keeps<GLTF, LOD>(A, i, j, e0, e1, e2, area)) atomicMax(p, key);
+    }
+}
+
+// the slices (gridDim.y) are k_surface_visibility's; without SAILOR_SURFACE_ALPHA_CUTOUT in draw.flags the keys are k_surface_visibility's
+template <bool GLTF, bool LOD = false, bool PEEL = false>
 __device__ __forceinline__ void surf_visibility_masked(const Mat4& P, const Mat4& V, const SailorSurfaceDraw& draw, const float* __restrict__ instances,
                                                        const SailorMaterialData* __restrict__ materials, uint32_t numMaterials,
                                                        const SailorTextureDesc* __restrict__ textures, uint32_t numTextures, uint32_t drawIndex, int W, int H,
-                                                       int rowBegin, int rows, void* __restrict__ workspace)
+                                                       int rowBegin, int rows, void* __restrict__ workspace, SurfPeel peel = SurfPeel())
 {
     const SurfWorkspace ws = surf_workspace(workspace, (size_t)rows * W);
     const unsigned int slice = blockIdx.y, slices = gridDim.y;
     if (blockIdx.x == 0 && slice == 0 && threadIdx.x == 0) ws.draws[drawIndex] = draw; // the resolve finds the draw here
     unsigned long long* keys = ws.keys;
     SURF_KEEP_VECTOR(keys); // (the last scalar pair that was spilled)
+    // two more pairs the scalar file does not have.  The Standard peel keeps the compiler's allocation: 4 scalar spills to vector lanes at 168 registers, the
+    // siblings' 3 waves per SIMD (pinned: none at 171, 2 waves).  The glTF peel has 2 waves either way (170 with the spills), so there they are pinned: 173, none.
+    if constexpr (PEEL && GLTF) { SURF_KEEP_VECTOR(peel.depth); SURF_KEEP_VECTOR(peel.last); }
     const float* __restrict__ vertices = reinterpret_cast<const float*>(draw.dVertices);
     const unsigned long long total = (unsigned long long)draw.numDrawn * draw.numTriangles;
     const unsigned long long id = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
@@ -186,7 +208,10 @@ __device__ __forceinline__ void surf_visibility_masked(const Mat4& P, const Mat4
         // the fill: the alpha words are the payload, carried to the wave once per large triangle
         surf_fill(t, orderPlus1, A, [](const SurfAlphaOf<LOD>& a, int src) { return surf_alpha_bcast<GLTF, LOD>(a, src); }, slice, slices, lane,
                   [&](int i, int j, float z, unsigned int tag, const SurfAlphaOf<LOD>& a, long long e0, long long e1, long long e2, float area) {
-                      surf_fragment_masked<GLTF, LOD>(keys + (size_t)(j - rowBegin) * W + i, i, j, z, tag, a, e0, e1, e2, area);
+                      if constexpr (PEEL) {
+                          const size_t atBand = (size_t)(j - rowBegin) * W + i;
+                          surf_fragment_peel<GLTF, LOD>(keys + atBand, peel, (size_t)j * W + i, atBand, i, j, z, tag, a, e0, e1, e2, area);
+                      } else surf_fragment_masked<GLTF, LOD>(keys + (size_t)(j - rowBegin) * W + i, i, j, z, tag, a, e0, e1, e2, area);
                   });
         if (part == 0) again = second;
     }

@@ -1145,6 +1145,85 @@ class SurfacePass:
                                                                    _ptr(target), self.W, self.H, C.byref(self.band)), "sailor_hip_surface_composite_gltf", self.ctx.handle)
         return target
 
+    def transparent(self, frame: UboFrameData, draws, instances: torch.Tensor, materials: torch.Tensor, textures: torch.Tensor, num_textures: int,
+                    depth: torch.Tensor, shade, target: torch.Tensor, ao_in: torch.Tensor | None = None, layers: int | None = None, prim_base: int = 0,
+                    on_layer=None) -> torch.Tensor:
+        """A RenderScene pass with `Tag: Transparent` (the Transparent section of include/sailor_hip.h): depth test against `depth` (the raw depth attachment of
+        the WHOLE frame, float32 [H, W], read only), no depth write, every fragment blended onto `target` (float32 [rows, W, 4]) in primitive order.  The pass is
+        peeled by primitive order, one layer at a time, and every layer rasterises the draws again.
+        draws: dicts of draw()'s keyword arguments (vertices, indices, instance_ids, num_drawn, first_instance, cull_back, alpha_cutout, gltf) plus `blend`:
+        "none", "additive" or "alpha" ("multiply" is refused: unsupported).
+        shade: a callable (surface float32 [3, rows, W, 4], ao float32 [rows, W] | None) -> radiance float32 [rows, W, 4]: the shade of the opaque pass bound to
+        its lights, lists and shadow maps -- e.g. lambda s, ao: fp.shade(frame, s, lights, n).  ao is resolve_gltf's aoOut (None if no draw is glTF's).
+        layers=N records N layers and the overflow round, reads nothing back and returns the device counters, int32 [N + 1]: the pixels each layer committed and,
+        last, the OVERFLOW -- the pixels that still had a fragment left.  layers=None is for tools and tests and SYNCHRONISES: it reads the committed count
+        after each layer and stops at the first empty one (the counters returned end with that 0).
+        on_layer(k, surface, coverage, emissive | None, ao | None): called behind every resolve (a test's window into the layers)."""
+        ctx, lib, dev = self.ctx, self.ctx._lib, self.ctx.device
+        assert depth.dtype == torch.float32 and depth.shape == (self.H, self.W) and depth.is_contiguous()
+        assert target.dtype == torch.float32 and target.shape == (self.rows, self.W, 4) and target.is_contiguous()
+        assert layers is None or layers >= 0
+        any_gltf = any(d.get("gltf", False) for d in draws)
+        num_materials = materials.numel() * materials.element_size() // 80
+        ws, n = _ptr(self.workspace), self.workspace.numel()
+        self.last = torch.empty((self.rows, self.W), dtype=torch.int32, device=dev)
+        descs, base = [], prim_base
+        for d in draws:
+            blend = d.get("blend", "none")
+            blend = _lib.SURFACE_BLEND_MODES[blend] if isinstance(blend, str) else int(blend)
+            ids, first = d.get("instance_ids"), d.get("first_instance", 0)
+            drawn = d.get("num_drawn")
+            if drawn is None:
+                drawn = ids.numel() if ids is not None else instances.numel() * instances.element_size() // 96 - first
+            nt = d["indices"].numel() // 3
+            flags = (_lib.SURFACE_CULL_BACK if d.get("cull_back", False) else 0) | (_lib.SURFACE_ALPHA_CUTOUT if d.get("alpha_cutout", False) else 0) | \
+                    (_lib.SURFACE_GLTF if d.get("gltf", False) else 0) | (blend << _lib.SURFACE_BLEND_SHIFT)
+            descs.append(_lib.SurfaceDraw(_ptr(d["vertices"]), _ptr(d["indices"]), _ptr(ids), nt, drawn, base, flags, first, 0))
+            base += host.surface_draw_prims(nt, drawn)
+        self.prim_base, self.draw_index = base, len(descs)
+
+        def peel(k, count):
+            _lib.check(lib.sailor_hip_surface_peel_begin(ctx.handle, self.W, self.H, C.byref(self.band), ws, n, _ptr(self.last), 1 if k == 0 else 0),
+                       "sailor_hip_surface_peel_begin", ctx.handle)
+            for index, d in enumerate(descs):
+                name = "sailor_hip_surface_peel_draw_gltf" if d.flags & _lib.SURFACE_GLTF else "sailor_hip_surface_peel_draw"
+                _lib.check(getattr(lib, name)(ctx.handle, C.byref(frame), C.byref(d), _ptr(instances), _ptr(materials), num_materials, _ptr(textures), num_textures, index,
+                                              self.W, self.H, C.byref(self.band), ws, n, _ptr(depth), _ptr(self.last)), name, ctx.handle)
+            _lib.check(lib.sailor_hip_surface_peel_commit(ctx.handle, self.W, self.H, C.byref(self.band), ws, n, _ptr(self.last), _ptr(count)),
+                       "sailor_hip_surface_peel_commit", ctx.handle)
+
+        def blend_layer(k):
+            if any_gltf:
+                surface, _, cov, ao, emissive = self.resolve_gltf(frame, instances, materials, textures, num_textures, ao_in=ao_in, want_depth=False,
+                                                                  want_coverage=on_layer is not None)
+            else:
+                surface, _, cov = self.resolve(frame, instances, materials, textures, num_textures, want_depth=False, want_coverage=on_layer is not None)
+                ao, emissive = ao_in, None
+            if on_layer is not None:
+                on_layer(k, surface, cov, emissive, ao)
+            radiance = shade(surface, ao)
+            assert radiance.dtype == torch.float32 and radiance.shape == (self.rows, self.W, 4) and radiance.is_contiguous()
+            _lib.check(lib.sailor_hip_surface_blend(ctx.handle, _ptr(radiance), _ptr(surface), _ptr(emissive), ws, n, _ptr(target), self.W, self.H, C.byref(self.band)),
+                       "sailor_hip_surface_blend", ctx.handle)
+
+        if layers is not None:
+            counts = torch.zeros(layers + 1, dtype=torch.int32, device=dev)
+            for k in range(layers):
+                peel(k, counts[k:])
+                blend_layer(k)
+            peel(layers, counts[layers:])
+            return counts
+        counts, k = [], 0
+        while True:
+            count = torch.zeros(1, dtype=torch.int32, device=dev)
+            peel(k, count)
+            ctx.synchronize()
+            counts.append(count)
+            if int(count.item()) == 0:
+                return torch.cat(counts)
+            blend_layer(k)
+            k += 1
+
     def download_keys(self) -> np.ndarray:
         """the keys as uint64 [rows, W]: depth bits << 32 | (order + 1)"""
         self.ctx.synchronize()

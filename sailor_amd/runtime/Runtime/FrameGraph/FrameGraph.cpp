@@ -398,7 +398,17 @@ void RenderSceneNode::Process(RHIFrameGraphPtr frameGraph, RHICommandListPtr tra
         for (const auto& b : sceneView.m_batches) {
             if (!b.m_tag.empty() && !(tagged && b.m_tag == tag)) continue; // the render queue filter: an untagged batch belongs to every queue
             RHIMaterialPtr material = m_pMaterial;
-            if (b.m_bGltf) { // an imported model's material: Standard_glTF.shader (ModelImporter.cpp:156-231), with the same two variations
+            if (!b.m_bZWrite) { // a material of the Transparent queue (ModelImporter.cpp:213-229): depth test, no depth write, the batch's blend mode
+                RHIMaterialPtr& variant = m_pTransparentMaterials[(((b.m_bGltf ? 2 : 0) + (b.m_bAlphaCutout ? 1 : 0)) * 2 + (b.m_bDoubleSided ? 1 : 0)) * 4 + (int)b.m_blendMode];
+                if (!variant) {
+                    const char* path = b.m_bGltf ? "Shaders/Standard_glTF.shader" : "Shaders/Standard.shader";
+                    variant = driver->CreateMaterial(b.m_bAlphaCutout ? driver->CreateShader(path, { "ALPHA_CUTOUT" }) : driver->CreateShader(path));
+                    variant->m_bDoubleSided = b.m_bDoubleSided;
+                    variant->m_bZWrite = false;
+                    variant->m_blendMode = b.m_blendMode;
+                }
+                material = variant;
+            } else if (b.m_bGltf) { // an imported model's material: Standard_glTF.shader (ModelImporter.cpp:156-231), with the same two variations
                 RHIMaterialPtr& variant = m_pGltfMaterials[(b.m_bAlphaCutout ? 2 : 0) + (b.m_bDoubleSided ? 1 : 0)];
                 if (!variant) {
                     RHIShaderPtr& shader = b.m_bAlphaCutout ? m_pGltfCutoutShader : m_pGltfShader;
@@ -448,6 +458,7 @@ void RenderSceneNode::Clear()
     m_pGltfShader.Clear();
     m_pGltfCutoutShader.Clear();
     for (auto& v : m_pGltfMaterials) v.Clear();
+    for (auto& v : m_pTransparentMaterials) v.Clear();
     m_surfaceBindings.Clear();
     m_draws.Clear();
 }

@@ -68,6 +68,8 @@ protected:
     // the materials of glTF batches (RHISceneBatch::m_bGltf), Shaders/Standard_glTF.shader: [0] plain, [1] double-sided, [2] ALPHA_CUTOUT, [3] both
     RHI::RHIShaderPtr m_pGltfShader, m_pGltfCutoutShader;
     RHI::RHIMaterialPtr m_pGltfMaterials[4];
+    // the materials of batches without z-write (the Transparent queue): [((gltf * 2 + ALPHA_CUTOUT) * 2 + double-sided) * 4 + blend mode]
+    RHI::RHIMaterialPtr m_pTransparentMaterials[32];
     RHI::RHIShaderBindingSetPtr m_surfaceBindings;
     // `GPUCulling: true` (DefaultRenderer.renderer): the draws are recorded as RHIRecordDrawCallGPUCulling records them (SceneIndirectDraws.h); without the
     // string the node records DrawIndexed with host counts, as before

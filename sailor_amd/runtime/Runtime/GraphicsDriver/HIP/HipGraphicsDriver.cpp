@@ -1144,6 +1144,104 @@ int HipGraphicsDriver::RecordSurfaceEnd(const TVector<RHIShaderBindingSetPtr>& b
     return sailor_hip_surface_store_depth(m_ctx, m_surfaceWorkspace->m_hip.m_devicePtr, bytes, (float*)depthToStore->m_buffer->m_hip.m_devicePtr, W, H, &band);
 }
 
+// The Transparent queue's pass (include/sailor_hip.h, the Transparent section): SurfacePass.transparent(layers = the budget) of forward_plus.py, launch for launch.
+int HipGraphicsDriver::RecordTransparentPass(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& color, const RHITexturePtr& depth,
+                                             const TVector<RHICommandList::TransparentDraw>& draws)
+{
+    m_surfaceBegun = false; // (the workspace is this pass's from here on)
+    SurfacePass pass;
+    RHIBufferPtr instances = scene_buffer(bindings, "data");
+    const SurfaceTables t = surface_tables(bindings);
+    if (bindings.size() < 2 || !bindings[1] || !host_copy_of(bindings[0], "frameData", pass.frame) || !color || !color->m_buffer || !depth || !depth->m_buffer || !instances ||
+        !t.bound || draws.empty() || draws.size() > SURFACE_MAX_DRAWS)
+        return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    if (m_worldSize > 1) return SAILOR_HIP_ERR_UNSUPPORTED; // (the pass runs on whole frames here)
+    const int W = color->GetExtent().x, H = color->GetExtent().y;
+    if (W != pass.frame.viewportSize[0] || H != pass.frame.viewportSize[1] || color->m_format != EFormat::R32G32B32A32_SFLOAT || depth->GetExtent().x != W ||
+        depth->GetExtent().y != H || depth->m_format != EFormat::R32_SFLOAT)
+        return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    // the descriptors, with the running primBase; every refusal comes before the first launch
+    TVector<SailorSurfaceDraw> descs;
+    bool gltf = false;
+    uint64_t primBase = 0;
+    for (const auto& src : draws) {
+        if (((src.m_flags >> SAILOR_SURFACE_BLEND_SHIFT) & SAILOR_SURFACE_BLEND_MASK) == SAILOR_SURFACE_BLEND_MULTIPLY) return SAILOR_HIP_ERR_UNSUPPORTED;
+        if (!src.m_vertexBuffer || !src.m_indexBuffer || (size_t)src.m_firstIndex + src.m_indexCount > src.m_indexBuffer->m_size / 4 ||
+            ((size_t)src.m_firstInstance + src.m_instanceCount) * sizeof(SailorPerInstanceData) > instances->m_size ||
+            (size_t)src.m_vertexOffset * sizeof(SailorVertexP3N3T3B3UV2C4) > src.m_vertexBuffer->m_size || primBase > 0xFFFFFFFFull)
+            return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+        SailorSurfaceDraw d {};
+        d.dVertices = (const SailorVertexP3N3T3B3UV2C4*)src.m_vertexBuffer->m_hip.m_devicePtr + src.m_vertexOffset;
+        d.dIndices = (const uint32_t*)src.m_indexBuffer->m_hip.m_devicePtr + src.m_firstIndex;
+        d.numTriangles = src.m_indexCount / 3; d.numDrawn = src.m_instanceCount;
+        d.primBase = (uint32_t)primBase; d.flags = src.m_flags; d.firstInstance = src.m_firstInstance;
+        gltf = gltf || (src.m_flags & SAILOR_SURFACE_GLTF);
+        uint64_t prims = 0;
+        sailor_hip_surface_draw_prims(d.numTriangles, d.numDrawn, &prims);
+        primBase += prims;
+        descs.push_back(d);
+    }
+    int st = SurfaceWorkspace(W, H, true, pass);
+    if (st != SAILOR_HIP_OK) return st;
+    const size_t pixels = (size_t)W * H, bytes = pass.bytes;
+    const uint32_t layers = m_transparentLayers;
+    if (!m_peelLast || m_peelLast->m_size != pixels * 4) m_peelLast = CreateBuffer(pixels * 4);
+    if (!m_peelCounts || m_peelCounts->m_size != (TRANSPARENT_MAX_LAYERS + 1) * 4) m_peelCounts = CreateBuffer((TRANSPARENT_MAX_LAYERS + 1) * 4);
+    if (!m_surfacePlanes || m_surfacePlanes->m_size != pixels * 48) m_surfacePlanes = CreateBuffer(pixels * 48);
+    if (!m_surfaceRadiance || m_surfaceRadiance->m_size != pixels * 16) m_surfaceRadiance = CreateBuffer(pixels * 16);
+    if (gltf && (!m_surfaceAo || m_surfaceAo->m_size != pixels * 4)) m_surfaceAo = CreateBuffer(pixels * 4);
+    if (gltf && (!m_surfaceEmissive || m_surfaceEmissive->m_size != pixels * 16)) m_surfaceEmissive = CreateBuffer(pixels * 16);
+    if (!m_peelLast || !m_peelCounts || !m_surfacePlanes || !m_surfaceRadiance || (gltf && (!m_surfaceAo || !m_surfaceEmissive))) return SAILOR_HIP_ERR_OUT_OF_MEMORY;
+    void* workspace = m_surfaceWorkspace->m_hip.m_devicePtr;
+    uint32_t* last = (uint32_t*)m_peelLast->m_hip.m_devicePtr;
+    uint32_t* counts = (uint32_t*)m_peelCounts->m_hip.m_devicePtr;
+    const float* dDepth = (const float*)depth->m_buffer->m_hip.m_devicePtr;
+    const SailorPerInstanceData* dInstances = (const SailorPerInstanceData*)instances->m_hip.m_devicePtr;
+    st = sailor_hip_buffer_fill_u32(m_ctx, counts, 0, 0u, layers + 1);
+    if (st != SAILOR_HIP_OK) return st;
+    m_peelCountsLayers = layers;
+    m_peelRecorded = true;
+    auto peel = [&](uint32_t k) {
+        int s = sailor_hip_surface_peel_begin(m_ctx, W, H, &pass.band, workspace, bytes, last, k == 0 ? 1 : 0);
+        for (size_t i = 0; i < descs.size() && s == SAILOR_HIP_OK; i++)
+            s = (descs[i].flags & SAILOR_SURFACE_GLTF ? sailor_hip_surface_peel_draw_gltf : sailor_hip_surface_peel_draw)(
+                m_ctx, &pass.frame, &descs[i], dInstances, t.materials, t.numMaterials, t.textures, t.numTextures, (uint32_t)i, W, H, &pass.band, workspace, bytes, dDepth, last);
+        return s != SAILOR_HIP_OK ? s : sailor_hip_surface_peel_commit(m_ctx, W, H, &pass.band, workspace, bytes, last, counts + k);
+    };
+    auto own = RHIShaderBindingSetPtr::Make();
+    own->GetOrAddShaderBinding("surface")->m_buffer = m_surfacePlanes;
+    own->GetOrAddShaderBinding("radiance")->m_buffer = m_surfaceRadiance;
+    auto ao = bound_texture(bindings[1], "g_aoSampler");
+    const float* aoIn = (ao && ao->m_extent.x == W && ao->m_extent.y == H) ? (const float*)ao->m_buffer->m_hip.m_devicePtr : nullptr;
+    for (uint32_t k = 0; k < layers; k++) {
+        if ((st = peel(k)) != SAILOR_HIP_OK) return st;
+        // the layer is an ordinary surface workspace: the existing resolve (no depth output) and the existing shade
+        st = gltf ? sailor_hip_surface_resolve_gltf(m_ctx, &pass.frame, dInstances, t.materials, t.numMaterials, t.textures, t.numTextures, W, H, &pass.band, workspace, bytes,
+                                                    (float*)m_surfacePlanes->m_hip.m_devicePtr, pixels, nullptr, nullptr, aoIn, (float*)m_surfaceAo->m_hip.m_devicePtr,
+                                                    (float*)m_surfaceEmissive->m_hip.m_devicePtr)
+                  : sailor_hip_surface_resolve(m_ctx, &pass.frame, dInstances, t.materials, t.numMaterials, t.textures, t.numTextures, W, H, &pass.band, workspace, bytes,
+                                               (float*)m_surfacePlanes->m_hip.m_devicePtr, pixels, nullptr, nullptr);
+        if (st != SAILOR_HIP_OK) return st;
+        m_shadeAoOverride = gltf ? (const float*)m_surfaceAo->m_hip.m_devicePtr : nullptr;
+        st = RecordShade({ bindings[0], bindings[1], own });
+        m_shadeAoOverride = nullptr;
+        if (st != SAILOR_HIP_OK) return st;
+        BeforeBufferWrite(color->m_buffer->m_hip.m_devicePtr);
+        st = sailor_hip_surface_blend(m_ctx, (const float*)m_surfaceRadiance->m_hip.m_devicePtr, (const float*)m_surfacePlanes->m_hip.m_devicePtr,
+                                      gltf ? (const float*)m_surfaceEmissive->m_hip.m_devicePtr : nullptr, workspace, bytes, (float*)color->m_buffer->m_hip.m_devicePtr, W, H,
+                                      &pass.band);
+        if (st != SAILOR_HIP_OK) return st;
+    }
+    return peel(layers); // what is left behind the budget: the overflow
+}
+
+int HipGraphicsDriver::TransparentOverflow(uint32_t& outPixels)
+{
+    outPixels = 0;
+    if (!m_peelRecorded || !m_peelCounts) return SAILOR_HIP_OK;
+    return sailor_hip_buffer_download(m_ctx, &outPixels, m_peelCounts->m_hip.m_devicePtr, (size_t)m_peelCountsLayers * 4, 4);
+}
+
 // ---- the render-pass subset: state is kept on the command list, a 6-index draw of a known full-screen material becomes a
 // kernel launch at submit time (record-then-submit, like Dispatch) ---------------------------------------------------------------
 void HipGraphicsDriver::BeginRenderPass(RHICommandListPtr cmd, const TVector<RHITexturePtr>& colorAttachments, RHITexturePtr depthStencilAttachment,
@@ -1156,6 +1254,8 @@ void HipGraphicsDriver::BeginRenderPass(RHICommandListPtr cmd, const TVector<RHI
     cmd->m_surfaceDraws = 0;
     cmd->m_surfaceCutout = false;
     cmd->m_surfaceGltf = false;
+    cmd->m_transparentDraws.clear();
+    cmd->m_bTransparentRefused = false;
     cmd->m_uiCommands.clear();
     cmd->m_scissorOffset = { 0, 0 };
     cmd->m_scissorExtent = { -1, -1 };
@@ -1190,7 +1290,15 @@ void HipGraphicsDriver::EndRenderPass(RHICommandListPtr cmd)
                                              color->m_buffer->m_hip.m_devicePtr);
         });
     }
-    if (cmd->m_surfaceDraws > 0 && cmd->m_colorAttachments.empty()) {
+    if (cmd->m_bTransparentRefused) {
+        // z-write on and off in one pass, or an indirect draw of a material without z-write: the pass is not ended (no resolve, no blend)
+        cmd->m_hip.m_commands.push_back([this]() { m_surfaceBegun = false; return (int)SAILOR_HIP_ERR_UNSUPPORTED; });
+    } else if (!cmd->m_transparentDraws.empty()) { // the Transparent queue's pass: every fragment behind the depth attachment, blended in primitive order
+        RHITexturePtr color = cmd->m_colorAttachments.empty() ? RHITexturePtr() : cmd->m_colorAttachments[0], depth = cmd->m_depthAttachment;
+        TVector<RHIShaderBindingSetPtr> bindings = cmd->m_boundBindings;
+        TVector<RHICommandList::TransparentDraw> draws = std::move(cmd->m_transparentDraws);
+        cmd->m_hip.m_commands.push_back([this, bindings, color, depth, draws]() { return RecordTransparentPass(bindings, color, depth, draws); });
+    } else if (cmd->m_surfaceDraws > 0 && cmd->m_colorAttachments.empty()) {
         // a pass with no colour attachment whose draws went to the surface pass (DepthPrepassNode): the keys' depth into the depth attachment and nothing
         // else -- no resolve, no shade, no composite
         RHITexturePtr depth = cmd->m_depthAttachment;
@@ -1222,6 +1330,8 @@ void HipGraphicsDriver::EndRenderPass(RHICommandListPtr cmd)
     cmd->m_casterDraws = 0;
     cmd->m_surfaceDraws = 0;
     cmd->m_surfaceCutout = false;
+    cmd->m_transparentDraws.clear();
+    cmd->m_bTransparentRefused = false;
     cmd->m_bClearDepth = false;
     cmd->m_colorAttachments.clear();
     cmd->m_boundMaterial.Clear();
@@ -1284,6 +1394,17 @@ void HipGraphicsDriver::DrawIndexed(RHICommandListPtr cmd, uint32_t indexCount, 
         RHITexturePtr color = cmd->m_colorAttachments.empty() ? RHITexturePtr() : cmd->m_colorAttachments[0], depth = cmd->m_depthAttachment;
         RHIBufferPtr vb = cmd->m_vertexBuffer, ib = cmd->m_indexBuffer;
         TVector<RHIShaderBindingSetPtr> bindings = cmd->m_boundBindings;
+        if (!cmd->m_boundMaterial->m_bZWrite) {
+            // a draw of the Transparent queue: noted, launched by the pass's end.  (Its cutout and glTF flags are the draw's own: they ask nothing of a
+            // z-writing pass's end.)  A pass that mixes z-write on and off is refused.
+            const bool cutoutBefore = cmd->m_surfaceCutout, gltfBefore = cmd->m_surfaceGltf;
+            const uint32_t flags = surface_draw_flags(cmd, name) | ((uint32_t)cmd->m_boundMaterial->m_blendMode << SAILOR_SURFACE_BLEND_SHIFT);
+            cmd->m_surfaceCutout = cutoutBefore; cmd->m_surfaceGltf = gltfBefore;
+            if (cmd->m_surfaceDraws > 0) cmd->m_bTransparentRefused = true;
+            cmd->m_transparentDraws.push_back({ vb, ib, indexCount, instanceCount, firstIndex, vertexOffset, firstInstance, flags });
+            return;
+        }
+        if (!cmd->m_transparentDraws.empty() || cmd->m_bTransparentRefused) { cmd->m_bTransparentRefused = true; return; } // (mixed: nothing of the pass is launched)
         const uint32_t drawIndex = cmd->m_surfaceDraws++;
         const uint32_t flags = surface_draw_flags(cmd, name);
         cmd->m_hip.m_commands.push_back([this, bindings, color, depth, vb, ib, drawIndex, indexCount, instanceCount, firstIndex, vertexOffset, firstInstance, flags]() {
@@ -1400,6 +1521,7 @@ void HipGraphicsDriver::DrawIndexedIndirect(RHICommandListPtr cmd, RHIBufferPtr 
         cmd->m_hip.m_commands.push_back([]() { return (int)SAILOR_HIP_ERR_UNSUPPORTED; });
         return;
     }
+    if (standard && !cmd->m_boundMaterial->m_bZWrite) { cmd->m_bTransparentRefused = true; return; } // an indirect transparent pass: refused at the pass's end
     RHITexturePtr color = cmd->m_colorAttachments.empty() ? RHITexturePtr() : cmd->m_colorAttachments[0], depth = cmd->m_depthAttachment;
     RHIBufferPtr vb = cmd->m_vertexBuffer, ib = cmd->m_indexBuffer;
     TVector<RHIShaderBindingSetPtr> bindings = cmd->m_boundBindings;

@@ -213,6 +213,19 @@ private:
                                   const RHI::RHIBufferPtr& vertices, const RHI::RHIBufferPtr& indices, bool first, bool clearDepth, uint32_t drawIndex,
                                   const SailorDrawIndexedIndirectData& host, const RHI::RHIBufferPtr& command, size_t commandOffset, uint32_t flags);
     int RecordSurfaceEndDepthOnly(const RHI::RHITexturePtr& depth);
+    // A RenderScene pass whose draws all have z-write off (the Transparent queue), recorded at EndRenderPass: m_transparentLayers times { peel_begin, every
+    // draw, peel_commit, the resolve, the shade, the blend onto `color` } and one more { peel_begin, draws, peel_commit } whose count is the overflow.  The
+    // depth attachment is read only.  Refused with the unsupported status, before anything is launched: a Multiply draw, a split frame.
+    int RecordTransparentPass(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& color, const RHI::RHITexturePtr& depth,
+                              const TVector<RHI::RHICommandList::TransparentDraw>& draws);
+public:
+    // the layer budget of a transparent pass (1 .. TRANSPARENT_MAX_LAYERS; default 4): false, and nothing changed, outside the range
+    static constexpr uint32_t TRANSPARENT_MAX_LAYERS = 64;
+    bool SetTransparentLayers(uint32_t layers) { if (layers < 1 || layers > TRANSPARENT_MAX_LAYERS) return false; m_transparentLayers = layers; return true; }
+    // the overflow of the LAST recorded transparent pass: the pixels that still had a fragment behind the budget's layers (0 if no pass was recorded).  A host
+    // read that waits for the stream: for the next frame's start, like sailor_hip_exchange_adapt's status -- it is never part of a recorded frame.
+    int TransparentOverflow(uint32_t& outPixels);
+private:
     int RecordDebugLines(const RHI::RHITexturePtr& color, const RHI::RHITexturePtr& depth, const RHI::RHIBufferPtr& vertices, const RHI::RHIBufferPtr& indices,
                          const TVector<uint8_t>& pushConstants, uint32_t indexCount, uint32_t firstIndex, uint32_t vertexOffset);
     int RecordUi(const RHI::RHITexturePtr& color, const RHI::RHIBufferPtr& vertices, const RHI::RHIBufferPtr& indices, bool bIndexUint16,
@@ -276,6 +289,10 @@ private:
     RHI::RHIBufferPtr m_uiWorkspace;
     uint64_t m_surfacePrimBase = 0;
     bool m_surfaceBegun = false;
+    // the transparent pass: the orders each pixel committed last, the layers' counters ([layer] committed pixels, [budget] the overflow) and the budget
+    RHI::RHIBufferPtr m_peelLast, m_peelCounts;
+    uint32_t m_transparentLayers = 4, m_peelCountsLayers = 0;
+    bool m_peelRecorded = false;
     int32_t m_cullW = 0, m_cullH = 0, m_cullLights = 0; // geometry of the last light cull: locates its shading-order hint in the workspace
     bool m_cullOrderValid = false;
     std::map<const void*, RHI::RHIBufferPtr> m_rasterWorkspaces; // depth attachment -> the rasteriser's workspace (coarse depth, mesh box, giants' queue)

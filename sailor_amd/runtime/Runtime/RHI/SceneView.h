@@ -22,6 +22,10 @@ struct RHISceneBatch {
     // the batch's shader is Shaders/Standard_glTF.shader, what ModelImporter.cpp:156-231 gives every imported model, and its material slots are that shader's
     // MaterialData; false = Shaders/Standard.shader
     bool m_bGltf = false;
+    // RenderState::m_bEnableZWrite and m_blendMode of the batch's material: a glTF material with alphaMode == "BLEND" has the render queue Transparent, z-write
+    // off and blend None (ModelImporter.cpp:213-229); a .mat file chooses its blendMode (MaterialImporter.cpp:329-357).  The defaults are the batch of before.
+    bool m_bZWrite = true;
+    EBlendMode m_blendMode = EBlendMode::None;
 };
 
 enum class EShadowType : uint32_t { None = 0, PCF = 1, EVSM = 2 }; // RHI/SceneView.h:13-18

@@ -181,6 +181,9 @@ public:
     EBlendMode m_blendMode = EBlendMode::None;
     // RenderState::m_cullMode == ECullMode::None (a glTF doubleSided material); otherwise back faces are culled.  Read by the draws of Standard.shader only.
     bool m_bDoubleSided = false;
+    // RenderState::m_bEnableZWrite.  false = a material of the Transparent queue (ModelImporter.cpp:213-229: depth test on, z-write off): its draws of
+    // Standard.shader / Standard_glTF.shader are blended in primitive order under m_blendMode, and the depth attachment is read only
+    bool m_bZWrite = true;
     // the topology the material's pipeline was created with (CreateMaterial(vertexDescription, topology, ...)): LineList for DebugContext's Gizmo material
     EPrimitiveTopology m_topology = EPrimitiveTopology::TriangleList;
 };
@@ -201,6 +204,11 @@ public:
     bool m_bClearDepth = false;                                // BeginRenderPass(..., bClearDepthStencil): a surface pass then starts from cleared keys
     bool m_surfaceCutout = false;                              // ... one of them with ALPHA_CUTOUT: the pass ends with the depth write (sailor_hip_surface_store_depth)
     bool m_surfaceGltf = false;                                // ... one of them with Standard_glTF.shader: the pass ends with the glTF resolve and composite
+    // the draws of materials WITHOUT z-write recorded in the current pass (the Transparent queue): nothing is launched per draw, the pass ends with the peel
+    // over all of them.  m_bTransparentRefused: the pass mixed z-write on and off, or held an indirect transparent draw: it ends with the unsupported status
+    struct TransparentDraw { TRefPtr<class RHIBuffer> m_vertexBuffer, m_indexBuffer; uint32_t m_indexCount, m_instanceCount, m_firstIndex, m_vertexOffset, m_firstInstance, m_flags; };
+    TVector<TransparentDraw> m_transparentDraws;
+    bool m_bTransparentRefused = false;
     TRefPtr<class RHIMaterial> m_boundMaterial;
     TVector<TRefPtr<class RHIShaderBindingSet>> m_boundBindings;
     bool m_bIndexUint16 = false;                               // BindIndexBuffer(..., bUint16InsteadOfUint32)

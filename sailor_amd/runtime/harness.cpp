@@ -490,6 +490,35 @@ RT_API int sailor_rt_set_scene_shaders(SailorRuntime* rt, const uint32_t* shader
     return 0;
 }
 
+// RenderState::m_blendMode and m_bEnableZWrite of the batches' materials (ModelImporter.cpp:213-229 for alphaMode BLEND, MaterialImporter.cpp:329-357 for a .mat
+// file): blendModes[i] is EBlendMode (0 None, 1 Additive, 2 AlphaBlending, 3 Multiply), zWrite[i] 0 or 1.  -1, and nothing changed, unless numBatches is the
+// scene's and every entry is known.
+RT_API int sailor_rt_set_scene_blend(SailorRuntime* rt, const uint32_t* blendModes, const uint32_t* zWrite, int numBatches)
+{
+    if (!rt || numBatches < 0 || (size_t)numBatches != rt->snapshot.m_batches.size() || !sailor_rt_scene_blend_ok(blendModes, zWrite, numBatches)) return -1;
+    for (int i = 0; i < numBatches; i++) {
+        rt->snapshot.m_batches[(size_t)i].m_blendMode = (EBlendMode)blendModes[i];
+        rt->snapshot.m_batches[(size_t)i].m_bZWrite = zWrite[i] != 0;
+    }
+    return 0;
+}
+
+// the layer budget of a transparent pass (default 4); -1, and nothing changed, outside 1 .. 64
+RT_API int sailor_rt_set_transparent_layers(SailorRuntime* rt, int layers)
+{
+    if (!rt || layers < 0) return -1;
+    return static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver())->SetTransparentLayers((uint32_t)layers) ? 0 : -1;
+}
+
+// the overflow of the last frame's transparent pass: the pixels that still had a fragment behind the budget's layers.  A host read that waits for the stream:
+// call it at the next frame's start (or after the frame), as sailor_hip_exchange_adapt's status is read; the recorded frame never reads it.  -1 on failure.
+RT_API long long sailor_rt_transparent_overflow(SailorRuntime* rt)
+{
+    if (!rt) return -1;
+    uint32_t pixels = 0;
+    return static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver())->TransparentOverflow(pixels) == 0 ? (long long)pixels : -1;
+}
+
 // RenderScene's attachments for those draws: "color" (RGBA32F, e.g. Main) and "depthStencil" (the raw R32F DepthBuffer of the prepass, or null)
 RT_API int sailor_rt_set_scene_targets(SailorRuntime* rt, void* color, void* depth, int width, int height)
 {

@@ -54,3 +54,13 @@ inline bool sailor_rt_scene_flags_ok(const uint32_t* flags, int count)
         if (flags[i] & ~(SAILOR_RT_BATCH_ALPHA_CUTOUT | SAILOR_RT_BATCH_DOUBLE_SIDED)) return false;
     return true;
 }
+
+// the blend mode (EBlendMode: None 0, Additive 1, AlphaBlending 2, Multiply 3 -- Multiply is a known mode; the pass that draws it is refused) and the z-write
+// flag (0 or 1) of one batch, as sailor_rt_set_scene_blend takes them
+inline bool sailor_rt_scene_blend_ok(const uint32_t* blendModes, const uint32_t* zWrite, int count)
+{
+    if (count < 0 || (count > 0 && (!blendModes || !zWrite))) return false;
+    for (int i = 0; i < count; i++)
+        if (blendModes[i] > 3u || zWrite[i] > 1u) return false;
+    return true;
+}

@@ -79,6 +79,10 @@ def load() -> C.CDLL:
         rt.sailor_rt_set_scene_targets.argtypes = [P, P, P, C.c_int, C.c_int]
         rt.sailor_rt_set_scene_tags.argtypes = [P, C.c_char_p, P, C.c_int]
         rt.sailor_rt_set_scene_shaders.argtypes = [P, P, C.c_int]
+        rt.sailor_rt_set_scene_blend.argtypes = [P, P, P, C.c_int]
+        rt.sailor_rt_set_transparent_layers.argtypes = [P, C.c_int]
+        rt.sailor_rt_transparent_overflow.argtypes = [P]
+        rt.sailor_rt_transparent_overflow.restype = C.c_longlong
         rt.sailor_rt_process_frame.argtypes = [P]
         rt.sailor_rt_node_indirect_commands.argtypes = [P, C.c_int, P, C.c_int]
         rt.sailor_rt_draw_indexed_indirect.argtypes = [P, C.c_char_p, P, C.c_int, C.c_int]
@@ -451,6 +455,25 @@ class Runtime:
         what an imported model's material uses: its slots of the material table are that shader's records)"""
         s = np.ascontiguousarray(shaders, np.uint32)
         _lib.check(self.rt.sailor_rt_set_scene_shaders(self.h, s.ctypes.data if len(s) else None, len(s)), "sailor_rt_set_scene_shaders")
+
+    def set_scene_blend(self, blend_modes, z_write):
+        """the blend mode and the z-write of set_scene's batches' materials, after set_scene: one EBlendMode per batch (0 None, 1 Additive, 2 AlphaBlending,
+        3 Multiply) and one 0 / 1.  A RenderScene pass whose batches all have z-write off is the Transparent queue's: peeled by primitive order and blended"""
+        b, z = np.ascontiguousarray(blend_modes, np.uint32), np.ascontiguousarray(z_write, np.uint32)
+        assert len(b) == len(z)
+        _lib.check(self.rt.sailor_rt_set_scene_blend(self.h, b.ctypes.data if len(b) else None, z.ctypes.data if len(z) else None, len(b)), "sailor_rt_set_scene_blend")
+
+    def set_transparent_layers(self, layers: int):
+        """the layer budget of a transparent pass (default 4)"""
+        _lib.check(self.rt.sailor_rt_set_transparent_layers(self.h, layers), "sailor_rt_set_transparent_layers")
+
+    def transparent_overflow(self) -> int:
+        """the pixels that still had a fragment behind the budget's layers in the last frame's transparent pass.  SYNCHRONISES with the stream: read it after the
+        frame or at the next frame's start"""
+        n = self.rt.sailor_rt_transparent_overflow(self.h)
+        if n < 0:
+            raise _lib.SailorHipError(-1, "sailor_rt_transparent_overflow")
+        return int(n)
 
     def set_scene_targets(self, color, depth=None):
         """RenderScene's colour attachment (float32 [H, W, 4]) and the prepass's raw depth (float32 [H, W]) or None"""
