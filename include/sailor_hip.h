@@ -1284,7 +1284,7 @@ typedef struct SailorSurfaceDraw {
     uint32_t numTriangles;
     uint32_t numDrawn;
     uint32_t primBase;                          /* the order of the draw's first primitive: the previous draw's primBase + its sailor_hip_surface_draw_prims */
-    uint32_t flags;                             /* SAILOR_SURFACE_CULL_BACK; SAILOR_SURFACE_ALPHA_CUTOUT through sailor_hip_surface_draw_masked, _draw_gltf and _draw_indirect only; SAILOR_SURFACE_GLTF (below) through _draw_gltf and _draw_indirect only; SAILOR_SURFACE_BLEND_* (the Transparent section) through _peel_draw and _peel_draw_gltf only */
+    uint32_t flags;                             /* SAILOR_SURFACE_CULL_BACK; SAILOR_SURFACE_ALPHA_CUTOUT through sailor_hip_surface_draw_masked, _draw_gltf and _draw_indirect only; SAILOR_SURFACE_GLTF (below) through _draw_gltf and _draw_indirect only; SAILOR_SURFACE_BLEND_* (the Transparent section) through _peel_draw, _peel_draw_gltf, _bucket_draw and _bucket_draw_gltf only */
     uint32_t firstInstance;
     uint32_t _pad;
 } SailorSurfaceDraw;
@@ -1557,7 +1557,7 @@ SAILOR_HIP_API int sailor_hip_surface_draw_indirect_lod(SailorHipContext* ctx, c
  *   sailor_hip_surface_blend.  A pass of L layers is L such rounds and one more { begin, draws, commit } whose count is the OVERFLOW: the pixels that still
  *   had a fragment left.  Every layer rasterises the pass again.  Indirect draws and the `_lod` fetch are not part of this section.
  * All entry points record only (no allocation, no synchronisation, capturable); a refused call launches nothing and leaves its text in last_error. */
-#define SAILOR_SURFACE_BLEND_SHIFT 3u /* SailorSurfaceDraw.flags bits 3-4: the draw's EBlendMode; accepted by sailor_hip_surface_peel_draw / _peel_draw_gltf only */
+#define SAILOR_SURFACE_BLEND_SHIFT 3u /* SailorSurfaceDraw.flags bits 3-4: the draw's EBlendMode; accepted by sailor_hip_surface_peel_draw / _peel_draw_gltf and _bucket_draw / _bucket_draw_gltf only */
 #define SAILOR_SURFACE_BLEND_MASK 3u
 #define SAILOR_SURFACE_BLEND_NONE 0u
 #define SAILOR_SURFACE_BLEND_ADDITIVE 1u
@@ -1590,6 +1590,47 @@ SAILOR_HIP_API int sailor_hip_surface_peel_commit(SailorHipContext* ctx, int32_t
  * pixel of the band, as dTarget.  A pixel without a fragment keeps the target's bits. */
 SAILOR_HIP_API int sailor_hip_surface_blend(SailorHipContext* ctx, const float* dRadiance, const float* dSurfaceP0, const float* dEmissiveOrNull,
                                             const void* dWorkspace, size_t workspaceBytes, float* dTarget, int32_t width, int32_t height, const SailorBand* band);
+
+/* -- Per-pixel fragment buckets: the Transparent queue in ONE rasterisation (surface_buckets.hip) --
+ * A SECOND MECHANISM under the same rules: 1 to 5 above are untouched, and so are the peel's entry points, which remain the default route of every caller.
+ * The draws run once and leave, at every pixel, the pixel's first K fragments in primitive order; every layer is then read out of that store instead of being
+ * rasterised again, and goes through the same resolve, the same shade and sailor_hip_surface_blend.  A layer read out is the key the peel's commit would have
+ * left, so the two routes give the same bits.
+ * The store: K + 1 planes of uint64 over the band's rows, plane-major -- bucket[p][row * width + x], p = 0 .. K.  A slot holds orderPlus1 << 32 | zbits, or
+ * EMPTY, all ones (never a key: an order that would reach 2^32 - 1 is refused).  After the draws plane p holds the pixel's (p + 1)-th smallest orderPlus1
+ * among the fragments that exist by rule 1, or EMPTY; plane K is the sentinel, non-empty exactly where the pixel has more than K fragments.  The insertion
+ * is order-free, 64-bit atomicMin alone (surface_masked_body.h has the argument).  (K + 1) x 8 bytes a pixel.
+ * A pass: _bucket_begin -> every draw once through _bucket_draw / _bucket_draw_gltf -> K times { _bucket_layer(k), sailor_hip_surface_resolve /
+ * _resolve_gltf (dDepthOutOrNull = NULL), the shade, sailor_hip_surface_blend } -> _bucket_layer(K), whose count is the OVERFLOW, equal to the peel's by
+ * definition.  Indirect draws and the `_lod` fetch are not part of this sub-section either.
+ * All entry points record only (no allocation, no synchronisation, capturable); a refused call launches nothing and leaves its text in last_error.
+ * Refused everywhere: layers outside 1 .. 64; a NULL or not 8-byte aligned dBuckets; bucketBytes below sailor_hip_surface_bucket_bytes. */
+/* The bytes of the store of `layers` (= K) layers over the band's rows: (layers + 1) * fbRowCount * width * 8.  0 on a bad argument (a NULL band, a width or
+ * a row count outside 1 .. 32768, layers outside 1 .. 64). */
+SAILOR_HIP_API size_t sailor_hip_surface_bucket_bytes(int32_t width, const SailorBand* band, uint32_t layers);
+/* Begins a pass: sailor_hip_surface_begin without a depth (zero keys, empty descriptor slots, the sRGB table) and every slot of the store EMPTY. */
+SAILOR_HIP_API int sailor_hip_surface_bucket_begin(SailorHipContext* ctx, int32_t width, int32_t height, const SailorBand* band, void* dWorkspace,
+                                                   size_t workspaceBytes, void* dBuckets, size_t bucketBytes, uint32_t layers);
+/* One DrawIndexed of the pass, issued ONCE: k_surface_bucket.  The arguments, checks and refusals of sailor_hip_surface_peel_draw (MULTIPLY:
+ * SAILOR_HIP_ERR_UNSUPPORTED) with the store in place of dLast.  The workspace takes the draw's descriptor, for the resolves and the blend. */
+SAILOR_HIP_API int sailor_hip_surface_bucket_draw(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSurfaceDraw* draw,
+                                                  const SailorPerInstanceData* dInstances, const SailorMaterialData* dMaterials, uint32_t numMaterials,
+                                                  const SailorTextureDesc* dTextures, uint32_t numTextures, uint32_t drawIndex, int32_t width, int32_t height,
+                                                  const SailorBand* band, void* dWorkspace, size_t workspaceBytes, const float* dDepth, void* dBuckets,
+                                                  size_t bucketBytes, uint32_t layers);
+/* The same for a Standard_glTF.shader material: k_surface_bucket_gltf; flags must hold SAILOR_SURFACE_GLTF. */
+SAILOR_HIP_API int sailor_hip_surface_bucket_draw_gltf(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSurfaceDraw* draw,
+                                                       const SailorPerInstanceData* dInstances, const SailorMaterialData* dMaterials, uint32_t numMaterials,
+                                                       const SailorTextureDesc* dTextures, uint32_t numTextures, uint32_t drawIndex, int32_t width,
+                                                       int32_t height, const SailorBand* band, void* dWorkspace, size_t workspaceBytes, const float* dDepth,
+                                                       void* dBuckets, size_t bucketBytes, uint32_t layers);
+/* Reads layer k out of the store: k_surface_bucket_layer.  k < layers: every key of the workspace becomes plane k's fragment as zbits << 32 | orderPlus1 (0
+ * where the slot is EMPTY) -- an ordinary surface workspace, as behind sailor_hip_surface_peel_commit -- and *dCount (device, uint32; the caller zeroes it)
+ * += the pixels that have one.  k == layers: the workspace is left alone and *dCount += the pixels whose sentinel slot is taken, the OVERFLOW.
+ * Also refused: k > layers; a NULL or not 4-byte aligned dCount. */
+SAILOR_HIP_API int sailor_hip_surface_bucket_layer(SailorHipContext* ctx, int32_t width, int32_t height, const SailorBand* band, void* dWorkspace,
+                                                   size_t workspaceBytes, const void* dBuckets, size_t bucketBytes, uint32_t layers, uint32_t k,
+                                                   uint32_t* dCount);
 
 /* ---- DebugDraw: the line-list pass of the Gizmo material (debug_lines.hip) ---------------------------------------------------------------------
  * Replaces: the draw FrameGraph/DebugDrawNode.cpp:19-79 replays -- RHI/DebugContext.cpp:382-398 (DrawDebugMesh: one DrawIndexed over the line list that

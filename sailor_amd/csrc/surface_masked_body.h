@@ -3,7 +3,9 @@
 // alphaCutoff).  GLTF is a template argument, so each kernel holds its own record's offsets and, for Standard, no threshold word at all.
 // LOD (default false: the kernels as they were) makes the alpha fetch the implicit-level-of-detail one of surface_lod.h: the lane also carries the level
 // count of the albedo descriptor and the six steps of the edge functions to the next pixel, so a fragment can evaluate uv at its quad's other centres.
-// PEEL (default false, likewise) is the Transparent queue's draw of surface_transparent.hip: the same fragments against a read-only depth plane, keyed by order.
+// MODE (default SURF_DRAW_MASKED, likewise) chooses what a fragment does: SURF_DRAW_PEEL is the Transparent queue's draw of surface_transparent.hip -- the same
+// fragments against a read-only depth plane, keyed by order --, SURF_DRAW_BUCKET its one-rasterisation draw of surface_buckets.hip: the same fragments again,
+// inserted into the pixel's K + 1 ordered slots.
 #pragma once
 #include <type_traits>
 #include "surface_fill.h"
@@ -155,13 +157,55 @@ __device__ __forceinline__ void surf_fragment_peel(unsigned long long* p, const 
     }
 }
 
-// the slices (gridDim.y) are k_surface_visibility's; without SAILOR_SURFACE_ALPHA_CUTOUT in draw.flags the keys are k_surface_visibility's
-template <bool GLTF, bool LOD = false, bool PEEL = false>
+// BUCKET (surface_buckets.hip, the Transparent queue in one rasterisation): a pixel keeps its first K fragments in primitive order, and whether there is a
+// (K + 1)-th.  buckets = K + 1 planes of 64-bit slots over the band's rows, plane-major, `plane` slots apart; a slot holds orderPlus1 << 32 | zbits or
+// SURF_BUCKET_EMPTY (all ones: never a key, an order that would reach 2^32 - 1 is refused by the entry point).  After the draws plane p holds the pixel's
+// (p + 1)-th smallest key among the fragments that exist; plane K is the sentinel, non-empty exactly where the pixel has more than K fragments.
+//
+// The insertion is order-free and made of 64-bit atomicMin alone: a fragment with key v walks p = 0 .. K; old = atomicMin(&slot[p], v); old == EMPTY: the
+// slot was free, stop; otherwise go on with max(old, v); what is carried past plane K is dropped.  Why every schedule leaves the same planes: plane 0 ends as
+// the minimum of everything offered to it, whatever the arrival order.  Every other value offered to plane 0 is carried to plane 1 EXACTLY ONCE: as itself
+// when it met something smaller (its atomicMin changed nothing and max(old, v) = v), or, when it was stored, by the one smaller value that later displaces it
+// (that atomicMin returns it as `old`, and max(old, v) = old).  So plane 1 is offered everything but the minimum and ends as its minimum, the second
+// smallest; and so on by induction down to plane K.  The keys of a pixel are distinct (a primitive has at most one fragment there), so no tie arises.
+//
+// Two shortcuts, both exact because a slot only ever decreases, so a relaxed load of it (surf_fragment_masked's idiom) can only show a value that is too LARGE:
+//   - v > slot[p] as loaded proves the atomicMin there would store nothing and return something smaller than v: the walk goes to p + 1 with v, without it;
+//   - v > slot[K] as loaded proves v is not among the pixel's K + 1 smallest (the slot is at or above its final value, the (K + 1)-th smallest of everything
+//     that is inserted): the fragment is dropped with no atomic at all, and before its discard is evaluated.
+// The order of a fragment's tests: depth, the plane-K reject, the discard, the chain -- a discarded fragment never touches a slot.
+#define SURF_BUCKET_EMPTY 0xFFFFFFFFFFFFFFFFull
+struct SurfBucket { const uint32_t* depth; unsigned long long* buckets; size_t plane; uint32_t layers; };
+template <bool GLTF, bool LOD = false>
+__device__ __forceinline__ void surf_fragment_bucket(const SurfBucket& b, size_t atFrame, size_t atBand, int i, int j, float z, unsigned int orderPlus1,
+                                                     const SurfAlphaOf<LOD>& A, long long e0, long long e1, long long e2, float area)
+{
+    const unsigned int zbits = __float_as_uint(z);
+    if (zbits < b.depth[atFrame]) return;   // surf_fragment_peel's test: equal depth passes, nothing is written back
+    unsigned long long v = ((unsigned long long)orderPlus1 << 32) | zbits;
+    unsigned long long* slot = b.buckets + atBand;
+    if (v > __hip_atomic_load(slot + (size_t)b.layers * b.plane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;   // the pixel is full below this order
+    if (!surf_alpha_keeps<GLTF, LOD>(A, i, j, e0, e1, e2, area)) return;
+    for (uint32_t p = 0; p <= b.layers; p++, slot += b.plane) {
+        if (v > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) continue;
+        const unsigned long long old = atomicMin(slot, v);
+        if (old == SURF_BUCKET_EMPTY) return;
+        v = old > v ? old : v;
+    }
+}
+
+// what a draw kernel does with a fragment
+enum { SURF_DRAW_MASKED = 0, SURF_DRAW_PEEL = 1, SURF_DRAW_BUCKET = 2 };
+
+// the slices (gridDim.y) are k_surface_visibility's; without SAILOR_SURFACE_ALPHA_CUTOUT in draw.flags the keys are k_surface_visibility's.
+// X: what MODE needs beyond the workspace -- SurfPeel, or SurfBucket under SURF_DRAW_BUCKET (the workspace then only takes the draw's descriptor).
+template <bool GLTF, bool LOD = false, int MODE = SURF_DRAW_MASKED, typename X = SurfPeel>
 __device__ __forceinline__ void surf_visibility_masked(const Mat4& P, const Mat4& V, const SailorSurfaceDraw& draw, const float* __restrict__ instances,
                                                        const SailorMaterialData* __restrict__ materials, uint32_t numMaterials,
                                                        const SailorTextureDesc* __restrict__ textures, uint32_t numTextures, uint32_t drawIndex, int W, int H,
-                                                       int rowBegin, int rows, void* __restrict__ workspace, SurfPeel peel = SurfPeel())
+                                                       int rowBegin, int rows, void* __restrict__ workspace, X peel = X())
 {
+    constexpr bool PEEL = MODE == SURF_DRAW_PEEL;
     const SurfWorkspace ws = surf_workspace(workspace, (size_t)rows * W);
     const unsigned int slice = blockIdx.y, slices = gridDim.y;
     if (blockIdx.x == 0 && slice == 0 && threadIdx.x == 0) ws.draws[drawIndex] = draw; // the resolve finds the draw here
@@ -170,6 +214,8 @@ __device__ __forceinline__ void surf_visibility_masked(const Mat4& P, const Mat4
     // two more pairs the scalar file does not have.  The Standard peel keeps the compiler's allocation: 4 scalar spills to vector lanes at 168 registers, the
     // siblings' 3 waves per SIMD (pinned: none at 171, 2 waves).  The glTF peel has 2 waves either way (170 with the spills), so there they are pinned: 173, none.
     if constexpr (PEEL && GLTF) { SURF_KEEP_VECTOR(peel.depth); SURF_KEEP_VECTOR(peel.last); }
+    // The bucket draws keep the compiler's allocation in both: 15 scalar spills to vector lanes (none read inside the insertion's walk) at 168 registers and 3
+    // waves (Standard), 170 and 2 (glTF).  Pinning any of SurfBucket's words takes the Standard one to 170 or more, 2 waves; pinning all leaves 2 spills at 177 / 179.
     const float* __restrict__ vertices = reinterpret_cast<const float*>(draw.dVertices);
     const unsigned long long total = (unsigned long long)draw.numDrawn * draw.numTriangles;
     const unsigned long long id = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
@@ -208,7 +254,9 @@ __device__ __forceinline__ void surf_visibility_masked(const Mat4& P, const Mat4
         // the fill: the alpha words are the payload, carried to the wave once per large triangle
         surf_fill(t, orderPlus1, A, [](const SurfAlphaOf<LOD>& a, int src) { return surf_alpha_bcast<GLTF, LOD>(a, src); }, slice, slices, lane,
                   [&](int i, int j, float z, unsigned int tag, const SurfAlphaOf<LOD>& a, long long e0, long long e1, long long e2, float area) {
-                      if constexpr (PEEL) {
+                      if constexpr (MODE == SURF_DRAW_BUCKET) {
+                          surf_fragment_bucket<GLTF, LOD>(peel, (size_t)j * W + i, (size_t)(j - rowBegin) * W + i, i, j, z, tag, a, e0, e1, e2, area);
+                      } else if constexpr (PEEL) {
                           const size_t atBand = (size_t)(j - rowBegin) * W + i;
                           surf_fragment_peel<GLTF, LOD>(keys + atBand, peel, (size_t)j * W + i, atBand, i, j, z, tag, a, e0, e1, e2, area);
                       } else surf_fragment_masked<GLTF, LOD>(keys + (size_t)(j - rowBegin) * W + i, i, j, z, tag, a, e0, e1, e2, area);

@@ -15,7 +15,8 @@
 //   k_surface_blend                      a lane per pixel: the owning draw by the resolve's binary search, its blend mode, one load and one store of the target.
 //
 // A pass of L layers re-rasterises its draws L + 1 times (the last time only counts what is left): the price of reusing the resolve and the shade.
-#include "surface_masked_body.h"
+// (surface_buckets.hip is the route that rasterises once; it ends in the same resolve, shade and k_surface_blend.)
+#include "surface_transparent.h"
 
 __global__ __launch_bounds__(256) void k_surface_peel(Mat4 P, Mat4 V, SailorSurfaceDraw draw, const float* __restrict__ instances,
                                                       const SailorMaterialData* __restrict__ materials, uint32_t numMaterials,
@@ -24,7 +25,7 @@ __global__ __launch_bounds__(256) void k_surface_peel(Mat4 P, Mat4 V, SailorSurf
 {
     SurfPeel peel;
     peel.depth = depth; peel.last = last;
-    surf_visibility_masked<false, false, true>(P, V, draw, instances, materials, numMaterials, textures, numTextures, drawIndex, W, H, rowBegin, rows, workspace, peel);
+    surf_visibility_masked<false, false, SURF_DRAW_PEEL>(P, V, draw, instances, materials, numMaterials, textures, numTextures, drawIndex, W, H, rowBegin, rows, workspace, peel);
 }
 
 __global__ __launch_bounds__(256) void k_surface_peel_gltf(Mat4 P, Mat4 V, SailorSurfaceDraw draw, const float* __restrict__ instances,
@@ -35,7 +36,7 @@ __global__ __launch_bounds__(256) void k_surface_peel_gltf(Mat4 P, Mat4 V, Sailo
 {
     SurfPeel peel;
     peel.depth = depth; peel.last = last;
-    surf_visibility_masked<true, false, true>(P, V, draw, instances, materials, numMaterials, textures, numTextures, drawIndex, W, H, rowBegin, rows, workspace, peel);
+    surf_visibility_masked<true, false, SURF_DRAW_PEEL>(P, V, draw, instances, materials, numMaterials, textures, numTextures, drawIndex, W, H, rowBegin, rows, workspace, peel);
 }
 
 // A wave takes 64 texels of PEEL_COMMIT_ROWS rows one after the other and adds what it committed ONCE: every atomicAdd lands on one word, and a wave per
@@ -101,19 +102,12 @@ __global__ __launch_bounds__(256) void k_surface_blend(const float4* __restrict_
 }
 
 // ---- entry points ---------------------------------------------------------------------------------------------------------------------------------
-static const uint32_t PEEL_BLEND_BITS = SAILOR_SURFACE_BLEND_MASK << SAILOR_SURFACE_BLEND_SHIFT;
-
 // what the two peel draws check beyond surf_draw_prologue: why not, or NULL
 static const char* peel_planes_why(const float* dDepth, const uint32_t* dLast)
 {
     if (!aligned(dDepth, 4)) return "the depth attachment is NULL or not 4-byte aligned";
     if (!aligned(dLast, 4)) return "the last-order plane is NULL or not 4-byte aligned";
     return nullptr;
-}
-static int peel_refuse_multiply(SailorHipContext* ctx, const char* who)
-{
-    ctx->lastError = std::string(who) + ": EBlendMode::Multiply is not a blend of scene draws (VK_BLEND_OP_MULTIPLY_EXT)";
-    return SAILOR_HIP_ERR_UNSUPPORTED;
 }
 
 extern "C" {
@@ -140,7 +134,7 @@ int sailor_hip_surface_peel_draw(SailorHipContext* ctx, const SailorUboFrameData
                                           surf_tables_ok(dMaterials, numMaterials, dTextures, numTextures), drawIndex, width, height, band, dWorkspace, workspaceBytes, s))
         return st;
     if (const char* why = peel_planes_why(dDepth, dLast)) return surf_refuse(ctx, who, why);
-    if (((draw->flags >> SAILOR_SURFACE_BLEND_SHIFT) & SAILOR_SURFACE_BLEND_MASK) == SAILOR_SURFACE_BLEND_MULTIPLY) return peel_refuse_multiply(ctx, who);
+    if (peel_is_multiply(draw)) return peel_refuse_multiply(ctx, who);
     SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
     sailor_launch(ctx, k_surface_peel, s.grid, dim3(256), s.P, s.V, *draw, reinterpret_cast<const float*>(dInstances), dMaterials, numMaterials, dTextures, numTextures,
                   drawIndex, (int)width, (int)height, (int)band->fbRowBegin, (int)band->fbRowCount, dWorkspace, reinterpret_cast<const uint32_t*>(dDepth), dLast);
@@ -160,7 +154,7 @@ int sailor_hip_surface_peel_draw_gltf(SailorHipContext* ctx, const SailorUboFram
                                           workspaceBytes, s))
         return st;
     if (const char* why = peel_planes_why(dDepth, dLast)) return surf_refuse(ctx, who, why);
-    if (((draw->flags >> SAILOR_SURFACE_BLEND_SHIFT) & SAILOR_SURFACE_BLEND_MASK) == SAILOR_SURFACE_BLEND_MULTIPLY) return peel_refuse_multiply(ctx, who);
+    if (peel_is_multiply(draw)) return peel_refuse_multiply(ctx, who);
     SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
     sailor_launch(ctx, k_surface_peel_gltf, s.grid, dim3(256), s.P, s.V, *draw, reinterpret_cast<const float*>(dInstances), dMaterials, numMaterials, dTextures, numTextures,
                   drawIndex, (int)width, (int)height, (int)band->fbRowBegin, (int)band->fbRowCount, dWorkspace, reinterpret_cast<const uint32_t*>(dDepth), dLast);

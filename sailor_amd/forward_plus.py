@@ -1147,7 +1147,7 @@ class SurfacePass:
 
     def transparent(self, frame: UboFrameData, draws, instances: torch.Tensor, materials: torch.Tensor, textures: torch.Tensor, num_textures: int,
                     depth: torch.Tensor, shade, target: torch.Tensor, ao_in: torch.Tensor | None = None, layers: int | None = None, prim_base: int = 0,
-                    on_layer=None) -> torch.Tensor:
+                    on_layer=None, mode: str = "peel") -> torch.Tensor:
         """A RenderScene pass with `Tag: Transparent` (the Transparent section of include/sailor_hip.h): depth test against `depth` (the raw depth attachment of
         the WHOLE frame, float32 [H, W], read only), no depth write, every fragment blended onto `target` (float32 [rows, W, 4]) in primitive order.  The pass is
         peeled by primitive order, one layer at a time, and every layer rasterises the draws again.
@@ -1158,8 +1158,12 @@ class SurfacePass:
         layers=N records N layers and the overflow round, reads nothing back and returns the device counters, int32 [N + 1]: the pixels each layer committed and,
         last, the OVERFLOW -- the pixels that still had a fragment left.  layers=None is for tools and tests and SYNCHRONISES: it reads the committed count
         after each layer and stops at the first empty one (the counters returned end with that 0).
-        on_layer(k, surface, coverage, emissive | None, ao | None): called behind every resolve (a test's window into the layers)."""
+        on_layer(k, surface, coverage, emissive | None, ao | None): called behind every resolve (a test's window into the layers).
+        mode: "peel" (the default: the launches above) or "buckets" -- the draws run ONCE into per-pixel fragment buckets (sailor_hip_surface_bucket_*; self.buckets,
+        (layers + 1) x 8 bytes a pixel) and every layer is read out of them.  "buckets" requires layers=N, 1 .. 64; the counters, the target's bits and on_layer
+        are the peel's."""
         ctx, lib, dev = self.ctx, self.ctx._lib, self.ctx.device
+        assert mode in ("peel", "buckets") and (mode == "peel" or layers is not None), "mode='buckets' requires layers=N"
         assert depth.dtype == torch.float32 and depth.shape == (self.H, self.W) and depth.is_contiguous()
         assert target.dtype == torch.float32 and target.shape == (self.rows, self.W, 4) and target.is_contiguous()
         assert layers is None or layers >= 0
@@ -1206,6 +1210,22 @@ class SurfacePass:
             _lib.check(lib.sailor_hip_surface_blend(ctx.handle, _ptr(radiance), _ptr(surface), _ptr(emissive), ws, n, _ptr(target), self.W, self.H, C.byref(self.band)),
                        "sailor_hip_surface_blend", ctx.handle)
 
+        if mode == "buckets":
+            nb = lib.sailor_hip_surface_bucket_bytes(self.W, C.byref(self.band), layers)
+            self.buckets = torch.empty(nb // 8, dtype=torch.int64, device=dev)
+            store = (_ptr(self.buckets), nb, layers)
+            _lib.check(lib.sailor_hip_surface_bucket_begin(ctx.handle, self.W, self.H, C.byref(self.band), ws, n, *store), "sailor_hip_surface_bucket_begin", ctx.handle)
+            for index, d in enumerate(descs):
+                name = "sailor_hip_surface_bucket_draw_gltf" if d.flags & _lib.SURFACE_GLTF else "sailor_hip_surface_bucket_draw"
+                _lib.check(getattr(lib, name)(ctx.handle, C.byref(frame), C.byref(d), _ptr(instances), _ptr(materials), num_materials, _ptr(textures), num_textures, index,
+                                              self.W, self.H, C.byref(self.band), ws, n, _ptr(depth), *store), name, ctx.handle)
+            counts = torch.zeros(layers + 1, dtype=torch.int32, device=dev)
+            for k in range(layers + 1):
+                _lib.check(lib.sailor_hip_surface_bucket_layer(ctx.handle, self.W, self.H, C.byref(self.band), ws, n, *store, k, _ptr(counts[k:])),
+                           "sailor_hip_surface_bucket_layer", ctx.handle)
+                if k < layers:
+                    blend_layer(k)
+            return counts
         if layers is not None:
             counts = torch.zeros(layers + 1, dtype=torch.int32, device=dev)
             for k in range(layers):
@@ -1229,6 +1249,11 @@ class SurfacePass:
         self.ctx.synchronize()
         at, n = self.ctx._lib.sailor_hip_surface_keys_offset(), self.rows * self.W * 8
         return self.workspace[at: at + n].cpu().numpy().view(np.uint64).reshape(self.rows, self.W)
+
+    def download_buckets(self) -> np.ndarray:
+        """the store of the last transparent(mode="buckets") as uint64 [layers + 1, rows, W]: (order + 1) << 32 | depth bits, all ones where a slot is empty"""
+        self.ctx.synchronize()
+        return self.buckets.cpu().numpy().view(np.uint64).reshape(-1, self.rows, self.W)
 
 
 def masked_depth_prepass(sp: SurfacePass, frame: UboFrameData, depth: torch.Tensor, draws, instances: torch.Tensor, materials: torch.Tensor, textures: torch.Tensor,

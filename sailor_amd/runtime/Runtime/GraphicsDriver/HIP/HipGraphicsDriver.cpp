@@ -1144,7 +1144,8 @@ int HipGraphicsDriver::RecordSurfaceEnd(const TVector<RHIShaderBindingSetPtr>& b
     return sailor_hip_surface_store_depth(m_ctx, m_surfaceWorkspace->m_hip.m_devicePtr, bytes, (float*)depthToStore->m_buffer->m_hip.m_devicePtr, W, H, &band);
 }
 
-// The Transparent queue's pass (include/sailor_hip.h, the Transparent section): SurfacePass.transparent(layers = the budget) of forward_plus.py, launch for launch.
+// The Transparent queue's pass (include/sailor_hip.h, the Transparent section): SurfacePass.transparent(layers = the budget) of forward_plus.py, launch for launch,
+// in either mode (m_transparentMode: 0 = mode="peel", 1 = mode="buckets").
 int HipGraphicsDriver::RecordTransparentPass(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& color, const RHITexturePtr& depth,
                                              const TVector<RHICommandList::TransparentDraw>& draws)
 {
@@ -1185,13 +1186,17 @@ int HipGraphicsDriver::RecordTransparentPass(const TVector<RHIShaderBindingSetPt
     if (st != SAILOR_HIP_OK) return st;
     const size_t pixels = (size_t)W * H, bytes = pass.bytes;
     const uint32_t layers = m_transparentLayers;
+    const bool buckets = m_transparentMode == 1;
+    const size_t bucketBytes = buckets ? sailor_hip_surface_bucket_bytes(W, &pass.band, layers) : 0;
     if (!m_peelLast || m_peelLast->m_size != pixels * 4) m_peelLast = CreateBuffer(pixels * 4);
+    if (buckets && (!m_transparentBuckets || m_transparentBuckets->m_size != bucketBytes)) m_transparentBuckets = CreateBuffer(bucketBytes);
     if (!m_peelCounts || m_peelCounts->m_size != (TRANSPARENT_MAX_LAYERS + 1) * 4) m_peelCounts = CreateBuffer((TRANSPARENT_MAX_LAYERS + 1) * 4);
     if (!m_surfacePlanes || m_surfacePlanes->m_size != pixels * 48) m_surfacePlanes = CreateBuffer(pixels * 48);
     if (!m_surfaceRadiance || m_surfaceRadiance->m_size != pixels * 16) m_surfaceRadiance = CreateBuffer(pixels * 16);
     if (gltf && (!m_surfaceAo || m_surfaceAo->m_size != pixels * 4)) m_surfaceAo = CreateBuffer(pixels * 4);
     if (gltf && (!m_surfaceEmissive || m_surfaceEmissive->m_size != pixels * 16)) m_surfaceEmissive = CreateBuffer(pixels * 16);
-    if (!m_peelLast || !m_peelCounts || !m_surfacePlanes || !m_surfaceRadiance || (gltf && (!m_surfaceAo || !m_surfaceEmissive))) return SAILOR_HIP_ERR_OUT_OF_MEMORY;
+    if (!m_peelLast || !m_peelCounts || !m_surfacePlanes || !m_surfaceRadiance || (gltf && (!m_surfaceAo || !m_surfaceEmissive)) || (buckets && !m_transparentBuckets))
+        return SAILOR_HIP_ERR_OUT_OF_MEMORY;
     void* workspace = m_surfaceWorkspace->m_hip.m_devicePtr;
     uint32_t* last = (uint32_t*)m_peelLast->m_hip.m_devicePtr;
     uint32_t* counts = (uint32_t*)m_peelCounts->m_hip.m_devicePtr;
@@ -1201,7 +1206,18 @@ int HipGraphicsDriver::RecordTransparentPass(const TVector<RHIShaderBindingSetPt
     if (st != SAILOR_HIP_OK) return st;
     m_peelCountsLayers = layers;
     m_peelRecorded = true;
+    void* store = buckets ? m_transparentBuckets->m_hip.m_devicePtr : nullptr;
+    if (buckets) { // the draws, once
+        st = sailor_hip_surface_bucket_begin(m_ctx, W, H, &pass.band, workspace, bytes, store, bucketBytes, layers);
+        for (size_t i = 0; i < descs.size() && st == SAILOR_HIP_OK; i++)
+            st = (descs[i].flags & SAILOR_SURFACE_GLTF ? sailor_hip_surface_bucket_draw_gltf : sailor_hip_surface_bucket_draw)(
+                m_ctx, &pass.frame, &descs[i], dInstances, t.materials, t.numMaterials, t.textures, t.numTextures, (uint32_t)i, W, H, &pass.band, workspace, bytes, dDepth, store,
+                bucketBytes, layers);
+        if (st != SAILOR_HIP_OK) return st;
+    }
+    // layer k into the workspace and its pixels into counts[k]: read out of the buckets, or rasterised again
     auto peel = [&](uint32_t k) {
+        if (buckets) return sailor_hip_surface_bucket_layer(m_ctx, W, H, &pass.band, workspace, bytes, store, bucketBytes, layers, k, counts + k);
         int s = sailor_hip_surface_peel_begin(m_ctx, W, H, &pass.band, workspace, bytes, last, k == 0 ? 1 : 0);
         for (size_t i = 0; i < descs.size() && s == SAILOR_HIP_OK; i++)
             s = (descs[i].flags & SAILOR_SURFACE_GLTF ? sailor_hip_surface_peel_draw_gltf : sailor_hip_surface_peel_draw)(

@@ -216,12 +216,16 @@ private:
     // A RenderScene pass whose draws all have z-write off (the Transparent queue), recorded at EndRenderPass: m_transparentLayers times { peel_begin, every
     // draw, peel_commit, the resolve, the shade, the blend onto `color` } and one more { peel_begin, draws, peel_commit } whose count is the overflow.  The
     // depth attachment is read only.  Refused with the unsupported status, before anything is launched: a Multiply draw, a split frame.
+    // Under mode 1 (SetTransparentMode) the same pass through the per-pixel fragment buckets: bucket_begin, every draw ONCE, then per layer { bucket_layer, the
+    // resolve, the shade, the blend } and bucket_layer(budget) for the overflow.  The refusals come first and are common to both routes.
     int RecordTransparentPass(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& color, const RHI::RHITexturePtr& depth,
                               const TVector<RHI::RHICommandList::TransparentDraw>& draws);
 public:
     // the layer budget of a transparent pass (1 .. TRANSPARENT_MAX_LAYERS; default 4): false, and nothing changed, outside the range
     static constexpr uint32_t TRANSPARENT_MAX_LAYERS = 64;
     bool SetTransparentLayers(uint32_t layers) { if (layers < 1 || layers > TRANSPARENT_MAX_LAYERS) return false; m_transparentLayers = layers; return true; }
+    // the route of a transparent pass: 0 = the peel (default), 1 = the buckets; false, and nothing changed, for anything else
+    bool SetTransparentMode(int mode) { if (mode != 0 && mode != 1) return false; m_transparentMode = mode; return true; }
     // the overflow of the LAST recorded transparent pass: the pixels that still had a fragment behind the budget's layers (0 if no pass was recorded).  A host
     // read that waits for the stream: for the next frame's start, like sailor_hip_exchange_adapt's status -- it is never part of a recorded frame.
     int TransparentOverflow(uint32_t& outPixels);
@@ -291,7 +295,9 @@ private:
     bool m_surfaceBegun = false;
     // the transparent pass: the orders each pixel committed last, the layers' counters ([layer] committed pixels, [budget] the overflow) and the budget
     RHI::RHIBufferPtr m_peelLast, m_peelCounts;
+    RHI::RHIBufferPtr m_transparentBuckets; // mode 1: sailor_hip_surface_bucket_bytes of the frame under the current budget, (budget + 1) x 8 bytes a pixel
     uint32_t m_transparentLayers = 4, m_peelCountsLayers = 0;
+    int m_transparentMode = 0;
     bool m_peelRecorded = false;
     int32_t m_cullW = 0, m_cullH = 0, m_cullLights = 0; // geometry of the last light cull: locates its shading-order hint in the workspace
     bool m_cullOrderValid = false;

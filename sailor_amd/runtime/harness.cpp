@@ -510,6 +510,14 @@ RT_API int sailor_rt_set_transparent_layers(SailorRuntime* rt, int layers)
     return static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver())->SetTransparentLayers((uint32_t)layers) ? 0 : -1;
 }
 
+// the route of a transparent pass: 0 = peeled by primitive order (default), 1 = per-pixel fragment buckets, one rasterisation a pass and (budget + 1) x 8
+// bytes a pixel; the frame's bits and the overflow are the same.  -1, and nothing changed, for any other value
+RT_API int sailor_rt_set_transparent_mode(SailorRuntime* rt, int mode)
+{
+    if (!rt) return -1;
+    return static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver())->SetTransparentMode(mode) ? 0 : -1;
+}
+
 // the overflow of the last frame's transparent pass: the pixels that still had a fragment behind the budget's layers.  A host read that waits for the stream:
 // call it at the next frame's start (or after the frame), as sailor_hip_exchange_adapt's status is read; the recorded frame never reads it.  -1 on failure.
 RT_API long long sailor_rt_transparent_overflow(SailorRuntime* rt)

@@ -81,6 +81,7 @@ def load() -> C.CDLL:
         rt.sailor_rt_set_scene_shaders.argtypes = [P, P, C.c_int]
         rt.sailor_rt_set_scene_blend.argtypes = [P, P, P, C.c_int]
         rt.sailor_rt_set_transparent_layers.argtypes = [P, C.c_int]
+        rt.sailor_rt_set_transparent_mode.argtypes = [P, C.c_int]
         rt.sailor_rt_transparent_overflow.argtypes = [P]
         rt.sailor_rt_transparent_overflow.restype = C.c_longlong
         rt.sailor_rt_process_frame.argtypes = [P]
@@ -466,6 +467,10 @@ class Runtime:
     def set_transparent_layers(self, layers: int):
         """the layer budget of a transparent pass (default 4)"""
         _lib.check(self.rt.sailor_rt_set_transparent_layers(self.h, layers), "sailor_rt_set_transparent_layers")
+
+    def set_transparent_mode(self, mode: int):
+        """the route of a transparent pass: 0 = the peel (default), 1 = per-pixel fragment buckets (one rasterisation a pass, (budget + 1) x 8 bytes a pixel)"""
+        _lib.check(self.rt.sailor_rt_set_transparent_mode(self.h, mode), "sailor_rt_set_transparent_mode")
 
     def transparent_overflow(self) -> int:
         """the pixels that still had a fragment behind the budget's layers in the last frame's transparent pass.  SYNCHRONISES with the stream: read it after the
