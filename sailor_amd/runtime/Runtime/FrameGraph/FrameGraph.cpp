@@ -80,6 +80,9 @@ void RHIFrameGraph::Process(RHISceneViewSnapshot& snapshot)
     auto driver = Renderer::GetDriver();
     auto transferCmdList = driver->CreateCommandList();
     auto cmdList = driver->CreateCommandList();
+    const FrameCaptureHook capture = std::move(m_captureHook); // armed for this frame alone (RHIFrameGraph.h)
+    m_captureHook = nullptr;
+    if (capture) capture(transferCmdList, CaptureSlotFrameStart);
     m_prevFrameData = FillFrameData(transferCmdList, snapshot, m_prevFrameData, snapshot.m_deltaTime, snapshot.m_currentTime); // (:189)
     if (snapshot.m_rhiLightsData) { // RHIFrameGraph.cpp:128-163: the IBL samplers and the AO target join the lights set (bindings 3, 4, 5, 9)
         struct { const char* name; RHITexturePtr tex; uint32_t binding; } ibl[] = {
@@ -93,7 +96,12 @@ void RHIFrameGraph::Process(RHISceneViewSnapshot& snapshot)
         }
     }
     for (auto& node : m_graph) node->Prepare(this, snapshot);
-    for (auto& node : m_graph) node->Process(this, transferCmdList, cmdList, snapshot); // RHIFrameGraph.cpp:250-252
+    if (capture) capture(cmdList, CaptureSlotBeforeNodes);
+    int slot = CaptureSlotFirstNode;
+    for (auto& node : m_graph) {
+        node->Process(this, transferCmdList, cmdList, snapshot); // RHIFrameGraph.cpp:250-252
+        if (capture) capture(cmdList, slot++);
+    }
     driver->SubmitCommandList(transferCmdList);
     driver->SubmitCommandList(cmdList);
 }
@@ -104,6 +112,7 @@ void RHIFrameGraph::Clear()
     m_graph.clear();
     m_renderTargets.clear();
     m_prevFrameData = UboFrameData {}; // (a graph built next starts with a first frame)
+    m_captureHook = nullptr;
 }
 
 // ---- EnvironmentNode (FrameGraph/EnvironmentNode.cpp:19-281) --------------------------------------------------------------------

@@ -2,6 +2,7 @@
 // targets, FillFrameData (RHIFrameGraph.cpp:50-73) and the per-frame node walk (RHIFrameGraph.cpp:95,250-252).  The Vulkan-
 // specific barrier balancing (:201-246) and command-list chaining (:254-322) are out of scope.
 #pragma once
+#include <functional>
 #include <map>
 #include <set>
 #include <string>
@@ -51,6 +52,14 @@ public:
     }
     // One frame: FillFrameData, then node->Process in graph order, then submit (record-then-submit)
     void Process(RHI::RHISceneViewSnapshot& snapshot);
+    // Frame capture (a test facility, off by default): the hook is called while the NEXT Process() records, then dropped -- with the transfer list and
+    // CaptureSlotFrameStart before anything is recorded, with the main list and CaptureSlotBeforeNodes before node 0 (when it executes, the whole transfer
+    // list has: the work the nodes record there lies between these two slots), and with the main list and CaptureSlotFirstNode + i after node i's Process.
+    // What the hook records executes in that place of the frame.  Without a hook Process() records what it always did.
+    static constexpr int CaptureSlotFrameStart = 0, CaptureSlotBeforeNodes = 1, CaptureSlotFirstNode = 2;
+    using FrameCaptureHook = std::function<void(RHI::RHICommandListPtr cmdList, int slot)>;
+    void CaptureNextFrame(FrameCaptureHook hook) { m_captureHook = std::move(hook); }
+    bool IsCaptureArmed() const { return (bool)m_captureHook; }
     void Clear();
 
 private:
@@ -63,6 +72,7 @@ private:
     // RHIFrameGraph.h:72 `RHI::UboFrameData m_prevFrameData{}`: all zeros on a graph's first frame, afterwards what the last Process() uploaded as `frameData`
     // (RHIFrameGraph.cpp:189).  The reference builds a new RHIFrameGraph per `.renderer` file; here Clear() zeroes it with the graph.
     RHI::UboFrameData m_prevFrameData {};
+    FrameCaptureHook m_captureHook;
 };
 
 } // namespace Sailor::Framegraph

@@ -253,6 +253,42 @@ void HipGraphicsDriver::SubmitCommandList(RHICommandListPtr commandList)
     m_ownGrid = nullptr; m_ownCulled = nullptr;
 }
 
+// Frame capture (HipGraphicsDriver.h): reads only -- neither BeforeBufferWrite nor the cull's ownership of its SSBOs is touched, so the commands behind it
+// take the routes they would have taken.  m_packPending stays set: the submit's own join at its end is a second, harmless wait.
+void HipGraphicsDriver::RecordCapture(RHICommandListPtr cmd, void* storage, TVector<CaptureCopy> copies)
+{
+    SailorHipContext* ctx = m_ctx;
+    cmd->m_hip.m_commands.push_back([this, ctx, storage, copies = std::move(copies)]() {
+        if (!storage) return (int)SAILOR_HIP_ERR_INVALID_ARGUMENT;
+        if (m_packPending && m_ctxAux) { const int st = sailor_hip_context_wait_for(m_ctx, m_ctxAux); if (st != SAILOR_HIP_OK) return st; }
+        for (const auto& c : copies) {
+            if (c.m_bytes == 0) continue;
+            const int st = c.m_device ? sailor_hip_buffer_copy(ctx, storage, c.m_offset, c.m_device, 0, c.m_bytes)
+                                      : sailor_hip_buffer_upload(ctx, storage, c.m_offset, c.m_host.data(), c.m_bytes);
+            if (st != SAILOR_HIP_OK) return st;
+        }
+        return (int)SAILOR_HIP_OK;
+    });
+}
+
+int HipGraphicsDriver::IsStreamCapturing() const
+{
+    // hipStreamIsCapturing of the HIP runtime the C-ABI library is linked against (this library sees the device only through that C-ABI)
+    using Query = int (*)(void*, int*);
+    static const Query query = []() {
+        void* sym = dlsym(RTLD_DEFAULT, "hipStreamIsCapturing");
+        for (const char* name : { "libamdhip64.so", "libamdhip64.so.7", "libamdhip64.so.6", "libamdhip64.so.5" }) { // already mapped: found, never loaded
+            if (sym) break;
+            if (void* h = dlopen(name, RTLD_NOW | RTLD_NOLOAD)) sym = dlsym(h, "hipStreamIsCapturing");
+        }
+        return (Query)sym;
+    }();
+    void* stream = nullptr;
+    int status = 0; // hipStreamCaptureStatusNone
+    if (!query || !m_ctx || sailor_hip_context_stream(m_ctx, &stream) != SAILOR_HIP_OK || query(stream, &status) != 0) return -1;
+    return status != 0 ? 1 : 0;
+}
+
 // A command is about to WRITE this buffer: if it is one of the two SSBOs the last cull filled, the shade must read what the write leaves there, not the
 // cull's per-tile lists -- and the write must come behind the compaction that is still filling the buffer on the second queue.
 void HipGraphicsDriver::BeforeBufferWrite(const void* devicePtr)

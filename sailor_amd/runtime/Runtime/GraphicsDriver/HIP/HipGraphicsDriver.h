@@ -109,6 +109,15 @@ public:
     // (a PostProcess entry that must be created and record nothing); in the engine the backend would simply route both.  false for any other path.
     bool EnableShader(const std::string& assetPath);
     bool ReserveUiWorkspace(uint32_t numTriangles); // the UI pass' workspace, grown outside the submitted commands (see "Shaders/ImGuiUI.shader" above)
+
+    // Frame capture (a test facility; RHIFrameGraph::CaptureNextFrame): ONE recorded command that copies each source, as it is when the command executes,
+    // to storage + its offset, on the context's stream.  A device source is copied device to device; a host source (a uniform block's bytes) is taken when
+    // the command is RECORDED, as UpdateShaderBinding takes its payload, and uploaded when it executes.  If a light cull of this submit still has its
+    // compaction on the second queue, the stream waits for it first (the copy may be of lightsGrid / culledLights); what the frame's own commands do is unchanged.
+    struct CaptureCopy { const void* m_device = nullptr; TVector<uint8_t> m_host; size_t m_bytes = 0, m_offset = 0; };
+    void RecordCapture(RHI::RHICommandListPtr cmd, void* storage, TVector<CaptureCopy> copies);
+    // is the context's stream being captured into a hipGraph?  (-1: cannot tell -- the caller then refuses, as for 1)
+    int IsStreamCapturing() const;
     bool IsShaderEnabled(const std::string& assetPath) const { return m_enabledShaders.count(assetPath) != 0; }
 
     // IGraphicsDriver

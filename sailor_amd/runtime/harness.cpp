@@ -37,6 +37,8 @@ struct SailorRuntime {
     DebugContext debug; // the world's DebugContext (Engine/World.h): the snapshot points at it
     RHIImGuiDrawData ui; // the frame's ImDrawData and ImGuiApi's backend data: the snapshot points at it while there is draw data
     int frames = 0;
+    std::vector<long long> captureBytes; // sailor_rt_capture_next_frame: [slot][name] bytes copied, -1 absent, -2 larger than its capacity
+    int captureSlots = 0;
 };
 
 RT_API SailorRuntime* sailor_rt_create(int device, void* stream, int ownStream, int* outStatus)
@@ -1225,6 +1227,95 @@ RT_API int sailor_rt_csm_planner_frame(SailorCsmPlanner* planner, uint32_t numLi
         }
     }
     return (int)placed;
+}
+
+// ---- frame capture (a test facility, off by default): see the frame between its entries -------------------------------------------------------------------
+// A named resource as it is bound right now: a device range, or host bytes (a uniform block), or neither (absent).  Names: a render target or a published
+// sampler / cube of the graph (its whole buffer: every mip level, every face), "lightsGrid" / "culledLights" (the LightCulling node's SSBOs), "light" (the
+// lights SSBO), "lightsMatrices" (a host block on this backend), "csm0" .. "csm3" (the cascade maps), "eyeAdaptation" (the EyeAdaptation node's state: 256
+// counts and the adapted luminance), "indirect<i>" (the indirect commands of graph node i, 20 bytes each).
+static GraphicsDriver::HIP::HipGraphicsDriver::CaptureCopy capture_source(SailorRuntime* rt, const std::string& name)
+{
+    GraphicsDriver::HIP::HipGraphicsDriver::CaptureCopy c;
+    auto of_buffer = [&c](const RHIBufferPtr& b) { if (b && b->m_hip.m_devicePtr) { c.m_device = b->m_hip.m_devicePtr; c.m_bytes = b->m_size; } };
+    if (name == "lightsGrid" || name == "culledLights") {
+        auto node = rt->lightCulling.DynamicCast<LightCullingNode>();
+        auto b = node && node->GetCulledLights() ? node->GetCulledLights()->Find(name) : RHIShaderBindingPtr();
+        if (b) of_buffer(b->m_buffer);
+    } else if (name == "light" || name == "lightsMatrices") {
+        auto b = rt->lighting->GetLightsData() ? rt->lighting->GetLightsData()->Find(name) : RHIShaderBindingPtr();
+        if (b && b->m_buffer) of_buffer(b->m_buffer);
+        else if (b && !b->m_hostCopy.empty()) { c.m_host = b->m_hostCopy; c.m_bytes = c.m_host.size(); }
+    } else if (name.size() == 4 && name.rfind("csm", 0) == 0 && name[3] >= '0' && name[3] < '0' + SAILOR_NUM_CSM_CASCADES) {
+        const size_t k = (size_t)(name[3] - '0');
+        if (k < rt->lighting->GetCsmShadowMaps().size() && rt->lighting->GetCsmShadowMaps()[k]) of_buffer(rt->lighting->GetCsmShadowMaps()[k]->m_buffer);
+    } else if (name == "eyeAdaptation") {
+        for (const auto& n : rt->graph.GetGraph()) {
+            auto node = n.DynamicCast<EyeAdaptationNode>();
+            auto hist = node && node->GetHistogramBindings() ? node->GetHistogramBindings()->Find("histogram") : RHIShaderBindingPtr();
+            if (hist) { of_buffer(hist->m_buffer); break; }
+        }
+    } else if (name.rfind("indirect", 0) == 0 && name.size() > 8 && name.find_first_not_of("0123456789", 8) == std::string::npos) {
+        int commands = 0;
+        if (void* device = node_indirect_buffer(rt, atoi(name.c_str() + 8), &commands)) { c.m_device = device; c.m_bytes = (size_t)commands * sizeof(SailorDrawIndexedIndirectData); }
+    } else {
+        auto t = rt->graph.GetRenderTarget(name);
+        if (!t) t = rt->graph.GetSampler(name);
+        if (t) of_buffer(t->m_buffer);
+    }
+    return c;
+}
+
+// Arms a capture of the NEXT sailor_rt_process_frame: `names` (comma-separated, `count` of them) are resolved while that frame is recorded -- before the
+// transfer list (slot 0), before the first entry (slot 1: the whole transfer list has executed by then, which is where the nodes' transfer-list work shows)
+// and after each graph node i (slot 2 + i) -- and their bytes copied, in that place of the frame, to storage + slot * sum(capacities) + the capacities before
+// it.  A resource that does not exist at a slot (a cube before the frame that creates it) is absent there, not an error; one larger than its capacity is not
+// copied and reported.  Returns the number of slots (nodes + 2); -1 on a bad argument or too little storage; the unsupported status while the driver's stream
+// is being captured into a hipGraph.  Nothing is recorded, and nothing differs, in a frame that was not armed.
+RT_API int sailor_rt_capture_next_frame(SailorRuntime* rt, const char* names, const size_t* capacities, int count, void* storage, size_t storageBytes)
+{
+    if (!rt || !names || !capacities || count <= 0 || !storage) return -1;
+    auto* hip = static_cast<GraphicsDriver::HIP::HipGraphicsDriver*>(Renderer::GetDriver());
+    if (hip->IsStreamCapturing() != 0) return SAILOR_HIP_ERR_UNSUPPORTED; // fails closed: a stream whose capture status cannot be read is refused too
+    std::vector<std::string> list;
+    for (const char* p = names;;) {
+        const char* e = strchr(p, ',');
+        list.emplace_back(p, e ? (size_t)(e - p) : strlen(p));
+        if (!e) break;
+        p = e + 1;
+    }
+    if ((int)list.size() != count) return -1;
+    std::vector<size_t> offsets((size_t)count);
+    size_t stride = 0;
+    for (int k = 0; k < count; k++) { offsets[(size_t)k] = stride; stride += capacities[k]; }
+    const int slots = (int)rt->graph.GetGraph().size() + RHIFrameGraph::CaptureSlotFirstNode;
+    if (stride == 0 || storageBytes / stride < (size_t)slots) return -1;
+    std::vector<size_t> caps(capacities, capacities + count);
+    rt->captureSlots = slots;
+    rt->captureBytes.assign((size_t)slots * count, -1);
+    rt->graph.CaptureNextFrame([rt, hip, list, offsets, caps, stride, storage, slots](RHICommandListPtr cmd, int slot) {
+        if (slot < 0 || slot >= slots) return;
+        TVector<GraphicsDriver::HIP::HipGraphicsDriver::CaptureCopy> copies;
+        for (size_t k = 0; k < list.size(); k++) {
+            auto c = capture_source(rt, list[k]);
+            long long& bytes = rt->captureBytes[(size_t)slot * list.size() + k];
+            if (!c.m_device && c.m_host.empty()) { bytes = -1; continue; }
+            if (c.m_bytes > caps[k]) { bytes = -2; continue; }
+            bytes = (long long)c.m_bytes;
+            c.m_offset = (size_t)slot * stride + offsets[k];
+            copies.push_back(std::move(c));
+        }
+        hip->RecordCapture(cmd, storage, std::move(copies));
+    });
+    return slots;
+}
+
+// what the last armed frame recorded: [slot][name] = bytes copied, -1 absent, -2 larger than its capacity; returns slots x names (0 before any capture)
+RT_API int sailor_rt_capture_result(SailorRuntime* rt, long long* out, int maxEntries)
+{
+    if (!rt) return -1;
+    for (int i = 0; out && i < (int)rt->captureBytes.size() && i < maxEntries; i++) out[i] = rt->captureBytes[(size_t)i];
+    return (int)rt->captureBytes.size();
 }
 
 RT_API int sailor_rt_process_frame(SailorRuntime* rt)

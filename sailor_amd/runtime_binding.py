@@ -85,6 +85,8 @@ def load() -> C.CDLL:
         rt.sailor_rt_transparent_overflow.argtypes = [P]
         rt.sailor_rt_transparent_overflow.restype = C.c_longlong
         rt.sailor_rt_process_frame.argtypes = [P]
+        rt.sailor_rt_capture_next_frame.argtypes = [P, C.c_char_p, P, C.c_int, P, C.c_size_t]
+        rt.sailor_rt_capture_result.argtypes = [P, P, C.c_int]
         rt.sailor_rt_node_indirect_commands.argtypes = [P, C.c_int, P, C.c_int]
         rt.sailor_rt_draw_indexed_indirect.argtypes = [P, C.c_char_p, P, C.c_int, C.c_int]
         rt.sailor_rt_last_frame_regions.argtypes = [P, C.c_char_p, C.c_int]
@@ -641,6 +643,42 @@ class Runtime:
 
     def process_frame(self) -> int:
         return self.rt.sailor_rt_process_frame(self.h)
+
+    def capture_next_frame(self, capacities: dict, storage) -> int:
+        """Arm a capture of the next process_frame() (a test facility; off unless armed): `capacities` maps resource names -- a render target or published
+        sampler / cube of the graph, "lightsGrid", "culledLights", "light", "lightsMatrices", "csm0" .. "csm3", "eyeAdaptation", "indirect<node index>" -- to the
+        bytes reserved for each; `storage` is a contiguous uint8 device tensor of at least (nodes + 2) * sum(capacities) bytes that must outlive the frame.
+        Slot 0 is taken before the frame's transfer list, slot 1 before the first entry (after the whole transfer list), slot 2 + i after entry i.  Returns the
+        number of slots; raises while the stream is being captured into a hipGraph.  Read the frame with captured_frame() after wait_idle()."""
+        names = list(capacities)
+        assert names and all("," not in n for n in names) and storage.is_contiguous() and storage.element_size() == 1
+        caps = (C.c_size_t * len(names))(*[int(capacities[n]) for n in names])
+        slots = self.rt.sailor_rt_capture_next_frame(self.h, ",".join(names).encode(), caps, len(names), storage.data_ptr(), storage.numel())
+        if slots < 0:
+            raise _lib.SailorHipError(slots, "sailor_rt_capture_next_frame")
+        self._capture = (names, [int(capacities[n]) for n in names], storage, slots)
+        return slots
+
+    def captured_frame(self):
+        """the armed frame, after wait_idle(): one dict per slot, name -> uint8 device tensor (a view of the storage, as long as the resource was at that slot);
+        a resource absent at a slot is left out"""
+        names, caps, storage, slots = self._capture
+        table = np.full(slots * len(names), -1, np.int64)
+        n = self.rt.sailor_rt_capture_result(self.h, table.ctypes.data, table.size)
+        assert n == table.size, (n, table.size)
+        table = table.reshape(slots, len(names))
+        too_large = [names[k] for k in range(len(names)) if (table[:, k] == -2).any()]
+        if too_large:
+            raise ValueError(f"larger than the capacity given for them: {too_large}")
+        stride, out = sum(caps), []
+        for s in range(slots):
+            at, row = s * stride, {}
+            for k, name in enumerate(names):
+                if table[s, k] >= 0:
+                    row[name] = storage[at:at + int(table[s, k])]
+                at += caps[k]
+            out.append(row)
+        return out
 
     def process_frame_overwriting_lists(self, grid, culled) -> int:
         """one frame with an UpdateBuffer of lightsGrid / culledLights (numpy uint32 arrays or None) recorded between the LightCulling node and RenderScene"""
