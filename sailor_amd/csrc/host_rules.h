@@ -48,6 +48,17 @@ static inline const SailorBand* band_or_whole_frame(int32_t height, const Sailor
     return band_is_valid(height, band) ? band : nullptr;
 }
 
+// ---- the shade's plane addressing ----
+// The shade kernels address a pixel of the band's three surface planes and of the radiance plane by ONE 32-bit byte offset per lane on top of a scalar
+// base (shade_body.h: !WIDE).  That holds while the last byte of a plane of the band lies below 2^32 -- 16 bytes a pixel: fbRowCount x width <= 2^28 pixels --
+// and, as the planes' bases are derived one from the other in scalars, while the plane stride in bytes does too.  Anything larger takes the kernels with
+// 64-bit pixel indices.  (width, fbRowCount > 0)
+static inline bool shade_planes_fit_32_bits(size_t planeStridePixels, int32_t fbRowCount, int32_t width)
+{
+    const uint64_t limit = (uint64_t)1 << 28; // pixels of 16 bytes in 4 GB
+    return (uint64_t)planeStridePixels < limit && (uint64_t)fbRowCount * (uint64_t)width <= limit;
+}
+
 // ---- integer A / B knobs from the environment ----
 // Read once (`static const EnvKnob k = env_knob_read("NAME");` where it is used).  env_knob gives the value if it is set and inside [lo, hi], else -1:
 // the default holds, and a value that was set but lies outside says so in *lastError (when there is a message and somewhere to put it).

@@ -71,14 +71,14 @@ template <bool ON> __device__ __forceinline__ void sprof_mark_grid(const int i) 
 
 // Entry points: without shadow lookups in it the kernel fits 64 VGPRs, and the register allocator is told to stay there
 // (8 waves per SIMD); with the 16-tap PCF inlined it does not, and forcing it would spill.  The ambient term adds a third.
-#define SHADE_ENTRY(NAME, ATTR, CSM, IBL, PREP, TL)                                                                                                \
+#define SHADE_ENTRY(NAME, ATTR, CSM, IBL, PREP, TL, WIDE)                                                                                              \
     __global__ __launch_bounds__(256) ATTR void NAME(ShadeArgs A, CsmArgs C, IblArgs I, const float4* __restrict__ surface, size_t planeStride,    \
                                                      const SailorLightShaderData* __restrict__ lights, const SailorLightsGrid* __restrict__ grid, \
                                                      const uint32_t* __restrict__ culled, float4* __restrict__ radiance)                          \
     {                                                                                                                                              \
         __shared__ ShadeLds lds;                                                                                                                   \
         SPROF_TG(0, !(IBL))                                                                                                               \
-        k2_shade_body<CSM, IBL, ROLE_TILE, PREP, TL>(lds, A, C, I, surface, planeStride, lights, grid, culled, radiance);                          \
+        k2_shade_body<CSM, IBL, ROLE_TILE, PREP, TL, WIDE>(lds, A, C, I, surface, planeStride, lights, grid, culled, radiance);                    \
         SPROF_TG(3, !(IBL))                                                                                                               \
     }
 #define FORCE_64_VGPRS __attribute__((amdgpu_waves_per_eu(8, 8)))
@@ -88,17 +88,22 @@ template <bool ON> __device__ __forceinline__ void sprof_mark_grid(const int i) 
 #define FIVE_WAVES __attribute__((amdgpu_waves_per_eu(5, 5))) // (K3 + ambient: 88-91 registers by itself; its prepared twin 134 unpinned)
 // Four kernels (plain, K3, ambient, K3 + ambient) x the lights as 112-byte records or as sailor_hip_prepare_lights' staged records (_p: `lights` = the
 // staged array) x the lists in the reference's lightsGrid / culledLights or in the cull's per-tile slots (..t: `grid` = tileNum, `culled` = the slots)
-#define SHADE_ENTRIES(SUFFIX, PREP, TL)                                          \
-    SHADE_ENTRY(k2_shade##SUFFIX, FORCE_64_VGPRS, false, false, PREP, TL)         \
-    SHADE_ENTRY(k2_shade_csm##SUFFIX, CSM_PIN, true, false, PREP, TL)             \
-    SHADE_ENTRY(k2_shade_ibl##SUFFIX, , false, true, PREP, TL)                    \
-    SHADE_ENTRY(k2_shade_csm_ibl##SUFFIX, FIVE_WAVES, true, true, PREP, TL)
-SHADE_ENTRIES(, false, false)
-SHADE_ENTRIES(_p, true, false)
-SHADE_ENTRIES(_t, false, true)
-SHADE_ENTRIES(_pt, true, true)
+// x the planes addressed by a 32-bit byte offset per lane or (.._w: WIDE in shade_body.h, for planes of 4 GB and more) by 64-bit pixel indices
+#define SHADE_ENTRIES(SUFFIX, PREP, TL, WIDE)                                          \
+    SHADE_ENTRY(k2_shade##SUFFIX, FORCE_64_VGPRS, false, false, PREP, TL, WIDE)         \
+    SHADE_ENTRY(k2_shade_csm##SUFFIX, CSM_PIN, true, false, PREP, TL, WIDE)             \
+    SHADE_ENTRY(k2_shade_ibl##SUFFIX, , false, true, PREP, TL, WIDE)                    \
+    SHADE_ENTRY(k2_shade_csm_ibl##SUFFIX, FIVE_WAVES, true, true, PREP, TL, WIDE)
+SHADE_ENTRIES(, false, false, false)
+SHADE_ENTRIES(_p, true, false, false)
+SHADE_ENTRIES(_t, false, true, false)
+SHADE_ENTRIES(_pt, true, true, false)
+SHADE_ENTRIES(_w, false, false, true)
+SHADE_ENTRIES(_p_w, true, false, true)
+SHADE_ENTRIES(_t_w, false, true, true)
+SHADE_ENTRIES(_pt_w, true, true, true)
 
-template <bool PREP, bool TL, bool CSM>
+template <bool PREP, bool TL, bool CSM, bool WIDE>
 __device__ __forceinline__ void k2_shade_band_body(ShadeLds& lds, const ShadeArgs& A, const CsmArgs& C, int bandTiles, const float4* __restrict__ surface, size_t planeStride,
                                                    const SailorLightShaderData* __restrict__ lights, const SailorLightsGrid* __restrict__ grid,
                                                    const uint32_t* __restrict__ culled, float4* __restrict__ radiance)
@@ -110,7 +115,7 @@ __device__ __forceinline__ void k2_shade_band_body(ShadeLds& lds, const ShadeArg
         // C4 band's step)
         const int ty = CSM ? A.bandTileRows - 1 - tr : tr;
         SPROF_T(0)
-        k2_shade_body<CSM, false, ROLE_BAND_TILE, PREP, TL>(lds, A, C, IblArgs(), surface, planeStride, lights, grid, culled, radiance, t - tr * A.Tx, ty, 0);
+        k2_shade_body<CSM, false, ROLE_BAND_TILE, PREP, TL, WIDE>(lds, A, C, IblArgs(), surface, planeStride, lights, grid, culled, radiance, t - tr * A.Tx, ty, 0);
         SPROF_T(3)
         return;
     }
@@ -132,7 +137,7 @@ __device__ __forceinline__ void k2_shade_band_body(ShadeLds& lds, const ShadeArg
             todo &= todo - 1ull;
             const uint32_t item = base + l * (uint32_t)SPLIT_BLOCKS, tile = item >> 2;
             const uint32_t ty = tile / (uint32_t)A.Tx;
-            k2_shade_body<CSM, false, ROLE_BAND_SPLIT, PREP, TL>(lds, A, C, IblArgs(), surface, planeStride, lights, grid, culled, radiance, (int)(tile - ty * (uint32_t)A.Tx), (int)ty,
+            k2_shade_body<CSM, false, ROLE_BAND_SPLIT, PREP, TL, WIDE>(lds, A, C, IblArgs(), surface, planeStride, lights, grid, culled, radiance, (int)(tile - ty * (uint32_t)A.Tx), (int)ty,
                                                                (int)(item & 3u));
             __syncthreads(); // the LDS arrays are reused by the block's next tile
         }
@@ -140,18 +145,24 @@ __device__ __forceinline__ void k2_shade_band_body(ShadeLds& lds, const ShadeArg
     SPROF_T(3)
 }
 
-#define SHADE_BAND_ENTRY(NAME, PREP, TL, CSM, WAVES)                                                                                                                   \
+#define SHADE_BAND_ENTRY(NAME, PREP, TL, CSM, WAVES, WIDE)                                                                                                               \
     __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES)))                                                                                   \
     void NAME(ShadeArgs A, CsmArgs C, int bandTiles, const float4* __restrict__ surface, size_t planeStride, const SailorLightShaderData* __restrict__ lights,        \
               const SailorLightsGrid* __restrict__ grid, const uint32_t* __restrict__ culled, float4* __restrict__ radiance)                                         \
     {                                                                                                                                                                \
         __shared__ ShadeLds lds;                                                                                                                                     \
-        k2_shade_band_body<PREP, TL, CSM>(lds, A, C, bandTiles, surface, planeStride, lights, grid, culled, radiance);                                                   \
+        k2_shade_band_body<PREP, TL, CSM, WIDE>(lds, A, C, bandTiles, surface, planeStride, lights, grid, culled, radiance);                                             \
     }
-SHADE_BAND_ENTRY(k2_shade_band, false, false, false, 8)
-SHADE_BAND_ENTRY(k2_shade_band_p, true, false, false, 8)
-SHADE_BAND_ENTRY(k2_shade_band_t, false, true, false, 8)
-SHADE_BAND_ENTRY(k2_shade_band_pt, true, true, false, 8)
+#define SHADE_BAND_ENTRIES(K, CSM, WAVES)            \
+    SHADE_BAND_ENTRY(K, false, false, CSM, WAVES, false)      \
+    SHADE_BAND_ENTRY(K##_p, true, false, CSM, WAVES, false)   \
+    SHADE_BAND_ENTRY(K##_t, false, true, CSM, WAVES, false)   \
+    SHADE_BAND_ENTRY(K##_pt, true, true, CSM, WAVES, false)   \
+    SHADE_BAND_ENTRY(K##_w, false, false, CSM, WAVES, true)   \
+    SHADE_BAND_ENTRY(K##_p_w, true, false, CSM, WAVES, true)  \
+    SHADE_BAND_ENTRY(K##_t_w, false, true, CSM, WAVES, true)  \
+    SHADE_BAND_ENTRY(K##_pt_w, true, true, CSM, WAVES, true)
+SHADE_BAND_ENTRIES(k2_shade_band, false, 8)
 // (round 4: with shadow maps too -- a band of C4 was its longest tile: 63 us for 25 us of block-slot time, scripts/shade_prof_csm.py.  Two copies of the
 // K3 body do not fit 64 registers without scratch (4-5 spilled registers even with round 5's window look-ups).  Seven waves per SIMD = 72 registers, none
 // spilled, 94 scalar registers = seven blocks per CU by that file too; round 4's six (80) had more than the body needs: a quarter band of C4 94 -> 90 us,
@@ -159,10 +170,7 @@ SHADE_BAND_ENTRY(k2_shade_band_pt, true, true, false, 8)
 #ifndef BAND_CSM_WAVES
 #define BAND_CSM_WAVES 7
 #endif
-SHADE_BAND_ENTRY(k2_shade_band_csm, false, false, true, BAND_CSM_WAVES)
-SHADE_BAND_ENTRY(k2_shade_band_csm_p, true, false, true, BAND_CSM_WAVES)
-SHADE_BAND_ENTRY(k2_shade_band_csm_t, false, true, true, BAND_CSM_WAVES)
-SHADE_BAND_ENTRY(k2_shade_band_csm_pt, true, true, true, BAND_CSM_WAVES)
+SHADE_BAND_ENTRIES(k2_shade_band_csm, true, BAND_CSM_WAVES)
 
 // ---- sailor_hip_prepare_lights: the per-light half of the path, once per UPLOADED light instead of once per frame and list slot ----
 // One lane per light of [first, first + count): the cull's 20-byte view of it -- (worldPosition, bounds.x) as a float4 and the type, two dense
@@ -324,13 +332,14 @@ extern "C" int sailor_hip_compute_brdf_lut(SailorHipContext* ctx, float* dLut, i
     return SAILOR_HIP_OK;
 }
 
-// A kernel family = one kernel in its four variants, indexed (prepared lights ? 1 : 0) | (tile lists ? 2 : 0): plain, _p, _t, _pt.  `Third` is the argument
+// A kernel family = one kernel in its eight variants, indexed (prepared lights ? 1 : 0) | (tile lists ? 2 : 0) | (64-bit plane addressing ? 4 : 0): plain, _p, _t,
+// _pt, and the same four with _w behind them.  `Third` is the argument
 // the families differ in: IblArgs for the per-tile grid's kernels (SHADE_ENTRY), the band's tile count for the band form's (SHADE_BAND_ENTRY).
 template <typename Third> struct ShadeFamily {
-    void (*kernel[4])(ShadeArgs, CsmArgs, Third, const float4*, size_t, const SailorLightShaderData*, const SailorLightsGrid*, const uint32_t*, float4*);
-    const char* name[4]; // (the launched variant's name, for sailor_hip_context_launch_log)
+    void (*kernel[8])(ShadeArgs, CsmArgs, Third, const float4*, size_t, const SailorLightShaderData*, const SailorLightsGrid*, const uint32_t*, float4*);
+    const char* name[8]; // (the launched variant's name, for sailor_hip_context_launch_log)
 };
-#define SHADE_FAMILY(K) { { K, K##_p, K##_t, K##_pt }, { #K, #K "_p", #K "_t", #K "_pt" } }
+#define SHADE_FAMILY(K) { { K, K##_p, K##_t, K##_pt, K##_w, K##_p_w, K##_t_w, K##_pt_w }, { #K, #K "_p", #K "_t", #K "_pt", #K "_w", #K "_p_w", #K "_t_w", #K "_pt_w" } }
 static const ShadeFamily<IblArgs> shadeGridFamilies[4] = { SHADE_FAMILY(k2_shade), SHADE_FAMILY(k2_shade_csm), SHADE_FAMILY(k2_shade_ibl), SHADE_FAMILY(k2_shade_csm_ibl) }; // [csm | ibl << 1]
 static const ShadeFamily<int> shadeBandFamilies[2] = { SHADE_FAMILY(k2_shade_band), SHADE_FAMILY(k2_shade_band_csm) };                                                       // [csm]
 #undef SHADE_FAMILY
@@ -434,7 +443,12 @@ static int shade_impl(SailorHipContext* ctx, const SailorUboFrameData* frame, co
     // (the wave-slot reserve: 0 on the whole frame)
     const unsigned bandLds = (!partial || ibl) ? 0u : (bandLdsEnv >= 0 ? (unsigned)bandLdsEnv : (reserve ? (unsigned)SHADE_BAND_RESERVE : 0u));
     // ---- the kernel: its family (the band form has no ambient term: splitBand implies !ibl), then its variant ----
-    const int variant = (dPreparedLights ? 1 : 0) | (dTileNum ? 2 : 0);
+    // (the planes' addressing: 32-bit byte offsets wherever a plane of the band stays below 4 GB -- host_rules.h; SAILOR_SHADE_WIDE_ADDRESSING=1 takes the 64-bit
+    // kernels regardless: A / B, and the tests' way to the kernels that no frame of a test's size would pick)
+    const EnvKnob wideKnob = env_knob_read("SAILOR_SHADE_WIDE_ADDRESSING"); // (read at every call, unlike the knobs above: a test switches it inside one process)
+    const int wideEnv = env_knob(wideKnob, 0, 1, &ctx->lastError, "SAILOR_SHADE_WIDE_ADDRESSING is 0 or 1: ignored");
+    const bool wide = wideEnv == 1 || !shade_planes_fit_32_bits(surfacePlaneStride, band->fbRowCount, W);
+    const int variant = (dPreparedLights ? 1 : 0) | (dTileNum ? 2 : 0) | (wide ? 4 : 0);
     const char* kname = splitBand
         ? launch_shade(ctx, shadeBandFamilies[hasCsm ? 1 : 0], variant, dim3((unsigned)SPLIT_BLOCKS + (unsigned)bandTiles), bandLds, A, C, bandTiles, S, surfacePlaneStride, L, G,
                        dCulledLights, Rd)

@@ -360,6 +360,9 @@ __device__ __forceinline__ float dot3_pk(const v2f_ axy, const float az, const v
 #ifndef SHADE_XCD_PIECES
 #define SHADE_XCD_PIECES 10 // pieces of a tile row per XCD (see the grid mapping in k2_shade_body)
 #endif
+// Section marks for scripts/analysis/shade_instruction_budget.py: an assembler comment in the listing, no instruction.  (The listing is split by position:
+// what the scheduler moves across a mark is counted on the other side of it.)
+#define SHADE_SECTION(NAME) asm volatile("; SECTION " NAME)
 #define PENDK 4  // queued pairs per pixel in one window (their queue positions ride in one register, 7 bits each under a sentinel bit)
 #define QMAX 128 // queued pairs per wave in one window (two lights that reach every pixel fit; positions are 7 bits; 17.4 KB of LDS per block, 9 blocks per CU)
 typedef float v2f __attribute__((ext_vector_type(2)));
@@ -435,7 +438,7 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
 // with roughness 0), by hand: the wave is bound by instruction issue -- a scalar instruction costs what a vector one costs -- and the
 // compiler's version of this loop spends more instructions on getting around it than on the tests.  Per light: the conservative reach test on
 // rec0 (and rec1 for a cone), out if no pixel passes; the facing test on rec3, out if no pixel passes both; the two overflow checks (queue,
-// pairs per pixel), which end the window with the light still in `rest`; the append of (slot << 6 | lane) for the lanes that
+// pairs per pixel), which end the window with the light's bit still set in its segment; the append of (slot << 6 | lane) for the lanes that
 // passed, exec set to them.  Registers v56-v62 hold rec0 and rec1 / rec3 (inline assembly cannot name the parts of a register tuple, so the
 // tuples are fixed ones, and they double as the loop's temporaries); everything else is the compiler's choice.  Hazards (the compiler does
 // not look inside): a v_pk result is not read by the next instruction, a v_rsq result not by the next one either.  The arithmetic is instruction for instruction what the
@@ -456,10 +459,18 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
     "v_fmac_f32 v62, v56, v60\n\t"      /* (the dot product's last term in the wait state of the v_rsq result) */ \
     "v_mul_f32_e64 v62, -v62, v61\n\t" \
     "v_cmp_ngt_f32 vcc, v62, v59\n\t"
-#define SHADE_LIGHT_LOOP(H_LINE, LOADS, TEST) \
-    asm volatile("s_mov_b64 %[ex], exec\n" \
+// One segment (a light kind in a list half) of the window: SHADE_LIGHT_SEGMENT is the loop over the segment's mask `TODO`, IN PLACE -- a light's bit is cleared
+// once the light is dealt with, and the loop leaves on overflow (label 1, behind the last segment) with that light's bit still set: what the masks hold
+// afterwards is what the next window has to look at.  SHADE_LIGHT_LOOPS strings the four segments of the usual quadrant together in list order, in ONE
+// statement: an empty segment costs a compare and a branch, and one flag says whether the window overflowed.  (Was: a statement per segment, each on a copy of
+// its mask with a second mask for what is left -- zeroed in front of the loop, tested and copied back behind it -- and the compiler's control flow around
+// the six: 69 instructions a wave and window on the 4K frame where this takes about 20; scripts/analysis/shade_instruction_budget.py.)
+#define SHADE_LIGHT_SEGMENT(KIND, TODO, H_LINE, LOADS, TEST) \
+                 "s_cmp_lg_u64 %[" TODO "], 0\n\t" \
+                 "s_cbranch_scc0 3f\n" \
                  "0:\n\t" \
-                 "s_ff1_i32_b64 %[bit], %[todo]\n\t" \
+                 "; SECTION light_test_" KIND "\n\t" \
+                 "s_ff1_i32_b64 %[bit], %[" TODO "]\n\t" \
                  H_LINE \
                  "s_lshl2_add_u32 %[n], %[bit], %[bit]\n\t"        /* 5 bit */ \
                  "s_lshl4_add_u32 %[n], %[n], %[base]\n\t"         /* the record's LDS address: 80 bit + base (LREC * 16 = 80) */ \
@@ -471,6 +482,7 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
                  "v_sub_f32 v58, v58, %[wz]\n\t" \
                  TEST \
                  "s_cbranch_vccz 2f\n\t" \
+                 "; SECTION light_reach\n\t" \
                  "v_mov_b32 v60, %[n]\n\t" \
                  "ds_read_b96 v[60:62], v60 offset:48\n\t" \
                  "s_waitcnt lgkmcnt(0)\n\t" \
@@ -482,6 +494,7 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
                  "v_cmp_lt_f32_e64 %[m], 0, v60\n\t" \
                  "s_and_b64 vcc, %[m], vcc\n\t" \
                  "s_cbranch_scc0 2f\n\t" \
+                 "; SECTION light_append\n\t" \
                  "s_bcnt1_i32_b64 %[n], vcc\n\t" \
                  "s_add_i32 %[n], %[n], %[cnt]\n\t" \
                  "s_cmp_gt_u32 %[n], %[qmax]\n\t" \
@@ -500,14 +513,27 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
                  "s_mov_b64 exec, %[ex]\n\t" \
                  "s_mov_b32 %[cnt], %[n]\n" \
                  "2:\n\t" \
-                 "s_bitset0_b64 %[todo], %[bit]\n\t" \
-                 "s_cmp_lg_u64 %[todo], 0\n\t" \
-                 "s_cbranch_scc1 0b\n\t" \
-                 "s_branch 3f\n" \
+                 "; SECTION light_next\n\t" \
+                 "s_bitset0_b64 %[" TODO "], %[bit]\n\t" \
+                 "s_cmp_lg_u64 %[" TODO "], 0\n\t" \
+                 "s_cbranch_scc1 0b\n" \
+                 "3:\n\t" \
+                 "; SECTION window_control\n\t"
+#define SHADE_SECOND_HALF "s_or_b32 %[bit], %[bit], 64\n\t"
+#define SHADE_SPOT_LOADS "ds_read_b96 v[60:62], v62 offset:16\n\t"
+#define SHADE_LIGHT_LOOPS(P0, P1, S0, S1) \
+    asm volatile("s_mov_b64 %[ex], exec\n\t" \
+                 "s_mov_b32 %[ovf], 0\n\t" \
+                 SHADE_LIGHT_SEGMENT("point", "p0", "", "", SHADE_TEST_POINT) \
+                 SHADE_LIGHT_SEGMENT("point", "p1", SHADE_SECOND_HALF, "", SHADE_TEST_POINT) \
+                 SHADE_LIGHT_SEGMENT("spot", "s0", "", SHADE_SPOT_LOADS, SHADE_TEST_SPOT) \
+                 SHADE_LIGHT_SEGMENT("spot", "s1", SHADE_SECOND_HALF, SHADE_SPOT_LOADS, SHADE_TEST_SPOT) \
+                 "s_branch 4f\n" \
                  "1:\n\t" \
-                 "s_mov_b64 %[rest], %[todo]\n" \
-                 "3:" \
-                 : [todo] "+&s"(todo), [cnt] "+&s"(cnt), [pc] "+&v"(pc), [rest] "+&s"(rest), [bit] "=&s"(bit), [n] "=&s"(n), [m] "=&s"(m), [ex] "=&s"(ex) \
+                 "s_mov_b32 %[ovf], 1\n" \
+                 "4:" \
+                 : [p0] "+&s"(P0), [p1] "+&s"(P1), [s0] "+&s"(S0), [s1] "+&s"(S1), [cnt] "+&s"(cnt), [pc] "+&v"(pc), [ovf] "=&s"(ovf), [bit] "=&s"(bit), [n] "=&s"(n), \
+                   [m] "=&s"(m), [ex] "=&s"(ex) \
                  : [wxy] "v"(wxy), [wz] "v"(wz), [nx] "v"(nx), [ny] "v"(ny), [nz] "v"(nz), [q] "v"(qAddr), [base] "s"(sLAddr), \
                    [lim] "s"((1u << (7 * PENDK)) - 1u), [qmax] "n"(QMAX), [lane] "v"(lane) \
                  : "v56", "v57", "v58", "v59", "v60", "v61", "v62", "vcc", "scc", "memory")
@@ -530,7 +556,7 @@ struct ShadeLds {
     float4 sL[KEEP * LREC];
     float sRes[4 * 3 * QMAX]; // per wave: [3 colours][queue position]
     uint16_t sQ[4 * QMAX];
-    uint32_t sEnd[4];
+    uint32_t sEnd[4]; // ([0], [1]: see the staging; the other two keep the struct's size)
 };
 #define ROLE_TILE 0       // one block per tile, grid (tiles per row, tile rows)
 #define ROLE_BAND_TILE 1  // the same inside k2_shade_band: returns at once on a tile of the split blocks
@@ -548,7 +574,11 @@ struct ShadeLds {
 // of LDS of its own: no barrier, nobody's slowest quadrant to sit out -- fills 90 % of the slots (the gap shrinks to 0.8 us) but every wave then does the
 // list's loads and the compaction itself: wave life 7.44 us, kernel 140 against 135 us, and the frame pipeline's step 176 against 166 us because the next
 // frame's cull blocks no longer find four free slots beside it.  Oracle parity was green; profiles/r05/ab_quad_form.txt.)
-template <bool HAS_CSM, bool HAS_IBL, int ROLE = ROLE_TILE, bool PREPARED = false, bool TILE_LISTS = false>
+// WIDE: the planes are addressed with 64-bit per-lane pixel indices, as every kernel did up to round 6.  The kernels the host picks whenever a plane of the
+// band is below 4 GB (host_rules.h: shade_planes_fit_32_bits) are !WIDE: ONE 32-bit byte offset per lane and scalar plane bases -- the `saddr` form of the
+// global loads and of the store -- and, in a quadrant that lies wholly inside the frame, the tile's and the quadrant's origin folded into that scalar
+// base, so that the lane's part depends on its number and the frame's width alone: no per-lane compares, no 64-bit vector arithmetic.
+template <bool HAS_CSM, bool HAS_IBL, int ROLE = ROLE_TILE, bool PREPARED = false, bool TILE_LISTS = false, bool WIDE = false>
 __device__ __forceinline__ void k2_shade_body(ShadeLds& lds, const ShadeArgs& A, const CsmArgs& C, const IblArgs& I, const float4* __restrict__ surface, size_t planeStride,
                                                  const SailorLightShaderData* __restrict__ lights,
                                                  const SailorLightsGrid* __restrict__ grid, const uint32_t* __restrict__ culled,
@@ -561,6 +591,10 @@ __device__ __forceinline__ void k2_shade_body(ShadeLds& lds, const ShadeArgs& A,
     constexpr bool BAND = ROLE != ROLE_TILE;
     constexpr bool splitRole = ROLE == ROLE_BAND_SPLIT;
     int tid = threadIdx.x;
+    // (the arguments the prologue needs, asked for together: adjacent scalar loads merge into wide ones and wait once -- left to itself the compiler loads
+    // each where it is first used, one load and one wait a field)
+    if constexpr (!WIDE && ROLE == ROLE_TILE)
+        asm volatile("" :: "s"(surface), "s"(planeStride), "s"(lights), "s"(culled), "s"(A.fbRow0), "s"(A.fbRows), "s"(A.bandTileRows), "s"(A.lightsNum), "s"(A.camX), "s"(A.camY), "s"(A.camZ));
     // (the band kernel holds two copies of this body at 64 registers each, and the thread id -- live from the entry through both -- is what the
     // allocator spills: seven reloads from scratch in the prologue of every ordinary tile.  Put together again from the wave's number, a
     // scalar, and the lane's, two instructions, it need not live across anything.)
@@ -582,19 +616,50 @@ __device__ __forceinline__ void k2_shade_body(ShadeLds& lds, const ShadeArgs& A,
     constexpr unsigned rot = HAS_CSM ? 0u : 1u;
     int btx = ((int)((blockIdx.x - (unsigned)bty * rot) & 7u) + 8 * (int)blockIdx.y) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3);
     if (ROLE == ROLE_TILE && btx >= A.Tx) return;
-    const int lane = tid & 63, wave = tid >> 6;
+    const int lane = tid & 63;
+    // (the wave's number as a scalar: the quadrant's origin, the wave's LDS slots and its sEnd word are then scalar arithmetic)
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int quad = wave;
     if (BAND) { btx = selTx; bty = selTy; if (splitRole) quad = selQuad; }
     const int tx = btx, ty = A.tileRow0 + bty;
     const int bandTile = bty * A.Tx + btx;
     // each wave shades one 8x8 quadrant of the tile: the most compact 64-pixel footprint, so that "no pixel of the wave
     // is within reach of this light" holds as often as possible
-    const int gx = tx * TILE + (quad & 1) * 8 + (lane & 7);
-    const int gy = ty * TILE + (quad >> 1) * 8 + (lane >> 3);
-    const int py = A.H - 1 - gy;            // framebuffer row (Standard.shader:414: screenUv.y = H - fragY)
-    const unsigned long long activeMask = __ballot(gx < A.W) & __ballot(py >= 0); // (masks of single compares, the per-lane flag from the mask: a ballot of `a && b`, or a flag kept as a bool, costs a VGPR 0 / 1 and a compare per use)
+    // framebuffer row py = H - 1 - gy (Standard.shader:414: screenUv.y = H - fragY)
+    unsigned long long activeMask; // (masks of single compares, the per-lane flag from the mask: a ballot of `a && b`, or a flag kept as a bool, costs a VGPR 0 / 1 and a compare per use)
+    size_t pix = 0;        // WIDE: the lane's pixel index in a plane of the band
+    uint32_t pixBase = 0u; // !WIDE: the scalar part of that index (the quadrant's lowest-addressed pixel, or 0) ...
+    uint32_t voff = 0u;    // ... and the lane's part in bytes
+    // (the lane's part in a whole quadrant: offsets count up from the quadrant's lowest address -- its LAST pixel row, lane >> 3 == 7, first column)
+    auto whole_offset = [&](const uint32_t l) { const uint32_t t = l ^ 56u; return (__umul24(t >> 3, (uint32_t)A.W) + (t & 7u)) << 4; };
+    auto ragged_offset = [&](const int l, const bool act) {
+        const int gx = tx * TILE + (quad & 1) * 8 + (l & 7), py = A.H - 1 - (ty * TILE + (quad >> 1) * 8 + (l >> 3));
+        return act ? ((uint32_t)(py - A.fbRow0) * (uint32_t)A.W + (uint32_t)gx) << 4 : 0u;
+    };
+    bool wholeQuad = false;
+    if constexpr (WIDE) {
+        const int gx = tx * TILE + (quad & 1) * 8 + (lane & 7);
+        const int gy = ty * TILE + (quad >> 1) * 8 + (lane >> 3);
+        const int py = A.H - 1 - gy;
+        activeMask = __ballot(gx < A.W) & __ballot(py >= 0);
+        pix = __builtin_amdgcn_inverse_ballot_w64(activeMask) ? ((size_t)(py - A.fbRow0) * A.W + gx) : 0;
+    } else {
+        // whole: the quadrant's last column is inside the frame and so is its last row (its rows are the band's by construction: host_rules.h, band_from_rows)
+        const int qx = tx * TILE + (quad & 1) * 8, rowLast = A.H - 1 - (ty * TILE + (quad >> 1) * 8 + 7);
+        wholeQuad = ((A.W - 8 - qx) | rowLast) >= 0; // (both non-negative: one compare)
+        if (wholeQuad) {
+            SHADE_SECTION("entry");
+            activeMask = ~0ull;
+            pixBase = (uint32_t)(rowLast - A.fbRow0) * (uint32_t)A.W + (uint32_t)qx;
+            voff = whole_offset((uint32_t)lane);
+        } else {
+            SHADE_SECTION("entry_ragged");
+            activeMask = __ballot(qx + (lane & 7) < A.W) & __ballot(rowLast + 7 - (lane >> 3) >= 0);
+            voff = ragged_offset(lane, __builtin_amdgcn_inverse_ballot_w64(activeMask));
+        }
+    }
+    SHADE_SECTION("entry");
     const bool active = __builtin_amdgcn_inverse_ballot_w64(activeMask);
-    const size_t pix = active ? ((size_t)(py - A.fbRow0) * A.W + gx) : 0;
 
     // Prologue, ordered by what waits for what.  The list is a chain of three dependent round trips (grid entry -> culledLights indices -> light
     // records), the surface is one; a wave that sits through them one after the other spends a third of its life waiting.  So: the grid entry
@@ -608,9 +673,16 @@ __device__ __forceinline__ void k2_shade_body(ShadeLds& lds, const ShadeArgs& A,
     // (streamed once: non-temporal, so that what every tile reads again -- lists, light records, the next frame's depth and masks -- keeps its
     // place in L2)
 #define NT_LOAD4(P) make_float4(__builtin_nontemporal_load(&(P).x), __builtin_nontemporal_load(&(P).y), __builtin_nontemporal_load(&(P).z), __builtin_nontemporal_load(&(P).w))
-    const float4 P0 = NT_LOAD4(surface[pix]);
-    const float4 P1 = NT_LOAD4(surface[planeStride + pix]);
-    const float4 P2 = NT_LOAD4(surface[2 * planeStride + pix]);
+    // (!WIDE: a wave-uniform base plus the zero-extended 32-bit offset -- the addressing mode with a scalar base register pair)
+    // (the planes' bases one from the other: a shift and three 64-bit scalar additions in all)
+    const float4* const plane0 = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(surface) + (pixBase << 4)); // (below 2^32: the host's choice of this form)
+    const float4* const plane1 = plane0 + planeStride;
+    const float4* const plane2 = plane1 + planeStride;
+#define PLANE_PIXEL(BASE) (*reinterpret_cast<const float4*>(reinterpret_cast<const char*>(BASE) + voff))
+    const float4 P0 = WIDE ? NT_LOAD4(surface[pix]) : NT_LOAD4(PLANE_PIXEL(plane0));
+    const float4 P1 = WIDE ? NT_LOAD4(surface[planeStride + pix]) : NT_LOAD4(PLANE_PIXEL(plane1));
+    const float4 P2 = WIDE ? NT_LOAD4(surface[2 * planeStride + pix]) : NT_LOAD4(PLANE_PIXEL(plane2));
+#undef PLANE_PIXEL
 #undef NT_LOAD4
     if (ROLE == ROLE_BAND_TILE && g.num >= (uint32_t)A.splitMin) return; // a tile of the split blocks
     const uint32_t listNum = g.num < (uint32_t)KEEP ? g.num : (uint32_t)KEEP;
@@ -669,9 +741,19 @@ __device__ __forceinline__ void k2_shade_body(ShadeLds& lds, const ShadeArgs& A,
     };
     constexpr bool K3_FIRST = HAS_CSM && !HAS_IBL; // (the ambient term keeps the view and material terms live to the very end: with them the K3 + IBL kernels need 91 registers one way, 136 the other)
     if constexpr (!K3_FIRST) view_and_material(A.camX, A.camY, A.camZ, 1.0f);
-    {
+    // Where the list ends early: the first slot with an index that is no light's.  Only waves 0 and 1 hold list slots (128 = two waves' lanes), so only they
+    // say so -- one word each, all in scalars (the first set bit of an empty mask is -1: "nowhere", and stays -1 under the wave's 64), written by lane 0 with
+    // the exec mask set by hand: as `if (lane == 0)` it is a compare, a saveexec and a branch.  Every lane is live here, so exec goes back to all ones.
+    if (wave < 2) {
         const unsigned long long bad = haveMask & ~stagedMask;
-        if (lane == 0) sEnd[wave] = bad ? (uint32_t)(wave * 64 + __builtin_ctzll(bad)) : 0xFFFFFFFFu;
+        uint32_t first;
+        asm("s_ff1_i32_b64 %0, %1" : "=s"(first) : "s"(bad));
+        first |= (uint32_t)wave << 6;
+        const uint32_t endAddr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)sEnd + 4u * (uint32_t)wave;
+        asm volatile("s_mov_b64 exec, 1\n\t"
+                     "ds_write_b32 %[a], %[v]\n\t"
+                     "s_mov_b64 exec, -1"
+                     :: [a] "v"(endAddr), [v] "v"(first) : "memory");
     }
     if (staged) {
         // (staging is the block's critical path -- the other three waves wait at the barrier for the first; with PREPARED records it is a copy)
@@ -684,7 +766,8 @@ __device__ __forceinline__ void k2_shade_body(ShadeLds& lds, const ShadeArgs& A,
         }
     }
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); // the records are in LDS (global loads may stay in flight)
-    const uint32_t numLights = min(min(listNum, sEnd[0]), min(sEnd[1], min(sEnd[2], sEnd[3])));
+    SHADE_SECTION("setup");
+    const uint32_t numLights = min(listNum, min(sEnd[0], sEnd[1]));
     const float alpha = roughness * roughness, alphaSq = alpha * alpha;
 
     // ---- which lights can reach this quadrant at all?  One LANE per LIGHT against the bounding SPHERE of the quadrant's 64 surface
@@ -709,6 +792,7 @@ __device__ __forceinline__ void k2_shade_body(ShadeLds& lds, const ShadeArgs& A,
 #pragma unroll
     for (int h = 0; h < 2; h++) {
         if ((uint32_t)(h * 64) >= numLights) break;
+        if (h == 0) SHADE_SECTION("lane_pass_0"); else SHADE_SECTION("lane_pass_1");
         // (every condition as a wave mask of ONE simple compare, the combinations as scalar mask arithmetic: a bool that is assigned in branches
         // lives in a VGPR as 0 / 1 and costs a v_cndmask + v_cmp per use)
         const uint32_t li = (uint32_t)(h * 64 + lane);
@@ -741,6 +825,7 @@ __device__ __forceinline__ void k2_shade_body(ShadeLds& lds, const ShadeArgs& A,
         seg[4 + h] = all & ~(seg[h] | seg[2 + h] | seg[6 + h]);
     }
 
+    SHADE_SECTION("setup");
     if (BAND && splitRole) { // this wave's share of the list: every fourth slot
         const unsigned long long share = 0x1111111111111111ull << __builtin_amdgcn_readfirstlane(wave); // (scalar: the masks stay in SGPRs)
 #pragma unroll
@@ -815,9 +900,10 @@ __device__ __forceinline__ void k2_shade_body(ShadeLds& lds, const ShadeArgs& A,
     uint16_t* Q = sQ + wave * QMAX;
     const uint32_t qAddr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint16_t*)Q; // its LDS byte address, for the hand-written append below
     const uint32_t sLAddr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float4*)sL;
-    static_assert(LREC == 5, "SHADE_LIGHT_LOOP computes 80 x slot as (5 x slot) << 4");
+    static_assert(LREC == 5, "SHADE_LIGHT_SEGMENT computes 80 x slot as (5 x slot) << 4");
     float* res = sRes + wave * (3 * QMAX); // this wave's [3 colours][QMAX queue positions] slots
     for (;;) {
+        SHADE_SECTION("window_control");
         uint32_t cnt = 0u;      // queued pairs (wave-uniform)
         uint32_t pc = 1u;       // the queue positions of this pixel's pairs: 1 (sentinel), then 7 bits per pair, the first one queued on top
         // The wave is bound by instruction issue of every kind (a scalar instruction costs what a vector one costs: measured), and the loop
@@ -826,23 +912,23 @@ __device__ __forceinline__ void k2_shade_body(ShadeLds& lds, const ShadeArgs& A,
         auto light_loop = [&](auto plainTag, auto kindTag, auto hTag) -> bool {
             constexpr bool PLAIN = decltype(plainTag)::value;
             constexpr int kind = decltype(kindTag)::value, h = decltype(hTag)::value;
-            unsigned long long todo = seg[kind * 2 + h];
-            unsigned long long rest = 0ull; // on overflow: what is left, this light included
+            if constexpr (PLAIN) SHADE_SECTION("window_control"); else SHADE_SECTION("window_general");
             if constexpr (PLAIN && kind < 2) {
-                // The usual case by hand (see SHADE_LIGHT_LOOP above): the same tests, the same append, 15 instructions around a light out of
+                // The usual case by hand (see SHADE_LIGHT_SEGMENT above): the same tests, the same append, 15 instructions around a light out of
                 // reach where the compiler's control flow takes 21.
-                if (todo != 0ull) {
-                    uint32_t bit, n;
-                    unsigned long long m, ex;
-                    if constexpr (kind == 0 && h == 0) SHADE_LIGHT_LOOP("", "", SHADE_TEST_POINT);
-                    if constexpr (kind == 0 && h == 1) SHADE_LIGHT_LOOP("s_or_b32 %[bit], %[bit], 64\n\t", "", SHADE_TEST_POINT);
-                    if constexpr (kind == 1 && h == 0) SHADE_LIGHT_LOOP("", "ds_read_b96 v[60:62], v62 offset:16\n\t", SHADE_TEST_SPOT);
-                    if constexpr (kind == 1 && h == 1) SHADE_LIGHT_LOOP("s_or_b32 %[bit], %[bit], 64\n\t", "ds_read_b96 v[60:62], v62 offset:16\n\t", SHADE_TEST_SPOT);
-                }
+                // (SHADE_LIGHT_LOOPS above: the four segments in one statement, on the masks in place)
+                uint32_t bit, n, ovf;
+                unsigned long long m, ex;
+                static_assert(kind == 0 && h == 0, "the statement covers both list halves of both kinds: called once, as (point, first half)");
+                SHADE_LIGHT_LOOPS(seg[0], seg[1], seg[2], seg[3]);
+                return ovf != 0u;
             } else {
+                unsigned long long todo = seg[kind * 2 + h];
+                unsigned long long rest = 0ull; // on overflow: what is left, this light included
                 // (one way out of the loop, through its condition: with a `break` in the middle the loop is no single-exit region of its own, falls
                 // into the region of the divergent pair pass below and is structurised along with it -- see the append)
                 while (todo) {
+                    SHADE_SECTION("light_general");
                     const int bit = __builtin_ctzll(todo);
                     const uint32_t s = (uint32_t)(h * 64 + bit);
                     unsigned long long m = activeMask; // "the rest": every pixel is a pair
@@ -891,16 +977,24 @@ __device__ __forceinline__ void k2_shade_body(ShadeLds& lds, const ShadeArgs& A,
                     }
                     asm("s_bitset0_b64 %0, %1" : "+s"(todo) : "s"(bit)); // todo &= todo - 1 in one scalar instruction instead of three
                 }
+                if constexpr (PLAIN) SHADE_SECTION("window_control"); else SHADE_SECTION("window_general");
+                seg[kind * 2 + h] = rest; // what the next window still has to look at
+                return rest != 0ull;
             }
-            seg[kind * 2 + h] = rest; // what the next window still has to look at
-            return rest != 0ull;
         };
         auto fill_window = [&](auto plainTag) -> bool {
             using K0 = std::integral_constant<int, 0>; using K1 = std::integral_constant<int, 1>; using K2 = std::integral_constant<int, 2>;
-            return light_loop(plainTag, K0{}, K0{}) || light_loop(plainTag, K0{}, K1{}) || light_loop(plainTag, K1{}, K0{}) || light_loop(plainTag, K1{}, K1{}) ||
-                   light_loop(plainTag, K2{}, K0{}) || light_loop(plainTag, K2{}, K1{});
+            if constexpr (decltype(plainTag)::value) {
+                if (__builtin_expect(light_loop(plainTag, K0{}, K0{}), 0)) return true; // (point and spot lights, both list halves)
+                if (__builtin_expect((seg[4] | seg[5]) == 0ull, 1)) return false;
+                return light_loop(plainTag, K2{}, K0{}) || light_loop(plainTag, K2{}, K1{});
+            } else
+                return light_loop(plainTag, K0{}, K0{}) || light_loop(plainTag, K0{}, K1{}) || light_loop(plainTag, K1{}, K0{}) || light_loop(plainTag, K1{}, K1{}) ||
+                       light_loop(plainTag, K2{}, K0{}) || light_loop(plainTag, K2{}, K1{});
         };
-        const bool overflow = (forceMask == 0ull && activeMask == ~0ull) ? fill_window(std::true_type{}) : fill_window(std::false_type{});
+        SHADE_SECTION("window_control");
+        const bool overflow = __builtin_expect(forceMask == 0ull && activeMask == ~0ull, 1) ? fill_window(std::true_type{}) : fill_window(std::false_type{});
+        SHADE_SECTION("window_control");
         if (cnt == 0u) break;
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         for (uint32_t base = 0u; base < cnt; base += 64u) {
@@ -909,6 +1003,7 @@ __device__ __forceinline__ void k2_shade_body(ShadeLds& lds, const ShadeArgs& A,
             // (the lanes past the last pair repeat the batch's FIRST pair and store the result in their own slot, which no pixel looks at: every
             // lane runs the same straight code -- no `if (valid)` around the three stretches of arithmetic, which was 13 instructions of
             // exec-mask bookkeeping and zero-initialisation per batch)
+            SHADE_SECTION("pair_pass");
             const uint32_t qi = base + (uint32_t)lane;
             const uint32_t e = Q[qi < cnt ? qi : base];
             constexpr bool valid = true;
@@ -980,12 +1075,14 @@ __device__ __forceinline__ void k2_shade_body(ShadeLds& lds, const ShadeArgs& A,
 #undef PULL
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        SHADE_SECTION("sum_up");
         // each pixel adds up the results of its own pairs, in the order they were queued (the position list shifted up against the sentinel:
         // the first pair's position then sits in bits 30..24, the next one in 23..17, ...)
         const uint32_t pcTop = pc << __builtin_clz(pc);
 #pragma unroll
         for (uint32_t j = 0; j < (uint32_t)PENDK; j++) {
             if (__ballot(pc >= (1u << (7u * (j + 1u)))) == 0ull) break;
+            SHADE_SECTION("sum_round");
             if (pc >= (1u << (7u * (j + 1u)))) {
                 const float* r = res + ((pcTop >> (24u - 7u * j)) & 127u);
                 accX += r[0];
@@ -993,11 +1090,14 @@ __device__ __forceinline__ void k2_shade_body(ShadeLds& lds, const ShadeArgs& A,
                 accZ += r[2 * QMAX];
             }
         }
+        SHADE_SECTION("window_control");
         if (!overflow) break;
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     }
+    SHADE_SECTION("directional");
     if constexpr (!K3_FIRST) {
         if ((seg[6] | seg[7]) != 0ull) {
+            SHADE_SECTION("directional_light");
 #pragma unroll
             for (int h = 0; h < 2; h++) {
                 unsigned long long todo = seg[6 + h];
@@ -1009,6 +1109,7 @@ __device__ __forceinline__ void k2_shade_body(ShadeLds& lds, const ShadeArgs& A,
             }
         }
     }
+    SHADE_SECTION("epilogue");
     if (BAND && splitRole) { // the four partial sums of each pixel: wave 0 + 1 + 2 + 3
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         res[lane] = accX; res[64 + lane] = accY; res[128 + lane] = accZ; // (in the wave's own slots: another wave may still be reading its own)
@@ -1053,7 +1154,7 @@ __device__ __forceinline__ void k2_shade_body(ShadeLds& lds, const ShadeArgs& A,
             ambX = fmaf(sx * f, b.x, ambX); ambY = fmaf(sy * f, b.y, ambY); ambZ = fmaf(sz * f, b.z, ambZ);
         }
         __builtin_amdgcn_sched_barrier(0);
-        const float ao = I.ao ? I.ao[pix] : 1.0f;                                                                     // :386
+        const float ao = I.ao ? (WIDE ? I.ao[pix] : *reinterpret_cast<const float*>(reinterpret_cast<const char*>(I.ao + pixBase) + (voff >> 2))) : 1.0f;                                                                     // :386
         accX = fmaf(ambX, ao, accX); accY = fmaf(ambY, ao, accY); accZ = fmaf(ambZ, ao, accZ);                              // :371, :425 ambient + sum over lights
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -1062,10 +1163,17 @@ __device__ __forceinline__ void k2_shade_body(ShadeLds& lds, const ShadeArgs& A,
         // the prologue to here they are two registers live across the whole kernel, which at 64 registers and no scratch is two too many for the K3 kernels)
         int lane2 = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
         asm volatile("" : "+v"(lane2));
-        const int quadS = __builtin_amdgcn_readfirstlane(quad);
-        const int gx2 = tx * TILE + (quadS & 1) * 8 + (lane2 & 7);
-        const int py2 = A.H - 1 - (ty * TILE + (quadS >> 1) * 8 + (lane2 >> 3));
-        float4* o = radiance + ((size_t)(py2 - A.fbRow0) * A.W + gx2);
+        float4* o;
+        if constexpr (WIDE) {
+            const int quadS = __builtin_amdgcn_readfirstlane(quad);
+            const int gx2 = tx * TILE + (quadS & 1) * 8 + (lane2 & 7);
+            const int py2 = A.H - 1 - (ty * TILE + (quadS >> 1) * 8 + (lane2 >> 3));
+            o = radiance + ((size_t)(py2 - A.fbRow0) * A.W + gx2);
+        } else {
+            // (the same offset as the loads': in a whole quadrant five instructions on the lane's number)
+            const uint32_t voff2 = HAS_CSM ? (wholeQuad ? whole_offset((uint32_t)lane2) : ragged_offset(lane2, true)) : voff;
+            o = reinterpret_cast<float4*>(reinterpret_cast<char*>(radiance) + (pixBase << 4) + voff2);
+        }
         __builtin_nontemporal_store(accX, &o->x); __builtin_nontemporal_store(accY, &o->y);
         __builtin_nontemporal_store(accZ, &o->z); __builtin_nontemporal_store(P0.w, &o->w);
     }
