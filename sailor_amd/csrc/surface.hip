@@ -8,7 +8,8 @@
 //                         not rule out one lane per texel.  A fragment READS the pixel's key and issues the 64-bit atomicMax only if its own is larger:
 //                         behind a prepass almost every losing fragment ends at that plain load.
 //   k_surface_resolve     a lane per pixel: key -> draw (binary search of primBase over the descriptors) -> instance, triangle, part; the set-up again,
-//                         the edge functions at this pixel, the varyings one by one (never all 54 vertex values at once), material, four samples.
+//                         the edge functions at this pixel, the varyings one by one (never all 54 vertex values at once), material, four samples.  The
+//                         body is surface_resolve_body.h's surf_resolve_pixel, shared with k_surface_resolve_gltf and k_surface_resolve_lod.
 //   k_surface_composite   target = covered ? radiance : target
 //
 // The depth of a fragment and everything in front of it (clip, cut, snap, edges, top-left) are raster.hip's, so that the depth is the prepass's bit for
@@ -16,7 +17,7 @@
 // reads tightly packed positions and keeps its own raster_setup; surface_setup (surface_common.h) is that set-up over interleaved vertices, which also
 // reports where each vertex came from.  The fill of a set-up triangle is surface_fill.h's, shared with surface_masked.hip (the Masked queue:
 // ALPHA_CUTOUT in the draw), surface_gltf.hip (Standard_glTF.shader), surface_indirect.hip and particles.hip.
-#include "surface_fill.h"
+#include "surface_resolve_body.h"
 
 __global__ __launch_bounds__(256) void k_surface_begin(const float* __restrict__ depth, int W, int rowBegin, int rows, uint32_t maxDraws, void* __restrict__ workspace,
                                                        SurfSrgb table)
@@ -83,94 +84,15 @@ __global__ __launch_bounds__(256) void k_surface_visibility(Mat4 P, Mat4 V, Sail
     }
 }
 
-// ---- the resolve (surf_varying: surface_common.h) ---------------------------------------------------------------------------------------------------
+// ---- the resolve (surf_resolve_pixel: surface_resolve_body.h; Standard.shader alone, no occlusion or emissive plane) ---------------------------------
 
 __global__ __launch_bounds__(256) void k_surface_resolve(Mat4 P, Mat4 V, const float* __restrict__ instances, const SailorMaterialData* __restrict__ materials,
                                                          uint32_t numMaterials, const SailorTextureDesc* __restrict__ textures, uint32_t numTextures, int W, int H,
                                                          int rowBegin, int rows, uint32_t maxDraws, const void* __restrict__ workspace, float4* __restrict__ surface, size_t planeStride,
                                                          float* __restrict__ depthOut, uint8_t* __restrict__ coverage)
 {
-    const int i = texel_i(), jb = texel_j();
-    if (i >= W || jb >= rows) return;
-    const SurfWorkspace ws = surf_workspace(const_cast<void*>(workspace), (size_t)rows * W);
-    const size_t at = (size_t)jb * W + i;
-    const unsigned long long key = ws.keys[at];
-    const unsigned int low = (unsigned int)key;
-    if (depthOut) depthOut[at] = __uint_as_float((unsigned int)(key >> 32));
-    float4 p0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), p1 = make_float4(0.0f, 0.0f, 1.0f, 1.0f), p2 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    bool covered = false;
-    if (low != 0u) {
-        const unsigned int order = low - 1u;
-        // the last descriptor whose primBase does not exceed the order (empty slots hold 0xFFFFFFFF)
-        unsigned int lo = 0, hi = maxDraws; // (from the workspace's size, as begin derived it)
-        while (hi - lo > 1u) {
-            const unsigned int mid = lo + ((hi - lo) >> 1);
-            if (ws.draws[mid].primBase <= order) lo = mid; else hi = mid;
-        }
-        const SailorSurfaceDraw draw = ws.draws[lo];
-        const unsigned int rel = order - draw.primBase;
-        const unsigned int per = 2u * draw.numTriangles;
-        const unsigned int d = per ? rel / per : 0xFFFFFFFFu;
-        if (draw.primBase <= order && d < draw.numDrawn) {
-            const unsigned int r = rel - d * per, tri = r >> 1;
-            const int part = (int)(r & 1u);
-            const uint32_t inst = draw.dInstanceIds ? draw.dInstanceIds[d] : draw.firstInstance + d;
-            const float* __restrict__ model = instances + SURF_INSTANCE_FLOATS * (size_t)inst;
-            const float* __restrict__ vertices = reinterpret_cast<const float*>(draw.dVertices);
-            bool second;
-            SurfSrc S;
-            const SurfTri t = surface_setup(P, V, model, vertices, draw.dIndices + 3 * (size_t)tri, W, H, rowBegin, rowBegin + rows,
-                                            (draw.flags & SAILOR_SURFACE_CULL_BACK) != 0, part, second, S);
-            if (t.valid) {
-                covered = true;
-                const long long px = 256ll * i + 128, py = 256ll * (jb + rowBegin) + 128;
-                const float area = (float)surf_edge(t.x0, t.y0, t.x1, t.y1, t.x2, t.y2);
-                const float l0 = (float)surf_edge(t.x1, t.y1, t.x2, t.y2, px, py) / area, l1 = (float)surf_edge(t.x2, t.y2, t.x0, t.y0, px, py) / area,
-                            l2 = (float)surf_edge(t.x0, t.y0, t.x1, t.y1, px, py) / area;
-                const float q0 = l0 / S.w[0], q1 = l1 / S.w[1], q2 = l2 / S.w[2];
-                const float s = (q0 + q1) + q2;
-                const float b0 = q0 / s, b1 = q1 / s, b2 = q2 / s;
-                const float* __restrict__ vI0 = vertices + SURF_VERTEX_FLOATS * (size_t)S.I[0];
-                const float* __restrict__ vI1 = vertices + SURF_VERTEX_FLOATS * (size_t)S.I[1];
-                const float* __restrict__ vI2 = vertices + SURF_VERTEX_FLOATS * (size_t)S.I[2];
-                const float* __restrict__ vO1 = vertices + SURF_VERTEX_FLOATS * (size_t)S.O[1];
-                const float* __restrict__ vO2 = vertices + SURF_VERTEX_FLOATS * (size_t)S.O[2];
-                float a[18]; // (statically indexed under full unrolling: registers)
-#pragma unroll
-                for (int c = 0; c < 18; c++) {
-                    const float a0 = surf_varying(vI0, model, c); // (vertex 0 is never a cut one)
-                    float a1 = surf_varying(vI1, model, c), a2 = surf_varying(vI2, model, c);
-                    if (S.cut[1]) a1 = a1 + (surf_varying(vO1, model, c) - a1) * S.t[1];
-                    if (S.cut[2]) a2 = a2 + (surf_varying(vO2, model, c) - a2) * S.t[2];
-                    a[c] = (a0 * b0 + a1 * b1) + a2 * b2;
-                }
-                const uint32_t mi = reinterpret_cast<const uint32_t*>(model)[20]; // PerInstanceData.materialInstance, flat
-                const SailorMaterialData mat = materials[mi < numMaterials ? mi : 0u];
-                const float u = a[0], v = a[1];
-                const float4 tA = surf_texture(textures, numTextures, mat.albedoSampler, ws.srgb, u, v);
-                const float tM = surf_texture(textures, numTextures, mat.metalnessSampler, ws.srgb, u, v).x;
-                const float tR = surf_texture(textures, numTextures, mat.roughnessSampler, ws.srgb, u, v).x;
-                const float4 tN = surf_texture(textures, numTextures, mat.normalSampler, ws.srgb, u, v);
-                // :383-385
-                const float ar = (mat.albedo[0] * tA.x) * a[5], ag = (mat.albedo[1] * tA.y) * a[6], ab = (mat.albedo[2] * tA.z) * a[7], aa = (mat.albedo[3] * tA.w) * a[8];
-                const float metallic = mat.metallic * tM, roughness = mat.roughness * tR;
-                // :388-389
-                float nx = 2.0f * tN.x - 1.0f, ny = 2.0f * tN.y - 1.0f, nz = 2.0f * tN.z - 1.0f;
-                float len = sqrtf(dot3f(nx, ny, nz, nx, ny, nz));
-                nx = nx / len; ny = ny / len; nz = nz / len;
-                float wx = (a[9] * nx + a[12] * ny) + a[15] * nz, wy = (a[10] * nx + a[13] * ny) + a[16] * nz, wz = (a[11] * nx + a[14] * ny) + a[17] * nz;
-                len = sqrtf(dot3f(wx, wy, wz, wx, wy, wz));
-                wx = wx / len; wy = wy / len; wz = wz / len;
-                p0 = make_float4(a[2], a[3], a[4], aa);
-                p1 = make_float4(wx, wy, wz, roughness);
-                p2 = make_float4(ar, ag, ab, metallic);
-            }
-        }
-    }
-    surface[at] = p0;
-    surface[planeStride + at] = p1;
-    surface[2 * planeStride + at] = p2;
-    if (coverage) coverage[at] = covered ? 1 : 0;
+    surf_resolve_pixel<false, false>(P, V, instances, materials, numMaterials, textures, numTextures, W, H, rowBegin, rows, maxDraws, workspace, surface, planeStride, depthOut,
+                                     coverage, nullptr, nullptr, nullptr);
 }
 
 __global__ __launch_bounds__(256) void k_surface_composite(const float4* __restrict__ radiance, const void* __restrict__ workspace, float4* __restrict__ target, int W, int rows)
@@ -247,17 +169,8 @@ int sailor_hip_surface_resolve(SailorHipContext* ctx, const SailorUboFrameData* 
                                uint32_t numMaterials, const SailorTextureDesc* dTextures, uint32_t numTextures, int32_t width, int32_t height, const SailorBand* band,
                                const void* dWorkspace, size_t workspaceBytes, float* dSurface, size_t planeStride, float* dDepthOutOrNull, uint8_t* dCoverageOrNull)
 {
-    if (!ctx) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    SurfResolveSetup s;
-    if (const char* why = surf_resolve_why(frame, dInstances && surf_tables_ok(dMaterials, numMaterials, dTextures, numTextures), width, height, band, dWorkspace,
-                                           workspaceBytes, dSurface, planeStride, dDepthOutOrNull, s))
-        return surf_refuse(ctx, "sailor_hip_surface_resolve", why);
-    SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
-    sailor_launch(ctx, k_surface_resolve, texel_grid(width, band->fbRowCount), dim3(256), s.P, s.V, reinterpret_cast<const float*>(dInstances), dMaterials, numMaterials,
-                  dTextures, numTextures, (int)width, (int)height, (int)band->fbRowBegin, (int)band->fbRowCount, s.maxDraws, dWorkspace, reinterpret_cast<float4*>(dSurface),
-                  planeStride, dDepthOutOrNull, dCoverageOrNull);
-    SAILOR_CHECK_LAUNCH(ctx, "k_surface_resolve");
-    return SAILOR_HIP_OK;
+    return surf_resolve_launch(ctx, "sailor_hip_surface_resolve", k_surface_resolve, "k_surface_resolve", frame, dInstances, dMaterials, numMaterials, dTextures, numTextures,
+                               width, height, band, dWorkspace, workspaceBytes, dSurface, planeStride, dDepthOutOrNull, dCoverageOrNull);
 }
 
 int sailor_hip_surface_composite(SailorHipContext* ctx, const float* dRadiance, const void* dWorkspace, size_t workspaceBytes, float* dTarget, int32_t width,

@@ -72,26 +72,13 @@ static const char* bucket_store_why(int32_t width, const SailorBand* band, const
     return nullptr;
 }
 
-// the two draws: surf_draw_prologue under the peel draws' flags, the depth attachment, the store, MULTIPLY; then the launch
-template <typename K>
-static int bucket_draw(SailorHipContext* ctx, const char* who, K kernel, const char* kernelName, bool gltf, const SailorUboFrameData* frame, const SailorSurfaceDraw* draw,
-                       const SailorPerInstanceData* dInstances, const SailorMaterialData* dMaterials, uint32_t numMaterials, const SailorTextureDesc* dTextures,
-                       uint32_t numTextures, uint32_t drawIndex, int32_t width, int32_t height, const SailorBand* band, void* dWorkspace, size_t workspaceBytes,
-                       const float* dDepth, void* dBuckets, size_t bucketBytes, uint32_t layers)
+// what the two draws refuse beyond surf_draw_prologue (surf_draw_launch's `extra`): the depth attachment, the store, MULTIPLY
+static int bucket_draw_refusals(SailorHipContext* ctx, const char* who, const SailorSurfaceDraw* draw, int32_t width, const SailorBand* band, const float* dDepth,
+                                const void* dBuckets, size_t bucketBytes, uint32_t layers)
 {
-    SurfDrawSetup s;
-    if (const int st = surf_draw_prologue(ctx, who, SAILOR_SURFACE_CULL_BACK | SAILOR_SURFACE_ALPHA_CUTOUT | (gltf ? SAILOR_SURFACE_GLTF : 0u) | PEEL_BLEND_BITS, gltf, nullptr,
-                                          frame, draw, dInstances, surf_tables_ok(dMaterials, numMaterials, dTextures, numTextures), drawIndex, width, height, band, dWorkspace,
-                                          workspaceBytes, s))
-        return st;
     if (!aligned(dDepth, 4)) return surf_refuse(ctx, who, "the depth attachment is NULL or not 4-byte aligned");
     if (const char* why = bucket_store_why(width, band, dBuckets, bucketBytes, layers)) return surf_refuse(ctx, who, why);
     if (peel_is_multiply(draw)) return peel_refuse_multiply(ctx, who);
-    SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
-    sailor_launch(ctx, kernel, s.grid, dim3(256), s.P, s.V, *draw, reinterpret_cast<const float*>(dInstances), dMaterials, numMaterials, dTextures, numTextures, drawIndex,
-                  (int)width, (int)height, (int)band->fbRowBegin, (int)band->fbRowCount, dWorkspace, reinterpret_cast<const uint32_t*>(dDepth),
-                  reinterpret_cast<unsigned long long*>(dBuckets), layers);
-    SAILOR_CHECK_LAUNCH(ctx, kernelName);
     return SAILOR_HIP_OK;
 }
 
@@ -120,8 +107,11 @@ int sailor_hip_surface_bucket_draw(SailorHipContext* ctx, const SailorUboFrameDa
                                    int32_t width, int32_t height, const SailorBand* band, void* dWorkspace, size_t workspaceBytes, const float* dDepth, void* dBuckets,
                                    size_t bucketBytes, uint32_t layers)
 {
-    return bucket_draw(ctx, "sailor_hip_surface_bucket_draw", k_surface_bucket, "k_surface_bucket", false, frame, draw, dInstances, dMaterials, numMaterials, dTextures,
-                       numTextures, drawIndex, width, height, band, dWorkspace, workspaceBytes, dDepth, dBuckets, bucketBytes, layers);
+    static const char* who = "sailor_hip_surface_bucket_draw";
+    return surf_draw_launch(ctx, who, SAILOR_SURFACE_CULL_BACK | SAILOR_SURFACE_ALPHA_CUTOUT | PEEL_BLEND_BITS, false, k_surface_bucket, "k_surface_bucket", nullptr, nullptr,
+                            SurfNoCommand(), [&] { return bucket_draw_refusals(ctx, who, draw, width, band, dDepth, dBuckets, bucketBytes, layers); }, frame, draw, dInstances,
+                            dMaterials, numMaterials, dTextures, numTextures, drawIndex, width, height, band, dWorkspace, workspaceBytes,
+                            reinterpret_cast<const uint32_t*>(dDepth), reinterpret_cast<unsigned long long*>(dBuckets), layers);
 }
 
 int sailor_hip_surface_bucket_draw_gltf(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSurfaceDraw* draw, const SailorPerInstanceData* dInstances,
@@ -129,8 +119,12 @@ int sailor_hip_surface_bucket_draw_gltf(SailorHipContext* ctx, const SailorUboFr
                                         uint32_t drawIndex, int32_t width, int32_t height, const SailorBand* band, void* dWorkspace, size_t workspaceBytes, const float* dDepth,
                                         void* dBuckets, size_t bucketBytes, uint32_t layers)
 {
-    return bucket_draw(ctx, "sailor_hip_surface_bucket_draw_gltf", k_surface_bucket_gltf, "k_surface_bucket_gltf", true, frame, draw, dInstances, dMaterials, numMaterials,
-                       dTextures, numTextures, drawIndex, width, height, band, dWorkspace, workspaceBytes, dDepth, dBuckets, bucketBytes, layers);
+    static const char* who = "sailor_hip_surface_bucket_draw_gltf";
+    return surf_draw_launch(ctx, who, SAILOR_SURFACE_CULL_BACK | SAILOR_SURFACE_ALPHA_CUTOUT | SAILOR_SURFACE_GLTF | PEEL_BLEND_BITS, true, k_surface_bucket_gltf,
+                            "k_surface_bucket_gltf", nullptr, nullptr, SurfNoCommand(),
+                            [&] { return bucket_draw_refusals(ctx, who, draw, width, band, dDepth, dBuckets, bucketBytes, layers); }, frame, draw, dInstances, dMaterials,
+                            numMaterials, dTextures, numTextures, drawIndex, width, height, band, dWorkspace, workspaceBytes, reinterpret_cast<const uint32_t*>(dDepth),
+                            reinterpret_cast<unsigned long long*>(dBuckets), layers);
 }
 
 int sailor_hip_surface_bucket_layer(SailorHipContext* ctx, int32_t width, int32_t height, const SailorBand* band, void* dWorkspace, size_t workspaceBytes,

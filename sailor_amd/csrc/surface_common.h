@@ -1,10 +1,12 @@
 // What the surface-pass translation units share (surface.hip: the Opaque queue; surface_masked.hip: the Masked queue with ALPHA_CUTOUT; surface_gltf.hip:
 // Standard_glTF.shader's materials): the set-up (raster.hip's rules over interleaved vertices, on the helpers of raster_prims.h), the depth test of one fragment, the workspace layout, the varyings of a vertex, the
 // texture taps and the checks of the entry points.  Those checks are written once, host-only, at the end of this file: surf_workspace_why (band, workspace
-// alignment, descriptor slots) for every entry that takes the workspace, surf_draw_prologue (every check of the four draw entries, their matrices and their
-// grid with its slices) and surf_resolve_why (the two resolves).  An entry keeps the checks that are its own and its launch; surf_refuse puts the entry's
-// name in front of the reason.
+// alignment, descriptor slots) for every entry that takes the workspace, surf_draw_prologue (every check the draw entries share, their matrices and their
+// grid with its slices) and surf_resolve_why (the three resolves).  The launches behind them are written once as well: surf_draw_launch for every draw entry
+// that takes the tables, surf_resolve_launch for the resolves.  An entry keeps the checks that are its own; surf_refuse puts the entry's name in front of the
+// reason.  The resolve kernels' body and the search for a pixel's draw are surface_resolve_body.h's.
 #pragma once
+#include <type_traits>
 #include "common.h"
 #include "sampling.h"
 #include "texel_pass.h"
@@ -296,7 +298,7 @@ static bool surf_tables_ok(const SailorMaterialData* dMaterials, uint32_t numMat
     return dMaterials && dTextures && numMaterials != 0 && numTextures != 0;
 }
 
-// What the four draw entries (sailor_hip_surface_draw, _masked, _gltf, _indirect) check, in one order, and what their launches share: the two matrices,
+// What the draw entries (sailor_hip_surface_draw and, through surf_draw_launch, those that take the tables) check, in one order, and what their launches share: the two matrices,
 // the lanes of the draw and the grid.  `allowed` = the flag bits the entry accepts, needGltf = SAILOR_SURFACE_GLTF has to be among the draw's, `tables` =
 // surf_tables_ok of the entry's tables (read under ALPHA_CUTOUT only); dCommand = NULL for a direct entry, the address of the indirect entry's command
 // pointer: that entry checks the command and dInstanceIds as well, and its lanes are the CAPACITY's (the count is not known on the host).
@@ -325,8 +327,42 @@ static int surf_draw_prologue(SailorHipContext* ctx, const char* who, uint32_t a
     return SAILOR_HIP_OK;
 }
 
-// What sailor_hip_surface_resolve and _resolve_gltf check alike (`rest` = the instances are there and surf_tables_ok of the tables), and the matrices and
-// the descriptor slots their kernels take: why not, or NULL
+// Every draw entry that takes the tables (_draw_masked, _draw_gltf, _draw_indirect, _draw_lod, _draw_indirect_lod, _peel_draw[_gltf], _bucket_draw[_gltf]), in
+// the one order that can be observed (a refusal launches nothing): surf_draw_prologue, the entry's own refusals, hipSetDevice, the launch.  kernelGltf (or
+// NULL; its type is `kernel`'s, not deduced) is launched instead of `kernel` for a draw that carries SAILOR_SURFACE_GLTF.  command = SurfNoCommand(), or the indirect entry's command and record
+// count, which its kernels take after the draw.  extra() = the status of the entry's own refusals, made through surf_refuse (SAILOR_HIP_OK: none); tail = what
+// the kernel takes after the workspace.
+struct SurfNoCommand {};
+struct SurfCommand { const SailorDrawIndexedIndirectData* dCommand; uint32_t numInstanceRecords; };
+static int surf_no_refusals() { return SAILOR_HIP_OK; }
+template <typename K, typename C, typename Extra, typename... Tail>
+static int surf_draw_launch(SailorHipContext* ctx, const char* who, uint32_t allowed, bool needGltf, K kernel, const char* kernelName, typename std::common_type<K>::type kernelGltf,
+                            const char* kernelGltfName, const C command, Extra extra, const SailorUboFrameData* frame, const SailorSurfaceDraw* draw,
+                            const SailorPerInstanceData* dInstances, const SailorMaterialData* dMaterials, uint32_t numMaterials, const SailorTextureDesc* dTextures,
+                            uint32_t numTextures, uint32_t drawIndex, int32_t width, int32_t height, const SailorBand* band, void* dWorkspace, size_t workspaceBytes, Tail... tail)
+{
+    constexpr bool indirect = std::is_same<C, SurfCommand>::value;
+    const SailorDrawIndexedIndirectData* const* dCommand = nullptr;
+    if constexpr (indirect) dCommand = &command.dCommand;
+    SurfDrawSetup s;
+    if (const int st = surf_draw_prologue(ctx, who, allowed, needGltf, dCommand, frame, draw, dInstances, surf_tables_ok(dMaterials, numMaterials, dTextures, numTextures), drawIndex,
+                                          width, height, band, dWorkspace, workspaceBytes, s))
+        return st;
+    if (const int st = extra()) return st;
+    SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
+    const bool gltf = kernelGltf && (draw->flags & SAILOR_SURFACE_GLTF);
+    const auto launch = [&](auto... afterDraw) {
+        sailor_launch(ctx, gltf ? kernelGltf : kernel, s.grid, dim3(256), s.P, s.V, *draw, afterDraw..., reinterpret_cast<const float*>(dInstances), dMaterials, numMaterials,
+                      dTextures, numTextures, drawIndex, (int)width, (int)height, (int)band->fbRowBegin, (int)band->fbRowCount, dWorkspace, tail...);
+    };
+    if constexpr (indirect) launch(reinterpret_cast<const uint32_t*>(command.dCommand), command.numInstanceRecords);
+    else launch();
+    SAILOR_CHECK_LAUNCH(ctx, gltf ? kernelGltfName : kernelName);
+    return SAILOR_HIP_OK;
+}
+
+// What the three resolve entries check alike (`rest` = the instances are there and surf_tables_ok of the tables), and the matrices and the descriptor slots
+// their kernels take: why not, or NULL
 struct SurfResolveSetup { Mat4 P, V; uint32_t maxDraws; };
 static const char* surf_resolve_why(const SailorUboFrameData* frame, bool rest, int32_t width, int32_t height, const SailorBand* band, const void* dWorkspace,
                                     size_t workspaceBytes, const float* dSurface, size_t planeStride, const float* dDepthOutOrNull, SurfResolveSetup& s)
@@ -339,4 +375,32 @@ static const char* surf_resolve_why(const SailorUboFrameData* frame, bool rest, 
     memcpy(s.P.m, frame->projection, 64);
     memcpy(s.V.m, frame->view, 64);
     return nullptr;
+}
+// what _resolve_gltf and _resolve_lod check of their occlusion and emissive planes, after everything else; sailor_hip_surface_resolve has no such planes
+static const char* surf_resolve_planes_why() { return nullptr; }
+static const char* surf_resolve_planes_why(const float* dAoInOrNull, float* dAoOutOrNull, float4* dEmissive)
+{
+    if ((dAoInOrNull && !aligned(dAoInOrNull, 4)) || (dAoOutOrNull && !aligned(dAoOutOrNull, 4))) return "an occlusion plane is misaligned";
+    if (!aligned(dEmissive, 16)) return "the emissive plane is NULL or not 16-byte aligned";
+    return nullptr;
+}
+// The three resolve entries: the checks, hipSetDevice, the launch.  planes = what the kernel takes after the coverage: nothing, or (aoIn, aoOut, emissive).
+template <typename K, typename... Planes>
+static int surf_resolve_launch(SailorHipContext* ctx, const char* who, K kernel, const char* kernelName, const SailorUboFrameData* frame, const SailorPerInstanceData* dInstances,
+                               const SailorMaterialData* dMaterials, uint32_t numMaterials, const SailorTextureDesc* dTextures, uint32_t numTextures, int32_t width, int32_t height,
+                               const SailorBand* band, const void* dWorkspace, size_t workspaceBytes, float* dSurface, size_t planeStride, float* dDepthOutOrNull,
+                               uint8_t* dCoverageOrNull, Planes... planes)
+{
+    if (!ctx) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    SurfResolveSetup s;
+    const char* why = surf_resolve_why(frame, dInstances && surf_tables_ok(dMaterials, numMaterials, dTextures, numTextures), width, height, band, dWorkspace, workspaceBytes,
+                                       dSurface, planeStride, dDepthOutOrNull, s);
+    if (!why) why = surf_resolve_planes_why(planes...);
+    if (why) return surf_refuse(ctx, who, why);
+    SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
+    sailor_launch(ctx, kernel, texel_grid(width, band->fbRowCount), dim3(256), s.P, s.V, reinterpret_cast<const float*>(dInstances), dMaterials, numMaterials, dTextures,
+                  numTextures, (int)width, (int)height, (int)band->fbRowBegin, (int)band->fbRowCount, s.maxDraws, dWorkspace, reinterpret_cast<float4*>(dSurface), planeStride,
+                  dDepthOutOrNull, dCoverageOrNull, planes...);
+    SAILOR_CHECK_LAUNCH(ctx, kernelName);
+    return SAILOR_HIP_OK;
 }

@@ -41,23 +41,11 @@ int sailor_hip_surface_draw_indirect(SailorHipContext* ctx, const SailorUboFrame
                                      const SailorMaterialData* dMaterials, uint32_t numMaterials, const SailorTextureDesc* dTextures, uint32_t numTextures,
                                      uint32_t drawIndex, int32_t width, int32_t height, const SailorBand* band, void* dWorkspace, size_t workspaceBytes)
 {
-    SurfDrawSetup s; // (the grid and its slices from the capacity: the count is not known here)
-    if (const int st = surf_draw_prologue(ctx, "sailor_hip_surface_draw_indirect", SAILOR_SURFACE_CULL_BACK | SAILOR_SURFACE_ALPHA_CUTOUT | SAILOR_SURFACE_GLTF, false, &dCommand,
-                                          frame, draw, dInstances, surf_tables_ok(dMaterials, numMaterials, dTextures, numTextures), drawIndex, width, height, band, dWorkspace,
-                                          workspaceBytes, s))
-        return st;
-    SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
-    const uint32_t* command = reinterpret_cast<const uint32_t*>(dCommand);
-    if (draw->flags & SAILOR_SURFACE_GLTF) {
-        sailor_launch(ctx, k_surface_visibility_indirect_gltf, s.grid, dim3(256), s.P, s.V, *draw, command, numInstanceRecords, reinterpret_cast<const float*>(dInstances),
-                      dMaterials, numMaterials, dTextures, numTextures, drawIndex, (int)width, (int)height, (int)band->fbRowBegin, (int)band->fbRowCount, dWorkspace);
-        SAILOR_CHECK_LAUNCH(ctx, "k_surface_visibility_indirect_gltf");
-    } else {
-        sailor_launch(ctx, k_surface_visibility_indirect, s.grid, dim3(256), s.P, s.V, *draw, command, numInstanceRecords, reinterpret_cast<const float*>(dInstances),
-                      dMaterials, numMaterials, dTextures, numTextures, drawIndex, (int)width, (int)height, (int)band->fbRowBegin, (int)band->fbRowCount, dWorkspace);
-        SAILOR_CHECK_LAUNCH(ctx, "k_surface_visibility_indirect");
-    }
-    return SAILOR_HIP_OK;
+    // (the grid and its slices come from the capacity: the count is not known here)
+    return surf_draw_launch(ctx, "sailor_hip_surface_draw_indirect", SAILOR_SURFACE_CULL_BACK | SAILOR_SURFACE_ALPHA_CUTOUT | SAILOR_SURFACE_GLTF, false,
+                            k_surface_visibility_indirect, "k_surface_visibility_indirect", k_surface_visibility_indirect_gltf, "k_surface_visibility_indirect_gltf",
+                            SurfCommand{dCommand, numInstanceRecords}, surf_no_refusals, frame, draw, dInstances, dMaterials, numMaterials, dTextures, numTextures, drawIndex,
+                            width, height, band, dWorkspace, workspaceBytes);
 }
 
 } // extern "C"

@@ -40,15 +40,9 @@ int sailor_hip_surface_draw_masked(SailorHipContext* ctx, const SailorUboFrameDa
                                    const SailorMaterialData* dMaterials, uint32_t numMaterials, const SailorTextureDesc* dTextures, uint32_t numTextures,
                                    uint32_t drawIndex, int32_t width, int32_t height, const SailorBand* band, void* dWorkspace, size_t workspaceBytes)
 {
-    SurfDrawSetup s;
-    if (const int st = surf_draw_prologue(ctx, "sailor_hip_surface_draw_masked", SAILOR_SURFACE_CULL_BACK | SAILOR_SURFACE_ALPHA_CUTOUT, false, nullptr, frame, draw, dInstances,
-                                          surf_tables_ok(dMaterials, numMaterials, dTextures, numTextures), drawIndex, width, height, band, dWorkspace, workspaceBytes, s))
-        return st;
-    SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
-    sailor_launch(ctx, k_surface_visibility_masked, s.grid, dim3(256), s.P, s.V, *draw, reinterpret_cast<const float*>(dInstances), dMaterials, numMaterials, dTextures,
-                  numTextures, drawIndex, (int)width, (int)height, (int)band->fbRowBegin, (int)band->fbRowCount, dWorkspace);
-    SAILOR_CHECK_LAUNCH(ctx, "k_surface_visibility_masked");
-    return SAILOR_HIP_OK;
+    return surf_draw_launch(ctx, "sailor_hip_surface_draw_masked", SAILOR_SURFACE_CULL_BACK | SAILOR_SURFACE_ALPHA_CUTOUT, false, k_surface_visibility_masked,
+                            "k_surface_visibility_masked", nullptr, nullptr, SurfNoCommand(), surf_no_refusals, frame, draw, dInstances, dMaterials, numMaterials, dTextures,
+                            numTextures, drawIndex, width, height, band, dWorkspace, workspaceBytes);
 }
 
 int sailor_hip_surface_store_depth(SailorHipContext* ctx, const void* dWorkspace, size_t workspaceBytes, float* dDepth, int32_t width, int32_t height, const SailorBand* band)

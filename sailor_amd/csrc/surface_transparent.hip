@@ -12,11 +12,13 @@
 //   k_surface_peel_commit                a lane per pixel of 16 rows: a non-zero key becomes the standard zbits << 32 | orderPlus1, last[pixel] = orderPlus1,
 //                                        and the pixels committed are added to a counter, one atomicAdd per wave behind its ballots.  After it the workspace
 //                                        is an ordinary surface workspace: the resolves and the shade run on it unchanged.
-//   k_surface_blend                      a lane per pixel: the owning draw by the resolve's binary search, its blend mode, one load and one store of the target.
+//   k_surface_blend                      a lane per pixel: the owning draw by the resolve's binary search (surf_owning_draw, surface_resolve_body.h), its blend
+//                                        mode, one load and one store of the target.
 //
 // A pass of L layers re-rasterises its draws L + 1 times (the last time only counts what is left): the price of reusing the resolve and the shade.
 // (surface_buckets.hip is the route that rasterises once; it ends in the same resolve, shade and k_surface_blend.)
 #include "surface_transparent.h"
+#include "surface_resolve_body.h"
 
 __global__ __launch_bounds__(256) void k_surface_peel(Mat4 P, Mat4 V, SailorSurfaceDraw draw, const float* __restrict__ instances,
                                                       const SailorMaterialData* __restrict__ materials, uint32_t numMaterials,
@@ -84,14 +86,10 @@ __global__ __launch_bounds__(256) void k_surface_blend(const float4* __restrict_
     const size_t at = (size_t)jb * W + i;
     const unsigned int low = (unsigned int)ws.keys[at];
     if (low == 0u) return;
-    const unsigned int order = low - 1u;
-    // the last descriptor whose primBase does not exceed the order, as the resolve finds it
-    unsigned int lo = 0, hi = maxDraws;
-    while (hi - lo > 1u) {
-        const unsigned int mid = lo + ((hi - lo) >> 1);
-        if (ws.draws[mid].primBase <= order) lo = mid; else hi = mid;
-    }
-    const uint32_t mode = (ws.draws[lo].flags >> SAILOR_SURFACE_BLEND_SHIFT) & SAILOR_SURFACE_BLEND_MASK;
+    SailorSurfaceDraw draw; // (the pixel went through the resolve: of what the search reports only the draw's flags are read here)
+    unsigned int instance, rest;
+    surf_owning_draw(ws, maxDraws, low - 1u, draw, instance, rest);
+    const uint32_t mode = (draw.flags >> SAILOR_SURFACE_BLEND_SHIFT) & SAILOR_SURFACE_BLEND_MASK;
     const float4 r = radiance[at];
     float4 src = make_float4(r.x, r.y, r.z, surfaceP0[at].w);
     if (emissive) {
@@ -102,12 +100,13 @@ __global__ __launch_bounds__(256) void k_surface_blend(const float4* __restrict_
 }
 
 // ---- entry points ---------------------------------------------------------------------------------------------------------------------------------
-// what the two peel draws check beyond surf_draw_prologue: why not, or NULL
-static const char* peel_planes_why(const float* dDepth, const uint32_t* dLast)
+// what the two peel draws refuse beyond surf_draw_prologue (surf_draw_launch's `extra`): the two planes, then MULTIPLY
+static int peel_draw_refusals(SailorHipContext* ctx, const char* who, const SailorSurfaceDraw* draw, const float* dDepth, const uint32_t* dLast)
 {
-    if (!aligned(dDepth, 4)) return "the depth attachment is NULL or not 4-byte aligned";
-    if (!aligned(dLast, 4)) return "the last-order plane is NULL or not 4-byte aligned";
-    return nullptr;
+    if (!aligned(dDepth, 4)) return surf_refuse(ctx, who, "the depth attachment is NULL or not 4-byte aligned");
+    if (!aligned(dLast, 4)) return surf_refuse(ctx, who, "the last-order plane is NULL or not 4-byte aligned");
+    if (peel_is_multiply(draw)) return peel_refuse_multiply(ctx, who);
+    return SAILOR_HIP_OK;
 }
 
 extern "C" {
@@ -129,17 +128,9 @@ int sailor_hip_surface_peel_draw(SailorHipContext* ctx, const SailorUboFrameData
                                  int32_t width, int32_t height, const SailorBand* band, void* dWorkspace, size_t workspaceBytes, const float* dDepth, const uint32_t* dLast)
 {
     static const char* who = "sailor_hip_surface_peel_draw";
-    SurfDrawSetup s;
-    if (const int st = surf_draw_prologue(ctx, who, SAILOR_SURFACE_CULL_BACK | SAILOR_SURFACE_ALPHA_CUTOUT | PEEL_BLEND_BITS, false, nullptr, frame, draw, dInstances,
-                                          surf_tables_ok(dMaterials, numMaterials, dTextures, numTextures), drawIndex, width, height, band, dWorkspace, workspaceBytes, s))
-        return st;
-    if (const char* why = peel_planes_why(dDepth, dLast)) return surf_refuse(ctx, who, why);
-    if (peel_is_multiply(draw)) return peel_refuse_multiply(ctx, who);
-    SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
-    sailor_launch(ctx, k_surface_peel, s.grid, dim3(256), s.P, s.V, *draw, reinterpret_cast<const float*>(dInstances), dMaterials, numMaterials, dTextures, numTextures,
-                  drawIndex, (int)width, (int)height, (int)band->fbRowBegin, (int)band->fbRowCount, dWorkspace, reinterpret_cast<const uint32_t*>(dDepth), dLast);
-    SAILOR_CHECK_LAUNCH(ctx, "k_surface_peel");
-    return SAILOR_HIP_OK;
+    return surf_draw_launch(ctx, who, SAILOR_SURFACE_CULL_BACK | SAILOR_SURFACE_ALPHA_CUTOUT | PEEL_BLEND_BITS, false, k_surface_peel, "k_surface_peel", nullptr, nullptr,
+                            SurfNoCommand(), [&] { return peel_draw_refusals(ctx, who, draw, dDepth, dLast); }, frame, draw, dInstances, dMaterials, numMaterials, dTextures,
+                            numTextures, drawIndex, width, height, band, dWorkspace, workspaceBytes, reinterpret_cast<const uint32_t*>(dDepth), dLast);
 }
 
 int sailor_hip_surface_peel_draw_gltf(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSurfaceDraw* draw, const SailorPerInstanceData* dInstances,
@@ -148,18 +139,10 @@ int sailor_hip_surface_peel_draw_gltf(SailorHipContext* ctx, const SailorUboFram
                                       const uint32_t* dLast)
 {
     static const char* who = "sailor_hip_surface_peel_draw_gltf";
-    SurfDrawSetup s;
-    if (const int st = surf_draw_prologue(ctx, who, SAILOR_SURFACE_CULL_BACK | SAILOR_SURFACE_ALPHA_CUTOUT | SAILOR_SURFACE_GLTF | PEEL_BLEND_BITS, true, nullptr, frame, draw,
-                                          dInstances, surf_tables_ok(dMaterials, numMaterials, dTextures, numTextures), drawIndex, width, height, band, dWorkspace,
-                                          workspaceBytes, s))
-        return st;
-    if (const char* why = peel_planes_why(dDepth, dLast)) return surf_refuse(ctx, who, why);
-    if (peel_is_multiply(draw)) return peel_refuse_multiply(ctx, who);
-    SAILOR_TRY_HIP(ctx, hipSetDevice(ctx->device));
-    sailor_launch(ctx, k_surface_peel_gltf, s.grid, dim3(256), s.P, s.V, *draw, reinterpret_cast<const float*>(dInstances), dMaterials, numMaterials, dTextures, numTextures,
-                  drawIndex, (int)width, (int)height, (int)band->fbRowBegin, (int)band->fbRowCount, dWorkspace, reinterpret_cast<const uint32_t*>(dDepth), dLast);
-    SAILOR_CHECK_LAUNCH(ctx, "k_surface_peel_gltf");
-    return SAILOR_HIP_OK;
+    return surf_draw_launch(ctx, who, SAILOR_SURFACE_CULL_BACK | SAILOR_SURFACE_ALPHA_CUTOUT | SAILOR_SURFACE_GLTF | PEEL_BLEND_BITS, true, k_surface_peel_gltf,
+                            "k_surface_peel_gltf", nullptr, nullptr, SurfNoCommand(), [&] { return peel_draw_refusals(ctx, who, draw, dDepth, dLast); }, frame, draw, dInstances,
+                            dMaterials, numMaterials, dTextures, numTextures, drawIndex, width, height, band, dWorkspace, workspaceBytes,
+                            reinterpret_cast<const uint32_t*>(dDepth), dLast);
 }
 
 int sailor_hip_surface_peel_commit(SailorHipContext* ctx, int32_t width, int32_t height, const SailorBand* band, void* dWorkspace, size_t workspaceBytes, uint32_t* dLast,

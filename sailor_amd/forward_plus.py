@@ -1043,21 +1043,11 @@ class SurfacePass:
         nt = indices.numel() // 3
         flags = (_lib.SURFACE_CULL_BACK if cull_back else 0) | (_lib.SURFACE_ALPHA_CUTOUT if alpha_cutout else 0) | (_lib.SURFACE_GLTF if gltf else 0)
         d = _lib.SurfaceDraw(_ptr(vertices), _ptr(indices), _ptr(instance_ids), nt, num_drawn, self.prim_base, flags, first_instance, 0)
-        if lod:
-            _lib.check(self.ctx._lib.sailor_hip_surface_draw_lod(self.ctx.handle, C.byref(frame), C.byref(d), _ptr(instances), _ptr(materials),
-                                                                 0 if materials is None else materials.numel() * materials.element_size() // 80, _ptr(textures),
-                                                                 num_textures, self.draw_index, self.W, self.H, C.byref(self.band), _ptr(self.workspace),
-                                                                 self.workspace.numel()), "sailor_hip_surface_draw_lod", self.ctx.handle)
-        elif gltf:
-            _lib.check(self.ctx._lib.sailor_hip_surface_draw_gltf(self.ctx.handle, C.byref(frame), C.byref(d), _ptr(instances), _ptr(materials),
-                                                                  0 if materials is None else materials.numel() * materials.element_size() // 80, _ptr(textures),
-                                                                  num_textures, self.draw_index, self.W, self.H, C.byref(self.band), _ptr(self.workspace),
-                                                                  self.workspace.numel()), "sailor_hip_surface_draw_gltf", self.ctx.handle)
-        elif alpha_cutout:
-            _lib.check(self.ctx._lib.sailor_hip_surface_draw_masked(self.ctx.handle, C.byref(frame), C.byref(d), _ptr(instances), _ptr(materials),
-                                                                    0 if materials is None else materials.numel() * materials.element_size() // 80, _ptr(textures),
-                                                                    num_textures, self.draw_index, self.W, self.H, C.byref(self.band), _ptr(self.workspace),
-                                                                    self.workspace.numel()), "sailor_hip_surface_draw_masked", self.ctx.handle)
+        if lod or gltf or alpha_cutout:
+            name = "sailor_hip_surface_draw_lod" if lod else "sailor_hip_surface_draw_gltf" if gltf else "sailor_hip_surface_draw_masked"
+            _lib.check(getattr(self.ctx._lib, name)(self.ctx.handle, C.byref(frame), C.byref(d), _ptr(instances), _ptr(materials),
+                                                    0 if materials is None else materials.numel() * materials.element_size() // 80, _ptr(textures), num_textures,
+                                                    self.draw_index, self.W, self.H, C.byref(self.band), _ptr(self.workspace), self.workspace.numel()), name, self.ctx.handle)
         else:
             _lib.check(self.ctx._lib.sailor_hip_surface_draw(self.ctx.handle, C.byref(frame), C.byref(d), _ptr(instances), self.draw_index, self.W, self.H,
                                                              C.byref(self.band), _ptr(self.workspace), self.workspace.numel()), "sailor_hip_surface_draw", self.ctx.handle)

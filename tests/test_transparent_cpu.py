@@ -44,7 +44,7 @@ def test_the_older_draw_entries_exclude_the_blend_bits_from_what_they_accept():
     csrc = ROOT / "sailor_amd" / "csrc"
     seen = 0
     for unit in ("surface.hip", "surface_masked.hip", "surface_gltf.hip", "surface_indirect.hip", "surface_lod.hip"):
-        for call in re.findall(r"surf_draw_prologue\(ctx, \"(\w+)\", ([^,]+),", (csrc / unit).read_text()):
+        for call in re.findall(r"surf_draw_(?:prologue|launch)\(ctx, \"(\w+)\", ([^,]+),", (csrc / unit).read_text()):  # (_launch: the prologue and the launch behind it)
             flags = [f.strip() for f in call[1].split("|")]
             assert set(flags) <= {"SAILOR_SURFACE_CULL_BACK", "SAILOR_SURFACE_ALPHA_CUTOUT", "SAILOR_SURFACE_GLTF"}, call
             seen += 1
