@@ -1284,7 +1284,7 @@ typedef struct SailorSurfaceDraw {
     uint32_t numTriangles;
     uint32_t numDrawn;
     uint32_t primBase;                          /* the order of the draw's first primitive: the previous draw's primBase + its sailor_hip_surface_draw_prims */
-    uint32_t flags;                             /* SAILOR_SURFACE_CULL_BACK; SAILOR_SURFACE_ALPHA_CUTOUT through sailor_hip_surface_draw_masked, _draw_gltf and _draw_indirect only; SAILOR_SURFACE_GLTF (below) through _draw_gltf and _draw_indirect only; SAILOR_SURFACE_BLEND_* (the Transparent section) through _peel_draw, _peel_draw_gltf, _bucket_draw and _bucket_draw_gltf only */
+    uint32_t flags;                             /* SAILOR_SURFACE_CULL_BACK; SAILOR_SURFACE_ALPHA_CUTOUT through sailor_hip_surface_draw_masked, _draw_gltf, _draw_indirect, _msaa_draw and _msaa_draw_gltf only; SAILOR_SURFACE_GLTF (below) through _draw_gltf, _draw_indirect and _msaa_draw_gltf only; SAILOR_SURFACE_BLEND_* (the Transparent section) through _peel_draw, _peel_draw_gltf, _bucket_draw and _bucket_draw_gltf only */
     uint32_t firstInstance;
     uint32_t _pad;
 } SailorSurfaceDraw;
@@ -1548,7 +1548,7 @@ SAILOR_HIP_API int sailor_hip_surface_draw_indirect_lod(SailorHipContext* ctx, c
  *       ALPHA    : dst.rgb = src.rgb * src.a + dst.rgb * (1 - src.a);  dst.a = src.a * src.a - dst.a * (1 - src.a)    (the alpha op is SUBTRACT)
  *       MULTIPLY : SAILOR_HIP_ERR_UNSUPPORTED for scene draws (VK_BLEND_OP_MULTIPLY_EXT: the decision recorded for the sun shafts stands)
  *     A fragment with src.a == 0 still blends; NaN and Inf pass through.
- *  5. The target is the RGBA32F Main plane, as for every other pass; MSAA does not apply.
+ *  5. The target is the RGBA32F Main plane, as for every other pass; this queue stays single-sampled (the Multisampled section lists it as not reproduced).
  * Mechanism: the pass is peeled by primitive order.  Layer k holds, at each pixel, that pixel's k-th fragment in primitive order:
  *   sailor_hip_surface_peel_begin (zero keys; `last` zeroed for layer 0 only) -> every draw through _peel_draw / _peel_draw_gltf (a fragment of rule 1 with
  *   orderPlus1 > last[pixel] issues (0xFFFFFFFF - orderPlus1) << 32 | zbits by plain load and atomicMax: the maximum is the smallest order beyond the previous
@@ -1631,6 +1631,97 @@ SAILOR_HIP_API int sailor_hip_surface_bucket_draw_gltf(SailorHipContext* ctx, co
 SAILOR_HIP_API int sailor_hip_surface_bucket_layer(SailorHipContext* ctx, int32_t width, int32_t height, const SailorBand* band, void* dWorkspace,
                                                    size_t workspaceBytes, const void* dBuckets, size_t bucketBytes, uint32_t layers, uint32_t k,
                                                    uint32_t* dCount);
+
+/* ---- Multisampled RenderScene pass: per-sample keys, shaded layers, the AVERAGE resolve (surface_msaa.hip) ------------------------------------------
+ * Replaces: the multisampled targets of the scene pass.  Sailor.cpp:150 creates the renderer with EMsaaSamples::Samples_8; VulkanCommandBuffer.cpp:341-386
+ * puts every pass whose material supports multisampling (the default) on the driver's cached MSAA colour and depth targets and resolves both with
+ * VK_RESOLVE_MODE_AVERAGE_BIT (:287-298).  VulkanPipileneStates.cpp:141-149 has sampleShadingEnable = VK_FALSE and alphaToCoverageEnable = VK_FALSE, and no
+ * varying of Standard.shader or Standard_glTF.shader is `centroid`: coverage and depth are per sample, the fragment shader runs once per pixel and primitive
+ * with its varyings at the pixel centre, `discard` removes the whole fragment.
+ * OPT-IN: no existing entry point, kernel or default changes; a pass that is not multisampled keeps the single-sample entries.  Pinned:
+ *  1. Sample positions: Vulkan's standard sample locations, in 1/256 pixel from the pixel's top-left corner, exact on the rasteriser's grid.
+ *     S = 1: (128,128).  S = 2: (192,192), (64,64).  S = 4: (96,32), (224,96), (32,160), (160,224).
+ *     S = 8: (144,80), (112,176), (208,144), (80,48), (48,208), (16,112), (176,240), (240,16).
+ *     Any other count is refused (the reference's 16 / 32 / 64 have no standard table restated here).  sailor_host_msaa_sample_positions returns the table.
+ *  2. Coverage of sample s of pixel (i, j) by a set-up triangle (the surface pass's vertices, near-plane cut, snap and cull, unchanged): the three edge
+ *     functions at (256 i + sx, 256 j + sy), none negative, a value of 0 counting only on a top or left edge -- the surface pass's rule moved from the centre
+ *     to the sample.  The box is every pixel that holds a sample inside the triangle's bounding box (the walk may visit more; they hold no covered sample).
+ *     A triangle that covers samples but no pixel centre exists here.
+ *  3. Depth of a covered sample: z0 + (z1 - z0) (float(e1) / area) + (z2 - z0) (float(e2) / area) with the SAMPLE's e1, e2 and the triangle's area; kept
+ *     iff 0 < z <= 1.  With S = 1 the keys are sailor_hip_surface_draw_masked's, bit for bit.
+ *  4. Discard (ALPHA_CUTOUT, both shaders) is evaluated once per pixel and primitive, by the Masked queue's rule with the edge functions of the pixel
+ *     CENTRE; the centre may lie outside the triangle, and the barycentrics then extrapolate, as the hardware does without `centroid`.  A discarded fragment
+ *     owns no sample.  Base-level fetch, as sailor_hip_surface_draw_masked.
+ *  5. Store: one uint64 per sample, pixel-major -- store[(row * width + x) * S + s], row counted from the band's first -- holding zbits << 32 | orderPlus1
+ *     under an unsigned maximum: GreaterOrEqual in primitive order, as the surface pass.  orderPlus1 == 0: no primitive of this pass.  S x 8 bytes a pixel
+ *     (64 at S = 8: 531 MB for 3840 x 2160).  A fragment's order of work is the masked draw's, per pixel: a plain relaxed load per covered sample; the discard
+ *     only if some sample would win; an atomic maximum only for the samples that would win.  The keys are order-free.
+ *  6. Begin: keys = sampleDepthBits << 32 from an optional per-sample depth (floats in the store's layout: what a multisampled prepass stored through
+ *     _msaa_store_depth), or 0.
+ *  7. Layers: layer k of a pixel is its (k + 1)-th smallest distinct non-zero orderPlus1 among its S keys.  _msaa_layer(k), k < layers = L, 1 <= L <= S,
+ *     writes an ordinary surface workspace key zbits << 32 | orderPlus1 -- the zbits of the lowest-numbered sample holding that order; 0 where the pixel has
+ *     no such layer --, a weight byte w_k = the samples holding that order, adds the pixels that have the layer to a device counter and, for k = 0, writes a
+ *     byte u = the samples that hold no order.  With L < S the samples whose order is not among the pixel's first L are CLIPPED: their number is added to
+ *     w_(L-1) of that pixel, and the pixel is counted in a second device counter.  L = S never clips.  The read-out is stateless: it recomputes from the S
+ *     keys and keeps no per-pixel cursor.
+ *  8. Shading of a layer: the unchanged sailor_hip_surface_resolve / _resolve_gltf / _resolve_lod with dDepthOutOrNull = NULL, then the unchanged shade --
+ *     the fragment shader at the pixel centre, once per primitive and pixel.
+ *  9. Accumulate: the reference's AVERAGE resolve over what `Blit Sky -> Main` left in every sample.  c_k = what sailor_hip_surface_composite would store,
+ *     or sailor_hip_surface_composite_gltf's (emissive.rgb + radiance.rgb, radiance.a) when an emissive plane is given.  The weights w / S are exact in fp32;
+ *     every product and every sum is rounded on its own (no fused multiply-add); a term of weight 0 is omitted, not multiplied.
+ *       k = 0: w_0 = 0: untouched.  w_0 = S: target = c_0, its bits.  Otherwise target = (u / S) target + (w_0 / S) c_0, the first term omitted when u = 0.
+ *       k >= 1: w_k = 0: untouched.  Otherwise target = target + (w_k / S) c_k.
+ *     Samples this pass does not own take the target's value at the pixel: exact when the target was uniform over each pixel's samples before the pass, the
+ *     case behind the Sky blit.  SANCTIONED DIVERGENCE: a second pass over the edge pixels of an earlier multisampled pass; to be exact there, draw both
+ *     queues into ONE store (the entries allow it: the orders of the second continue the first's).
+ * 10. Depth out: the S sample depths (the keys' high words, in the store's layout) for the next pass's begin, and the resolved depth, the reference's
+ *     AVERAGE (((z_0 + z_1) + ...) + z_(S-1)) * (1 / S) in fp32, into the band's rows of the whole-frame depth attachment.
+ * A pass: _msaa_begin -> every draw once through _msaa_draw / _msaa_draw_gltf -> L times { _msaa_layer(k), a resolve, the shade, _msaa_accumulate(k) } ->
+ * _msaa_store_depth where the pass writes depth.
+ * NOT reproduced (a pass that needs one keeps the single-sample entries): the runtime mirror (HipGraphicsDriver, FrameGraph.cpp -- DepthPrepass, DebugDraw,
+ * particles and the Transparent queue share the surface and would all have to follow); indirect draws and the `_lod` draw's alpha fetch (a layer may still
+ * be resolved by sailor_hip_surface_resolve_lod); the Transparent queue; SAILOR_VULKAN_MSAA_IMPACTS_TEXTURE_SAMPLING (sample shading); 16 samples and more.
+ * All entry points record only (no allocation, no synchronisation, capturable); a refused call launches nothing, leaves its text in last_error and leaves
+ * store, workspace and outputs untouched.  Refused everywhere: samples outside {1, 2, 4, 8}; a NULL or not 16-byte aligned dStore; storeBytes below
+ * sailor_hip_surface_msaa_bytes. */
+/* The table of rule 1: out[s] = (sx, sy), s < samples.  SAILOR_HIP_ERR_INVALID_ARGUMENT for another count or a NULL out. */
+SAILOR_HIP_API int sailor_host_msaa_sample_positions(uint32_t samples, int32_t out[][2]);
+/* The bytes of the store over the band's rows: fbRowCount * width * samples * 8.  0 on a bad argument (a NULL band, a width or a row count outside
+ * 1 .. 32768, samples outside {1, 2, 4, 8}). */
+SAILOR_HIP_API size_t sailor_hip_surface_msaa_bytes(int32_t width, const SailorBand* band, uint32_t samples);
+/* Begins a pass: rule 6 into the store (dSampleDepthOrNull: device, fbRowCount * width * samples floats, or NULL), and sailor_hip_surface_begin without a
+ * depth into the workspace (zero keys, empty descriptor slots, the sRGB table).  Also refused: a misaligned dSampleDepthOrNull. */
+SAILOR_HIP_API int sailor_hip_surface_msaa_begin(SailorHipContext* ctx, int32_t width, int32_t height, const SailorBand* band, void* dWorkspace,
+                                                 size_t workspaceBytes, void* dStore, size_t storeBytes, uint32_t samples, const float* dSampleDepthOrNull);
+/* One DrawIndexed of the pass: k_surface_msaa.  The arguments, checks and refusals of sailor_hip_surface_draw_masked (so the LOD, indirect and blend flags are
+ * unknown flags here) plus the store.  The workspace takes the draw's descriptor, for the resolves. */
+SAILOR_HIP_API int sailor_hip_surface_msaa_draw(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSurfaceDraw* draw,
+                                                const SailorPerInstanceData* dInstances, const SailorMaterialData* dMaterials, uint32_t numMaterials,
+                                                const SailorTextureDesc* dTextures, uint32_t numTextures, uint32_t drawIndex, int32_t width, int32_t height,
+                                                const SailorBand* band, void* dWorkspace, size_t workspaceBytes, void* dStore, size_t storeBytes,
+                                                uint32_t samples);
+/* The same for a Standard_glTF.shader material: k_surface_msaa_gltf; flags must hold SAILOR_SURFACE_GLTF, as for sailor_hip_surface_draw_gltf. */
+SAILOR_HIP_API int sailor_hip_surface_msaa_draw_gltf(SailorHipContext* ctx, const SailorUboFrameData* frame, const SailorSurfaceDraw* draw,
+                                                     const SailorPerInstanceData* dInstances, const SailorMaterialData* dMaterials, uint32_t numMaterials,
+                                                     const SailorTextureDesc* dTextures, uint32_t numTextures, uint32_t drawIndex, int32_t width, int32_t height,
+                                                     const SailorBand* band, void* dWorkspace, size_t workspaceBytes, void* dStore, size_t storeBytes,
+                                                     uint32_t samples);
+/* Rule 7 for layer k: k_surface_msaa_layer.  dWeight, dUncoveredOrNull: device, a byte per pixel of the band; dCount, dClippedOrNull: device uint32, added
+ * to (the caller zeroes them).  Also refused: layers outside 1 .. samples; k >= layers; a NULL dWeight; a NULL dUncoveredOrNull at k = 0; a NULL or
+ * misaligned dCount; a misaligned dClippedOrNull. */
+SAILOR_HIP_API int sailor_hip_surface_msaa_layer(SailorHipContext* ctx, int32_t width, int32_t height, const SailorBand* band, void* dWorkspace,
+                                                 size_t workspaceBytes, const void* dStore, size_t storeBytes, uint32_t samples, uint32_t layers, uint32_t k,
+                                                 uint8_t* dWeight, uint8_t* dUncoveredOrNull, uint32_t* dCount, uint32_t* dClippedOrNull);
+/* Rule 9 for layer k: k_surface_msaa_accumulate.  dRadiance: the shade's output; dEmissiveOrNull: a glTF resolve's emissive plane, or NULL; dWeight,
+ * dUncoveredOrNull: what _msaa_layer(k) wrote; all over the band's rows, as dTarget.  Also refused: k >= samples; a NULL dWeight; a NULL dUncoveredOrNull at
+ * k = 0; a NULL or not 16-byte aligned colour plane. */
+SAILOR_HIP_API int sailor_hip_surface_msaa_accumulate(SailorHipContext* ctx, const float* dRadiance, const float* dEmissiveOrNull, const uint8_t* dWeight,
+                                                      const uint8_t* dUncoveredOrNull, uint32_t samples, uint32_t k, float* dTarget, int32_t width,
+                                                      int32_t height, const SailorBand* band);
+/* Rule 10: k_surface_msaa_store_depth.  dSampleDepthOutOrNull: device, fbRowCount * width * samples floats; dDepthOrNull: the raw width x height depth
+ * attachment of the WHOLE frame.  Also refused: both NULL; a misaligned output. */
+SAILOR_HIP_API int sailor_hip_surface_msaa_store_depth(SailorHipContext* ctx, const void* dStore, size_t storeBytes, uint32_t samples,
+                                                       float* dSampleDepthOutOrNull, float* dDepthOrNull, int32_t width, int32_t height, const SailorBand* band);
 
 /* ---- DebugDraw: the line-list pass of the Gizmo material (debug_lines.hip) ---------------------------------------------------------------------
  * Replaces: the draw FrameGraph/DebugDrawNode.cpp:19-79 replays -- RHI/DebugContext.cpp:382-398 (DrawDebugMesh: one DrawIndexed over the line list that

@@ -496,6 +496,17 @@ SIGNATURES = {
     "sailor_hip_surface_bucket_draw_gltf": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(SurfaceDraw), _P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_int32,
                                                       C.c_int32, C.POINTER(Band), _P, C.c_size_t, _P, _P, C.c_size_t, C.c_uint32]),
     "sailor_hip_surface_bucket_layer": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(Band), _P, C.c_size_t, _P, C.c_size_t, C.c_uint32, C.c_uint32, _P]),
+    "sailor_host_msaa_sample_positions": (C.c_int, [C.c_uint32, _P]),
+    "sailor_hip_surface_msaa_bytes": (C.c_size_t, [C.c_int32, C.POINTER(Band), C.c_uint32]),
+    "sailor_hip_surface_msaa_begin": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(Band), _P, C.c_size_t, _P, C.c_size_t, C.c_uint32, _P]),
+    "sailor_hip_surface_msaa_draw": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(SurfaceDraw), _P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32,
+                                               C.POINTER(Band), _P, C.c_size_t, _P, C.c_size_t, C.c_uint32]),
+    "sailor_hip_surface_msaa_draw_gltf": (C.c_int, [_P, C.POINTER(UboFrameData), C.POINTER(SurfaceDraw), _P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_int32,
+                                                    C.c_int32, C.POINTER(Band), _P, C.c_size_t, _P, C.c_size_t, C.c_uint32]),
+    "sailor_hip_surface_msaa_layer": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(Band), _P, C.c_size_t, _P, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P,
+                                                _P]),
+    "sailor_hip_surface_msaa_accumulate": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_int32, C.c_int32, C.POINTER(Band)]),
+    "sailor_hip_surface_msaa_store_depth": (C.c_int, [_P, _P, C.c_size_t, C.c_uint32, _P, _P, C.c_int32, C.c_int32, C.POINTER(Band)]),
     "sailor_hip_surface_keys_offset": (C.c_size_t, []),
     "sailor_host_srgb_table": (C.c_int, [C.POINTER(C.c_float)]),
     "sailor_hip_surface_draw_prims": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),

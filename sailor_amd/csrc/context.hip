@@ -5,7 +5,7 @@
 
 extern "C" {
 
-int sailor_hip_version(void) { return 1000 * 0 + 13; }
+int sailor_hip_version(void) { return 1000 * 0 + 14; }
 
 const char* sailor_hip_status_string(int status)
 {

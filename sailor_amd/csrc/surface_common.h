@@ -30,6 +30,9 @@ struct SurfSrc { uint32_t I[3], O[3]; float t[3], w[3]; bool cut[3]; };
 
 // raster_setup of raster.hip from the clip positions c[0..2] of the triangle's vertices v0, v1, v2 on: the near-plane cut, the snap, the cull and the box;
 // rows [rowBegin, rowEnd) of the frame only.  S reports the vertices' sources for the varyings (dead code where it is not read).
+// PIXEL_BOX (default false: the box of the pixel CENTRES inside the bounding box, as ever): the box of every pixel the bounding box touches, for the
+// multisampled walk of surface_fill_msaa.h, whose samples lie anywhere in a pixel -- a triangle that holds no centre is valid there.
+template <bool PIXEL_BOX = false>
 __device__ __forceinline__ SurfTri surface_setup_clip(float4 (&c)[3], const uint32_t v0, const uint32_t v1, const uint32_t v2, int W, int H, int rowBegin, int rowEnd,
                                                       bool cullBack, int part, bool& hasSecond, SurfSrc& S)
 {
@@ -100,6 +103,7 @@ __device__ __forceinline__ SurfTri surface_setup_clip(float4 (&c)[3], const uint
     const long long miny = min(Y[0], min(Y[1], Y[2])), maxy = max(Y[0], max(Y[1], Y[2]));
     long long i0 = surf_floor_div256(minx - 128 + 255), i1 = surf_floor_div256(maxx - 128);
     long long j0 = surf_floor_div256(miny - 128 + 255), j1 = surf_floor_div256(maxy - 128);
+    if constexpr (PIXEL_BOX) { i0 = surf_floor_div256(minx); i1 = surf_floor_div256(maxx); j0 = surf_floor_div256(miny); j1 = surf_floor_div256(maxy); }
     if (i0 < 0) i0 = 0;
     if (j0 < rowBegin) j0 = rowBegin;
     if (i1 > W - 1) i1 = W - 1;
@@ -111,6 +115,7 @@ __device__ __forceinline__ SurfTri surface_setup_clip(float4 (&c)[3], const uint
 }
 
 // hasView form: clip = projection * (view * (model * position)) (DepthOnly.shader:51 == Standard.shader:131) over interleaved vertices
+template <bool PIXEL_BOX = false>
 __device__ __forceinline__ SurfTri surface_setup(const Mat4& P, const Mat4& V, const float* __restrict__ model, const float* __restrict__ vertices,
                                                  const uint32_t* __restrict__ tri, int W, int H, int rowBegin, int rowEnd, bool cullBack, int part, bool& hasSecond,
                                                  SurfSrc& S)
@@ -127,7 +132,7 @@ __device__ __forceinline__ SurfTri surface_setup(const Mat4& P, const Mat4& V, c
         const float4 bq = glsl_mul(V, a.x, a.y, a.z, a.w);
         c[k] = glsl_mul(P, bq.x, bq.y, bq.z, bq.w);
     }
-    return surface_setup_clip(c, v0, v1, v2, W, H, rowBegin, rowEnd, cullBack, part, hasSecond, S);
+    return surface_setup_clip<PIXEL_BOX>(c, v0, v1, v2, W, H, rowBegin, rowEnd, cullBack, part, hasSecond, S);
 }
 
 // one matrix: clip = LM * position (a caster draw: LM = lightMatrix * model, raster.hip's form without a view)
@@ -327,7 +332,7 @@ static int surf_draw_prologue(SailorHipContext* ctx, const char* who, uint32_t a
     return SAILOR_HIP_OK;
 }
 
-// Every draw entry that takes the tables (_draw_masked, _draw_gltf, _draw_indirect, _draw_lod, _draw_indirect_lod, _peel_draw[_gltf], _bucket_draw[_gltf]), in
+// Every draw entry that takes the tables (_draw_masked, _draw_gltf, _draw_indirect, _draw_lod, _draw_indirect_lod, _peel_draw[_gltf], _bucket_draw[_gltf], _msaa_draw[_gltf]), in
 // the one order that can be observed (a refusal launches nothing): surf_draw_prologue, the entry's own refusals, hipSetDevice, the launch.  kernelGltf (or
 // NULL; its type is `kernel`'s, not deduced) is launched instead of `kernel` for a draw that carries SAILOR_SURFACE_GLTF.  command = SurfNoCommand(), or the indirect entry's command and record
 // count, which its kernels take after the draw.  extra() = the status of the entry's own refusals, made through surf_refuse (SAILOR_HIP_OK: none); tail = what

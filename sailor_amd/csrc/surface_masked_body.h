@@ -5,10 +5,12 @@
 // count of the albedo descriptor and the six steps of the edge functions to the next pixel, so a fragment can evaluate uv at its quad's other centres.
 // MODE (default SURF_DRAW_MASKED, likewise) chooses what a fragment does: SURF_DRAW_PEEL is the Transparent queue's draw of surface_transparent.hip -- the same
 // fragments against a read-only depth plane, keyed by order --, SURF_DRAW_BUCKET its one-rasterisation draw of surface_buckets.hip: the same fragments again,
-// inserted into the pixel's K + 1 ordered slots.
+// inserted into the pixel's K + 1 ordered slots.  SURF_DRAW_MSAA is the multisampled draw of surface_msaa.hip: the walk is surface_fill_msaa.h's over pixels, a
+// fragment is a pixel with its covered samples, and the keys go to the per-sample store.
 #pragma once
 #include <type_traits>
 #include "surface_fill.h"
+#include "surface_fill_msaa.h"
 #include "surface_lod.h"
 
 // what the alpha of a fragment needs of its triangle, prepared once by the owning lane: the three clip w, (u, v, colour alpha) of the three set-up
@@ -194,11 +196,49 @@ __device__ __forceinline__ void surf_fragment_bucket(const SurfBucket& b, size_t
     }
 }
 
+// MSAA (surface_msaa.hip, the multisampled pass; the Multisampled section of include/sailor_hip.h has the rules): one fragment a pixel and primitive, one key a
+// SAMPLE.  p = the pixel's S keys (pixel-major store).  The order of work is surf_fragment_masked's, per pixel: every sample that is covered (`full`: all of
+// them, untested) and whose depth exists is compared with a plain relaxed load of its key; the discard is evaluated ONCE, with the edge functions of the pixel
+// CENTRE (which may be negative: the barycentrics extrapolate), and only if some sample would win; only those samples issue the atomicMax.  The sample loop is
+// kept a loop (the alpha words are live across it); a winner's depth is computed again behind the discard rather than kept for S samples.
+struct SurfMsaa { unsigned long long* store; unsigned long long pattern; int samples; };
+template <bool GLTF>
+__device__ __forceinline__ void surf_pixel_msaa(unsigned long long* p, int S, unsigned long long pattern, const SurfTri& t, const SurfMsaaEdges& m, int tl, bool full, int i,
+                                                int j, unsigned int orderPlus1, const SurfAlpha& A, long long e0, long long e1, long long e2, float area)
+{
+    unsigned int wins = 0;
+#pragma unroll 1
+    for (int s = 0; s < S; s++) {
+        const int mx = surf_msaa_dx(pattern, s), my = surf_msaa_dy(pattern, s);
+        const long long s1 = surf_msaa_at(m, 1, e1, mx, my), s2 = surf_msaa_at(m, 2, e2, mx, my);
+        if (!full) {
+            const long long s0 = surf_msaa_at(m, 0, e0, mx, my);
+            if (s0 < 0 || s1 < 0 || s2 < 0) continue;
+            if (surf_on_excluded_edge(s0, s1, s2, tl)) continue;
+        }
+        const float z = surf_depth(t, s1, s2, area);
+        if (!(z > 0.0f && z <= 1.0f)) continue;
+        const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | orderPlus1;
+        if (key > __hip_atomic_load(p + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) wins |= 1u << s;
+    }
+    if (!wins) return;
+    if (!surf_alpha_keeps<GLTF, false>(A, i, j, e0, e1, e2, area)) return;
+#pragma unroll 1
+    for (; wins; wins &= wins - 1u) {
+        const int s = __builtin_ctz(wins);
+        const int mx = surf_msaa_dx(pattern, s), my = surf_msaa_dy(pattern, s);
+        const float z = surf_depth(t, surf_msaa_at(m, 1, e1, mx, my), surf_msaa_at(m, 2, e2, mx, my), area);
+        atomicMax(p + s, ((unsigned long long)__float_as_uint(z) << 32) | orderPlus1);
+    }
+}
+
 // what a draw kernel does with a fragment
 enum { SURF_DRAW_MASKED = 0, SURF_DRAW_PEEL = 1, SURF_DRAW_BUCKET = 2 };
+enum { SURF_DRAW_MSAA = 3 }; // (the multisampled pass: a fragment is a pixel with its covered samples)
 
 // the slices (gridDim.y) are k_surface_visibility's; without SAILOR_SURFACE_ALPHA_CUTOUT in draw.flags the keys are k_surface_visibility's.
-// X: what MODE needs beyond the workspace -- SurfPeel, or SurfBucket under SURF_DRAW_BUCKET (the workspace then only takes the draw's descriptor).
+// X: what MODE needs beyond the workspace -- SurfPeel, SurfBucket under SURF_DRAW_BUCKET or SurfMsaa under SURF_DRAW_MSAA (the workspace then only takes the
+// draw's descriptor).
 template <bool GLTF, bool LOD = false, int MODE = SURF_DRAW_MASKED, typename X = SurfPeel>
 __device__ __forceinline__ void surf_visibility_masked(const Mat4& P, const Mat4& V, const SailorSurfaceDraw& draw, const float* __restrict__ instances,
                                                        const SailorMaterialData* __restrict__ materials, uint32_t numMaterials,
@@ -244,7 +284,8 @@ __device__ __forceinline__ void surf_visibility_masked(const Mat4& P, const Mat4
             // rowEnd - 1 and the cull mask out of all loops, and these eight scalar registers are the ones the file does not have (they were spilled)
             int Wl = W, rowB = rowBegin, rowE = rowBegin + rows, fl = (int)draw.flags;
             asm volatile("" : "+s"(Wl), "+s"(rowB), "+s"(rowE), "+s"(fl));
-            t = surface_setup(P, V, model, vertices, draw.dIndices + 3 * (size_t)tri, Wl, H, rowB, rowE, (fl & (int)SAILOR_SURFACE_CULL_BACK) != 0, part, second, S);
+            t = surface_setup<MODE == SURF_DRAW_MSAA>(P, V, model, vertices, draw.dIndices + 3 * (size_t)tri, Wl, H, rowB, rowE, (fl & (int)SAILOR_SURFACE_CULL_BACK) != 0, part,
+                                                      second, S);
             if (A.height >= 0 && t.valid) {
                 surf_alpha_vertices(A, S, vertices);
                 if constexpr (LOD) surf_alpha_steps(A, t);
@@ -252,15 +293,25 @@ __device__ __forceinline__ void surf_visibility_masked(const Mat4& P, const Mat4
         }
         const unsigned int orderPlus1 = draw.primBase + (unsigned int)(2ull * id) + (unsigned int)part + 1u; // (the entry point has checked the range)
         // the fill: the alpha words are the payload, carried to the wave once per large triangle
-        surf_fill(t, orderPlus1, A, [](const SurfAlphaOf<LOD>& a, int src) { return surf_alpha_bcast<GLTF, LOD>(a, src); }, slice, slices, lane,
-                  [&](int i, int j, float z, unsigned int tag, const SurfAlphaOf<LOD>& a, long long e0, long long e1, long long e2, float area) {
-                      if constexpr (MODE == SURF_DRAW_BUCKET) {
-                          surf_fragment_bucket<GLTF, LOD>(peel, (size_t)j * W + i, (size_t)(j - rowBegin) * W + i, i, j, z, tag, a, e0, e1, e2, area);
-                      } else if constexpr (PEEL) {
-                          const size_t atBand = (size_t)(j - rowBegin) * W + i;
-                          surf_fragment_peel<GLTF, LOD>(keys + atBand, peel, (size_t)j * W + i, atBand, i, j, z, tag, a, e0, e1, e2, area);
-                      } else surf_fragment_masked<GLTF, LOD>(keys + (size_t)(j - rowBegin) * W + i, i, j, z, tag, a, e0, e1, e2, area);
-                  });
+        if constexpr (MODE == SURF_DRAW_MSAA) {
+            static_assert(!LOD, "the multisampled draw fetches the base level");
+            surf_fill_msaa(t, orderPlus1, A, [](const SurfAlpha& a, int src) { return surf_alpha_bcast<GLTF, false>(a, src); }, slice, slices, lane, peel.samples, peel.pattern,
+                           [&](int i, int j, const SurfTri& tri, const SurfMsaaEdges& m, int tl, bool full, unsigned int tag, const SurfAlpha& a, long long e0, long long e1,
+                               long long e2, float area) {
+                               surf_pixel_msaa<GLTF>(peel.store + ((size_t)(j - rowBegin) * W + i) * (size_t)peel.samples, peel.samples, peel.pattern, tri, m, tl, full, i, j, tag,
+                                                     a, e0, e1, e2, area);
+                           });
+        } else {
+            surf_fill(t, orderPlus1, A, [](const SurfAlphaOf<LOD>& a, int src) { return surf_alpha_bcast<GLTF, LOD>(a, src); }, slice, slices, lane,
+                      [&](int i, int j, float z, unsigned int tag, const SurfAlphaOf<LOD>& a, long long e0, long long e1, long long e2, float area) {
+                          if constexpr (MODE == SURF_DRAW_BUCKET) {
+                              surf_fragment_bucket<GLTF, LOD>(peel, (size_t)j * W + i, (size_t)(j - rowBegin) * W + i, i, j, z, tag, a, e0, e1, e2, area);
+                          } else if constexpr (PEEL) {
+                              const size_t atBand = (size_t)(j - rowBegin) * W + i;
+                              surf_fragment_peel<GLTF, LOD>(keys + atBand, peel, (size_t)j * W + i, atBand, i, j, z, tag, a, e0, e1, e2, area);
+                          } else surf_fragment_masked<GLTF, LOD>(keys + (size_t)(j - rowBegin) * W + i, i, j, z, tag, a, e0, e1, e2, area);
+                      });
+        }
         if (part == 0) again = second;
     }
 }

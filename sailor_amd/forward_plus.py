@@ -1234,6 +1234,86 @@ class SurfacePass:
             blend_layer(k)
             k += 1
 
+    def multisampled(self, frame: UboFrameData, draws, instances: torch.Tensor, materials: torch.Tensor, textures: torch.Tensor, num_textures: int, shade,
+                     target: torch.Tensor, samples: int = 8, layers: int | None = None, sample_depth: torch.Tensor | None = None,
+                     ao_in: torch.Tensor | None = None, prim_base: int = 0, on_layer=None) -> torch.Tensor:
+        """A multisampled RenderScene pass (the Multisampled section of include/sailor_hip.h; sailor_hip_surface_msaa_*): the draws run once into a store of
+        `samples` keys a pixel (self.sample_store, samples x 8 bytes a pixel), every layer -- the pixel's primitives in primitive order -- is read out into the
+        workspace, resolved and shaded at the pixel centre as ever, and accumulated onto `target` (float32 [rows, W, 4]) with the share of the samples it owns:
+        the reference's AVERAGE resolve.  samples: 1, 2, 4 or 8.
+        draws: dicts of draw()'s keyword arguments (vertices, indices, instance_ids, num_drawn, first_instance, cull_back, alpha_cutout, gltf).
+        shade: the callable of transparent(): (surface float32 [3, rows, W, 4], ao float32 [rows, W] | None) -> radiance float32 [rows, W, 4].
+        layers: how many primitives a pixel may show, 1 .. samples (None: samples, which never clips); a pixel with more gives the samples of the others to
+        its last layer.  sample_depth: float32 [rows, W, samples], what store_sample_depth() of a multisampled prepass returned, or None.
+        Records only and reads nothing back; returns the device counters, int32 [layers + 1]: the pixels each layer holds and, last, the clipped pixels.
+        on_layer(k, surface, weight uint8 [rows, W], emissive | None, ao | None): called behind every resolve (a test's window into the layers); the bytes of
+        the samples no primitive owns are self.uncovered."""
+        ctx, lib, dev = self.ctx, self.ctx._lib, self.ctx.device
+        layers = samples if layers is None else layers
+        assert target.dtype == torch.float32 and target.shape == (self.rows, self.W, 4) and target.is_contiguous()
+        assert sample_depth is None or (sample_depth.dtype == torch.float32 and sample_depth.shape == (self.rows, self.W, samples) and sample_depth.is_contiguous())
+        any_gltf = any(d.get("gltf", False) for d in draws)
+        num_materials = materials.numel() * materials.element_size() // 80
+        ws, n = _ptr(self.workspace), self.workspace.numel()
+        nb = lib.sailor_hip_surface_msaa_bytes(self.W, C.byref(self.band), samples)
+        if nb == 0:
+            raise _lib.SailorHipError(-1, "sailor_hip_surface_msaa_bytes")
+        if getattr(self, "sample_store", None) is None or self.sample_store.numel() * 8 != nb:
+            self.sample_store = torch.empty(nb // 8, dtype=torch.int64, device=dev)
+        self.samples = samples
+        store = (_ptr(self.sample_store), nb, samples)
+        _lib.check(lib.sailor_hip_surface_msaa_begin(ctx.handle, self.W, self.H, C.byref(self.band), ws, n, *store, _ptr(sample_depth)), "sailor_hip_surface_msaa_begin",
+                   ctx.handle)
+        base = prim_base
+        for index, d in enumerate(draws):
+            ids, first = d.get("instance_ids"), d.get("first_instance", 0)
+            drawn = d.get("num_drawn")
+            if drawn is None:
+                drawn = ids.numel() if ids is not None else instances.numel() * instances.element_size() // 96 - first
+            nt = d["indices"].numel() // 3
+            flags = (_lib.SURFACE_CULL_BACK if d.get("cull_back", False) else 0) | (_lib.SURFACE_ALPHA_CUTOUT if d.get("alpha_cutout", False) else 0) | \
+                    (_lib.SURFACE_GLTF if d.get("gltf", False) else 0)
+            desc = _lib.SurfaceDraw(_ptr(d["vertices"]), _ptr(d["indices"]), _ptr(ids), nt, drawn, base, flags, first, 0)
+            name = "sailor_hip_surface_msaa_draw_gltf" if d.get("gltf", False) else "sailor_hip_surface_msaa_draw"
+            _lib.check(getattr(lib, name)(ctx.handle, C.byref(frame), C.byref(desc), _ptr(instances), _ptr(materials), num_materials, _ptr(textures), num_textures, index,
+                                          self.W, self.H, C.byref(self.band), ws, n, *store), name, ctx.handle)
+            base += host.surface_draw_prims(nt, drawn)
+        self.prim_base, self.draw_index = base, len(draws)
+        counts = torch.zeros(layers + 1, dtype=torch.int32, device=dev)
+        self.weights = torch.empty((layers, self.rows, self.W), dtype=torch.uint8, device=dev)
+        self.uncovered = torch.empty((self.rows, self.W), dtype=torch.uint8, device=dev)
+        for k in range(layers):
+            weight = self.weights[k]
+            _lib.check(lib.sailor_hip_surface_msaa_layer(ctx.handle, self.W, self.H, C.byref(self.band), ws, n, *store, layers, k, _ptr(weight),
+                                                         _ptr(self.uncovered) if k == 0 else None, _ptr(counts[k:]), _ptr(counts[layers:])),
+                       "sailor_hip_surface_msaa_layer", ctx.handle)
+            if any_gltf:
+                surface, _, _, ao, emissive = self.resolve_gltf(frame, instances, materials, textures, num_textures, ao_in=ao_in, want_depth=False, want_coverage=False)
+            else:
+                surface, _, _ = self.resolve(frame, instances, materials, textures, num_textures, want_depth=False, want_coverage=False)
+                ao, emissive = ao_in, None
+            if on_layer is not None:
+                on_layer(k, surface, weight, emissive, ao)
+            radiance = shade(surface, ao)
+            assert radiance.dtype == torch.float32 and radiance.shape == (self.rows, self.W, 4) and radiance.is_contiguous()
+            _lib.check(lib.sailor_hip_surface_msaa_accumulate(ctx.handle, _ptr(radiance), _ptr(emissive), _ptr(weight), _ptr(self.uncovered), samples, k, _ptr(target),
+                                                              self.W, self.H, C.byref(self.band)), "sailor_hip_surface_msaa_accumulate", ctx.handle)
+        return counts
+
+    def store_sample_depth(self, depth: torch.Tensor | None = None, want_samples: bool = True):
+        """the depth of the last multisampled() pass: -> (the sample depths, float32 [rows, W, samples], for the next pass's sample_depth -- None without
+        want_samples --, depth).  depth: the raw depth attachment of the WHOLE frame, float32 [H, W], or None; the band's rows of it take the samples' AVERAGE"""
+        assert depth is None or (depth.dtype == torch.float32 and depth.shape == (self.H, self.W) and depth.is_contiguous())
+        out = torch.empty((self.rows, self.W, self.samples), dtype=torch.float32, device=self.ctx.device) if want_samples else None
+        _lib.check(self.ctx._lib.sailor_hip_surface_msaa_store_depth(self.ctx.handle, _ptr(self.sample_store), self.sample_store.numel() * 8, self.samples, _ptr(out),
+                                                                     _ptr(depth), self.W, self.H, C.byref(self.band)), "sailor_hip_surface_msaa_store_depth", self.ctx.handle)
+        return out, depth
+
+    def download_samples(self) -> np.ndarray:
+        """the store of the last multisampled() as uint64 [rows, W, samples]: depth bits << 32 | (order + 1)"""
+        self.ctx.synchronize()
+        return self.sample_store.cpu().numpy().view(np.uint64).reshape(self.rows, self.W, self.samples)
+
     def download_keys(self) -> np.ndarray:
         """the keys as uint64 [rows, W]: depth bits << 32 | (order + 1)"""
         self.ctx.synchronize()

@@ -484,6 +484,14 @@ def texture_mip_levels(width: int, height: int) -> int:
     return int(_lib.load().sailor_hip_texture_mip_levels(width, height))
 
 
+def msaa_sample_positions(samples: int) -> np.ndarray:
+    """sailor_host_msaa_sample_positions: the standard sample locations of a `samples`-times multisampled pixel, int32 [samples, 2], (sx, sy) in 1/256 pixel
+    from the pixel's top-left corner; samples is 1, 2, 4 or 8"""
+    out = np.zeros((max(int(samples), 1), 2), np.int32)
+    _lib.check(_lib.load().sailor_host_msaa_sample_positions(samples, out.ctypes.data_as(C.c_void_p)), "sailor_host_msaa_sample_positions")
+    return out
+
+
 def surface_draw_prims(num_triangles: int, num_drawn: int) -> int:
     """sailor_hip_surface_draw_prims: what a draw adds to the surface pass's running primBase"""
     out = C.c_uint64()
