@@ -563,3 +563,9 @@ def check(status: int, where: str, ctx=None) -> None:
         if ctx is not None:
             detail = load().sailor_hip_context_last_error(ctx).decode()
         raise SailorHipError(status, where, detail)
+
+
+def call(name: str, *args) -> None:
+    """the checked call of the entry `name`, one that takes no context (HipContext.call is the one for those that do): a status other than 0 raises under
+    the entry's name"""
+    check(getattr(load(), name)(*args), name)

@@ -274,21 +274,17 @@ class ListExchange:
         self.slot_words = 0   # what the context will use for the next record(): 0 = the worst case
 
     def record(self, band_grid: torch.Tensor, band_culled: torch.Tensor):
-        from . import _lib
-        lib = self.ctx._lib
-        _lib.check(lib.sailor_hip_exchange_light_lists_rows(self.ctx.handle, self.comm.handle, self.comm.rank, self.world, self.W, self.H, self.bounds.ctypes.data,
-                                                             band_grid.data_ptr(), band_culled.data_ptr(), self.out_grid.data_ptr(), self.Tx * self.Ty,
-                                                             self.out_culled.data_ptr(), self.out_culled.numel(), self.ws.data_ptr(), self.ws.numel()),
-                   "sailor_hip_exchange_light_lists_rows", self.ctx.handle)
+        self.ctx.call("sailor_hip_exchange_light_lists_rows", self.comm.handle, self.comm.rank, self.world, self.W, self.H, self.bounds.ctypes.data, band_grid.data_ptr(),
+                      band_culled.data_ptr(), self.out_grid.data_ptr(), self.Tx * self.Ty, self.out_culled.data_ptr(), self.out_culled.numel(), self.ws.data_ptr(),
+                      self.ws.numel())
         return self.out_grid, self.out_culled
 
     def adapt(self):
         """-> (largest band total of the last exchange, clipped?, slot words of the next one)"""
         import ctypes as C
 
-        from . import _lib
         largest, clipped, slot = C.c_uint32(0), C.c_int32(0), C.c_size_t(0)
-        _lib.check(self.ctx._lib.sailor_hip_exchange_adapt(self.ctx.handle, C.byref(largest), C.byref(clipped), C.byref(slot)), "sailor_hip_exchange_adapt", self.ctx.handle)
+        self.ctx.call("sailor_hip_exchange_adapt", C.byref(largest), C.byref(clipped), C.byref(slot))
         self.slot_words = int(slot.value)
         return int(largest.value), bool(clipped.value), int(slot.value)
 
@@ -320,9 +316,7 @@ def exchange_lists_rccl(ctx, comm: "RcclComm", width: int, height: int, tile_row
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
     out_grid = torch.zeros(Tx * Ty * 2, dtype=torch.int32, device=dev)
     out_culled = torch.zeros(1 + Tx * Ty * _lib.LIGHTS_PER_TILE, dtype=torch.int32, device=dev)
-    _lib.check(lib.sailor_hip_exchange_light_lists_rows(ctx.handle, comm.handle, comm.rank, world, width, height, bounds.ctypes.data, band_grid.data_ptr(),
-                                                         band_culled.data_ptr(), out_grid.data_ptr(), Tx * Ty, out_culled.data_ptr(), out_culled.numel(),
-                                                         ws.data_ptr(), ws.numel()),
-               "sailor_hip_exchange_light_lists_rows", ctx.handle)
+    ctx.call("sailor_hip_exchange_light_lists_rows", comm.handle, comm.rank, world, width, height, bounds.ctypes.data, band_grid.data_ptr(), band_culled.data_ptr(),
+             out_grid.data_ptr(), Tx * Ty, out_culled.data_ptr(), out_culled.numel(), ws.data_ptr(), ws.numel())
     ctx.synchronize()   # (the workspace is released on return)
     return out_grid, out_culled

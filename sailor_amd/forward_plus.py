@@ -23,6 +23,11 @@ def _ptr(t: torch.Tensor | None) -> int | None:
     return None if t is None else t.data_ptr()
 
 
+def _ref(s):
+    """a structure by reference, or NULL"""
+    return None if s is None else C.byref(s)
+
+
 class HipContext:
     """RAII wrapper of SailorHipContext bound to a torch device and stream."""
 
@@ -34,21 +39,25 @@ class HipContext:
         self.device = torch.device("cuda", index)
         self.stream = stream if stream is not None else torch.cuda.current_stream(self.device)
         handle = C.c_void_p()
-        lib = _lib.load()
-        _lib.check(lib.sailor_hip_context_create(index, C.c_void_p(self.stream.cuda_stream), 0, C.byref(handle)), "sailor_hip_context_create")
+        _lib.call("sailor_hip_context_create", index, C.c_void_p(self.stream.cuda_stream), 0, C.byref(handle))
         self.handle = handle
-        self._lib = lib
+        self._lib = _lib.load()
+
+    def call(self, name: str, *args):
+        """the checked call of the C-ABI entry `name`, which takes this context first: a status other than 0 raises under the entry's name, with the context's
+        last error"""
+        _lib.check(getattr(self._lib, name)(self.handle, *args), name, self.handle)
 
     def synchronize(self):
-        _lib.check(self._lib.sailor_hip_context_synchronize(self.handle), "synchronize", self.handle)
+        self.call("sailor_hip_context_synchronize")
 
     def time_launches(self, first_slot: int, count: int):
         """the next `count` kernel launches through this context carry event pairs on their dispatch packets (sailor_hip_context_time_launches)"""
-        _lib.check(self._lib.sailor_hip_context_time_launches(self.handle, first_slot, count), "sailor_hip_context_time_launches", self.handle)
+        self.call("sailor_hip_context_time_launches", first_slot, count)
 
     def timed_launch_ms(self, slot: int) -> float:
         ms = C.c_float()
-        _lib.check(self._lib.sailor_hip_context_timed_launch_ms(self.handle, slot, C.byref(ms)), "sailor_hip_context_timed_launch_ms", self.handle)
+        self.call("sailor_hip_context_timed_launch_ms", slot, C.byref(ms))
         return float(ms.value)
 
     def launch_log(self, max_names: int = 16):
@@ -56,7 +65,7 @@ class HipContext:
         (sailor_hip_context_launch_log).  The kernels of ONE call = the names behind the count read in front of it."""
         count = C.c_uint64()
         names = (C.c_char_p * max_names)()
-        _lib.check(self._lib.sailor_hip_context_launch_log(self.handle, C.byref(count), names, max_names), "sailor_hip_context_launch_log", self.handle)
+        self.call("sailor_hip_context_launch_log", C.byref(count), names, max_names)
         return int(count.value), [n.decode() for n in names if n is not None]
 
     def launches_of(self, fn):
@@ -85,8 +94,7 @@ def linearize_depth(ctx: "HipContext", frame: UboFrameData, raw: torch.Tensor, o
     assert raw.dtype == torch.float32 and raw.dim() == 2 and raw.is_contiguous()
     if out is None:
         out = torch.empty_like(raw)
-    _lib.check(ctx._lib.sailor_hip_linearize_depth(ctx.handle, C.byref(frame), _ptr(raw), _ptr(out), raw.shape[1], raw.shape[0]),
-               "sailor_hip_linearize_depth", ctx.handle)
+    ctx.call("sailor_hip_linearize_depth", C.byref(frame), _ptr(raw), _ptr(out), raw.shape[1], raw.shape[0])
     return out
 
 
@@ -105,15 +113,12 @@ class PreparedLights:
         self.prepare(0, lights_num)
 
     def prepare(self, first: int, count: int, ctx: "HipContext | None" = None):
-        ctx = ctx or self.ctx
-        _lib.check(ctx._lib.sailor_hip_prepare_lights(ctx.handle, _ptr(self.lights), first, count, self.capacity, _ptr(self.buffer), self.buffer.numel()),
-                   "sailor_hip_prepare_lights", ctx.handle)
+        (ctx or self.ctx).call("sailor_hip_prepare_lights", _ptr(self.lights), first, count, self.capacity, _ptr(self.buffer), self.buffer.numel())
 
     def views(self):
         """(posRadius float32 [capacity, 4], type int32 [capacity], staged float32 [capacity, 5, 4]) as tensors over the buffer"""
-        lib = self.ctx._lib
         a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        _lib.check(lib.sailor_hip_prepared_lights_views(self.capacity, _ptr(self.buffer), C.byref(a), C.byref(b), C.byref(c)), "sailor_hip_prepared_lights_views")
+        _lib.call("sailor_hip_prepared_lights_views", self.capacity, _ptr(self.buffer), C.byref(a), C.byref(b), C.byref(c))
         base = self.buffer.data_ptr()
         n = self.capacity
         f = self.buffer
@@ -121,12 +126,20 @@ class PreparedLights:
                 f[c.value - base: c.value - base + 80 * n].view(torch.float32).view(n, 5, 4))
 
 
+def _prepared_args(prepared: "PreparedLights | None", lights_num: int):
+    """(the prepared buffer, its capacity) as the `_prepared` and `_tile_lists` entries take them: (NULL, 0) without prepared lights"""
+    if prepared is None:
+        return None, 0
+    assert lights_num <= prepared.capacity
+    return _ptr(prepared.buffer), prepared.capacity
+
+
 class ForwardPlus:
     """Cull + shade for one band of a W x H frame on one GPU."""
 
     def __init__(self, ctx: HipContext, width: int, height: int, max_lights: int, band: Band | None = None, prepared: "PreparedLights | None" = None):
-        """prepared: the prepared views of the light buffer this object will be used with -- cull() and shade() then go through the prepared entry
-        points unless told otherwise per call"""
+        """prepared: the prepared views of the light buffer this object will be used with -- cull() and shade() then hand them to the kernels unless told
+        otherwise per call"""
         self.ctx, self.W, self.H, self.max_lights = ctx, width, height, max_lights
         self.prepared = prepared
         self.Tx, self.Ty = host.num_tiles(width, height)
@@ -149,8 +162,7 @@ class ForwardPlus:
         # the cull's own per-tile form of the lists (tileNum[t] entries at tileLists[128 t ..]): what the shade reads by default -- the canonical
         # grid / culledLights are then only needed by other consumers, and k1_pack can run beside the shade (cull(..., defer_pack=True) + pack())
         a, b = C.c_void_p(), C.c_void_p()
-        _lib.check(lib.sailor_hip_light_cull_tile_lists(width, height, max_lights, C.byref(self.band), _ptr(self.workspace), C.byref(a), C.byref(b)),
-                   "sailor_hip_light_cull_tile_lists")
+        _lib.call("sailor_hip_light_cull_tile_lists", width, height, max_lights, C.byref(self.band), _ptr(self.workspace), C.byref(a), C.byref(b))
         self.tile_num, self.tile_lists = a.value, b.value
         self.shade_from_tile_lists = os.environ.get("SAILOR_SHADE_CANONICAL_LISTS") is None
 
@@ -170,26 +182,15 @@ class ForwardPlus:
             assert prepared is not None
             flags |= _lib.CULL_PREPARE_LIGHTS
         pc = host.push_constants(frame, self.W, self.H, lights_num)
-        ctx = ctx or self.ctx
-        lib = ctx._lib
-        if prepared is not None:
-            assert lights_num <= prepared.capacity
-            _lib.check(lib.sailor_hip_light_cull_prepared(ctx.handle, C.byref(frame), C.byref(pc), _ptr(lights), _ptr(depth), _ptr(self.grid), _ptr(self.culled),
-                                                          self.culled.numel(), _ptr(self.workspace), self.workspace.numel(), C.byref(self.band), flags,
-                                                          _ptr(prepared.buffer), prepared.capacity),
-                       "sailor_hip_light_cull_prepared", ctx.handle)
-        else:
-            _lib.check(lib.sailor_hip_light_cull(ctx.handle, C.byref(frame), C.byref(pc), _ptr(lights), _ptr(depth), _ptr(self.grid), _ptr(self.culled),
-                                                 self.culled.numel(), _ptr(self.workspace), self.workspace.numel(), C.byref(self.band), flags),
-                       "sailor_hip_light_cull", ctx.handle)
+        (ctx or self.ctx).call("sailor_hip_light_cull_prepared", C.byref(frame), C.byref(pc), _ptr(lights), _ptr(depth), _ptr(self.grid), _ptr(self.culled),
+                               self.culled.numel(), _ptr(self.workspace), self.workspace.numel(), C.byref(self.band), flags, *_prepared_args(prepared, lights_num))
         self._culled_once = True
         return self.grid, self.culled
 
     def pack(self, ctx: "HipContext | None" = None):
         """the second half of a cull(..., defer_pack=True): lightsGrid / culledLights from the per-tile lists, on ctx's stream (default: the cull's)"""
-        ctx = ctx or self.ctx
-        _lib.check(ctx._lib.sailor_hip_light_cull_pack(ctx.handle, self.W, self.H, self.max_lights, C.byref(self.band), _ptr(self.workspace), _ptr(self.grid),
-                                                       _ptr(self.culled), self.culled.numel()), "sailor_hip_light_cull_pack", ctx.handle)
+        (ctx or self.ctx).call("sailor_hip_light_cull_pack", self.W, self.H, self.max_lights, C.byref(self.band), _ptr(self.workspace), _ptr(self.grid),
+                               _ptr(self.culled), self.culled.numel())
 
     # -- K2 + K3 --------------------------------------------------------------------------------------------------
     def shade(self, frame: UboFrameData, surface: torch.Tensor, lights: torch.Tensor, lights_num: int, csm: CsmDesc | None = None,
@@ -197,65 +198,35 @@ class ForwardPlus:
               ctx: "HipContext | None" = None) -> torch.Tensor:
         """surface: float32 [3, band rows, W, 4]; returns radiance float32 [band rows, W, 4].  ibl: ambient term (its `ao`
         pointer, if any, holds the band's rows).  ctx: record on another context's stream."""
+        ctx = ctx or self.ctx
         rows = self.band.fbRowCount
-        own_ctx = self.ctx
-        if ctx is not None:
-            self.ctx = ctx
-        try:
-            return self._shade(frame, surface, lights, lights_num, csm, out, ibl, prepared, rows)
-        finally:
-            self.ctx = own_ctx
-
-    def _shade(self, frame, surface, lights, lights_num, csm, out, ibl, prepared, rows):
         assert surface.dtype == torch.float32 and surface.is_contiguous() and surface.shape == (3, rows, self.W, 4), surface.shape
         if out is None:
             if self.radiance is None:
-                self.radiance = torch.empty((rows, self.W, 4), dtype=torch.float32, device=self.ctx.device)
+                self.radiance = torch.empty((rows, self.W, 4), dtype=torch.float32, device=ctx.device)
             out = self.radiance
-        lib = self.ctx._lib
         prepared = prepared if prepared is not None else self.prepared
         order = self.tile_order if (self.use_tile_order and self._culled_once) else None  # only lists made by THIS object's cull have an order
         if self.shade_from_tile_lists and self._culled_once:
             # the lists where the cull left them (the same entries in the same order as grid / culledLights: the same radiance bit for bit)
-            if prepared is not None:
-                assert lights_num <= prepared.capacity
-            _lib.check(lib.sailor_hip_shade_tile_lists(self.ctx.handle, C.byref(frame), _ptr(surface), rows * self.W, _ptr(lights), lights_num, self.tile_num,
-                                                       self.tile_lists, C.byref(csm) if csm is not None else None, C.byref(ibl) if ibl is not None else None,
-                                                       _ptr(out), C.byref(self.band), order, _ptr(prepared.buffer) if prepared is not None else None,
-                                                       prepared.capacity if prepared is not None else 0),
-                       "sailor_hip_shade_tile_lists", self.ctx.handle)
-            return out
-        if prepared is not None:
-            assert lights_num <= prepared.capacity
-            _lib.check(lib.sailor_hip_shade_prepared(self.ctx.handle, C.byref(frame), _ptr(surface), rows * self.W, _ptr(lights), lights_num, _ptr(self.grid),
-                                                     _ptr(self.culled), C.byref(csm) if csm is not None else None, C.byref(ibl) if ibl is not None else None,
-                                                     _ptr(out), C.byref(self.band), order, _ptr(prepared.buffer), prepared.capacity),
-                       "sailor_hip_shade_prepared", self.ctx.handle)
-            return out
-        if ibl is not None or order is not None:
-            _lib.check(lib.sailor_hip_shade_ex(self.ctx.handle, C.byref(frame), _ptr(surface), rows * self.W, _ptr(lights), lights_num, _ptr(self.grid),
-                                               _ptr(self.culled), C.byref(csm) if csm is not None else None, C.byref(ibl) if ibl is not None else None,
-                                               _ptr(out), C.byref(self.band), order),
-                       "sailor_hip_shade_ex", self.ctx.handle)
-            return out
-        _lib.check(lib.sailor_hip_shade(self.ctx.handle, C.byref(frame), _ptr(surface), rows * self.W, _ptr(lights), lights_num, _ptr(self.grid),
-                                        _ptr(self.culled), C.byref(csm) if csm is not None else None, _ptr(out), C.byref(self.band)),
-                   "sailor_hip_shade", self.ctx.handle)
+            entry, lists = "sailor_hip_shade_tile_lists", (self.tile_num, self.tile_lists)
+        else:
+            entry, lists = "sailor_hip_shade_prepared", (_ptr(self.grid), _ptr(self.culled))
+        ctx.call(entry, C.byref(frame), _ptr(surface), rows * self.W, _ptr(lights), lights_num, *lists, _ref(csm), _ref(ibl), _ptr(out), C.byref(self.band), order,
+                 *_prepared_args(prepared, lights_num))
         return out
 
     # -- helpers ----------------------------------------------------------------------------------------------------
     def cull_diagnostics(self, lights_num: int) -> dict:
         out = (C.c_uint64 * 8)()
-        _lib.check(self.ctx._lib.sailor_hip_light_cull_diagnostics(self.ctx.handle, self.W, self.H, lights_num, C.byref(self.band),
-                                                                   _ptr(self.workspace), out), "light_cull_diagnostics", self.ctx.handle)
+        self.ctx.call("sailor_hip_light_cull_diagnostics", self.W, self.H, lights_num, C.byref(self.band), _ptr(self.workspace), out)
         keys = ["bands", "mask_bits", "groups", "group_list_sum", "groups_overflowed", "group_list_max", "words_per_band", "column_mask_bits"]
         return dict(zip(keys, [int(v) for v in out]))
 
     def band_selection(self, lights_num: int):
         """(M, lightMap uint32[M]) of the last cull with lights_num lights, if that cull ran the band selection (the caller knows: HipContext.launches_of)"""
         a, b = C.c_void_p(), C.c_void_p()
-        _lib.check(self.ctx._lib.sailor_hip_light_cull_band_selection(self.W, self.H, lights_num, C.byref(self.band), _ptr(self.workspace), C.byref(a), C.byref(b)),
-                   "sailor_hip_light_cull_band_selection")
+        _lib.call("sailor_hip_light_cull_band_selection", self.W, self.H, lights_num, C.byref(self.band), _ptr(self.workspace), C.byref(a), C.byref(b))
         self.ctx.synchronize()
         base = self.workspace.data_ptr()
         m = int(self.workspace[a.value - base: a.value - base + 4].view(torch.int32).cpu().numpy().view(np.uint32)[0])
@@ -315,8 +286,7 @@ def evsm_blur(ctx: "HipContext", moments: torch.Tensor, radius_umbra: int, radiu
     assert moments.dtype == torch.float32 and moments.dim() == 3 and moments.shape[2] == 4 and moments.is_contiguous()
     if temp is None:
         temp = torch.empty_like(moments)
-    _lib.check(ctx._lib.sailor_hip_evsm_blur(ctx.handle, _ptr(moments), _ptr(temp), moments.shape[1], moments.shape[0], radius_umbra, radius_penumbra),
-               "sailor_hip_evsm_blur", ctx.handle)
+    ctx.call("sailor_hip_evsm_blur", _ptr(moments), _ptr(temp), moments.shape[1], moments.shape[0], radius_umbra, radius_penumbra)
     return moments
 
 
@@ -325,44 +295,29 @@ def evsm_blur_pass(ctx: "HipContext", src: torch.Tensor, radius_umbra: int, radi
     assert src.dtype == torch.float32 and src.dim() == 3 and src.shape[2] == 4 and src.is_contiguous()
     if out is None:
         out = torch.empty_like(src)
-    _lib.check(ctx._lib.sailor_hip_evsm_blur_pass(ctx.handle, _ptr(src), _ptr(out), src.shape[1], src.shape[0], radius_umbra, radius_penumbra, int(vertical)),
-               "sailor_hip_evsm_blur_pass", ctx.handle)
+    ctx.call("sailor_hip_evsm_blur_pass", _ptr(src), _ptr(out), src.shape[1], src.shape[0], radius_umbra, radius_penumbra, int(vertical))
     return out
 
 
 def compute_brdf_lut(ctx: "HipContext", width: int, height: int) -> torch.Tensor:
     """ComputeBrdfLut.shader on the GPU -> float32 [height, width, 2]"""
     out = torch.empty((height, width, 2), dtype=torch.float32, device=ctx.device)
-    _lib.check(ctx._lib.sailor_hip_compute_brdf_lut(ctx.handle, _ptr(out), width, height), "sailor_hip_compute_brdf_lut", ctx.handle)
+    ctx.call("sailor_hip_compute_brdf_lut", _ptr(out), width, height)
     return out
 
 
 def compute_irradiance_map(ctx: "HipContext", env_chain: torch.Tensor, env_size: int, env_levels: int, size: int) -> torch.Tensor:
     """ComputeIrradianceMap.shader on the GPU: flat RGBA32F cube mip chain -> float32 [6, size, size, 4]"""
     out = torch.empty((6, size, size, 4), dtype=torch.float32, device=ctx.device)
-    _lib.check(ctx._lib.sailor_hip_compute_irradiance_map(ctx.handle, _ptr(env_chain), env_size, env_levels, _ptr(out), size),
-               "sailor_hip_compute_irradiance_map", ctx.handle)
+    ctx.call("sailor_hip_compute_irradiance_map", _ptr(env_chain), env_size, env_levels, _ptr(out), size)
     return out
 
 
 def prefilter_env_map(ctx: "HipContext", raw_chain: torch.Tensor, size: int, levels: int) -> torch.Tensor:
     """EnvironmentNode's specular pre-filter (ComputeEnvMap_IBL.shader per mip) on the GPU: flat chain -> flat chain"""
     out = torch.empty_like(raw_chain)
-    _lib.check(ctx._lib.sailor_hip_prefilter_env_map(ctx.handle, _ptr(raw_chain), _ptr(out), size, levels), "sailor_hip_prefilter_env_map", ctx.handle)
+    ctx.call("sailor_hip_prefilter_env_map", _ptr(raw_chain), _ptr(out), size, levels)
     return out
-
-
-def raw_env_cubemap(ctx: "HipContext", equirect: torch.Tensor, size: int, levels: int, repeat: bool = True, cover=None) -> torch.Tensor:
-    """EnvironmentNode.cpp:116-140: ConvertEquirect2Cubemap + GenerateMipMaps -> the flat RGBA32F chain of `rawEnvCubemap`.
-    `equirect` is float32 [H, W, 4]; `cover` = (w, h) mirrors the reference's equirectExtent / 32 dispatch (default: the whole cube)."""
-    assert equirect.dtype == torch.float32 and equirect.dim() == 3 and equirect.shape[2] == 4 and equirect.is_contiguous()
-    total = sum(6 * max(size >> l, 1) ** 2 * 4 for l in range(levels))
-    chain = torch.zeros(total, dtype=torch.float32, device=ctx.device)
-    cw, ch = (size, size) if cover is None else cover
-    _lib.check(ctx._lib.sailor_hip_equirect_to_cube(ctx.handle, _ptr(equirect), equirect.shape[1], equirect.shape[0], 1 if repeat else 0,
-                                                    _ptr(chain), size, cw, ch), "sailor_hip_equirect_to_cube", ctx.handle)
-    _lib.check(ctx._lib.sailor_hip_generate_mipmaps_cube(ctx.handle, _ptr(chain), size, levels), "sailor_hip_generate_mipmaps_cube", ctx.handle)
-    return chain
 
 
 def cube_chain_floats(size: int, levels: int) -> int:
@@ -370,11 +325,22 @@ def cube_chain_floats(size: int, levels: int) -> int:
     return sum(6 * max(size >> l, 1) ** 2 * 4 for l in range(levels))
 
 
+def raw_env_cubemap(ctx: "HipContext", equirect: torch.Tensor, size: int, levels: int, repeat: bool = True, cover=None) -> torch.Tensor:
+    """EnvironmentNode.cpp:116-140: ConvertEquirect2Cubemap + GenerateMipMaps -> the flat RGBA32F chain of `rawEnvCubemap`.
+    `equirect` is float32 [H, W, 4]; `cover` = (w, h) mirrors the reference's equirectExtent / 32 dispatch (default: the whole cube)."""
+    assert equirect.dtype == torch.float32 and equirect.dim() == 3 and equirect.shape[2] == 4 and equirect.is_contiguous()
+    chain = torch.zeros(cube_chain_floats(size, levels), dtype=torch.float32, device=ctx.device)
+    cw, ch = (size, size) if cover is None else cover
+    ctx.call("sailor_hip_equirect_to_cube", _ptr(equirect), equirect.shape[1], equirect.shape[0], 1 if repeat else 0, _ptr(chain), size, cw, ch)
+    ctx.call("sailor_hip_generate_mipmaps_cube", _ptr(chain), size, levels)
+    return chain
+
+
 def sky_fill(ctx: "HipContext", frame: UboFrameData, params, width: int = _lib.SKY_RESOLUTION, height: int | None = None) -> torch.Tensor:
     """Sky.shader {FILL} (SkyNode.cpp:536-563): the atmosphere as seen through `frame` -> float32 [height, width, 4]"""
     height = width if height is None else height
     out = torch.empty((height, width, 4), dtype=torch.float32, device=ctx.device)
-    _lib.check(ctx._lib.sailor_hip_sky_fill(ctx.handle, C.byref(frame), C.byref(params), _ptr(out), width, height), "sailor_hip_sky_fill", ctx.handle)
+    ctx.call("sailor_hip_sky_fill", C.byref(frame), C.byref(params), _ptr(out), width, height)
     return out
 
 
@@ -382,8 +348,7 @@ def sky_sun(ctx: "HipContext", frame: UboFrameData, params, size: int = _lib.SKY
     """Sky.shader {SUN} (SkyNode.cpp:611-642): the sun disk -> float32 [size, size, 4]; `clouds` = None is the cleared clouds target"""
     out = torch.empty((size, size, 4), dtype=torch.float32, device=ctx.device)
     cw, ch = (0, 0) if clouds is None else (clouds.shape[1], clouds.shape[0])
-    _lib.check(ctx._lib.sailor_hip_sky_sun(ctx.handle, C.byref(frame), C.byref(params), _ptr(clouds), cw, ch, _ptr(out), size, size), "sailor_hip_sky_sun",
-               ctx.handle)
+    ctx.call("sailor_hip_sky_sun", C.byref(frame), C.byref(params), _ptr(clouds), cw, ch, _ptr(out), size, size)
     return out
 
 
@@ -396,8 +361,8 @@ def sky_compose(ctx: "HipContext", frame: UboFrameData, params, sky: torch.Tenso
     if out is None:
         out = torch.empty((band.fbRowCount, width, 4), dtype=torch.float32, device=ctx.device)
     assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (band.fbRowCount, width, 4), tuple(out.shape)
-    _lib.check(ctx._lib.sailor_hip_sky_compose(ctx.handle, C.byref(frame), C.byref(params), _ptr(sky), sky.shape[1], sky.shape[0], _ptr(sun), sun.shape[1],
-                                               sun.shape[0], _ptr(out), width, height, C.byref(band)), "sailor_hip_sky_compose", ctx.handle)
+    ctx.call("sailor_hip_sky_compose", C.byref(frame), C.byref(params), _ptr(sky), sky.shape[1], sky.shape[0], _ptr(sun), sun.shape[1], sun.shape[0], _ptr(out), width,
+             height, C.byref(band))
     return out
 
 
@@ -413,10 +378,9 @@ def sky_clouds(ctx: "HipContext", frame: UboFrameData, params, sky: torch.Tensor
     if out is None:
         out = torch.empty((height, width, 4), dtype=torch.float32, device=ctx.device)
     assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (height, width, 4), tuple(out.shape)
-    _lib.check(ctx._lib.sailor_hip_sky_clouds(ctx.handle, C.byref(frame), C.byref(params), _ptr(sky), sky.shape[1], sky.shape[0], _ptr(weather), weather.shape[1],
-                                              weather.shape[0], _ptr(noise_low), noise_low.shape[0], _ptr(noise_high), noise_high.shape[0], _ptr(noise),
-                                              noise.shape[1], noise.shape[0], _ptr(linear_depth), linear_depth.shape[1], linear_depth.shape[0], _ptr(out), width,
-                                              height), "sailor_hip_sky_clouds", ctx.handle)
+    ctx.call("sailor_hip_sky_clouds", C.byref(frame), C.byref(params), _ptr(sky), sky.shape[1], sky.shape[0], _ptr(weather), weather.shape[1], weather.shape[0],
+             _ptr(noise_low), noise_low.shape[0], _ptr(noise_high), noise_high.shape[0], _ptr(noise), noise.shape[1], noise.shape[0], _ptr(linear_depth),
+             linear_depth.shape[1], linear_depth.shape[0], _ptr(out), width, height)
     return out
 
 
@@ -424,8 +388,7 @@ def sky_sun_clouds(ctx: "HipContext", frame: UboFrameData, params, clouds: torch
     """Sky.shader {SUN} behind the clouds plane (Sky.shader:707-715): zero where the clouds' alpha is >= 0.5 -> float32 [size, size, 4]"""
     assert clouds.dtype == torch.float32 and clouds.is_contiguous() and clouds.dim() == 3 and clouds.shape[2] == 4, (clouds.dtype, tuple(clouds.shape))
     out = torch.empty((size, size, 4), dtype=torch.float32, device=ctx.device)
-    _lib.check(ctx._lib.sailor_hip_sky_sun_clouds(ctx.handle, C.byref(frame), C.byref(params), _ptr(clouds), clouds.shape[1], clouds.shape[0], _ptr(out), size,
-                                                  size), "sailor_hip_sky_sun_clouds", ctx.handle)
+    ctx.call("sailor_hip_sky_sun_clouds", C.byref(frame), C.byref(params), _ptr(clouds), clouds.shape[1], clouds.shape[0], _ptr(out), size, size)
     return out
 
 
@@ -434,8 +397,7 @@ def sky_blit_clouds(ctx: "HipContext", clouds: torch.Tensor, target: torch.Tenso
     band = band or host.band_whole_frame(width, height)
     assert clouds.dtype == torch.float32 and clouds.is_contiguous() and clouds.dim() == 3 and clouds.shape[2] == 4, (clouds.dtype, tuple(clouds.shape))
     assert target.dtype == torch.float32 and target.is_contiguous() and tuple(target.shape) == (band.fbRowCount, width, 4), tuple(target.shape)
-    _lib.check(ctx._lib.sailor_hip_sky_blit_clouds(ctx.handle, _ptr(clouds), clouds.shape[1], clouds.shape[0], _ptr(target), width, height, C.byref(band)),
-               "sailor_hip_sky_blit_clouds", ctx.handle)
+    ctx.call("sailor_hip_sky_blit_clouds", _ptr(clouds), clouds.shape[1], clouds.shape[0], _ptr(target), width, height, C.byref(band))
     return target
 
 
@@ -445,8 +407,7 @@ def sky_sun_shafts(ctx: "HipContext", frame: UboFrameData, params, clouds: torch
     band = band or host.band_whole_frame(width, height)
     assert clouds.dtype == torch.float32 and clouds.is_contiguous() and clouds.dim() == 3 and clouds.shape[2] == 4, (clouds.dtype, tuple(clouds.shape))
     assert target.dtype == torch.float32 and target.is_contiguous() and tuple(target.shape) == (band.fbRowCount, width, 4), tuple(target.shape)
-    _lib.check(ctx._lib.sailor_hip_sky_sun_shafts(ctx.handle, C.byref(frame), C.byref(params), _ptr(clouds), clouds.shape[1], clouds.shape[0], _ptr(target),
-                                                  width, height, C.byref(band)), "sailor_hip_sky_sun_shafts", ctx.handle)
+    ctx.call("sailor_hip_sky_sun_shafts", C.byref(frame), C.byref(params), _ptr(clouds), clouds.shape[1], clouds.shape[0], _ptr(target), width, height, C.byref(band))
     return target
 
 
@@ -472,18 +433,16 @@ class SkyStars:
             assert clouds.dtype == torch.float32 and clouds.is_contiguous() and clouds.dim() == 3 and clouds.shape[2] == 4, (clouds.dtype, tuple(clouds.shape))
         cw, ch = (0, 0) if clouds is None else (clouds.shape[1], clouds.shape[0])
         model = np.ascontiguousarray(model, dtype=np.float32).reshape(16)
-        _lib.check(ctx._lib.sailor_hip_sky_stars_bind_workspace(ctx.handle, _ptr(self.workspace), self.workspace.numel()), "sailor_hip_sky_stars_bind_workspace",
-                   ctx.handle)
-        _lib.check(ctx._lib.sailor_hip_sky_stars(ctx.handle, C.byref(frame), model.ctypes.data_as(C.POINTER(C.c_float)), _ptr(self.positions), _ptr(self.colors),
-                                                 self.count, _ptr(clouds), cw, ch, _ptr(target), width, height, C.byref(band)), "sailor_hip_sky_stars", ctx.handle)
+        ctx.call("sailor_hip_sky_stars_bind_workspace", _ptr(self.workspace), self.workspace.numel())
+        ctx.call("sailor_hip_sky_stars", C.byref(frame), model.ctypes.data_as(C.POINTER(C.c_float)), _ptr(self.positions), _ptr(self.colors), self.count, _ptr(clouds),
+                 cw, ch, _ptr(target), width, height, C.byref(band))
         return target
 
 
 def sky_env_face(ctx: "HipContext", camera_position, params, chain: torch.Tensor, size: int, face: int) -> torch.Tensor:
     """one face of g_skyCubemap's level 0 (SkyNode.cpp:764-797), written into the flat RGBA32F chain"""
     cam = np.ascontiguousarray(camera_position, dtype=np.float32).reshape(-1)[:3].copy()
-    _lib.check(ctx._lib.sailor_hip_sky_env_face(ctx.handle, cam.ctypes.data_as(C.POINTER(C.c_float)), C.byref(params), _ptr(chain), size, face),
-               "sailor_hip_sky_env_face", ctx.handle)
+    ctx.call("sailor_hip_sky_env_face", cam.ctypes.data_as(C.POINTER(C.c_float)), C.byref(params), _ptr(chain), size, face)
     return chain
 
 
@@ -491,8 +450,7 @@ def sky_env_cubemap(ctx: "HipContext", camera_position, params, size: int = _lib
     """g_skyCubemap in one call (six faces + GenerateMipMaps, SkyNode.cpp:749-818) -> the flat RGBA32F chain"""
     cam = np.ascontiguousarray(camera_position, dtype=np.float32).reshape(-1)[:3].copy()
     chain = torch.zeros(cube_chain_floats(size, levels), dtype=torch.float32, device=ctx.device)
-    _lib.check(ctx._lib.sailor_hip_sky_env_cubemap(ctx.handle, cam.ctypes.data_as(C.POINTER(C.c_float)), C.byref(params), _ptr(chain), size, levels),
-               "sailor_hip_sky_env_cubemap", ctx.handle)
+    ctx.call("sailor_hip_sky_env_cubemap", cam.ctypes.data_as(C.POINTER(C.c_float)), C.byref(params), _ptr(chain), size, levels)
     return chain
 
 
@@ -528,22 +486,20 @@ class Bloom:
         self._check(chain)
         (sw, sh), (dw, dh) = self.extents[i], self.extents[i + 1]
         t = host.bloom_push_constants(self.params.threshold, self.params.knee)
-        _lib.check(self.ctx._lib.sailor_hip_bloom_downscale(self.ctx.handle, _ptr(self.level(chain, i)), sw, sh, _ptr(self.level(chain, i + 1)), dw, dh,
-                                                            t.ctypes.data_as(C.POINTER(C.c_float)), 1 if i == 0 else 0), "sailor_hip_bloom_downscale", self.ctx.handle)
+        self.ctx.call("sailor_hip_bloom_downscale", _ptr(self.level(chain, i)), sw, sh, _ptr(self.level(chain, i + 1)), dw, dh, t.ctypes.data_as(C.POINTER(C.c_float)),
+                      1 if i == 0 else 0)
 
     def upscale(self, chain: torch.Tensor, i: int) -> None:
         """one Dispatch of the upscale loop: level i added to level i - 1"""
         self._check(chain)
         (sw, sh), (dw, dh) = self.extents[i], self.extents[i - 1]
-        _lib.check(self.ctx._lib.sailor_hip_bloom_upscale(self.ctx.handle, _ptr(self.level(chain, i)), sw, sh, _ptr(self.level(chain, i - 1)), dw, dh, i,
-                                                          self.params.bloomIntensity, self.params.dirtIntensity, *self._dirt_args()),
-                   "sailor_hip_bloom_upscale", self.ctx.handle)
+        self.ctx.call("sailor_hip_bloom_upscale", _ptr(self.level(chain, i)), sw, sh, _ptr(self.level(chain, i - 1)), dw, dh, i, self.params.bloomIntensity,
+                      self.params.dirtIntensity, *self._dirt_args())
 
     def run(self, chain: torch.Tensor) -> torch.Tensor:
         """the node's whole Process, in place; records only"""
         self._check(chain)
-        _lib.check(self.ctx._lib.sailor_hip_bloom(self.ctx.handle, _ptr(chain), self.width, self.height, self.levels, C.byref(self.params), *self._dirt_args()),
-                   "sailor_hip_bloom", self.ctx.handle)
+        self.ctx.call("sailor_hip_bloom", _ptr(chain), self.width, self.height, self.levels, C.byref(self.params), *self._dirt_args())
         return chain
 
 
@@ -551,7 +507,7 @@ def ecs_range_for_rank(n: int, rank: int, world: int):
     """(begin, end, words per rank) of rank's slice of an equal split of n entities in whole visibility words (sailor_hip_ecs_range_for_rank; pure host
     arithmetic, no device)"""
     b, e, per = C.c_uint32(), C.c_uint32(), C.c_uint32()
-    _lib.check(_lib.load().sailor_hip_ecs_range_for_rank(n, rank, world, C.byref(b), C.byref(e), C.byref(per)), "sailor_hip_ecs_range_for_rank")
+    _lib.call("sailor_hip_ecs_range_for_rank", n, rank, world, C.byref(b), C.byref(e), C.byref(per))
     return int(b.value), int(e.value), int(per.value)
 
 
@@ -563,12 +519,12 @@ def _scene_trace(trace: str, octree_root_size: int | None, inserted: torch.Tenso
 
 
 class EcsSweep:
-    """K4 on one GPU over level-sorted entities.  rank / world: this GPU sweeps its slice of an equal split only (sailor_hip_ecs_sweep_range); the
-    visibility buffer then has room for every rank's words and exchange_visibility() completes it.
-    trace: "flat" tests the float world boxes (the default, sailor_hip_ecs_sweep); "octree" gives RHISceneView::TraceScene's set as the reference
-    computes it over integer-truncated boxes (sailor_hip_ecs_sweep_traced) and fills `.inserted` (one bit per entity: in the octree at all) as well;
-    octree_root_size: the root's size (None = SceneView.h's 264 576).  The matrices and boxes are the same in both modes.  With world > 1 each rank's
-    `.inserted` holds its own slice's words only: exchange_visibility() gathers the visibility words, not the inserted ones."""
+    """K4 on one GPU over level-sorted entities.  rank / world: this GPU sweeps its slice of an equal split only (sailor_hip_ecs_range_for_rank; one rank of
+    one has every entity); the visibility buffer then has room for every rank's words and exchange_visibility() completes it.
+    trace: "flat" tests the float world boxes (the default: sailor_hip_ecs_sweep_traced without a trace, what sailor_hip_ecs_sweep runs); "octree" gives
+    RHISceneView::TraceScene's set as the reference computes it over integer-truncated boxes and fills `.inserted` (one bit per entity: in the octree at
+    all) as well; octree_root_size: the root's size (None = SceneView.h's 264 576).  The matrices and boxes are the same in both modes.  With world > 1
+    each rank's `.inserted` holds its own slice's words only: exchange_visibility() gathers the visibility words, not the inserted ones."""
 
     def __init__(self, ctx: HipContext, entities, rank: int = 0, world: int = 1, trace: str = "flat", octree_root_size: int | None = None):
         _scene_trace(trace, octree_root_size, None)  # an unknown mode raises before anything is allocated
@@ -590,26 +546,9 @@ class EcsSweep:
 
     def run(self, planes: np.ndarray):
         planes = np.ascontiguousarray(planes, np.float32).reshape(24)
-        lib = self.ctx._lib
-        if self.trace != "flat":
-            _lib.check(lib.sailor_hip_ecs_sweep_traced(self.ctx.handle, self.n, _ptr(self.trs), _ptr(self.parent),
-                                                       self.level_offsets.ctypes.data_as(C.POINTER(C.c_uint32)), len(self.level_offsets) - 1,
-                                                       _ptr(self.local_aabb), planes.ctypes.data_as(C.POINTER(C.c_float)),
-                                                       _ptr(self.world), _ptr(self.world_aabb), _ptr(self.visibility), self.begin, self.end,
-                                                       C.byref(self._trace)),
-                       "sailor_hip_ecs_sweep_traced", self.ctx.handle)
-        elif self.world_size == 1:
-            _lib.check(lib.sailor_hip_ecs_sweep(self.ctx.handle, self.n, _ptr(self.trs), _ptr(self.parent),
-                                                self.level_offsets.ctypes.data_as(C.POINTER(C.c_uint32)), len(self.level_offsets) - 1,
-                                                _ptr(self.local_aabb), planes.ctypes.data_as(C.POINTER(C.c_float)),
-                                                _ptr(self.world), _ptr(self.world_aabb), _ptr(self.visibility)),
-                       "sailor_hip_ecs_sweep", self.ctx.handle)
-        else:
-            _lib.check(lib.sailor_hip_ecs_sweep_range(self.ctx.handle, self.n, _ptr(self.trs), _ptr(self.parent),
-                                                      self.level_offsets.ctypes.data_as(C.POINTER(C.c_uint32)), len(self.level_offsets) - 1,
-                                                      _ptr(self.local_aabb), planes.ctypes.data_as(C.POINTER(C.c_float)),
-                                                      _ptr(self.world), _ptr(self.world_aabb), _ptr(self.visibility), self.begin, self.end),
-                       "sailor_hip_ecs_sweep_range", self.ctx.handle)
+        self.ctx.call("sailor_hip_ecs_sweep_traced", self.n, _ptr(self.trs), _ptr(self.parent), self.level_offsets.ctypes.data_as(C.POINTER(C.c_uint32)),
+                      len(self.level_offsets) - 1, _ptr(self.local_aabb), planes.ctypes.data_as(C.POINTER(C.c_float)), _ptr(self.world), _ptr(self.world_aabb),
+                      _ptr(self.visibility), self.begin, self.end, C.byref(self._trace) if self.trace != "flat" else None)
         return self.world, self.world_aabb, self.visibility
 
     def exchange_visibility(self, comm=None, group=None):
@@ -618,9 +557,7 @@ class EcsSweep:
         if self.world_size == 1:
             return self.visibility
         if comm is not None:
-            _lib.check(self.ctx._lib.sailor_hip_exchange_visibility(self.ctx.handle, comm.handle, self.rank, self.world_size, self.n, _ptr(self.visibility),
-                                                                        self.visibility.numel()),
-                       "sailor_hip_exchange_visibility", self.ctx.handle)
+            self.ctx.call("sailor_hip_exchange_visibility", comm.handle, self.rank, self.world_size, self.n, _ptr(self.visibility), self.visibility.numel())
         else:
             from . import dist as sdist
             sdist.allgather_visibility(self.visibility, self.rank, self.world_size, self.words_per_rank, group)
@@ -636,10 +573,8 @@ def raster_depth(ctx: "HipContext", light_matrix, positions: torch.Tensor, indic
     lm = np.ascontiguousarray(light_matrix, np.float32).reshape(16)
     out = depth if depth is not None else torch.empty((height, width), dtype=torch.float32, device=ctx.device)
     n = models.shape[0] if instance_ids is None else instance_ids.numel()
-    _lib.check(ctx._lib.sailor_hip_raster_depth(ctx.handle, lm.ctypes.data_as(C.POINTER(C.c_float)), _ptr(positions), _ptr(indices), indices.numel() // 3,
-                                                _ptr(models), _ptr(instance_ids) if instance_ids is not None else None, n, width, height, _ptr(out),
-                                                (0 if depth is not None else _lib.RASTER_CLEAR) | (_lib.RASTER_CULL_BACK if cull_back else 0), _ptr(coarse)),
-               "sailor_hip_raster_depth", ctx.handle)
+    ctx.call("sailor_hip_raster_depth", lm.ctypes.data_as(C.POINTER(C.c_float)), _ptr(positions), _ptr(indices), indices.numel() // 3, _ptr(models), _ptr(instance_ids),
+             n, width, height, _ptr(out), (0 if depth is not None else _lib.RASTER_CLEAR) | (_lib.RASTER_CULL_BACK if cull_back else 0), _ptr(coarse))
     return out
 
 
@@ -648,10 +583,8 @@ def raster_depth_camera(ctx: "HipContext", frame, positions: torch.Tensor, indic
     """sailor_hip_raster_depth_camera: the depth prepass -> raw reversed-Z depth float32 [height, width] (0 = nothing drawn)"""
     out = torch.empty((height, width), dtype=torch.float32, device=ctx.device)
     n = models.shape[0] if instance_ids is None else instance_ids.numel()
-    _lib.check(ctx._lib.sailor_hip_raster_depth_camera(ctx.handle, C.byref(frame), _ptr(positions), _ptr(indices), indices.numel() // 3, _ptr(models),
-                                                       _ptr(instance_ids) if instance_ids is not None else None, n, width, height, _ptr(out),
-                                                       _lib.RASTER_CLEAR | (_lib.RASTER_CULL_BACK if cull_back else 0), _ptr(coarse)),
-               "sailor_hip_raster_depth_camera", ctx.handle)
+    ctx.call("sailor_hip_raster_depth_camera", C.byref(frame), _ptr(positions), _ptr(indices), indices.numel() // 3, _ptr(models), _ptr(instance_ids), n, width, height,
+             _ptr(out), _lib.RASTER_CLEAR | (_lib.RASTER_CULL_BACK if cull_back else 0), _ptr(coarse))
     return out
 
 
@@ -664,7 +597,7 @@ def shadow_resolve(ctx: "HipContext", depth: torch.Tensor, fmt: int) -> torch.Te
         out = torch.empty((h, w), dtype=torch.float16, device=ctx.device)
     else:
         out = torch.empty((h, w), dtype=torch.float32, device=ctx.device)
-    _lib.check(ctx._lib.sailor_hip_shadow_resolve(ctx.handle, _ptr(depth), w, h, fmt, _ptr(out)), "sailor_hip_shadow_resolve", ctx.handle)
+    ctx.call("sailor_hip_shadow_resolve", _ptr(depth), w, h, fmt, _ptr(out))
     return out
 
 
@@ -680,12 +613,9 @@ def csm_caster_masks(ctx: "HipContext", world_aabb: torch.Tensor, cascade_planes
         raise ValueError(f"inserted must be a contiguous int64 tensor of at least {(n + 63) // 64} words")
     out = torch.empty((len(pl), (n + 63) // 64), dtype=torch.int64, device=ctx.device)  # every word is written
     if trace == "flat":
-        _lib.check(ctx._lib.sailor_hip_csm_caster_masks(ctx.handle, n, _ptr(world_aabb), pl.ctypes.data_as(C.POINTER(C.c_float)), len(pl), _ptr(out)),
-                   "sailor_hip_csm_caster_masks", ctx.handle)
+        ctx.call("sailor_hip_csm_caster_masks", n, _ptr(world_aabb), pl.ctypes.data_as(C.POINTER(C.c_float)), len(pl), _ptr(out))
     else:
-        _lib.check(ctx._lib.sailor_hip_csm_caster_masks_traced(ctx.handle, n, _ptr(world_aabb), pl.ctypes.data_as(C.POINTER(C.c_float)), len(pl), _ptr(out),
-                                                               C.byref(tr)),
-                   "sailor_hip_csm_caster_masks_traced", ctx.handle)
+        ctx.call("sailor_hip_csm_caster_masks_traced", n, _ptr(world_aabb), pl.ctypes.data_as(C.POINTER(C.c_float)), len(pl), _ptr(out), C.byref(tr))
     return out
 
 
@@ -696,7 +626,7 @@ def shadow_extract_positions(ctx: "HipContext", vertices: torch.Tensor) -> torch
     if not vertices.is_contiguous() or vertices.numel() * vertices.element_size() != 72 * n:
         raise ValueError("vertices must be a contiguous tensor of whole 72-byte records")
     out = torch.empty((n, 3), dtype=torch.float32, device=ctx.device)
-    _lib.check(ctx._lib.sailor_hip_shadow_extract_positions(ctx.handle, _ptr(vertices), n, _ptr(out)), "sailor_hip_shadow_extract_positions", ctx.handle)
+    ctx.call("sailor_hip_shadow_extract_positions", _ptr(vertices), n, _ptr(out))
     return out
 
 
@@ -720,9 +650,7 @@ def shadow_gather_instances_batched(ctx: "HipContext", instances: torch.Tensor, 
     need = int(ctx._lib.sailor_hip_shadow_gather_workspace_bytes(arr, len(jobs)))
     if workspace is None or workspace.numel() * workspace.element_size() < need:
         workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=ctx.device)
-    _lib.check(ctx._lib.sailor_hip_shadow_gather_instances_batched(ctx.handle, _ptr(instances), n, arr, len(jobs), _ptr(workspace),
-                                                                   workspace.numel() * workspace.element_size()),
-               "sailor_hip_shadow_gather_instances_batched", ctx.handle)
+    ctx.call("sailor_hip_shadow_gather_instances_batched", _ptr(instances), n, arr, len(jobs), _ptr(workspace), workspace.numel() * workspace.element_size())
     return workspace
 
 
@@ -736,9 +664,8 @@ def shadow_gather_instances(ctx: "HipContext", instances: torch.Tensor, mask: to
     need = int(ctx._lib.sailor_hip_shadow_gather_workspace_bytes(C.byref(job), 1))
     if workspace is None or workspace.numel() * workspace.element_size() < need:
         workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=ctx.device)
-    _lib.check(ctx._lib.sailor_hip_shadow_gather_instances(ctx.handle, _ptr(instances), instances.numel() * instances.element_size() // 96, _ptr(mask), begin,
-                                                           end, _ptr(out), cap, _ptr(count), _ptr(workspace), workspace.numel() * workspace.element_size()),
-               "sailor_hip_shadow_gather_instances", ctx.handle)
+    ctx.call("sailor_hip_shadow_gather_instances", _ptr(instances), instances.numel() * instances.element_size() // 96, _ptr(mask), begin, end, _ptr(out), cap, _ptr(count),
+             _ptr(workspace), workspace.numel() * workspace.element_size())
     return out, count
 
 
@@ -746,8 +673,7 @@ def hiz_build(ctx: "HipContext", depth: torch.Tensor, width: int, height: int, l
     """DepthHighZNode's loop on the GPU: raw depth [H, W] float32 -> flat level-major min pyramid"""
     total = sum(max(width >> l, 1) * max(height >> l, 1) for l in range(levels))
     out = torch.empty(total, dtype=torch.float32, device=ctx.device)
-    _lib.check(ctx._lib.sailor_hip_hiz_build(ctx.handle, _ptr(depth), depth.shape[1], depth.shape[0], _ptr(out), width, height, levels),
-               "sailor_hip_hiz_build", ctx.handle)
+    ctx.call("sailor_hip_hiz_build", _ptr(depth), depth.shape[1], depth.shape[0], _ptr(out), width, height, levels)
     return out
 
 
@@ -771,10 +697,8 @@ class MeshCull:
         desc = None
         if hiz is not None:
             desc = _lib.HiZDesc(hiz[0].data_ptr(), hiz[1], hiz[2], hiz[3])
-        _lib.check(self.ctx._lib.sailor_hip_mesh_cull_compact_ex(self.ctx.handle, C.byref(frame), _ptr(self.instances), n, first_instance,
-                                                                  _ptr(self.batches), self.num_batches, _ptr(self.workspace), self._ws_bytes,
-                                                                  C.byref(desc) if desc is not None else None),
-                   "sailor_hip_mesh_cull_compact_ex", self.ctx.handle)
+        self.ctx.call("sailor_hip_mesh_cull_compact_ex", C.byref(frame), _ptr(self.instances), n, first_instance, _ptr(self.batches), self.num_batches,
+                      _ptr(self.workspace), self._ws_bytes, _ref(desc))
         return self.instances, self.batches
 
     def download(self):
@@ -800,7 +724,7 @@ class EyeAdaptation:
         self.reset(initial_luminance)
 
     def reset(self, luminance: float = 0.5):
-        _lib.check(self.ctx._lib.sailor_hip_eye_adaptation_reset(self.ctx.handle, _ptr(self.state), luminance), "sailor_hip_eye_adaptation_reset", self.ctx.handle)
+        self.ctx.call("sailor_hip_eye_adaptation_reset", _ptr(self.state), luminance)
 
     def constants(self, delta_time: float):
         return host.eye_adaptation_constants(self.width, self.height, delta_time)
@@ -808,7 +732,7 @@ class EyeAdaptation:
     def views(self):
         """(counts, luminance): views of the 256 counts and the adapted-luminance word inside the state tensor"""
         counts, lum = C.c_void_p(), C.c_void_p()
-        _lib.check(self.ctx._lib.sailor_hip_eye_adaptation_state_views(_ptr(self.state), C.byref(counts), C.byref(lum)), "sailor_hip_eye_adaptation_state_views")
+        _lib.call("sailor_hip_eye_adaptation_state_views", _ptr(self.state), C.byref(counts), C.byref(lum))
         c0, l0 = (counts.value - self.state.data_ptr()) // 4, (lum.value - self.state.data_ptr()) // 4
         return self.state[c0:c0 + 256], self.state[l0:l0 + 1].view(torch.float32)
 
@@ -819,12 +743,10 @@ class EyeAdaptation:
         """adds the counts of the band's rows (`color`: rows x width x 4 float32) to the state's"""
         band = band or self.whole
         self._check_rows(color, band)
-        _lib.check(self.ctx._lib.sailor_hip_luminance_histogram(self.ctx.handle, _ptr(color), self.width, self.height, C.byref(band), C.byref(constants),
-                                                                _ptr(self.state)), "sailor_hip_luminance_histogram", self.ctx.handle)
+        self.ctx.call("sailor_hip_luminance_histogram", _ptr(color), self.width, self.height, C.byref(band), C.byref(constants), _ptr(self.state))
 
     def average(self, constants):
-        _lib.check(self.ctx._lib.sailor_hip_average_luminance(self.ctx.handle, C.byref(constants), _ptr(self.state)), "sailor_hip_average_luminance",
-                   self.ctx.handle)
+        self.ctx.call("sailor_hip_average_luminance", C.byref(constants), _ptr(self.state))
 
     def tonemap(self, color: torch.Tensor, out: torch.Tensor | None = None, band: Band | None = None) -> torch.Tensor:
         band = band or self.whole
@@ -832,8 +754,7 @@ class EyeAdaptation:
         if out is None:
             out = torch.empty_like(color)
         self._check_rows(out, band)
-        _lib.check(self.ctx._lib.sailor_hip_tonemap(self.ctx.handle, _ptr(color), _ptr(out), self.width, self.height, C.byref(band), self.flags,
-                                                    self.white_point, self.exposure, _ptr(self.state)), "sailor_hip_tonemap", self.ctx.handle)
+        self.ctx.call("sailor_hip_tonemap", _ptr(color), _ptr(out), self.width, self.height, C.byref(band), self.flags, self.white_point, self.exposure, _ptr(self.state))
         return out
 
     def run(self, color: torch.Tensor, delta_time: float, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -843,8 +764,8 @@ class EyeAdaptation:
             out = torch.empty_like(color)
         self._check_rows(out, self.whole)
         constants = self.constants(delta_time)
-        _lib.check(self.ctx._lib.sailor_hip_eye_adaptation(self.ctx.handle, _ptr(color), _ptr(out), self.width, self.height, C.byref(constants), self.flags,
-                                                           self.white_point, self.exposure, _ptr(self.state)), "sailor_hip_eye_adaptation", self.ctx.handle)
+        self.ctx.call("sailor_hip_eye_adaptation", _ptr(color), _ptr(out), self.width, self.height, C.byref(constants), self.flags, self.white_point, self.exposure,
+                      _ptr(self.state))
         return out
 
 
@@ -869,33 +790,28 @@ class Hbao:
 
     def blit(self, src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
         self._check_plane(src), self._check_plane(dst)
-        _lib.check(self.ctx._lib.sailor_hip_blit_nearest(self.ctx.handle, _ptr(src), src.shape[1], src.shape[0], _ptr(dst), dst.shape[1], dst.shape[0]),
-                   "sailor_hip_blit_nearest", self.ctx.handle)
+        self.ctx.call("sailor_hip_blit_nearest", _ptr(src), src.shape[1], src.shape[0], _ptr(dst), dst.shape[1], dst.shape[0])
         return dst
 
     def hbao(self, frame, depth: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
         self._check_plane(depth), self._check_plane(out)
-        _lib.check(self.ctx._lib.sailor_hip_hbao(self.ctx.handle, C.byref(frame), _ptr(depth), depth.shape[1], depth.shape[0], _ptr(self.noise),
-                                                 self.noise.shape[1], self.noise.shape[0], C.byref(self.params), _ptr(out), out.shape[1], out.shape[0]),
-                   "sailor_hip_hbao", self.ctx.handle)
+        self.ctx.call("sailor_hip_hbao", C.byref(frame), _ptr(depth), depth.shape[1], depth.shape[0], _ptr(self.noise), self.noise.shape[1], self.noise.shape[0],
+                      C.byref(self.params), _ptr(out), out.shape[1], out.shape[0])
         return out
 
     def blur_pass(self, ao: torch.Tensor, depth: torch.Tensor, out: torch.Tensor, vertical: bool) -> torch.Tensor:
         self._check_plane(ao), self._check_plane(depth), self._check_plane(out)
-        _lib.check(self.ctx._lib.sailor_hip_hbao_blur_pass(self.ctx.handle, _ptr(ao), ao.shape[1], ao.shape[0], _ptr(depth), depth.shape[1], depth.shape[0],
-                                                           C.byref(self.blur_params), _ptr(out), out.shape[1], out.shape[0], 1 if vertical else 0),
-                   "sailor_hip_hbao_blur_pass", self.ctx.handle)
+        self.ctx.call("sailor_hip_hbao_blur_pass", _ptr(ao), ao.shape[1], ao.shape[0], _ptr(depth), depth.shape[1], depth.shape[0], C.byref(self.blur_params), _ptr(out),
+                      out.shape[1], out.shape[0], 1 if vertical else 0)
         return out
 
     def run(self, frame, raw_depth: torch.Tensor) -> torch.Tensor:
         """the four launches on the raw (reversed-Z) depth attachment, height x width float32; returns g_AO"""
         self._check_plane(raw_depth)
         h, a, t, o = self.half_depth, self.ao, self.temp, self.g_ao
-        _lib.check(self.ctx._lib.sailor_hip_hbao_chain(self.ctx.handle, C.byref(frame), _ptr(raw_depth), raw_depth.shape[1], raw_depth.shape[0],
-                                                       _ptr(h), h.shape[1], h.shape[0], _ptr(self.noise), self.noise.shape[1], self.noise.shape[0],
-                                                       C.byref(self.params), _ptr(a), a.shape[1], a.shape[0], C.byref(self.blur_params),
-                                                       _ptr(t), t.shape[1], t.shape[0], _ptr(o), o.shape[1], o.shape[0]),
-                   "sailor_hip_hbao_chain", self.ctx.handle)
+        self.ctx.call("sailor_hip_hbao_chain", C.byref(frame), _ptr(raw_depth), raw_depth.shape[1], raw_depth.shape[0], _ptr(h), h.shape[1], h.shape[0], _ptr(self.noise),
+                      self.noise.shape[1], self.noise.shape[0], C.byref(self.params), _ptr(a), a.shape[1], a.shape[0], C.byref(self.blur_params), _ptr(t), t.shape[1],
+                      t.shape[0], _ptr(o), o.shape[1], o.shape[0])
         return o
 
 
@@ -911,9 +827,8 @@ class MotionBlur:
     def run(self, frame, previous_frame, raw_depth: torch.Tensor, color: torch.Tensor) -> torch.Tensor:
         assert raw_depth.dtype == torch.float32 and raw_depth.is_contiguous() and raw_depth.dim() == 2, tuple(raw_depth.shape)
         assert color.dtype == torch.float32 and color.is_contiguous() and color.dim() == 3 and color.shape[2] == 4, tuple(color.shape)
-        _lib.check(self.ctx._lib.sailor_hip_motion_blur(self.ctx.handle, C.byref(frame), C.byref(previous_frame), _ptr(raw_depth), raw_depth.shape[1],
-                                                        raw_depth.shape[0], _ptr(color), color.shape[1], color.shape[0], C.byref(self.params), _ptr(self.out),
-                                                        self.width, self.height), "sailor_hip_motion_blur", self.ctx.handle)
+        self.ctx.call("sailor_hip_motion_blur", C.byref(frame), C.byref(previous_frame), _ptr(raw_depth), raw_depth.shape[1], raw_depth.shape[0], _ptr(color),
+                      color.shape[1], color.shape[0], C.byref(self.params), _ptr(self.out), self.width, self.height)
         return self.out
 
 
@@ -933,9 +848,8 @@ class DebugView:
             assert t is None or t.is_contiguous()
         w = lambda t: 0 if t is None else t.shape[1]
         h = lambda t: 0 if t is None else t.shape[0]
-        _lib.check(self.ctx._lib.sailor_hip_debug_view(self.ctx.handle, C.byref(frame), self.mode, _ptr(scene), w(scene), h(scene), _ptr(linear_depth),
-                                                       w(linear_depth), h(linear_depth), _ptr(lights_grid), _ptr(culled_lights), _ptr(ao), w(ao), h(ao),
-                                                       _ptr(self.out), self.width, self.height), "sailor_hip_debug_view", self.ctx.handle)
+        self.ctx.call("sailor_hip_debug_view", C.byref(frame), self.mode, _ptr(scene), w(scene), h(scene), _ptr(linear_depth), w(linear_depth), h(linear_depth),
+                      _ptr(lights_grid), _ptr(culled_lights), _ptr(ao), w(ao), h(ao), _ptr(self.out), self.width, self.height)
         return self.out
 
 
@@ -955,8 +869,7 @@ class Blur:
 
     def run(self, color: torch.Tensor) -> torch.Tensor:
         _check_rgba(color)
-        _lib.check(self.ctx._lib.sailor_hip_blur(self.ctx.handle, _ptr(color), color.shape[1], color.shape[0], C.byref(self.params), self.flags, _ptr(self.out),
-                                                 self.width, self.height), "sailor_hip_blur", self.ctx.handle)
+        self.ctx.call("sailor_hip_blur", _ptr(color), color.shape[1], color.shape[0], C.byref(self.params), self.flags, _ptr(self.out), self.width, self.height)
         return self.out
 
 
@@ -971,8 +884,7 @@ class ChromaticAberration:
 
     def run(self, color: torch.Tensor) -> torch.Tensor:
         _check_rgba(color)
-        _lib.check(self.ctx._lib.sailor_hip_chromatic_aberration(self.ctx.handle, _ptr(color), color.shape[1], color.shape[0], C.byref(self.params), _ptr(self.out),
-                                                                 self.width, self.height), "sailor_hip_chromatic_aberration", self.ctx.handle)
+        self.ctx.call("sailor_hip_chromatic_aberration", _ptr(color), color.shape[1], color.shape[0], C.byref(self.params), _ptr(self.out), self.width, self.height)
         return self.out
 
 
@@ -980,8 +892,7 @@ def blit_linear(ctx: HipContext, src: torch.Tensor, dst: torch.Tensor) -> torch.
     """The Blit entry of a scaled image with Linear filtration (BlitNode.cpp:88-96): src -> dst, both (h, w, 4) RGBA32F or both (h, w) one-channel fp32"""
     assert src.dtype == dst.dtype == torch.float32 and src.is_contiguous() and dst.is_contiguous(), (src.dtype, dst.dtype)
     assert src.dim() == dst.dim() and (src.dim() == 2 or (src.dim() == 3 and src.shape[2] == dst.shape[2] == 4)), (tuple(src.shape), tuple(dst.shape))
-    _lib.check(ctx._lib.sailor_hip_blit_linear(ctx.handle, _ptr(src), src.shape[1], src.shape[0], _ptr(dst), dst.shape[1], dst.shape[0], 4 if src.dim() == 3 else 1),
-               "sailor_hip_blit_linear", ctx.handle)
+    ctx.call("sailor_hip_blit_linear", _ptr(src), src.shape[1], src.shape[0], _ptr(dst), dst.shape[1], dst.shape[0], 4 if src.dim() == 3 else 1)
     return dst
 
 
@@ -1002,7 +913,7 @@ def upload_textures(ctx: HipContext, images, srgb, mips: bool = False) -> tuple[
             chain = torch.zeros(host.mip_chain_texels(w, h, levels), dtype=torch.int32, device=ctx.device)
             chain[: h * w] = t.reshape(-1)
             t = chain
-            _lib.check(ctx._lib.sailor_hip_texture_generate_mips(ctx.handle, _ptr(t), w, h, levels, flags), "sailor_hip_texture_generate_mips", ctx.handle)
+            ctx.call("sailor_hip_texture_generate_mips", _ptr(t), w, h, levels, flags)
         keep.append(t)
         table[k] = _lib.TextureDesc(t.data_ptr(), w, h, flags, levels)
     d = torch.from_numpy(np.frombuffer(bytes(table), np.uint8).copy()).to(ctx.device)
@@ -1024,11 +935,65 @@ class SurfacePass:
         self.workspace = torch.empty(n, dtype=torch.uint8, device=ctx.device)
         self.prim_base = self.draw_index = 0
 
+    # -- what every entry of the pass takes, built in one place each -------------------------------------------------------
+    def _frame_args(self):
+        """(W, H, band, workspace, its bytes): the frame arguments of the pass's entries"""
+        return self.W, self.H, C.byref(self.band), _ptr(self.workspace), self.workspace.numel()
+
+    @staticmethod
+    def _table_args(instances, materials, textures, num_textures):
+        """(instances, materials, their count of 80-byte records, textures, their count): the table arguments of the draws and the resolves"""
+        return _ptr(instances), _ptr(materials), 0 if materials is None else materials.numel() * materials.element_size() // 80, _ptr(textures), num_textures
+
+    @staticmethod
+    def _draw_desc(d: dict, instances: torch.Tensor, prim_base: int, blend: bool = False):
+        """a draw's keyword arguments (draw()'s: vertices, indices, instance_ids, num_drawn, first_instance, cull_back, alpha_cutout, gltf; with `blend`
+        also its blend mode) -> (its SailorSurfaceDraw at prim_base, the primitives it advances the pass's primBase by)"""
+        ids, first, drawn = d.get("instance_ids"), d.get("first_instance", 0), d.get("num_drawn")
+        if drawn is None:
+            drawn = ids.numel() if ids is not None else instances.numel() * instances.element_size() // 96 - first
+        nt = d["indices"].numel() // 3
+        flags = (_lib.SURFACE_CULL_BACK if d.get("cull_back", False) else 0) | (_lib.SURFACE_ALPHA_CUTOUT if d.get("alpha_cutout", False) else 0) | \
+                (_lib.SURFACE_GLTF if d.get("gltf", False) else 0)
+        if blend:
+            mode = d.get("blend", "none")
+            flags |= (_lib.SURFACE_BLEND_MODES[mode] if isinstance(mode, str) else int(mode)) << _lib.SURFACE_BLEND_SHIFT
+        return _lib.SurfaceDraw(_ptr(d["vertices"]), _ptr(d["indices"]), _ptr(ids), nt, drawn, prim_base, flags, first, 0), host.surface_draw_prims(nt, drawn)
+
+    def _draw_descs(self, draws, instances: torch.Tensor, prim_base: int, blend: bool = False):
+        """the descriptors of a pass recorded from dicts, with the running primBase; leaves prim_base / draw_index behind the last of them"""
+        descs = []
+        for d in draws:
+            desc, prims = self._draw_desc(d, instances, prim_base, blend)
+            descs.append(desc)
+            prim_base += prims
+        self.prim_base, self.draw_index = prim_base, len(descs)
+        return descs
+
+    @staticmethod
+    def _draw_entry(route: str, desc) -> str:
+        """the draw entry of a route ("peel", "bucket", "msaa"): Standard.shader's, or Standard_glTF.shader's by the descriptor's flag"""
+        return f"sailor_hip_surface_{route}_draw_gltf" if desc.flags & _lib.SURFACE_GLTF else f"sailor_hip_surface_{route}_draw"
+
+    def _shade_layer(self, k: int, frame, scene, any_gltf: bool, ao_in, shade, on_layer, weight: torch.Tensor | None = None):
+        """The layer step: the layer in the workspace resolved (resolve_gltf if the pass holds a glTF draw) -> on_layer -> shade -> (surface, radiance,
+        emissive | None).  scene: (instances, materials, textures, num_textures).  on_layer's third argument is `weight` or, without one, the coverage."""
+        want_coverage = on_layer is not None and weight is None
+        if any_gltf:
+            surface, _, cov, ao, emissive = self.resolve_gltf(frame, *scene, ao_in=ao_in, want_depth=False, want_coverage=want_coverage)
+        else:
+            surface, _, cov = self.resolve(frame, *scene, want_depth=False, want_coverage=want_coverage)
+            ao, emissive = ao_in, None
+        if on_layer is not None:
+            on_layer(k, surface, cov if weight is None else weight, emissive, ao)
+        radiance = shade(surface, ao)
+        assert radiance.dtype == torch.float32 and radiance.shape == (self.rows, self.W, 4) and radiance.is_contiguous()
+        return surface, radiance, emissive
+
     def begin(self, depth: torch.Tensor | None = None, prim_base: int = 0):
         """depth: the prepass's raw depth of the WHOLE frame, float32 [H, W], or None"""
         assert depth is None or (depth.dtype == torch.float32 and depth.shape == (self.H, self.W) and depth.is_contiguous())
-        _lib.check(self.ctx._lib.sailor_hip_surface_begin(self.ctx.handle, _ptr(depth), self.W, self.H, C.byref(self.band), _ptr(self.workspace), self.workspace.numel()),
-                   "sailor_hip_surface_begin", self.ctx.handle)
+        self.ctx.call("sailor_hip_surface_begin", _ptr(depth), *self._frame_args())
         self.prim_base, self.draw_index = prim_base, 0
 
     def draw(self, frame: UboFrameData, vertices: torch.Tensor, indices: torch.Tensor, instances: torch.Tensor, instance_ids: torch.Tensor | None = None,
@@ -1038,20 +1003,14 @@ class SurfacePass:
         lod: through sailor_hip_surface_draw_lod -- the alpha behind ALPHA_CUTOUT is fetched at the implicit level of detail; such a pass ends with resolve_lod.
         alpha_cutout: the ALPHA_CUTOUT permutation (Standard.shader:403-408) through sailor_hip_surface_draw_masked, which needs the resolve's material and
         texture tables.  gltf: the draw's material is Standard_glTF.shader's (sailor_hip_surface_draw_gltf); such a pass ends with resolve_gltf / composite_gltf"""
-        if num_drawn is None:
-            num_drawn = instance_ids.numel() if instance_ids is not None else instances.numel() * instances.element_size() // 96 - first_instance
-        nt = indices.numel() // 3
-        flags = (_lib.SURFACE_CULL_BACK if cull_back else 0) | (_lib.SURFACE_ALPHA_CUTOUT if alpha_cutout else 0) | (_lib.SURFACE_GLTF if gltf else 0)
-        d = _lib.SurfaceDraw(_ptr(vertices), _ptr(indices), _ptr(instance_ids), nt, num_drawn, self.prim_base, flags, first_instance, 0)
+        d, prims = self._draw_desc(dict(vertices=vertices, indices=indices, instance_ids=instance_ids, num_drawn=num_drawn, first_instance=first_instance,
+                                        cull_back=cull_back, alpha_cutout=alpha_cutout, gltf=gltf), instances, self.prim_base)
         if lod or gltf or alpha_cutout:
             name = "sailor_hip_surface_draw_lod" if lod else "sailor_hip_surface_draw_gltf" if gltf else "sailor_hip_surface_draw_masked"
-            _lib.check(getattr(self.ctx._lib, name)(self.ctx.handle, C.byref(frame), C.byref(d), _ptr(instances), _ptr(materials),
-                                                    0 if materials is None else materials.numel() * materials.element_size() // 80, _ptr(textures), num_textures,
-                                                    self.draw_index, self.W, self.H, C.byref(self.band), _ptr(self.workspace), self.workspace.numel()), name, self.ctx.handle)
+            self.ctx.call(name, C.byref(frame), C.byref(d), *self._table_args(instances, materials, textures, num_textures), self.draw_index, *self._frame_args())
         else:
-            _lib.check(self.ctx._lib.sailor_hip_surface_draw(self.ctx.handle, C.byref(frame), C.byref(d), _ptr(instances), self.draw_index, self.W, self.H,
-                                                             C.byref(self.band), _ptr(self.workspace), self.workspace.numel()), "sailor_hip_surface_draw", self.ctx.handle)
-        self.prim_base += host.surface_draw_prims(nt, num_drawn)
+            self.ctx.call("sailor_hip_surface_draw", C.byref(frame), C.byref(d), _ptr(instances), self.draw_index, *self._frame_args())
+        self.prim_base += prims
         self.draw_index += 1
 
     def draw_indirect(self, frame: UboFrameData, vertices: torch.Tensor, indices: torch.Tensor, instances: torch.Tensor, command: torch.Tensor, capacity: int,
@@ -1063,23 +1022,19 @@ class SurfacePass:
         holds for the draw's guard (default: all of the tensor)."""
         if num_instance_records is None:
             num_instance_records = instances.numel() * instances.element_size() // 96
-        nt = indices.numel() // 3
-        flags = (_lib.SURFACE_CULL_BACK if cull_back else 0) | (_lib.SURFACE_ALPHA_CUTOUT if alpha_cutout else 0) | (_lib.SURFACE_GLTF if gltf else 0)
-        d = _lib.SurfaceDraw(_ptr(vertices), _ptr(indices), None, nt, capacity, self.prim_base, flags, 0, 0)
-        name = "sailor_hip_surface_draw_indirect_lod" if lod else "sailor_hip_surface_draw_indirect"
-        _lib.check(getattr(self.ctx._lib, name)(self.ctx.handle, C.byref(frame), C.byref(d), command.data_ptr() + 20 * command_index, _ptr(instances),
-                                                num_instance_records, _ptr(materials), 0 if materials is None else materials.numel() * materials.element_size() // 80,
-                                                _ptr(textures), num_textures, self.draw_index, self.W, self.H, C.byref(self.band), _ptr(self.workspace),
-                                                self.workspace.numel()), name, self.ctx.handle)
-        self.prim_base += host.surface_draw_prims(nt, capacity)
+        d, prims = self._draw_desc(dict(vertices=vertices, indices=indices, num_drawn=capacity, cull_back=cull_back, alpha_cutout=alpha_cutout, gltf=gltf), instances,
+                                   self.prim_base)
+        d_instances, *tables = self._table_args(instances, materials, textures, num_textures)
+        self.ctx.call("sailor_hip_surface_draw_indirect_lod" if lod else "sailor_hip_surface_draw_indirect", C.byref(frame), C.byref(d),
+                      command.data_ptr() + 20 * command_index, d_instances, num_instance_records, *tables, self.draw_index, *self._frame_args())
+        self.prim_base += prims
         self.draw_index += 1
 
     def store_depth(self, depth: torch.Tensor) -> torch.Tensor:
         """the keys' depth into the band's rows of `depth`, the raw depth attachment of the WHOLE frame, float32 [H, W]: the depth write of a pass that held
         cutout draws"""
         assert depth.dtype == torch.float32 and depth.shape == (self.H, self.W) and depth.is_contiguous()
-        _lib.check(self.ctx._lib.sailor_hip_surface_store_depth(self.ctx.handle, _ptr(self.workspace), self.workspace.numel(), _ptr(depth), self.W, self.H,
-                                                                C.byref(self.band)), "sailor_hip_surface_store_depth", self.ctx.handle)
+        self.ctx.call("sailor_hip_surface_store_depth", _ptr(self.workspace), self.workspace.numel(), _ptr(depth), self.W, self.H, C.byref(self.band))
         return depth
 
     def resolve(self, frame: UboFrameData, instances: torch.Tensor, materials: torch.Tensor, textures: torch.Tensor, num_textures: int, want_depth: bool = True,
@@ -1089,18 +1044,15 @@ class SurfacePass:
         surface = torch.empty((3, self.rows, self.W, 4), dtype=torch.float32, device=dev)
         depth = torch.empty((self.rows, self.W), dtype=torch.float32, device=dev) if want_depth else None
         cov = torch.empty((self.rows, self.W), dtype=torch.uint8, device=dev) if want_coverage else None
-        _lib.check(self.ctx._lib.sailor_hip_surface_resolve(self.ctx.handle, C.byref(frame), _ptr(instances), _ptr(materials),
-                                                            materials.numel() * materials.element_size() // 80, _ptr(textures), num_textures, self.W, self.H,
-                                                            C.byref(self.band), _ptr(self.workspace), self.workspace.numel(), _ptr(surface), self.rows * self.W,
-                                                            _ptr(depth), _ptr(cov)), "sailor_hip_surface_resolve", self.ctx.handle)
+        self.ctx.call("sailor_hip_surface_resolve", C.byref(frame), *self._table_args(instances, materials, textures, num_textures), *self._frame_args(), _ptr(surface),
+                      self.rows * self.W, _ptr(depth), _ptr(cov))
         return surface, depth, cov
 
     def composite(self, radiance: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         """target = covered ? radiance : target; both float32 [rows, W, 4]"""
         for t in (radiance, target):
             assert t.dtype == torch.float32 and t.shape == (self.rows, self.W, 4) and t.is_contiguous()
-        _lib.check(self.ctx._lib.sailor_hip_surface_composite(self.ctx.handle, _ptr(radiance), _ptr(self.workspace), self.workspace.numel(), _ptr(target), self.W,
-                                                              self.H, C.byref(self.band)), "sailor_hip_surface_composite", self.ctx.handle)
+        self.ctx.call("sailor_hip_surface_composite", _ptr(radiance), _ptr(self.workspace), self.workspace.numel(), _ptr(target), self.W, self.H, C.byref(self.band))
         return target
 
     def resolve_lod(self, frame: UboFrameData, instances: torch.Tensor, materials: torch.Tensor, textures: torch.Tensor, num_textures: int,
@@ -1121,18 +1073,16 @@ class SurfacePass:
         cov = torch.empty((self.rows, self.W), dtype=torch.uint8, device=dev) if want_coverage else None
         ao_out = torch.empty((self.rows, self.W), dtype=torch.float32, device=dev) if want_ao else None
         emissive = torch.empty((self.rows, self.W, 4), dtype=torch.float32, device=dev)
-        _lib.check(getattr(self.ctx._lib, entry)(self.ctx.handle, C.byref(frame), _ptr(instances), _ptr(materials),
-                                                 materials.numel() * materials.element_size() // 80, _ptr(textures), num_textures, self.W, self.H,
-                                                 C.byref(self.band), _ptr(self.workspace), self.workspace.numel(), _ptr(surface), self.rows * self.W,
-                                                 _ptr(depth), _ptr(cov), _ptr(ao_in), _ptr(ao_out), _ptr(emissive)), entry, self.ctx.handle)
+        self.ctx.call(entry, C.byref(frame), *self._table_args(instances, materials, textures, num_textures), *self._frame_args(), _ptr(surface), self.rows * self.W,
+                      _ptr(depth), _ptr(cov), _ptr(ao_in), _ptr(ao_out), _ptr(emissive))
         return surface, depth, cov, ao_out, emissive
 
     def composite_gltf(self, radiance: torch.Tensor, emissive: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         """target = covered ? (emissive.rgb + radiance.rgb, radiance.a) : target; all float32 [rows, W, 4]"""
         for t in (radiance, emissive, target):
             assert t.dtype == torch.float32 and t.shape == (self.rows, self.W, 4) and t.is_contiguous()
-        _lib.check(self.ctx._lib.sailor_hip_surface_composite_gltf(self.ctx.handle, _ptr(radiance), _ptr(emissive), _ptr(self.workspace), self.workspace.numel(),
-                                                                   _ptr(target), self.W, self.H, C.byref(self.band)), "sailor_hip_surface_composite_gltf", self.ctx.handle)
+        self.ctx.call("sailor_hip_surface_composite_gltf", _ptr(radiance), _ptr(emissive), _ptr(self.workspace), self.workspace.numel(), _ptr(target), self.W, self.H,
+                      C.byref(self.band))
         return target
 
     def transparent(self, frame: UboFrameData, draws, instances: torch.Tensor, materials: torch.Tensor, textures: torch.Tensor, num_textures: int,
@@ -1152,67 +1102,37 @@ class SurfacePass:
         mode: "peel" (the default: the launches above) or "buckets" -- the draws run ONCE into per-pixel fragment buckets (sailor_hip_surface_bucket_*; self.buckets,
         (layers + 1) x 8 bytes a pixel) and every layer is read out of them.  "buckets" requires layers=N, 1 .. 64; the counters, the target's bits and on_layer
         are the peel's."""
-        ctx, lib, dev = self.ctx, self.ctx._lib, self.ctx.device
+        ctx, dev = self.ctx, self.ctx.device
         assert mode in ("peel", "buckets") and (mode == "peel" or layers is not None), "mode='buckets' requires layers=N"
         assert depth.dtype == torch.float32 and depth.shape == (self.H, self.W) and depth.is_contiguous()
         assert target.dtype == torch.float32 and target.shape == (self.rows, self.W, 4) and target.is_contiguous()
         assert layers is None or layers >= 0
         any_gltf = any(d.get("gltf", False) for d in draws)
-        num_materials = materials.numel() * materials.element_size() // 80
-        ws, n = _ptr(self.workspace), self.workspace.numel()
+        scene = (instances, materials, textures, num_textures)
+        tables, fa = self._table_args(*scene), self._frame_args()
         self.last = torch.empty((self.rows, self.W), dtype=torch.int32, device=dev)
-        descs, base = [], prim_base
-        for d in draws:
-            blend = d.get("blend", "none")
-            blend = _lib.SURFACE_BLEND_MODES[blend] if isinstance(blend, str) else int(blend)
-            ids, first = d.get("instance_ids"), d.get("first_instance", 0)
-            drawn = d.get("num_drawn")
-            if drawn is None:
-                drawn = ids.numel() if ids is not None else instances.numel() * instances.element_size() // 96 - first
-            nt = d["indices"].numel() // 3
-            flags = (_lib.SURFACE_CULL_BACK if d.get("cull_back", False) else 0) | (_lib.SURFACE_ALPHA_CUTOUT if d.get("alpha_cutout", False) else 0) | \
-                    (_lib.SURFACE_GLTF if d.get("gltf", False) else 0) | (blend << _lib.SURFACE_BLEND_SHIFT)
-            descs.append(_lib.SurfaceDraw(_ptr(d["vertices"]), _ptr(d["indices"]), _ptr(ids), nt, drawn, base, flags, first, 0))
-            base += host.surface_draw_prims(nt, drawn)
-        self.prim_base, self.draw_index = base, len(descs)
+        descs = self._draw_descs(draws, instances, prim_base, blend=True)
 
         def peel(k, count):
-            _lib.check(lib.sailor_hip_surface_peel_begin(ctx.handle, self.W, self.H, C.byref(self.band), ws, n, _ptr(self.last), 1 if k == 0 else 0),
-                       "sailor_hip_surface_peel_begin", ctx.handle)
+            ctx.call("sailor_hip_surface_peel_begin", *fa, _ptr(self.last), 1 if k == 0 else 0)
             for index, d in enumerate(descs):
-                name = "sailor_hip_surface_peel_draw_gltf" if d.flags & _lib.SURFACE_GLTF else "sailor_hip_surface_peel_draw"
-                _lib.check(getattr(lib, name)(ctx.handle, C.byref(frame), C.byref(d), _ptr(instances), _ptr(materials), num_materials, _ptr(textures), num_textures, index,
-                                              self.W, self.H, C.byref(self.band), ws, n, _ptr(depth), _ptr(self.last)), name, ctx.handle)
-            _lib.check(lib.sailor_hip_surface_peel_commit(ctx.handle, self.W, self.H, C.byref(self.band), ws, n, _ptr(self.last), _ptr(count)),
-                       "sailor_hip_surface_peel_commit", ctx.handle)
+                ctx.call(self._draw_entry("peel", d), C.byref(frame), C.byref(d), *tables, index, *fa, _ptr(depth), _ptr(self.last))
+            ctx.call("sailor_hip_surface_peel_commit", *fa, _ptr(self.last), _ptr(count))
 
         def blend_layer(k):
-            if any_gltf:
-                surface, _, cov, ao, emissive = self.resolve_gltf(frame, instances, materials, textures, num_textures, ao_in=ao_in, want_depth=False,
-                                                                  want_coverage=on_layer is not None)
-            else:
-                surface, _, cov = self.resolve(frame, instances, materials, textures, num_textures, want_depth=False, want_coverage=on_layer is not None)
-                ao, emissive = ao_in, None
-            if on_layer is not None:
-                on_layer(k, surface, cov, emissive, ao)
-            radiance = shade(surface, ao)
-            assert radiance.dtype == torch.float32 and radiance.shape == (self.rows, self.W, 4) and radiance.is_contiguous()
-            _lib.check(lib.sailor_hip_surface_blend(ctx.handle, _ptr(radiance), _ptr(surface), _ptr(emissive), ws, n, _ptr(target), self.W, self.H, C.byref(self.band)),
-                       "sailor_hip_surface_blend", ctx.handle)
+            surface, radiance, emissive = self._shade_layer(k, frame, scene, any_gltf, ao_in, shade, on_layer)
+            ctx.call("sailor_hip_surface_blend", _ptr(radiance), _ptr(surface), _ptr(emissive), _ptr(self.workspace), self.workspace.numel(), _ptr(target), self.W, self.H, C.byref(self.band))
 
         if mode == "buckets":
-            nb = lib.sailor_hip_surface_bucket_bytes(self.W, C.byref(self.band), layers)
+            nb = ctx._lib.sailor_hip_surface_bucket_bytes(self.W, C.byref(self.band), layers)
             self.buckets = torch.empty(nb // 8, dtype=torch.int64, device=dev)
             store = (_ptr(self.buckets), nb, layers)
-            _lib.check(lib.sailor_hip_surface_bucket_begin(ctx.handle, self.W, self.H, C.byref(self.band), ws, n, *store), "sailor_hip_surface_bucket_begin", ctx.handle)
+            ctx.call("sailor_hip_surface_bucket_begin", *fa, *store)
             for index, d in enumerate(descs):
-                name = "sailor_hip_surface_bucket_draw_gltf" if d.flags & _lib.SURFACE_GLTF else "sailor_hip_surface_bucket_draw"
-                _lib.check(getattr(lib, name)(ctx.handle, C.byref(frame), C.byref(d), _ptr(instances), _ptr(materials), num_materials, _ptr(textures), num_textures, index,
-                                              self.W, self.H, C.byref(self.band), ws, n, _ptr(depth), *store), name, ctx.handle)
+                ctx.call(self._draw_entry("bucket", d), C.byref(frame), C.byref(d), *tables, index, *fa, _ptr(depth), *store)
             counts = torch.zeros(layers + 1, dtype=torch.int32, device=dev)
             for k in range(layers + 1):
-                _lib.check(lib.sailor_hip_surface_bucket_layer(ctx.handle, self.W, self.H, C.byref(self.band), ws, n, *store, k, _ptr(counts[k:])),
-                           "sailor_hip_surface_bucket_layer", ctx.handle)
+                ctx.call("sailor_hip_surface_bucket_layer", *fa, *store, k, _ptr(counts[k:]))
                 if k < layers:
                     blend_layer(k)
             return counts
@@ -1248,56 +1168,33 @@ class SurfacePass:
         Records only and reads nothing back; returns the device counters, int32 [layers + 1]: the pixels each layer holds and, last, the clipped pixels.
         on_layer(k, surface, weight uint8 [rows, W], emissive | None, ao | None): called behind every resolve (a test's window into the layers); the bytes of
         the samples no primitive owns are self.uncovered."""
-        ctx, lib, dev = self.ctx, self.ctx._lib, self.ctx.device
+        ctx, dev = self.ctx, self.ctx.device
         layers = samples if layers is None else layers
         assert target.dtype == torch.float32 and target.shape == (self.rows, self.W, 4) and target.is_contiguous()
         assert sample_depth is None or (sample_depth.dtype == torch.float32 and sample_depth.shape == (self.rows, self.W, samples) and sample_depth.is_contiguous())
         any_gltf = any(d.get("gltf", False) for d in draws)
-        num_materials = materials.numel() * materials.element_size() // 80
-        ws, n = _ptr(self.workspace), self.workspace.numel()
-        nb = lib.sailor_hip_surface_msaa_bytes(self.W, C.byref(self.band), samples)
+        scene = (instances, materials, textures, num_textures)
+        tables, fa = self._table_args(*scene), self._frame_args()
+        nb = ctx._lib.sailor_hip_surface_msaa_bytes(self.W, C.byref(self.band), samples)
         if nb == 0:
             raise _lib.SailorHipError(-1, "sailor_hip_surface_msaa_bytes")
         if getattr(self, "sample_store", None) is None or self.sample_store.numel() * 8 != nb:
             self.sample_store = torch.empty(nb // 8, dtype=torch.int64, device=dev)
         self.samples = samples
         store = (_ptr(self.sample_store), nb, samples)
-        _lib.check(lib.sailor_hip_surface_msaa_begin(ctx.handle, self.W, self.H, C.byref(self.band), ws, n, *store, _ptr(sample_depth)), "sailor_hip_surface_msaa_begin",
-                   ctx.handle)
-        base = prim_base
-        for index, d in enumerate(draws):
-            ids, first = d.get("instance_ids"), d.get("first_instance", 0)
-            drawn = d.get("num_drawn")
-            if drawn is None:
-                drawn = ids.numel() if ids is not None else instances.numel() * instances.element_size() // 96 - first
-            nt = d["indices"].numel() // 3
-            flags = (_lib.SURFACE_CULL_BACK if d.get("cull_back", False) else 0) | (_lib.SURFACE_ALPHA_CUTOUT if d.get("alpha_cutout", False) else 0) | \
-                    (_lib.SURFACE_GLTF if d.get("gltf", False) else 0)
-            desc = _lib.SurfaceDraw(_ptr(d["vertices"]), _ptr(d["indices"]), _ptr(ids), nt, drawn, base, flags, first, 0)
-            name = "sailor_hip_surface_msaa_draw_gltf" if d.get("gltf", False) else "sailor_hip_surface_msaa_draw"
-            _lib.check(getattr(lib, name)(ctx.handle, C.byref(frame), C.byref(desc), _ptr(instances), _ptr(materials), num_materials, _ptr(textures), num_textures, index,
-                                          self.W, self.H, C.byref(self.band), ws, n, *store), name, ctx.handle)
-            base += host.surface_draw_prims(nt, drawn)
-        self.prim_base, self.draw_index = base, len(draws)
+        ctx.call("sailor_hip_surface_msaa_begin", *fa, *store, _ptr(sample_depth))
+        for index, d in enumerate(self._draw_descs(draws, instances, prim_base)):
+            ctx.call(self._draw_entry("msaa", d), C.byref(frame), C.byref(d), *tables, index, *fa, *store)
         counts = torch.zeros(layers + 1, dtype=torch.int32, device=dev)
         self.weights = torch.empty((layers, self.rows, self.W), dtype=torch.uint8, device=dev)
         self.uncovered = torch.empty((self.rows, self.W), dtype=torch.uint8, device=dev)
         for k in range(layers):
             weight = self.weights[k]
-            _lib.check(lib.sailor_hip_surface_msaa_layer(ctx.handle, self.W, self.H, C.byref(self.band), ws, n, *store, layers, k, _ptr(weight),
-                                                         _ptr(self.uncovered) if k == 0 else None, _ptr(counts[k:]), _ptr(counts[layers:])),
-                       "sailor_hip_surface_msaa_layer", ctx.handle)
-            if any_gltf:
-                surface, _, _, ao, emissive = self.resolve_gltf(frame, instances, materials, textures, num_textures, ao_in=ao_in, want_depth=False, want_coverage=False)
-            else:
-                surface, _, _ = self.resolve(frame, instances, materials, textures, num_textures, want_depth=False, want_coverage=False)
-                ao, emissive = ao_in, None
-            if on_layer is not None:
-                on_layer(k, surface, weight, emissive, ao)
-            radiance = shade(surface, ao)
-            assert radiance.dtype == torch.float32 and radiance.shape == (self.rows, self.W, 4) and radiance.is_contiguous()
-            _lib.check(lib.sailor_hip_surface_msaa_accumulate(ctx.handle, _ptr(radiance), _ptr(emissive), _ptr(weight), _ptr(self.uncovered), samples, k, _ptr(target),
-                                                              self.W, self.H, C.byref(self.band)), "sailor_hip_surface_msaa_accumulate", ctx.handle)
+            ctx.call("sailor_hip_surface_msaa_layer", *fa, *store, layers, k, _ptr(weight), _ptr(self.uncovered) if k == 0 else None, _ptr(counts[k:]),
+                     _ptr(counts[layers:]))
+            _, radiance, emissive = self._shade_layer(k, frame, scene, any_gltf, ao_in, shade, on_layer, weight)
+            ctx.call("sailor_hip_surface_msaa_accumulate", _ptr(radiance), _ptr(emissive), _ptr(weight), _ptr(self.uncovered), samples, k, _ptr(target), self.W, self.H,
+                     C.byref(self.band))
         return counts
 
     def store_sample_depth(self, depth: torch.Tensor | None = None, want_samples: bool = True):
@@ -1305,8 +1202,8 @@ class SurfacePass:
         want_samples --, depth).  depth: the raw depth attachment of the WHOLE frame, float32 [H, W], or None; the band's rows of it take the samples' AVERAGE"""
         assert depth is None or (depth.dtype == torch.float32 and depth.shape == (self.H, self.W) and depth.is_contiguous())
         out = torch.empty((self.rows, self.W, self.samples), dtype=torch.float32, device=self.ctx.device) if want_samples else None
-        _lib.check(self.ctx._lib.sailor_hip_surface_msaa_store_depth(self.ctx.handle, _ptr(self.sample_store), self.sample_store.numel() * 8, self.samples, _ptr(out),
-                                                                     _ptr(depth), self.W, self.H, C.byref(self.band)), "sailor_hip_surface_msaa_store_depth", self.ctx.handle)
+        self.ctx.call("sailor_hip_surface_msaa_store_depth", _ptr(self.sample_store), self.sample_store.numel() * 8, self.samples, _ptr(out), _ptr(depth), self.W, self.H,
+                      C.byref(self.band))
         return out, depth
 
     def download_samples(self) -> np.ndarray:
@@ -1357,16 +1254,14 @@ class DebugLinesPass:
             num_segments = indices.numel() // 2 if indices is not None else vertices.numel() * vertices.element_size() // 56
         self._vp = (C.c_float * 16)(*[float(x) for x in np.asarray(view_projection, np.float32).reshape(16)])
         self._draw = _lib.DebugLinesDraw(_ptr(vertices), _ptr(indices), num_segments, prim_base)
-        _lib.check(self.ctx._lib.sailor_hip_debug_lines_draw(self.ctx.handle, self._vp, C.byref(self._draw), self.W, self.H, C.byref(self.band), _ptr(self.workspace),
-                                                             self.workspace.numel()), "sailor_hip_debug_lines_draw", self.ctx.handle)
+        self.ctx.call("sailor_hip_debug_lines_draw", self._vp, C.byref(self._draw), *self.surface._frame_args())
 
     def resolve(self, target: torch.Tensor, depth: torch.Tensor):
         """target: float32 [rows, W, 4] (the band's rows of Main); depth: float32 [H, W] (the whole DepthBuffer); both written where a segment owns the pixel"""
         assert self._draw is not None, "resolve() before draw()"
         assert target.dtype == torch.float32 and target.shape == (self.rows, self.W, 4) and target.is_contiguous()
         assert depth.dtype == torch.float32 and depth.shape == (self.H, self.W) and depth.is_contiguous()
-        _lib.check(self.ctx._lib.sailor_hip_debug_lines_resolve(self.ctx.handle, self._vp, C.byref(self._draw), self.W, self.H, C.byref(self.band), _ptr(self.workspace),
-                                                                self.workspace.numel(), _ptr(target), _ptr(depth)), "sailor_hip_debug_lines_resolve", self.ctx.handle)
+        self.ctx.call("sailor_hip_debug_lines_resolve", self._vp, C.byref(self._draw), *self.surface._frame_args(), _ptr(target), _ptr(depth))
         return target, depth
 
     def download_keys(self) -> np.ndarray:
@@ -1389,7 +1284,7 @@ class UiPass:
         """a workspace for draws of up to num_triangles triangles (allocates: not inside a capture)"""
         if num_triangles > self.capacity:
             n = C.c_size_t()
-            _lib.check(self.ctx._lib.sailor_hip_ui_workspace_bytes(num_triangles, self.W, self.H, C.byref(n)), "sailor_hip_ui_workspace_bytes")
+            _lib.call("sailor_hip_ui_workspace_bytes", num_triangles, self.W, self.H, C.byref(n))
             self.workspace, self.capacity = torch.empty(n.value, dtype=torch.uint8, device=self.ctx.device), num_triangles
 
     def set_texture(self, image: np.ndarray | None):
@@ -1411,10 +1306,9 @@ class UiPass:
         assert int((commands["indexCount"] // 3).sum()) <= self.capacity, "reserve() more triangles first"
         self._scale = (C.c_float * 2)(float(scale[0]), float(scale[1]))
         self._translate = (C.c_float * 2)(float(translate[0]), float(translate[1]))
-        _lib.check(self.ctx._lib.sailor_hip_ui_draw(self.ctx.handle, _ptr(vertices), vertices.numel() * vertices.element_size() // 20, _ptr(indices),
-                                                    indices.element_size(), indices.numel(), commands.ctypes.data if len(commands) else None, _ptr(d_commands),
-                                                    len(commands), self._scale, self._translate, C.byref(self._texture), _ptr(self.workspace),
-                                                    self.workspace.numel(), _ptr(target), self.W, self.H, C.byref(self.band)), "sailor_hip_ui_draw", self.ctx.handle)
+        self.ctx.call("sailor_hip_ui_draw", _ptr(vertices), vertices.numel() * vertices.element_size() // 20, _ptr(indices), indices.element_size(), indices.numel(),
+                      commands.ctypes.data if len(commands) else None, _ptr(d_commands), len(commands), self._scale, self._translate, C.byref(self._texture),
+                      _ptr(self.workspace), self.workspace.numel(), _ptr(target), self.W, self.H, C.byref(self.band))
         return target
 
     def draw_flat(self, target: torch.Tensor, flat: dict, index_bytes: int = 2):

@@ -45,32 +45,32 @@ def _f32(a, n) -> np.ndarray:
 
 def num_tiles(width: int, height: int) -> tuple[int, int]:
     tx, ty = C.c_int32(), C.c_int32()
-    _lib.check(_lib.load().sailor_hip_num_tiles(width, height, C.byref(tx), C.byref(ty)), "num_tiles")
+    _lib.call("sailor_hip_num_tiles", width, height, C.byref(tx), C.byref(ty))
     return tx.value, ty.value
 
 
 def band_whole_frame(width: int, height: int) -> Band:
     b = Band()
-    _lib.check(_lib.load().sailor_hip_band_whole_frame(width, height, C.byref(b)), "band_whole_frame")
+    _lib.call("sailor_hip_band_whole_frame", width, height, C.byref(b))
     return b
 
 
 def band_from_tile_rows(width: int, height: int, row_begin: int, row_end: int) -> Band:
     b = Band()
-    _lib.check(_lib.load().sailor_hip_band_from_tile_rows(width, height, row_begin, row_end, C.byref(b)), "band_from_tile_rows")
+    _lib.call("sailor_hip_band_from_tile_rows", width, height, row_begin, row_end, C.byref(b))
     return b
 
 
 def band_for_rank(width: int, height: int, rank: int, world_size: int) -> Band:
     b = Band()
-    _lib.check(_lib.load().sailor_hip_band_for_rank(width, height, rank, world_size, C.byref(b)), "band_for_rank")
+    _lib.call("sailor_hip_band_for_rank", width, height, rank, world_size, C.byref(b))
     return b
 
 
 def eye_adaptation_constants(width: int, height: int, delta_time: float) -> "_lib.EyeAdaptationConstants":
     """EyeAdaptationNode.cpp:154-170: the push constants of the histogram and the average Dispatch"""
     c = _lib.EyeAdaptationConstants()
-    _lib.check(_lib.load().sailor_host_eye_adaptation_constants(width, height, delta_time, C.byref(c)), "sailor_host_eye_adaptation_constants")
+    _lib.call("sailor_host_eye_adaptation_constants", width, height, delta_time, C.byref(c))
     return c
 
 
@@ -169,7 +169,7 @@ def particle_instances(records: np.ndarray, num_particles: int, trace_frames: in
 def bloom_push_constants(threshold: float, knee: float) -> np.ndarray:
     """BloomNode.cpp:89-93: u_threshold = (t, t - knee, 2 knee, 0.25 knee) as float32[4]"""
     out = np.empty(4, np.float32)
-    _lib.check(_lib.load().sailor_host_bloom_push_constants(threshold, knee, _fp(out)), "sailor_host_bloom_push_constants")
+    _lib.call("sailor_host_bloom_push_constants", threshold, knee, _fp(out))
     return out
 
 
@@ -186,7 +186,7 @@ def mip_chain_texels(width: int, height: int, levels: int) -> int:
 def sky_params(**overrides) -> "_lib.SkyParams":
     """SkyNode::SkyParams with the initialisers of SkyNode.h:50-67; `lightDirection` takes 3 or 4 floats (w = 0), the other members by name"""
     p = _lib.SkyParams()
-    _lib.check(_lib.load().sailor_host_sky_params_default(C.byref(p)), "sailor_host_sky_params_default")
+    _lib.call("sailor_host_sky_params_default", C.byref(p))
     for name, value in overrides.items():
         if name == "lightDirection":
             v = [float(x) for x in value]
@@ -203,7 +203,7 @@ def sky_params(**overrides) -> "_lib.SkyParams":
 def sky_sun_color(sun_direction) -> np.ndarray:
     """Sky.shader:247-264 CalculateSunColor(sunDirection) in fp32; the cloud march passes -dirToSun"""
     d, out = _f32(sun_direction, 3), np.empty(3, np.float32)
-    _lib.check(_lib.load().sailor_host_sky_sun_color(_fp(d), _fp(out)), "sailor_host_sky_sun_color")
+    _lib.call("sailor_host_sky_sun_color", _fp(d), _fp(out))
     return out
 
 
@@ -212,7 +212,7 @@ def sky_star_color_table(rows) -> np.ndarray:
     rows = np.ascontiguousarray(rows, dtype=np.float32)
     assert rows.ndim == 2 and rows.shape[1] == 11, rows.shape
     out = np.empty((_lib.SKY_STAR_TABLE_ROWS, 3), np.float32)
-    _lib.check(_lib.load().sailor_host_sky_star_color_table(_fp(rows), rows.shape[0], _fp(out)), "sailor_host_sky_star_color_table")
+    _lib.call("sailor_host_sky_star_color_table", _fp(rows), rows.shape[0], _fp(out))
     return out
 
 
@@ -222,21 +222,21 @@ def sky_star_mesh(catalogue: bytes, table):
     data = bytes(catalogue)
     capacity = max(0, len(data) - 28) // 32
     pos, col, count = np.empty((capacity, 3), np.float32), np.empty((capacity, 4), np.float32), C.c_uint32()
-    _lib.check(_lib.load().sailor_host_sky_star_mesh(data, len(data), _fp(table), _fp(pos), _fp(col), capacity, C.byref(count)), "sailor_host_sky_star_mesh")
+    _lib.call("sailor_host_sky_star_mesh", data, len(data), _fp(table), _fp(pos), _fp(col), capacity, C.byref(count))
     return pos[:count.value].copy(), col[:count.value].copy()
 
 
 def sky_stars_model(camera_position) -> np.ndarray:
     """SkyNode.cpp:208-211, :698: translate(cameraPosition) * toMat4(precession), column-major float32[16]"""
     cam, out = np.ascontiguousarray(camera_position, dtype=np.float32).reshape(-1)[:3].copy(), np.empty(16, np.float32)
-    _lib.check(_lib.load().sailor_host_sky_stars_model(_fp(cam), _fp(out)), "sailor_host_sky_stars_model")
+    _lib.call("sailor_host_sky_stars_model", _fp(cam), _fp(out))
     return out
 
 
 def sky_face_matrices(face: int):
     """SkyNode.cpp:487-508: (view, projection, invProjection) of cube face 0..5, column-major float32[16] each"""
     v, p, ip = (np.empty(16, np.float32) for _ in range(3))
-    _lib.check(_lib.load().sailor_host_sky_face_matrices(face, _fp(v), _fp(p), _fp(ip)), "sailor_host_sky_face_matrices")
+    _lib.call("sailor_host_sky_face_matrices", face, _fp(v), _fp(p), _fp(ip))
     return v, p, ip
 
 
@@ -244,21 +244,21 @@ def transform_matrix(position, rotation_xyzw, scale) -> np.ndarray:
     """Math/Transform.cpp:39-42; returns a column-major float32[16]."""
     trs = np.concatenate([_f32(position, 4), _f32(rotation_xyzw, 4), _f32(scale, 4)])
     out = np.empty(16, np.float32)
-    _lib.check(_lib.load().sailor_host_transform_matrix(_fp(trs), _fp(out)), "transform_matrix")
+    _lib.call("sailor_host_transform_matrix", _fp(trs), _fp(out))
     return out
 
 
 def mat4_inverse(m) -> np.ndarray:
     m = _f32(m, 16)
     out = np.empty(16, np.float32)
-    _lib.check(_lib.load().sailor_host_mat4_inverse(_fp(m), _fp(out)), "mat4_inverse")
+    _lib.call("sailor_host_mat4_inverse", _fp(m), _fp(out))
     return out
 
 
 def mat4_mul(a, b) -> np.ndarray:
     a, b = _f32(a, 16), _f32(b, 16)
     out = np.empty(16, np.float32)
-    _lib.check(_lib.load().sailor_host_mat4_mul(_fp(a), _fp(b), _fp(out)), "mat4_mul")
+    _lib.call("sailor_host_mat4_mul", _fp(a), _fp(b), _fp(out))
     return out
 
 
@@ -268,8 +268,7 @@ def fill_frame_data(camera_world, fov_degrees: float, z_near: float, z_far: floa
     cw = _f32(camera_world, 16)
     frame = UboFrameData()
     asp = np.float32(width) / np.float32(height) if aspect is None else np.float32(aspect)
-    _lib.check(_lib.load().sailor_host_fill_frame_data(_fp(cw), fov_degrees, float(asp), z_near, z_far, width, height,
-                                                        current_time, delta_time, C.byref(frame)), "fill_frame_data")
+    _lib.call("sailor_host_fill_frame_data", _fp(cw), fov_degrees, float(asp), z_near, z_far, width, height, current_time, delta_time, C.byref(frame))
     return frame
 
 
@@ -288,8 +287,7 @@ def extract_frustum_planes(world_matrix, aspect: float, fov_y_degrees: float, z_
     wm = _f32(world_matrix, 16)
     planes = np.empty(24, np.float32)
     corners = np.empty(24, np.float32)
-    _lib.check(_lib.load().sailor_host_extract_frustum_planes(_fp(wm), aspect, fov_y_degrees, z_near, z_far, _fp(planes), _fp(corners)),
-               "extract_frustum_planes")
+    _lib.call("sailor_host_extract_frustum_planes", _fp(wm), aspect, fov_y_degrees, z_near, z_far, _fp(planes), _fp(corners))
     return planes.reshape(6, 4), corners.reshape(8, 3)
 
 
@@ -298,7 +296,7 @@ def extract_frustum_planes_matrix(projection_view_matrix):
     m = _f32(projection_view_matrix, 16)
     planes = np.empty(24, np.float32)
     corners = np.empty(24, np.float32)
-    _lib.check(_lib.load().sailor_host_extract_frustum_planes_matrix(_fp(m), _fp(planes), _fp(corners)), "extract_frustum_planes_matrix")
+    _lib.call("sailor_host_extract_frustum_planes_matrix", _fp(m), _fp(planes), _fp(corners))
     return planes.reshape(6, 4), corners.reshape(8, 3)
 
 
@@ -352,11 +350,11 @@ class CsmSnapshots:
 
     def __getitem__(self, k: int):
         n = C.c_uint32()
-        _lib.check(self._lib.sailor_host_csm_snapshot_get(self.handle, k, 0, C.byref(n), None, None, None, None), "csm_snapshot_get")
+        _lib.call("sailor_host_csm_snapshot_get", self.handle, k, 0, C.byref(n), None, None, None, None)
         idx = np.zeros(max(n.value, 1), np.uint32); frames = np.zeros(max(n.value, 1), np.uint64)
         has = C.c_int32(); v = _lib.CsmView()
-        _lib.check(self._lib.sailor_host_csm_snapshot_get(self.handle, k, n.value, C.byref(n), idx.ctypes.data_as(C.c_void_p), frames.ctypes.data_as(C.c_void_p),
-                                                          C.byref(has), C.byref(v)), "csm_snapshot_get")
+        _lib.call("sailor_host_csm_snapshot_get", self.handle, k, n.value, C.byref(n), idx.ctypes.data_as(C.c_void_p), frames.ctypes.data_as(C.c_void_p), C.byref(has),
+                  C.byref(v))
         view = (int(v.componentIndex), np.float32(list(v.cameraPosition)), np.float32(list(v.cameraRotation)), np.float32(list(v.lightPosition)),
                 np.float32(list(v.lightRotation))) if has.value else None
         return idx[: n.value], frames[: n.value], view
@@ -400,9 +398,8 @@ def plan_csm_passes(overlap_masks: np.ndarray, shadow_types, last_changed_frame:
     render = np.zeros(n_casc, np.uint32)
     out = np.zeros_like(masks_in)
     vs = _csm_view_struct(view) if view is not None else None
-    _lib.check(_lib.load().sailor_host_csm_plan_passes(snaps.handle, 0, n_casc, n, masks_in.ctypes.data_as(C.c_void_p), types.ctypes.data_as(C.c_void_p),
-                                                       frames.ctypes.data_as(C.c_void_p), C.byref(vs) if vs is not None else None,
-                                                       render.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)), "csm_plan_passes")
+    _lib.call("sailor_host_csm_plan_passes", snaps.handle, 0, n_casc, n, masks_in.ctypes.data_as(C.c_void_p), types.ctypes.data_as(C.c_void_p),
+              frames.ctypes.data_as(C.c_void_p), C.byref(vs) if vs is not None else None, render.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
     return [int(k) for k in np.nonzero(render)[0]], out, snaps
 
 
@@ -429,8 +426,8 @@ def lights_in_frustum(planes, camera_position, types, shadow_types, positions, b
     dp, ds = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.float32)
     nd, npt, ns = C.c_uint32(), C.c_uint32(), C.c_uint32()
     vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-    _lib.check(_lib.load().sailor_host_lights_in_frustum(_fp(pl), _fp(cp), n, vp(t), vp(st), vp(act), vp(pos), vp(bd), vp(od), C.byref(nd), vp(op), vp(dp), C.byref(npt),
-                                                         vp(os_), vp(ds), C.byref(ns)), "lights_in_frustum")
+    _lib.call("sailor_host_lights_in_frustum", _fp(pl), _fp(cp), n, vp(t), vp(st), vp(act), vp(pos), vp(bd), vp(od), C.byref(nd), vp(op), vp(dp), C.byref(npt), vp(os_),
+              vp(ds), C.byref(ns))
     return od[: nd.value].copy(), (op[: npt.value].copy(), dp[: npt.value].copy()), (os_[: ns.value].copy(), ds[: ns.value].copy())
 
 
@@ -438,7 +435,7 @@ def csm_matrices(light_view, camera_world, aspect: float, fov_y_degrees: float, 
     """The 4 `lightsMatrices` (FrameGraph/ShadowPrepassNode.cpp:387-404, ECS/LightingECS.cpp:292) as float32[4,16]."""
     lv, cw = _f32(light_view, 16), _f32(camera_world, 16)
     out = np.empty(64, np.float32)
-    _lib.check(_lib.load().sailor_host_csm_matrices(_fp(lv), _fp(cw), aspect, fov_y_degrees, camera_near, camera_far, _fp(out)), "csm_matrices")
+    _lib.call("sailor_host_csm_matrices", _fp(lv), _fp(cw), aspect, fov_y_degrees, camera_near, camera_far, _fp(out))
     return out.reshape(4, 16)
 
 
@@ -447,7 +444,7 @@ def cutoff_cosines(inner_degrees: float, outer_degrees: float) -> tuple[np.float
     z3 = np.zeros(3, np.float32)
     cut = np.array([inner_degrees, outer_degrees], np.float32)
     rec = _lib.LightShaderData()
-    _lib.check(_lib.load().sailor_host_pack_light(1, 0, _fp(z3), _fp(z3), _fp(z3), _fp(z3), _fp(cut), _fp(z3), C.byref(rec)), "pack_light")
+    _lib.call("sailor_host_pack_light", 1, 0, _fp(z3), _fp(z3), _fp(z3), _fp(z3), _fp(cut), _fp(z3), C.byref(rec))
     return np.float32(rec.cutOff[0]), np.float32(rec.cutOff[1])
 
 
@@ -467,7 +464,7 @@ def make_csm_desc(lights_matrices: np.ndarray, maps: list) -> CsmDesc:
 def srgb_table() -> np.ndarray:
     """sailor_host_srgb_table: the sRGB transfer function of the 256 byte values (double, rounded once to fp32)"""
     out = np.zeros(256, np.float32)
-    _lib.check(_lib.load().sailor_host_srgb_table(_fp(out)), "sailor_host_srgb_table")
+    _lib.call("sailor_host_srgb_table", _fp(out))
     return out
 
 
@@ -475,7 +472,7 @@ def srgb_encode_table() -> np.ndarray:
     """sailor_host_srgb_encode_table: the 255 rounding boundaries of the sRGB encode, out[k - 1] = the decode of (k - 0.5) / 255 (double, rounded once to fp32);
     the byte of x is the number of entries <= x"""
     out = np.zeros(255, np.float32)
-    _lib.check(_lib.load().sailor_host_srgb_encode_table(_fp(out)), "sailor_host_srgb_encode_table")
+    _lib.call("sailor_host_srgb_encode_table", _fp(out))
     return out
 
 
@@ -488,21 +485,21 @@ def msaa_sample_positions(samples: int) -> np.ndarray:
     """sailor_host_msaa_sample_positions: the standard sample locations of a `samples`-times multisampled pixel, int32 [samples, 2], (sx, sy) in 1/256 pixel
     from the pixel's top-left corner; samples is 1, 2, 4 or 8"""
     out = np.zeros((max(int(samples), 1), 2), np.int32)
-    _lib.check(_lib.load().sailor_host_msaa_sample_positions(samples, out.ctypes.data_as(C.c_void_p)), "sailor_host_msaa_sample_positions")
+    _lib.call("sailor_host_msaa_sample_positions", samples, out.ctypes.data_as(C.c_void_p))
     return out
 
 
 def surface_draw_prims(num_triangles: int, num_drawn: int) -> int:
     """sailor_hip_surface_draw_prims: what a draw adds to the surface pass's running primBase"""
     out = C.c_uint64()
-    _lib.check(_lib.load().sailor_hip_surface_draw_prims(num_triangles, num_drawn, C.byref(out)), "sailor_hip_surface_draw_prims")
+    _lib.call("sailor_hip_surface_draw_prims", num_triangles, num_drawn, C.byref(out))
     return int(out.value)
 
 
 def debug_lines_prims(num_segments: int) -> int:
     """sailor_hip_debug_lines_prims: what the DebugDraw pass's draw adds to a running primBase"""
     out = C.c_uint64()
-    _lib.check(_lib.load().sailor_hip_debug_lines_prims(num_segments, C.byref(out)), "sailor_hip_debug_lines_prims")
+    _lib.call("sailor_hip_debug_lines_prims", num_segments, C.byref(out))
     return int(out.value)
 
 
@@ -608,8 +605,8 @@ def ui_flatten(draw_data: dict) -> dict:
     f2 = lambda v: (C.c_float * 2)(*[float(x) for x in v])  # noqa: E731
     pc, count, w, h = (C.c_float * 4)(), C.c_uint32(), C.c_int32(), C.c_int32()
     out = (_lib.UiCommand * max(len(flat), 1))()
-    _lib.check(_lib.load().sailor_host_ui_flatten(f2(draw_data["display_pos"]), f2(draw_data["display_size"]), f2(draw_data["framebuffer_scale"]), cl, len(lists), cc,
-                                                  len(flat), pc, out, len(flat), C.byref(count), C.byref(w), C.byref(h)), "sailor_host_ui_flatten")
+    _lib.call("sailor_host_ui_flatten", f2(draw_data["display_pos"]), f2(draw_data["display_size"]), f2(draw_data["framebuffer_scale"]), cl, len(lists), cc, len(flat),
+              pc, out, len(flat), C.byref(count), C.byref(w), C.byref(h))
     commands = np.frombuffer(bytes(out), _lib.UI_COMMAND_DTYPE)[: count.value].copy()
     vertices = np.concatenate([np.asarray(l["vertices"], _lib.VERTEX_P2UV2C1_DTYPE) for l in lists]) if lists else np.zeros(0, _lib.VERTEX_P2UV2C1_DTYPE)
     indices = np.concatenate([np.asarray(l["indices"], np.uint32) for l in lists]) if lists else np.zeros(0, np.uint32)

@@ -864,7 +864,7 @@ int HipGraphicsDriver::ExchangeLightLists(RHIBufferPtr bandGrid, RHIBufferPtr ba
                                            m_exchangeWorkspace->m_size);
 }
 
-int HipGraphicsDriver::RecordShade(const TVector<RHIShaderBindingSetPtr>& bindings)
+int HipGraphicsDriver::RecordShade(const TVector<RHIShaderBindingSetPtr>& bindings, const float* aoOverride)
 {
     // Standard.shader:180-251: set 0 frame, set 1 lights {0 light, 1 culledLights, 2 lightsGrid, 6 lightsMatrices, 8 shadowMaps},
     // set 2 the surface/radiance buffers: the driver's own planes behind RenderScene's draws (RecordSurfaceEnd: per-instance / material / textures sets resolved
@@ -902,7 +902,7 @@ int HipGraphicsDriver::RecordShade(const TVector<RHIShaderBindingSetPtr>& bindin
             ibl.env = (const float*)env->m_buffer->m_hip.m_devicePtr; ibl.envSize = env->m_extent.x; ibl.envLevels = (int32_t)env->m_mipLevels;
             ibl.brdfLut = (const float*)lut->m_buffer->m_hip.m_devicePtr; ibl.lutW = lut->m_extent.x; ibl.lutH = lut->m_extent.y;
             ibl.ao = (ao && ao->m_extent.x == W && ao->m_extent.y == H) ? (const float*)ao->m_buffer->m_hip.m_devicePtr : nullptr;
-            if (m_shadeAoOverride) ibl.ao = m_shadeAoOverride; // behind a pass with glTF draws: min(g_AO, the occlusion texel), RecordSurfaceEnd
+            if (aoOverride) ibl.ao = aoOverride; // behind a pass with glTF draws: min(g_AO, the occlusion texel), RecordSurfaceResolveShade
             hasIbl = true;
         }
     }
@@ -971,6 +971,23 @@ static SurfaceTables surface_tables(const TVector<RHIShaderBindingSetPtr>& bindi
     return t;
 }
 
+// One draw's descriptor from its buffers and ranges, and the host-side range checks: false = a buffer is missing or a range ends outside its buffer.
+// instances == nullptr: the instance range is the kernel's to check (an indirect draw: it is handed the number of records).
+static bool surface_draw_desc(SailorSurfaceDraw& d, const RHIBufferPtr& vertices, const RHIBufferPtr& indices, const RHIBufferPtr& instances, uint32_t indexCount,
+                              uint32_t instanceCount, uint32_t firstIndex, int64_t vertexOffset, uint32_t firstInstance, uint32_t flags, uint64_t primBase)
+{
+    if (!vertices || !indices || (size_t)firstIndex + indexCount > indices->m_size / 4 || vertexOffset < 0 ||
+        (size_t)vertexOffset * sizeof(SailorVertexP3N3T3B3UV2C4) > vertices->m_size ||
+        (instances && ((size_t)firstInstance + instanceCount) * sizeof(SailorPerInstanceData) > instances->m_size))
+        return false;
+    d = SailorSurfaceDraw {};
+    d.dVertices = (const SailorVertexP3N3T3B3UV2C4*)vertices->m_hip.m_devicePtr + vertexOffset;
+    d.dIndices = (const uint32_t*)indices->m_hip.m_devicePtr + firstIndex;
+    d.numTriangles = indexCount / 3; d.numDrawn = instanceCount; // (of an indirect draw: the capacity, the un-culled count the host wrote)
+    d.primBase = (uint32_t)primBase; d.flags = flags; d.firstInstance = firstInstance;
+    return true;
+}
+
 int HipGraphicsDriver::SurfaceWorkspace(int W, int H, bool create, SurfacePass& pass)
 {
     pass.W = W; pass.H = H;
@@ -982,7 +999,7 @@ int HipGraphicsDriver::SurfaceWorkspace(int W, int H, bool create, SurfacePass& 
 
 template <typename Issue>
 int HipGraphicsDriver::RecordSurfacePassDraw(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& color, const RHITexturePtr& depth, bool first, bool needColor,
-                                             bool clearDepth, bool buffersBound, bool rangesOk, Issue&& issue)
+                                             bool clearDepth, bool buffersBound, bool rangesOk, SailorSurfaceDraw& d, Issue&& issue)
 {
     if (first) m_surfaceBegun = false;
     SurfacePass pass;
@@ -1006,7 +1023,6 @@ int HipGraphicsDriver::RecordSurfacePassDraw(const TVector<RHIShaderBindingSetPt
         m_surfaceBegun = true;
     }
     if (!m_surfaceBegun || !m_surfaceWorkspace || m_surfaceWorkspace->m_size != pass.bytes || m_surfacePrimBase > 0xFFFFFFFFull) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    SailorSurfaceDraw d {};
     d.primBase = (uint32_t)m_surfacePrimBase;
     st = issue(pass, d);
     if (st != SAILOR_HIP_OK) { m_surfaceBegun = false; return st; }
@@ -1022,16 +1038,11 @@ int HipGraphicsDriver::RecordSurfaceDraw(const TVector<RHIShaderBindingSetPtr>& 
 {
     RHIBufferPtr instances = scene_buffer(bindings, "data");
     const bool buffersBound = vertices && indices && instances;
-    const bool rangesOk = buffersBound && (size_t)firstIndex + indexCount <= indices->m_size / 4 &&
-                          ((size_t)firstInstance + instanceCount) * sizeof(SailorPerInstanceData) <= instances->m_size &&
-                          (size_t)vertexOffset * sizeof(SailorVertexP3N3T3B3UV2C4) <= vertices->m_size;
+    // flags, SAILOR_SURFACE_CULL_BACK: the reference's materials cull back faces (ECullMode::Back, frontFace counter-clockwise) unless double-sided
+    SailorSurfaceDraw desc {}; // (primBase: the pass's, set by RecordSurfacePassDraw)
+    const bool rangesOk = buffersBound && surface_draw_desc(desc, vertices, indices, instances, indexCount, instanceCount, firstIndex, vertexOffset, firstInstance, flags, 0);
     // the direct route needs a colour attachment and always starts the keys from the depth attachment
-    return RecordSurfacePassDraw(bindings, color, depth, first, true, false, buffersBound, rangesOk, [&](const SurfacePass& pass, SailorSurfaceDraw& d) {
-        d.dVertices = (const SailorVertexP3N3T3B3UV2C4*)vertices->m_hip.m_devicePtr + vertexOffset;
-        d.dIndices = (const uint32_t*)indices->m_hip.m_devicePtr + firstIndex;
-        d.numTriangles = indexCount / 3; d.numDrawn = instanceCount;
-        d.flags = flags; // SAILOR_SURFACE_CULL_BACK: the reference's materials cull back faces (ECullMode::Back, frontFace counter-clockwise) unless double-sided
-        d.firstInstance = firstInstance;
+    return RecordSurfacePassDraw(bindings, color, depth, first, true, false, buffersBound, rangesOk, desc, [&](const SurfacePass& pass, const SailorSurfaceDraw& d) {
         const SailorPerInstanceData* dInstances = (const SailorPerInstanceData*)instances->m_hip.m_devicePtr;
         void* workspace = m_surfaceWorkspace->m_hip.m_devicePtr;
         const SurfaceTables t = surface_tables(bindings);
@@ -1123,61 +1134,71 @@ int HipGraphicsDriver::RecordUi(const RHITexturePtr& color, const RHIBufferPtr& 
                               m_uiWorkspace->m_size, (float*)color->m_buffer->m_hip.m_devicePtr, W, H, &band);
 }
 
+int HipGraphicsDriver::SurfacePassBuffers(size_t pixels, bool gltf)
+{
+    if (!m_surfacePlanes || m_surfacePlanes->m_size != pixels * 48) m_surfacePlanes = CreateBuffer(pixels * 48);
+    if (!m_surfaceRadiance || m_surfaceRadiance->m_size != pixels * 16) m_surfaceRadiance = CreateBuffer(pixels * 16);
+    if (gltf && (!m_surfaceAo || m_surfaceAo->m_size != pixels * 4)) m_surfaceAo = CreateBuffer(pixels * 4);
+    if (gltf && (!m_surfaceEmissive || m_surfaceEmissive->m_size != pixels * 16)) m_surfaceEmissive = CreateBuffer(pixels * 16);
+    return (!m_surfacePlanes || !m_surfaceRadiance || (gltf && (!m_surfaceAo || !m_surfaceEmissive))) ? SAILOR_HIP_ERR_OUT_OF_MEMORY : SAILOR_HIP_OK;
+}
+
+int HipGraphicsDriver::RecordSurfaceResolveShade(const TVector<RHIShaderBindingSetPtr>& bindings, const SurfacePass& pass, SurfaceResolveGltf resolveGltf)
+{
+    const SurfaceTables t = surface_tables(bindings);
+    const SailorPerInstanceData* dInstances = (const SailorPerInstanceData*)scene_buffer(bindings, "data")->m_hip.m_devicePtr;
+    const size_t pixels = (size_t)pass.W * pass.H;
+    void* workspace = m_surfaceWorkspace->m_hip.m_devicePtr;
+    float* planes = (float*)m_surfacePlanes->m_hip.m_devicePtr;
+    int st;
+    if (resolveGltf) {
+        // a pass that recorded a Standard_glTF.shader draw: the resolve also writes the emissive term and the occlusion the shade is to read, min(g_AO, the
+        // occlusion texel) -- g_AO = the `g_aoSampler` binding of the lights set if bound at the frame's extent (what RecordShade would hand the shade), else 1
+        auto ao = bindings[1] ? bound_texture(bindings[1], "g_aoSampler") : RHITexturePtr();
+        const float* aoIn = (ao && ao->m_extent.x == pass.W && ao->m_extent.y == pass.H) ? (const float*)ao->m_buffer->m_hip.m_devicePtr : nullptr;
+        st = resolveGltf(m_ctx, &pass.frame, dInstances, t.materials, t.numMaterials, t.textures, t.numTextures, pass.W, pass.H, &pass.band, workspace, pass.bytes, planes, pixels,
+                         nullptr, nullptr, aoIn, (float*)m_surfaceAo->m_hip.m_devicePtr, (float*)m_surfaceEmissive->m_hip.m_devicePtr);
+    } else
+        st = sailor_hip_surface_resolve(m_ctx, &pass.frame, dInstances, t.materials, t.numMaterials, t.textures, t.numTextures, pass.W, pass.H, &pass.band, workspace, pass.bytes,
+                                        planes, pixels, nullptr, nullptr);
+    if (st != SAILOR_HIP_OK) return st;
+    // the rest of the fragment stage: the shade over the planes, exactly as over a caller's surface
+    if (!bindings[1]) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
+    auto own = RHIShaderBindingSetPtr::Make();
+    own->GetOrAddShaderBinding("surface")->m_buffer = m_surfacePlanes;
+    own->GetOrAddShaderBinding("radiance")->m_buffer = m_surfaceRadiance;
+    return RecordShade({ bindings[0], bindings[1], own }, resolveGltf ? (const float*)m_surfaceAo->m_hip.m_devicePtr : nullptr);
+}
+
 int HipGraphicsDriver::RecordSurfaceEnd(const TVector<RHIShaderBindingSetPtr>& bindings, const RHITexturePtr& color, const RHITexturePtr& depthToStore, bool gltf)
 {
     if (!m_surfaceBegun) return SAILOR_HIP_ERR_INVALID_ARGUMENT; // a draw of the pass was refused: nothing to resolve
     m_surfaceBegun = false;
-    SailorUboFrameData frame;
+    SurfacePass pass;
     RHIBufferPtr instances = scene_buffer(bindings, "data");
     const SurfaceTables t = surface_tables(bindings);
     gltf = gltf || t.lod; // mip-mapped textures: the resolve with the implicit level of detail serves both shaders and ends like the glTF one
-    if (bindings.size() < 2 || !host_copy_of(bindings[0], "frameData", frame) || !color || !color->m_buffer || !instances || !t.bound)
+    if (bindings.size() < 2 || !host_copy_of(bindings[0], "frameData", pass.frame) || !color || !color->m_buffer || !instances || !t.bound)
         return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    const int W = color->GetExtent().x, H = color->GetExtent().y;
-    SailorBand band;
-    sailor_hip_band_whole_frame(W, H, &band);
-    const size_t pixels = (size_t)W * H, bytes = m_surfaceWorkspace->m_size;
-    if (!m_surfacePlanes || m_surfacePlanes->m_size != pixels * 48) m_surfacePlanes = CreateBuffer(pixels * 48);
-    if (!m_surfaceRadiance || m_surfaceRadiance->m_size != pixels * 16) m_surfaceRadiance = CreateBuffer(pixels * 16);
-    if (!m_surfacePlanes || !m_surfaceRadiance) return SAILOR_HIP_ERR_OUT_OF_MEMORY;
-    int st;
-    if (gltf) {
-        // a pass that recorded a Standard_glTF.shader draw: the resolve also writes the emissive term and the occlusion the shade is to read, min(g_AO, the
-        // occlusion texel) -- g_AO = the `g_aoSampler` binding of the lights set if bound at the frame's extent (what RecordShade would hand the shade), else 1
-        if (!m_surfaceAo || m_surfaceAo->m_size != pixels * 4) m_surfaceAo = CreateBuffer(pixels * 4);
-        if (!m_surfaceEmissive || m_surfaceEmissive->m_size != pixels * 16) m_surfaceEmissive = CreateBuffer(pixels * 16);
-        if (!m_surfaceAo || !m_surfaceEmissive) return SAILOR_HIP_ERR_OUT_OF_MEMORY;
-        auto ao = bindings[1] ? bound_texture(bindings[1], "g_aoSampler") : RHITexturePtr();
-        const float* aoIn = (ao && ao->m_extent.x == W && ao->m_extent.y == H) ? (const float*)ao->m_buffer->m_hip.m_devicePtr : nullptr;
-        st = (t.lod ? sailor_hip_surface_resolve_lod : sailor_hip_surface_resolve_gltf)(
-                                             m_ctx, &frame, (const SailorPerInstanceData*)instances->m_hip.m_devicePtr, t.materials, t.numMaterials, t.textures, t.numTextures,
-                                             W, H, &band, m_surfaceWorkspace->m_hip.m_devicePtr, bytes, (float*)m_surfacePlanes->m_hip.m_devicePtr, pixels, nullptr, nullptr,
-                                             aoIn, (float*)m_surfaceAo->m_hip.m_devicePtr, (float*)m_surfaceEmissive->m_hip.m_devicePtr);
-    } else
-        st = sailor_hip_surface_resolve(m_ctx, &frame, (const SailorPerInstanceData*)instances->m_hip.m_devicePtr, t.materials, t.numMaterials, t.textures, t.numTextures, W, H,
-                                        &band, m_surfaceWorkspace->m_hip.m_devicePtr, bytes, (float*)m_surfacePlanes->m_hip.m_devicePtr, pixels, nullptr, nullptr);
-    if (st != SAILOR_HIP_OK) return st;
-    // the rest of the fragment stage: the shade over the planes, exactly as over a caller's surface
-    auto own = RHIShaderBindingSetPtr::Make();
-    own->GetOrAddShaderBinding("surface")->m_buffer = m_surfacePlanes;
-    own->GetOrAddShaderBinding("radiance")->m_buffer = m_surfaceRadiance;
-    if (!bindings[1]) return SAILOR_HIP_ERR_INVALID_ARGUMENT;
-    m_shadeAoOverride = gltf ? (const float*)m_surfaceAo->m_hip.m_devicePtr : nullptr;
-    st = RecordShade({ bindings[0], bindings[1], own });
-    m_shadeAoOverride = nullptr;
+    const int W = pass.W = color->GetExtent().x, H = pass.H = color->GetExtent().y;
+    sailor_hip_band_whole_frame(W, H, &pass.band);
+    const SailorBand* band = &pass.band;
+    const size_t bytes = pass.bytes = m_surfaceWorkspace->m_size; // (the workspace the pass's draws wrote)
+    int st = SurfacePassBuffers((size_t)W * H, gltf);
+    if (st == SAILOR_HIP_OK) st = RecordSurfaceResolveShade(bindings, pass, !gltf ? nullptr : t.lod ? sailor_hip_surface_resolve_lod : sailor_hip_surface_resolve_gltf);
     if (st != SAILOR_HIP_OK) return st;
     BeforeBufferWrite(color->m_buffer->m_hip.m_devicePtr);
     st = gltf ? sailor_hip_surface_composite_gltf(m_ctx, (const float*)m_surfaceRadiance->m_hip.m_devicePtr, (const float*)m_surfaceEmissive->m_hip.m_devicePtr,
-                                                  m_surfaceWorkspace->m_hip.m_devicePtr, bytes, (float*)color->m_buffer->m_hip.m_devicePtr, W, H, &band)
+                                                  m_surfaceWorkspace->m_hip.m_devicePtr, bytes, (float*)color->m_buffer->m_hip.m_devicePtr, W, H, band)
               : sailor_hip_surface_composite(m_ctx, (const float*)m_surfaceRadiance->m_hip.m_devicePtr, m_surfaceWorkspace->m_hip.m_devicePtr, bytes,
-                                             (float*)color->m_buffer->m_hip.m_devicePtr, W, H, &band);
+                                             (float*)color->m_buffer->m_hip.m_devicePtr, W, H, band);
     if (st != SAILOR_HIP_OK || !depthToStore) return st;
     // a pass that held a cutout draw writes its depth: the attachment gets the keys' depth (the opaque draws' depth is the prepass's already; a masked fragment
     // that survived writes its own, a discarded one none)
     if (!depthToStore->m_buffer || depthToStore->GetExtent().x != W || depthToStore->GetExtent().y != H || depthToStore->m_format != EFormat::R32_SFLOAT)
         return SAILOR_HIP_ERR_INVALID_ARGUMENT;
     BeforeBufferWrite(depthToStore->m_buffer->m_hip.m_devicePtr);
-    return sailor_hip_surface_store_depth(m_ctx, m_surfaceWorkspace->m_hip.m_devicePtr, bytes, (float*)depthToStore->m_buffer->m_hip.m_devicePtr, W, H, &band);
+    return sailor_hip_surface_store_depth(m_ctx, m_surfaceWorkspace->m_hip.m_devicePtr, bytes, (float*)depthToStore->m_buffer->m_hip.m_devicePtr, W, H, band);
 }
 
 // The Transparent queue's pass (include/sailor_hip.h, the Transparent section): SurfacePass.transparent(layers = the budget) of forward_plus.py, launch for launch,
@@ -1203,15 +1224,10 @@ int HipGraphicsDriver::RecordTransparentPass(const TVector<RHIShaderBindingSetPt
     uint64_t primBase = 0;
     for (const auto& src : draws) {
         if (((src.m_flags >> SAILOR_SURFACE_BLEND_SHIFT) & SAILOR_SURFACE_BLEND_MASK) == SAILOR_SURFACE_BLEND_MULTIPLY) return SAILOR_HIP_ERR_UNSUPPORTED;
-        if (!src.m_vertexBuffer || !src.m_indexBuffer || (size_t)src.m_firstIndex + src.m_indexCount > src.m_indexBuffer->m_size / 4 ||
-            ((size_t)src.m_firstInstance + src.m_instanceCount) * sizeof(SailorPerInstanceData) > instances->m_size ||
-            (size_t)src.m_vertexOffset * sizeof(SailorVertexP3N3T3B3UV2C4) > src.m_vertexBuffer->m_size || primBase > 0xFFFFFFFFull)
-            return SAILOR_HIP_ERR_INVALID_ARGUMENT;
         SailorSurfaceDraw d {};
-        d.dVertices = (const SailorVertexP3N3T3B3UV2C4*)src.m_vertexBuffer->m_hip.m_devicePtr + src.m_vertexOffset;
-        d.dIndices = (const uint32_t*)src.m_indexBuffer->m_hip.m_devicePtr + src.m_firstIndex;
-        d.numTriangles = src.m_indexCount / 3; d.numDrawn = src.m_instanceCount;
-        d.primBase = (uint32_t)primBase; d.flags = src.m_flags; d.firstInstance = src.m_firstInstance;
+        if (!surface_draw_desc(d, src.m_vertexBuffer, src.m_indexBuffer, instances, src.m_indexCount, src.m_instanceCount, src.m_firstIndex, src.m_vertexOffset,
+                               src.m_firstInstance, src.m_flags, primBase) || primBase > 0xFFFFFFFFull)
+            return SAILOR_HIP_ERR_INVALID_ARGUMENT;
         gltf = gltf || (src.m_flags & SAILOR_SURFACE_GLTF);
         uint64_t prims = 0;
         sailor_hip_surface_draw_prims(d.numTriangles, d.numDrawn, &prims);
@@ -1227,12 +1243,7 @@ int HipGraphicsDriver::RecordTransparentPass(const TVector<RHIShaderBindingSetPt
     if (!m_peelLast || m_peelLast->m_size != pixels * 4) m_peelLast = CreateBuffer(pixels * 4);
     if (buckets && (!m_transparentBuckets || m_transparentBuckets->m_size != bucketBytes)) m_transparentBuckets = CreateBuffer(bucketBytes);
     if (!m_peelCounts || m_peelCounts->m_size != (TRANSPARENT_MAX_LAYERS + 1) * 4) m_peelCounts = CreateBuffer((TRANSPARENT_MAX_LAYERS + 1) * 4);
-    if (!m_surfacePlanes || m_surfacePlanes->m_size != pixels * 48) m_surfacePlanes = CreateBuffer(pixels * 48);
-    if (!m_surfaceRadiance || m_surfaceRadiance->m_size != pixels * 16) m_surfaceRadiance = CreateBuffer(pixels * 16);
-    if (gltf && (!m_surfaceAo || m_surfaceAo->m_size != pixels * 4)) m_surfaceAo = CreateBuffer(pixels * 4);
-    if (gltf && (!m_surfaceEmissive || m_surfaceEmissive->m_size != pixels * 16)) m_surfaceEmissive = CreateBuffer(pixels * 16);
-    if (!m_peelLast || !m_peelCounts || !m_surfacePlanes || !m_surfaceRadiance || (gltf && (!m_surfaceAo || !m_surfaceEmissive)) || (buckets && !m_transparentBuckets))
-        return SAILOR_HIP_ERR_OUT_OF_MEMORY;
+    if (SurfacePassBuffers(pixels, gltf) != SAILOR_HIP_OK || !m_peelLast || !m_peelCounts || (buckets && !m_transparentBuckets)) return SAILOR_HIP_ERR_OUT_OF_MEMORY;
     void* workspace = m_surfaceWorkspace->m_hip.m_devicePtr;
     uint32_t* last = (uint32_t*)m_peelLast->m_hip.m_devicePtr;
     uint32_t* counts = (uint32_t*)m_peelCounts->m_hip.m_devicePtr;
@@ -1260,23 +1271,11 @@ int HipGraphicsDriver::RecordTransparentPass(const TVector<RHIShaderBindingSetPt
                 m_ctx, &pass.frame, &descs[i], dInstances, t.materials, t.numMaterials, t.textures, t.numTextures, (uint32_t)i, W, H, &pass.band, workspace, bytes, dDepth, last);
         return s != SAILOR_HIP_OK ? s : sailor_hip_surface_peel_commit(m_ctx, W, H, &pass.band, workspace, bytes, last, counts + k);
     };
-    auto own = RHIShaderBindingSetPtr::Make();
-    own->GetOrAddShaderBinding("surface")->m_buffer = m_surfacePlanes;
-    own->GetOrAddShaderBinding("radiance")->m_buffer = m_surfaceRadiance;
-    auto ao = bound_texture(bindings[1], "g_aoSampler");
-    const float* aoIn = (ao && ao->m_extent.x == W && ao->m_extent.y == H) ? (const float*)ao->m_buffer->m_hip.m_devicePtr : nullptr;
     for (uint32_t k = 0; k < layers; k++) {
         if ((st = peel(k)) != SAILOR_HIP_OK) return st;
-        // the layer is an ordinary surface workspace: the existing resolve (no depth output) and the existing shade
-        st = gltf ? sailor_hip_surface_resolve_gltf(m_ctx, &pass.frame, dInstances, t.materials, t.numMaterials, t.textures, t.numTextures, W, H, &pass.band, workspace, bytes,
-                                                    (float*)m_surfacePlanes->m_hip.m_devicePtr, pixels, nullptr, nullptr, aoIn, (float*)m_surfaceAo->m_hip.m_devicePtr,
-                                                    (float*)m_surfaceEmissive->m_hip.m_devicePtr)
-                  : sailor_hip_surface_resolve(m_ctx, &pass.frame, dInstances, t.materials, t.numMaterials, t.textures, t.numTextures, W, H, &pass.band, workspace, bytes,
-                                               (float*)m_surfacePlanes->m_hip.m_devicePtr, pixels, nullptr, nullptr);
-        if (st != SAILOR_HIP_OK) return st;
-        m_shadeAoOverride = gltf ? (const float*)m_surfaceAo->m_hip.m_devicePtr : nullptr;
-        st = RecordShade({ bindings[0], bindings[1], own });
-        m_shadeAoOverride = nullptr;
+        // the layer is an ordinary surface workspace: the existing resolve (no depth output) and the existing shade.  Never sailor_hip_surface_resolve_lod,
+        // also where the texture table has levels (RecordSurfaceEnd takes it then): the behaviour this pass had before the step was shared, not a decision
+        st = RecordSurfaceResolveShade(bindings, pass, gltf ? sailor_hip_surface_resolve_gltf : nullptr);
         if (st != SAILOR_HIP_OK) return st;
         BeforeBufferWrite(color->m_buffer->m_hip.m_devicePtr);
         st = sailor_hip_surface_blend(m_ctx, (const float*)m_surfaceRadiance->m_hip.m_devicePtr, (const float*)m_surfacePlanes->m_hip.m_devicePtr,
@@ -1600,15 +1599,12 @@ int HipGraphicsDriver::RecordSurfaceDrawIndirect(const TVector<RHIShaderBindingS
 {
     RHIBufferPtr instances = scene_buffer(bindings, "data");
     const bool buffersBound = vertices && indices && instances && command;
-    // (the instance range is the kernel's to check: it is handed the number of records)
-    const bool rangesOk = buffersBound && (size_t)host.firstIndex + host.indexCount <= indices->m_size / 4 && host.vertexOffset >= 0 &&
-                          (size_t)host.vertexOffset * sizeof(SailorVertexP3N3T3B3UV2C4) <= vertices->m_size && commandOffset % 4 == 0 &&
-                          commandOffset + sizeof(SailorDrawIndexedIndirectData) <= command->m_size;
-    return RecordSurfacePassDraw(bindings, color, depth, first, false, clearDepth, buffersBound, rangesOk, [&](const SurfacePass& pass, SailorSurfaceDraw& d) {
-        d.dVertices = (const SailorVertexP3N3T3B3UV2C4*)vertices->m_hip.m_devicePtr + host.vertexOffset;
-        d.dIndices = (const uint32_t*)indices->m_hip.m_devicePtr + host.firstIndex;
-        d.numTriangles = host.indexCount / 3; d.numDrawn = host.instanceCount; // the capacity: the un-culled count the host wrote
-        d.flags = flags;
+    // (no instance buffer to the descriptor's checks: the instance range is the kernel's to check, it is handed the number of records)
+    SailorSurfaceDraw desc {}; // (primBase: the pass's, set by RecordSurfacePassDraw)
+    const bool rangesOk = buffersBound && surface_draw_desc(desc, vertices, indices, RHIBufferPtr(), host.indexCount, host.instanceCount, host.firstIndex, host.vertexOffset, 0,
+                                                            flags, 0) &&
+                          commandOffset % 4 == 0 && commandOffset + sizeof(SailorDrawIndexedIndirectData) <= command->m_size;
+    return RecordSurfacePassDraw(bindings, color, depth, first, false, clearDepth, buffersBound, rangesOk, desc, [&](const SurfacePass& pass, const SailorSurfaceDraw& d) {
         const SurfaceTables t = surface_tables(bindings);
         if ((flags & SAILOR_SURFACE_ALPHA_CUTOUT) && !t.bound) return (int)SAILOR_HIP_ERR_INVALID_ARGUMENT;
         return (t.lod ? sailor_hip_surface_draw_indirect_lod : sailor_hip_surface_draw_indirect)(

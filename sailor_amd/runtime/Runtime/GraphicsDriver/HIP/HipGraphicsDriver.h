@@ -200,19 +200,27 @@ public:
 
 private:
     int RecordLightCulling(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const TVector<uint8_t>& pc);
-    int RecordShade(const TVector<RHI::RHIShaderBindingSetPtr>& bindings);
+    // aoOverride: the occlusion plane the ambient term reads instead of the bound g_aoSampler (behind a pass with glTF draws: RecordSurfaceResolveShade)
+    int RecordShade(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const float* aoOverride = nullptr);
     // The surface pass a recorded draw works in: the frame data of set 0, the attachments' extent, the whole-frame band and the workspace's size.
     struct SurfacePass { SailorUboFrameData frame; int W = 0, H = 0; SailorBand band {}; size_t bytes = 0; };
     // the band and the size of the surface workspace of a W x H pass; `create`: m_surfaceWorkspace is (re)created at that size
     int SurfaceWorkspace(int W, int H, bool create, SurfacePass& pass);
+    // the buffers a pass resolves and shades into: m_surfacePlanes, m_surfaceRadiance and, with glTF draws, m_surfaceAo and m_surfaceEmissive; out of memory if one fails
+    int SurfacePassBuffers(size_t pixels, bool gltf);
+    // The layer step of every pass, behind SurfacePassBuffers: resolves m_surfaceWorkspace into the planes and shades them into m_surfaceRadiance.  resolveGltf:
+    // nullptr = sailor_hip_surface_resolve; else the caller's choice of sailor_hip_surface_resolve_gltf or _lod, which also writes m_surfaceAo (from g_aoSampler,
+    // if bound at the frame's extent) and m_surfaceEmissive, and the shade then reads m_surfaceAo.
+    using SurfaceResolveGltf = decltype(&sailor_hip_surface_resolve_gltf);
+    int RecordSurfaceResolveShade(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const SurfacePass& pass, SurfaceResolveGltf resolveGltf);
     // Begins (first) or continues the pass for one recorded draw and records the draw.  Checks in this order: the bindings and the draw's own buffers
     // (buffersBound), the frame split, the attachments (needColor: a pass without a colour attachment is refused, else it is a depth-only pass of the depth
-    // attachment's extent), the draw's host-side ranges (rangesOk).  On `first` the workspace is created and the keys start from the depth attachment, or
-    // from cleared keys if clearDepth.  `issue(pass, d)` then completes the descriptor d (primBase is set) and calls the C entry; a draw it refuses
-    // un-begins the pass (RecordSurfaceEnd then has nothing to resolve), one it records advances the pass's primBase.
+    // attachment's extent), the draw's host-side ranges (rangesOk, from surface_draw_desc, which filled the descriptor d).  On `first` the workspace is
+    // created and the keys start from the depth attachment, or from cleared keys if clearDepth.  d.primBase is set to the pass's and `issue(pass, d)` calls
+    // the C entry; a draw it refuses un-begins the pass (RecordSurfaceEnd then has nothing to resolve), one it records advances the pass's primBase.
     template <typename Issue>
     int RecordSurfacePassDraw(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& color, const RHI::RHITexturePtr& depth, bool first,
-                              bool needColor, bool clearDepth, bool buffersBound, bool rangesOk, Issue&& issue);
+                              bool needColor, bool clearDepth, bool buffersBound, bool rangesOk, SailorSurfaceDraw& d, Issue&& issue);
     int RecordSurfaceDraw(const TVector<RHI::RHIShaderBindingSetPtr>& bindings, const RHI::RHITexturePtr& color, const RHI::RHITexturePtr& depth,
                           const RHI::RHIBufferPtr& vertices, const RHI::RHIBufferPtr& indices, bool first, uint32_t drawIndex, uint32_t indexCount,
                           uint32_t instanceCount, uint32_t firstIndex, uint32_t vertexOffset, uint32_t firstInstance, uint32_t flags);
@@ -296,9 +304,8 @@ private:
     // reads, the shade's radiance; the running primBase; begun = the first draw's sailor_hip_surface_begin went through
     RHI::RHIBufferPtr m_surfaceWorkspace, m_surfacePlanes, m_surfaceRadiance;
     // behind a pass that recorded a Standard_glTF.shader draw: the occlusion the shade reads (min(g_AO, the occlusion texel)) and the emissive term the
-    // composite adds; the override is set only around that pass's RecordShade
+    // composite adds
     RHI::RHIBufferPtr m_surfaceAo, m_surfaceEmissive;
-    const float* m_shadeAoOverride = nullptr;
     RHI::RHIBufferPtr m_uiWorkspace;
     uint64_t m_surfacePrimBase = 0;
     bool m_surfaceBegun = false;

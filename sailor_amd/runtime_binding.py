@@ -184,6 +184,10 @@ class Runtime:
         if not self.h:
             raise _lib.SailorHipError(st.value, "sailor_rt_create")
 
+    def call(self, name: str, *args):
+        """the checked call of the harness entry `name`, which takes this runtime first: a status other than 0 raises under the entry's name"""
+        _lib.check(getattr(self.rt, name)(self.h, *args), name)
+
     def close(self):
         if self.h:
             self.rt.sailor_rt_destroy(self.h)
@@ -430,12 +434,12 @@ class Runtime:
         nbytes = lambda t: t.numel() * t.element_size()
         b = np.ascontiguousarray(batches, np.uint32).reshape(-1, 5)
         ptr = lambda t: None if t is None else t.data_ptr()
-        _lib.check(self.rt.sailor_rt_set_scene(self.h, ptr(vertices), nbytes(vertices) // 72, ptr(indices), indices.numel(), ptr(instances),
-                                               0 if instances is None else nbytes(instances) // 96, ptr(materials), 0 if materials is None else nbytes(materials) // 80,
-                                               ptr(textures), num_textures, b.ctypes.data, len(b)), "sailor_rt_set_scene")
+        self.call("sailor_rt_set_scene", ptr(vertices), nbytes(vertices) // 72, ptr(indices), indices.numel(), ptr(instances),
+                  0 if instances is None else nbytes(instances) // 96, ptr(materials), 0 if materials is None else nbytes(materials) // 80, ptr(textures), num_textures,
+                  b.ctypes.data, len(b))
         if texture_levels is not None:
             levels = np.ascontiguousarray(texture_levels, np.uint32)
-            _lib.check(self.rt.sailor_rt_set_scene_texture_levels(self.h, levels.ctypes.data if len(levels) else None, len(levels)), "sailor_rt_set_scene_texture_levels")
+            self.call("sailor_rt_set_scene_texture_levels", levels.ctypes.data if len(levels) else None, len(levels))
 
     def generate_texture_mips(self, image, srgb: bool) -> np.ndarray:
         """IGraphicsDriver::CreateTexture with a full chain + GenerateMipMaps for one uint8 [H, W, 4] image -> the whole chain as uint32 texels, level after level"""
@@ -443,7 +447,7 @@ class Runtime:
         img = np.ascontiguousarray(image, np.uint8)
         h, w = img.shape[:2]
         out = np.zeros(host.mip_chain_texels(w, h, host.texture_mip_levels(w, h)), np.uint32)
-        _lib.check(self.rt.sailor_rt_generate_texture_mips(self.h, img.ctypes.data, w, h, 1 if srgb else 0, out.ctypes.data, out.size), "sailor_rt_generate_texture_mips")
+        self.call("sailor_rt_generate_texture_mips", img.ctypes.data, w, h, 1 if srgb else 0, out.ctypes.data, out.size)
         return out
 
     def set_scene_tags(self, tags, flags):
@@ -451,28 +455,28 @@ class Runtime:
         RenderScene node), flags = one int per batch, BATCH_ALPHA_CUTOUT | BATCH_DOUBLE_SIDED"""
         assert len(tags) == len(flags)
         f = np.ascontiguousarray(flags, np.uint32)
-        _lib.check(self.rt.sailor_rt_set_scene_tags(self.h, ",".join(tags).encode(), f.ctypes.data if len(f) else None, len(f)), "sailor_rt_set_scene_tags")
+        self.call("sailor_rt_set_scene_tags", ",".join(tags).encode(), f.ctypes.data if len(f) else None, len(f))
 
     def set_scene_shaders(self, shaders):
         """the shaders of set_scene's batches, after set_scene: one int per batch, SHADER_STANDARD (Standard.shader) or SHADER_STANDARD_GLTF (Standard_glTF.shader,
         what an imported model's material uses: its slots of the material table are that shader's records)"""
         s = np.ascontiguousarray(shaders, np.uint32)
-        _lib.check(self.rt.sailor_rt_set_scene_shaders(self.h, s.ctypes.data if len(s) else None, len(s)), "sailor_rt_set_scene_shaders")
+        self.call("sailor_rt_set_scene_shaders", s.ctypes.data if len(s) else None, len(s))
 
     def set_scene_blend(self, blend_modes, z_write):
         """the blend mode and the z-write of set_scene's batches' materials, after set_scene: one EBlendMode per batch (0 None, 1 Additive, 2 AlphaBlending,
         3 Multiply) and one 0 / 1.  A RenderScene pass whose batches all have z-write off is the Transparent queue's: peeled by primitive order and blended"""
         b, z = np.ascontiguousarray(blend_modes, np.uint32), np.ascontiguousarray(z_write, np.uint32)
         assert len(b) == len(z)
-        _lib.check(self.rt.sailor_rt_set_scene_blend(self.h, b.ctypes.data if len(b) else None, z.ctypes.data if len(z) else None, len(b)), "sailor_rt_set_scene_blend")
+        self.call("sailor_rt_set_scene_blend", b.ctypes.data if len(b) else None, z.ctypes.data if len(z) else None, len(b))
 
     def set_transparent_layers(self, layers: int):
         """the layer budget of a transparent pass (default 4)"""
-        _lib.check(self.rt.sailor_rt_set_transparent_layers(self.h, layers), "sailor_rt_set_transparent_layers")
+        self.call("sailor_rt_set_transparent_layers", layers)
 
     def set_transparent_mode(self, mode: int):
         """the route of a transparent pass: 0 = the peel (default), 1 = per-pixel fragment buckets (one rasterisation a pass, (budget + 1) x 8 bytes a pixel)"""
-        _lib.check(self.rt.sailor_rt_set_transparent_mode(self.h, mode), "sailor_rt_set_transparent_mode")
+        self.call("sailor_rt_set_transparent_mode", mode)
 
     def transparent_overflow(self) -> int:
         """the pixels that still had a fragment behind the budget's layers in the last frame's transparent pass.  SYNCHRONISES with the stream: read it after the
@@ -484,8 +488,7 @@ class Runtime:
 
     def set_scene_targets(self, color, depth=None):
         """RenderScene's colour attachment (float32 [H, W, 4]) and the prepass's raw depth (float32 [H, W]) or None"""
-        _lib.check(self.rt.sailor_rt_set_scene_targets(self.h, color.data_ptr(), None if depth is None else depth.data_ptr(), color.shape[1], color.shape[0]),
-                   "sailor_rt_set_scene_targets")
+        self.call("sailor_rt_set_scene_targets", color.data_ptr(), None if depth is None else depth.data_ptr(), color.shape[1], color.shape[0])
 
     def set_shadow_maps(self, map_tensors, formats, lights_matrices):
         ptrs = (C.c_void_p * 4)(*[t.data_ptr() for t in map_tensors])
@@ -500,7 +503,7 @@ class Runtime:
         (every instance casts), resolutions = the four cascade maps' sizes or None (the reference's 4096), trace = "flat" | "octree" | None (as the runtime's
         sweep system traces).  From then on process_frame() plans the cascades first and a ShadowPrepass node draws them.  world_aabb None takes it away."""
         if world_aabb is None:
-            _lib.check(self.rt.sailor_rt_set_caster_data(self.h, None, 0, None, None, None, 0, 0), "sailor_rt_set_caster_data")
+            self.call("sailor_rt_set_caster_data", None, 0, None, None, None, 0, 0)
             return
         n = world_aabb.shape[0]
         assert world_aabb.is_contiguous() and world_aabb.numel() * world_aabb.element_size() == 24 * n, tuple(world_aabb.shape)
@@ -510,13 +513,13 @@ class Runtime:
         assert cast is None or len(cast) == (n + 63) // 64
         res = None if resolutions is None else (C.c_int * 4)(*[int(r) for r in resolutions])
         mode = 0xFFFFFFFF if trace is None else _lib.trace_mode(trace)
-        _lib.check(self.rt.sailor_rt_set_caster_data(self.h, world_aabb.data_ptr(), n, None if cast is None else cast.ctypes.data, frames.ctypes.data, res, mode,
-                                                     0 if octree_root_size is None else octree_root_size), "sailor_rt_set_caster_data")
+        self.call("sailor_rt_set_caster_data", world_aabb.data_ptr(), n, None if cast is None else cast.ctypes.data, frames.ctypes.data, res, mode,
+                  0 if octree_root_size is None else octree_root_size)
 
     def set_light_rotation(self, index: int, rotation):
         """the owner's rotation (x, y, z, w) of light `index`: with its position the transform whose inverse is the light's view matrix"""
         q = np.ascontiguousarray(rotation, np.float32).reshape(4)
-        _lib.check(self.rt.sailor_rt_set_light_rotation(self.h, index, q.ctypes.data), "sailor_rt_set_light_rotation")
+        self.call("sailor_rt_set_light_rotation", index, q.ctypes.data)
 
     def shadow_passes(self, num_instances: int = 0):
         """sceneView.m_shadowMapsToUpdate of the last process_frame(): one dict per pass -- cascade (m_lighMatrixIndex), shadow_type, casters, dependencies
@@ -542,11 +545,11 @@ class Runtime:
 
     def set_frame_split(self, rank: int, world_size: int, comm=None):
         """this runtime renders tile-row band `rank` of `world_size`; per-pixel targets set afterwards hold the band's rows"""
-        _lib.check(self.rt.sailor_rt_set_frame_split(self.h, rank, world_size, C.c_void_p(comm) if comm else None), "sailor_rt_set_frame_split")
+        self.call("sailor_rt_set_frame_split", rank, world_size, C.c_void_p(comm) if comm else None)
 
     def exchange_light_lists(self, global_grid, global_culled):
-        _lib.check(self.rt.sailor_rt_exchange_light_lists(self.h, global_grid.data_ptr(), global_grid.numel() * global_grid.element_size(),
-                                                          global_culled.data_ptr(), global_culled.numel() * global_culled.element_size()), "sailor_rt_exchange_light_lists")
+        self.call("sailor_rt_exchange_light_lists", global_grid.data_ptr(), global_grid.numel() * global_grid.element_size(), global_culled.data_ptr(),
+                  global_culled.numel() * global_culled.element_size())
 
     # ---- the world's DebugContext (RHI/DebugContext.cpp): what the DebugDraw node draws; `duration` is the line's lifetime in seconds of debug_tick ----
     @staticmethod
